@@ -8,7 +8,10 @@ the workload is BASELINE.json configs[1] (paired-end short reads vs a GENCODE-sh
 annotation, 1 x MI355X); N>1 shards read-name groups across ranks (one process per GPU, a
 private index replica each, no collective on the data path) -- weak scaling.
 
-  python bench.py --gpus N --steps K --warmup W [--pairs P]
+  python bench.py --gpus N --steps K --warmup W [--pairs P] [--dump-outputs DIR]
+
+--dump-outputs DIR: rank 0 writes the rows its last timed step returned as DIR/<name>.npy (float64, a seeded sample
+of at most 64 MB; see dump_outputs), so that two builds can be compared output for output on the same inputs.
 
 Rank 0 prints ONE JSON line (contract in the task statement):
   value / ms_per_step   device-resident: the batch is already in HBM when the timed region starts and the packed
@@ -65,7 +68,10 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=400_000, help="alignments in the CPU-baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's rows (rank 0) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # One command, N ranks: like the reference's one reader feeding N workers from a single process
@@ -171,6 +177,8 @@ def main():
     elapsed = time.perf_counter() - t_start
     kernel_ms = {k: [ms, ln] for k, (ms, ln) in ctx.kernel_ms_sum().items()}   # every launch of the timed region, summed by the context
     ctx.set_profiling(False)
+    if args.dump_outputs and rank == 0:   # before any other projection call: the rows live in the context until then
+        dump_outputs(args.dump_outputs, brdev.packed_as_tensors(rows, n_aln, device=dev), rows, n_aln)
     per_rank_ms = [1e3 * e / args.steps for e in gather_all(elapsed)]
     per_rank_aln = gather_all(n_aln)
     elapsed, total_aln = reduce_max_sum(elapsed, n_aln)
@@ -341,6 +349,69 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 19        # rows and alignments kept by dump_outputs: about 40 MB of float64 at the default size
+DUMP_SEED = 0x5A3D1E
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, t, rows, n_aln):
+    """What the timed path returned to its caller (br_device_rows; t = bramble_amd.device.packed_as_tensors of it) as
+    float64 arrays in out_dir/<name>.npy.  Rows and alignments are a fixed seeded sample (all of them when there are no
+    more than DUMP_SAMPLE), and each sampled row's CIGAR is resolved to its ops, so that nothing depends on where the
+    context's pool keeps the longer ones:
+      counts                 n_aln, n_rows, n_matches, total_complete, total_unique, dropped_reads, total_processed
+      row_index              the sampled rows, ascending
+      rows_a                 [rows, 4]: transcript_id, pos, meta (BR_ROW_* bits | op count), nh
+      cigar_off, cigar_ops   the rewritten CIGAR of sampled row k is cigar_ops[cigar_off[k]:cigar_off[k + 1]] (BAM-packed)
+      similarity_score, clip_score   of the sampled rows, when the preset returns them
+      aln_index, row_off     row_off[] at the sampled alignments (indices 0 .. n_aln)"""
+    import numpy as np
+    import torch
+
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(n):
+        return np.arange(n, dtype=np.int64) if n <= DUMP_SAMPLE else np.unique(rng.integers(0, n, DUMP_SAMPLE))
+
+    def gather(x, idx):
+        return x.index_select(0, torch.from_numpy(idx).to(x.device)).cpu().numpy()
+
+    n_rows = int(rows.n_rows)
+    ri = sample(n_rows)
+    out = {"counts": np.array([n_aln, n_rows, int(rows.n_matches), int(rows.total_complete), int(rows.total_unique),
+                               int(rows.dropped_reads), int(rows.total_processed)]), "row_index": ri}
+    a = gather(t["a"], ri).view(np.uint32) if n_rows else np.zeros((0, 4), np.uint32)
+    cig = gather(t["cigar"], ri).view(np.uint64) if n_rows else np.zeros(0, np.uint64)
+    ncig = (a[:, 2] & 0xffffff).astype(np.int64)
+    off = np.zeros(ri.size + 1, dtype=np.int64)
+    np.cumsum(ncig, out=off[1:])
+    ops = np.zeros(int(off[-1]), dtype=np.uint32)
+    one, two, pooled = np.nonzero((ncig == 1) | (ncig == 2))[0], np.nonzero(ncig == 2)[0], np.nonzero(ncig > 2)[0]
+    ops[off[one]] = (cig[one] & np.uint64(0xffffffff)).astype(np.uint32)   # <= 2 ops: inline, op 0 in the low word
+    ops[off[two] + 1] = (cig[two] >> np.uint64(32)).astype(np.uint32)
+    if pooled.size:                                                          # else: offset of the ops in the pool
+        cnt = ncig[pooled]
+        which = np.repeat(np.arange(pooled.size), cnt)
+        within = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        src = cig[pooled].astype(np.int64)[which] + within
+        if src.max() >= int(rows.n_pool_words):
+            raise RuntimeError("dump_outputs: a CIGAR reference points past the pool (%d words)" % int(rows.n_pool_words))
+        ops[off[pooled][which] + within] = gather(t["pool"], src).view(np.uint32)
+    out.update(rows_a=a, cigar_off=off, cigar_ops=ops)
+    if "similarity_score" in t:
+        out["similarity_score"] = gather(t["similarity_score"], ri)
+        out["clip_score"] = gather(t["clip_score"], ri)
+    ai = sample(n_aln + 1)
+    out.update(aln_index=ai, row_off=gather(t["row_off"], ai).view(np.uint64))
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in out.items()}   # every value above is below 2**53
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError("dump_outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def spawn_ranks(n):

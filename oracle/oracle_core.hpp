@@ -18,7 +18,7 @@
 //     recurrence follows the in-tree patch file
 //     subprojects/packagefiles/ksw2/ksw2_extz2_sse.cpp, but ksw2.h (pinned at
 //     lh3/ksw2@289609b in subprojects/ksw2.wrap) is absent from
-//     /root/reference; ksw_reset_extz / ksw_apply_zdrop / ksw_backtrack /
+//     the reference tree; ksw_reset_extz / ksw_apply_zdrop / ksw_backtrack /
 //     ksw_push_cigar are restated from the published upstream header.
 //   * cgranges IITree (pinned at lh3/cgranges@b3d5e2c in
 //     subprojects/cgranges.wrap) is absent too; its published contract
@@ -26,7 +26,7 @@
 //     start-sorted array) is restated in IntervalIndex below.
 //
 // Every function cites the reference file:line it follows (paths relative to
-// /root/reference).
+// the reference tree's root).
 // ============================================================================
 #pragma once
 

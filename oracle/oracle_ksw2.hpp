@@ -2,7 +2,7 @@
 // TEST INFRASTRUCTURE ONLY -- scalar restatement of ksw_extz2_sse as bramble
 // calls it (see oracle_core.hpp header for the oracle's role and pinning).
 //
-// Follows subprojects/packagefiles/ksw2/ksw2_extz2_sse.cpp (in /root/reference)
+// Follows subprojects/packagefiles/ksw2/ksw2_extz2_sse.cpp (in the reference tree)
 // for the DP; ksw2.h helpers (absent from the reference tree; lh3/ksw2@289609b per
 // subprojects/ksw2.wrap) are restated from the published upstream header.  No
 // reference test exercises this path, so there is no reference-held vector for it.

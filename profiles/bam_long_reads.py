@@ -1,5 +1,5 @@
 import sys, time, os
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from bramble_amd import lib, synth, device as brdev
 mode, flags = sys.argv[1], ({"lr_hq": 1} if sys.argv[1] == "hifi" else {"lr": 1})
