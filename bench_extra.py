@@ -6,6 +6,8 @@
   python bench_extra.py bam [--reads N]  re-encode the rows of configs[1] as BAM records (device part)
   python bench_extra.py bundle [--reads N]  raw BAM records resident in HBM -> projected BAM records (br_project_bam_device)
   python bench_extra.py cli [--reads N] [--threads T]  the command line file to file (BGZF inflate, device path, BGZF deflate)
+  python bench_extra.py sam [--reads N]  SAM text input: device parse time per chunk (hipEvents), text GB/s and records/s of
+                                         br_sam_reader, and the command line file to file for the workload of `cli` as SAM and as BAM
   python bench_extra.py small            small calls: us per device-resident step at 1 .. 52 000 pairs (without the per-kernel
                                          events bench.py keeps on), the path without host round trips against the ordinary one,
                                          and br_project_group / br_project_groups host to host from plain C (profiles/group_latency.c)
@@ -23,7 +25,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
@@ -188,6 +190,58 @@ def main():
         print(json.dumps({"config": "inflate", "workload": "%d BAM records, %d bytes in %d BGZF blocks of %d compressed bytes (host writer, level 6)" % (len(rlen), total, len(blocks), raw.size),
                           "device_ms": el * 1e3, "device_GBps_out": total / el / 1e9, "device_GBps_in": raw.size / el / 1e9, "block_scan_host_s": round(scan_s, 3),
                           "host_whole_file_s (br_bgzf_read_file, includes its buffer growth)": host, "kernel_ms": {k: round(v[0], 3) for k, v in ctx.kernel_ms().items() if v[0]}}))
+        return
+    if args.config == "sam":
+        import subprocess
+        import tempfile
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from tests import bamio
+        n = args.reads or 2_000_000
+        ann = synth.Annotation("G")
+        annd = ann.as_dict()
+        batch = ann.reads(n, "pe", with_records=1)
+        stream_h, roff, rlen = synth.Annotation.frame_records(batch)
+        refs = [(r, 250_000_000) for r in annd["refnames"]]
+        header = "@HD\tVN:1.6\tSO:unsorted\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs)
+        text = synth.records_to_sam(stream_h, annd["refnames"])
+        tmp = os.environ.get("CLI_TMP") or tempfile.mkdtemp(prefix="bramble_sam_")
+        os.makedirs(tmp, exist_ok=True)
+        gtf, in_sam, in_bam = os.path.join(tmp, "guides.gtf"), os.path.join(tmp, "in.sam"), os.path.join(tmp, "in.bam")
+        bamio.write_gtf(gtf, annd)
+        with open(in_sam, "wb") as f:
+            f.write(header.encode())
+            f.write(text)
+        bamio.write_bam(in_bam, header, refs, stream_h.tobytes(), level=1)
+        # device parse: the text in chunks of the command line's size (1 M records' worth), warmup first
+        chunk = int(len(text) / max(len(rlen), 1) * 1_000_000)
+        r = lib.SamReader(header)
+        for _ in range(args.warmup):
+            r.next(text[:text.rfind(b"\n", 0, chunk) + 1], True, fetch=False)
+        s0 = r.stats()
+        n_rec = 0
+        for _ in range(args.steps):
+            pos = 0
+            while pos < len(text):
+                got = r.next(text[pos:pos + chunk], pos + chunk >= len(text), fetch=False)
+                pos += got["consumed"]
+                n_rec += got["n"] + got["n_unmapped"]
+        s1 = r.stats()
+        r.close()
+        parse_s, up_s, nch, nb = s1["parse_s"] - s0["parse_s"], s1["upload_s"] - s0["upload_s"], s1["chunks"] - s0["chunks"], s1["bytes"] - s0["bytes"]
+        exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bramble_amd", "bin", "bramble")
+        walls = {}
+        for label, path in (("bam", in_bam), ("sam", in_sam), ("bam'", in_bam), ("sam'", in_sam)):   # alternated, twice
+            out = os.path.join(tmp, "out_%s.bam" % label.strip("'"))
+            t0 = time.perf_counter()
+            p = subprocess.run([exe, path, "-G", gtf, "-o", out, "-p", str(args.threads)], capture_output=True, text=True)
+            if p.returncode != 0:
+                print(p.stderr, file=sys.stderr)
+                sys.exit(1)
+            walls[label] = round(time.perf_counter() - t0, 3)
+        print(json.dumps({"config": "sam", "workload": "%d paired-end alignments as SAM text (%.2f GB), %d chunks of ~%.0f MB" % (len(rlen), len(text) / 1e9, nch / max(args.steps, 1), chunk / 1e6),
+                          "device_parse_ms_per_chunk": round(1e3 * parse_s / max(nch, 1), 2), "text_GBps_parse": round(nb / parse_s / 1e9, 1),
+                          "records_per_s_parse": round(n_rec / parse_s), "text_GBps_upload": round(nb / up_s / 1e9, 1),
+                          "cli_wall_s": walls, "sam_bytes": len(text), "bam_bytes": os.path.getsize(in_bam)}))
         return
     if args.config == "cli":
         pass

@@ -73,8 +73,8 @@ static const uint8_t EOF_BLOCK[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 
 
 BgzfReader::~BgzfReader() { if (map_) munmap((void *)map_, map_size_); if (f_ && f_ != stdin) fclose(f_); }
 
-bool BgzfReader::open(const char *path, int threads) {
-  f_ = strcmp(path, "-") == 0 ? stdin : fopen(path, "rb");   // "-": standard input, like htslib
+bool BgzfReader::open(const char *path, int threads, const std::string &prefix, int fd) {
+  f_ = fd == 0 ? stdin : fd > 0 ? fdopen(fd, "rb") : strcmp(path, "-") == 0 ? stdin : fopen(path, "rb");   // "-": standard input, like htslib
   threads_ = threads < 1 ? 1 : threads;
   if (!f_) { err_ = std::string("cannot open ") + path; return false; }
   // regular files are mapped: the inflate workers read the page cache directly (no fread copy on the reader thread)
@@ -83,6 +83,7 @@ bool BgzfReader::open(const char *path, int threads) {
     void *m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fileno(f_), 0);
     if (m != MAP_FAILED) { map_ = (const uint8_t *)m; map_size_ = (size_t)sb.st_size; madvise(m, map_size_, MADV_SEQUENTIAL); }
   }
+  if (!map_ && !prefix.empty()) { cbuf_.resize(prefix.size()); memcpy(cbuf_.data(), prefix.data(), prefix.size()); }
   if (!fill(18) || have() < 18 || cur()[0] != 0x1f || cur()[1] != 0x8b || !(cur()[3] & 4)) {
     err_ = std::string(path) + " is not a BGZF (BAM) file";
     return false;

@@ -59,8 +59,10 @@ class ByteBuf {
 class BgzfReader {
  public:
   ~BgzfReader();
-  // returns false (and sets error()) when the file cannot be opened or is not BGZF
-  bool open(const char *path, int threads);
+  // returns false (and sets error()) when the file cannot be opened or is not BGZF.  fd >= 0: a stream already open (standard
+  // input, a pipe or FIFO given by its path) instead of opening path; prefix: the bytes already read from it to find out what
+  // it holds -- they come first
+  bool open(const char *path, int threads, const std::string &prefix = std::string(), int fd = -1);
   // appends at least `want` uncompressed bytes to `out` unless the stream ends first;
   // returns the number of bytes appended, 0 at end of stream, -1 on a corrupt block
   int64_t read(ByteBuf &out, size_t want);

@@ -8,10 +8,17 @@
 //   uploader      : br_bam_bundle_stage (records to one of three device slots, own copy stream)
 //   main thread   : br_project_bam_staged (everything between the raw records on the device)
 //   writer thread : BGZF deflate (threaded) -> output file
+//
+// SAM text input (told apart from BGZF by its first bytes, as htslib's hts_open does): a feeder thread cuts the text (the
+// mapped file, or what a pipe delivers) into chunks of about --bundle-size records at read-name changes and deals them to one
+// br_sam_reader per device, which makes the BAM records on the device; the projection and the writer are the BAM path's.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <errno.h>
+#include <fcntl.h>
 #include <sys/mman.h>
+#include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
 #include <zlib.h>
@@ -31,6 +38,7 @@
 
 #include "../../../include/bramble_amd.h"
 #include "bgzf.h"
+#include "../sam_header.h"
 
 #define BRAMBLE_REF_VERSION "0.1.6"  // src/bramble.cpp:35
 
@@ -53,7 +61,7 @@ struct Options {
 void usage(FILE *f) {
   fprintf(f,
           "bramble (MI355X) usage:\n\n"
-          "bramble <in.bam> -G <annotation.gtf> -o <out.bam> [-p <cpus>] [-S <genome.fa>]\n"
+          "bramble <in.bam|in.sam|-> -G <annotation.gtf> -o <out.bam> [-p <cpus>] [-S <genome.fa>]\n"
           " [--help] [--version] [--quiet] [--fr] [--rf] [--lr] [--lr-hq] [--strict]\n"
           " [--max-soft-clip N] [--max-junction-insertion N] [--max-junction-deletion N]\n"
           " [--max-error-exon N] [--similarity-threshold X]\n"
@@ -63,7 +71,10 @@ void usage(FILE *f) {
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
           "--devices 0,1,...: bundles are dealt to one worker per listed GPU (an index replica each, no exchange between them);\n"
-          "the output keeps the input order.\n");
+          "the output keeps the input order.\n"
+          "The input is BAM or SAM text (a file, or standard input as -), told apart by its bytes; SAM lines become BAM\n"
+          "records on the GPU.  --device-reader / --host-reader choose how BAM is read and do not apply to SAM.\n"
+          "BGZF-compressed SAM and plain gzip input are not supported.\n");
 }
 
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
@@ -114,7 +125,7 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (o.in_bam.empty()) o.in_bam = a;
     else { fprintf(stderr, "unexpected argument %s\n", a.c_str()); return -1; }
   }
-  if (o.in_bam.empty()) { fprintf(stderr, "in.bam is required\n"); return -1; }
+  if (o.in_bam.empty()) { fprintf(stderr, "an input (in.bam, in.sam or -) is required\n"); return -1; }
   if (o.out_bam.empty()) { fprintf(stderr, "--out is required\n"); return -1; }
   if (o.gff.empty()) { fprintf(stderr, "--guide is required\n"); return -1; }
   if (!o.fasta.empty()) o.cfg.use_fasta = 1;
@@ -154,7 +165,7 @@ bool read_header(BgzfReader &rd, brio::ByteBuf &buf, size_t &pos, BamHeader &h, 
   };
   auto u32 = [&](size_t at) { uint32_t v; memcpy(&v, buf.data() + at, 4); return v; };
   if (!need(12)) return false;
-  if (memcmp(buf.data() + pos, "BAM\1", 4) != 0) { err = "not a BAM file (bad magic)"; return false; }
+  if (memcmp(buf.data() + pos, "BAM\1", 4) != 0) { err = "not a BAM file (bad magic): BGZF-compressed SAM (bgzipped SAM) is not supported, decompress it first"; return false; }
   uint32_t l_text = u32(pos + 4);
   if (!need(12 + (size_t)l_text)) return false;
   h.text.assign((const char *)buf.data() + pos + 8, l_text);
@@ -228,6 +239,133 @@ std::vector<uint8_t> make_bam_header(const std::string &text, const br_index *ix
   return o;
 }
 
+// ---- SAM input ----------------------------------------------------------------------------------
+// What the input holds, from its first bytes: 0 BGZF (BAM), 1 SAM text, -1 error.  A regular file is looked at with pread and
+// reopened by its path (the readers map it); anything else -- standard input ("-"), a pipe or FIFO given by its path -- is read
+// once: *stream_fd is the open descriptor the reader goes on with, and the bytes read to find out are kept in `peek` for it.
+int sniff_input(const std::string &path, int *stream_fd, std::string &peek, std::string &err) {
+  uint8_t h[18];
+  size_t got = 0;
+  *stream_fd = -1;
+  int fd = 0;
+  if (path != "-") {
+    fd = ::open(path.c_str(), O_RDONLY);
+    if (fd < 0) { err = "cannot open " + path; return -1; }
+    struct stat sb;
+    if (fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode)) {
+      const ssize_t k = pread(fd, h, sizeof h, 0);
+      close(fd);
+      if (k < 0) { err = "cannot read " + path; return -1; }
+      got = (size_t)k;
+      fd = -1;
+    }
+  }
+  if (fd >= 0) {
+    *stream_fd = fd;
+    while (got < sizeof h) {
+      const ssize_t k = read(fd, h + got, sizeof h - got);
+      if (k < 0 && errno == EINTR) continue;
+      if (k < 0) { err = "cannot read the input"; return -1; }
+      if (k == 0) break;
+      got += (size_t)k;
+    }
+    peek.assign((const char *)h, got);
+  }
+  if (got == 0) { err = "empty input"; return -1; }
+  if (got >= 2 && h[0] == 0x1f && h[1] == 0x8b) {
+    if (got >= 14 && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C') return 0;
+    err = "gzip-compressed input is not supported (plain SAM, or BAM)";
+    return -1;
+  }
+  return 1;
+}
+
+// the SAM text: the mapped file, or a pipe read as it comes
+struct SamInput {
+  const uint8_t *map = nullptr; size_t map_size = 0;
+  int fd = -1; bool own_fd = false, eof = false, read_failed = false;
+  brio::ByteBuf pbuf;            // pipe: bytes read, not yet handed out
+  uint64_t header_bytes = 0, header_lines = 0;
+  ~SamInput() { if (map) munmap((void *)map, map_size); if (own_fd && fd >= 0) close(fd); }
+  size_t read_more(size_t want) {   // appends up to `want` bytes of the pipe; 0 at its end
+    size_t got = 0;
+    while (got < want && !eof) {
+      const size_t old = pbuf.size();
+      pbuf.resize(old + (want - got));
+      ssize_t k = read(fd, pbuf.data() + old, want - got);
+      pbuf.resize(old + (k > 0 ? (size_t)k : 0));
+      if (k < 0 && errno == EINTR) continue;
+      if (k < 0) read_failed = true;   // (a read error is not the end of the input: the run fails)
+      if (k <= 0) { eof = true; break; }
+      got += (size_t)k;
+    }
+    return got;
+  }
+  // stream_fd >= 0: a stream sniff_input has begun to read (peek = its first bytes); else the regular file at path
+  bool open(const std::string &path, int stream_fd, const std::string &peek, BamHeader &h, std::string &err) {
+    if (stream_fd >= 0) { fd = stream_fd; own_fd = fd != 0; }
+    else { fd = ::open(path.c_str(), O_RDONLY); own_fd = true; if (fd < 0) { err = "cannot open " + path; return false; } }
+    struct stat sb;
+    if (stream_fd < 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) {
+      void *m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (m != MAP_FAILED) { map = (const uint8_t *)m; map_size = (size_t)sb.st_size; madvise(m, map_size, MADV_SEQUENTIAL); }
+    }
+    const uint8_t *d; uint64_t n;
+    if (map) { d = map; n = map_size; (void)br_sam_header_scan(d, n, &header_bytes); }
+    else {
+      pbuf.resize(peek.size()); memcpy(pbuf.data(), peek.data(), peek.size());
+      for (;;) {   // until a line that is not a header line has begun, or the stream ends
+        (void)br_sam_header_scan(pbuf.data(), pbuf.size(), &header_bytes);
+        if (header_bytes < pbuf.size() || eof) break;
+        read_more(1u << 20);
+      }
+      if (read_failed) { err = "read error"; return false; }
+      d = pbuf.data(); n = pbuf.size();
+    }
+    h.text.assign((const char *)d, (size_t)header_bytes);
+    for (uint64_t i = 0; i < header_bytes; i++) header_lines += d[i] == '\n';
+    if (!br::sam_header_refs(h.text.data(), h.text.size(), h.ref_names, h.ref_lens)) { err = "@SQ line without SN:"; return false; }
+    if (!map) pbuf.erase_front((size_t)header_bytes);
+    return true;
+  }
+};
+
+// the read name of the line at p (up to its first tab)
+inline std::pair<const uint8_t *, size_t> line_name(const uint8_t *p, const uint8_t *end) {
+  const uint8_t *t = (const uint8_t *)memchr(p, '\t', (size_t)(end - p));
+  const uint8_t *nl = (const uint8_t *)memchr(p, '\n', (size_t)(end - p));
+  const uint8_t *e = t && (!nl || t < nl) ? t : nl ? nl : end;
+  return {p, (size_t)(e - p)};
+}
+// Where the chunk that starts at `start` ends: at a read-name change near `target`.  Backwards from the last complete line in
+// front of target to the first line of its name group; when that group began at `start` (one group longer than the target),
+// forwards to the next name change.  nullptr: the text in [start, end) does not reach that change yet (at_eof: the end does).
+const uint8_t *sam_cut(const uint8_t *start, const uint8_t *target, const uint8_t *end, bool at_eof) {
+  auto same = [&](const uint8_t *a, const uint8_t *b) { auto x = line_name(a, end), y = line_name(b, end); return x.second == y.second && memcmp(x.first, y.first, x.second) == 0; };
+  const uint8_t *nl = target > start ? (const uint8_t *)memrchr(start, '\n', (size_t)(target - start)) : nullptr;
+  if (nl) {
+    const uint8_t *pn = nl > start ? (const uint8_t *)memrchr(start, '\n', (size_t)(nl - start)) : nullptr;
+    const uint8_t *L = pn ? pn + 1 : start;
+    while (L > start) {
+      const uint8_t *q = L - 1 > start ? (const uint8_t *)memrchr(start, '\n', (size_t)(L - 1 - start)) : nullptr;
+      const uint8_t *P = q ? q + 1 : start;
+      if (!same(P, L)) break;
+      L = P;
+    }
+    if (L > start) return L;
+  }
+  for (const uint8_t *q = start;;) {   // forwards: the first line whose name differs from the first line's
+    const uint8_t *e = (const uint8_t *)memchr(q, '\n', (size_t)(end - q));
+    if (!e) return at_eof ? end : nullptr;
+    q = e + 1;
+    if (q >= end) return at_eof ? end : nullptr;
+    if (!memchr(q, '\n', (size_t)(end - q)) && !at_eof) return nullptr;   // (a name is only known once its line is complete)
+    if (!same(start, q)) return q;
+  }
+}
+
+struct SamChunk { const uint8_t *data = nullptr; uint64_t n = 0; brio::ByteBuf own; int64_t line0 = -1; uint64_t seq = 0; };
+
 // ---- bounded single-slot hand-off between pipeline stages ---------------------------------------
 template <typename T>
 struct Slot {  // bounded FIFO between two pipeline stages
@@ -276,11 +414,22 @@ extern "C" int br_cli_main(int argc, char **argv) {
   std::vector<std::thread> warm;
   for (int d : o.devices) warm.emplace_back([d]() { (void)br_device_warmup(d); });
   struct WarmJoin { std::vector<std::thread> &t; ~WarmJoin() { for (auto &x : t) if (x.joinable()) x.join(); } } warm_join{warm};
+  // BAM or SAM: decided by the bytes, not the name (htslib's hts_open does the same for the reference)
+  std::string peek, err;
+  int stream_fd = -1;
+  const int in_kind = sniff_input(o.in_bam, &stream_fd, peek, err);
+  if (in_kind < 0) { if (stream_fd > 0) close(stream_fd); fprintf(stderr, "error: %s: %s\n", o.in_bam.c_str(), err.c_str()); return 1; }
+  const bool is_sam = in_kind == 1;
   BgzfReader rd;
-  if (!rd.open(o.in_bam.c_str(), o.threads)) { fprintf(stderr, "error: %s\n", rd.error().c_str()); return 1; }
   brio::ByteBuf buf; size_t pos = 0;
-  BamHeader hdr; std::string err;
-  if (!read_header(rd, buf, pos, hdr, err)) { fprintf(stderr, "error: %s: %s\n", o.in_bam.c_str(), err.c_str()); return 1; }
+  BamHeader hdr;
+  SamInput sam;
+  if (is_sam) {
+    if (!sam.open(o.in_bam, stream_fd, peek, hdr, err)) { fprintf(stderr, "error: %s: %s\n", o.in_bam.c_str(), err.c_str()); return 1; }
+  } else {
+    if (!rd.open(o.in_bam.c_str(), o.threads, peek, stream_fd)) { fprintf(stderr, "error: %s\n", rd.error().c_str()); return 1; }
+    if (!read_header(rd, buf, pos, hdr, err)) { fprintf(stderr, "error: %s: %s\n", o.in_bam.c_str(), err.c_str()); return 1; }
+  }
   Slot<Bundle> to_gpu(16);     // the reader runs ahead while the guides are parsed and the indexes are built (sixteen bundles: about 3 GB of records)
   // consumed bundle buffers go back to the reader: their pages are already faulted in
   std::mutex pool_m; std::vector<std::unique_ptr<brio::ByteBuf>> pool;
@@ -304,10 +453,20 @@ extern "C" int br_cli_main(int argc, char **argv) {
   struct DevBundle { br_device_records recs; int64_t id; uint64_t seq; };
   std::mutex out_m; std::condition_variable out_cv; std::map<uint64_t, OutChunk> out_map; uint64_t out_next = 0; bool out_done = false;   // the ordered writer's inbox
   if (o.device_reader < 0) if (const char *e = getenv("BRAMBLE_AMD_DEVICE_READER")) o.device_reader = atoi(e) != 0;   // (A/B with one command line: the @PG line quotes it)
-  const bool use_dev_reader = o.device_reader != 0 && rd.mapped() && (o.device_reader > 0 || rd.mapped_size() >= (1u << 20));
+  const bool use_dev_reader = !is_sam && o.device_reader != 0 && rd.mapped() && (o.device_reader > 0 || rd.mapped_size() >= (1u << 20));
+  const bool dev_bundles = use_dev_reader || is_sam;   // bundles made on the devices (no host record split, no uploaders)
   const size_t n_dev = o.devices.size();
   std::vector<std::unique_ptr<Slot<DevBundle>>> to_dev;
   std::vector<br_bam_reader *> dev_readers(n_dev, nullptr);
+  std::vector<br_sam_reader *> sam_readers(n_dev, nullptr);
+  std::vector<std::unique_ptr<Slot<SamChunk>>> sam_q;
+  for (size_t d = 0; d < n_dev; d++) sam_q.emplace_back(new Slot<SamChunk>(2));
+  // a device's SAM uploader puts chunk j into text slot j % 2 while its processor parses chunk j - 1 (two permits = two slots)
+  struct SamStaged { std::unique_ptr<SamChunk> c; int slot; int rc; };
+  struct SamDev { Slot<SamStaged> ready{2}; std::mutex m; std::condition_variable cv; int permits = 2; };
+  std::vector<std::unique_ptr<SamDev>> sam_dev;
+  for (size_t d = 0; d < n_dev; d++) sam_dev.emplace_back(new SamDev());
+  bool reader_err_at_line = false;   // reader_err is "<line>: <reason>" (a malformed SAM line)
   for (size_t d = 0; d < n_dev; d++) to_dev.emplace_back(new Slot<DevBundle>(64));
   // the whole file's block table: it grows while the readers are already at work on its first pieces (a lazily committed
   // mapping of the worst-case size, so that the table never moves: a block is at least 28 bytes)
@@ -325,7 +484,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
   struct UpState { std::mutex m; std::condition_variable cv; int free_slots = 2; std::deque<int64_t> ready; bool done = false; };
   std::vector<std::unique_ptr<UpState>> ups;
   for (size_t d = 0; d < n_dev; d++) ups.emplace_back(new UpState());
-  auto set_reader_err = [&](const std::string &m) { std::lock_guard<std::mutex> l(err_m); if (reader_err.empty()) reader_err = m; cancel = true; piece_cv.notify_all(); for (auto &u : ups) u->cv.notify_all(); };
+  auto set_reader_err = [&](const std::string &m) { std::lock_guard<std::mutex> l(err_m); if (reader_err.empty()) reader_err = m; cancel = true; piece_cv.notify_all(); for (auto &u : ups) u->cv.notify_all(); for (auto &sd : sam_dev) { std::lock_guard<std::mutex> l2(sd->m); sd->cv.notify_all(); } };
   // blocks [b0, b1) of piece k and the `extra` blocks behind them; waits until the table has grown past them (or is whole).
   // false: no such piece (the table ended in front of it), or the run is being cancelled
   auto piece_range = [&](int64_t k, int64_t extra, int64_t &b0, int64_t &b1, int64_t &b1x, int64_t &nb_now) -> bool {
@@ -452,7 +611,126 @@ extern "C" int br_cli_main(int argc, char **argv) {
       });
     }
   }
-  std::thread reader = use_dev_reader ? std::thread([&]() {
+  if (is_sam) {
+    // one SAM reader per device: its chunks (whole read-name groups, in file order k = d, d + N, ...) become device records.
+    // Two threads a device: the uploader (br_sam_reader_upload, one chunk ahead) and the processor (br_sam_reader_next_staged)
+    for (size_t d = 0; d < n_dev; d++) {
+      dev_threads.emplace_back([&, d]() {
+        SamDev &D = *sam_dev[d];
+        int rrc = cancel ? 0 : br_sam_reader_new(o.devices[d], hdr.text.data(), hdr.text.size(), &sam_readers[d]);
+        if (rrc) set_reader_err(std::string("SAM reader: ") + br_strerror(rrc));
+        for (int64_t j = 0;; j++) {
+          auto c = sam_q[d]->take();
+          if (!c) break;
+          if (cancel || !sam_readers[d]) continue;   // (drain)
+          { std::unique_lock<std::mutex> l(D.m); D.cv.wait(l, [&] { return D.permits > 0 || cancel; }); if (cancel) continue; D.permits--; }
+          auto st = std::make_unique<SamStaged>();
+          st->slot = (int)(j & 1);
+          st->rc = br_sam_reader_upload(sam_readers[d], st->slot, c->data, c->n);
+          st->c = std::move(c);
+          D.ready.put(std::move(st));
+        }
+        D.ready.finish();
+      });
+      dev_threads.emplace_back([&, d]() {
+        auto tr0 = now();
+        SamDev &D = *sam_dev[d];
+        for (;;) {
+          auto st = D.ready.take();
+          if (!st) break;
+          auto give_back = [&]() { { std::lock_guard<std::mutex> l(D.m); D.permits++; } D.cv.notify_all(); };
+          if (cancel) { give_back(); continue; }   // (drain)
+          br_sam_reader *R = sam_readers[d];
+          SamChunk *c = st->c.get();
+          int64_t lines_before = 0;
+          (void)br_sam_reader_stats(R, nullptr, nullptr, nullptr, nullptr, &lines_before);
+          auto b = std::make_unique<DevBundle>();
+          uint64_t used = 0; int64_t un = 0, bad = 0;
+          int rrc = st->rc ? st->rc : br_sam_reader_next_staged(R, st->slot, c->data, c->n, 1, &used, &b->recs, &b->id, &un, &bad);
+          give_back();
+          if (rrc) {
+            if (rrc == BR_ERR_INVALID_ARG && bad > 0) {
+              // the file's line number: header lines + lines in front of the chunk + the line inside it
+              int64_t l0 = c->line0;
+              if (l0 < 0) { l0 = (int64_t)sam.header_lines; for (const uint8_t *p = sam.map + sam.header_bytes; p < c->data; p++) l0 += *p == '\n'; }
+              std::string m = std::to_string(l0 + (bad - lines_before)) + ": " + br_sam_reader_error(R);
+              if (sam.header_bytes == 0) m += " (the input is not BGZF/BAM, and as SAM text it has no header)";
+              { std::lock_guard<std::mutex> l(err_m); if (reader_err.empty()) { reader_err = m; reader_err_at_line = true; } }
+              set_reader_err(m);   // (cancels the run and wakes the waiting threads; the message is in place already)
+            } else set_reader_err(std::string("SAM reader: ") + br_strerror(rrc));
+            continue;
+          }
+          if (used != c->n) {   // (a chunk the reader could not take whole: one read-name group of more than 1 GiB of text)
+            (void)br_sam_reader_release(R, b->id);
+            set_reader_err("a read-name group spans more than the SAM reader can take at once (1 GiB of text)");
+            continue;
+          }
+          total_reads_a += (uint64_t)(b->recs.n_aln + un); unmapped_reads_a += (uint64_t)un;
+          b->seq = c->seq;
+          if (b->recs.n_aln == 0) {   // nothing to project: the writer steps over this chunk
+            (void)br_sam_reader_release(R, b->id);
+            { std::lock_guard<std::mutex> l(out_m); out_map[b->seq] = OutChunk{nullptr, 0, -1}; }
+            out_cv.notify_all();
+            continue;
+          }
+          to_dev[d]->put(std::move(b));
+        }
+        to_dev[d]->finish();
+        const double t = secs(tr0, now());
+        { std::lock_guard<std::mutex> l(err_m); t_dev_reader = std::max(t_dev_reader, t); }
+      });
+    }
+  }
+  std::thread reader = is_sam ? std::thread([&]() {
+    // the SAM feeder: chunks of about --bundle-size records, cut at read-name changes, dealt round-robin to the devices
+    auto tr0 = now();
+    uint64_t k = 0;
+    const bool mapped = sam.map != nullptr;
+    if (!mapped && !sam.eof) sam.read_more(4u << 20);
+    // bytes a record takes, from the first lines (the chunk size follows from --bundle-size)
+    const uint8_t *s0 = mapped ? sam.map + sam.header_bytes : sam.pbuf.data();
+    const uint64_t n0 = mapped ? sam.map_size - sam.header_bytes : sam.pbuf.size();
+    uint64_t probe = std::min<uint64_t>(n0, 4u << 20), nl0 = 0;
+    for (uint64_t i = 0; i < probe; i++) nl0 += s0[i] == '\n';
+    const uint64_t per_line = nl0 ? probe / nl0 + 1 : 512;
+    const uint64_t chunk_bytes = std::max<uint64_t>(1u << 20, std::min<uint64_t>((uint64_t)o.bundle_records * per_line, 768ull << 20));
+    uint64_t off = 0;            // mapped: where the next chunk starts (behind the header)
+    int64_t line0 = (int64_t)sam.header_lines;   // pipe: the file line of the next chunk's first line
+    while (!cancel) {
+      auto c = std::make_unique<SamChunk>();
+      if (mapped) {
+        const uint8_t *start = s0 + off, *end = s0 + n0;
+        if (start >= end) break;
+        const uint8_t *target = start + std::min<uint64_t>(chunk_bytes, (uint64_t)(end - start));
+        const uint8_t *cut = target == end ? end : sam_cut(start, target, end, true);
+        c->data = start; c->n = (uint64_t)(cut - start);
+        off += c->n;
+      } else {
+        const uint8_t *cut = nullptr;
+        for (uint64_t want = chunk_bytes;; want *= 2) {
+          while (sam.pbuf.size() < want && !sam.eof) sam.read_more(std::min<uint64_t>(want - sam.pbuf.size(), 64u << 20));
+          if (sam.pbuf.size() == 0) break;
+          const uint8_t *start = sam.pbuf.data(), *end = start + sam.pbuf.size();
+          const uint8_t *target = start + std::min<uint64_t>(want, sam.pbuf.size());
+          cut = (target == end && sam.eof) ? end : sam_cut(start, target, end, sam.eof);
+          if (cut) break;
+        }
+        if (!cut) break;
+        const uint64_t n = (uint64_t)(cut - sam.pbuf.data());
+        c->own.resize(n); memcpy(c->own.data(), sam.pbuf.data(), n);
+        sam.pbuf.erase_front(n);
+        c->data = c->own.data(); c->n = n; c->line0 = line0;
+        for (uint64_t i = 0; i < n; i++) line0 += c->data[i] == '\n';
+      }
+      c->seq = k;
+      sam_q[k % n_dev]->put(std::move(c));
+      k++;
+    }
+    if (sam.read_failed) set_reader_err("read error");
+    next_seq = k;
+    for (auto &q : sam_q) q->finish();
+    t_reader = secs(tr0, now());
+  }) : use_dev_reader ? std::thread([&]() {
     // (the device readers run on dev_threads; this thread only waits for the block table, for next_seq)
     std::unique_lock<std::mutex> l(piece_m); piece_cv.wait(l, [&] { return table_ready || cancel; });
     next_seq = (uint64_t)n_pieces;
@@ -574,11 +852,11 @@ extern "C" int br_cli_main(int argc, char **argv) {
   // the reader is already inflating while the guides are parsed and the indexes are built
   // (only the queues the running reader feeds are ever finished: taking from the others would wait for ever)
   auto join_dev_threads = [&]() { for (auto &t : dev_threads) if (t.joinable()) t.join(); };
-  auto free_dev_readers = [&]() { for (auto &r : dev_readers) { if (r) br_bam_reader_free(r); r = nullptr; } };
+  auto free_dev_readers = [&]() { for (auto &r : dev_readers) { if (r) br_bam_reader_free(r); r = nullptr; } for (auto &r : sam_readers) { if (r) br_sam_reader_free(r); r = nullptr; } };
   auto stop_reader = [&]() -> int {
     cancel = true;
     piece_cv.notify_all(); for (auto &u : ups) u->cv.notify_all();
-    if (use_dev_reader) { for (auto &q : to_dev) while (q->take()) {} } else { while (to_gpu.take()) {} }
+    if (dev_bundles) { for (auto &q : to_dev) while (q->take()) {} } else { while (to_gpu.take()) {} }
     reader.join(); join_dev_threads(); free_dev_readers();
     return 1;
   };
@@ -699,7 +977,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
     }
   });
 
-  if (use_dev_reader) {
+  if (dev_bundles) {
     // no uploaders: every worker's bundles are in its device's HBM already (its own reader made them)
     for (auto &wp : workers) {
       Worker *w = wp.get();
@@ -719,7 +997,8 @@ extern "C" int br_cli_main(int argc, char **argv) {
             w->gpu_seconds += secs(t0, now());
             if (prc2) { fprintf(stderr, "error: projection failed on device %d: %s\n", w->device, br_strerror(prc2)); raise_fail(); }
           }
-          (void)br_bam_reader_release(dev_readers[(size_t)w->id], b->id);
+          if (is_sam) (void)br_sam_reader_release(sam_readers[(size_t)w->id], b->id);
+          else (void)br_bam_reader_release(dev_readers[(size_t)w->id], b->id);
           if (fail) continue;  // drain
           w->total_complete += hb.total_complete; w->total_unique += hb.total_unique; w->dropped += hb.dropped_reads; w->n_bundles++;
           { std::lock_guard<std::mutex> l(w->done_m); w->produced++; }
@@ -785,9 +1064,9 @@ extern "C" int br_cli_main(int argc, char **argv) {
   { std::lock_guard<std::mutex> l(out_m); out_done = true; }
   out_cv.notify_all();
   reader.join(); join_dev_threads(); writer.join();
-  if (use_dev_reader) { total_reads = total_reads_a.load(); unmapped_reads = unmapped_reads_a.load(); }
+  if (dev_bundles) { total_reads = total_reads_a.load(); unmapped_reads = unmapped_reads_a.load(); }
   int failed = fail.load();
-  if (!reader_err.empty()) { fprintf(stderr, "error: %s: %s\n", o.in_bam.c_str(), reader_err.c_str()); failed = 1; }
+  if (!reader_err.empty()) { fprintf(stderr, reader_err_at_line ? "error: %s:%s\n" : "error: %s: %s\n", o.in_bam.c_str(), reader_err.c_str()); failed = 1; }
   if (!writer_err.empty()) { fprintf(stderr, "error: %s: %s\n", o.out_bam.c_str(), writer_err.c_str()); failed = 1; }
   if (!failed && out_next != next_seq) { fprintf(stderr, "error: %s: output incomplete\n", o.out_bam.c_str()); failed = 1; }
   if (failed) {
@@ -838,7 +1117,13 @@ extern "C" int br_cli_main(int argc, char **argv) {
     fprintf(stderr, "[bramble] device readers: block table %.2fs; the longest processing thread %.2fs in all (inflate + record split + cuts: %.2fs; the rest: waiting for its uploads, its neighbour's cut, the runner's queue); %llu pieces, %llu processed again from the true start\n",
             t_block_scan, t_dev_reader, t_in, (unsigned long long)n_pieces, (unsigned long long)reprocessed.load());
   }
-  if (getenv("BRAMBLE_AMD_TIMING") && !use_dev_reader) fprintf(stderr, "[bramble] reader thread: %.2fs in all, %.2fs reserving buffers, %.2fs waiting for a free queue slot\n", t_reader, t_reserve, t_put);
+  if (getenv("BRAMBLE_AMD_TIMING") && is_sam) {
+    double t_up = 0, t_parse = 0; uint64_t nb = 0;
+    for (auto r : sam_readers) { double u = 0, p = 0; uint64_t b = 0; (void)br_sam_reader_stats(r, &u, &p, nullptr, &b, nullptr); t_up += u; t_parse += p; nb += b; }
+    fprintf(stderr, "[bramble] SAM readers: %.3f GB of text, device upload %.3fs, device parse %.3fs (summed over devices); feeder thread %.2fs\n",
+            1e-9 * (double)nb, t_up, t_parse, t_reader);
+  }
+  if (getenv("BRAMBLE_AMD_TIMING") && !use_dev_reader && !is_sam) fprintf(stderr, "[bramble] reader thread: %.2fs in all, %.2fs reserving buffers, %.2fs waiting for a free queue slot\n", t_reader, t_reserve, t_put);
   // the unwinding below this line (record buffers, worker contexts, reader and writer pools) was 0.5 s of a 1.9 s run
   if (g_exit_at_end.load() && !getenv("BRAMBLE_AMD_CLI_CLEANUP")) {   // (tools that write their results from exit handlers -- a profiler -- ask for the clean return)
     if (getenv("BRAMBLE_AMD_TIMING")) { struct timespec t; clock_gettime(CLOCK_REALTIME, &t); fprintf(stderr, "[bramble] leaving at %.3f\n", (double)t.tv_sec + 1e-9 * (double)t.tv_nsec); }

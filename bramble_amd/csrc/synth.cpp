@@ -501,6 +501,65 @@ void synth_frame_records(const uint8_t *blob, const uint64_t *off, int64_t n, ui
     o += 4 + (uint64_t)len;
   }
 }
+// BAM records -> SAM text (what `samtools view` prints for them): stream = [block_size][record]..., ref_names = the header's
+// references.  Returns the text's length; *out is malloc'd (synth_free).  Benchmarks and tests need SAM input in bulk.
+int64_t synth_records_to_sam(const uint8_t *stream, uint64_t n, const char *const *ref_names, int32_t n_ref, char **out) {
+  std::string o;
+  o.reserve((size_t)(n * 2 + 64));
+  auto u32 = [](const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; };
+  auto ref = [&](int32_t r) -> const char * { return r >= 0 && r < n_ref ? ref_names[r] : "*"; };
+  char num[64];
+  for (uint64_t p = 0; p + 4 <= n;) {
+    const uint32_t bs = u32(stream + p);
+    const uint8_t *r = stream + p + 4, *e = r + bs;
+    p += 4 + (uint64_t)bs;
+    const int32_t rid = (int32_t)u32(r), pos = (int32_t)u32(r + 4), nrid = (int32_t)u32(r + 20), npos = (int32_t)u32(r + 24), tlen = (int32_t)u32(r + 28);
+    const uint32_t lqn = r[8], mapq = r[9], ncig = u32(r + 12) & 0xffff, flag = u32(r + 12) >> 16, l_seq = u32(r + 16);
+    const uint8_t *q = r + 32;
+    o.append((const char *)q, lqn ? lqn - 1 : 0); q += lqn;
+    snprintf(num, sizeof num, "\t%u\t", flag); o += num; o += ref(rid);
+    snprintf(num, sizeof num, "\t%d\t%u\t", pos + 1, mapq); o += num;
+    if (!ncig) o += '*';
+    for (uint32_t k = 0; k < ncig; k++) { const uint32_t w = u32(q + 4 * k); snprintf(num, sizeof num, "%u%c", w >> 4, "MIDNSHP=XB"[std::min<uint32_t>(w & 15, 9)]); o += num; }
+    q += 4ull * ncig;
+    o += '\t'; o += nrid < 0 ? "*" : nrid == rid ? "=" : ref(nrid);
+    snprintf(num, sizeof num, "\t%d\t%d\t", npos + 1, tlen); o += num;
+    if (!l_seq) o += '*';
+    for (uint32_t k = 0; k < l_seq; k++) o += "=ACMGRSVTWYHKDBN"[(q[k >> 1] >> ((~k & 1) * 4)) & 15];
+    q += (l_seq + 1) / 2;
+    o += '\t';
+    if (!l_seq || q[0] == 0xff) o += '*';
+    else for (uint32_t k = 0; k < l_seq; k++) o += (char)(q[k] + 33);
+    q += l_seq;
+    while (q + 3 <= e) {
+      o += '\t'; o.append((const char *)q, 2); const uint8_t t = q[2]; q += 3;
+      auto ival = [&](uint8_t ty, const uint8_t *v) -> long long {
+        switch (ty) { case 'c': return (int8_t)v[0]; case 'C': return v[0]; case 's': { int16_t x; memcpy(&x, v, 2); return x; }
+                      case 'S': { uint16_t x; memcpy(&x, v, 2); return x; } case 'i': return (int32_t)u32(v); default: return u32(v); }
+      };
+      auto isz = [](uint8_t ty) { return ty == 'c' || ty == 'C' ? 1 : ty == 's' || ty == 'S' ? 2 : 4; };
+      if (t == 'A') { o += ":A:"; o += (char)q[0]; q += 1; }
+      else if (t == 'c' || t == 'C' || t == 's' || t == 'S' || t == 'i' || t == 'I') { snprintf(num, sizeof num, ":i:%lld", ival(t, q)); o += num; q += isz(t); }
+      else if (t == 'f') { float f; memcpy(&f, q, 4); snprintf(num, sizeof num, ":f:%g", f); o += num; q += 4; }
+      else if (t == 'Z' || t == 'H') { o += ':'; o += (char)t; o += ':'; const uint8_t *z = q; while (z < e && *z) z++; o.append((const char *)q, (size_t)(z - q)); q = z + 1; }
+      else if (t == 'B') {
+        const uint8_t sub = q[0]; const uint32_t cnt = u32(q + 1); q += 5;
+        o += ":B:"; o += (char)sub;
+        for (uint32_t k = 0; k < cnt; k++) {
+          if (sub == 'f') { float f; memcpy(&f, q, 4); snprintf(num, sizeof num, ",%g", f); q += 4; }
+          else { snprintf(num, sizeof num, ",%lld", ival(sub, q)); q += isz(sub); }
+          o += num;
+        }
+      } else break;
+    }
+    o += '\n';
+  }
+  *out = (char *)malloc(o.size() + 1);
+  if (!*out) return -1;
+  memcpy(*out, o.data(), o.size());
+  return (int64_t)o.size();
+}
+void synth_free(char *p) { free(p); }
 const uint64_t *synth_reads_seq_off(void *h) { return ((Reads *)h)->seq_off.data(); }
 const char *synth_reads_seqs(void *h) { return ((Reads *)h)->seqs.data(); }
 

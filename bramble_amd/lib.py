@@ -164,6 +164,7 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_project_batch", "br_project_batch_device", "br_device_rows_expand", "br_batch_stage", "br_project_staged", "br_host_rows_wait", "br_project_batch_packed",
            "br_pin_host", "br_unpin_host", "br_project_group", "br_project_groups", "br_bam_encode_device", "br_project_bam_device", "br_project_bam_bundle", "br_bam_bundle_stage", "br_project_bam_staged", "br_bam_split", "br_annotation_load", "br_annotation_load_mt", "br_annotation_free",
            "br_annotation_num_transcripts", "br_annotation_transcripts", "br_annotation_num_refs", "br_annotation_refnames", "br_cli_main", "br_cli_exit_at_end", "br_device_warmup", "br_project_bam_staged_nowait", "br_host_bam_wait", "br_bgzf_scan", "br_bgzf_inflate_device", "br_bam_split_device", "br_bam_reader_new", "br_bam_reader_next", "br_bam_reader_set_piece_blocks", "br_bam_reader_release", "br_bam_reader_free", "br_bam_piece_upload", "br_bam_piece_process", "br_bam_reader_seconds", "br_bam_reader_upload_seconds", "br_project_bam_resident", "br_bgzf_write_file", "br_bgzf_read_file",
+           "br_sam_header_scan", "br_sam_reader_new", "br_sam_reader_next", "br_sam_reader_upload", "br_sam_reader_next_staged", "br_sam_reader_release", "br_sam_reader_free", "br_sam_reader_error", "br_sam_reader_stats",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -757,6 +758,90 @@ class Context:
     def close(self):
         if self.h:
             lib().br_ctx_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sam_header_scan(data):
+    """br_sam_header_scan: bytes of the leading '@' lines of `data` (bytes)."""
+    hb = C.c_uint64()
+    L = lib()
+    L.br_sam_header_scan.argtypes = [C.c_char_p, C.c_uint64, _P(C.c_uint64)]
+    check(L.br_sam_header_scan(data, len(data), C.byref(hb)), "br_sam_header_scan")
+    return int(hb.value)
+
+
+class SamError(BrambleError):
+    """A malformed SAM line: .line is its 1-based number from the reader's start, .reason what is wrong with it."""
+
+    def __init__(self, line, reason):
+        super().__init__("SAM line %d: %s" % (line, reason))
+        self.line, self.reason = line, reason
+
+
+class SamReader:
+    """br_sam_reader on `device`: SAM record text in, the bundles' mapped BAM records out as host bytes (for tests and tools;
+    the command line hands the device-resident bundles to the projection instead)."""
+
+    def __init__(self, header_text, device=0):
+        L = lib()
+        L.br_sam_reader_new.argtypes = [C.c_int, C.c_char_p, C.c_uint64, _P(C.c_void_p)]
+        L.br_sam_reader_next.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, _P(C.c_uint64), _P(BrDeviceRecords),
+                                         _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)]
+        L.br_sam_reader_release.argtypes = [C.c_void_p, C.c_int64]
+        L.br_sam_reader_free.argtypes = [C.c_void_p]
+        L.br_sam_reader_error.argtypes = [C.c_void_p]
+        L.br_sam_reader_error.restype = C.c_char_p
+        L.br_sam_reader_stats.argtypes = [C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_int64), _P(C.c_uint64), _P(C.c_int64)]
+        self.h = None
+        self.device = device
+        h = C.c_void_p()
+        header_text = header_text.encode() if isinstance(header_text, str) else bytes(header_text)
+        check(L.br_sam_reader_new(device, header_text, len(header_text), C.byref(h)), "br_sam_reader_new")
+        self.h = h
+
+    def next(self, text, last, fetch=True):
+        """-> dict(stream = uint8 [block_size][record]... of the mapped records (fetch=False: not downloaded), n, n_unmapped,
+        consumed)."""
+        L = lib()
+        recs, rid, un, bad, used = BrDeviceRecords(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_uint64()
+        rc = L.br_sam_reader_next(self.h, bytes(text), len(text), 1 if last else 0, C.byref(used), C.byref(recs), C.byref(rid),
+                                  C.byref(un), C.byref(bad))
+        if rc == -1 and bad.value > 0:
+            raise SamError(int(bad.value), L.br_sam_reader_error(self.h).decode())
+        check(rc, "br_sam_reader_next")
+        n = int(recs.n_aln)
+        stream = np.zeros(0, dtype=np.uint8)
+        try:
+            if n and fetch:
+                import torch
+                from .device import _DevArray
+                dev = "cuda:%d" % self.device
+                off = torch.as_tensor(_DevArray(recs.rec_off, n, "<u8"), device=dev).cpu().numpy().astype(np.uint64)
+                ln = torch.as_tensor(_DevArray(recs.rec_len, n, "<i4"), device=dev).cpu().numpy().view(np.uint32).astype(np.uint64)
+                lo, hi = int(off[0]) - 4, int(off[-1] + ln[-1])
+                blob = torch.as_tensor(_DevArray(recs.blob + lo, hi - lo, "|u1"), device=dev).cpu().numpy()
+                parts = [blob[int(o) - 4 - lo:int(o + l) - lo] for o, l in zip(off, ln)]
+                stream = np.concatenate(parts).astype(np.uint8)
+        finally:
+            if rid.value >= 0:
+                check(L.br_sam_reader_release(self.h, rid.value), "br_sam_reader_release")
+        return {"stream": stream, "n": n, "n_unmapped": int(un.value), "consumed": int(used.value)}
+
+    def stats(self):
+        up, parse, ch, nb, nl = C.c_double(), C.c_double(), C.c_int64(), C.c_uint64(), C.c_int64()
+        check(lib().br_sam_reader_stats(self.h, C.byref(up), C.byref(parse), C.byref(ch), C.byref(nb), C.byref(nl)),
+              "br_sam_reader_stats")
+        return {"upload_s": up.value, "parse_s": parse.value, "chunks": int(ch.value), "bytes": int(nb.value), "lines": int(nl.value)}
+
+    def close(self):
+        if self.h:
+            lib().br_sam_reader_free(self.h)
             self.h = None
 
     def __del__(self):

@@ -173,3 +173,22 @@ class Annotation:
             lib().synth_annotation_free(self.h)
         except Exception:
             pass
+
+
+def records_to_sam(stream, ref_names):
+    """BAM records ([block_size][record]..., numpy uint8) -> SAM text (bytes), the lines `samtools view` prints for them
+    (bramble_amd/csrc/synth.cpp: synth_records_to_sam)."""
+    L = lib()
+    L.synth_records_to_sam.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_void_p)]
+    L.synth_records_to_sam.restype = C.c_int64
+    L.synth_free.argtypes = [C.c_void_p]
+    stream = np.ascontiguousarray(stream, dtype=np.uint8)
+    names = (C.c_char_p * max(len(ref_names), 1))(*[n.encode() for n in ref_names])
+    out = C.c_void_p()
+    n = L.synth_records_to_sam(stream.ctypes.data, stream.size, names, len(ref_names), C.byref(out))
+    if n < 0:
+        raise MemoryError("synth_records_to_sam")
+    try:
+        return C.string_at(out.value, n) if n else b""
+    finally:
+        L.synth_free(out)

@@ -520,6 +520,45 @@ int br_bam_piece_process(br_bam_reader *, int slot, const br_bgzf_block *blocks,
 double br_bam_reader_seconds(const br_bam_reader *);   /* time spent inside br_bam_piece_process so far */
 double br_bam_reader_upload_seconds(const br_bam_reader *);   /* ... inside br_bam_piece_upload (host copies into pinned buffers + queueing) */
 void br_bam_reader_free(br_bam_reader *);
+
+/* ---- SAM text input (sam_reader.cpp, sam_kernels.hip) ------------------------------------------------------------------
+ * The reference reads SAM like BAM, through htslib (GSamReader -> hts_open, gclib/GSam.h:371): every line becomes the bam1_t
+ * sam_parse1 builds.  A SAM reader turns SAM record lines into BAM records on the device, laid out as br_bam_split_device lays
+ * them out, so its bundles feed br_project_bam_resident unchanged and the records are byte for byte what `samtools view -b`
+ * writes for the same lines (bam_write1: no extra NULs after the read name, the CG:B,I form for more than 65535 CIGAR ops).
+ *   br_sam_header_scan   host only: the length of the leading '@' lines of data[0, n) (the last one may lack its '\n')
+ *   br_sam_reader_new    header_text = the '@' lines; the references are its @SQ lines' SN: names, in order.  The names go to
+ *                        a device hash table, built once per reader
+ *   br_sam_reader_next   text = SAM record lines in HOST memory (copied to the device through two pinned slots on the reader's
+ *                        own stream).  *consumed = up to the start of the last read-name group's first mapped line
+ *                        (everything when last != 0, where a final line without '\n' is accepted); 0 when the text holds no
+ *                        complete group -- call again with more bytes.  bundle as br_bam_reader_next (mapped records in HBM,
+ *                        valid until br_sam_reader_release(id)); *n_unmapped = the lines in front of the cut that are unmapped
+ *                        (flag 0x4, an RNAME without an @SQ line, no query-consuming CIGAR op).  BR_ERR_INVALID_ARG for a
+ *                        malformed line: *bad_line = its 1-based number counted from the reader's first line,
+ *                        br_sam_reader_error says what is wrong with it.  At most 1 GiB of text is taken per call.
+ * br_sam_reader_next is called from one thread; br_sam_reader_release may come from another. */
+typedef struct br_sam_reader br_sam_reader;
+int br_sam_header_scan(const uint8_t *data, uint64_t n, uint64_t *header_bytes);
+int br_sam_reader_new(int device, const char *header_text, uint64_t header_len, br_sam_reader **out);
+int br_sam_reader_next(br_sam_reader *, const uint8_t *text, uint64_t n_bytes, int last, uint64_t *consumed,
+                       br_device_records *bundle, int64_t *id, int64_t *n_unmapped, int64_t *bad_line);
+/* The same call in two steps, so that the upload of chunk k+1 overlaps the parse of chunk k (two device text slots; the upload
+ * runs on a copy stream of its own and may be called from another thread, one chunk ahead): br_sam_reader_upload puts text
+ * into slot 0 / 1 and returns when it is on the device; br_sam_reader_next_staged parses the slot (text must be the same host
+ * bytes: the float fallback reads them).  A slot may be uploaded again once its br_sam_reader_next_staged call has returned.
+ * br_sam_reader_next is upload + next_staged on slot 0. */
+int br_sam_reader_upload(br_sam_reader *, int slot, const uint8_t *text, uint64_t n_bytes);
+int br_sam_reader_next_staged(br_sam_reader *, int slot, const uint8_t *text, uint64_t n_bytes, int last, uint64_t *consumed,
+                              br_device_records *bundle, int64_t *id, int64_t *n_unmapped, int64_t *bad_line);
+int br_sam_reader_release(br_sam_reader *, int64_t id);
+void br_sam_reader_free(br_sam_reader *);
+const char *br_sam_reader_error(const br_sam_reader *);   /* the reason of the last BR_ERR_INVALID_ARG ("" otherwise) */
+/* so far: device time of the text uploads and of the parse (line index through emit), calls, text bytes and lines consumed
+ * (any pointer may be NULL) */
+int br_sam_reader_stats(const br_sam_reader *, double *upload_seconds, double *parse_seconds, int64_t *chunks, uint64_t *bytes,
+                        int64_t *lines);
+
 /* br_project_bam_staged / _nowait for records that are in HBM already (a br_bam_reader bundle, or br_bam_split_device's) */
 int br_project_bam_resident(br_ctx *, const br_config *, const br_device_records *recs, const int32_t *ref_map, int32_t n_ref_map,
                             int bgzf_on_device, int nowait, br_host_bam *out);
