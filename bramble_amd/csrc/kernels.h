@@ -39,14 +39,6 @@ struct ProjectArgs {
   uint4 *m_b;            // {clip_score, 0, similarity lo, similarity hi}
   uint64_t *m_cigoff;
   uint32_t *cig_arena;
-  // single-pass count + emit (k_project1 / k_emit_wl; null p1: the two-pass path): the kernel that finds an alignment's
-  // survivors takes its slice of the match table, of the general-class work list and of the CIGAR arena from pages its
-  // wave owns, and writes match_off / cig_base itself
-  uint32_t *match_off_w;
-  uint64_t *cig_base_w;
-  uint4 *wl;             // work list of the general class: {alignment, slab row | strand << 31, match slot, rank}; ~0u in .x: hole
-  uint64_t *p1;          // device counters, see P1_* below
-  uint64_t cap_m, cap_w, cap_c;   // capacities of the match table (slots), the work list (entries) and the arena (words)
   // small batches without host round trips: the scan totals stay on the device (tot[0] matches, tot[1] arena words,
   // tot[2] matches of the simple class), the tables were sized from upper bounds lim_m / lim_c, and a kernel that finds the
   // totals beyond them does nothing (the host sees the same totals at the end and takes the ordinary path).  null: the
@@ -56,14 +48,6 @@ struct ProjectArgs {
   uint64_t cover;        // work-list entries the launch's grid covers (large batches launched from predicted counts): more -> nothing is done
 };
 __device__ __forceinline__ bool tot_over(const uint64_t *tot, uint64_t lim_m, uint64_t lim_c) { return tot && (tot[0] > lim_m || tot[1] > lim_c); }
-// k_project1's counters (u64 each): the three allocators' high-water marks, "a capacity was exceeded", matches found,
-// work-list entries written
-// (the three allocators sit in different 128-byte lines: same-line atomics serialise in one L2 channel)
-enum { P1_M = 0, P1_W = 16, P1_C = 32, P1_OVF = 48, P1_NM = 49, P1_NW = 50, P1_WORDS = 64 };
-#define P1_PAGE_M 16384u   // match slots a wave takes from the global counter at a time
-#define P1_PAGE_W 4096u    // work-list entries per page (unused entries are filled with hole markers)
-#define P1_PAGE_C 262144u  // arena words per page
-
 
 // -S clip rescue (rescue_kernels.inc)
 struct FaArgs {
@@ -452,9 +436,6 @@ void launch_ksw_trace(hipStream_t st, const KswFastArgs &A, int bin);   // bin <
 uint32_t ksw_dp_resident_groups(int bin, int n_cu);
 size_t ksw_prob_bytes();
 size_t ksw_res_bytes();
-// single pass: part 1 = the main kernel (alignments that need the exon walk go to walk_list), 2 = the listed ones
-void launch_project1(hipStream_t st, const ProjectArgs &A, int group_lanes, int n_blocks, int part);
-void launch_emit_wl(hipStream_t st, const ProjectArgs &A, int64_t n_entries);
 void launch_expand(hipStream_t st, const ProjectArgs &A);
 // n_simple: length of the work list's simple-class prefix (k_scan3's third total); part 0: one launch over
 // everything, 1: the simple prefix, 2: the rest

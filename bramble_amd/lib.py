@@ -17,7 +17,7 @@ KERNEL_NAMES = ["k_segment", "k_project<G,false,false,1>", "k_emit_dense<false,2
                 "k_rows", "k_scan_*", "k_project<64,true>", "k_ksw", "k_bam_scan+k_bam_size+k_bam_encode",
                 "k_rec_fields+k_group_off+k_rec_copy+k_mates+k_seq_*", "k_deflate_*+k_bgzf_compact",
                 "k_emit_dense<false,1>", "k_primary", "(unused)", "k_project<G,false,false,2>", "k_expand", "k_group_ids",
-                "k_project1<G,1>", "k_project1<G,2>", "k_emit_wl", "k_name_seed", "k_pair_mask", "k_big<0>+k_pair_big", "k_group_desc",
+                "(unused)", "(unused)", "(unused)", "k_name_seed", "k_pair_mask", "k_big<0>+k_pair_big", "k_group_desc",
                 "k_expand_rows", "k_emit_rows<1>", "k_emit_rows<2>", "k_big<1>"]
 
 

@@ -652,9 +652,9 @@ const char *br_bgzf_codec(void); /* "libdeflate" (bound at run time when present
 #define BR_K_COUNT_WALK 15 /* k_project<G,false,false,2>: the deferred alignments of the split count pass, with the exon walk */
 #define BR_K_EXPAND 16    /* k_expand (emit work list) */
 #define BR_K_GROUP_IDS 17 /* k_group_ids */
-#define BR_K_P1 18        /* k_project1<G,1>: single-pass count + emit, main kernel (simple class written, general class listed) */
-#define BR_K_P1_WALK 19   /* k_project1<G,2>: the alignments that need the exon walk */
-#define BR_K_EMIT_WL 20   /* k_emit_wl: the general class from the single pass's work list */
+#define BR_K_P1 18        /* unused since the single-pass count + emit variant was removed */
+#define BR_K_P1_WALK 19   /* unused since the single-pass count + emit variant was removed */
+#define BR_K_EMIT_WL 20   /* unused since the single-pass count + emit variant was removed */
 #define BR_K_NAME_SEED 21  /* k_name_seed: first mt19937_64 output per read name (direct rows) */
 #define BR_K_PAIR_MASK 22  /* k_pair_mask: pairing on the survivor sets, before the emit pass */
 #define BR_K_PAIR_BIG 23   /* k_big<0> + k_pair_big: the same for alignments with > 64 candidate rows */

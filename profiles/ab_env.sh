@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of one build under two settings of an environment variable, interleaved on one box (boxes differ by a few per cent):
-#   bash profiles/ab_env.sh BRAMBLE_AMD_SINGLE_PASS 0 1 [bench.py args]
+#   bash profiles/ab_env.sh BRAMBLE_AMD_SPECULATE 1 0 [bench.py args]
 set -o pipefail
 var=$1; a=$2; b=$3; shift 3
 mkdir -p gpurun_out

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-3 evidence (run through gpurun from the repo root): bash profiles/collect_r03.sh [tag]
-# The bench line, rocprofv3 kernel stats and the two PMC passes of the same command, the single-pass A/B with its issue
-# counters, small calls (bench_extra small), configs[2] / configs[4] shapes, the records path, the command line, and
+# The bench line, rocprofv3 kernel stats and the two PMC passes of the same command, small calls (bench_extra small),
+# configs[2] / configs[4] shapes, the records path, the command line, and
 # `bench.py --gpus 2` starting its own ranks.  Outputs under gpurun_out/$1/.
 set -o pipefail
 R=${1:-r03}
@@ -15,9 +15,6 @@ echo "stats done"
 rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-pcie > $O/pmc_fetch.log 2>&1 || exit 1
 rocprofv3 --output-format csv --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-pcie > $O/pmc_write.log 2>&1 || exit 1
 echo "traffic passes done"
-bash profiles/ab_env.sh BRAMBLE_AMD_SINGLE_PASS 0 1 > $O/ab_single_pass.log 2>&1 || exit 1
-bash profiles/pmc_p1.sh > $O/pmc_single_pass.txt 2>&1 || exit 1
-echo "single-pass A/B done"
 python3 bench_extra.py small > $O/bench_extra_small.json.log 2> $O/small.err || exit 1
 for p in 5000 52000; do python3 bench.py --pairs $p --steps 50 --warmup 5 --no-cpu-baseline --no-pcie > $O/bench_pairs$p.json.log 2>/dev/null || exit 1; done
 echo "small calls done"

@@ -369,11 +369,12 @@ def test_single_kernel_forms_of_the_split_passes(key):
         idx.close()
 
 
-def test_single_pass_variant_equals_oracle():
-    """"single_pass" = 1: count and emit in one sweep (k_project1 places every alignment's matches from wave-owned pages,
-    writes the simple class at once and lists the general class for k_emit_wl).  The variant lost its A/B (DESIGN
-    section 10) and is off by default; it stays selectable, so it stays bit-exact: short-read presets, both group
-    widths, a dense locus (> 64 candidate rows, > 32 survivors), small first-call capacities that overflow and retry."""
+def test_short_read_paths_equal_oracle_at_dense_loci():
+    """Every short-read pipeline a context can choose -- the default (small-batch path; the larger batches here: direct
+    rows, then the launch from the last call's counts), small_batch = 0 (direct rows) and small_batch = 0 with
+    direct_rows = 0 (the match-table path) -- against the oracle: the short-read presets and their options, both group
+    widths, a dense locus (> 64 candidate rows, > 32 survivors), pairs turned unpaired (every match emitted), long
+    CIGARs under the short-read preset; two calls per context, the second starting from the state the first one left."""
     cases = []
     s_ann = synth.Annotation("S")
     for mode, flags in (("se", {}), ("pe", {}), ("pe", {"strict": 1}), ("pe", {"fr": 1}), ("pe", {"max_clip": 2, "max_junc_ins": 3, "max_junc_gap": 3}),
@@ -402,12 +403,14 @@ def test_single_pass_variant_equals_oracle():
         orc, _, _ = ob.run(ob.OracleIndex(ann), ob.make_flags(**flags), b, want_matches=False)
         idx = lib.Index(ann, device=0)
         for gl in (8, 16):
-            ctx = lib.Context(idx)
-            ctx.set_param("group_lanes", gl)
-            ctx.set_param("single_pass", 1)
-            for _ in range(2):   # the second call starts from the first one's high-water marks
-                assert_rows_equal(ctx.project_batch(lib.make_config(**flags), b), orc)
-            ctx.close()
+            for params in ({}, {"small_batch": 0}, {"small_batch": 0, "direct_rows": 0}):
+                ctx = lib.Context(idx)
+                ctx.set_param("group_lanes", gl)
+                for k, v in params.items():
+                    ctx.set_param(k, v)
+                for _ in range(2):
+                    assert_rows_equal(ctx.project_batch(lib.make_config(**flags), b), orc)
+                ctx.close()
         idx.close()
 
 
