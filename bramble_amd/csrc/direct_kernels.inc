@@ -703,10 +703,9 @@ __global__ void __launch_bounds__(256) k_expand_rows(DirectArgs D) {
 
 // ---------------------------------------------------------------------------
 // k_emit_rows<CLS>: one lane per kept match (work-list entry).  Entry -> alignment -> its k-th kept survivor (k-th set
-// bit of the filtered mask) and that survivor's tid rank c among the kept (a nibble of the rank word; beyond 16 kept: the
-// rank loop over s_tid, as k_emit_dense) -> candidate row -> ideal CIGAR, merge -> the packed row at
-// first record + stride * c.  CLS as k_emit_dense: 1 = the simple prefix (one read exon from a single M op), 2 = the
-// rest, 0 = everything in one launch.
+// bit of the filtered mask) and that survivor's tid rank c among the kept (the rank loop over s_tid, as k_emit_dense) ->
+// candidate row -> ideal CIGAR, merge -> the packed row at first record + stride * c.  CLS as k_emit_dense: 1 = the simple
+// prefix (one read exon from a single M op), 2 = the rest.
 // ---------------------------------------------------------------------------
 template <int CLS>
 __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 6) k_emit_rows(ProjectArgs A, DirectArgs D, int64_t first, int64_t n_end) {
@@ -731,7 +730,7 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 6) k_emit_rows(ProjectArgs
   const uint4 hd = make_uint4(hd_.x, hd_.y, hd_.z, hd_.w), rg = make_uint4(rg_.x, rg_.y, rg_.z, rg_.w);
   const uint2 f = make_uint2(f_.x, f_.y), gd = make_uint2(gd_.x, gd_.y), dp = make_uint2(dp_.x, dp_.y);
   const uint4 E = make_uint4(gd.x, gd.y, dp.x, dp.y);   // the emit descriptor: {PF_* | (primary rank + 1) << 8, NH, first record, work-list position}
-  const uint32_t is_fast = CLS == 1 ? 1u : CLS == 2 ? 0u : (A.fast_flag[a] >> 31);
+  const uint32_t is_fast = CLS == 1;
   uint4 hd2 = make_uint4(0, 0, 0, 0);
   uint32_t c0 = 0, c1 = 0;
   RealCig rc;
@@ -857,10 +856,9 @@ void launch_group_desc(hipStream_t st, const DirectArgs &D) {
 void launch_expand_rows(hipStream_t st, const DirectArgs &D) {
   if (D.n_aln > 0) hipLaunchKernelGGL(k_expand_rows, dim3(grid_for_d(D.n_aln, 256)), dim3(256), 0, st, D);
 }
-// part 0: the whole work list in one launch, 1: its simple prefix [0, n_simple), 2: the rest
+// part 1: the work list's simple prefix [0, n_simple), 2: the rest
 void launch_emit_rows(hipStream_t st, const ProjectArgs &A, const DirectArgs &D, int64_t n_kept, int64_t n_simple, int part) {
   if (A.n_aln <= 0 || n_kept <= 0) return;
-  if (part == 0) { hipLaunchKernelGGL((k_emit_rows<0>), dim3(grid_for_d(n_kept, 256)), dim3(256), 0, st, A, D, (int64_t)0, n_kept); return; }
   if (part == 1) { if (n_simple > 0) hipLaunchKernelGGL((k_emit_rows<1>), dim3(grid_for_d(n_simple, 256)), dim3(256), 0, st, A, D, (int64_t)0, n_simple); }
   else if (n_kept > n_simple) hipLaunchKernelGGL((k_emit_rows<2>), dim3(grid_for_d(n_kept - n_simple, 256)), dim3(256), 0, st, A, D, n_simple, n_kept);
 }

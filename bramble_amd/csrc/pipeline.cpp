@@ -1,0 +1,952 @@
+// run_device: the HIP projection pipeline over a device-resident batch (small / speculative, direct rows, match table,
+// -S), the -S rescue DP, and what is derived from the last call's rows (detail column, wide view, counters).
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "ctx.h"
+
+// a second stream for kernels that can run beside the main one (a shape's tracebacks beside the next shape's DP; the
+// few-block emit kernel of the > 64-candidate alignments beside the work-list kernels); it and the third (aux2_stream) are
+// of normal priority (0)
+int ensure_aux_stream(br_ctx *c) {
+  if (c->ksw_stream) return BR_OK;
+  HIPCHK(hipStreamCreateWithPriority(&c->ksw_stream, hipStreamNonBlocking, 0));
+  for (auto &e : c->ksw_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto &e : c->aux_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return BR_OK;
+}
+
+// The -S rescue DP over n_prob problems.  Problems whose target fits a register array go
+// through the streamed kernels piece by piece (a piece = a range of problems whose direction tape fits the budget):
+// k_ksw_bin -> [host reads the bin sizes] -> k_ksw_plan -> k_ksw_dp per bin -> k_ksw over the leftovers -> k_ksw_trace.
+int run_ksw(br_ctx *c, hipStream_t st, const KswRun &R) {
+  if (R.n_prob <= 0) return BR_OK;
+  const uint64_t n_all = (uint64_t)R.n_prob;
+  const uint64_t qmax = std::max<uint64_t>(R.qmax, 1), tmax = std::max<uint64_t>(R.tmax, 1);
+  KswArgs K{};
+  K.n_prob = R.n_prob; K.probs = R.probs; K.results = R.results; K.seq_arena = R.seq_arena; K.clip_ops = R.clip_ops;
+  K.stats = R.stats;
+  K.raw_out = R.raw_out; K.raw_n = R.raw_n; K.max_out = R.max_out; K.raw_cap = R.raw_cap;
+  // the general kernel: per-wave scratch = direction matrix + raw traceback ops + (large targets) u / v / x / y, sized by the
+  // longest query / target it will see.  16 GB are set aside; one outlier (a 100 kb soft clip) may take more: then a single
+  // wave runs, as long as its matrix fits in 60 % of the free HBM
+  auto general = [&](uint64_t n_work, uint64_t q_hi, uint64_t t_hi, const uint32_t *list, const uint32_t *n_list) -> int {
+    q_hi = std::max<uint64_t>(q_hi, 1); t_hi = std::max<uint64_t>(t_hi, 1);
+    K.tmax = (uint32_t)t_hi;
+    K.pmat_bytes = (size_t)(((q_hi + t_hi) * t_hi + 15) & ~15ull);
+    K.raw_words = (size_t)((q_hi + t_hi + 4 + 3) & ~3ull);
+    K.scratch_per_wave = K.pmat_bytes + K.raw_words * 4 + ((4 * t_hi + 15) & ~15ull);
+    const uint64_t budget = 16ull << 30;
+    uint64_t waves = std::min<uint64_t>({(uint64_t)c->n_cu * 16, budget / K.scratch_per_wave, n_work});
+    if (waves == 0) {
+      size_t free_b = 0, total_b = 0;
+      HIPCHK(hipMemGetInfo(&free_b, &total_b));
+      if ((double)K.scratch_per_wave > 0.6 * (double)(free_b + c->fa_scratch.cap)) return BR_ERR_CAPACITY;
+      waves = 1;
+    }
+    RC(c->fa_scratch.ensure((size_t)waves * K.scratch_per_wave));
+    K.scratch = c->fa_scratch.as<uint8_t>(); K.list = list; K.n_list = n_list; K.n_waves = (int64_t)waves;
+    launch_ksw(st, K, (int)((waves + 3) / 4));
+    return BR_OK;
+  };
+  memset(c->ksw_diag, 0, sizeof(c->ksw_diag));
+  c->h_totals[24] = 0;
+  if (!c->ksw_fast) return general(n_all, qmax, tmax, nullptr, nullptr);
+
+  RC(c->ksw_raw.ensure((size_t)(R.seq_total + n_all + 1) * 4));
+  RC(c->ksw_cnt.ensure(128));
+  uint32_t *h_cnt = (uint32_t *)(c->h_totals + 16);   // 16 words of the pinned totals
+  const uint64_t tape_budget = (uint64_t)c->ksw_tape_mb << 20;
+  // groups of a bin = what is resident at once (one wave of blocks: every group runs from the first cycle)
+  uint32_t max_groups[KSW_N_BINS];
+  for (int b = 0; b < KSW_N_BINS; b++) {
+    if (!c->ksw_groups[b]) c->ksw_groups[b] = ksw_dp_resident_groups(b, c->n_cu);
+    max_groups[b] = c->ksw_groups[b];
+  }
+  std::vector<std::pair<uint64_t, uint64_t>> todo;   // [p0, p1)
+  todo.emplace_back(0, n_all);
+  while (!todo.empty()) {
+    const uint64_t p0 = todo.back().first, p1 = todo.back().second, n = p1 - p0;
+    todo.pop_back();
+    RC(c->ksw_desc.ensure((size_t)n * sizeof(KswDesc) * KSW_N_BINS));
+    RC(c->ksw_dp.ensure((size_t)n * sizeof(KswDp)));
+    RC(c->ksw_left.ensure((size_t)n * 4));
+    KswFastArgs A{};
+    A.p0 = (int64_t)p0; A.n = (int64_t)n; A.probs = R.probs; A.results = R.results; A.seq_arena = R.seq_arena;
+    A.clip_ops = R.clip_ops; A.raw_ops = c->ksw_raw.as<uint32_t>();
+    for (int b = 0; b < KSW_N_BINS; b++) A.desc[b] = c->ksw_desc.as<KswDesc>() + (size_t)b * n;
+    A.counters = c->ksw_cnt.as<uint32_t>(); A.leftover = c->ksw_left.as<uint32_t>(); A.dp = c->ksw_dp.as<KswDp>();
+    A.stats = R.stats; A.raw_out = R.raw_out; A.raw_n = R.raw_n; A.max_out = R.max_out; A.raw_cap = R.raw_cap;
+    HIPCHK(hipMemsetAsync(c->ksw_cnt.p, 0, 128, st));
+    launch_ksw_bin(st, A);
+    HIPCHK(hipMemcpyAsync(h_cnt, c->ksw_cnt.p, 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t *h_rows = (const uint64_t *)(h_cnt + 8);
+    // tape: a row = one step of a wave (512 or 1024 B); a bin's waves run (tape rows of its problems) / (groups per wave) steps when
+    // its groups stay equally busy (they share one queue), 15 % on top, and every wave rounds up to chunks and drains
+    uint64_t tape_bytes = 0, tape_fixed = 0; uint32_t n_groups_total = 0;   // tape_fixed: what every wave rounds up and drains, whatever the piece holds
+    for (int b = 0; b < KSW_N_BINS; b++) {
+      A.n_bin[b] = h_cnt[b];
+      A.n_groups[b] = std::min<uint32_t>(max_groups[b], (h_cnt[b] + 7u) / 8u);   // a group takes its problems eight at a time
+      n_groups_total += A.n_groups[b];
+      const uint64_t gpw = 64u / (uint64_t)KSW_BIN_G(b), waves = (A.n_groups[b] + gpw - 1) / gpw;
+      const uint64_t fixed = waves * (1ull * KSW_CHUNK_ROWS + KSW_BIN_W(b) + 64);
+      const uint64_t rows = h_rows[b] / gpw + h_rows[b] / gpw / 7 + fixed;
+      if (A.n_bin[b]) { tape_bytes += rows * (uint64_t)KSW_BIN_ROWBYTES(b); tape_fixed += fixed * (uint64_t)KSW_BIN_ROWBYTES(b); }
+    }
+    if (tape_bytes > tape_budget && n >= 2048) {
+      // as few pieces as fit: the part of the tape that scales with the problems over what a piece has left for it (halves
+      // when the fixed part alone nearly fills the budget); a piece that still does not fit is cut again
+      uint64_t k = 2;
+      if (tape_budget > tape_fixed + tape_fixed / 4) k = ((tape_bytes - tape_fixed) + (tape_budget - tape_fixed) - 1) / (tape_budget - tape_fixed);
+      k = std::min<uint64_t>(std::max<uint64_t>(k, 2), std::min<uint64_t>(64, n / 1024));
+      for (uint64_t i = k; i-- > 0;) todo.emplace_back(p0 + n * i / k, p0 + n * (i + 1) / k);
+      continue;
+    }
+    const uint32_t n_left = h_cnt[KSW_N_BINS];
+    c->ksw_diag[0]++;
+    for (int b = 0; b < KSW_N_BINS; b++) c->ksw_diag[1 + b] += h_cnt[b];
+    c->ksw_diag[5] += n_left; c->ksw_diag[6] = std::max<uint64_t>(c->ksw_diag[6], tape_bytes);
+    for (int b = 0; b < KSW_N_BINS; b++) c->ksw_diag[8 + b] += h_rows[b];
+    if (n_groups_total) {
+      RC(c->ksw_tape.ensure((size_t)tape_bytes + 256));
+      A.tape = c->ksw_tape.as<uint8_t>(); A.tape_cap = tape_bytes / 100 * (uint64_t)c->ksw_tape_pct;
+      // a shape's tracebacks (one lane per problem, waiting on tape lines) run on a second stream beside the next shape's
+      // DP kernel (issue-bound, one wave of registers to spare per SIMD)
+      RC(ensure_aux_stream(c));
+      for (int b = KSW_N_BINS - 1; b >= 0; b--) {     // widest shape first: the exposed last traceback is the smallest shape's
+        if (!A.n_bin[b]) continue;
+        launch_ksw_dp(st, A, b);
+        HIPCHK(hipEventRecord(c->ksw_ev[b], st));
+        HIPCHK(hipStreamWaitEvent(c->ksw_stream, c->ksw_ev[b], 0));
+        launch_ksw_trace(c->ksw_stream, A, b);
+      }
+      HIPCHK(hipEventRecord(c->ksw_ev[KSW_N_BINS], c->ksw_stream));
+    }
+    // what the arrays do not take: targets beyond the widest array, and (never seen outside tests) groups whose tape ran out
+    // (problems a wave hands back when the tape runs out come from the arrays: at most KSW_MAX_SPAN bases)
+    RC(general(n_left ? n_left : 64, std::max<uint64_t>(h_cnt[5], KSW_MAX_SPAN), std::max<uint64_t>(h_cnt[6], KSW_BIN_W(KSW_N_BINS - 1)), A.leftover, A.counters + KSW_N_BINS));
+    if (n_groups_total) HIPCHK(hipStreamWaitEvent(st, c->ksw_ev[KSW_N_BINS], 0));   // the tape and the result arrays are free again
+    // leftovers after the DP (those of the last piece; read by br_ctx_ksw_diag once the stream has been synchronised)
+    HIPCHK(hipMemcpyAsync((uint32_t *)(c->h_totals + 24), A.counters + KSW_N_BINS, 4, hipMemcpyDeviceToHost, st));
+  }
+  return BR_OK;
+}
+
+// ---- what the three pipelines share: the tables and arguments of the count pass, its launch, the match table's emit
+// pass and the end of a call ----
+static int ensure_count_tables(br_ctx *c, const br_device_batch *b) {
+  const int64_t n = b->n_aln;
+  RC(c->seg.ensure((size_t)(b->n_cigar_words + n) * sizeof(uint2)));
+  RC(c->meta.ensure((size_t)n * sizeof(AlnMeta))); RC(c->head.ensure((size_t)n * sizeof(uint4))); RC(c->head2.ensure((size_t)n * sizeof(uint4)));
+  RC(c->fast_flag.ensure((size_t)n * 4)); RC(c->ranges.ensure((size_t)n * sizeof(uint4))); RC(c->mask.ensure((size_t)n * 8));
+  RC(c->cig_base.ensure((size_t)(n + 1) * 8)); RC(c->big_list.ensure((size_t)n * 4)); RC(c->totals.ensure(16 * 8));
+  return BR_OK;
+}
+
+// (n_matches is sized by the caller)
+static ProjectArgs count_args(br_ctx *c, const DevCfg &dc, const br_device_batch *b) {
+  ProjectArgs A{};
+  A.ix = c->ix->dev; A.cfg = dc; A.n_aln = b->n_aln; A.ref_id = b->ref_id; A.cigar_off = b->cigar_off; A.cigar = b->cigar;
+  A.seg = c->seg.as<uint2>(); A.meta = c->meta.as<AlnMeta>(); A.head = c->head.as<uint4>(); A.head2 = c->head2.as<uint4>();
+  A.fast_flag = c->fast_flag.as<uint32_t>(); A.n_matches = c->n_matches.as<uint32_t>();
+  A.ranges = c->ranges.as<uint4>(); A.mask = c->mask.as<uint64_t>(); A.big_list = c->big_list.as<uint32_t>();
+  return A;
+}
+
+// the count pass: one kernel with the exon walk inline, or (split) the main kernel without it and a second one for the
+// alignments it put on A.walk_list
+static int count_pass(br_ctx *c, hipStream_t st, const ProjectArgs &A, Prof &pf, bool split) {
+  const int n_blocks = c->n_cu * c->blocks_per_cu;
+  RC(pf.begin(BR_K_COUNT));
+  launch_project(st, A, false, c->group_lanes, n_blocks, split ? 1 : 0);
+  RC(pf.end());
+  if (split) {
+    RC(pf.begin(BR_K_COUNT_WALK));
+    launch_project(st, A, false, c->group_lanes, n_blocks, 2);
+    RC(pf.end());
+  }
+  return BR_OK;
+}
+
+// the match table's emit pass over a work list of n_list entries: without the similarity filter, its simple prefix (one
+// read exon from a single M op, n_simple entries) and the rest as two launches; with it, the whole list in one
+static int emit_match_table(hipStream_t st, const ProjectArgs &A, Prof &pf, int64_t n_list, int64_t n_simple) {
+  if (!A.cfg.filter_by_similarity) {
+    RC(pf.begin(BR_K_EMIT_SIMPLE));
+    launch_emit_dense(st, A, n_list, n_simple, 1);
+    RC(pf.end());
+    RC(pf.begin(BR_K_EMIT));
+    launch_emit_dense(st, A, n_list, n_simple, 2);
+    RC(pf.end());
+  } else {
+    RC(pf.begin(BR_K_EMIT));
+    launch_emit_dense(st, A, n_list, -1, 0);
+    RC(pf.end());
+  }
+  return BR_OK;
+}
+
+// the counts of a finished call (h_totals[5..6]: unique reads, dropped reads) and what the context keeps of it; the row
+// table pointers are the caller's
+static void finish_call(br_ctx *c, const DevCfg &dc, const br_device_batch *b, br_device_rows *out, uint64_t n_matches,
+                        uint64_t n_rows, uint64_t n_pool, bool aux_cols) {
+  out->n_matches = (int64_t)n_matches; out->n_rows = (int64_t)n_rows; out->n_pool_words = (int64_t)n_pool;
+  out->total_complete = n_rows; out->total_unique = c->h_totals[5]; out->dropped_reads = c->h_totals[6];
+  out->pool = c->cig_arena.as<uint32_t>(); out->row_off = c->row_off.as<uint64_t>();
+  c->counters[6] = n_matches;
+  c->last_n_rows = (int64_t)n_rows; c->last_n_aln = b->n_aln; c->last_n_pool = (int64_t)n_pool;
+  c->last_aux_cols = aux_cols; c->wide_valid = false; c->detail_valid = false; c->last_l_qseq = b->l_qseq; c->last_long_reads = dc.long_reads;
+}
+
+// Small batches (a read-name group, the 64 groups a bramble-cli worker holds, the 100 k alignments of a reference bundle):
+// the ordinary pipeline stops three times for the host to read a total and size the next tables, and launches about
+// twenty kernels -- for 10 k alignments that is 0.3 ms of which the kernels are a fraction.  Here the tables are sized from
+// upper bounds (32 matches per alignment and the CIGAR room that goes with them), the scan totals stay on the device
+// (ProjectArgs::tot: the kernels that need a count read it there, and do nothing when a total is beyond its table), the
+// split kernels run in their single-launch forms, everything goes down ONE stream, and the host waits once, at the end.
+// A batch that does not fit the bounds (a dense locus) comes back as BR_RETRY_ORDINARY and takes the ordinary path.
+// LARGE batches take the same route when the context has projected a batch before (`big`): the tables are what earlier calls
+// left behind (grown with a quarter of headroom), the launch grids of the two emit classes and of the row kernel come from
+// the LAST call's counts scaled to this batch's size (+15 %), the kernels keep their split, two-stream forms -- and the
+// host, instead of stopping three times, checks once at the end that nothing outgrew its table or its grid.  A batch that
+// did is redone the ordinary way, which also grows the tables.
+static int run_device_small(br_ctx *c, const DevCfg &dc, const br_device_batch *b, hipStream_t st, br_device_rows *out, Prof &pf,
+                            bool keep_events, bool big) {
+  const br_index *ix = c->ix;
+  const int64_t n = b->n_aln, ng = b->n_groups;
+  const bool aux_cols = dc.filter_by_similarity != 0;
+  uint64_t cap_m = 32ull * (uint64_t)n + 8192;
+  const uint64_t per = 9ull * (uint64_t)std::min<int32_t>(std::max<int32_t>(b->max_n_cigar, 4), 64) + 12ull;   // n_real + 2 (4 n_seg + 2) <= 9 n_cigar + 12
+  uint64_t cap_c = std::min<uint64_t>(cap_m * per, 1ull << 28);
+  uint64_t cap_r = cap_m, cover_m = cap_m, cover_s = cap_m, cover_g = cap_m, cover_r = cap_m;   // tables' capacities; what the emit / row grids cover (all matches, simple class, general class, records)
+  if (big) {
+    const double f = 1.15 * (double)n / (double)std::max<int64_t>(c->hist_n, 1);
+    cover_m = (uint64_t)(f * (double)c->hist[0]) + 4096; cover_s = (uint64_t)(f * (double)c->hist[2]) + 4096; cover_r = (uint64_t)(f * (double)c->hist[3]) + 4096;
+    cover_g = (uint64_t)(f * (double)(c->hist[0] - std::min(c->hist[0], c->hist[2]))) + 4096;
+    const uint64_t need_c = (uint64_t)(f * (double)c->hist[1]) + 4096;
+    cap_m = std::min<uint64_t>({c->m_tid.cap / 4, c->m_aux.cap / 4, c->m_p.cap / 8, c->m_x.cap / 8, c->m_b.cap / 16, c->m_cigoff.cap / 8, c->m_aln.cap / 4});
+    cap_c = c->cig_arena.cap / 4;
+    cap_r = std::min<uint64_t>({c->r_rec.cap / 16, c->pk_a.cap / 16, c->pk_c.cap / 8});
+    if (aux_cols) cap_r = std::min<uint64_t>({cap_r, c->pk_sim.cap / 8, c->pk_clip.cap / 4});
+    if (cover_m > cap_m || need_c > cap_c || cover_r > cap_r) return BR_RETRY_ORDINARY;   // the tables have to grow: the ordinary path does that
+  }
+  const int64_t tiles = std::max<int64_t>(scan_tiles_for(std::max<int64_t>(n, ng) + 1), 1);
+  RC(ensure_count_tables(c, b));
+  RC(c->n_matches.ensure((size_t)n * 4)); RC(c->fast_pre.ensure((size_t)(n + 1) * 4)); RC(c->match_off.ensure((size_t)(n + 1) * 4));
+  RC(c->tile_sums.ensure((size_t)tiles * 8 * 3)); RC(c->counters_d.ensure(GD_COUNTER_WORDS * 8)); RC(c->n_big.ensure(16));
+  if (!big) {
+    RC(c->m_tid.ensure(cap_m * 4)); RC(c->m_aux.ensure(cap_m * 4)); RC(c->m_p.ensure(cap_m * sizeof(uint2))); RC(c->m_x.ensure(cap_m * sizeof(uint2)));
+    RC(c->m_b.ensure(cap_m * sizeof(uint4))); RC(c->m_cigoff.ensure(cap_m * 8)); RC(c->m_aln.ensure(cap_m * 4));
+    RC(c->cig_arena.ensure(cap_c * 4));
+  }
+  // a queued packed download of the last call (br_project_staged) may still read the row tables: small batches wait for it here;
+  // large ones keep the overlap -- their tables are not reallocated (checked above) -- and make the row scan wait instead
+  const bool rows_busy_wait = c->rows_busy_set && big && c->row_off.cap >= (size_t)(n + 1) * 8;
+  if (c->rows_busy_set && !rows_busy_wait) HIPCHK(hipEventSynchronize(c->rows_busy));
+  RC(c->n_rows.ensure((size_t)n * 4)); RC(c->row_off.ensure((size_t)(n + 1) * 8)); RC(c->aln_group.ensure((size_t)n * 4));
+  RC(c->pmask.ensure((size_t)n * 8)); RC(c->pbit.ensure((size_t)n));
+  if (!big) {
+    RC(c->r_rec.ensure(cap_m * sizeof(uint4))); RC(c->pk_a.ensure(cap_m * sizeof(uint4))); RC(c->pk_c.ensure(cap_m * sizeof(uint2)));
+    if (aux_cols) { RC(c->pk_sim.ensure(cap_m * 8)); RC(c->pk_clip.ensure(cap_m * 4)); }
+  }
+  if (!aux_cols) RC(c->pick.ensure((size_t)std::max<int64_t>(ng, 1) * 8));
+  if (big) { RC(c->walk_list.ensure((size_t)n * 4)); RC(ensure_aux_stream(c)); }
+  uint64_t *d_tot = c->totals.as<uint64_t>();
+
+  // (the per-batch counters sit behind the totals, d_tot[8..11]: one download brings both home; k_segment zeroes them and
+  // the two work-list counters, and labels the alignments with their read-name groups)
+  uint64_t *d_cnt = d_tot + 8;
+  SegExtra X{};
+  X.group_off = b->group_off; X.aln_group = c->aln_group.as<uint32_t>(); X.n_groups = ng;
+  X.zero_a = (uint64_t *)c->n_big.p; X.n_zero_a = 1; X.zero_b = d_cnt; X.n_zero_b = 4;
+  RC(pf.begin(BR_K_SEGMENT));
+  launch_segment(st, n, b->ref_id, b->ref_start, b->flags, b->xs, b->ts, b->cigar_off, b->cigar, dc, ix->n_refs,
+                 c->seg.as<uint2>(), c->meta.as<AlnMeta>(), c->head.as<uint4>(), c->head2.as<uint4>(), c->fast_flag.as<uint32_t>(), &X);
+  RC(pf.end());
+  ProjectArgs A = count_args(c, dc, b);
+  A.fast_pre = c->fast_pre.as<uint32_t>(); A.match_off = c->match_off.as<uint32_t>(); A.cig_base = c->cig_base.as<uint64_t>();
+  A.n_big = c->n_big.as<uint32_t>();
+  A.m_aln = c->m_aln.as<uint32_t>(); A.m_tid = c->m_tid.as<uint32_t>(); A.m_aux = c->m_aux.as<uint32_t>(); A.m_p = c->m_p.as<uint2>();
+  A.m_x = c->m_x.as<uint2>(); A.m_b = c->m_b.as<uint4>(); A.m_cigoff = c->m_cigoff.as<uint64_t>(); A.cig_arena = c->cig_arena.as<uint32_t>();
+  A.tot = d_tot; A.lim_m = cap_m; A.lim_c = cap_c;
+  const bool split = big && !dc.filter_by_similarity;   // (small: one kernel, the exon walk inline)
+  if (split) { A.walk_list = c->walk_list.as<uint32_t>(); A.n_walk = c->n_big.as<uint32_t>() + 1; }
+  RC(count_pass(c, st, A, pf, split));
+  ScanArgs S{};
+  S.n = n; S.src32 = c->n_matches.as<uint32_t>(); S.cigar_off = b->cigar_off; S.head = c->head.as<uint4>();
+  S.tile_sums = c->tile_sums.as<uint64_t>(); S.fast_flag = c->fast_flag.as<uint32_t>();
+  RC(pf.begin(BR_K_SCAN));
+  const bool expanded = launch_scan3(st, S, c->match_off.as<uint32_t>(), c->cig_base.as<uint64_t>(), c->fast_pre.as<uint32_t>(), d_tot + 0, &A);
+  RC(pf.end());
+  if (!expanded) {
+    RC(pf.begin(BR_K_EXPAND));
+    launch_expand(st, A);
+    RC(pf.end());
+  }
+  if (!big) {
+    RC(pf.begin(BR_K_EMIT));
+    launch_emit_dense(st, A, (int64_t)cover_m, -1, 0);          // one launch over the whole list; the kernel stops at tot[0]
+    launch_project(st, A, true, 64, std::min(c->n_cu, 64));     // alignments with > 64 candidate rows (reads *n_big)
+    RC(pf.end());
+  } else {
+    // as the ordinary path: the dense-locus kernel on the second stream beside the two classes of the work list
+    HIPCHK(hipEventRecord(c->aux_ev[0], st));
+    HIPCHK(hipStreamWaitEvent(c->ksw_stream, c->aux_ev[0], 0));
+    RC(pf.begin(BR_K_EMIT_AUX, c->ksw_stream));
+    launch_project(c->ksw_stream, A, true, 64, c->n_cu);
+    RC(pf.end());
+    HIPCHK(hipEventRecord(c->aux_ev[1], c->ksw_stream));
+    // (the grids: cover_s + cover_g entries of the two classes, or cover_m of the whole list)
+    RC(emit_match_table(st, A, pf, (int64_t)(dc.filter_by_similarity ? cover_m : cover_s + cover_g), (int64_t)cover_s));
+    HIPCHK(hipStreamWaitEvent(st, c->aux_ev[1], 0));
+  }
+
+  PairArgs P{};
+  P.n_groups = ng; P.n_aln = n; P.long_reads = dc.long_reads; P.group_off = b->group_off; P.mate_idx = b->mate_idx;
+  P.aln_group = c->aln_group.as<uint32_t>();
+  P.match_off = c->match_off.as<uint32_t>(); P.n_matches = c->n_matches.as<uint32_t>(); P.m_tid = A.m_tid; P.m_p = A.m_p; P.m_x = A.m_x; P.m_b = A.m_b;
+  P.m_cigoff = A.m_cigoff;
+  P.n_rows = c->n_rows.as<uint32_t>(); P.row_off = c->row_off.as<uint64_t>(); P.counters = d_cnt;
+  P.pmask = c->pmask.as<uint64_t>(); P.pbit = c->pbit.as<uint8_t>();
+  P.tot = d_tot; P.lim_m = cap_m; P.lim_c = cap_c; P.lim_r = std::min(cap_r, cover_r);
+  RC(pf.begin(BR_K_PAIR_COUNT));
+  launch_pair(st, P, false);
+  RC(pf.end());
+  ScanArgs S2{};
+  S2.n = n; S2.src32 = c->n_rows.as<uint32_t>(); S2.tile_sums = c->tile_sums.as<uint64_t>();
+  if (rows_busy_wait) HIPCHK(hipStreamWaitEvent(st, c->rows_busy, 0));
+  RC(pf.begin(BR_K_SCAN));
+  launch_scan(st, S2, 2, c->row_off.p, true, d_tot + 3);
+  RC(pf.end());
+  P.n_rows_total = (int64_t)P.lim_r; P.r_rec = c->r_rec.as<uint4>();
+  P.r_a = c->pk_a.as<uint4>(); P.r_c = c->pk_c.as<uint2>(); P.r_x = nullptr;
+  P.r_sim = aux_cols ? c->pk_sim.as<double>() : nullptr; P.r_clip = aux_cols ? c->pk_clip.as<int32_t>() : nullptr;
+  // a caller that wants the few rows of a small call on the host (br_project_group): the row kernel writes the packed rows
+  // and their detail column straight into pinned host memory -- no download, no second wait
+  c->rows_at_host = false;
+  if (c->rows_to_host) {
+    RC(c->g_a.resize(cap_m)); RC(c->g_c.resize(cap_m)); RC(c->g_x.resize(cap_m));
+    if (aux_cols) RC(c->g_sim.resize(cap_m));
+    P.r_a = c->g_a.p; P.r_c = c->g_c.p; P.r_x = c->g_x.p;
+    if (aux_cols) P.r_sim = c->g_sim.p;
+    c->rows_at_host = true;
+  }
+  const uint8_t *names = (b->names && b->name_off) ? b->names : nullptr;
+  if (!aux_cols) {   // the primary choice needs row_off and the pair bits only: before the records exist, its pick applied by k_rows
+    P.pick = c->pick.as<uint64_t>();
+    hipStream_t ps = st;
+    if (big) {   // ... and beside the emit pass, on the second stream
+      ps = c->ksw_stream;
+      HIPCHK(hipEventRecord(c->aux_ev[0], st));
+      HIPCHK(hipStreamWaitEvent(ps, c->aux_ev[0], 0));
+    }
+    RC(pf.begin(BR_K_PRIMARY, ps));
+    launch_primary(ps, P, b->name_off, names, false);
+    RC(pf.end());
+    if (big) HIPCHK(hipEventRecord(c->aux_ev[1], ps));
+  }
+  RC(pf.begin(BR_K_PAIR_EMIT));
+  launch_pair(st, P, true);
+  RC(pf.end());
+  if (big && !aux_cols) HIPCHK(hipStreamWaitEvent(st, c->aux_ev[1], 0));
+  if (aux_cols) {
+    RC(pf.begin(BR_K_PRIMARY));
+    launch_primary(st, P, b->name_off, names, true);
+    RC(pf.end());
+  }
+  RC(pf.begin(BR_K_ROWS));
+  launch_rows(st, P, aux_cols);
+  RC(pf.end());
+  HIPCHK(hipMemcpyAsync(c->h_totals + 32, d_tot, 12 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int k = 0; k < 4; k++) { c->h_totals[k] = c->h_totals[32 + k]; c->h_totals[4 + k] = c->h_totals[40 + k]; }
+  const uint64_t n_matches = c->h_totals[0], n_cig_arena = c->h_totals[1], n_simple = c->h_totals[2], n_rows = c->h_totals[3];
+  // nothing was written past a table or left out by a grid: the kernels checked the same totals and did nothing then
+  if (n_matches > cap_m || n_cig_arena > cap_c || n_rows > P.lim_r) return BR_RETRY_ORDINARY;
+  if (big && (!dc.filter_by_similarity ? (n_simple > cover_s || n_matches - n_simple > cover_g) : n_matches > cover_m)) return BR_RETRY_ORDINARY;
+  c->hist_simf = dc.filter_by_similarity != 0;
+  c->hist_n = n; c->hist[0] = n_matches; c->hist[1] = n_cig_arena; c->hist[2] = n_simple; c->hist[3] = n_rows;
+  if (!keep_events) RC(pf.collect());
+  if (c->h_totals[7]) return BR_ERR_UNSUPPORTED;  // a rewritten CIGAR with more than 2^24 - 1 ops
+  finish_call(c, dc, b, out, n_matches, n_rows, n_cig_arena, aux_cols);
+  out->a = (const br_row_a *)P.r_a; out->cigar = (const uint64_t *)P.r_c; out->x = (const br_row_x *)P.r_x;
+  out->similarity_score = aux_cols ? P.r_sim : nullptr;
+  out->clip_score = aux_cols ? c->pk_clip.as<int32_t>() : nullptr;
+  return BR_OK;
+}
+
+// Direct rows: presets without the similarity filter and without -S (every short-read preset; long reads with the filter
+// switched off).  segment -> count -> [k_pair_mask || k_big<0> + k_pair_big] -> k_scan5 (one host wait: sizes) ->
+// k_expand_rows -> k_emit_rows (|| k_big<1>): the packed rows are written once, by the lane that computes the match; the
+// match table, the per-record r_rec, k_pair<true> and k_rows do not exist on this path.  On the second stream: the name
+// seeds of the primary tie-break (beside segment + count), the big alignments' pairing (beside k_pair_mask), k_group_desc
+// (beside the scan), k_big<1> (beside the emit kernels).
+static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch *b, hipStream_t st, br_device_rows *out, Prof &pf,
+                             bool keep_events) {
+  const br_index *ix = c->ix;
+  const int64_t n = b->n_aln, ng = b->n_groups;
+  const int64_t tiles = std::max<int64_t>(scan_tiles_for(std::max<int64_t>(n, ng) + 1), 1);
+  RC(ensure_count_tables(c, b));
+  RC(c->n_matches.ensure((size_t)n * 4 + 16));   // (+ 16: k_group_desc reads four elements at a time)
+  RC(c->tile_sums.ensure((size_t)tiles * 8 * 5));   // (k_scan5: five sums per tile)
+  // every small counter of the step in one block, zeroed by one fill at the start: [0, GD_COUNTER_WORDS) the four counters + k_group_desc's
+  // slots, then the side arena's two words, then n_big | n_walk | pm_n | -
+  RC(c->counters_d.ensure((GD_COUNTER_WORDS + 4) * 8));
+  uint64_t *const dz = c->counters_d.as<uint64_t>();
+  uint32_t *const dz_nbig = (uint32_t *)(dz + GD_COUNTER_WORDS + 2);
+  RC(c->walk_list.ensure((size_t)n * 4));
+  RC(c->aln_group.ensure((size_t)n * 4)); RC(c->n_rows.ensure((size_t)n * 4 + 16)); RC(c->pbit.ensure((size_t)n + 16));
+  RC(c->d_fm.ensure((size_t)n * sizeof(uint2) + (size_t)(n / 62 + 2) * 4));   // + the window list of k_pair_mask
+  RC(c->d_nkept.ensure((size_t)n * 4)); RC(c->d_desc.ensure((size_t)n * sizeof(uint4)));
+  RC(c->d_hi0.ensure((size_t)n * 4)); RC(c->d_clspos.ensure((size_t)n * 4)); RC(c->d_rnd.ensure((size_t)std::max<int64_t>(ng, 1) * 8));
+  if (c->d_side_cap == 0) c->d_side_cap = std::max<uint64_t>((uint64_t)n / 4, 1u << 20);
+  RC(c->d_side.ensure((size_t)c->d_side_cap * sizeof(uint2)));
+  // (a buffer that a queued packed download still reads must not be reallocated under it)
+  if (c->rows_busy_set && c->row_off.cap < (size_t)(n + 1) * 8) HIPCHK(hipEventSynchronize(c->rows_busy));
+  RC(c->row_off.ensure((size_t)(n + 1) * 8));
+  RC(ensure_aux_stream(c));
+  hipStream_t ax = c->ksw_stream;
+  uint64_t *d_tot = c->totals.as<uint64_t>();
+
+  ProjectArgs A = count_args(c, dc, b);
+  A.n_big = dz_nbig; A.walk_list = c->walk_list.as<uint32_t>(); A.n_walk = dz_nbig + 1;
+  const bool have_names = b->names && b->name_off;
+  DirectArgs D{};
+  D.n_aln = n; D.n_groups = ng; D.group_off = b->group_off; D.aln_group = c->aln_group.as<uint32_t>(); D.mate_idx = b->mate_idx;
+  D.n_matches = c->n_matches.as<uint32_t>(); D.mask = c->mask.as<uint64_t>(); D.ranges = c->ranges.as<uint4>();
+  D.fast_flag = c->fast_flag.as<uint32_t>(); D.s_tid = ix->dev.s_tid; D.big_list = A.big_list; D.n_big = A.n_big;
+  D.fm = c->d_fm.as<uint2>(); D.pm_list = (uint32_t *)(c->d_fm.as<uint2>() + n); D.pm_n = dz_nbig + 2; D.n_kept = c->d_nkept.as<uint32_t>(); D.n_rows = c->n_rows.as<uint32_t>(); D.pflag = c->pbit.as<uint8_t>();
+  D.side = c->d_side.as<uint2>(); D.side_cap = c->d_side_cap; D.side_used = (unsigned long long *)(dz + GD_COUNTER_WORDS);
+  D.cls_pos = c->d_clspos.as<uint32_t>(); D.cig_base = c->cig_base.as<uint64_t>(); D.row_off = c->row_off.as<uint64_t>();
+  D.name_off = have_names ? b->name_off : nullptr; D.names = have_names ? b->names : nullptr; D.rnd0 = c->d_rnd.as<uint64_t>();
+  D.gd = c->d_desc.as<uint2>(); D.dpos = c->d_desc.as<uint2>() + n; D.hi0 = c->d_hi0.as<uint32_t>(); D.counters = c->counters_d.as<uint64_t>(); D.tot = d_tot;
+
+  if (!c->aux2_stream) { HIPCHK(hipStreamCreateWithPriority(&c->aux2_stream, hipStreamNonBlocking, 0)); HIPCHK(hipEventCreateWithFlags(&c->aux2_ev, hipEventDisableTiming)); }
+  hipStream_t ax2 = c->aux2_stream;
+  HIPCHK(hipMemsetAsync(dz, 0, (GD_COUNTER_WORDS + 4) * 8, st));
+  HIPCHK(hipEventRecord(c->aux_ev[0], st));
+  HIPCHK(hipStreamWaitEvent(ax, c->aux_ev[0], 0));
+  // a1/a2/a6: CIGAR -> read exons; a3-a8, a11-a14 (survival only): the count pass
+  RC(pf.begin(BR_K_SEGMENT));
+  launch_segment(st, n, b->ref_id, b->ref_start, b->flags, b->xs, b->ts, b->cigar_off, b->cigar, dc, ix->n_refs,
+                 c->seg.as<uint2>(), c->meta.as<AlnMeta>(), c->head.as<uint4>(), c->head2.as<uint4>(), c->fast_flag.as<uint32_t>());
+  RC(pf.end());
+  RC(pf.begin(BR_K_GROUP_IDS));
+  launch_group_ids(st, ng, b->group_off, c->aln_group.as<uint32_t>());
+  RC(pf.end());
+  RC(count_pass(c, st, A, pf, true));
+  // a packed download of the previous call may still be reading row_off / the row tables (br_project_staged)
+  if (c->rows_busy_set) { HIPCHK(hipStreamWaitEvent(st, c->rows_busy, 0)); }
+  // a16 (src/mates.cpp:150-261) on the survivor sets, then placement
+  const int big_blocks = c->n_cu * 4;
+  uint64_t kept = 0, arena = 0, n_simple = 0, n_rows = 0, n_raw = 0;
+  bool expanded_ahead = false;
+  // third stream: the name seeds need nothing but the names, and their 156 dependent multiplies per read name are pure ALU work:
+  // beside k_pair_mask, which waits on LDS and memory most of the time
+  if (have_names) {
+    HIPCHK(hipEventRecord(c->aux_ev[7], st));
+    HIPCHK(hipStreamWaitEvent(ax2, c->aux_ev[7], 0));
+    RC(pf.begin(BR_K_NAME_SEED, ax2));
+    launch_name_seed(ax2, D);
+    RC(pf.end());
+    HIPCHK(hipEventRecord(c->aux2_ev, ax2));
+  }
+  for (int attempt = 0;; attempt++) {
+    if (attempt) {   // (the first attempt's counters were zeroed with everything else at the start)
+      HIPCHK(hipMemsetAsync(dz, 0, (GD_COUNTER_WORDS + 2) * 8, st));
+      HIPCHK(hipMemsetAsync(D.pm_n, 0, 4, st));
+    }
+    HIPCHK(hipEventRecord(c->aux_ev[1], st));
+    HIPCHK(hipStreamWaitEvent(ax, c->aux_ev[1], 0));
+    RC(pf.begin(BR_K_PAIR_BIG, ax));
+    launch_big_collect(ax, A, D, big_blocks);
+    launch_pair_big(ax, D, big_blocks);
+    RC(pf.end());
+    HIPCHK(hipEventRecord(c->aux_ev[2], ax));
+    RC(pf.begin(BR_K_PAIR_MASK));
+    launch_pair_mask(st, D, c->n_cu * 2);
+    RC(pf.end());
+    HIPCHK(hipStreamWaitEvent(st, c->aux_ev[2], 0));
+    // NH / HI / primary per read name on the second stream beside the scan
+    HIPCHK(hipEventRecord(c->aux_ev[3], st));
+    HIPCHK(hipStreamWaitEvent(ax, c->aux_ev[3], 0));
+    if (have_names) HIPCHK(hipStreamWaitEvent(ax, c->aux2_ev, 0));
+    RC(pf.begin(BR_K_GROUP_DESC, ax));
+    launch_group_desc(ax, D);
+    RC(pf.end());
+    HIPCHK(hipEventRecord(c->aux_ev[4], ax));
+    RC(pf.begin(BR_K_SCAN));
+    launch_scan5(st, D, c->tile_sums.as<uint64_t>(), d_tot);
+    RC(pf.end());
+    // the work list goes out at once, into the list the last call left (it checks the total against that room on the
+    // device): it runs while the host waits for the totals, wakes up and sizes the row tables
+    expanded_ahead = false;
+    if (c->m_aln.cap >= 4) {
+      D.m_aln = c->m_aln.as<uint32_t>(); D.m_aln_cap = c->m_aln.cap / 4;
+      RC(pf.begin(BR_K_EXPAND_ROWS));
+      launch_expand_rows(st, D);
+      RC(pf.end());
+      expanded_ahead = true;
+    }
+    HIPCHK(hipMemcpyAsync(c->h_totals, d_tot, 5 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_totals + 8, dz + GD_COUNTER_WORDS, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (c->h_totals[9]) {   // the side arena of the > 64-candidate alignments ran out: grow it to what was asked for, repeat
+      if (attempt >= 3) return BR_ERR_CAPACITY;
+      HIPCHK(hipEventSynchronize(c->aux_ev[4]));
+      c->d_side_cap = c->h_totals[8] + c->h_totals[8] / 4 + 4096;
+      RC(c->d_side.ensure((size_t)c->d_side_cap * sizeof(uint2)));
+      D.side = c->d_side.as<uint2>(); D.side_cap = c->d_side_cap;
+      continue;
+    }
+    kept = c->h_totals[0]; arena = c->h_totals[1]; n_simple = c->h_totals[2]; n_rows = c->h_totals[3]; n_raw = c->h_totals[4];
+    break;
+  }
+  if (n_raw >= 0xffffffffull || kept >= 0xffffffffull) return BR_ERR_CAPACITY;
+  if (kept != n_rows) return BR_ERR_HIP;   // (every kept match is one record: the pairing kernels disagree with themselves)
+
+  const size_t nr = (size_t)std::max<uint64_t>(n_rows, 1);
+  if (c->rows_busy_set && (c->pk_a.cap < nr * sizeof(uint4) || c->pk_c.cap < nr * sizeof(uint2))) HIPCHK(hipEventSynchronize(c->rows_busy));
+  RC(c->pk_a.ensure(nr * sizeof(uint4))); RC(c->pk_c.ensure(nr * sizeof(uint2)));
+  if (expanded_ahead && kept > D.m_aln_cap) expanded_ahead = false;   // (the kernel saw the same and did nothing)
+  RC(c->m_aln.ensure(nr * 4)); RC(c->cig_arena.ensure((size_t)std::max<uint64_t>(arena, 1) * 4));
+  const bool with_x = c->want_x;
+  if (with_x) {
+    if (c->rows_busy_set && c->pk_x.cap < nr * sizeof(uint4)) HIPCHK(hipEventSynchronize(c->rows_busy));
+    RC(c->pk_x.ensure(nr * sizeof(uint4)));
+  }
+  A.cig_arena = c->cig_arena.as<uint32_t>();
+  D.m_aln = c->m_aln.as<uint32_t>(); D.r_a = c->pk_a.as<uint4>(); D.r_c = c->pk_c.as<uint2>(); D.r_x = with_x ? c->pk_x.as<uint4>() : nullptr;
+  D.m_aln_cap = 0;
+  if (kept) {
+    if (!expanded_ahead) {
+      RC(pf.begin(BR_K_EXPAND_ROWS));
+      launch_expand_rows(st, D);
+      RC(pf.end());
+    }
+    HIPCHK(hipStreamWaitEvent(st, c->aux_ev[4], 0));   // k_group_desc: the descriptors' first halves
+    HIPCHK(hipEventRecord(c->aux_ev[5], st));
+    HIPCHK(hipStreamWaitEvent(ax, c->aux_ev[5], 0));
+    RC(pf.begin(BR_K_BIG_EMIT, ax));
+    launch_big_emit(ax, A, D, big_blocks);
+    RC(pf.end());
+    HIPCHK(hipEventRecord(c->aux_ev[6], ax));
+    RC(pf.begin(BR_K_EMIT_ROWS_SIMPLE));
+    launch_emit_rows(st, A, D, (int64_t)kept, (int64_t)n_simple, 1);
+    RC(pf.end());
+    RC(pf.begin(BR_K_EMIT_ROWS));
+    launch_emit_rows(st, A, D, (int64_t)kept, (int64_t)n_simple, 2);
+    RC(pf.end());
+    HIPCHK(hipStreamWaitEvent(st, c->aux_ev[6], 0));
+  } else {
+    HIPCHK(hipStreamWaitEvent(st, c->aux_ev[4], 0));
+  }
+  HIPCHK(hipMemcpyAsync(c->h_totals + 192, c->counters_d.p, GD_COUNTER_WORDS * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (!keep_events) RC(pf.collect());
+  for (int k = 0; k < 4; k++) c->h_totals[4 + k] = c->h_totals[192 + k];
+  for (int k = 0; k < GD_SLOTS; k++) { c->h_totals[5] += c->h_totals[192 + GD_SLOT0 + k * GD_SLOT_STRIDE]; c->h_totals[6] += c->h_totals[192 + GD_SLOT0 + k * GD_SLOT_STRIDE + 1]; }
+  if (c->h_totals[7]) return BR_ERR_UNSUPPORTED;  // a rewritten CIGAR with more than 2^24 - 1 ops, or NH beyond 28 bits
+  c->hist_n = 0;   // (nothing a later speculative launch of the match-table path could be sized from)
+  finish_call(c, dc, b, out, n_raw, n_rows, arena, false);
+  out->a = (const br_row_a *)c->pk_a.p; out->cigar = (const uint64_t *)c->pk_c.p; out->x = with_x ? (const br_row_x *)c->pk_x.p : nullptr;
+  out->similarity_score = nullptr; out->clip_score = nullptr;
+  c->detail_valid = with_x;
+  c->last_direct = true; c->dA = A; c->dD = D; c->d_kept = (int64_t)kept; c->d_simple = (int64_t)n_simple;
+  return BR_OK;
+}
+
+// The HIP pipeline over a device-resident batch: small and speculative batches (run_device_small), direct rows
+// (run_device_direct), or the match table below (presets with the similarity filter, -S, direct_rows = 0).
+int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStream_t st, br_device_rows *out, bool keep_events) {
+  const br_index *ix = c->ix;
+  memset(out, 0, sizeof(*out));
+  DevCfg dc;
+  RC(make_devcfg(cfg, dc));
+  // -S only changes long-read runs (src/evaluate.cpp:916-919,939)
+  const bool fa_mode = dc.use_fasta && dc.long_reads;
+  if (fa_mode && (!ix->has_seq || !b->seq_src || !b->seq_off || !b->seqs)) return BR_ERR_INVALID_ARG;
+  int64_t n = b->n_aln, ng = b->n_groups;
+  if (n < 0 || ng < 0 || n >= 0x7fffffffll || b->n_cigar_words >= 0xffffffffll - n) return BR_ERR_CAPACITY;
+  HIPCHK(hipSetDevice(ix->device));
+  Prof pf{c, st};
+  if (!keep_events) c->events_used = 0;
+  out->total_processed = (uint64_t)n;
+  c->last_n_rows = 0; c->last_n_aln = n; c->last_n_pool = 0; c->wide_valid = false; c->last_aux_cols = false; c->last_direct = false;
+  c->last_l_qseq = b->l_qseq; c->last_long_reads = dc.long_reads;
+  if (n == 0) { pf.collect(); return BR_OK; }
+  if (!fa_mode && c->small_batch && ix->dev.n_rows != 0) {
+    // small batches always; large ones when an earlier call left tables and counts to predict from (same preset class)
+    const bool small = n <= c->small_n;
+    // (up to speculate_n alignments: at 20 M alignments the three waits are 2 % of the step and the 15 % of empty blocks in
+    // the predicted grids cost as much, profiles/r03/ab_speculate.log; at 0.1-1 M alignments the step gets 6-13 % shorter)
+    const bool big = !small && n <= c->speculate_n && c->speculate && c->hist_n > 0 && c->hist_simf == (dc.filter_by_similarity != 0);
+    if (small || big) {
+      const int rc = run_device_small(c, dc, b, st, out, pf, keep_events, big);
+      if (rc != BR_RETRY_ORDINARY) return rc;
+      if (!keep_events) c->events_used = 0;
+    }
+  }
+
+  if (!fa_mode && !dc.filter_by_similarity && c->direct_rows) return run_device_direct(c, dc, b, st, out, pf, keep_events);
+
+  int64_t tiles = std::max<int64_t>(scan_tiles_for(std::max<int64_t>(n, ng) + 1), 1);
+  RC(ensure_count_tables(c, b));
+  RC(c->n_matches.ensure((size_t)n * 4)); RC(c->fast_pre.ensure((size_t)(n + 1) * 4)); RC(c->match_off.ensure((size_t)(n + 1) * 4));
+  RC(c->tile_sums.ensure((size_t)tiles * 8 * 3)); RC(c->counters_d.ensure(4 * 8));
+  RC(c->n_big.ensure(16)); RC(c->walk_list.ensure((size_t)n * 4));
+  uint64_t *d_tot = c->totals.as<uint64_t>();
+
+  // a1/a2/a6: CIGAR -> read exons
+  RC(pf.begin(BR_K_SEGMENT));
+  launch_segment(st, n, b->ref_id, b->ref_start, b->flags, b->xs, b->ts, b->cigar_off, b->cigar, dc, ix->n_refs,
+                 c->seg.as<uint2>(), c->meta.as<AlnMeta>(), c->head.as<uint4>(), c->head2.as<uint4>(),
+                 c->fast_flag.as<uint32_t>());
+  RC(pf.end());
+  ProjectArgs A = count_args(c, dc, b);
+  A.fast_pre = c->fast_pre.as<uint32_t>(); A.match_off = c->match_off.as<uint32_t>(); A.cig_base = c->cig_base.as<uint64_t>();
+  HIPCHK(hipMemsetAsync(c->n_big.p, 0, 8, st));
+  A.n_big = c->n_big.as<uint32_t>(); A.walk_list = c->walk_list.as<uint32_t>(); A.n_walk = c->n_big.as<uint32_t>() + 1;
+  int n_blocks = c->n_cu * c->blocks_per_cu;
+  ScanArgs S{};
+  S.n = n; S.src32 = c->n_matches.as<uint32_t>(); S.cigar_off = b->cigar_off; S.head = c->head.as<uint4>();
+  S.tile_sums = c->tile_sums.as<uint64_t>(); S.fast_flag = c->fast_flag.as<uint32_t>();
+  FaArgs F{};
+  if (!fa_mode) {
+    RC(count_pass(c, st, A, pf, !dc.filter_by_similarity));
+    RC(pf.begin(BR_K_SCAN));
+    launch_scan3(st, S, c->match_off.as<uint32_t>(), c->cig_base.as<uint64_t>(), c->fast_pre.as<uint32_t>(), d_tot + 0);
+    RC(pf.end());
+  } else {
+    // rescue planning -> ksw2 DP -> count with the rescue results
+    RC(c->fa_n_prob.ensure((size_t)n * 4)); RC(c->fa_seq_bytes.ensure((size_t)n * 4));
+    RC(c->fa_prob_off.ensure((size_t)(n + 1) * 4)); RC(c->fa_seqarena_off.ensure((size_t)(n + 1) * 8));
+    RC(c->fa_ideal_cap.ensure((size_t)n * 4)); RC(c->fa_want.ensure((size_t)n * 16));
+    F.seq_src = b->seq_src; F.seq_off = b->seq_off; F.seqs = b->seqs;
+    F.n_prob = c->fa_n_prob.as<uint32_t>(); F.seq_bytes = c->fa_seq_bytes.as<uint32_t>();
+    F.prob_off = c->fa_prob_off.as<uint32_t>(); F.seqarena_off = c->fa_seqarena_off.as<uint64_t>();
+    F.ideal_cap = c->fa_ideal_cap.as<uint32_t>(); F.want_l = c->fa_want.as<uint64_t>(); F.want_r = F.want_l + n;
+    RC(pf.begin(BR_K_COUNT));
+    launch_project_fa(st, A, F, 0, n_blocks);
+    RC(pf.end());
+    ScanArgs SP{}; SP.n = n; SP.src32 = F.n_prob; SP.tile_sums = c->tile_sums.as<uint64_t>();
+    ScanArgs SB{}; SB.n = n; SB.src32 = F.seq_bytes; SB.tile_sums = c->tile_sums.as<uint64_t>();
+    RC(pf.begin(BR_K_SCAN));
+    launch_scan(st, SP, 2, c->fa_prob_off.p, false, d_tot + 4);
+    launch_scan(st, SB, 2, c->fa_seqarena_off.p, true, d_tot + 5);
+    RC(pf.end());
+    HIPCHK(hipMemcpyAsync(c->h_totals + 4, d_tot + 4, 2 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    uint64_t n_prob = c->h_totals[4], seq_total = c->h_totals[5];
+    RC(c->fa_stats.ensure(16));
+    HIPCHK(hipMemsetAsync(c->fa_stats.p, 0, 16, st));
+    c->rescue_stats[0] = n_prob; c->rescue_stats[1] = 0; c->rescue_stats[2] = 0; c->rescue_stats[3] = seq_total;
+    if (n_prob >= 0xffffffffull) return BR_ERR_CAPACITY;
+    RC(c->fa_probs.ensure(std::max<size_t>(n_prob, 1) * ksw_prob_bytes()));
+    RC(c->fa_results.ensure(std::max<size_t>(n_prob, 1) * ksw_res_bytes()));
+    RC(c->fa_seq_arena.ensure((size_t)seq_total + 1024));   // the streamed DP reads whole dwords past a problem's last base
+    RC(c->fa_clip_ops.ensure((std::max<size_t>(seq_total + n_prob, 1)) * 4));
+    RC(c->fa_srcs.ensure(std::max<size_t>(n_prob, 1) * sizeof(FaSrc)));
+    F.probs = (KswProb *)c->fa_probs.p; F.results = (KswRes *)c->fa_results.p; F.srcs = c->fa_srcs.as<FaSrc>();
+    F.seq_arena = c->fa_seq_arena.as<uint8_t>(); F.clip_ops = c->fa_clip_ops.as<uint32_t>();
+    if (n_prob) {
+      RC(pf.begin(BR_K_COUNT));
+      launch_project_fa(st, A, F, 1, n_blocks);
+      launch_fa_fill(st, A, F, (int64_t)n_prob);
+      RC(pf.end());
+      uint64_t qmax = (uint64_t)std::max(b->max_soft_clip, 0) + std::max(dc.max_clip, dc.max_junc_ins);
+      KswRun R{};
+      R.n_prob = (int64_t)n_prob; R.probs = F.probs; R.results = F.results; R.seq_arena = F.seq_arena; R.clip_ops = F.clip_ops;
+      R.seq_total = seq_total; R.qmax = qmax; R.tmax = qmax + 40; R.stats = c->fa_stats.as<uint64_t>();
+      RC(pf.begin(BR_K_KSW));
+      RC(run_ksw(c, st, R));
+      RC(pf.end());
+      HIPCHK(hipMemcpyAsync(c->h_totals + 8, c->fa_stats.p, 16, hipMemcpyDeviceToHost, st));
+    }
+    RC(pf.begin(BR_K_COUNT));
+    launch_project_fa(st, A, F, 2, n_blocks);
+    RC(pf.end());
+    S.ideal_cap = F.ideal_cap;
+    RC(pf.begin(BR_K_SCAN));
+    launch_scan3(st, S, c->match_off.as<uint32_t>(), c->cig_base.as<uint64_t>(), c->fast_pre.as<uint32_t>(), d_tot + 0);
+    RC(pf.end());
+  }
+  HIPCHK(hipMemcpyAsync(c->h_totals, d_tot, 3 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t n_matches = c->h_totals[0], n_cig_arena = c->h_totals[1];
+  const int64_t n_simple = fa_mode ? -1 : (int64_t)c->h_totals[2];  // matches of the single-M class (first in the emit list)
+  if (n_matches >= 0xffffffffull) return BR_ERR_CAPACITY;
+
+  size_t nm = (size_t)std::max<uint64_t>(n_matches, 1);
+  RC(c->m_tid.ensure(nm * 4)); RC(c->m_aux.ensure(nm * 4)); RC(c->m_p.ensure(nm * sizeof(uint2))); RC(c->m_x.ensure(nm * sizeof(uint2)));
+  RC(c->m_b.ensure(nm * sizeof(uint4))); RC(c->m_cigoff.ensure(nm * 8)); RC(c->m_aln.ensure(nm * 4));
+  A.m_aln = c->m_aln.as<uint32_t>();
+  RC(c->cig_arena.ensure((size_t)std::max<uint64_t>(n_cig_arena, 1) * 4));
+  A.m_tid = c->m_tid.as<uint32_t>(); A.m_aux = c->m_aux.as<uint32_t>(); A.m_p = c->m_p.as<uint2>(); A.m_x = c->m_x.as<uint2>();
+  A.m_b = c->m_b.as<uint4>(); A.m_cigoff = c->m_cigoff.as<uint64_t>(); A.cig_arena = c->cig_arena.as<uint32_t>();
+  if (n_matches) {
+    if (fa_mode) {
+      // the work list + one lane per match for alignments with at most 64 candidate rows, k_project_fa<3> for the others
+      RC(pf.begin(BR_K_EXPAND));
+      launch_expand(st, A);
+      RC(pf.end());
+      RC(pf.begin(BR_K_EMIT));
+      launch_project_fa(st, A, F, 3, n_blocks);
+      launch_emit_dense_fa(st, A, F, (int64_t)n_matches);
+      RC(pf.end());
+    } else {
+      // alignments with > 64 candidate rows only: a few long-running blocks, on the second stream beside the work list
+      RC(ensure_aux_stream(c));
+      HIPCHK(hipEventRecord(c->aux_ev[0], st));
+      HIPCHK(hipStreamWaitEvent(c->ksw_stream, c->aux_ev[0], 0));
+      RC(pf.begin(BR_K_EMIT_AUX, c->ksw_stream));
+      launch_project(c->ksw_stream, A, true, 64, c->n_cu);
+      RC(pf.end());
+      HIPCHK(hipEventRecord(c->aux_ev[1], c->ksw_stream));
+      RC(pf.begin(BR_K_EXPAND));
+      launch_expand(st, A);
+      RC(pf.end());
+      RC(emit_match_table(st, A, pf, (int64_t)n_matches, n_simple));
+      HIPCHK(hipStreamWaitEvent(st, c->aux_ev[1], 0));
+    }
+  }
+
+  // a16/a17: pairing + NH -> the packed row table
+  // (a buffer that a queued packed download still reads must not be reallocated under it)
+  if (c->rows_busy_set && c->row_off.cap < (size_t)(n + 1) * 8) HIPCHK(hipEventSynchronize(c->rows_busy));
+  RC(c->n_rows.ensure((size_t)n * 4)); RC(c->row_off.ensure((size_t)(n + 1) * 8)); RC(c->aln_group.ensure((size_t)n * 4));
+  RC(pf.begin(BR_K_GROUP_IDS));
+  launch_group_ids(st, ng, b->group_off, c->aln_group.as<uint32_t>());
+  RC(pf.end());
+  HIPCHK(hipMemsetAsync(c->counters_d.p, 0, 4 * 8, st));
+  PairArgs P{};
+  P.n_groups = ng; P.n_aln = n; P.long_reads = dc.long_reads; P.group_off = b->group_off; P.mate_idx = b->mate_idx;
+  P.aln_group = c->aln_group.as<uint32_t>();
+  P.match_off = c->match_off.as<uint32_t>(); P.n_matches = c->n_matches.as<uint32_t>(); P.m_tid = A.m_tid; P.m_p = A.m_p; P.m_x = A.m_x; P.m_b = A.m_b;
+  P.m_cigoff = A.m_cigoff;
+  P.n_rows = c->n_rows.as<uint32_t>();
+  P.row_off = c->row_off.as<uint64_t>(); P.counters = c->counters_d.as<uint64_t>();
+  RC(c->pmask.ensure((size_t)n * 8)); P.pmask = c->pmask.as<uint64_t>();
+  RC(c->pbit.ensure((size_t)n)); P.pbit = c->pbit.as<uint8_t>();
+  RC(pf.begin(BR_K_PAIR_COUNT));
+  launch_pair(st, P, false);
+  RC(pf.end());
+  ScanArgs S2{};
+  S2.n = n; S2.src32 = c->n_rows.as<uint32_t>(); S2.tile_sums = c->tile_sums.as<uint64_t>();
+  // a packed download of the previous call may still be reading row_off / the row tables (br_project_staged)
+  if (c->rows_busy_set) { HIPCHK(hipStreamWaitEvent(st, c->rows_busy, 0)); }
+  RC(pf.begin(BR_K_SCAN));
+  launch_scan(st, S2, 2, c->row_off.p, true, d_tot + 2);
+  RC(pf.end());
+  HIPCHK(hipMemcpyAsync(c->h_totals + 2, d_tot + 2, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t n_rows = c->h_totals[2];
+
+  const size_t nr = (size_t)std::max<uint64_t>(n_rows, 1);
+  // clip score / similarity score columns exist only when the preset filters by similarity (long reads): else all zero
+  const bool aux_cols = dc.filter_by_similarity != 0;
+  if (c->rows_busy_set && (c->pk_a.cap < nr * sizeof(uint4) || (aux_cols && (c->pk_sim.cap < nr * 8 || c->pk_clip.cap < nr * 4))))
+    HIPCHK(hipEventSynchronize(c->rows_busy));
+  RC(c->r_rec.ensure(nr * sizeof(uint4)));
+  RC(c->pk_a.ensure(nr * sizeof(uint4))); RC(c->pk_c.ensure(nr * sizeof(uint2)));
+  if (aux_cols) { RC(c->pk_sim.ensure(nr * 8)); RC(c->pk_clip.ensure(nr * 4)); }
+  P.n_rows_total = (int64_t)n_rows; P.r_rec = c->r_rec.as<uint4>();
+  P.r_a = c->pk_a.as<uint4>(); P.r_c = c->pk_c.as<uint2>(); P.r_x = nullptr;
+  P.r_sim = aux_cols ? c->pk_sim.as<double>() : nullptr; P.r_clip = aux_cols ? c->pk_clip.as<int32_t>() : nullptr;
+  // presets without scores: the primary choice (ALU: the mt19937_64 seeding chain) needs row_off and the pair bits only,
+  // so it runs on the second stream beside the emit pass of k_pair and leaves its choice for k_rows
+  const bool split_primary = !aux_cols;
+  if (split_primary) {
+    RC(ensure_aux_stream(c));
+    RC(c->pick.ensure((size_t)std::max<int64_t>(ng, 1) * 8)); P.pick = c->pick.as<uint64_t>();
+    HIPCHK(hipEventRecord(c->aux_ev[0], st));
+    HIPCHK(hipStreamWaitEvent(c->ksw_stream, c->aux_ev[0], 0));
+    RC(pf.begin(BR_K_PRIMARY, c->ksw_stream));
+    launch_primary(c->ksw_stream, P, b->name_off, (b->names && b->name_off) ? b->names : nullptr, false);  // + per-group counters
+    RC(pf.end());
+    HIPCHK(hipEventRecord(c->aux_ev[1], c->ksw_stream));
+  }
+  if (n_rows) {
+    RC(pf.begin(BR_K_PAIR_EMIT));
+    launch_pair(st, P, true);
+    RC(pf.end());
+  }
+  if (split_primary) HIPCHK(hipStreamWaitEvent(st, c->aux_ev[1], 0));
+  else {
+    RC(pf.begin(BR_K_PRIMARY));
+    launch_primary(st, P, b->name_off, (b->names && b->name_off) ? b->names : nullptr, aux_cols);  // + per-group counters
+    RC(pf.end());
+  }
+  if (n_rows) {
+    RC(pf.begin(BR_K_ROWS));
+    launch_rows(st, P, aux_cols);
+    RC(pf.end());
+  }
+  HIPCHK(hipMemcpyAsync(c->h_totals + 4, c->counters_d.p, 4 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (!keep_events) RC(pf.collect());
+  if (c->h_totals[7]) return BR_ERR_UNSUPPORTED;  // a rewritten CIGAR with more than 2^24 - 1 ops
+  if (fa_mode && c->rescue_stats[0]) { c->rescue_stats[1] = c->h_totals[8]; c->rescue_stats[2] = c->h_totals[9]; }
+
+  // what a later large batch is predicted from (run_device_small, big)
+  c->hist_n = n; c->hist[0] = n_matches; c->hist[1] = n_cig_arena; c->hist[2] = n_simple >= 0 ? (uint64_t)n_simple : 0; c->hist[3] = n_rows;
+  c->hist_simf = dc.filter_by_similarity != 0;
+  if (fa_mode) c->hist_n = 0;
+  finish_call(c, dc, b, out, n_matches, n_rows, n_cig_arena, aux_cols);
+  out->a = (const br_row_a *)c->pk_a.p; out->cigar = (const uint64_t *)c->pk_c.p; out->x = nullptr;   // br_device_rows_detail
+  out->similarity_score = aux_cols ? c->pk_sim.as<double>() : nullptr;
+  out->clip_score = aux_cols ? c->pk_clip.as<int32_t>() : nullptr;
+  return BR_OK;
+}
+
+// br_row_x of the last call's rows, derived on first request (k_rows_detail)
+int ensure_detail(br_ctx *c, hipStream_t st) {
+  if (c->detail_valid) return BR_OK;
+  const size_t nr = (size_t)std::max<int64_t>(c->last_n_rows, 1);
+  if (c->rows_busy_set && c->pk_x.cap < nr * sizeof(uint4)) HIPCHK(hipEventSynchronize(c->rows_busy));   // a download may still read it
+  RC(c->pk_x.ensure(nr * sizeof(uint4)));
+  if (c->last_direct) {
+    // direct rows keep no match table to gather from: the emit kernels run once more and write the detail column next to
+    // the rows (the last call's batch and the context's tables are still in place: nothing has run since)
+    if (c->last_n_rows > 0) {
+      DirectArgs D = c->dD;
+      D.r_x = c->pk_x.as<uint4>();
+      launch_emit_rows(st, c->dA, D, c->d_kept, c->d_simple, 1);
+      launch_emit_rows(st, c->dA, D, c->d_kept, c->d_simple, 2);
+      launch_big_emit(st, c->dA, D, c->n_cu * 4);
+    }
+    c->detail_valid = true;
+    return BR_OK;
+  }
+  if (c->last_n_rows > 0) {
+    PairArgs P{};
+    P.n_rows_total = c->last_n_rows; P.r_rec = c->r_rec.as<uint4>(); P.m_x = c->m_x.as<uint2>(); P.r_x = c->pk_x.as<uint4>();
+    launch_rows_detail(st, P);
+  }
+  c->detail_valid = true;
+  return BR_OK;
+}
+
+extern "C" int br_device_rows_detail(br_ctx *c, void *stream, const br_row_x **x) {
+  if (!c || !x) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->ix->device));
+  RC(ensure_detail(c, (hipStream_t)stream));
+  *x = (const br_row_x *)c->pk_x.p;
+  return BR_OK;
+}
+
+// The wide view of the last call's rows: one device array per field (what tests, debuggers and the host-row entry
+// points read).  Everything is derived from the packed table; nothing here is on the projection's own path.
+int expand_rows(br_ctx *c, hipStream_t st, br_device_wide_rows *out) {
+  memset(out, 0, sizeof(*out));
+  HIPCHK(hipSetDevice(c->ix->device));
+  const uint64_t n_rows = (uint64_t)c->last_n_rows;
+  const size_t nr = (size_t)std::max<uint64_t>(n_rows, 1);
+  RC(c->r_input.ensure(nr * 4)); RC(c->r_nh.ensure(nr * 4)); RC(c->r_hi.ensure(nr * 4));
+  RC(c->r_mapq.ensure(nr * 4)); RC(c->r_group.ensure(nr * 4));
+  RC(c->r_mate_tid.ensure(nr * 4)); RC(c->r_mate_pos.ensure(nr * 4)); RC(c->r_isize.ensure(nr * 4));
+  RC(c->r_tid.ensure(nr * 4)); RC(c->r_pos.ensure(nr * 4)); RC(c->r_ncig.ensure(nr * 4)); RC(c->r_strand.ensure(nr));
+  RC(c->r_sim.ensure(nr * 8)); RC(c->r_clip.ensure(nr * 4)); RC(c->r_junc.ensure(nr * 4)); RC(c->r_refc.ensure(nr * 4));
+  RC(c->r_cigoff.ensure((nr + 1) * 8));
+  RC(c->r_paired.ensure(nr)); RC(c->r_same.ensure(nr)); RC(c->r_first.ensure(nr)); RC(c->r_primary.ensure(nr));
+  uint64_t n_out_words = 0;
+  if (n_rows) {
+    WideArgs W{};
+    W.n_rows = (int64_t)n_rows; W.n_aln = c->last_n_aln; W.long_reads = c->last_long_reads;
+    RC(ensure_detail(c, st));
+    W.r_a = c->pk_a.as<uint4>(); W.r_c = c->pk_c.as<uint2>(); W.r_x = c->pk_x.as<uint4>();
+    W.r_sim = c->last_aux_cols ? c->pk_sim.as<double>() : nullptr; W.r_clip = c->last_aux_cols ? c->pk_clip.as<int32_t>() : nullptr;
+    W.pool = c->cig_arena.as<uint32_t>(); W.aln_group = c->aln_group.as<uint32_t>(); W.l_qseq = c->last_l_qseq;
+    W.w_input = c->r_input.as<int32_t>(); W.w_nh = c->r_nh.as<uint32_t>(); W.w_hi = c->r_hi.as<uint32_t>();
+    W.w_mapq = c->r_mapq.as<uint32_t>(); W.w_group = c->r_group.as<uint32_t>(); W.w_mate_tid = c->r_mate_tid.as<int32_t>();
+    W.w_mate_pos = c->r_mate_pos.as<int32_t>(); W.w_isize = c->r_isize.as<int32_t>(); W.w_tid = c->r_tid.as<uint32_t>();
+    W.w_pos = c->r_pos.as<uint32_t>(); W.w_ncig = c->r_ncig.as<uint32_t>(); W.w_strand = c->r_strand.as<int8_t>();
+    W.w_sim = c->r_sim.as<double>(); W.w_clip = c->r_clip.as<int32_t>(); W.w_junc = c->r_junc.as<int32_t>();
+    W.w_refc = c->r_refc.as<int32_t>(); W.w_paired = c->r_paired.as<uint8_t>(); W.w_same = c->r_same.as<uint8_t>();
+    W.w_first = c->r_first.as<uint8_t>(); W.w_primary = c->r_primary.as<uint8_t>();
+    launch_wide_fields(st, W);
+    ScanArgs S3{};
+    RC(c->tile_sums.ensure((size_t)std::max<int64_t>(scan_tiles_for((int64_t)n_rows + 1), 1) * 8 * 3));
+    RC(c->totals.ensure(16 * 8));
+    S3.n = (int64_t)n_rows; S3.src32 = c->r_ncig.as<uint32_t>(); S3.tile_sums = c->tile_sums.as<uint64_t>();
+    uint64_t *d_tot = c->totals.as<uint64_t>();
+    launch_scan(st, S3, 2, c->r_cigoff.p, true, d_tot + 8);
+    HIPCHK(hipMemcpyAsync(c->h_totals + 12, d_tot + 8, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    n_out_words = c->h_totals[12];
+    RC(c->cigar_out.ensure((size_t)std::max<uint64_t>(n_out_words, 1) * 4));
+    W.w_cigoff = c->r_cigoff.as<uint64_t>(); W.w_cigar = c->cigar_out.as<uint32_t>();
+    launch_wide_cigars(st, W, (int64_t)n_out_words);
+  } else {
+    HIPCHK(hipMemsetAsync(c->r_cigoff.p, 0, 8, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  c->wide_valid = true;
+  out->n_rows = (int64_t)n_rows; out->n_cigar_words = (int64_t)n_out_words;
+  out->input_index = c->r_input.as<int32_t>(); out->transcript_id = c->r_tid.as<uint32_t>();
+  out->pos = c->r_pos.as<uint32_t>(); out->strand = c->r_strand.as<int8_t>();
+  out->cigar_off = c->r_cigoff.as<uint64_t>(); out->cigar = c->cigar_out.as<uint32_t>();
+  out->similarity_score = c->r_sim.as<double>(); out->clip_score = c->r_clip.as<int32_t>();
+  out->junc_hits = c->r_junc.as<int32_t>(); out->aligned_len = c->r_refc.as<int32_t>();
+  out->nh = c->r_nh.as<uint32_t>(); out->hi = c->r_hi.as<uint32_t>(); out->mapq = c->r_mapq.as<uint32_t>();
+  out->is_paired = c->r_paired.as<uint8_t>(); out->same_transcript_as_mate = c->r_same.as<uint8_t>();
+  out->is_first = c->r_first.as<uint8_t>();
+  out->mate_transcript_id = c->r_mate_tid.as<int32_t>(); out->mate_pos = c->r_mate_pos.as<int32_t>();
+  out->insert_size = c->r_isize.as<int32_t>(); out->group = c->r_group.as<uint32_t>();
+  out->is_primary = c->r_primary.as<uint8_t>();
+  return BR_OK;
+}
+
+// Exact counters of the algorithmic-bytes formula for the batch the context
+// projected last (its exon / match tables are still resident).
+extern "C" int br_ctx_collect_counters(br_ctx *c, const br_device_batch *b, void *stream) {
+  if (!c || !b) return BR_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipSetDevice(c->ix->device));
+  if (c->last_direct) {
+    // The formula's B_out counts the rewritten CIGAR words of every MATCH (the evaluator's output, before pairing), and
+    // only the match table holds those: this diagnostic projects the batch once more through the match-table path (never timed).
+    br_config cfgc; memset(&cfgc, 0, sizeof(cfgc)); cfgc.junc_miss_discount = 1.0;
+    const DevCfg &d = c->dA.cfg;
+    cfgc.lr = d.long_reads; cfgc.fr = d.fr; cfgc.rf = d.rf;
+    cfgc.has_max_clip = 1; cfgc.max_clip = d.max_clip; cfgc.has_max_junc_ins = 1; cfgc.max_junc_ins = d.max_junc_ins;
+    cfgc.has_max_junc_gap = 1; cfgc.max_junc_gap = d.max_junc_gap; cfgc.has_max_error_exon = 1; cfgc.max_error_exon = d.max_error_exon;
+    cfgc.has_sim_thr = 1; cfgc.sim_thr = 1.0f;
+    const int keep_direct = c->direct_rows, keep_small = c->small_batch;
+    c->direct_rows = 0; c->small_batch = 0;
+    br_device_rows tmp;
+    const int rc = run_device(c, &cfgc, b, st, &tmp);
+    c->direct_rows = keep_direct; c->small_batch = keep_small;
+    if (rc) return rc;
+  }
+  RC(c->totals.ensure(16 * 8));
+  DevBuf stats; RC(stats.ensure(8 * 8));   // (freed on the way out)
+  HIPCHK(hipMemsetAsync(stats.p, 0, 8 * 8, st));
+  StatsArgs T{};
+  T.ix = c->ix->dev; T.n_aln = b->n_aln; T.ref_id = b->ref_id; T.cigar_off = b->cigar_off;
+  T.seg = c->seg.as<uint2>(); T.head = c->head.as<uint4>(); T.head2 = c->head2.as<uint4>(); T.out = stats.as<uint64_t>();
+  int64_t nm = (int64_t)c->counters[6];
+  launch_stats(st, T, nm ? c->m_p.as<uint2>() : nullptr, c->match_off.as<uint32_t>(), c->n_matches.as<uint32_t>());
+  uint64_t h[8];
+  HIPCHK(hipMemcpyAsync(h, stats.p, 8 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  uint64_t n = (uint64_t)b->n_aln;
+  c->counters[3] = h[3]; c->counters[4] = h[4]; c->counters[5] = h[5]; c->counters[7] = h[7];
+  c->counters[0] = 24ull * n + 4ull * h[3];
+  c->counters[1] = h[1];
+  c->counters[2] = 4ull * n + 24ull * (uint64_t)nm + 4ull * h[7];
+  return BR_OK;
+}
+
+extern "C" int br_project_batch_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, void *stream,
+                                       br_device_rows *out) {
+  if (!c || !cfg || !b || !out) return BR_ERR_INVALID_ARG;
+  return run_device(c, cfg, b, (hipStream_t)stream, out);
+}
+
+extern "C" int br_device_rows_expand(br_ctx *c, void *stream, br_device_wide_rows *out) {
+  if (!c || !out) return BR_ERR_INVALID_ARG;
+  return expand_rows(c, (hipStream_t)stream, out);
+}

@@ -1,5 +1,5 @@
 // br_sam_reader: SAM text in (host memory), bundles of device-resident BAM records of whole read-name groups out -- the SAM
-// counterpart of br_bam_reader (abi.cpp).  The reference reads SAM through htslib like BAM (GSamReader -> hts_open,
+// counterpart of br_bam_reader (reader.cpp).  The reference reads SAM through htslib like BAM (GSamReader -> hts_open,
 // gclib/GSam.h:371; BamIO::start, include/bramble.h:45): every line becomes the bam1_t that sam_parse1 builds.  Here the text
 // goes up as it is and sam_kernels.hip makes the records where br_project_bam_resident needs them.
 //
@@ -22,37 +22,14 @@
 #include <vector>
 
 #include "../../include/bramble_amd.h"
+#include "devmem.h"
 #include "kernels.h"
 #include "sam_header.h"
 #include "sam_kernels.h"
 
 using namespace br;
 
-#define SAM_HIPCHK(expr)                                                                                         \
-  do {                                                                                                           \
-    hipError_t _e = (expr);                                                                                      \
-    if (_e != hipSuccess) {                                                                                      \
-      fprintf(stderr, "[bramble_amd] HIP error %s at %s:%d: %s\n", hipGetErrorName(_e), __FILE__, __LINE__, #expr); \
-      return BR_ERR_HIP;                                                                                         \
-    }                                                                                                            \
-  } while (0)
-#define SAM_RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 namespace {
-
-struct DBuf {
-  void *p = nullptr; size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return BR_OK;
-    if (p) { SAM_HIPCHK(hipFree(p)); p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    SAM_HIPCHK(hipMalloc(&p, want));
-    cap = want;
-    return BR_OK;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <typename T> T *as() { return (T *)p; }
-};
 
 const char *sam_reason(int e) {
   switch (e) {
@@ -82,14 +59,14 @@ struct br_sam_reader {
   hipStream_t st = nullptr;
   int32_t n_ref = 0;
   uint32_t h_mask = 0;
-  DBuf h_slot, name_off, names;
-  DBuf text[2], tile, tmp, lend, line, mapped, bytes, small, fix;
+  DevBuf h_slot, name_off, names;
+  DevBuf text[2], tile, tmp, lend, line, mapped, bytes, small, fix;
   uint64_t text_n[2] = {0, 0};
   hipStream_t up_st = nullptr;
   hipEvent_t up_done[2] = {nullptr, nullptr}, up_t[2] = {nullptr, nullptr};
   std::mutex stat_m;
   uint32_t fix_cap = 4096;
-  struct Chunk { DBuf blob, off, len, rline; int64_t id = -1; bool out = false; };
+  struct Chunk { DevBuf blob, off, len, rline; int64_t id = -1; bool out = false; };
   std::vector<std::unique_ptr<Chunk>> chunks;
   std::mutex m;
   static constexpr size_t PIN_BYTES = 8u << 20;
@@ -125,9 +102,7 @@ extern "C" void br_sam_reader_free(br_sam_reader *r) {
   if (!r) return;
   (void)hipSetDevice(r->device);
   if (r->st) (void)hipStreamSynchronize(r->st);
-  for (auto &c : r->chunks) { c->blob.release(); c->off.release(); c->len.release(); c->rline.release(); }
   if (r->up_st) (void)hipStreamSynchronize(r->up_st);
-  for (DBuf *b : {&r->h_slot, &r->name_off, &r->names, &r->text[0], &r->text[1], &r->tile, &r->tmp, &r->lend, &r->line, &r->mapped, &r->bytes, &r->small, &r->fix}) b->release();
   for (int k = 0; k < 2; k++) { if (r->pin[k]) (void)hipHostFree(r->pin[k]); if (r->pin_ev[k]) (void)hipEventDestroy(r->pin_ev[k]); }
   for (auto &e : r->ev) if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < 2; k++) { if (r->up_done[k]) (void)hipEventDestroy(r->up_done[k]); if (r->up_t[k]) (void)hipEventDestroy(r->up_t[k]); }
@@ -157,30 +132,30 @@ static int sam_reader_init(br_sam_reader *r, const char *header_text, uint64_t h
     if (!dup) slot[k] = (int32_t)i;   // (a repeated name resolves to its first @SQ line)
   }
   off[names.size()] = blob.size();
-  SAM_RC(r->h_slot.ensure(sz * 4)); SAM_RC(r->name_off.ensure(off.size() * 8)); SAM_RC(r->names.ensure(blob.size() + 1));
-  SAM_HIPCHK(hipMemcpy(r->h_slot.p, slot.data(), sz * 4, hipMemcpyHostToDevice));
-  SAM_HIPCHK(hipMemcpy(r->name_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-  if (!blob.empty()) SAM_HIPCHK(hipMemcpy(r->names.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
-  SAM_HIPCHK(hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking));
-  SAM_HIPCHK(hipStreamCreateWithFlags(&r->up_st, hipStreamNonBlocking));
+  RC(r->h_slot.ensure(sz * 4)); RC(r->name_off.ensure(off.size() * 8)); RC(r->names.ensure(blob.size() + 1));
+  HIPCHK(hipMemcpy(r->h_slot.p, slot.data(), sz * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(r->name_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+  if (!blob.empty()) HIPCHK(hipMemcpy(r->names.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&r->up_st, hipStreamNonBlocking));
   for (int k = 0; k < 2; k++) {
-    SAM_HIPCHK(hipEventCreateWithFlags(&r->up_done[k], hipEventDisableTiming));
-    SAM_HIPCHK(hipEventCreate(&r->up_t[k]));
+    HIPCHK(hipEventCreateWithFlags(&r->up_done[k], hipEventDisableTiming));
+    HIPCHK(hipEventCreate(&r->up_t[k]));
   }
   for (int k = 0; k < 2; k++) {
-    SAM_HIPCHK(hipHostMalloc((void **)&r->pin[k], br_sam_reader::PIN_BYTES, hipHostMallocDefault));
-    SAM_HIPCHK(hipEventCreateWithFlags(&r->pin_ev[k], hipEventDisableTiming));
+    HIPCHK(hipHostMalloc((void **)&r->pin[k], br_sam_reader::PIN_BYTES, hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&r->pin_ev[k], hipEventDisableTiming));
   }
-  for (auto &e : r->ev) SAM_HIPCHK(hipEventCreate(&e));
-  SAM_RC(r->small.ensure(64));
+  for (auto &e : r->ev) HIPCHK(hipEventCreate(&e));
+  RC(r->small.ensure(64));
   return BR_OK;
 }
 
 extern "C" int br_sam_reader_new(int device, const char *header_text, uint64_t header_len, br_sam_reader **out) {
   if (!out || (!header_text && header_len)) return BR_ERR_INVALID_ARG;
   *out = nullptr;
-  SAM_RC(sam_check_device(device));
-  SAM_HIPCHK(hipSetDevice(device));
+  RC(sam_check_device(device));
+  HIPCHK(hipSetDevice(device));
   br_sam_reader *r = new br_sam_reader();
   r->device = device;
   const int rc = sam_reader_init(r, header_text, header_len);
@@ -214,23 +189,23 @@ constexpr uint64_t SAM_MAX_CHUNK = 1ull << 30;   // text per call (field offsets
 extern "C" int br_sam_reader_upload(br_sam_reader *r, int slot, const uint8_t *text, uint64_t n) {
   if (!r || slot < 0 || slot > 1 || (!text && n)) return BR_ERR_INVALID_ARG;
   n = std::min(n, SAM_MAX_CHUNK);
-  SAM_HIPCHK(hipSetDevice(r->device));
+  HIPCHK(hipSetDevice(r->device));
   hipStream_t st = r->up_st;
-  SAM_RC(r->text[slot].ensure(n + 16));
-  SAM_HIPCHK(hipEventRecord(r->up_t[0], st));
+  RC(r->text[slot].ensure(n + 16));
+  HIPCHK(hipEventRecord(r->up_t[0], st));
   // two pinned buffers: the host fills one while the other one's bytes cross PCIe
   for (uint64_t o = 0, k = 0; o < n; o += br_sam_reader::PIN_BYTES, k++) {
     const int s = (int)(k & 1);
     const size_t len = (size_t)std::min<uint64_t>(br_sam_reader::PIN_BYTES, n - o);
-    if (r->pin_used[s]) SAM_HIPCHK(hipEventSynchronize(r->pin_ev[s]));
+    if (r->pin_used[s]) HIPCHK(hipEventSynchronize(r->pin_ev[s]));
     memcpy(r->pin[s], text + o, len);
-    SAM_HIPCHK(hipMemcpyAsync(r->text[slot].as<uint8_t>() + o, r->pin[s], len, hipMemcpyHostToDevice, st));
-    SAM_HIPCHK(hipEventRecord(r->pin_ev[s], st));
+    HIPCHK(hipMemcpyAsync(r->text[slot].as<uint8_t>() + o, r->pin[s], len, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(r->pin_ev[s], st));
     r->pin_used[s] = true;
   }
-  SAM_HIPCHK(hipEventRecord(r->up_t[1], st));
-  SAM_HIPCHK(hipEventRecord(r->up_done[slot], st));
-  SAM_HIPCHK(hipEventSynchronize(r->up_t[1]));
+  HIPCHK(hipEventRecord(r->up_t[1], st));
+  HIPCHK(hipEventRecord(r->up_done[slot], st));
+  HIPCHK(hipEventSynchronize(r->up_t[1]));
   float ms = 0;
   if (hipEventElapsedTime(&ms, r->up_t[0], r->up_t[1]) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
   std::lock_guard<std::mutex> l(r->stat_m);
@@ -242,38 +217,38 @@ extern "C" int br_sam_reader_upload(br_sam_reader *r, int slot, const uint8_t *t
 static int sam_next(br_sam_reader *r, int slot, const uint8_t *text, uint64_t n, int last, uint64_t *consumed, br_device_records *bundle,
                     int64_t *id, int64_t *n_unmapped, int64_t *bad_line) {
   hipStream_t st = r->st;
-  SAM_HIPCHK(hipSetDevice(r->device));
+  HIPCHK(hipSetDevice(r->device));
   {
     std::lock_guard<std::mutex> l(r->stat_m);
     if (r->text_n[slot] != n) return BR_ERR_INVALID_ARG;   // the slot does not hold these bytes
   }
-  SAM_HIPCHK(hipStreamWaitEvent(st, r->up_done[slot], 0));
-  SAM_HIPCHK(hipEventRecord(r->ev[1], st));
+  HIPCHK(hipStreamWaitEvent(st, r->up_done[slot], 0));
+  HIPCHK(hipEventRecord(r->ev[1], st));
   const uint8_t *d_text = r->text[slot].as<uint8_t>();
   // line index
   const uint64_t tiles = (n + SAM_NL_TILE - 1) / SAM_NL_TILE;
-  SAM_RC(r->tile.ensure((tiles + 1) * 8));
-  SAM_RC(r->tmp.ensure(((std::max<uint64_t>(tiles, n / 64) + 1) / 1024 + 4) * 8));
+  RC(r->tile.ensure((tiles + 1) * 8));
+  RC(r->tmp.ensure(((std::max<uint64_t>(tiles, n / 64) + 1) / 1024 + 4) * 8));
   launch_sam_nl_count(st, d_text, n, r->tile.as<uint64_t>());
   launch_sam_scan(st, r->tile.as<uint64_t>(), (int64_t)tiles, r->tmp.as<uint64_t>());
   uint64_t n_nl = 0;
-  SAM_HIPCHK(hipMemcpyAsync(&n_nl, r->tile.as<uint64_t>() + tiles, 8, hipMemcpyDeviceToHost, st));
-  SAM_HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(&n_nl, r->tile.as<uint64_t>() + tiles, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   const bool tail_line = last && text[n - 1] != '\n';   // the file's last line may lack its '\n'
   const int64_t n_lines = (int64_t)n_nl + (tail_line ? 1 : 0);
   if (n_lines == 0) { *consumed = 0; return BR_OK; }
-  SAM_RC(r->lend.ensure((size_t)(n_lines + 1) * 8));
+  RC(r->lend.ensure((size_t)(n_lines + 1) * 8));
   launch_sam_nl_write(st, d_text, n, r->tile.as<uint64_t>(), r->lend.as<uint64_t>());
-  if (tail_line) { r->last_nl = n; SAM_HIPCHK(hipMemcpyAsync(r->lend.as<uint64_t>() + n_nl, &r->last_nl, 8, hipMemcpyHostToDevice, st)); }
+  if (tail_line) { r->last_nl = n; HIPCHK(hipMemcpyAsync(r->lend.as<uint64_t>() + n_nl, &r->last_nl, 8, hipMemcpyHostToDevice, st)); }
   // measure
   const size_t nl1 = (size_t)n_lines + 1;
-  SAM_RC(r->line.ensure(nl1 * sizeof(SamLine))); SAM_RC(r->mapped.ensure(nl1 * 8)); SAM_RC(r->bytes.ensure(nl1 * 8));
-  SAM_RC(r->tmp.ensure((nl1 / 1024 + 4) * 8));
-  SAM_RC(r->fix.ensure((size_t)r->fix_cap * sizeof(SamFix)));
+  RC(r->line.ensure(nl1 * sizeof(SamLine))); RC(r->mapped.ensure(nl1 * 8)); RC(r->bytes.ensure(nl1 * 8));
+  RC(r->tmp.ensure((nl1 / 1024 + 4) * 8));
+  RC(r->fix.ensure((size_t)r->fix_cap * sizeof(SamFix)));
   unsigned long long *first_bad = (unsigned long long *)r->small.p;
   uint32_t *n_fix = (uint32_t *)(r->small.as<uint8_t>() + 8);
-  SAM_HIPCHK(hipMemsetAsync(r->small.p, 0xff, 8, st));
-  SAM_HIPCHK(hipMemsetAsync(n_fix, 0, 4, st));
+  HIPCHK(hipMemsetAsync(r->small.p, 0xff, 8, st));
+  HIPCHK(hipMemsetAsync(n_fix, 0, 4, st));
   SamArgs A{};
   A.text = d_text; A.n_bytes = n; A.lend = r->lend.as<uint64_t>(); A.n_lines = n_lines; A.line = r->line.as<SamLine>();
   A.mapped = r->mapped.as<uint64_t>(); A.bytes = r->bytes.as<uint64_t>(); A.first_bad = first_bad;
@@ -283,10 +258,10 @@ static int sam_next(br_sam_reader *r, int slot, const uint8_t *text, uint64_t n,
   launch_sam_scan(st, A.mapped, n_lines, r->tmp.as<uint64_t>());
   launch_sam_scan(st, A.bytes, n_lines, r->tmp.as<uint64_t>());
   uint64_t h3[3] = {0, 0, 0};
-  SAM_HIPCHK(hipMemcpyAsync(&h3[0], first_bad, 8, hipMemcpyDeviceToHost, st));
-  SAM_HIPCHK(hipMemcpyAsync(&h3[1], A.mapped + n_lines, 8, hipMemcpyDeviceToHost, st));
-  SAM_HIPCHK(hipMemcpyAsync(&h3[2], A.bytes + n_lines, 8, hipMemcpyDeviceToHost, st));
-  SAM_HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(&h3[0], first_bad, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&h3[1], A.mapped + n_lines, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&h3[2], A.bytes + n_lines, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   if (h3[0] != ~0ull) {
     const int64_t bl = (int64_t)(h3[0] >> 8);
     *bad_line = r->line_base + bl + 1;
@@ -302,27 +277,27 @@ static int sam_next(br_sam_reader *r, int slot, const uint8_t *text, uint64_t n,
     for (auto &c : r->chunks) if (!c->out) { ch = c.get(); break; }
     if (!ch) { r->chunks.push_back(std::make_unique<br_sam_reader::Chunk>()); ch = r->chunks.back().get(); }
   }
-  SAM_RC(ch->blob.ensure(total + 64)); SAM_RC(ch->off.ensure((size_t)n_mapped * 8 + 8));
-  SAM_RC(ch->len.ensure((size_t)n_mapped * 4 + 4)); SAM_RC(ch->rline.ensure((size_t)n_mapped * 4 + 4));
+  RC(ch->blob.ensure(total + 64)); RC(ch->off.ensure((size_t)n_mapped * 8 + 8));
+  RC(ch->len.ensure((size_t)n_mapped * 4 + 4)); RC(ch->rline.ensure((size_t)n_mapped * 4 + 4));
   A.blob = ch->blob.as<uint8_t>(); A.rec_off = ch->off.as<uint64_t>(); A.rec_len = ch->len.as<uint32_t>(); A.rec_line = ch->rline.as<uint32_t>();
   A.n_fix = n_fix;
   uint32_t nf = 0;
   for (int pass = 0; pass < 2; pass++) {
     A.fix = r->fix.as<SamFix>(); A.fix_cap = r->fix_cap;
     if (n_mapped) launch_sam_emit(st, A);
-    SAM_HIPCHK(hipMemcpyAsync(&nf, n_fix, 4, hipMemcpyDeviceToHost, st));
-    SAM_HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(&nf, n_fix, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     if (nf <= r->fix_cap) break;
     r->fix_cap = nf;   // more floats off the fast path than the list holds: a longer list, and the records once more
-    SAM_RC(r->fix.ensure((size_t)r->fix_cap * sizeof(SamFix)));
-    SAM_HIPCHK(hipMemsetAsync(n_fix, 0, 4, st));
+    RC(r->fix.ensure((size_t)r->fix_cap * sizeof(SamFix)));
+    HIPCHK(hipMemsetAsync(n_fix, 0, 4, st));
   }
-  SAM_HIPCHK(hipEventRecord(r->ev[2], st));
+  HIPCHK(hipEventRecord(r->ev[2], st));
   // floats the device could not convert exactly: (float)strtod(text), as sam_parse1 does
   if (nf) {
     std::vector<SamFix> fx(nf);
-    SAM_HIPCHK(hipMemcpyAsync(fx.data(), r->fix.p, nf * sizeof(SamFix), hipMemcpyDeviceToHost, st));
-    SAM_HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(fx.data(), r->fix.p, nf * sizeof(SamFix), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     std::vector<float> val(nf);
     int64_t bad = -1;
     for (uint32_t k = 0; k < nf; k++) {
@@ -333,25 +308,25 @@ static int sam_next(br_sam_reader *r, int slot, const uint8_t *text, uint64_t n,
       val[k] = (float)d;
     }
     if (bad >= 0) { *bad_line = r->line_base + bad + 1; r->err = sam_reason(SAM_E_FLOAT); return BR_ERR_INVALID_ARG; }
-    for (uint32_t k = 0; k < nf; k++) SAM_HIPCHK(hipMemcpyAsync(A.blob + fx[k].dst, &val[k], 4, hipMemcpyHostToDevice, st));
-    SAM_HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t k = 0; k < nf; k++) HIPCHK(hipMemcpyAsync(A.blob + fx[k].dst, &val[k], 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
   }
   // the cut: everything in front of the last read-name group, unless the text ends with the file
   int64_t n_take = n_mapped, cut_line = n_lines;
   uint64_t used = n;
   if (!last) {
     if (n_mapped > 0) {
-      SAM_HIPCHK(hipMemsetAsync(r->small.as<uint8_t>() + 16, 0, 8, st));
+      HIPCHK(hipMemsetAsync(r->small.as<uint8_t>() + 16, 0, 8, st));
       launch_last_group(st, A.blob, A.rec_off, n_mapped, (unsigned long long *)(r->small.as<uint8_t>() + 16));
       uint64_t g = 0;
-      SAM_HIPCHK(hipMemcpyAsync(&g, r->small.as<uint8_t>() + 16, 8, hipMemcpyDeviceToHost, st));
-      SAM_HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpyAsync(&g, r->small.as<uint8_t>() + 16, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
       uint32_t gl = 0;
-      SAM_HIPCHK(hipMemcpyAsync(&gl, A.rec_line + g, 4, hipMemcpyDeviceToHost, st));
-      SAM_HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpyAsync(&gl, A.rec_line + g, 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
       n_take = (int64_t)g; cut_line = gl;
       uint64_t prev_end = 0;
-      if (gl) { SAM_HIPCHK(hipMemcpyAsync(&prev_end, A.lend + gl - 1, 8, hipMemcpyDeviceToHost, st)); SAM_HIPCHK(hipStreamSynchronize(st)); }
+      if (gl) { HIPCHK(hipMemcpyAsync(&prev_end, A.lend + gl - 1, 8, hipMemcpyDeviceToHost, st)); HIPCHK(hipStreamSynchronize(st)); }
       used = gl ? prev_end + 1 : 0;
     } else {   // only unmapped lines: all complete ones are done with
       n_take = 0; cut_line = n_lines;
@@ -389,6 +364,6 @@ extern "C" int br_sam_reader_next_staged(br_sam_reader *r, int slot, const uint8
 extern "C" int br_sam_reader_next(br_sam_reader *r, const uint8_t *text, uint64_t n_bytes, int last, uint64_t *consumed,
                                   br_device_records *bundle, int64_t *id, int64_t *n_unmapped, int64_t *bad_line) {
   if (!r || (!text && n_bytes)) return BR_ERR_INVALID_ARG;
-  SAM_RC(br_sam_reader_upload(r, 0, text, n_bytes));
+  RC(br_sam_reader_upload(r, 0, text, n_bytes));
   return br_sam_reader_next_staged(r, 0, text, n_bytes, last, consumed, bundle, id, n_unmapped, bad_line);
 }

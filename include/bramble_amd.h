@@ -635,7 +635,7 @@ const char *br_bgzf_codec(void); /* "libdeflate" (bound at run time when present
 
 /* Kernel names reported by br_ctx_kernel_ms / rocprof. */
 #define BR_K_SEGMENT 0    /* k_segment */
-#define BR_K_COUNT 1      /* k_project<G,false> (count pass; with "count_split" the main kernel, without the exon walk) */
+#define BR_K_COUNT 1      /* k_project<G,false> (count pass; on the large short-read paths the main kernel, without the exon walk) */
 #define BR_K_EMIT 2       /* k_emit_dense (general class; the whole list for long-read presets) */
 #define BR_K_PAIR_COUNT 3 /* k_pair */
 #define BR_K_PAIR_EMIT 4  /* k_pair<true> (per-record {match, input, NH, HI | flags}) */
@@ -661,16 +661,17 @@ const char *br_bgzf_codec(void); /* "libdeflate" (bound at run time when present
 #define BR_K_GROUP_DESC 24 /* k_group_desc: NH / HI / primary per read name (+ the per-read-name counters) */
 #define BR_K_EXPAND_ROWS 25 /* k_expand_rows: emit work list + emit descriptors */
 #define BR_K_EMIT_ROWS_SIMPLE 26 /* k_emit_rows<1>: packed rows of the simple class */
-#define BR_K_EMIT_ROWS 27  /* k_emit_rows<2|0>: packed rows of the general class (or of everything) */
+#define BR_K_EMIT_ROWS 27  /* k_emit_rows<2>: packed rows of the general class */
 #define BR_K_BIG_EMIT 28   /* k_big<1>: packed rows of the alignments with > 64 candidate rows */
 #define BR_K_NUM 29
 /* When enabled, every launch is bracketed by hipEvents on the launch stream. */
 int br_ctx_set_profiling(br_ctx *, int enabled);
 /* Launch tuning: "group_lanes" (8|16|32|64 lanes cooperating on one alignment),
  * "blocks_per_cu" (grid size of the grid-stride projection kernels), "bam_lanes" (0, the default: a wave per 32
- * re-encoded records, their byte regions as 16-byte copy tasks; 4..64: that many lanes per record), "deflate_dynamic" (1: per-block Huffman codes, 0: the fixed code), "emit_split" (1: the emit
- * work list is launched per class, 0: one launch), "count_split" (1: short-read presets run the count pass as a main
- * kernel without the exon walk plus a second one for the alignments that need it, 0: one kernel). */
+ * re-encoded records, their byte regions as 16-byte copy tasks; 4..64: that many lanes per record), "deflate_dynamic" (1: per-block Huffman codes, 0: the fixed code).
+ * Short-read presets run the count pass of large batches as a main kernel without the exon walk plus a second one for the
+ * alignments that need it, and launch the emit work list per class; small batches and the similarity-filter presets use
+ * one kernel for each. */
 int br_ctx_set_param(br_ctx *, const char *key, int64_t value);
 /* Device time (ms) of kernel `which` during the last projection call, summed
  * over its launches; *launches receives the launch count. */

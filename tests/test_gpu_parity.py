@@ -349,24 +349,31 @@ def test_bucket_table_ranges_at_bin_edges():
             assert_rows_equal(prod, orc)
 
 
-@pytest.mark.parametrize("key", ["count_split", "emit_split"])
-def test_single_kernel_forms_of_the_split_passes(key):
-    """count_split = 0 / emit_split = 0: the count pass as one kernel (exon walk inline), the emit work list in one
-    launch -- the forms the long-read presets use; same rows as the oracle on short reads, and on long reads under a
+def test_single_kernel_forms_of_the_split_passes():
+    """The count pass as one kernel (exon walk inline) and the emit work list in one launch -- the forms of small batches
+    and of the long-read presets -- and both passes split (the main count kernel plus the exon walk; one emit launch per
+    class) on direct rows and on the match-table path: same rows as the oracle on short reads, and on long reads under a
     short-read preset (every alignment takes the second count kernel when the split is on)."""
     ann = synth.Annotation("G", n_genes=3000, n_refs=3)
+    idx = lib.Index(ann.as_dict(), device=0)
+    oi = ob.OracleIndex(ann.as_dict())
+    walk, simple = lib.KERNEL_NAMES[lib.K_COUNT_WALK], (lib.KERNEL_NAMES[lib.K_EMIT_SIMPLE], lib.KERNEL_NAMES[lib.K_EMIT_ROWS_SIMPLE])
     for mode, n in (("pe", 30000), ("hifi", 4000)):
         b = ann.reads(n, mode)
-        idx = lib.Index(ann.as_dict(), device=0)
-        oi = ob.OracleIndex(ann.as_dict())
         orc, _, _ = ob.run(oi, ob.make_flags(), b, want_matches=False)
-        for v in (0, 1):
+        # the small path (the whole batch within small_n), direct rows, the match table
+        for params, split in (({"small_n": b["n_aln"]}, False), ({"small_batch": 0}, True), ({"small_batch": 0, "direct_rows": 0}, True)):
             ctx = lib.Context(idx)
-            ctx.set_param(key, v)
+            for k, v in params.items():
+                ctx.set_param(k, v)
+            ctx.set_profiling(True)
             prod = ctx.project_batch(lib.make_config(), b)
             assert_rows_equal(prod, orc)
+            launches = ctx.kernel_ms()
+            assert (launches[walk][1] > 0) == split, (mode, params)
+            assert (sum(launches[k][1] for k in simple) > 0) == split, (mode, params)
             ctx.close()
-        idx.close()
+    idx.close()
 
 
 def test_short_read_paths_equal_oracle_at_dense_loci():
