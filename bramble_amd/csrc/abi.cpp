@@ -136,8 +136,11 @@ static int build_index_flat(size_t n_tx, const int32_t *tx_ref, const int8_t *tx
       at++;
     }
   });
-  // bucket tables (replace the per-read binary search of the slab)
-  const uint32_t SHIFT = 10;
+  // bucket tables (replace the per-read binary search of the slab).  512-base bins: the count pass's candidate rows are a
+  // superset bounded by the bins around a read, and narrower bins test fewer rows (bench step: 1 kb -> 512 b bins took the
+  // main count kernel from 1.74 to 1.60 ms, 2 kb bins cost 0.18 ms more); the table is 16 bytes per bin and reference
+  // (about 100 MB on a human-sized genome), which still leaves the index resident in the Infinity Cache
+  const uint32_t SHIFT = 9;
   std::vector<uint64_t> n_bins(ix->n_refs, 2);
   ix->bin_off.assign((size_t)ix->n_refs + 1, 0);
   {

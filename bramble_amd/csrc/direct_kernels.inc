@@ -555,6 +555,10 @@ __global__ void __launch_bounds__(256) k_scan5_apply(DirectArgs D, const uint64_
 // is only read when the draw's rejection branch needs it.)
 struct __attribute__((packed, aligned(4))) GD4 { uint32_t a, b, c, d; };
 __global__ void __launch_bounds__(256) k_group_desc(DirectArgs D) {
+  // The side arena ran out: k_pair_big left the outputs of the > 64-candidate alignments (and of their partners) unwritten,
+  // so rows, flags and mate links are not to be trusted -- a stale PF_PAIRED on an unpaired alignment sends the mate write
+  // to gd[-1].  The host grows the arena and repeats; nothing here is used.
+  if (D.side_used[1]) return;
   unsigned long long uniq = 0, dropped = 0;
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < D.n_groups; g += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t a0 = D.group_off[g], a1 = D.group_off[g + 1];
@@ -667,6 +671,7 @@ __global__ void __launch_bounds__(256) k_expand_rows(DirectArgs D) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (D.m_aln_cap && D.tot[0] > D.m_aln_cap) return;   // launched ahead with the last call's list: too small this time (the host launches again)
+  if (D.side_used[1]) return;   // the side arena ran out: counts and class positions are not to be trusted (see k_group_desc)
   uint32_t nk = 0, pos = 0, v = 0;
   bool fast = false;
   if (a < D.n_aln) nk = D.n_kept[a];

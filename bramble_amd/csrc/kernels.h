@@ -49,6 +49,31 @@ struct ProjectArgs {
 };
 __device__ __forceinline__ bool tot_over(const uint64_t *tot, uint64_t lim_m, uint64_t lim_c) { return tot && (tot[0] > lim_m || tot[1] > lim_c); }
 
+// What the split count pass (k_project<G, false, false, 1 / 2>) reads and writes, and nothing else: every uniform value the
+// kernels keep live is an SGPR, and with ProjectArgs the main one spilled 37 of them to VGPR lanes.  The preset flags
+// (long_reads, ignore_small_exons, and so whether max_error_exon is in play) are template arguments of the short-read
+// instantiation; the generic one reads them here.
+struct CountArgs {
+  // index
+  const uint32_t *slab_off, *bin_off, *s_start, *s_pmax;
+  const uint4 *t_bin, *s_row, *tx_ex;
+  uint32_t n_refs, bin_shift;
+  // thresholds
+  uint32_t max_clip, max_junc_ins, max_junc_gap, max_error_exon;
+  int32_t ignore_small_exons, long_reads;
+  uint32_t n_aln;
+  // inputs: k_segment's head records and read exons (cigar_off: where an alignment's exons start in seg)
+  const uint4 *head, *head2;
+  const uint32_t *cigar_off;
+  const uint2 *seg;
+  // outputs (see ProjectArgs)
+  uint32_t *n_matches;
+  uint64_t *mask;
+  uint4 *ranges;
+  uint32_t *walk_list, *n_walk;
+  uint32_t *big_list, *n_big;
+};
+
 // -S clip rescue (rescue_kernels.inc)
 struct FaArgs {
   const int32_t *seq_src;      // [n_aln] alignment whose sequence the read-name group shares (-1: none)
@@ -426,7 +451,9 @@ void launch_segment(hipStream_t st, int64_t n_aln, const int32_t *ref_id, const 
                     const uint32_t *cigar, const DevCfg &cfg, uint32_t n_refs, uint2 *seg, AlnMeta *meta,
                     uint4 *head, uint4 *head2, uint32_t *fast_flag, const SegExtra *extra = nullptr);
 // part: see launch_project_g (0 = everything)
-void launch_project(hipStream_t st, const ProjectArgs &A, bool emit, int group_lanes, int n_blocks, int part = 0);
+void launch_project(hipStream_t st, const ProjectArgs &A, bool emit, int group_lanes, int n_blocks);
+// the split count pass (presets without the similarity filter): part 1 = the main kernel, 2 = the one with the exon walk
+void launch_count(hipStream_t st, const CountArgs &C, int group_lanes, int n_blocks, int part);
 void launch_project_fa(hipStream_t st, const ProjectArgs &A, const FaArgs &F, int mode, int n_blocks);
 void launch_fa_fill(hipStream_t st, const ProjectArgs &A, const FaArgs &F, int64_t n_prob);   // coded sequences of every problem
 void launch_ksw(hipStream_t st, const KswArgs &K, int n_blocks);

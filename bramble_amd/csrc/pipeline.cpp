@@ -155,18 +155,38 @@ static ProjectArgs count_args(br_ctx *c, const DevCfg &dc, const br_device_batch
   return A;
 }
 
-// the count pass: one kernel with the exon walk inline, or (split) the main kernel without it and a second one for the
-// alignments it put on A.walk_list
+// what the split count pass reads and writes (A's other fields are the emit pass's)
+static CountArgs count_view(const ProjectArgs &A) {
+  CountArgs C{};
+  const DevIndex &ix = A.ix;
+  C.slab_off = ix.slab_off; C.bin_off = ix.bin_off; C.s_start = ix.s_start; C.s_pmax = ix.s_pmax;
+  C.t_bin = ix.t_bin; C.s_row = ix.s_row; C.tx_ex = ix.tx_ex; C.n_refs = ix.n_refs; C.bin_shift = ix.bin_shift;
+  C.max_clip = A.cfg.max_clip; C.max_junc_ins = A.cfg.max_junc_ins; C.max_junc_gap = A.cfg.max_junc_gap;
+  C.max_error_exon = A.cfg.max_error_exon; C.ignore_small_exons = A.cfg.ignore_small_exons; C.long_reads = A.cfg.long_reads;
+  C.n_aln = (uint32_t)A.n_aln;   // (br_batch_prepare: < 2^31; the work lists hold 32-bit alignment numbers)
+  C.head = A.head; C.head2 = A.head2; C.cigar_off = A.cigar_off; C.seg = A.seg;
+  C.n_matches = A.n_matches; C.mask = A.mask; C.ranges = A.ranges;
+  C.walk_list = A.walk_list; C.n_walk = A.n_walk; C.big_list = A.big_list; C.n_big = A.n_big;
+  return C;
+}
+
+// the count pass: one kernel with the exon walk inline, or (split: presets without the similarity filter) the main kernel
+// without it and a second one for the alignments it put on A.walk_list
 static int count_pass(br_ctx *c, hipStream_t st, const ProjectArgs &A, Prof &pf, bool split) {
   const int n_blocks = c->n_cu * c->blocks_per_cu;
-  RC(pf.begin(BR_K_COUNT));
-  launch_project(st, A, false, c->group_lanes, n_blocks, split ? 1 : 0);
-  RC(pf.end());
-  if (split) {
-    RC(pf.begin(BR_K_COUNT_WALK));
-    launch_project(st, A, false, c->group_lanes, n_blocks, 2);
+  if (!split || A.ix.n_rows == 0) {   // (an empty annotation: launch_project zeroes the counts)
+    RC(pf.begin(BR_K_COUNT));
+    launch_project(st, A, false, c->group_lanes, n_blocks);
     RC(pf.end());
+    return BR_OK;
   }
+  const CountArgs C = count_view(A);
+  RC(pf.begin(BR_K_COUNT));
+  launch_count(st, C, c->group_lanes, n_blocks, 1);
+  RC(pf.end());
+  RC(pf.begin(BR_K_COUNT_WALK));
+  launch_count(st, C, c->group_lanes, n_blocks, 2);
+  RC(pf.end());
   return BR_OK;
 }
 

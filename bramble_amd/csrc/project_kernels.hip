@@ -678,8 +678,28 @@ __device__ __forceinline__ bool similarity(const DevCfg &cfg, const Acc &acc, do
 // needs the full exon walk (three or more read exons, or a two-exon read outside the shortcut) is put on walk_list
 // instead, so that the walk's code and registers stay out of this kernel (it sits at the 64-VGPR ceiling and is
 // bound by instruction issue); 2 = the listed alignments, with the walk.  0 = everything in one kernel.
-template <int G, bool EMIT, bool SIMF, int MODE = 0>
-__global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(ProjectArgs A) {
+//
+// Args: ProjectArgs, or CountArgs for the split count pass (MODE 1 / 2).  PRE = 1 (CountArgs only): the short-read preset --
+// no long-read rules, no small-exon rescue, so max_error_exon is not in play -- with those flags as constants.
+__device__ __forceinline__ const DevIndex &proj_index(const ProjectArgs &A) { return A.ix; }
+__device__ __forceinline__ DevIndex proj_index(const CountArgs &C) {
+  DevIndex ix{};
+  ix.n_refs = C.n_refs; ix.slab_off = C.slab_off; ix.s_start = C.s_start; ix.s_pmax = C.s_pmax; ix.s_row = C.s_row;
+  ix.tx_ex = C.tx_ex; ix.bin_shift = C.bin_shift; ix.bin_off = C.bin_off; ix.t_bin = C.t_bin;
+  return ix;
+}
+template <int PRE> __device__ __forceinline__ const DevCfg &proj_cfg(const ProjectArgs &A) { return A.cfg; }
+template <int PRE> __device__ __forceinline__ DevCfg proj_cfg(const CountArgs &C) {
+  DevCfg c{};
+  c.max_clip = C.max_clip; c.max_junc_ins = C.max_junc_ins; c.max_junc_gap = C.max_junc_gap;
+  c.max_error_exon = PRE ? 0u : C.max_error_exon;
+  c.ignore_small_exons = PRE ? 0 : C.ignore_small_exons;
+  c.long_reads = PRE ? 0 : C.long_reads;
+  return c;
+}
+
+template <int G, bool EMIT, bool SIMF, int MODE = 0, int PRE = 0, class Args = ProjectArgs>
+__global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(Args A) {
   __shared__ uint32_t sh_slab[SLAB_LDS];
   __shared__ uint32_t sh_bin[EMIT ? 1 : SLAB_LDS];
   __shared__ uint32_t sh_cig[EMIT ? 256 * LDS_SLOT : 1];
@@ -694,12 +714,16 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(ProjectArgs A) {
   const int gl = threadIdx.x & (G - 1);
   const int gbase = (threadIdx.x & 63) & ~(G - 1);
   const uint64_t gmask = (G == 64) ? ~0ull : ((1ull << G) - 1);
-  const int64_t groups_total = (int64_t)gridDim.x * (blockDim.x / G);
-  const int64_t gid = (int64_t)blockIdx.x * (blockDim.x / G) + threadIdx.x / G;
-  const DevIndex &ix = A.ix;
-  const DevCfg &cfg = A.cfg;
+  // the split count pass counts alignments with 32 bits (CountArgs::n_aln < 2^31)
+  constexpr bool CNT = std::is_same<Args, CountArgs>::value;
+  using Ix = typename std::conditional<CNT, uint32_t, int64_t>::type;
+  const uint32_t per_block = blockDim.x / G;
+  const Ix groups_total = (Ix)gridDim.x * per_block;
+  const Ix gid = (Ix)blockIdx.x * per_block + threadIdx.x / G;
+  const DevIndex &ix = proj_index(A);
+  const DevCfg &cfg = proj_cfg<PRE>(A);
   const uint32_t n_slab_off = 2 * ix.n_refs + 1;
-  const bool slab_in_lds = n_slab_off <= SLAB_LDS;
+  const bool slab_in_lds = n_slab_off <= SLAB_LDS;   // (a run-time test even for PRE = 1: as a constant it cost the main count kernel 0.03 ms)
   if (slab_in_lds) {
     for (uint32_t i = threadIdx.x; i < n_slab_off; i += blockDim.x) {
       sh_slab[i] = ix.slab_off[i];
@@ -710,10 +734,10 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(ProjectArgs A) {
 
   // EMIT: only the alignments with more than 64 candidate rows come here (the
   // rest is written by k_emit_dense); the count pass listed them in big_list.
-  if (EMIT && tot_over(A.tot, A.lim_m, A.lim_c)) return;
-  const int64_t n_work = EMIT ? (int64_t)*A.n_big : MODE == 2 ? (int64_t)*A.n_walk : A.n_aln;
-  for (int64_t w = gid; w < n_work; w += groups_total) {
-    const int64_t a = EMIT ? (int64_t)A.big_list[w] : MODE == 2 ? (int64_t)A.walk_list[w] : w;
+  if constexpr (EMIT) { if (tot_over(A.tot, A.lim_m, A.lim_c)) return; }
+  const Ix n_work = EMIT ? (Ix)*A.n_big : MODE == 2 ? (Ix)*A.n_walk : (Ix)A.n_aln;
+  for (Ix w = gid; w < n_work; w += groups_total) {
+    const Ix a = EMIT ? (Ix)A.big_list[w] : MODE == 2 ? (Ix)A.walk_list[w] : w;
     uint4 hd = A.head[a];
     uint4 hd2 = A.head2[a];
     uint32_t n_seg = hd.z;
@@ -730,7 +754,7 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(ProjectArgs A) {
     sb[1] = se[0];
 
     uint32_t lo[2] = {0, 0}, hi[2] = {0, 0};
-    if (EMIT) {
+    if constexpr (EMIT) {
       if (A.n_matches[a] == 0) continue;
       uint4 rg = A.ranges[a];
       lo[0] = rg.x; hi[0] = rg.y; lo[1] = rg.z; hi[1] = rg.w;
@@ -798,10 +822,9 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(ProjectArgs A) {
     if (EMIT || n_seg > 3) {
       uint32_t c0 = A.cigar_off[a];
       rd.seg = A.seg + (size_t)c0 + (size_t)a;
-      rd.real = A.cigar + c0;
-      if (EMIT) rd.n_real = A.cigar_off[a + 1] - c0;
+      if constexpr (EMIT) { rd.real = A.cigar + c0; rd.n_real = A.cigar_off[a + 1] - c0; }
     }
-    if (EMIT) {
+    if constexpr (EMIT) {
       moff = A.match_off[a]; cbase = A.cig_base[a];
       ideal_cap = 4u * n_seg + 2u;
       cap = rd.n_real + 2u * ideal_cap;
@@ -901,7 +924,7 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(ProjectArgs A) {
         }
         uint32_t rank = 0;
         bool do_emit = false;
-        if (!EMIT) {
+        if constexpr (!EMIT) {
           uint64_t m = (__ballot(alive) >> gbase) & gmask;
           total += (uint32_t)__popcll(m);
           if (base < 64) mask_all |= (G == 64) ? m : (m << base);
@@ -933,7 +956,8 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(ProjectArgs A) {
             do_emit = true;
           }
         }
-        if (EMIT && do_emit) {
+        if constexpr (EMIT) {
+          if (!do_emit) continue;
           uint32_t *slot = A.cig_arena + cbase + (uint64_t)rank * cap;
           uint32_t *lds = &sh_cig[(EMIT ? threadIdx.x : 0) * LDS_SLOT];
           bool ideal_lds = ideal_cap <= LDS_IDEAL;
@@ -2053,42 +2077,69 @@ void launch_segment(hipStream_t st, int64_t n_aln, const int32_t *ref_id, const 
                      xs, ts, cigar_off, cigar, cfg, n_refs, seg, meta, head, head2, fast_flag, X);
 }
 
-// part (count pass of the presets without the similarity filter, walk_list set): 0 = both kernels, 1 = the main one, 2 = the
-// one with the exon walk over the deferred alignments
+// the count pass in one kernel (the exon walk inline), or the emit pass over big_list
 template <int G>
-static void launch_project_g(hipStream_t st, const ProjectArgs &A, bool emit, int n_blocks, int part) {
+static void launch_project_g(hipStream_t st, const ProjectArgs &A, bool emit, int n_blocks) {
   bool simf = A.cfg.filter_by_similarity != 0;
   if (emit) {
     if (simf) hipLaunchKernelGGL((k_project<G, true, true>), dim3(n_blocks), dim3(256), 0, st, A);
     else hipLaunchKernelGGL((k_project<G, true, false>), dim3(n_blocks), dim3(256), 0, st, A);
   } else {
     if (simf) hipLaunchKernelGGL((k_project<G, false, true>), dim3(n_blocks), dim3(256), 0, st, A);
-    else if (A.walk_list) {
-      if (part != 2) hipLaunchKernelGGL((k_project<G, false, false, 1>), dim3(n_blocks), dim3(256), 0, st, A);
-      if (part != 1) hipLaunchKernelGGL((k_project<G, false, false, 2>), dim3(n_blocks), dim3(256), 0, st, A);
-    } else hipLaunchKernelGGL((k_project<G, false, false>), dim3(n_blocks), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((k_project<G, false, false>), dim3(n_blocks), dim3(256), 0, st, A);
   }
 }
 
-void launch_project(hipStream_t st, const ProjectArgs &A, bool emit, int group_lanes, int n_blocks, int part) {
+// (a grid of at most one group per alignment)
+static int project_blocks(int64_t n_aln, int group_lanes, int n_blocks) {
+  const int per_block = 256 / group_lanes;
+  const int64_t need = (n_aln + per_block - 1) / per_block;
+  if (need < n_blocks) n_blocks = (int)need;
+  return n_blocks < 1 ? 1 : n_blocks;
+}
+
+void launch_project(hipStream_t st, const ProjectArgs &A, bool emit, int group_lanes, int n_blocks) {
   if (!emit && A.ix.n_rows == 0) {
-    if (part == 2) return;  // empty annotation: nothing can match (and the kernel's clamped loads need one row)
+    // empty annotation: nothing can match (and the kernel's clamped loads need one row)
     (void)hipMemsetAsync(A.n_matches, 0, (size_t)A.n_aln * 4, st);
     (void)hipMemsetAsync(A.mask, 0, (size_t)A.n_aln * 8, st);
     (void)hipMemsetAsync(A.ranges, 0, (size_t)A.n_aln * sizeof(uint4), st);
     return;
   }
   if (A.n_aln <= 0) return;
-  int64_t groups = A.n_aln;
-  int per_block = 256 / group_lanes;
-  int64_t need = (groups + per_block - 1) / per_block;
-  if (need < n_blocks) n_blocks = (int)need;
-  if (n_blocks < 1) n_blocks = 1;
+  n_blocks = project_blocks(A.n_aln, group_lanes, n_blocks);
   switch (group_lanes) {
-    case 8: launch_project_g<8>(st, A, emit, n_blocks, part); break;
-    case 16: launch_project_g<16>(st, A, emit, n_blocks, part); break;
-    case 32: launch_project_g<32>(st, A, emit, n_blocks, part); break;
-    default: launch_project_g<64>(st, A, emit, n_blocks, part); break;
+    case 8: launch_project_g<8>(st, A, emit, n_blocks); break;
+    case 16: launch_project_g<16>(st, A, emit, n_blocks); break;
+    case 32: launch_project_g<32>(st, A, emit, n_blocks); break;
+    default: launch_project_g<64>(st, A, emit, n_blocks); break;
+  }
+}
+
+// part 1: the main kernel (defers what needs the exon walk to walk_list), part 2: the one with the walk over that list.
+// PRE = 1 for the short-read preset (no long-read rules, no small-exon rescue), the generic instantiation for the rest.
+template <int G>
+static void launch_count_g(hipStream_t st, const CountArgs &C, int n_blocks, int part) {
+  const bool pre = !C.long_reads && !C.ignore_small_exons;
+  const dim3 g(n_blocks), b(256);
+  if (part == 1) {
+    if (pre) hipLaunchKernelGGL((k_project<G, false, false, 1, 1, CountArgs>), g, b, 0, st, C);
+    else hipLaunchKernelGGL((k_project<G, false, false, 1, 0, CountArgs>), g, b, 0, st, C);
+  } else {
+    if (pre) hipLaunchKernelGGL((k_project<G, false, false, 2, 1, CountArgs>), g, b, 0, st, C);
+    else hipLaunchKernelGGL((k_project<G, false, false, 2, 0, CountArgs>), g, b, 0, st, C);
+  }
+}
+
+// (the caller takes the empty annotation to launch_project)
+void launch_count(hipStream_t st, const CountArgs &C, int group_lanes, int n_blocks, int part) {
+  if (C.n_aln == 0) return;
+  n_blocks = project_blocks(C.n_aln, group_lanes, n_blocks);
+  switch (group_lanes) {
+    case 8: launch_count_g<8>(st, C, n_blocks, part); break;
+    case 16: launch_count_g<16>(st, C, n_blocks, part); break;
+    case 32: launch_count_g<32>(st, C, n_blocks, part); break;
+    default: launch_count_g<64>(st, C, n_blocks, part); break;
   }
 }
 
