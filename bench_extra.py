@@ -8,6 +8,9 @@
   python bench_extra.py cli [--reads N] [--threads T]  the command line file to file (BGZF inflate, device path, BGZF deflate)
   python bench_extra.py sam [--reads N]  SAM text input: device parse time per chunk (hipEvents), text GB/s and records/s of
                                          br_sam_reader, and the command line file to file for the workload of `cli` as SAM and as BAM
+  python bench_extra.py collate [--reads N]  br_collator over N pairs' records (default 10 M pairs, ~20 M records) in HBM in a
+                                         random order, added in bundles of 1 M: add / finish / bundle-cut seconds, collator
+                                         peak device bytes per record, against br_bam_split_device over the same stream
   python bench_extra.py small            small calls: us per device-resident step at 1 .. 52 000 pairs (without the per-kernel
                                          events bench.py keeps on), the path without host round trips against the ordinary one,
                                          and br_project_group / br_project_groups host to host from plain C (profiles/group_latency.c)
@@ -25,7 +28,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
@@ -34,6 +37,57 @@ def main():
     import torch
     from bramble_amd import device as brdev
     from bramble_amd import lib, synth
+    if args.config == "collate":
+        import ctypes as C
+        n = args.reads or 10_000_000
+        ann = synth.Annotation("G")
+        batch = ann.reads(n, "pe", with_records=1)
+        stream, roff, rlen = synth.Annotation.frame_records(batch)
+        del batch
+        n_rec = len(roff)
+        perm = np.random.default_rng(7).permutation(n_rec)   # an order that is not collated (a coordinate sort scatters names alike)
+        d_blob = torch.from_numpy(stream).cuda()
+        d_off = torch.from_numpy(roff[perm].astype(np.int64)).cuda()
+        d_len = torch.from_numpy(rlen[perm].astype(np.int32)).cuda()
+        torch.cuda.synchronize()
+        runs = []
+        for step in range(args.warmup + args.steps):
+            c = lib.Collator(0)
+            t0 = time.perf_counter()
+            for a in range(0, n_rec, 1_000_000):
+                c.add_device(d_blob, d_off[a:a + 1_000_000], d_len[a:a + 1_000_000])
+            t1 = time.perf_counter()
+            _, n_grp = c.finish()
+            t2 = time.perf_counter()
+            n_b = 0
+            while c.next_records(1_000_000).n_aln:
+                n_b += 1
+            t3 = time.perf_counter()
+            st = c.stats()
+            c.close()
+            if step >= args.warmup:
+                runs.append({"add_s": round(t1 - t0, 4), "finish_s": round(t2 - t1, 4), "cut_s": round(t3 - t2, 4), "bundles": n_b,
+                             "groups": n_grp, "arena_bytes_per_record": round(st["arena_bytes"] / n_rec, 1),
+                             "peak_bytes_per_record": round(st["peak_bytes"] / n_rec, 1)})
+        # the same stream split into records on the device without collating (the reader's split step, no inflate)
+        idx = lib.Index.from_flat(ann.flat, device=0)
+        ctx = lib.Context(idx)
+        L = lib.lib()
+        L.br_bam_split_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(lib.BrDeviceRecords),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]
+        split = []
+        for step in range(args.warmup + args.steps):
+            recs, un, used = lib.BrDeviceRecords(), C.c_int64(), C.c_uint64()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lib.check(L.br_bam_split_device(ctx.h, C.c_void_p(d_blob.data_ptr()), stream.size, ann.n_refs, None, C.byref(recs), C.byref(un),
+                                            C.byref(used)), "br_bam_split_device")
+            torch.cuda.synchronize()
+            if step >= args.warmup:
+                split.append(round(time.perf_counter() - t0, 4))
+        print(json.dumps({"config": "collate", "pairs": n, "records": n_rec, "stream_bytes": int(stream.size), "runs": runs,
+                          "split_device_s": split}))
+        return
     if args.config == "small":
         import subprocess
         root = os.path.dirname(os.path.abspath(__file__))

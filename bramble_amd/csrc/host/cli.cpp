@@ -34,7 +34,7 @@ void usage(FILE *f) {
           " [--max-soft-clip N] [--max-junction-insertion N] [--max-junction-deletion N]\n"
           " [--max-error-exon N] [--similarity-threshold X]\n"
           " [--device-deflate | --host-deflate | --compression-level 0-9] [--device-reader | --host-reader] [--bundle-size N]\n"
-          "               [--device N | --devices a,b,...]\n\n"
+          "               [--device N | --devices a,b,...] [--collate]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -42,7 +42,8 @@ void usage(FILE *f) {
           "the output keeps the input order.\n"
           "The input is BAM or SAM text (a file, or standard input as -), told apart by its bytes; SAM lines become BAM\n"
           "records on the GPU.  --device-reader / --host-reader choose how BAM is read and do not apply to SAM.\n"
-          "BGZF-compressed SAM and plain gzip input are not supported.\n");
+          "BGZF-compressed SAM and plain gzip input are not supported.\n"
+          "--collate: input in any order (e.g. coordinate-sorted); the whole input is read into one device's memory and grouped by read name before the first bundle is projected.\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -81,6 +82,7 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (a == "--device-deflate") o.device_deflate = true;
     else if (a == "--device-reader") o.device_reader = 1;
     else if (a == "--host-reader") o.device_reader = 0;
+    else if (a == "--collate") o.collate = true;
     else if (a == "--device") { const char *v = value(); if (!v) return -1; o.devices.assign(1, atoi(v)); }
     else if (a == "--devices") {
       const char *v = value(); if (!v) return -1;
@@ -96,6 +98,7 @@ int parse_args(int argc, char **argv, Options &o) {
   if (o.out_bam.empty()) { fprintf(stderr, "--out is required\n"); return -1; }
   if (o.gff.empty()) { fprintf(stderr, "--guide is required\n"); return -1; }
   if (!o.fasta.empty()) o.cfg.use_fasta = 1;
+  if (o.collate && o.devices.size() > 1) { fprintf(stderr, "--collate works on one device: give --device N, not a --devices list\n"); return -1; }
   return 0;
 }
 
@@ -361,6 +364,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
   Outbox out;
   std::string err;
   std::unique_ptr<Input> in = open_input(o, err);
+  if (in && o.collate) in = open_collate(o, std::move(in));
   if (!in || !in->start(out, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return 1; }
 
   // the input is already being read while the guides are parsed and the indexes are built

@@ -32,6 +32,7 @@ struct Options {
   int64_t bundle_records = 1000000;   // (1 M: 1.20 s inside the program for 20.9 M alignments, 2 M: 1.38 s, 0.5 M: 1.47 s; the pinned result buffers scale with it)
   bool quiet = false;
   bool device_deflate = true;   // BGZF blocks made on the GPU unless a host level is asked for
+  bool collate = false;          // --collate: the whole input is read into one device's memory and regrouped by read name first
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };
 inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
@@ -148,5 +149,7 @@ class DevInput : public Input {
 std::unique_ptr<Input> open_input(const Options &o, std::string &err);
 // stream_fd >= 0: a stream open_input has begun to read (peek = its first bytes); else the regular file at o.in_bam
 std::unique_ptr<Input> open_sam(const Options &o, int stream_fd, const std::string &peek, std::string &err);
+// --collate: `inner` (what open_input opened) read whole into a br_collator on o.devices[0], its read-name groups dealt from there
+std::unique_ptr<Input> open_collate(const Options &o, std::unique_ptr<Input> inner);
 
 }  // namespace brcli

@@ -165,6 +165,8 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_pin_host", "br_unpin_host", "br_project_group", "br_project_groups", "br_bam_encode_device", "br_project_bam_device", "br_project_bam_bundle", "br_bam_bundle_stage", "br_project_bam_staged", "br_bam_split", "br_annotation_load", "br_annotation_load_mt", "br_annotation_free",
            "br_annotation_num_transcripts", "br_annotation_transcripts", "br_annotation_num_refs", "br_annotation_refnames", "br_cli_main", "br_cli_exit_at_end", "br_device_warmup", "br_project_bam_staged_nowait", "br_host_bam_wait", "br_bgzf_scan", "br_bgzf_inflate_device", "br_bam_split_device", "br_bam_reader_new", "br_bam_reader_next", "br_bam_reader_set_piece_blocks", "br_bam_reader_release", "br_bam_reader_free", "br_bam_piece_upload", "br_bam_piece_process", "br_bam_reader_seconds", "br_bam_reader_upload_seconds", "br_project_bam_resident", "br_bgzf_write_file", "br_bgzf_read_file",
            "br_sam_header_scan", "br_sam_reader_new", "br_sam_reader_next", "br_sam_reader_upload", "br_sam_reader_next_staged", "br_sam_reader_release", "br_sam_reader_free", "br_sam_reader_error", "br_sam_reader_stats",
+           "br_collator_new", "br_collator_add", "br_collator_finish", "br_collator_next", "br_collator_order", "br_collator_set_param",
+           "br_collator_stats", "br_collator_free",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -622,6 +624,22 @@ class Context:
             return torch.zeros(0, dtype=torch.uint8, device=src.device)
         return torch.as_tensor(_DevArray(out.value, n.value, "|u1"), device=src.device)
 
+    def project_bam_resident(self, cfg, recs, ref_map):
+        """br_project_bam_resident over a BrDeviceRecords that is in HBM already (a reader's or a Collator's bundle):
+        (stream uint8[], counters dict) as project_bam_bundle."""
+        rm = np.ascontiguousarray(ref_map, dtype=np.int32)
+        out = BrHostBam()
+        L = lib()
+        L.br_project_bam_resident.argtypes = [C.c_void_p, _P(BrConfig), _P(BrDeviceRecords), C.c_void_p, C.c_int32, C.c_int, C.c_int,
+                                              _P(BrHostBam)]
+        check(L.br_project_bam_resident(self.h, C.byref(cfg), C.byref(recs), rm.ctypes.data, len(rm), 0, 0, C.byref(out)),
+              "br_project_bam_resident")
+        n = int(out.n_bytes)
+        data = np.ctypeslib.as_array(C.cast(out.data, _P(C.c_uint8)), shape=(n,)).copy() if n else np.zeros(0, np.uint8)
+        return data, {"n_rows": int(out.n_rows), "total_complete": int(out.total_complete),
+                      "total_unique": int(out.total_unique), "dropped_reads": int(out.dropped_reads),
+                      "total_processed": int(out.total_processed)}
+
     def project_bam_bundle(self, cfg, blob, rec_off, rec_len, ref_map, bgzf_on_device=False):
         """Host form: numpy blob / rec_off (uint64) / rec_len (uint32) in, (stream uint8[], counters dict) out."""
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
@@ -842,6 +860,101 @@ class SamReader:
     def close(self):
         if self.h:
             lib().br_sam_reader_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Collator:
+    """br_collator on `device`: mapped records in any order in, bundles of whole read-name groups out (groups in the order of
+    their first record, records in input order inside a group)."""
+
+    def __init__(self, device=0):
+        L = lib()
+        L.br_collator_new.argtypes = [C.c_int, _P(C.c_void_p)]
+        L.br_collator_add.argtypes = [C.c_void_p, _P(BrDeviceRecords), C.c_int, C.c_void_p]
+        L.br_collator_finish.argtypes = [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]
+        L.br_collator_next.argtypes = [C.c_void_p, C.c_int64, _P(BrDeviceRecords)]
+        L.br_collator_order.argtypes = [C.c_void_p, C.c_void_p]
+        L.br_collator_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+        L.br_collator_stats.argtypes = [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double)]
+        L.br_collator_free.argtypes = [C.c_void_p]
+        self.h = None
+        self.device = device
+        self.n = 0
+        h = C.c_void_p()
+        check(L.br_collator_new(device, C.byref(h)), "br_collator_new")
+        self.h = h
+
+    def set_param(self, name, value):
+        check(lib().br_collator_set_param(self.h, name.encode(), int(value)), "br_collator_set_param")
+
+    def add_records(self, recs, on_device, stream=None):
+        """br_collator_add as it is: the return code (0, or a BR_ERR_* value)."""
+        return lib().br_collator_add(self.h, C.byref(recs), 1 if on_device else 0, C.c_void_p(stream or 0))
+
+    def add_host(self, stream_np):
+        """An uncompressed BAM alignment section in host memory ([block_size][record]..., unmapped records skipped)."""
+        data = np.ascontiguousarray(stream_np, dtype=np.uint8)
+        off, ln, _, used = bam_split(data)
+        assert used == data.size
+        recs = BrDeviceRecords(data.ctypes.data if data.size else None, off.ctypes.data if off.size else None, len(off),
+                               ln.ctypes.data if ln.size else None)
+        check(self.add_records(recs, False), "br_collator_add")
+
+    def add_device(self, blob, rec_off, rec_len):
+        """torch CUDA tensors: blob uint8 (each record's block_size in the 4 bytes in front of rec_off[i]), rec_off int64 [n],
+        rec_len int32 [n]."""
+        import torch
+        recs = BrDeviceRecords(blob.data_ptr(), rec_off.data_ptr(), rec_len.numel(), rec_len.data_ptr())
+        check(self.add_records(recs, True, torch.cuda.current_stream(blob.device).cuda_stream), "br_collator_add")
+
+    def finish(self):
+        n, g = C.c_int64(), C.c_int64()
+        check(lib().br_collator_finish(self.h, C.byref(n), C.byref(g)), "br_collator_finish")
+        self.n = int(n.value)
+        return self.n, int(g.value)
+
+    def order(self):
+        out = np.zeros(max(self.n, 1), dtype=np.int64)
+        check(lib().br_collator_order(self.h, out.ctypes.data), "br_collator_order")
+        return out[:self.n]
+
+    def next_records(self, max_records):
+        """The next bundle as a BrDeviceRecords in HBM (n_aln = 0 at the end)."""
+        recs = BrDeviceRecords()
+        check(lib().br_collator_next(self.h, int(max_records), C.byref(recs)), "br_collator_next")
+        return recs
+
+    def stats(self):
+        a, p, ad, fi = C.c_uint64(), C.c_uint64(), C.c_double(), C.c_double()
+        check(lib().br_collator_stats(self.h, C.byref(a), C.byref(p), C.byref(ad), C.byref(fi)), "br_collator_stats")
+        return {"arena_bytes": int(a.value), "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value}
+
+    def bundles(self, max_records):
+        """Yields each bundle's records as a numpy copy: uint8 [block_size][record]... in output order."""
+        import torch
+        from .device import _DevArray
+        dev = "cuda:%d" % self.device
+        arena = None
+        while True:
+            recs = self.next_records(max_records)
+            n = int(recs.n_aln)
+            if n == 0:
+                return
+            if arena is None:
+                arena = torch.as_tensor(_DevArray(recs.blob, self.stats()["arena_bytes"], "|u1"), device=dev).cpu().numpy()
+            off = torch.as_tensor(_DevArray(recs.rec_off, n, "<u8"), device=dev).cpu().numpy().astype(np.int64)
+            ln = torch.as_tensor(_DevArray(recs.rec_len, n, "<i4"), device=dev).cpu().numpy().view(np.uint32).astype(np.int64)
+            yield np.concatenate([arena[o - 4:o + l] for o, l in zip(off, ln)]).astype(np.uint8)
+
+    def close(self):
+        if self.h:
+            lib().br_collator_free(self.h)
             self.h = None
 
     def __del__(self):

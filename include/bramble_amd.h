@@ -559,6 +559,36 @@ const char *br_sam_reader_error(const br_sam_reader *);   /* the reason of the l
 int br_sam_reader_stats(const br_sam_reader *, double *upload_seconds, double *parse_seconds, int64_t *chunks, uint64_t *bytes,
                         int64_t *lines);
 
+/* A collator: the mapped records of a whole input, in any order, in one device's HBM; bundles of whole read-name groups out,
+ * for br_project_bam_resident.  Its output is C(input): groups in the order of their first record, records in input order
+ * inside a group (a stable grouping: an input that is collated already comes out unchanged).  A name is l_read_name and the
+ * read_name bytes, compared byte for byte.
+ *   br_collator_new        BR_ERR_NO_DEVICE without the device
+ *   br_collator_add        copies the records (device memory with on_device != 0, after the work queued on `stream`, which may
+ *                          be NULL for the null stream; host memory with on_device = 0) into the collator's arena, [block_size][record] each (the 4
+ *                          bytes in front of rec_off[i] are the block_size); returns when the copy is done, so the caller may
+ *                          reuse the records.  BR_ERR_CAPACITY when the arena would exceed "max_bytes" or the device's memory
+ *                          (the collator may still be freed), BR_ERR_INVALID_ARG after finish
+ *   br_collator_finish     key, radix sort, collisions, placement (collate_kernels.hip); the counts of records and groups
+ *   br_collator_next       the next bundle: whole groups, max_records or more up to the first group start at or behind that
+ *                          (a group larger than max_records alone); n_aln = 0 at the end.  blob is the arena and rec_off / rec_len
+ *                          point into it (the offsets are not monotone); valid until br_collator_free
+ *   br_collator_order      host: the input index (position among the added records) of every output record
+ *   br_collator_set_param  before the first add: "max_bytes" (arena cap, 0 = none), "hash_bits" (test hook: 0..64 bits of the
+ *                          name hash are kept, so that different names collide; the result does not change)
+ *   br_collator_stats      arena bytes, the most device memory the collator has held, seconds in add and in finish
+ * The arena grows by allocating a larger buffer and copying.  Per record the collator holds the arena's 4 + block_size bytes
+ * and 12 bytes of tables while adding, 64 bytes during finish, 24 afterwards (collate.cpp). */
+typedef struct br_collator br_collator;
+int br_collator_new(int device, br_collator **out);
+int br_collator_add(br_collator *, const br_device_records *recs, int on_device, void *stream);
+int br_collator_finish(br_collator *, int64_t *n_records, int64_t *n_groups);
+int br_collator_next(br_collator *, int64_t max_records, br_device_records *bundle);
+int br_collator_order(const br_collator *, int64_t *order);
+int br_collator_set_param(br_collator *, const char *name, int64_t value);
+int br_collator_stats(const br_collator *, uint64_t *arena_bytes, uint64_t *peak_bytes, double *add_seconds, double *finish_seconds);
+void br_collator_free(br_collator *);
+
 /* br_project_bam_staged / _nowait for records that are in HBM already (a br_bam_reader bundle, or br_bam_split_device's) */
 int br_project_bam_resident(br_ctx *, const br_config *, const br_device_records *recs, const int32_t *ref_map, int32_t n_ref_map,
                             int bgzf_on_device, int nowait, br_host_bam *out);
