@@ -218,6 +218,7 @@ static void finish_call(br_ctx *c, const DevCfg &dc, const br_device_batch *b, b
   c->counters[6] = n_matches;
   c->last_n_rows = (int64_t)n_rows; c->last_n_aln = b->n_aln; c->last_n_pool = (int64_t)n_pool;
   c->last_aux_cols = aux_cols; c->wide_valid = false; c->detail_valid = false; c->last_l_qseq = b->l_qseq; c->last_long_reads = dc.long_reads;
+  c->last_direct = false;   // (run_device_direct says otherwise after this)
 }
 
 // Small batches (a read-name group, the 64 groups a bramble-cli worker holds, the 100 k alignments of a reference bundle):
@@ -578,41 +579,15 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
   return BR_OK;
 }
 
-// The HIP pipeline over a device-resident batch: small and speculative batches (run_device_small), direct rows
-// (run_device_direct), or the match table below (presets with the similarity filter, -S, direct_rows = 0).
-int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStream_t st, br_device_rows *out, bool keep_events) {
+// The match-table path: segment -> count -> scan (host wait: sizes) -> k_expand -> k_emit_dense (|| k_project<64,true>)
+// -> k_pair -> scan (host wait: sizes) -> k_pair<true> -> k_primary -> k_rows.  The -S rescue plans, runs and applies its
+// DP between the count and the scan.
+static int run_match_table(br_ctx *c, const DevCfg &dc, const br_device_batch *b, hipStream_t st, br_device_rows *out, Prof &pf,
+                           bool keep_events) {
   const br_index *ix = c->ix;
-  memset(out, 0, sizeof(*out));
-  DevCfg dc;
-  RC(make_devcfg(cfg, dc));
-  // -S only changes long-read runs (src/evaluate.cpp:916-919,939)
   const bool fa_mode = dc.use_fasta && dc.long_reads;
-  if (fa_mode && (!ix->has_seq || !b->seq_src || !b->seq_off || !b->seqs)) return BR_ERR_INVALID_ARG;
-  int64_t n = b->n_aln, ng = b->n_groups;
-  if (n < 0 || ng < 0 || n >= 0x7fffffffll || b->n_cigar_words >= 0xffffffffll - n) return BR_ERR_CAPACITY;
-  HIPCHK(hipSetDevice(ix->device));
-  Prof pf{c, st};
-  if (!keep_events) c->events_used = 0;
-  out->total_processed = (uint64_t)n;
-  c->last_n_rows = 0; c->last_n_aln = n; c->last_n_pool = 0; c->wide_valid = false; c->last_aux_cols = false; c->last_direct = false;
-  c->last_l_qseq = b->l_qseq; c->last_long_reads = dc.long_reads;
-  if (n == 0) { pf.collect(); return BR_OK; }
-  if (!fa_mode && c->small_batch && ix->dev.n_rows != 0) {
-    // small batches always; large ones when an earlier call left tables and counts to predict from (same preset class)
-    const bool small = n <= c->small_n;
-    // (up to speculate_n alignments: at 20 M alignments the three waits are 2 % of the step and the 15 % of empty blocks in
-    // the predicted grids cost as much, profiles/r03/ab_speculate.log; at 0.1-1 M alignments the step gets 6-13 % shorter)
-    const bool big = !small && n <= c->speculate_n && c->speculate && c->hist_n > 0 && c->hist_simf == (dc.filter_by_similarity != 0);
-    if (small || big) {
-      const int rc = run_device_small(c, dc, b, st, out, pf, keep_events, big);
-      if (rc != BR_RETRY_ORDINARY) return rc;
-      if (!keep_events) c->events_used = 0;
-    }
-  }
-
-  if (!fa_mode && !dc.filter_by_similarity && c->direct_rows) return run_device_direct(c, dc, b, st, out, pf, keep_events);
-
-  int64_t tiles = std::max<int64_t>(scan_tiles_for(std::max<int64_t>(n, ng) + 1), 1);
+  const int64_t n = b->n_aln, ng = b->n_groups;
+  const int64_t tiles = std::max<int64_t>(scan_tiles_for(std::max<int64_t>(n, ng) + 1), 1);
   RC(ensure_count_tables(c, b));
   RC(c->n_matches.ensure((size_t)n * 4)); RC(c->fast_pre.ensure((size_t)(n + 1) * 4)); RC(c->match_off.ensure((size_t)(n + 1) * 4));
   RC(c->tile_sums.ensure((size_t)tiles * 8 * 3)); RC(c->counters_d.ensure(4 * 8));
@@ -629,7 +604,7 @@ int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStr
   A.fast_pre = c->fast_pre.as<uint32_t>(); A.match_off = c->match_off.as<uint32_t>(); A.cig_base = c->cig_base.as<uint64_t>();
   HIPCHK(hipMemsetAsync(c->n_big.p, 0, 8, st));
   A.n_big = c->n_big.as<uint32_t>(); A.walk_list = c->walk_list.as<uint32_t>(); A.n_walk = c->n_big.as<uint32_t>() + 1;
-  int n_blocks = c->n_cu * c->blocks_per_cu;
+  const int n_blocks = c->n_cu * c->blocks_per_cu;
   ScanArgs S{};
   S.n = n; S.src32 = c->n_matches.as<uint32_t>(); S.cigar_off = b->cigar_off; S.head = c->head.as<uint4>();
   S.tile_sums = c->tile_sums.as<uint64_t>(); S.fast_flag = c->fast_flag.as<uint32_t>();
@@ -821,6 +796,42 @@ int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStr
   return BR_OK;
 }
 
+// The HIP pipeline over a device-resident batch: small and speculative batches (run_device_small), direct rows
+// (run_device_direct), or the match table (run_match_table: presets with the similarity filter, -S, direct_rows = 0).
+int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStream_t st, br_device_rows *out, bool keep_events) {
+  const br_index *ix = c->ix;
+  memset(out, 0, sizeof(*out));
+  DevCfg dc;
+  RC(make_devcfg(cfg, dc));
+  // -S only changes long-read runs (src/evaluate.cpp:916-919,939)
+  const bool fa_mode = dc.use_fasta && dc.long_reads;
+  if (fa_mode && (!ix->has_seq || !b->seq_src || !b->seq_off || !b->seqs)) return BR_ERR_INVALID_ARG;
+  const int64_t n = b->n_aln, ng = b->n_groups;
+  if (n < 0 || ng < 0 || n >= 0x7fffffffll || b->n_cigar_words >= 0xffffffffll - n) return BR_ERR_CAPACITY;
+  HIPCHK(hipSetDevice(ix->device));
+  Prof pf{c, st};
+  if (!keep_events) c->events_used = 0;
+  out->total_processed = (uint64_t)n;
+  c->last_n_rows = 0; c->last_n_aln = n; c->last_n_pool = 0; c->wide_valid = false; c->last_aux_cols = false; c->last_direct = false;
+  c->last_l_qseq = b->l_qseq; c->last_long_reads = dc.long_reads;
+  if (n == 0) { pf.collect(); return BR_OK; }
+  if (!fa_mode && c->small_batch && ix->dev.n_rows != 0) {
+    // small batches always; large ones when an earlier call left tables and counts to predict from (same preset class)
+    const bool small = n <= c->small_n;
+    // (up to speculate_n alignments: at 20 M alignments the three waits are 2 % of the step and the 15 % of empty blocks in
+    // the predicted grids cost as much, profiles/r03/ab_speculate.log; at 0.1-1 M alignments the step gets 6-13 % shorter)
+    const bool big = !small && n <= c->speculate_n && c->speculate && c->hist_n > 0 && c->hist_simf == (dc.filter_by_similarity != 0);
+    if (small || big) {
+      const int rc = run_device_small(c, dc, b, st, out, pf, keep_events, big);
+      if (rc != BR_RETRY_ORDINARY) return rc;
+      if (!keep_events) c->events_used = 0;
+    }
+  }
+
+  if (!fa_mode && !dc.filter_by_similarity && c->direct_rows) return run_device_direct(c, dc, b, st, out, pf, keep_events);
+  return run_match_table(c, dc, b, st, out, pf, keep_events);
+}
+
 // br_row_x of the last call's rows, derived on first request (k_rows_detail)
 int ensure_detail(br_ctx *c, hipStream_t st) {
   if (c->detail_valid) return BR_OK;
@@ -927,19 +938,14 @@ extern "C" int br_ctx_collect_counters(br_ctx *c, const br_device_batch *b, void
   HIPCHK(hipSetDevice(c->ix->device));
   if (c->last_direct) {
     // The formula's B_out counts the rewritten CIGAR words of every MATCH (the evaluator's output, before pairing), and
-    // only the match table holds those: this diagnostic projects the batch once more through the match-table path (never timed).
-    br_config cfgc; memset(&cfgc, 0, sizeof(cfgc)); cfgc.junc_miss_discount = 1.0;
-    const DevCfg &d = c->dA.cfg;
-    cfgc.lr = d.long_reads; cfgc.fr = d.fr; cfgc.rf = d.rf;
-    cfgc.has_max_clip = 1; cfgc.max_clip = d.max_clip; cfgc.has_max_junc_ins = 1; cfgc.max_junc_ins = d.max_junc_ins;
-    cfgc.has_max_junc_gap = 1; cfgc.max_junc_gap = d.max_junc_gap; cfgc.has_max_error_exon = 1; cfgc.max_error_exon = d.max_error_exon;
-    cfgc.has_sim_thr = 1; cfgc.sim_thr = 1.0f;
-    const int keep_direct = c->direct_rows, keep_small = c->small_batch;
-    c->direct_rows = 0; c->small_batch = 0;
+    // only the match table holds those: this diagnostic projects the batch once more through the match-table path, with the
+    // configuration of the last call (never timed; the row tables are then that projection's)
+    const DevCfg dc = c->dA.cfg;
+    Prof pf{c, st};
+    c->events_used = 0;
     br_device_rows tmp;
-    const int rc = run_device(c, &cfgc, b, st, &tmp);
-    c->direct_rows = keep_direct; c->small_batch = keep_small;
-    if (rc) return rc;
+    memset(&tmp, 0, sizeof(tmp));
+    RC(run_match_table(c, dc, b, st, &tmp, pf, false));
   }
   RC(c->totals.ensure(16 * 8));
   DevBuf stats; RC(stats.ensure(8 * 8));   // (freed on the way out)

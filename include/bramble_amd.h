@@ -709,7 +709,8 @@ int br_ctx_kernel_ms(br_ctx *, int which, double *ms, int32_t *launches);
 /* ... summed over every call since br_ctx_set_profiling(ctx, 1) (a timed loop reads it once, behind its last step) */
 int br_ctx_kernel_ms_sum(br_ctx *, int which, double *ms, int64_t *launches);
 /* Diagnostic pass (never part of a timed region): computes the exact counters below
- * for the device batch the context projected last. */
+ * for the device batch the context projected last.  After a direct-rows call it projects the batch once more through
+ * the match-table path with that call's configuration: the context's last-call row tables are then that projection's. */
 int br_ctx_collect_counters(br_ctx *, const br_device_batch *, void *stream);
 /* Exact algorithmic byte counters (SURVEY.md 8d formula), after br_ctx_collect_counters:
  * out[0]=B_in, out[1]=B_idx, out[2]=B_out, out[3]=sum n_cigar, out[4]=read exons,

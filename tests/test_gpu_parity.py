@@ -378,8 +378,8 @@ def test_single_kernel_forms_of_the_split_passes():
 
 def test_short_read_paths_equal_oracle_at_dense_loci():
     """Every short-read pipeline a context can choose -- the default (small-batch path; the larger batches here: direct
-    rows, then the launch from the last call's counts), small_batch = 0 (direct rows) and small_batch = 0 with
-    direct_rows = 0 (the match-table path) -- against the oracle: the short-read presets and their options, both group
+    rows both times, a direct-rows call leaves nothing to predict the next call from), small_batch = 0 (direct rows) and
+    small_batch = 0 with direct_rows = 0 (the match-table path) -- against the oracle: the short-read presets and their options, both group
     widths, a dense locus (> 64 candidate rows, > 32 survivors), pairs turned unpaired (every match emitted), long
     CIGARs under the short-read preset; two calls per context, the second starting from the state the first one left."""
     cases = []
@@ -422,27 +422,76 @@ def test_short_read_paths_equal_oracle_at_dense_loci():
 
 
 def test_large_batches_launched_from_the_last_calls_counts():
-    """Batches beyond `small_n` alignments on a context that has projected before are launched without the three host round
-    trips of the ordinary pipeline: tables as earlier calls left them, emit / row grids from the LAST call's counts scaled to the
-    batch (+15 %), one check at the end, the ordinary pipeline again when a table or a grid fell short.  Same rows as the
-    oracle whatever the order of batches: equal ones (prediction exact), a smaller one, one with far more matches per alignment
-    than predicted (falls back and grows the tables), and the long-read preset in between (other kernels, other tables)."""
+    """Batches beyond `small_n` alignments are launched without the three host round trips of the match-table path when the
+    last call that could predict them (a small call, or a call of a similarity-filter preset on the match table) left tables
+    and counts to size from: tables as those calls left them, emit / row grids from the last call's counts scaled to the batch
+    (+15 %), one check at the end, the ordinary pipeline again when a table or a grid fell short.  A direct-rows call
+    predicts nothing: the short-read batches speculate only right after the small call, and take direct rows again once one
+    has fallen back or run direct rows.  The route of every call is read from the kernel timers: direct rows launch
+    k_pair_mask, the ordinary match-table path k_group_ids, and the predicted launch neither (k_segment labels the groups).
+    Same rows as the oracle whatever the order of batches: equal ones (prediction exact), smaller ones, one with far more
+    matches per alignment than predicted (falls back), the two preset classes in turn."""
     ann = synth.Annotation("G", n_genes=4000, n_refs=4)
     annd = ann.as_dict()
     oi = ob.OracleIndex(annd)
-    batches = {"a": ann.reads(40000, "pe"), "b": ann.reads(34000, "pe", seed=77), "c": ann.reads(45000, "pe", seed=78, p_multimap=0.5),
-               "h": ann.reads(70000, "hifi", seed=79)}
-    for k in ("a", "b", "c"):
+    batches = {"s": ann.reads(25000, "pe", seed=76), "a": ann.reads(40000, "pe"), "b": ann.reads(34000, "pe", seed=77),
+               "c": ann.reads(45000, "pe", seed=78, p_multimap=0.5), "h": ann.reads(70000, "hifi", seed=79),
+               "h2": ann.reads(70000, "hifi", seed=80), "hs": ann.reads(67000, "hifi", seed=81)}
+    hl = dict(batches["h2"])   # the same alignments, nine in ten of them unmapped: far fewer matches per alignment
+    hl["ref_id"] = np.where(np.arange(hl["n_aln"]) % 10 == 0, hl["ref_id"], -1).astype(np.int32)
+    batches["hl"] = hl
+    assert batches["s"]["n_aln"] <= 65536
+    for k in ("a", "b", "c", "h", "h2", "hs", "hl"):
         assert batches[k]["n_aln"] > 65536
     want = {}
-    for k, flags in (("a", {}), ("b", {}), ("c", {}), ("h", {"lr_hq": 1})):
-        want[k], _, _ = ob.run(oi, ob.make_flags(**flags), batches[k], want_matches=False)
+    for k in batches:
+        want[k], _, _ = ob.run(oi, ob.make_flags(**({"lr_hq": 1} if k[0] == "h" else {})), batches[k], want_matches=False)
+    group_ids, pair_mask = lib.KERNEL_NAMES[lib.K_GROUP_IDS], lib.KERNEL_NAMES[lib.K_PAIR_MASK]
+    # (call, route with speculate = 1, with speculate = 0); None: not asserted (a fallback depends on the counts)
+    seq = [("s", "predicted", "predicted"), ("a", "predicted", "direct"), ("a", "predicted", "direct"), ("b", "predicted", "direct"),
+           ("c", None, "direct"), ("a", None, "direct"), ("h", "ordinary", "ordinary"), ("h", "predicted", "ordinary"),
+           ("h2", "predicted", "ordinary"), ("hs", "predicted", "ordinary"), ("hl", "predicted", "ordinary"),
+           ("h", "ordinary", "ordinary"), ("c", "direct", "direct"), ("b", "direct", "direct")]
     idx = lib.Index(annd, device=0)
     for spec in (1, 0):
         ctx = lib.Context(idx)
         ctx.set_param("speculate", spec)
-        for k in ("a", "a", "b", "c", "a", "h", "h", "c", "b"):
-            flags = {"lr_hq": 1} if k == "h" else {}
+        ctx.set_profiling(True)
+        for k, route1, route0 in seq:
+            flags = {"lr_hq": 1} if k[0] == "h" else {}
             assert_rows_equal(ctx.project_batch(lib.make_config(**flags), batches[k]), want[k])
+            launches = ctx.kernel_ms()
+            route = "direct" if launches[pair_mask][1] else "ordinary" if launches[group_ids][1] else "predicted"
+            expect = route1 if spec else route0
+            assert expect is None or route == expect, (spec, k, route, expect)
         ctx.close()
+    idx.close()
+
+
+@pytest.mark.parametrize("flags", [{}, {"strict": 1}, {"max_clip": 2, "max_junc_ins": 3, "max_junc_gap": 3}])
+def test_collect_counters_after_direct_rows(flags):
+    """The algorithmic-bytes counters after a direct-rows call (the diagnostic projects the batch once more through the
+    match-table path, with the last call's configuration) equal those after a small-path call of the same batch (its match
+    table is still resident); the context then projects on as before."""
+    from bramble_amd import device as brdev
+    ann = synth.Annotation("S")
+    b = ann.reads(10000, "pe")
+    cfg = lib.make_config(**flags)
+    orc, _, _ = ob.run(ob.OracleIndex(ann.as_dict()), ob.make_flags(**flags), b, want_matches=False)
+    idx = lib.Index(ann.as_dict(), device=0)
+    db = brdev.upload_batch(b, "cuda:0")
+    got = {}
+    for name, params in (("small", {}), ("direct", {"small_batch": 0})):
+        ctx = lib.Context(idx)
+        for k, v in params.items():
+            ctx.set_param(k, v)
+        ctx.set_profiling(True)
+        rows = ctx.project_batch_device(cfg, db)
+        assert (ctx.kernel_ms()[lib.KERNEL_NAMES[lib.K_PAIR_MASK]][1] > 0) == (name == "direct")
+        assert int(rows.n_rows) == orc["n_rows"]
+        got[name] = ctx.collect_counters(db)
+        assert_rows_equal(ctx.project_batch(cfg, b), orc)
+        ctx.close()
+    assert got["direct"] == got["small"]
+    assert got["small"]["matches"] >= orc["n_rows"] > 1000
     idx.close()
