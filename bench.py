@@ -8,14 +8,16 @@ the workload is BASELINE.json configs[1] (paired-end short reads vs a GENCODE-sh
 annotation, 1 x MI355X); N>1 shards read-name groups across ranks (one process per GPU, a
 private index replica each, no collective on the data path) -- weak scaling.
 
-  python bench.py --gpus N --steps K --warmup W [--pairs P] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--pairs P] [--dump-outputs DIR] [--full]
 
 --dump-outputs DIR: rank 0 writes the rows its last timed step returned as DIR/<name>.npy (float64, a seeded sample
 of at most 64 MB; see dump_outputs), so that two builds can be compared output for output on the same inputs.
 
-Rank 0 prints ONE JSON line (contract in the task statement):
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, dumps (when asked) and prints the headline:
   value / ms_per_step   device-resident: the batch is already in HBM when the timed region starts and the packed
-                        rows stay in HBM (said in config.workload);
+                        rows stay in HBM (said in config.workload); the per-kernel hipEvent times of the timed steps
+                        (kernel_ms_per_step) come with it.
+--full adds the legs that take runs of their own (--no-pcie / --no-cpu-baseline leave one of them out):
   pcie_inclusive        the same batch from pinned host arrays to packed rows in pinned host memory through the
                         staged C ABI (br_batch_stage / br_project_staged / br_host_rows_wait): batch k+1 uploads and
                         batch k-1 downloads while batch k is projected;
@@ -65,9 +67,12 @@ def main():
     ap.add_argument("--pairs", type=int, default=int(os.environ.get("BENCH_PAIRS", 10_000_000)),
                     help="read pairs per GPU per step (BASELINE configs[1]: 10M)")
     ap.add_argument("--group-lanes", type=int, default=int(os.environ.get("BRAMBLE_AMD_GROUP_LANES", 0)))
-    ap.add_argument("--cpu-sample", type=int, default=400_000, help="alignments in the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the PCIe-inclusive leg, the roofline (a counter pass of its own) "
+                         "and the CPU baseline")
+    ap.add_argument("--cpu-sample", type=int, default=400_000, help="alignments in the CPU-baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-pcie", action="store_true", help="--full without the PCIe-inclusive leg")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's rows (rank 0) to DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
@@ -183,11 +188,11 @@ def main():
     per_rank_aln = gather_all(n_aln)
     elapsed, total_aln = reduce_max_sum(elapsed, n_aln)
     n_rows, n_matches = int(rows.n_rows), int(rows.n_matches)
-    counters = ctx.collect_counters(dbatch, stream) if rank == 0 else None
+    counters = ctx.collect_counters(dbatch, stream) if args.full and rank == 0 else None
 
-    # ---- leg 2: PCIe-inclusive (pinned host arrays in, packed rows in pinned host memory out) ----
+    # ---- leg 2 (--full): PCIe-inclusive (pinned host arrays in, packed rows in pinned host memory out) ----
     pcie = None
-    if not args.no_pcie:
+    if args.full and not args.no_pcie:
         pinned = {"n_aln": n_aln, "seq_off": None, "seqs": None}
         for name, dt in (("ref_id", np.int32), ("ref_start", np.int32), ("flags", np.uint16), ("xs", np.int8),
                          ("ts", np.int8), ("cigar_off", np.uint64), ("cigar", np.uint32), ("mate_ref_id", np.int32),
@@ -238,53 +243,8 @@ def main():
                         "device; uploads, projection and downloads of consecutive batches overlap"}
 
     if rank == 0:
-        alg_bytes = counters["B_in"] + counters["B_idx"] + counters["B_out"]
         step_s = elapsed / args.steps
         per_ms = {k: v[0] / args.steps for k, v in kernel_ms.items() if v[1]}
-        # PMC traffic (profiles/pmc_traffic.json: separate --pmc passes of this same command, per launch)
-        pmc = {}
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                if tj.get("pairs") == args.pairs:
-                    pmc = tj.get("kernels", {})
-            except Exception:
-                pmc = {}
-        kb = kernel_bytes(counters, n_aln, n_rows)
-
-        def entry(ms, nbytes, names):
-            tr = [pmc[x]["hbm_bytes_corrected"] for x in names if x in pmc]
-            e = {"ms": round(ms, 4), "alg_bytes": nbytes, "achieved": nbytes / (ms * 1e-3) / 1e9 if ms else None,
-                 "traffic": sum(tr) if len(tr) == len(names) and tr else None}
-            e["frac"] = e["achieved"] / HBM_PEAK_GBS if e["achieved"] is not None else None
-            return e
-
-        g = per_ms.get
-        table = {
-            "k_segment": entry(g("k_segment", 0.0), kb["segment"], ["k_segment"]),
-            "count (k_project<G,false,false,1|2>)": entry(g("k_project<G,false,false,1>", 0.0) + g("k_project<G,false,false,2>", 0.0),
-                                                          kb["count"],
-                                                          ["k_project<G,false,false,1>", "k_project<G,false,false,2>"]),
-        }
-        if g("k_emit_rows<2>", 0.0) or g("k_emit_rows<1>", 0.0):
-            # direct rows (the default): pairing on the survivor sets, then the emit kernels write the packed rows
-            pair_names = ["k_group_ids", "k_pair_mask", "k_big<0>+k_pair_big", "k_name_seed", "k_group_desc"]
-            emit_names = ["k_expand_rows", "k_emit_rows<1>", "k_emit_rows<2>", "k_big<1>"]
-            table["pairing (k_group_ids + k_pair_mask + k_big<0> + k_pair_big + k_name_seed + k_group_desc)"] = entry(
-                sum(g(x, 0.0) for x in pair_names), kb["pairing"], pair_names)
-            table["emit (k_expand_rows + k_emit_rows<1|2> + k_big<1>)"] = entry(sum(g(x, 0.0) for x in emit_names), kb["emit_rows"], emit_names)
-        else:
-            table["emit (k_expand + k_emit_dense<false,1|2> + k_project<64,true>)"] = entry(
-                g("k_expand", 0.0) + g("k_emit_dense<false,1>", 0.0) + g("k_emit_dense<false,2>", 0.0) + g("k_project<64,true>", 0.0),
-                kb["emit"], ["k_expand", "k_emit_dense<false,1>", "k_emit_dense<false,2>", "k_project<64,true>"])
-            table["rows (k_group_ids + k_pair<false|true> + k_primary + k_rows)"] = entry(
-                g("k_group_ids", 0.0) + g("k_pair<false>", 0.0) + g("k_pair<true>", 0.0) + g("k_rows", 0.0) + g("k_primary", 0.0),
-                kb["rows"], ["k_group_ids", "k_pair<false>", "k_pair<true>", "k_rows", "k_primary"])
-        # dominant = the single kernel with the most device time per step (k_scan_* is a group of small launches)
-        single = {k: v for k, v in per_ms.items() if k != "k_scan_*"}
-        dom = max(single, key=lambda k: single[k])
-        whole_tr = [pmc[k]["hbm_bytes_corrected"] for k in pmc]
         out = {
             "metric": "projected alignments/sec vs GENCODE-scale annotation",
             "value": total_aln * args.steps / elapsed,
@@ -318,37 +278,89 @@ def main():
             "matches_per_step": n_matches,
             "setup_seconds": round(setup_s, 1),
             "kernel_ms_per_step": {k: round(v, 4) for k, v in per_ms.items()},
-            "pcie_inclusive": pcie,
-            "roofline": {
-                "bound": "hbm",
-                "kernel": "whole path (%d timed kernel groups per step: k_scan_* is three launches, k_pair_mask and "
-                          "k_big<0>+k_pair_big two each)" % int(sum(v[1] for v in kernel_ms.values()) / args.steps),
-                "achieved": alg_bytes / step_s / 1e9,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": alg_bytes / step_s / 1e9 / HBM_PEAK_GBS,
-                "traffic": sum(whole_tr) if whole_tr else None,
-                "algorithmic_bytes_per_alignment": alg_bytes / n_aln,
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "counters": counters,
-                "dominant_kernel": {"name": dom, "ms_per_launch": round(single[dom], 4),
-                                    "share_of_step": round(single[dom] / (1e3 * step_s), 3)},
-                "per_kernel": table,
-                "note": "achieved = the SURVEY 8d algorithmic bytes of one step over the whole step (every launch of the path); "
-                        "per_kernel charges each stage only the formula terms it must move itself (DESIGN.md section 4) over its "
-                        "own hipEvent time (k_big<0> + k_pair_big, k_name_seed, k_group_desc and k_big<1> run on the context's second "
-                        "and third streams beside k_pair_mask, the scan and the emit kernels: overlapped kernels stretch each other, "
-                        "so the stage times sum to more than ms_per_step and the pairing / emit fractions are lower bounds); traffic "
-                        "is NOT measured by this run: it is the corrected rocprofv3 FETCH_SIZE + WRITE_SIZE per launch that the builder "
-                        "collected for this workload and committed as profiles/pmc_traffic.json (null when that file is for another size)",
-            },
         }
-        if not args.no_cpu_baseline and world == 1:   # the CPU leg is timed at N=1 only (the other ranks would wait for it)
-            out["cpu_baseline"] = cpu_baseline(ann, batch, args.cpu_sample)
+        if args.full:
+            out["pcie_inclusive"] = pcie
+            out["roofline"] = roofline(counters, kernel_ms, per_ms, n_aln, n_rows, step_s, args.pairs, args.steps)
+            if not args.no_cpu_baseline and world == 1:   # the CPU leg is timed at N=1 only (the other ranks would wait for it)
+                out["cpu_baseline"] = cpu_baseline(ann, batch, args.cpu_sample)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def roofline(counters, kernel_ms, per_ms, n_aln, n_rows, step_s, pairs, steps):
+    """The line's roofline (--full): the whole path's algorithmic bytes (counters: br_ctx_collect_counters, a pass of
+    its own) over the step, and the per-kernel table over the timed steps' hipEvent times (per_ms)."""
+    alg_bytes = counters["B_in"] + counters["B_idx"] + counters["B_out"]
+    # PMC traffic (profiles/pmc_traffic.json: separate --pmc passes of this same command, per launch)
+    pmc = {}
+    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(tpath):
+        try:
+            tj = json.load(open(tpath))
+            if tj.get("pairs") == pairs:
+                pmc = tj.get("kernels", {})
+        except Exception:
+            pmc = {}
+    kb = kernel_bytes(counters, n_aln, n_rows)
+
+    def entry(ms, nbytes, names):
+        tr = [pmc[x]["hbm_bytes_corrected"] for x in names if x in pmc]
+        e = {"ms": round(ms, 4), "alg_bytes": nbytes, "achieved": nbytes / (ms * 1e-3) / 1e9 if ms else None,
+             "traffic": sum(tr) if len(tr) == len(names) and tr else None}
+        e["frac"] = e["achieved"] / HBM_PEAK_GBS if e["achieved"] is not None else None
+        return e
+
+    g = per_ms.get
+    table = {
+        "k_segment": entry(g("k_segment", 0.0), kb["segment"], ["k_segment"]),
+        "count (k_project<G,false,false,1|2>)": entry(g("k_project<G,false,false,1>", 0.0) + g("k_project<G,false,false,2>", 0.0),
+                                                      kb["count"],
+                                                      ["k_project<G,false,false,1>", "k_project<G,false,false,2>"]),
+    }
+    if g("k_emit_rows<2>", 0.0) or g("k_emit_rows<1>", 0.0):
+        # direct rows (the default): pairing on the survivor sets, then the emit kernels write the packed rows
+        pair_names = ["k_group_ids", "k_pair_mask", "k_big<0>+k_pair_big", "k_name_seed", "k_group_desc"]
+        emit_names = ["k_expand_rows", "k_emit_rows<1>", "k_emit_rows<2>", "k_big<1>"]
+        table["pairing (k_group_ids + k_pair_mask + k_big<0> + k_pair_big + k_name_seed + k_group_desc)"] = entry(
+            sum(g(x, 0.0) for x in pair_names), kb["pairing"], pair_names)
+        table["emit (k_expand_rows + k_emit_rows<1|2> + k_big<1>)"] = entry(sum(g(x, 0.0) for x in emit_names), kb["emit_rows"], emit_names)
+    else:
+        table["emit (k_expand + k_emit_dense<false,1|2> + k_project<64,true>)"] = entry(
+            g("k_expand", 0.0) + g("k_emit_dense<false,1>", 0.0) + g("k_emit_dense<false,2>", 0.0) + g("k_project<64,true>", 0.0),
+            kb["emit"], ["k_expand", "k_emit_dense<false,1>", "k_emit_dense<false,2>", "k_project<64,true>"])
+        table["rows (k_group_ids + k_pair<false|true> + k_primary + k_rows)"] = entry(
+            g("k_group_ids", 0.0) + g("k_pair<false>", 0.0) + g("k_pair<true>", 0.0) + g("k_rows", 0.0) + g("k_primary", 0.0),
+            kb["rows"], ["k_group_ids", "k_pair<false>", "k_pair<true>", "k_rows", "k_primary"])
+    # dominant = the single kernel with the most device time per step (k_scan_* is a group of small launches)
+    single = {k: v for k, v in per_ms.items() if k != "k_scan_*"}
+    dom = max(single, key=lambda k: single[k])
+    whole_tr = [pmc[k]["hbm_bytes_corrected"] for k in pmc]
+    return {
+        "bound": "hbm",
+        "kernel": "whole path (%d timed kernel groups per step: k_scan_* is three launches, k_pair_mask and "
+                  "k_big<0>+k_pair_big two each)" % int(sum(v[1] for v in kernel_ms.values()) / steps),
+        "achieved": alg_bytes / step_s / 1e9,
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": alg_bytes / step_s / 1e9 / HBM_PEAK_GBS,
+        "traffic": sum(whole_tr) if whole_tr else None,
+        "algorithmic_bytes_per_alignment": alg_bytes / n_aln,
+        "algorithmic_bytes_per_launch": alg_bytes,
+        "counters": counters,
+        "dominant_kernel": {"name": dom, "ms_per_launch": round(single[dom], 4),
+                            "share_of_step": round(single[dom] / (1e3 * step_s), 3)},
+        "per_kernel": table,
+        "note": "achieved = the SURVEY 8d algorithmic bytes of one step over the whole step (every launch of the path); "
+                "per_kernel charges each stage only the formula terms it must move itself (DESIGN.md section 4) over its "
+                "own hipEvent time (k_big<0> + k_pair_big, k_name_seed, k_group_desc and k_big<1> run on the context's second "
+                "and third streams beside k_pair_mask, the scan and the emit kernels: overlapped kernels stretch each other, "
+                "so the stage times sum to more than ms_per_step and the pairing / emit fractions are lower bounds); traffic "
+                "is NOT measured by this run: it is the corrected rocprofv3 FETCH_SIZE + WRITE_SIZE per launch that the builder "
+                "collected for this workload and committed as profiles/pmc_traffic.json (null when that file is for another size)",
+    }
 
 
 DUMP_SAMPLE = 1 << 19        # rows and alignments kept by dump_outputs: about 40 MB of float64 at the default size

@@ -7,7 +7,7 @@ R=${1:-r02}
 O=gpurun_out/$R
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-python3 bench.py > $O/bench_10m.json.log 2> $O/bench_10m.err || exit 1
+python3 bench.py --full > $O/bench_10m.json.log 2> $O/bench_10m.err || exit 1
 echo "bench done"
 rocprofv3 --output-format csv --kernel-trace --stats -d $O/stats -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pcie > $O/rocprof_stats.log 2>&1 || exit 1
 echo "stats done"
@@ -34,5 +34,5 @@ echo "bam stage done"
 python3 bench_extra.py bundle > $O/bench_extra_bundle.json.log 2> $O/bundle.err || exit 1
 rocprofv3 --output-format csv --kernel-trace --stats -d $O/stats_bundle -o run -- python3 bench_extra.py bundle > $O/bundle_stats.log 2>&1 || exit 1
 echo "bundle done"
-BENCH_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 3 --warmup 1 --pairs 2000000 --no-cpu-baseline > $O/bench_2rank_gloo_rehearsal.json.log 2> $O/bench_2rank.err || exit 1
+BENCH_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 3 --warmup 1 --pairs 2000000 --full --no-cpu-baseline > $O/bench_2rank_gloo_rehearsal.json.log 2> $O/bench_2rank.err || exit 1
 echo "2-rank rehearsal done"

@@ -8,7 +8,7 @@ R=${1:-r03}
 O=gpurun_out/$R
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-python3 bench.py > $O/bench_10m.json.log 2> $O/bench_10m.err || exit 1
+python3 bench.py --full > $O/bench_10m.json.log 2> $O/bench_10m.err || exit 1
 echo "bench done"
 rocprofv3 --output-format csv --kernel-trace --stats -d $O/stats -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pcie > $O/rocprof_stats.log 2>&1 || exit 1
 echo "stats done"
@@ -24,5 +24,5 @@ python3 bench_extra.py bundle > $O/bench_extra_bundle.json.log 2> $O/bundle.err 
 echo "c3 / c5 / bundle done"
 CLI_LEVELS=device,device python3 bench_extra.py cli --reads 10000000 > $O/bench_extra_cli10m.json.log 2> $O/cli.err || exit 1
 echo "cli done"
-BENCH_DIST_BACKEND=gloo python3 bench.py --gpus 2 --steps 3 --warmup 1 --pairs 2000000 > $O/bench_2rank_self_launched.json.log 2> $O/bench_2rank.err || exit 1
+BENCH_DIST_BACKEND=gloo python3 bench.py --gpus 2 --steps 3 --warmup 1 --pairs 2000000 --full > $O/bench_2rank_self_launched.json.log 2> $O/bench_2rank.err || exit 1
 echo "2-rank self-launch done"

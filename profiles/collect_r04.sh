@@ -7,7 +7,7 @@ R=${1:-r04}
 O=gpurun_out/$R
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-python3 bench.py > $O/bench_10m.json.log 2> $O/bench_10m.err || exit 1
+python3 bench.py --full > $O/bench_10m.json.log 2> $O/bench_10m.err || exit 1
 echo "bench done"
 rocprofv3 --output-format csv --kernel-trace --stats -d $O/stats -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pcie > $O/rocprof_stats.log 2>&1 || exit 1
 echo "stats done"

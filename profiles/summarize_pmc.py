@@ -4,7 +4,7 @@
 usage: summarize_pmc.py FETCH_counter_collection.csv WRITE_counter_collection.csv PAIRS OUT_DIR
 
 FETCH_SIZE / WRITE_SIZE are collected in separate `rocprofv3 --pmc X --kernel-trace` passes of
-`python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline` (MI355X_MICROARCH.md, HBM section).
+`python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline` (MI355X_MICROARCH.md, HBM section).
 Per dispatch the counter is in KiB.  FETCH_SIZE = TCC_EA0_RDREQ x 64 B, but on gfx950 every L2->fabric read request is
 128 bytes wide -- for coalesced streams and for random 4/16/32/64-byte gathers alike (TCC_EA0_RDREQ_128B == TCC_EA0_RDREQ,
 the 32B / 64B request counters stay at zero: profiles/r02/pmc_calibration.json, profiles/calib_fetch.hip) -- so
@@ -77,7 +77,7 @@ def main():
         if k == "k_pair_mask_wide":
             return "k_pair_mask"
         return k
-    # direct rows (the default path): bench.py's counter diagnostic at the end of the run projects the batch once more through
+    # direct rows (the default path): bench.py --full's counter diagnostic at the end of the run projects the batch once more through
     # the match-table path (br_ctx_collect_counters); those kernels are not part of the timed step
     direct = any(k.startswith("k_emit_rows") for k in full)
     direct_step = re.compile(r"^(k_segment|k_group_ids|k_project<\d+, ?false, ?false, ?[12]>|k_name_seed|k_pair_mask(_wide)?|k_big<[01]>|k_pair_big|"
@@ -100,7 +100,7 @@ def main():
     traffic = {
         "pairs": pairs,
         "note": "per launch; rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of "
-                "`python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline`; bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 "
+                "`python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline`; bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 "
                 "(gfx950 correction, MI355X_MICROARCH.md HBM section). Made by profiles/summarize_pmc.py from the "
                 "CSVs beside pmc_summary.json.",
         "kernels": kern,

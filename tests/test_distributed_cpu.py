@@ -123,7 +123,7 @@ def test_bench_starts_its_own_ranks():
     the reductions); the line must say n_gpus 2 = n_ranks_seen 2, carry both ranks' times, and value = both ranks'
     alignments over the slowest rank's time."""
     import json
-    r = _run_bench(["--gpus", "2", "--pairs", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    r = _run_bench(["--gpus", "2", "--pairs", "20000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                    {"BENCH_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

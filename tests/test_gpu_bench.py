@@ -58,3 +58,32 @@ def test_bench_dumps_the_rows_of_its_last_step(tmp_path):
     assert np.array_equal(first["cigar_ops"], w["cigar"].astype(np.float64))
     assert np.array_equal(first["aln_index"], np.arange(p["n_aln"] + 1))
     assert np.array_equal(first["row_off"], p["row_off"].astype(np.float64))
+
+
+def _bench_line(extra):
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", "20000", "--steps", "2", "--warmup", "1"]
+                       + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_is_the_headline_and_full_adds_the_other_legs():
+    plain = _bench_line([])
+    full = _bench_line(["--full", "--cpu-sample", "1000"])
+    for d in (plain, full):
+        assert d["unit"] == "alignments/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert abs(d["value"] - d["per_rank_alignments_per_step"][0] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert d["kernel_ms_per_step"]
+    assert plain["metric"] == full["metric"]
+    assert plain["projected_records_per_step"] == full["projected_records_per_step"] > 0
+    assert not {"pcie_inclusive", "roofline", "cpu_baseline"} & set(plain)
+    assert full["pcie_inclusive"]["value"] > 0
+    assert 0 < full["roofline"]["frac"] <= 1 and full["roofline"]["per_kernel"]
+    assert full["cpu_baseline"]["value"] > 0
