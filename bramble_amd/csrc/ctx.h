@@ -88,7 +88,8 @@ struct br_ctx {
   // sets before anything is emitted, and the emit kernels write the packed rows themselves
   int direct_rows = 1;       // "direct_rows" / BRAMBLE_AMD_DIRECT_ROWS=0: the match-table path (k_emit_dense -> k_pair -> k_rows), the A/B switch
   DevBuf d_fm, d_nkept, d_desc, d_hi0, d_clspos, d_rnd, d_side, d_sidectr;
-  uint64_t d_side_cap = 0;
+  uint64_t d_side_cap = 0;   // (br_ctx_set_param "side_cap": the first capacity, a test hook)
+  int d_side_attempts = 0;   // side-arena attempts of the last direct-rows call (br_ctx_direct_diag)
   bool last_direct = false;  // the last call's rows came from the direct path: the detail column is re-emitted on request, not gathered
   bool want_x = false;       // the caller of run_device needs the detail column (input alignment, HI: the BAM encoder) with the rows
   ProjectArgs dA{}; DirectArgs dD{}; int64_t d_kept = 0, d_simple = 0;

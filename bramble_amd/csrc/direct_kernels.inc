@@ -255,7 +255,18 @@ __global__ void __launch_bounds__(64) k_big(ProjectArgs A, DirectArgs D) {
   const DevCfg &cfg = A.cfg;
   const uint32_t n_work = *D.n_big;
   for (uint32_t w = blockIdx.x; w < n_work; w += gridDim.x) {
-    if (D.side_used[1]) return;   // the arena ran out: the host grows it and repeats
+    if (D.side_used[1]) {   // the arena ran out: the host grows it and repeats
+      if (EM) return;
+      // no walk and no write from here on, but the need of every entry this block has left still counts (it depends on
+      // n_matches alone), so that side_used[0] ends as the exact total and the repeat's arena holds it: lane l adds up the
+      // entries w + (l + 64 k) * gridDim.x, one atomic per wave
+      unsigned long long need = 0;
+      for (uint64_t v = (uint64_t)w + (uint64_t)lane * gridDim.x; v < n_work; v += 64ull * gridDim.x) need += side_need(D.n_matches[D.big_list[v]]);
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) need += __shfl_down(need, d, 64);
+      if (lane == 0 && need) atomicAdd(D.side_used, need);
+      return;
+    }
     const uint32_t a = D.big_list[w];
     const uint32_t nm = D.n_matches[a];
     if (EM && D.n_kept[a] == 0) continue;

@@ -514,8 +514,10 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
     HIPCHK(hipMemcpyAsync(c->h_totals, d_tot, 5 * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(c->h_totals + 8, dz + GD_COUNTER_WORDS, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (c->h_totals[9]) {   // the side arena of the > 64-candidate alignments ran out: grow it to what was asked for, repeat
-      if (attempt >= 3) return BR_ERR_CAPACITY;
+    c->d_side_attempts = attempt + 1;
+    if (c->h_totals[9]) {   // the side arena of the > 64-candidate alignments ran out: grow it to the exact total k_big<0> counted
+      // (every entry adds its need, also after the overflow) plus a margin for the calls to come, repeat: the repeat fits
+      if (attempt >= 3) return BR_ERR_CAPACITY;   // (a guard: the second attempt always fits)
       HIPCHK(hipEventSynchronize(c->aux_ev[4]));
       c->d_side_cap = c->h_totals[8] + c->h_totals[8] / 4 + 4096;
       RC(c->d_side.ensure((size_t)c->d_side_cap * sizeof(uint2)));
@@ -963,6 +965,23 @@ extern "C" int br_ctx_collect_counters(br_ctx *c, const br_device_batch *b, void
   c->counters[0] = 24ull * n + 4ull * h[3];
   c->counters[1] = h[1];
   c->counters[2] = 4ull * n + 24ull * (uint64_t)nm + 4ull * h[7];
+  return BR_OK;
+}
+
+// Diagnostic of the last call, which must have been a direct-rows call: read back from what that call left on the device
+// (its counter block, the pairing flags), nothing recomputed.
+extern "C" int br_ctx_direct_diag(br_ctx *c, uint64_t out[8], uint8_t *pflags) {
+  if (!c || !out || !c->last_direct) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->ix->device));
+  const DirectArgs &D = c->dD;
+  uint64_t used = 0;
+  uint32_t nb[3] = {0, 0, 0};   // n_big | n_walk | pm_n
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(&used, D.side_used, 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(nb, D.n_big, 12, hipMemcpyDeviceToHost));
+  if (pflags && D.n_aln > 0) HIPCHK(hipMemcpy(pflags, D.pflag, (size_t)D.n_aln, hipMemcpyDeviceToHost));
+  memset(out, 0, 8 * sizeof(uint64_t));
+  out[0] = nb[0]; out[1] = (uint64_t)c->d_side_attempts; out[2] = used; out[3] = D.side_cap; out[4] = nb[2];
   return BR_OK;
 }
 

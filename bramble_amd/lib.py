@@ -157,6 +157,9 @@ class BrDeviceBam(C.Structure):
     _fields_ = [("data", C.c_void_p), ("n_bytes", C.c_uint64), ("row_off", C.c_void_p), ("n_rows", C.c_int64)]
 
 
+# the pairing flags per alignment that Context.direct_diag returns (kernels.h)
+PF_PAIRED, PF_SAME, PF_MATE, PF_BIG = 1, 2, 4, 8
+
 # every symbol include/bramble_amd.h declares
 EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_num_transcripts", "br_index_transcript_name",
            "br_index_transcript_len", "br_index_num_refs", "br_index_num_intervals", "br_index_device_bytes", "br_config_short_read",
@@ -168,7 +171,7 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_collator_new", "br_collator_add", "br_collator_finish", "br_collator_next", "br_collator_order", "br_collator_set_param",
            "br_collator_stats", "br_collator_free",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
-           "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
+           "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
 _LIB = None
 
@@ -252,6 +255,7 @@ def lib():
         L.br_ctx_kernel_ms.argtypes = [C.c_void_p, C.c_int, _P(C.c_double), _P(C.c_int32)]
         L.br_ctx_collect_counters.argtypes = [C.c_void_p, _P(BrDeviceBatch), C.c_void_p]
         L.br_ctx_last_counters.argtypes = [C.c_void_p, C.c_void_p]
+        L.br_ctx_direct_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.br_ctx_rescue_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.br_ctx_ksw_diag.argtypes = [C.c_void_p, C.c_void_p]
         L.br_device_rows_detail.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -581,6 +585,18 @@ class Context:
         check(lib().br_ctx_last_counters(self.h, out), "br_ctx_last_counters")
         keys = ("B_in", "B_idx", "B_out", "n_cigar", "read_exons", "overlap_hits", "matches", "out_cigar_words")
         return dict(zip(keys, [int(v) for v in out]))
+
+    def direct_diag(self, n_aln=None):
+        """What the last call (a direct-rows call) left on the device: {"n_big": big_list length, "side_attempts",
+        "side_used": arena entries the last attempt asked for, "side_cap": its capacity, "pm_n": windows sent to
+        k_pair_mask_wide}, plus "pflags" (uint8 [n_aln]: PF_PAIRED 1 | PF_SAME 2 | PF_MATE 4 | PF_BIG 8) when n_aln is given."""
+        out = (C.c_uint64 * 8)()
+        pf = np.zeros(n_aln, dtype=np.uint8) if n_aln is not None else None
+        check(lib().br_ctx_direct_diag(self.h, out, pf.ctypes.data if pf is not None and n_aln else None), "br_ctx_direct_diag")
+        d = dict(zip(("n_big", "side_attempts", "side_used", "side_cap", "pm_n"), [int(v) for v in out[:5]]))
+        if pf is not None:
+            d["pflags"] = pf
+        return d
 
     def project_bam_device(self, cfg, blob, rec_off, rec_len, ref_map, stream=0):
         """Raw mapped BAM records resident in HBM -> (BrDeviceRows, BrDeviceBam): reader side, projection and

@@ -716,6 +716,14 @@ int br_ctx_collect_counters(br_ctx *, const br_device_batch *, void *stream);
  * out[0]=B_in, out[1]=B_idx, out[2]=B_out, out[3]=sum n_cigar, out[4]=read exons,
  * out[5]=overlap hits, out[6]=matches, out[7]=rewritten-CIGAR words over all matches. */
 int br_ctx_last_counters(br_ctx *, uint64_t out[8]);
+/* Diagnostic of the last call, which must have been a direct-rows call (else BR_ERR_INVALID_ARG), read from what that call
+ * left on the device: out[0] = alignments with more than 64 candidate rows (big_list), out[1] = side-arena attempts,
+ * out[2] = arena entries the last attempt asked for, out[3] = arena capacity of that attempt (entries), out[4] = windows
+ * that k_pair_mask handed to k_pair_mask_wide, out[5..7] = 0.  pflags (NULL, or n_aln bytes): the pairing flags per
+ * alignment (1 paired, 2 a transcript in common with the mate, 4 the mate of a pair led by the other record, 8 more than
+ * 64 candidate rows).  The test hook br_ctx_set_param("side_cap", v >= 64) sets the arena's first capacity; a call that
+ * outgrows it grows the arena to what it asked for and repeats once. */
+int br_ctx_direct_diag(br_ctx *, uint64_t out[8], uint8_t *pflags);
 
 /* -S runs: out[0] = rescue problems of the last call, out[1] = ksw2 DP cells (sum of qlen x tlen),
  * out[2] = accepted rescues, out[3] = coded sequence bytes. */

@@ -115,6 +115,32 @@ def test_unpaired_emits_every_match(setup):
     assert rows.n_rows == rows.n_matches and rows.n_matches > 5 * PAIRS
 
 
+def test_full_size_head_direct_rows_equal_oracle(setup):
+    """A 200 k-pair head of the configs[1] batch (cut at a read-name boundary) on the direct-rows route against the oracle.
+    The bucket-range supersets give the GENCODE-shaped reads a few alignments with more than 64 candidate rows: the head
+    must hold some (big_list), and some of them paired, so that k_big<0> / k_pair_big run on realistic input too."""
+    from oracle import oracle_binding as ob
+    from tests.parity import assert_rows_equal
+    ann, idx, _, batch = setup
+    head = {k: batch[k][:600_000] for k in ("name_off",)}
+    head["n_aln"] = 600_000 - 1
+    head["names"] = batch["names"]
+    starts = _name_group_starts(head)
+    assert len(starts) > 200_001
+    sub = _oracle_head(ann, batch, starts, {}, 200_000, False)
+    ctx = lib.Context(idx)
+    ctx.set_param("small_batch", 0)
+    cfg = lib.make_config()
+    prod = ctx.project_batch(cfg, sub)
+    d = ctx.direct_diag(sub["n_aln"])
+    orc, _, _ = ob.run(ob.OracleIndex(ann.as_dict()), ob.make_flags(), sub, want_matches=False)
+    assert_rows_equal(prod, orc)
+    pf = d["pflags"]
+    n_big_paired = int((((pf & lib.PF_BIG) != 0) & ((pf & lib.PF_PAIRED) != 0)).sum())
+    assert d["n_big"] > 0 and n_big_paired > 0, (d["n_big"], n_big_paired, d["side_used"], sub["n_aln"])
+    ctx.close()
+
+
 def test_full_size_bam_bundle_stream_properties():
     """The records-in / records-out path at full size (20.9 M raw records -> 108.8 M projected records, 24 GB):
       * the output is a well-formed chain: every record's block_size equals the distance to the next row offset;
