@@ -721,7 +721,8 @@ __global__ void __launch_bounds__(256) k_expand_rows(DirectArgs D) {
 // k_emit_rows<CLS>: one lane per kept match (work-list entry).  Entry -> alignment -> its k-th kept survivor (k-th set
 // bit of the filtered mask) and that survivor's tid rank c among the kept (the rank loop over s_tid, as k_emit_dense) ->
 // candidate row -> ideal CIGAR, merge -> the packed row at first record + stride * c.  CLS as k_emit_dense: 1 = the simple
-// prefix (one read exon from a single M op), 2 = the rest.
+// prefix (one read exon from a single M op, and the light two-exon class the count pass adds to it: "M N M" with exact
+// inner junctions, a closed form as well), 2 = the rest.
 // ---------------------------------------------------------------------------
 template <int CLS>
 __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 6) k_emit_rows(ProjectArgs A, DirectArgs D, int64_t first, int64_t n_end) {
@@ -751,6 +752,7 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 6) k_emit_rows(ProjectArgs
   uint32_t c0 = 0, c1 = 0;
   RealCig rc;
   if (CLS != 1) { hd2 = A.head2[a]; c0 = A.cigar_off[a]; c1 = A.cigar_off[a + 1]; }
+  else if (hd.z == 2) hd2 = A.head2[a];   // the light two-exon class: read exon 1 (in flight with the row load below)
   const uint32_t n_seg = hd.z, rid = hd.w >> 2;
   const uint2 q0 = make_uint2(hd.x, hd.y);
   const int st0 = (n_seg == 1) ? ST_ONLY : ST_FIRST;
@@ -786,18 +788,35 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 6) k_emit_rows(ProjectArgs
   if (is_fast) {
     // one read exon from a single M op: the rewritten CIGAR is [S left_ins] M [S right_ins] (see k_emit_dense)
     const uint32_t os = q0.x > gs ? q0.x : gs, oe = q0.y < gend ? q0.y : gend;
-    const uint32_t ml = oe - os;
+    uint32_t ml = oe - os, pos = h0.pos, r_ins = h0.right_ins, junc_in = 0;
+    bool r_exact = h0.right_ins == 0 && h0.right_gap == 0;
+    if (n_seg == 2) {
+      // The light two-exon class ("M N M", every kept survivor's inner junction the annotated one: the count pass's mark).
+      // walk_pass2 under `plain` for it: the second read exon hits exactly the exon after the candidate's (status LAST),
+      // build_match adds (ml0)M then (ml1)M -- one op in the ideal sink -- and two junction hits for the inner sides; the
+      // merge with "aM bN cM" drops the N, so the rewritten CIGAR is [S left_ins] (ml0 + ml1)M [S right_ins of the
+      // second hit].  pos: the first hit's on '+', acc.last_pos (the second hit's) on '-'.
+      const uint2 q1 = make_uint2(hd2.x, hd2.y);
+      const uint4 e1 = next_row(make_uint4(gs, gend, pay.z, 0), make_uint2(r_a.z, r_b.w), s == 1);
+      Hit hh;
+      classify(s == 1, ST_LAST, q1.x, q1.y, e1.x, e1.y, e1.z, cfg, hh);
+      ml += (q1.y < e1.y ? q1.y : e1.y) - q1.x;
+      pos = s == 0 ? h0.pos : hh.pos;
+      r_ins = hh.right_ins; r_exact = hh.right_ins == 0 && hh.right_gap == 0;
+      junc_in = 2;
+    }
     uint32_t w0, w1 = 0, w2 = 0, n_out;
-    if (h0.left_ins) { w0 = CIG_GEN(h0.left_ins, OP_S); w1 = CIG_GEN(ml, OP_M); n_out = 2; if (h0.right_ins) { w2 = CIG_GEN(h0.right_ins, OP_S); n_out = 3; } }
-    else { w0 = CIG_GEN(ml, OP_M); n_out = 1; if (h0.right_ins) { w1 = CIG_GEN(h0.right_ins, OP_S); n_out = 2; } }
-    const uint32_t junc = ((h0.left_ins == 0 && h0.left_gap == 0) ? 1u : 0u) + ((h0.right_ins == 0 && h0.right_gap == 0) ? 1u : 0u);
+    if (h0.left_ins) { w0 = CIG_GEN(h0.left_ins, OP_S); w1 = CIG_GEN(ml, OP_M); n_out = 2; if (r_ins) { w2 = CIG_GEN(r_ins, OP_S); n_out = 3; } }
+    else { w0 = CIG_GEN(ml, OP_M); n_out = 1; if (r_ins) { w1 = CIG_GEN(r_ins, OP_S); n_out = 2; } }
+    const uint32_t junc = junc_in + ((h0.left_ins == 0 && h0.left_gap == 0) ? 1u : 0u) + (r_exact ? 1u : 0u);
     uint64_t cref = (uint64_t)w0 | ((uint64_t)w1 << 32);
     if (n_out == 3) {
-      cref = D.cig_base[a] + (uint64_t)c * (1u + 2u * 6u);
+      // the alignment's own slot capacity (k_segment / the count pass): n_cigar + 2 * (4 * n_seg + 2)
+      cref = D.cig_base[a] + (uint64_t)c * (n_seg == 2 ? 3u + 2u * 10u : 1u + 2u * 6u);
       uint32_t *slot = A.cig_arena + cref;
       slot[0] = w0; slot[1] = w1; slot[2] = w2;
     }
-    write_row(D, E, a, c, pay.x, h0.pos, n_out, s == 1, cref, junc, ml);
+    write_row(D, E, a, c, pay.x, pos, n_out, s == 1, cref, junc, ml);
     return;
   }
   if (CLS == 1) return;

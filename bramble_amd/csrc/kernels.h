@@ -18,7 +18,7 @@ struct ProjectArgs {
   const uint2 *seg;
   const AlnMeta *meta;
   const uint4 *head;     // [n_aln] {exon0.start, exon0.end, n_seg, refid<<2|smode}
-  const uint4 *head2;    // [n_aln] read exons 1 and 2
+  const uint4 *head2;    // [n_aln] read exons 1 and 2 (two exons: .z = 1 marks an "M N M" CIGAR in the light-class presets)
   const uint32_t *fast_flag;  // [n_aln] 1: one read exon from a single M op (short-read presets)
   const uint32_t *fast_pre;   // [n_aln + 1] exclusive prefix of the simple alignments' matches
   // count pass outputs / emit pass inputs
@@ -72,6 +72,7 @@ struct CountArgs {
   uint4 *ranges;
   uint32_t *walk_list, *n_walk;
   uint32_t *big_list, *n_big;
+  uint32_t *light_flag;   // MODE 1, direct rows only (else null): fast_flag, set to the simple class for light two-exon alignments
 };
 
 // -S clip rescue (rescue_kernels.inc)

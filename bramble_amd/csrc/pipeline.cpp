@@ -171,8 +171,9 @@ static CountArgs count_view(const ProjectArgs &A) {
 }
 
 // the count pass: one kernel with the exon walk inline, or (split: presets without the similarity filter) the main kernel
-// without it and a second one for the alignments it put on A.walk_list
-static int count_pass(br_ctx *c, hipStream_t st, const ProjectArgs &A, Prof &pf, bool split) {
+// without it and a second one for the alignments it put on A.walk_list.  light (direct rows): the main kernel moves the
+// light two-exon alignments into the simple class (fast_flag)
+static int count_pass(br_ctx *c, hipStream_t st, const ProjectArgs &A, Prof &pf, bool split, bool light = false) {
   const int n_blocks = c->n_cu * c->blocks_per_cu;
   if (!split || A.ix.n_rows == 0) {   // (an empty annotation: launch_project zeroes the counts)
     RC(pf.begin(BR_K_COUNT));
@@ -180,7 +181,8 @@ static int count_pass(br_ctx *c, hipStream_t st, const ProjectArgs &A, Prof &pf,
     RC(pf.end());
     return BR_OK;
   }
-  const CountArgs C = count_view(A);
+  CountArgs C = count_view(A);
+  if (light) C.light_flag = const_cast<uint32_t *>(A.fast_flag);
   RC(pf.begin(BR_K_COUNT));
   launch_count(st, C, c->group_lanes, n_blocks, 1);
   RC(pf.end());
@@ -457,7 +459,7 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
   RC(pf.begin(BR_K_GROUP_IDS));
   launch_group_ids(st, ng, b->group_off, c->aln_group.as<uint32_t>());
   RC(pf.end());
-  RC(count_pass(c, st, A, pf, true));
+  RC(count_pass(c, st, A, pf, true, true));
   // a packed download of the previous call may still be reading row_off / the row tables (br_project_staged)
   if (c->rows_busy_set) { HIPCHK(hipStreamWaitEvent(st, c->rows_busy, 0)); }
   // a16 (src/mates.cpp:150-261) on the survivor sets, then placement
@@ -982,6 +984,20 @@ extern "C" int br_ctx_direct_diag(br_ctx *c, uint64_t out[8], uint8_t *pflags) {
   if (pflags && D.n_aln > 0) HIPCHK(hipMemcpy(pflags, D.pflag, (size_t)D.n_aln, hipMemcpyDeviceToHost));
   memset(out, 0, 8 * sizeof(uint64_t));
   out[0] = nb[0]; out[1] = (uint64_t)c->d_side_attempts; out[2] = used; out[3] = D.side_cap; out[4] = nb[2];
+  if (D.n_aln > 0) {   // work-list entries of the light two-exon class: kept matches of simple-class alignments with two read exons
+    const size_t n = (size_t)D.n_aln;
+    std::vector<uint32_t> ff(n), nk(n);
+    std::vector<uint4> hd(n);
+    std::vector<uint8_t> pf(n);
+    HIPCHK(hipMemcpy(ff.data(), D.fast_flag, n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(nk.data(), D.n_kept, n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hd.data(), c->head.p, n * sizeof(uint4), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pf.data(), D.pflag, n, hipMemcpyDeviceToHost));
+    uint64_t light = 0;
+    for (size_t a = 0; a < n; a++)
+      if ((ff[a] >> 31) && hd[a].z == 2 && !(pf[a] & PF_BIG)) light += nk[a];
+    out[5] = light;
+  }
   return BR_OK;
 }
 

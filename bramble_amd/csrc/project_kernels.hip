@@ -144,7 +144,15 @@ __global__ void __launch_bounds__(256) k_segment(int64_t n_aln, const int32_t *_
   head[a] = make_uint4(q0.x, q0.y, n, n ? (((uint32_t)rid << 2) | smode) : 0u);
   // read exons 1 and 2: only a spliced read has them (the readers load the record unconditionally and use it from two
   // exons on: for the others the 16 bytes are not written)
-  if (n > 1) { const uint2 q2 = n > 2 ? e2 : make_uint2(0, 0); head2[a] = make_uint4(e1.x, e1.y, q2.x, q2.y); }
+  // For two read exons .z is free: 1 marks a real CIGAR of exactly "M N M" (ops M, not = / X) in the short-read presets
+  // without --max-error-exon, the alignments the direct-rows count pass may give the light two-exon emit path.
+  if (n > 1) {
+    // (from the registers of the first four words: the batch's last few alignments, which do not take them, stay general)
+    const bool mnm = n == 2 && n_cigar == 3 && pre4 && CIG_OP(w4[0]) == OP_M && CIG_OP(w4[2]) == OP_M && !cfg.filter_by_similarity &&
+                     !cfg.long_reads && !cfg.ignore_small_exons;
+    const uint2 q2 = n > 2 ? e2 : make_uint2(mnm ? 1u : 0u, 0);
+    head2[a] = make_uint4(e1.x, e1.y, q2.x, q2.y);
+  }
   // "simple" alignments: one read exon from a single M op, short-read presets.  They
   // are processed first (k_perm) so that whole waves take the short code paths.
   uint32_t fast = (n == 1 && n_cigar == 1 && CIG_OP(cg[0]) == OP_M && !cfg.filter_by_similarity && !cfg.long_reads) ? 1u : 0u;
@@ -834,6 +842,8 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(Args A) {
     uint32_t total = 0;
     uint64_t mask_all = 0;
     bool defer = false;  // MODE 1: some candidate needs the walk
+    uint32_t inexact = 0;  // MODE 1: survivors of this lane's whose inner junction is not the annotated one (a counter, not a
+                           // bool: a bool carried across the loop is a 64-bit scalar mask, four more SGPR spills)
 
     // EMIT without a stored mask (> 64 candidate rows): sweep 0 records every
     // survivor's tid in m_aux[], sweep 1 ranks against that list.
@@ -912,6 +922,7 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(Args A) {
             }
           }
         }
+        if (MODE == 1 && PRE == 1) inexact += (alive && (gend != q0.y || nxt != hd2.x)) ? 1u : 0u;
         Acc acc; IdealSink sk; double score = 0.0;
         if (!EMIT || !have_mask) {
           // similarity filter needs the pass-2 accumulators (long reads only; SIMF is
@@ -994,8 +1005,18 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(Args A) {
       }
       continue;
     }
+    // Light two-exon class (direct rows only: light_flag is null on the match-table path; the short-read preset only, as
+    // k_emit_rows<2>'s `plain`): an "M N M" alignment (k_segment's mark in head2.z) with at most 64 candidate rows, none
+    // deferred -- so every survivor came through the two-exon shortcut above -- and every survivor's inner junction exactly
+    // the annotated one.  Its rewritten CIGAR is then [S] (ml0 + ml1)M [S], which k_emit_rows<1> writes; it joins the simple
+    // class (bit 31) with the slot capacity of n_cigar = 3, n_seg = 2.  Pairing only removes survivors: what it keeps is
+    // light as well.
+    bool light = false;
+    if constexpr (MODE == 1 && CNT && PRE == 1)
+      light = n_seg == 2 && hd2.z != 0 && n_items <= 64 && ((__ballot(inexact != 0u) >> gbase) & gmask) == 0;
     if (!EMIT && gl == 0) {
       A.n_matches[a] = total; A.mask[a] = mask_all;
+      if constexpr (MODE == 1 && CNT && PRE == 1) { if (light && A.light_flag) A.light_flag[a] = (1u << 31) | (3u + 2u * (4u * 2u + 2u)); }
       if (n_items > 64 && total) {
         const uint32_t k = atomicAdd(&sh_bn, 1u);
         if (k < BIG_LDS) sh_bl[EMIT ? 0 : k] = (uint32_t)a;

@@ -719,7 +719,9 @@ int br_ctx_last_counters(br_ctx *, uint64_t out[8]);
 /* Diagnostic of the last call, which must have been a direct-rows call (else BR_ERR_INVALID_ARG), read from what that call
  * left on the device: out[0] = alignments with more than 64 candidate rows (big_list), out[1] = side-arena attempts,
  * out[2] = arena entries the last attempt asked for, out[3] = arena capacity of that attempt (entries), out[4] = windows
- * that k_pair_mask handed to k_pair_mask_wide, out[5..7] = 0.  pflags (NULL, or n_aln bytes): the pairing flags per
+ * that k_pair_mask handed to k_pair_mask_wide, out[5] = work-list entries of the light two-exon class (kept matches of
+ * "M N M" alignments whose every survivor meets the annotated junction exactly, emitted by the simple-class kernel; those
+ * of alignments with more than 64 candidate rows or their mates are not counted), out[6..7] = 0.  pflags (NULL, or n_aln bytes): the pairing flags per
  * alignment (1 paired, 2 a transcript in common with the mate, 4 the mate of a pair led by the other record, 8 more than
  * 64 candidate rows).  The test hook br_ctx_set_param("side_cap", v >= 64) sets the arena's first capacity; a call that
  * outgrows it grows the arena to what it asked for and repeats once. */
