@@ -11,6 +11,10 @@
   python bench_extra.py collate [--reads N]  br_collator over N pairs' records (default 10 M pairs, ~20 M records) in HBM in a
                                          random order, added in bundles of 1 M: add / finish / bundle-cut seconds, collator
                                          peak device bytes per record, against br_bam_split_device over the same stream
+  python bench_extra.py samout [--reads N]  SAM text out: br_sam_format_device on the projected records of N pairs (default 500 000,
+                                         about 1 M records: one CLI bundle) against br_bgzf_deflate_device of the same stream in the
+                                         same process (ms per bundle, text GB/s), then the command line file to file with -O sam
+                                         against the default BAM, alternated (SAMOUT_CLI_RUNS pairs, default 3; 0 skips them)
   python bench_extra.py small            small calls: us per device-resident step at 1 .. 52 000 pairs (without the per-kernel
                                          events bench.py keeps on), the path without host round trips against the ordinary one,
                                          and br_project_group / br_project_groups host to host from plain C (profiles/group_latency.c)
@@ -28,7 +32,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
@@ -202,6 +206,78 @@ def main():
         print(json.dumps({"config": "bundle", "device_deflate": deflate, "workload": "%d raw paired-end BAM records resident in HBM -> %d projected BAM records (reader side, projection and re-encoding on the device)" % (len(rlen), int(bam.n_rows)),
                           "alignments_per_s": len(rlen) / el, "ms_per_step": el * 1e3, "input_bytes": int(stream_h.size),
                           "output_bytes": int(bam.n_bytes), "kernel_ms_per_step": {k: round(v / args.steps, 3) for k, v in kms.items() if v}}))
+        return
+    if args.config == "samout":
+        import subprocess
+        import tempfile
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from tests import bamio
+        n = args.reads or 500_000
+        ann = synth.Annotation("G")
+        annd = ann.as_dict()
+        batch = ann.reads(n, "pe", with_records=1)
+        stream_h, roff, rlen = synth.Annotation.frame_records(batch)
+        del batch
+        cfg = lib.make_config()
+        idx = lib.Index.from_flat(ann.flat, device=0)
+        ctx = lib.Context(idx)
+        ctx.set_sam_refs([idx.transcript_name(t) for t in range(idx.num_transcripts())])
+        blob = torch.from_numpy(stream_h).to("cuda:0")
+        off_d = torch.from_numpy(roff.view(np.int64)).to("cuda:0")
+        len_d = torch.from_numpy(rlen.view(np.int32)).to("cuda:0")
+        ref_map = np.arange(ann.n_refs, dtype=np.int32)
+        st = torch.cuda.current_stream().cuda_stream
+        _, bam = ctx.project_bam_device(cfg, blob, off_d, len_d, ref_map, st)
+        # the projected stream, copied out of the context's buffers (the calls below reuse them)
+        recs = torch.as_tensor(brdev._DevArray(bam.data, int(bam.n_bytes), "|u1"), device="cuda:0").clone()
+        rows = torch.as_tensor(brdev._DevArray(bam.row_off, int(bam.n_rows), "<u8"), device="cuda:0").view(torch.int64).clone()
+        torch.cuda.synchronize()
+        res = {"config": "samout", "workload": "SAM text of the %d projected records of %d paired-end alignments (%d record bytes) in HBM"
+               % (int(bam.n_rows), len(rlen), int(bam.n_bytes))}
+        ctx.set_profiling(True)
+        for name, call in (("sam_format", lambda: ctx.sam_format_device(recs, rows, st)),
+                           ("device_deflate", lambda: ctx.bgzf_deflate_device(recs, st))):
+            for _ in range(args.warmup):
+                out = call()
+            times, kms = [], {}
+            for _ in range(args.steps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = call()
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+                for k, (ms, ln) in ctx.kernel_ms().items():
+                    kms[k] = kms.get(k, 0.0) + ms
+            ms = 1e3 * float(np.median(times))
+            res[name] = {"ms_per_bundle": round(ms, 3), "ms_min": round(1e3 * min(times), 3), "out_bytes": int(out.numel()),
+                         "out_GBps": int(out.numel()) / (ms * 1e-3) / 1e9, "in_GBps": int(bam.n_bytes) / (ms * 1e-3) / 1e9,
+                         "kernel_ms_per_step": {k: round(v / args.steps, 3) for k, v in kms.items() if v}}
+        ctx.set_profiling(False)
+        del recs, rows
+        runs = int(os.environ.get("SAMOUT_CLI_RUNS", "3"))
+        if runs:
+            tmp = tempfile.mkdtemp(prefix="bramble_samout_")
+            gtf, in_bam = os.path.join(tmp, "guides.gtf"), os.path.join(tmp, "in.bam")
+            bamio.write_gtf(gtf, annd)
+            refs = [(r, 250_000_000) for r in annd["refnames"]]
+            bamio.write_bam(in_bam, "@HD\tVN:1.6\tSO:unsorted\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs), refs, stream_h.tobytes(), level=1)
+            exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bramble_amd", "bin", "bramble")
+            import re
+            wall, dev = {"bam": [], "sam": []}, {"bam": [], "sam": []}
+            size = {}
+            for k in range(runs):
+                for fmt in ("bam", "sam"):
+                    out = os.path.join(tmp, "out." + fmt)
+                    t0 = time.perf_counter()
+                    r = subprocess.run([exe, in_bam, "-G", gtf, "-o", out, "-p", str(args.threads), "-O", fmt], capture_output=True, timeout=600)
+                    wall[fmt].append(time.perf_counter() - t0)
+                    assert r.returncode == 0, r.stderr.decode()
+                    dev[fmt].append(float(re.search(rb"([0-9.]+)s on the device path", r.stdout).group(1)))   # (the report line)
+                    size[fmt] = os.path.getsize(out)
+                    os.remove(out)
+            res["cli_file_to_file_s"] = {f: {"median": round(float(np.median(v)), 3), "runs": [round(x, 3) for x in v], "out_bytes": size[f],
+                                             "device_path_s": dev[f]} for f, v in wall.items()}
+        print(json.dumps(res))
         return
     if args.config == "inflate":
         # BGZF inflate on the device against the host codec: the raw records of N read pairs, compressed by the library's writer

@@ -296,10 +296,10 @@ extern "C" int br_bam_bundle_stage(br_ctx *c, const br_bam_bundle *bb, int slot)
   return BR_OK;
 }
 
-// records in HBM -> projected records (or their BGZF blocks) in pinned host memory: the part the staged and the resident
-// entry points share
+// records in HBM -> projected records (or their BGZF blocks, or their SAM lines) in pinned host memory: the part the staged and
+// the resident entry points share.  out_mode: br_bam_bundle.bgzf_on_device (0 records, 1 BGZF, BR_OUT_SAM_TEXT)
 static int project_bam_tail(br_ctx *c, const br_config *cfg, const br_device_records *dr, const int32_t *ref_map, int32_t n_ref_map,
-                            bool bgzf_on_device, bool nowait, double wait_ms, br_host_bam *out) {
+                            int out_mode, bool nowait, double wait_ms, br_host_bam *out) {
   static const bool timing = getenv("BRAMBLE_AMD_TIMING") != nullptr;
   auto tnow = []() { return std::chrono::steady_clock::now(); };
   auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -311,12 +311,17 @@ static int project_bam_tail(br_ctx *c, const br_config *cfg, const br_device_rec
   auto t2 = tnow();
   int hs = c->h_bam_next; c->h_bam_next ^= 1;
   if (c->home_pending[hs]) { HIPCHK(hipEventSynchronize(c->ev_home[hs])); c->home_pending[hs] = false; }   // (a caller that never asked)
-  const bool later = nowait && bgzf_on_device && db.n_bytes;
-  if (bgzf_on_device && db.n_bytes) {
+  const bool later = nowait && out_mode && db.n_bytes;
+  if (out_mode == 1 && db.n_bytes) {
     c->z_dense_which = hs;
     const uint8_t *z = nullptr; uint64_t zn = 0;
     RC(deflate_device_impl(c, db.data, db.n_bytes, st, &z, &zn, false));
     db.data = z; db.n_bytes = zn;
+  } else if (out_mode == BR_OUT_SAM_TEXT && db.n_bytes) {   // the lines, where the BGZF blocks would be made (sam_writer.cpp)
+    c->sf_which = hs;
+    const uint8_t *t = nullptr; uint64_t tn = 0;
+    RC(sam_format_impl(c, &db, st, &t, &tn));
+    db.data = t; db.n_bytes = tn;
   }
   auto t3 = tnow();
   if (db.n_bytes > c->h_bam_cap[hs]) {
@@ -326,7 +331,7 @@ static int project_bam_tail(br_ctx *c, const br_config *cfg, const br_device_rec
     c->h_bam[hs] = c->h_bam_mem[hs].p; c->h_bam_cap[hs] = c->h_bam_mem[hs].cap;
   }
   if (later) {
-    // everything on `st` is complete (the deflate step ends with the block sizes on the host): the copy goes to a stream of its
+    // everything on `st` is complete (the deflate step ends with the block sizes on the host, the SAM step with its text made): the copy goes to a stream of its
     // own and the caller asks for it with br_host_bam_wait, so the next bundle's kernels start without the 4 ms of PCIe in front
     if (!c->down_stream) HIPCHK(hipStreamCreateWithFlags(&c->down_stream, hipStreamNonBlocking));
     if (!c->ev_home[hs]) HIPCHK(hipEventCreateWithFlags(&c->ev_home[hs], hipEventDisableTiming));
@@ -337,12 +342,15 @@ static int project_bam_tail(br_ctx *c, const br_config *cfg, const br_device_rec
     if (db.n_bytes) HIPCHK(hipMemcpyAsync(c->h_bam[hs], db.data, (size_t)db.n_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
-  if (timing) fprintf(stderr, "[bundle] %lld records: upload wait %.1f ms, records -> records %.1f ms, deflate %.1f ms, download of %.0f MB %.1f ms\n", (long long)n, wait_ms, tms(t1, t2), tms(t2, t3), (double)db.n_bytes / 1e6, tms(t3, tnow()));
+  if (timing) fprintf(stderr, "[bundle] %lld records: upload wait %.1f ms, records -> records %.1f ms, deflate / format %.1f ms, download of %.0f MB %.1f ms\n", (long long)n, wait_ms, tms(t1, t2), tms(t2, t3), (double)db.n_bytes / 1e6, tms(t3, tnow()));
   out->data = c->h_bam[hs]; out->n_bytes = db.n_bytes; out->n_rows = db.n_rows;
   out->total_complete = rows.total_complete; out->total_unique = rows.total_unique;
   out->dropped_reads = rows.dropped_reads; out->total_processed = rows.total_processed;
   return BR_OK;
 }
+
+// bgzf_on_device: BR_OUT_SAM_TEXT, or BGZF blocks for any other value than 0 (as before there was a third output)
+static int out_mode_of(int v) { return v == BR_OUT_SAM_TEXT ? BR_OUT_SAM_TEXT : v != 0 ? 1 : 0; }
 
 static int project_bam_staged_impl(br_ctx *c, const br_config *cfg, const br_bam_bundle *bb, int slot, br_host_bam *out, bool nowait) {
   if (!c || !cfg || !bb || !out || slot < 0 || slot > 2) return BR_ERR_INVALID_ARG;
@@ -357,7 +365,7 @@ static int project_bam_staged_impl(br_ctx *c, const br_config *cfg, const br_bam
   const double wait_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (n == 0) return BR_OK;
   br_device_records dr{S.blob.as<uint8_t>(), S.off.as<uint64_t>(), n, S.len.as<uint32_t>()};
-  return project_bam_tail(c, cfg, &dr, bb->ref_map, bb->n_ref_map, bb->bgzf_on_device != 0, nowait, wait_ms, out);
+  return project_bam_tail(c, cfg, &dr, bb->ref_map, bb->n_ref_map, out_mode_of(bb->bgzf_on_device), nowait, wait_ms, out);
 }
 
 extern "C" int br_project_bam_resident(br_ctx *c, const br_config *cfg, const br_device_records *recs, const int32_t *ref_map, int32_t n_ref_map,
@@ -367,7 +375,7 @@ extern "C" int br_project_bam_resident(br_ctx *c, const br_config *cfg, const br
   HIPCHK(hipSetDevice(c->ix->device));
   out->total_processed = (uint64_t)recs->n_aln;
   if (recs->n_aln == 0) return BR_OK;
-  return project_bam_tail(c, cfg, recs, ref_map, n_ref_map, bgzf_on_device != 0, nowait != 0, 0.0, out);
+  return project_bam_tail(c, cfg, recs, ref_map, n_ref_map, out_mode_of(bgzf_on_device), nowait != 0, 0.0, out);
 }
 
 extern "C" int br_project_bam_staged(br_ctx *c, const br_config *cfg, const br_bam_bundle *bb, int slot, br_host_bam *out) {

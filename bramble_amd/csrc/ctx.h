@@ -75,6 +75,11 @@ struct br_ctx {
   DevBuf z_slots, z_sizes, z_off, z_dense, z_dense_alt, z_tabs, z_tokens;
   DevBuf inf_out, inf_blocks, inf_tabs, inf_cnt; bool inf_tabs_ready = false;   // br_bgzf_inflate_device
   DevBuf sp_entry, sp_entry2, sp_exit, sp_nmap, sp_nunm, sp_ended, sp_redo, sp_pre, sp_small, sp_off, sp_len;   // br_bam_split_device
+  // SAM text out (sam_writer.cpp): the reference names of RNAME / RNEXT, line lengths -> offsets, the long-record list, and two
+  // text buffers that alternate like z_dense / z_dense_alt
+  DevBuf sf_names, sf_name_off, sf_len, sf_long, sf_small, sf_tmp, sf_text[2];
+  int32_t sf_n_names = 0;
+  int sf_which = 0;
   int z_dense_which = 0;           // br_project_bam_staged_nowait: the packed blocks of call j are still on their way home while call j + 1 packs its own
   hipStream_t down_stream = nullptr; hipEvent_t ev_home[2] = {nullptr, nullptr}; std::atomic<bool> home_pending[2] = {{false}, {false}};
   int deflate_dynamic = 1;
@@ -206,3 +211,4 @@ int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStr
                bool keep_events = false);
 int ensure_detail(br_ctx *c, hipStream_t st);
 int expand_rows(br_ctx *c, hipStream_t st, br_device_wide_rows *out);
+int sam_format_impl(br_ctx *c, const br_device_bam *in, hipStream_t st, const uint8_t **text, uint64_t *n_bytes);

@@ -184,9 +184,9 @@ int64_t BgzfReader::read(ByteBuf &out, size_t want) {
 
 BgzfWriter::~BgzfWriter() { if (f_ && f_ != stdout) fclose(f_); }
 
-bool BgzfWriter::open(const char *path, int threads, int level) {
+bool BgzfWriter::open(const char *path, int threads, int level, bool bgzf) {
   f_ = strcmp(path, "-") == 0 ? stdout : fopen(path, "wb");
-  threads_ = threads < 1 ? 1 : threads; level_ = level;
+  threads_ = threads < 1 ? 1 : threads; level_ = level; bgzf_ = bgzf;
   if (!f_) { err_ = std::string("cannot create ") + path; return false; }
   return true;
 }
@@ -276,8 +276,10 @@ bool BgzfWriter::close() {
   if (!f_) return true;
   bool ok = true;
   if (!pending_.empty()) { ok = flush_blocks(pending_.data(), 1, pending_.size()); pending_.clear(); }
-  if (ok && fwrite(EOF_BLOCK, 1, 28, f_) != 28) { err_ = "short write"; ok = false; }
-  bytes_out_ += 28;
+  if (bgzf_) {
+    if (ok && fwrite(EOF_BLOCK, 1, 28, f_) != 28) { err_ = "short write"; ok = false; }
+    bytes_out_ += 28;
+  }
   if ((f_ == stdout ? fflush(f_) : fclose(f_)) != 0) { err_ = "close failed"; ok = false; }
   f_ = nullptr;
   return ok;

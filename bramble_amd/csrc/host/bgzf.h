@@ -88,7 +88,8 @@ class BgzfReader {
 class BgzfWriter {
  public:
   ~BgzfWriter();
-  bool open(const char *path, int threads, int level);
+  // bgzf = false: a plain file (SAM text): only write_raw is used, and close() appends no EOF block
+  bool open(const char *path, int threads, int level, bool bgzf = true);
   // compresses [p, p+n) into 0xff00-byte blocks (a trailing partial block is kept for the next call)
   bool write(const uint8_t *p, size_t n);
   // closes the pending partial block, then appends bytes that already ARE complete BGZF blocks (device deflate)
@@ -102,6 +103,7 @@ class BgzfWriter {
   bool flush_blocks(const uint8_t *p, size_t n_blocks, size_t last_len);
   FILE *f_ = nullptr;
   int threads_ = 1, level_ = 6;
+  bool bgzf_ = true;
   std::vector<uint8_t> pending_;
   std::vector<uint8_t> cout_;
   std::string err_;

@@ -6,7 +6,8 @@
 //                   readers (cli_input.h: one source per format)
 //   uploader      : br_bam_bundle_stage (host bundles: records to one of three device slots, own copy stream)
 //   runner        : br_project_bam_staged_nowait / br_project_bam_resident (everything between the raw records on the device)
-//   writer thread : BGZF deflate (threaded) -> output file
+//   writer thread : BGZF deflate (threaded) -> output file; device-made BGZF blocks or SAM lines (-O sam) go out as they are
+#include <ctype.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -29,7 +30,7 @@ using brio::BgzfWriter;
 void usage(FILE *f) {
   fprintf(f,
           "bramble (MI355X) usage:\n\n"
-          "bramble <in.bam|in.sam|-> -G <annotation.gtf> -o <out.bam> [-p <cpus>] [-S <genome.fa>]\n"
+          "bramble <in.bam|in.sam|-> -G <annotation.gtf> -o <out.bam|out.sam|-> [-O bam|sam] [-p <cpus>] [-S <genome.fa>]\n"
           " [--help] [--version] [--quiet] [--fr] [--rf] [--lr] [--lr-hq] [--strict]\n"
           " [--max-soft-clip N] [--max-junction-insertion N] [--max-junction-deletion N]\n"
           " [--max-error-exon N] [--similarity-threshold X]\n"
@@ -43,7 +44,10 @@ void usage(FILE *f) {
           "The input is BAM or SAM text (a file, or standard input as -), told apart by its bytes; SAM lines become BAM\n"
           "records on the GPU.  --device-reader / --host-reader choose how BAM is read and do not apply to SAM.\n"
           "BGZF-compressed SAM and plain gzip input are not supported.\n"
-          "--collate: input in any order (e.g. coordinate-sorted); the whole input is read into one device's memory and grouped by read name before the first bundle is projected.\n");
+          "--collate: input in any order (e.g. coordinate-sorted); the whole input is read into one device's memory and grouped by read name before the first bundle is projected.\n"
+          "-O, --output-fmt bam|sam: BAM (the default) or SAM text, formatted on the GPU (the header text, then one line per record,\n"
+          "no BGZF framing); the format is never taken from the output's extension.  --compression-level, --host-deflate and\n"
+          "--device-deflate apply to BAM only.\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -51,6 +55,7 @@ bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(
 int parse_args(int argc, char **argv, Options &o) {
   memset(&o.cfg, 0, sizeof(o.cfg));
   o.cfg.junc_miss_discount = 1.0;
+  bool codec = false;   // a BGZF codec option was given
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "%s: missing value\n", argv[i]); return nullptr; } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -76,10 +81,18 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (a == "-S" || a == "--genome") { const char *v = value(); if (!v) return -1; o.fasta = v; }
     else if (a == "-o" || a == "--out") { const char *v = value(); if (!v) return -1; o.out_bam = v; }
     else if (a == "-p" || a == "--threads") { const char *v = value(); if (!v) return -1; o.threads = atoi(v); if (o.threads < 1) o.threads = 1; }
-    else if (a == "--compression-level") { const char *v = value(); if (!v) return -1; o.level = atoi(v); if (o.level < 0 || o.level > 9) return -1; o.device_deflate = false; }
-    else if (a == "--host-deflate") o.device_deflate = false;
+    else if (a == "--compression-level") { const char *v = value(); if (!v) return -1; o.level = atoi(v); if (o.level < 0 || o.level > 9) return -1; o.device_deflate = false; codec = true; }
+    else if (a == "--host-deflate") { o.device_deflate = false; codec = true; }
+    else if (a == "-O" || a == "--output-fmt") {
+      const char *v = value(); if (!v) return -1;
+      std::string f = v;
+      for (auto &ch : f) ch = (char)tolower((unsigned char)ch);
+      if (f == "sam") o.sam_out = true;
+      else if (f == "bam") o.sam_out = false;
+      else { fprintf(stderr, "--output-fmt: unknown format %s (bam or sam)\n", v); return -1; }
+    }
     else if (a == "--bundle-size") { const char *v = value(); if (!v) return -1; o.bundle_records = atoll(v); if (o.bundle_records < 1) return -1; }
-    else if (a == "--device-deflate") o.device_deflate = true;
+    else if (a == "--device-deflate") { o.device_deflate = true; codec = true; }
     else if (a == "--device-reader") o.device_reader = 1;
     else if (a == "--host-reader") o.device_reader = 0;
     else if (a == "--collate") o.collate = true;
@@ -98,6 +111,7 @@ int parse_args(int argc, char **argv, Options &o) {
   if (o.out_bam.empty()) { fprintf(stderr, "--out is required\n"); return -1; }
   if (o.gff.empty()) { fprintf(stderr, "--guide is required\n"); return -1; }
   if (!o.fasta.empty()) o.cfg.use_fasta = 1;
+  if (o.sam_out && codec) { fprintf(stderr, "--compression-level, --host-deflate and --device-deflate apply to BAM output, not to --output-fmt sam\n"); return -1; }
   if (o.collate && o.devices.size() > 1) { fprintf(stderr, "--collate works on one device: give --device N, not a --devices list\n"); return -1; }
   return 0;
 }
@@ -252,7 +266,7 @@ struct Run {
         int wrc = br_host_bam_wait(workers[(size_t)c.worker]->ctx, &hb);
         if (wrc && writer_err.empty()) { writer_err = std::string("download failed: ") + br_strerror(wrc); raise_fail(); }
       }
-      if (writer_err.empty() && c.n && !(o.device_deflate ? wr.write_raw(c.data, (size_t)c.n) : wr.write(c.data, (size_t)c.n))) {
+      if (writer_err.empty() && c.n && !(o.device_deflate || o.sam_out ? wr.write_raw(c.data, (size_t)c.n) : wr.write(c.data, (size_t)c.n))) {
         writer_err = wr.error();
         raise_fail();                      // nothing projected from here on could be written: the runners drain
       }
@@ -264,8 +278,9 @@ struct Run {
     }
   }
   br_bam_bundle args(Bundle &b) const {
-    return br_bam_bundle{b.blob.data(), b.blob.size(), b.off.data(), b.len.data(), (int64_t)b.off.size(), ref_map.data(), (int32_t)ref_map.size(), o.device_deflate ? 1 : 0};
+    return br_bam_bundle{b.blob.data(), b.blob.size(), b.off.data(), b.len.data(), (int64_t)b.off.size(), ref_map.data(), (int32_t)ref_map.size(), out_mode()};
   }
+  int out_mode() const { return o.sam_out ? BR_OUT_SAM_TEXT : o.device_deflate ? 1 : 0; }
   // one projection call (none after a failure), once chunk j - 2 of this worker is on disk: the context's two pinned
   // result buffers alternate
   template <typename F>
@@ -328,7 +343,7 @@ struct Run {
       w->t_wait_in += secs(tw0, now());
       if (!b) break;
       br_host_bam hb;
-      project(w, hb, [&](br_host_bam *h) { return br_project_bam_resident(w->ctx, &o.cfg, &b->recs, ref_map.data(), (int32_t)ref_map.size(), o.device_deflate ? 1 : 0, 1, h); });
+      project(w, hb, [&](br_host_bam *h) { return br_project_bam_resident(w->ctx, &o.cfg, &b->recs, ref_map.data(), (int32_t)ref_map.size(), out_mode(), 1, h); });
       b->release();   // (failed or not: the reader may use its chunk again)
       deliver(w, b->seq, hb);
     }
@@ -349,7 +364,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
   for (int i = 0; i < argc; i++) { if (i) cl += ' '; cl += argv[i]; }
   auto t_start = std::chrono::steady_clock::now();
   auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
-  if (o.out_bam == "-") o.quiet = true;   // the BAM stream owns standard output
+  if (o.out_bam == "-") o.quiet = true;   // the BAM (or SAM) stream owns standard output
   if (!o.quiet) { printf("\n[bramble] starting version: %s (bramble_amd %s)\n", BRAMBLE_REF_VERSION, br_version()); printf("[bramble] loading reference annotation...\n"); }
 
   // the guide loader starts first, on a thread of its own: opening the input, reading its header and starting the reader
@@ -417,11 +432,23 @@ extern "C" int br_cli_main(int argc, char **argv) {
   std::vector<int32_t> ref_map(hdr.ref_names.size());
   int32_t extra = (int32_t)n_refs;
   for (size_t r = 0; r < hdr.ref_names.size(); r++) { auto it = ref_of.find(hdr.ref_names[r]); ref_map[r] = it != ref_of.end() ? it->second : extra++; }
+  if (o.sam_out) {   // RNAME / RNEXT: the @SQ list make_bam_header writes (transcripts of length > 0, in index order)
+    std::vector<const char *> sq;
+    for (size_t t = 0, nt = br_index_num_transcripts(ix0); t < nt; t++)
+      if (br_index_transcript_len(ix0, (uint32_t)t) > 0) sq.push_back(br_index_transcript_name(ix0, (uint32_t)t));
+    for (auto &w : workers) {
+      int src = br_ctx_set_sam_refs(w->ctx, sq.data(), (int32_t)sq.size());
+      if (src) { fprintf(stderr, "error: reference names on device %d: %s\n", w->device, br_strerror(src)); return give_up(); }
+    }
+  }
   OutFile file(o.out_bam);
-  if (!file.wr.open(file.tmp.c_str(), o.threads, o.level)) { fprintf(stderr, "error: %s\n", file.wr.error().c_str()); return give_up(); }
+  if (!file.wr.open(file.tmp.c_str(), o.threads, o.level, !o.sam_out)) { fprintf(stderr, "error: %s\n", file.wr.error().c_str()); return give_up(); }
   {
-    std::vector<uint8_t> h = make_bam_header(make_header_text(hdr.text, ix0, cl, o.gff), ix0);
-    if (!file.wr.write(h.data(), h.size())) { fprintf(stderr, "error: %s\n", file.wr.error().c_str()); file.discard(); return give_up(); }
+    const std::string text = make_header_text(hdr.text, ix0, cl, o.gff);
+    bool ok;
+    if (o.sam_out) ok = file.wr.write_raw((const uint8_t *)text.data(), text.size());   // SAM: the header text as it is
+    else { std::vector<uint8_t> h = make_bam_header(text, ix0); ok = file.wr.write(h.data(), h.size()); }
+    if (!ok) { fprintf(stderr, "error: %s\n", file.wr.error().c_str()); file.discard(); return give_up(); }
   }
   if (!o.quiet) printf("[bramble] processing alignments :-)\n");
   double t_setup = since();

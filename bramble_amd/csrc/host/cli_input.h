@@ -32,6 +32,7 @@ struct Options {
   int64_t bundle_records = 1000000;   // (1 M: 1.20 s inside the program for 20.9 M alignments, 2 M: 1.38 s, 0.5 M: 1.47 s; the pinned result buffers scale with it)
   bool quiet = false;
   bool device_deflate = true;   // BGZF blocks made on the GPU unless a host level is asked for
+  bool sam_out = false;         // -O sam: SAM text formatted on the GPU (BR_OUT_SAM_TEXT) instead of BAM
   bool collate = false;          // --collate: the whole input is read into one device's memory and regrouped by read name first
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };

@@ -12,13 +12,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbramble_amd.so")
 _P = C.POINTER
 
-K_SEGMENT, K_COUNT, K_EMIT, K_PAIR_COUNT, K_PAIR_EMIT, K_GATHER, K_SCAN, K_EMIT_AUX, K_KSW, K_BAM, K_PARSE, K_CODEC, K_EMIT_SIMPLE, K_PRIMARY, K_CIGAR_POOL, K_COUNT_WALK, K_EXPAND, K_GROUP_IDS, K_P1, K_P1_WALK, K_EMIT_WL, K_NAME_SEED, K_PAIR_MASK, K_PAIR_BIG, K_GROUP_DESC, K_EXPAND_ROWS, K_EMIT_ROWS_SIMPLE, K_EMIT_ROWS, K_BIG_EMIT, K_NUM = range(30)
+K_SEGMENT, K_COUNT, K_EMIT, K_PAIR_COUNT, K_PAIR_EMIT, K_GATHER, K_SCAN, K_EMIT_AUX, K_KSW, K_BAM, K_PARSE, K_CODEC, K_EMIT_SIMPLE, K_PRIMARY, K_CIGAR_POOL, K_COUNT_WALK, K_EXPAND, K_GROUP_IDS, K_P1, K_P1_WALK, K_EMIT_WL, K_NAME_SEED, K_PAIR_MASK, K_PAIR_BIG, K_GROUP_DESC, K_EXPAND_ROWS, K_EMIT_ROWS_SIMPLE, K_EMIT_ROWS, K_BIG_EMIT, K_SAM_FORMAT, K_NUM = range(31)
 KERNEL_NAMES = ["k_segment", "k_project<G,false,false,1>", "k_emit_dense<false,2>", "k_pair<false>", "k_pair<true>",
                 "k_rows", "k_scan_*", "k_project<64,true>", "k_ksw", "k_bam_scan+k_bam_size+k_bam_encode",
                 "k_rec_fields+k_group_off+k_rec_copy+k_mates+k_seq_*", "k_deflate_*+k_bgzf_compact",
                 "k_emit_dense<false,1>", "k_primary", "(unused)", "k_project<G,false,false,2>", "k_expand", "k_group_ids",
                 "(unused)", "(unused)", "(unused)", "k_name_seed", "k_pair_mask", "k_big<0>+k_pair_big", "k_group_desc",
-                "k_expand_rows", "k_emit_rows<1>", "k_emit_rows<2>", "k_big<1>"]
+                "k_expand_rows", "k_emit_rows<1>", "k_emit_rows<2>", "k_big<1>", "k_samfmt_*"]
 
 
 class BrambleError(RuntimeError):
@@ -134,6 +134,8 @@ class BrBamBundle(C.Structure):
                 ("n_records", C.c_int64), ("ref_map", C.c_void_p), ("n_ref_map", C.c_int32), ("bgzf_on_device", C.c_int32)]
 
 
+OUT_SAM_TEXT = 2   # br_bam_bundle.bgzf_on_device / br_project_bam_resident: SAM lines instead of records or BGZF blocks
+
 BGZF_BLOCK = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("clen", "<u4"), ("ulen", "<u4"), ("crc", "<u4"), ("pad", "<u4")])
 
 
@@ -167,6 +169,7 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_project_batch", "br_project_batch_device", "br_device_rows_expand", "br_batch_stage", "br_project_staged", "br_host_rows_wait", "br_project_batch_packed",
            "br_pin_host", "br_unpin_host", "br_project_group", "br_project_groups", "br_bam_encode_device", "br_project_bam_device", "br_project_bam_bundle", "br_bam_bundle_stage", "br_project_bam_staged", "br_bam_split", "br_annotation_load", "br_annotation_load_mt", "br_annotation_free",
            "br_annotation_num_transcripts", "br_annotation_transcripts", "br_annotation_num_refs", "br_annotation_refnames", "br_cli_main", "br_cli_exit_at_end", "br_device_warmup", "br_project_bam_staged_nowait", "br_host_bam_wait", "br_bgzf_scan", "br_bgzf_inflate_device", "br_bam_split_device", "br_bam_reader_new", "br_bam_reader_next", "br_bam_reader_set_piece_blocks", "br_bam_reader_release", "br_bam_reader_free", "br_bam_piece_upload", "br_bam_piece_process", "br_bam_reader_seconds", "br_bam_reader_upload_seconds", "br_project_bam_resident", "br_bgzf_write_file", "br_bgzf_read_file",
+           "br_ctx_set_sam_refs", "br_sam_format_device",
            "br_sam_header_scan", "br_sam_reader_new", "br_sam_reader_next", "br_sam_reader_upload", "br_sam_reader_next_staged", "br_sam_reader_release", "br_sam_reader_free", "br_sam_reader_error", "br_sam_reader_stats",
            "br_collator_new", "br_collator_add", "br_collator_finish", "br_collator_next", "br_collator_order", "br_collator_set_param",
            "br_collator_stats", "br_collator_free",
@@ -640,15 +643,43 @@ class Context:
             return torch.zeros(0, dtype=torch.uint8, device=src.device)
         return torch.as_tensor(_DevArray(out.value, n.value, "|u1"), device=src.device)
 
-    def project_bam_resident(self, cfg, recs, ref_map):
+    def set_sam_refs(self, names):
+        """The reference names SAM text prints as RNAME / RNEXT, in refID order (br_ctx_set_sam_refs)."""
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() if isinstance(n, str) else bytes(n) for n in names])
+        L = lib()
+        L.br_ctx_set_sam_refs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        check(L.br_ctx_set_sam_refs(self.h, arr, len(names)), "br_ctx_set_sam_refs")
+
+    def sam_format_device(self, data, row_off=None, stream=0):
+        """br_sam_format_device: a record stream in HBM ([block_size][record]...) -> torch CUDA uint8 view of its SAM lines (valid
+        until the next call on this context).  data: a BrDeviceBam (as project_bam_device returns it), or a torch CUDA uint8
+        tensor with row_off, a torch CUDA int64 tensor of each record's offset."""
+        import torch
+        from .device import _DevArray
+        if isinstance(data, BrDeviceBam):
+            db, dev = data, torch.device("cuda", torch.cuda.current_device())
+        else:
+            db, dev = BrDeviceBam(), data.device
+            db.data, db.n_bytes = data.data_ptr() if data.numel() else None, data.numel()
+            db.row_off, db.n_rows = row_off.data_ptr() if row_off.numel() else None, row_off.numel()
+        out, n = C.c_void_p(), C.c_uint64()
+        L = lib()
+        L.br_sam_format_device.argtypes = [C.c_void_p, _P(BrDeviceBam), C.c_void_p, _P(C.c_void_p), _P(C.c_uint64)]
+        check(L.br_sam_format_device(self.h, C.byref(db), C.c_void_p(stream), C.byref(out), C.byref(n)), "br_sam_format_device")
+        if n.value == 0:
+            return torch.zeros(0, dtype=torch.uint8, device=dev)
+        return torch.as_tensor(_DevArray(out.value, n.value, "|u1"), device=dev)
+
+    def project_bam_resident(self, cfg, recs, ref_map, sam_text=False):
         """br_project_bam_resident over a BrDeviceRecords that is in HBM already (a reader's or a Collator's bundle):
-        (stream uint8[], counters dict) as project_bam_bundle."""
+        (stream uint8[], counters dict) as project_bam_bundle; with sam_text the stream is the records' SAM lines."""
         rm = np.ascontiguousarray(ref_map, dtype=np.int32)
         out = BrHostBam()
         L = lib()
         L.br_project_bam_resident.argtypes = [C.c_void_p, _P(BrConfig), _P(BrDeviceRecords), C.c_void_p, C.c_int32, C.c_int, C.c_int,
                                               _P(BrHostBam)]
-        check(L.br_project_bam_resident(self.h, C.byref(cfg), C.byref(recs), rm.ctypes.data, len(rm), 0, 0, C.byref(out)),
+        check(L.br_project_bam_resident(self.h, C.byref(cfg), C.byref(recs), rm.ctypes.data, len(rm), OUT_SAM_TEXT if sam_text else 0, 0,
+                                        C.byref(out)),
               "br_project_bam_resident")
         n = int(out.n_bytes)
         data = np.ctypeslib.as_array(C.cast(out.data, _P(C.c_uint8)), shape=(n,)).copy() if n else np.zeros(0, np.uint8)
@@ -656,14 +687,15 @@ class Context:
                       "total_unique": int(out.total_unique), "dropped_reads": int(out.dropped_reads),
                       "total_processed": int(out.total_processed)}
 
-    def project_bam_bundle(self, cfg, blob, rec_off, rec_len, ref_map, bgzf_on_device=False):
-        """Host form: numpy blob / rec_off (uint64) / rec_len (uint32) in, (stream uint8[], counters dict) out."""
+    def project_bam_bundle(self, cfg, blob, rec_off, rec_len, ref_map, bgzf_on_device=False, sam_text=False):
+        """Host form: numpy blob / rec_off (uint64) / rec_len (uint32) in, (stream uint8[], counters dict) out; with sam_text the
+        stream is the projected records' SAM lines (set_sam_refs names their references)."""
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
         rec_len = np.ascontiguousarray(rec_len, dtype=np.uint32)
         rm = np.ascontiguousarray(ref_map, dtype=np.int32)
         bb = BrBamBundle(blob.ctypes.data, blob.size, rec_off.ctypes.data, rec_len.ctypes.data, len(rec_len),
-                         rm.ctypes.data, len(rm), 1 if bgzf_on_device else 0)
+                         rm.ctypes.data, len(rm), OUT_SAM_TEXT if sam_text else 1 if bgzf_on_device else 0)
         out = BrHostBam()
         check(lib().br_project_bam_bundle(self.h, C.byref(cfg), C.byref(bb), C.byref(out)), "br_project_bam_bundle")
         n = int(out.n_bytes)

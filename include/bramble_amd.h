@@ -434,8 +434,10 @@ typedef struct br_bam_bundle {
   const int32_t *ref_map;
   int32_t n_ref_map;
   int32_t bgzf_on_device;   /* 1: deflate the projected stream on the device; br_host_bam.data then holds complete
-                             * BGZF blocks (append them to the output file as they are) */
+                             * BGZF blocks (append them to the output file as they are).  BR_OUT_SAM_TEXT: format it as
+                             * SAM text on the device (br_sam_format_device); br_host_bam.data then holds the lines */
 } br_bam_bundle;
+#define BR_OUT_SAM_TEXT 2
 
 typedef struct br_host_bam {
   const uint8_t *data;      /* [block_size][record]... ready for BGZF framing; owned by the context, valid until
@@ -589,9 +591,22 @@ int br_collator_set_param(br_collator *, const char *name, int64_t value);
 int br_collator_stats(const br_collator *, uint64_t *arena_bytes, uint64_t *peak_bytes, double *add_seconds, double *finish_seconds);
 void br_collator_free(br_collator *);
 
-/* br_project_bam_staged / _nowait for records that are in HBM already (a br_bam_reader bundle, or br_bam_split_device's) */
+/* br_project_bam_staged / _nowait for records that are in HBM already (a br_bam_reader bundle, or br_bam_split_device's);
+ * bgzf_on_device takes the values of br_bam_bundle.bgzf_on_device (0, 1, BR_OUT_SAM_TEXT) */
 int br_project_bam_resident(br_ctx *, const br_config *, const br_device_records *recs, const int32_t *ref_map, int32_t n_ref_map,
                             int bgzf_on_device, int nowait, br_host_bam *out);
+
+/* ---- SAM text out -------------------------------------------------------------------------- */
+
+/* The reference names RNAME and RNEXT print, in refID order (a refID < 0 or >= n prints '*'); uploaded to HBM once, kept by
+ * the context until the next call.  Without it every RNAME prints '*'. */
+int br_ctx_set_sam_refs(br_ctx *, const char *const *names, int32_t n);
+/* An uncompressed record stream in HBM (br_device_bam: data / n_bytes / row_off / n_rows, as br_project_bam_device leaves it)
+ * -> SAM text in HBM, one '\n'-terminated line per record, byte for byte what htslib's bam_read1 + sam_format1 print for it
+ * (`samtools view`): a record in the spilled CIGAR form (<l_seq>S<ref_len>N plus CG:B,I) prints its real CIGAR and no CG tag,
+ * f values print as printf("%g").  *text is a device pointer owned by the context, valid until its next call.
+ * BR_ERR_INVALID_ARG, and no text, when a record has a tag type outside AcCsSiIfZHB or data past its end. */
+int br_sam_format_device(br_ctx *, const br_device_bam *in, void *stream, const uint8_t **text, uint64_t *n_bytes);
 
 /* BGZF inflate on the device (one wave per block: the reader side of br_bgzf_deflate_device).  br_bgzf_scan (host) walks
  * the block headers of a piece of a BGZF file -- up to `cap` complete blocks; empty ones (the EOF marker) are stepped over --
@@ -693,7 +708,8 @@ const char *br_bgzf_codec(void); /* "libdeflate" (bound at run time when present
 #define BR_K_EMIT_ROWS_SIMPLE 26 /* k_emit_rows<1>: packed rows of the simple class */
 #define BR_K_EMIT_ROWS 27  /* k_emit_rows<2>: packed rows of the general class */
 #define BR_K_BIG_EMIT 28   /* k_big<1>: packed rows of the alignments with > 64 candidate rows */
-#define BR_K_NUM 29
+#define BR_K_SAM_FORMAT 29 /* k_samfmt_measure<16|64> + k_samfmt_emit16 + k_samfmt_emit64 (SAM text out) */
+#define BR_K_NUM 30
 /* When enabled, every launch is bracketed by hipEvents on the launch stream. */
 int br_ctx_set_profiling(br_ctx *, int enabled);
 /* Launch tuning: "group_lanes" (8|16|32|64 lanes cooperating on one alignment),
