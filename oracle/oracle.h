@@ -103,6 +103,14 @@ void orc_result_free(orc_result *);
 /* real (+) ideal -> out; returns n_out (out must hold n_real + n_ideal + 1 words) */
 int32_t orc_merge_cigar(const uint32_t *real, int32_t n_real, const uint32_t *ideal, int32_t n_ideal,
                         uint32_t *out);
+/* one cell of merge_ops (src/bam.cpp:22-111): the merged op code, or 95 ('_') for "drop" */
+int32_t orc_merge_ops(int32_t real_op, int32_t ideal_op);
+/* Coverage counter of the merge (process-wide, off by default): while enabled, every merge_ops evaluation inside
+ * merge_cigars bumps out256[real_op * 16 + (ideal_op & 15)]; an exhausted ideal CIGAR in the front-clip phase
+ * (ideal_op 0xff) counts in column 15. */
+void orc_merge_hits_enable(int32_t on);
+void orc_merge_hits_reset(void);
+void orc_merge_hits_read(uint64_t *out256);
 /* CIGAR -> read exons; returns count or -1 where the reference aborts */
 int32_t orc_segments(int32_t ref_start, const uint32_t *cigar, int32_t n_cigar, uint32_t *out_pairs,
                      int32_t cap);

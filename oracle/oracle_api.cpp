@@ -422,6 +422,12 @@ int32_t orc_merge_cigar(const uint32_t *real, int32_t n_real, const uint32_t *id
   return (int32_t)r.size();
 }
 
+int32_t orc_merge_ops(int32_t real_op, int32_t ideal_op) { return (int32_t)merge_ops((char)real_op, (char)ideal_op); }
+
+void orc_merge_hits_enable(int32_t on) { merge_hits().on.store(on != 0); }
+void orc_merge_hits_reset(void) { for (auto &c : merge_hits().cell) c.store(0); }
+void orc_merge_hits_read(uint64_t *out256) { for (int i = 0; i < 256; i++) out256[i] = merge_hits().cell[i].load(); }
+
 int32_t orc_segments(int32_t ref_start, const uint32_t *cigar, int32_t n_cigar, uint32_t *out_pairs,
                      int32_t cap) {
   std::vector<GSeg> segs;

@@ -135,6 +135,10 @@ def lib():
         L.orc_result_free.argtypes = [C.c_void_p]
         L.orc_merge_cigar.restype = C.c_int32
         L.orc_merge_cigar.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.orc_merge_ops.restype = C.c_int32
+        L.orc_merge_ops.argtypes = [C.c_int32, C.c_int32]
+        L.orc_merge_hits_enable.argtypes = [C.c_int32]
+        L.orc_merge_hits_read.argtypes = [C.c_void_p]
         L.orc_segments.restype = C.c_int32
         L.orc_segments.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.orc_resolve_config.restype = C.c_int32
@@ -314,6 +318,31 @@ def merge_cigar(real, ideal):
     out = np.zeros(len(real) + len(ideal) + 1, dtype=np.uint32)
     n = lib().orc_merge_cigar(real.ctypes.data, len(real), ideal.ctypes.data, len(ideal), out.ctypes.data)
     return out[:n]
+
+
+def merge_ops(real_op, ideal_op):
+    """One cell of merge_ops: op letters in CIGAR_ALPHABET (',' '.' '/' ';' = the override ops) -> letter, or 'drop'."""
+    r = lib().orc_merge_ops(CIGAR_ALPHABET.index(real_op), CIGAR_ALPHABET.index(ideal_op))
+    return "drop" if r == ord("_") else CIGAR_ALPHABET[r]
+
+
+class merge_hits:
+    """with merge_hits() as h: ... ob.run(...) ...; h.cells() -> the 16 x 16 count of merge_ops(real, ideal) evaluations
+    made by merge_cigars inside the block (column 15: the front-clip phase with the ideal CIGAR exhausted)."""
+
+    def __enter__(self):
+        lib().orc_merge_hits_reset()
+        lib().orc_merge_hits_enable(1)
+        return self
+
+    def __exit__(self, *exc):
+        lib().orc_merge_hits_enable(0)
+        return False
+
+    def cells(self):
+        out = np.zeros(256, dtype=np.uint64)
+        lib().orc_merge_hits_read(out.ctypes.data)
+        return out.reshape(16, 16)
 
 
 def segments(ref_start, cigar):

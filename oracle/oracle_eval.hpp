@@ -6,6 +6,7 @@
 #pragma once
 #include "oracle_core.hpp"
 #include "oracle_ksw2.hpp"
+#include <atomic>
 
 namespace orc {
 
@@ -570,6 +571,8 @@ struct Evaluator {
 // ---- CIGAR merge ------------------------------------------------------------
 // src/bam.cpp:22-111.  `char` is signed in the reference build
 // (meson.build: -fsigned-char); op codes 0..13 and '_' (95) are unaffected.
+// Pinned cell by cell (9 real ops x 10 ideal ops) by tests/golden/merge_ops_table.json, transcribed from the
+// reference's rule order by hand.
 static inline char merge_ops(char real_op, char ideal_op) {
   if ((real_op == C_MATCH || real_op == C_SOFT_CLIP) && ideal_op == C_CLIP_OVERRIDE) return C_SOFT_CLIP;
   if ((real_op == C_MATCH || real_op == C_SOFT_CLIP) && ideal_op == C_MATCH_OVERRIDE) return C_MATCH;
@@ -593,6 +596,22 @@ static inline char merge_ops(char real_op, char ideal_op) {
   if (real_op == C_MATCH || real_op == C_EQUAL) return C_MATCH;
   if (real_op == C_DIFF) return C_DIFF;
   return ideal_op;
+}
+
+// Optional coverage counter (tests only): while enabled, every merge_ops evaluation of merge_cigars -- the main loop
+// and the front-clip phase -- bumps cell [real_op & 15][ideal_op & 15].  The clip phase evaluates merge_ops with
+// ideal_op = 0xff once the ideal CIGAR is exhausted: that lands in column 15, which no CIGAR op uses.
+struct MergeHits {
+  std::atomic<bool> on{false};
+  std::atomic<uint64_t> cell[256];
+  MergeHits() { for (auto &c : cell) c.store(0, std::memory_order_relaxed); }
+};
+static inline MergeHits &merge_hits() { static MergeHits h; return h; }
+static inline char merge_ops_counted(char real_op, char ideal_op) {
+  MergeHits &h = merge_hits();
+  if (h.on.load(std::memory_order_relaxed))
+    h.cell[(((uint8_t)real_op & 15u) << 4) | ((uint8_t)ideal_op & 15u)].fetch_add(1, std::memory_order_relaxed);
+  return merge_ops(real_op, ideal_op);
 }
 
 // src/bam.cpp:113-315
@@ -633,14 +652,14 @@ static inline std::vector<uint32_t> merge_cigars(const uint32_t *real_cigar, uin
     if (is_override) {
       if (ideal_op == C_DEL_OVERRIDE) {
         uint32_t chunk = ideal_remaining;
-        add_op((uint8_t)merge_ops((char)real_op, (char)ideal_op), chunk);
+        add_op((uint8_t)merge_ops_counted((char)real_op, (char)ideal_op), chunk);
         ideal_pos += chunk;
         if (ideal_pos >= cig_len(ideal[ii])) { ii++; ideal_pos = 0; }
       } else {
         uint32_t chunk = clips_remaining;
         if (chunk > real_remaining) chunk = real_remaining;
         if (chunk > ideal_remaining) chunk = ideal_remaining;
-        add_op((uint8_t)merge_ops((char)real_op, (char)ideal_op), chunk);
+        add_op((uint8_t)merge_ops_counted((char)real_op, (char)ideal_op), chunk);
         clips_remaining -= chunk;
         real_pos += chunk; ideal_pos += chunk;
         if (real_pos >= cig_len(real_cigar[ri])) { ri++; real_pos = 0; }
@@ -649,7 +668,7 @@ static inline std::vector<uint32_t> merge_cigars(const uint32_t *real_cigar, uin
     } else {
       uint32_t chunk = clips_remaining;
       if (chunk > real_remaining) chunk = real_remaining;
-      add_op((uint8_t)merge_ops((char)real_op, (char)ideal_op), chunk);
+      add_op((uint8_t)merge_ops_counted((char)real_op, (char)ideal_op), chunk);
       clips_remaining -= chunk;
       real_pos += chunk;
       if (real_pos >= cig_len(real_cigar[ri])) { ri++; real_pos = 0; }
@@ -689,7 +708,7 @@ static inline std::vector<uint32_t> merge_cigars(const uint32_t *real_cigar, uin
       ii++; ideal_pos = 0;
     } else {
       uint32_t chunk = (real_remaining < ideal_remaining) ? real_remaining : ideal_remaining;
-      uint8_t merged_op = (uint8_t)merge_ops((char)real_op, (char)ideal_op);
+      uint8_t merged_op = (uint8_t)merge_ops_counted((char)real_op, (char)ideal_op);
       add_op(merged_op, chunk);
       real_pos += chunk; ideal_pos += chunk;
       if (real_pos >= cig_len(real_cigar[ri])) { ri++; real_pos = 0; }

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Differential fuzzing of the HIP path against the oracle (not collected by pytest; run on a GPU box:
 `python tests/fuzz_gpu.py [rounds] [seed]`).  Each round draws an annotation size, a read mode, a flag combination
-(incl. the --max-* / --similarity-threshold overrides) and random synth perturbation rates, then compares
+(incl. the --max-* / --similarity-threshold overrides) and random synth perturbation rates -- one round in four takes its
+annotation and reads from tests/adversarial.py instead (the full CIGAR alphabet, see there) -- then compares
   * rows of br_project_batch with the oracle's, and
   * the BAM stream of br_project_bam_bundle (records in / records out) with the oracle's write_to_bam stream.
 Prints the first diverging configuration and exits non-zero."""
@@ -13,12 +14,20 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bramble_amd import lib, synth  # noqa: E402
 from oracle import oracle_binding as ob  # noqa: E402
+from tests import adversarial as adv  # noqa: E402
 from tests.parity import assert_rows_equal  # noqa: E402
+
+
+def adversarial_rounds(rounds, seed):
+    """Which rounds of run(rounds, seed) draw from tests/adversarial.py: a stream of its own, so that the other rounds
+    draw what they drew before there were such rounds, and so that a seed can be checked without a GPU."""
+    return [it for it, u in enumerate(np.random.RandomState((seed + 7919) & 0x7fffffff).rand(rounds)) if u < 0.25]
 
 
 def run(rounds, seed, verbose=True, read_counts=(500, 3000, 9000), gene_counts=(30, 300, 1500)):
     """Returns None when every round agrees, else the description of the first diverging configuration."""
     rng = np.random.RandomState(seed)
+    adversarial = set(adversarial_rounds(rounds, seed))
     for it in range(rounds):
         mode = ["pe", "se", "hifi", "ont"][rng.randint(0, 4)]
         long_mode = mode in ("hifi", "ont")
@@ -53,9 +62,24 @@ def run(rounds, seed, verbose=True, read_counts=(500, 3000, 9000), gene_counts=(
         xs = (not long_mode) and locals().get("xs", False)
         n_reads = int(rng.choice(list(read_counts)))
         desc = dict(it=it, mode=mode, flags=flags, n_genes=n_genes, n_refs=n_refs, n_reads=n_reads, kw=kw, seed=seed)
-        ann = synth.Annotation("G", n_genes=n_genes, n_refs=n_refs, with_genome=with_genome, seed=int(rng.randint(1, 1 << 30)))
-        annd = ann.as_dict()
-        b = ann.reads(n_reads, mode, with_records=1, with_seq=1 if with_genome else 0, seed=int(rng.randint(1, 1 << 30)), xs_tag=bool(xs), **kw)
+        ann_seed, read_seed = int(rng.randint(1, 1 << 30)), int(rng.randint(1, 1 << 30))
+        if it in adversarial:
+            desc["adversarial"] = 1
+            annd = adv.annotation(ann_seed, n_genes=n_genes, n_refs=n_refs, with_genome=with_genome)
+            amode = "long" if long_mode else ("pe" if mode == "pe" else ["se", "mm"][read_seed & 1])
+            orient = "fr" if flags.get("fr") else "rf" if flags.get("rf") else None
+            arng = np.random.RandomState(read_seed)     # (not rng: the rounds after this one keep their draws)
+            desc["kw"] = {"p_off": float(arng.uniform(0, 0.3)), "p_clip": float(arng.uniform(0, 0.8)), "p_tail_pad": float(arng.uniform(0, 0.6))}
+            recs = adv.reads(annd, n_reads, amode, read_seed, with_seq=with_genome, orient=orient, **desc["kw"])
+            b = adv.batch(recs)
+            stream = adv.bam_stream(recs)
+            roff, rlen, _, used = lib.bam_split(stream)
+            assert used == stream.size and len(roff) == len(recs)
+        else:
+            ann = synth.Annotation("G", n_genes=n_genes, n_refs=n_refs, with_genome=with_genome, seed=ann_seed)
+            annd = ann.as_dict()
+            b = ann.reads(n_reads, mode, with_records=1, with_seq=1 if with_genome else 0, seed=read_seed, xs_tag=bool(xs), **kw)
+            stream, roff, rlen = synth.Annotation.frame_records(b)
         idx = lib.Index(annd, device=0)
         ctx = lib.Context(idx)
         ctx.set_param("small_batch", it & 1)        # the path without host round trips on odd rounds, the ordinary one on even rounds
@@ -69,9 +93,8 @@ def run(rounds, seed, verbose=True, read_counts=(500, 3000, 9000), gene_counts=(
         oi = ob.OracleIndex(annd)
         try:
             prod = ctx.project_batch(cfg, b)
-            orc, _, _ = ob.run(oi, ob.make_flags(**flags), b, want_matches=False, bam_records=(b["rec_blob"], b["rec_off"]))
+            orc, _, _ = ob.run(oi, ob.make_flags(**flags), b, want_matches=False)
             assert_rows_equal(prod, orc)
-            stream, roff, rlen = synth.Annotation.frame_records(b)
             got, counters = ctx.project_bam_bundle(cfg, stream, roff, rlen, np.arange(n_refs, dtype=np.int32))
             # the records are the input here (their SEQ carries injected N codes the flat table lacks): oracle from records
             orc2, _, _, _ = ob.run_bam(oi, ob.make_flags(**flags), stream, roff, rlen, np.arange(n_refs, dtype=np.int32))
@@ -83,7 +106,7 @@ def run(rounds, seed, verbose=True, read_counts=(500, 3000, 9000), gene_counts=(
             ctx.close()
             idx.close()
         if verbose:
-            print("ok", it, mode, flags, "rows", orc["n_rows"], flush=True)
+            print("ok", it, "adversarial" if it in adversarial else "synth", mode, flags, "rows", orc["n_rows"], flush=True)
     return None
 
 
@@ -94,7 +117,7 @@ def main():
     if bad:
         print("DIVERGENCE", bad)
         sys.exit(1)
-    print("fuzz ok: %d rounds" % rounds)
+    print("fuzz ok: %d rounds, %d of them adversarial" % (rounds, len(adversarial_rounds(rounds, seed))))
 
 
 if __name__ == "__main__":
