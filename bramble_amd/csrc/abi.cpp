@@ -385,7 +385,8 @@ extern "C" int br_ctx_new(const br_index *ix, br_ctx **out) {
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, ix->device));
   c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  HIPCHK(hipHostMalloc((void **)&c->h_totals, 512 * sizeof(uint64_t), hipHostMallocDefault));   // [0..31] scan totals and counters
+  HIPCHK(hipHostMalloc((void **)&c->rb, sizeof(ReadBack), hipHostMallocDefault));
+  memset(c->rb, 0, sizeof(ReadBack));
   const char *bl = getenv("BRAMBLE_AMD_BAM_LANES");
   if (bl) { int v = atoi(bl); if (v == 0 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) c->bam_lanes = v; }
   const char *spec = getenv("BRAMBLE_AMD_SPECULATE");      // A/B: 0 = large batches always through the ordinary pipeline (three host round trips)
@@ -402,7 +403,7 @@ extern "C" void br_ctx_free(br_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->ix->device);   // (the buffers are freed on this device when the context goes)
   for (auto &e : c->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-  if (c->h_totals) (void)hipHostFree(c->h_totals);
+  if (c->rb) (void)hipHostFree(c->rb);
   for (auto &S : c->stage) if (S.ready) (void)hipEventDestroy(S.ready);
   for (auto &S : c->in_slot) {
     if (S.ready) (void)hipEventDestroy(S.ready);
@@ -410,8 +411,8 @@ extern "C" void br_ctx_free(br_ctx *c) {
   }
   if (c->rows_busy) (void)hipEventDestroy(c->rows_busy);
   if (c->alt.busy) (void)hipEventDestroy(c->alt.busy);
-  if (c->aux2_stream) { (void)hipStreamDestroy(c->aux2_stream); (void)hipEventDestroy(c->aux2_ev); }
-  if (c->ksw_stream) { (void)hipStreamDestroy(c->ksw_stream); for (auto &e : c->ksw_ev) if (e) (void)hipEventDestroy(e); for (auto &e : c->aux_ev) if (e) (void)hipEventDestroy(e); }
+  if (c->side2_stream) (void)hipStreamDestroy(c->side2_stream);
+  if (c->side_stream) { (void)hipStreamDestroy(c->side_stream); for (auto &p : c->side_ev) for (auto &e : p) if (e) (void)hipEventDestroy(e); }
   if (c->run_stream) (void)hipStreamDestroy(c->run_stream);
   if (c->d2h_stream) (void)hipStreamDestroy(c->d2h_stream);
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -462,7 +463,7 @@ extern "C" int br_ctx_kernel_ms(br_ctx *c, int which, double *ms, int32_t *launc
 extern "C" int br_ctx_ksw_diag(br_ctx *c, uint64_t out[16]) {
   if (!c || !out) return BR_ERR_INVALID_ARG;
   memcpy(out, c->ksw_diag, sizeof(c->ksw_diag));
-  out[7] = (uint32_t)c->h_totals[24];
+  out[7] = (uint32_t)c->rb->ksw_left_after;
   return BR_OK;
 }
 

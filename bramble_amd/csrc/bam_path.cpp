@@ -37,8 +37,9 @@ static int bam_encode_impl(br_ctx *c, const br_config *cfg, const br_device_reco
   B.pool = c->cig_arena.as<uint32_t>(); B.l_qseq = c->last_l_qseq;
   B.out_len = c->bam_len.as<uint32_t>(); B.out_off = c->bam_off.as<uint64_t>();
   RC(c->tile_sums.ensure((size_t)std::max<int64_t>(scan_tiles_for(nr + 1), 1) * 8 * 3));
-  RC(c->totals.ensure(16 * 8));
-  B.too_long = c->totals.as<uint64_t>() + 6;
+  RC(ensure_totals(c));
+  uint64_t *d_tot = c->totals.as<uint64_t>();
+  B.too_long = d_tot + TOT_BAM_LONG;
   HIPCHK(hipMemsetAsync(B.too_long, 0, 8, st));
   RC(pf.begin(BR_K_BAM));
   if (!aux_done) { HIPCHK(hipMemsetAsync(B.blob_end, 0, BLOB_END_SLOTS * BLOB_END_STRIDE * 8, st)); launch_bam_scan(st, B); }
@@ -46,20 +47,20 @@ static int bam_encode_impl(br_ctx *c, const br_config *cfg, const br_device_reco
   RC(pf.end());
   ScanArgs S{}; S.n = nr; S.src32 = B.out_len; S.tile_sums = c->tile_sums.as<uint64_t>();
   RC(pf.begin(BR_K_SCAN));
-  launch_scan(st, S, 2, c->bam_off.p, true, c->totals.as<uint64_t>() + 7);
+  launch_scan(st, S, 2, c->bam_off.p, true, d_tot + TOT_BAM_BYTES);
   RC(pf.end());
-  HIPCHK(hipMemcpyAsync(c->h_totals + 10, c->totals.as<uint64_t>() + 6, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(c->rb->bam, d_tot + TOT_BAM_LONG, 16, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  // (h_totals[10], "a spilled CIGAR spans 2^28 reference bases or more", is set by the encoder: checked after it)
-  uint64_t total = nr ? c->h_totals[11] : 0;
+  // (bam[0], "a spilled CIGAR spans 2^28 reference bases or more", is set by the encoder: checked after it)
+  uint64_t total = nr ? c->rb->bam[1] : 0;
   RC(c->bam_out.ensure(std::max<size_t>(total, 16)));
   B.out = c->bam_out.as<uint8_t>();
   RC(pf.begin(BR_K_BAM));
   launch_bam_encode(st, B, c->bam_lanes);
   RC(pf.end());
-  HIPCHK(hipMemcpyAsync(c->h_totals + 10, c->totals.as<uint64_t>() + 6, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(c->rb->bam, d_tot + TOT_BAM_LONG, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (nr && c->h_totals[10]) { pf.collect(); return BR_ERR_UNSUPPORTED; }  // bam_write1 refuses such a record too
+  if (nr && c->rb->bam[0]) { pf.collect(); return BR_ERR_UNSUPPORTED; }  // bam_write1 refuses such a record too
   RC(pf.collect());
   out->data = c->bam_out.as<uint8_t>(); out->n_bytes = total; out->row_off = c->bam_off.as<uint64_t>();
   return BR_OK;
@@ -106,7 +107,7 @@ extern "C" int br_project_bam_device(br_ctx *c, const br_config *cfg, const br_d
   RC(c->bam_aux.ensure(nn * sizeof(BamAux)));
   RC(c->bam_base.ensure(nn * 4));
   RC(c->tile_sums.ensure((size_t)std::max<int64_t>(scan_tiles_for(n + 1), 1) * 8 * 3));
-  RC(c->totals.ensure(16 * 8));
+  RC(ensure_totals(c));
   if (n_ref_map) HIPCHK(hipMemcpyAsync(c->p_ref_map.p, ref_map, (size_t)n_ref_map * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(c->p_small.p, 0, 64, st));  // [0] max n_cigar, [1] max soft clip, [2] big-group count
 
@@ -125,31 +126,31 @@ extern "C" int br_project_bam_device(br_ctx *c, const br_config *cfg, const br_d
   RC(c->bam_end.ensure(BLOB_END_SLOTS * BLOB_END_STRIDE * 8)); B.blob_end = c->bam_end.as<uint64_t>();
   HIPCHK(hipMemsetAsync(B.blob_end, 0, BLOB_END_SLOTS * BLOB_END_STRIDE * 8, st));
 
-  // the aux walk of the records (one lane per record, latency-bound) on the second stream beside the reader side
+  // the aux walk of the records (one lane per record, latency-bound) on the side stream beside the reader side
   // (k_rec_fields .. k_mates, the same kind of kernel over the same records): joined below, in front of the projection
-  RC(ensure_aux_stream(c));
-  HIPCHK(hipEventRecord(c->aux_ev[0], st));
-  HIPCHK(hipStreamWaitEvent(c->ksw_stream, c->aux_ev[0], 0));
-  RC(pf.begin(BR_K_BAM, c->ksw_stream));
-  launch_bam_scan(c->ksw_stream, B);
+  RC(ensure_side_stream(c));
+  SideWork aux_walk(c, st, c->side_stream);
+  RC(aux_walk.fork());
+  RC(pf.begin(BR_K_BAM, c->side_stream));
+  launch_bam_scan(c->side_stream, B);
   RC(pf.end());
-  HIPCHK(hipEventRecord(c->aux_ev[1], c->ksw_stream));
+  RC(aux_walk.done());
   RC(pf.begin(BR_K_PARSE));
   launch_rec_fields(st, P);
   RC(pf.end());
   uint64_t *d_tot = c->totals.as<uint64_t>();
   ScanArgs S{}; S.n = n; S.tile_sums = c->tile_sums.as<uint64_t>();
   RC(pf.begin(BR_K_SCAN));
-  S.src32 = P.ncig;     launch_scan(st, S, 2, c->b_cigar_off.p, false, d_tot + 0);
-  S.src32 = P.name_len; launch_scan(st, S, 2, c->b_name_off.p, false, d_tot + 1);
-  S.src32 = P.isnew;    launch_scan(st, S, 2, c->p_group_pre.p, false, d_tot + 2);
+  S.src32 = P.ncig;     launch_scan(st, S, 2, c->b_cigar_off.p, false, d_tot + TOT_PARSE_CIGAR);
+  S.src32 = P.name_len; launch_scan(st, S, 2, c->b_name_off.p, false, d_tot + TOT_PARSE_NAMES);
+  S.src32 = P.isnew;    launch_scan(st, S, 2, c->p_group_pre.p, false, d_tot + TOT_PARSE_GROUPS);
   RC(pf.end());
-  HIPCHK(hipMemcpyAsync(c->h_totals + 16, d_tot, 3 * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(c->h_totals + 20, c->p_small.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(c->rb->parse_n, d_tot + TOT_PARSE_CIGAR, 3 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&c->rb->parse_max, c->p_small.p, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  uint64_t n_words = c->h_totals[16], name_bytes = c->h_totals[17], ng = c->h_totals[18];
-  uint32_t max_nc = (uint32_t)(c->h_totals[20] & 0xffffffffu), max_clip = (uint32_t)(c->h_totals[20] >> 32);
-  if (n_words >= 0xffffffffull - (uint64_t)n || name_bytes >= 0xfffffff0ull) { (void)hipStreamSynchronize(c->ksw_stream); pf.collect(); return BR_ERR_CAPACITY; }
+  uint64_t n_words = c->rb->parse_n[0], name_bytes = c->rb->parse_n[1], ng = c->rb->parse_n[2];
+  uint32_t max_nc = (uint32_t)(c->rb->parse_max & 0xffffffffu), max_clip = (uint32_t)(c->rb->parse_max >> 32);
+  if (n_words >= 0xffffffffull - (uint64_t)n || name_bytes >= 0xfffffff0ull) { pf.collect(); return BR_ERR_CAPACITY; }
   RC(c->b_cigar.ensure(std::max<size_t>((size_t)n_words, 1) * 4)); RC(c->b_names.ensure(std::max<size_t>((size_t)name_bytes, 1)));
   RC(c->b_group_off.ensure(((size_t)ng + 1) * 4));
   P.n_groups = (int64_t)ng; P.group_off = c->b_group_off.as<uint32_t>();
@@ -159,7 +160,7 @@ extern "C" int br_project_bam_device(br_ctx *c, const br_config *cfg, const br_d
   launch_rec_copy(st, P);
   launch_mates(st, P);
   RC(pf.end());
-  HIPCHK(hipStreamWaitEvent(st, c->aux_ev[1], 0));   // k_bam_scan: XS / ts characters, the aux table
+  RC(aux_walk.join());   // k_bam_scan: XS / ts characters, the aux table
 
   br_device_batch db{};
   if (fa_mode) {
@@ -169,11 +170,11 @@ extern "C" int br_project_bam_device(br_ctx *c, const br_config *cfg, const br_d
     launch_seq_src(st, P);
     RC(pf.end());
     RC(pf.begin(BR_K_SCAN));
-    S.src32 = P.seq_len; launch_scan(st, S, 2, c->b_seq_off.p, false, d_tot + 3);
+    S.src32 = P.seq_len; launch_scan(st, S, 2, c->b_seq_off.p, false, d_tot + TOT_PARSE_SEQ);
     RC(pf.end());
-    HIPCHK(hipMemcpyAsync(c->h_totals + 19, d_tot + 3, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&c->rb->parse_seq, d_tot + TOT_PARSE_SEQ, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    uint64_t sbytes = c->h_totals[19];
+    uint64_t sbytes = c->rb->parse_seq;
     if (sbytes >= 0xfffffff0ull) { pf.collect(); return BR_ERR_CAPACITY; }
     RC(c->b_seqs.ensure(std::max<size_t>((size_t)sbytes, 1)));
     P.seqs = c->b_seqs.as<uint8_t>();
@@ -218,7 +219,8 @@ static int deflate_device_impl(br_ctx *c, const uint8_t *src, uint64_t n, hipStr
   uint64_t nb = (n + DEFLATE_PAYLOAD - 1) / DEFLATE_PAYLOAD;
   RC(c->z_slots.ensure((size_t)nb * DEFLATE_SLOT)); RC(c->z_sizes.ensure((size_t)nb * 4)); RC(c->z_off.ensure(((size_t)nb + 1) * 8));
   RC(c->tile_sums.ensure((size_t)std::max<int64_t>(scan_tiles_for((int64_t)nb + 1), 1) * 8 * 3));
-  RC(c->totals.ensure(16 * 8));
+  RC(ensure_totals(c));
+  uint64_t *d_tot = c->totals.as<uint64_t>();
   DeflateArgs A{};
   A.src = src; A.n_bytes = n; A.n_blocks = nb; A.slots = c->z_slots.as<uint8_t>(); A.sizes = c->z_sizes.as<uint32_t>();
   A.crc_tab = c->z_tabs.as<uint32_t>(); A.crc_shift = c->z_tabs.as<uint32_t>() + 256;
@@ -232,7 +234,7 @@ static int deflate_device_impl(br_ctx *c, const uint8_t *src, uint64_t n, hipStr
     HIPCHK(hipMemsetAsync(c->z_tokens.as<uint8_t>() + (size_t)dyn_waves * DEFLATE_PAYLOAD * 4, 0, 64, st));
 #endif
     A.tokens = c->z_tokens.as<uint32_t>();
-    A.queue = (uint32_t *)(c->totals.as<uint64_t>() + 15);
+    A.queue = (uint32_t *)(d_tot + TOT_DEFLATE_QUEUE);
     HIPCHK(hipMemsetAsync(A.queue, 0, 8, st));
   }
   RC(pf.begin(BR_K_CODEC));
@@ -250,11 +252,11 @@ static int deflate_device_impl(br_ctx *c, const uint8_t *src, uint64_t n, hipStr
 #endif
   ScanArgs S{}; S.n = (int64_t)nb; S.src32 = A.sizes; S.tile_sums = c->tile_sums.as<uint64_t>();
   RC(pf.begin(BR_K_SCAN));
-  launch_scan(st, S, 2, c->z_off.p, true, c->totals.as<uint64_t>() + 5);
+  launch_scan(st, S, 2, c->z_off.p, true, d_tot + TOT_DEFLATE);
   RC(pf.end());
-  HIPCHK(hipMemcpyAsync(c->h_totals + 24, c->totals.as<uint64_t>() + 5, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&c->rb->deflate_total, d_tot + TOT_DEFLATE, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  uint64_t total = c->h_totals[24];
+  uint64_t total = c->rb->deflate_total;
   DevBuf &dense = c->z_dense_which ? c->z_dense_alt : c->z_dense;
   RC(dense.ensure((size_t)total + 16));
   RC(pf.begin(BR_K_CODEC));

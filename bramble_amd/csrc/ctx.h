@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cassert>
 #include <string>
 #include <vector>
 
@@ -32,6 +33,33 @@ struct br_index {
 };
 
 struct KEvent { int which; hipEvent_t a, b; };
+
+// The pinned read-back page (br_ctx::rb, one hipHostMalloc): every word a device-to-host copy brings home, named for what
+// it holds and grouped by owner.  No member has two owners; words that one copy fetches together are one array.
+struct ReadBack {
+  // the projection (pipeline.cpp)
+  uint64_t scan[5];                       // TOT_MATCHES .. TOT_RAW as the scans left them (the row scan: scan[TOT_ROWS] alone)
+  uint64_t counters[4];                   // PairArgs::counters of the call: -, unique reads, dropped reads, a field overflowed its width
+  uint64_t small[TOT_SMALL_CNT + 4];      // run_device_small: the totals up to its counter block, one copy at the end
+  uint64_t direct_cnt[GD_COUNTER_WORDS];  // run_device_direct: the four counters + k_group_desc's slots
+  uint64_t side[2];                       //   its side arena: entries asked for, overflowed
+  uint64_t wide_cigar;                    // expand_rows: CIGAR words of the wide view
+  // the -S rescue
+  uint64_t rescue_n[2];                 // problems, sequence bytes (TOT_RESCUE_PROB, TOT_RESCUE_SEQ)
+  uint64_t rescue_stats[2];               // DP cells, accepted rescues
+  uint32_t ksw_bins[16];                  // run_ksw: k_ksw_bin's counters of a piece (problems per bin, leftovers, maxima, tape rows)
+  uint64_t ksw_left_after;                // leftovers of the last piece after the DP (br_ctx_ksw_diag out[7]; low 32 bits)
+  // BAM in and out (bam_path.cpp)
+  uint64_t parse_n[3];                  // CIGAR words, name bytes, read-name groups (TOT_PARSE_CIGAR ..)
+  uint64_t parse_seq;                     // sequence bytes (-S)
+  uint64_t parse_max;                     // max n_cigar | max soft clip << 32
+  uint64_t bam[2];                        // the encoder: a record it cannot write, the records' bytes (TOT_BAM_LONG, TOT_BAM_BYTES)
+  uint64_t deflate_total;                 // compressed bytes of a BGZF call
+  // flat batches (host_rows.cpp)
+  uint64_t host_groups, host_max, host_pool;   // read-name groups, max n_cigar | max soft clip << 32, dense pool words
+  // SAM text out (sam_writer.cpp)
+  uint64_t sam_bad, sam_bytes;            // the first record the text cannot say (~0: none), the text's bytes
+};
 
 struct br_ctx {
   const br_index *ix = nullptr;
@@ -118,8 +146,11 @@ struct br_ctx {
   // rows / offsets, the direction tape, raw traceback ops
   DevBuf ksw_desc, ksw_dp, ksw_left, ksw_cnt, ksw_group, ksw_tape, ksw_raw;
   int ksw_fast = 1;            // 0: every problem through the general kernel k_ksw
-  hipStream_t ksw_stream = nullptr; hipEvent_t ksw_ev[KSW_N_BINS + 1] = {}; hipEvent_t aux_ev[8] = {};   // the second stream
-  hipStream_t aux2_stream = nullptr; hipEvent_t aux2_ev = nullptr;   // a third one: the name seeds of the direct path beside k_pair_mask
+  // the side stream (ensure_side_stream) for kernels that run beside the main chain, a second one (ensure_side2_stream: the
+  // name seeds of the direct path beside k_pair_mask), and the event pairs a SideWork in scope holds (side_live of them)
+  hipStream_t side_stream = nullptr, side2_stream = nullptr;
+  static constexpr int SIDE_EV = 8;
+  hipEvent_t side_ev[SIDE_EV][2] = {}; int side_live = 0;
   uint32_t ksw_groups[KSW_N_BINS] = {0};
   int64_t ksw_tape_mb = 49152; // HBM set aside for the direction tape; larger batches go through in pieces
   int ksw_tape_pct = 100;      // test hook: the share of the computed tape the DP kernels may use (the rest of the problems goes to k_ksw)
@@ -132,7 +163,7 @@ struct br_ctx {
   DevBuf b_name_off, b_names;
   // device staging of host batches (br_project_batch)
   DevBuf b_ref_id, b_ref_start, b_flags, b_xs, b_ts, b_cigar_off, b_cigar, b_mate_idx, b_group_off, b_lqseq;
-  uint64_t *h_totals = nullptr;  // pinned, 512 words ([192..] the direct path's counters with k_group_desc's slots)
+  ReadBack *rb = nullptr;        // pinned
   // host result storage (br_project_batch / br_project_group)
   // pinned: the row download runs at PCIe speed instead of through the pageable bounce path
   PinnedVec<int32_t> h_input, h_clip, h_junc, h_refc, h_mate_tid, h_mate_pos, h_isize;
@@ -188,6 +219,26 @@ struct Prof {
   }
 };
 
+// One piece of work on a side stream beside the main chain: fork (the side stream waits for what the main one has queued),
+// the work, done (recorded behind it), join (the main stream waits for it).  Leaving the scope finishes what is open, so no
+// return leaves side-stream kernels over the context's tables with nothing on the caller's stream ordered behind them.  A
+// fork after a join starts over.  The events are the context's: a pair per SideWork in scope.
+struct SideWork {
+  br_ctx *c; hipStream_t main, side; hipEvent_t *ev;
+  enum { IDLE, FORKED, DONE } state = IDLE;
+  SideWork(br_ctx *c_, hipStream_t main_, hipStream_t side_) : c(c_), main(main_), side(side_), ev(c_->side_ev[c_->side_live++]) { assert(c->side_live <= br_ctx::SIDE_EV); }
+  SideWork(const SideWork &) = delete;
+  ~SideWork() { if (state == FORKED) (void)done(); if (state == DONE) (void)join(); c->side_live--; }
+  int fork() { HIPCHK(hipEventRecord(ev[0], main)); HIPCHK(hipStreamWaitEvent(side, ev[0], 0)); state = FORKED; return BR_OK; }
+  int done() { HIPCHK(hipEventRecord(ev[1], side)); state = DONE; return BR_OK; }
+  int join() { return join_on(main); }
+  int join_on(hipStream_t other) { state = IDLE; HIPCHK(hipStreamWaitEvent(other, ev[1], 0)); return BR_OK; }   // (another side stream takes the result)
+  int wait_host() { state = IDLE; HIPCHK(hipEventSynchronize(ev[1])); return BR_OK; }   // (the host reallocates what the work reads)
+};
+
+// the device totals (kernels.h: TOT_*)
+inline int ensure_totals(br_ctx *c) { return c->totals.ensure(TOT_N * 8); }
+
 // the next run_device call should leave the detail column (input alignment, junc_hits, aligned_len, HI) next to the rows:
 // the direct path then writes it in the emit pass instead of emitting a second time on request
 struct WantDetail { br_ctx *c; bool old; WantDetail(br_ctx *c_, bool v) : c(c_), old(c_->want_x) { c->want_x = v; } ~WantDetail() { c->want_x = old; } };
@@ -204,7 +255,7 @@ struct KswRun {
 
 int check_device(int device);
 int make_devcfg(const br_config *c, DevCfg &d);
-int ensure_aux_stream(br_ctx *c);
+int ensure_side_stream(br_ctx *c);
 int run_ksw(br_ctx *c, hipStream_t st, const KswRun &R);
 // keep_events: append to the running event list instead of restarting it
 int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStream_t st, br_device_rows *out,

@@ -681,7 +681,7 @@ __global__ void __launch_bounds__(256) k_expand_rows(DirectArgs D) {
   __shared__ uint32_t sh_pre[4][64], sh_v[4][64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (D.m_aln_cap && D.tot[0] > D.m_aln_cap) return;   // launched ahead with the last call's list: too small this time (the host launches again)
+  if (D.m_aln_cap && D.tot[TOT_MATCHES] > D.m_aln_cap) return;   // launched ahead with the last call's list: too small this time (the host launches again)
   if (D.side_used[1]) return;   // the side arena ran out: counts and class positions are not to be trusted (see k_group_desc)
   uint32_t nk = 0, pos = 0, v = 0;
   bool fast = false;

@@ -27,9 +27,9 @@ static int d2h(PinnedVec<T> &dst, const void *src, size_t n, hipStream_t st) {
 static int ensure_streams(br_ctx *c) {
   // The runtime keeps a small pool of hardware queues per stream priority and lets streams of one priority share them once
   // there are more streams than queues: two streams on one queue run one after the other.  The context's kernel streams
-  // (run, aux, aux2, the caller's) are of normal priority; the upload stream takes the high pool and the download stream the
+  // (run, side, side2, the caller's) are of normal priority; the upload stream takes the high pool and the download stream the
   // low one, so that neither transfer ever queues behind the other or behind a kernel stream (a context that had already
-  // created its aux streams -- a device-resident call first -- found its uploads and downloads serialised: 80 ms per
+  // created its side streams -- a device-resident call first -- found its uploads and downloads serialised: 80 ms per
   // PCIe-inclusive step where 60 is the wire, profiles/pcie_phases.py)
   int prio_low = 0, prio_high = 0;
   HIPCHK(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
@@ -99,7 +99,7 @@ static int prep_staged(br_ctx *c, const br_config *cfg, br_ctx::InSlot &S, hipSt
   if (S.has_seq) { RC(S.seq_off.ensure((nn + 1) * 4)); RC(S.seq_src.ensure(nn * 4)); }
   RC(c->p_small.ensure(64)); RC(c->p_big.ensure((nn / 96 + 2) * 4));
   RC(c->tile_sums.ensure((size_t)std::max<int64_t>(scan_tiles_for(n + 1), 1) * 8 * 3));
-  RC(c->totals.ensure(16 * 8));
+  RC(ensure_totals(c));
   HIPCHK(hipMemsetAsync(c->p_small.p, 0, 64, st));
   SoaArgs A{};
   A.n = n; A.cigar_off64 = S.cigar_off64.as<uint64_t>(); A.name_off64 = S.name_off64.as<uint64_t>();
@@ -109,12 +109,12 @@ static int prep_staged(br_ctx *c, const br_config *cfg, br_ctx::InSlot &S, hipSt
   launch_soa_fields(st, A);
   uint64_t *d_tot = c->totals.as<uint64_t>();
   ScanArgs SC{}; SC.n = n; SC.tile_sums = c->tile_sums.as<uint64_t>(); SC.src32 = A.isnew;
-  launch_scan(st, SC, 2, S.group_pre.p, false, d_tot + 9);
-  HIPCHK(hipMemcpyAsync(c->h_totals + 26, d_tot + 9, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(c->h_totals + 27, c->p_small.p, 8, hipMemcpyDeviceToHost, st));
+  launch_scan(st, SC, 2, S.group_pre.p, false, d_tot + TOT_HOST_GROUPS);
+  HIPCHK(hipMemcpyAsync(&c->rb->host_groups, d_tot + TOT_HOST_GROUPS, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&c->rb->host_max, c->p_small.p, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  const uint64_t ng = c->h_totals[26];
-  const uint32_t max_nc = (uint32_t)(c->h_totals[27] & 0xffffffffu), max_clip = (uint32_t)(c->h_totals[27] >> 32);
+  const uint64_t ng = c->rb->host_groups;
+  const uint32_t max_nc = (uint32_t)(c->rb->host_max & 0xffffffffu), max_clip = (uint32_t)(c->rb->host_max >> 32);
   RC(S.group_off.ensure(((size_t)ng + 1) * 4));
   ParseArgs P{};
   P.n = n; P.n_groups = (int64_t)ng; P.isnew = A.isnew; P.group_pre = S.group_pre.as<uint32_t>(); P.group_off = S.group_off.as<uint32_t>();
@@ -168,10 +168,10 @@ extern "C" int br_project_staged(br_ctx *c, const br_config *cfg, int slot, br_h
     if (c->host_detail) RC(ensure_detail(c, st));
     launch_pool_sizes(st, Q);
     ScanArgs SP{}; SP.n = (int64_t)nr; SP.src32 = Q.sizes; SP.tile_sums = c->tile_sums.as<uint64_t>();
-    launch_scan(st, SP, 2, c->pool_off.p, true, c->totals.as<uint64_t>() + 10);
-    HIPCHK(hipMemcpyAsync(c->h_totals + 28, c->totals.as<uint64_t>() + 10, 8, hipMemcpyDeviceToHost, st));
+    launch_scan(st, SP, 2, c->pool_off.p, true, c->totals.as<uint64_t>() + TOT_HOST_POOL);
+    HIPCHK(hipMemcpyAsync(&c->rb->host_pool, c->totals.as<uint64_t>() + TOT_HOST_POOL, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    np = (size_t)c->h_totals[28];
+    np = (size_t)c->rb->host_pool;
     RC(c->pool.ensure(std::max<size_t>(np, 1) * 4));
     Q.pool = c->pool.as<uint32_t>();
     launch_pool_copy(st, Q, np > 8 * nr);

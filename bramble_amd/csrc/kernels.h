@@ -8,6 +8,32 @@
 
 namespace br {
 
+// The slots of the context's device totals (br_ctx::totals, 8-byte words): one owner each.  TOT_MATCHES .. TOT_RAW are written
+// consecutively by the three- and five-value scans and read back by the kernels (ProjectArgs::tot, PairArgs::tot,
+// DirectArgs::tot); the others are the host's, and words that one download brings home together are adjacent.
+enum {
+  TOT_MATCHES = 0,        // matches (direct rows: kept matches)
+  TOT_ARENA = 1,          // rewritten CIGAR words
+  TOT_SIMPLE = 2,         // matches of the simple class
+  TOT_ROWS = 3,           // records (the row scan; k_scan5)
+  TOT_RAW = 4,            // survivors before pairing (k_scan5)
+  TOT_RESCUE_PROB = 5,    // -S: DP problems,
+  TOT_RESCUE_SEQ = 6,     //     their sequence bytes
+  TOT_WIDE_CIGAR = 7,     // the wide view's CIGAR words (expand_rows)
+  TOT_SMALL_CNT = 8,      // [4] run_device_small's counter block (PairArgs::counters): one download with TOT_MATCHES .. TOT_ROWS
+  TOT_PARSE_CIGAR = 12,   // the record parser: CIGAR words,
+  TOT_PARSE_NAMES = 13,   //     name bytes,
+  TOT_PARSE_GROUPS = 14,  //     read-name groups,
+  TOT_PARSE_SEQ = 15,     //     sequence bytes (-S)
+  TOT_BAM_LONG = 16,      // the BAM encoder: a record it cannot write,
+  TOT_BAM_BYTES = 17,     //     the records' bytes
+  TOT_DEFLATE = 18,       // the deflater: compressed bytes,
+  TOT_DEFLATE_QUEUE = 19, //     its block queue (two u32)
+  TOT_HOST_GROUPS = 20,   // host_rows.cpp: read-name groups,
+  TOT_HOST_POOL = 21,     //     dense pool words
+  TOT_N
+};
+
 struct ProjectArgs {
   DevIndex ix;
   DevCfg cfg;
@@ -39,15 +65,15 @@ struct ProjectArgs {
   uint4 *m_b;            // {clip_score, 0, similarity lo, similarity hi}
   uint64_t *m_cigoff;
   uint32_t *cig_arena;
-  // small batches without host round trips: the scan totals stay on the device (tot[0] matches, tot[1] arena words,
-  // tot[2] matches of the simple class), the tables were sized from upper bounds lim_m / lim_c, and a kernel that finds the
+  // small batches without host round trips: the scan totals stay on the device (TOT_MATCHES, TOT_ARENA,
+  // TOT_SIMPLE), the tables were sized from upper bounds lim_m / lim_c, and a kernel that finds the
   // totals beyond them does nothing (the host sees the same totals at the end and takes the ordinary path).  null: the
   // host read the totals and passes them by value
   const uint64_t *tot;
   uint64_t lim_m, lim_c;
   uint64_t cover;        // work-list entries the launch's grid covers (large batches launched from predicted counts): more -> nothing is done
 };
-__device__ __forceinline__ bool tot_over(const uint64_t *tot, uint64_t lim_m, uint64_t lim_c) { return tot && (tot[0] > lim_m || tot[1] > lim_c); }
+__device__ __forceinline__ bool tot_over(const uint64_t *tot, uint64_t lim_m, uint64_t lim_c) { return tot && (tot[TOT_MATCHES] > lim_m || tot[TOT_ARENA] > lim_c); }
 
 // What the split count pass (k_project<G, false, false, 1 / 2>) reads and writes, and nothing else: every uniform value the
 // kernels keep live is an SGPR, and with ProjectArgs the main one spilled 37 of them to VGPR lanes.  The preset flags
@@ -179,11 +205,11 @@ struct PairArgs {
   double *r_sim;            // aux presets only (similarity filter on)
   int32_t *r_clip;
   uint64_t *counters;       // [4] total_complete, total_unique, dropped_reads, a field overflowed its packed width
-  const uint64_t *tot;      // small batches (see ProjectArgs): tot[0..1] against lim_m / lim_c, tot[3] = records (n_rows_total is then the tables' capacity)
+  const uint64_t *tot;      // small batches (see ProjectArgs): TOT_MATCHES / TOT_ARENA against lim_m / lim_c, TOT_ROWS = records (n_rows_total is then the tables' capacity)
   uint64_t lim_m, lim_c;
-  uint64_t lim_r;           // records the row tables (and the row kernel's grid) hold; tot[3] beyond it -> the kernels behind the row scan do nothing
+  uint64_t lim_r;           // records the row tables (and the row kernel's grid) hold; TOT_ROWS beyond it -> the kernels behind the row scan do nothing
 };
-__device__ __forceinline__ bool rows_over(const uint64_t *tot, uint64_t lim_r) { return tot && tot[3] > lim_r; }
+__device__ __forceinline__ bool rows_over(const uint64_t *tot, uint64_t lim_r) { return tot && tot[TOT_ROWS] > lim_r; }
 #define RR_HI 0x0fffffffu        // r_rec.w bits 0..27: HI
 #define RR_PRIMARY (1u << 28)
 #define RR_PAIRED (1u << 29)
@@ -237,7 +263,7 @@ struct DirectArgs {
   uint2 *dpos;                   // [n_aln] k_expand_rows: {first record, position of its entries in the emit work list}
   uint32_t *hi0;                 // [n_aln] HI of the alignment's first record
   uint64_t *counters;            // [4] total_complete, total_unique, dropped_reads, a field overflowed its packed width; + k_group_desc's slots (GD_*)
-  const uint64_t *tot;           // scan totals on the device: [0] kept, [1] arena words, [2] kept of the simple class, [3] records, [4] survivors
+  const uint64_t *tot;           // scan totals on the device (TOT_*): kept, arena words, kept of the simple class, records, survivors
   // emit
   uint32_t *m_aln;               // emit work list
   uint64_t m_aln_cap;            // its room in entries when k_expand_rows is launched ahead of the host's look at the totals (0: the list was sized for them)

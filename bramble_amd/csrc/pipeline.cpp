@@ -6,14 +6,13 @@
 
 #include "ctx.h"
 
-// a second stream for kernels that can run beside the main one (a shape's tracebacks beside the next shape's DP; the
-// few-block emit kernel of the > 64-candidate alignments beside the work-list kernels); it and the third (aux2_stream) are
-// of normal priority (0)
-int ensure_aux_stream(br_ctx *c) {
-  if (c->ksw_stream) return BR_OK;
-  HIPCHK(hipStreamCreateWithPriority(&c->ksw_stream, hipStreamNonBlocking, 0));
-  for (auto &e : c->ksw_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto &e : c->aux_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+// the side stream for kernels that can run beside the main one (a shape's tracebacks beside the next shape's DP; the
+// few-block emit kernel of the > 64-candidate alignments beside the work-list kernels), with the events of every SideWork;
+// it and the second one (side2_stream) are of normal priority (0)
+int ensure_side_stream(br_ctx *c) {
+  if (c->side_stream) return BR_OK;
+  HIPCHK(hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, 0));
+  for (auto &p : c->side_ev) for (auto &e : p) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   return BR_OK;
 }
 
@@ -51,12 +50,13 @@ int run_ksw(br_ctx *c, hipStream_t st, const KswRun &R) {
     return BR_OK;
   };
   memset(c->ksw_diag, 0, sizeof(c->ksw_diag));
-  c->h_totals[24] = 0;
+  c->rb->ksw_left_after = 0;
   if (!c->ksw_fast) return general(n_all, qmax, tmax, nullptr, nullptr);
 
   RC(c->ksw_raw.ensure((size_t)(R.seq_total + n_all + 1) * 4));
   RC(c->ksw_cnt.ensure(128));
-  uint32_t *h_cnt = (uint32_t *)(c->h_totals + 16);   // 16 words of the pinned totals
+  RC(ensure_side_stream(c));
+  uint32_t *h_cnt = c->rb->ksw_bins;
   const uint64_t tape_budget = (uint64_t)c->ksw_tape_mb << 20;
   // groups of a bin = what is resident at once (one wave of blocks: every group runs from the first cycle)
   uint32_t max_groups[KSW_N_BINS];
@@ -105,6 +105,7 @@ int run_ksw(br_ctx *c, hipStream_t st, const KswRun &R) {
       continue;
     }
     const uint32_t n_left = h_cnt[KSW_N_BINS];
+    SideWork traces(c, st, c->side_stream);
     c->ksw_diag[0]++;
     for (int b = 0; b < KSW_N_BINS; b++) c->ksw_diag[1 + b] += h_cnt[b];
     c->ksw_diag[5] += n_left; c->ksw_diag[6] = std::max<uint64_t>(c->ksw_diag[6], tape_bytes);
@@ -112,36 +113,43 @@ int run_ksw(br_ctx *c, hipStream_t st, const KswRun &R) {
     if (n_groups_total) {
       RC(c->ksw_tape.ensure((size_t)tape_bytes + 256));
       A.tape = c->ksw_tape.as<uint8_t>(); A.tape_cap = tape_bytes / 100 * (uint64_t)c->ksw_tape_pct;
-      // a shape's tracebacks (one lane per problem, waiting on tape lines) run on a second stream beside the next shape's
+      // a shape's tracebacks (one lane per problem, waiting on tape lines) run on the side stream beside the next shape's
       // DP kernel (issue-bound, one wave of registers to spare per SIMD)
-      RC(ensure_aux_stream(c));
       for (int b = KSW_N_BINS - 1; b >= 0; b--) {     // widest shape first: the exposed last traceback is the smallest shape's
         if (!A.n_bin[b]) continue;
         launch_ksw_dp(st, A, b);
-        HIPCHK(hipEventRecord(c->ksw_ev[b], st));
-        HIPCHK(hipStreamWaitEvent(c->ksw_stream, c->ksw_ev[b], 0));
-        launch_ksw_trace(c->ksw_stream, A, b);
+        RC(traces.fork());
+        launch_ksw_trace(c->side_stream, A, b);
       }
-      HIPCHK(hipEventRecord(c->ksw_ev[KSW_N_BINS], c->ksw_stream));
+      RC(traces.done());
     }
     // what the arrays do not take: targets beyond the widest array, and (never seen outside tests) groups whose tape ran out
     // (problems a wave hands back when the tape runs out come from the arrays: at most KSW_MAX_SPAN bases)
     RC(general(n_left ? n_left : 64, std::max<uint64_t>(h_cnt[5], KSW_MAX_SPAN), std::max<uint64_t>(h_cnt[6], KSW_BIN_W(KSW_N_BINS - 1)), A.leftover, A.counters + KSW_N_BINS));
-    if (n_groups_total) HIPCHK(hipStreamWaitEvent(st, c->ksw_ev[KSW_N_BINS], 0));   // the tape and the result arrays are free again
+    if (n_groups_total) RC(traces.join());   // the tape and the result arrays are free again
     // leftovers after the DP (those of the last piece; read by br_ctx_ksw_diag once the stream has been synchronised)
-    HIPCHK(hipMemcpyAsync((uint32_t *)(c->h_totals + 24), A.counters + KSW_N_BINS, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&c->rb->ksw_left_after, A.counters + KSW_N_BINS, 4, hipMemcpyDeviceToHost, st));
   }
   return BR_OK;
 }
 
-// ---- what the three pipelines share: the tables and arguments of the count pass, its launch, the match table's emit
-// pass and the end of a call ----
+// ---- what the three pipelines share: the segment stage, the tables and arguments of the count pass, its launch, the match
+// table's arguments and emit pass, pairing's arguments, the row tables, the row tail and the end of a call ----
+// a1/a2/a6: CIGAR -> read exons (X: what the small route has the kernel do on the side)
+static int segment_stage(br_ctx *c, hipStream_t st, const DevCfg &dc, const br_device_batch *b, Prof &pf, const SegExtra *X = nullptr) {
+  RC(pf.begin(BR_K_SEGMENT));
+  launch_segment(st, b->n_aln, b->ref_id, b->ref_start, b->flags, b->xs, b->ts, b->cigar_off, b->cigar, dc, c->ix->n_refs,
+                 c->seg.as<uint2>(), c->meta.as<AlnMeta>(), c->head.as<uint4>(), c->head2.as<uint4>(), c->fast_flag.as<uint32_t>(), X);
+  RC(pf.end());
+  return BR_OK;
+}
+
 static int ensure_count_tables(br_ctx *c, const br_device_batch *b) {
   const int64_t n = b->n_aln;
   RC(c->seg.ensure((size_t)(b->n_cigar_words + n) * sizeof(uint2)));
   RC(c->meta.ensure((size_t)n * sizeof(AlnMeta))); RC(c->head.ensure((size_t)n * sizeof(uint4))); RC(c->head2.ensure((size_t)n * sizeof(uint4)));
   RC(c->fast_flag.ensure((size_t)n * 4)); RC(c->ranges.ensure((size_t)n * sizeof(uint4))); RC(c->mask.ensure((size_t)n * 8));
-  RC(c->cig_base.ensure((size_t)(n + 1) * 8)); RC(c->big_list.ensure((size_t)n * 4)); RC(c->totals.ensure(16 * 8));
+  RC(c->cig_base.ensure((size_t)(n + 1) * 8)); RC(c->big_list.ensure((size_t)n * 4)); RC(ensure_totals(c));
   return BR_OK;
 }
 
@@ -192,6 +200,14 @@ static int count_pass(br_ctx *c, hipStream_t st, const ProjectArgs &A, Prof &pf,
   return BR_OK;
 }
 
+// what the three-value scan reads (matches per alignment; CIGAR sizes from the exon heads; the simple class)
+static ScanArgs scan3_args(br_ctx *c, const br_device_batch *b) {
+  ScanArgs S{};
+  S.n = b->n_aln; S.src32 = c->n_matches.as<uint32_t>(); S.cigar_off = b->cigar_off; S.head = c->head.as<uint4>();
+  S.tile_sums = c->tile_sums.as<uint64_t>(); S.fast_flag = c->fast_flag.as<uint32_t>();
+  return S;
+}
+
 // the match table's emit pass over a work list of n_list entries: without the similarity filter, its simple prefix (one
 // read exon from a single M op, n_simple entries) and the rest as two launches; with it, the whole list in one
 static int emit_match_table(hipStream_t st, const ProjectArgs &A, Prof &pf, int64_t n_list, int64_t n_simple) {
@@ -210,17 +226,146 @@ static int emit_match_table(hipStream_t st, const ProjectArgs &A, Prof &pf, int6
   return BR_OK;
 }
 
-// the counts of a finished call (h_totals[5..6]: unique reads, dropped reads) and what the context keeps of it; the row
-// table pointers are the caller's
+// the match table for n_m matches and the CIGAR arena for n_c words (0: as earlier calls left them), and A pointed at them
+static int match_tables(br_ctx *c, ProjectArgs &A, uint64_t n_m, uint64_t n_c) {
+  if (n_m) {
+    RC(c->m_tid.ensure(n_m * 4)); RC(c->m_aux.ensure(n_m * 4)); RC(c->m_p.ensure(n_m * sizeof(uint2))); RC(c->m_x.ensure(n_m * sizeof(uint2)));
+    RC(c->m_b.ensure(n_m * sizeof(uint4))); RC(c->m_cigoff.ensure(n_m * 8)); RC(c->m_aln.ensure(n_m * 4));
+    RC(c->cig_arena.ensure(n_c * 4));
+  }
+  A.m_aln = c->m_aln.as<uint32_t>(); A.m_tid = c->m_tid.as<uint32_t>(); A.m_aux = c->m_aux.as<uint32_t>(); A.m_p = c->m_p.as<uint2>();
+  A.m_x = c->m_x.as<uint2>(); A.m_b = c->m_b.as<uint4>(); A.m_cigoff = c->m_cigoff.as<uint64_t>(); A.cig_arena = c->cig_arena.as<uint32_t>();
+  return BR_OK;
+}
+
+// the dense-locus kernel (alignments with > 64 candidate rows: a few long-running blocks) on the side stream beside the
+// emit classes of the work list; expand: the work list is written first, beside it too
+static int emit_beside_dense(br_ctx *c, hipStream_t st, const ProjectArgs &A, Prof &pf, int64_t n_list, int64_t n_simple, bool expand) {
+  RC(ensure_side_stream(c));
+  SideWork dense(c, st, c->side_stream);
+  RC(dense.fork());
+  RC(pf.begin(BR_K_EMIT_AUX, c->side_stream));
+  launch_project(c->side_stream, A, true, 64, c->n_cu);
+  RC(pf.end());
+  RC(dense.done());
+  if (expand) {
+    RC(pf.begin(BR_K_EXPAND));
+    launch_expand(st, A);
+    RC(pf.end());
+  }
+  RC(emit_match_table(st, A, pf, n_list, n_simple));
+  return dense.join();
+}
+
+// a16/a17: what pairing reads (the match table of A) and writes (per-alignment record counts and offsets, pair bits); the
+// per-alignment tables are sized here, the counters are the context's block
+static int pair_args(br_ctx *c, const DevCfg &dc, const br_device_batch *b, const ProjectArgs &A, PairArgs &P) {
+  const int64_t n = b->n_aln;
+  RC(c->pmask.ensure((size_t)n * 8)); RC(c->pbit.ensure((size_t)n));
+  P = PairArgs{};
+  P.n_groups = b->n_groups; P.n_aln = n; P.long_reads = dc.long_reads; P.group_off = b->group_off; P.mate_idx = b->mate_idx;
+  P.aln_group = c->aln_group.as<uint32_t>();
+  P.match_off = c->match_off.as<uint32_t>(); P.n_matches = c->n_matches.as<uint32_t>(); P.m_tid = A.m_tid; P.m_p = A.m_p; P.m_x = A.m_x; P.m_b = A.m_b;
+  P.m_cigoff = A.m_cigoff;
+  P.n_rows = c->n_rows.as<uint32_t>(); P.row_off = c->row_off.as<uint64_t>(); P.counters = c->counters_d.as<uint64_t>();
+  P.pmask = c->pmask.as<uint64_t>(); P.pbit = c->pbit.as<uint8_t>();
+  return BR_OK;
+}
+
+// k_pair<false>, and its record counts scanned into row_off and TOT_ROWS (wait_busy: a packed download of the previous call
+// may still be reading row_off / the row tables, br_project_staged)
+static int pair_count(br_ctx *c, hipStream_t st, const PairArgs &P, Prof &pf, bool wait_busy) {
+  RC(pf.begin(BR_K_PAIR_COUNT));
+  launch_pair(st, P, false);
+  RC(pf.end());
+  ScanArgs S2{};
+  S2.n = P.n_aln; S2.src32 = P.n_rows; S2.tile_sums = c->tile_sums.as<uint64_t>();
+  if (wait_busy) HIPCHK(hipStreamWaitEvent(st, c->rows_busy, 0));
+  RC(pf.begin(BR_K_SCAN));
+  launch_scan(st, S2, 2, c->row_off.p, true, c->totals.as<uint64_t>() + TOT_ROWS);
+  RC(pf.end());
+  return BR_OK;
+}
+
+// the row tables for n_rows records (grow: sized here -- a buffer that a queued packed download still reads must not be
+// reallocated under it), and P pointed at them.  The clip score / similarity score columns exist only when the preset
+// filters by similarity (long reads): else all zero
+static int row_tables(br_ctx *c, PairArgs &P, uint64_t n_rows, bool aux_cols, bool grow) {
+  if (grow) {
+    const size_t nr = (size_t)std::max<uint64_t>(n_rows, 1);
+    if (c->rows_busy_set && (c->pk_a.cap < nr * sizeof(uint4) || (aux_cols && (c->pk_sim.cap < nr * 8 || c->pk_clip.cap < nr * 4))))
+      HIPCHK(hipEventSynchronize(c->rows_busy));
+    RC(c->r_rec.ensure(nr * sizeof(uint4)));
+    RC(c->pk_a.ensure(nr * sizeof(uint4))); RC(c->pk_c.ensure(nr * sizeof(uint2)));
+    if (aux_cols) { RC(c->pk_sim.ensure(nr * 8)); RC(c->pk_clip.ensure(nr * 4)); }
+  }
+  P.n_rows_total = (int64_t)n_rows; P.r_rec = c->r_rec.as<uint4>();
+  P.r_a = c->pk_a.as<uint4>(); P.r_c = c->pk_c.as<uint2>(); P.r_x = nullptr;
+  P.r_sim = aux_cols ? c->pk_sim.as<double>() : nullptr; P.r_clip = aux_cols ? c->pk_clip.as<int32_t>() : nullptr;
+  return BR_OK;
+}
+
+// The row tail: k_pair<true> -> k_primary -> k_rows.  Presets without scores: the primary choice (ALU: the mt19937_64
+// seeding chain) needs row_off and the pair bits only, so it runs before the records exist -- on the side stream beside the
+// emit pass of k_pair when `side` -- and leaves its pick for k_rows; with scores it follows the emit pass.  have_rows: false
+// when the host knows that there are none (the kernels that need records are not launched).  host_cap: the caller wants
+// the few rows of a small call on the host (br_project_group) -- the row kernel writes the packed rows and their detail
+// column straight into pinned host memory of that many records: no download, no second wait
+static int row_tail(br_ctx *c, hipStream_t st, const br_device_batch *b, PairArgs &P, Prof &pf, bool aux_cols, bool side,
+                    bool have_rows, uint64_t host_cap) {
+  c->rows_at_host = false;
+  if (host_cap) {
+    RC(c->g_a.resize(host_cap)); RC(c->g_c.resize(host_cap)); RC(c->g_x.resize(host_cap));
+    if (aux_cols) RC(c->g_sim.resize(host_cap));
+    P.r_a = c->g_a.p; P.r_c = c->g_c.p; P.r_x = c->g_x.p;
+    if (aux_cols) P.r_sim = c->g_sim.p;
+    c->rows_at_host = true;
+  }
+  const uint8_t *names = (b->names && b->name_off) ? b->names : nullptr;
+  if (side) RC(ensure_side_stream(c));
+  SideWork choice(c, st, c->side_stream);
+  if (!aux_cols) {
+    RC(c->pick.ensure((size_t)std::max<int64_t>(b->n_groups, 1) * 8)); P.pick = c->pick.as<uint64_t>();
+    if (side) RC(choice.fork());
+    RC(pf.begin(BR_K_PRIMARY, side ? c->side_stream : st));
+    launch_primary(side ? c->side_stream : st, P, b->name_off, names, false);   // + per-group counters
+    RC(pf.end());
+    if (side) RC(choice.done());
+  }
+  if (have_rows) {
+    RC(pf.begin(BR_K_PAIR_EMIT));
+    launch_pair(st, P, true);
+    RC(pf.end());
+  }
+  if (!aux_cols) { if (side) RC(choice.join()); }
+  else {
+    RC(pf.begin(BR_K_PRIMARY));
+    launch_primary(st, P, b->name_off, names, true);   // + per-group counters
+    RC(pf.end());
+  }
+  if (have_rows) {
+    RC(pf.begin(BR_K_ROWS));
+    launch_rows(st, P, aux_cols);
+    RC(pf.end());
+  }
+  return BR_OK;
+}
+
+// the counts of a finished call (rb->counters: unique reads, dropped reads) and what the context keeps of it; P: the row
+// tables of the match-table routes (the direct route passes its own)
 static void finish_call(br_ctx *c, const DevCfg &dc, const br_device_batch *b, br_device_rows *out, uint64_t n_matches,
-                        uint64_t n_rows, uint64_t n_pool, bool aux_cols) {
+                        uint64_t n_rows, uint64_t n_pool, bool aux_cols, const PairArgs *P = nullptr) {
   out->n_matches = (int64_t)n_matches; out->n_rows = (int64_t)n_rows; out->n_pool_words = (int64_t)n_pool;
-  out->total_complete = n_rows; out->total_unique = c->h_totals[5]; out->dropped_reads = c->h_totals[6];
+  out->total_complete = n_rows; out->total_unique = c->rb->counters[1]; out->dropped_reads = c->rb->counters[2];
   out->pool = c->cig_arena.as<uint32_t>(); out->row_off = c->row_off.as<uint64_t>();
   c->counters[6] = n_matches;
   c->last_n_rows = (int64_t)n_rows; c->last_n_aln = b->n_aln; c->last_n_pool = (int64_t)n_pool;
   c->last_aux_cols = aux_cols; c->wide_valid = false; c->detail_valid = false; c->last_l_qseq = b->l_qseq; c->last_long_reads = dc.long_reads;
   c->last_direct = false;   // (run_device_direct says otherwise after this)
+  if (P) {
+    out->a = (const br_row_a *)P->r_a; out->cigar = (const uint64_t *)P->r_c; out->x = (const br_row_x *)P->r_x;   // (null: br_device_rows_detail)
+    out->similarity_score = P->r_sim; out->clip_score = P->r_clip;
+  }
 }
 
 // Small batches (a read-name group, the 64 groups a bramble-cli worker holds, the 100 k alignments of a reference bundle):
@@ -237,7 +382,6 @@ static void finish_call(br_ctx *c, const DevCfg &dc, const br_device_batch *b, b
 // did is redone the ordinary way, which also grows the tables.
 static int run_device_small(br_ctx *c, const DevCfg &dc, const br_device_batch *b, hipStream_t st, br_device_rows *out, Prof &pf,
                             bool keep_events, bool big) {
-  const br_index *ix = c->ix;
   const int64_t n = b->n_aln, ng = b->n_groups;
   const bool aux_cols = dc.filter_by_similarity != 0;
   uint64_t cap_m = 32ull * (uint64_t)n + 8192;
@@ -259,49 +403,32 @@ static int run_device_small(br_ctx *c, const DevCfg &dc, const br_device_batch *
   RC(ensure_count_tables(c, b));
   RC(c->n_matches.ensure((size_t)n * 4)); RC(c->fast_pre.ensure((size_t)(n + 1) * 4)); RC(c->match_off.ensure((size_t)(n + 1) * 4));
   RC(c->tile_sums.ensure((size_t)tiles * 8 * 3)); RC(c->counters_d.ensure(GD_COUNTER_WORDS * 8)); RC(c->n_big.ensure(16));
-  if (!big) {
-    RC(c->m_tid.ensure(cap_m * 4)); RC(c->m_aux.ensure(cap_m * 4)); RC(c->m_p.ensure(cap_m * sizeof(uint2))); RC(c->m_x.ensure(cap_m * sizeof(uint2)));
-    RC(c->m_b.ensure(cap_m * sizeof(uint4))); RC(c->m_cigoff.ensure(cap_m * 8)); RC(c->m_aln.ensure(cap_m * 4));
-    RC(c->cig_arena.ensure(cap_c * 4));
-  }
   // a queued packed download of the last call (br_project_staged) may still read the row tables: small batches wait for it here;
   // large ones keep the overlap -- their tables are not reallocated (checked above) -- and make the row scan wait instead
   const bool rows_busy_wait = c->rows_busy_set && big && c->row_off.cap >= (size_t)(n + 1) * 8;
   if (c->rows_busy_set && !rows_busy_wait) HIPCHK(hipEventSynchronize(c->rows_busy));
   RC(c->n_rows.ensure((size_t)n * 4)); RC(c->row_off.ensure((size_t)(n + 1) * 8)); RC(c->aln_group.ensure((size_t)n * 4));
-  RC(c->pmask.ensure((size_t)n * 8)); RC(c->pbit.ensure((size_t)n));
-  if (!big) {
-    RC(c->r_rec.ensure(cap_m * sizeof(uint4))); RC(c->pk_a.ensure(cap_m * sizeof(uint4))); RC(c->pk_c.ensure(cap_m * sizeof(uint2)));
-    if (aux_cols) { RC(c->pk_sim.ensure(cap_m * 8)); RC(c->pk_clip.ensure(cap_m * 4)); }
-  }
-  if (!aux_cols) RC(c->pick.ensure((size_t)std::max<int64_t>(ng, 1) * 8));
-  if (big) { RC(c->walk_list.ensure((size_t)n * 4)); RC(ensure_aux_stream(c)); }
+  if (big) RC(c->walk_list.ensure((size_t)n * 4));
   uint64_t *d_tot = c->totals.as<uint64_t>();
 
-  // (the per-batch counters sit behind the totals, d_tot[8..11]: one download brings both home; k_segment zeroes them and
-  // the two work-list counters, and labels the alignments with their read-name groups)
-  uint64_t *d_cnt = d_tot + 8;
+  // (the per-batch counters sit behind the totals: one download brings both home; k_segment zeroes them and the two
+  // work-list counters, and labels the alignments with their read-name groups)
+  uint64_t *d_cnt = d_tot + TOT_SMALL_CNT;
   SegExtra X{};
   X.group_off = b->group_off; X.aln_group = c->aln_group.as<uint32_t>(); X.n_groups = ng;
   X.zero_a = (uint64_t *)c->n_big.p; X.n_zero_a = 1; X.zero_b = d_cnt; X.n_zero_b = 4;
-  RC(pf.begin(BR_K_SEGMENT));
-  launch_segment(st, n, b->ref_id, b->ref_start, b->flags, b->xs, b->ts, b->cigar_off, b->cigar, dc, ix->n_refs,
-                 c->seg.as<uint2>(), c->meta.as<AlnMeta>(), c->head.as<uint4>(), c->head2.as<uint4>(), c->fast_flag.as<uint32_t>(), &X);
-  RC(pf.end());
+  RC(segment_stage(c, st, dc, b, pf, &X));
   ProjectArgs A = count_args(c, dc, b);
   A.fast_pre = c->fast_pre.as<uint32_t>(); A.match_off = c->match_off.as<uint32_t>(); A.cig_base = c->cig_base.as<uint64_t>();
   A.n_big = c->n_big.as<uint32_t>();
-  A.m_aln = c->m_aln.as<uint32_t>(); A.m_tid = c->m_tid.as<uint32_t>(); A.m_aux = c->m_aux.as<uint32_t>(); A.m_p = c->m_p.as<uint2>();
-  A.m_x = c->m_x.as<uint2>(); A.m_b = c->m_b.as<uint4>(); A.m_cigoff = c->m_cigoff.as<uint64_t>(); A.cig_arena = c->cig_arena.as<uint32_t>();
+  RC(match_tables(c, A, big ? 0 : cap_m, cap_c));   // (big: checked above)
   A.tot = d_tot; A.lim_m = cap_m; A.lim_c = cap_c;
   const bool split = big && !dc.filter_by_similarity;   // (small: one kernel, the exon walk inline)
   if (split) { A.walk_list = c->walk_list.as<uint32_t>(); A.n_walk = c->n_big.as<uint32_t>() + 1; }
   RC(count_pass(c, st, A, pf, split));
-  ScanArgs S{};
-  S.n = n; S.src32 = c->n_matches.as<uint32_t>(); S.cigar_off = b->cigar_off; S.head = c->head.as<uint4>();
-  S.tile_sums = c->tile_sums.as<uint64_t>(); S.fast_flag = c->fast_flag.as<uint32_t>();
+  ScanArgs S = scan3_args(c, b);
   RC(pf.begin(BR_K_SCAN));
-  const bool expanded = launch_scan3(st, S, c->match_off.as<uint32_t>(), c->cig_base.as<uint64_t>(), c->fast_pre.as<uint32_t>(), d_tot + 0, &A);
+  const bool expanded = launch_scan3(st, S, c->match_off.as<uint32_t>(), c->cig_base.as<uint64_t>(), c->fast_pre.as<uint32_t>(), d_tot + TOT_MATCHES, &A);
   RC(pf.end());
   if (!expanded) {
     RC(pf.begin(BR_K_EXPAND));
@@ -310,100 +437,42 @@ static int run_device_small(br_ctx *c, const DevCfg &dc, const br_device_batch *
   }
   if (!big) {
     RC(pf.begin(BR_K_EMIT));
-    launch_emit_dense(st, A, (int64_t)cover_m, -1, 0);          // one launch over the whole list; the kernel stops at tot[0]
+    launch_emit_dense(st, A, (int64_t)cover_m, -1, 0);          // one launch over the whole list; the kernel stops at TOT_MATCHES
     launch_project(st, A, true, 64, std::min(c->n_cu, 64));     // alignments with > 64 candidate rows (reads *n_big)
     RC(pf.end());
   } else {
-    // as the ordinary path: the dense-locus kernel on the second stream beside the two classes of the work list
-    HIPCHK(hipEventRecord(c->aux_ev[0], st));
-    HIPCHK(hipStreamWaitEvent(c->ksw_stream, c->aux_ev[0], 0));
-    RC(pf.begin(BR_K_EMIT_AUX, c->ksw_stream));
-    launch_project(c->ksw_stream, A, true, 64, c->n_cu);
-    RC(pf.end());
-    HIPCHK(hipEventRecord(c->aux_ev[1], c->ksw_stream));
-    // (the grids: cover_s + cover_g entries of the two classes, or cover_m of the whole list)
-    RC(emit_match_table(st, A, pf, (int64_t)(dc.filter_by_similarity ? cover_m : cover_s + cover_g), (int64_t)cover_s));
-    HIPCHK(hipStreamWaitEvent(st, c->aux_ev[1], 0));
+    // as the ordinary path, over the grids of the predictions: cover_s + cover_g entries of the two classes, or cover_m of the whole list
+    RC(emit_beside_dense(c, st, A, pf, (int64_t)(dc.filter_by_similarity ? cover_m : cover_s + cover_g), (int64_t)cover_s, false));
   }
 
-  PairArgs P{};
-  P.n_groups = ng; P.n_aln = n; P.long_reads = dc.long_reads; P.group_off = b->group_off; P.mate_idx = b->mate_idx;
-  P.aln_group = c->aln_group.as<uint32_t>();
-  P.match_off = c->match_off.as<uint32_t>(); P.n_matches = c->n_matches.as<uint32_t>(); P.m_tid = A.m_tid; P.m_p = A.m_p; P.m_x = A.m_x; P.m_b = A.m_b;
-  P.m_cigoff = A.m_cigoff;
-  P.n_rows = c->n_rows.as<uint32_t>(); P.row_off = c->row_off.as<uint64_t>(); P.counters = d_cnt;
-  P.pmask = c->pmask.as<uint64_t>(); P.pbit = c->pbit.as<uint8_t>();
-  P.tot = d_tot; P.lim_m = cap_m; P.lim_c = cap_c; P.lim_r = std::min(cap_r, cover_r);
-  RC(pf.begin(BR_K_PAIR_COUNT));
-  launch_pair(st, P, false);
-  RC(pf.end());
-  ScanArgs S2{};
-  S2.n = n; S2.src32 = c->n_rows.as<uint32_t>(); S2.tile_sums = c->tile_sums.as<uint64_t>();
-  if (rows_busy_wait) HIPCHK(hipStreamWaitEvent(st, c->rows_busy, 0));
-  RC(pf.begin(BR_K_SCAN));
-  launch_scan(st, S2, 2, c->row_off.p, true, d_tot + 3);
-  RC(pf.end());
-  P.n_rows_total = (int64_t)P.lim_r; P.r_rec = c->r_rec.as<uint4>();
-  P.r_a = c->pk_a.as<uint4>(); P.r_c = c->pk_c.as<uint2>(); P.r_x = nullptr;
-  P.r_sim = aux_cols ? c->pk_sim.as<double>() : nullptr; P.r_clip = aux_cols ? c->pk_clip.as<int32_t>() : nullptr;
-  // a caller that wants the few rows of a small call on the host (br_project_group): the row kernel writes the packed rows
-  // and their detail column straight into pinned host memory -- no download, no second wait
-  c->rows_at_host = false;
-  if (c->rows_to_host) {
-    RC(c->g_a.resize(cap_m)); RC(c->g_c.resize(cap_m)); RC(c->g_x.resize(cap_m));
-    if (aux_cols) RC(c->g_sim.resize(cap_m));
-    P.r_a = c->g_a.p; P.r_c = c->g_c.p; P.r_x = c->g_x.p;
-    if (aux_cols) P.r_sim = c->g_sim.p;
-    c->rows_at_host = true;
-  }
-  const uint8_t *names = (b->names && b->name_off) ? b->names : nullptr;
-  if (!aux_cols) {   // the primary choice needs row_off and the pair bits only: before the records exist, its pick applied by k_rows
-    P.pick = c->pick.as<uint64_t>();
-    hipStream_t ps = st;
-    if (big) {   // ... and beside the emit pass, on the second stream
-      ps = c->ksw_stream;
-      HIPCHK(hipEventRecord(c->aux_ev[0], st));
-      HIPCHK(hipStreamWaitEvent(ps, c->aux_ev[0], 0));
-    }
-    RC(pf.begin(BR_K_PRIMARY, ps));
-    launch_primary(ps, P, b->name_off, names, false);
-    RC(pf.end());
-    if (big) HIPCHK(hipEventRecord(c->aux_ev[1], ps));
-  }
-  RC(pf.begin(BR_K_PAIR_EMIT));
-  launch_pair(st, P, true);
-  RC(pf.end());
-  if (big && !aux_cols) HIPCHK(hipStreamWaitEvent(st, c->aux_ev[1], 0));
-  if (aux_cols) {
-    RC(pf.begin(BR_K_PRIMARY));
-    launch_primary(st, P, b->name_off, names, true);
-    RC(pf.end());
-  }
-  RC(pf.begin(BR_K_ROWS));
-  launch_rows(st, P, aux_cols);
-  RC(pf.end());
-  HIPCHK(hipMemcpyAsync(c->h_totals + 32, d_tot, 12 * 8, hipMemcpyDeviceToHost, st));
+  PairArgs P;
+  RC(pair_args(c, dc, b, A, P));
+  P.counters = d_cnt; P.tot = d_tot; P.lim_m = cap_m; P.lim_c = cap_c; P.lim_r = std::min(cap_r, cover_r);
+  RC(pair_count(c, st, P, pf, rows_busy_wait));
+  // (small: the row tables of the upper bound, lim_r = cap_m; big: the ones earlier calls left, checked above; the record
+  // count stays on the device: every launch of the tail is made)
+  RC(row_tables(c, P, P.lim_r, aux_cols, !big));
+  RC(row_tail(c, st, b, P, pf, aux_cols, big, true, c->rows_to_host ? cap_m : 0));
+  ReadBack *rb = c->rb;
+  HIPCHK(hipMemcpyAsync(rb->small, d_tot, sizeof(rb->small), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  for (int k = 0; k < 4; k++) { c->h_totals[k] = c->h_totals[32 + k]; c->h_totals[4 + k] = c->h_totals[40 + k]; }
-  const uint64_t n_matches = c->h_totals[0], n_cig_arena = c->h_totals[1], n_simple = c->h_totals[2], n_rows = c->h_totals[3];
+  for (int k = 0; k < 4; k++) { rb->scan[k] = rb->small[k]; rb->counters[k] = rb->small[TOT_SMALL_CNT + k]; }
+  const uint64_t n_matches = rb->scan[TOT_MATCHES], n_cig_arena = rb->scan[TOT_ARENA], n_simple = rb->scan[TOT_SIMPLE], n_rows = rb->scan[TOT_ROWS];
   // nothing was written past a table or left out by a grid: the kernels checked the same totals and did nothing then
   if (n_matches > cap_m || n_cig_arena > cap_c || n_rows > P.lim_r) return BR_RETRY_ORDINARY;
   if (big && (!dc.filter_by_similarity ? (n_simple > cover_s || n_matches - n_simple > cover_g) : n_matches > cover_m)) return BR_RETRY_ORDINARY;
   c->hist_simf = dc.filter_by_similarity != 0;
   c->hist_n = n; c->hist[0] = n_matches; c->hist[1] = n_cig_arena; c->hist[2] = n_simple; c->hist[3] = n_rows;
   if (!keep_events) RC(pf.collect());
-  if (c->h_totals[7]) return BR_ERR_UNSUPPORTED;  // a rewritten CIGAR with more than 2^24 - 1 ops
-  finish_call(c, dc, b, out, n_matches, n_rows, n_cig_arena, aux_cols);
-  out->a = (const br_row_a *)P.r_a; out->cigar = (const uint64_t *)P.r_c; out->x = (const br_row_x *)P.r_x;
-  out->similarity_score = aux_cols ? P.r_sim : nullptr;
-  out->clip_score = aux_cols ? c->pk_clip.as<int32_t>() : nullptr;
+  if (rb->counters[3]) return BR_ERR_UNSUPPORTED;  // a rewritten CIGAR with more than 2^24 - 1 ops
+  finish_call(c, dc, b, out, n_matches, n_rows, n_cig_arena, aux_cols, &P);
   return BR_OK;
 }
 
 // Direct rows: presets without the similarity filter and without -S (every short-read preset; long reads with the filter
 // switched off).  segment -> count -> [k_pair_mask || k_big<0> + k_pair_big] -> k_scan5 (one host wait: sizes) ->
 // k_expand_rows -> k_emit_rows (|| k_big<1>): the packed rows are written once, by the lane that computes the match; the
-// match table, the per-record r_rec, k_pair<true> and k_rows do not exist on this path.  On the second stream: the name
+// match table, the per-record r_rec, k_pair<true> and k_rows do not exist on this path.  On the side streams: the name
 // seeds of the primary tie-break (beside segment + count), the big alignments' pairing (beside k_pair_mask), k_group_desc
 // (beside the scan), k_big<1> (beside the emit kernels).
 static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch *b, hipStream_t st, br_device_rows *out, Prof &pf,
@@ -429,9 +498,11 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
   // (a buffer that a queued packed download still reads must not be reallocated under it)
   if (c->rows_busy_set && c->row_off.cap < (size_t)(n + 1) * 8) HIPCHK(hipEventSynchronize(c->rows_busy));
   RC(c->row_off.ensure((size_t)(n + 1) * 8));
-  RC(ensure_aux_stream(c));
-  hipStream_t ax = c->ksw_stream;
+  RC(ensure_side_stream(c));
+  if (!c->side2_stream) HIPCHK(hipStreamCreateWithPriority(&c->side2_stream, hipStreamNonBlocking, 0));
+  hipStream_t ax = c->side_stream, ax2 = c->side2_stream;
   uint64_t *d_tot = c->totals.as<uint64_t>();
+  ReadBack *rb = c->rb;
 
   ProjectArgs A = count_args(c, dc, b);
   A.n_big = dz_nbig; A.walk_list = c->walk_list.as<uint32_t>(); A.n_walk = dz_nbig + 1;
@@ -446,16 +517,12 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
   D.name_off = have_names ? b->name_off : nullptr; D.names = have_names ? b->names : nullptr; D.rnd0 = c->d_rnd.as<uint64_t>();
   D.gd = c->d_desc.as<uint2>(); D.dpos = c->d_desc.as<uint2>() + n; D.hi0 = c->d_hi0.as<uint32_t>(); D.counters = c->counters_d.as<uint64_t>(); D.tot = d_tot;
 
-  if (!c->aux2_stream) { HIPCHK(hipStreamCreateWithPriority(&c->aux2_stream, hipStreamNonBlocking, 0)); HIPCHK(hipEventCreateWithFlags(&c->aux2_ev, hipEventDisableTiming)); }
-  hipStream_t ax2 = c->aux2_stream;
+  // the pieces beside the main chain: the name seeds (second side stream), the big alignments' pairing, k_group_desc, k_big<1>
+  SideWork seeds(c, st, ax2), pair_big(c, st, ax), group_desc(c, st, ax), big_emit(c, st, ax);
   HIPCHK(hipMemsetAsync(dz, 0, (GD_COUNTER_WORDS + 4) * 8, st));
-  HIPCHK(hipEventRecord(c->aux_ev[0], st));
-  HIPCHK(hipStreamWaitEvent(ax, c->aux_ev[0], 0));
-  // a1/a2/a6: CIGAR -> read exons; a3-a8, a11-a14 (survival only): the count pass
-  RC(pf.begin(BR_K_SEGMENT));
-  launch_segment(st, n, b->ref_id, b->ref_start, b->flags, b->xs, b->ts, b->cigar_off, b->cigar, dc, ix->n_refs,
-                 c->seg.as<uint2>(), c->meta.as<AlnMeta>(), c->head.as<uint4>(), c->head2.as<uint4>(), c->fast_flag.as<uint32_t>());
-  RC(pf.end());
+  RC(pair_big.fork());   // (the side stream behind the fill; every attempt below forks again)
+  // a3-a8, a11-a14 (survival only): the count pass
+  RC(segment_stage(c, st, dc, b, pf));
   RC(pf.begin(BR_K_GROUP_IDS));
   launch_group_ids(st, ng, b->group_off, c->aln_group.as<uint32_t>());
   RC(pf.end());
@@ -466,40 +533,37 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
   const int big_blocks = c->n_cu * 4;
   uint64_t kept = 0, arena = 0, n_simple = 0, n_rows = 0, n_raw = 0;
   bool expanded_ahead = false;
-  // third stream: the name seeds need nothing but the names, and their 156 dependent multiplies per read name are pure ALU work:
+  // second side stream: the name seeds need nothing but the names, and their 156 dependent multiplies per read name are pure ALU work:
   // beside k_pair_mask, which waits on LDS and memory most of the time
   if (have_names) {
-    HIPCHK(hipEventRecord(c->aux_ev[7], st));
-    HIPCHK(hipStreamWaitEvent(ax2, c->aux_ev[7], 0));
+    RC(seeds.fork());
     RC(pf.begin(BR_K_NAME_SEED, ax2));
     launch_name_seed(ax2, D);
     RC(pf.end());
-    HIPCHK(hipEventRecord(c->aux2_ev, ax2));
+    RC(seeds.done());
   }
   for (int attempt = 0;; attempt++) {
     if (attempt) {   // (the first attempt's counters were zeroed with everything else at the start)
       HIPCHK(hipMemsetAsync(dz, 0, (GD_COUNTER_WORDS + 2) * 8, st));
       HIPCHK(hipMemsetAsync(D.pm_n, 0, 4, st));
     }
-    HIPCHK(hipEventRecord(c->aux_ev[1], st));
-    HIPCHK(hipStreamWaitEvent(ax, c->aux_ev[1], 0));
+    RC(pair_big.fork());
     RC(pf.begin(BR_K_PAIR_BIG, ax));
     launch_big_collect(ax, A, D, big_blocks);
     launch_pair_big(ax, D, big_blocks);
     RC(pf.end());
-    HIPCHK(hipEventRecord(c->aux_ev[2], ax));
+    RC(pair_big.done());
     RC(pf.begin(BR_K_PAIR_MASK));
     launch_pair_mask(st, D, c->n_cu * 2);
     RC(pf.end());
-    HIPCHK(hipStreamWaitEvent(st, c->aux_ev[2], 0));
-    // NH / HI / primary per read name on the second stream beside the scan
-    HIPCHK(hipEventRecord(c->aux_ev[3], st));
-    HIPCHK(hipStreamWaitEvent(ax, c->aux_ev[3], 0));
-    if (have_names) HIPCHK(hipStreamWaitEvent(ax, c->aux2_ev, 0));
+    RC(pair_big.join());
+    // NH / HI / primary per read name on the side stream beside the scan
+    RC(group_desc.fork());
+    if (have_names) RC(seeds.join_on(ax));
     RC(pf.begin(BR_K_GROUP_DESC, ax));
     launch_group_desc(ax, D);
     RC(pf.end());
-    HIPCHK(hipEventRecord(c->aux_ev[4], ax));
+    RC(group_desc.done());
     RC(pf.begin(BR_K_SCAN));
     launch_scan5(st, D, c->tile_sums.as<uint64_t>(), d_tot);
     RC(pf.end());
@@ -513,20 +577,20 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
       RC(pf.end());
       expanded_ahead = true;
     }
-    HIPCHK(hipMemcpyAsync(c->h_totals, d_tot, 5 * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(c->h_totals + 8, dz + GD_COUNTER_WORDS, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rb->scan, d_tot, sizeof(rb->scan), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rb->side, dz + GD_COUNTER_WORDS, sizeof(rb->side), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     c->d_side_attempts = attempt + 1;
-    if (c->h_totals[9]) {   // the side arena of the > 64-candidate alignments ran out: grow it to the exact total k_big<0> counted
+    if (rb->side[1]) {   // the side arena of the > 64-candidate alignments ran out: grow it to the exact total k_big<0> counted
       // (every entry adds its need, also after the overflow) plus a margin for the calls to come, repeat: the repeat fits
       if (attempt >= 3) return BR_ERR_CAPACITY;   // (a guard: the second attempt always fits)
-      HIPCHK(hipEventSynchronize(c->aux_ev[4]));
-      c->d_side_cap = c->h_totals[8] + c->h_totals[8] / 4 + 4096;
+      RC(group_desc.wait_host());
+      c->d_side_cap = rb->side[0] + rb->side[0] / 4 + 4096;
       RC(c->d_side.ensure((size_t)c->d_side_cap * sizeof(uint2)));
       D.side = c->d_side.as<uint2>(); D.side_cap = c->d_side_cap;
       continue;
     }
-    kept = c->h_totals[0]; arena = c->h_totals[1]; n_simple = c->h_totals[2]; n_rows = c->h_totals[3]; n_raw = c->h_totals[4];
+    kept = rb->scan[TOT_MATCHES]; arena = rb->scan[TOT_ARENA]; n_simple = rb->scan[TOT_SIMPLE]; n_rows = rb->scan[TOT_ROWS]; n_raw = rb->scan[TOT_RAW];
     break;
   }
   if (n_raw >= 0xffffffffull || kept >= 0xffffffffull) return BR_ERR_CAPACITY;
@@ -551,29 +615,28 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
       launch_expand_rows(st, D);
       RC(pf.end());
     }
-    HIPCHK(hipStreamWaitEvent(st, c->aux_ev[4], 0));   // k_group_desc: the descriptors' first halves
-    HIPCHK(hipEventRecord(c->aux_ev[5], st));
-    HIPCHK(hipStreamWaitEvent(ax, c->aux_ev[5], 0));
+    RC(group_desc.join());   // the descriptors' first halves
+    RC(big_emit.fork());
     RC(pf.begin(BR_K_BIG_EMIT, ax));
     launch_big_emit(ax, A, D, big_blocks);
     RC(pf.end());
-    HIPCHK(hipEventRecord(c->aux_ev[6], ax));
+    RC(big_emit.done());
     RC(pf.begin(BR_K_EMIT_ROWS_SIMPLE));
     launch_emit_rows(st, A, D, (int64_t)kept, (int64_t)n_simple, 1);
     RC(pf.end());
     RC(pf.begin(BR_K_EMIT_ROWS));
     launch_emit_rows(st, A, D, (int64_t)kept, (int64_t)n_simple, 2);
     RC(pf.end());
-    HIPCHK(hipStreamWaitEvent(st, c->aux_ev[6], 0));
+    RC(big_emit.join());
   } else {
-    HIPCHK(hipStreamWaitEvent(st, c->aux_ev[4], 0));
+    RC(group_desc.join());
   }
-  HIPCHK(hipMemcpyAsync(c->h_totals + 192, c->counters_d.p, GD_COUNTER_WORDS * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(rb->direct_cnt, c->counters_d.p, sizeof(rb->direct_cnt), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (!keep_events) RC(pf.collect());
-  for (int k = 0; k < 4; k++) c->h_totals[4 + k] = c->h_totals[192 + k];
-  for (int k = 0; k < GD_SLOTS; k++) { c->h_totals[5] += c->h_totals[192 + GD_SLOT0 + k * GD_SLOT_STRIDE]; c->h_totals[6] += c->h_totals[192 + GD_SLOT0 + k * GD_SLOT_STRIDE + 1]; }
-  if (c->h_totals[7]) return BR_ERR_UNSUPPORTED;  // a rewritten CIGAR with more than 2^24 - 1 ops, or NH beyond 28 bits
+  for (int k = 0; k < 4; k++) rb->counters[k] = rb->direct_cnt[k];
+  for (int k = 0; k < GD_SLOTS; k++) { rb->counters[1] += rb->direct_cnt[GD_SLOT0 + k * GD_SLOT_STRIDE]; rb->counters[2] += rb->direct_cnt[GD_SLOT0 + k * GD_SLOT_STRIDE + 1]; }
+  if (rb->counters[3]) return BR_ERR_UNSUPPORTED;  // a rewritten CIGAR with more than 2^24 - 1 ops, or NH beyond 28 bits
   c->hist_n = 0;   // (nothing a later speculative launch of the match-table path could be sized from)
   finish_call(c, dc, b, out, n_raw, n_rows, arena, false);
   out->a = (const br_row_a *)c->pk_a.p; out->cigar = (const uint64_t *)c->pk_c.p; out->x = with_x ? (const br_row_x *)c->pk_x.p : nullptr;
@@ -588,7 +651,6 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
 // DP between the count and the scan.
 static int run_match_table(br_ctx *c, const DevCfg &dc, const br_device_batch *b, hipStream_t st, br_device_rows *out, Prof &pf,
                            bool keep_events) {
-  const br_index *ix = c->ix;
   const bool fa_mode = dc.use_fasta && dc.long_reads;
   const int64_t n = b->n_aln, ng = b->n_groups;
   const int64_t tiles = std::max<int64_t>(scan_tiles_for(std::max<int64_t>(n, ng) + 1), 1);
@@ -597,26 +659,20 @@ static int run_match_table(br_ctx *c, const DevCfg &dc, const br_device_batch *b
   RC(c->tile_sums.ensure((size_t)tiles * 8 * 3)); RC(c->counters_d.ensure(4 * 8));
   RC(c->n_big.ensure(16)); RC(c->walk_list.ensure((size_t)n * 4));
   uint64_t *d_tot = c->totals.as<uint64_t>();
+  ReadBack *rb = c->rb;
 
-  // a1/a2/a6: CIGAR -> read exons
-  RC(pf.begin(BR_K_SEGMENT));
-  launch_segment(st, n, b->ref_id, b->ref_start, b->flags, b->xs, b->ts, b->cigar_off, b->cigar, dc, ix->n_refs,
-                 c->seg.as<uint2>(), c->meta.as<AlnMeta>(), c->head.as<uint4>(), c->head2.as<uint4>(),
-                 c->fast_flag.as<uint32_t>());
-  RC(pf.end());
+  RC(segment_stage(c, st, dc, b, pf));
   ProjectArgs A = count_args(c, dc, b);
   A.fast_pre = c->fast_pre.as<uint32_t>(); A.match_off = c->match_off.as<uint32_t>(); A.cig_base = c->cig_base.as<uint64_t>();
   HIPCHK(hipMemsetAsync(c->n_big.p, 0, 8, st));
   A.n_big = c->n_big.as<uint32_t>(); A.walk_list = c->walk_list.as<uint32_t>(); A.n_walk = c->n_big.as<uint32_t>() + 1;
   const int n_blocks = c->n_cu * c->blocks_per_cu;
-  ScanArgs S{};
-  S.n = n; S.src32 = c->n_matches.as<uint32_t>(); S.cigar_off = b->cigar_off; S.head = c->head.as<uint4>();
-  S.tile_sums = c->tile_sums.as<uint64_t>(); S.fast_flag = c->fast_flag.as<uint32_t>();
+  ScanArgs S = scan3_args(c, b);
   FaArgs F{};
   if (!fa_mode) {
     RC(count_pass(c, st, A, pf, !dc.filter_by_similarity));
     RC(pf.begin(BR_K_SCAN));
-    launch_scan3(st, S, c->match_off.as<uint32_t>(), c->cig_base.as<uint64_t>(), c->fast_pre.as<uint32_t>(), d_tot + 0);
+    launch_scan3(st, S, c->match_off.as<uint32_t>(), c->cig_base.as<uint64_t>(), c->fast_pre.as<uint32_t>(), d_tot + TOT_MATCHES);
     RC(pf.end());
   } else {
     // rescue planning -> ksw2 DP -> count with the rescue results
@@ -633,12 +689,12 @@ static int run_match_table(br_ctx *c, const DevCfg &dc, const br_device_batch *b
     ScanArgs SP{}; SP.n = n; SP.src32 = F.n_prob; SP.tile_sums = c->tile_sums.as<uint64_t>();
     ScanArgs SB{}; SB.n = n; SB.src32 = F.seq_bytes; SB.tile_sums = c->tile_sums.as<uint64_t>();
     RC(pf.begin(BR_K_SCAN));
-    launch_scan(st, SP, 2, c->fa_prob_off.p, false, d_tot + 4);
-    launch_scan(st, SB, 2, c->fa_seqarena_off.p, true, d_tot + 5);
+    launch_scan(st, SP, 2, c->fa_prob_off.p, false, d_tot + TOT_RESCUE_PROB);
+    launch_scan(st, SB, 2, c->fa_seqarena_off.p, true, d_tot + TOT_RESCUE_SEQ);
     RC(pf.end());
-    HIPCHK(hipMemcpyAsync(c->h_totals + 4, d_tot + 4, 2 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rb->rescue_n, d_tot + TOT_RESCUE_PROB, sizeof(rb->rescue_n), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    uint64_t n_prob = c->h_totals[4], seq_total = c->h_totals[5];
+    uint64_t n_prob = rb->rescue_n[0], seq_total = rb->rescue_n[1];
     RC(c->fa_stats.ensure(16));
     HIPCHK(hipMemsetAsync(c->fa_stats.p, 0, 16, st));
     c->rescue_stats[0] = n_prob; c->rescue_stats[1] = 0; c->rescue_stats[2] = 0; c->rescue_stats[3] = seq_total;
@@ -662,29 +718,23 @@ static int run_match_table(br_ctx *c, const DevCfg &dc, const br_device_batch *b
       RC(pf.begin(BR_K_KSW));
       RC(run_ksw(c, st, R));
       RC(pf.end());
-      HIPCHK(hipMemcpyAsync(c->h_totals + 8, c->fa_stats.p, 16, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(rb->rescue_stats, c->fa_stats.p, sizeof(rb->rescue_stats), hipMemcpyDeviceToHost, st));
     }
     RC(pf.begin(BR_K_COUNT));
     launch_project_fa(st, A, F, 2, n_blocks);
     RC(pf.end());
     S.ideal_cap = F.ideal_cap;
     RC(pf.begin(BR_K_SCAN));
-    launch_scan3(st, S, c->match_off.as<uint32_t>(), c->cig_base.as<uint64_t>(), c->fast_pre.as<uint32_t>(), d_tot + 0);
+    launch_scan3(st, S, c->match_off.as<uint32_t>(), c->cig_base.as<uint64_t>(), c->fast_pre.as<uint32_t>(), d_tot + TOT_MATCHES);
     RC(pf.end());
   }
-  HIPCHK(hipMemcpyAsync(c->h_totals, d_tot, 3 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(rb->scan, d_tot, 3 * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  const uint64_t n_matches = c->h_totals[0], n_cig_arena = c->h_totals[1];
-  const int64_t n_simple = fa_mode ? -1 : (int64_t)c->h_totals[2];  // matches of the single-M class (first in the emit list)
+  const uint64_t n_matches = rb->scan[TOT_MATCHES], n_cig_arena = rb->scan[TOT_ARENA];
+  const int64_t n_simple = fa_mode ? -1 : (int64_t)rb->scan[TOT_SIMPLE];  // matches of the single-M class (first in the emit list)
   if (n_matches >= 0xffffffffull) return BR_ERR_CAPACITY;
 
-  size_t nm = (size_t)std::max<uint64_t>(n_matches, 1);
-  RC(c->m_tid.ensure(nm * 4)); RC(c->m_aux.ensure(nm * 4)); RC(c->m_p.ensure(nm * sizeof(uint2))); RC(c->m_x.ensure(nm * sizeof(uint2)));
-  RC(c->m_b.ensure(nm * sizeof(uint4))); RC(c->m_cigoff.ensure(nm * 8)); RC(c->m_aln.ensure(nm * 4));
-  A.m_aln = c->m_aln.as<uint32_t>();
-  RC(c->cig_arena.ensure((size_t)std::max<uint64_t>(n_cig_arena, 1) * 4));
-  A.m_tid = c->m_tid.as<uint32_t>(); A.m_aux = c->m_aux.as<uint32_t>(); A.m_p = c->m_p.as<uint2>(); A.m_x = c->m_x.as<uint2>();
-  A.m_b = c->m_b.as<uint4>(); A.m_cigoff = c->m_cigoff.as<uint64_t>(); A.cig_arena = c->cig_arena.as<uint32_t>();
+  RC(match_tables(c, A, std::max<uint64_t>(n_matches, 1), std::max<uint64_t>(n_cig_arena, 1)));
   if (n_matches) {
     if (fa_mode) {
       // the work list + one lane per match for alignments with at most 64 candidate rows, k_project_fa<3> for the others
@@ -696,19 +746,7 @@ static int run_match_table(br_ctx *c, const DevCfg &dc, const br_device_batch *b
       launch_emit_dense_fa(st, A, F, (int64_t)n_matches);
       RC(pf.end());
     } else {
-      // alignments with > 64 candidate rows only: a few long-running blocks, on the second stream beside the work list
-      RC(ensure_aux_stream(c));
-      HIPCHK(hipEventRecord(c->aux_ev[0], st));
-      HIPCHK(hipStreamWaitEvent(c->ksw_stream, c->aux_ev[0], 0));
-      RC(pf.begin(BR_K_EMIT_AUX, c->ksw_stream));
-      launch_project(c->ksw_stream, A, true, 64, c->n_cu);
-      RC(pf.end());
-      HIPCHK(hipEventRecord(c->aux_ev[1], c->ksw_stream));
-      RC(pf.begin(BR_K_EXPAND));
-      launch_expand(st, A);
-      RC(pf.end());
-      RC(emit_match_table(st, A, pf, (int64_t)n_matches, n_simple));
-      HIPCHK(hipStreamWaitEvent(st, c->aux_ev[1], 0));
+      RC(emit_beside_dense(c, st, A, pf, (int64_t)n_matches, n_simple, true));
     }
   }
 
@@ -720,83 +758,27 @@ static int run_match_table(br_ctx *c, const DevCfg &dc, const br_device_batch *b
   launch_group_ids(st, ng, b->group_off, c->aln_group.as<uint32_t>());
   RC(pf.end());
   HIPCHK(hipMemsetAsync(c->counters_d.p, 0, 4 * 8, st));
-  PairArgs P{};
-  P.n_groups = ng; P.n_aln = n; P.long_reads = dc.long_reads; P.group_off = b->group_off; P.mate_idx = b->mate_idx;
-  P.aln_group = c->aln_group.as<uint32_t>();
-  P.match_off = c->match_off.as<uint32_t>(); P.n_matches = c->n_matches.as<uint32_t>(); P.m_tid = A.m_tid; P.m_p = A.m_p; P.m_x = A.m_x; P.m_b = A.m_b;
-  P.m_cigoff = A.m_cigoff;
-  P.n_rows = c->n_rows.as<uint32_t>();
-  P.row_off = c->row_off.as<uint64_t>(); P.counters = c->counters_d.as<uint64_t>();
-  RC(c->pmask.ensure((size_t)n * 8)); P.pmask = c->pmask.as<uint64_t>();
-  RC(c->pbit.ensure((size_t)n)); P.pbit = c->pbit.as<uint8_t>();
-  RC(pf.begin(BR_K_PAIR_COUNT));
-  launch_pair(st, P, false);
-  RC(pf.end());
-  ScanArgs S2{};
-  S2.n = n; S2.src32 = c->n_rows.as<uint32_t>(); S2.tile_sums = c->tile_sums.as<uint64_t>();
-  // a packed download of the previous call may still be reading row_off / the row tables (br_project_staged)
-  if (c->rows_busy_set) { HIPCHK(hipStreamWaitEvent(st, c->rows_busy, 0)); }
-  RC(pf.begin(BR_K_SCAN));
-  launch_scan(st, S2, 2, c->row_off.p, true, d_tot + 2);
-  RC(pf.end());
-  HIPCHK(hipMemcpyAsync(c->h_totals + 2, d_tot + 2, 8, hipMemcpyDeviceToHost, st));
+  PairArgs P;
+  RC(pair_args(c, dc, b, A, P));
+  RC(pair_count(c, st, P, pf, c->rows_busy_set));
+  HIPCHK(hipMemcpyAsync(&rb->scan[TOT_ROWS], d_tot + TOT_ROWS, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  const uint64_t n_rows = c->h_totals[2];
+  const uint64_t n_rows = rb->scan[TOT_ROWS];
 
-  const size_t nr = (size_t)std::max<uint64_t>(n_rows, 1);
-  // clip score / similarity score columns exist only when the preset filters by similarity (long reads): else all zero
   const bool aux_cols = dc.filter_by_similarity != 0;
-  if (c->rows_busy_set && (c->pk_a.cap < nr * sizeof(uint4) || (aux_cols && (c->pk_sim.cap < nr * 8 || c->pk_clip.cap < nr * 4))))
-    HIPCHK(hipEventSynchronize(c->rows_busy));
-  RC(c->r_rec.ensure(nr * sizeof(uint4)));
-  RC(c->pk_a.ensure(nr * sizeof(uint4))); RC(c->pk_c.ensure(nr * sizeof(uint2)));
-  if (aux_cols) { RC(c->pk_sim.ensure(nr * 8)); RC(c->pk_clip.ensure(nr * 4)); }
-  P.n_rows_total = (int64_t)n_rows; P.r_rec = c->r_rec.as<uint4>();
-  P.r_a = c->pk_a.as<uint4>(); P.r_c = c->pk_c.as<uint2>(); P.r_x = nullptr;
-  P.r_sim = aux_cols ? c->pk_sim.as<double>() : nullptr; P.r_clip = aux_cols ? c->pk_clip.as<int32_t>() : nullptr;
-  // presets without scores: the primary choice (ALU: the mt19937_64 seeding chain) needs row_off and the pair bits only,
-  // so it runs on the second stream beside the emit pass of k_pair and leaves its choice for k_rows
-  const bool split_primary = !aux_cols;
-  if (split_primary) {
-    RC(ensure_aux_stream(c));
-    RC(c->pick.ensure((size_t)std::max<int64_t>(ng, 1) * 8)); P.pick = c->pick.as<uint64_t>();
-    HIPCHK(hipEventRecord(c->aux_ev[0], st));
-    HIPCHK(hipStreamWaitEvent(c->ksw_stream, c->aux_ev[0], 0));
-    RC(pf.begin(BR_K_PRIMARY, c->ksw_stream));
-    launch_primary(c->ksw_stream, P, b->name_off, (b->names && b->name_off) ? b->names : nullptr, false);  // + per-group counters
-    RC(pf.end());
-    HIPCHK(hipEventRecord(c->aux_ev[1], c->ksw_stream));
-  }
-  if (n_rows) {
-    RC(pf.begin(BR_K_PAIR_EMIT));
-    launch_pair(st, P, true);
-    RC(pf.end());
-  }
-  if (split_primary) HIPCHK(hipStreamWaitEvent(st, c->aux_ev[1], 0));
-  else {
-    RC(pf.begin(BR_K_PRIMARY));
-    launch_primary(st, P, b->name_off, (b->names && b->name_off) ? b->names : nullptr, aux_cols);  // + per-group counters
-    RC(pf.end());
-  }
-  if (n_rows) {
-    RC(pf.begin(BR_K_ROWS));
-    launch_rows(st, P, aux_cols);
-    RC(pf.end());
-  }
-  HIPCHK(hipMemcpyAsync(c->h_totals + 4, c->counters_d.p, 4 * 8, hipMemcpyDeviceToHost, st));
+  RC(row_tables(c, P, n_rows, aux_cols, true));
+  RC(row_tail(c, st, b, P, pf, aux_cols, true, n_rows != 0, 0));
+  HIPCHK(hipMemcpyAsync(rb->counters, c->counters_d.p, sizeof(rb->counters), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (!keep_events) RC(pf.collect());
-  if (c->h_totals[7]) return BR_ERR_UNSUPPORTED;  // a rewritten CIGAR with more than 2^24 - 1 ops
-  if (fa_mode && c->rescue_stats[0]) { c->rescue_stats[1] = c->h_totals[8]; c->rescue_stats[2] = c->h_totals[9]; }
+  if (rb->counters[3]) return BR_ERR_UNSUPPORTED;  // a rewritten CIGAR with more than 2^24 - 1 ops
+  if (fa_mode && c->rescue_stats[0]) { c->rescue_stats[1] = rb->rescue_stats[0]; c->rescue_stats[2] = rb->rescue_stats[1]; }
 
   // what a later large batch is predicted from (run_device_small, big)
   c->hist_n = n; c->hist[0] = n_matches; c->hist[1] = n_cig_arena; c->hist[2] = n_simple >= 0 ? (uint64_t)n_simple : 0; c->hist[3] = n_rows;
   c->hist_simf = dc.filter_by_similarity != 0;
   if (fa_mode) c->hist_n = 0;
-  finish_call(c, dc, b, out, n_matches, n_rows, n_cig_arena, aux_cols);
-  out->a = (const br_row_a *)c->pk_a.p; out->cigar = (const uint64_t *)c->pk_c.p; out->x = nullptr;   // br_device_rows_detail
-  out->similarity_score = aux_cols ? c->pk_sim.as<double>() : nullptr;
-  out->clip_score = aux_cols ? c->pk_clip.as<int32_t>() : nullptr;
+  finish_call(c, dc, b, out, n_matches, n_rows, n_cig_arena, aux_cols, &P);
   return BR_OK;
 }
 
@@ -904,13 +886,13 @@ int expand_rows(br_ctx *c, hipStream_t st, br_device_wide_rows *out) {
     launch_wide_fields(st, W);
     ScanArgs S3{};
     RC(c->tile_sums.ensure((size_t)std::max<int64_t>(scan_tiles_for((int64_t)n_rows + 1), 1) * 8 * 3));
-    RC(c->totals.ensure(16 * 8));
+    RC(ensure_totals(c));
     S3.n = (int64_t)n_rows; S3.src32 = c->r_ncig.as<uint32_t>(); S3.tile_sums = c->tile_sums.as<uint64_t>();
     uint64_t *d_tot = c->totals.as<uint64_t>();
-    launch_scan(st, S3, 2, c->r_cigoff.p, true, d_tot + 8);
-    HIPCHK(hipMemcpyAsync(c->h_totals + 12, d_tot + 8, 8, hipMemcpyDeviceToHost, st));
+    launch_scan(st, S3, 2, c->r_cigoff.p, true, d_tot + TOT_WIDE_CIGAR);
+    HIPCHK(hipMemcpyAsync(&c->rb->wide_cigar, d_tot + TOT_WIDE_CIGAR, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    n_out_words = c->h_totals[12];
+    n_out_words = c->rb->wide_cigar;
     RC(c->cigar_out.ensure((size_t)std::max<uint64_t>(n_out_words, 1) * 4));
     W.w_cigoff = c->r_cigoff.as<uint64_t>(); W.w_cigar = c->cigar_out.as<uint32_t>();
     launch_wide_cigars(st, W, (int64_t)n_out_words);
@@ -951,7 +933,6 @@ extern "C" int br_ctx_collect_counters(br_ctx *c, const br_device_batch *b, void
     memset(&tmp, 0, sizeof(tmp));
     RC(run_match_table(c, dc, b, st, &tmp, pf, false));
   }
-  RC(c->totals.ensure(16 * 8));
   DevBuf stats; RC(stats.ensure(8 * 8));   // (freed on the way out)
   HIPCHK(hipMemsetAsync(stats.p, 0, 8 * 8, st));
   StatsArgs T{};

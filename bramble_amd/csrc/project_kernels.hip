@@ -1110,8 +1110,8 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 6) k_emit_dense(ProjectArg
   }
   if (A.tot) {   // the totals never left the device: the whole list (CLS 0), its simple prefix (1) or the rest (2) from tot[]
     if (tot_over(A.tot, A.lim_m, A.lim_c)) return;
-    n_matches = CLS == 1 ? (int64_t)A.tot[2] : (int64_t)A.tot[0];
-    first = CLS == 2 ? (int64_t)A.tot[2] : 0;
+    n_matches = CLS == 1 ? (int64_t)A.tot[TOT_SIMPLE] : (int64_t)A.tot[TOT_MATCHES];
+    first = CLS == 2 ? (int64_t)A.tot[TOT_SIMPLE] : 0;
     if ((uint64_t)(n_matches - first) > A.cover) return;   // the grid was sized from a prediction that fell short: the host sees the same and redoes the batch
   }
   int64_t mi64 = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1883,7 +1883,7 @@ __global__ void __launch_bounds__(256) k_primary(PairArgs P, const uint32_t *__r
 template <bool AUX>
 __global__ void __launch_bounds__(256) k_rows(PairArgs P) {
   int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (P.tot) { if (tot_over(P.tot, P.lim_m, P.lim_c) || rows_over(P.tot, P.lim_r) || r >= (int64_t)P.tot[3]) return; }   // the record count is on the device
+  if (P.tot) { if (tot_over(P.tot, P.lim_m, P.lim_c) || rows_over(P.tot, P.lim_r) || r >= (int64_t)P.tot[TOT_ROWS]) return; }   // the record count is on the device
   else if (r >= P.n_rows_total) return;
   const uint4 rec = P.r_rec[r];
   const uint32_t x = rec.x;

@@ -55,11 +55,11 @@ int sam_format_impl(br_ctx *c, const br_device_bam *in, hipStream_t st, const ui
   RC(pf.begin(BR_K_SCAN));
   launch_sam_scan(st, A.len, n, c->sf_tmp.as<uint64_t>());
   RC(pf.end());
-  HIPCHK(hipMemcpyAsync(c->h_totals + 48, first_bad, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(c->h_totals + 49, A.len + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&c->rb->sam_bad, first_bad, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&c->rb->sam_bytes, A.len + n, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (c->h_totals[48] != ~0ull) { pf.collect(); return BR_ERR_INVALID_ARG; }   // a record the text cannot say: no line of it
-  const uint64_t total = c->h_totals[49];
+  if (c->rb->sam_bad != ~0ull) { pf.collect(); return BR_ERR_INVALID_ARG; }   // a record the text cannot say: no line of it
+  const uint64_t total = c->rb->sam_bytes;
   DevBuf &tb = c->sf_text[c->sf_which];
   RC(tb.ensure((size_t)total + 16));
   A.text = tb.as<uint8_t>();

@@ -174,6 +174,12 @@ def test_streamed_dp_every_array_shape_leftovers_and_pieces():
     d = ctx.ksw_diag()
     assert d["pieces"] == 1 and all(n > 100 for n in d["per_shape"]) and d["leftover_before"] > 50, d
     assert d["leftover_after"] == d["leftover_before"], d       # no group ran out of tape
+    # the diagnostic is the DP's own: a BGZF call on the same context (its compressed size, some tens of KiB, is no
+    # leftover count) leaves it as it was
+    import torch
+    z = ctx.bgzf_deflate_device(torch.from_numpy(rng.randint(0, 256, 48 * 1024).astype(np.uint8)).cuda())
+    assert z.numel() > 40 * 1024
+    assert ctx.ksw_diag() == d
     ctx.set_param("ksw_tape_mb", 1)
     check(*ctx.ksw_pairs(pairs))
     assert ctx.ksw_diag()["pieces"] > 1
