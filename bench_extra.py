@@ -11,6 +11,10 @@
   python bench_extra.py collate [--reads N]  br_collator over N pairs' records (default 10 M pairs, ~20 M records) in HBM in a
                                          random order, added in bundles of 1 M: add / finish / bundle-cut seconds, collator
                                          peak device bytes per record, against br_bam_split_device over the same stream
+  python bench_extra.py sort [--reads N]  br_sorter over the projected records of the bench.py workload (N pairs, default 10 M): handed
+                                         to the sorter from HBM in slices of 1 M rows, finished, then drained with next (128 MiB
+                                         pieces) into br_bgzf_deflate_device: add / finish / drain seconds (the gather's share of the
+                                         drain apart), sorter peak device bytes per record
   python bench_extra.py samout [--reads N]  SAM text out: br_sam_format_device on the projected records of N pairs (default 500 000,
                                          about 1 M records: one CLI bundle) against br_bgzf_deflate_device of the same stream in the
                                          same process (ms per bundle, text GB/s), then the command line file to file with -O sam
@@ -32,7 +36,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
@@ -91,6 +95,55 @@ def main():
                 split.append(round(time.perf_counter() - t0, 4))
         print(json.dumps({"config": "collate", "pairs": n, "records": n_rec, "stream_bytes": int(stream.size), "runs": runs,
                           "split_device_s": split}))
+        return
+    if args.config == "sort":
+        n = args.reads or 10_000_000
+        ann = synth.Annotation("G")
+        batch = ann.reads(n, "pe", with_records=1)
+        stream_h, roff, rlen = synth.Annotation.frame_records(batch)
+        del batch
+        cfg = lib.make_config()
+        idx = lib.Index.from_flat(ann.flat, device=0)
+        ctx = lib.Context(idx)
+        blob = torch.from_numpy(stream_h).to("cuda:0")
+        off_d = torch.from_numpy(roff.view(np.int64)).to("cuda:0")
+        len_d = torch.from_numpy(rlen.view(np.int32)).to("cuda:0")
+        st = torch.cuda.current_stream().cuda_stream
+        _, bam = ctx.project_bam_device(cfg, blob, off_d, len_d, np.arange(ann.flat["n_refs"], dtype=np.int32), st)
+        torch.cuda.synchronize()
+        n_rows, n_bytes = int(bam.n_rows), int(bam.n_bytes)
+        # the deflate and the context's other calls reuse the context's buffers: the sorter works on a copy of the stream
+        data = torch.as_tensor(brdev._DevArray(bam.data, n_bytes, "|u1"), device="cuda:0").clone()
+        rows = torch.as_tensor(brdev._DevArray(bam.row_off, n_rows + 1, "<u8"), device="cuda:0").clone()
+        torch.cuda.synchronize()
+        runs = []
+        for step in range(args.warmup + args.steps):
+            s = lib.Sorter(0)
+            t0 = time.perf_counter()
+            for a in range(0, n_rows, 1_000_000):
+                m = min(1_000_000, n_rows - a)
+                s.add_device(lib.BrDeviceBam(data.data_ptr(), n_bytes, rows.data_ptr() + 8 * a, m), None)
+            t1 = time.perf_counter()
+            s.finish()
+            t2 = time.perf_counter()
+            pieces, z_bytes = 0, 0
+            while True:
+                p = s.next_records(128 << 20)
+                if not p.n_rows:
+                    break
+                z = ctx.bgzf_deflate_device(torch.as_tensor(brdev._DevArray(p.data, int(p.n_bytes), "|u1"), device="cuda:0"), st)
+                z_bytes += int(z.numel())
+                pieces += 1
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            stt = s.stats()
+            s.close()
+            if step >= args.warmup:
+                runs.append({"add_s": round(t1 - t0, 4), "finish_s": round(t2 - t1, 4), "drain_s": round(t3 - t2, 4),
+                             "gather_s": round(stt["next_s"], 4), "pieces": pieces, "compressed_bytes": z_bytes,
+                             "arena_bytes_per_record": round(stt["arena_bytes"] / n_rows, 1),
+                             "peak_bytes_per_record": round(stt["peak_bytes"] / n_rows, 1)})
+        print(json.dumps({"config": "sort", "pairs": n, "records": n_rows, "stream_bytes": n_bytes, "runs": runs}))
         return
     if args.config == "small":
         import subprocess

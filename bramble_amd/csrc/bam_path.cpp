@@ -298,18 +298,13 @@ extern "C" int br_bam_bundle_stage(br_ctx *c, const br_bam_bundle *bb, int slot)
   return BR_OK;
 }
 
-// records in HBM -> projected records (or their BGZF blocks, or their SAM lines) in pinned host memory: the part the staged and
-// the resident entry points share.  out_mode: br_bam_bundle.bgzf_on_device (0 records, 1 BGZF, BR_OUT_SAM_TEXT)
-static int project_bam_tail(br_ctx *c, const br_config *cfg, const br_device_records *dr, const int32_t *ref_map, int32_t n_ref_map,
-                            int out_mode, bool nowait, double wait_ms, br_host_bam *out) {
+// a record stream in HBM -> its bytes (or its BGZF blocks, or its SAM lines) in one of the two pinned host buffers.  note: the
+// BRAMBLE_AMD_TIMING line's front (what came before the stream), or NULL
+static int device_bam_home(br_ctx *c, br_device_bam db, int out_mode, bool nowait, const char *note, br_host_bam *out) {
   static const bool timing = getenv("BRAMBLE_AMD_TIMING") != nullptr;
   auto tnow = []() { return std::chrono::steady_clock::now(); };
   auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   hipStream_t st = nullptr;
-  const int64_t n = dr->n_aln;
-  auto t1 = tnow();
-  br_device_rows rows; br_device_bam db;
-  RC(br_project_bam_device(c, cfg, dr, ref_map, n_ref_map, st, &rows, &db));
   auto t2 = tnow();
   int hs = c->h_bam_next; c->h_bam_next ^= 1;
   if (c->home_pending[hs]) { HIPCHK(hipEventSynchronize(c->ev_home[hs])); c->home_pending[hs] = false; }   // (a caller that never asked)
@@ -344,15 +339,46 @@ static int project_bam_tail(br_ctx *c, const br_config *cfg, const br_device_rec
     if (db.n_bytes) HIPCHK(hipMemcpyAsync(c->h_bam[hs], db.data, (size_t)db.n_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
-  if (timing) fprintf(stderr, "[bundle] %lld records: upload wait %.1f ms, records -> records %.1f ms, deflate / format %.1f ms, download of %.0f MB %.1f ms\n", (long long)n, wait_ms, tms(t1, t2), tms(t2, t3), (double)db.n_bytes / 1e6, tms(t3, tnow()));
+  if (timing && note) fprintf(stderr, "%s, deflate / format %.1f ms, download of %.0f MB %.1f ms\n", note, tms(t2, t3), (double)db.n_bytes / 1e6, tms(t3, tnow()));
   out->data = c->h_bam[hs]; out->n_bytes = db.n_bytes; out->n_rows = db.n_rows;
+  return BR_OK;
+}
+
+// records in HBM -> projected records (or their BGZF blocks, or their SAM lines) in pinned host memory, or left in HBM
+// (BR_OUT_RESIDENT): the part the staged and the resident entry points share.  out_mode: br_bam_bundle.bgzf_on_device
+static int project_bam_tail(br_ctx *c, const br_config *cfg, const br_device_records *dr, const int32_t *ref_map, int32_t n_ref_map,
+                            int out_mode, bool nowait, double wait_ms, br_host_bam *out) {
+  static const bool timing = getenv("BRAMBLE_AMD_TIMING") != nullptr;
+  hipStream_t st = nullptr;
+  auto t1 = std::chrono::steady_clock::now();
+  br_device_rows rows; br_device_bam db;
+  c->last_bam = br_device_bam{};
+  RC(br_project_bam_device(c, cfg, dr, ref_map, n_ref_map, st, &rows, &db));
+  char note[160]; note[0] = 0;
+  if (timing) snprintf(note, sizeof note, "[bundle] %lld records: upload wait %.1f ms, records -> records %.1f ms", (long long)dr->n_aln, wait_ms,
+                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
+  if (out_mode == BR_OUT_RESIDENT) { c->last_bam = db; out->n_rows = db.n_rows; if (timing) fprintf(stderr, "%s, kept in HBM\n", note); }
+  else RC(device_bam_home(c, db, out_mode, nowait, note, out));
   out->total_complete = rows.total_complete; out->total_unique = rows.total_unique;
   out->dropped_reads = rows.dropped_reads; out->total_processed = rows.total_processed;
   return BR_OK;
 }
 
+extern "C" int br_ctx_last_device_bam(const br_ctx *c, br_device_bam *out) {
+  if (!c || !out) return BR_ERR_INVALID_ARG;
+  *out = c->last_bam;
+  return BR_OK;
+}
+
+extern "C" int br_device_bam_download(br_ctx *c, const br_device_bam *in, int out_mode, int nowait, br_host_bam *out) {
+  if (!c || !in || !out || (in->n_bytes && (!in->data || !in->row_off)) || (out_mode != 0 && out_mode != 1 && out_mode != BR_OUT_SAM_TEXT)) return BR_ERR_INVALID_ARG;
+  memset(out, 0, sizeof(*out));
+  HIPCHK(hipSetDevice(c->ix->device));
+  return device_bam_home(c, *in, out_mode, nowait != 0, nullptr, out);
+}
+
 // bgzf_on_device: BR_OUT_SAM_TEXT, or BGZF blocks for any other value than 0 (as before there was a third output)
-static int out_mode_of(int v) { return v == BR_OUT_SAM_TEXT ? BR_OUT_SAM_TEXT : v != 0 ? 1 : 0; }
+static int out_mode_of(int v) { return v == BR_OUT_SAM_TEXT || v == BR_OUT_RESIDENT ? v : v != 0 ? 1 : 0; }
 
 static int project_bam_staged_impl(br_ctx *c, const br_config *cfg, const br_bam_bundle *bb, int slot, br_host_bam *out, bool nowait) {
   if (!c || !cfg || !bb || !out || slot < 0 || slot > 2) return BR_ERR_INVALID_ARG;

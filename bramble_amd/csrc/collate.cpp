@@ -28,19 +28,6 @@
 
 using namespace br;
 
-namespace {
-// an exactly sized device buffer; a failed allocation is BR_ERR_CAPACITY (the records do not fit), not a HIP error
-struct ColBuf {
-  void *p = nullptr; size_t cap = 0;
-  ColBuf() = default;
-  ColBuf(ColBuf &&o) noexcept { *this = std::move(o); }
-  ColBuf &operator=(ColBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
-  ~ColBuf() { release(); }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <typename T> T *as() const { return (T *)p; }
-};
-}  // namespace
-
 struct br_collator {
   int device = 0;
   hipStream_t st = nullptr;

@@ -221,11 +221,14 @@ void launch_col_copy(hipStream_t st, const uint8_t *blob, const uint64_t *rec_of
   const int64_t g = (n + 3) / 4;
   hipLaunchKernelGGL(k_col_copy, dim3((unsigned)(g < 65536 ? g : 65536)), dim3(256), 0, st, blob, rec_off, rec_len, n, dst, base, arena, off_out, len_out);
 }
+void launch_col_bits(hipStream_t st, const uint64_t *part, int64_t blocks, uint64_t *bits) {
+  hipLaunchKernelGGL(k_col_bits, dim3(1), dim3(256), 0, st, part, blocks, bits);
+}
 void launch_col_key(hipStream_t st, const uint8_t *arena, const uint64_t *off, int64_t n, uint64_t mask, uint64_t *key,
                     uint32_t *idx, uint64_t *part, uint64_t *bits) {
   if (n <= 0) return;
   hipLaunchKernelGGL(k_col_key, dim3(blocks256(n)), dim3(256), 0, st, arena, off, n, mask, key, idx, part);
-  hipLaunchKernelGGL(k_col_bits, dim3(1), dim3(256), 0, st, (const uint64_t *)part, (int64_t)blocks256(n), bits);
+  launch_col_bits(st, part, (int64_t)blocks256(n), bits);
 }
 void launch_col_radix_pass(hipStream_t st, const uint64_t *key_in, const uint32_t *idx_in, uint64_t *key_out, uint32_t *idx_out,
                            int64_t n, int shift, uint64_t *hist, uint64_t *tmp) {

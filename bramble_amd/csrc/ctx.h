@@ -140,6 +140,7 @@ struct br_ctx {
   uint8_t *h_bam[2] = {nullptr, nullptr}; size_t h_bam_cap[2] = {0, 0}; int h_bam_next = 0;  // pinned download buffers of br_project_bam_bundle (alternating)
   BigPinned h_bam_mem[2];
   int64_t last_n_rows = 0, last_n_aln = 0;
+  br_device_bam last_bam{};   // BR_OUT_RESIDENT: the last bundle's projected records, left in HBM (br_ctx_last_device_bam)
   DevBuf fa_stats, fa_n_prob, fa_seq_bytes, fa_prob_off, fa_seqarena_off, fa_probs, fa_results, fa_seq_arena, fa_clip_ops,
       fa_ideal_cap, fa_scratch, fa_srcs, fa_want, b_seq_off, b_seqs, b_seq_src;
   // the streamed -S DP (ksw_kernels.hip): per-bin descriptors, per-problem DP results, leftovers, counters, group

@@ -80,6 +80,18 @@ struct DevBuf {
   template <typename T> T *as() { return (T *)p; }
 };
 
+// an exactly sized device buffer (the collator's and the sorter's arenas and tables: their owners count the bytes and turn a
+// failed allocation into BR_ERR_CAPACITY -- the records do not fit -- instead of a HIP error)
+struct ColBuf {
+  void *p = nullptr; size_t cap = 0;
+  ColBuf() = default;
+  ColBuf(ColBuf &&o) noexcept { *this = std::move(o); }
+  ColBuf &operator=(ColBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  ~ColBuf() { release(); }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  template <typename T> T *as() const { return (T *)p; }
+};
+
 // growable pinned host array (contents are not preserved across growth: every call rewrites it)
 // (large ones on huge pages, registered: BigPinned; small ones from hipHostMalloc)
 template <typename T>

@@ -94,6 +94,8 @@ class BgzfWriter {
   bool write(const uint8_t *p, size_t n);
   // closes the pending partial block, then appends bytes that already ARE complete BGZF blocks (device deflate)
   bool write_raw(const uint8_t *p, size_t n);
+  // closes the pending partial block: bytes_out() is then the file position of whatever is written next
+  bool flush() { return write_raw(nullptr, 0); }
   bool close();  // flushes and appends the 28-byte EOF block
   void abandon();  // closes the file without the EOF block (a failed run must not leave a stream that looks complete)
   const std::string &error() const { return err_; }

@@ -7,6 +7,9 @@
 //   uploader      : br_bam_bundle_stage (host bundles: records to one of three device slots, own copy stream)
 //   runner        : br_project_bam_staged_nowait / br_project_bam_resident (everything between the raw records on the device)
 //   writer thread : BGZF deflate (threaded) -> output file; device-made BGZF blocks or SAM lines (-O sam) go out as they are
+//   --sort        : the runner leaves every bundle's records in HBM (BR_OUT_RESIDENT) and adds them to a br_sorter; after the last
+//                   bundle the sorted pieces take the same way out (br_device_bam_download -> writer); --write-index: the writer
+//                   notes the blocks it writes and br_sorter_index builds <out>.bai from them
 #include <ctype.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -35,7 +38,7 @@ void usage(FILE *f) {
           " [--max-soft-clip N] [--max-junction-insertion N] [--max-junction-deletion N]\n"
           " [--max-error-exon N] [--similarity-threshold X]\n"
           " [--device-deflate | --host-deflate | --compression-level 0-9] [--device-reader | --host-reader] [--bundle-size N]\n"
-          "               [--device N | --devices a,b,...] [--collate]\n\n"
+          "               [--device N | --devices a,b,...] [--collate] [--sort [--write-index]]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -47,7 +50,11 @@ void usage(FILE *f) {
           "--collate: input in any order (e.g. coordinate-sorted); the whole input is read into one device's memory and grouped by read name before the first bundle is projected.\n"
           "-O, --output-fmt bam|sam: BAM (the default) or SAM text, formatted on the GPU (the header text, then one line per record,\n"
           "no BGZF framing); the format is never taken from the output's extension.  --compression-level, --host-deflate and\n"
-          "--device-deflate apply to BAM only.\n");
+          "--device-deflate apply to BAM only.\n"
+          "--sort: the output is sorted by coordinate (transcript, position, forward strand first; ties keep the order of the unsorted\n"
+          "output) and its header says @HD SO:coordinate; the projected records of the whole run are kept in one device's memory and\n"
+          "sorted there.  --write-index: with --sort and BAM output to a file, also write <out>.bai, built on the GPU (device deflate only).\n"
+          "A run with --sort prints one more line in front of the final report, which is unchanged: [bramble] sorted N records by coordinate ...\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -55,7 +62,7 @@ bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(
 int parse_args(int argc, char **argv, Options &o) {
   memset(&o.cfg, 0, sizeof(o.cfg));
   o.cfg.junc_miss_discount = 1.0;
-  bool codec = false;   // a BGZF codec option was given
+  bool codec = false, host_codec = false;   // a BGZF codec option was given; one that asks for the host codec
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "%s: missing value\n", argv[i]); return nullptr; } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -81,8 +88,8 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (a == "-S" || a == "--genome") { const char *v = value(); if (!v) return -1; o.fasta = v; }
     else if (a == "-o" || a == "--out") { const char *v = value(); if (!v) return -1; o.out_bam = v; }
     else if (a == "-p" || a == "--threads") { const char *v = value(); if (!v) return -1; o.threads = atoi(v); if (o.threads < 1) o.threads = 1; }
-    else if (a == "--compression-level") { const char *v = value(); if (!v) return -1; o.level = atoi(v); if (o.level < 0 || o.level > 9) return -1; o.device_deflate = false; codec = true; }
-    else if (a == "--host-deflate") { o.device_deflate = false; codec = true; }
+    else if (a == "--compression-level") { const char *v = value(); if (!v) return -1; o.level = atoi(v); if (o.level < 0 || o.level > 9) return -1; o.device_deflate = false; codec = host_codec = true; }
+    else if (a == "--host-deflate") { o.device_deflate = false; codec = host_codec = true; }
     else if (a == "-O" || a == "--output-fmt") {
       const char *v = value(); if (!v) return -1;
       std::string f = v;
@@ -96,6 +103,8 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (a == "--device-reader") o.device_reader = 1;
     else if (a == "--host-reader") o.device_reader = 0;
     else if (a == "--collate") o.collate = true;
+    else if (a == "--sort") o.sort = true;
+    else if (a == "--write-index") o.write_index = true;
     else if (a == "--device") { const char *v = value(); if (!v) return -1; o.devices.assign(1, atoi(v)); }
     else if (a == "--devices") {
       const char *v = value(); if (!v) return -1;
@@ -113,6 +122,11 @@ int parse_args(int argc, char **argv, Options &o) {
   if (!o.fasta.empty()) o.cfg.use_fasta = 1;
   if (o.sam_out && codec) { fprintf(stderr, "--compression-level, --host-deflate and --device-deflate apply to BAM output, not to --output-fmt sam\n"); return -1; }
   if (o.collate && o.devices.size() > 1) { fprintf(stderr, "--collate works on one device: give --device N, not a --devices list\n"); return -1; }
+  if (o.sort && o.devices.size() > 1) { fprintf(stderr, "--sort works on one device: give --device N, not a --devices list\n"); return -1; }
+  if (o.write_index && !o.sort) { fprintf(stderr, "--write-index needs --sort: a BAI index describes a coordinate-sorted file\n"); return -1; }
+  if (o.write_index && o.sam_out) { fprintf(stderr, "--write-index applies to BAM output, not to --output-fmt sam\n"); return -1; }
+  if (o.write_index && o.out_bam == "-") { fprintf(stderr, "--write-index needs an output file, not standard output\n"); return -1; }
+  if (o.write_index && host_codec) { fprintf(stderr, "--write-index works with the device deflate, not with --host-deflate or --compression-level\n"); return -1; }
   return 0;
 }
 
@@ -141,11 +155,34 @@ bool load_fasta(const char *path, Fasta &fa) {
 // ---- output header ------------------------------------------------------------------------------
 // src/bramble.cpp:513-623: @HD first, one @SQ per transcript in guide order, then every other input
 // line except @SQ / @HD (with the new @PG appended the way sam_hdr_add_pg chains it), then the @CO line.
-std::string make_header_text(const std::string &in_text, const br_index *ix, const std::string &cl, const std::string &gff) {
+// --sort: the @HD line with SO:coordinate -- the input's fields in their order, SO replaced (appended when absent), GO and SS
+// dropped (they describe another order); "@HD VN:1.6 SO:coordinate" when the input has no such line
+std::string sorted_hd_line(const std::string &hd) {
+  if (hd.empty()) return "@HD\tVN:1.6\tSO:coordinate";
+  std::string out = "@HD";
+  bool so = false;
+  for (size_t a = hd.find('\t'); a != std::string::npos;) {
+    const size_t b = hd.find('\t', a + 1);
+    const std::string f = hd.substr(a + 1, b == std::string::npos ? std::string::npos : b - a - 1);
+    a = b;
+    if (f.compare(0, 3, "GO:") == 0 || f.compare(0, 3, "SS:") == 0 || f.empty()) continue;
+    if (f.compare(0, 3, "SO:") == 0) { if (!so) out += "\tSO:coordinate"; so = true; continue; }
+    out += '\t'; out += f;
+  }
+  if (!so) out += "\tSO:coordinate";
+  return out;
+}
+
+std::string make_header_text(const std::string &in_text, const br_index *ix, const std::string &cl, const std::string &gff, bool sorted) {
   std::vector<std::string> lines;
   for (size_t a = 0; a < in_text.size();) { size_t b = in_text.find('\n', a); if (b == std::string::npos) b = in_text.size(); if (b > a) lines.emplace_back(in_text, a, b - a); a = b + 1; }
   std::string out;
-  for (auto &l : lines) if (l.compare(0, 3, "@HD") == 0) { out += l; out += '\n'; }
+  if (sorted) {
+    std::string hd;
+    for (auto &l : lines) if (l.compare(0, 3, "@HD") == 0 && hd.empty()) hd = l;
+    out += sorted_hd_line(hd); out += '\n';
+  } else
+    for (auto &l : lines) if (l.compare(0, 3, "@HD") == 0) { out += l; out += '\n'; }
   size_t nt = br_index_num_transcripts(ix);
   for (size_t t = 0; t < nt; t++) {
     int64_t len = br_index_transcript_len(ix, (uint32_t)t);
@@ -232,9 +269,17 @@ struct OutFile {
 struct Run {
   const Options &o; Input &in; Outbox &out; BgzfWriter &wr;
   const std::vector<int32_t> &ref_map; std::vector<std::unique_ptr<Worker>> &workers;
+  br_sorter *sorter = nullptr;   // --sort: the runner's records go here; drain_sorted() writes them once the input is through
+  bool track_blocks = false;     // --write-index: the writer notes where every BGZF block of the record section starts
+  std::vector<br_bgzf_span> spans;
+  uint64_t stream_pos = 0;       // uncompressed record bytes written so far
+  uint64_t sorted_chunks = 0;    // chunks drain_sorted() handed to the writer
+  int64_t sorted_records = 0;
+  double t_sort_add = 0, t_sort_finish = 0;
   std::atomic<int> fail{0};
   std::string writer_err;
   double t_deflate = 0;
+  static constexpr uint64_t SORT_PIECE = 128ull << 20;   // record bytes per sorted piece (one deflate / format call and one download)
   void go() {
     std::thread writer([this] { write(); });
     for (auto &wp : workers) {
@@ -245,6 +290,7 @@ struct Run {
       } else w->runner = std::thread([this, w] { run_resident(w, *in.dev_queue((size_t)w->id)); });   // (the bundles are in its HBM already)
     }
     for (auto &w : workers) { if (w->uploader.joinable()) w->uploader.join(); if (w->runner.joinable()) w->runner.join(); }
+    if (sorter && !fail) { in.join(); drain_sorted(workers[0].get()); }   // (the source's last sequence number is final after join)
     out.finish();
     in.join(); writer.join();
   }
@@ -266,6 +312,7 @@ struct Run {
         int wrc = br_host_bam_wait(workers[(size_t)c.worker]->ctx, &hb);
         if (wrc && writer_err.empty()) { writer_err = std::string("download failed: ") + br_strerror(wrc); raise_fail(); }
       }
+      if (writer_err.empty() && c.n && track_blocks && !note_blocks(c)) { writer_err = wr.error().empty() ? "malformed BGZF block from the device" : wr.error(); raise_fail(); }
       if (writer_err.empty() && c.n && !(o.device_deflate || o.sam_out ? wr.write_raw(c.data, (size_t)c.n) : wr.write(c.data, (size_t)c.n))) {
         writer_err = wr.error();
         raise_fail();                      // nothing projected from here on could be written: the runners drain
@@ -277,10 +324,47 @@ struct Run {
       w->done_cv.notify_all();
     }
   }
+  // the blocks of a device-deflated chunk: file offset (the header's partial block is closed first) and stream offset of each
+  bool note_blocks(const OutChunk &c) {
+    if (!wr.flush()) return false;
+    const uint64_t at = wr.bytes_out();
+    for (uint64_t p = 0; p < c.n;) {
+      if (p + 26 > c.n) return false;
+      const uint64_t bsize = (uint64_t)(c.data[p + 16] | c.data[p + 17] << 8) + 1;
+      if (bsize < 26 || p + bsize > c.n) return false;
+      uint32_t isize; memcpy(&isize, c.data + p + bsize - 4, 4);
+      spans.push_back(br_bgzf_span{at + p, stream_pos});
+      stream_pos += isize; p += bsize;
+    }
+    return true;
+  }
+  // --sort, after the last bundle: finish, then piece by piece next -> deflate or format + download (nowait) -> the writer
+  void drain_sorted(Worker *w) {
+    auto t0 = now();
+    int rc = br_sorter_finish(sorter, &sorted_records);
+    uint64_t seq = in.next_seq;
+    while (!rc && !fail) {
+      br_device_bam piece;
+      rc = br_sorter_next(sorter, SORT_PIECE, &piece);
+      if (rc || piece.n_rows == 0) break;
+      { std::unique_lock<std::mutex> l(w->done_m); w->done_cv.wait(l, [&] { return w->written + 2 > w->produced || fail; }); }
+      if (fail) break;
+      br_host_bam hb;
+      rc = br_device_bam_download(w->ctx, &piece, final_mode(), 1, &hb);
+      if (rc) break;
+      { std::lock_guard<std::mutex> l(w->done_m); w->produced++; }
+      out.put(seq++, OutChunk{hb.data, hb.n_bytes, w->id});
+      sorted_chunks++;
+    }
+    w->gpu_seconds += secs(t0, now());
+    (void)br_sorter_stats(sorter, nullptr, nullptr, &t_sort_add, &t_sort_finish, nullptr);
+    if (rc) { fprintf(stderr, "error: sorting failed on device %d: %s\n", w->device, br_strerror(rc)); raise_fail(); }
+  }
   br_bam_bundle args(Bundle &b) const {
     return br_bam_bundle{b.blob.data(), b.blob.size(), b.off.data(), b.len.data(), (int64_t)b.off.size(), ref_map.data(), (int32_t)ref_map.size(), out_mode()};
   }
-  int out_mode() const { return o.sam_out ? BR_OUT_SAM_TEXT : o.device_deflate ? 1 : 0; }
+  int final_mode() const { return o.sam_out ? BR_OUT_SAM_TEXT : o.device_deflate ? 1 : 0; }   // what the writer gets
+  int out_mode() const { return sorter ? BR_OUT_RESIDENT : final_mode(); }                     // what a projection call leaves
   // one projection call (none after a failure), once chunk j - 2 of this worker is on disk: the context's two pinned
   // result buffers alternate
   template <typename F>
@@ -297,6 +381,14 @@ struct Run {
   void deliver(Worker *w, uint64_t seq, const br_host_bam &hb) {
     if (fail) return;
     w->total_complete += hb.total_complete; w->total_unique += hb.total_unique; w->dropped += hb.dropped_reads; w->n_bundles++;
+    if (sorter) {   // the records stay in HBM: into the sorter (the runner sees the bundles in order), nothing for the writer yet
+      br_device_bam db;
+      int src = br_ctx_last_device_bam(w->ctx, &db);
+      if (!src) src = br_sorter_add(sorter, &db, 1, nullptr);
+      if (src) { fprintf(stderr, "error: the sorter could not take a bundle on device %d: %s\n", w->device, br_strerror(src)); raise_fail(); return; }
+      out.put(seq, OutChunk{nullptr, 0, -1});
+      return;
+    }
     { std::lock_guard<std::mutex> l(w->done_m); w->produced++; }
     out.put(seq, OutChunk{hb.data, hb.n_bytes, w->id});
   }
@@ -384,7 +476,10 @@ extern "C" int br_cli_main(int argc, char **argv) {
 
   // the input is already being read while the guides are parsed and the indexes are built
   std::vector<std::unique_ptr<Worker>> workers;
+  br_sorter *sorter = nullptr;
   auto free_all = [&]() {
+    if (sorter) br_sorter_free(sorter);
+    sorter = nullptr;
     for (auto &w : workers) { if (w->ctx) br_ctx_free(w->ctx); if (w->ix) br_index_free(w->ix); w->ctx = nullptr; w->ix = nullptr; }
     if (ann) br_annotation_free(ann);
     ann = nullptr;
@@ -441,10 +536,16 @@ extern "C" int br_cli_main(int argc, char **argv) {
       if (src) { fprintf(stderr, "error: reference names on device %d: %s\n", w->device, br_strerror(src)); return give_up(); }
     }
   }
+  uint32_t n_sq = 0;
+  for (size_t t = 0, nt = br_index_num_transcripts(ix0); t < nt; t++) if (br_index_transcript_len(ix0, (uint32_t)t) > 0) n_sq++;
+  if (o.sort) {
+    int src = br_sorter_new(o.devices[0], &sorter);
+    if (src) { fprintf(stderr, "error: sorter on device %d: %s\n", o.devices[0], br_strerror(src)); return give_up(); }
+  }
   OutFile file(o.out_bam);
   if (!file.wr.open(file.tmp.c_str(), o.threads, o.level, !o.sam_out)) { fprintf(stderr, "error: %s\n", file.wr.error().c_str()); return give_up(); }
   {
-    const std::string text = make_header_text(hdr.text, ix0, cl, o.gff);
+    const std::string text = make_header_text(hdr.text, ix0, cl, o.gff, o.sort);
     bool ok;
     if (o.sam_out) ok = file.wr.write_raw((const uint8_t *)text.data(), text.size());   // SAM: the header text as it is
     else { std::vector<uint8_t> h = make_bam_header(text, ix0); ok = file.wr.write(h.data(), h.size()); }
@@ -453,12 +554,30 @@ extern "C" int br_cli_main(int argc, char **argv) {
   if (!o.quiet) printf("[bramble] processing alignments :-)\n");
   double t_setup = since();
   Run run{o, *in, out, file.wr, ref_map, workers};
+  run.sorter = sorter; run.track_blocks = o.write_index;
   run.go();
   int failed = run.fail.load();
   if (!in->err.empty()) { fprintf(stderr, in->err_at_line ? "error: %s:%s\n" : "error: %s: %s\n", o.in_bam.c_str(), in->err.c_str()); failed = 1; }
   if (!run.writer_err.empty()) { fprintf(stderr, "error: %s: %s\n", o.out_bam.c_str(), run.writer_err.c_str()); failed = 1; }
-  if (!failed && out.next != in->next_seq) { fprintf(stderr, "error: %s: output incomplete\n", o.out_bam.c_str()); failed = 1; }
+  if (!failed && out.next != in->next_seq + run.sorted_chunks) { fprintf(stderr, "error: %s: output incomplete\n", o.out_bam.c_str()); failed = 1; }
+  const std::string bai_path = o.out_bam + ".bai", bai_tmp = bai_path + ".tmp-bramble";
+  if (!failed && o.write_index) {   // the index of the blocks just written; it takes the output's route: a temporary name, renamed on success
+    uint8_t *bai = nullptr; uint64_t bai_n = 0;
+    int irc = file.wr.flush() ? br_sorter_index(sorter, (int32_t)n_sq, run.spans.data(), (int64_t)run.spans.size(), file.wr.bytes_out(), &bai, &bai_n) : BR_ERR_INVALID_ARG;
+    if (irc) { fprintf(stderr, "error: %s: index: %s\n", bai_path.c_str(), br_strerror(irc)); failed = 1; }
+    else {
+      FILE *f = fopen(bai_tmp.c_str(), "wb");
+      if (!f || fwrite(bai, 1, (size_t)bai_n, f) != (size_t)bai_n) { fprintf(stderr, "error: could not write %s\n", bai_tmp.c_str()); failed = 1; }
+      if (f && fclose(f) != 0) { fprintf(stderr, "error: could not write %s\n", bai_tmp.c_str()); failed = 1; }
+      br_free_buffer(bai);
+    }
+  }
   if (!file.finish(!failed)) failed = 1;
+  if (o.write_index) {
+    if (failed) remove(bai_tmp.c_str());
+    else if (rename(bai_tmp.c_str(), bai_path.c_str()) != 0) { fprintf(stderr, "error: could not rename %s to %s\n", bai_tmp.c_str(), bai_path.c_str()); failed = 1; }
+  }
+  if (!o.quiet && o.sort && !failed) printf("[bramble] sorted %lld records by coordinate on device %d (add %.2fs, sort %.2fs)%s\n", (long long)run.sorted_records, o.devices[0], run.t_sort_add, run.t_sort_finish, o.write_index ? ", index written" : "");
   double t_done = since();
   uint64_t total_complete = 0, total_unique = 0, dropped = 0, n_bundles = 0;
   double gpu_seconds = 0, t_upload = 0, t_wait_gpu_in = 0;

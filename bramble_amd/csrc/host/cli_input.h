@@ -34,6 +34,8 @@ struct Options {
   bool device_deflate = true;   // BGZF blocks made on the GPU unless a host level is asked for
   bool sam_out = false;         // -O sam: SAM text formatted on the GPU (BR_OUT_SAM_TEXT) instead of BAM
   bool collate = false;          // --collate: the whole input is read into one device's memory and regrouped by read name first
+  bool sort = false;             // --sort: the projected records stay in one device's memory and are written in coordinate order
+  bool write_index = false;      // --write-index: <out>.bai beside the sorted BAM, built on the GPU
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };
 inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }

@@ -135,6 +135,7 @@ class BrBamBundle(C.Structure):
 
 
 OUT_SAM_TEXT = 2   # br_bam_bundle.bgzf_on_device / br_project_bam_resident: SAM lines instead of records or BGZF blocks
+OUT_RESIDENT = 3    # BR_OUT_RESIDENT: the projected records stay in HBM (br_ctx_last_device_bam)
 
 BGZF_BLOCK = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("clen", "<u4"), ("ulen", "<u4"), ("crc", "<u4"), ("pad", "<u4")])
 
@@ -173,6 +174,8 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_sam_header_scan", "br_sam_reader_new", "br_sam_reader_next", "br_sam_reader_upload", "br_sam_reader_next_staged", "br_sam_reader_release", "br_sam_reader_free", "br_sam_reader_error", "br_sam_reader_stats",
            "br_collator_new", "br_collator_add", "br_collator_finish", "br_collator_next", "br_collator_order", "br_collator_set_param",
            "br_collator_stats", "br_collator_free",
+           "br_sorter_new", "br_sorter_set_param", "br_sorter_add", "br_sorter_finish", "br_sorter_next", "br_sorter_order", "br_sorter_stats",
+           "br_sorter_index", "br_sorter_free", "br_ctx_last_device_bam", "br_device_bam_download",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -687,6 +690,31 @@ class Context:
                       "total_unique": int(out.total_unique), "dropped_reads": int(out.dropped_reads),
                       "total_processed": int(out.total_processed)}
 
+    def project_bam_resident_kept(self, cfg, recs, ref_map):
+        """br_project_bam_resident with BR_OUT_RESIDENT: the projected records stay in HBM -> (BrDeviceBam valid until the context's
+        next call, counters dict).  A Sorter takes the BrDeviceBam (add_device)."""
+        rm = np.ascontiguousarray(ref_map, dtype=np.int32)
+        out, db = BrHostBam(), BrDeviceBam()
+        L = lib()
+        L.br_project_bam_resident.argtypes = [C.c_void_p, _P(BrConfig), _P(BrDeviceRecords), C.c_void_p, C.c_int32, C.c_int, C.c_int,
+                                              _P(BrHostBam)]
+        L.br_ctx_last_device_bam.argtypes = [C.c_void_p, _P(BrDeviceBam)]
+        check(L.br_project_bam_resident(self.h, C.byref(cfg), C.byref(recs), rm.ctypes.data, len(rm), OUT_RESIDENT, 0, C.byref(out)),
+              "br_project_bam_resident")
+        check(L.br_ctx_last_device_bam(self.h, C.byref(db)), "br_ctx_last_device_bam")
+        return db, {"n_rows": int(out.n_rows), "total_complete": int(out.total_complete), "total_unique": int(out.total_unique),
+                    "dropped_reads": int(out.dropped_reads), "total_processed": int(out.total_processed)}
+
+    def device_bam_download(self, piece, out_mode=0):
+        """br_device_bam_download: a record stream in HBM (a Sorter piece) -> numpy uint8 of its bytes (out_mode 0), its BGZF
+        blocks (1) or its SAM lines (OUT_SAM_TEXT)."""
+        out = BrHostBam()
+        L = lib()
+        L.br_device_bam_download.argtypes = [C.c_void_p, _P(BrDeviceBam), C.c_int, C.c_int, _P(BrHostBam)]
+        check(L.br_device_bam_download(self.h, C.byref(piece), int(out_mode), 0, C.byref(out)), "br_device_bam_download")
+        n = int(out.n_bytes)
+        return np.ctypeslib.as_array(C.cast(out.data, _P(C.c_uint8)), shape=(n,)).copy() if n else np.zeros(0, np.uint8)
+
     def project_bam_bundle(self, cfg, blob, rec_off, rec_len, ref_map, bgzf_on_device=False, sam_text=False):
         """Host form: numpy blob / rec_off (uint64) / rec_len (uint32) in, (stream uint8[], counters dict) out; with sam_text the
         stream is the projected records' SAM lines (set_sam_refs names their references)."""
@@ -1003,6 +1031,131 @@ class Collator:
     def close(self):
         if self.h:
             lib().br_collator_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BrBgzfSpan(C.Structure):
+    _fields_ = [("coffset", C.c_uint64), ("uoffset", C.c_uint64)]
+
+
+class Sorter:
+    """br_sorter on `device`: projected records ([block_size][record] rows) in, the same records in coordinate order out (key
+    (u32)refID << 32 | (u32)(pos + 1) << 1 | reverse strand, ties in the order they were added), and the BAI index of that
+    order."""
+
+    def __init__(self, device=0):
+        L = lib()
+        L.br_sorter_new.argtypes = [C.c_int, _P(C.c_void_p)]
+        L.br_sorter_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+        L.br_sorter_add.argtypes = [C.c_void_p, _P(BrDeviceBam), C.c_int, C.c_void_p]
+        L.br_sorter_finish.argtypes = [C.c_void_p, _P(C.c_int64)]
+        L.br_sorter_next.argtypes = [C.c_void_p, C.c_uint64, _P(BrDeviceBam)]
+        L.br_sorter_order.argtypes = [C.c_void_p, C.c_void_p]
+        L.br_sorter_stats.argtypes = [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_double)]
+        L.br_sorter_index.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_uint64, _P(C.c_void_p), _P(C.c_uint64)]
+        L.br_sorter_free.argtypes = [C.c_void_p]
+        L.br_free_buffer.argtypes = [C.c_void_p]
+        self.h = None
+        self.device = device
+        self.n = 0
+        h = C.c_void_p()
+        check(L.br_sorter_new(device, C.byref(h)), "br_sorter_new")
+        self.h = h
+
+    def set_param(self, name, value):
+        check(lib().br_sorter_set_param(self.h, name.encode(), int(value)), "br_sorter_set_param")
+
+    def add_records(self, recs, on_device, stream=None):
+        """br_sorter_add as it is: the return code (0, or a BR_ERR_* value)."""
+        return lib().br_sorter_add(self.h, C.byref(recs), 1 if on_device else 0, C.c_void_p(stream or 0))
+
+    @staticmethod
+    def row_offsets(stream_np):
+        """offsets (uint64, n + 1) of the rows of an uncompressed record stream in host memory"""
+        data = np.ascontiguousarray(stream_np, dtype=np.uint8)
+        off, p = [0], 0
+        while p < data.size:
+            p += 4 + int(data[p:p + 4].view("<u4")[0])
+            off.append(p)
+        assert p == data.size
+        return np.asarray(off, dtype=np.uint64)
+
+    def add_host(self, stream_np):
+        """An uncompressed record stream in host memory ([block_size][record]..., every record is taken)."""
+        data = np.ascontiguousarray(stream_np, dtype=np.uint8)
+        off = self.row_offsets(data)
+        recs = BrDeviceBam(data.ctypes.data if data.size else None, data.size, off.ctypes.data, len(off) - 1)
+        check(self.add_records(recs, False), "br_sorter_add")
+
+    def add_device(self, data, row_off):
+        """add_device(data, row_off): torch CUDA tensors, data uint8 ([block_size][record] rows, contiguous) and row_off int64
+        [n + 1].  add_device(bam, None): a BrDeviceBam that describes rows in HBM (what project_bam_device or
+        project_bam_resident_kept return, or a slice of it); it is read after the null stream's work."""
+        import torch
+        if isinstance(data, BrDeviceBam):
+            check(self.add_records(data, True, None), "br_sorter_add")
+            return
+        recs = BrDeviceBam(data.data_ptr(), data.numel(), row_off.data_ptr(), row_off.numel() - 1)
+        check(self.add_records(recs, True, torch.cuda.current_stream(data.device).cuda_stream), "br_sorter_add")
+
+    def finish(self):
+        n = C.c_int64()
+        check(lib().br_sorter_finish(self.h, C.byref(n)), "br_sorter_finish")
+        self.n = int(n.value)
+        return self.n
+
+    def order(self):
+        out = np.zeros(max(self.n, 1), dtype=np.int64)
+        check(lib().br_sorter_order(self.h, out.ctypes.data), "br_sorter_order")
+        return out[:self.n]
+
+    def next_records(self, max_bytes):
+        """The next piece as a BrDeviceBam in HBM (n_rows = 0 at the end; valid until the second next call)."""
+        piece = BrDeviceBam()
+        check(lib().br_sorter_next(self.h, int(max_bytes), C.byref(piece)), "br_sorter_next")
+        return piece
+
+    def pieces(self, max_bytes):
+        """Yields each piece as numpy copies: (uint8 records, int64 row_off [n_rows + 1])."""
+        import torch
+        from .device import _DevArray
+        dev = "cuda:%d" % self.device
+        while True:
+            p = self.next_records(max_bytes)
+            n = int(p.n_rows)
+            if n == 0:
+                return
+            data = torch.as_tensor(_DevArray(p.data, int(p.n_bytes), "|u1"), device=dev).cpu().numpy().copy()
+            off = torch.as_tensor(_DevArray(p.row_off, n + 1, "<u8"), device=dev).cpu().numpy().astype(np.int64)
+            yield data, off
+
+    def index(self, n_ref, blocks, eof_coffset):
+        """br_sorter_index: blocks = [(coffset, uoffset)] of the BGZF blocks that hold the sorted stream -> the BAI file's bytes."""
+        arr = (BrBgzfSpan * max(len(blocks), 1))()
+        for k, (co, uo) in enumerate(blocks):
+            arr[k].coffset, arr[k].uoffset = int(co), int(uo)
+        out, n = C.c_void_p(), C.c_uint64()
+        check(lib().br_sorter_index(self.h, int(n_ref), C.cast(arr, C.c_void_p), len(blocks), int(eof_coffset), C.byref(out), C.byref(n)),
+              "br_sorter_index")
+        try:
+            return C.string_at(out.value, n.value)
+        finally:
+            lib().br_free_buffer(out)
+
+    def stats(self):
+        a, p, ad, fi, nx = C.c_uint64(), C.c_uint64(), C.c_double(), C.c_double(), C.c_double()
+        check(lib().br_sorter_stats(self.h, C.byref(a), C.byref(p), C.byref(ad), C.byref(fi), C.byref(nx)), "br_sorter_stats")
+        return {"arena_bytes": int(a.value), "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value, "next_s": nx.value}
+
+    def close(self):
+        if self.h:
+            lib().br_sorter_free(self.h)
             self.h = None
 
     def __del__(self):

@@ -591,10 +591,75 @@ int br_collator_set_param(br_collator *, const char *name, int64_t value);
 int br_collator_stats(const br_collator *, uint64_t *arena_bytes, uint64_t *peak_bytes, double *add_seconds, double *finish_seconds);
 void br_collator_free(br_collator *);
 
+/* A sorter: the projected records of a whole run in one device's HBM, handed out in coordinate order, and the BAI index of that
+ * order (sort.cpp, sort_kernels.hip).  The order is defined here, modelled on `samtools sort` (equality with it is not tested:
+ * the test machines have no samtools): records are ordered by the 64-bit key
+ *     (uint32)refID << 32 | (uint32)(pos + 1) << 1 | ((flag >> 4) & 1)
+ * so a refID of -1 sorts last and, at one position, the forward strand comes before the reverse one; equal keys keep the order
+ * in which they were added (a stable sort: an input that is sorted already comes out unchanged).
+ *   br_sorter_new        BR_ERR_NO_DEVICE without the device
+ *   br_sorter_add        copies the rows of `recs` ([block_size][record] each, row i = data[row_off[i] .. row_off[i + 1]), the rows
+ *                        contiguous) into the sorter's arena: device memory with on_device != 0, after the work queued on
+ *                        `stream` (NULL: the null stream), host memory (data and row_off) with on_device = 0.  Returns when the
+ *                        copy is done.  BR_ERR_CAPACITY when the arena would exceed "max_bytes" or the device's memory (the
+ *                        sorter may still be freed) or the records would number more than 2^32 - 1 (32-bit radix indices),
+ *                        BR_ERR_INVALID_ARG after finish, or for a device row_off that descends somewhere (nothing is added;
+ *                        a host row_off is checked the same way)
+ *   br_sorter_finish     keys and the radix sort; the number of records.  BR_ERR_INVALID_ARG when a record's pos is below -1 or
+ *                        2^31 - 1 (no BAM position: pos + 1 has to fit the key's 31 bits); the sorter is then to be freed
+ *   br_sorter_next       the next run of whole records in sorted order, gathered into one contiguous buffer with its row_off:
+ *                        at most max_bytes, or one record when that record alone is larger; n_rows = 0 at the end.  The buffer
+ *                        is valid until the SECOND next call (two alternate, as the deflate's do)
+ *   br_sorter_order      host: the add-order index of every output record
+ *   br_sorter_set_param  before the first add: "max_bytes" (arena cap, 0 = none)
+ *   br_sorter_stats      arena bytes, the most device memory the sorter has held, seconds in add, finish and next
+ * Per record the sorter holds the arena's 4 + block_size bytes and 8 bytes of tables while adding, 44 bytes during finish, 32
+ * afterwards (sort.cpp).
+ *
+ * br_sorter_index builds the BAI file (SAM specification 5.2) of the sorted records on the device, after finish.  `blocks` lists
+ * the BGZF blocks that hold the sorted record stream, in file order: coffset = where the block starts in the file, uoffset =
+ * which byte of the sorted, uncompressed record stream is its first (blocks[0].uoffset = 0); eof_coffset = where the EOF block
+ * starts.  *bai is a host buffer for br_free_buffer.  The content:
+ *   virtual offsets  begin of record r = coffset(block holding the first byte of its block_size) << 16 | offset inside that
+ *                    block; its end = the begin of record r + 1, eof_coffset << 16 for the last record
+ *   bins             reg2bin(pos, end), end = pos + the reference length of the CIGAR field (M D N = X; the spilled
+ *                    <l_seq>S<ref_len>N form needs no special case), pos + 1 when that is 0.  A record with refID < 0 or pos < 0 is
+ *                    in no bin and counts in n_no_coor; one with end > 2^29 fails the call with BR_ERR_UNSUPPORTED
+ *   per reference    its bins in ascending bin number; inside a bin, consecutive records of the file that share the bin are one
+ *                    chunk (begin of the first, end of the last) and nothing else is merged (small bins are not folded into their
+ *                    parents, as samtools index does: the file is valid for every BAI reader, not byte-identical to samtools');
+ *                    pseudo-bin 37450 last, with (begin of the reference's first record, end of its last) and (n_mapped,
+ *                    n_unmapped by flag 0x4); a reference without records has n_bin = 0 and n_intv = 0
+ *   linear index     n_intv = 1 + max (end - 1) >> 14; ioffset[w] = the smallest begin among the records that overlap window w,
+ *                    an empty window takes the value of the next one (filled from the right)
+ *   tail             n_no_coor, always
+ * BR_ERR_INVALID_ARG for a refID >= n_ref or a block table that does not cover the stream in blocks of less than 64 KiB. */
+typedef struct br_sorter br_sorter;
+typedef struct br_bgzf_span { uint64_t coffset, uoffset; } br_bgzf_span;
+int br_sorter_new(int device, br_sorter **out);
+int br_sorter_set_param(br_sorter *, const char *name, int64_t value);
+int br_sorter_add(br_sorter *, const br_device_bam *recs, int on_device, void *stream);
+int br_sorter_finish(br_sorter *, int64_t *n_records);
+int br_sorter_next(br_sorter *, uint64_t max_bytes, br_device_bam *piece);
+int br_sorter_order(const br_sorter *, int64_t *order);
+int br_sorter_stats(const br_sorter *, uint64_t *arena_bytes, uint64_t *peak_bytes, double *add_seconds, double *finish_seconds,
+                    double *next_seconds);
+int br_sorter_index(br_sorter *, int32_t n_ref, const br_bgzf_span *blocks, int64_t n_blocks, uint64_t eof_coffset, uint8_t **bai,
+                    uint64_t *n_bytes);
+void br_sorter_free(br_sorter *);
+
 /* br_project_bam_staged / _nowait for records that are in HBM already (a br_bam_reader bundle, or br_bam_split_device's);
  * bgzf_on_device takes the values of br_bam_bundle.bgzf_on_device (0, 1, BR_OUT_SAM_TEXT) */
 int br_project_bam_resident(br_ctx *, const br_config *, const br_device_records *recs, const int32_t *ref_map, int32_t n_ref_map,
                             int bgzf_on_device, int nowait, br_host_bam *out);
+/* The calls above with bgzf_on_device = BR_OUT_RESIDENT leave the projected records in HBM: no deflate, no SAM text, no
+ * download (br_host_bam: the counters and n_rows, n_bytes = 0, data = NULL).  br_ctx_last_device_bam returns them, valid until
+ * the context's next call (a br_sorter takes them from there).  br_device_bam_download is the other half: a record stream in
+ * HBM (a br_sorter_next piece) -> the bytes of out_mode (0 records, 1 BGZF blocks, BR_OUT_SAM_TEXT lines) in the context's
+ * pinned buffers, under the buffer rule of br_host_bam; nowait as br_project_bam_staged_nowait (br_host_bam_wait). */
+#define BR_OUT_RESIDENT 3
+int br_ctx_last_device_bam(const br_ctx *, br_device_bam *out);
+int br_device_bam_download(br_ctx *, const br_device_bam *in, int out_mode, int nowait, br_host_bam *out);
 
 /* ---- SAM text out -------------------------------------------------------------------------- */
 
