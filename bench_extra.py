@@ -15,6 +15,10 @@
                                          to the sorter from HBM in slices of 1 M rows, finished, then drained with next (128 MiB
                                          pieces) into br_bgzf_deflate_device: add / finish / drain seconds (the gather's share of the
                                          drain apart), sorter peak device bytes per record
+  python bench_extra.py quant [--reads N]  br_quant over the rows of the bench.py workload (N pairs, default 10 M), projected once
+                                         (br_project_batch_device, timed): the read names handed over from HBM in slices of 1 M
+                                         alignments, the classes, the EM -- seconds in add / finish / em, iterations, names, classes,
+                                         labels, quantifier peak device bytes per read name
   python bench_extra.py samout [--reads N]  SAM text out: br_sam_format_device on the projected records of N pairs (default 500 000,
                                          about 1 M records: one CLI bundle) against br_bgzf_deflate_device of the same stream in the
                                          same process (ms per bundle, text GB/s), then the command line file to file with -O sam
@@ -36,7 +40,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
@@ -144,6 +148,49 @@ def main():
                              "arena_bytes_per_record": round(stt["arena_bytes"] / n_rows, 1),
                              "peak_bytes_per_record": round(stt["peak_bytes"] / n_rows, 1)})
         print(json.dumps({"config": "sort", "pairs": n, "records": n_rows, "stream_bytes": n_bytes, "runs": runs}))
+        return
+    if args.config == "quant":
+        n = args.reads or 10_000_000
+        ann = synth.Annotation("G")
+        batch = ann.reads(n, "pe")
+        cfg = lib.make_config()
+        idx = lib.Index.from_flat(ann.flat, device=0)
+        ctx = lib.Context(idx)
+        db = brdev.upload_batch(batch)
+        goff = db["group_off"].cpu().numpy().view(np.uint32)
+        n_aln, n_groups = int(db["n_aln"]), int(db["n_groups"])
+        del batch
+        n_tx = idx.num_transcripts()
+        lens = np.asarray([idx.transcript_len(t) for t in range(n_tx)], dtype=np.int64)
+        project = []
+        for _ in range(2):   # (the second call runs on warm tables)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rows = ctx.project_batch_device(cfg, db)
+            torch.cuda.synchronize()
+            project.append(round(time.perf_counter() - t0, 4))
+        n_rows = int(rows.n_rows)
+        cuts = sorted(set(int(np.searchsorted(goff, a, side="left")) for a in range(0, n_aln, 1_000_000)) | {n_groups})   # names whose first alignment opens a slice
+        runs = []
+        for step in range(args.warmup + args.steps):
+            q = lib.Quant(n_tx, lens)
+            t0 = time.perf_counter()
+            for g0, g1 in zip(cuts, cuts[1:]):
+                lib.check(q.add_raw(rows.a, rows.row_off, db["group_off"].data_ptr() + 4 * g0, g1 - g0, True), "br_quant_add")
+            t1 = time.perf_counter()
+            names, classes = q.finish()
+            t2 = time.perf_counter()
+            iters, rel = q.em()
+            t3 = time.perf_counter()
+            stt = q.stats()
+            q.close()
+            if step >= args.warmup:
+                runs.append({"add_s": round(t1 - t0, 4), "add_ms_per_slice": round(1e3 * (t1 - t0) / (len(cuts) - 1), 3), "finish_s": round(t2 - t1, 4),
+                             "em_s": round(t3 - t2, 4), "iterations": iters, "rel_change": rel, "em_us_per_iteration": round(1e6 * (t3 - t2) / max(iters, 1), 2),
+                             "names": names, "unassigned": stt["n_unassigned"], "classes": classes, "labels": stt["n_labels"],
+                             "peak_bytes_per_name": round(stt["peak_bytes"] / max(names, 1), 1)})
+        print(json.dumps({"config": "quant", "pairs": n, "alignments": n_aln, "rows": n_rows, "transcripts": n_tx, "slices": len(cuts) - 1,
+                          "project_s": project, "runs": runs}))
         return
     if args.config == "small":
         import subprocess

@@ -141,6 +141,8 @@ struct br_ctx {
   BigPinned h_bam_mem[2];
   int64_t last_n_rows = 0, last_n_aln = 0;
   br_device_bam last_bam{};   // BR_OUT_RESIDENT: the last bundle's projected records, left in HBM (br_ctx_last_device_bam)
+  // the last projection call's rows, read-name groups and stream, whichever entry point made it (br_quant_add_last); valid like the rows
+  br_device_rows last_rows{}; const uint32_t *last_group_off = nullptr; int64_t last_n_groups = 0; hipStream_t last_stream = nullptr;
   DevBuf fa_stats, fa_n_prob, fa_seq_bytes, fa_prob_off, fa_seqarena_off, fa_probs, fa_results, fa_seq_arena, fa_clip_ops,
       fa_ideal_cap, fa_scratch, fa_srcs, fa_want, b_seq_off, b_seqs, b_seq_src;
   // the streamed -S DP (ksw_kernels.hip): per-bin descriptors, per-problem DP results, leftovers, counters, group

@@ -10,6 +10,8 @@
 //   --sort        : the runner leaves every bundle's records in HBM (BR_OUT_RESIDENT) and adds them to a br_sorter; after the last
 //                   bundle the sorted pieces take the same way out (br_device_bam_download -> writer); --write-index: the writer
 //                   notes the blocks it writes and br_sorter_index builds <out>.bai from them
+//   --quant       : the runner hands every bundle's rows, where the projection left them in HBM, to a br_quant (br_quant_add_last);
+//                   after the last bundle: classes, EM, one download, and the two text files formatted here
 #include <ctype.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -38,7 +40,8 @@ void usage(FILE *f) {
           " [--max-soft-clip N] [--max-junction-insertion N] [--max-junction-deletion N]\n"
           " [--max-error-exon N] [--similarity-threshold X]\n"
           " [--device-deflate | --host-deflate | --compression-level 0-9] [--device-reader | --host-reader] [--bundle-size N]\n"
-          "               [--device N | --devices a,b,...] [--collate] [--sort [--write-index]]\n\n"
+          "               [--device N | --devices a,b,...] [--collate] [--sort [--write-index]]\n"
+          "               [--quant <quant.tsv> [--quant-classes <eq_classes.txt>] [--quant-length-norm | --quant-no-length-norm]]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -54,7 +57,13 @@ void usage(FILE *f) {
           "--sort: the output is sorted by coordinate (transcript, position, forward strand first; ties keep the order of the unsorted\n"
           "output) and its header says @HD SO:coordinate; the projected records of the whole run are kept in one device's memory and\n"
           "sorted there.  --write-index: with --sort and BAM output to a file, also write <out>.bai, built on the GPU (device deflate only).\n"
-          "A run with --sort prints one more line in front of the final report, which is unchanged: [bramble] sorted N records by coordinate ...\n");
+          "A run with --sort prints one more line in front of the final report, which is unchanged: [bramble] sorted N records by coordinate ...\n"
+          "--quant FILE: the projected records of the whole run are reduced, on one GPU, to equivalence classes (the set of transcripts a\n"
+          "read name was projected to; both mates count) and per-transcript abundances are estimated from them by EM; FILE gets one line\n"
+          "per @SQ transcript: Name, Length, NumReads, TPM, UniqueReads, AmbigReads.  --quant-classes FILE: the classes in the layout of\n"
+          "salmon's eq_classes.txt.  Reads are weighted by 1 / transcript length in the short-read preset and not under --lr / --lr-hq;\n"
+          "--quant-length-norm / --quant-no-length-norm say otherwise.  No fragment-length or bias model, no bootstraps.  One more line\n"
+          "in front of the final report: [bramble] quantified N read names in C classes ...\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -105,6 +114,10 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (a == "--collate") o.collate = true;
     else if (a == "--sort") o.sort = true;
     else if (a == "--write-index") o.write_index = true;
+    else if (a == "--quant") { const char *v = value(); if (!v) return -1; o.quant = v; }
+    else if (a == "--quant-classes") { const char *v = value(); if (!v) return -1; o.quant_classes = v; }
+    else if (a == "--quant-length-norm") o.quant_length_norm = 1;
+    else if (a == "--quant-no-length-norm") o.quant_length_norm = 0;
     else if (a == "--device") { const char *v = value(); if (!v) return -1; o.devices.assign(1, atoi(v)); }
     else if (a == "--devices") {
       const char *v = value(); if (!v) return -1;
@@ -123,6 +136,8 @@ int parse_args(int argc, char **argv, Options &o) {
   if (o.sam_out && codec) { fprintf(stderr, "--compression-level, --host-deflate and --device-deflate apply to BAM output, not to --output-fmt sam\n"); return -1; }
   if (o.collate && o.devices.size() > 1) { fprintf(stderr, "--collate works on one device: give --device N, not a --devices list\n"); return -1; }
   if (o.sort && o.devices.size() > 1) { fprintf(stderr, "--sort works on one device: give --device N, not a --devices list\n"); return -1; }
+  if (!o.quant.empty() && o.devices.size() > 1) { fprintf(stderr, "--quant works on one device: give --device N, not a --devices list\n"); return -1; }
+  if (o.quant.empty() && (!o.quant_classes.empty() || o.quant_length_norm >= 0)) { fprintf(stderr, "--quant-classes, --quant-length-norm and --quant-no-length-norm need --quant\n"); return -1; }
   if (o.write_index && !o.sort) { fprintf(stderr, "--write-index needs --sort: a BAI index describes a coordinate-sorted file\n"); return -1; }
   if (o.write_index && o.sam_out) { fprintf(stderr, "--write-index applies to BAM output, not to --output-fmt sam\n"); return -1; }
   if (o.write_index && o.out_bam == "-") { fprintf(stderr, "--write-index needs an output file, not standard output\n"); return -1; }
@@ -270,6 +285,10 @@ struct Run {
   const Options &o; Input &in; Outbox &out; BgzfWriter &wr;
   const std::vector<int32_t> &ref_map; std::vector<std::unique_ptr<Worker>> &workers;
   br_sorter *sorter = nullptr;   // --sort: the runner's records go here; drain_sorted() writes them once the input is through
+  br_quant *quant = nullptr;     // --quant: deliver() adds every bundle's rows; quantify() runs once the input is through
+  int64_t q_names = 0, q_classes = 0; int32_t q_iters = 0;
+  double t_q_add = 0, t_q_finish = 0, t_q_em = 0;
+  std::vector<double> q_theta, q_tpm; std::vector<uint64_t> q_unique, q_ambig, q_label_off, q_counts; std::vector<uint32_t> q_labels;
   bool track_blocks = false;     // --write-index: the writer notes where every BGZF block of the record section starts
   std::vector<br_bgzf_span> spans;
   uint64_t stream_pos = 0;       // uncompressed record bytes written so far
@@ -290,6 +309,7 @@ struct Run {
       } else w->runner = std::thread([this, w] { run_resident(w, *in.dev_queue((size_t)w->id)); });   // (the bundles are in its HBM already)
     }
     for (auto &w : workers) { if (w->uploader.joinable()) w->uploader.join(); if (w->runner.joinable()) w->runner.join(); }
+    if (quant && !fail) quantify(workers[0].get());
     if (sorter && !fail) { in.join(); drain_sorted(workers[0].get()); }   // (the source's last sequence number is final after join)
     out.finish();
     in.join(); writer.join();
@@ -360,6 +380,26 @@ struct Run {
     (void)br_sorter_stats(sorter, nullptr, nullptr, &t_sort_add, &t_sort_finish, nullptr);
     if (rc) { fprintf(stderr, "error: sorting failed on device %d: %s\n", w->device, br_strerror(rc)); raise_fail(); }
   }
+  // --quant, after the last bundle: classes, EM, and everything the two files need in one download
+  void quantify(Worker *w) {
+    auto t0 = now();
+    int rc = br_quant_finish(quant, &q_names, &q_classes);
+    if (!rc) rc = br_quant_em(quant, &q_iters, nullptr);
+    if (!rc) {
+      const size_t nt = br_index_num_transcripts(w->ix);
+      q_theta.resize(nt + 1); q_tpm.resize(nt + 1); q_unique.resize(nt + 1); q_ambig.resize(nt + 1);
+      rc = br_quant_result(quant, q_theta.data(), q_tpm.data(), q_unique.data(), q_ambig.data());
+    }
+    if (!rc && !o.quant_classes.empty()) {
+      int64_t n_labels = 0;
+      rc = br_quant_stats(quant, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n_labels);
+      q_label_off.resize((size_t)q_classes + 1); q_counts.resize((size_t)q_classes + 1); q_labels.resize((size_t)n_labels + 1);
+      if (!rc) rc = br_quant_classes(quant, q_label_off.data(), q_labels.data(), q_counts.data(), nullptr);
+    }
+    w->gpu_seconds += secs(t0, now());
+    (void)br_quant_stats(quant, nullptr, nullptr, &t_q_add, &t_q_finish, &t_q_em, nullptr, nullptr, nullptr);
+    if (rc) { fprintf(stderr, "error: quantification failed on device %d: %s\n", w->device, br_strerror(rc)); raise_fail(); }
+  }
   br_bam_bundle args(Bundle &b) const {
     return br_bam_bundle{b.blob.data(), b.blob.size(), b.off.data(), b.len.data(), (int64_t)b.off.size(), ref_map.data(), (int32_t)ref_map.size(), out_mode()};
   }
@@ -381,6 +421,10 @@ struct Run {
   void deliver(Worker *w, uint64_t seq, const br_host_bam &hb) {
     if (fail) return;
     w->total_complete += hb.total_complete; w->total_unique += hb.total_unique; w->dropped += hb.dropped_reads; w->n_bundles++;
+    if (quant) {   // the bundle's rows are still where the projection left them: the context's next call comes after this one
+      const int qrc = br_quant_add_last(quant, w->ctx);
+      if (qrc) { fprintf(stderr, "error: the quantifier could not take a bundle on device %d: %s\n", w->device, br_strerror(qrc)); raise_fail(); return; }
+    }
     if (sorter) {   // the records stay in HBM: into the sorter (the runner sees the bundles in order), nothing for the writer yet
       br_device_bam db;
       int src = br_ctx_last_device_bam(w->ctx, &db);
@@ -477,9 +521,12 @@ extern "C" int br_cli_main(int argc, char **argv) {
   // the input is already being read while the guides are parsed and the indexes are built
   std::vector<std::unique_ptr<Worker>> workers;
   br_sorter *sorter = nullptr;
+  br_quant *quant = nullptr;
   auto free_all = [&]() {
     if (sorter) br_sorter_free(sorter);
     sorter = nullptr;
+    if (quant) br_quant_free(quant);
+    quant = nullptr;
     for (auto &w : workers) { if (w->ctx) br_ctx_free(w->ctx); if (w->ix) br_index_free(w->ix); w->ctx = nullptr; w->ix = nullptr; }
     if (ann) br_annotation_free(ann);
     ann = nullptr;
@@ -542,6 +589,17 @@ extern "C" int br_cli_main(int argc, char **argv) {
     int src = br_sorter_new(o.devices[0], &sorter);
     if (src) { fprintf(stderr, "error: sorter on device %d: %s\n", o.devices[0], br_strerror(src)); return give_up(); }
   }
+  // --quant: tid = the index's transcript, its line in the files = the @SQ list's (transcripts of length > 0)
+  std::vector<int64_t> tx_len;
+  if (!o.quant.empty()) {
+    const size_t nt = br_index_num_transcripts(ix0);
+    tx_len.resize(nt);
+    for (size_t t = 0; t < nt; t++) tx_len[t] = br_index_transcript_len(ix0, (uint32_t)t);
+    int qrc = br_quant_new(o.devices[0], (int64_t)nt, tx_len.data(), &quant);
+    const int norm = o.quant_length_norm >= 0 ? o.quant_length_norm : (o.cfg.lr || o.cfg.lr_hq) ? 0 : 1;   // (oarfish does not length-normalise long reads)
+    if (!qrc) qrc = br_quant_set_param(quant, "length_norm", norm);
+    if (qrc) { fprintf(stderr, "error: quantifier on device %d: %s\n", o.devices[0], br_strerror(qrc)); return give_up(); }
+  }
   OutFile file(o.out_bam);
   if (!file.wr.open(file.tmp.c_str(), o.threads, o.level, !o.sam_out)) { fprintf(stderr, "error: %s\n", file.wr.error().c_str()); return give_up(); }
   {
@@ -554,7 +612,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
   if (!o.quiet) printf("[bramble] processing alignments :-)\n");
   double t_setup = since();
   Run run{o, *in, out, file.wr, ref_map, workers};
-  run.sorter = sorter; run.track_blocks = o.write_index;
+  run.sorter = sorter; run.track_blocks = o.write_index; run.quant = quant;
   run.go();
   int failed = run.fail.load();
   if (!in->err.empty()) { fprintf(stderr, in->err_at_line ? "error: %s:%s\n" : "error: %s: %s\n", o.in_bam.c_str(), in->err.c_str()); failed = 1; }
@@ -572,12 +630,57 @@ extern "C" int br_cli_main(int argc, char **argv) {
       br_free_buffer(bai);
     }
   }
+  // the quantifier's files take the output's route as well
+  const std::string q_tmp = o.quant + ".tmp-bramble", qc_tmp = o.quant_classes + ".tmp-bramble";
+  if (!failed && quant) {
+    const size_t nt = tx_len.size();
+    std::vector<int64_t> sq_of(nt, -1);
+    int64_t nsq = 0;
+    for (size_t t = 0; t < nt; t++) if (tx_len[t] > 0) sq_of[t] = nsq++;
+    auto close_ok = [&](FILE *f, const std::string &p) {
+      const bool bad = !f || ferror(f);
+      if (f && fclose(f) != 0) { fprintf(stderr, "error: could not write %s\n", p.c_str()); return false; }
+      if (bad) fprintf(stderr, "error: could not write %s\n", p.c_str());
+      return !bad;
+    };
+    FILE *f = fopen(q_tmp.c_str(), "w");
+    if (f) {
+      fprintf(f, "Name\tLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\n");
+      for (size_t t = 0; t < nt; t++)
+        if (tx_len[t] > 0) fprintf(f, "%s\t%lld\t%.6f\t%.6f\t%llu\t%llu\n", br_index_transcript_name(ix0, (uint32_t)t), (long long)tx_len[t], run.q_theta[t], run.q_tpm[t],
+                                   (unsigned long long)run.q_unique[t], (unsigned long long)run.q_ambig[t]);
+    }
+    if (!close_ok(f, q_tmp)) failed = 1;
+    if (!failed && !o.quant_classes.empty()) {
+      f = fopen(qc_tmp.c_str(), "w");
+      if (f) {
+        fprintf(f, "%lld\n%lld\n", (long long)nsq, (long long)run.q_classes);
+        for (size_t t = 0; t < nt; t++) if (tx_len[t] > 0) fprintf(f, "%s\n", br_index_transcript_name(ix0, (uint32_t)t));
+        for (int64_t c = 0; c < run.q_classes; c++) {
+          fprintf(f, "%llu", (unsigned long long)(run.q_label_off[(size_t)c + 1] - run.q_label_off[(size_t)c]));
+          for (uint64_t e = run.q_label_off[(size_t)c]; e < run.q_label_off[(size_t)c + 1]; e++) fprintf(f, "\t%lld", (long long)sq_of[run.q_labels[(size_t)e]]);
+          fprintf(f, "\t%llu\n", (unsigned long long)run.q_counts[(size_t)c]);
+        }
+      }
+      if (!close_ok(f, qc_tmp)) failed = 1;
+    }
+  }
   if (!file.finish(!failed)) failed = 1;
+  if (quant) {
+    auto settle = [&](const std::string &tmp, const std::string &path) {
+      if (path.empty()) return;
+      if (failed) remove(tmp.c_str());
+      else if (rename(tmp.c_str(), path.c_str()) != 0) { fprintf(stderr, "error: could not rename %s to %s\n", tmp.c_str(), path.c_str()); failed = 1; }
+    };
+    settle(q_tmp, o.quant); settle(qc_tmp, o.quant_classes);
+    if (failed) { remove(q_tmp.c_str()); if (!o.quant_classes.empty()) remove(qc_tmp.c_str()); }
+  }
   if (o.write_index) {
     if (failed) remove(bai_tmp.c_str());
     else if (rename(bai_tmp.c_str(), bai_path.c_str()) != 0) { fprintf(stderr, "error: could not rename %s to %s\n", bai_tmp.c_str(), bai_path.c_str()); failed = 1; }
   }
   if (!o.quiet && o.sort && !failed) printf("[bramble] sorted %lld records by coordinate on device %d (add %.2fs, sort %.2fs)%s\n", (long long)run.sorted_records, o.devices[0], run.t_sort_add, run.t_sort_finish, o.write_index ? ", index written" : "");
+  if (!o.quiet && quant && !failed) printf("[bramble] quantified %lld read names in %lld classes (%d iterations, add %.2fs, classes %.2fs, EM %.2fs)\n", (long long)run.q_names, (long long)run.q_classes, (int)run.q_iters, run.t_q_add, run.t_q_finish, run.t_q_em);
   double t_done = since();
   uint64_t total_complete = 0, total_unique = 0, dropped = 0, n_bundles = 0;
   double gpu_seconds = 0, t_upload = 0, t_wait_gpu_in = 0;

@@ -36,6 +36,8 @@ struct Options {
   bool collate = false;          // --collate: the whole input is read into one device's memory and regrouped by read name first
   bool sort = false;             // --sort: the projected records stay in one device's memory and are written in coordinate order
   bool write_index = false;      // --write-index: <out>.bai beside the sorted BAM, built on the GPU
+  std::string quant, quant_classes;   // --quant FILE / --quant-classes FILE: per-transcript abundances and the equivalence classes (br_quant)
+  int quant_length_norm = -1;    // -1: on for the short-read preset, off under --lr / --lr-hq; --quant-length-norm / --quant-no-length-norm
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };
 inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }

@@ -784,7 +784,7 @@ static int run_match_table(br_ctx *c, const DevCfg &dc, const br_device_batch *b
 
 // The HIP pipeline over a device-resident batch: small and speculative batches (run_device_small), direct rows
 // (run_device_direct), or the match table (run_match_table: presets with the similarity filter, -S, direct_rows = 0).
-int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStream_t st, br_device_rows *out, bool keep_events) {
+static int run_device_paths(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStream_t st, br_device_rows *out, bool keep_events) {
   const br_index *ix = c->ix;
   memset(out, 0, sizeof(*out));
   DevCfg dc;
@@ -816,6 +816,13 @@ int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStr
 
   if (!fa_mode && !dc.filter_by_similarity && c->direct_rows) return run_device_direct(c, dc, b, st, out, pf, keep_events);
   return run_match_table(c, dc, b, st, out, pf, keep_events);
+}
+
+int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStream_t st, br_device_rows *out, bool keep_events) {
+  c->last_rows = br_device_rows{}; c->last_group_off = nullptr; c->last_n_groups = 0; c->last_stream = st;
+  RC(run_device_paths(c, cfg, b, st, out, keep_events));
+  if (out->row_off) { c->last_rows = *out; c->last_group_off = b->group_off; c->last_n_groups = b->n_groups; }   // (no rows table: an empty batch)
+  return BR_OK;
 }
 
 // br_row_x of the last call's rows, derived on first request (k_rows_detail)

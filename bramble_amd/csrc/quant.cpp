@@ -1,0 +1,471 @@
+// br_quant: the read names of a whole run reduced to equivalence classes in one device's HBM, and the EM over them
+// (quant_kernels.hip).
+//
+//   add      per read name (a read-name group of the projected batch) the ascending list of the distinct transcript ids of its rows,
+//            written into the label arena at the slot of the name's first row -- the rows' offsets are the placement, a product
+//            of the projection's own scan -- with its length and a 64-bit hash of (labels, k)
+//   finish   the names with labels, compacted -> stable LSD radix sort of (hash & mask, name index) with the collator's passes ->
+//            class heads by comparing the label lists of neighbours; a run of equal hashes that holds different lists is ordered
+//            on the device by (k, labels, name index) and the heads are found again, so the result is exact at any hash_bits ->
+//            counts from the scanned heads -> a second sort of the classes by their first name index -> label_off (a scan), labels
+//            -> radix sort of (transcript, label entry): the transposed table, per transcript its classes in ascending order ->
+//            classes of more than 64 labels and transcripts in more than 64 classes listed (a wave each in the EM) -> unique /
+//            ambiguous names per transcript
+//   em       per iteration a class kernel (q_c = n_c / sum over its labels of theta_t w_t) and a transcript kernel (theta'_t =
+//            theta_t w_t * sum of q_c over the transcript's classes, gathered through the transposed table); every 16th iteration
+//            and the last the transcript kernel also leaves the largest relative change in one word, which the host reads
+//
+// Device memory (N names, of them M with labels; R rows added; C classes; L labels over all classes; T transcripts):
+//   while adding   4 R (the arena: a slot per row) + 20 N (offset, k, hash) + 4 bytes a name of the largest add (the list of its
+//                  names of many rows); while the tables grow, the old one beside the new
+//   finish         adds 8 N (the compaction's scan, freed before the sort), then 32 M (keys 2 x 8, indices 2 x 4, heads 8; 4 M more
+//                  for the run marks when hashes collide) and the radix histograms (2 KiB a tile of 2048), 32 C (class starts 8, the
+//                  second sort 2 x 8 + 2 x 4), then -- the arena, the name tables and the sort's buffers freed -- 32 L (class of an
+//                  entry 4, (transcript, entry) keys 2 x 8 and indices 2 x 4) beside what stays
+//   afterwards     24 C (first name, count, label_off) + 8 L (labels, the transposed table's classes) + 24 T (the table's offsets,
+//                  unique, ambiguous) + 4 bytes per listed class / transcript
+//   em             adds 40 T (theta and theta w twice, w) + 8 C (q)
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "collate_kernels.h"
+#include "ctx.h"
+#include "quant_kernels.h"
+#include "sam_kernels.h"
+
+using namespace br;
+
+struct br_quant {
+  int device = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t ev = nullptr;
+  int64_t n_tx = 0;
+  std::vector<int64_t> lens;   // empty: no lengths were given
+  int hash_bits = 64, length_norm = 1;
+  int64_t max_iters = 10000;
+  double tolerance = 1e-2;
+  bool finished = false, em_done = false;
+  int64_t n = 0;               // names added
+  uint64_t rows = 0;           // arena slots in use
+  int64_t n_assigned = 0, n_cls = 0, n_lab = 0;
+  uint32_t n_big_cls = 0, n_big_tx = 0;
+  uint64_t collisions = 0;
+  uint64_t live = 0, peak = 0;
+  double add_s = 0, finish_s = 0, em_s = 0;
+  ColBuf lab, noff, nk, hash, big;                       // add
+  ColBuf c_first, c_cnt, c_loff, c_labels, t_cls, t_off, uniq, ambig, big_cls, big_tx;   // after finish
+  ColBuf theta[2], x[2], w, qv;                          // em
+  int cur = 0;
+  ColBuf tmp, small;
+  int alloc(ColBuf &b, size_t bytes, bool keep = false) {
+    if (bytes <= b.cap) return BR_OK;
+    void *p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? BR_ERR_CAPACITY : BR_ERR_HIP; }
+    live += bytes; peak = std::max(peak, live);
+    if (keep && b.p) HIPCHK(hipMemcpyAsync(p, b.p, b.cap, hipMemcpyDeviceToDevice, st));
+    if (b.p) { HIPCHK(hipStreamSynchronize(st)); live -= b.cap; b.release(); }
+    b.p = p; b.cap = bytes;
+    return BR_OK;
+  }
+  void drop(ColBuf &b) { live -= b.cap; b.release(); }
+};
+// words of `small`
+enum { QS_BITS = 0, QS_COLL = 2, QS_SPAN = 3, QS_NBIG = 5, QS_MAXTID = 6, QS_BAD = 7, QS_REL = 8, QS_NBIG_CLS = 9, QS_NBIG_TX = 10, QS_WORDS = 16 };
+
+// device tables of one call: whatever the outcome, they go (and leave the byte count) when the call returns
+struct QuantDrop {
+  br_quant *c; std::vector<ColBuf *> b;
+  ~QuantDrop() { for (auto *x : b) c->drop(*x); }
+};
+
+extern "C" void br_quant_free(br_quant *c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  if (c->st) (void)hipStreamSynchronize(c->st);
+  if (c->ev) (void)hipEventDestroy(c->ev);
+  if (c->st) (void)hipStreamDestroy(c->st);
+  delete c;
+}
+
+extern "C" int br_quant_new(int device, int64_t n_transcripts, const int64_t *lengths, br_quant **out) {
+  if (!out) return BR_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (n_transcripts < 0 || n_transcripts >= (1ll << 32)) return BR_ERR_INVALID_ARG;
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0 || device < 0 || device >= nd) { (void)hipGetLastError(); return BR_ERR_NO_DEVICE; }
+  HIPCHK(hipSetDevice(device));
+  br_quant *c = new br_quant();
+  c->device = device; c->n_tx = n_transcripts;
+  if (lengths) c->lens.assign(lengths, lengths + n_transcripts);
+  int rc = hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) == hipSuccess ? BR_OK : BR_ERR_HIP;
+  if (!rc) rc = c->alloc(c->small, QS_WORDS * 8);
+  if (!rc && (hipMemsetAsync(c->small.p, 0, QS_WORDS * 8, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) rc = BR_ERR_HIP;
+  if (rc) { br_quant_free(c); return rc; }
+  *out = c;
+  return BR_OK;
+}
+
+extern "C" int br_quant_set_param(br_quant *c, const char *name, int64_t value) {
+  if (!c || !name || c->finished) return BR_ERR_INVALID_ARG;
+  if (!strcmp(name, "hash_bits")) { if (value < 1 || value > 64) return BR_ERR_INVALID_ARG; c->hash_bits = (int)value; return BR_OK; }
+  if (!strcmp(name, "length_norm")) { if (value != 0 && value != 1) return BR_ERR_INVALID_ARG; c->length_norm = (int)value; return BR_OK; }
+  if (!strcmp(name, "max_iters")) { if (value < 1) return BR_ERR_INVALID_ARG; c->max_iters = value; return BR_OK; }
+  if (!strcmp(name, "tolerance_ppm")) { if (value < 0) return BR_ERR_INVALID_ARG; c->tolerance = (double)value * 1e-6; return BR_OK; }
+  return BR_ERR_INVALID_ARG;
+}
+extern "C" int br_quant_set_tolerance(br_quant *c, double tolerance) {
+  if (!c || c->finished || !(tolerance >= 0.0)) return BR_ERR_INVALID_ARG;
+  c->tolerance = tolerance;
+  return BR_OK;
+}
+
+// room for m more names whose rows number `rows`
+static int quant_reserve(br_quant *c, int64_t m, uint64_t rows) {
+  if ((uint64_t)(c->n + m) >= (1ull << 32)) return BR_ERR_CAPACITY;   // (32-bit radix indices)
+  const size_t need = (size_t)(c->rows + rows) + 1;
+  if (need * 4 > c->lab.cap) RC(c->alloc(c->lab, std::max(need, (size_t)(c->lab.cap / 4) * 3 / 2) * 4, true));
+  const size_t nn = (size_t)(c->n + m) + 1;
+  if (nn * 8 > c->noff.cap) {
+    const size_t want = std::max(nn, (size_t)(c->noff.cap / 8) * 3 / 2);
+    RC(c->alloc(c->noff, want * 8, true)); RC(c->alloc(c->hash, want * 8, true)); RC(c->alloc(c->nk, want * 4, true));
+  }
+  RC(c->alloc(c->big, (size_t)(m + 1) * 4));   // (the list of the names of many rows: no longer than the names)
+  return BR_OK;
+}
+
+// the names of one add, their tables on the device (A: a, row_off, group_off, the biases, r_first, r_last and n_groups are set)
+static int quant_add_names(br_quant *c, QAddArgs A) {
+  hipStream_t st = c->st;
+  RC(quant_reserve(c, A.n_groups, A.r_last - A.r_first));
+  uint64_t *small = c->small.as<uint64_t>();
+  HIPCHK(hipMemsetAsync(small + QS_NBIG, 0, 8, st)); HIPCHK(hipMemsetAsync(small + QS_BAD, 0, 8, st));
+  A.lab_base = c->rows; A.lab = c->lab.as<uint32_t>();
+  A.noff = c->noff.as<uint64_t>() + c->n; A.nk = c->nk.as<uint32_t>() + c->n; A.hash = c->hash.as<uint64_t>() + c->n;
+  A.big = c->big.as<uint32_t>(); A.n_big = (uint32_t *)(small + QS_NBIG);
+  A.max_tid = (uint32_t *)(small + QS_MAXTID); A.bad = (uint32_t *)(small + QS_BAD);
+  launch_q_names(st, A);
+  uint32_t bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, small + QS_BAD, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));   // the caller's rows may be reused now
+  if (bad) return BR_ERR_INVALID_ARG;   // offsets that descend somewhere: nothing was added
+  c->rows += A.r_last - A.r_first; c->n += A.n_groups;
+  return BR_OK;
+}
+
+static int quant_add_device(br_quant *c, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t ng, hipStream_t caller) {
+  hipStream_t st = c->st;
+  HIPCHK(hipEventRecord(c->ev, caller)); HIPCHK(hipStreamWaitEvent(st, c->ev, 0));   // after whatever made the rows (NULL: the null stream's work)
+  uint64_t *small = c->small.as<uint64_t>();
+  launch_q_span(st, row_off, group_off, ng, small + QS_SPAN);
+  uint64_t span[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(span, small + QS_SPAN, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (span[1] < span[0]) return BR_ERR_INVALID_ARG;
+  QAddArgs A{};
+  A.a = (const uint4 *)a; A.row_off = row_off; A.group_off = group_off; A.n_groups = ng; A.r_first = span[0]; A.r_last = span[1];
+  return quant_add_names(c, A);
+}
+
+static int quant_add_host(br_quant *c, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t ng) {
+  const uint32_t a0 = group_off[0], a1 = group_off[ng];
+  for (int64_t g = 0; g < ng; g++) if (group_off[g + 1] < group_off[g]) return BR_ERR_INVALID_ARG;
+  for (uint32_t i = a0; i < a1; i++) if (row_off[i + 1] < row_off[i]) return BR_ERR_INVALID_ARG;
+  const uint64_t r0 = row_off[a0], r1 = row_off[a1];
+  ColBuf d_a, d_ro, d_go;
+  QuantDrop dropper{c, {&d_a, &d_ro, &d_go}};
+  RC(c->alloc(d_a, (size_t)(r1 - r0 + 1) * sizeof(br_row_a))); RC(c->alloc(d_ro, (size_t)(a1 - a0 + 1) * 8)); RC(c->alloc(d_go, (size_t)(ng + 1) * 4));
+  hipStream_t st = c->st;
+  if (r1 > r0) HIPCHK(hipMemcpyAsync(d_a.p, a + r0, (size_t)(r1 - r0) * sizeof(br_row_a), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_ro.p, row_off + a0, (size_t)(a1 - a0 + 1) * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_go.p, group_off, (size_t)(ng + 1) * 4, hipMemcpyHostToDevice, st));
+  QAddArgs A{};
+  A.a = d_a.as<uint4>(); A.a_bias = (int64_t)r0; A.row_off = d_ro.as<uint64_t>(); A.ro_bias = (int64_t)a0;
+  A.group_off = d_go.as<uint32_t>(); A.n_groups = ng; A.r_first = r0; A.r_last = r1;
+  return quant_add_names(c, A);   // (it waits for the stream: the uploads are done when the host arrays go)
+}
+
+extern "C" int br_quant_add(br_quant *c, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t n_groups,
+                            int on_device, void *stream) {
+  if (!c || n_groups < 0 || c->finished || (n_groups && (!row_off || !group_off))) return BR_ERR_INVALID_ARG;
+  if (n_groups == 0) return BR_OK;
+  auto t0 = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(c->device));
+  const int rc = on_device ? quant_add_device(c, a, row_off, group_off, n_groups, (hipStream_t)stream) : quant_add_host(c, a, row_off, group_off, n_groups);
+  c->add_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+extern "C" int br_quant_add_last(br_quant *c, br_ctx *ctx) {
+  if (!c || !ctx || !ctx->ix || ctx->ix->device != c->device) return BR_ERR_INVALID_ARG;
+  if (ctx->last_n_groups == 0) return c->finished ? BR_ERR_INVALID_ARG : BR_OK;
+  return br_quant_add(c, ctx->last_rows.a, ctx->last_rows.row_off, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
+}
+
+// scratch of the scans (over n + 1 items or the histograms) and of the OR / AND reduction (2 words a block of 256)
+static int quant_tmp(br_quant *c, int64_t n) {
+  const int64_t blocks = (n + 255) / 256, nh = 256 * ((n + COL_TILE - 1) / COL_TILE);
+  return c->alloc(c->tmp, (size_t)std::max<int64_t>(2 * blocks + 2, std::max<int64_t>(nh, n + 1) / 1024 + 8) * 8);
+}
+// a stable LSD radix sort of (key, idx) pairs over the digits in which the keys differ; *cur = the buffer that holds the result
+static int quant_sort(br_quant *c, ColBuf key[2], ColBuf idx[2], int64_t n, int *cur) {
+  hipStream_t st = c->st;
+  uint64_t *small = c->small.as<uint64_t>();
+  *cur = 0;
+  if (n <= 0) return BR_OK;
+  RC(quant_tmp(c, n));
+  launch_q_bits(st, key[0].as<uint64_t>(), n, c->tmp.as<uint64_t>(), small + QS_BITS);
+  uint64_t bits[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(bits, small + QS_BITS, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const int64_t tiles = (n + COL_TILE - 1) / COL_TILE, nh = 256 * tiles;
+  ColBuf hist;
+  QuantDrop dropper{c, {&hist}};
+  RC(c->alloc(hist, (size_t)(nh + 1) * 8));
+  for (int shift = 0; shift < 64; shift += 8) {
+    if ((((bits[0] ^ bits[1]) >> shift) & 255u) == 0) continue;   // the digit is the same in every key
+    launch_col_radix_pass(st, key[*cur].as<uint64_t>(), idx[*cur].as<uint32_t>(), key[*cur ^ 1].as<uint64_t>(), idx[*cur ^ 1].as<uint32_t>(),
+                          n, shift, hist.as<uint64_t>(), c->tmp.as<uint64_t>());
+    *cur ^= 1;
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return BR_OK;
+}
+
+static int quant_finish(br_quant *c) {
+  hipStream_t st = c->st;
+  const int64_t N = c->n, T = c->n_tx;
+  uint64_t *small = c->small.as<uint64_t>();
+  RC(c->alloc(c->t_off, (size_t)(T + 2) * 8)); RC(c->alloc(c->uniq, (size_t)(T + 1) * 8)); RC(c->alloc(c->ambig, (size_t)(T + 1) * 8));
+  HIPCHK(hipMemsetAsync(c->t_off.p, 0, (size_t)(T + 2) * 8, st));
+  HIPCHK(hipMemsetAsync(c->uniq.p, 0, (size_t)(T + 1) * 8, st)); HIPCHK(hipMemsetAsync(c->ambig.p, 0, (size_t)(T + 1) * 8, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (N == 0) return BR_OK;
+  // the names with labels
+  uint64_t M = 0;
+  ColBuf key[2], idx[2], head, mark, gbeg, key2[2], val2[2];
+  QuantDrop sort_bufs{c, {&key[0], &key[1], &idx[0], &idx[1], &head, &mark, &gbeg, &key2[0], &key2[1], &val2[0], &val2[1]}};
+  {
+    ColBuf pos;
+    QuantDrop dropper{c, {&pos}};
+    RC(c->alloc(pos, (size_t)(N + 1) * 8)); RC(quant_tmp(c, N));
+    launch_q_flag(st, c->nk.as<uint32_t>(), N, pos.as<uint64_t>());
+    launch_sam_scan(st, pos.as<uint64_t>(), N, c->tmp.as<uint64_t>());
+    uint32_t max_tid = 0;
+    HIPCHK(hipMemcpyAsync(&M, pos.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&max_tid, small + QS_MAXTID, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    c->n_assigned = (int64_t)M;
+    if (M == 0) return BR_OK;
+    if ((int64_t)max_tid >= T) return BR_ERR_INVALID_ARG;   // a transcript id the quantifier has no transcript for
+    const size_t m1 = (size_t)M + 1;
+    RC(c->alloc(key[0], m1 * 8)); RC(c->alloc(key[1], m1 * 8)); RC(c->alloc(idx[0], m1 * 4)); RC(c->alloc(idx[1], m1 * 4));
+    const uint64_t mask = c->hash_bits >= 64 ? ~0ull : (1ull << c->hash_bits) - 1;
+    launch_q_compact(st, c->nk.as<uint32_t>(), c->hash.as<uint64_t>(), pos.as<uint64_t>(), N, mask, key[0].as<uint64_t>(), idx[0].as<uint32_t>());
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  const int64_t m = (int64_t)M;
+  int cur = 0;
+  RC(quant_sort(c, key, idx, m, &cur));
+  // class heads; runs of equal hashes with different lists are put in order and the heads found again
+  const uint32_t *lab = c->lab.as<uint32_t>(), *nk = c->nk.as<uint32_t>();
+  const uint64_t *noff = c->noff.as<uint64_t>();
+  RC(c->alloc(head, (size_t)(m + 1) * 8));
+  auto heads = [&](uint32_t *mk, uint64_t *n_coll) -> int {
+    HIPCHK(hipMemsetAsync(small + QS_COLL, 0, 8, st));
+    launch_q_heads(st, lab, noff, nk, key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), m, head.as<uint64_t>(), (unsigned long long *)(small + QS_COLL), mk);
+    HIPCHK(hipMemcpyAsync(n_coll, small + QS_COLL, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return BR_OK;
+  };
+  uint64_t n_coll = 0;
+  RC(heads(nullptr, &n_coll));
+  c->collisions = n_coll;
+  if (n_coll) {
+    RC(c->alloc(mark, (size_t)m * 4));
+    HIPCHK(hipMemsetAsync(mark.p, 0, (size_t)m * 4, st));
+    RC(heads(mark.as<uint32_t>(), &n_coll));
+    launch_q_resolve(st, lab, noff, nk, key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), m, mark.as<uint32_t>(), key[cur ^ 1].as<uint64_t>(), idx[cur ^ 1].as<uint32_t>());
+    cur ^= 1;
+    RC(heads(nullptr, &n_coll));
+  }
+  RC(quant_tmp(c, m));
+  launch_sam_scan(st, head.as<uint64_t>(), m, c->tmp.as<uint64_t>());   // head -> class ids (exclusive), head[m] = C
+  uint64_t C = 0;
+  HIPCHK(hipMemcpyAsync(&C, head.as<uint64_t>() + m, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (C == 0 || C > (uint64_t)m) return BR_ERR_HIP;
+  c->n_cls = (int64_t)C;
+  const size_t c1 = (size_t)C + 1;
+  RC(c->alloc(gbeg, c1 * 8));
+  launch_col_gbeg(st, head.as<uint64_t>(), m, gbeg.as<uint64_t>());
+  // the classes by their first name
+  RC(c->alloc(key2[0], c1 * 8)); RC(c->alloc(key2[1], c1 * 8)); RC(c->alloc(val2[0], c1 * 4)); RC(c->alloc(val2[1], c1 * 4));
+  launch_q_class_key(st, gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), (int64_t)C, key2[0].as<uint64_t>(), val2[0].as<uint32_t>());
+  int cur2 = 0;
+  RC(quant_sort(c, key2, val2, (int64_t)C, &cur2));
+  RC(c->alloc(c->c_first, c1 * 8)); RC(c->alloc(c->c_cnt, c1 * 8)); RC(c->alloc(c->c_loff, c1 * 8));
+  launch_q_class_fill(st, key2[cur2].as<uint64_t>(), val2[cur2].as<uint32_t>(), gbeg.as<uint64_t>(), nk, (int64_t)C, c->c_first.as<uint64_t>(),
+                      c->c_cnt.as<uint64_t>(), c->c_loff.as<uint64_t>());
+  RC(quant_tmp(c, (int64_t)C));
+  launch_sam_scan(st, c->c_loff.as<uint64_t>(), (int64_t)C, c->tmp.as<uint64_t>());
+  uint64_t L = 0;
+  HIPCHK(hipMemcpyAsync(&L, c->c_loff.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (L >= (1ull << 32)) return BR_ERR_CAPACITY;   // (32-bit radix indices)
+  c->n_lab = (int64_t)L;
+  for (auto *b : sort_bufs.b) c->drop(*b);   // (dropping twice is harmless: an empty buffer counts nothing)
+  // labels and the transposed table
+  ColBuf ecls, tkey[2], tidx[2], d_lens;
+  QuantDrop table_bufs{c, {&ecls, &tkey[0], &tkey[1], &tidx[0], &tidx[1], &d_lens}};
+  const size_t l1 = (size_t)L + 1;
+  RC(c->alloc(c->c_labels, l1 * 4)); RC(c->alloc(ecls, l1 * 4)); RC(c->alloc(c->t_cls, l1 * 4));
+  RC(c->alloc(tkey[0], l1 * 8)); RC(c->alloc(tkey[1], l1 * 8)); RC(c->alloc(tidx[0], l1 * 4)); RC(c->alloc(tidx[1], l1 * 4));
+  const bool check_len = c->length_norm && !c->lens.empty();
+  if (c->length_norm && c->lens.empty()) return BR_ERR_INVALID_ARG;   // length normalisation without lengths
+  if (check_len) {
+    RC(c->alloc(d_lens, (size_t)(T + 1) * 8));
+    HIPCHK(hipMemcpyAsync(d_lens.p, c->lens.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(hipMemsetAsync(small + QS_BAD, 0, 8, st));
+  launch_q_labels(st, c->c_loff.as<uint64_t>(), c->c_first.as<uint64_t>(), noff, lab, (int64_t)C, (int64_t)L, check_len ? d_lens.as<int64_t>() : nullptr,
+                  c->c_labels.as<uint32_t>(), ecls.as<uint32_t>(), tkey[0].as<uint64_t>(), tidx[0].as<uint32_t>(), (uint32_t *)(small + QS_BAD));
+  uint32_t bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, small + QS_BAD, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (bad) return BR_ERR_INVALID_ARG;   // a transcript of length <= 0 has reads, and lengths normalise
+  c->drop(c->lab); c->drop(c->noff); c->drop(c->nk); c->drop(c->hash); c->drop(c->big);   // the names are classes now
+  int cur3 = 0;
+  RC(quant_sort(c, tkey, tidx, (int64_t)L, &cur3));
+  launch_q_transpose(st, tkey[cur3].as<uint64_t>(), tidx[cur3].as<uint32_t>(), ecls.as<uint32_t>(), (int64_t)L, T, c->t_cls.as<uint32_t>(), c->t_off.as<uint64_t>());
+  // the wave-sized items
+  const size_t most = (size_t)(L / (Q_WAVE_ITEMS + 1) + 1);
+  RC(c->alloc(c->big_cls, most * 4)); RC(c->alloc(c->big_tx, most * 4));
+  HIPCHK(hipMemsetAsync(small + QS_NBIG_CLS, 0, 16, st));
+  launch_q_bin(st, c->c_loff.as<uint64_t>(), (int64_t)C, c->big_cls.as<uint32_t>(), (uint32_t *)(small + QS_NBIG_CLS));
+  launch_q_bin(st, c->t_off.as<uint64_t>(), T, c->big_tx.as<uint32_t>(), (uint32_t *)(small + QS_NBIG_TX));
+  uint64_t nb[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(nb, small + QS_NBIG_CLS, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  c->n_big_cls = (uint32_t)nb[0]; c->n_big_tx = (uint32_t)nb[1];
+  launch_q_counts(st, c->t_cls.as<uint32_t>(), c->t_off.as<uint64_t>(), c->c_loff.as<uint64_t>(), c->c_cnt.as<uint64_t>(), T, c->big_tx.as<uint32_t>(),
+                  c->n_big_tx, c->uniq.as<uint64_t>(), c->ambig.as<uint64_t>());
+  HIPCHK(hipStreamSynchronize(st));
+  return BR_OK;
+}
+
+extern "C" int br_quant_finish(br_quant *c, int64_t *n_names, int64_t *n_classes) {
+  if (!c || c->finished) return BR_ERR_INVALID_ARG;
+  auto t0 = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(c->device));
+  RC(quant_finish(c));
+  c->finished = true;
+  c->finish_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (n_names) *n_names = c->n;
+  if (n_classes) *n_classes = c->n_cls;
+  return BR_OK;
+}
+
+extern "C" int br_quant_classes(br_quant *c, uint64_t *label_off, uint32_t *labels, uint64_t *counts, uint64_t *first_name) {
+  if (!c || !c->finished) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  const size_t C = (size_t)c->n_cls, L = (size_t)c->n_lab;
+  if (label_off) { if (C) HIPCHK(hipMemcpyAsync(label_off, c->c_loff.p, (C + 1) * 8, hipMemcpyDeviceToHost, st)); else label_off[0] = 0; }
+  if (labels && L) HIPCHK(hipMemcpyAsync(labels, c->c_labels.p, L * 4, hipMemcpyDeviceToHost, st));
+  if (counts && C) HIPCHK(hipMemcpyAsync(counts, c->c_cnt.p, C * 8, hipMemcpyDeviceToHost, st));
+  if (first_name && C) HIPCHK(hipMemcpyAsync(first_name, c->c_first.p, C * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return BR_OK;
+}
+
+static double quant_weight(const br_quant *c, int64_t t) {
+  if (!c->length_norm) return 1.0;
+  return c->lens[(size_t)t] > 0 ? 1.0 / (double)c->lens[(size_t)t] : 0.0;   // (a transcript of length <= 0 has no reads: finish saw to it)
+}
+
+extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
+  if (!c || !c->finished) return BR_ERR_INVALID_ARG;
+  auto t0 = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  const int64_t T = c->n_tx, C = c->n_cls;
+  const size_t t1 = (size_t)T + 1;
+  for (int k = 0; k < 2; k++) { RC(c->alloc(c->theta[k], t1 * 8)); RC(c->alloc(c->x[k], t1 * 8)); }
+  RC(c->alloc(c->w, t1 * 8)); RC(c->alloc(c->qv, (size_t)(C + 1) * 8));
+  std::vector<double> one((size_t)T, 1.0), w((size_t)T);
+  for (int64_t t = 0; t < T; t++) w[(size_t)t] = quant_weight(c, t);
+  if (T) {
+    HIPCHK(hipMemcpyAsync(c->theta[0].p, one.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->x[0].p, w.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));   // theta w at theta = 1
+    HIPCHK(hipMemcpyAsync(c->w.p, w.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+  }
+  QEmArgs E{};
+  E.n_cls = C; E.n_tx = T; E.label_off = c->c_loff.as<uint64_t>(); E.labels = c->c_labels.as<uint32_t>(); E.cnt = c->c_cnt.as<uint64_t>();
+  E.t_off = c->t_off.as<uint64_t>(); E.t_cls = c->t_cls.as<uint32_t>();
+  E.big_cls = c->big_cls.as<uint32_t>(); E.n_big_cls = c->n_big_cls; E.big_tx = c->big_tx.as<uint32_t>(); E.n_big_tx = c->n_big_tx;
+  E.w = c->w.as<double>(); E.q = c->qv.as<double>();
+  unsigned long long *d_rel = (unsigned long long *)(c->small.as<uint64_t>() + QS_REL);
+  int cur = 0;
+  int64_t it = 0;
+  double rel = 0.0;
+  while (it < c->max_iters) {
+    it++;
+    const bool look = it % 16 == 0 || it == c->max_iters;
+    if (look) HIPCHK(hipMemsetAsync(d_rel, 0, 8, st));
+    launch_q_em_classes(st, E, c->x[cur].as<double>());
+    launch_q_em_tx(st, E, c->theta[cur].as<double>(), c->x[cur].as<double>(), c->theta[cur ^ 1].as<double>(), c->x[cur ^ 1].as<double>(), look ? d_rel : nullptr);
+    cur ^= 1;
+    if (!look) continue;
+    uint64_t bits = 0;
+    HIPCHK(hipMemcpyAsync(&bits, d_rel, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    memcpy(&rel, &bits, 8);
+    if (rel < c->tolerance) break;
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  c->cur = cur; c->em_done = true;
+  c->em_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (n_iters) *n_iters = (int32_t)it;
+  if (rel_change) *rel_change = rel;
+  return BR_OK;
+}
+
+extern "C" int br_quant_result(br_quant *c, double *theta, double *tpm, uint64_t *unique, uint64_t *ambig) {
+  if (!c || !c->finished || ((theta || tpm) && !c->em_done)) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  const size_t T = (size_t)c->n_tx;
+  if (!T) return BR_OK;
+  std::vector<double> x;
+  if (theta) HIPCHK(hipMemcpyAsync(theta, c->theta[c->cur].p, T * 8, hipMemcpyDeviceToHost, st));
+  if (tpm) { x.resize(T); HIPCHK(hipMemcpyAsync(x.data(), c->x[c->cur].p, T * 8, hipMemcpyDeviceToHost, st)); }
+  if (unique) HIPCHK(hipMemcpyAsync(unique, c->uniq.p, T * 8, hipMemcpyDeviceToHost, st));
+  if (ambig) HIPCHK(hipMemcpyAsync(ambig, c->ambig.p, T * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (tpm) {   // one pass over T numbers, in transcript order
+    double sum = 0.0;
+    for (size_t t = 0; t < T; t++) sum += x[t];
+    for (size_t t = 0; t < T; t++) tpm[t] = sum > 0.0 ? 1e6 * x[t] / sum : 0.0;
+  }
+  return BR_OK;
+}
+
+extern "C" int br_quant_stats(const br_quant *c, uint64_t *held_bytes, uint64_t *peak_bytes, double *add_seconds, double *finish_seconds,
+                              double *em_seconds, uint64_t *collisions, int64_t *n_unassigned, int64_t *n_labels) {
+  if (!c) return BR_ERR_INVALID_ARG;
+  if (held_bytes) *held_bytes = c->live;
+  if (peak_bytes) *peak_bytes = c->peak;
+  if (add_seconds) *add_seconds = c->add_s;
+  if (finish_seconds) *finish_seconds = c->finish_s;
+  if (em_seconds) *em_seconds = c->em_s;
+  if (collisions) *collisions = c->collisions;
+  if (n_unassigned) *n_unassigned = c->finished ? c->n - c->n_assigned : 0;
+  if (n_labels) *n_labels = c->n_lab;
+  return BR_OK;
+}

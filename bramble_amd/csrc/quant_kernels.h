@@ -1,0 +1,77 @@
+// Transcript quantification on the device: read names -> transcript sets -> equivalence classes -> EM (quant_kernels.hip; host
+// side: quant.cpp, which holds the pipeline's description).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace br {
+
+constexpr int Q_SMALL_ROWS = 16;   // a read name of up to this many rows is one lane's work in k_q_names, a larger one a wave's
+constexpr int Q_WAVE_ITEMS = 64;   // a class of more labels / a transcript in more classes than this is a wave's work in the EM
+constexpr unsigned Q_BIG_GRID = 1024;   // blocks (of 4 waves) that walk a list whose length only the device knows
+
+// One add.  Rows, row_off and group_off may be slices of the caller's tables (a host add uploads only what it needs): element
+// i of the caller's table is at [i - bias] here.
+struct QAddArgs {
+  const uint4 *a; int64_t a_bias;              // br_row_a
+  const uint64_t *row_off; int64_t ro_bias;
+  const uint32_t *group_off; int64_t n_groups;
+  uint64_t r_first, r_last;   // row_off[group_off[0]], row_off[group_off[n_groups]]: the add's rows
+  uint64_t lab_base;          // arena slot of row r_first
+  uint32_t *lab;              // label arena: a name's list sits at the slot of its first row (as many slots as it has rows)
+  uint64_t *noff; uint32_t *nk; uint64_t *hash;   // per name, at the add's first name: arena offset, labels, hash of (k, labels)
+  uint32_t *big; uint32_t *n_big;   // names of more than Q_SMALL_ROWS rows: k_q_names lists them, k_q_names_big takes them
+  uint32_t *max_tid;          // the largest transcript id met so far (atomicMax)
+  uint32_t *bad;              // a name whose rows leave [r_first, r_last): nothing is written for it
+};
+// span[0] = row_off[group_off[0]], span[1] = row_off[group_off[n_groups]] of device tables
+void launch_q_span(hipStream_t st, const uint64_t *row_off, const uint32_t *group_off, int64_t n_groups, uint64_t *span);
+void launch_q_names(hipStream_t st, const QAddArgs &A);
+
+// finish: the assigned names (k > 0) in add order -> (hash & mask, name index)
+void launch_q_flag(hipStream_t st, const uint32_t *nk, int64_t n, uint64_t *flag);
+void launch_q_compact(hipStream_t st, const uint32_t *nk, const uint64_t *hash, const uint64_t *pos, int64_t n, uint64_t mask,
+                      uint64_t *key, uint32_t *idx);
+// bits[0] = OR, bits[1] = AND over key[0, n) (part: 2 words per block of 256)
+void launch_q_bits(hipStream_t st, const uint64_t *key, int64_t n, uint64_t *part, uint64_t *bits);
+// head[j] = sorted item j starts a class (its label list differs from item j - 1's); *n_coll = adjacent pairs with equal keys and
+// different lists.  mark != NULL: mark[first item of the key's run] = 1 for those pairs
+void launch_q_heads(hipStream_t st, const uint32_t *lab, const uint64_t *noff, const uint32_t *nk, const uint64_t *key,
+                    const uint32_t *idx, int64_t n, uint64_t *head, unsigned long long *n_coll, uint32_t *mark);
+// the marked runs ordered by (k, labels, name index), every other item where it was
+void launch_q_resolve(hipStream_t st, const uint32_t *lab, const uint64_t *noff, const uint32_t *nk, const uint64_t *key,
+                      const uint32_t *idx, int64_t n, const uint32_t *mark, uint64_t *key_out, uint32_t *idx_out);
+// classes in hash order -> (first name index, class in hash order), to be sorted
+void launch_q_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *idx, int64_t n_cls, uint64_t *key, uint32_t *val);
+// classes in their final order: first name, count, number of labels (to be scanned into label_off)
+void launch_q_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *nk,
+                         int64_t n_cls, uint64_t *first, uint64_t *cnt, uint64_t *label_off);
+// one thread per label entry e: labels[e], its class, (transcript, e) for the transposed table; *bad |= 1 for a transcript
+// whose length is <= 0 (lens != NULL)
+void launch_q_labels(hipStream_t st, const uint64_t *label_off, const uint64_t *first, const uint64_t *noff, const uint32_t *lab,
+                     int64_t n_cls, int64_t n_lab, const int64_t *lens, uint32_t *labels, uint32_t *ecls, uint64_t *tkey,
+                     uint32_t *tidx, uint32_t *bad);
+// the transposed table: t_cls[p] = class of the p-th (transcript, entry) pair; t_off[t] = the first pair of transcript t
+void launch_q_transpose(hipStream_t st, const uint64_t *tkey, const uint32_t *tidx, const uint32_t *ecls, int64_t n_lab,
+                        int64_t n_tx, uint32_t *t_cls, uint64_t *t_off);
+// the items of more than Q_WAVE_ITEMS entries (off: n + 1 offsets), in any order
+void launch_q_bin(hipStream_t st, const uint64_t *off, int64_t n, uint32_t *list, uint32_t *n_list);
+void launch_q_counts(hipStream_t st, const uint32_t *t_cls, const uint64_t *t_off, const uint64_t *label_off, const uint64_t *cnt,
+                     int64_t n_tx, const uint32_t *big, uint32_t n_big, uint64_t *uniq, uint64_t *ambig);
+
+// EM.  x[t] = theta[t] * w[t].  One iteration: launch_q_em_classes (q[c] = n_c / sum of x over the class, 0 when that is 0), then
+// launch_q_em_tx (theta'[t] = x[t] * sum of q over the classes of t in ascending class order; x'[t] = theta'[t] * w[t]).
+// rel != NULL: atomicMax of the bits of |theta' - theta| / theta' over theta' > 1e-8 (non-negative doubles order like their bits)
+struct QEmArgs {
+  int64_t n_cls, n_tx;
+  const uint64_t *label_off; const uint32_t *labels; const uint64_t *cnt;
+  const uint64_t *t_off; const uint32_t *t_cls;
+  const uint32_t *big_cls; uint32_t n_big_cls; const uint32_t *big_tx; uint32_t n_big_tx;
+  const double *w;
+  double *q;
+};
+void launch_q_em_classes(hipStream_t st, const QEmArgs &E, const double *x);
+void launch_q_em_tx(hipStream_t st, const QEmArgs &E, const double *theta, const double *x, double *theta_out, double *x_out,
+                    unsigned long long *rel);
+
+}  // namespace br

@@ -176,6 +176,8 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_collator_stats", "br_collator_free",
            "br_sorter_new", "br_sorter_set_param", "br_sorter_add", "br_sorter_finish", "br_sorter_next", "br_sorter_order", "br_sorter_stats",
            "br_sorter_index", "br_sorter_free", "br_ctx_last_device_bam", "br_device_bam_download",
+           "br_quant_new", "br_quant_set_param", "br_quant_set_tolerance", "br_quant_add", "br_quant_add_last", "br_quant_finish",
+           "br_quant_classes", "br_quant_em", "br_quant_result", "br_quant_stats", "br_quant_free",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -1156,6 +1158,121 @@ class Sorter:
     def close(self):
         if self.h:
             lib().br_sorter_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Quant:
+    """br_quant on `device`: read names (the rows of projected batches) in, equivalence classes and the EM's per-transcript
+    abundances out.  lengths: one per transcript (None: no length normalisation)."""
+
+    def __init__(self, n_transcripts, lengths=None, device=0):
+        L = lib()
+        L.br_quant_new.argtypes = [C.c_int, C.c_int64, C.c_void_p, _P(C.c_void_p)]
+        L.br_quant_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+        L.br_quant_set_tolerance.argtypes = [C.c_void_p, C.c_double]
+        L.br_quant_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+        L.br_quant_add_last.argtypes = [C.c_void_p, C.c_void_p]
+        L.br_quant_finish.argtypes = [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]
+        L.br_quant_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.br_quant_em.argtypes = [C.c_void_p, _P(C.c_int32), _P(C.c_double)]
+        L.br_quant_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.br_quant_stats.argtypes = [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_double),
+                                     _P(C.c_uint64), _P(C.c_int64), _P(C.c_int64)]
+        L.br_quant_free.argtypes = [C.c_void_p]
+        self.h = None
+        self.device = device
+        self.n_transcripts = int(n_transcripts)
+        self.n_names = self.n_classes = 0
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64)
+        assert lens is None or lens.size == self.n_transcripts
+        h = C.c_void_p()
+        check(L.br_quant_new(device, self.n_transcripts, lens.ctypes.data if lens is not None else None, C.byref(h)), "br_quant_new")
+        self.h = h
+        if lens is None:
+            self.set_param("length_norm", 0)
+
+    def set_param(self, name, value):
+        """"hash_bits", "length_norm", "max_iters" (integers) or "tolerance" (a float)."""
+        if name == "tolerance":
+            check(lib().br_quant_set_tolerance(self.h, float(value)), "br_quant_set_tolerance")
+        else:
+            check(lib().br_quant_set_param(self.h, name.encode(), int(value)), "br_quant_set_param")
+
+    def add_raw(self, a, row_off, group_off, n_groups, on_device, stream=None):
+        """br_quant_add as it is: the return code (0, or a BR_ERR_* value)."""
+        return lib().br_quant_add(self.h, C.c_void_p(a), C.c_void_p(row_off), C.c_void_p(group_off), int(n_groups), 1 if on_device else 0,
+                                  C.c_void_p(stream or 0))
+
+    def add_host(self, rows_a, row_off, group_off):
+        """rows_a: uint32 [n_rows, 4] (br_row_a: transcript_id, pos, meta, nh), row_off uint64 [n_aln + 1], group_off uint32
+        [n_groups + 1], in host memory."""
+        a = np.ascontiguousarray(rows_a, dtype=np.uint32).reshape(-1, 4)
+        ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+        go = np.ascontiguousarray(group_off, dtype=np.uint32)
+        check(self.add_raw(a.ctypes.data if a.size else None, ro.ctypes.data, go.ctypes.data, len(go) - 1, False), "br_quant_add")
+
+    def add_device(self, rows_a, row_off, group_off, g0=0, g1=None):
+        """The same tables as torch CUDA tensors (rows_a int32 / uint8 storage of br_row_a, row_off int64, group_off int32); the
+        read names [g0, g1) of them are added."""
+        import torch
+        g1 = group_off.numel() - 1 if g1 is None else g1
+        check(self.add_raw(rows_a.data_ptr(), row_off.data_ptr(), group_off.data_ptr() + 4 * g0, g1 - g0, True,
+                           torch.cuda.current_stream(row_off.device).cuda_stream), "br_quant_add")
+
+    def add_last(self, ctx):
+        """The read names of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
+        check(lib().br_quant_add_last(self.h, ctx.h), "br_quant_add_last")
+
+    def finish(self):
+        n, c = C.c_int64(), C.c_int64()
+        check(lib().br_quant_finish(self.h, C.byref(n), C.byref(c)), "br_quant_finish")
+        self.n_names, self.n_classes = int(n.value), int(c.value)
+        return self.n_names, self.n_classes
+
+    def classes(self):
+        """-> (label_off uint64 [C + 1], labels uint32, counts uint64 [C], first_name uint64 [C])"""
+        nc = self.n_classes
+        off = np.zeros(nc + 1, dtype=np.uint64)
+        cnt, first = np.zeros(max(nc, 1), dtype=np.uint64), np.zeros(max(nc, 1), dtype=np.uint64)
+        check(lib().br_quant_classes(self.h, off.ctypes.data, None, None, None), "br_quant_classes")
+        labels = np.zeros(max(int(off[-1]), 1), dtype=np.uint32)
+        check(lib().br_quant_classes(self.h, None, labels.ctypes.data, cnt.ctypes.data, first.ctypes.data), "br_quant_classes")
+        return off, labels[:int(off[-1])], cnt[:nc], first[:nc]
+
+    def em(self):
+        """-> (iterations, the last relative change looked at)"""
+        n, r = C.c_int32(), C.c_double()
+        check(lib().br_quant_em(self.h, C.byref(n), C.byref(r)), "br_quant_em")
+        return int(n.value), float(r.value)
+
+    def result(self, em=True):
+        """-> dict of theta, tpm (float64; with em) and unique, ambig (uint64), one entry per transcript"""
+        nt = max(self.n_transcripts, 1)
+        out = {"unique": np.zeros(nt, dtype=np.uint64), "ambig": np.zeros(nt, dtype=np.uint64)}
+        if em:
+            out["theta"], out["tpm"] = np.zeros(nt, dtype=np.float64), np.zeros(nt, dtype=np.float64)
+        check(lib().br_quant_result(self.h, out["theta"].ctypes.data if em else None, out["tpm"].ctypes.data if em else None,
+                                    out["unique"].ctypes.data, out["ambig"].ctypes.data), "br_quant_result")
+        return {k: v[:self.n_transcripts] for k, v in out.items()}
+
+    def stats(self):
+        h, p, co = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        ad, fi, em = C.c_double(), C.c_double(), C.c_double()
+        un, nl = C.c_int64(), C.c_int64()
+        check(lib().br_quant_stats(self.h, C.byref(h), C.byref(p), C.byref(ad), C.byref(fi), C.byref(em), C.byref(co), C.byref(un),
+                                   C.byref(nl)), "br_quant_stats")
+        return {"held_bytes": int(h.value), "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value, "em_s": em.value,
+                "collisions": int(co.value), "n_unassigned": int(un.value), "n_labels": int(nl.value)}
+
+    def close(self):
+        if self.h:
+            lib().br_quant_free(self.h)
             self.h = None
 
     def __del__(self):

@@ -648,6 +648,64 @@ int br_sorter_index(br_sorter *, int32_t n_ref, const br_bgzf_span *blocks, int6
                     uint64_t *n_bytes);
 void br_sorter_free(br_sorter *);
 
+/* A quantifier: the read names of a whole run reduced to equivalence classes in one device's HBM, and per-transcript abundances
+ * estimated from them by EM (quant.cpp, quant_kernels.hip).  The definitions:
+ *   read name      a read-name group of a projected batch.  Its rows are row_off[group_off[g]] .. row_off[group_off[g + 1]]; its
+ *                  transcript set is the ascending list of the distinct transcript_id of those rows.  Both mates count: a pair
+ *                  emitted on two different transcripts (mate_case 2 of process_mate_pair) contributes both.  A name without rows
+ *                  makes no class and counts in n_unassigned
+ *   class          a distinct transcript set; its count is the number of read names that have that set.  Classes are ordered by
+ *                  the add-order index of their first read name, the labels ascend inside a class.  How the adds were cut into
+ *                  calls does not change the result
+ *   per transcript unique[t] = names whose class is {t}; ambig[t] = names whose class holds t and has two labels or more
+ *   EM             w[t] = 1 / len[t] with length normalisation, else 1; theta = 1 for every transcript at the start.  One
+ *                  iteration: d_c = sum over t in c of theta_t w_t, then theta'_t = theta_t w_t * sum over the classes c that hold
+ *                  t of n_c / d_c (a class with d_c == 0 contributes nothing).  After every iteration whose number is a multiple
+ *                  of 16, and after the last one, the relative change is the maximum over t with theta'_t > 1e-8 of
+ *                  |theta'_t - theta_t| / theta'_t; the run stops when that is < tolerance, or at max_iters (tolerance = 0 runs
+ *                  exactly max_iters iterations).  Defaults: max_iters 10000, tolerance 1e-2 (salmon's minAlpha /
+ *                  relDiffTolerance convention).  TPM_t = 1e6 theta_t w_t / sum of theta w.  Not modelled: fragment lengths,
+ *                  sequence or position bias, bootstraps
+ *   numerics       float64 throughout, no floating-point atomics: a class's sum runs over its labels in ascending order, a
+ *                  transcript's over its classes in ascending order through a transposed membership table; items of more than 64
+ *                  entries are summed by a wave (lane l takes entries l, l + 64, ..., then a fixed tree), so the shape of every sum
+ *                  depends on the data alone and two runs on the same input give the same bits
+ *   br_quant_new        lengths: n_transcripts transcript lengths, or NULL (then "length_norm" must be 0).  BR_ERR_NO_DEVICE
+ *                       without the device
+ *   br_quant_set_param  before finish: "hash_bits" (test hook: 1..64 bits of the label hash are kept, so that different sets
+ *                       collide; the result does not change), "length_norm" 0 / 1 (default 1), "max_iters", "tolerance_ppm"
+ *                       (tolerance in millionths; br_quant_set_tolerance takes the double itself)
+ *   br_quant_add        the read names group_off[0 .. n_groups] of a batch: a / row_off / group_off as br_device_rows and
+ *                       br_device_batch hold them (device memory with on_device != 0, read after the work queued on `stream`, NULL
+ *                       for the null stream; host memory with on_device = 0).  Returns when the tables have been read.
+ *                       BR_ERR_INVALID_ARG after finish, or for offsets that descend (nothing is added); BR_ERR_CAPACITY when the
+ *                       device's memory does not take it or the names would number 2^32 or more
+ *   br_quant_add_last   the same for the context's last projection call, whichever entry point made it
+ *   br_quant_finish     the classes; the numbers of names added and of classes.  BR_ERR_INVALID_ARG for a transcript_id >=
+ *                       n_transcripts, or when lengths normalise and a transcript of length <= 0 (or no lengths at all) has a read
+ *   br_quant_classes    host copies: label_off (n_classes + 1), labels (label_off[n_classes]), counts, first_name (the add-order
+ *                       index of the class's first read name); any pointer may be NULL
+ *   br_quant_em         the EM, after finish; the iterations run and the last relative change looked at
+ *   br_quant_result     host copies, n_transcripts each, any may be NULL: theta and tpm (after em), unique and ambig (after finish)
+ *   br_quant_stats      device bytes held now, the most held so far, seconds in add / finish / em, label sets met with equal
+ *                       hashes and different contents, names without rows, labels over all classes (any pointer may be NULL)
+ * Device memory: 4 bytes a row and 20 bytes a read name while adding; finish peaks at 32 more a name with labels, then holds 24
+ * bytes a class, 8 a label and 24 a transcript; the EM adds 40 a transcript and 8 a class (quant.cpp). */
+typedef struct br_quant br_quant;
+int br_quant_new(int device, int64_t n_transcripts, const int64_t *lengths, br_quant **out);
+int br_quant_set_param(br_quant *, const char *name, int64_t value);
+int br_quant_set_tolerance(br_quant *, double tolerance);
+int br_quant_add(br_quant *, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t n_groups, int on_device,
+                 void *stream);
+int br_quant_add_last(br_quant *, br_ctx *);
+int br_quant_finish(br_quant *, int64_t *n_names, int64_t *n_classes);
+int br_quant_classes(br_quant *, uint64_t *label_off, uint32_t *labels, uint64_t *counts, uint64_t *first_name);
+int br_quant_em(br_quant *, int32_t *n_iters, double *rel_change);
+int br_quant_result(br_quant *, double *theta, double *tpm, uint64_t *unique, uint64_t *ambig);
+int br_quant_stats(const br_quant *, uint64_t *held_bytes, uint64_t *peak_bytes, double *add_seconds, double *finish_seconds,
+                   double *em_seconds, uint64_t *collisions, int64_t *n_unassigned, int64_t *n_labels);
+void br_quant_free(br_quant *);
+
 /* br_project_bam_staged / _nowait for records that are in HBM already (a br_bam_reader bundle, or br_bam_split_device's);
  * bgzf_on_device takes the values of br_bam_bundle.bgzf_on_device (0, 1, BR_OUT_SAM_TEXT) */
 int br_project_bam_resident(br_ctx *, const br_config *, const br_device_records *recs, const int32_t *ref_map, int32_t n_ref_map,
@@ -720,7 +778,8 @@ const char *const *br_annotation_refnames(const br_annotation *);
 /* The reference's command line (src/bramble.cpp:443-485): in.bam -G -o [-S] [-p] [--fr|--rf]
  * [--lr|--lr-hq] [--strict] [--max-*] [--similarity-threshold] [--quiet], plus --device-deflate (default: BGZF blocks made on the
  * GPU) / --host-deflate / --compression-level N (host codec), --device-reader (default for a regular file on one device: the
- * input is inflated and split into records on the GPU, br_bam_reader) / --host-reader, --bundle-size and --device / --devices.
+ * input is inflated and split into records on the GPU, br_bam_reader) / --host-reader, --bundle-size and --device / --devices,
+ * --collate, -O bam|sam, --sort [--write-index], --quant FILE [--quant-classes FILE] (br_quant above; the usage text says the rest).
  * Returns the process exit code. */
 int br_cli_main(int argc, char **argv);
 /* For a process whose only job is that one call (the `bramble` binary): with `on` != 0 br_cli_main does not return after a
