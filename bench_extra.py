@@ -18,7 +18,8 @@
   python bench_extra.py quant [--reads N]  br_quant over the rows of the bench.py workload (N pairs, default 10 M), projected once
                                          (br_project_batch_device, timed): the read names handed over from HBM in slices of 1 M
                                          alignments, the classes, the EM -- seconds in add / finish / em, iterations, names, classes,
-                                         labels, quantifier peak device bytes per read name
+                                         labels, quantifier peak device bytes per read name; then the same with the fragment-length
+                                         model ("eff_len": the adds through br_quant_add_rows), as runs_eff_length
   python bench_extra.py samout [--reads N]  SAM text out: br_sam_format_device on the projected records of N pairs (default 500 000,
                                          about 1 M records: one CLI bundle) against br_bgzf_deflate_device of the same stream in the
                                          same process (ms per bundle, text GB/s), then the command line file to file with -O sam
@@ -171,26 +172,37 @@ def main():
             project.append(round(time.perf_counter() - t0, 4))
         n_rows = int(rows.n_rows)
         cuts = sorted(set(int(np.searchsorted(goff, a, side="left")) for a in range(0, n_aln, 1_000_000)) | {n_groups})   # names whose first alignment opens a slice
-        runs = []
-        for step in range(args.warmup + args.steps):
-            q = lib.Quant(n_tx, lens)
-            t0 = time.perf_counter()
-            for g0, g1 in zip(cuts, cuts[1:]):
-                lib.check(q.add_raw(rows.a, rows.row_off, db["group_off"].data_ptr() + 4 * g0, g1 - g0, True), "br_quant_add")
-            t1 = time.perf_counter()
-            names, classes = q.finish()
-            t2 = time.perf_counter()
-            iters, rel = q.em()
-            t3 = time.perf_counter()
-            stt = q.stats()
-            q.close()
-            if step >= args.warmup:
-                runs.append({"add_s": round(t1 - t0, 4), "add_ms_per_slice": round(1e3 * (t1 - t0) / (len(cuts) - 1), 3), "finish_s": round(t2 - t1, 4),
-                             "em_s": round(t3 - t2, 4), "iterations": iters, "rel_change": rel, "em_us_per_iteration": round(1e6 * (t3 - t2) / max(iters, 1), 2),
-                             "names": names, "unassigned": stt["n_unassigned"], "classes": classes, "labels": stt["n_labels"],
-                             "peak_bytes_per_name": round(stt["peak_bytes"] / max(names, 1), 1)})
+        runs, runs_eff = [], []
+        for eff_len in (0, 1):   # 1: the fragment-length model, the adds through br_quant_add_rows (the CIGAR references and the pool as well)
+            for step in range(args.warmup + args.steps):
+                q = lib.Quant(n_tx, lens)
+                q.set_param("eff_len", eff_len)
+                t0 = time.perf_counter()
+                for g0, g1 in zip(cuts, cuts[1:]):
+                    if eff_len:
+                        lib.check(q.add_rows_raw(rows.a, rows.cigar, rows.pool, rows.row_off, rows.n_rows, rows.n_pool_words,
+                                                 db["group_off"].data_ptr() + 4 * g0, g1 - g0, True), "br_quant_add_rows")
+                    else:
+                        lib.check(q.add_raw(rows.a, rows.row_off, db["group_off"].data_ptr() + 4 * g0, g1 - g0, True), "br_quant_add")
+                t1 = time.perf_counter()
+                names, classes = q.finish()
+                t2 = time.perf_counter()
+                iters, rel = q.em()
+                t3 = time.perf_counter()
+                stt = q.stats()
+                fld = q.fld() if eff_len else None
+                q.close()
+                if step >= args.warmup:
+                    run = {"add_s": round(t1 - t0, 4), "add_ms_per_slice": round(1e3 * (t1 - t0) / (len(cuts) - 1), 3), "finish_s": round(t2 - t1, 4),
+                           "em_s": round(t3 - t2, 4), "iterations": iters, "rel_change": rel, "em_us_per_iteration": round(1e6 * (t3 - t2) / max(iters, 1), 2),
+                           "names": names, "unassigned": stt["n_unassigned"], "classes": classes, "labels": stt["n_labels"],
+                           "peak_bytes_per_name": round(stt["peak_bytes"] / max(names, 1), 1)}
+                    if eff_len:
+                        run.update({k: fld[k] for k in ("n_obs", "n_no_fragment", "n_out_of_range")})
+                        run["mean_fragment_length"] = round(float((np.arange(len(fld["hist"])) * fld["hist"].astype(np.float64)).sum()) / max(fld["n_obs"], 1), 2)
+                    (runs_eff if eff_len else runs).append(run)
         print(json.dumps({"config": "quant", "pairs": n, "alignments": n_aln, "rows": n_rows, "transcripts": n_tx, "slices": len(cuts) - 1,
-                          "project_s": project, "runs": runs}))
+                          "project_s": project, "runs": runs, "runs_eff_length": runs_eff}))
         return
     if args.config == "small":
         import subprocess

@@ -12,6 +12,7 @@
 //                   notes the blocks it writes and br_sorter_index builds <out>.bai from them
 //   --quant       : the runner hands every bundle's rows, where the projection left them in HBM, to a br_quant (br_quant_add_last);
 //                   after the last bundle: classes, EM, one download, and the two text files formatted here
+//                   (--quant-eff-length: the adds count the fragment lengths as well, "eff_len"; --quant-fld: the histogram's file)
 #include <ctype.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -41,7 +42,8 @@ void usage(FILE *f) {
           " [--max-error-exon N] [--similarity-threshold X]\n"
           " [--device-deflate | --host-deflate | --compression-level 0-9] [--device-reader | --host-reader] [--bundle-size N]\n"
           "               [--device N | --devices a,b,...] [--collate] [--sort [--write-index]]\n"
-          "               [--quant <quant.tsv> [--quant-classes <eq_classes.txt>] [--quant-length-norm | --quant-no-length-norm]]\n\n"
+          "               [--quant <quant.tsv> [--quant-classes <eq_classes.txt>] [--quant-length-norm | --quant-no-length-norm]\n"
+          "                [--quant-eff-length [--quant-fld <fld.tsv>]]]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -62,8 +64,14 @@ void usage(FILE *f) {
           "read name was projected to; both mates count) and per-transcript abundances are estimated from them by EM; FILE gets one line\n"
           "per @SQ transcript: Name, Length, NumReads, TPM, UniqueReads, AmbigReads.  --quant-classes FILE: the classes in the layout of\n"
           "salmon's eq_classes.txt.  Reads are weighted by 1 / transcript length in the short-read preset and not under --lr / --lr-hq;\n"
-          "--quant-length-norm / --quant-no-length-norm say otherwise.  No fragment-length or bias model, no bootstraps.  One more line\n"
-          "in front of the final report: [bramble] quantified N read names in C classes ...\n");
+          "--quant-length-norm / --quant-no-length-norm say otherwise.  No bias model, no bootstraps.  One more line\n"
+          "in front of the final report: [bramble] quantified N read names in C classes ...\n"
+          "--quant-eff-length: the fragment lengths of the pairs that project to one transcript alone are counted on the GPU and reads\n"
+          "are weighted by 1 / effective length (the transcript's length minus the mean of the observed fragment lengths that fit it,\n"
+          "plus 1: salmon's and kallisto's convention); quant.tsv gains an EffectiveLength column behind Length.  It needs length\n"
+          "normalisation: not with --quant-no-length-norm, and under --lr / --lr-hq only with --quant-length-norm.  --quant-fld FILE:\n"
+          "the histogram, FragmentLength and Count for the lengths 0 .. 1000.  One more line in front of the quantified line:\n"
+          "[bramble] fragment lengths: N observed, mean M.M, U unique names without a pair, R out of range\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -118,6 +126,8 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (a == "--quant-classes") { const char *v = value(); if (!v) return -1; o.quant_classes = v; }
     else if (a == "--quant-length-norm") o.quant_length_norm = 1;
     else if (a == "--quant-no-length-norm") o.quant_length_norm = 0;
+    else if (a == "--quant-eff-length") o.quant_eff_length = true;
+    else if (a == "--quant-fld") { const char *v = value(); if (!v) return -1; o.quant_fld = v; }
     else if (a == "--device") { const char *v = value(); if (!v) return -1; o.devices.assign(1, atoi(v)); }
     else if (a == "--devices") {
       const char *v = value(); if (!v) return -1;
@@ -138,6 +148,10 @@ int parse_args(int argc, char **argv, Options &o) {
   if (o.sort && o.devices.size() > 1) { fprintf(stderr, "--sort works on one device: give --device N, not a --devices list\n"); return -1; }
   if (!o.quant.empty() && o.devices.size() > 1) { fprintf(stderr, "--quant works on one device: give --device N, not a --devices list\n"); return -1; }
   if (o.quant.empty() && (!o.quant_classes.empty() || o.quant_length_norm >= 0)) { fprintf(stderr, "--quant-classes, --quant-length-norm and --quant-no-length-norm need --quant\n"); return -1; }
+  if (o.quant.empty() && (o.quant_eff_length || !o.quant_fld.empty())) { fprintf(stderr, "--quant-eff-length and --quant-fld need --quant\n"); return -1; }
+  if (!o.quant_fld.empty() && !o.quant_eff_length) { fprintf(stderr, "--quant-fld needs --quant-eff-length: without it no fragment lengths are counted\n"); return -1; }
+  if (o.quant_eff_length && o.quant_length_norm == 0) { fprintf(stderr, "--quant-eff-length is a length normalisation: not with --quant-no-length-norm\n"); return -1; }
+  if (o.quant_eff_length && (o.cfg.lr || o.cfg.lr_hq) && o.quant_length_norm != 1) { fprintf(stderr, "--quant-eff-length under --lr / --lr-hq needs --quant-length-norm: long reads are not length-normalised by default\n"); return -1; }
   if (o.write_index && !o.sort) { fprintf(stderr, "--write-index needs --sort: a BAI index describes a coordinate-sorted file\n"); return -1; }
   if (o.write_index && o.sam_out) { fprintf(stderr, "--write-index applies to BAM output, not to --output-fmt sam\n"); return -1; }
   if (o.write_index && o.out_bam == "-") { fprintf(stderr, "--write-index needs an output file, not standard output\n"); return -1; }
@@ -288,6 +302,7 @@ struct Run {
   br_quant *quant = nullptr;     // --quant: deliver() adds every bundle's rows; quantify() runs once the input is through
   int64_t q_names = 0, q_classes = 0; int32_t q_iters = 0;
   double t_q_add = 0, t_q_finish = 0, t_q_em = 0;
+  std::vector<double> q_eff; std::vector<uint64_t> q_fld; uint64_t q_fld_obs = 0, q_fld_nofrag = 0, q_fld_oor = 0;   // --quant-eff-length
   std::vector<double> q_theta, q_tpm; std::vector<uint64_t> q_unique, q_ambig, q_label_off, q_counts; std::vector<uint32_t> q_labels;
   bool track_blocks = false;     // --write-index: the writer notes where every BGZF block of the record section starts
   std::vector<br_bgzf_span> spans;
@@ -298,6 +313,7 @@ struct Run {
   std::atomic<int> fail{0};
   std::string writer_err;
   double t_deflate = 0;
+  static constexpr size_t QUANT_FLD_MAX = 1000;           // br_quant's default "fld_max"
   static constexpr uint64_t SORT_PIECE = 128ull << 20;   // record bytes per sorted piece (one deflate / format call and one download)
   void go() {
     std::thread writer([this] { write(); });
@@ -389,6 +405,11 @@ struct Run {
       const size_t nt = br_index_num_transcripts(w->ix);
       q_theta.resize(nt + 1); q_tpm.resize(nt + 1); q_unique.resize(nt + 1); q_ambig.resize(nt + 1);
       rc = br_quant_result(quant, q_theta.data(), q_tpm.data(), q_unique.data(), q_ambig.data());
+    }
+    if (!rc && o.quant_eff_length) {
+      q_eff.resize(br_index_num_transcripts(w->ix) + 1); q_fld.resize(QUANT_FLD_MAX + 1);
+      rc = br_quant_eff_lengths(quant, q_eff.data());
+      if (!rc) rc = br_quant_fld(quant, q_fld.data(), &q_fld_obs, &q_fld_nofrag, &q_fld_oor);
     }
     if (!rc && !o.quant_classes.empty()) {
       int64_t n_labels = 0;
@@ -598,6 +619,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
     int qrc = br_quant_new(o.devices[0], (int64_t)nt, tx_len.data(), &quant);
     const int norm = o.quant_length_norm >= 0 ? o.quant_length_norm : (o.cfg.lr || o.cfg.lr_hq) ? 0 : 1;   // (oarfish does not length-normalise long reads)
     if (!qrc) qrc = br_quant_set_param(quant, "length_norm", norm);
+    if (!qrc && o.quant_eff_length) qrc = br_quant_set_param(quant, "eff_len", 1);
     if (qrc) { fprintf(stderr, "error: quantifier on device %d: %s\n", o.devices[0], br_strerror(qrc)); return give_up(); }
   }
   OutFile file(o.out_bam);
@@ -631,7 +653,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
     }
   }
   // the quantifier's files take the output's route as well
-  const std::string q_tmp = o.quant + ".tmp-bramble", qc_tmp = o.quant_classes + ".tmp-bramble";
+  const std::string q_tmp = o.quant + ".tmp-bramble", qc_tmp = o.quant_classes + ".tmp-bramble", qf_tmp = o.quant_fld + ".tmp-bramble";
   if (!failed && quant) {
     const size_t nt = tx_len.size();
     std::vector<int64_t> sq_of(nt, -1);
@@ -644,7 +666,12 @@ extern "C" int br_cli_main(int argc, char **argv) {
       return !bad;
     };
     FILE *f = fopen(q_tmp.c_str(), "w");
-    if (f) {
+    if (f && o.quant_eff_length) {
+      fprintf(f, "Name\tLength\tEffectiveLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\n");
+      for (size_t t = 0; t < nt; t++)
+        if (tx_len[t] > 0) fprintf(f, "%s\t%lld\t%.3f\t%.6f\t%.6f\t%llu\t%llu\n", br_index_transcript_name(ix0, (uint32_t)t), (long long)tx_len[t], run.q_eff[t], run.q_theta[t],
+                                   run.q_tpm[t], (unsigned long long)run.q_unique[t], (unsigned long long)run.q_ambig[t]);
+    } else if (f) {
       fprintf(f, "Name\tLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\n");
       for (size_t t = 0; t < nt; t++)
         if (tx_len[t] > 0) fprintf(f, "%s\t%lld\t%.6f\t%.6f\t%llu\t%llu\n", br_index_transcript_name(ix0, (uint32_t)t), (long long)tx_len[t], run.q_theta[t], run.q_tpm[t],
@@ -664,6 +691,14 @@ extern "C" int br_cli_main(int argc, char **argv) {
       }
       if (!close_ok(f, qc_tmp)) failed = 1;
     }
+    if (!failed && !o.quant_fld.empty()) {
+      f = fopen(qf_tmp.c_str(), "w");
+      if (f) {
+        fprintf(f, "FragmentLength\tCount\n");
+        for (size_t k = 0; k <= Run::QUANT_FLD_MAX; k++) fprintf(f, "%zu\t%llu\n", k, (unsigned long long)run.q_fld[k]);
+      }
+      if (!close_ok(f, qf_tmp)) failed = 1;
+    }
   }
   if (!file.finish(!failed)) failed = 1;
   if (quant) {
@@ -672,14 +707,20 @@ extern "C" int br_cli_main(int argc, char **argv) {
       if (failed) remove(tmp.c_str());
       else if (rename(tmp.c_str(), path.c_str()) != 0) { fprintf(stderr, "error: could not rename %s to %s\n", tmp.c_str(), path.c_str()); failed = 1; }
     };
-    settle(q_tmp, o.quant); settle(qc_tmp, o.quant_classes);
-    if (failed) { remove(q_tmp.c_str()); if (!o.quant_classes.empty()) remove(qc_tmp.c_str()); }
+    settle(q_tmp, o.quant); settle(qc_tmp, o.quant_classes); settle(qf_tmp, o.quant_fld);
+    if (failed) { remove(q_tmp.c_str()); if (!o.quant_classes.empty()) remove(qc_tmp.c_str()); if (!o.quant_fld.empty()) remove(qf_tmp.c_str()); }
   }
   if (o.write_index) {
     if (failed) remove(bai_tmp.c_str());
     else if (rename(bai_tmp.c_str(), bai_path.c_str()) != 0) { fprintf(stderr, "error: could not rename %s to %s\n", bai_tmp.c_str(), bai_path.c_str()); failed = 1; }
   }
   if (!o.quiet && o.sort && !failed) printf("[bramble] sorted %lld records by coordinate on device %d (add %.2fs, sort %.2fs)%s\n", (long long)run.sorted_records, o.devices[0], run.t_sort_add, run.t_sort_finish, o.write_index ? ", index written" : "");
+  if (!o.quiet && quant && !failed && o.quant_eff_length) {
+    double sum = 0;
+    for (size_t k = 0; k <= Run::QUANT_FLD_MAX; k++) sum += (double)k * (double)run.q_fld[k];
+    printf("[bramble] fragment lengths: %llu observed, mean %.1f, %llu unique names without a pair, %llu out of range\n", (unsigned long long)run.q_fld_obs,
+           run.q_fld_obs ? sum / (double)run.q_fld_obs : 0.0, (unsigned long long)run.q_fld_nofrag, (unsigned long long)run.q_fld_oor);
+  }
   if (!o.quiet && quant && !failed) printf("[bramble] quantified %lld read names in %lld classes (%d iterations, add %.2fs, classes %.2fs, EM %.2fs)\n", (long long)run.q_names, (long long)run.q_classes, (int)run.q_iters, run.t_q_add, run.t_q_finish, run.t_q_em);
   double t_done = since();
   uint64_t total_complete = 0, total_unique = 0, dropped = 0, n_bundles = 0;

@@ -11,6 +11,10 @@
 //            -> radix sort of (transcript, label entry): the transposed table, per transcript its classes in ascending order ->
 //            classes of more than 64 labels and transcripts in more than 64 classes listed (a wave each in the EM) -> unique /
 //            ambiguous names per transcript
+//   lengths  ("eff_len") every add also counts, per read name of one label, the length of its first fragment (a pair's two adjacent
+//            rows on one transcript: positions and the reference bases of the two rewritten CIGARs) into the add's own histogram,
+//            which joins the run's once the add is known to be good; finish scans the histogram into C and S and writes the
+//            effective length and w = 1 / eff per transcript, which the EM then takes from the device
 //   em       per iteration a class kernel (q_c = n_c / sum over its labels of theta_t w_t) and a transcript kernel (theta'_t =
 //            theta_t w_t * sum of q_c over the transcript's classes, gathered through the transposed table); every 16th iteration
 //            and the last the transcript kernel also leaves the largest relative change in one word, which the host reads
@@ -25,6 +29,9 @@
 //   afterwards     24 C (first name, count, label_off) + 8 L (labels, the transposed table's classes) + 24 T (the table's offsets,
 //                  unique, ambiguous) + 4 bytes per listed class / transcript
 //   em             adds 40 T (theta and theta w twice, w) + 8 C (q)
+//   "eff_len"      adds 16 (fld_max + 1 + 3) from the first add on (the histogram and its three counters, the run's and the add's
+//                  own), 8 per row and 4 per pool word of a host add's CIGAR copies while it runs, 16 (fld_max + 1) for the
+//                  prefixes during finish, and 8 T for eff from finish on (w, 8 T of the EM's 40, is held from finish on as well)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,7 +53,8 @@ struct br_quant {
   hipEvent_t ev = nullptr;
   int64_t n_tx = 0;
   std::vector<int64_t> lens;   // empty: no lengths were given
-  int hash_bits = 64, length_norm = 1;
+  int hash_bits = 64, length_norm = 1, eff_len = 0;
+  int64_t fld_max = 1000;      // (salmon's fragLenDistMax)
   int64_t max_iters = 10000;
   double tolerance = 1e-2;
   bool finished = false, em_done = false;
@@ -60,6 +68,17 @@ struct br_quant {
   ColBuf lab, noff, nk, hash, big;                       // add
   ColBuf c_first, c_cnt, c_loff, c_labels, t_cls, t_off, uniq, ambig, big_cls, big_tx;   // after finish
   ColBuf theta[2], x[2], w, qv;                          // em
+  ColBuf fld_stage, fld_total, eff;                      // "eff_len": fld_max + 1 bins + Q_FLD_SIDE counters each (an add's, the run's); per transcript
+  size_t fld_words() const { return (size_t)fld_max + 1 + Q_FLD_SIDE; }
+  int fld_tables() {                                     // (zeroed once; a commit leaves the add's table zero again)
+    if (fld_total.p) return BR_OK;                       // (fld_max is fixed from here on: br_quant_set_param)
+    const size_t bytes = fld_words() * 8;
+    int rc = alloc(fld_stage, bytes);
+    if (!rc) rc = alloc(fld_total, bytes);
+    if (!rc && (hipMemsetAsync(fld_stage.p, 0, bytes, st) != hipSuccess || hipMemsetAsync(fld_total.p, 0, bytes, st) != hipSuccess)) rc = BR_ERR_HIP;
+    if (rc) { drop(fld_stage); drop(fld_total); }        // both, zeroed, or neither
+    return rc;
+  }
   int cur = 0;
   ColBuf tmp, small;
   int alloc(ColBuf &b, size_t bytes, bool keep = false) {
@@ -115,6 +134,11 @@ extern "C" int br_quant_set_param(br_quant *c, const char *name, int64_t value) 
   if (!c || !name || c->finished) return BR_ERR_INVALID_ARG;
   if (!strcmp(name, "hash_bits")) { if (value < 1 || value > 64) return BR_ERR_INVALID_ARG; c->hash_bits = (int)value; return BR_OK; }
   if (!strcmp(name, "length_norm")) { if (value != 0 && value != 1) return BR_ERR_INVALID_ARG; c->length_norm = (int)value; return BR_OK; }
+  // what the adds already counted depends on these two, and the histogram's tables are sized by fld_max when the first add that
+  // counts fragments makes them: before the first add only, a refused one included
+  const bool fixed = c->n > 0 || c->fld_total.p != nullptr;
+  if (!strcmp(name, "eff_len")) { if ((value != 0 && value != 1) || fixed) return BR_ERR_INVALID_ARG; c->eff_len = (int)value; return BR_OK; }
+  if (!strcmp(name, "fld_max")) { if (value < 1 || value > 65535 || fixed) return BR_ERR_INVALID_ARG; c->fld_max = value; return BR_OK; }
   if (!strcmp(name, "max_iters")) { if (value < 1) return BR_ERR_INVALID_ARG; c->max_iters = value; return BR_OK; }
   if (!strcmp(name, "tolerance_ppm")) { if (value < 0) return BR_ERR_INVALID_ARG; c->tolerance = (double)value * 1e-6; return BR_OK; }
   return BR_ERR_INVALID_ARG;
@@ -139,10 +163,12 @@ static int quant_reserve(br_quant *c, int64_t m, uint64_t rows) {
   return BR_OK;
 }
 
-// the names of one add, their tables on the device (A: a, row_off, group_off, the biases, r_first, r_last and n_groups are set)
+// the names of one add, their tables on the device (A: a, row_off, group_off, the biases, r_first, r_last and n_groups are set;
+// cigar, pool and n_pool_words as well when the fragments are counted)
 static int quant_add_names(br_quant *c, QAddArgs A) {
   hipStream_t st = c->st;
   RC(quant_reserve(c, A.n_groups, A.r_last - A.r_first));
+  if (A.cigar) RC(c->fld_tables());
   uint64_t *small = c->small.as<uint64_t>();
   HIPCHK(hipMemsetAsync(small + QS_NBIG, 0, 8, st)); HIPCHK(hipMemsetAsync(small + QS_BAD, 0, 8, st));
   A.lab_base = c->rows; A.lab = c->lab.as<uint32_t>();
@@ -150,15 +176,25 @@ static int quant_add_names(br_quant *c, QAddArgs A) {
   A.big = c->big.as<uint32_t>(); A.n_big = (uint32_t *)(small + QS_NBIG);
   A.max_tid = (uint32_t *)(small + QS_MAXTID); A.bad = (uint32_t *)(small + QS_BAD);
   launch_q_names(st, A);
+  if (A.cigar) {
+    A.fld_max = (uint32_t)c->fld_max; A.stage = c->fld_stage.as<unsigned long long>();
+    launch_q_frag(st, A);
+  }
   uint32_t bad = 0;
   HIPCHK(hipMemcpyAsync(&bad, small + QS_BAD, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));   // the caller's rows may be reused now
-  if (bad) return BR_ERR_INVALID_ARG;   // offsets that descend somewhere: nothing was added
+  if (bad) {   // offsets that descend somewhere, or a CIGAR reference that leaves the pool: nothing was added
+    if (A.cigar) HIPCHK(hipMemsetAsync(c->fld_stage.p, 0, c->fld_words() * 8, st));
+    return BR_ERR_INVALID_ARG;
+  }
+  if (A.cigar) launch_q_fld_commit(st, A.stage, c->fld_total.as<unsigned long long>(), (uint32_t)c->fld_words());
   c->rows += A.r_last - A.r_first; c->n += A.n_groups;
   return BR_OK;
 }
 
-static int quant_add_device(br_quant *c, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t ng, hipStream_t caller) {
+// rows: a and row_off; cigar, pool, n_pool_words and n_rows as well when the fragments are counted (cigar != NULL)
+static int quant_add_device(br_quant *c, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, hipStream_t caller) {
+  const br_row_a *a = rows.a; const uint64_t *row_off = rows.row_off;
   hipStream_t st = c->st;
   HIPCHK(hipEventRecord(c->ev, caller)); HIPCHK(hipStreamWaitEvent(st, c->ev, 0));   // after whatever made the rows (NULL: the null stream's work)
   uint64_t *small = c->small.as<uint64_t>();
@@ -166,19 +202,22 @@ static int quant_add_device(br_quant *c, const br_row_a *a, const uint64_t *row_
   uint64_t span[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(span, small + QS_SPAN, 16, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (span[1] < span[0]) return BR_ERR_INVALID_ARG;
+  if (span[1] < span[0] || (rows.cigar && span[1] > (uint64_t)rows.n_rows)) return BR_ERR_INVALID_ARG;
   QAddArgs A{};
   A.a = (const uint4 *)a; A.row_off = row_off; A.group_off = group_off; A.n_groups = ng; A.r_first = span[0]; A.r_last = span[1];
+  A.cigar = rows.cigar; A.pool = rows.pool; A.n_pool_words = (uint64_t)rows.n_pool_words;
   return quant_add_names(c, A);
 }
 
-static int quant_add_host(br_quant *c, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t ng) {
+static int quant_add_host(br_quant *c, const br_device_rows &rows, const uint32_t *group_off, int64_t ng) {
+  const br_row_a *a = rows.a; const uint64_t *row_off = rows.row_off;
   const uint32_t a0 = group_off[0], a1 = group_off[ng];
   for (int64_t g = 0; g < ng; g++) if (group_off[g + 1] < group_off[g]) return BR_ERR_INVALID_ARG;
   for (uint32_t i = a0; i < a1; i++) if (row_off[i + 1] < row_off[i]) return BR_ERR_INVALID_ARG;
   const uint64_t r0 = row_off[a0], r1 = row_off[a1];
-  ColBuf d_a, d_ro, d_go;
-  QuantDrop dropper{c, {&d_a, &d_ro, &d_go}};
+  if (rows.cigar && r1 > (uint64_t)rows.n_rows) return BR_ERR_INVALID_ARG;
+  ColBuf d_a, d_ro, d_go, d_c, d_pool;
+  QuantDrop dropper{c, {&d_a, &d_ro, &d_go, &d_c, &d_pool}};
   RC(c->alloc(d_a, (size_t)(r1 - r0 + 1) * sizeof(br_row_a))); RC(c->alloc(d_ro, (size_t)(a1 - a0 + 1) * 8)); RC(c->alloc(d_go, (size_t)(ng + 1) * 4));
   hipStream_t st = c->st;
   if (r1 > r0) HIPCHK(hipMemcpyAsync(d_a.p, a + r0, (size_t)(r1 - r0) * sizeof(br_row_a), hipMemcpyHostToDevice, st));
@@ -187,24 +226,50 @@ static int quant_add_host(br_quant *c, const br_row_a *a, const uint64_t *row_of
   QAddArgs A{};
   A.a = d_a.as<uint4>(); A.a_bias = (int64_t)r0; A.row_off = d_ro.as<uint64_t>(); A.ro_bias = (int64_t)a0;
   A.group_off = d_go.as<uint32_t>(); A.n_groups = ng; A.r_first = r0; A.r_last = r1;
+  if (rows.cigar) {   // the rows' CIGAR references at the bias of a, and the whole pool: the references are offsets from its start
+    const size_t np = (size_t)rows.n_pool_words;
+    RC(c->alloc(d_c, (size_t)(r1 - r0 + 1) * 8)); RC(c->alloc(d_pool, (np + 1) * 4));
+    if (r1 > r0) HIPCHK(hipMemcpyAsync(d_c.p, rows.cigar + r0, (size_t)(r1 - r0) * 8, hipMemcpyHostToDevice, st));
+    if (np) HIPCHK(hipMemcpyAsync(d_pool.p, rows.pool, np * 4, hipMemcpyHostToDevice, st));
+    A.cigar = d_c.as<uint64_t>(); A.pool = d_pool.as<uint32_t>(); A.n_pool_words = np;
+  }
   return quant_add_names(c, A);   // (it waits for the stream: the uploads are done when the host arrays go)
+}
+
+static int quant_add(br_quant *c, const br_device_rows &rows, const uint32_t *group_off, int64_t n_groups, int on_device, void *stream) {
+  if (n_groups == 0) return BR_OK;
+  auto t0 = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(c->device));
+  const int rc = on_device ? quant_add_device(c, rows, group_off, n_groups, (hipStream_t)stream) : quant_add_host(c, rows, group_off, n_groups);
+  c->add_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
 }
 
 extern "C" int br_quant_add(br_quant *c, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t n_groups,
                             int on_device, void *stream) {
   if (!c || n_groups < 0 || c->finished || (n_groups && (!row_off || !group_off))) return BR_ERR_INVALID_ARG;
-  if (n_groups == 0) return BR_OK;
-  auto t0 = std::chrono::steady_clock::now();
-  HIPCHK(hipSetDevice(c->device));
-  const int rc = on_device ? quant_add_device(c, a, row_off, group_off, n_groups, (hipStream_t)stream) : quant_add_host(c, a, row_off, group_off, n_groups);
-  c->add_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  if (c->eff_len) return BR_ERR_INVALID_ARG;   // the fragments need the CIGARs: br_quant_add_rows
+  br_device_rows rows{};
+  rows.a = a; rows.row_off = row_off;
+  return quant_add(c, rows, group_off, n_groups, on_device, stream);
+}
+
+extern "C" int br_quant_add_rows(br_quant *c, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups, int on_device,
+                                 void *stream) {
+  if (!c || !rows || n_groups < 0 || c->finished || (n_groups && (!rows->row_off || !group_off))) return BR_ERR_INVALID_ARG;
+  br_device_rows r{};
+  r.a = rows->a; r.row_off = rows->row_off;
+  if (c->eff_len) {   // (without it: br_quant_add, and nothing else of the table is looked at)
+    if (n_groups && (!rows->cigar || rows->n_rows < 0 || rows->n_pool_words < 0 || (rows->n_pool_words && !rows->pool))) return BR_ERR_INVALID_ARG;
+    r.cigar = rows->cigar; r.pool = rows->pool; r.n_rows = rows->n_rows; r.n_pool_words = rows->n_pool_words;
+  }
+  return quant_add(c, r, group_off, n_groups, on_device, stream);
 }
 
 extern "C" int br_quant_add_last(br_quant *c, br_ctx *ctx) {
   if (!c || !ctx || !ctx->ix || ctx->ix->device != c->device) return BR_ERR_INVALID_ARG;
   if (ctx->last_n_groups == 0) return c->finished ? BR_ERR_INVALID_ARG : BR_OK;
-  return br_quant_add(c, ctx->last_rows.a, ctx->last_rows.row_off, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
+  return br_quant_add_rows(c, &ctx->last_rows, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
 }
 
 // scratch of the scans (over n + 1 items or the histograms) and of the OR / AND reduction (2 words a block of 256)
@@ -359,11 +424,30 @@ static int quant_finish(br_quant *c) {
   return BR_OK;
 }
 
+// "eff_len": the histogram's prefixes, then eff and w per transcript
+static int quant_eff(br_quant *c) {
+  if (!c->eff_len || c->lens.empty()) return BR_OK;
+  hipStream_t st = c->st;
+  const int64_t T = c->n_tx;
+  const uint32_t n_bins = (uint32_t)c->fld_max + 1;
+  ColBuf cs, d_lens;
+  QuantDrop dropper{c, {&cs, &d_lens}};
+  RC(c->fld_tables());
+  RC(c->alloc(c->eff, (size_t)(T + 1) * 8)); RC(c->alloc(c->w, (size_t)(T + 1) * 8));
+  RC(c->alloc(cs, (size_t)n_bins * 16)); RC(c->alloc(d_lens, (size_t)(T + 1) * 8));
+  if (T) HIPCHK(hipMemcpyAsync(d_lens.p, c->lens.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+  launch_q_fld_prefix(st, c->fld_total.as<unsigned long long>(), n_bins, cs.as<uint64_t>());
+  launch_q_efflen(st, d_lens.as<int64_t>(), T, cs.as<uint64_t>(), n_bins, c->eff.as<double>(), c->w.as<double>());
+  HIPCHK(hipStreamSynchronize(st));
+  return BR_OK;
+}
+
 extern "C" int br_quant_finish(br_quant *c, int64_t *n_names, int64_t *n_classes) {
   if (!c || c->finished) return BR_ERR_INVALID_ARG;
   auto t0 = std::chrono::steady_clock::now();
   HIPCHK(hipSetDevice(c->device));
   RC(quant_finish(c));
+  RC(quant_eff(c));
   c->finished = true;
   c->finish_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (n_names) *n_names = c->n;
@@ -384,6 +468,31 @@ extern "C" int br_quant_classes(br_quant *c, uint64_t *label_off, uint32_t *labe
   return BR_OK;
 }
 
+extern "C" int br_quant_fld(br_quant *c, uint64_t *hist, uint64_t *n_obs, uint64_t *n_no_fragment, uint64_t *n_out_of_range) {
+  if (!c) return BR_ERR_INVALID_ARG;
+  const size_t n_bins = (size_t)c->fld_max + 1;
+  uint64_t side[Q_FLD_SIDE] = {0, 0, 0};
+  if (hist) memset(hist, 0, n_bins * 8);
+  if (c->fld_total.p) {   // (no table yet: nothing was counted)
+    HIPCHK(hipSetDevice(c->device));
+    if (hist) HIPCHK(hipMemcpyAsync(hist, c->fld_total.p, n_bins * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(side, c->fld_total.as<uint64_t>() + n_bins, sizeof(side), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+  }
+  if (n_obs) *n_obs = side[0];
+  if (n_no_fragment) *n_no_fragment = side[1];
+  if (n_out_of_range) *n_out_of_range = side[2];
+  return BR_OK;
+}
+
+extern "C" int br_quant_eff_lengths(br_quant *c, double *eff) {
+  if (!c || !eff || !c->finished || !c->eff_len || c->lens.empty()) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  if (c->n_tx) HIPCHK(hipMemcpyAsync(eff, c->eff.p, (size_t)c->n_tx * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return BR_OK;
+}
+
 static double quant_weight(const br_quant *c, int64_t t) {
   if (!c->length_norm) return 1.0;
   return c->lens[(size_t)t] > 0 ? 1.0 / (double)c->lens[(size_t)t] : 0.0;   // (a transcript of length <= 0 has no reads: finish saw to it)
@@ -391,6 +500,7 @@ static double quant_weight(const br_quant *c, int64_t t) {
 
 extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
   if (!c || !c->finished) return BR_ERR_INVALID_ARG;
+  if (c->eff_len && (!c->length_norm || c->lens.empty())) return BR_ERR_INVALID_ARG;   // effective lengths are a length normalisation
   auto t0 = std::chrono::steady_clock::now();
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->st;
@@ -398,12 +508,17 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
   const size_t t1 = (size_t)T + 1;
   for (int k = 0; k < 2; k++) { RC(c->alloc(c->theta[k], t1 * 8)); RC(c->alloc(c->x[k], t1 * 8)); }
   RC(c->alloc(c->w, t1 * 8)); RC(c->alloc(c->qv, (size_t)(C + 1) * 8));
-  std::vector<double> one((size_t)T, 1.0), w((size_t)T);
-  for (int64_t t = 0; t < T; t++) w[(size_t)t] = quant_weight(c, t);
-  if (T) {
-    HIPCHK(hipMemcpyAsync(c->theta[0].p, one.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->x[0].p, w.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));   // theta w at theta = 1
-    HIPCHK(hipMemcpyAsync(c->w.p, w.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+  std::vector<double> one((size_t)T, 1.0), w;
+  if (T) HIPCHK(hipMemcpyAsync(c->theta[0].p, one.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+  if (c->eff_len) {   // w = 1 / eff is on the device since finish (k_q_efflen)
+    if (T) HIPCHK(hipMemcpyAsync(c->x[0].p, c->w.p, (size_t)T * 8, hipMemcpyDeviceToDevice, st));
+  } else {
+    w.resize((size_t)T);
+    for (int64_t t = 0; t < T; t++) w[(size_t)t] = quant_weight(c, t);
+    if (T) {
+      HIPCHK(hipMemcpyAsync(c->x[0].p, w.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));   // theta w at theta = 1
+      HIPCHK(hipMemcpyAsync(c->w.p, w.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+    }
   }
   QEmArgs E{};
   E.n_cls = C; E.n_tx = T; E.label_off = c->c_loff.as<uint64_t>(); E.labels = c->c_labels.as<uint32_t>(); E.cnt = c->c_cnt.as<uint64_t>();

@@ -23,10 +23,27 @@ struct QAddArgs {
   uint32_t *big; uint32_t *n_big;   // names of more than Q_SMALL_ROWS rows: k_q_names lists them, k_q_names_big takes them
   uint32_t *max_tid;          // the largest transcript id met so far (atomicMax)
   uint32_t *bad;              // a name whose rows leave [r_first, r_last): nothing is written for it
+  // the fragment pass (launch_q_frag; "eff_len"): the rows' CIGAR references, at the bias of a, and the pool they point into
+  const uint64_t *cigar; const uint32_t *pool; uint64_t n_pool_words;
+  uint32_t fld_max;
+  unsigned long long *stage;  // the add's own histogram, fld_max + 1 bins, then observations / unique names without a fragment /
+                              // lengths out of range (Q_FLD_SIDE words); *bad |= 1 for a pooled CIGAR that leaves the pool
 };
+constexpr int Q_FLD_SIDE = 3;             // words behind a histogram: n_obs, n_no_fragment, n_out_of_range
+constexpr uint32_t Q_FLD_LDS_BINS = 8192; // up to this many bins a block counts in LDS (32 KiB of counters); above, in the table itself
+constexpr uint32_t Q_EFF_LDS_BINS = 2048; // up to this many bins k_q_efflen keeps C and S in LDS (32 KiB); above, it loads them from HBM
 // span[0] = row_off[group_off[0]], span[1] = row_off[group_off[n_groups]] of device tables
 void launch_q_span(hipStream_t st, const uint64_t *row_off, const uint32_t *group_off, int64_t n_groups, uint64_t *span);
 void launch_q_names(hipStream_t st, const QAddArgs &A);
+// after launch_q_names of the same add (nk and the list of big names are its): per read name of one label its first fragment's
+// length into A.stage (definitions: bramble_amd.h, br_quant)
+void launch_q_frag(hipStream_t st, const QAddArgs &A);
+// total[i] += stage[i]; stage[i] = 0, over fld_max + 1 + Q_FLD_SIDE words
+void launch_q_fld_commit(hipStream_t st, unsigned long long *stage, unsigned long long *total, uint32_t n_words);
+// cs[f] = C(f), cs[n_bins + f] = S(f): the inclusive prefix sums of hist[f] and f * hist[f]
+void launch_q_fld_prefix(hipStream_t st, const unsigned long long *hist, uint32_t n_bins, uint64_t *cs);
+// eff[t] and w[t] = 1 / eff[t] (0 where eff is 0) from the lengths and the prefix sums
+void launch_q_efflen(hipStream_t st, const int64_t *lens, int64_t n_tx, const uint64_t *cs, uint32_t n_bins, double *eff, double *w);
 
 // finish: the assigned names (k > 0) in add order -> (hash & mask, name index)
 void launch_q_flag(hipStream_t st, const uint32_t *nk, int64_t n, uint64_t *flag);

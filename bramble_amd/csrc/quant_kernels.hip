@@ -9,6 +9,10 @@
 //   table    radix passes over (transcript, label entry) + k_q_transpose: per transcript its classes, ascending; k_q_bin;
 //            k_q_counts: unique / ambiguous names per transcript
 //   EM       k_q_em_classes / k_q_em_tx, a lane per item of up to Q_WAVE_ITEMS entries and a wave per larger one
+//   lengths  ("eff_len") k_q_frag / k_q_frag_big behind the names of an add: per read name of one label the length of its first
+//            fragment, counted in LDS by integer atomics and flushed to the add's own table with one integer atomicAdd per
+//            non-zero bin and block; k_q_fld_commit adds a good add's table to the run's; at finish k_q_fld_prefix (C and S) and
+//            k_q_efflen (eff and w per transcript)
 //
 // No floating-point atomic anywhere: every sum is one lane's loop in ascending order, or a wave's -- lane l takes the entries
 // l, l + 64, ... in ascending order, then the 64 partial sums meet in a fixed xor tree -- so its shape depends on the number of
@@ -16,6 +20,7 @@
 // the doubles' bit patterns (a maximum does not depend on the order it is taken in).
 #include <hip/hip_runtime.h>
 
+#include "../../include/bramble_amd.h"
 #include "collate_kernels.h"
 #include "quant_kernels.h"
 
@@ -138,6 +143,212 @@ __global__ void __launch_bounds__(256) k_q_names_big(QAddArgs A) {
       if (k) atomicMax(A.max_tid, (uint32_t)prev);
     }
   }
+}
+
+// ---- fragment lengths ("eff_len"; the definitions: bramble_amd.h, br_quant) --------------------------------------------------------
+namespace {
+typedef uint32_t q_u4 __attribute__((ext_vector_type(4)));
+constexpr uint32_t Q_LEAD = BR_ROW_PAIRED | BR_ROW_SAME_TX | BR_ROW_FIRST;
+constexpr uint64_t Q_NO_ROW = ~0ull;
+// the rows are read once here: non-temporal, as the projection's other consumers take them
+__device__ __forceinline__ q_u4 row_a(const QAddArgs &A, uint64_t r) { return __builtin_nontemporal_load((const q_u4 *)A.a + ((int64_t)r - A.a_bias)); }
+__device__ __forceinline__ uint64_t row_cigar(const QAddArgs &A, uint64_t r) { return __builtin_nontemporal_load(A.cigar + ((int64_t)r - A.a_bias)); }
+// (the definition's three conditions on the neighbour; on a name of one label, the only kind looked at, its transcript is the leader's anyway)
+__device__ __forceinline__ bool is_fragment(const q_u4 lead, const q_u4 mate) {
+  return (lead.z & Q_LEAD) == Q_LEAD && (mate.z & (BR_ROW_PAIRED | BR_ROW_FIRST)) == BR_ROW_PAIRED && mate.x == lead.x;
+}
+// reference bases of one op: M D N = X (0, 2, 3, 7, 8) consume the reference
+__device__ __forceinline__ uint64_t ref_len(uint32_t w) { return (0x18du >> (w & 15u)) & 1u ? (uint64_t)(w >> 4) : 0ull; }
+__device__ __forceinline__ uint64_t ref_len_inline(uint64_t c, uint32_t n) {
+  return (n >= 1u ? ref_len((uint32_t)c) : 0ull) + (n >= 2u ? ref_len((uint32_t)(c >> 32)) : 0ull);
+}
+__device__ __forceinline__ bool in_pool(const QAddArgs &A, uint64_t off, uint32_t n) { return off <= A.n_pool_words && (uint64_t)n <= A.n_pool_words - off; }
+__device__ __forceinline__ void count_length(const QAddArgs &A, uint32_t *sh_hist, bool lds, uint64_t lo, uint64_t hi, uint32_t &n_obs, uint32_t &n_oor) {
+  const uint64_t len = hi - lo;
+  if (len == 0 || len > (uint64_t)A.fld_max) { n_oor++; return; }
+  n_obs++;
+  if (lds) atomicAdd(sh_hist + len, 1u); else atomicAdd(A.stage + len, 1ull);
+}
+__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
+  for (int s = 32; s; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s);
+  return v;
+}
+// the block's counts leave it once: the side counters through LDS, then one integer atomicAdd per non-zero word of the block
+__device__ __forceinline__ void frag_flush(const QAddArgs &A, uint32_t *sh_hist, uint32_t *sh_side, bool lds, uint32_t n_obs, uint32_t n_nofrag,
+                                           uint32_t n_oor, bool is_bad) {
+  n_obs = wave_sum32(n_obs); n_nofrag = wave_sum32(n_nofrag); n_oor = wave_sum32(n_oor);
+  if ((threadIdx.x & 63) == 0) {
+    if (n_obs) atomicAdd(sh_side + 0, n_obs);
+    if (n_nofrag) atomicAdd(sh_side + 1, n_nofrag);
+    if (n_oor) atomicAdd(sh_side + 2, n_oor);
+  }
+  if (__ballot(is_bad) && is_bad) *A.bad = 1;
+  __syncthreads();
+  const uint32_t n_bins = A.fld_max + 1u;
+  if (lds) for (uint32_t i = threadIdx.x; i < n_bins; i += 256) { const uint32_t v = sh_hist[i]; if (v) atomicAdd(A.stage + i, (unsigned long long)v); }
+  if (threadIdx.x < Q_FLD_SIDE && sh_side[threadIdx.x]) atomicAdd(A.stage + n_bins + threadIdx.x, (unsigned long long)sh_side[threadIdx.x]);
+}
+__device__ __forceinline__ void frag_begin(const QAddArgs &A, uint32_t *sh_hist, uint32_t *sh_side, bool lds) {
+  if (lds) for (uint32_t i = threadIdx.x; i <= A.fld_max; i += 256) sh_hist[i] = 0;
+  if (threadIdx.x < Q_FLD_SIDE) sh_side[threadIdx.x] = 0;
+  __syncthreads();
+}
+}  // namespace
+
+// one lane per read name of one label and at most Q_SMALL_ROWS rows; a pooled CIGAR of more than 64 ops is summed by the wave
+template <bool LDS>
+__global__ void __launch_bounds__(256) k_q_frag(QAddArgs A) {
+  extern __shared__ uint32_t sh_hist[];
+  __shared__ uint32_t sh_side[Q_FLD_SIDE];
+  frag_begin(A, sh_hist, sh_side, LDS);
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  bool unique = false, found = false, is_bad = false;
+  uint64_t pos[2] = {0, 0}, ref[2] = {0, 0}, wide_off[2] = {0, 0};
+  uint32_t wide_n[2] = {0, 0};   // a CIGAR left to the wave
+  if (g < A.n_groups && A.nk[g] == 1u) {
+    uint64_t r0, r1;
+    if (name_rows(A, g, r0, r1) && r1 - r0 <= (uint64_t)Q_SMALL_ROWS) {   // (one label: it has a row)
+      unique = true;
+      uint64_t fr = 0;
+      q_u4 lead = row_a(A, r0), mate = lead;
+      for (uint64_t r = r0; r + 1 < r1; r++) {
+        mate = row_a(A, r + 1);
+        if (is_fragment(lead, mate)) { found = true; fr = r; break; }
+        lead = mate;
+      }
+      if (found) {
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          const q_u4 m = j ? mate : lead;
+          const uint32_t n = BR_ROW_NCIGAR(m.z);
+          const uint64_t c = row_cigar(A, fr + (uint64_t)j);
+          pos[j] = m.y;
+          if (n <= 2u) ref[j] = ref_len_inline(c, n);
+          else if (!in_pool(A, c, n)) is_bad = true;
+          else if (n <= 64u) { uint64_t s = 0; for (uint32_t k = 0; k < n; k++) s += ref_len(A.pool[c + k]); ref[j] = s; }
+          else { wide_off[j] = c; wide_n[j] = n; }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    uint64_t todo = __ballot(wide_n[j] != 0u && !is_bad);
+    while (todo) {
+      const int src = __ffsll((unsigned long long)todo) - 1;
+      todo &= todo - 1;
+      const uint64_t off = __shfl(wide_off[j], src);
+      const uint32_t n = (uint32_t)__shfl((int)wide_n[j], src);
+      uint64_t s = 0;
+      for (uint32_t k = (uint32_t)lane; k < n; k += 64u) s += ref_len(A.pool[off + k]);
+      s = wave_sum(s);
+      if (lane == src) ref[j] = s;
+    }
+  }
+  uint32_t n_obs = 0, n_oor = 0;
+  if (found && !is_bad) {
+    const uint64_t lo = pos[0] < pos[1] ? pos[0] : pos[1], e0 = pos[0] + ref[0], e1 = pos[1] + ref[1];
+    count_length(A, sh_hist, LDS, lo, e0 > e1 ? e0 : e1, n_obs, n_oor);
+  }
+  frag_flush(A, sh_hist, sh_side, LDS, n_obs, unique && !found ? 1u : 0u, n_oor, is_bad);
+}
+
+// one wave per listed name (the list k_q_names made of the names of more than Q_SMALL_ROWS rows), grid-stride: the lanes scan the
+// rows in strides of 64 (one load a row; the neighbour by shuffle), the lowest row that leads a fragment is a wave minimum, and the
+// wave sums the two CIGARs
+template <bool LDS>
+__global__ void __launch_bounds__(256) k_q_frag_big(QAddArgs A) {
+  extern __shared__ uint32_t sh_hist[];
+  __shared__ uint32_t sh_side[Q_FLD_SIDE];
+  frag_begin(A, sh_hist, sh_side, LDS);
+  const int lane = threadIdx.x & 63;
+  const uint32_t n_big = *A.n_big;
+  uint32_t n_obs = 0, n_nofrag = 0, n_oor = 0;   // (lane 0 counts for the wave)
+  bool is_bad = false;
+  for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n_big; i += gridDim.x * 4) {
+    const int64_t g = A.big[i];
+    if (A.nk[g] != 1u) continue;   // (wave-uniform, as everything below that branches)
+    uint64_t r0, r1;
+    (void)name_rows(A, g, r0, r1);
+    uint64_t fr = Q_NO_ROW;
+    for (uint64_t base = r0; fr == Q_NO_ROW && base + 1 < r1; base += 64) {
+      // a row is loaded once: the neighbour's transcript and meta come from the next lane, lane 63's from the stride's edge
+      const uint64_t r = base + (uint64_t)lane;
+      q_u4 lead = {0u, 0u, 0u, 0u}, mate = {0u, 0u, 0u, 0u};
+      if (r < r1) lead = row_a(A, r);
+      mate.x = (uint32_t)__shfl_down((int)lead.x, 1); mate.z = (uint32_t)__shfl_down((int)lead.z, 1);
+      if (lane == 63 && r + 1 < r1) mate = row_a(A, r + 1);
+      fr = wave_min(r + 1 < r1 && is_fragment(lead, mate) ? r : Q_NO_ROW);
+    }
+    if (fr == Q_NO_ROW) { if (lane == 0) n_nofrag++; continue; }
+    uint64_t pos[2], ref[2];
+    bool ok = true;
+    for (int j = 0; j < 2; j++) {
+      const q_u4 m = row_a(A, fr + (uint64_t)j);
+      const uint32_t n = BR_ROW_NCIGAR(m.z);
+      const uint64_t c = row_cigar(A, fr + (uint64_t)j);
+      pos[j] = m.y; ref[j] = 0;
+      if (n <= 2u) ref[j] = ref_len_inline(c, n);
+      else if (!in_pool(A, c, n)) ok = false;
+      else {
+        uint64_t s = 0;
+        for (uint32_t k = (uint32_t)lane; k < n; k += 64u) s += ref_len(A.pool[c + k]);
+        ref[j] = wave_sum(s);
+      }
+    }
+    if (!ok) { is_bad = true; continue; }
+    if (lane == 0) {
+      const uint64_t lo = pos[0] < pos[1] ? pos[0] : pos[1], e0 = pos[0] + ref[0], e1 = pos[1] + ref[1];
+      count_length(A, sh_hist, LDS, lo, e0 > e1 ? e0 : e1, n_obs, n_oor);
+    }
+  }
+  frag_flush(A, sh_hist, sh_side, LDS, n_obs, n_nofrag, n_oor, is_bad);
+}
+
+__global__ void __launch_bounds__(256) k_q_fld_commit(unsigned long long *stage, unsigned long long *total, uint32_t n_words) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_words) return;
+  const unsigned long long v = stage[i];
+  if (v) { total[i] += v; stage[i] = 0; }
+}
+
+// one block: thread k takes bins [k * per, (k + 1) * per), the 256 partial sums are scanned by thread 0 (integers: exact in any order)
+__global__ void __launch_bounds__(256) k_q_fld_prefix(const unsigned long long *hist, uint32_t n_bins, uint64_t *cs) {
+  __shared__ uint64_t sh_c[256], sh_s[256];
+  const uint32_t per = (n_bins + 255u) / 256u, b = threadIdx.x * per, e = b + per < n_bins ? b + per : n_bins;
+  uint64_t c = 0, s = 0;
+  for (uint32_t f = b; f < e; f++) { c += hist[f]; s += (uint64_t)f * hist[f]; }
+  sh_c[threadIdx.x] = c; sh_s[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t tc = 0, ts = 0;
+    for (int k = 0; k < 256; k++) { const uint64_t vc = sh_c[k], vs = sh_s[k]; sh_c[k] = tc; sh_s[k] = ts; tc += vc; ts += vs; }
+  }
+  __syncthreads();
+  c = sh_c[threadIdx.x]; s = sh_s[threadIdx.x];
+  for (uint32_t f = b; f < e; f++) { c += hist[f]; s += (uint64_t)f * hist[f]; cs[f] = c; cs[n_bins + f] = s; }
+}
+
+// one lane per transcript: eff = ((L + 1) C(x) - S(x)) / C(x) at x = min(L, fld_max), L where C(x) is 0; w = 1 / eff
+template <bool LDS>
+__global__ void __launch_bounds__(256) k_q_efflen(const int64_t *lens, int64_t n_tx, const uint64_t *cs, uint32_t n_bins, double *eff, double *w) {
+  extern __shared__ uint64_t sh_cs[];
+  if (LDS) {
+    for (uint32_t i = threadIdx.x; i < 2u * n_bins; i += 256) sh_cs[i] = cs[i];
+    __syncthreads();
+  }
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_tx) return;
+  const uint64_t *tab = LDS ? sh_cs : cs;
+  const int64_t len = lens[t];
+  double e = 0.0;
+  if (len > 0) {
+    const uint64_t x = (uint64_t)len < (uint64_t)(n_bins - 1u) ? (uint64_t)len : (uint64_t)(n_bins - 1u);
+    const uint64_t c = tab[x], s = tab[n_bins + x];
+    e = c == 0 ? (double)len : (double)(((uint64_t)len + 1ull) * c - s) / (double)c;
+  }
+  eff[t] = e; w[t] = e > 0.0 ? 1.0 / e : 0.0;
 }
 
 __global__ void __launch_bounds__(256) k_q_flag(const uint32_t *nk, int64_t n, uint64_t *flag) {
@@ -352,6 +563,31 @@ void launch_q_names(hipStream_t st, const QAddArgs &A) {
   hipLaunchKernelGGL(k_q_names, dim3(blocks256(A.n_groups)), dim3(256), 0, st, A);
   const int64_t most = (A.n_groups + 3) / 4;   // (the list is no longer than the names)
   hipLaunchKernelGGL(k_q_names_big, dim3((unsigned)(most < (int64_t)Q_BIG_GRID ? most : (int64_t)Q_BIG_GRID)), dim3(256), 0, st, A);
+}
+void launch_q_frag(hipStream_t st, const QAddArgs &A) {
+  if (A.n_groups <= 0) return;
+  const bool lds = A.fld_max < Q_FLD_LDS_BINS;
+  const size_t sh = lds ? (size_t)(A.fld_max + 1u) * 4 : 0;
+  const int64_t most = (A.n_groups + 3) / 4;
+  const dim3 big_grid((unsigned)(most < (int64_t)Q_BIG_GRID ? most : (int64_t)Q_BIG_GRID));
+  if (lds) {
+    hipLaunchKernelGGL(k_q_frag<true>, dim3(blocks256(A.n_groups)), dim3(256), sh, st, A);
+    hipLaunchKernelGGL(k_q_frag_big<true>, big_grid, dim3(256), sh, st, A);
+  } else {
+    hipLaunchKernelGGL(k_q_frag<false>, dim3(blocks256(A.n_groups)), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_q_frag_big<false>, big_grid, dim3(256), 0, st, A);
+  }
+}
+void launch_q_fld_commit(hipStream_t st, unsigned long long *stage, unsigned long long *total, uint32_t n_words) {
+  hipLaunchKernelGGL(k_q_fld_commit, dim3(blocks256(n_words)), dim3(256), 0, st, stage, total, n_words);
+}
+void launch_q_fld_prefix(hipStream_t st, const unsigned long long *hist, uint32_t n_bins, uint64_t *cs) {
+  hipLaunchKernelGGL(k_q_fld_prefix, dim3(1), dim3(256), 0, st, hist, n_bins, cs);
+}
+void launch_q_efflen(hipStream_t st, const int64_t *lens, int64_t n_tx, const uint64_t *cs, uint32_t n_bins, double *eff, double *w) {
+  if (n_tx <= 0) return;
+  if (n_bins <= Q_EFF_LDS_BINS) hipLaunchKernelGGL(k_q_efflen<true>, dim3(blocks256(n_tx)), dim3(256), (size_t)n_bins * 16, st, lens, n_tx, cs, n_bins, eff, w);
+  else hipLaunchKernelGGL(k_q_efflen<false>, dim3(blocks256(n_tx)), dim3(256), 0, st, lens, n_tx, cs, n_bins, eff, w);
 }
 void launch_q_flag(hipStream_t st, const uint32_t *nk, int64_t n, uint64_t *flag) {
   if (n > 0) hipLaunchKernelGGL(k_q_flag, dim3(blocks256(n)), dim3(256), 0, st, nk, n, flag);

@@ -176,8 +176,8 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_collator_stats", "br_collator_free",
            "br_sorter_new", "br_sorter_set_param", "br_sorter_add", "br_sorter_finish", "br_sorter_next", "br_sorter_order", "br_sorter_stats",
            "br_sorter_index", "br_sorter_free", "br_ctx_last_device_bam", "br_device_bam_download",
-           "br_quant_new", "br_quant_set_param", "br_quant_set_tolerance", "br_quant_add", "br_quant_add_last", "br_quant_finish",
-           "br_quant_classes", "br_quant_em", "br_quant_result", "br_quant_stats", "br_quant_free",
+           "br_quant_new", "br_quant_set_param", "br_quant_set_tolerance", "br_quant_add", "br_quant_add_rows", "br_quant_add_last", "br_quant_finish",
+           "br_quant_classes", "br_quant_em", "br_quant_result", "br_quant_fld", "br_quant_eff_lengths", "br_quant_stats", "br_quant_free",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -1177,7 +1177,10 @@ class Quant:
         L.br_quant_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         L.br_quant_set_tolerance.argtypes = [C.c_void_p, C.c_double]
         L.br_quant_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+        L.br_quant_add_rows.argtypes = [C.c_void_p, _P(BrDeviceRows), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         L.br_quant_add_last.argtypes = [C.c_void_p, C.c_void_p]
+        L.br_quant_fld.argtypes = [C.c_void_p, C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]
+        L.br_quant_eff_lengths.argtypes = [C.c_void_p, C.c_void_p]
         L.br_quant_finish.argtypes = [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]
         L.br_quant_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.br_quant_em.argtypes = [C.c_void_p, _P(C.c_int32), _P(C.c_double)]
@@ -1189,6 +1192,7 @@ class Quant:
         self.device = device
         self.n_transcripts = int(n_transcripts)
         self.n_names = self.n_classes = 0
+        self.fld_max = 1000
         lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64)
         assert lens is None or lens.size == self.n_transcripts
         h = C.c_void_p()
@@ -1198,11 +1202,13 @@ class Quant:
             self.set_param("length_norm", 0)
 
     def set_param(self, name, value):
-        """"hash_bits", "length_norm", "max_iters" (integers) or "tolerance" (a float)."""
+        """"hash_bits", "length_norm", "max_iters", "eff_len", "fld_max" (integers) or "tolerance" (a float)."""
         if name == "tolerance":
             check(lib().br_quant_set_tolerance(self.h, float(value)), "br_quant_set_tolerance")
         else:
             check(lib().br_quant_set_param(self.h, name.encode(), int(value)), "br_quant_set_param")
+            if name == "fld_max":
+                self.fld_max = int(value)
 
     def add_raw(self, a, row_off, group_off, n_groups, on_device, stream=None):
         """br_quant_add as it is: the return code (0, or a BR_ERR_* value)."""
@@ -1224,6 +1230,34 @@ class Quant:
         g1 = group_off.numel() - 1 if g1 is None else g1
         check(self.add_raw(rows_a.data_ptr(), row_off.data_ptr(), group_off.data_ptr() + 4 * g0, g1 - g0, True,
                            torch.cuda.current_stream(row_off.device).cuda_stream), "br_quant_add")
+
+    def add_rows_raw(self, a, cigar, pool, row_off, n_rows, n_pool_words, group_off, n_groups, on_device, stream=None):
+        """br_quant_add_rows as it is (the tables as addresses): the return code (0, or a BR_ERR_* value)."""
+        rows = BrDeviceRows()
+        rows.n_rows, rows.n_pool_words = int(n_rows), int(n_pool_words)
+        rows.a, rows.cigar, rows.pool, rows.row_off = a, cigar, pool, row_off
+        return lib().br_quant_add_rows(self.h, C.byref(rows), C.c_void_p(group_off), int(n_groups), 1 if on_device else 0,
+                                       C.c_void_p(stream or 0))
+
+    def add_rows_host(self, rows_a, cigar, pool, row_off, group_off):
+        """add_host with the whole row table: cigar uint64 [n_rows] (the ops themselves up to two, else an offset into pool),
+        pool uint32, in host memory."""
+        a = np.ascontiguousarray(rows_a, dtype=np.uint32).reshape(-1, 4)
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        pl = np.ascontiguousarray(pool, dtype=np.uint32)
+        ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+        go = np.ascontiguousarray(group_off, dtype=np.uint32)
+        assert len(cg) == len(a)
+        check(self.add_rows_raw(a.ctypes.data if a.size else None, cg.ctypes.data, pl.ctypes.data if pl.size else None, ro.ctypes.data,
+                                len(a), len(pl), go.ctypes.data, len(go) - 1, False), "br_quant_add_rows")
+
+    def add_rows_device(self, rows_a, cigar, pool, row_off, group_off, g0=0, g1=None):
+        """The same tables as torch CUDA tensors (cigar int64, pool int32); the read names [g0, g1) of them are added."""
+        import torch
+        g1 = group_off.numel() - 1 if g1 is None else g1
+        check(self.add_rows_raw(rows_a.data_ptr(), cigar.data_ptr(), pool.data_ptr() if pool.numel() else None, row_off.data_ptr(),
+                                cigar.numel(), pool.numel(), group_off.data_ptr() + 4 * g0, g1 - g0, True,
+                                torch.cuda.current_stream(row_off.device).cuda_stream), "br_quant_add_rows")
 
     def add_last(self, ctx):
         """The read names of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
@@ -1260,6 +1294,20 @@ class Quant:
         check(lib().br_quant_result(self.h, out["theta"].ctypes.data if em else None, out["tpm"].ctypes.data if em else None,
                                     out["unique"].ctypes.data, out["ambig"].ctypes.data), "br_quant_result")
         return {k: v[:self.n_transcripts] for k, v in out.items()}
+
+    def fld(self):
+        """-> dict of hist (uint64 [fld_max + 1]: observed fragment lengths of the read names of one label) and n_obs,
+        n_no_fragment, n_out_of_range, of the adds so far"""
+        hist = np.zeros(self.fld_max + 1, dtype=np.uint64)
+        n, u, r = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().br_quant_fld(self.h, hist.ctypes.data, C.byref(n), C.byref(u), C.byref(r)), "br_quant_fld")
+        return {"hist": hist, "n_obs": int(n.value), "n_no_fragment": int(u.value), "n_out_of_range": int(r.value)}
+
+    def eff_lengths(self):
+        """-> float64 per transcript: the effective lengths ("eff_len" = 1, after finish)"""
+        eff = np.zeros(max(self.n_transcripts, 1), dtype=np.float64)
+        check(lib().br_quant_eff_lengths(self.h, eff.ctypes.data), "br_quant_eff_lengths")
+        return eff[:self.n_transcripts]
 
     def stats(self):
         h, p, co = C.c_uint64(), C.c_uint64(), C.c_uint64()

@@ -664,8 +664,24 @@ void br_sorter_free(br_sorter *);
  *                  of 16, and after the last one, the relative change is the maximum over t with theta'_t > 1e-8 of
  *                  |theta'_t - theta_t| / theta'_t; the run stops when that is < tolerance, or at max_iters (tolerance = 0 runs
  *                  exactly max_iters iterations).  Defaults: max_iters 10000, tolerance 1e-2 (salmon's minAlpha /
- *                  relDiffTolerance convention).  TPM_t = 1e6 theta_t w_t / sum of theta w.  Not modelled: fragment lengths,
- *                  sequence or position bias, bootstraps
+ *                  relDiffTolerance convention).  TPM_t = 1e6 theta_t w_t / sum of theta w.  Not modelled: sequence or position
+ *                  bias, bootstraps
+ *   fragment       ("eff_len" = 1; salmon's and kallisto's truncated-mean effective length.)  A row r with BR_ROW_PAIRED |
+ *                  BR_ROW_SAME_TX | BR_ROW_FIRST all set, together with row r + 1, which must lie inside the same read name's rows,
+ *                  have BR_ROW_PAIRED set and BR_ROW_FIRST clear, and carry the same transcript_id.  A row that fails any of these
+ *                  is not a fragment; nothing outside the name's rows is read.  reflen(row) = the sum of the lengths of the row's
+ *                  rewritten CIGAR ops that consume the reference (M D N = X: op codes 0, 2, 3, 7, 8), taken from cigar[row] itself
+ *                  when BR_ROW_NCIGAR(meta) <= 2, else from pool[cigar[row] ...].  The fragment's length is
+ *                  max(pos_r + reflen_r, pos_r+1 + reflen_r+1) - min(pos_r, pos_r+1), in 64-bit arithmetic
+ *   observation    only read names whose transcript set has exactly one label contribute, each at most one observation: its
+ *                  fragment of lowest row index.  Such a name without a fragment counts in n_no_fragment; a length of 0 or above
+ *                  "fld_max" counts in n_out_of_range and not in the histogram.  hist[f], f = 0 .. fld_max, is the number of
+ *                  observations of length f (uint64) and n_obs their sum.  How the adds were cut into calls changes nothing
+ *   eff. length    C(x) = sum over f <= x of hist[f], S(x) = sum over f <= x of f hist[f], both uint64.  For a transcript of length
+ *                  L > 0 and x = min(L, fld_max): eff = (double)L when C(x) == 0 (no pairs at all, long reads, a transcript shorter
+ *                  than every observed fragment), else eff = (double)((L + 1) C(x) - S(x)) / (double)C(x), one correctly rounded
+ *                  division of two exact integers: L - E[f | f <= L] + 1, always >= 1, the same bits on every machine.  L <= 0
+ *                  gives eff = 0.  With "eff_len" on the EM's w[t] = 1 / eff[t], and 0 where eff is 0; everything else is unchanged
  *   numerics       float64 throughout, no floating-point atomics: a class's sum runs over its labels in ascending order, a
  *                  transcript's over its classes in ascending order through a transposed membership table; items of more than 64
  *                  entries are summed by a wave (lane l takes entries l, l + 64, ..., then a fixed tree), so the shape of every sum
@@ -674,34 +690,49 @@ void br_sorter_free(br_sorter *);
  *                       without the device
  *   br_quant_set_param  before finish: "hash_bits" (test hook: 1..64 bits of the label hash are kept, so that different sets
  *                       collide; the result does not change), "length_norm" 0 / 1 (default 1), "max_iters", "tolerance_ppm"
- *                       (tolerance in millionths; br_quant_set_tolerance takes the double itself)
+ *                       (tolerance in millionths; br_quant_set_tolerance takes the double itself); before the first add only, a
+ *                       refused one with "eff_len" on included (the histogram is sized by then):
+ *                       "eff_len" 0 / 1 (default 0: the fragment-length model above), "fld_max" 1 .. 65535 (default 1000, salmon's
+ *                       fragLenDistMax)
  *   br_quant_add        the read names group_off[0 .. n_groups] of a batch: a / row_off / group_off as br_device_rows and
  *                       br_device_batch hold them (device memory with on_device != 0, read after the work queued on `stream`, NULL
  *                       for the null stream; host memory with on_device = 0).  Returns when the tables have been read.
  *                       BR_ERR_INVALID_ARG after finish, or for offsets that descend (nothing is added); BR_ERR_CAPACITY when the
- *                       device's memory does not take it or the names would number 2^32 or more
- *   br_quant_add_last   the same for the context's last projection call, whichever entry point made it
+ *                       device's memory does not take it or the names would number 2^32 or more; BR_ERR_INVALID_ARG with
+ *                       "eff_len" on (the fragments need the CIGARs)
+ *   br_quant_add_rows   br_quant_add with the whole row table: a, cigar, pool and row_off of `rows` (n_rows and n_pool_words size the
+ *                       copies of a host table; on_device = 0 takes the same layout in host memory).  With "eff_len" off it is
+ *                       br_quant_add and reads nothing else; with it on the add also counts the fragments.  BR_ERR_INVALID_ARG, and
+ *                       nothing added, also for rows past n_rows or a pooled CIGAR reference (of a fragment) that leaves n_pool_words
+ *   br_quant_add_last   br_quant_add_rows for the context's last projection call, whichever entry point made it
  *   br_quant_finish     the classes; the numbers of names added and of classes.  BR_ERR_INVALID_ARG for a transcript_id >=
  *                       n_transcripts, or when lengths normalise and a transcript of length <= 0 (or no lengths at all) has a read
  *   br_quant_classes    host copies: label_off (n_classes + 1), labels (label_off[n_classes]), counts, first_name (the add-order
  *                       index of the class's first read name); any pointer may be NULL
- *   br_quant_em         the EM, after finish; the iterations run and the last relative change looked at
+ *   br_quant_em         the EM, after finish; the iterations run and the last relative change looked at.  BR_ERR_INVALID_ARG with
+ *                       "eff_len" on and "length_norm" off, or without lengths
+ *   br_quant_fld        host copies, any may be NULL: hist ("fld_max" + 1 entries) and the three counters, of the adds so far
+ *   br_quant_eff_lengths  eff, n_transcripts doubles; after finish, with "eff_len" on and lengths given
  *   br_quant_result     host copies, n_transcripts each, any may be NULL: theta and tpm (after em), unique and ambig (after finish)
  *   br_quant_stats      device bytes held now, the most held so far, seconds in add / finish / em, label sets met with equal
  *                       hashes and different contents, names without rows, labels over all classes (any pointer may be NULL)
  * Device memory: 4 bytes a row and 20 bytes a read name while adding; finish peaks at 32 more a name with labels, then holds 24
- * bytes a class, 8 a label and 24 a transcript; the EM adds 40 a transcript and 8 a class (quant.cpp). */
+ * bytes a class, 8 a label and 24 a transcript; the EM adds 40 a transcript and 8 a class; "eff_len" adds 16 (fld_max + 4) for the
+ * histogram (the run's and an add's own), 16 (fld_max + 1) for the prefixes during finish and 8 a transcript for eff (quant.cpp). */
 typedef struct br_quant br_quant;
 int br_quant_new(int device, int64_t n_transcripts, const int64_t *lengths, br_quant **out);
 int br_quant_set_param(br_quant *, const char *name, int64_t value);
 int br_quant_set_tolerance(br_quant *, double tolerance);
 int br_quant_add(br_quant *, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t n_groups, int on_device,
                  void *stream);
+int br_quant_add_rows(br_quant *, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups, int on_device, void *stream);
 int br_quant_add_last(br_quant *, br_ctx *);
 int br_quant_finish(br_quant *, int64_t *n_names, int64_t *n_classes);
 int br_quant_classes(br_quant *, uint64_t *label_off, uint32_t *labels, uint64_t *counts, uint64_t *first_name);
 int br_quant_em(br_quant *, int32_t *n_iters, double *rel_change);
 int br_quant_result(br_quant *, double *theta, double *tpm, uint64_t *unique, uint64_t *ambig);
+int br_quant_fld(br_quant *, uint64_t *hist, uint64_t *n_obs, uint64_t *n_no_fragment, uint64_t *n_out_of_range);
+int br_quant_eff_lengths(br_quant *, double *eff);
 int br_quant_stats(const br_quant *, uint64_t *held_bytes, uint64_t *peak_bytes, double *add_seconds, double *finish_seconds,
                    double *em_seconds, uint64_t *collisions, int64_t *n_unassigned, int64_t *n_labels);
 void br_quant_free(br_quant *);
@@ -779,7 +810,8 @@ const char *const *br_annotation_refnames(const br_annotation *);
  * [--lr|--lr-hq] [--strict] [--max-*] [--similarity-threshold] [--quiet], plus --device-deflate (default: BGZF blocks made on the
  * GPU) / --host-deflate / --compression-level N (host codec), --device-reader (default for a regular file on one device: the
  * input is inflated and split into records on the GPU, br_bam_reader) / --host-reader, --bundle-size and --device / --devices,
- * --collate, -O bam|sam, --sort [--write-index], --quant FILE [--quant-classes FILE] (br_quant above; the usage text says the rest).
+ * --collate, -O bam|sam, --sort [--write-index], --quant FILE [--quant-classes FILE] [--quant-eff-length [--quant-fld FILE]]
+ * (br_quant above; the usage text says the rest).
  * Returns the process exit code. */
 int br_cli_main(int argc, char **argv);
 /* For a process whose only job is that one call (the `bramble` binary): with `on` != 0 br_cli_main does not return after a
