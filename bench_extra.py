@@ -20,6 +20,11 @@
                                          alignments, the classes, the EM -- seconds in add / finish / em, iterations, names, classes,
                                          labels, quantifier peak device bytes per read name; then the same with the fragment-length
                                          model ("eff_len": the adds through br_quant_add_rows), as runs_eff_length
+  python bench_extra.py coverage [--reads N]  br_coverage over the rows of the bench.py workload (N pairs, default 10 M), projected once
+                                         (br_project_batch_device, timed) and resident in HBM: all rows in one add, then finish --
+                                         br_coverage_stats' add and finish seconds, rows, bases, runs, peak device bytes per base; the
+                                         same in slices of 1 M rows; and, for comparison, br_quant_add_rows with "eff_len" on over the
+                                         same rows in the same process (the same shape of pass over a, cigar and pool)
   python bench_extra.py samout [--reads N]  SAM text out: br_sam_format_device on the projected records of N pairs (default 500 000,
                                          about 1 M records: one CLI bundle) against br_bgzf_deflate_device of the same stream in the
                                          same process (ms per bundle, text GB/s), then the command line file to file with -O sam
@@ -41,7 +46,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "coverage"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
@@ -203,6 +208,57 @@ def main():
                     (runs_eff if eff_len else runs).append(run)
         print(json.dumps({"config": "quant", "pairs": n, "alignments": n_aln, "rows": n_rows, "transcripts": n_tx, "slices": len(cuts) - 1,
                           "project_s": project, "runs": runs, "runs_eff_length": runs_eff}))
+        return
+    if args.config == "coverage":
+        n = args.reads or 10_000_000
+        ann = synth.Annotation("G")
+        batch = ann.reads(n, "pe")
+        cfg = lib.make_config()
+        idx = lib.Index.from_flat(ann.flat, device=0)
+        ctx = lib.Context(idx)
+        db = brdev.upload_batch(batch)
+        n_aln, n_groups = int(db["n_aln"]), int(db["n_groups"])
+        del batch
+        n_tx = idx.num_transcripts()
+        lens = np.asarray([idx.transcript_len(t) for t in range(n_tx)], dtype=np.int64)
+        n_bases = int(np.maximum(lens, 0).sum())
+        project = []
+        for _ in range(2):   # (the second call runs on warm tables)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rows = ctx.project_batch_device(cfg, db)
+            torch.cuda.synchronize()
+            project.append(round(time.perf_counter() - t0, 4))
+        n_rows = int(rows.n_rows)
+        out = {"config": "coverage", "pairs": n, "alignments": n_aln, "rows": n_rows, "transcripts": n_tx, "bases": n_bases, "project_s": project}
+        for key, step_rows in (("runs", n_rows), ("runs_sliced", 1_000_000)):
+            runs = []
+            for step in range(args.warmup + args.steps):
+                c = lib.Coverage(lens)
+                for r0 in range(0, n_rows, max(step_rows, 1)):
+                    lib.check(c.add_rows_raw(rows.a, rows.cigar, rows.pool, rows.n_rows, rows.n_pool_words, r0, min(r0 + step_rows, n_rows), True),
+                              "br_coverage_add_rows")
+                n_runs = c.finish()
+                stt, summ = c.stats(), c.summary()
+                c.close()
+                if step >= args.warmup:
+                    runs.append({"add_s": round(stt["add_s"], 5), "finish_s": round(stt["finish_s"], 5), "adds": -(-n_rows // max(step_rows, 1)),
+                                 "n_runs": n_runs, "rows_counted": stt["rows_counted"], "clipped_bases": stt["clipped_bases"],
+                                 "aligned_bases": int(summ["aligned_bases"].sum()), "covered_bases": int(summ["covered_bases"].sum()),
+                                 "max_depth": int(summ["max_depth"].max()) if n_tx else 0,
+                                 "peak_bytes_per_base": round(stt["peak_bytes"] / max(n_bases, 1), 2)})
+            out[key] = runs
+        quant_add = []
+        for step in range(args.warmup + args.steps):   # the comparison: the quantifier's add with the fragment pass, all names in one call
+            q = lib.Quant(n_tx, lens)
+            q.set_param("eff_len", 1)
+            lib.check(q.add_rows_raw(rows.a, rows.cigar, rows.pool, rows.row_off, rows.n_rows, rows.n_pool_words, db["group_off"].data_ptr(), n_groups,
+                                     True), "br_quant_add_rows")
+            if step >= args.warmup:
+                quant_add.append(round(q.stats()["add_s"], 5))
+            q.close()
+        out["quant_eff_len_add_s"] = quant_add
+        print(json.dumps(out))
         return
     if args.config == "small":
         import subprocess

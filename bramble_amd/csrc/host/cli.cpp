@@ -13,6 +13,8 @@
 //   --quant       : the runner hands every bundle's rows, where the projection left them in HBM, to a br_quant (br_quant_add_last);
 //                   after the last bundle: classes, EM, one download, and the two text files formatted here
 //                   (--quant-eff-length: the adds count the fragment lengths as well, "eff_len"; --quant-fld: the histogram's file)
+//   --coverage    : the runner hands every bundle's rows to a br_coverage as well (br_coverage_add_last); after the last bundle: depth,
+//                   summary and runs on the device, and the bedGraph / the table formatted here from pages of br_coverage_runs
 #include <ctype.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -43,7 +45,8 @@ void usage(FILE *f) {
           " [--device-deflate | --host-deflate | --compression-level 0-9] [--device-reader | --host-reader] [--bundle-size N]\n"
           "               [--device N | --devices a,b,...] [--collate] [--sort [--write-index]]\n"
           "               [--quant <quant.tsv> [--quant-classes <eq_classes.txt>] [--quant-length-norm | --quant-no-length-norm]\n"
-          "                [--quant-eff-length [--quant-fld <fld.tsv>]]]\n\n"
+          "                [--quant-eff-length [--quant-fld <fld.tsv>]]]\n"
+          "               [--coverage <cov.bedgraph>] [--coverage-summary <cov.tsv>] [--coverage-primary]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -71,7 +74,13 @@ void usage(FILE *f) {
           "plus 1: salmon's and kallisto's convention); quant.tsv gains an EffectiveLength column behind Length.  It needs length\n"
           "normalisation: not with --quant-no-length-norm, and under --lr / --lr-hq only with --quant-length-norm.  --quant-fld FILE:\n"
           "the histogram, FragmentLength and Count for the lengths 0 .. 1000.  One more line in front of the quantified line:\n"
-          "[bramble] fragment lengths: N observed, mean M.M, U unique names without a pair, R out of range\n");
+          "[bramble] fragment lengths: N observed, mean M.M, U unique names without a pair, R out of range\n"
+          "--coverage FILE: the depth of coverage along every transcript, counted on one GPU from the projected records of the whole\n"
+          "run, as a bedGraph (name, start, end, depth; 0-based, half-open, no header; @SQ order, then ascending start; depth > 0\n"
+          "only, as bedtools genomecov -bg -split lists it).  M = X cover, D N do not; secondary records and both mates count, a base\n"
+          "both mates cover twice.  --coverage-summary FILE: one line per @SQ transcript: Name, Length, Records, AlignedBases,\n"
+          "CoveredBases, MaxDepth, MeanDepth, Breadth.  Either switch alone turns the feature on; --coverage-primary counts primary\n"
+          "records only.  One more line in front of the final report: [bramble] coverage: N records, A aligned bases on C of B bases in R runs ...\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -128,6 +137,9 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (a == "--quant-no-length-norm") o.quant_length_norm = 0;
     else if (a == "--quant-eff-length") o.quant_eff_length = true;
     else if (a == "--quant-fld") { const char *v = value(); if (!v) return -1; o.quant_fld = v; }
+    else if (a == "--coverage") { const char *v = value(); if (!v) return -1; o.coverage = v; }
+    else if (a == "--coverage-summary") { const char *v = value(); if (!v) return -1; o.coverage_summary = v; }
+    else if (a == "--coverage-primary") o.coverage_primary = true;
     else if (a == "--device") { const char *v = value(); if (!v) return -1; o.devices.assign(1, atoi(v)); }
     else if (a == "--devices") {
       const char *v = value(); if (!v) return -1;
@@ -152,6 +164,8 @@ int parse_args(int argc, char **argv, Options &o) {
   if (!o.quant_fld.empty() && !o.quant_eff_length) { fprintf(stderr, "--quant-fld needs --quant-eff-length: without it no fragment lengths are counted\n"); return -1; }
   if (o.quant_eff_length && o.quant_length_norm == 0) { fprintf(stderr, "--quant-eff-length is a length normalisation: not with --quant-no-length-norm\n"); return -1; }
   if (o.quant_eff_length && (o.cfg.lr || o.cfg.lr_hq) && o.quant_length_norm != 1) { fprintf(stderr, "--quant-eff-length under --lr / --lr-hq needs --quant-length-norm: long reads are not length-normalised by default\n"); return -1; }
+  if (o.coverage_primary && o.coverage.empty() && o.coverage_summary.empty()) { fprintf(stderr, "--coverage-primary needs --coverage or --coverage-summary\n"); return -1; }
+  if ((!o.coverage.empty() || !o.coverage_summary.empty()) && o.devices.size() > 1) { fprintf(stderr, "--coverage works on one device: give --device N, not a --devices list\n"); return -1; }
   if (o.write_index && !o.sort) { fprintf(stderr, "--write-index needs --sort: a BAI index describes a coordinate-sorted file\n"); return -1; }
   if (o.write_index && o.sam_out) { fprintf(stderr, "--write-index applies to BAM output, not to --output-fmt sam\n"); return -1; }
   if (o.write_index && o.out_bam == "-") { fprintf(stderr, "--write-index needs an output file, not standard output\n"); return -1; }
@@ -304,6 +318,9 @@ struct Run {
   double t_q_add = 0, t_q_finish = 0, t_q_em = 0;
   std::vector<double> q_eff; std::vector<uint64_t> q_fld; uint64_t q_fld_obs = 0, q_fld_nofrag = 0, q_fld_oor = 0;   // --quant-eff-length
   std::vector<double> q_theta, q_tpm; std::vector<uint64_t> q_unique, q_ambig, q_label_off, q_counts; std::vector<uint32_t> q_labels;
+  br_coverage *coverage = nullptr;   // --coverage: deliver() adds every bundle's rows; cover() runs once the input is through
+  int64_t cov_runs = 0; double t_cov_add = 0, t_cov_finish = 0;
+  std::vector<uint64_t> cov_records, cov_aligned, cov_covered; std::vector<uint32_t> cov_max;
   bool track_blocks = false;     // --write-index: the writer notes where every BGZF block of the record section starts
   std::vector<br_bgzf_span> spans;
   uint64_t stream_pos = 0;       // uncompressed record bytes written so far
@@ -326,6 +343,7 @@ struct Run {
     }
     for (auto &w : workers) { if (w->uploader.joinable()) w->uploader.join(); if (w->runner.joinable()) w->runner.join(); }
     if (quant && !fail) quantify(workers[0].get());
+    if (coverage && !fail) cover(workers[0].get());
     if (sorter && !fail) { in.join(); drain_sorted(workers[0].get()); }   // (the source's last sequence number is final after join)
     out.finish();
     in.join(); writer.join();
@@ -421,6 +439,19 @@ struct Run {
     (void)br_quant_stats(quant, nullptr, nullptr, &t_q_add, &t_q_finish, &t_q_em, nullptr, nullptr, nullptr);
     if (rc) { fprintf(stderr, "error: quantification failed on device %d: %s\n", w->device, br_strerror(rc)); raise_fail(); }
   }
+  // --coverage, after the last bundle: depth, summary and runs; the per-transcript table comes home here, the runs in pages later
+  void cover(Worker *w) {
+    auto t0 = now();
+    int rc = br_coverage_finish(coverage, &cov_runs);
+    if (!rc) {
+      const size_t nt = br_index_num_transcripts(w->ix);
+      cov_records.resize(nt + 1); cov_aligned.resize(nt + 1); cov_covered.resize(nt + 1); cov_max.resize(nt + 1);
+      rc = br_coverage_summary(coverage, cov_records.data(), cov_aligned.data(), cov_covered.data(), cov_max.data());
+    }
+    w->gpu_seconds += secs(t0, now());
+    (void)br_coverage_stats(coverage, nullptr, nullptr, nullptr, nullptr, nullptr, &t_cov_add, &t_cov_finish);
+    if (rc) { fprintf(stderr, "error: coverage failed on device %d: %s\n", w->device, br_strerror(rc)); raise_fail(); }
+  }
   br_bam_bundle args(Bundle &b) const {
     return br_bam_bundle{b.blob.data(), b.blob.size(), b.off.data(), b.len.data(), (int64_t)b.off.size(), ref_map.data(), (int32_t)ref_map.size(), out_mode()};
   }
@@ -445,6 +476,10 @@ struct Run {
     if (quant) {   // the bundle's rows are still where the projection left them: the context's next call comes after this one
       const int qrc = br_quant_add_last(quant, w->ctx);
       if (qrc) { fprintf(stderr, "error: the quantifier could not take a bundle on device %d: %s\n", w->device, br_strerror(qrc)); raise_fail(); return; }
+    }
+    if (coverage) {
+      const int crc = br_coverage_add_last(coverage, w->ctx);
+      if (crc) { fprintf(stderr, "error: the coverage could not take a bundle on device %d: %s\n", w->device, br_strerror(crc)); raise_fail(); return; }
     }
     if (sorter) {   // the records stay in HBM: into the sorter (the runner sees the bundles in order), nothing for the writer yet
       br_device_bam db;
@@ -543,7 +578,10 @@ extern "C" int br_cli_main(int argc, char **argv) {
   std::vector<std::unique_ptr<Worker>> workers;
   br_sorter *sorter = nullptr;
   br_quant *quant = nullptr;
+  br_coverage *coverage = nullptr;
   auto free_all = [&]() {
+    if (coverage) br_coverage_free(coverage);
+    coverage = nullptr;
     if (sorter) br_sorter_free(sorter);
     sorter = nullptr;
     if (quant) br_quant_free(quant);
@@ -622,6 +660,16 @@ extern "C" int br_cli_main(int argc, char **argv) {
     if (!qrc && o.quant_eff_length) qrc = br_quant_set_param(quant, "eff_len", 1);
     if (qrc) { fprintf(stderr, "error: quantifier on device %d: %s\n", o.devices[0], br_strerror(qrc)); return give_up(); }
   }
+  // --coverage: the same numbering (tid = the index's transcript, a line per @SQ transcript)
+  const bool want_cov = !o.coverage.empty() || !o.coverage_summary.empty();
+  if (want_cov) {
+    const size_t nt = br_index_num_transcripts(ix0);
+    tx_len.resize(nt);
+    for (size_t t = 0; t < nt; t++) tx_len[t] = br_index_transcript_len(ix0, (uint32_t)t);
+    int crc = br_coverage_new(o.devices[0], (int64_t)nt, tx_len.data(), &coverage);
+    if (!crc && o.coverage_primary) crc = br_coverage_set_param(coverage, "primary_only", 1);
+    if (crc) { fprintf(stderr, "error: coverage on device %d: %s\n", o.devices[0], br_strerror(crc)); return give_up(); }
+  }
   OutFile file(o.out_bam);
   if (!file.wr.open(file.tmp.c_str(), o.threads, o.level, !o.sam_out)) { fprintf(stderr, "error: %s\n", file.wr.error().c_str()); return give_up(); }
   {
@@ -634,7 +682,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
   if (!o.quiet) printf("[bramble] processing alignments :-)\n");
   double t_setup = since();
   Run run{o, *in, out, file.wr, ref_map, workers};
-  run.sorter = sorter; run.track_blocks = o.write_index; run.quant = quant;
+  run.sorter = sorter; run.track_blocks = o.write_index; run.quant = quant; run.coverage = coverage;
   run.go();
   int failed = run.fail.load();
   if (!in->err.empty()) { fprintf(stderr, in->err_at_line ? "error: %s:%s\n" : "error: %s: %s\n", o.in_bam.c_str(), in->err.c_str()); failed = 1; }
@@ -700,7 +748,52 @@ extern "C" int br_cli_main(int argc, char **argv) {
       if (!close_ok(f, qf_tmp)) failed = 1;
     }
   }
+  // the coverage's two files likewise; the bedGraph's text is made here, from pages of runs
+  const std::string cv_tmp = o.coverage + ".tmp-bramble", cs_tmp = o.coverage_summary + ".tmp-bramble";
+  uint64_t cov_n = 0, cov_a = 0, cov_c = 0, cov_b = 0;
+  if (!failed && coverage) {
+    const size_t nt = tx_len.size();
+    auto close_ok = [&](FILE *f, const std::string &p) {
+      const bool bad = !f || ferror(f);
+      if (f && fclose(f) != 0) { fprintf(stderr, "error: could not write %s\n", p.c_str()); return false; }
+      if (bad) fprintf(stderr, "error: could not write %s\n", p.c_str());
+      return !bad;
+    };
+    for (size_t t = 0; t < nt; t++) { cov_n += run.cov_records[t]; cov_a += run.cov_aligned[t]; cov_c += run.cov_covered[t]; cov_b += (uint64_t)std::max<int64_t>(tx_len[t], 0); }
+    if (!o.coverage.empty()) {
+      FILE *f = fopen(cv_tmp.c_str(), "w");
+      constexpr int64_t PAGE = 1 << 20;
+      std::vector<uint32_t> r_tid((size_t)std::min(run.cov_runs, PAGE) + 1), r_start(r_tid.size()), r_end(r_tid.size()), r_depth(r_tid.size());
+      for (int64_t first = 0; f && !failed && first < run.cov_runs; first += PAGE) {
+        const int64_t n = std::min(PAGE, run.cov_runs - first);
+        const int crc = br_coverage_runs(coverage, first, n, r_tid.data(), r_start.data(), r_end.data(), r_depth.data());
+        if (crc) { fprintf(stderr, "error: coverage on device %d: %s\n", o.devices[0], br_strerror(crc)); failed = 1; break; }
+        for (int64_t k = 0; k < n; k++) fprintf(f, "%s\t%u\t%u\t%u\n", br_index_transcript_name(ix0, r_tid[(size_t)k]), r_start[(size_t)k], r_end[(size_t)k], r_depth[(size_t)k]);
+      }
+      if (!close_ok(f, cv_tmp)) failed = 1;
+    }
+    if (!failed && !o.coverage_summary.empty()) {
+      FILE *f = fopen(cs_tmp.c_str(), "w");
+      if (f) {
+        fprintf(f, "Name\tLength\tRecords\tAlignedBases\tCoveredBases\tMaxDepth\tMeanDepth\tBreadth\n");
+        for (size_t t = 0; t < nt; t++)
+          if (tx_len[t] > 0) fprintf(f, "%s\t%lld\t%llu\t%llu\t%llu\t%u\t%.6f\t%.6f\n", br_index_transcript_name(ix0, (uint32_t)t), (long long)tx_len[t],
+                                     (unsigned long long)run.cov_records[t], (unsigned long long)run.cov_aligned[t], (unsigned long long)run.cov_covered[t], run.cov_max[t],
+                                     (double)run.cov_aligned[t] / (double)tx_len[t], (double)run.cov_covered[t] / (double)tx_len[t]);
+      }
+      if (!close_ok(f, cs_tmp)) failed = 1;
+    }
+  }
   if (!file.finish(!failed)) failed = 1;
+  if (coverage) {
+    auto settle = [&](const std::string &tmp, const std::string &path) {
+      if (path.empty()) return;
+      if (failed) remove(tmp.c_str());
+      else if (rename(tmp.c_str(), path.c_str()) != 0) { fprintf(stderr, "error: could not rename %s to %s\n", tmp.c_str(), path.c_str()); failed = 1; }
+    };
+    settle(cv_tmp, o.coverage); settle(cs_tmp, o.coverage_summary);
+    if (failed) { if (!o.coverage.empty()) remove(cv_tmp.c_str()); if (!o.coverage_summary.empty()) remove(cs_tmp.c_str()); }
+  }
   if (quant) {
     auto settle = [&](const std::string &tmp, const std::string &path) {
       if (path.empty()) return;
@@ -722,6 +815,8 @@ extern "C" int br_cli_main(int argc, char **argv) {
            run.q_fld_obs ? sum / (double)run.q_fld_obs : 0.0, (unsigned long long)run.q_fld_nofrag, (unsigned long long)run.q_fld_oor);
   }
   if (!o.quiet && quant && !failed) printf("[bramble] quantified %lld read names in %lld classes (%d iterations, add %.2fs, classes %.2fs, EM %.2fs)\n", (long long)run.q_names, (long long)run.q_classes, (int)run.q_iters, run.t_q_add, run.t_q_finish, run.t_q_em);
+  if (!o.quiet && coverage && !failed) printf("[bramble] coverage: %llu records, %llu aligned bases on %llu of %llu bases in %lld runs (add %.2fs, finish %.2fs)\n", (unsigned long long)cov_n, (unsigned long long)cov_a,
+                                              (unsigned long long)cov_c, (unsigned long long)cov_b, (long long)run.cov_runs, run.t_cov_add, run.t_cov_finish);
   double t_done = since();
   uint64_t total_complete = 0, total_unique = 0, dropped = 0, n_bundles = 0;
   double gpu_seconds = 0, t_upload = 0, t_wait_gpu_in = 0;

@@ -40,6 +40,8 @@ struct Options {
   int quant_length_norm = -1;    // -1: on for the short-read preset, off under --lr / --lr-hq; --quant-length-norm / --quant-no-length-norm
   bool quant_eff_length = false; // --quant-eff-length: the fragment-length model (br_quant "eff_len"): reads weighted by 1 / effective length
   std::string quant_fld;         // --quant-fld FILE: the observed fragment-length histogram
+  std::string coverage, coverage_summary;   // --coverage FILE / --coverage-summary FILE: the bedGraph of the depth along every transcript and the per-transcript table (br_coverage)
+  bool coverage_primary = false; // --coverage-primary: only primary records count ("primary_only")
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };
 inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }

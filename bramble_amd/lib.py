@@ -178,6 +178,8 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_sorter_index", "br_sorter_free", "br_ctx_last_device_bam", "br_device_bam_download",
            "br_quant_new", "br_quant_set_param", "br_quant_set_tolerance", "br_quant_add", "br_quant_add_rows", "br_quant_add_last", "br_quant_finish",
            "br_quant_classes", "br_quant_em", "br_quant_result", "br_quant_fld", "br_quant_eff_lengths", "br_quant_stats", "br_quant_free",
+           "br_coverage_new", "br_coverage_set_param", "br_coverage_add_rows", "br_coverage_add_last", "br_coverage_finish", "br_coverage_runs",
+           "br_coverage_depth", "br_coverage_summary", "br_coverage_stats", "br_coverage_free",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -1321,6 +1323,119 @@ class Quant:
     def close(self):
         if self.h:
             lib().br_quant_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Coverage:
+    """br_coverage on `device`: the rows of projected batches in, the depth of coverage along every transcript out (runs of equal
+    depth, per-transcript summary, the depth itself).  lengths: one per transcript."""
+
+    RUN_PAGE = 1 << 20
+
+    def __init__(self, lengths, device=0):
+        L = lib()
+        L.br_coverage_new.argtypes = [C.c_int, C.c_int64, C.c_void_p, _P(C.c_void_p)]
+        L.br_coverage_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+        L.br_coverage_add_rows.argtypes = [C.c_void_p, _P(BrDeviceRows), C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+        L.br_coverage_add_last.argtypes = [C.c_void_p, C.c_void_p]
+        L.br_coverage_finish.argtypes = [C.c_void_p, _P(C.c_int64)]
+        L.br_coverage_runs.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.br_coverage_depth.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.br_coverage_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.br_coverage_stats.argtypes = [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64),
+                                        _P(C.c_double), _P(C.c_double)]
+        L.br_coverage_free.argtypes = [C.c_void_p]
+        self.h = None
+        self.device = device
+        self.lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+        self.n_transcripts = int(self.lengths.size)
+        self.n_runs = 0
+        h = C.c_void_p()
+        check(L.br_coverage_new(device, self.n_transcripts, self.lengths.ctypes.data if self.n_transcripts else None, C.byref(h)),
+              "br_coverage_new")
+        self.h = h
+
+    def set_param(self, name, value):
+        """"primary_only" 0 / 1, before the first add."""
+        check(lib().br_coverage_set_param(self.h, name.encode(), int(value)), "br_coverage_set_param")
+
+    def add_rows_raw(self, a, cigar, pool, n_rows, n_pool_words, r0, r1, on_device, stream=None):
+        """br_coverage_add_rows as it is (the tables as addresses): the return code (0, or a BR_ERR_* value)."""
+        rows = BrDeviceRows()
+        rows.n_rows, rows.n_pool_words = int(n_rows), int(n_pool_words)
+        rows.a, rows.cigar, rows.pool = a, cigar, pool
+        return lib().br_coverage_add_rows(self.h, C.byref(rows), int(r0), int(r1), 1 if on_device else 0, C.c_void_p(stream or 0))
+
+    def add_rows_host(self, rows_a, cigar, pool, r0=0, r1=None):
+        """rows_a: uint32 [n_rows, 4] (br_row_a: transcript_id, pos, meta, nh), cigar uint64 [n_rows] (the ops themselves up to two,
+        else an offset into pool), pool uint32, in host memory; the rows [r0, r1) of them are added."""
+        a = np.ascontiguousarray(rows_a, dtype=np.uint32).reshape(-1, 4)
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        pl = np.ascontiguousarray(pool, dtype=np.uint32)
+        assert len(cg) == len(a)
+        r1 = len(a) if r1 is None else r1
+        check(self.add_rows_raw(a.ctypes.data if a.size else None, cg.ctypes.data if cg.size else None, pl.ctypes.data if pl.size else None,
+                                len(a), len(pl), r0, r1, False), "br_coverage_add_rows")
+
+    def add_rows_device(self, rows_a, cigar, pool, r0=0, r1=None):
+        """The same tables as torch CUDA tensors (rows_a int32 / uint8 storage of br_row_a, cigar int64, pool int32)."""
+        import torch
+        r1 = cigar.numel() if r1 is None else r1
+        check(self.add_rows_raw(rows_a.data_ptr() if cigar.numel() else None, cigar.data_ptr() if cigar.numel() else None,
+                                pool.data_ptr() if pool.numel() else None, cigar.numel(), pool.numel(), r0, r1, True,
+                                torch.cuda.current_stream(cigar.device).cuda_stream), "br_coverage_add_rows")
+
+    def add_last(self, ctx):
+        """All rows of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
+        check(lib().br_coverage_add_last(self.h, ctx.h), "br_coverage_add_last")
+
+    def finish(self):
+        n = C.c_int64()
+        check(lib().br_coverage_finish(self.h, C.byref(n)), "br_coverage_finish")
+        self.n_runs = int(n.value)
+        return self.n_runs
+
+    def runs(self, page=None):
+        """-> (tid, start, end, depth), uint32 [n_runs] each, ordered by (tid, start); fetched in pages of `page` runs"""
+        page = int(page or self.RUN_PAGE)
+        out = [np.zeros(max(self.n_runs, 1), dtype=np.uint32) for _ in range(4)]
+        for first in range(0, self.n_runs, page):
+            n = min(page, self.n_runs - first)
+            check(lib().br_coverage_runs(self.h, first, n, *[o[first:].ctypes.data for o in out]), "br_coverage_runs")
+        return tuple(o[:self.n_runs] for o in out)
+
+    def depth(self, tid):
+        """-> uint32 [max(L[tid], 0)]"""
+        d = np.zeros(max(int(self.lengths[tid]), 1), dtype=np.uint32)
+        check(lib().br_coverage_depth(self.h, int(tid), d.ctypes.data), "br_coverage_depth")
+        return d[:max(int(self.lengths[tid]), 0)]
+
+    def summary(self):
+        """-> dict of records, aligned_bases, covered_bases (uint64) and max_depth (uint32), one entry per transcript"""
+        nt = max(self.n_transcripts, 1)
+        out = {"records": np.zeros(nt, dtype=np.uint64), "aligned_bases": np.zeros(nt, dtype=np.uint64),
+               "covered_bases": np.zeros(nt, dtype=np.uint64), "max_depth": np.zeros(nt, dtype=np.uint32)}
+        check(lib().br_coverage_summary(self.h, out["records"].ctypes.data, out["aligned_bases"].ctypes.data,
+                                        out["covered_bases"].ctypes.data, out["max_depth"].ctypes.data), "br_coverage_summary")
+        return {k: v[:self.n_transcripts] for k, v in out.items()}
+
+    def stats(self):
+        rc, rs, cb, h, p = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        ad, fi = C.c_double(), C.c_double()
+        check(lib().br_coverage_stats(self.h, C.byref(rc), C.byref(rs), C.byref(cb), C.byref(h), C.byref(p), C.byref(ad), C.byref(fi)),
+              "br_coverage_stats")
+        return {"rows_counted": int(rc.value), "rows_skipped": int(rs.value), "clipped_bases": int(cb.value), "held_bytes": int(h.value),
+                "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value}
+
+    def close(self):
+        if self.h:
+            lib().br_coverage_free(self.h)
             self.h = None
 
     def __del__(self):

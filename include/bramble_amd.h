@@ -737,6 +737,61 @@ int br_quant_stats(const br_quant *, uint64_t *held_bytes, uint64_t *peak_bytes,
                    double *em_seconds, uint64_t *collisions, int64_t *n_unassigned, int64_t *n_labels);
 void br_quant_free(br_quant *);
 
+/* Coverage: the depth of coverage along every transcript, from the rows of a whole run, in one device's HBM (coverage.cpp,
+ * coverage_kernels.hip).  Integers throughout.  The definitions:
+ *   transcriptome  n_transcripts lengths L[t]; transcript t owns max(L[t], 0) bases, B is their sum
+ *   counted row    every row of every add; with "primary_only" = 1 only the rows with BR_ROW_PRIMARY set, the others count in
+ *                  rows_skipped.  Secondary records count by default (for a multi-mapped read the choice of the primary among its
+ *                  transcripts is arbitrary, and so would the track be).  Both mates of a pair count, a base they both cover twice
+ *                  (samtools depth without -s, bedtools genomecov).  Strand and NH are not looked at
+ *   covered bases  the row's rewritten CIGAR is walked from p = pos in 64-bit arithmetic -- taken from cigar[row] itself when
+ *                  BR_ROW_NCIGAR(meta) <= 2, else from pool[cigar[row] ...], as br_quant's fragments read it.  M = X (op codes 0, 7,
+ *                  8) of length n cover [p, p + n) and advance p; D N (2, 3) advance p and cover nothing (samtools depth without
+ *                  -J, genomecov -split); I S H P do nothing.  A covered interval is clamped to [0, L[t]); the bases it loses
+ *                  count in clipped_bases (all of them on a transcript with L <= 0)
+ *   depth          depth[t][x] = the counted rows that cover base x of t, uint32.  The rows of one object number fewer than 2^32:
+ *                  the add that would reach 2^32 returns BR_ERR_CAPACITY and adds nothing, so the depth cannot overflow
+ *   per transcript records[t] (uint64) = the counted rows with that transcript_id, however much of them was clipped;
+ *                  aligned_bases[t] (uint64) = the sum of the depth; covered_bases[t] (uint64) = the bases of depth > 0;
+ *                  max_depth[t] (uint32)
+ *   run            a maximal interval [start, end) of one transcript with one depth > 0.  Runs never span two transcripts, whatever
+ *                  the depths on both sides of the boundary; they are ordered by (transcript, start)
+ *   invariance     how the rows were cut into adds, and their order, changes nothing; two runs give the same bits (integer atomics)
+ *   br_coverage_new        BR_ERR_INVALID_ARG for a length above 2^32 - 1 (start and end are 32-bit), BR_ERR_NO_DEVICE without the
+ *                          device, BR_ERR_CAPACITY when the device's memory does not take 4 (B + 1) bytes
+ *   br_coverage_set_param  before the first add: "primary_only" 0 / 1 (default 0)
+ *   br_coverage_add_rows   the rows [r0, r1) of a table: a, cigar, pool, n_rows and n_pool_words of `rows` (device memory with
+ *                          on_device != 0, read after the work queued on `stream`, NULL for the null stream; host memory in the
+ *                          same layout with on_device = 0).  Returns when the tables have been read.  A row whose transcript_id is
+ *                          >= n_transcripts is skipped and nothing outside the tables is touched; br_coverage_finish then returns
+ *                          BR_ERR_INVALID_ARG.  A row range outside [0, n_rows] or a pooled CIGAR reference that leaves
+ *                          n_pool_words makes the add return BR_ERR_INVALID_ARG, and from then on the object answers
+ *                          BR_ERR_INVALID_ARG to everything except br_coverage_free: PART OF THAT ADD MAY ALREADY HAVE BEEN COUNTED.
+ *                          BR_ERR_INVALID_ARG after finish
+ *   br_coverage_add_last   br_coverage_add_rows for all rows of the context's last projection call, whichever entry point made it
+ *                          (a call that left no rows: BR_OK)
+ *   br_coverage_finish     depth, summary and runs; the number of runs
+ *   br_coverage_runs       after finish: runs [first, first + n) as four host arrays (BR_ERR_INVALID_ARG outside [0, n_runs])
+ *   br_coverage_depth      after finish: the max(L[tid], 0) depths of one transcript
+ *   br_coverage_summary    after finish: n_transcripts entries each
+ *   br_coverage_stats      rows counted / skipped and bases clipped by the adds so far, device bytes held now and the most held so
+ *                          far, seconds in add / finish
+ * Any out-pointer may be NULL.  Device memory: 4 bytes a base (diff, which finish turns into the depth in place) and 16 a transcript
+ * from br_coverage_new on; finish adds 20 a transcript, 16 a run and, while it runs, 8 a tile of 4096 bases; a host add holds 24
+ * bytes a row and 4 a pool word while it runs (coverage.cpp). */
+typedef struct br_coverage br_coverage;
+int br_coverage_new(int device, int64_t n_transcripts, const int64_t *lengths, br_coverage **out);
+int br_coverage_set_param(br_coverage *, const char *name, int64_t value);
+int br_coverage_add_rows(br_coverage *, const br_device_rows *rows, int64_t r0, int64_t r1, int on_device, void *stream);
+int br_coverage_add_last(br_coverage *, br_ctx *);
+int br_coverage_finish(br_coverage *, int64_t *n_runs);
+int br_coverage_runs(br_coverage *, int64_t first, int64_t n, uint32_t *tid, uint32_t *start, uint32_t *end, uint32_t *depth);
+int br_coverage_depth(br_coverage *, int64_t tid, uint32_t *depth);
+int br_coverage_summary(br_coverage *, uint64_t *records, uint64_t *aligned_bases, uint64_t *covered_bases, uint32_t *max_depth);
+int br_coverage_stats(const br_coverage *, uint64_t *rows_counted, uint64_t *rows_skipped, uint64_t *clipped_bases, uint64_t *held_bytes,
+                      uint64_t *peak_bytes, double *add_seconds, double *finish_seconds);
+void br_coverage_free(br_coverage *);
+
 /* br_project_bam_staged / _nowait for records that are in HBM already (a br_bam_reader bundle, or br_bam_split_device's);
  * bgzf_on_device takes the values of br_bam_bundle.bgzf_on_device (0, 1, BR_OUT_SAM_TEXT) */
 int br_project_bam_resident(br_ctx *, const br_config *, const br_device_records *recs, const int32_t *ref_map, int32_t n_ref_map,
@@ -811,7 +866,8 @@ const char *const *br_annotation_refnames(const br_annotation *);
  * GPU) / --host-deflate / --compression-level N (host codec), --device-reader (default for a regular file on one device: the
  * input is inflated and split into records on the GPU, br_bam_reader) / --host-reader, --bundle-size and --device / --devices,
  * --collate, -O bam|sam, --sort [--write-index], --quant FILE [--quant-classes FILE] [--quant-eff-length [--quant-fld FILE]]
- * (br_quant above; the usage text says the rest).
+ * (br_quant above), --coverage FILE / --coverage-summary FILE [--coverage-primary] (br_coverage above; the usage text says the
+ * rest).
  * Returns the process exit code. */
 int br_cli_main(int argc, char **argv);
 /* For a process whose only job is that one call (the `bramble` binary): with `on` != 0 br_cli_main does not return after a
