@@ -11,74 +11,46 @@
 //
 // Device memory (n records, R arena bytes = sum of 4 + block_size): add holds R + 12 n (and, while the arena grows, the old
 // arena beside the new one); finish adds keys 2 x 8 n, indices 2 x 4 n, head counts 8 n, the permuted tables 12 n, marks
-// 8 n and the radix histograms (2 KiB a tile of 2048), so its peak is R + 64 n; afterwards R + 24 n stay until free.
+// 8 n and the radix histograms (2 KiB a tile of 2048), so its peak is R + 64 n; afterwards R + 24 n stay until free.  The
+// tables of one call are under a guard (accum.h): a finish that fails drops them as well, and the count is what is held.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "../../include/bramble_amd.h"
+#include "accum.h"
 #include "collate_kernels.h"
-#include "devmem.h"
 #include "sam_kernels.h"
 
 using namespace br;
 
-struct br_collator {
-  int device = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev = nullptr;
+struct br_collator : Accum {
   int hash_bits = 64;
   uint64_t max_bytes = 0;     // 0: no cap but the device's memory
   bool finished = false;
   int64_t n = 0, groups = 0, cur = 0;
   uint64_t used = 0;          // arena bytes in use
-  uint64_t live = 0, peak = 0;  // device bytes held by the collator now / at most
   double add_s = 0, finish_s = 0;
   ColBuf arena, off_in, len_in;         // input order
   ColBuf out_off, out_len, out_idx, starts;   // output order; starts: G + 1 group starts
   ColBuf tmp, small;
-  int alloc(ColBuf &b, size_t bytes, bool keep = false) {
-    if (bytes <= b.cap) return BR_OK;
-    void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? BR_ERR_CAPACITY : BR_ERR_HIP; }
-    live += bytes; peak = std::max(peak, live);
-    if (keep && b.p) HIPCHK(hipMemcpyAsync(q, b.p, b.cap, hipMemcpyDeviceToDevice, st));
-    if (b.p) { HIPCHK(hipStreamSynchronize(st)); live -= b.cap; b.release(); }
-    b.p = q; b.cap = bytes;
-    return BR_OK;
-  }
-  void drop(ColBuf &b) { live -= b.cap; b.release(); }
 };
-
-static int col_check_device(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) { (void)hipGetLastError(); return BR_ERR_NO_DEVICE; }
-  return BR_OK;
-}
 
 extern "C" void br_collator_free(br_collator *c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamSynchronize(c->st);
-  if (c->ev) (void)hipEventDestroy(c->ev);
-  if (c->st) (void)hipStreamDestroy(c->st);
+  c->close();
   delete c;
 }
 
 extern "C" int br_collator_new(int device, br_collator **out) {
   if (!out) return BR_ERR_INVALID_ARG;
   *out = nullptr;
-  RC(col_check_device(device));
-  HIPCHK(hipSetDevice(device));
   br_collator *c = new br_collator();
-  c->device = device;
-  int rc = hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) == hipSuccess ? BR_OK : BR_ERR_HIP;
+  int rc = c->open(device);
   if (!rc) rc = c->alloc(c->small, 64);
   if (rc) { br_collator_free(c); return rc; }
   *out = c;
@@ -113,7 +85,7 @@ static int col_reserve(br_collator *c, int64_t m, uint64_t bytes) {
 static int col_add_device(br_collator *c, const br_device_records *r, hipStream_t caller) {
   const int64_t m = r->n_aln;
   hipStream_t st = c->st;
-  HIPCHK(hipEventRecord(c->ev, caller)); HIPCHK(hipStreamWaitEvent(st, c->ev, 0));   // after whatever made the records (NULL: the null stream's work)
+  RC(c->after(caller));   // after whatever made the records
   RC(c->alloc(c->tmp, (size_t)(m + 1) * 8 + ((size_t)m / 1024 + 4) * 8));
   uint64_t *bytes = c->tmp.as<uint64_t>(), *scan_tmp = bytes + m + 1;
   launch_col_lens(st, r->rec_off, r->rec_len, m, bytes);
@@ -156,11 +128,9 @@ static int col_add_host(br_collator *c, const br_device_records *r) {
 extern "C" int br_collator_add(br_collator *c, const br_device_records *recs, int on_device, void *stream) {
   if (!c || !recs || recs->n_aln < 0 || (recs->n_aln && (!recs->blob || !recs->rec_off)) || c->finished) return BR_ERR_INVALID_ARG;
   if (recs->n_aln == 0) return BR_OK;
-  auto t0 = std::chrono::steady_clock::now();
+  ScopeTimer timer(&c->add_s);
   HIPCHK(hipSetDevice(c->device));
-  const int rc = on_device ? col_add_device(c, recs, (hipStream_t)stream) : col_add_host(c, recs);
-  c->add_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  return on_device ? col_add_device(c, recs, (hipStream_t)stream) : col_add_host(c, recs);
 }
 
 // collisions: the runs of equal keys whose names differ are sorted by name on the host (stable: input order inside a name)
@@ -178,13 +148,14 @@ static int col_resolve(br_collator *c, uint32_t *idx, std::vector<uint64_t> runs
     p += (size_t)(r.second - r.first);
   }
   ColBuf list, slots;
+  DropGuard dropper{c, {&list, &slots}};
   RC(c->alloc(list, m * 4)); RC(c->alloc(slots, m * 256));
   HIPCHK(hipMemcpyAsync(list.p, members.data(), m * 4, hipMemcpyHostToDevice, c->st));
   launch_col_names(c->st, c->arena.as<uint8_t>(), c->off_in.as<uint64_t>(), list.as<uint32_t>(), (int64_t)m, slots.as<uint8_t>());
   std::vector<uint8_t> names(m * 256);
   HIPCHK(hipMemcpyAsync(names.data(), slots.p, m * 256, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
-  c->drop(list); c->drop(slots);
+  c->drop(list); c->drop(slots);   // (before the host's sort, not after it)
   p = 0;
   std::vector<size_t> ord;
   std::vector<uint32_t> sorted(m);
@@ -209,12 +180,10 @@ static int col_finish(br_collator *c) {
   hipStream_t st = c->st;
   const int64_t n = c->n;
   const size_t n1 = (size_t)n + 1;
-  ColBuf key[2], idx[2], hc, mark, hist;
+  ColBuf key[2], idx[2], hc, mark, runs;
+  DropGuard dropper{c, {&key[0], &key[1], &idx[0], &idx[1], &hc, &mark, &runs}};   // (what finish keeps is swapped out of them)
   RC(c->alloc(key[0], n1 * 8)); RC(c->alloc(key[1], n1 * 8)); RC(c->alloc(idx[0], n1 * 4)); RC(c->alloc(idx[1], n1 * 4));
-  const int64_t blocks = (n + 255) / 256, tiles = (n + COL_TILE - 1) / COL_TILE;
-  const int64_t nh = 256 * tiles;
-  RC(c->alloc(c->tmp, (size_t)std::max<int64_t>(2 * blocks + 2, std::max<int64_t>(nh, n) / 1024 + 8) * 8));
-  RC(c->alloc(hist, (size_t)(nh + 1) * 8));
+  RC(c->alloc(c->tmp, scan_tmp_bytes(n)));
   uint64_t *small = c->small.as<uint64_t>();
   const uint64_t mask = c->hash_bits >= 64 ? ~0ull : (1ull << c->hash_bits) - 1;
   launch_col_key(st, c->arena.as<uint8_t>(), c->off_in.as<uint64_t>(), n, mask, key[0].as<uint64_t>(), idx[0].as<uint32_t>(),
@@ -223,19 +192,12 @@ static int col_finish(br_collator *c) {
   HIPCHK(hipMemcpyAsync(bits, small, 16, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   int cur = 0;
-  for (int shift = 0; shift < 64; shift += 8) {
-    if ((((bits[0] ^ bits[1]) >> shift) & 255u) == 0) continue;   // the digit is the same in every key
-    launch_col_radix_pass(st, key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), key[cur ^ 1].as<uint64_t>(), idx[cur ^ 1].as<uint32_t>(),
-                          n, shift, hist.as<uint64_t>(), c->tmp.as<uint64_t>());
-    cur ^= 1;
-  }
-  c->drop(hist);
+  RC(c->radix_sort(key, idx, n, bits, c->tmp, &cur));
   const uint64_t *K = key[cur].as<uint64_t>();
   uint32_t *I = idx[cur].as<uint32_t>();
   uint64_t *head = key[cur ^ 1].as<uint64_t>();
   // group starts; runs with collisions are sorted by name and the starts found again
   uint64_t run_cap = 4096;
-  ColBuf runs;
   for (bool resolved = false;;) {
     RC(c->alloc(runs, (size_t)run_cap * 16));
     HIPCHK(hipMemsetAsync(small + 2, 0, 16, st));
@@ -273,18 +235,18 @@ static int col_finish(br_collator *c) {
   HIPCHK(hipStreamSynchronize(st));
   std::swap(c->starts, hc);
   std::swap(c->out_idx, idx[cur ^ 1]);
-  for (auto *b : {&key[0], &key[1], &idx[0], &idx[1], &hc, &mark, &c->off_in, &c->len_in, &c->tmp}) c->drop(*b);
+  for (auto *b : {&c->off_in, &c->len_in, &c->tmp}) c->drop(*b);
   c->groups = (int64_t)G;
   return BR_OK;
 }
 
 extern "C" int br_collator_finish(br_collator *c, int64_t *n_records, int64_t *n_groups) {
   if (!c || c->finished) return BR_ERR_INVALID_ARG;
-  auto t0 = std::chrono::steady_clock::now();
+  const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
   if (c->n) RC(col_finish(c));
   c->finished = true;
-  c->finish_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  c->finish_s = timer.seconds();
   if (n_records) *n_records = c->n;
   if (n_groups) *n_groups = c->groups;
   return BR_OK;

@@ -7,27 +7,25 @@
 //   finish   diff -> depth by an in-place inclusive scan modulo 2^32; sum, non-zero count and maximum per transcript; run heads
 //            counted per tile of 4096 bases, the counts scanned, the runs written
 //
-// Device memory (B bases, T transcripts, R runs):
-//   from new on    4 (B + 1) (diff, then the depth) + 16 T (offsets, records) + 64 bytes of counters
-//   a host add     adds 24 a row of the add and 4 a pool word while it runs
-//   finish         adds 8 a tile of 4096 bases (the tile sums, then the tile counts; freed again), 20 T (the summary) and 16 R
+// Device memory (B bases, T transcripts, R runs; to the byte, every table has one entry more than its items):
+//   from new on    4 (B + 1) (diff, then the depth) + 16 (T + 1) (offsets, records) + 64 bytes of counters
+//   a host add     adds 24 a row of the add and 4 a pool word while it runs (24 and 4 more for the entry behind them)
+//   finish         adds 8 a tile of 4096 bases (the tile sums, then the tile counts; freed again), 20 (T + 1) (the summary) and
+//                  16 (R + 1)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <vector>
 
+#include "accum.h"
 #include "coverage_kernels.h"
 #include "ctx.h"
 #include "sam_kernels.h"
 
 using namespace br;
 
-struct br_coverage {
-  int device = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev = nullptr;
+struct br_coverage : Accum {
   int64_t n_tx = 0;
   std::vector<uint64_t> off;   // n_tx + 1
   int64_t n_bases = 0;
@@ -36,34 +34,13 @@ struct br_coverage {
   uint64_t rows = 0;           // rows of all adds, counted or skipped
   int64_t n_runs = 0;
   uint64_t counters[CV_WORDS] = {};
-  uint64_t live = 0, peak = 0;
   double add_s = 0, finish_s = 0;
   ColBuf d_off, diff, records, small, aligned, covered, max_depth, runs;
-  int alloc(ColBuf &b, size_t bytes) {
-    if (bytes <= b.cap) return BR_OK;
-    void *p = nullptr;
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? BR_ERR_CAPACITY : BR_ERR_HIP; }
-    live += bytes; peak = std::max(peak, live);
-    if (b.p) { HIPCHK(hipStreamSynchronize(st)); live -= b.cap; b.release(); }
-    b.p = p; b.cap = bytes;
-    return BR_OK;
-  }
-  void drop(ColBuf &b) { live -= b.cap; b.release(); }
-};
-
-// device tables of one call: whatever the outcome, they go (and leave the byte count) when the call returns
-struct CoverageDrop {
-  br_coverage *c; std::vector<ColBuf *> b;
-  ~CoverageDrop() { for (auto *x : b) c->drop(*x); }
 };
 
 extern "C" void br_coverage_free(br_coverage *c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamSynchronize(c->st);
-  if (c->ev) (void)hipEventDestroy(c->ev);
-  if (c->st) (void)hipStreamDestroy(c->st);
+  c->close();
   delete c;
 }
 
@@ -72,16 +49,13 @@ extern "C" int br_coverage_new(int device, int64_t n_transcripts, const int64_t 
   *out = nullptr;
   if (n_transcripts < 0 || n_transcripts >= (1ll << 32) || (n_transcripts && !lengths)) return BR_ERR_INVALID_ARG;
   for (int64_t t = 0; t < n_transcripts; t++) if (lengths[t] > 0xffffffffll) return BR_ERR_INVALID_ARG;   // (start and end are 32-bit)
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0 || device < 0 || device >= nd) { (void)hipGetLastError(); return BR_ERR_NO_DEVICE; }
-  HIPCHK(hipSetDevice(device));
   br_coverage *c = new br_coverage();
-  c->device = device; c->n_tx = n_transcripts;
+  c->n_tx = n_transcripts;
   c->off.assign((size_t)n_transcripts + 1, 0);
   for (int64_t t = 0; t < n_transcripts; t++) c->off[(size_t)t + 1] = c->off[(size_t)t] + (uint64_t)std::max<int64_t>(lengths[t], 0);
   c->n_bases = (int64_t)c->off[(size_t)n_transcripts];
   const size_t t1 = (size_t)n_transcripts + 1, b1 = (size_t)c->n_bases + 1;
-  int rc = hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) == hipSuccess ? BR_OK : BR_ERR_HIP;
+  int rc = c->open(device);
   if (!rc) rc = c->alloc(c->small, CV_WORDS * 8);
   if (!rc) rc = c->alloc(c->d_off, t1 * 8);
   if (!rc) rc = c->alloc(c->records, t1 * 8);
@@ -116,21 +90,16 @@ static int coverage_add_rows(br_coverage *c, CovAddArgs A, uint64_t r0, uint64_t
 }
 
 static int coverage_add_host(br_coverage *c, const br_device_rows &rows, uint64_t r0, uint64_t r1) {
-  ColBuf d_a, d_c, d_pool;
-  CoverageDrop dropper{c, {&d_a, &d_c, &d_pool}};
-  const size_t n = (size_t)(r1 - r0), np = (size_t)rows.n_pool_words;
-  RC(c->alloc(d_a, (n + 1) * sizeof(br_row_a))); RC(c->alloc(d_c, (n + 1) * 8)); RC(c->alloc(d_pool, (np + 1) * 4));
-  hipStream_t st = c->st;
-  HIPCHK(hipMemcpyAsync(d_a.p, rows.a + r0, n * sizeof(br_row_a), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_c.p, rows.cigar + r0, n * 8, hipMemcpyHostToDevice, st));
-  if (np) HIPCHK(hipMemcpyAsync(d_pool.p, rows.pool, np * 4, hipMemcpyHostToDevice, st));   // the whole pool: the references are offsets from its start
+  RowWindow w;
+  DropGuard dropper{c, {&w.a, &w.cigar, &w.pool}};
+  RC(c->upload_rows(rows, r0, r1, true, w));
   CovAddArgs A{};
-  A.a = d_a.as<uint4>(); A.cigar = d_c.as<uint64_t>(); A.bias = (int64_t)r0; A.pool = d_pool.as<uint32_t>(); A.n_pool_words = np;
+  A.a = w.a.as<uint4>(); A.cigar = w.cigar.as<uint64_t>(); A.bias = w.bias; A.pool = w.pool.as<uint32_t>(); A.n_pool_words = w.n_pool_words;
   return coverage_add_rows(c, A, r0, r1);   // (it waits for the stream: the uploads are done when the host arrays go)
 }
 
 static int coverage_add_device(br_coverage *c, const br_device_rows &rows, uint64_t r0, uint64_t r1, hipStream_t caller) {
-  HIPCHK(hipEventRecord(c->ev, caller)); HIPCHK(hipStreamWaitEvent(c->st, c->ev, 0));   // after whatever made the rows (NULL: the null stream's work)
+  RC(c->after(caller));   // after whatever made the rows
   CovAddArgs A{};
   A.a = (const uint4 *)rows.a; A.cigar = rows.cigar; A.pool = rows.pool; A.n_pool_words = (uint64_t)rows.n_pool_words;
   return coverage_add_rows(c, A, r0, r1);
@@ -143,11 +112,9 @@ extern "C" int br_coverage_add_rows(br_coverage *c, const br_device_rows *rows, 
   if (c->rows + (uint64_t)(r1 - r0) >= (1ull << 32)) return BR_ERR_CAPACITY;   // (the depth is 32-bit)
   c->added = true;
   if (r1 == r0) return BR_OK;
-  auto t0 = std::chrono::steady_clock::now();
+  ScopeTimer timer(&c->add_s);
   HIPCHK(hipSetDevice(c->device));
-  const int rc = on_device ? coverage_add_device(c, *rows, (uint64_t)r0, (uint64_t)r1, (hipStream_t)stream) : coverage_add_host(c, *rows, (uint64_t)r0, (uint64_t)r1);
-  c->add_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  return on_device ? coverage_add_device(c, *rows, (uint64_t)r0, (uint64_t)r1, (hipStream_t)stream) : coverage_add_host(c, *rows, (uint64_t)r0, (uint64_t)r1);
 }
 
 extern "C" int br_coverage_add_last(br_coverage *c, br_ctx *ctx) {
@@ -163,7 +130,7 @@ static int coverage_finish(br_coverage *c) {
   const size_t t1 = (size_t)T + 1;
   const int64_t tiles = (B + COV_TILE - 1) / COV_TILE;
   ColBuf tile, tmp;
-  CoverageDrop dropper{c, {&tile, &tmp}};
+  DropGuard dropper{c, {&tile, &tmp}};
   RC(c->alloc(c->aligned, t1 * 8)); RC(c->alloc(c->covered, t1 * 8)); RC(c->alloc(c->max_depth, t1 * 4));
   RC(c->alloc(tile, (size_t)(tiles + 2) * 8)); RC(c->alloc(tmp, (size_t)(tiles / 1024 + 8) * 8));
   HIPCHK(hipMemsetAsync(c->aligned.p, 0, t1 * 8, st)); HIPCHK(hipMemsetAsync(c->covered.p, 0, t1 * 8, st));
@@ -189,12 +156,12 @@ static int coverage_finish(br_coverage *c) {
 
 extern "C" int br_coverage_finish(br_coverage *c, int64_t *n_runs) {
   if (!c || c->broken || c->finished) return BR_ERR_INVALID_ARG;
-  auto t0 = std::chrono::steady_clock::now();
+  const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
   const int rc = coverage_finish(c);
   if (rc) { if (rc != BR_ERR_INVALID_ARG) c->broken = true; return rc; }   // (diff may be half a depth by now)
   c->finished = true;
-  c->finish_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  c->finish_s = timer.seconds();
   if (n_runs) *n_runs = c->n_runs;
   return BR_OK;
 }

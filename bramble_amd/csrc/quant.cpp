@@ -35,11 +35,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#include "accum.h"
 #include "collate_kernels.h"
 #include "ctx.h"
 #include "quant_kernels.h"
@@ -47,10 +47,7 @@
 
 using namespace br;
 
-struct br_quant {
-  int device = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev = nullptr;
+struct br_quant : Accum {
   int64_t n_tx = 0;
   std::vector<int64_t> lens;   // empty: no lengths were given
   int hash_bits = 64, length_norm = 1, eff_len = 0;
@@ -63,7 +60,6 @@ struct br_quant {
   int64_t n_assigned = 0, n_cls = 0, n_lab = 0;
   uint32_t n_big_cls = 0, n_big_tx = 0;
   uint64_t collisions = 0;
-  uint64_t live = 0, peak = 0;
   double add_s = 0, finish_s = 0, em_s = 0;
   ColBuf lab, noff, nk, hash, big;                       // add
   ColBuf c_first, c_cnt, c_loff, c_labels, t_cls, t_off, uniq, ambig, big_cls, big_tx;   // after finish
@@ -81,34 +77,13 @@ struct br_quant {
   }
   int cur = 0;
   ColBuf tmp, small;
-  int alloc(ColBuf &b, size_t bytes, bool keep = false) {
-    if (bytes <= b.cap) return BR_OK;
-    void *p = nullptr;
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? BR_ERR_CAPACITY : BR_ERR_HIP; }
-    live += bytes; peak = std::max(peak, live);
-    if (keep && b.p) HIPCHK(hipMemcpyAsync(p, b.p, b.cap, hipMemcpyDeviceToDevice, st));
-    if (b.p) { HIPCHK(hipStreamSynchronize(st)); live -= b.cap; b.release(); }
-    b.p = p; b.cap = bytes;
-    return BR_OK;
-  }
-  void drop(ColBuf &b) { live -= b.cap; b.release(); }
 };
 // words of `small`
 enum { QS_BITS = 0, QS_COLL = 2, QS_SPAN = 3, QS_NBIG = 5, QS_MAXTID = 6, QS_BAD = 7, QS_REL = 8, QS_NBIG_CLS = 9, QS_NBIG_TX = 10, QS_WORDS = 16 };
 
-// device tables of one call: whatever the outcome, they go (and leave the byte count) when the call returns
-struct QuantDrop {
-  br_quant *c; std::vector<ColBuf *> b;
-  ~QuantDrop() { for (auto *x : b) c->drop(*x); }
-};
-
 extern "C" void br_quant_free(br_quant *c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamSynchronize(c->st);
-  if (c->ev) (void)hipEventDestroy(c->ev);
-  if (c->st) (void)hipStreamDestroy(c->st);
+  c->close();
   delete c;
 }
 
@@ -116,13 +91,10 @@ extern "C" int br_quant_new(int device, int64_t n_transcripts, const int64_t *le
   if (!out) return BR_ERR_INVALID_ARG;
   *out = nullptr;
   if (n_transcripts < 0 || n_transcripts >= (1ll << 32)) return BR_ERR_INVALID_ARG;
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0 || device < 0 || device >= nd) { (void)hipGetLastError(); return BR_ERR_NO_DEVICE; }
-  HIPCHK(hipSetDevice(device));
   br_quant *c = new br_quant();
-  c->device = device; c->n_tx = n_transcripts;
+  c->n_tx = n_transcripts;
   if (lengths) c->lens.assign(lengths, lengths + n_transcripts);
-  int rc = hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) == hipSuccess ? BR_OK : BR_ERR_HIP;
+  int rc = c->open(device);
   if (!rc) rc = c->alloc(c->small, QS_WORDS * 8);
   if (!rc && (hipMemsetAsync(c->small.p, 0, QS_WORDS * 8, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) rc = BR_ERR_HIP;
   if (rc) { br_quant_free(c); return rc; }
@@ -196,7 +168,7 @@ static int quant_add_names(br_quant *c, QAddArgs A) {
 static int quant_add_device(br_quant *c, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, hipStream_t caller) {
   const br_row_a *a = rows.a; const uint64_t *row_off = rows.row_off;
   hipStream_t st = c->st;
-  HIPCHK(hipEventRecord(c->ev, caller)); HIPCHK(hipStreamWaitEvent(st, c->ev, 0));   // after whatever made the rows (NULL: the null stream's work)
+  RC(c->after(caller));   // after whatever made the rows
   uint64_t *small = c->small.as<uint64_t>();
   launch_q_span(st, row_off, group_off, ng, small + QS_SPAN);
   uint64_t span[2] = {0, 0};
@@ -210,39 +182,32 @@ static int quant_add_device(br_quant *c, const br_device_rows &rows, const uint3
 }
 
 static int quant_add_host(br_quant *c, const br_device_rows &rows, const uint32_t *group_off, int64_t ng) {
-  const br_row_a *a = rows.a; const uint64_t *row_off = rows.row_off;
+  const uint64_t *row_off = rows.row_off;
   const uint32_t a0 = group_off[0], a1 = group_off[ng];
   for (int64_t g = 0; g < ng; g++) if (group_off[g + 1] < group_off[g]) return BR_ERR_INVALID_ARG;
   for (uint32_t i = a0; i < a1; i++) if (row_off[i + 1] < row_off[i]) return BR_ERR_INVALID_ARG;
   const uint64_t r0 = row_off[a0], r1 = row_off[a1];
   if (rows.cigar && r1 > (uint64_t)rows.n_rows) return BR_ERR_INVALID_ARG;
-  ColBuf d_a, d_ro, d_go, d_c, d_pool;
-  QuantDrop dropper{c, {&d_a, &d_ro, &d_go, &d_c, &d_pool}};
-  RC(c->alloc(d_a, (size_t)(r1 - r0 + 1) * sizeof(br_row_a))); RC(c->alloc(d_ro, (size_t)(a1 - a0 + 1) * 8)); RC(c->alloc(d_go, (size_t)(ng + 1) * 4));
+  RowWindow w;   // a and, when the fragments are counted, the CIGAR references and the pool
+  ColBuf d_ro, d_go;
+  DropGuard dropper{c, {&w.a, &w.cigar, &w.pool, &d_ro, &d_go}};
+  RC(c->upload_rows(rows, r0, r1, rows.cigar != nullptr, w));
+  RC(c->alloc(d_ro, (size_t)(a1 - a0 + 1) * 8)); RC(c->alloc(d_go, (size_t)(ng + 1) * 4));
   hipStream_t st = c->st;
-  if (r1 > r0) HIPCHK(hipMemcpyAsync(d_a.p, a + r0, (size_t)(r1 - r0) * sizeof(br_row_a), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_ro.p, row_off + a0, (size_t)(a1 - a0 + 1) * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d_go.p, group_off, (size_t)(ng + 1) * 4, hipMemcpyHostToDevice, st));
   QAddArgs A{};
-  A.a = d_a.as<uint4>(); A.a_bias = (int64_t)r0; A.row_off = d_ro.as<uint64_t>(); A.ro_bias = (int64_t)a0;
+  A.a = w.a.as<uint4>(); A.a_bias = w.bias; A.row_off = d_ro.as<uint64_t>(); A.ro_bias = (int64_t)a0;
   A.group_off = d_go.as<uint32_t>(); A.n_groups = ng; A.r_first = r0; A.r_last = r1;
-  if (rows.cigar) {   // the rows' CIGAR references at the bias of a, and the whole pool: the references are offsets from its start
-    const size_t np = (size_t)rows.n_pool_words;
-    RC(c->alloc(d_c, (size_t)(r1 - r0 + 1) * 8)); RC(c->alloc(d_pool, (np + 1) * 4));
-    if (r1 > r0) HIPCHK(hipMemcpyAsync(d_c.p, rows.cigar + r0, (size_t)(r1 - r0) * 8, hipMemcpyHostToDevice, st));
-    if (np) HIPCHK(hipMemcpyAsync(d_pool.p, rows.pool, np * 4, hipMemcpyHostToDevice, st));
-    A.cigar = d_c.as<uint64_t>(); A.pool = d_pool.as<uint32_t>(); A.n_pool_words = np;
-  }
+  A.cigar = w.cigar.as<uint64_t>(); A.pool = w.pool.as<uint32_t>(); A.n_pool_words = w.n_pool_words;
   return quant_add_names(c, A);   // (it waits for the stream: the uploads are done when the host arrays go)
 }
 
 static int quant_add(br_quant *c, const br_device_rows &rows, const uint32_t *group_off, int64_t n_groups, int on_device, void *stream) {
   if (n_groups == 0) return BR_OK;
-  auto t0 = std::chrono::steady_clock::now();
+  ScopeTimer timer(&c->add_s);
   HIPCHK(hipSetDevice(c->device));
-  const int rc = on_device ? quant_add_device(c, rows, group_off, n_groups, (hipStream_t)stream) : quant_add_host(c, rows, group_off, n_groups);
-  c->add_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
+  return on_device ? quant_add_device(c, rows, group_off, n_groups, (hipStream_t)stream) : quant_add_host(c, rows, group_off, n_groups);
 }
 
 extern "C" int br_quant_add(br_quant *c, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t n_groups,
@@ -272,12 +237,8 @@ extern "C" int br_quant_add_last(br_quant *c, br_ctx *ctx) {
   return br_quant_add_rows(c, &ctx->last_rows, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
 }
 
-// scratch of the scans (over n + 1 items or the histograms) and of the OR / AND reduction (2 words a block of 256)
-static int quant_tmp(br_quant *c, int64_t n) {
-  const int64_t blocks = (n + 255) / 256, nh = 256 * ((n + COL_TILE - 1) / COL_TILE);
-  return c->alloc(c->tmp, (size_t)std::max<int64_t>(2 * blocks + 2, std::max<int64_t>(nh, n + 1) / 1024 + 8) * 8);
-}
-// a stable LSD radix sort of (key, idx) pairs over the digits in which the keys differ; *cur = the buffer that holds the result
+static int quant_tmp(br_quant *c, int64_t n) { return c->alloc(c->tmp, scan_tmp_bytes(n)); }
+// the radix sort of (key, idx) over the digits in which the keys differ (launch_q_bits finds them); *cur = the buffer that holds the result
 static int quant_sort(br_quant *c, ColBuf key[2], ColBuf idx[2], int64_t n, int *cur) {
   hipStream_t st = c->st;
   uint64_t *small = c->small.as<uint64_t>();
@@ -288,18 +249,7 @@ static int quant_sort(br_quant *c, ColBuf key[2], ColBuf idx[2], int64_t n, int 
   uint64_t bits[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(bits, small + QS_BITS, 16, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  const int64_t tiles = (n + COL_TILE - 1) / COL_TILE, nh = 256 * tiles;
-  ColBuf hist;
-  QuantDrop dropper{c, {&hist}};
-  RC(c->alloc(hist, (size_t)(nh + 1) * 8));
-  for (int shift = 0; shift < 64; shift += 8) {
-    if ((((bits[0] ^ bits[1]) >> shift) & 255u) == 0) continue;   // the digit is the same in every key
-    launch_col_radix_pass(st, key[*cur].as<uint64_t>(), idx[*cur].as<uint32_t>(), key[*cur ^ 1].as<uint64_t>(), idx[*cur ^ 1].as<uint32_t>(),
-                          n, shift, hist.as<uint64_t>(), c->tmp.as<uint64_t>());
-    *cur ^= 1;
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  return BR_OK;
+  return c->radix_sort(key, idx, n, bits, c->tmp, cur);
 }
 
 static int quant_finish(br_quant *c) {
@@ -314,10 +264,10 @@ static int quant_finish(br_quant *c) {
   // the names with labels
   uint64_t M = 0;
   ColBuf key[2], idx[2], head, mark, gbeg, key2[2], val2[2];
-  QuantDrop sort_bufs{c, {&key[0], &key[1], &idx[0], &idx[1], &head, &mark, &gbeg, &key2[0], &key2[1], &val2[0], &val2[1]}};
+  DropGuard sort_bufs{c, {&key[0], &key[1], &idx[0], &idx[1], &head, &mark, &gbeg, &key2[0], &key2[1], &val2[0], &val2[1]}};
   {
     ColBuf pos;
-    QuantDrop dropper{c, {&pos}};
+    DropGuard dropper{c, {&pos}};
     RC(c->alloc(pos, (size_t)(N + 1) * 8)); RC(quant_tmp(c, N));
     launch_q_flag(st, c->nk.as<uint32_t>(), N, pos.as<uint64_t>());
     launch_sam_scan(st, pos.as<uint64_t>(), N, c->tmp.as<uint64_t>());
@@ -387,7 +337,7 @@ static int quant_finish(br_quant *c) {
   for (auto *b : sort_bufs.b) c->drop(*b);   // (dropping twice is harmless: an empty buffer counts nothing)
   // labels and the transposed table
   ColBuf ecls, tkey[2], tidx[2], d_lens;
-  QuantDrop table_bufs{c, {&ecls, &tkey[0], &tkey[1], &tidx[0], &tidx[1], &d_lens}};
+  DropGuard table_bufs{c, {&ecls, &tkey[0], &tkey[1], &tidx[0], &tidx[1], &d_lens}};
   const size_t l1 = (size_t)L + 1;
   RC(c->alloc(c->c_labels, l1 * 4)); RC(c->alloc(ecls, l1 * 4)); RC(c->alloc(c->t_cls, l1 * 4));
   RC(c->alloc(tkey[0], l1 * 8)); RC(c->alloc(tkey[1], l1 * 8)); RC(c->alloc(tidx[0], l1 * 4)); RC(c->alloc(tidx[1], l1 * 4));
@@ -431,7 +381,7 @@ static int quant_eff(br_quant *c) {
   const int64_t T = c->n_tx;
   const uint32_t n_bins = (uint32_t)c->fld_max + 1;
   ColBuf cs, d_lens;
-  QuantDrop dropper{c, {&cs, &d_lens}};
+  DropGuard dropper{c, {&cs, &d_lens}};
   RC(c->fld_tables());
   RC(c->alloc(c->eff, (size_t)(T + 1) * 8)); RC(c->alloc(c->w, (size_t)(T + 1) * 8));
   RC(c->alloc(cs, (size_t)n_bins * 16)); RC(c->alloc(d_lens, (size_t)(T + 1) * 8));
@@ -444,12 +394,12 @@ static int quant_eff(br_quant *c) {
 
 extern "C" int br_quant_finish(br_quant *c, int64_t *n_names, int64_t *n_classes) {
   if (!c || c->finished) return BR_ERR_INVALID_ARG;
-  auto t0 = std::chrono::steady_clock::now();
+  const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
   RC(quant_finish(c));
   RC(quant_eff(c));
   c->finished = true;
-  c->finish_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  c->finish_s = timer.seconds();
   if (n_names) *n_names = c->n;
   if (n_classes) *n_classes = c->n_cls;
   return BR_OK;
@@ -501,7 +451,7 @@ static double quant_weight(const br_quant *c, int64_t t) {
 extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
   if (!c || !c->finished) return BR_ERR_INVALID_ARG;
   if (c->eff_len && (!c->length_norm || c->lens.empty())) return BR_ERR_INVALID_ARG;   // effective lengths are a length normalisation
-  auto t0 = std::chrono::steady_clock::now();
+  const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->st;
   const int64_t T = c->n_tx, C = c->n_cls;
@@ -545,7 +495,7 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
   }
   HIPCHK(hipStreamSynchronize(st));
   c->cur = cur; c->em_done = true;
-  c->em_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  c->em_s = timer.seconds();
   if (n_iters) *n_iters = (int32_t)it;
   if (rel_change) *rel_change = rel;
   return BR_OK;

@@ -22,66 +22,42 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../../include/bramble_amd.h"
+#include "accum.h"
 #include "collate_kernels.h"
-#include "devmem.h"
 #include "sam_kernels.h"
 #include "sort_kernels.h"
 
 using namespace br;
 
-struct br_sorter {
-  int device = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev = nullptr;
+struct br_sorter : Accum {
   uint64_t max_bytes = 0;     // 0: no cap but the device's memory
   bool finished = false;
   int64_t n = 0, cur = 0;
   uint64_t used = 0;            // arena bytes in use
-  uint64_t live = 0, peak = 0;  // device bytes held by the sorter now / at most
   double add_s = 0, finish_s = 0, next_s = 0;
   ColBuf arena, off;                 // add order
   ColBuf key, order, ends, s_off;    // after finish: sorted keys, add index of every sorted record, ends (add order), stream offsets
   ColBuf buf[2], rows[2];            // next: two gather buffers alternate
   int which = 0;
   ColBuf tmp, small;
-  int alloc(ColBuf &b, size_t bytes, bool keep = false) {
-    if (bytes <= b.cap) return BR_OK;
-    void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return e == hipErrorOutOfMemory ? BR_ERR_CAPACITY : BR_ERR_HIP; }
-    live += bytes; peak = std::max(peak, live);
-    if (keep && b.p) HIPCHK(hipMemcpyAsync(q, b.p, b.cap, hipMemcpyDeviceToDevice, st));
-    if (b.p) { HIPCHK(hipStreamSynchronize(st)); live -= b.cap; b.release(); }
-    b.p = q; b.cap = bytes;
-    return BR_OK;
-  }
-  void drop(ColBuf &b) { live -= b.cap; b.release(); }
 };
 
 extern "C" void br_sorter_free(br_sorter *c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->st) (void)hipStreamSynchronize(c->st);
-  if (c->ev) (void)hipEventDestroy(c->ev);
-  if (c->st) (void)hipStreamDestroy(c->st);
+  c->close();
   delete c;
 }
 
 extern "C" int br_sorter_new(int device, br_sorter **out) {
   if (!out) return BR_ERR_INVALID_ARG;
   *out = nullptr;
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0 || device < 0 || device >= nd) { (void)hipGetLastError(); return BR_ERR_NO_DEVICE; }
-  HIPCHK(hipSetDevice(device));
   br_sorter *c = new br_sorter();
-  c->device = device;
-  int rc = hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&c->ev, hipEventDisableTiming) == hipSuccess ? BR_OK : BR_ERR_HIP;
+  int rc = c->open(device);
   if (!rc) rc = c->alloc(c->small, 64);
   if (rc) { br_sorter_free(c); return rc; }
   *out = c;
@@ -93,12 +69,6 @@ extern "C" int br_sorter_set_param(br_sorter *c, const char *name, int64_t value
   if (!strcmp(name, "max_bytes")) { if (value < 0) return BR_ERR_INVALID_ARG; c->max_bytes = (uint64_t)value; return BR_OK; }
   return BR_ERR_INVALID_ARG;
 }
-
-// device tables of one call: whatever the outcome, they go (and leave the byte count) when the call returns
-struct SortDrop {
-  br_sorter *c; std::vector<ColBuf *> b;
-  ~SortDrop() { for (auto *x : b) c->drop(*x); }
-};
 
 // room for m more records of `bytes` arena bytes (the arena keeps 64 bytes behind its end: the gather reads whole words)
 static int sort_reserve(br_sorter *c, int64_t m, uint64_t bytes) {
@@ -118,7 +88,7 @@ static int sort_reserve(br_sorter *c, int64_t m, uint64_t bytes) {
 static int sort_add_device(br_sorter *c, const br_device_bam *r, hipStream_t caller) {
   const int64_t m = r->n_rows;
   hipStream_t st = c->st;
-  HIPCHK(hipEventRecord(c->ev, caller)); HIPCHK(hipStreamWaitEvent(st, c->ev, 0));   // after whatever made the rows (NULL: the null stream's work)
+  RC(c->after(caller));   // after whatever made the rows
   uint64_t ends[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(&ends[0], r->row_off, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(&ends[1], r->row_off + m, 8, hipMemcpyDeviceToHost, st));
@@ -158,33 +128,9 @@ static int sort_add_host(br_sorter *c, const br_device_bam *r) {
 extern "C" int br_sorter_add(br_sorter *c, const br_device_bam *recs, int on_device, void *stream) {
   if (!c || !recs || recs->n_rows < 0 || (recs->n_rows && (!recs->data || !recs->row_off)) || c->finished) return BR_ERR_INVALID_ARG;
   if (recs->n_rows == 0) return BR_OK;
-  auto t0 = std::chrono::steady_clock::now();
+  ScopeTimer timer(&c->add_s);
   HIPCHK(hipSetDevice(c->device));
-  const int rc = on_device ? sort_add_device(c, recs, (hipStream_t)stream) : sort_add_host(c, recs);
-  c->add_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
-}
-
-// a stable LSD radix sort of (key, idx) pairs over the digits in which the keys differ; *cur = the buffer that holds the result
-static int sort_pairs(br_sorter *c, ColBuf key[2], ColBuf idx[2], int64_t n, const uint64_t bits[2], int *cur) {
-  const int64_t tiles = (n + COL_TILE - 1) / COL_TILE, nh = 256 * tiles;
-  ColBuf hist;
-  SortDrop dropper{c, {&hist}};
-  RC(c->alloc(hist, (size_t)(nh + 1) * 8));
-  *cur = 0;
-  for (int shift = 0; shift < 64; shift += 8) {
-    if ((((bits[0] ^ bits[1]) >> shift) & 255u) == 0) continue;   // the digit is the same in every key
-    launch_col_radix_pass(c->st, key[*cur].as<uint64_t>(), idx[*cur].as<uint32_t>(), key[*cur ^ 1].as<uint64_t>(), idx[*cur ^ 1].as<uint32_t>(),
-                          n, shift, hist.as<uint64_t>(), c->tmp.as<uint64_t>());
-    *cur ^= 1;
-  }
-  HIPCHK(hipStreamSynchronize(c->st));
-  return BR_OK;
-}
-// scratch of the scans (over n + 1 items or the histograms) and of the OR / AND reduction (2 words a block of 256)
-static size_t sort_tmp_bytes(int64_t n) {
-  const int64_t blocks = (n + 255) / 256, nh = 256 * ((n + COL_TILE - 1) / COL_TILE);
-  return (size_t)std::max<int64_t>(2 * blocks + 2, std::max<int64_t>(nh, n + 1) / 1024 + 8) * 8;
+  return on_device ? sort_add_device(c, recs, (hipStream_t)stream) : sort_add_host(c, recs);
 }
 
 static int sort_finish(br_sorter *c) {
@@ -192,9 +138,9 @@ static int sort_finish(br_sorter *c) {
   const int64_t n = c->n;
   const size_t n1 = (size_t)n + 1;
   ColBuf key[2], idx[2];
-  SortDrop dropper{c, {&key[0], &key[1], &idx[0], &idx[1]}};   // (what finish keeps is swapped out of them)
+  DropGuard dropper{c, {&key[0], &key[1], &idx[0], &idx[1]}};   // (what finish keeps is swapped out of them)
   RC(c->alloc(key[0], n1 * 8)); RC(c->alloc(key[1], n1 * 8)); RC(c->alloc(idx[0], n1 * 4)); RC(c->alloc(idx[1], n1 * 4));
-  RC(c->alloc(c->ends, n1 * 4)); RC(c->alloc(c->tmp, sort_tmp_bytes(n)));
+  RC(c->alloc(c->ends, n1 * 4)); RC(c->alloc(c->tmp, scan_tmp_bytes(n)));
   uint64_t *small = c->small.as<uint64_t>();
   HIPCHK(hipMemsetAsync(small + 6, 0, 8, st));
   launch_sort_key(st, c->arena.as<uint8_t>(), c->off.as<uint64_t>(), n, key[0].as<uint64_t>(), idx[0].as<uint32_t>(), c->ends.as<uint32_t>(),
@@ -206,7 +152,7 @@ static int sort_finish(br_sorter *c) {
   HIPCHK(hipStreamSynchronize(st));
   if (bad) return BR_ERR_INVALID_ARG;   // a pos that is no BAM position
   int cur = 0;
-  RC(sort_pairs(c, key, idx, n, bits, &cur));
+  RC(c->radix_sort(key, idx, n, bits, c->tmp, &cur));
   RC(c->alloc(c->s_off, n1 * 8));
   launch_sort_lens(st, c->off.as<uint64_t>(), idx[cur].as<uint32_t>(), n, c->s_off.as<uint64_t>());
   launch_sam_scan(st, c->s_off.as<uint64_t>(), n, c->tmp.as<uint64_t>());
@@ -217,11 +163,11 @@ static int sort_finish(br_sorter *c) {
 
 extern "C" int br_sorter_finish(br_sorter *c, int64_t *n_records) {
   if (!c || c->finished) return BR_ERR_INVALID_ARG;
-  auto t0 = std::chrono::steady_clock::now();
+  const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
   if (c->n) RC(sort_finish(c));
   c->finished = true;
-  c->finish_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  c->finish_s = timer.seconds();
   if (n_records) *n_records = c->n;
   return BR_OK;
 }
@@ -230,7 +176,7 @@ extern "C" int br_sorter_next(br_sorter *c, uint64_t max_bytes, br_device_bam *p
   if (!c || !piece || !c->finished) return BR_ERR_INVALID_ARG;
   memset(piece, 0, sizeof(*piece));
   if (c->cur >= c->n) return BR_OK;
-  auto t0 = std::chrono::steady_clock::now();
+  const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->st;
   uint64_t *res = c->small.as<uint64_t>() + 4;
@@ -247,7 +193,7 @@ extern "C" int br_sorter_next(br_sorter *c, uint64_t max_bytes, br_device_bam *p
   HIPCHK(hipStreamSynchronize(st));
   piece->data = c->buf[w].as<uint8_t>(); piece->n_bytes = cut[1]; piece->row_off = c->rows[w].as<uint64_t>(); piece->n_rows = e - c->cur;
   c->cur = e;
-  c->next_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  c->next_s += timer.seconds();
   return BR_OK;
 }
 
@@ -281,12 +227,12 @@ static int sort_index_device(br_sorter *c, int32_t n_ref, const br_bgzf_span *bl
   const size_t n1 = (size_t)n + 1, nr1 = (size_t)n_ref + 1;
   ColBuf blk, vo, key2[2], idx2[2], um, bh, ch, binc0, refmax, ref, lin_off, ref_pos, lin, out;
   // (whatever the outcome, the tables go when the call returns)
-  SortDrop dropper{c, {&blk, &vo, &key2[0], &key2[1], &idx2[0], &idx2[1], &um, &bh, &ch, &binc0, &refmax, &ref, &lin_off, &ref_pos, &lin, &out}};
+  DropGuard dropper{c, {&blk, &vo, &key2[0], &key2[1], &idx2[0], &idx2[1], &um, &bh, &ch, &binc0, &refmax, &ref, &lin_off, &ref_pos, &lin, &out}};
   RC(c->alloc(blk, (size_t)n_blocks * 16)); RC(c->alloc(vo, n1 * 8));
   RC(c->alloc(key2[0], n1 * 8)); RC(c->alloc(key2[1], n1 * 8)); RC(c->alloc(idx2[0], n1 * 4)); RC(c->alloc(idx2[1], n1 * 4));
   RC(c->alloc(um, n1 * 8)); RC(c->alloc(bh, (n1 + 1) * 8)); RC(c->alloc(ch, (n1 + 1) * 8)); RC(c->alloc(binc0, (n1 + 1) * 8));
   RC(c->alloc(refmax, nr1 * 4)); RC(c->alloc(ref, nr1 * sizeof(BaiRef))); RC(c->alloc(lin_off, nr1 * 8)); RC(c->alloc(ref_pos, nr1 * 8));
-  RC(c->alloc(c->tmp, std::max(sort_tmp_bytes(n), (size_t)(n_ref / 1024 + 8) * 8)));
+  RC(c->alloc(c->tmp, std::max(scan_tmp_bytes(n), (size_t)(n_ref / 1024 + 8) * 8)));
   uint64_t *small = c->small.as<uint64_t>();
   HIPCHK(hipMemcpyAsync(blk.p, blocks, (size_t)n_blocks * 16, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(small, 0, 32, st));
@@ -304,7 +250,7 @@ static int sort_index_device(br_sorter *c, int32_t n_ref, const br_bgzf_span *bl
   HIPCHK(hipStreamSynchronize(st));
   if (sm[3] & (BAI_ERR_BLOCKS | BAI_ERR_REF)) return BR_ERR_INVALID_ARG;   // a record outside the block table, or a refID >= n_ref
   if (sm[3] & BAI_ERR_RANGE) return BR_ERR_UNSUPPORTED;                     // an end beyond 2^29: the binning scheme's reach
-  RC(sort_pairs(c, key2, idx2, n, sm, &A.cur));
+  RC(c->radix_sort(key2, idx2, n, sm, c->tmp, &A.cur));
   launch_sam_scan(st, A.um, n, c->tmp.as<uint64_t>());
   launch_bai_heads(st, A);
   launch_sam_scan(st, A.bh, n, c->tmp.as<uint64_t>());

@@ -949,33 +949,60 @@ class SamReader:
             pass
 
 
-class Collator:
+class _Accumulator:
+    """What the wrappers of the run accumulators (br_collator, br_sorter, br_quant, br_coverage) share: the handle, made by
+    br_<NAME>_new and freed by br_<NAME>_free, and the calls of br_<NAME>_<what> on it.  A subclass gives NAME and ARGTYPES
+    (<what> -> the argument types)."""
+    NAME, ARGTYPES, h = None, {}, None
+
+    def _open(self, device, *args):
+        L = lib()
+        for what, types in self.ARGTYPES.items():
+            getattr(L, "br_%s_%s" % (self.NAME, what)).argtypes = types
+        self.device = device
+        h = C.c_void_p()
+        check(getattr(L, "br_%s_new" % self.NAME)(device, *args, C.byref(h)), "br_%s_new" % self.NAME)
+        self.h = h
+
+    def _raw(self, what, *args):
+        """br_<NAME>_<what> on the handle as it is: the return code (0, or a BR_ERR_* value)."""
+        return getattr(lib(), "br_%s_%s" % (self.NAME, what))(self.h, *args)
+
+    def _call(self, what, *args):
+        check(self._raw(what, *args), "br_%s_%s" % (self.NAME, what))
+
+    def set_param(self, name, value):
+        self._call("set_param", name.encode(), int(value))
+
+    def close(self):
+        if self.h:
+            self._raw("free")
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Collator(_Accumulator):
     """br_collator on `device`: mapped records in any order in, bundles of whole read-name groups out (groups in the order of
     their first record, records in input order inside a group)."""
 
-    def __init__(self, device=0):
-        L = lib()
-        L.br_collator_new.argtypes = [C.c_int, _P(C.c_void_p)]
-        L.br_collator_add.argtypes = [C.c_void_p, _P(BrDeviceRecords), C.c_int, C.c_void_p]
-        L.br_collator_finish.argtypes = [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]
-        L.br_collator_next.argtypes = [C.c_void_p, C.c_int64, _P(BrDeviceRecords)]
-        L.br_collator_order.argtypes = [C.c_void_p, C.c_void_p]
-        L.br_collator_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-        L.br_collator_stats.argtypes = [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double)]
-        L.br_collator_free.argtypes = [C.c_void_p]
-        self.h = None
-        self.device = device
-        self.n = 0
-        h = C.c_void_p()
-        check(L.br_collator_new(device, C.byref(h)), "br_collator_new")
-        self.h = h
+    NAME = "collator"
+    ARGTYPES = {"new": [C.c_int, _P(C.c_void_p)], "add": [C.c_void_p, _P(BrDeviceRecords), C.c_int, C.c_void_p],
+                "finish": [C.c_void_p, _P(C.c_int64), _P(C.c_int64)], "next": [C.c_void_p, C.c_int64, _P(BrDeviceRecords)],
+                "order": [C.c_void_p, C.c_void_p], "set_param": [C.c_void_p, C.c_char_p, C.c_int64],
+                "stats": [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double)], "free": [C.c_void_p]}
 
-    def set_param(self, name, value):
-        check(lib().br_collator_set_param(self.h, name.encode(), int(value)), "br_collator_set_param")
+    def __init__(self, device=0):
+        self.n = 0
+        self._open(device)
 
     def add_records(self, recs, on_device, stream=None):
         """br_collator_add as it is: the return code (0, or a BR_ERR_* value)."""
-        return lib().br_collator_add(self.h, C.byref(recs), 1 if on_device else 0, C.c_void_p(stream or 0))
+        return self._raw("add", C.byref(recs), 1 if on_device else 0, C.c_void_p(stream or 0))
 
     def add_host(self, stream_np):
         """An uncompressed BAM alignment section in host memory ([block_size][record]..., unmapped records skipped)."""
@@ -995,24 +1022,24 @@ class Collator:
 
     def finish(self):
         n, g = C.c_int64(), C.c_int64()
-        check(lib().br_collator_finish(self.h, C.byref(n), C.byref(g)), "br_collator_finish")
+        self._call("finish", C.byref(n), C.byref(g))
         self.n = int(n.value)
         return self.n, int(g.value)
 
     def order(self):
         out = np.zeros(max(self.n, 1), dtype=np.int64)
-        check(lib().br_collator_order(self.h, out.ctypes.data), "br_collator_order")
+        self._call("order", out.ctypes.data)
         return out[:self.n]
 
     def next_records(self, max_records):
         """The next bundle as a BrDeviceRecords in HBM (n_aln = 0 at the end)."""
         recs = BrDeviceRecords()
-        check(lib().br_collator_next(self.h, int(max_records), C.byref(recs)), "br_collator_next")
+        self._call("next", int(max_records), C.byref(recs))
         return recs
 
     def stats(self):
         a, p, ad, fi = C.c_uint64(), C.c_uint64(), C.c_double(), C.c_double()
-        check(lib().br_collator_stats(self.h, C.byref(a), C.byref(p), C.byref(ad), C.byref(fi)), "br_collator_stats")
+        self._call("stats", C.byref(a), C.byref(p), C.byref(ad), C.byref(fi))
         return {"arena_bytes": int(a.value), "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value}
 
     def bundles(self, max_records):
@@ -1032,52 +1059,31 @@ class Collator:
             ln = torch.as_tensor(_DevArray(recs.rec_len, n, "<i4"), device=dev).cpu().numpy().view(np.uint32).astype(np.int64)
             yield np.concatenate([arena[o - 4:o + l] for o, l in zip(off, ln)]).astype(np.uint8)
 
-    def close(self):
-        if self.h:
-            lib().br_collator_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class BrBgzfSpan(C.Structure):
     _fields_ = [("coffset", C.c_uint64), ("uoffset", C.c_uint64)]
 
 
-class Sorter:
+class Sorter(_Accumulator):
     """br_sorter on `device`: projected records ([block_size][record] rows) in, the same records in coordinate order out (key
     (u32)refID << 32 | (u32)(pos + 1) << 1 | reverse strand, ties in the order they were added), and the BAI index of that
     order."""
 
-    def __init__(self, device=0):
-        L = lib()
-        L.br_sorter_new.argtypes = [C.c_int, _P(C.c_void_p)]
-        L.br_sorter_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-        L.br_sorter_add.argtypes = [C.c_void_p, _P(BrDeviceBam), C.c_int, C.c_void_p]
-        L.br_sorter_finish.argtypes = [C.c_void_p, _P(C.c_int64)]
-        L.br_sorter_next.argtypes = [C.c_void_p, C.c_uint64, _P(BrDeviceBam)]
-        L.br_sorter_order.argtypes = [C.c_void_p, C.c_void_p]
-        L.br_sorter_stats.argtypes = [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_double)]
-        L.br_sorter_index.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_uint64, _P(C.c_void_p), _P(C.c_uint64)]
-        L.br_sorter_free.argtypes = [C.c_void_p]
-        L.br_free_buffer.argtypes = [C.c_void_p]
-        self.h = None
-        self.device = device
-        self.n = 0
-        h = C.c_void_p()
-        check(L.br_sorter_new(device, C.byref(h)), "br_sorter_new")
-        self.h = h
+    NAME = "sorter"
+    ARGTYPES = {"new": [C.c_int, _P(C.c_void_p)], "set_param": [C.c_void_p, C.c_char_p, C.c_int64],
+                "add": [C.c_void_p, _P(BrDeviceBam), C.c_int, C.c_void_p], "finish": [C.c_void_p, _P(C.c_int64)],
+                "next": [C.c_void_p, C.c_uint64, _P(BrDeviceBam)], "order": [C.c_void_p, C.c_void_p],
+                "stats": [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_double)],
+                "index": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_uint64, _P(C.c_void_p), _P(C.c_uint64)], "free": [C.c_void_p]}
 
-    def set_param(self, name, value):
-        check(lib().br_sorter_set_param(self.h, name.encode(), int(value)), "br_sorter_set_param")
+    def __init__(self, device=0):
+        lib().br_free_buffer.argtypes = [C.c_void_p]
+        self.n = 0
+        self._open(device)
 
     def add_records(self, recs, on_device, stream=None):
         """br_sorter_add as it is: the return code (0, or a BR_ERR_* value)."""
-        return lib().br_sorter_add(self.h, C.byref(recs), 1 if on_device else 0, C.c_void_p(stream or 0))
+        return self._raw("add", C.byref(recs), 1 if on_device else 0, C.c_void_p(stream or 0))
 
     @staticmethod
     def row_offsets(stream_np):
@@ -1110,19 +1116,19 @@ class Sorter:
 
     def finish(self):
         n = C.c_int64()
-        check(lib().br_sorter_finish(self.h, C.byref(n)), "br_sorter_finish")
+        self._call("finish", C.byref(n))
         self.n = int(n.value)
         return self.n
 
     def order(self):
         out = np.zeros(max(self.n, 1), dtype=np.int64)
-        check(lib().br_sorter_order(self.h, out.ctypes.data), "br_sorter_order")
+        self._call("order", out.ctypes.data)
         return out[:self.n]
 
     def next_records(self, max_bytes):
         """The next piece as a BrDeviceBam in HBM (n_rows = 0 at the end; valid until the second next call)."""
         piece = BrDeviceBam()
-        check(lib().br_sorter_next(self.h, int(max_bytes), C.byref(piece)), "br_sorter_next")
+        self._call("next", int(max_bytes), C.byref(piece))
         return piece
 
     def pieces(self, max_bytes):
@@ -1145,8 +1151,7 @@ class Sorter:
         for k, (co, uo) in enumerate(blocks):
             arr[k].coffset, arr[k].uoffset = int(co), int(uo)
         out, n = C.c_void_p(), C.c_uint64()
-        check(lib().br_sorter_index(self.h, int(n_ref), C.cast(arr, C.c_void_p), len(blocks), int(eof_coffset), C.byref(out), C.byref(n)),
-              "br_sorter_index")
+        self._call("index", int(n_ref), C.cast(arr, C.c_void_p), len(blocks), int(eof_coffset), C.byref(out), C.byref(n))
         try:
             return C.string_at(out.value, n.value)
         finally:
@@ -1154,68 +1159,48 @@ class Sorter:
 
     def stats(self):
         a, p, ad, fi, nx = C.c_uint64(), C.c_uint64(), C.c_double(), C.c_double(), C.c_double()
-        check(lib().br_sorter_stats(self.h, C.byref(a), C.byref(p), C.byref(ad), C.byref(fi), C.byref(nx)), "br_sorter_stats")
+        self._call("stats", C.byref(a), C.byref(p), C.byref(ad), C.byref(fi), C.byref(nx))
         return {"arena_bytes": int(a.value), "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value, "next_s": nx.value}
 
-    def close(self):
-        if self.h:
-            lib().br_sorter_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Quant:
+class Quant(_Accumulator):
     """br_quant on `device`: read names (the rows of projected batches) in, equivalence classes and the EM's per-transcript
     abundances out.  lengths: one per transcript (None: no length normalisation)."""
 
+    NAME = "quant"
+    ARGTYPES = {"new": [C.c_int, C.c_int64, C.c_void_p, _P(C.c_void_p)], "set_param": [C.c_void_p, C.c_char_p, C.c_int64],
+                "set_tolerance": [C.c_void_p, C.c_double],
+                "add": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p],
+                "add_rows": [C.c_void_p, _P(BrDeviceRows), C.c_void_p, C.c_int64, C.c_int, C.c_void_p], "add_last": [C.c_void_p, C.c_void_p],
+                "fld": [C.c_void_p, C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)], "eff_lengths": [C.c_void_p, C.c_void_p],
+                "finish": [C.c_void_p, _P(C.c_int64), _P(C.c_int64)], "classes": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                "em": [C.c_void_p, _P(C.c_int32), _P(C.c_double)], "result": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                "stats": [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_uint64),
+                          _P(C.c_int64), _P(C.c_int64)], "free": [C.c_void_p]}
+
     def __init__(self, n_transcripts, lengths=None, device=0):
-        L = lib()
-        L.br_quant_new.argtypes = [C.c_int, C.c_int64, C.c_void_p, _P(C.c_void_p)]
-        L.br_quant_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-        L.br_quant_set_tolerance.argtypes = [C.c_void_p, C.c_double]
-        L.br_quant_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
-        L.br_quant_add_rows.argtypes = [C.c_void_p, _P(BrDeviceRows), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
-        L.br_quant_add_last.argtypes = [C.c_void_p, C.c_void_p]
-        L.br_quant_fld.argtypes = [C.c_void_p, C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]
-        L.br_quant_eff_lengths.argtypes = [C.c_void_p, C.c_void_p]
-        L.br_quant_finish.argtypes = [C.c_void_p, _P(C.c_int64), _P(C.c_int64)]
-        L.br_quant_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.br_quant_em.argtypes = [C.c_void_p, _P(C.c_int32), _P(C.c_double)]
-        L.br_quant_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.br_quant_stats.argtypes = [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_double),
-                                     _P(C.c_uint64), _P(C.c_int64), _P(C.c_int64)]
-        L.br_quant_free.argtypes = [C.c_void_p]
-        self.h = None
-        self.device = device
         self.n_transcripts = int(n_transcripts)
         self.n_names = self.n_classes = 0
         self.fld_max = 1000
         lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64)
         assert lens is None or lens.size == self.n_transcripts
-        h = C.c_void_p()
-        check(L.br_quant_new(device, self.n_transcripts, lens.ctypes.data if lens is not None else None, C.byref(h)), "br_quant_new")
-        self.h = h
+        self._open(device, self.n_transcripts, lens.ctypes.data if lens is not None else None)
         if lens is None:
             self.set_param("length_norm", 0)
 
     def set_param(self, name, value):
         """"hash_bits", "length_norm", "max_iters", "eff_len", "fld_max" (integers) or "tolerance" (a float)."""
         if name == "tolerance":
-            check(lib().br_quant_set_tolerance(self.h, float(value)), "br_quant_set_tolerance")
+            self._call("set_tolerance", float(value))
         else:
-            check(lib().br_quant_set_param(self.h, name.encode(), int(value)), "br_quant_set_param")
+            super().set_param(name, value)
             if name == "fld_max":
                 self.fld_max = int(value)
 
     def add_raw(self, a, row_off, group_off, n_groups, on_device, stream=None):
         """br_quant_add as it is: the return code (0, or a BR_ERR_* value)."""
-        return lib().br_quant_add(self.h, C.c_void_p(a), C.c_void_p(row_off), C.c_void_p(group_off), int(n_groups), 1 if on_device else 0,
-                                  C.c_void_p(stream or 0))
+        return self._raw("add", C.c_void_p(a), C.c_void_p(row_off), C.c_void_p(group_off), int(n_groups), 1 if on_device else 0,
+                         C.c_void_p(stream or 0))
 
     def add_host(self, rows_a, row_off, group_off):
         """rows_a: uint32 [n_rows, 4] (br_row_a: transcript_id, pos, meta, nh), row_off uint64 [n_aln + 1], group_off uint32
@@ -1238,8 +1223,7 @@ class Quant:
         rows = BrDeviceRows()
         rows.n_rows, rows.n_pool_words = int(n_rows), int(n_pool_words)
         rows.a, rows.cigar, rows.pool, rows.row_off = a, cigar, pool, row_off
-        return lib().br_quant_add_rows(self.h, C.byref(rows), C.c_void_p(group_off), int(n_groups), 1 if on_device else 0,
-                                       C.c_void_p(stream or 0))
+        return self._raw("add_rows", C.byref(rows), C.c_void_p(group_off), int(n_groups), 1 if on_device else 0, C.c_void_p(stream or 0))
 
     def add_rows_host(self, rows_a, cigar, pool, row_off, group_off):
         """add_host with the whole row table: cigar uint64 [n_rows] (the ops themselves up to two, else an offset into pool),
@@ -1263,11 +1247,11 @@ class Quant:
 
     def add_last(self, ctx):
         """The read names of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
-        check(lib().br_quant_add_last(self.h, ctx.h), "br_quant_add_last")
+        self._call("add_last", ctx.h)
 
     def finish(self):
         n, c = C.c_int64(), C.c_int64()
-        check(lib().br_quant_finish(self.h, C.byref(n), C.byref(c)), "br_quant_finish")
+        self._call("finish", C.byref(n), C.byref(c))
         self.n_names, self.n_classes = int(n.value), int(c.value)
         return self.n_names, self.n_classes
 
@@ -1276,15 +1260,15 @@ class Quant:
         nc = self.n_classes
         off = np.zeros(nc + 1, dtype=np.uint64)
         cnt, first = np.zeros(max(nc, 1), dtype=np.uint64), np.zeros(max(nc, 1), dtype=np.uint64)
-        check(lib().br_quant_classes(self.h, off.ctypes.data, None, None, None), "br_quant_classes")
+        self._call("classes", off.ctypes.data, None, None, None)
         labels = np.zeros(max(int(off[-1]), 1), dtype=np.uint32)
-        check(lib().br_quant_classes(self.h, None, labels.ctypes.data, cnt.ctypes.data, first.ctypes.data), "br_quant_classes")
+        self._call("classes", None, labels.ctypes.data, cnt.ctypes.data, first.ctypes.data)
         return off, labels[:int(off[-1])], cnt[:nc], first[:nc]
 
     def em(self):
         """-> (iterations, the last relative change looked at)"""
         n, r = C.c_int32(), C.c_double()
-        check(lib().br_quant_em(self.h, C.byref(n), C.byref(r)), "br_quant_em")
+        self._call("em", C.byref(n), C.byref(r))
         return int(n.value), float(r.value)
 
     def result(self, em=True):
@@ -1293,8 +1277,8 @@ class Quant:
         out = {"unique": np.zeros(nt, dtype=np.uint64), "ambig": np.zeros(nt, dtype=np.uint64)}
         if em:
             out["theta"], out["tpm"] = np.zeros(nt, dtype=np.float64), np.zeros(nt, dtype=np.float64)
-        check(lib().br_quant_result(self.h, out["theta"].ctypes.data if em else None, out["tpm"].ctypes.data if em else None,
-                                    out["unique"].ctypes.data, out["ambig"].ctypes.data), "br_quant_result")
+        self._call("result", out["theta"].ctypes.data if em else None, out["tpm"].ctypes.data if em else None, out["unique"].ctypes.data,
+                   out["ambig"].ctypes.data)
         return {k: v[:self.n_transcripts] for k, v in out.items()}
 
     def fld(self):
@@ -1302,75 +1286,50 @@ class Quant:
         n_no_fragment, n_out_of_range, of the adds so far"""
         hist = np.zeros(self.fld_max + 1, dtype=np.uint64)
         n, u, r = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        check(lib().br_quant_fld(self.h, hist.ctypes.data, C.byref(n), C.byref(u), C.byref(r)), "br_quant_fld")
+        self._call("fld", hist.ctypes.data, C.byref(n), C.byref(u), C.byref(r))
         return {"hist": hist, "n_obs": int(n.value), "n_no_fragment": int(u.value), "n_out_of_range": int(r.value)}
 
     def eff_lengths(self):
         """-> float64 per transcript: the effective lengths ("eff_len" = 1, after finish)"""
         eff = np.zeros(max(self.n_transcripts, 1), dtype=np.float64)
-        check(lib().br_quant_eff_lengths(self.h, eff.ctypes.data), "br_quant_eff_lengths")
+        self._call("eff_lengths", eff.ctypes.data)
         return eff[:self.n_transcripts]
 
     def stats(self):
         h, p, co = C.c_uint64(), C.c_uint64(), C.c_uint64()
         ad, fi, em = C.c_double(), C.c_double(), C.c_double()
         un, nl = C.c_int64(), C.c_int64()
-        check(lib().br_quant_stats(self.h, C.byref(h), C.byref(p), C.byref(ad), C.byref(fi), C.byref(em), C.byref(co), C.byref(un),
-                                   C.byref(nl)), "br_quant_stats")
+        self._call("stats", C.byref(h), C.byref(p), C.byref(ad), C.byref(fi), C.byref(em), C.byref(co), C.byref(un), C.byref(nl))
         return {"held_bytes": int(h.value), "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value, "em_s": em.value,
                 "collisions": int(co.value), "n_unassigned": int(un.value), "n_labels": int(nl.value)}
 
-    def close(self):
-        if self.h:
-            lib().br_quant_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Coverage:
+class Coverage(_Accumulator):
     """br_coverage on `device`: the rows of projected batches in, the depth of coverage along every transcript out (runs of equal
-    depth, per-transcript summary, the depth itself).  lengths: one per transcript."""
+    depth, per-transcript summary, the depth itself).  lengths: one per transcript.  set_param: "primary_only" 0 / 1, before the first add."""
 
     RUN_PAGE = 1 << 20
 
+    NAME = "coverage"
+    ARGTYPES = {"new": [C.c_int, C.c_int64, C.c_void_p, _P(C.c_void_p)], "set_param": [C.c_void_p, C.c_char_p, C.c_int64],
+                "add_rows": [C.c_void_p, _P(BrDeviceRows), C.c_int64, C.c_int64, C.c_int, C.c_void_p], "add_last": [C.c_void_p, C.c_void_p],
+                "finish": [C.c_void_p, _P(C.c_int64)], "runs": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                "depth": [C.c_void_p, C.c_int64, C.c_void_p], "summary": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                "stats": [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double),
+                          _P(C.c_double)], "free": [C.c_void_p]}
+
     def __init__(self, lengths, device=0):
-        L = lib()
-        L.br_coverage_new.argtypes = [C.c_int, C.c_int64, C.c_void_p, _P(C.c_void_p)]
-        L.br_coverage_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-        L.br_coverage_add_rows.argtypes = [C.c_void_p, _P(BrDeviceRows), C.c_int64, C.c_int64, C.c_int, C.c_void_p]
-        L.br_coverage_add_last.argtypes = [C.c_void_p, C.c_void_p]
-        L.br_coverage_finish.argtypes = [C.c_void_p, _P(C.c_int64)]
-        L.br_coverage_runs.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.br_coverage_depth.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-        L.br_coverage_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.br_coverage_stats.argtypes = [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64),
-                                        _P(C.c_double), _P(C.c_double)]
-        L.br_coverage_free.argtypes = [C.c_void_p]
-        self.h = None
-        self.device = device
         self.lengths = np.ascontiguousarray(lengths, dtype=np.int64)
         self.n_transcripts = int(self.lengths.size)
         self.n_runs = 0
-        h = C.c_void_p()
-        check(L.br_coverage_new(device, self.n_transcripts, self.lengths.ctypes.data if self.n_transcripts else None, C.byref(h)),
-              "br_coverage_new")
-        self.h = h
-
-    def set_param(self, name, value):
-        """"primary_only" 0 / 1, before the first add."""
-        check(lib().br_coverage_set_param(self.h, name.encode(), int(value)), "br_coverage_set_param")
+        self._open(device, self.n_transcripts, self.lengths.ctypes.data if self.n_transcripts else None)
 
     def add_rows_raw(self, a, cigar, pool, n_rows, n_pool_words, r0, r1, on_device, stream=None):
         """br_coverage_add_rows as it is (the tables as addresses): the return code (0, or a BR_ERR_* value)."""
         rows = BrDeviceRows()
         rows.n_rows, rows.n_pool_words = int(n_rows), int(n_pool_words)
         rows.a, rows.cigar, rows.pool = a, cigar, pool
-        return lib().br_coverage_add_rows(self.h, C.byref(rows), int(r0), int(r1), 1 if on_device else 0, C.c_void_p(stream or 0))
+        return self._raw("add_rows", C.byref(rows), int(r0), int(r1), 1 if on_device else 0, C.c_void_p(stream or 0))
 
     def add_rows_host(self, rows_a, cigar, pool, r0=0, r1=None):
         """rows_a: uint32 [n_rows, 4] (br_row_a: transcript_id, pos, meta, nh), cigar uint64 [n_rows] (the ops themselves up to two,
@@ -1393,11 +1352,11 @@ class Coverage:
 
     def add_last(self, ctx):
         """All rows of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
-        check(lib().br_coverage_add_last(self.h, ctx.h), "br_coverage_add_last")
+        self._call("add_last", ctx.h)
 
     def finish(self):
         n = C.c_int64()
-        check(lib().br_coverage_finish(self.h, C.byref(n)), "br_coverage_finish")
+        self._call("finish", C.byref(n))
         self.n_runs = int(n.value)
         return self.n_runs
 
@@ -1407,13 +1366,13 @@ class Coverage:
         out = [np.zeros(max(self.n_runs, 1), dtype=np.uint32) for _ in range(4)]
         for first in range(0, self.n_runs, page):
             n = min(page, self.n_runs - first)
-            check(lib().br_coverage_runs(self.h, first, n, *[o[first:].ctypes.data for o in out]), "br_coverage_runs")
+            self._call("runs", first, n, *[o[first:].ctypes.data for o in out])
         return tuple(o[:self.n_runs] for o in out)
 
     def depth(self, tid):
         """-> uint32 [max(L[tid], 0)]"""
         d = np.zeros(max(int(self.lengths[tid]), 1), dtype=np.uint32)
-        check(lib().br_coverage_depth(self.h, int(tid), d.ctypes.data), "br_coverage_depth")
+        self._call("depth", int(tid), d.ctypes.data)
         return d[:max(int(self.lengths[tid]), 0)]
 
     def summary(self):
@@ -1421,25 +1380,13 @@ class Coverage:
         nt = max(self.n_transcripts, 1)
         out = {"records": np.zeros(nt, dtype=np.uint64), "aligned_bases": np.zeros(nt, dtype=np.uint64),
                "covered_bases": np.zeros(nt, dtype=np.uint64), "max_depth": np.zeros(nt, dtype=np.uint32)}
-        check(lib().br_coverage_summary(self.h, out["records"].ctypes.data, out["aligned_bases"].ctypes.data,
-                                        out["covered_bases"].ctypes.data, out["max_depth"].ctypes.data), "br_coverage_summary")
+        self._call("summary", out["records"].ctypes.data, out["aligned_bases"].ctypes.data, out["covered_bases"].ctypes.data,
+                   out["max_depth"].ctypes.data)
         return {k: v[:self.n_transcripts] for k, v in out.items()}
 
     def stats(self):
         rc, rs, cb, h, p = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
         ad, fi = C.c_double(), C.c_double()
-        check(lib().br_coverage_stats(self.h, C.byref(rc), C.byref(rs), C.byref(cb), C.byref(h), C.byref(p), C.byref(ad), C.byref(fi)),
-              "br_coverage_stats")
+        self._call("stats", C.byref(rc), C.byref(rs), C.byref(cb), C.byref(h), C.byref(p), C.byref(ad), C.byref(fi))
         return {"rows_counted": int(rc.value), "rows_skipped": int(rs.value), "clipped_bases": int(cb.value), "held_bytes": int(h.value),
                 "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value}
-
-    def close(self):
-        if self.h:
-            lib().br_coverage_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -157,6 +157,23 @@ def test_hand_built_table(how, primary_only):
     c.close()
 
 
+def test_held_bytes_follow_the_device_memory_account():
+    """coverage.cpp's "Device memory" account, to the byte: what new makes; a host add's uploads (24 bytes a row and 4 a pool word,
+    one entry more each) are in the peak and gone from the held bytes when the add returns; what finish leaves"""
+    rows, _ = _hand_built()
+    a, ref, pool = packed_of(rows)
+    T, B = len(HAND_LENS), int(np.maximum(HAND_LENS, 0).sum())
+    from_new = 4 * (B + 1) + 16 * (T + 1) + 64
+    c = lib.Coverage(HAND_LENS)
+    assert c.stats()["held_bytes"] == from_new
+    c.add_rows_host(a, ref, pool)
+    st = c.stats()
+    assert st["held_bytes"] == from_new and st["peak_bytes"] == from_new + 24 * (len(a) + 1) + 4 * (len(pool) + 1)
+    n_runs = c.finish()
+    assert n_runs > 300 and c.stats()["held_bytes"] == from_new + 20 * (T + 1) + 16 * (n_runs + 1)
+    c.close()
+
+
 def test_a_depth_carried_through_more_tiles_than_one_scan_block_takes():
     """4 300 000 bases are more than 1 024 tiles of 4 096: the scan of the tile sums is itself tiled"""
     lens = np.asarray([4300000, 7], dtype=np.int64)
