@@ -9,6 +9,7 @@
 
 #include "collate_kernels.h"
 #include "devmem.h"
+#include "scan_kernels.h"
 
 namespace br {
 
@@ -99,10 +100,11 @@ struct ScopeTimer {
   ~ScopeTimer() { if (to) *to += seconds(); }
 };
 
-// scratch of the scans (over n + 1 items or the radix histograms) and of the OR / AND reduction (2 words a block of 256)
+// scratch of the scans (over n + 1 items or the radix histograms: scan_kernels.h) and of the OR / AND reduction (2 words a
+// block of 256)
 inline size_t scan_tmp_bytes(int64_t n) {
   const int64_t blocks = (n + 255) / 256, nh = 256 * ((n + COL_TILE - 1) / COL_TILE);
-  return (size_t)std::max<int64_t>(2 * blocks + 2, std::max<int64_t>(nh, n + 1) / 1024 + 8) * 8;
+  return (size_t)std::max<int64_t>(2 * blocks + 2, scan_tiles_for(std::max<int64_t>(nh, n + 1))) * 8;
 }
 
 inline int Accum::radix_sort(ColBuf key[2], ColBuf idx[2], int64_t n, const uint64_t bits[2], const ColBuf &tmp, int *cur) {

@@ -22,6 +22,7 @@
 #include "bam_cg.h"
 #include "kernels.h"
 #include "records_inl.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -40,7 +41,7 @@ __global__ void __launch_bounds__(256) k_bam_scan(BamArgs B) {
   // end of the last record byte of the blob: a k_bam_tasks copy of fewer than 16 bytes loads 16 and must not read past it
   unsigned long long e = 0;
   if (a < B.n_aln) e = B.rec_off[a] + (B.rec_len ? (uint64_t)B.rec_len[a] : B.rec_off[a + 1] - B.rec_off[a]);
-  for (int o = 32; o; o >>= 1) { unsigned long long t = __shfl_xor(e, o); e = t > e ? t : e; }
+  e = wave_max(e);
   if ((threadIdx.x & 63) == 0) sh_end[threadIdx.x >> 6] = e;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -160,8 +161,7 @@ __device__ __forceinline__ void encode_row(const BamArgs &B, int64_t r, int lane
   if (spill) {
     uint32_t part = 0;        // bam_cigar2rlen: M, D, N, =, X consume the reference
     for (uint32_t k = lane; k < n_cig; k += G) { const uint32_t w = cgp[k], op = w & 0xfu; if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) part += w >> 4; }
-#pragma unroll
-    for (int d = G / 2; d; d >>= 1) part += (uint32_t)__shfl_xor((int)part, d, G);
+    part = wave_sum<uint32_t, G>(part);
     if (part >= (1u << 28) && lane == 0) *B.too_long = 1;   // bam_write1 fails on such a record
     if (lane == 0) { *(u32u *)(out + o) = ((uint32_t)l_seq << 4) | 4u; *(u32u *)(out + o + 4) = (part << 4) | 3u; }
     o += 8;
@@ -297,8 +297,7 @@ __global__ void __launch_bounds__(256) k_bam_tasks(BamArgs B) {
   const int nr = (int)(B.n_rows - r0 < R ? B.n_rows - r0 : R);
   const uint64_t span0 = B.out_off[r0];
   uint64_t be = B.blob_end[(size_t)(lane & (BLOB_END_SLOTS - 1)) * BLOB_END_STRIDE];   // the maximum over k_bam_scan's slots
-#pragma unroll
-  for (int o = 32; o; o >>= 1) { const uint64_t t = __shfl_xor(be, o); be = t > be ? t : be; }
+  be = wave_max(be);
   const uint8_t *blob_end = B.blob + be;
 
   // ---- 1. one lane per row ----
@@ -390,9 +389,7 @@ __global__ void __launch_bounds__(256) k_bam_tasks(BamArgs B) {
   }
   static_assert(R + 4 <= 64 && (R & (R - 1)) == 0, "rows per wave");
   // first task of every row: a scan over the wave
-  uint32_t incl = row_tasks;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(incl, d); if (lane >= d) incl += up; }
+  const uint32_t incl = wave_scan(row_tasks);
   const uint32_t n_tasks = (uint32_t)__builtin_amdgcn_readfirstlane((int)__shfl(incl, 63));
   if (lane < R + 4) { L.row_tp[lane] = lane < nr ? incl - row_tasks : 0xffffffffu; L.row_at[lane] = row_at; }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

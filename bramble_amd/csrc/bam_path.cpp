@@ -45,9 +45,8 @@ static int bam_encode_impl(br_ctx *c, const br_config *cfg, const br_device_reco
   if (!aux_done) { HIPCHK(hipMemsetAsync(B.blob_end, 0, BLOB_END_SLOTS * BLOB_END_STRIDE * 8, st)); launch_bam_scan(st, B); }
   launch_bam_size(st, B);
   RC(pf.end());
-  ScanArgs S{}; S.n = nr; S.src32 = B.out_len; S.tile_sums = c->tile_sums.as<uint64_t>();
   RC(pf.begin(BR_K_SCAN));
-  launch_scan(st, S, 2, c->bam_off.p, true, d_tot + TOT_BAM_BYTES);
+  launch_scan(st, B.out_len, nr, c->tile_sums.as<uint64_t>(), c->bam_off.p, true, d_tot + TOT_BAM_BYTES);
   RC(pf.end());
   HIPCHK(hipMemcpyAsync(c->rb->bam, d_tot + TOT_BAM_LONG, 16, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -139,11 +138,11 @@ extern "C" int br_project_bam_device(br_ctx *c, const br_config *cfg, const br_d
   launch_rec_fields(st, P);
   RC(pf.end());
   uint64_t *d_tot = c->totals.as<uint64_t>();
-  ScanArgs S{}; S.n = n; S.tile_sums = c->tile_sums.as<uint64_t>();
+  uint64_t *const ts = c->tile_sums.as<uint64_t>();
   RC(pf.begin(BR_K_SCAN));
-  S.src32 = P.ncig;     launch_scan(st, S, 2, c->b_cigar_off.p, false, d_tot + TOT_PARSE_CIGAR);
-  S.src32 = P.name_len; launch_scan(st, S, 2, c->b_name_off.p, false, d_tot + TOT_PARSE_NAMES);
-  S.src32 = P.isnew;    launch_scan(st, S, 2, c->p_group_pre.p, false, d_tot + TOT_PARSE_GROUPS);
+  launch_scan(st, P.ncig, n, ts, c->b_cigar_off.p, false, d_tot + TOT_PARSE_CIGAR);
+  launch_scan(st, P.name_len, n, ts, c->b_name_off.p, false, d_tot + TOT_PARSE_NAMES);
+  launch_scan(st, P.isnew, n, ts, c->p_group_pre.p, false, d_tot + TOT_PARSE_GROUPS);
   RC(pf.end());
   HIPCHK(hipMemcpyAsync(c->rb->parse_n, d_tot + TOT_PARSE_CIGAR, 3 * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(&c->rb->parse_max, c->p_small.p, 8, hipMemcpyDeviceToHost, st));
@@ -170,7 +169,7 @@ extern "C" int br_project_bam_device(br_ctx *c, const br_config *cfg, const br_d
     launch_seq_src(st, P);
     RC(pf.end());
     RC(pf.begin(BR_K_SCAN));
-    S.src32 = P.seq_len; launch_scan(st, S, 2, c->b_seq_off.p, false, d_tot + TOT_PARSE_SEQ);
+    launch_scan(st, P.seq_len, n, ts, c->b_seq_off.p, false, d_tot + TOT_PARSE_SEQ);
     RC(pf.end());
     HIPCHK(hipMemcpyAsync(&c->rb->parse_seq, d_tot + TOT_PARSE_SEQ, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -250,9 +249,8 @@ static int deflate_device_impl(br_ctx *c, const uint8_t *src, uint64_t n, hipStr
     for (int k = 0; k < 8; k++) fprintf(stderr, "[deflate profile] %-12s %5.1f %%\n", nm[k], 100.0 * (double)pt[k] / tot);
   }
 #endif
-  ScanArgs S{}; S.n = (int64_t)nb; S.src32 = A.sizes; S.tile_sums = c->tile_sums.as<uint64_t>();
   RC(pf.begin(BR_K_SCAN));
-  launch_scan(st, S, 2, c->z_off.p, true, d_tot + TOT_DEFLATE);
+  launch_scan(st, A.sizes, (int64_t)nb, c->tile_sums.as<uint64_t>(), c->z_off.p, true, d_tot + TOT_DEFLATE);
   RC(pf.end());
   HIPCHK(hipMemcpyAsync(&c->rb->deflate_total, d_tot + TOT_DEFLATE, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -64,8 +65,7 @@ struct BitWriter {
 
   // every lane contributes up to two pieces (<= 31 bits each), A before B, lane order
   __device__ __forceinline__ void round(int lane, uint32_t va, uint32_t na, uint32_t vb, uint32_t nb) {
-    uint32_t nbits = na + nb, inc = nbits;
-    for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    const uint32_t nbits = na + nb, inc = wave_scan(nbits);
     uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63) + cbits;
     uint32_t pos = cbits + inc - nbits;
     if (lane == 0) obuf[0] = carry;
@@ -298,7 +298,7 @@ __device__ __forceinline__ void build_lengths(uint32_t *freq, uint8_t *lens, int
   // symbols of this lane: lane, lane + 64, ...
   uint32_t total = 0, used = 0;
   for (int i = lane; i < nsym; i += 64) { total += freq[i]; used += freq[i] ? 1u : 0u; }
-  for (int o = 32; o > 0; o >>= 1) { total += __shfl_xor(total, o); used += __shfl_xor(used, o); }
+  total = wave_sum(total); used = wave_sum(used);
   if (used == 0) { for (int i = lane; i < nsym; i += 64) lens[i] = 0; return; }
   if (used == 1) {   // one symbol: one bit (an inflater accepts the incomplete code only for distances; callers make
                      // sure the literal/length alphabet has at least two symbols: a literal or match plus end-of-block)
@@ -315,14 +315,14 @@ __device__ __forceinline__ void build_lengths(uint32_t *freq, uint8_t *lens, int
     }
     lens[i] = l;
   }
-  for (int o = 32; o > 0; o >>= 1) k15 += __shfl_xor(k15, o);
+  k15 = wave_sum(k15);
   __builtin_amdgcn_wave_barrier();
   // above one (only through the 15-bit limit): lengthen the rarest symbol that is not at the limit yet
   while (k15 > 32768) {
     uint32_t best = 0xffffffffu; int bi = -1;
     for (int i = lane; i < nsym; i += 64) if (lens[i] && lens[i] < 15 && freq[i] < best) { best = freq[i]; bi = i; }
     uint64_t key = ((uint64_t)best << 32) | (uint32_t)bi;
-    for (int o = 32; o > 0; o >>= 1) { uint64_t t = __shfl_xor(key, o); key = t < key ? t : key; }
+    key = wave_min(key);
     int pick = (int)(uint32_t)key;
     if (pick < 0) break;                              // cannot happen: 286 symbols at 15 bits sum to < 1
     uint8_t l = lens[pick];

@@ -24,7 +24,7 @@
 #include "../../include/bramble_amd.h"
 #include "accum.h"
 #include "collate_kernels.h"
-#include "sam_kernels.h"
+#include "scan_kernels.h"
 
 using namespace br;
 
@@ -86,10 +86,10 @@ static int col_add_device(br_collator *c, const br_device_records *r, hipStream_
   const int64_t m = r->n_aln;
   hipStream_t st = c->st;
   RC(c->after(caller));   // after whatever made the records
-  RC(c->alloc(c->tmp, (size_t)(m + 1) * 8 + ((size_t)m / 1024 + 4) * 8));
+  RC(c->alloc(c->tmp, (size_t)(m + 1) * 8 + scan_scratch_bytes(m)));
   uint64_t *bytes = c->tmp.as<uint64_t>(), *scan_tmp = bytes + m + 1;
   launch_col_lens(st, r->rec_off, r->rec_len, m, bytes);
-  launch_sam_scan(st, bytes, m, scan_tmp);
+  launch_scan(st, bytes, m, scan_tmp);
   uint64_t total = 0;
   HIPCHK(hipMemcpyAsync(&total, bytes + m, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -216,7 +216,7 @@ static int col_finish(br_collator *c) {
   }
   c->drop(runs);
   // place
-  launch_sam_scan(st, head, n, c->tmp.as<uint64_t>());   // head -> group ids (exclusive), head[n] = G
+  launch_scan(st, head, n, c->tmp.as<uint64_t>());   // head -> group ids (exclusive), head[n] = G
   uint64_t G = 0;
   HIPCHK(hipMemcpyAsync(&G, head + n, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -225,12 +225,12 @@ static int col_finish(br_collator *c) {
   RC(c->alloc(hc, n1 * 8));
   HIPCHK(hipMemsetAsync(hc.p, 0, n1 * 8, st));
   launch_col_head_count(st, gbeg, I, (int64_t)G, hc.as<uint64_t>());
-  launch_sam_scan(st, hc.as<uint64_t>(), n, c->tmp.as<uint64_t>());
+  launch_scan(st, hc.as<uint64_t>(), n, c->tmp.as<uint64_t>());
   RC(c->alloc(c->out_off, n1 * 8)); RC(c->alloc(c->out_len, n1 * 4)); RC(c->alloc(mark, n1 * 8));
   uint32_t *out_idx = idx[cur ^ 1].as<uint32_t>();
   launch_col_place(st, head, gbeg, hc.as<uint64_t>(), I, c->off_in.as<uint64_t>(), c->len_in.as<uint32_t>(), n, c->out_off.as<uint64_t>(),
                    c->out_len.as<uint32_t>(), out_idx, mark.as<uint64_t>());
-  launch_sam_scan(st, mark.as<uint64_t>(), n, c->tmp.as<uint64_t>());
+  launch_scan(st, mark.as<uint64_t>(), n, c->tmp.as<uint64_t>());
   launch_col_starts(st, mark.as<uint64_t>(), n, hc.as<uint64_t>());
   HIPCHK(hipStreamSynchronize(st));
   std::swap(c->starts, hc);

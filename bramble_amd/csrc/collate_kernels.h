@@ -18,7 +18,7 @@ void launch_col_key(hipStream_t st, const uint8_t *arena, const uint64_t *off, i
                     uint32_t *idx, uint64_t *part, uint64_t *bits);
 // bits[0] = OR, bits[1] = AND of the blocks' (OR, AND) pairs in part (the coordinate sort's keys go through the same reduction)
 void launch_col_bits(hipStream_t st, const uint64_t *part, int64_t blocks, uint64_t *bits);
-// one stable LSD pass over the 8-bit digit at `shift`: hist = 256 x n_tiles (digit-major), tmp for its scan
+// one stable LSD pass over the 8-bit digit at `shift`: hist = 256 x n_tiles (digit-major), tmp: scan_tiles_for(256 * n_tiles) words, for its scan
 void launch_col_radix_pass(hipStream_t st, const uint64_t *key_in, const uint32_t *idx_in, uint64_t *key_out, uint32_t *idx_out,
                            int64_t n, int shift, uint64_t *hist, uint64_t *tmp);
 // runs: head[j] = 1 where sorted item j starts a read-name group (key or name differs from item j - 1); *n_coll = adjacent

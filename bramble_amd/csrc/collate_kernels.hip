@@ -1,6 +1,6 @@
 // Collation by read name on the device (host side: collate.cpp, which holds the pipeline's description).
 //
-//   append   k_col_lens -> scan (launch_sam_scan) -> k_col_copy: records into one arena, compacted, [block_size][record]
+//   append   k_col_lens -> scan (launch_scan, scan_kernels.h) -> k_col_copy: records into one arena, compacted, [block_size][record]
 //   key      k_col_key: FNV-1a over l_read_name and the name bytes, a 64-bit finaliser, masked (hash_bits)
 //   sort     k_col_hist + scan + k_col_scatter per 8-bit digit: a stable LSD radix sort of (key, input index)
 //   runs     k_col_heads: group starts in sorted order; equal keys with different names are counted and listed
@@ -9,7 +9,8 @@
 #include <hip/hip_runtime.h>
 
 #include "collate_kernels.h"
-#include "sam_kernels.h"
+#include "scan_kernels.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -47,7 +48,6 @@ __global__ void __launch_bounds__(256) k_col_copy(const uint8_t *blob, const uin
 
 __global__ void __launch_bounds__(256) k_col_key(const uint8_t *arena, const uint64_t *off, int64_t n, uint64_t mask, uint64_t *key,
                                                  uint32_t *idx, uint64_t *part) {
-  __shared__ uint64_t sh[2][4];
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   uint64_t o = 0, a = ~0ull;
   if (i < n) {
@@ -61,22 +61,12 @@ __global__ void __launch_bounds__(256) k_col_key(const uint8_t *arena, const uin
     key[i] = h; idx[i] = (uint32_t)i;
     o = h; a = h;
   }
-  for (int s = 32; s; s >>= 1) { o |= __shfl_xor(o, s); a &= __shfl_xor(a, s); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = o; sh[1][threadIdx.x >> 6] = a; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; w++) { o |= sh[0][w]; a &= sh[1][w]; }
-    part[2 * blockIdx.x] = o; part[2 * blockIdx.x + 1] = a;
-  }
+  block_bits(o, a, part + 2 * blockIdx.x);
 }
 __global__ void __launch_bounds__(256) k_col_bits(const uint64_t *part, int64_t blocks, uint64_t *bits) {
-  __shared__ uint64_t sh[2][4];
   uint64_t o = 0, a = ~0ull;
   for (int64_t b = threadIdx.x; b < blocks; b += 256) { o |= part[2 * b]; a &= part[2 * b + 1]; }
-  for (int s = 32; s; s >>= 1) { o |= __shfl_xor(o, s); a &= __shfl_xor(a, s); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = o; sh[1][threadIdx.x >> 6] = a; }
-  __syncthreads();
-  if (threadIdx.x == 0) { for (int w = 1; w < 4; w++) { o |= sh[0][w]; a &= sh[1][w]; } bits[0] = o; bits[1] = a; }
+  block_bits(o, a, bits);
 }
 
 // per-tile digit counts in LDS, one store per digit per tile: hist[digit * n_tiles + tile]
@@ -235,7 +225,7 @@ void launch_col_radix_pass(hipStream_t st, const uint64_t *key_in, const uint32_
   if (n <= 0) return;
   const int64_t tiles = (n + COL_TILE - 1) / COL_TILE;
   hipLaunchKernelGGL(k_col_hist, dim3((unsigned)tiles), dim3(256), 0, st, key_in, n, shift, hist, tiles);
-  launch_sam_scan(st, hist, 256 * tiles, tmp);
+  launch_scan(st, hist, 256 * tiles, tmp);
   hipLaunchKernelGGL(k_col_scatter, dim3((unsigned)tiles), dim3(256), 0, st, key_in, idx_in, key_out, idx_out, n, shift,
                      (const uint64_t *)hist, tiles);
 }

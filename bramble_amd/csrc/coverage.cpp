@@ -21,7 +21,7 @@
 #include "accum.h"
 #include "coverage_kernels.h"
 #include "ctx.h"
-#include "sam_kernels.h"
+#include "scan_kernels.h"
 
 using namespace br;
 
@@ -132,7 +132,7 @@ static int coverage_finish(br_coverage *c) {
   ColBuf tile, tmp;
   DropGuard dropper{c, {&tile, &tmp}};
   RC(c->alloc(c->aligned, t1 * 8)); RC(c->alloc(c->covered, t1 * 8)); RC(c->alloc(c->max_depth, t1 * 4));
-  RC(c->alloc(tile, (size_t)(tiles + 2) * 8)); RC(c->alloc(tmp, (size_t)(tiles / 1024 + 8) * 8));
+  RC(c->alloc(tile, (size_t)(tiles + 2) * 8)); RC(c->alloc(tmp, scan_scratch_bytes(tiles)));
   HIPCHK(hipMemsetAsync(c->aligned.p, 0, t1 * 8, st)); HIPCHK(hipMemsetAsync(c->covered.p, 0, t1 * 8, st));
   HIPCHK(hipMemsetAsync(c->max_depth.p, 0, t1 * 4, st));
   uint32_t *depth = c->diff.as<uint32_t>();
@@ -142,7 +142,7 @@ static int coverage_finish(br_coverage *c) {
   uint64_t R = 0;
   if (B > 0) {
     launch_cov_count(st, depth, B, off, T, tile.as<uint64_t>());
-    launch_sam_scan(st, tile.as<uint64_t>(), tiles, tmp.as<uint64_t>());   // tile counts -> the first run of every tile; [tiles] = R
+    launch_scan(st, tile.as<uint64_t>(), tiles, tmp.as<uint64_t>());   // tile counts -> the first run of every tile; [tiles] = R
     HIPCHK(hipMemcpyAsync(&R, tile.as<uint64_t>() + tiles, 8, hipMemcpyDeviceToHost, st));
   }
   HIPCHK(hipStreamSynchronize(st));

@@ -27,8 +27,8 @@ struct CovAddArgs {
 };
 void launch_cov_add(hipStream_t st, const CovAddArgs &A);
 
-// depth[0, n) <- its inclusive prefix sums modulo 2^32, in place.  tile_sum: n / COV_TILE + 2 words, scan_tmp: what launch_sam_scan
-// needs for that many
+// depth[0, n) <- its inclusive prefix sums modulo 2^32, in place.  tile_sum: n / COV_TILE + 2 words, scan_tmp: what launch_scan
+// (scan_kernels.h) needs for that many
 void launch_cov_scan(hipStream_t st, uint32_t *depth, int64_t n, uint64_t *tile_sum, uint64_t *scan_tmp);
 // per transcript: the sum, the number of non-zero entries and the maximum of depth[off[t], off[t + 1])
 void launch_cov_summary(hipStream_t st, const uint32_t *depth, const uint64_t *off, int64_t n_tx, uint64_t *aligned, uint64_t *covered,

@@ -6,7 +6,7 @@
 //            wave, 64 ops a step, the positions by a wave scan.  records[t] gets one atomic per distinct transcript of the wave,
 //            the counters one per wave
 //   depth    every interval lies inside its transcript, so the plain inclusive scan of diff modulo 2^32 is the depth and returns
-//            to 0 at every transcript's end: tile sums, their scan (launch_sam_scan), and the tiles scanned again with their offsets
+//            to 0 at every transcript's end: tile sums, their scan (launch_scan), and the tiles scanned again with their offsets
 //   summary  a wave per transcript of up to COV_WAVE_LEN bases, a block per longer one
 //   runs     run heads counted per tile, the counts scanned, and the runs written: the lane of a run's first base stores
 //            (transcript, start), the lane of its last base (end, depth) -- the k-th last base belongs to the k-th head, and the
@@ -16,7 +16,8 @@
 
 #include "../../include/bramble_amd.h"
 #include "coverage_kernels.h"
-#include "sam_kernels.h"
+#include "scan_kernels.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -25,26 +26,6 @@ typedef uint32_t cv_u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t cv_u2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ bool op_covers(uint32_t w) { return (0x181u >> (w & 15u)) & 1u; }   // M = X (0, 7, 8)
 __device__ __forceinline__ bool op_skips(uint32_t w) { return (0x00cu >> (w & 15u)) & 1u; }    // D N (2, 3)
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-  for (int s = 32; s; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
-  for (int s = 32; s; s >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, s); v = o > v ? o : v; }
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-  for (int s = 32; s; s >>= 1) v += __shfl_xor(v, s);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_scan32(uint32_t v, int lane) {   // inclusive
-  for (int s = 1; s < 64; s <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)v, s); if (lane >= s) v += o; }
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_scan64(uint64_t v, int lane) {   // inclusive
-  for (int s = 1; s < 64; s <<= 1) { const uint64_t o = __shfl_up(v, s); if (lane >= s) v += o; }
-  return v;
-}
 // the interval [s, e) of a transcript of len bases whose first is diff[base]: the part inside [0, len) leaves its two events (the
 // second at most at base + len, the first base of the next transcript or the word behind the last), the rest is counted as clipped
 __device__ __forceinline__ void cover(uint32_t *diff, uint64_t base, uint64_t len, uint64_t s, uint64_t e, uint64_t &clipped) {
@@ -110,7 +91,7 @@ __global__ void __launch_bounds__(256) k_cov_add(CovAddArgs A) {
       const uint32_t k = k0 + (uint32_t)lane;
       const uint32_t op = k < n ? A.pool[off + k] : 4u;   // (past the end: a soft clip of no bases)
       const uint64_t bases = op >> 4, adv = op_covers(op) || op_skips(op) ? bases : 0ull;
-      const uint64_t inc = wave_scan64(adv, lane);
+      const uint64_t inc = wave_scan(adv);
       if (op_covers(op) && bases) cover(A.diff, w_base, w_len, p + inc - adv, p + inc, clipped);
       p += __shfl(inc, 63);
     }
@@ -124,7 +105,7 @@ __global__ void __launch_bounds__(256) k_cov_add(CovAddArgs A) {
     if (lane == src) atomicAdd(A.records + t, (unsigned long long)__popcll((unsigned long long)same));
     live &= ~same;
   }
-  counted = wave_sum32(counted); skipped = wave_sum32(skipped); clipped = wave_sum64(clipped);
+  counted = wave_sum(counted); skipped = wave_sum(skipped); clipped = wave_sum(clipped);
   const bool any_bad_pool = __ballot(bad_pool) != 0, any_bad_tid = __ballot(bad_tid) != 0;
   if (lane == 0) {
     if (counted) atomicAdd(A.counters + CV_COUNTED, (unsigned long long)counted);
@@ -161,7 +142,7 @@ __global__ void __launch_bounds__(256) k_cov_tile_sum(const uint32_t *d, int64_t
   uint32_t s = 0;
 #pragma unroll
   for (int j = 0; j < 4; j++) { const cv_u4 v = load4(d, chunk_at(t0, j), n); s += v.x + v.y + v.z + v.w; }
-  s = wave_sum32(s);
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) tile_sum[blockIdx.x] = (uint64_t)(uint32_t)(sh[0] + sh[1] + sh[2] + sh[3]);
@@ -171,23 +152,16 @@ __global__ void __launch_bounds__(256) k_cov_tile_sum(const uint32_t *d, int64_t
 __global__ void __launch_bounds__(256) k_cov_tile_apply(uint32_t *d, int64_t n, const uint64_t *tile_pre) {
   __shared__ uint32_t sh[4];
   const int64_t t0 = (int64_t)blockIdx.x * COV_TILE;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint32_t carry = (uint32_t)tile_pre[blockIdx.x];
   for (int j = 0; j < 4; j++) {
     const int64_t i = chunk_at(t0, j);
     cv_u4 v = load4(d, i, n);
     v.y += v.x; v.z += v.y; v.w += v.z;
-    const uint32_t inc = wave_scan32(v.w, lane);
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    uint32_t front = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { if (k < wave) front += sh[k]; total += sh[k]; }
-    const uint32_t add = carry + front + inc - v.w;
+    uint32_t total;
+    const uint32_t add = carry + block_excl_scan_256(v.w, sh, total);   // (the lanes' sums in front of this one's four)
     v.x += add; v.y += add; v.z += add; v.w += add;
     store4(d, i, n, v);
     carry += total;
-    __syncthreads();
   }
 }
 
@@ -200,7 +174,7 @@ __global__ void __launch_bounds__(256) k_cov_summary_wave(const uint32_t *depth,
   uint64_t sum = 0;
   uint32_t nz = 0, mx = 0;
   for (uint64_t i = b + (threadIdx.x & 63); i < e; i += 64) { const uint32_t v = depth[i]; sum += v; nz += v != 0u; mx = v > mx ? v : mx; }
-  sum = wave_sum64(sum); nz = wave_sum32(nz); mx = wave_max32(mx);
+  sum = wave_sum(sum); nz = wave_sum(nz); mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0) { aligned[t] = sum; covered[t] = nz; max_depth[t] = mx; }
 }
 
@@ -214,7 +188,7 @@ __global__ void __launch_bounds__(256) k_cov_summary_long(const uint32_t *depth,
     uint64_t sum = 0, nz = 0;
     uint32_t mx = 0;
     for (uint64_t i = b + threadIdx.x; i < e; i += 256) { const uint32_t v = depth[i]; sum += v; nz += v != 0u; mx = v > mx ? v : mx; }
-    sum = wave_sum64(sum); nz = wave_sum64(nz); mx = wave_max32(mx);
+    sum = wave_sum(sum); nz = wave_sum(nz); mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0) { sh_sum[threadIdx.x >> 6] = sum; sh_nz[threadIdx.x >> 6] = nz; sh_mx[threadIdx.x >> 6] = mx; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -278,7 +252,7 @@ __global__ void __launch_bounds__(256) k_cov_count(const uint32_t *depth, int64_
     const int64_t i0 = chunk_at(t0, j);
     if (i0 < n) cnt += (uint32_t)__popc(quad_at(depth, n, off, sh_t, i0).heads);
   }
-  cnt = wave_sum32(cnt);
+  cnt = wave_sum(cnt);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = cnt;
   __syncthreads();
   if (threadIdx.x == 0) tile_cnt[blockIdx.x] = (uint64_t)(sh[0] + sh[1] + sh[2] + sh[3]);
@@ -289,7 +263,6 @@ __global__ void __launch_bounds__(256) k_cov_runs(const uint32_t *depth, int64_t
   __shared__ int64_t sh_t[2];
   __shared__ uint32_t sh[4];
   const int64_t t0 = (int64_t)blockIdx.x * COV_TILE;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   tile_span(off, n_tx, t0, n, sh_t);
   uint64_t carry = tile_pre[blockIdx.x];   // heads in front of the chunk
   cv_u2 *out = (cv_u2 *)runs;
@@ -298,13 +271,8 @@ __global__ void __launch_bounds__(256) k_cov_runs(const uint32_t *depth, int64_t
     Quad q;
     q.heads = q.tails = 0;
     if (i0 < n) q = quad_at(depth, n, off, sh_t, i0);
-    const uint32_t mine = (uint32_t)__popc(q.heads), inc = wave_scan32(mine, lane);
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    uint32_t front = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { if (k < wave) front += sh[k]; total += sh[k]; }
-    uint64_t h = carry + front + inc - mine;   // heads in front of base i0
+    uint32_t total;
+    uint64_t h = carry + block_excl_scan_256((uint32_t)__popc(q.heads), sh, total);   // heads in front of base i0
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const bool head = (q.heads >> k) & 1u, tail = (q.tails >> k) & 1u;
@@ -315,7 +283,6 @@ __global__ void __launch_bounds__(256) k_cov_runs(const uint32_t *depth, int64_t
       h += head ? 1u : 0u;
     }
     carry += total;
-    __syncthreads();
   }
 }
 
@@ -331,7 +298,7 @@ void launch_cov_scan(hipStream_t st, uint32_t *depth, int64_t n, uint64_t *tile_
   if (n <= 0) return;
   const unsigned tiles = cov_tiles(n);
   hipLaunchKernelGGL(k_cov_tile_sum, dim3(tiles), dim3(256), 0, st, (const uint32_t *)depth, n, tile_sum);
-  launch_sam_scan(st, tile_sum, (int64_t)tiles, scan_tmp);
+  launch_scan(st, tile_sum, (int64_t)tiles, scan_tmp);
   hipLaunchKernelGGL(k_cov_tile_apply, dim3(tiles), dim3(256), 0, st, depth, n, (const uint64_t *)tile_sum);
 }
 void launch_cov_summary(hipStream_t st, const uint32_t *depth, const uint64_t *off, int64_t n_tx, uint64_t *aligned, uint64_t *covered,

@@ -143,6 +143,7 @@ __device__ __forceinline__ bool pair_window(const DirectArgs &D, PmSh<CAP> &S, i
   const uint32_t cnt4 = (cnt + 3u) & ~3u;
   const uint32_t ext = (active && !m_in) ? (uint32_t)__popcll(mk_p) : 0u;
   const uint32_t nA = active ? cnt4 : 0u, nP = (pair && !active ? cnt4 : 0u) + ((ext + 3u) & ~3u);
+  // (the two scans share their shuffles' waits; two wave_scan calls cost k_pair_mask two SGPRs)
   uint32_t incA = nA, incP = nP;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) { const uint32_t ua = __shfl_up(incA, d), up = __shfl_up(incP, d); if (lane >= d) { incA += ua; incP += up; } }
@@ -262,8 +263,7 @@ __global__ void __launch_bounds__(64) k_big(ProjectArgs A, DirectArgs D) {
       // entries w + (l + 64 k) * gridDim.x, one atomic per wave
       unsigned long long need = 0;
       for (uint64_t v = (uint64_t)w + (uint64_t)lane * gridDim.x; v < n_work; v += 64ull * gridDim.x) need += side_need(D.n_matches[D.big_list[v]]);
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) need += __shfl_down(need, d, 64);
+      need = wave_sum(need);
       if (lane == 0 && need) atomicAdd(D.side_used, need);
       return;
     }
@@ -494,8 +494,7 @@ __global__ void __launch_bounds__(256) k_scan5_tiles(DirectArgs D, uint64_t *til
   // sums only (no prefixes here): wave reductions, one barrier
 #pragma unroll
   for (int c = 0; c < 5; c++)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) sum[c] += __shfl_down(sum[c], d, 64);
+    sum[c] = wave_sum(sum[c]);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int c = 0; c < 5; c++) sh[threadIdx.x >> 6][c] = sum[c];
@@ -506,26 +505,9 @@ __global__ void __launch_bounds__(256) k_scan5_tiles(DirectArgs D, uint64_t *til
 // One block per quantity, 32 tile sums per thread and round (all of a round's loads in flight at once): the five
 // quantities in one block, eight sums per thread, took 0.23 ms -- 25 dependent load / scan / store rounds of one workgroup
 // on the step's critical path.
-#define SCAN5_TOP_ITEMS 32
 __global__ void __launch_bounds__(256) k_scan5_top(uint64_t *tile_sums, int64_t n_tiles, uint64_t *total_out) {
   __shared__ uint64_t sh[4];
-  uint64_t *ts = tile_sums + (int64_t)blockIdx.x * n_tiles;
-  uint64_t carry = 0;
-  for (int64_t base = 0; base < n_tiles; base += 256 * SCAN5_TOP_ITEMS) {
-    const int64_t i0 = base + (int64_t)threadIdx.x * SCAN5_TOP_ITEMS;
-    uint64_t v[SCAN5_TOP_ITEMS];
-#pragma unroll
-    for (int k = 0; k < SCAN5_TOP_ITEMS; k++) v[k] = i0 + k < n_tiles ? ts[i0 + k] : 0;
-    uint64_t sum = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN5_TOP_ITEMS; k++) sum += v[k];
-    uint64_t tot;
-    uint64_t ex = carry + block_excl_scan_256(sum, sh, tot);
-#pragma unroll
-    for (int k = 0; k < SCAN5_TOP_ITEMS; k++) { if (i0 + k < n_tiles) ts[i0 + k] = ex; ex += v[k]; }
-    carry += tot;
-  }
-  if (threadIdx.x == 0) total_out[blockIdx.x] = carry;
+  scan_top_rounds<1, 32>(tile_sums + (int64_t)blockIdx.x * n_tiles, n_tiles, total_out + blockIdx.x, sh);
 }
 __global__ void __launch_bounds__(256) k_scan5_apply(DirectArgs D, const uint64_t *tile_sums, int64_t n_tiles, const uint64_t *totals) {
   __shared__ uint64_t sh[4];
@@ -660,8 +642,7 @@ __global__ void __launch_bounds__(256) k_group_desc(DirectArgs D) {
   // address queue up in one L2 channel -- and every load of the kernels beside that needs that channel queues with them);
   // the host adds the slots up
   __shared__ unsigned long long sh_c[4][2];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { uniq += __shfl_down(uniq, d, 64); dropped += __shfl_down(dropped, d, 64); }
+  uniq = wave_sum(uniq); dropped = wave_sum(dropped);
   if ((threadIdx.x & 63) == 0) { sh_c[threadIdx.x >> 6][0] = uniq; sh_c[threadIdx.x >> 6][1] = dropped; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -701,6 +682,7 @@ __global__ void __launch_bounds__(256) k_expand_rows(DirectArgs D) {
     const uint32_t mine = (nk && fast == (c == 0)) ? nk : 0u;
     const uint64_t have = __ballot(mine != 0u);
     if (!have) continue;                       // the same for the whole wave
+    // (written out, not wave_scan: through the helper this kernel took 8 more SGPRs and a VGPR, for a reason not found, and it is on the step's path)
     uint32_t inc = mine;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d); if (lane >= d) inc += up; }

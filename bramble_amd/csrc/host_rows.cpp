@@ -108,8 +108,7 @@ static int prep_staged(br_ctx *c, const br_config *cfg, br_ctx::InSlot &S, hipSt
   A.names = S.names.as<uint8_t>(); A.cigar = S.cigar.as<uint32_t>(); A.isnew = S.isnew.as<uint32_t>(); A.maxima = c->p_small.as<uint32_t>();
   launch_soa_fields(st, A);
   uint64_t *d_tot = c->totals.as<uint64_t>();
-  ScanArgs SC{}; SC.n = n; SC.tile_sums = c->tile_sums.as<uint64_t>(); SC.src32 = A.isnew;
-  launch_scan(st, SC, 2, S.group_pre.p, false, d_tot + TOT_HOST_GROUPS);
+  launch_scan(st, A.isnew, n, c->tile_sums.as<uint64_t>(), S.group_pre.p, false, d_tot + TOT_HOST_GROUPS);
   HIPCHK(hipMemcpyAsync(&c->rb->host_groups, d_tot + TOT_HOST_GROUPS, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(&c->rb->host_max, c->p_small.p, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -167,8 +166,7 @@ extern "C" int br_project_staged(br_ctx *c, const br_config *cfg, int slot, br_h
     Q.sizes = c->pool_sizes.as<uint32_t>(); Q.off = c->pool_off.as<uint64_t>(); Q.c_out = c->pk_ch.as<uint2>();
     if (c->host_detail) RC(ensure_detail(c, st));
     launch_pool_sizes(st, Q);
-    ScanArgs SP{}; SP.n = (int64_t)nr; SP.src32 = Q.sizes; SP.tile_sums = c->tile_sums.as<uint64_t>();
-    launch_scan(st, SP, 2, c->pool_off.p, true, c->totals.as<uint64_t>() + TOT_HOST_POOL);
+    launch_scan(st, Q.sizes, (int64_t)nr, c->tile_sums.as<uint64_t>(), c->pool_off.p, true, c->totals.as<uint64_t>() + TOT_HOST_POOL);
     HIPCHK(hipMemcpyAsync(&c->rb->host_pool, c->totals.as<uint64_t>() + TOT_HOST_POOL, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     np = (size_t)c->rb->host_pool;

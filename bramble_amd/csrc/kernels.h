@@ -5,6 +5,7 @@
 
 #include "device_types.h"
 #include "ksw_types.h"
+#include "scan_kernels.h"
 
 namespace br {
 
@@ -155,15 +156,15 @@ struct KswFastArgs {
   uint32_t *raw_out, *raw_n; int32_t *max_out; uint32_t raw_cap;
 };
 
+// the fused three-value scan of the count pass (launch_scan3)
 struct ScanArgs {
   int64_t n;
-  const uint32_t *src32;
-  const uint32_t *cigar_off;  // mode 1 only
-  const uint4 *head;          // mode 1 only
-  const uint32_t *ideal_cap;  // mode 3 only
-  const uint32_t *fast_flag;  // scan3 only
-  uint64_t *tile_sums;
-  int64_t n_tiles;            // scan3 only (set by the launcher)
+  const uint32_t *src32;      // n_matches
+  const uint32_t *cigar_off;  // read with ideal_cap only
+  const uint32_t *ideal_cap;  // -S path: per-alignment capacities (NULL: the class word's)
+  const uint32_t *fast_flag;  // the class word: CIGAR slot capacity | simple class << 31
+  uint64_t *tile_sums;        // 3 x scan_tiles_for(n) words
+  int64_t n_tiles;            // (set by the launcher)
 };
 
 // Packed row table: the product of the row stage (one row per emitted BAM record, rows of one read-name group
@@ -495,10 +496,6 @@ void launch_expand(hipStream_t st, const ProjectArgs &A);
 // everything, 1: the simple prefix, 2: the rest
 void launch_emit_dense(hipStream_t st, const ProjectArgs &A, int64_t n_matches, int64_t n_simple, int part);
 void launch_emit_dense_fa(hipStream_t st, const ProjectArgs &A, const FaArgs &F, int64_t n_matches);
-int64_t scan_tiles_for(int64_t n);
-// mode 0: src32 as is; 1: n_matches * CIGAR slot capacity; 2: src32 as is (alias of 0);
-// 3: n_matches * CIGAR slot capacity with the per-alignment ideal_cap[] of the -S path
-void launch_scan(hipStream_t st, const ScanArgs &S, int mode, void *out, bool out64, uint64_t *total_out);
 void launch_group_ids(hipStream_t st, int64_t n_groups, const uint32_t *group_off, uint32_t *aln_group);
 bool launch_scan3(hipStream_t st, ScanArgs S, uint32_t *match_off, uint64_t *cig_base, uint32_t *fast_pre,
                   uint64_t *total_out3, const ProjectArgs *expand = nullptr);

@@ -25,6 +25,7 @@
 
 #include "device_types.h"
 #include "kernels.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -636,7 +637,7 @@ __global__ void __launch_bounds__(256) k_ksw_trace(KswFastArgs A, const KswDesc 
   }
   uint64_t m = __ballot(rescued != 0);
   if (lane == 0 && m && A.stats) atomicAdd((unsigned long long *)&A.stats[1], (unsigned long long)__popcll(m));
-  for (int d = 32; d >= 1; d >>= 1) cells += (unsigned long long)__shfl_xor((long long)cells, d, 64);   // qlen x tlen of the stats line
+  cells = wave_sum(cells);   // qlen x tlen of the stats line
   if (lane == 0 && cells && A.stats) atomicAdd((unsigned long long *)&A.stats[0], cells);
 }
 

@@ -22,6 +22,7 @@
 #include "bam_cg.h"
 #include "kernels.h"
 #include "records_inl.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -50,10 +51,7 @@ __global__ void __launch_bounds__(256) k_rec_fields(ParseArgs P) {
     rec_fields_one(P, i, rec, rec_length(P, i), prev, i > 0 ? rec_length(P, i - 1) : 0u, ncig, max_s);   // records_inl.h
   }
   // batch maxima: one atomic per wave
-  for (int o = 32; o > 0; o >>= 1) {
-    ncig = max(ncig, (uint32_t)__shfl_xor((int)ncig, o));
-    max_s = max(max_s, (uint32_t)__shfl_xor((int)max_s, o));
-  }
+  ncig = wave_max(ncig); max_s = wave_max(max_s);
   // the maxima only grow: a (possibly stale) plain read filters out nearly every same-address atomic
   if ((threadIdx.x & 63) == 0) {
     if (ncig > __builtin_nontemporal_load(P.maxima)) atomicMax(P.maxima, ncig);
@@ -248,10 +246,7 @@ __global__ void __launch_bounds__(256) k_soa_fields(SoaArgs S) {
       S.isnew[i] = isnew;
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    ncig = max(ncig, (uint32_t)__shfl_xor((int)ncig, o));
-    max_s = max(max_s, (uint32_t)__shfl_xor((int)max_s, o));
-  }
+  ncig = wave_max(ncig); max_s = wave_max(max_s);
   if ((threadIdx.x & 63) == 0) {
     if (ncig > __builtin_nontemporal_load(S.maxima)) atomicMax(S.maxima, ncig);
     if (max_s > __builtin_nontemporal_load(S.maxima + 1)) atomicMax(S.maxima + 1, max_s);

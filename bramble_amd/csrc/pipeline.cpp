@@ -203,7 +203,7 @@ static int count_pass(br_ctx *c, hipStream_t st, const ProjectArgs &A, Prof &pf,
 // what the three-value scan reads (matches per alignment; CIGAR sizes from the exon heads; the simple class)
 static ScanArgs scan3_args(br_ctx *c, const br_device_batch *b) {
   ScanArgs S{};
-  S.n = b->n_aln; S.src32 = c->n_matches.as<uint32_t>(); S.cigar_off = b->cigar_off; S.head = c->head.as<uint4>();
+  S.n = b->n_aln; S.src32 = c->n_matches.as<uint32_t>(); S.cigar_off = b->cigar_off;
   S.tile_sums = c->tile_sums.as<uint64_t>(); S.fast_flag = c->fast_flag.as<uint32_t>();
   return S;
 }
@@ -278,11 +278,9 @@ static int pair_count(br_ctx *c, hipStream_t st, const PairArgs &P, Prof &pf, bo
   RC(pf.begin(BR_K_PAIR_COUNT));
   launch_pair(st, P, false);
   RC(pf.end());
-  ScanArgs S2{};
-  S2.n = P.n_aln; S2.src32 = P.n_rows; S2.tile_sums = c->tile_sums.as<uint64_t>();
   if (wait_busy) HIPCHK(hipStreamWaitEvent(st, c->rows_busy, 0));
   RC(pf.begin(BR_K_SCAN));
-  launch_scan(st, S2, 2, c->row_off.p, true, c->totals.as<uint64_t>() + TOT_ROWS);
+  launch_scan(st, P.n_rows, P.n_aln, c->tile_sums.as<uint64_t>(), c->row_off.p, true, c->totals.as<uint64_t>() + TOT_ROWS);
   RC(pf.end());
   return BR_OK;
 }
@@ -686,11 +684,9 @@ static int run_match_table(br_ctx *c, const DevCfg &dc, const br_device_batch *b
     RC(pf.begin(BR_K_COUNT));
     launch_project_fa(st, A, F, 0, n_blocks);
     RC(pf.end());
-    ScanArgs SP{}; SP.n = n; SP.src32 = F.n_prob; SP.tile_sums = c->tile_sums.as<uint64_t>();
-    ScanArgs SB{}; SB.n = n; SB.src32 = F.seq_bytes; SB.tile_sums = c->tile_sums.as<uint64_t>();
     RC(pf.begin(BR_K_SCAN));
-    launch_scan(st, SP, 2, c->fa_prob_off.p, false, d_tot + TOT_RESCUE_PROB);
-    launch_scan(st, SB, 2, c->fa_seqarena_off.p, true, d_tot + TOT_RESCUE_SEQ);
+    launch_scan(st, F.n_prob, n, c->tile_sums.as<uint64_t>(), c->fa_prob_off.p, false, d_tot + TOT_RESCUE_PROB);
+    launch_scan(st, F.seq_bytes, n, c->tile_sums.as<uint64_t>(), c->fa_seqarena_off.p, true, d_tot + TOT_RESCUE_SEQ);
     RC(pf.end());
     HIPCHK(hipMemcpyAsync(rb->rescue_n, d_tot + TOT_RESCUE_PROB, sizeof(rb->rescue_n), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -891,12 +887,10 @@ int expand_rows(br_ctx *c, hipStream_t st, br_device_wide_rows *out) {
     W.w_refc = c->r_refc.as<int32_t>(); W.w_paired = c->r_paired.as<uint8_t>(); W.w_same = c->r_same.as<uint8_t>();
     W.w_first = c->r_first.as<uint8_t>(); W.w_primary = c->r_primary.as<uint8_t>();
     launch_wide_fields(st, W);
-    ScanArgs S3{};
     RC(c->tile_sums.ensure((size_t)std::max<int64_t>(scan_tiles_for((int64_t)n_rows + 1), 1) * 8 * 3));
     RC(ensure_totals(c));
-    S3.n = (int64_t)n_rows; S3.src32 = c->r_ncig.as<uint32_t>(); S3.tile_sums = c->tile_sums.as<uint64_t>();
     uint64_t *d_tot = c->totals.as<uint64_t>();
-    launch_scan(st, S3, 2, c->r_cigoff.p, true, d_tot + TOT_WIDE_CIGAR);
+    launch_scan(st, c->r_ncig.as<uint32_t>(), (int64_t)n_rows, c->tile_sums.as<uint64_t>(), c->r_cigoff.p, true, d_tot + TOT_WIDE_CIGAR);
     HIPCHK(hipMemcpyAsync(&c->rb->wide_cigar, d_tot + TOT_WIDE_CIGAR, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     n_out_words = c->rb->wide_cigar;

@@ -24,6 +24,7 @@
 #include "device_types.h"
 #include "kernels.h"
 #include "primary_pick.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -1067,6 +1068,7 @@ __device__ __forceinline__ void expand_chunk(const ProjectArgs &A, int64_t a, ui
     const uint32_t mine = (nm && fast == (c == 0)) ? nm : 0u;
     const uint64_t have = __ballot(mine != 0u);
     if (!have) continue;                       // the same for the whole wave
+    // (written out, not wave_scan: through the helper this kernel took 8 more SGPRs, for a reason not found, and it is on the step's path)
     uint32_t inc = mine;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d); if (lane >= d) inc += up; }
@@ -1254,151 +1256,9 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 6) k_emit_dense(ProjectArg
 }
 
 // ---------------------------------------------------------------------------
-// exclusive scans.  Tile = 256 threads x 8 items.
+// the fused exclusive scans.  Tile = 256 threads x SCAN_ITEMS items (scan_kernels.h); the block scan, the vector loads
+// and the top pass are wave_inl.h's.
 // ---------------------------------------------------------------------------
-#define SCAN_ITEMS 8
-#define SCAN_TILE (256 * SCAN_ITEMS)
-
-__device__ __forceinline__ uint64_t block_excl_scan_256(uint64_t v, uint64_t *sh, uint64_t &block_total) {
-  // wave-level inclusive scan by shuffles, then across the 4 waves through LDS
-  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint64_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    uint64_t y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) sh[w] = x;
-  __syncthreads();
-  uint64_t wbase = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) { if (i < w) wbase += sh[i]; tot += sh[i]; }
-  __syncthreads();
-  block_total = tot;
-  return wbase + x - v;
-}
-
-// value of element i: MODE 0: n_matches[i]; MODE 1: n_matches[i] * cap(i); MODE 2: src32[i]
-template <int MODE>
-__device__ __forceinline__ uint64_t scan_value(const ScanArgs &S, int64_t i) {
-  if (MODE == 0 || MODE == 2) return S.src32[i];
-  uint32_t nm = S.src32[i];
-  if (nm == 0) return 0;
-  uint32_t n_real = S.cigar_off[i + 1] - S.cigar_off[i];
-  if (MODE == 3) return (uint64_t)nm * (uint64_t)(n_real + 2u * S.ideal_cap[i]);
-  uint32_t ideal_cap = 4u * S.head[i].z + 2u;
-  return (uint64_t)nm * (uint64_t)(n_real + 2u * ideal_cap);
-}
-
-// A thread's SCAN_ITEMS consecutive 32-bit inputs as two 16-byte loads (base is a multiple of 8 items = 32 bytes; the
-// arrays are allocations or 16-byte aligned offsets into one).  One 4-byte load per item made a wave touch every
-// eighth word of a 2 KB span eight times over.
-__device__ __forceinline__ void load8(const uint32_t *p, int64_t base, int64_t n, uint32_t v[SCAN_ITEMS]) {
-  if (base + SCAN_ITEMS <= n && ((uintptr_t)(p + base) & 15u) == 0) {
-    const uint4 a = *(const uint4 *)(p + base), b = *(const uint4 *)(p + base + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) v[k] = (base + k < n) ? p[base + k] : 0u;
-  }
-}
-__device__ __forceinline__ void store8(uint32_t *p, int64_t base, int64_t n, const uint32_t v[SCAN_ITEMS]) {
-  if (base + SCAN_ITEMS <= n && ((uintptr_t)(p + base) & 15u) == 0) {
-    *(uint4 *)(p + base) = make_uint4(v[0], v[1], v[2], v[3]); *(uint4 *)(p + base + 4) = make_uint4(v[4], v[5], v[6], v[7]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) if (base + k < n) p[base + k] = v[k];
-  }
-}
-__device__ __forceinline__ void store8(uint64_t *p, int64_t base, int64_t n, const uint64_t v[SCAN_ITEMS]) {
-  if (base + SCAN_ITEMS <= n && ((uintptr_t)(p + base) & 15u) == 0) {
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k += 2) *(ulonglong2 *)(p + base + k) = make_ulonglong2(v[k], v[k + 1]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) if (base + k < n) p[base + k] = v[k];
-  }
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(256) k_scan_tiles(ScanArgs S) {
-  __shared__ uint64_t sh[4];
-  int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-  uint64_t sum = 0;
-  if (MODE == 0 || MODE == 2) {
-    uint32_t v[SCAN_ITEMS];
-    load8(S.src32, base, S.n, v);
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) sum += v[k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) { int64_t i = base + k; if (i < S.n) sum += scan_value<MODE>(S, i); }
-  }
-  uint64_t tot;
-  block_excl_scan_256(sum, sh, tot);
-  if (threadIdx.x == 0) S.tile_sums[blockIdx.x] = tot;
-}
-
-// The tile sums of a scan, scanned in place by ONE block: eight consecutive sums per thread and round (2048 per round: a
-// handful of rounds for 10^4 tiles, the loads of a round in flight together) -- one sum per thread and round was a chain
-// of n_tiles / 256 load-scan-store rounds, 30 us for the rows' scan and 80 us for the fused three-value one.
-template <int C>
-__device__ __forceinline__ void scan_top_rounds(uint64_t *tile_sums, int64_t n_tiles, uint64_t *total_out, uint64_t *sh) {
-  uint64_t carry[C];
-#pragma unroll
-  for (int c = 0; c < C; c++) carry[c] = 0;
-  for (int64_t base = 0; base < n_tiles; base += 256 * 8) {
-    const int64_t i0 = base + (int64_t)threadIdx.x * 8;
-    uint64_t v[C][8];
-#pragma unroll
-    for (int c = 0; c < C; c++)
-#pragma unroll
-      for (int k = 0; k < 8; k++) v[c][k] = i0 + k < n_tiles ? tile_sums[(int64_t)c * n_tiles + i0 + k] : 0;
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-      uint64_t sum = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) sum += v[c][k];
-      uint64_t tot;
-      uint64_t ex = carry[c] + block_excl_scan_256(sum, sh, tot);
-#pragma unroll
-      for (int k = 0; k < 8; k++) { if (i0 + k < n_tiles) tile_sums[(int64_t)c * n_tiles + i0 + k] = ex; ex += v[c][k]; }
-      carry[c] += tot;
-    }
-  }
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int c = 0; c < C; c++) total_out[c] = carry[c];
-  }
-}
-__global__ void __launch_bounds__(256) k_scan_top(uint64_t *tile_sums, int64_t n_tiles, uint64_t *total_out) {
-  __shared__ uint64_t sh[4];
-  scan_top_rounds<1>(tile_sums, n_tiles, total_out, sh);
-}
-
-template <int MODE, typename OutT>
-__global__ void __launch_bounds__(256) k_scan_apply(ScanArgs S, OutT *out) {
-  __shared__ uint64_t sh[4];
-  int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-  uint64_t v[SCAN_ITEMS];
-  uint64_t sum = 0;
-  if (MODE == 0 || MODE == 2) {
-    uint32_t w[SCAN_ITEMS];
-    load8(S.src32, base, S.n, w);
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) { v[k] = w[k]; sum += v[k]; }
-  } else {
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) { int64_t i = base + k; v[k] = i < S.n ? scan_value<MODE>(S, i) : 0; sum += v[k]; }
-  }
-  uint64_t tot;
-  uint64_t ex = block_excl_scan_256(sum, sh, tot) + S.tile_sums[blockIdx.x];
-  OutT o[SCAN_ITEMS];
-#pragma unroll
-  for (int k = 0; k < SCAN_ITEMS; k++) { o[k] = (OutT)ex; ex += v[k]; }
-  store8(out, base, S.n, o);
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) out[S.n] = (OutT)ex;
-}
 
 // Fused scan of the count pass: per alignment (n_matches, n_matches * CIGAR slot
 // capacity, n_matches of simple alignments) -> match_off (u32), cig_base (u64),
@@ -1445,7 +1305,7 @@ __global__ void __launch_bounds__(256) k_scan3_tiles(ScanArgs S) {
 }
 __global__ void __launch_bounds__(256) k_scan3_top(uint64_t *tile_sums, int64_t n_tiles, uint64_t *total_out) {
   __shared__ uint64_t sh[4];
-  scan_top_rounds<3>(tile_sums, n_tiles, total_out, sh);
+  scan_top_rounds<3, 8>(tile_sums, n_tiles, total_out, sh);
 }
 __global__ void __launch_bounds__(256) k_scan3_apply(ScanArgs S, uint32_t *match_off, uint64_t *cig_base, uint32_t *fast_pre) {
   __shared__ uint64_t sh[4];
@@ -1468,38 +1328,8 @@ __global__ void __launch_bounds__(256) k_scan3_apply(ScanArgs S, uint32_t *match
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) { match_off[S.n] = (uint32_t)ex[0]; cig_base[S.n] = ex[1]; fast_pre[S.n] = (uint32_t)ex[2]; }
 }
 
-// Small inputs (at most SCAN_SMALL_TILES tiles): the whole scan by ONE block, tile after tile with a running carry -- one
-// launch instead of three (tile sums, their scan, apply): what a batch of a few thousand alignments spends its time on is
-// launches, not bytes.
-#define SCAN_SMALL_TILES 4
+// Small inputs (at most SCAN_SMALL_TILES tiles): one block, tile after tile with a running carry, as k_scan_small does.
 #define EXPAND_SMALL_N 1024   // the scanning block writes the work list too up to this many alignments (four chunks of its 256 threads)
-template <int MODE, typename OutT>
-__global__ void __launch_bounds__(256) k_scan_small(ScanArgs S, OutT *out, uint64_t *total_out) {
-  __shared__ uint64_t sh[4];
-  uint64_t carry = 0;
-  for (int64_t t0 = 0; t0 < S.n || t0 == 0; t0 += SCAN_TILE) {
-    const int64_t base = t0 + (int64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t v[SCAN_ITEMS];
-    uint64_t sum = 0;
-    if (MODE == 0 || MODE == 2) {
-      uint32_t w[SCAN_ITEMS];
-      load8(S.src32, base, S.n, w);
-#pragma unroll
-      for (int k = 0; k < SCAN_ITEMS; k++) { v[k] = w[k]; sum += v[k]; }
-    } else {
-#pragma unroll
-      for (int k = 0; k < SCAN_ITEMS; k++) { int64_t i = base + k; v[k] = i < S.n ? scan_value<MODE>(S, i) : 0; sum += v[k]; }
-    }
-    uint64_t tot;
-    uint64_t ex = block_excl_scan_256(sum, sh, tot) + carry;
-    OutT o[SCAN_ITEMS];
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; k++) { o[k] = (OutT)ex; ex += v[k]; }
-    store8(out, base, S.n, o);
-    carry += tot;
-  }
-  if (threadIdx.x == 0) { out[S.n] = (OutT)carry; total_out[0] = carry; }
-}
 // EXPAND: the emit work list too (k_expand's job), by the same block once its offsets are in place
 template <bool EXPAND>
 __global__ void __launch_bounds__(256) k_scan3_small(ScanArgs S, uint32_t *match_off, uint64_t *cig_base, uint32_t *fast_pre, uint64_t *total_out,
@@ -1709,9 +1539,7 @@ __global__ void __launch_bounds__(256) k_pair_emit(PairArgs P) {
     else kind = 4;
   }
   // the wave's record run
-  uint32_t inc = rows;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d); if (lane >= d) inc += up; }
+  const uint32_t inc = wave_scan(rows);
   const uint32_t total = __shfl(inc, 63);
   const uint64_t have = __ballot(rows != 0u);
   if (!have) return;   // the same for the whole wave
@@ -1865,8 +1693,7 @@ __global__ void __launch_bounds__(256) k_primary(PairArgs P, const uint32_t *__r
   }
   // (one pair of atomics per block: same-address atomics queue up in one L2 channel, see k_group_desc)
   __shared__ unsigned long long sh_pc[4][2];
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { uniq += __shfl_down(uniq, d, 64); dropped += __shfl_down(dropped, d, 64); }
+  uniq = wave_sum(uniq); dropped = wave_sum(dropped);
   if ((threadIdx.x & 63) == 0) { sh_pc[(threadIdx.x >> 6) & 3][0] = uniq; sh_pc[(threadIdx.x >> 6) & 3][1] = dropped; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -2032,11 +1859,7 @@ __global__ void __launch_bounds__(256) k_stats(StatsArgs T) {
       }
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    b_idx += __shfl_down(b_idx, d, 64); hits += __shfl_down(hits, d, 64);
-    exons += __shfl_down(exons, d, 64); ncig += __shfl_down(ncig, d, 64);
-  }
+  b_idx = wave_sum(b_idx); hits = wave_sum(hits); exons = wave_sum(exons); ncig = wave_sum(ncig);
   if ((threadIdx.x & 63) == 0) {
     atomicAdd((unsigned long long *)&T.out[1], b_idx); atomicAdd((unsigned long long *)&T.out[3], ncig);
     atomicAdd((unsigned long long *)&T.out[4], exons); atomicAdd((unsigned long long *)&T.out[5], hits);
@@ -2050,8 +1873,7 @@ __global__ void __launch_bounds__(256) k_sum_ncig(const uint2 *m_p, const uint32
     const uint32_t nm = n_matches[i], m0 = nm ? match_off[i] : 0u;
     for (uint32_t k = 0; k < nm; k++) acc += m_p[m0 + k].y & 0x7fffffffu;
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_down(acc, d, 64);
+  acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long *)out, acc);
 }
 
@@ -2187,38 +2009,6 @@ void launch_emit_dense(hipStream_t st, const ProjectArgs &A0, int64_t n_matches,
 void launch_emit_dense_fa(hipStream_t st, const ProjectArgs &A, const FaArgs &F, int64_t n_matches) {
   if (A.n_aln <= 0 || n_matches <= 0) return;
   hipLaunchKernelGGL((k_emit_dense<true, 0, true>), dim3(grid_for(n_matches, 256)), dim3(256), 0, st, A, (int64_t)0, n_matches, F);
-}
-
-int64_t scan_tiles_for(int64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
-
-void launch_scan(hipStream_t st, const ScanArgs &S, int mode, void *out, bool out64, uint64_t *total_out) {
-  int64_t tiles = scan_tiles_for(S.n);
-  if (tiles < 1) tiles = 1;
-  dim3 g((unsigned)tiles), b(256);
-  if (tiles <= SCAN_SMALL_TILES) {   // one launch
-    const dim3 one(1);
-    if (mode == 1) hipLaunchKernelGGL((k_scan_small<1, uint64_t>), one, b, 0, st, S, (uint64_t *)out, total_out);
-    else if (mode == 3) hipLaunchKernelGGL((k_scan_small<3, uint64_t>), one, b, 0, st, S, (uint64_t *)out, total_out);
-    else if (out64) hipLaunchKernelGGL((k_scan_small<2, uint64_t>), one, b, 0, st, S, (uint64_t *)out, total_out);
-    else hipLaunchKernelGGL((k_scan_small<2, uint32_t>), one, b, 0, st, S, (uint32_t *)out, total_out);
-    return;
-  }
-  if (mode == 0) hipLaunchKernelGGL((k_scan_tiles<0>), g, b, 0, st, S);
-  else if (mode == 1) hipLaunchKernelGGL((k_scan_tiles<1>), g, b, 0, st, S);
-  else if (mode == 3) hipLaunchKernelGGL((k_scan_tiles<3>), g, b, 0, st, S);
-  else hipLaunchKernelGGL((k_scan_tiles<2>), g, b, 0, st, S);
-  hipLaunchKernelGGL(k_scan_top, dim3(1), b, 0, st, S.tile_sums, tiles, total_out);
-  if (mode == 0) {
-    if (out64) hipLaunchKernelGGL((k_scan_apply<0, uint64_t>), g, b, 0, st, S, (uint64_t *)out);
-    else hipLaunchKernelGGL((k_scan_apply<0, uint32_t>), g, b, 0, st, S, (uint32_t *)out);
-  } else if (mode == 1) {
-    hipLaunchKernelGGL((k_scan_apply<1, uint64_t>), g, b, 0, st, S, (uint64_t *)out);
-  } else if (mode == 3) {
-    hipLaunchKernelGGL((k_scan_apply<3, uint64_t>), g, b, 0, st, S, (uint64_t *)out);
-  } else {
-    if (out64) hipLaunchKernelGGL((k_scan_apply<2, uint64_t>), g, b, 0, st, S, (uint64_t *)out);
-    else hipLaunchKernelGGL((k_scan_apply<2, uint32_t>), g, b, 0, st, S, (uint32_t *)out);
-  }
 }
 
 // expand (small batches): the work list as well; returns whether it was written (one launch did both), else the caller

@@ -43,7 +43,7 @@
 #include "collate_kernels.h"
 #include "ctx.h"
 #include "quant_kernels.h"
-#include "sam_kernels.h"
+#include "scan_kernels.h"
 
 using namespace br;
 
@@ -270,7 +270,7 @@ static int quant_finish(br_quant *c) {
     DropGuard dropper{c, {&pos}};
     RC(c->alloc(pos, (size_t)(N + 1) * 8)); RC(quant_tmp(c, N));
     launch_q_flag(st, c->nk.as<uint32_t>(), N, pos.as<uint64_t>());
-    launch_sam_scan(st, pos.as<uint64_t>(), N, c->tmp.as<uint64_t>());
+    launch_scan(st, pos.as<uint64_t>(), N, c->tmp.as<uint64_t>());
     uint32_t max_tid = 0;
     HIPCHK(hipMemcpyAsync(&M, pos.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&max_tid, small + QS_MAXTID, 4, hipMemcpyDeviceToHost, st));
@@ -310,7 +310,7 @@ static int quant_finish(br_quant *c) {
     RC(heads(nullptr, &n_coll));
   }
   RC(quant_tmp(c, m));
-  launch_sam_scan(st, head.as<uint64_t>(), m, c->tmp.as<uint64_t>());   // head -> class ids (exclusive), head[m] = C
+  launch_scan(st, head.as<uint64_t>(), m, c->tmp.as<uint64_t>());   // head -> class ids (exclusive), head[m] = C
   uint64_t C = 0;
   HIPCHK(hipMemcpyAsync(&C, head.as<uint64_t>() + m, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -328,7 +328,7 @@ static int quant_finish(br_quant *c) {
   launch_q_class_fill(st, key2[cur2].as<uint64_t>(), val2[cur2].as<uint32_t>(), gbeg.as<uint64_t>(), nk, (int64_t)C, c->c_first.as<uint64_t>(),
                       c->c_cnt.as<uint64_t>(), c->c_loff.as<uint64_t>());
   RC(quant_tmp(c, (int64_t)C));
-  launch_sam_scan(st, c->c_loff.as<uint64_t>(), (int64_t)C, c->tmp.as<uint64_t>());
+  launch_scan(st, c->c_loff.as<uint64_t>(), (int64_t)C, c->tmp.as<uint64_t>());
   uint64_t L = 0;
   HIPCHK(hipMemcpyAsync(&L, c->c_loff.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

@@ -23,6 +23,7 @@
 #include "../../include/bramble_amd.h"
 #include "collate_kernels.h"
 #include "quant_kernels.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -33,22 +34,6 @@ __device__ __forceinline__ uint64_t hash_end(uint64_t h, uint64_t k) {
   h = hash_step(h, k);
   h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;   // (murmur3 fmix64)
   return h;
-}
-__device__ __forceinline__ uint64_t wave_min(uint64_t v) {
-  for (int s = 32; s; s >>= 1) { const uint64_t o = __shfl_xor(v, s); v = o < v ? o : v; }
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int s = 32; s; s >>= 1) v += __shfl_xor(v, s);
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-  for (int s = 32; s; s >>= 1) v += __shfl_xor(v, s);
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_max(uint64_t v) {
-  for (int s = 32; s; s >>= 1) { const uint64_t o = __shfl_xor(v, s); v = o > v ? o : v; }
-  return v;
 }
 // the rows of name g of the add: false when they leave the add's rows
 __device__ __forceinline__ bool name_rows(const QAddArgs &A, int64_t g, uint64_t &r0, uint64_t &r1) {
@@ -109,7 +94,7 @@ __global__ void __launch_bounds__(256) k_q_names(QAddArgs A) {
     base = __shfl(base, 0);
     if (is_big) A.big[base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)g;
   }
-  for (int s = 32; s; s >>= 1) { const uint32_t o = __shfl_xor(top, s); top = o > top ? o : top; }
+  top = wave_max(top);
   if ((threadIdx.x & 63) == 0 && top) atomicMax(A.max_tid, top);
   if (__ballot(is_bad) && is_bad) *A.bad = 1;
 }
@@ -169,14 +154,10 @@ __device__ __forceinline__ void count_length(const QAddArgs &A, uint32_t *sh_his
   n_obs++;
   if (lds) atomicAdd(sh_hist + len, 1u); else atomicAdd(A.stage + len, 1ull);
 }
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-  for (int s = 32; s; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s);
-  return v;
-}
 // the block's counts leave it once: the side counters through LDS, then one integer atomicAdd per non-zero word of the block
 __device__ __forceinline__ void frag_flush(const QAddArgs &A, uint32_t *sh_hist, uint32_t *sh_side, bool lds, uint32_t n_obs, uint32_t n_nofrag,
                                            uint32_t n_oor, bool is_bad) {
-  n_obs = wave_sum32(n_obs); n_nofrag = wave_sum32(n_nofrag); n_oor = wave_sum32(n_oor);
+  n_obs = wave_sum(n_obs); n_nofrag = wave_sum(n_nofrag); n_oor = wave_sum(n_oor);
   if ((threadIdx.x & 63) == 0) {
     if (n_obs) atomicAdd(sh_side + 0, n_obs);
     if (n_nofrag) atomicAdd(sh_side + 1, n_nofrag);
@@ -361,16 +342,8 @@ __global__ void __launch_bounds__(256) k_q_compact(const uint32_t *nk, const uin
   if (i < n && nk[i]) { key[pos[i]] = hash[i] & mask; idx[pos[i]] = (uint32_t)i; }
 }
 __global__ void __launch_bounds__(256) k_q_bits_part(const uint64_t *key, int64_t n, uint64_t *part) {
-  __shared__ uint64_t sh[2][4];
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  uint64_t o = i < n ? key[i] : 0, a = i < n ? key[i] : ~0ull;
-  for (int s = 32; s; s >>= 1) { o |= __shfl_xor(o, s); a &= __shfl_xor(a, s); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = o; sh[1][threadIdx.x >> 6] = a; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; w++) { o |= sh[0][w]; a &= sh[1][w]; }
-    part[2 * blockIdx.x] = o; part[2 * blockIdx.x + 1] = a;
-  }
+  block_bits(i < n ? key[i] : 0, i < n ? key[i] : ~0ull, part + 2 * blockIdx.x);
 }
 
 __global__ void __launch_bounds__(256) k_q_heads(const uint32_t *lab, const uint64_t *noff, const uint32_t *nk, const uint64_t *key,

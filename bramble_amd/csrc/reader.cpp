@@ -143,8 +143,7 @@ static int split_impl(br_ctx *c, const uint8_t *data, uint64_t n_bytes, int32_t 
     if (pass > n_seg + 2) return BR_ERR_INVALID_ARG;   // (cannot happen: every pass settles at least the first wrong segment)
     launch_split_walk(st, S, redo);
   }
-  ScanArgs SC{}; SC.n = n_seg; SC.src32 = S.n_map; SC.tile_sums = c->tile_sums.as<uint64_t>();
-  launch_scan(st, SC, 2, c->sp_pre.p, true, (uint64_t *)(c->sp_small.as<uint8_t>() + 32));
+  launch_scan(st, S.n_map, n_seg, c->tile_sums.as<uint64_t>(), c->sp_pre.p, true, (uint64_t *)(c->sp_small.as<uint8_t>() + 32));
   uint64_t n_mapped = 0;
   HIPCHK(hipMemcpyAsync(&n_mapped, c->sp_small.as<uint8_t>() + 32, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

@@ -152,9 +152,7 @@ __global__ void __launch_bounds__(256) k_project_fa(ProjectArgs A, FaArgs F) {
         uint32_t pidxR = pidxL + (fc.wantL ? 1u : 0u);
         uint32_t my_bytes = (fc.wantL ? fc.qlenL + fc.tlenL : 0u) + (fc.wantR ? fc.qlenR + fc.tlenR : 0u);
         // exclusive prefix of my_bytes over the wave
-        uint32_t incl = my_bytes;
-#pragma unroll
-        for (int d = 1; d < G; d <<= 1) { uint32_t y = __shfl_up(incl, d, G); if (gl >= d) incl += y; }
+        const uint32_t incl = wave_scan<uint32_t, G>(my_bytes);
         uint32_t chunk_bytes = __shfl(incl, G - 1, G);
         uint64_t my_off = run_bytes + (incl - my_bytes);
         run_prob += (uint32_t)__popcll(bl) + (uint32_t)__popcll(br);
@@ -201,8 +199,7 @@ __global__ void __launch_bounds__(256) k_project_fa(ProjectArgs A, FaArgs F) {
           if (base < 64u) { m_alive |= m << base; m_wl |= bl << base; m_wr |= br << base; }
           total += (uint32_t)__popcll(m);
           uint32_t ops = alive ? (L.n_ops + R.n_ops) : 0u;
-#pragma unroll
-          for (int d = G / 2; d >= 1; d >>= 1) { uint32_t y = __shfl_xor(ops, d, G); ops = ops > y ? ops : y; }
+          ops = wave_max<uint32_t, G>(ops);
           max_ops = max_ops > ops ? max_ops : ops;
           continue;
         }
@@ -268,8 +265,7 @@ __global__ void __launch_bounds__(256) k_fa_fill(const uint4 *tx_ex, const uint8
       t += take;
       if (left) { if (i == 0) break; i--; } else i++;
     }
-#pragma unroll
-    for (int d = FG / 2; d >= 1; d >>= 1) has_n |= (uint32_t)__shfl_xor((int)has_n, d, FG);
+    has_n = wave_or<uint32_t, FG>(has_n);
     if (gl == 0 && has_n) F.probs[p].t_has_n = 1;
   }
 }

@@ -3,7 +3,7 @@
 //
 //   k_samfmt_measure<16>  16 lanes per record of at most SF_LONG_REC bytes: the exact line length (longer records are listed)
 //   k_samfmt_measure<64>  a whole wave per listed record
-//   (launch_sam_scan)     line lengths -> line offsets
+//   (launch_scan)         line lengths -> line offsets
 //   k_samfmt_emit16       16 lanes per short record: the line is composed in LDS at the alignment of its destination and
 //                         leaves with 16-byte streaming stores (a line longer than the slot is written in place)
 //   k_samfmt_emit64       a whole wave per listed record, written in place
@@ -16,6 +16,7 @@
 
 #include "bam_cg.h"
 #include "sam_format.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -153,18 +154,6 @@ __device__ int g_put(const GNum &g, uint8_t *o) {
 }
 
 // ---- lanes of a group ---------------------------------------------------------------------------------
-template <int G>
-__device__ __forceinline__ uint32_t grp_incl(uint32_t v, int lane) {
-#pragma unroll
-  for (int d = 1; d < G; d <<= 1) { const uint32_t t = __shfl_up(v, d, G); if (lane >= d) v += t; }
-  return v;
-}
-template <int G>
-__device__ __forceinline__ uint32_t grp_min(uint32_t v) {
-#pragma unroll
-  for (int d = G / 2; d > 0; d >>= 1) { const uint32_t t = __shfl_xor(v, d, G); v = t < v ? t : v; }
-  return v;
-}
 
 // the first NUL in [p, e), as an offset from p, or -1: G lanes test 4 bytes each per step
 template <int G>
@@ -178,7 +167,7 @@ __device__ int64_t find_nul(const uint8_t *p, const uint8_t *e, int lane) {
     } else {
       for (int k = 0; c + k < e; k++) if (c[k] == 0) { hit = 4u * lane + k; break; }
     }
-    hit = grp_min<G>(hit);
+    hit = wave_min<uint32_t, G>(hit);
     if (hit != 0xffffffffu) return (b - p) + hit;
   }
   return -1;
@@ -247,7 +236,7 @@ __device__ int64_t sam_line(const SamFmtArgs &A, const uint8_t *r, uint32_t rlen
     const uint32_t k = b + lane;
     uint32_t w = 0, len = 0;
     if (k < nops) { w = ld_u32(cig + 4ull * k); len = (uint32_t)ndig(w >> 4) + 1; }
-    const uint32_t inc = grp_incl<G>(len, lane);
+    const uint32_t inc = wave_scan<uint32_t, G>(len);
     if (W && k < nops) {
       const int64_t q = p + inc - len;
       put_digits(o + q, w >> 4, (int)len - 1);
@@ -337,7 +326,7 @@ __device__ int64_t sam_line(const SamFmtArgs &A, const uint8_t *r, uint32_t rlen
           if (sub == 'f') { g = g_decompose(ld_u32(a + 4ull * k)); len = 1 + (uint32_t)g_put(g, nullptr); }
           else { x = ival(sub, a + (uint64_t)esz * k); len = 1 + (uint32_t)put_int(nullptr, x); }
         }
-        const uint32_t inc = grp_incl<G>(len, lane);
+        const uint32_t inc = wave_scan<uint32_t, G>(len);
         if (W && k < cnt) {
           uint8_t *d = o + p + inc - len;
           d[0] = ',';

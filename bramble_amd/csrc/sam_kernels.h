@@ -57,8 +57,6 @@ constexpr uint64_t SAM_NL_TILE = 64u << 10;   // bytes per block of the line ind
 
 void launch_sam_nl_count(hipStream_t st, const uint8_t *text, uint64_t n, uint64_t *tile_cnt);
 void launch_sam_nl_write(hipStream_t st, const uint8_t *text, uint64_t n, const uint64_t *tile_pre, uint64_t *lend);
-// exclusive scan of a[0, n) in place; a[n] = the total.  tmp: (n / 1024 + 2) words
-void launch_sam_scan(hipStream_t st, uint64_t *a, int64_t n, uint64_t *tmp);
 void launch_sam_measure(hipStream_t st, const SamArgs &A);
 void launch_sam_emit(hipStream_t st, const SamArgs &A);
 

@@ -5,7 +5,7 @@
 // from the same text holds.  The rules below restate what those two produce; each is repeated at the code that applies it.
 //
 //   k_sam_nl_count / k_sam_nl_write   line index: 64 KiB per block, 16-byte loads, '\n' counted with wave ballots
-//   k_sam_scan_*                      exclusive scans (tile sums, one block over the tiles, apply)
+//   (launch_scan, scan_kernels.h)     exclusive scans
 //   k_sam_measure                     one wave per line: fields, tags, CIGAR -> block_size, mapped / unmapped, error code
 //   k_sam_emit                        one wave per mapped line: the BAM record, every write inside the measured size
 //
@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "sam_kernels.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -51,20 +52,6 @@ __global__ void __launch_bounds__(256) k_sam_nl_count(const uint8_t *t, uint64_t
   if (threadIdx.x == 0) tile_cnt[blockIdx.x] = (uint64_t)sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-// exclusive scan over the block (256 threads); *total = the block's sum
-__device__ __forceinline__ uint64_t block_excl256(uint64_t v, uint64_t *sh, uint64_t *total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint64_t incl = v;
-  for (int o = 1; o < 64; o <<= 1) { const uint64_t x = __shfl_up(incl, o); if (lane >= o) incl += x; }
-  if (lane == 63) sh[w] = incl;
-  __syncthreads();
-  uint64_t pre = 0, tot = 0;
-  for (int k = 0; k < 4; k++) { if (k < w) pre += sh[k]; tot += sh[k]; }
-  __syncthreads();
-  *total = tot;
-  return pre + incl - v;
-}
-
 __global__ void __launch_bounds__(256) k_sam_nl_write(const uint8_t *t, uint64_t n, const uint64_t *tile_pre, uint64_t *lend) {
   __shared__ uint64_t sh[4];
   const uint64_t base = (uint64_t)blockIdx.x * SAM_NL_TILE;
@@ -77,44 +64,10 @@ __global__ void __launch_bounds__(256) k_sam_nl_write(const uint8_t *t, uint64_t
 #pragma unroll
     for (int j = 0; j < 16; j++) m |= (uint32_t)(b[j] == '\n') << j;
     uint64_t tot;
-    uint64_t k = out + block_excl256((uint64_t)__popc(m), sh, &tot);
+    uint64_t k = out + block_excl_scan_256((uint64_t)__popc(m), sh, tot);
     while (m) { const int j = __ffs(m) - 1; m &= m - 1; lend[k++] = a + (uint64_t)j; }
     out += tot;
   }
-}
-
-// ---- scans ----------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_sam_scan_reduce(const uint64_t *a, int64_t n, uint64_t *tmp) {
-  __shared__ uint64_t sh[4];
-  const int64_t i0 = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4;
-  uint64_t s = 0;
-  for (int k = 0; k < 4; k++) if (i0 + k < n) s += a[i0 + k];
-  uint64_t tot;
-  (void)block_excl256(s, sh, &tot);
-  if (threadIdx.x == 0) tmp[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(256) k_sam_scan_top(uint64_t *tmp, int64_t n_tiles) {
-  __shared__ uint64_t sh[4];
-  uint64_t carry = 0;
-  for (int64_t b = 0; b < n_tiles; b += 256) {
-    const int64_t i = b + threadIdx.x;
-    const uint64_t v = i < n_tiles ? tmp[i] : 0;
-    uint64_t tot;
-    const uint64_t e = block_excl256(v, sh, &tot);
-    if (i < n_tiles) tmp[i] = carry + e;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) tmp[n_tiles] = carry;
-}
-__global__ void __launch_bounds__(256) k_sam_scan_apply(uint64_t *a, int64_t n, const uint64_t *tmp, int64_t n_tiles) {
-  __shared__ uint64_t sh[4];
-  const int64_t i0 = (int64_t)blockIdx.x * 1024 + threadIdx.x * 4;
-  uint64_t v[4], s = 0;
-  for (int k = 0; k < 4; k++) { v[k] = i0 + k < n ? a[i0 + k] : 0; s += v[k]; }
-  uint64_t tot;
-  uint64_t run = tmp[blockIdx.x] + block_excl256(s, sh, &tot);
-  for (int k = 0; k < 4; k++) if (i0 + k < n) { a[i0 + k] = run; run += v[k]; }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) a[n] = tmp[n_tiles];
 }
 
 // ---- one wave per line ----------------------------------------------------------------------------
@@ -140,8 +93,7 @@ __device__ uint32_t wfind(const uint8_t *t, uint64_t wb, uint64_t lo, uint64_t h
     m |= (uint32_t)(in && hit) << j;
   }
   const uint32_t c = (uint32_t)__popc(m);
-  uint32_t incl = c;
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t x = __shfl_up(incl, o); if (lane >= o) incl += x; }
+  const uint32_t incl = wave_scan(c);
   const uint32_t total = __shfl(incl, 63);
   __syncthreads();   // (the caller is done with the previous window's positions)
   uint32_t k = incl - c;
@@ -408,7 +360,7 @@ __device__ void cigar_walk(const SamArgs &A, uint64_t ls, uint32_t cs, uint32_t 
     n += T;
   }
   if (prev != ce - 1) lerr = SAM_E_CIGAR;   // digits after the last op (or no op at all)
-  for (int o = 32; o; o >>= 1) { q += __shfl_xor(q, o); r += __shfl_xor(r, o); lerr = max(lerr, (uint32_t)__shfl_xor(lerr, o)); }
+  q = wave_sum(q); r = wave_sum(r); lerr = wave_max(lerr);
   n_ops = n; qlen = q; rlen = r;
   if (lerr && !err) err = lerr;
 }
@@ -456,7 +408,7 @@ __global__ void __launch_bounds__(64) k_sam_measure(SamArgs A) {
     }
     if (nt >= 11 && lane == 0) aux += tag_bytes(A, ls + last + 1, le, nullptr, (uint32_t)i, lerr);   // the last tag ends the line
     if (nt == 10 && lane == 0) fs[11] = len + 1;
-    for (int o = 32; o; o >>= 1) { aux += __shfl_xor(aux, o); lerr = max(lerr, (uint32_t)__shfl_xor(lerr, o)); }
+    aux = wave_sum(aux); lerr = wave_max(lerr);
     __syncthreads();
     if (!err && nt < 10) err = SAM_E_FIELDS;   // fewer than 11 fields
     if (!err && lerr) err = lerr;
@@ -641,8 +593,7 @@ __global__ void __launch_bounds__(64) k_sam_emit(SamArgs A) {
           const uint32_t k = k0 + lane;
           uint64_t s = 0, e = 0, sz = 0;
           if (k < T) { s = ls + (k ? pos[k - 1] : last) + 1; e = ls + pos[k]; sz = tag_bytes(A, s, e, nullptr, (uint32_t)i, terr); }
-          uint64_t incl = sz;
-          for (int q = 1; q < 64; q <<= 1) { const uint64_t x = __shfl_up(incl, q); if (lane >= q) incl += x; }
+          const uint64_t incl = wave_scan(sz);
           if (k < T) (void)tag_bytes(A, s, e, aux + ao + incl - sz, (uint32_t)i, terr, SAM_ZMAX);
           const bool zl = k < T && (t[s + 3] == 'Z' || t[s + 3] == 'H') && e - s - 5 > SAM_ZMAX;
           wave_copy(zl, s + 5, aux + ao + incl - sz + 3, (uint32_t)(e - s - 5));
@@ -664,13 +615,6 @@ void launch_sam_nl_count(hipStream_t st, const uint8_t *text, uint64_t n, uint64
 void launch_sam_nl_write(hipStream_t st, const uint8_t *text, uint64_t n, const uint64_t *tile_pre, uint64_t *lend) {
   const uint64_t tiles = (n + SAM_NL_TILE - 1) / SAM_NL_TILE;
   if (tiles) hipLaunchKernelGGL(k_sam_nl_write, dim3((unsigned)tiles), dim3(256), 0, st, text, n, tile_pre, lend);
-}
-void launch_sam_scan(hipStream_t st, uint64_t *a, int64_t n, uint64_t *tmp) {
-  const int64_t tiles = (n + 1023) / 1024;
-  if (tiles == 0) { (void)hipMemsetAsync(a, 0, 8, st); return; }
-  hipLaunchKernelGGL(k_sam_scan_reduce, dim3((unsigned)tiles), dim3(256), 0, st, (const uint64_t *)a, n, tmp);
-  hipLaunchKernelGGL(k_sam_scan_top, dim3(1), dim3(256), 0, st, tmp, tiles);
-  hipLaunchKernelGGL(k_sam_scan_apply, dim3((unsigned)tiles), dim3(256), 0, st, a, n, (const uint64_t *)tmp, tiles);
 }
 static unsigned line_grid(int64_t n) { return (unsigned)(n < (1 << 20) ? (n > 0 ? n : 1) : (1 << 20)); }
 void launch_sam_measure(hipStream_t st, const SamArgs &A) {

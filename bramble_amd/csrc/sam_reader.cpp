@@ -228,9 +228,9 @@ static int sam_next(br_sam_reader *r, int slot, const uint8_t *text, uint64_t n,
   // line index
   const uint64_t tiles = (n + SAM_NL_TILE - 1) / SAM_NL_TILE;
   RC(r->tile.ensure((tiles + 1) * 8));
-  RC(r->tmp.ensure(((std::max<uint64_t>(tiles, n / 64) + 1) / 1024 + 4) * 8));
+  RC(r->tmp.ensure(scan_scratch_bytes((int64_t)std::max<uint64_t>(tiles, n / 64))));   // (the line scans below: as a rule no second allocation)
   launch_sam_nl_count(st, d_text, n, r->tile.as<uint64_t>());
-  launch_sam_scan(st, r->tile.as<uint64_t>(), (int64_t)tiles, r->tmp.as<uint64_t>());
+  launch_scan(st, r->tile.as<uint64_t>(), (int64_t)tiles, r->tmp.as<uint64_t>());
   uint64_t n_nl = 0;
   HIPCHK(hipMemcpyAsync(&n_nl, r->tile.as<uint64_t>() + tiles, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -243,7 +243,7 @@ static int sam_next(br_sam_reader *r, int slot, const uint8_t *text, uint64_t n,
   // measure
   const size_t nl1 = (size_t)n_lines + 1;
   RC(r->line.ensure(nl1 * sizeof(SamLine))); RC(r->mapped.ensure(nl1 * 8)); RC(r->bytes.ensure(nl1 * 8));
-  RC(r->tmp.ensure((nl1 / 1024 + 4) * 8));
+  RC(r->tmp.ensure(scan_scratch_bytes((int64_t)n_lines)));
   RC(r->fix.ensure((size_t)r->fix_cap * sizeof(SamFix)));
   unsigned long long *first_bad = (unsigned long long *)r->small.p;
   uint32_t *n_fix = (uint32_t *)(r->small.as<uint8_t>() + 8);
@@ -255,8 +255,8 @@ static int sam_next(br_sam_reader *r, int slot, const uint8_t *text, uint64_t n,
   A.h_slot = r->h_slot.as<int32_t>(); A.h_mask = r->h_mask; A.name_off = r->name_off.as<uint64_t>(); A.names = r->names.as<uint8_t>();
   A.n_ref = r->n_ref;
   launch_sam_measure(st, A);
-  launch_sam_scan(st, A.mapped, n_lines, r->tmp.as<uint64_t>());
-  launch_sam_scan(st, A.bytes, n_lines, r->tmp.as<uint64_t>());
+  launch_scan(st, A.mapped, n_lines, r->tmp.as<uint64_t>());
+  launch_scan(st, A.bytes, n_lines, r->tmp.as<uint64_t>());
   uint64_t h3[3] = {0, 0, 0};
   HIPCHK(hipMemcpyAsync(&h3[0], first_bad, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(&h3[1], A.mapped + n_lines, 8, hipMemcpyDeviceToHost, st));

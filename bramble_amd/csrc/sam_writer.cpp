@@ -7,7 +7,7 @@
 
 #include "ctx.h"
 #include "sam_format.h"
-#include "sam_kernels.h"
+#include "scan_kernels.h"
 
 extern "C" int br_ctx_set_sam_refs(br_ctx *c, const char *const *names, int32_t n) {
   if (!c || n < 0 || (n && !names)) return BR_ERR_INVALID_ARG;
@@ -36,7 +36,7 @@ int sam_format_impl(br_ctx *c, const br_device_bam *in, hipStream_t st, const ui
   if (n == 0) return pf.collect();
   if (n >= 0xffffffffll) return BR_ERR_CAPACITY;   // (the long list holds 32-bit row numbers)
   RC(c->sf_len.ensure(((size_t)n + 1) * 8)); RC(c->sf_long.ensure((size_t)n * 4)); RC(c->sf_small.ensure(16));
-  RC(c->sf_tmp.ensure(((size_t)n / 1024 + 4) * 8));
+  RC(c->sf_tmp.ensure(scan_scratch_bytes(n)));
   if (!c->sf_name_off.p) {   // no names set: every RNAME / RNEXT prints '*'
     RC(c->sf_name_off.ensure(8)); RC(c->sf_names.ensure(8));
     HIPCHK(hipMemsetAsync(c->sf_name_off.p, 0, 8, st));
@@ -53,7 +53,7 @@ int sam_format_impl(br_ctx *c, const br_device_bam *in, hipStream_t st, const ui
   launch_sam_fmt_measure(st, A, c->n_cu);
   RC(pf.end());
   RC(pf.begin(BR_K_SCAN));
-  launch_sam_scan(st, A.len, n, c->sf_tmp.as<uint64_t>());
+  launch_scan(st, A.len, n, c->sf_tmp.as<uint64_t>());
   RC(pf.end());
   HIPCHK(hipMemcpyAsync(&c->rb->sam_bad, first_bad, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(&c->rb->sam_bytes, A.len + n, 8, hipMemcpyDeviceToHost, st));

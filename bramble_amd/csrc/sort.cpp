@@ -29,7 +29,7 @@
 #include "../../include/bramble_amd.h"
 #include "accum.h"
 #include "collate_kernels.h"
-#include "sam_kernels.h"
+#include "scan_kernels.h"
 #include "sort_kernels.h"
 
 using namespace br;
@@ -155,7 +155,7 @@ static int sort_finish(br_sorter *c) {
   RC(c->radix_sort(key, idx, n, bits, c->tmp, &cur));
   RC(c->alloc(c->s_off, n1 * 8));
   launch_sort_lens(st, c->off.as<uint64_t>(), idx[cur].as<uint32_t>(), n, c->s_off.as<uint64_t>());
-  launch_sam_scan(st, c->s_off.as<uint64_t>(), n, c->tmp.as<uint64_t>());
+  launch_scan(st, c->s_off.as<uint64_t>(), n, c->tmp.as<uint64_t>());
   HIPCHK(hipStreamSynchronize(st));
   std::swap(c->key, key[cur]); std::swap(c->order, idx[cur]);
   return BR_OK;
@@ -232,7 +232,7 @@ static int sort_index_device(br_sorter *c, int32_t n_ref, const br_bgzf_span *bl
   RC(c->alloc(key2[0], n1 * 8)); RC(c->alloc(key2[1], n1 * 8)); RC(c->alloc(idx2[0], n1 * 4)); RC(c->alloc(idx2[1], n1 * 4));
   RC(c->alloc(um, n1 * 8)); RC(c->alloc(bh, (n1 + 1) * 8)); RC(c->alloc(ch, (n1 + 1) * 8)); RC(c->alloc(binc0, (n1 + 1) * 8));
   RC(c->alloc(refmax, nr1 * 4)); RC(c->alloc(ref, nr1 * sizeof(BaiRef))); RC(c->alloc(lin_off, nr1 * 8)); RC(c->alloc(ref_pos, nr1 * 8));
-  RC(c->alloc(c->tmp, std::max(scan_tmp_bytes(n), (size_t)(n_ref / 1024 + 8) * 8)));
+  RC(c->alloc(c->tmp, std::max(scan_tmp_bytes(n), scan_scratch_bytes(n_ref))));
   uint64_t *small = c->small.as<uint64_t>();
   HIPCHK(hipMemcpyAsync(blk.p, blocks, (size_t)n_blocks * 16, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(small, 0, 32, st));
@@ -251,13 +251,13 @@ static int sort_index_device(br_sorter *c, int32_t n_ref, const br_bgzf_span *bl
   if (sm[3] & (BAI_ERR_BLOCKS | BAI_ERR_REF)) return BR_ERR_INVALID_ARG;   // a record outside the block table, or a refID >= n_ref
   if (sm[3] & BAI_ERR_RANGE) return BR_ERR_UNSUPPORTED;                     // an end beyond 2^29: the binning scheme's reach
   RC(c->radix_sort(key2, idx2, n, sm, c->tmp, &A.cur));
-  launch_sam_scan(st, A.um, n, c->tmp.as<uint64_t>());
+  launch_scan(st, A.um, n, c->tmp.as<uint64_t>());
   launch_bai_heads(st, A);
-  launch_sam_scan(st, A.bh, n, c->tmp.as<uint64_t>());
-  launch_sam_scan(st, A.ch, n, c->tmp.as<uint64_t>());
+  launch_scan(st, A.bh, n, c->tmp.as<uint64_t>());
+  launch_scan(st, A.ch, n, c->tmp.as<uint64_t>());
   launch_bai_binc0(st, A);
   launch_bai_refs(st, A);
-  if (n_ref > 0) { launch_sam_scan(st, A.lin_off, n_ref, c->tmp.as<uint64_t>()); launch_sam_scan(st, A.ref_pos, n_ref, c->tmp.as<uint64_t>()); }
+  if (n_ref > 0) { launch_scan(st, A.lin_off, n_ref, c->tmp.as<uint64_t>()); launch_scan(st, A.ref_pos, n_ref, c->tmp.as<uint64_t>()); }
   uint64_t tot[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(&tot[0], A.lin_off + n_ref, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(&tot[1], A.ref_pos + n_ref, 8, hipMemcpyDeviceToHost, st));

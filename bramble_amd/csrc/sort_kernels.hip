@@ -10,6 +10,7 @@
 
 #include "collate_kernels.h"
 #include "sort_kernels.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -37,17 +38,6 @@ __device__ __forceinline__ int64_t lower_bound(const uint64_t *a, int64_t n, uin
 }
 __device__ __forceinline__ int32_t key_ref(uint64_t k) { return (int32_t)(uint32_t)(k >> 32); }
 __device__ __forceinline__ int32_t key_pos(uint64_t k) { return (int32_t)((uint32_t)k >> 1) - 1; }
-// OR / AND of a block's keys -> part[2 * block], as k_col_key leaves them for k_col_bits
-__device__ __forceinline__ void block_bits(uint64_t o, uint64_t a, uint64_t *part) {
-  __shared__ uint64_t sh[2][4];
-  for (int s = 32; s; s >>= 1) { o |= __shfl_xor(o, s); a &= __shfl_xor(a, s); }
-  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = o; sh[1][threadIdx.x >> 6] = a; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; w++) { o |= sh[0][w]; a &= sh[1][w]; }
-    part[2 * blockIdx.x] = o; part[2 * blockIdx.x + 1] = a;
-  }
-}
 }  // namespace
 
 // (*bad is set when the table descends somewhere: the rows would have negative sizes)
@@ -87,7 +77,7 @@ __global__ void __launch_bounds__(256) k_sort_key(const uint8_t *arena, const ui
     key[i] = k; idx[i] = (uint32_t)i; ends[i] = e;
     o = k; a = k;
   }
-  block_bits(o, a, part);
+  block_bits(o, a, part + 2 * blockIdx.x);
 }
 
 __global__ void __launch_bounds__(256) k_sort_lens(const uint64_t *off, const uint32_t *idx, int64_t n, uint64_t *len) {
@@ -186,7 +176,7 @@ __global__ void __launch_bounds__(256) k_bai_rec(BaiArgs A) {
     if (s_nc) atomicAdd((unsigned long long *)(A.small + 2), (unsigned long long)s_nc);
     if (s_err) atomicOr((unsigned long long *)(A.small + 3), (unsigned long long)s_err);
   }
-  block_bits(o, a, A.part);
+  block_bits(o, a, A.part + 2 * blockIdx.x);
 }
 
 // in (refID, bin) order: a bin starts at a new key, a chunk at a new bin or where the record is not the file successor of the one

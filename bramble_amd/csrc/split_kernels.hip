@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -126,7 +127,7 @@ __global__ void __launch_bounds__(256) k_split_totals(SplitArgs S) {
   __shared__ unsigned long long sh_unm[4];
   unsigned long long unm = 0;
   for (int64_t s = threadIdx.x; s < S.n_seg; s += 256) { unm += S.n_unm[s]; if (S.entry[s] != ~0ull && S.ended[s] == 2u) atomicOr(S.flags, 1u); }
-  for (int o = 32; o; o >>= 1) unm += __shfl_xor(unm, o);
+  unm = wave_sum(unm);
   if ((threadIdx.x & 63) == 0) sh_unm[threadIdx.x >> 6] = unm;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -149,7 +150,7 @@ __global__ void __launch_bounds__(256) k_last_group(const uint8_t *data, const u
     for (uint32_t k = 0; same && k < la; k++) same = a[32 + k] == b[32 + k];
     if (!same) best = (unsigned long long)i;
   }
-  for (int o = 32; o; o >>= 1) { const unsigned long long t = __shfl_xor(best, o); best = t > best ? t : best; }
+  best = wave_max(best);
   if ((threadIdx.x & 63) == 0 && best) atomicMax(out, best);
 }
 
@@ -171,7 +172,7 @@ __global__ void __launch_bounds__(256) k_unmapped_before(SplitArgs S, uint64_t l
       }
     }
   }
-  for (int o = 32; o; o >>= 1) n += __shfl_xor(n, o);
+  n = wave_sum(n);
   if ((threadIdx.x & 63) == 0 && n) atomicAdd(out, n);
 }
 
@@ -247,7 +248,7 @@ __global__ void __launch_bounds__(256) k_unmapped_in(SplitArgs S, unsigned long 
       }
     }
   }
-  for (int o = 32; o; o >>= 1) n += __shfl_xor(n, o);
+  n = wave_sum(n);
   if ((threadIdx.x & 63) == 0 && n) atomicAdd(&cut[4], n);
 }
 void launch_first_record(hipStream_t st, const SplitArgs &S, uint64_t limit, unsigned long long *out) { hipLaunchKernelGGL(k_first_record, dim3(1), dim3(64), 0, st, S, limit, out); }

@@ -1,0 +1,160 @@
+// Wave and block primitives every kernel unit shares (device code only; include after hip_runtime.h).
+//
+// The lanes of a wave are taken in groups of W consecutive lanes (W = 64: the wave; 8, 16, 32: the sub-wave groups of the
+// kernels that give a group of lanes one alignment or one record).  A lane's place in its group is threadIdx.x & (W - 1):
+// every kernel here has one-dimensional blocks whose size is a multiple of 64.
+//
+//   wave_scan<T, W>(v)                                inclusive prefix sum over the group (lane k: v of lanes 0 .. k)
+//   wave_sum / wave_max / wave_min / wave_or / wave_and   butterfly reductions: every lane of the group gets the result
+//   block_excl_scan_256(v, sh, total)                 exclusive prefix sum over a block of 256 threads
+//   block_bits(o, a, out)                             OR of o and AND of a over a block of 256 threads (the radix sort's digits)
+//   load8 / store8                                    a thread's eight consecutive scan items as 16-byte accesses
+//   scan_top_rounds<C, ITEMS>(...)                    a scan's tile sums scanned in place by one block
+#pragma once
+#include <stdint.h>
+
+namespace br {
+
+template <typename T, int W = 64>
+__device__ __forceinline__ T wave_scan(T v) {
+  const int gl = (int)(threadIdx.x & (W - 1));
+#pragma unroll
+  for (int d = 1; d < W; d <<= 1) { const T y = __shfl_up(v, d, W); if (gl >= d) v += y; }
+  return v;
+}
+
+// The xor order W/2, ..., 1 is part of the contract: the quantification's EM sums doubles with wave_sum and its results are
+// compared bit by bit.
+template <typename T, int W = 64>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int d = W / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, W);
+  return v;
+}
+template <typename T, int W = 64>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+  for (int d = W / 2; d >= 1; d >>= 1) { const T y = __shfl_xor(v, d, W); v = y > v ? y : v; }
+  return v;
+}
+template <typename T, int W = 64>
+__device__ __forceinline__ T wave_min(T v) {
+#pragma unroll
+  for (int d = W / 2; d >= 1; d >>= 1) { const T y = __shfl_xor(v, d, W); v = y < v ? y : v; }
+  return v;
+}
+template <typename T, int W = 64>
+__device__ __forceinline__ T wave_or(T v) {
+#pragma unroll
+  for (int d = W / 2; d >= 1; d >>= 1) v |= __shfl_xor(v, d, W);
+  return v;
+}
+template <typename T, int W = 64>
+__device__ __forceinline__ T wave_and(T v) {
+#pragma unroll
+  for (int d = W / 2; d >= 1; d >>= 1) v &= __shfl_xor(v, d, W);
+  return v;
+}
+
+// Exclusive prefix sum of v over the block's 256 threads; total = the block's sum, in every thread.  Wave scans by shuffles,
+// then across the 4 waves through sh[4].  Two barriers: sh is free again when it returns.
+template <typename T>
+__device__ __forceinline__ T block_excl_scan_256(T v, T *sh, T &total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const T x = wave_scan(v);
+  if (lane == 63) sh[w] = x;
+  __syncthreads();
+  T wbase = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) { if (i < w) wbase += sh[i]; tot += sh[i]; }
+  __syncthreads();
+  total = tot;
+  return wbase + x - v;
+}
+
+// OR of o and AND of a over the block's 256 threads -> out[0], out[1] (thread 0 stores them).  The radix sorts skip the digits
+// in which OR and AND agree.
+__device__ __forceinline__ void block_bits(uint64_t o, uint64_t a, uint64_t *out) {
+  __shared__ uint64_t sh[2][4];
+  o = wave_or(o); a = wave_and(a);
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = o; sh[1][threadIdx.x >> 6] = a; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; w++) { o |= sh[0][w]; a &= sh[1][w]; }
+    out[0] = o; out[1] = a;
+  }
+}
+
+// A thread's eight consecutive items p[base .. base + 8) as 16-byte accesses (base is a multiple of 8 items).  One 4-byte
+// load per item made a wave touch every eighth word of a 2 KB span eight times over.  Items at or past n read as 0 and are
+// not written.  The arrays are allocations or offsets into one, and an offset need not be a multiple of 16 bytes (the
+// collation's byte counts sit behind its own n + 1 words): those, and the tile that holds n, go item by item.
+template <typename T>
+__device__ __forceinline__ void load8(const T *p, int64_t base, int64_t n, T v[8]) {
+  constexpr int V = 16 / sizeof(T);   // items per 16 bytes
+  typedef T vec_t __attribute__((ext_vector_type(V)));
+  if (base + 8 <= n && ((uintptr_t)(p + base) & 15u) == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; k += V) {
+      const vec_t a = *(const vec_t *)(p + base + k);
+#pragma unroll
+      for (int j = 0; j < V; j++) v[k + j] = a[j];
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; k++) v[k] = (base + k < n) ? p[base + k] : (T)0;
+  }
+}
+template <typename T>
+__device__ __forceinline__ void store8(T *p, int64_t base, int64_t n, const T v[8]) {
+  constexpr int V = 16 / sizeof(T);
+  typedef T vec_t __attribute__((ext_vector_type(V)));
+  if (base + 8 <= n && ((uintptr_t)(p + base) & 15u) == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; k += V) {
+      vec_t a;
+#pragma unroll
+      for (int j = 0; j < V; j++) a[j] = v[k + j];
+      *(vec_t *)(p + base + k) = a;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; k++) if (base + k < n) p[base + k] = v[k];
+  }
+}
+
+// The tile sums of a scan, scanned in place by ONE block of 256 threads: C arrays of n_tiles sums, one behind the other,
+// ITEMS consecutive sums per thread and round, the loads of a round in flight together -- one sum per thread and round was
+// a chain of n_tiles / 256 load-scan-store rounds, 30 us for the rows' scan and 80 us for the fused three-value one.
+// total_out[c] = the sum of array c (NULL: not wanted).
+template <int C, int ITEMS>
+__device__ __forceinline__ void scan_top_rounds(uint64_t *tile_sums, int64_t n_tiles, uint64_t *total_out, uint64_t *sh) {
+  uint64_t carry[C];
+#pragma unroll
+  for (int c = 0; c < C; c++) carry[c] = 0;
+  for (int64_t base = 0; base < n_tiles; base += 256 * ITEMS) {
+    const int64_t i0 = base + (int64_t)threadIdx.x * ITEMS;
+    uint64_t v[C][ITEMS];
+#pragma unroll
+    for (int c = 0; c < C; c++)
+#pragma unroll
+      for (int k = 0; k < ITEMS; k++) v[c][k] = i0 + k < n_tiles ? tile_sums[(int64_t)c * n_tiles + i0 + k] : 0;
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+      uint64_t sum = 0;
+#pragma unroll
+      for (int k = 0; k < ITEMS; k++) sum += v[c][k];
+      uint64_t tot;
+      uint64_t ex = carry[c] + block_excl_scan_256(sum, sh, tot);
+#pragma unroll
+      for (int k = 0; k < ITEMS; k++) { if (i0 + k < n_tiles) tile_sums[(int64_t)c * n_tiles + i0 + k] = ex; ex += v[c][k]; }
+      carry[c] += tot;
+    }
+  }
+  if (total_out && threadIdx.x == 0) {
+#pragma unroll
+    for (int c = 0; c < C; c++) total_out[c] = carry[c];
+  }
+}
+
+}  // namespace br

@@ -1,6 +1,7 @@
 """--collate on the GPU: br_collator's order and bundles against the tests' restatement of the collation (test_collate_cpu.py),
 with colliding hashes on purpose, the capacity cap, the projection of its bundles against the oracle, and the command line
 with --collate against the run without it on the collated input (device reader, host reader, BAM on stdin, SAM)."""
+import functools
 import os
 import random
 import struct
@@ -12,7 +13,7 @@ import pytest
 from bramble_amd import lib, synth
 from oracle import oracle_binding as ob
 from tests import bamio
-from tests.test_collate_cpu import collate_order, coordinate_sorted, mapped_records, read_name
+from tests.test_collate_cpu import _rec, collate_order, coordinate_sorted, mapped_records, read_name
 from tests.test_gpu_bam_bundle import framed_stream
 from tests.test_sam_cpu import encode_sam
 
@@ -106,6 +107,35 @@ def test_collator_hash_collisions_change_nothing(bits):
     c.finish()
     assert list(c.order()) == collate_order(recs)
     c.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _named_records(n):
+    """n minimal mapped records ([block_size][record]) whose names repeat so that the groups have 1 to 3 members, in an order
+    shuffled by a fixed seed"""
+    recs, g = [], 0
+    while len(recs) < n:
+        for _ in range(min(1 + g % 3, n - len(recs))):
+            recs.append(_rec(b"q%d" % g, 100 + 37 * len(recs) % 90001, ref=len(recs) % 3, flag=16 * (len(recs) % 2)))
+        g += 1
+    random.Random(5).shuffle(recs)
+    return tuple(recs)
+
+
+# The prefix sums of the collation run over n + 1 items and, in the radix sort, over 256 counts a tile of records.  These
+# sizes put n + 1 on either side of a scan tile (2048) and of the four tiles one launch takes (8192); at 70 000 the radix
+# counts (256 x 35 tiles = 8960) take the three-launch scan too.
+@pytest.mark.parametrize("n", [1, 2047, 2048, 2049, 8191, 8192, 8193, 70000])
+def test_collator_sizes_around_the_scan_tiles(n):
+    recs = list(_named_records(n))
+    exp = collate_order(recs)
+    groups = len(set(read_name(r) for r in recs))
+    stream = _cat(recs)
+    for bits in (64, 4):
+        c = _collate(stream, hash_bits=bits)
+        assert tuple(c.finish()) == (n, groups)
+        assert list(c.order()) == exp, bits
+        c.close()
 
 
 def test_collator_bundles_hold_whole_groups():

@@ -65,6 +65,35 @@ def test_packed_host_rows_unpack_to_the_oracle_rows(mode, flags, kw):
     idx.close()
 
 
+def _first(b, n):
+    """the first n alignments of a flat batch as a batch of its own"""
+    out = {k: (v[:n] if isinstance(v, np.ndarray) and v.shape == (b["n_aln"],) else v) for k, v in b.items()}
+    out["n_aln"] = n
+    for off, data in (("cigar_off", "cigar"), ("name_off", "names")):
+        out[off] = b[off][:n + 1].copy()
+        out[data] = b[data][:int(b[off][n])].copy()
+    return out
+
+
+# four scan tiles of 2048 alignments are one launch, more are three: the batch on either side of that cut
+@pytest.mark.parametrize("n", [8191, 8192, 8193])
+def test_packed_rows_at_the_one_launch_cut_of_the_scans(n):
+    ann = synth.Annotation("G", n_genes=1200, n_refs=3)
+    flags = {"fr": 1}
+    b = _first(ann.reads(8000, "se"), n)
+    assert b["n_aln"] == n and len(b["ref_id"]) == n
+    idx = lib.Index(ann.as_dict(), device=0)
+    ctx = lib.Context(idx)
+    ctx.set_param("host_detail", 1)
+    p = ctx.project_batch_packed(lib.make_config(**flags), b)
+    assert p["n_aln"] == n and p["n_rows"] > 1000
+    w = lib.unpack_host_rows(p, b["l_qseq"], long_reads=False)
+    w["group"] = _group_of_rows(b, w["input_index"])
+    assert_rows_equal(w, _oracle(ann, flags, b))
+    ctx.close()
+    idx.close()
+
+
 def test_device_input_contract_equals_host_prepare():
     """Read-name groups and the mate index of process_pairs, computed on the device for a staged flat batch
     (k_soa_fields / k_group_off / k_mates*), against br_batch_prepare on the host -- with multi-mapping reads (several

@@ -13,7 +13,7 @@ import pytest
 from bramble_amd import lib, synth
 from oracle import oracle_binding as ob
 from tests import bamio
-from tests.test_gpu_collate import _cat, _coordinate_stream, _files, _inputs, _report, _run
+from tests.test_gpu_collate import _cat, _coordinate_stream, _files, _inputs, _named_records, _report, _run
 from tests.test_sam_cpu import records_to_sam_py
 from tests.test_sort_cpu import bai_bytes, bai_query, coordinate_order, ref_pos_end, sort_key
 
@@ -227,6 +227,31 @@ def test_index_at_the_abi(which):
         got = s.index(n_ref, blocks, eof)
         assert got == want, (which, block)
         _check_queries(got, recs, vo, n_ref, seed=block)
+    s.close()
+
+
+# more records than one launch of the prefix sums takes (four tiles of 2048): the sorted stream's offset table, the index's
+# bin and chunk heads and the radix counts (at 70 000) go through the three-launch scan.  "by_ref": fed grouped by reference,
+# so every block of 256 records is uniform in the key's reference digit (and in most of its bin digits) while the blocks
+# differ: the digits the radix sorts skip must come from the OR / AND over ALL blocks
+@pytest.mark.parametrize("feed", ["shuffled", "by_ref"])
+@pytest.mark.parametrize("n", [8193, 70000])
+def test_sorter_sizes_beyond_one_scan_launch(n, feed):
+    recs = [r[4:] for r in _named_records(n)]
+    if feed == "by_ref":
+        recs.sort(key=lambda r: -struct.unpack_from("<i", r, 0)[0])   # (stable: positions stay shuffled; references descend)
+        assert len(set(struct.unpack_from("<i", r, 0)[0] for r in recs[-256:])) == 1
+    exp = coordinate_order(recs)
+    assert exp != list(range(n))
+    s = _sorter(bamio.frame(recs))
+    assert s.finish() == n
+    assert list(s.order()) == exp
+    want = [recs[i] for i in exp]
+    sorted_stream = _drain(s, 1 << 30)
+    assert np.array_equal(sorted_stream, bamio.frame(want))
+    blocks, eof = _blocks_of(bamio.bgzf_compress(sorted_stream.tobytes(), block=0xff00, level=1), 77)
+    vo = _voffsets(want, blocks, eof)
+    assert s.index(3, blocks, eof) == bai_bytes(want, vo, 3)
     s.close()
 
 
