@@ -175,7 +175,9 @@ def test_held_bytes_follow_the_device_memory_account():
 
 
 def test_a_depth_carried_through_more_tiles_than_one_scan_block_takes():
-    """4 300 000 bases are more than 1 024 tiles of 4 096: the scan of the tile sums is itself tiled"""
+    """4 300 000 bases are 1 050 tiles of 4 096: a depth carried from tile to tile of k_cov_tile_apply, through more tiles than one
+    block has threads.  The 1 050 tile sums are one tile of launch_scan, scanned by one block in one launch; the tiled top
+    level of the scan (more than 4 194 304 items) is test_gpu_scan_unit.py::test_launch_scan_from_u32's."""
     lens = np.asarray([4300000, 7], dtype=np.int64)
     rows = rows_of([(0, 0, 0, "4300000M"), (0, 4299000, 0, "1000M"), (0, 1, 0, "4194303M"), (1, 0, 0, "7M")])
     want = coverage_of(rows, lens)
