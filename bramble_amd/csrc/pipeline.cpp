@@ -932,7 +932,12 @@ extern "C" int br_ctx_collect_counters(br_ctx *c, const br_device_batch *b, void
     c->events_used = 0;
     br_device_rows tmp;
     memset(&tmp, 0, sizeof(tmp));
+    // (that projection overwrites the row tables and may move the CIGAR arena: what br_quant_add_last / br_coverage_add_last
+    // read is its table from here on, not the direct-rows call's description of buffers that no longer hold it)
+    c->last_rows = br_device_rows{}; c->last_group_off = nullptr; c->last_n_groups = 0; c->last_stream = st;
     RC(run_match_table(c, dc, b, st, &tmp, pf, false));
+    tmp.total_processed = (uint64_t)b->n_aln;
+    if (tmp.row_off) { c->last_rows = tmp; c->last_group_off = b->group_off; c->last_n_groups = b->n_groups; }
   }
   DevBuf stats; RC(stats.ensure(8 * 8));   // (freed on the way out)
   HIPCHK(hipMemsetAsync(stats.p, 0, 8 * 8, st));

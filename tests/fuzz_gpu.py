@@ -3,7 +3,10 @@
 `python tests/fuzz_gpu.py [rounds] [seed]`).  Each round draws an annotation size, a read mode, a flag combination
 (incl. the --max-* / --similarity-threshold overrides) and random synth perturbation rates -- one round in four takes its
 annotation and reads from tests/adversarial.py instead (the full CIGAR alphabet, see there) -- then compares
-  * rows of br_project_batch with the oracle's, and
+  * rows of br_project_batch with the oracle's,
+  * what quant, the fragment-length histogram and coverage make of the device row table that call left (br_quant_add_last,
+    br_coverage_add_last) with the tests' yardsticks over the oracle's rows (tests/route_cases.py; classes, histogram, effective
+    lengths and coverage, no EM), and
   * the BAM stream of br_project_bam_bundle (records in / records out) with the oracle's write_to_bam stream.
 Prints the first diverging configuration and exits non-zero."""
 import os
@@ -15,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bramble_amd import lib, synth  # noqa: E402
 from oracle import oracle_binding as ob  # noqa: E402
 from tests import adversarial as adv  # noqa: E402
+from tests import route_cases as rc  # noqa: E402
 from tests.parity import assert_rows_equal  # noqa: E402
 
 
@@ -95,6 +99,10 @@ def run(rounds, seed, verbose=True, read_counts=(500, 3000, 9000), gene_counts=(
             prod = ctx.project_batch(cfg, b)
             orc, _, _ = ob.run(oi, ob.make_flags(**flags), b, want_matches=False)
             assert_rows_equal(prod, orc)
+            # the table that call left in HBM through its device consumers, whatever route wrote it (nothing is drawn from rng)
+            lens = rc.oracle_lens(oi)
+            want = rc.yardsticks(*rc.yardstick_rows(orc, rc.group_starts(b)), lens)
+            rc.check_consumers(ctx, want, lens, len(lens), tag="round %d" % it)
             got, counters = ctx.project_bam_bundle(cfg, stream, roff, rlen, np.arange(n_refs, dtype=np.int32))
             # the records are the input here (their SEQ carries injected N codes the flat table lacks): oracle from records
             orc2, _, _, _ = ob.run_bam(oi, ob.make_flags(**flags), stream, roff, rlen, np.arange(n_refs, dtype=np.int32))

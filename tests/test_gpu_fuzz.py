@@ -1,5 +1,6 @@
 """A short run of the differential fuzz driver (tests/fuzz_gpu.py) so that it stays exercised: random annotation sizes,
-read modes, preset flags and overrides, reads of the synthetic generator and of tests/adversarial.py; rows and the records-in / records-out stream against the oracle."""
+read modes, preset flags and overrides, reads of the synthetic generator and of tests/adversarial.py; rows and the records-in / records-out stream against the oracle, and
+every round's device row table through quant, the fragment-length histogram and coverage against the yardsticks (tests/route_cases.py)."""
 import pytest
 
 from tests import fuzz_gpu

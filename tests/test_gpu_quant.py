@@ -216,6 +216,11 @@ def _spread(cl, n_tx, lens, length_norm, iters):
 
 def _assert_em(got, cl, n_tx, lens, length_norm, iters, tag):
     ref, s = _spread(cl, n_tx, lens, length_norm, iters)
+    _assert_em_to(got, ref, s, iters, tag)
+
+
+def _assert_em_to(got, ref, s, iters, tag):
+    """the rule itself, for callers that hold one _spread of an input to several device runs"""
     print("%s: spread s of the restatement over three class orders after %d iterations = %.3e" % (tag, iters, s))
     assert 0 < s < 1e-9
     for key in ("theta", "tpm"):

@@ -133,13 +133,9 @@ def wide_rows(mode, guide_order=False, collated=False):
     tb = oracle_tables(mode, recs, guide_order=guide_order)
     wide, _, _, _ = ob.run_bam(ob.OracleIndex(tb["annd"]), ob.make_flags(**tb["flags"]), tb["stream"], tb["roff"], tb["rlen"],
                                np.arange(len(tb["annd"]["refnames"]), dtype=np.int32))
-    assert np.array_equal(np.asarray(wide["tid"], dtype=np.uint32), tb["tids"])
-    ncig = np.diff(wide["cigar_off"]).astype(np.uint32)
-    meta = (ncig | np.where(wide["strand"] == ord("-"), ROW_MINUS, 0) | np.where(wide["is_paired"] != 0, ROW_PAIRED, 0)
-            | np.where(wide["same_transcript"] != 0, ROW_SAME_TX, 0) | np.where(wide["is_first"] != 0, ROW_FIRST, 0)
-            | np.where(wide["primary"] != 0, ROW_PRIMARY, 0)).astype(np.uint32)
-    rows = {"tid": tb["tids"], "pos": np.asarray(wide["pos"], dtype=np.uint32), "meta": meta,
-            "cigar_off": np.asarray(wide["cigar_off"], dtype=np.uint64), "cigar": np.asarray(wide["cigar"], dtype=np.uint32)}
+    from tests.route_cases import yardstick_rows
+    rows, row_off, group_off = yardstick_rows(wide, tb["group_off"])
+    assert np.array_equal(rows["tid"], tb["tids"]) and np.array_equal(row_off, tb["row_off"]) and np.array_equal(group_off, tb["group_off"])
     return tb, rows
 
 
