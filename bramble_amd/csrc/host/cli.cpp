@@ -7,14 +7,12 @@
 //   uploader      : br_bam_bundle_stage (host bundles: records to one of three device slots, own copy stream)
 //   runner        : br_project_bam_staged_nowait / br_project_bam_resident (everything between the raw records on the device)
 //   writer thread : BGZF deflate (threaded) -> output file; device-made BGZF blocks or SAM lines (-O sam) go out as they are
-//   --sort        : the runner leaves every bundle's records in HBM (BR_OUT_RESIDENT) and adds them to a br_sorter; after the last
-//                   bundle the sorted pieces take the same way out (br_device_bam_download -> writer); --write-index: the writer
-//                   notes the blocks it writes and br_sorter_index builds <out>.bai from them
-//   --quant       : the runner hands every bundle's rows, where the projection left them in HBM, to a br_quant (br_quant_add_last);
-//                   after the last bundle: classes, EM, one download, and the two text files formatted here
-//                   (--quant-eff-length: the adds count the fragment lengths as well, "eff_len"; --quant-fld: the histogram's file)
-//   --coverage    : the runner hands every bundle's rows to a br_coverage as well (br_coverage_add_last); after the last bundle: depth,
-//                   summary and runs on the device, and the bedGraph / the table formatted here from pages of br_coverage_runs
+//   consumers     : what else takes something from every projected bundle -- --sort, --quant, --coverage (cli_output.h: one consumer
+//                   per feature).  The runner hands each bundle to every consumer right after its projection call; after the last
+//                   bundle each finishes on the device, writes its files under temporary names and prints its report line.  One of
+//                   them may keep the records (--sort): then the projection leaves them in HBM (BR_OUT_RESIDENT), nothing of a
+//                   bundle goes to the writer, and after the last bundle the consumer's pieces take the same way out
+//                   (br_device_bam_download -> writer); the writer notes the blocks it writes for the consumer's index
 #include <ctype.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,6 +25,7 @@
 #include <unordered_map>
 
 #include "cli_input.h"
+#include "cli_output.h"
 
 #define BRAMBLE_REF_VERSION "0.1.6"  // src/bramble.cpp:35
 
@@ -312,27 +311,21 @@ struct OutFile {
 struct Run {
   const Options &o; Input &in; Outbox &out; BgzfWriter &wr;
   const std::vector<int32_t> &ref_map; std::vector<std::unique_ptr<Worker>> &workers;
-  br_sorter *sorter = nullptr;   // --sort: the runner's records go here; drain_sorted() writes them once the input is through
-  br_quant *quant = nullptr;     // --quant: deliver() adds every bundle's rows; quantify() runs once the input is through
-  int64_t q_names = 0, q_classes = 0; int32_t q_iters = 0;
-  double t_q_add = 0, t_q_finish = 0, t_q_em = 0;
-  std::vector<double> q_eff; std::vector<uint64_t> q_fld; uint64_t q_fld_obs = 0, q_fld_nofrag = 0, q_fld_oor = 0;   // --quant-eff-length
-  std::vector<double> q_theta, q_tpm; std::vector<uint64_t> q_unique, q_ambig, q_label_off, q_counts; std::vector<uint32_t> q_labels;
-  br_coverage *coverage = nullptr;   // --coverage: deliver() adds every bundle's rows; cover() runs once the input is through
-  int64_t cov_runs = 0; double t_cov_add = 0, t_cov_finish = 0;
-  std::vector<uint64_t> cov_records, cov_aligned, cov_covered; std::vector<uint32_t> cov_max;
-  bool track_blocks = false;     // --write-index: the writer notes where every BGZF block of the record section starts
+  std::vector<std::unique_ptr<Consumer>> &consumers;
+  std::vector<Consumer *> order;  // the consumers as add and finish reach them: one that keeps the records comes last
+  bool keep = false;              // one of them keeps the records: nothing of a bundle goes to the writer
+  bool track_blocks = false;      // --write-index: the writer notes where every BGZF block of the record section starts
   std::vector<br_bgzf_span> spans;
-  uint64_t stream_pos = 0;       // uncompressed record bytes written so far
-  uint64_t sorted_chunks = 0;    // chunks drain_sorted() handed to the writer
-  int64_t sorted_records = 0;
-  double t_sort_add = 0, t_sort_finish = 0;
+  uint64_t stream_pos = 0;        // uncompressed record bytes written so far
+  uint64_t drained_chunks = 0;    // chunks drain() handed to the writer
   std::atomic<int> fail{0};
   std::string writer_err;
   double t_deflate = 0;
-  static constexpr size_t QUANT_FLD_MAX = 1000;           // br_quant's default "fld_max"
   static constexpr uint64_t SORT_PIECE = 128ull << 20;   // record bytes per sorted piece (one deflate / format call and one download)
   void go() {
+    for (auto &c : consumers) order.push_back(c.get());
+    std::stable_partition(order.begin(), order.end(), [](Consumer *c) { return !c->keeps_records(); });
+    keep = !order.empty() && order.back()->keeps_records();
     std::thread writer([this] { write(); });
     for (auto &wp : workers) {
       Worker *w = wp.get();
@@ -342,9 +335,16 @@ struct Run {
       } else w->runner = std::thread([this, w] { run_resident(w, *in.dev_queue((size_t)w->id)); });   // (the bundles are in its HBM already)
     }
     for (auto &w : workers) { if (w->uploader.joinable()) w->uploader.join(); if (w->runner.joinable()) w->runner.join(); }
-    if (quant && !fail) quantify(workers[0].get());
-    if (coverage && !fail) cover(workers[0].get());
-    if (sorter && !fail) { in.join(); drain_sorted(workers[0].get()); }   // (the source's last sequence number is final after join)
+    for (Consumer *c : order) {   // the device work after the last bundle counts as worker 0's
+      if (fail) break;
+      Worker *w = workers[0].get();
+      if (c->keeps_records()) in.join();   // (the source's last sequence number is final after join)
+      auto t0 = now();
+      int rc = c->finish();
+      if (!rc && c->keeps_records()) rc = drain(w, c);
+      w->gpu_seconds += secs(t0, now());
+      if (rc) { fprintf(stderr, "error: %s failed on device %d: %s\n", c->failure, w->device, br_strerror(rc)); raise_fail(); }
+    }
     out.finish();
     in.join(); writer.join();
   }
@@ -392,14 +392,13 @@ struct Run {
     }
     return true;
   }
-  // --sort, after the last bundle: finish, then piece by piece next -> deflate or format + download (nowait) -> the writer
-  void drain_sorted(Worker *w) {
-    auto t0 = now();
-    int rc = br_sorter_finish(sorter, &sorted_records);
+  // the kept records, after the last bundle: piece by piece next_piece -> deflate or format + download (nowait) -> the writer
+  int drain(Worker *w, Consumer *c) {
+    int rc = 0;
     uint64_t seq = in.next_seq;
-    while (!rc && !fail) {
+    while (!fail) {
       br_device_bam piece;
-      rc = br_sorter_next(sorter, SORT_PIECE, &piece);
+      rc = c->next_piece(SORT_PIECE, &piece);
       if (rc || piece.n_rows == 0) break;
       { std::unique_lock<std::mutex> l(w->done_m); w->done_cv.wait(l, [&] { return w->written + 2 > w->produced || fail; }); }
       if (fail) break;
@@ -408,55 +407,15 @@ struct Run {
       if (rc) break;
       { std::lock_guard<std::mutex> l(w->done_m); w->produced++; }
       out.put(seq++, OutChunk{hb.data, hb.n_bytes, w->id});
-      sorted_chunks++;
+      drained_chunks++;
     }
-    w->gpu_seconds += secs(t0, now());
-    (void)br_sorter_stats(sorter, nullptr, nullptr, &t_sort_add, &t_sort_finish, nullptr);
-    if (rc) { fprintf(stderr, "error: sorting failed on device %d: %s\n", w->device, br_strerror(rc)); raise_fail(); }
-  }
-  // --quant, after the last bundle: classes, EM, and everything the two files need in one download
-  void quantify(Worker *w) {
-    auto t0 = now();
-    int rc = br_quant_finish(quant, &q_names, &q_classes);
-    if (!rc) rc = br_quant_em(quant, &q_iters, nullptr);
-    if (!rc) {
-      const size_t nt = br_index_num_transcripts(w->ix);
-      q_theta.resize(nt + 1); q_tpm.resize(nt + 1); q_unique.resize(nt + 1); q_ambig.resize(nt + 1);
-      rc = br_quant_result(quant, q_theta.data(), q_tpm.data(), q_unique.data(), q_ambig.data());
-    }
-    if (!rc && o.quant_eff_length) {
-      q_eff.resize(br_index_num_transcripts(w->ix) + 1); q_fld.resize(QUANT_FLD_MAX + 1);
-      rc = br_quant_eff_lengths(quant, q_eff.data());
-      if (!rc) rc = br_quant_fld(quant, q_fld.data(), &q_fld_obs, &q_fld_nofrag, &q_fld_oor);
-    }
-    if (!rc && !o.quant_classes.empty()) {
-      int64_t n_labels = 0;
-      rc = br_quant_stats(quant, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n_labels);
-      q_label_off.resize((size_t)q_classes + 1); q_counts.resize((size_t)q_classes + 1); q_labels.resize((size_t)n_labels + 1);
-      if (!rc) rc = br_quant_classes(quant, q_label_off.data(), q_labels.data(), q_counts.data(), nullptr);
-    }
-    w->gpu_seconds += secs(t0, now());
-    (void)br_quant_stats(quant, nullptr, nullptr, &t_q_add, &t_q_finish, &t_q_em, nullptr, nullptr, nullptr);
-    if (rc) { fprintf(stderr, "error: quantification failed on device %d: %s\n", w->device, br_strerror(rc)); raise_fail(); }
-  }
-  // --coverage, after the last bundle: depth, summary and runs; the per-transcript table comes home here, the runs in pages later
-  void cover(Worker *w) {
-    auto t0 = now();
-    int rc = br_coverage_finish(coverage, &cov_runs);
-    if (!rc) {
-      const size_t nt = br_index_num_transcripts(w->ix);
-      cov_records.resize(nt + 1); cov_aligned.resize(nt + 1); cov_covered.resize(nt + 1); cov_max.resize(nt + 1);
-      rc = br_coverage_summary(coverage, cov_records.data(), cov_aligned.data(), cov_covered.data(), cov_max.data());
-    }
-    w->gpu_seconds += secs(t0, now());
-    (void)br_coverage_stats(coverage, nullptr, nullptr, nullptr, nullptr, nullptr, &t_cov_add, &t_cov_finish);
-    if (rc) { fprintf(stderr, "error: coverage failed on device %d: %s\n", w->device, br_strerror(rc)); raise_fail(); }
+    return rc;
   }
   br_bam_bundle args(Bundle &b) const {
     return br_bam_bundle{b.blob.data(), b.blob.size(), b.off.data(), b.len.data(), (int64_t)b.off.size(), ref_map.data(), (int32_t)ref_map.size(), out_mode()};
   }
   int final_mode() const { return o.sam_out ? BR_OUT_SAM_TEXT : o.device_deflate ? 1 : 0; }   // what the writer gets
-  int out_mode() const { return sorter ? BR_OUT_RESIDENT : final_mode(); }                     // what a projection call leaves
+  int out_mode() const { return keep ? BR_OUT_RESIDENT : final_mode(); }                       // what a projection call leaves
   // one projection call (none after a failure), once chunk j - 2 of this worker is on disk: the context's two pinned
   // result buffers alternate
   template <typename F>
@@ -473,22 +432,9 @@ struct Run {
   void deliver(Worker *w, uint64_t seq, const br_host_bam &hb) {
     if (fail) return;
     w->total_complete += hb.total_complete; w->total_unique += hb.total_unique; w->dropped += hb.dropped_reads; w->n_bundles++;
-    if (quant) {   // the bundle's rows are still where the projection left them: the context's next call comes after this one
-      const int qrc = br_quant_add_last(quant, w->ctx);
-      if (qrc) { fprintf(stderr, "error: the quantifier could not take a bundle on device %d: %s\n", w->device, br_strerror(qrc)); raise_fail(); return; }
-    }
-    if (coverage) {
-      const int crc = br_coverage_add_last(coverage, w->ctx);
-      if (crc) { fprintf(stderr, "error: the coverage could not take a bundle on device %d: %s\n", w->device, br_strerror(crc)); raise_fail(); return; }
-    }
-    if (sorter) {   // the records stay in HBM: into the sorter (the runner sees the bundles in order), nothing for the writer yet
-      br_device_bam db;
-      int src = br_ctx_last_device_bam(w->ctx, &db);
-      if (!src) src = br_sorter_add(sorter, &db, 1, nullptr);
-      if (src) { fprintf(stderr, "error: the sorter could not take a bundle on device %d: %s\n", w->device, br_strerror(src)); raise_fail(); return; }
-      out.put(seq, OutChunk{nullptr, 0, -1});
-      return;
-    }
+    for (Consumer *c : order)
+      if (const int rc = c->add(w->ctx)) { fprintf(stderr, "error: the %s could not take a bundle on device %d: %s\n", c->name, w->device, br_strerror(rc)); raise_fail(); return; }
+    if (keep) { out.put(seq, OutChunk{nullptr, 0, -1}); return; }   // (the runner sees the bundles in order; nothing for the writer yet)
     { std::lock_guard<std::mutex> l(w->done_m); w->produced++; }
     out.put(seq, OutChunk{hb.data, hb.n_bytes, w->id});
   }
@@ -576,16 +522,9 @@ extern "C" int br_cli_main(int argc, char **argv) {
 
   // the input is already being read while the guides are parsed and the indexes are built
   std::vector<std::unique_ptr<Worker>> workers;
-  br_sorter *sorter = nullptr;
-  br_quant *quant = nullptr;
-  br_coverage *coverage = nullptr;
+  std::vector<std::unique_ptr<Consumer>> consumers;
   auto free_all = [&]() {
-    if (coverage) br_coverage_free(coverage);
-    coverage = nullptr;
-    if (sorter) br_sorter_free(sorter);
-    sorter = nullptr;
-    if (quant) br_quant_free(quant);
-    quant = nullptr;
+    consumers.clear();
     for (auto &w : workers) { if (w->ctx) br_ctx_free(w->ctx); if (w->ix) br_index_free(w->ix); w->ctx = nullptr; w->ix = nullptr; }
     if (ann) br_annotation_free(ann);
     ann = nullptr;
@@ -633,43 +572,23 @@ extern "C" int br_cli_main(int argc, char **argv) {
   std::vector<int32_t> ref_map(hdr.ref_names.size());
   int32_t extra = (int32_t)n_refs;
   for (size_t r = 0; r < hdr.ref_names.size(); r++) { auto it = ref_of.find(hdr.ref_names[r]); ref_map[r] = it != ref_of.end() ? it->second : extra++; }
-  if (o.sam_out) {   // RNAME / RNEXT: the @SQ list make_bam_header writes (transcripts of length > 0, in index order)
+  // every transcript's name and length, once: a line of a file, an RNAME, a BAI bin belong to the @SQ list, the transcripts of
+  // length > 0 in index order (what make_bam_header writes)
+  RunEnv env{o, o.devices[0], {}};
+  for (size_t t = 0, nt = br_index_num_transcripts(ix0); t < nt; t++) {
+    env.tx.name.push_back(br_index_transcript_name(ix0, (uint32_t)t));
+    env.tx.len.push_back(br_index_transcript_len(ix0, (uint32_t)t));
+  }
+  number_sq(env.tx);
+  if (o.sam_out) {   // RNAME / RNEXT
     std::vector<const char *> sq;
-    for (size_t t = 0, nt = br_index_num_transcripts(ix0); t < nt; t++)
-      if (br_index_transcript_len(ix0, (uint32_t)t) > 0) sq.push_back(br_index_transcript_name(ix0, (uint32_t)t));
+    for (size_t t = 0; t < env.tx.len.size(); t++) if (env.tx.len[t] > 0) sq.push_back(env.tx.name[t]);
     for (auto &w : workers) {
       int src = br_ctx_set_sam_refs(w->ctx, sq.data(), (int32_t)sq.size());
       if (src) { fprintf(stderr, "error: reference names on device %d: %s\n", w->device, br_strerror(src)); return give_up(); }
     }
   }
-  uint32_t n_sq = 0;
-  for (size_t t = 0, nt = br_index_num_transcripts(ix0); t < nt; t++) if (br_index_transcript_len(ix0, (uint32_t)t) > 0) n_sq++;
-  if (o.sort) {
-    int src = br_sorter_new(o.devices[0], &sorter);
-    if (src) { fprintf(stderr, "error: sorter on device %d: %s\n", o.devices[0], br_strerror(src)); return give_up(); }
-  }
-  // --quant: tid = the index's transcript, its line in the files = the @SQ list's (transcripts of length > 0)
-  std::vector<int64_t> tx_len;
-  if (!o.quant.empty()) {
-    const size_t nt = br_index_num_transcripts(ix0);
-    tx_len.resize(nt);
-    for (size_t t = 0; t < nt; t++) tx_len[t] = br_index_transcript_len(ix0, (uint32_t)t);
-    int qrc = br_quant_new(o.devices[0], (int64_t)nt, tx_len.data(), &quant);
-    const int norm = o.quant_length_norm >= 0 ? o.quant_length_norm : (o.cfg.lr || o.cfg.lr_hq) ? 0 : 1;   // (oarfish does not length-normalise long reads)
-    if (!qrc) qrc = br_quant_set_param(quant, "length_norm", norm);
-    if (!qrc && o.quant_eff_length) qrc = br_quant_set_param(quant, "eff_len", 1);
-    if (qrc) { fprintf(stderr, "error: quantifier on device %d: %s\n", o.devices[0], br_strerror(qrc)); return give_up(); }
-  }
-  // --coverage: the same numbering (tid = the index's transcript, a line per @SQ transcript)
-  const bool want_cov = !o.coverage.empty() || !o.coverage_summary.empty();
-  if (want_cov) {
-    const size_t nt = br_index_num_transcripts(ix0);
-    tx_len.resize(nt);
-    for (size_t t = 0; t < nt; t++) tx_len[t] = br_index_transcript_len(ix0, (uint32_t)t);
-    int crc = br_coverage_new(o.devices[0], (int64_t)nt, tx_len.data(), &coverage);
-    if (!crc && o.coverage_primary) crc = br_coverage_set_param(coverage, "primary_only", 1);
-    if (crc) { fprintf(stderr, "error: coverage on device %d: %s\n", o.devices[0], br_strerror(crc)); return give_up(); }
-  }
+  if (!open_consumers(env, consumers, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return give_up(); }
   OutFile file(o.out_bam);
   if (!file.wr.open(file.tmp.c_str(), o.threads, o.level, !o.sam_out)) { fprintf(stderr, "error: %s\n", file.wr.error().c_str()); return give_up(); }
   {
@@ -681,142 +600,18 @@ extern "C" int br_cli_main(int argc, char **argv) {
   }
   if (!o.quiet) printf("[bramble] processing alignments :-)\n");
   double t_setup = since();
-  Run run{o, *in, out, file.wr, ref_map, workers};
-  run.sorter = sorter; run.track_blocks = o.write_index; run.quant = quant; run.coverage = coverage;
+  Run run{o, *in, out, file.wr, ref_map, workers, consumers};
+  run.track_blocks = o.write_index;
   run.go();
   int failed = run.fail.load();
   if (!in->err.empty()) { fprintf(stderr, in->err_at_line ? "error: %s:%s\n" : "error: %s: %s\n", o.in_bam.c_str(), in->err.c_str()); failed = 1; }
   if (!run.writer_err.empty()) { fprintf(stderr, "error: %s: %s\n", o.out_bam.c_str(), run.writer_err.c_str()); failed = 1; }
-  if (!failed && out.next != in->next_seq + run.sorted_chunks) { fprintf(stderr, "error: %s: output incomplete\n", o.out_bam.c_str()); failed = 1; }
-  const std::string bai_path = o.out_bam + ".bai", bai_tmp = bai_path + ".tmp-bramble";
-  if (!failed && o.write_index) {   // the index of the blocks just written; it takes the output's route: a temporary name, renamed on success
-    uint8_t *bai = nullptr; uint64_t bai_n = 0;
-    int irc = file.wr.flush() ? br_sorter_index(sorter, (int32_t)n_sq, run.spans.data(), (int64_t)run.spans.size(), file.wr.bytes_out(), &bai, &bai_n) : BR_ERR_INVALID_ARG;
-    if (irc) { fprintf(stderr, "error: %s: index: %s\n", bai_path.c_str(), br_strerror(irc)); failed = 1; }
-    else {
-      FILE *f = fopen(bai_tmp.c_str(), "wb");
-      if (!f || fwrite(bai, 1, (size_t)bai_n, f) != (size_t)bai_n) { fprintf(stderr, "error: could not write %s\n", bai_tmp.c_str()); failed = 1; }
-      if (f && fclose(f) != 0) { fprintf(stderr, "error: could not write %s\n", bai_tmp.c_str()); failed = 1; }
-      br_free_buffer(bai);
-    }
-  }
-  // the quantifier's files take the output's route as well
-  const std::string q_tmp = o.quant + ".tmp-bramble", qc_tmp = o.quant_classes + ".tmp-bramble", qf_tmp = o.quant_fld + ".tmp-bramble";
-  if (!failed && quant) {
-    const size_t nt = tx_len.size();
-    std::vector<int64_t> sq_of(nt, -1);
-    int64_t nsq = 0;
-    for (size_t t = 0; t < nt; t++) if (tx_len[t] > 0) sq_of[t] = nsq++;
-    auto close_ok = [&](FILE *f, const std::string &p) {
-      const bool bad = !f || ferror(f);
-      if (f && fclose(f) != 0) { fprintf(stderr, "error: could not write %s\n", p.c_str()); return false; }
-      if (bad) fprintf(stderr, "error: could not write %s\n", p.c_str());
-      return !bad;
-    };
-    FILE *f = fopen(q_tmp.c_str(), "w");
-    if (f && o.quant_eff_length) {
-      fprintf(f, "Name\tLength\tEffectiveLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\n");
-      for (size_t t = 0; t < nt; t++)
-        if (tx_len[t] > 0) fprintf(f, "%s\t%lld\t%.3f\t%.6f\t%.6f\t%llu\t%llu\n", br_index_transcript_name(ix0, (uint32_t)t), (long long)tx_len[t], run.q_eff[t], run.q_theta[t],
-                                   run.q_tpm[t], (unsigned long long)run.q_unique[t], (unsigned long long)run.q_ambig[t]);
-    } else if (f) {
-      fprintf(f, "Name\tLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\n");
-      for (size_t t = 0; t < nt; t++)
-        if (tx_len[t] > 0) fprintf(f, "%s\t%lld\t%.6f\t%.6f\t%llu\t%llu\n", br_index_transcript_name(ix0, (uint32_t)t), (long long)tx_len[t], run.q_theta[t], run.q_tpm[t],
-                                   (unsigned long long)run.q_unique[t], (unsigned long long)run.q_ambig[t]);
-    }
-    if (!close_ok(f, q_tmp)) failed = 1;
-    if (!failed && !o.quant_classes.empty()) {
-      f = fopen(qc_tmp.c_str(), "w");
-      if (f) {
-        fprintf(f, "%lld\n%lld\n", (long long)nsq, (long long)run.q_classes);
-        for (size_t t = 0; t < nt; t++) if (tx_len[t] > 0) fprintf(f, "%s\n", br_index_transcript_name(ix0, (uint32_t)t));
-        for (int64_t c = 0; c < run.q_classes; c++) {
-          fprintf(f, "%llu", (unsigned long long)(run.q_label_off[(size_t)c + 1] - run.q_label_off[(size_t)c]));
-          for (uint64_t e = run.q_label_off[(size_t)c]; e < run.q_label_off[(size_t)c + 1]; e++) fprintf(f, "\t%lld", (long long)sq_of[run.q_labels[(size_t)e]]);
-          fprintf(f, "\t%llu\n", (unsigned long long)run.q_counts[(size_t)c]);
-        }
-      }
-      if (!close_ok(f, qc_tmp)) failed = 1;
-    }
-    if (!failed && !o.quant_fld.empty()) {
-      f = fopen(qf_tmp.c_str(), "w");
-      if (f) {
-        fprintf(f, "FragmentLength\tCount\n");
-        for (size_t k = 0; k <= Run::QUANT_FLD_MAX; k++) fprintf(f, "%zu\t%llu\n", k, (unsigned long long)run.q_fld[k]);
-      }
-      if (!close_ok(f, qf_tmp)) failed = 1;
-    }
-  }
-  // the coverage's two files likewise; the bedGraph's text is made here, from pages of runs
-  const std::string cv_tmp = o.coverage + ".tmp-bramble", cs_tmp = o.coverage_summary + ".tmp-bramble";
-  uint64_t cov_n = 0, cov_a = 0, cov_c = 0, cov_b = 0;
-  if (!failed && coverage) {
-    const size_t nt = tx_len.size();
-    auto close_ok = [&](FILE *f, const std::string &p) {
-      const bool bad = !f || ferror(f);
-      if (f && fclose(f) != 0) { fprintf(stderr, "error: could not write %s\n", p.c_str()); return false; }
-      if (bad) fprintf(stderr, "error: could not write %s\n", p.c_str());
-      return !bad;
-    };
-    for (size_t t = 0; t < nt; t++) { cov_n += run.cov_records[t]; cov_a += run.cov_aligned[t]; cov_c += run.cov_covered[t]; cov_b += (uint64_t)std::max<int64_t>(tx_len[t], 0); }
-    if (!o.coverage.empty()) {
-      FILE *f = fopen(cv_tmp.c_str(), "w");
-      constexpr int64_t PAGE = 1 << 20;
-      std::vector<uint32_t> r_tid((size_t)std::min(run.cov_runs, PAGE) + 1), r_start(r_tid.size()), r_end(r_tid.size()), r_depth(r_tid.size());
-      for (int64_t first = 0; f && !failed && first < run.cov_runs; first += PAGE) {
-        const int64_t n = std::min(PAGE, run.cov_runs - first);
-        const int crc = br_coverage_runs(coverage, first, n, r_tid.data(), r_start.data(), r_end.data(), r_depth.data());
-        if (crc) { fprintf(stderr, "error: coverage on device %d: %s\n", o.devices[0], br_strerror(crc)); failed = 1; break; }
-        for (int64_t k = 0; k < n; k++) fprintf(f, "%s\t%u\t%u\t%u\n", br_index_transcript_name(ix0, r_tid[(size_t)k]), r_start[(size_t)k], r_end[(size_t)k], r_depth[(size_t)k]);
-      }
-      if (!close_ok(f, cv_tmp)) failed = 1;
-    }
-    if (!failed && !o.coverage_summary.empty()) {
-      FILE *f = fopen(cs_tmp.c_str(), "w");
-      if (f) {
-        fprintf(f, "Name\tLength\tRecords\tAlignedBases\tCoveredBases\tMaxDepth\tMeanDepth\tBreadth\n");
-        for (size_t t = 0; t < nt; t++)
-          if (tx_len[t] > 0) fprintf(f, "%s\t%lld\t%llu\t%llu\t%llu\t%u\t%.6f\t%.6f\n", br_index_transcript_name(ix0, (uint32_t)t), (long long)tx_len[t],
-                                     (unsigned long long)run.cov_records[t], (unsigned long long)run.cov_aligned[t], (unsigned long long)run.cov_covered[t], run.cov_max[t],
-                                     (double)run.cov_aligned[t] / (double)tx_len[t], (double)run.cov_covered[t] / (double)tx_len[t]);
-      }
-      if (!close_ok(f, cs_tmp)) failed = 1;
-    }
-  }
+  if (!failed && out.next != in->next_seq + run.drained_chunks) { fprintf(stderr, "error: %s: output incomplete\n", o.out_bam.c_str()); failed = 1; }
+  // the consumers' files take the output's route: temporary names, renamed once everything has succeeded; none is begun after a failure
+  for (auto &c : consumers) if (!failed && !c->write_files(file.wr, run.spans)) failed = 1;
   if (!file.finish(!failed)) failed = 1;
-  if (coverage) {
-    auto settle = [&](const std::string &tmp, const std::string &path) {
-      if (path.empty()) return;
-      if (failed) remove(tmp.c_str());
-      else if (rename(tmp.c_str(), path.c_str()) != 0) { fprintf(stderr, "error: could not rename %s to %s\n", tmp.c_str(), path.c_str()); failed = 1; }
-    };
-    settle(cv_tmp, o.coverage); settle(cs_tmp, o.coverage_summary);
-    if (failed) { if (!o.coverage.empty()) remove(cv_tmp.c_str()); if (!o.coverage_summary.empty()) remove(cs_tmp.c_str()); }
-  }
-  if (quant) {
-    auto settle = [&](const std::string &tmp, const std::string &path) {
-      if (path.empty()) return;
-      if (failed) remove(tmp.c_str());
-      else if (rename(tmp.c_str(), path.c_str()) != 0) { fprintf(stderr, "error: could not rename %s to %s\n", tmp.c_str(), path.c_str()); failed = 1; }
-    };
-    settle(q_tmp, o.quant); settle(qc_tmp, o.quant_classes); settle(qf_tmp, o.quant_fld);
-    if (failed) { remove(q_tmp.c_str()); if (!o.quant_classes.empty()) remove(qc_tmp.c_str()); if (!o.quant_fld.empty()) remove(qf_tmp.c_str()); }
-  }
-  if (o.write_index) {
-    if (failed) remove(bai_tmp.c_str());
-    else if (rename(bai_tmp.c_str(), bai_path.c_str()) != 0) { fprintf(stderr, "error: could not rename %s to %s\n", bai_tmp.c_str(), bai_path.c_str()); failed = 1; }
-  }
-  if (!o.quiet && o.sort && !failed) printf("[bramble] sorted %lld records by coordinate on device %d (add %.2fs, sort %.2fs)%s\n", (long long)run.sorted_records, o.devices[0], run.t_sort_add, run.t_sort_finish, o.write_index ? ", index written" : "");
-  if (!o.quiet && quant && !failed && o.quant_eff_length) {
-    double sum = 0;
-    for (size_t k = 0; k <= Run::QUANT_FLD_MAX; k++) sum += (double)k * (double)run.q_fld[k];
-    printf("[bramble] fragment lengths: %llu observed, mean %.1f, %llu unique names without a pair, %llu out of range\n", (unsigned long long)run.q_fld_obs,
-           run.q_fld_obs ? sum / (double)run.q_fld_obs : 0.0, (unsigned long long)run.q_fld_nofrag, (unsigned long long)run.q_fld_oor);
-  }
-  if (!o.quiet && quant && !failed) printf("[bramble] quantified %lld read names in %lld classes (%d iterations, add %.2fs, classes %.2fs, EM %.2fs)\n", (long long)run.q_names, (long long)run.q_classes, (int)run.q_iters, run.t_q_add, run.t_q_finish, run.t_q_em);
-  if (!o.quiet && coverage && !failed) printf("[bramble] coverage: %llu records, %llu aligned bases on %llu of %llu bases in %lld runs (add %.2fs, finish %.2fs)\n", (unsigned long long)cov_n, (unsigned long long)cov_a,
-                                              (unsigned long long)cov_c, (unsigned long long)cov_b, (long long)run.cov_runs, run.t_cov_add, run.t_cov_finish);
+  for (auto c = consumers.rbegin(); c != consumers.rend(); ++c) if (!(*c)->settle(failed)) failed = 1;
+  if (!o.quiet && !failed) for (auto &c : consumers) c->report();
   double t_done = since();
   uint64_t total_complete = 0, total_unique = 0, dropped = 0, n_bundles = 0;
   double gpu_seconds = 0, t_upload = 0, t_wait_gpu_in = 0;

@@ -1,0 +1,84 @@
+// SideFile and the text of the five side files (cli_output_files.h).  No call into the library.
+#include "cli_output_files.h"
+
+#include <algorithm>
+
+namespace brcli {
+
+FILE *SideFile::open(bool binary) { return f_ = path.empty() ? nullptr : fopen(tmp.c_str(), binary ? "wb" : "w"); }
+
+bool SideFile::close() {
+  if (path.empty()) return true;
+  bool ok = f_ && !ferror(f_);
+  if (f_ && fclose(f_) != 0) ok = false;
+  f_ = nullptr;
+  if (!ok) fprintf(stderr, "error: could not write %s\n", tmp.c_str());
+  return ok;
+}
+
+bool SideFile::settle(bool failed) {
+  if (path.empty()) return true;
+  const bool renamed = !failed && rename(tmp.c_str(), path.c_str()) == 0;
+  if (!failed && !renamed) fprintf(stderr, "error: could not rename %s to %s\n", tmp.c_str(), path.c_str());
+  if (!renamed) remove(tmp.c_str());
+  return failed || renamed;
+}
+
+bool settle_all(std::initializer_list<SideFile *> files, bool failed) {
+  for (SideFile *f : files) if (!f->settle(failed)) failed = true;
+  return !failed;
+}
+
+void number_sq(TxTable &tx) {
+  tx.sq_of.assign(tx.len.size(), -1);
+  tx.n_sq = 0;
+  for (size_t t = 0; t < tx.len.size(); t++) if (tx.len[t] > 0) tx.sq_of[t] = tx.n_sq++;
+}
+
+void write_quant_table(FILE *f, const TxTable &tx, const std::vector<double> *eff, const std::vector<double> &theta, const std::vector<double> &tpm,
+                       const std::vector<uint64_t> &unique, const std::vector<uint64_t> &ambig) {
+  fprintf(f, eff ? "Name\tLength\tEffectiveLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\n" : "Name\tLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\n");
+  for (size_t t = 0; t < tx.len.size(); t++) {
+    if (tx.len[t] <= 0) continue;
+    fprintf(f, "%s\t%lld", tx.name[t], (long long)tx.len[t]);
+    if (eff) fprintf(f, "\t%.3f", (*eff)[t]);
+    fprintf(f, "\t%.6f\t%.6f\t%llu\t%llu\n", theta[t], tpm[t], (unsigned long long)unique[t], (unsigned long long)ambig[t]);
+  }
+}
+
+void write_quant_classes(FILE *f, const TxTable &tx, int64_t n_classes, const std::vector<uint64_t> &label_off, const std::vector<uint32_t> &labels,
+                         const std::vector<uint64_t> &counts) {
+  fprintf(f, "%lld\n%lld\n", (long long)tx.n_sq, (long long)n_classes);
+  for (size_t t = 0; t < tx.len.size(); t++) if (tx.len[t] > 0) fprintf(f, "%s\n", tx.name[t]);
+  for (size_t c = 0; c < (size_t)n_classes; c++) {
+    fprintf(f, "%llu", (unsigned long long)(label_off[c + 1] - label_off[c]));
+    for (uint64_t e = label_off[c]; e < label_off[c + 1]; e++) fprintf(f, "\t%lld", (long long)tx.sq_of[labels[(size_t)e]]);
+    fprintf(f, "\t%llu\n", (unsigned long long)counts[c]);
+  }
+}
+
+void write_fragment_lengths(FILE *f, const std::vector<uint64_t> &hist) {
+  fprintf(f, "FragmentLength\tCount\n");
+  for (size_t k = 0; k < hist.size(); k++) fprintf(f, "%zu\t%llu\n", k, (unsigned long long)hist[k]);
+}
+
+int write_bedgraph(FILE *f, const TxTable &tx, int64_t n_runs, int64_t page, const RunPage &fetch) {
+  std::vector<uint32_t> tid((size_t)std::min(n_runs, page) + 1), start(tid.size()), end(tid.size()), depth(tid.size());
+  for (int64_t first = 0; first < n_runs; first += page) {
+    const int64_t n = std::min(page, n_runs - first);
+    if (const int rc = fetch(first, n, tid.data(), start.data(), end.data(), depth.data())) return rc;
+    for (size_t k = 0; k < (size_t)n; k++) fprintf(f, "%s\t%u\t%u\t%u\n", tx.name[tid[k]], start[k], end[k], depth[k]);
+  }
+  return 0;
+}
+
+void write_coverage_summary(FILE *f, const TxTable &tx, const std::vector<uint64_t> &records, const std::vector<uint64_t> &aligned,
+                            const std::vector<uint64_t> &covered, const std::vector<uint32_t> &max_depth) {
+  fprintf(f, "Name\tLength\tRecords\tAlignedBases\tCoveredBases\tMaxDepth\tMeanDepth\tBreadth\n");
+  for (size_t t = 0; t < tx.len.size(); t++)
+    if (tx.len[t] > 0) fprintf(f, "%s\t%lld\t%llu\t%llu\t%llu\t%u\t%.6f\t%.6f\n", tx.name[t], (long long)tx.len[t], (unsigned long long)records[t],
+                               (unsigned long long)aligned[t], (unsigned long long)covered[t], max_depth[t], (double)aligned[t] / (double)tx.len[t],
+                               (double)covered[t] / (double)tx.len[t]);
+}
+
+}  // namespace brcli

@@ -1,0 +1,44 @@
+// The files beside the main output (cli_output.h): how each goes to disk and what its text is.  Plain data and a FILE * only --
+// nothing here knows the library, so cli_output_files.cpp builds and runs without it (tests/cli_output_probe.cpp).
+#pragma once
+#include <stdint.h>
+#include <stdio.h>
+
+#include <functional>
+#include <string>
+#include <vector>
+
+namespace brcli {
+
+// A file written under a temporary name next to its target and renamed once the whole run has succeeded, like the main output: a
+// failed run leaves neither.  An empty path: the file was not asked for, and every call does nothing.
+class SideFile {
+ public:
+  explicit SideFile(const std::string &p) : path(p), tmp(p.empty() ? p : p + ".tmp-bramble") {}
+  FILE *open(bool binary = false);   // nullptr: not asked for, or not opened -- close() says which
+  bool close();                      // false: opening, a write or the close failed (said here)
+  bool settle(bool failed);          // renames, or after a failure removes; false: the rename failed (said here, nothing is left)
+  const std::string path, tmp;
+ private:
+  FILE *f_ = nullptr;
+};
+bool settle_all(std::initializer_list<SideFile *> files, bool failed);   // in this order; after a failed rename the rest is removed; false: one failed
+
+// Every transcript of the index; the tables list those of length > 0 (the output's @SQ list), numbered in that order by sq_of
+struct TxTable { std::vector<const char *> name; std::vector<int64_t> len, sq_of; int64_t n_sq = 0; };
+void number_sq(TxTable &tx);   // sq_of and n_sq from len
+
+// eff: the EffectiveLength column behind Length, nullptr without it
+void write_quant_table(FILE *f, const TxTable &tx, const std::vector<double> *eff, const std::vector<double> &theta, const std::vector<double> &tpm,
+                       const std::vector<uint64_t> &unique, const std::vector<uint64_t> &ambig);
+// salmon's eq_classes.txt: the counts, the names, then per class its size, its transcripts' @SQ numbers and its count
+void write_quant_classes(FILE *f, const TxTable &tx, int64_t n_classes, const std::vector<uint64_t> &label_off, const std::vector<uint32_t> &labels,
+                         const std::vector<uint64_t> &counts);
+void write_fragment_lengths(FILE *f, const std::vector<uint64_t> &hist);
+// runs [first, first + n) into the four columns; not 0: an error, which ends the file there
+using RunPage = std::function<int(int64_t first, int64_t n, uint32_t *tid, uint32_t *start, uint32_t *end, uint32_t *depth)>;
+int write_bedgraph(FILE *f, const TxTable &tx, int64_t n_runs, int64_t page, const RunPage &fetch);   // the first error of fetch
+void write_coverage_summary(FILE *f, const TxTable &tx, const std::vector<uint64_t> &records, const std::vector<uint64_t> &aligned,
+                            const std::vector<uint64_t> &covered, const std::vector<uint32_t> &max_depth);
+
+}  // namespace brcli

@@ -1,0 +1,79 @@
+// --quant and its switches (cli_output.h): every bundle's rows go to a br_quant (br_quant_add_last; --quant-eff-length: the adds
+// count the fragment lengths as well, "eff_len"); after the last bundle: classes, EM, and everything the three files need in one
+// download each -- the table, --quant-classes, --quant-fld.
+#include "cli_output.h"
+
+namespace brcli {
+namespace {
+
+class QuantOut : public Consumer {
+ public:
+  explicit QuantOut(const RunEnv &e) : Consumer(e, "quantifier", "quantification"), table(e.o.quant), classes(e.o.quant_classes), fld(e.o.quant_fld) {}
+  ~QuantOut() override { if (q) br_quant_free(q); }
+  int open() {
+    const Options &o = env.o;
+    int rc = br_quant_new(env.device, (int64_t)env.tx.len.size(), env.tx.len.data(), &q);
+    const int norm = o.quant_length_norm >= 0 ? o.quant_length_norm : (o.cfg.lr || o.cfg.lr_hq) ? 0 : 1;   // (oarfish does not length-normalise long reads)
+    if (!rc) rc = br_quant_set_param(q, "length_norm", norm);
+    if (!rc && o.quant_eff_length) rc = br_quant_set_param(q, "eff_len", 1);
+    return rc;
+  }
+  int add(br_ctx *ctx) override { return br_quant_add_last(q, ctx); }
+  int finish() override {
+    const size_t nt = env.tx.len.size();
+    int rc = br_quant_finish(q, &n_names, &n_classes);
+    if (!rc) rc = br_quant_em(q, &n_iters, nullptr);
+    if (!rc) {
+      theta.resize(nt + 1); tpm.resize(nt + 1); unique.resize(nt + 1); ambig.resize(nt + 1);
+      rc = br_quant_result(q, theta.data(), tpm.data(), unique.data(), ambig.data());
+    }
+    if (!rc && env.o.quant_eff_length) {
+      eff.resize(nt + 1); hist.resize(FLD_MAX + 1);
+      rc = br_quant_eff_lengths(q, eff.data());
+      if (!rc) rc = br_quant_fld(q, hist.data(), &fld_obs, &fld_nofrag, &fld_oor);
+    }
+    if (!rc && !classes.path.empty()) {
+      int64_t n_labels = 0;
+      rc = br_quant_stats(q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n_labels);
+      label_off.resize((size_t)n_classes + 1); counts.resize((size_t)n_classes + 1); labels.resize((size_t)n_labels + 1);
+      if (!rc) rc = br_quant_classes(q, label_off.data(), labels.data(), counts.data(), nullptr);
+    }
+    (void)br_quant_stats(q, nullptr, nullptr, &t_add, &t_finish, &t_em, nullptr, nullptr, nullptr);
+    return rc;
+  }
+  bool write_files(brio::BgzfWriter &, const std::vector<br_bgzf_span> &) override {
+    if (FILE *f = table.open()) write_quant_table(f, env.tx, env.o.quant_eff_length ? &eff : nullptr, theta, tpm, unique, ambig);
+    if (!table.close()) return false;
+    if (FILE *f = classes.open()) write_quant_classes(f, env.tx, n_classes, label_off, labels, counts);
+    if (!classes.close()) return false;
+    if (FILE *f = fld.open()) write_fragment_lengths(f, hist);
+    return fld.close();
+  }
+  bool settle(bool failed) override { return settle_all({&table, &classes, &fld}, failed); }
+  void report() const override {
+    if (env.o.quant_eff_length) {
+      double sum = 0;
+      for (size_t k = 0; k < hist.size(); k++) sum += (double)k * (double)hist[k];
+      printf("[bramble] fragment lengths: %llu observed, mean %.1f, %llu unique names without a pair, %llu out of range\n", (unsigned long long)fld_obs,
+             fld_obs ? sum / (double)fld_obs : 0.0, (unsigned long long)fld_nofrag, (unsigned long long)fld_oor);
+    }
+    printf("[bramble] quantified %lld read names in %lld classes (%d iterations, add %.2fs, classes %.2fs, EM %.2fs)\n", (long long)n_names, (long long)n_classes,
+           (int)n_iters, t_add, t_finish, t_em);
+  }
+ private:
+  static constexpr size_t FLD_MAX = 1000;   // br_quant's default "fld_max"
+  br_quant *q = nullptr;
+  SideFile table, classes, fld;
+  int64_t n_names = 0, n_classes = 0; int32_t n_iters = 0;
+  double t_add = 0, t_finish = 0, t_em = 0;
+  std::vector<double> theta, tpm, eff;
+  std::vector<uint64_t> unique, ambig, label_off, counts, hist;   // hist, eff: --quant-eff-length
+  std::vector<uint32_t> labels;
+  uint64_t fld_obs = 0, fld_nofrag = 0, fld_oor = 0;
+};
+
+}  // namespace
+
+std::unique_ptr<Consumer> open_quant(const RunEnv &env, std::string &err) { return open_as<QuantOut>(env, err); }
+
+}  // namespace brcli
