@@ -273,7 +273,7 @@ __device__ uint32_t tag_bytes(const SamArgs &A, uint64_t s, uint64_t e, uint8_t 
       return 3 + w;
     }
     case 'f': {
-      if (n == 0) return bad(SAM_E_TAG);
+      if (n == 0) return bad(SAM_E_FLOAT);   // an empty value is a malformed float, as an empty B:f element is
       if (!d && !float_syntax(t + v, n)) return bad(SAM_E_FLOAT);
       if (d) { d[2] = 'f'; if (!b_elem(A, t + v, n, 'f', d + 3, line)) return bad(SAM_E_TAG); }
       return 7;
@@ -295,7 +295,7 @@ __device__ uint32_t tag_bytes(const SamArgs &A, uint64_t s, uint64_t e, uint8_t 
           uint64_t q = p;
           while (q < e && t[q] != ',') q++;
           if (!b_elem(A, t + p, (uint32_t)(q - p), sub, d ? d + 8 + (uint64_t)es * cnt : nullptr, line))
-            return bad(q > p && sub != 'f' ? SAM_E_TAG_RANGE : SAM_E_TAG);
+            return bad(sub == 'f' ? SAM_E_FLOAT : q > p ? SAM_E_TAG_RANGE : SAM_E_TAG);
           cnt++;
           if (q >= e) break;
           p = q + 1;

@@ -89,7 +89,8 @@ def encode_line(line, refs):
         aux += b"CGBI" + struct.pack("<I", len(words)) + struct.pack("<%dI" % len(words), *words)
         words = [l_seq << 4 | 4, rlen << 4 | 3]
     pos0 = int(pos) - 1
-    rec = struct.pack("<iiBBHHHIiii", ref, pos0, len(qname) + 1, int(mapq), reg2bin(pos0, pos0 + (rlen or 1)), len(words), flag,
+    # bin is a 16-bit field (bam1_core_t.bin is uint16_t): past 2^29 the record keeps reg2bin's 16 low bits
+    rec = struct.pack("<iiBBHHHIiii", ref, pos0, len(qname) + 1, int(mapq), reg2bin(pos0, pos0 + (rlen or 1)) & 0xffff, len(words), flag,
                       l_seq, nref, int(pnext) - 1, int(tlen))
     rec += qname + b"\0" + struct.pack("<%dI" % len(words), *words) + seqb + qualb + aux
     return struct.pack("<I", len(rec)) + rec, not (flag & 4)
