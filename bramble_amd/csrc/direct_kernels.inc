@@ -387,9 +387,7 @@ __global__ void __launch_bounds__(64) k_pair_big(DirectArgs D) {
       else {
         pmask = D.mask[m];
         if ((uint32_t)lane < np) {
-          uint64_t mm = pmask;
-          for (int j = 0; j < lane; j++) mm &= mm - 1;
-          y_bit = (uint32_t)__builtin_ctzll(mm);
+          y_bit = kth_set_bit64(pmask, (uint32_t)lane);
           y_tid = D.s_tid[row_of_bit(y_bit, rp.x, rp.z, rp.y - rp.x)];
         }
         sh_y[lane] = y_tid;
@@ -502,12 +500,14 @@ __global__ void __launch_bounds__(256) k_scan5_tiles(DirectArgs D, uint64_t *til
   __syncthreads();
   if (threadIdx.x < 5) tile_sums[(int64_t)threadIdx.x * n_tiles + blockIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
 }
-// One block per quantity, 32 tile sums per thread and round (all of a round's loads in flight at once): the five
-// quantities in one block, eight sums per thread, took 0.23 ms -- 25 dependent load / scan / store rounds of one workgroup
-// on the step's critical path.
+// One block per quantity, SCAN5_TOP_ITEMS tile sums per thread and round.  Alone, the 10 206 sums of a quantity of the bench
+// step take 13 us with 8 sums per thread (58 VGPRs), 15 with 16, 22 with 32 (155 VGPRs) and 18 with 64; on the step's path
+// the kernel takes 0.12 ms whatever the shape, because its five blocks wait for wave slots that k_group_desc's 2 048
+// resident blocks hold on the second stream (DESIGN 10.1, row 26).
+constexpr int SCAN5_TOP_ITEMS = 8;
 __global__ void __launch_bounds__(256) k_scan5_top(uint64_t *tile_sums, int64_t n_tiles, uint64_t *total_out) {
   __shared__ uint64_t sh[4];
-  scan_top_rounds<1, 32>(tile_sums + (int64_t)blockIdx.x * n_tiles, n_tiles, total_out + blockIdx.x, sh);
+  scan_top_rounds<1, SCAN5_TOP_ITEMS>(tile_sums + (int64_t)blockIdx.x * n_tiles, n_tiles, total_out + blockIdx.x, sh);
 }
 __global__ void __launch_bounds__(256) k_scan5_apply(DirectArgs D, const uint64_t *tile_sums, int64_t n_tiles, const uint64_t *totals) {
   __shared__ uint64_t sh[4];
@@ -706,8 +706,10 @@ __global__ void __launch_bounds__(256) k_expand_rows(DirectArgs D) {
 // prefix (one read exon from a single M op, and the light two-exon class the count pass adds to it: "M N M" with exact
 // inner junctions, a closed form as well), 2 = the rest.
 // ---------------------------------------------------------------------------
+// (CLS 2 at five waves per SIMD: 91 VGPRs and no scratch.  At six, the most its LDS allows, the budget is 80 VGPRs and ten
+// of them went to 44 bytes of scratch per lane: 0.80-0.87 ms against 0.73-0.74 now that the class holds only heavy entries.)
 template <int CLS>
-__global__ void __launch_bounds__(256, CLS == 1 ? 8 : 6) k_emit_rows(ProjectArgs A, DirectArgs D, int64_t first, int64_t n_end) {
+__global__ void __launch_bounds__(256, CLS == 1 ? 8 : 5) k_emit_rows(ProjectArgs A, DirectArgs D, int64_t first, int64_t n_end) {
   __shared__ uint32_t sh_cig[CLS == 1 ? 1 : 256 * LDS_SLOT];
   __shared__ uint16_t sh_mops[CLS == 1 ? 1 : 256];
   if (CLS != 1) {
@@ -742,9 +744,7 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 6) k_emit_rows(ProjectArgs
   if (CLS != 1) rc.fetch(A.cigar + c0, c1 - c0);   // in flight with the row load below
   const uint32_t k = (uint32_t)e64 - E.w;
   const uint64_t fmask = (uint64_t)f.x | ((uint64_t)f.y << 32);
-  uint64_t mm = fmask;
-  for (uint32_t j = 0; j < k; j++) mm &= mm - 1;
-  const uint32_t item = (uint32_t)(__ffsll((long long)mm) - 1);
+  const uint32_t item = kth_set_bit64(fmask, k);
   const int s = item < n0 ? 0 : 1;
   const uint32_t row = s == 0 ? rg.x + item : rg.z + (item - n0);
   const uint4 r_a = ix.s_row[2 * (size_t)row], r_b = ix.s_row[2 * (size_t)row + 1];

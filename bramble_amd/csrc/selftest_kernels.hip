@@ -66,6 +66,12 @@ __global__ void __launch_bounds__(256) k_probe_top(uint64_t *tile_sums, int64_t 
   scan_top_rounds<C, ITEMS>(tile_sums, n_tiles, total_out, sh);
 }
 
+// out[i] = kth_set_bit64(masks[i], ks[i]), blocks of 256
+__global__ void __launch_bounds__(256) k_probe_kth_bit(const uint64_t *masks, const uint32_t *ks, uint32_t *out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = kth_set_bit64(masks[i], ks[i]);
+}
+
 static int finish(hipStream_t st) {
   hipError_t e = hipGetLastError();
   hipError_t s = hipStreamSynchronize(st);
@@ -80,6 +86,15 @@ static bool wave_widths(hipStream_t st, int width, const void *in, void *out, in
     case 16: hipLaunchKernelGGL((k_probe_wave<OP, T, 16>), g, b, 0, st, (const T *)in, (T *)out); return true;
     case 32: hipLaunchKernelGGL((k_probe_wave<OP, T, 32>), g, b, 0, st, (const T *)in, (T *)out); return true;
     case 64: hipLaunchKernelGGL((k_probe_wave<OP, T, 64>), g, b, 0, st, (const T *)in, (T *)out); return true;
+  }
+  return false;
+}
+template <int C>
+static bool top_items(hipStream_t st, int items, uint64_t *tile_sums, int64_t n_tiles, uint64_t *total_out) {
+  const dim3 g(1), b(256);
+  switch (items) {
+    case 8: hipLaunchKernelGGL((k_probe_top<C, 8>), g, b, 0, st, tile_sums, n_tiles, total_out); return true;
+    case 32: hipLaunchKernelGGL((k_probe_top<C, 32>), g, b, 0, st, tile_sums, n_tiles, total_out); return true;
   }
   return false;
 }
@@ -137,13 +152,20 @@ int brst_copy8(void *st, int type, const void *src, int64_t n, void *dst, uint64
   return finish((hipStream_t)st);
 }
 
-// scan_top_rounds<C, ITEMS> by one block over C arrays of n_tiles sums, in place; total_out (C words) may be null
+// scan_top_rounds<C, ITEMS> by one block over C arrays of n_tiles sums, in place; total_out (C words) may be null;
+// channels: 1 or 3, items: 8 or 32
 int brst_top_rounds(void *st, int channels, int items, uint64_t *tile_sums, int64_t n_tiles, uint64_t *total_out) {
-  const dim3 g(1), b(256);
-  if (channels == 1 && items == 8) hipLaunchKernelGGL((k_probe_top<1, 8>), g, b, 0, (hipStream_t)st, tile_sums, n_tiles, total_out);
-  else if (channels == 3 && items == 8) hipLaunchKernelGGL((k_probe_top<3, 8>), g, b, 0, (hipStream_t)st, tile_sums, n_tiles, total_out);
-  else if (channels == 1 && items == 32) hipLaunchKernelGGL((k_probe_top<1, 32>), g, b, 0, (hipStream_t)st, tile_sums, n_tiles, total_out);
-  else return (int)hipErrorInvalidValue;
+  bool ok = false;
+  if (channels == 1) ok = top_items<1>((hipStream_t)st, items, tile_sums, n_tiles, total_out);
+  else if (channels == 3) ok = top_items<3>((hipStream_t)st, items, tile_sums, n_tiles, total_out);
+  if (!ok) return (int)hipErrorInvalidValue;
+  return finish((hipStream_t)st);
+}
+
+// kth_set_bit64(masks[i], ks[i]) -> out[i] for i < n; every ks[i] is below the population count of masks[i]
+int brst_kth_bit(void *st, const uint64_t *masks, const uint32_t *ks, uint32_t *out, int64_t n) {
+  if (n < 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_kth_bit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)st, masks, ks, out, n);
   return finish((hipStream_t)st);
 }
 

@@ -9,6 +9,7 @@
 //   block_excl_scan_256(v, sh, total)                 exclusive prefix sum over a block of 256 threads
 //   block_bits(o, a, out)                             OR of o and AND of a over a block of 256 threads (the radix sort's digits)
 //   load8 / store8                                    a thread's eight consecutive scan items as 16-byte accesses
+//   kth_set_bit64(mask, k)                            the index of a mask's k-th set bit, without a loop
 //   scan_top_rounds<C, ITEMS>(...)                    a scan's tile sums scanned in place by one block
 #pragma once
 #include <stdint.h>
@@ -123,31 +124,63 @@ __device__ __forceinline__ void store8(T *p, int64_t base, int64_t n, const T v[
   }
 }
 
+// The index of the k-th set bit of mask (k = 0: the lowest), for k < popcount(mask): six fixed steps, each keeping the half
+// whose population count holds k.  Clearing the lowest bit k times made a wave wait for its largest k.
+__device__ __forceinline__ uint32_t kth_set_bit64(uint64_t mask, uint32_t k) {
+  uint32_t w = (uint32_t)mask, r = 0;
+  uint32_t c = (uint32_t)__popc(w);
+  if (k >= c) { k -= c; w = (uint32_t)(mask >> 32); r = 32; }
+  c = (uint32_t)__popc(w & 0xffffu); if (k >= c) { k -= c; w >>= 16; r += 16; }
+  c = (uint32_t)__popc(w & 0xffu); if (k >= c) { k -= c; w >>= 8; r += 8; }
+  c = (uint32_t)__popc(w & 0xfu); if (k >= c) { k -= c; w >>= 4; r += 4; }
+  c = (uint32_t)__popc(w & 3u); if (k >= c) { k -= c; w >>= 2; r += 2; }
+  if (k >= (w & 1u)) r += 1;
+  return r;
+}
+
+// lane 63's v, in every lane of the wave (a scalar)
+__device__ __forceinline__ uint64_t wave_last64(uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
+  return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+
 // The tile sums of a scan, scanned in place by ONE block of 256 threads: C arrays of n_tiles sums, one behind the other,
-// ITEMS consecutive sums per thread and round, the loads of a round in flight together -- one sum per thread and round was
-// a chain of n_tiles / 256 load-scan-store rounds, 30 us for the rows' scan and 80 us for the fused three-value one.
-// total_out[c] = the sum of array c (NULL: not wanted).
+// 256 * ITEMS sums a round.  A wave takes 64 * ITEMS consecutive sums as ITEMS rows of 64: lane l loads and stores word
+// 64 k + l of them, so every access of a wave is one run of 512 bytes, and all of a round's loads are in flight before the
+// first use.  The rows are scanned by wave_scan, one behind the other with a running (scalar) carry; the four waves'
+// totals meet in sh[4].  (ITEMS consecutive sums per thread needed no shuffles but put a wave's lanes ITEMS * 8 bytes
+// apart: 64 cache lines per load and per store instruction; one sum per thread and round before that was a chain of
+// n_tiles / 256 load-scan-store rounds.)  total_out[c] = the sum of array c (NULL: not wanted).
 template <int C, int ITEMS>
 __device__ __forceinline__ void scan_top_rounds(uint64_t *tile_sums, int64_t n_tiles, uint64_t *total_out, uint64_t *sh) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   uint64_t carry[C];
 #pragma unroll
   for (int c = 0; c < C; c++) carry[c] = 0;
   for (int64_t base = 0; base < n_tiles; base += 256 * ITEMS) {
-    const int64_t i0 = base + (int64_t)threadIdx.x * ITEMS;
+    const int64_t i0 = base + (int64_t)w * (64 * ITEMS) + lane;
     uint64_t v[C][ITEMS];
 #pragma unroll
     for (int c = 0; c < C; c++)
 #pragma unroll
-      for (int k = 0; k < ITEMS; k++) v[c][k] = i0 + k < n_tiles ? tile_sums[(int64_t)c * n_tiles + i0 + k] : 0;
+      for (int k = 0; k < ITEMS; k++) v[c][k] = i0 + 64 * k < n_tiles ? tile_sums[(int64_t)c * n_tiles + i0 + 64 * k] : 0;
 #pragma unroll
     for (int c = 0; c < C; c++) {
-      uint64_t sum = 0;
+      uint64_t run = 0;   // the wave's sums before row k
 #pragma unroll
-      for (int k = 0; k < ITEMS; k++) sum += v[c][k];
-      uint64_t tot;
-      uint64_t ex = carry[c] + block_excl_scan_256(sum, sh, tot);
+      for (int k = 0; k < ITEMS; k++) {
+        const uint64_t x = wave_scan(v[c][k]);
+        v[c][k] = run + x - v[c][k];
+        run += wave_last64(x);
+      }
+      if (lane == 0) sh[w] = run;
+      __syncthreads();
+      uint64_t ex = carry[c], tot = 0;
 #pragma unroll
-      for (int k = 0; k < ITEMS; k++) { if (i0 + k < n_tiles) tile_sums[(int64_t)c * n_tiles + i0 + k] = ex; ex += v[c][k]; }
+      for (int i = 0; i < 4; i++) { if (i < w) ex += sh[i]; tot += sh[i]; }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < ITEMS; k++) if (i0 + 64 * k < n_tiles) tile_sums[(int64_t)c * n_tiles + i0 + 64 * k] = ex + v[c][k];
       carry[c] += tot;
     }
   }
