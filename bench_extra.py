@@ -20,6 +20,11 @@
                                          alignments, the classes, the EM -- seconds in add / finish / em, iterations, names, classes,
                                          labels, quantifier peak device bytes per read name; then the same with the fragment-length
                                          model ("eff_len": the adds through br_quant_add_rows), as runs_eff_length
+  python bench_extra.py quant_boot [--reads N] [--bootstraps B] [--boot-chunk W]  the bootstrap replicates on the quant workload, in one
+                                         process: br_quant_em (seconds, iterations, seconds per replicate-iteration), then
+                                         br_quant_bootstrap with B replicates (default 32; W of them together, 0: the library's
+                                         default), sampling and EM seconds apart (br_quant_boot_stats), seconds per
+                                         replicate-iteration and the ratio of the two
   python bench_extra.py coverage [--reads N]  br_coverage over the rows of the bench.py workload (N pairs, default 10 M), projected once
                                          (br_project_batch_device, timed) and resident in HBM: all rows in one add, then finish --
                                          br_coverage_stats' add and finish seconds, rows, bases, runs, peak device bytes per base; the
@@ -46,11 +51,13 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "coverage"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "quant_boot", "coverage"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--bootstraps", type=int, default=32)
+    ap.add_argument("--boot-chunk", type=int, default=0)
     args = ap.parse_args()
     import torch
     from bramble_amd import device as brdev
@@ -155,7 +162,7 @@ def main():
                              "peak_bytes_per_record": round(stt["peak_bytes"] / n_rows, 1)})
         print(json.dumps({"config": "sort", "pairs": n, "records": n_rows, "stream_bytes": n_bytes, "runs": runs}))
         return
-    if args.config == "quant":
+    if args.config in ("quant", "quant_boot"):
         n = args.reads or 10_000_000
         ann = synth.Annotation("G")
         batch = ann.reads(n, "pe")
@@ -177,6 +184,34 @@ def main():
             project.append(round(time.perf_counter() - t0, 4))
         n_rows = int(rows.n_rows)
         cuts = sorted(set(int(np.searchsorted(goff, a, side="left")) for a in range(0, n_aln, 1_000_000)) | {n_groups})   # names whose first alignment opens a slice
+        if args.config == "quant_boot":
+            runs = []
+            for step in range(args.warmup + args.steps):
+                q = lib.Quant(n_tx, lens)
+                q.set_param("bootstraps", args.bootstraps)
+                q.set_param("boot_seed", step)
+                q.set_param("boot_chunk", args.boot_chunk)
+                for g0, g1 in zip(cuts, cuts[1:]):
+                    lib.check(q.add_raw(rows.a, rows.row_off, db["group_off"].data_ptr() + 4 * g0, g1 - g0, True), "br_quant_add")
+                names, classes = q.finish()
+                t0 = time.perf_counter()
+                iters, _ = q.em()
+                t1 = time.perf_counter()
+                boot_iters = q.bootstrap()
+                t2 = time.perf_counter()
+                bs, stt = q.boot_stats(), q.stats()
+                q.close()
+                if step >= args.warmup:
+                    point, boot = (t1 - t0) / max(iters, 1), bs["em_s"] / max(bs["iterations_total"], 1)
+                    runs.append({"em_s": round(t1 - t0, 4), "iterations": iters, "em_us_per_replicate_iteration": round(1e6 * point, 2),
+                                 "bootstrap_s": round(t2 - t1, 4), "boot_sample_s": round(bs["sample_s"], 4), "boot_em_s": round(bs["em_s"], 4),
+                                 "boot_iterations_total": bs["iterations_total"], "boot_iterations_min": int(boot_iters.min()),
+                                 "boot_iterations_max": int(boot_iters.max()), "boot_em_us_per_replicate_iteration": round(1e6 * boot, 2),
+                                 "point_over_boot": round(point / boot, 2) if boot > 0 else None, "names": names, "classes": classes,
+                                 "labels": stt["n_labels"], "peak_bytes": stt["peak_bytes"]})
+            print(json.dumps({"config": "quant_boot", "pairs": n, "alignments": n_aln, "rows": n_rows, "transcripts": n_tx, "bootstraps": args.bootstraps,
+                              "boot_chunk": args.boot_chunk, "runs": runs}))
+            return
         runs, runs_eff = [], []
         for eff_len in (0, 1):   # 1: the fragment-length model, the adds through br_quant_add_rows (the CIGAR references and the pool as well)
             for step in range(args.warmup + args.steps):

@@ -14,6 +14,7 @@
 //                   bundle goes to the writer, and after the last bundle the consumer's pieces take the same way out
 //                   (br_device_bam_download -> writer); the writer notes the blocks it writes for the consumer's index
 #include <ctype.h>
+#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -44,7 +45,8 @@ void usage(FILE *f) {
           " [--device-deflate | --host-deflate | --compression-level 0-9] [--device-reader | --host-reader] [--bundle-size N]\n"
           "               [--device N | --devices a,b,...] [--collate] [--sort [--write-index]]\n"
           "               [--quant <quant.tsv> [--quant-classes <eq_classes.txt>] [--quant-length-norm | --quant-no-length-norm]\n"
-          "                [--quant-eff-length [--quant-fld <fld.tsv>]]]\n"
+          "                [--quant-eff-length [--quant-fld <fld.tsv>]]\n"
+          "                [--quant-bootstraps B [--quant-seed S] [--quant-boot-out <bootstraps.tsv>]]]\n"
           "               [--coverage <cov.bedgraph>] [--coverage-summary <cov.tsv>] [--coverage-primary]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
@@ -66,8 +68,14 @@ void usage(FILE *f) {
           "read name was projected to; both mates count) and per-transcript abundances are estimated from them by EM; FILE gets one line\n"
           "per @SQ transcript: Name, Length, NumReads, TPM, UniqueReads, AmbigReads.  --quant-classes FILE: the classes in the layout of\n"
           "salmon's eq_classes.txt.  Reads are weighted by 1 / transcript length in the short-read preset and not under --lr / --lr-hq;\n"
-          "--quant-length-norm / --quant-no-length-norm say otherwise.  No bias model, no bootstraps.  One more line\n"
+          "--quant-length-norm / --quant-no-length-norm say otherwise.  No bias model.  One more line\n"
           "in front of the final report: [bramble] quantified N read names in C classes ...\n"
+          "--quant-bootstraps B (1 .. 10000): B bootstrap replicates on the GPU: the read names are resampled with replacement (a\n"
+          "counter-based generator, Philox4x32-10 under --quant-seed S, default 0: the same seed gives the same replicates on every\n"
+          "run) and the EM runs on each replicate's counts, sixteen replicates at a time; quant.tsv gains two last columns, BootMean and\n"
+          "BootSD (the replicates' mean and sample standard deviation of NumReads).  --quant-boot-out FILE: one line per @SQ\n"
+          "transcript, Name and the B replicates' NumReads, under the header Name 0 1 ... B-1.  One more line in front of the\n"
+          "quantified line: [bramble] bootstrapped B replicates (seed S, I iterations in all, sampling X.XXs, EM Y.YYs)\n"
           "--quant-eff-length: the fragment lengths of the pairs that project to one transcript alone are counted on the GPU and reads\n"
           "are weighted by 1 / effective length (the transcript's length minus the mean of the observed fragment lengths that fit it,\n"
           "plus 1: salmon's and kallisto's convention); quant.tsv gains an EffectiveLength column behind Length.  It needs length\n"
@@ -136,6 +144,19 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (a == "--quant-no-length-norm") o.quant_length_norm = 0;
     else if (a == "--quant-eff-length") o.quant_eff_length = true;
     else if (a == "--quant-fld") { const char *v = value(); if (!v) return -1; o.quant_fld = v; }
+    else if (a == "--quant-bootstraps") {
+      const char *v = value(); if (!v) return -1;
+      char *e; const long long b = strtoll(v, &e, 10);
+      if (e == v || *e || b < 1 || b > 10000) { fprintf(stderr, "--quant-bootstraps: %s is not a number of replicates from 1 to 10000\n", v); return -1; }
+      o.quant_bootstraps = (int)b;
+    }
+    else if (a == "--quant-seed") {
+      const char *v = value(); if (!v) return -1;
+      char *e; errno = 0; const long long x = strtoll(v, &e, 10);
+      if (e == v || *e || errno) { fprintf(stderr, "--quant-seed: %s is not a 64-bit integer\n", v); return -1; }
+      o.quant_seed = x; o.quant_seed_given = true;
+    }
+    else if (a == "--quant-boot-out") { const char *v = value(); if (!v) return -1; o.quant_boot_out = v; }
     else if (a == "--coverage") { const char *v = value(); if (!v) return -1; o.coverage = v; }
     else if (a == "--coverage-summary") { const char *v = value(); if (!v) return -1; o.coverage_summary = v; }
     else if (a == "--coverage-primary") o.coverage_primary = true;
@@ -160,6 +181,8 @@ int parse_args(int argc, char **argv, Options &o) {
   if (!o.quant.empty() && o.devices.size() > 1) { fprintf(stderr, "--quant works on one device: give --device N, not a --devices list\n"); return -1; }
   if (o.quant.empty() && (!o.quant_classes.empty() || o.quant_length_norm >= 0)) { fprintf(stderr, "--quant-classes, --quant-length-norm and --quant-no-length-norm need --quant\n"); return -1; }
   if (o.quant.empty() && (o.quant_eff_length || !o.quant_fld.empty())) { fprintf(stderr, "--quant-eff-length and --quant-fld need --quant\n"); return -1; }
+  if (o.quant.empty() && (o.quant_bootstraps || o.quant_seed_given || !o.quant_boot_out.empty())) { fprintf(stderr, "--quant-bootstraps, --quant-seed and --quant-boot-out need --quant\n"); return -1; }
+  if (!o.quant_boot_out.empty() && !o.quant_bootstraps) { fprintf(stderr, "--quant-boot-out needs --quant-bootstraps: without it there are no replicates\n"); return -1; }
   if (!o.quant_fld.empty() && !o.quant_eff_length) { fprintf(stderr, "--quant-fld needs --quant-eff-length: without it no fragment lengths are counted\n"); return -1; }
   if (o.quant_eff_length && o.quant_length_norm == 0) { fprintf(stderr, "--quant-eff-length is a length normalisation: not with --quant-no-length-norm\n"); return -1; }
   if (o.quant_eff_length && (o.cfg.lr || o.cfg.lr_hq) && o.quant_length_norm != 1) { fprintf(stderr, "--quant-eff-length under --lr / --lr-hq needs --quant-length-norm: long reads are not length-normalised by default\n"); return -1; }

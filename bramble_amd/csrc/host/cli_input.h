@@ -40,6 +40,10 @@ struct Options {
   int quant_length_norm = -1;    // -1: on for the short-read preset, off under --lr / --lr-hq; --quant-length-norm / --quant-no-length-norm
   bool quant_eff_length = false; // --quant-eff-length: the fragment-length model (br_quant "eff_len"): reads weighted by 1 / effective length
   std::string quant_fld;         // --quant-fld FILE: the observed fragment-length histogram
+  int quant_bootstraps = 0;      // --quant-bootstraps B: bootstrap replicates (br_quant "bootstraps"), 0: none
+  long long quant_seed = 0;      // --quant-seed S: their seed (br_quant "boot_seed")
+  bool quant_seed_given = false;
+  std::string quant_boot_out;    // --quant-boot-out FILE: every replicate's NumReads per transcript
   std::string coverage, coverage_summary;   // --coverage FILE / --coverage-summary FILE: the bedGraph of the depth along every transcript and the per-transcript table (br_coverage)
   bool coverage_primary = false; // --coverage-primary: only primary records count ("primary_only")
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used

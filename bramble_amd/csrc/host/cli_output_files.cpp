@@ -1,6 +1,8 @@
 // SideFile and the text of the five side files (cli_output_files.h).  No call into the library.
 #include "cli_output_files.h"
 
+#include <math.h>
+
 #include <algorithm>
 
 namespace brcli {
@@ -36,13 +38,31 @@ void number_sq(TxTable &tx) {
 }
 
 void write_quant_table(FILE *f, const TxTable &tx, const std::vector<double> *eff, const std::vector<double> &theta, const std::vector<double> &tpm,
-                       const std::vector<uint64_t> &unique, const std::vector<uint64_t> &ambig) {
-  fprintf(f, eff ? "Name\tLength\tEffectiveLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\n" : "Name\tLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\n");
+                       const std::vector<uint64_t> &unique, const std::vector<uint64_t> &ambig, const std::vector<double> *boot_mean,
+                       const std::vector<double> *boot_var) {
+  const bool boot = boot_mean && boot_var;
+  fprintf(f, eff ? "Name\tLength\tEffectiveLength\tNumReads\tTPM\tUniqueReads\tAmbigReads" : "Name\tLength\tNumReads\tTPM\tUniqueReads\tAmbigReads");
+  fprintf(f, boot ? "\tBootMean\tBootSD\n" : "\n");
   for (size_t t = 0; t < tx.len.size(); t++) {
     if (tx.len[t] <= 0) continue;
     fprintf(f, "%s\t%lld", tx.name[t], (long long)tx.len[t]);
     if (eff) fprintf(f, "\t%.3f", (*eff)[t]);
-    fprintf(f, "\t%.6f\t%.6f\t%llu\t%llu\n", theta[t], tpm[t], (unsigned long long)unique[t], (unsigned long long)ambig[t]);
+    fprintf(f, "\t%.6f\t%.6f\t%llu\t%llu", theta[t], tpm[t], (unsigned long long)unique[t], (unsigned long long)ambig[t]);
+    if (boot) fprintf(f, "\t%.6f\t%.6f", (*boot_mean)[t], sqrt((*boot_var)[t]));
+    fputc('\n', f);
+  }
+}
+
+void write_quant_bootstraps(FILE *f, const TxTable &tx, int n_boot, const std::vector<double> &theta) {
+  const size_t n_tx = tx.len.size();
+  fprintf(f, "Name");
+  for (int b = 0; b < n_boot; b++) fprintf(f, "\t%d", b);
+  fputc('\n', f);
+  for (size_t t = 0; t < n_tx; t++) {
+    if (tx.len[t] <= 0) continue;
+    fprintf(f, "%s", tx.name[t]);
+    for (int b = 0; b < n_boot; b++) fprintf(f, "\t%.6f", theta[(size_t)b * n_tx + t]);
+    fputc('\n', f);
   }
 }
 

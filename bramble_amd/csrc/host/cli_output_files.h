@@ -28,9 +28,13 @@ bool settle_all(std::initializer_list<SideFile *> files, bool failed);   // in t
 struct TxTable { std::vector<const char *> name; std::vector<int64_t> len, sq_of; int64_t n_sq = 0; };
 void number_sq(TxTable &tx);   // sq_of and n_sq from len
 
-// eff: the EffectiveLength column behind Length, nullptr without it
+// eff: the EffectiveLength column behind Length, nullptr without it; boot_mean and boot_var: the last columns BootMean and BootSD
+// (the variance's square root), nullptr without them
 void write_quant_table(FILE *f, const TxTable &tx, const std::vector<double> *eff, const std::vector<double> &theta, const std::vector<double> &tpm,
-                       const std::vector<uint64_t> &unique, const std::vector<uint64_t> &ambig);
+                       const std::vector<uint64_t> &unique, const std::vector<uint64_t> &ambig, const std::vector<double> *boot_mean = nullptr,
+                       const std::vector<double> *boot_var = nullptr);
+// the replicates' NumReads (theta: n_boot rows of one value per transcript): Name 0 1 ... n_boot - 1, a line per @SQ transcript
+void write_quant_bootstraps(FILE *f, const TxTable &tx, int n_boot, const std::vector<double> &theta);
 // salmon's eq_classes.txt: the counts, the names, then per class its size, its transcripts' @SQ numbers and its count
 void write_quant_classes(FILE *f, const TxTable &tx, int64_t n_classes, const std::vector<uint64_t> &label_off, const std::vector<uint32_t> &labels,
                          const std::vector<uint64_t> &counts);

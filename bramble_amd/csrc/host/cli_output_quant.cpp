@@ -1,6 +1,7 @@
 // --quant and its switches (cli_output.h): every bundle's rows go to a br_quant (br_quant_add_last; --quant-eff-length: the adds
 // count the fragment lengths as well, "eff_len"); after the last bundle: classes, EM, and everything the three files need in one
-// download each -- the table, --quant-classes, --quant-fld.
+// download each -- the table, --quant-classes, --quant-fld; with --quant-bootstraps the replicates run behind the EM
+// (br_quant_bootstrap) and their summary joins the table, their values --quant-boot-out.
 #include "cli_output.h"
 
 namespace brcli {
@@ -8,7 +9,7 @@ namespace {
 
 class QuantOut : public Consumer {
  public:
-  explicit QuantOut(const RunEnv &e) : Consumer(e, "quantifier", "quantification"), table(e.o.quant), classes(e.o.quant_classes), fld(e.o.quant_fld) {}
+  explicit QuantOut(const RunEnv &e) : Consumer(e, "quantifier", "quantification"), table(e.o.quant), classes(e.o.quant_classes), fld(e.o.quant_fld), boot(e.o.quant_boot_out) {}
   ~QuantOut() override { if (q) br_quant_free(q); }
   int open() {
     const Options &o = env.o;
@@ -16,6 +17,8 @@ class QuantOut : public Consumer {
     const int norm = o.quant_length_norm >= 0 ? o.quant_length_norm : (o.cfg.lr || o.cfg.lr_hq) ? 0 : 1;   // (oarfish does not length-normalise long reads)
     if (!rc) rc = br_quant_set_param(q, "length_norm", norm);
     if (!rc && o.quant_eff_length) rc = br_quant_set_param(q, "eff_len", 1);
+    if (!rc && o.quant_bootstraps) rc = br_quant_set_param(q, "bootstraps", o.quant_bootstraps);
+    if (!rc && o.quant_bootstraps) rc = br_quant_set_param(q, "boot_seed", (int64_t)o.quant_seed);
     return rc;
   }
   int add(br_ctx *ctx) override { return br_quant_add_last(q, ctx); }
@@ -32,6 +35,16 @@ class QuantOut : public Consumer {
       rc = br_quant_eff_lengths(q, eff.data());
       if (!rc) rc = br_quant_fld(q, hist.data(), &fld_obs, &fld_nofrag, &fld_oor);
     }
+    if (const int n_boot = env.o.quant_bootstraps; !rc && n_boot) {
+      rc = br_quant_bootstrap(q, nullptr);
+      boot_mean.resize(nt + 1); boot_var.resize(nt + 1);
+      if (!rc) rc = br_quant_boot_summary(q, boot_mean.data(), boot_var.data());
+      if (!rc && !boot.path.empty()) {
+        boot_theta.resize((size_t)n_boot * nt + 1);
+        rc = br_quant_boot_theta(q, 0, n_boot, boot_theta.data());
+      }
+      if (!rc) rc = br_quant_boot_stats(q, &t_boot_sample, &t_boot_em, &boot_iters);
+    }
     if (!rc && !classes.path.empty()) {
       int64_t n_labels = 0;
       rc = br_quant_stats(q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n_labels);
@@ -42,14 +55,18 @@ class QuantOut : public Consumer {
     return rc;
   }
   bool write_files(brio::BgzfWriter &, const std::vector<br_bgzf_span> &) override {
-    if (FILE *f = table.open()) write_quant_table(f, env.tx, env.o.quant_eff_length ? &eff : nullptr, theta, tpm, unique, ambig);
+    const bool with_boot = env.o.quant_bootstraps > 0;
+    if (FILE *f = table.open()) write_quant_table(f, env.tx, env.o.quant_eff_length ? &eff : nullptr, theta, tpm, unique, ambig, with_boot ? &boot_mean : nullptr,
+                                                  with_boot ? &boot_var : nullptr);
     if (!table.close()) return false;
     if (FILE *f = classes.open()) write_quant_classes(f, env.tx, n_classes, label_off, labels, counts);
     if (!classes.close()) return false;
     if (FILE *f = fld.open()) write_fragment_lengths(f, hist);
-    return fld.close();
+    if (!fld.close()) return false;
+    if (FILE *f = boot.open()) write_quant_bootstraps(f, env.tx, env.o.quant_bootstraps, boot_theta);
+    return boot.close();
   }
-  bool settle(bool failed) override { return settle_all({&table, &classes, &fld}, failed); }
+  bool settle(bool failed) override { return settle_all({&table, &classes, &fld, &boot}, failed); }
   void report() const override {
     if (env.o.quant_eff_length) {
       double sum = 0;
@@ -57,16 +74,20 @@ class QuantOut : public Consumer {
       printf("[bramble] fragment lengths: %llu observed, mean %.1f, %llu unique names without a pair, %llu out of range\n", (unsigned long long)fld_obs,
              fld_obs ? sum / (double)fld_obs : 0.0, (unsigned long long)fld_nofrag, (unsigned long long)fld_oor);
     }
+    if (env.o.quant_bootstraps)
+      printf("[bramble] bootstrapped %d replicates (seed %lld, %lld iterations in all, sampling %.2fs, EM %.2fs)\n", env.o.quant_bootstraps, env.o.quant_seed,
+             (long long)boot_iters, t_boot_sample, t_boot_em);
     printf("[bramble] quantified %lld read names in %lld classes (%d iterations, add %.2fs, classes %.2fs, EM %.2fs)\n", (long long)n_names, (long long)n_classes,
            (int)n_iters, t_add, t_finish, t_em);
   }
  private:
   static constexpr size_t FLD_MAX = 1000;   // br_quant's default "fld_max"
   br_quant *q = nullptr;
-  SideFile table, classes, fld;
+  SideFile table, classes, fld, boot;
   int64_t n_names = 0, n_classes = 0; int32_t n_iters = 0;
   double t_add = 0, t_finish = 0, t_em = 0;
-  std::vector<double> theta, tpm, eff;
+  std::vector<double> theta, tpm, eff, boot_mean, boot_var, boot_theta;   // boot_*: --quant-bootstraps (boot_theta: one row a replicate)
+  double t_boot_sample = 0, t_boot_em = 0; int64_t boot_iters = 0;
   std::vector<uint64_t> unique, ambig, label_off, counts, hist;   // hist, eff: --quant-eff-length
   std::vector<uint32_t> labels;
   uint64_t fld_obs = 0, fld_nofrag = 0, fld_oor = 0;

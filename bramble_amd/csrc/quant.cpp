@@ -18,6 +18,13 @@
 //   em       per iteration a class kernel (q_c = n_c / sum over its labels of theta_t w_t) and a transcript kernel (theta'_t =
 //            theta_t w_t * sum of q_c over the transcript's classes, gathered through the transposed table); every 16th iteration
 //            and the last the transcript kernel also leaves the largest relative change in one word, which the host reads
+//   bootstrap B replicates in chunks of W (16 by default): a chunk's class counts are resampled when it starts (a lane a draw:
+//            Philox4x32-10 by (draw, replicate), a binary search in the scanned counts, an integer atomicAdd) and its EMs run
+//            together, replicate innermost in theta, theta w, q and the counts, so an index is read once for W replicates and a
+//            gather is W * 8 contiguous bytes; per replicate the sums have the point kernels' shape, so its bits are a point EM's.
+//            The host reads W relative changes at every look and clears the bit of a replicate that stops: its theta is copied
+//            through from then on.  The chunk ends when all have stopped; its theta go to the B x T result, which a last
+//            kernel reduces to mean and variance per transcript
 //
 // Device memory (N names, of them M with labels; R rows added; C classes; L labels over all classes; T transcripts):
 //   while adding   4 R (the arena: a slot per row) + 20 N (offset, k, hash) + 4 bytes a name of the largest add (the list of its
@@ -32,6 +39,10 @@
 //   "eff_len"      adds 16 (fld_max + 1 + 3) from the first add on (the histogram and its three counters, the run's and the add's
 //                  own), 8 per row and 4 per pool word of a host add's CIGAR copies while it runs, 16 (fld_max + 1) for the
 //                  prefixes during finish, and 8 T for eff from finish on (w, 8 T of the EM's 40, is held from finish on as well)
+//   bootstrap      ("bootstraps" = B) holds 8 B T (the result, replicate-major) + 8 C (cum) + 8 T (w, if the EM has not made it);
+//                  while it runs, for a chunk of W replicates, 32 W T (theta and theta w twice) + 12 W C (q 8, the resampled
+//                  counts 4) + 512 bytes (the relative changes); br_quant_boot_counts 4 C a replicate of up to 16 at a time, the
+//                  summary 16 T
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -77,6 +88,14 @@ struct br_quant : Accum {
   }
   int cur = 0;
   ColBuf tmp, small;
+  // bootstrap replicates: the parameters, the B x T result (replicate-major) and cum (C + 1), both held from br_quant_bootstrap on
+  int64_t bootstraps = 0, boot_chunk = 0;
+  uint64_t boot_seed = 0;
+  bool boot_done = false;
+  uint64_t boot_n = 0;         // cum[C]: the names with labels
+  double boot_sample_s = 0, boot_em_s = 0;
+  int64_t boot_iters = 0;
+  ColBuf boot_res, boot_cum;
 };
 // words of `small`
 enum { QS_BITS = 0, QS_COLL = 2, QS_SPAN = 3, QS_NBIG = 5, QS_MAXTID = 6, QS_BAD = 7, QS_REL = 8, QS_NBIG_CLS = 9, QS_NBIG_TX = 10, QS_WORDS = 16 };
@@ -103,7 +122,12 @@ extern "C" int br_quant_new(int device, int64_t n_transcripts, const int64_t *le
 }
 
 extern "C" int br_quant_set_param(br_quant *c, const char *name, int64_t value) {
-  if (!c || !name || c->finished) return BR_ERR_INVALID_ARG;
+  if (!c || !name) return BR_ERR_INVALID_ARG;
+  // the replicates' parameters: until br_quant_bootstrap has run, after finish as well
+  if (!strcmp(name, "bootstraps")) { if (value < 0 || value > 10000 || c->boot_done) return BR_ERR_INVALID_ARG; c->bootstraps = value; return BR_OK; }
+  if (!strcmp(name, "boot_seed")) { if (c->boot_done) return BR_ERR_INVALID_ARG; c->boot_seed = (uint64_t)value; return BR_OK; }
+  if (!strcmp(name, "boot_chunk")) { if (value < 0 || value > 64 || c->boot_done) return BR_ERR_INVALID_ARG; c->boot_chunk = value; return BR_OK; }
+  if (c->finished) return BR_ERR_INVALID_ARG;
   if (!strcmp(name, "hash_bits")) { if (value < 1 || value > 64) return BR_ERR_INVALID_ARG; c->hash_bits = (int)value; return BR_OK; }
   if (!strcmp(name, "length_norm")) { if (value != 0 && value != 1) return BR_ERR_INVALID_ARG; c->length_norm = (int)value; return BR_OK; }
   // what the adds already counted depends on these two, and the histogram's tables are sized by fld_max when the first add that
@@ -498,6 +522,154 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
   c->em_s = timer.seconds();
   if (n_iters) *n_iters = (int32_t)it;
   if (rel_change) *rel_change = rel;
+  return BR_OK;
+}
+
+// ---- bootstrap replicates (the definitions: bramble_amd.h, br_quant) ---------------------------------------------------------------
+// cum: the exclusive prefix sums of the classes' counts, cum[C] = the names with labels
+static int quant_boot_cum(br_quant *c) {
+  if (c->boot_cum.p) return BR_OK;
+  hipStream_t st = c->st;
+  const int64_t C = c->n_cls;
+  RC(c->alloc(c->boot_cum, (size_t)(C + 1) * 8));
+  c->boot_n = 0;
+  if (C == 0) return BR_OK;
+  RC(quant_tmp(c, C));
+  HIPCHK(hipMemcpyAsync(c->boot_cum.p, c->c_cnt.p, (size_t)C * 8, hipMemcpyDeviceToDevice, st));
+  launch_scan(st, c->boot_cum.as<uint64_t>(), C, c->tmp.as<uint64_t>());
+  HIPCHK(hipMemcpyAsync(&c->boot_n, c->boot_cum.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return BR_OK;
+}
+static bool quant_boot_ready(const br_quant *c) {
+  if (!c || !c->finished || c->bootstraps == 0) return false;
+  return !(c->eff_len && (!c->length_norm || c->lens.empty()));   // (what br_quant_em refuses)
+}
+
+extern "C" int br_quant_bootstrap(br_quant *c, int32_t *n_iters) {
+  if (!quant_boot_ready(c)) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  const int64_t T = c->n_tx, C = c->n_cls, B = c->bootstraps;
+  // replicates a chunk, and the power of two that holds them: the layout's W
+  const int per = (int)std::min<int64_t>(c->boot_chunk ? c->boot_chunk : (int64_t)Q_BOOT_CHUNK, B);
+  int lw = 0;
+  while ((1 << lw) < per) lw++;
+  const size_t W = (size_t)1 << lw;
+  c->boot_sample_s = c->boot_em_s = 0; c->boot_iters = 0;
+  if (!c->eff_len) {   // w as br_quant_em makes it (with "eff_len" it is on the device since finish)
+    std::vector<double> w((size_t)T);
+    for (int64_t t = 0; t < T; t++) w[(size_t)t] = quant_weight(c, t);
+    RC(c->alloc(c->w, ((size_t)T + 1) * 8));
+    if (T) HIPCHK(hipMemcpyAsync(c->w.p, w.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));   // (w goes)
+  }
+  RC(quant_boot_cum(c));
+  RC(c->alloc(c->boot_res, ((size_t)B * (size_t)T + 1) * 8));
+  ColBuf th[2], xx[2], q, cnt, d_rel;
+  DropGuard chunk_bufs{c, {&th[0], &th[1], &xx[0], &xx[1], &q, &cnt, &d_rel}};
+  for (int k = 0; k < 2; k++) { RC(c->alloc(th[k], ((size_t)T * W + 1) * 8)); RC(c->alloc(xx[k], ((size_t)T * W + 1) * 8)); }
+  RC(c->alloc(q, ((size_t)C * W + 1) * 8)); RC(c->alloc(cnt, ((size_t)C * W + 1) * 4)); RC(c->alloc(d_rel, 64 * 8));
+  QBootArgs A{};
+  QEmArgs &E = A.E;
+  E.n_cls = C; E.n_tx = T; E.label_off = c->c_loff.as<uint64_t>(); E.labels = c->c_labels.as<uint32_t>(); E.cnt = nullptr;
+  E.t_off = c->t_off.as<uint64_t>(); E.t_cls = c->t_cls.as<uint32_t>();
+  E.big_cls = c->big_cls.as<uint32_t>(); E.n_big_cls = c->n_big_cls; E.big_tx = c->big_tx.as<uint32_t>(); E.n_big_tx = c->n_big_tx;
+  E.w = c->w.as<double>(); E.q = q.as<double>();
+  A.cnt = cnt.as<uint32_t>(); A.lw = lw;
+  unsigned long long *rel = d_rel.as<unsigned long long>();
+  uint64_t bits[64];
+  for (int64_t b0 = 0; b0 < B; b0 += per) {
+    const int n_rep = (int)std::min<int64_t>(per, B - b0);
+    {
+      ScopeTimer timer(&c->boot_sample_s);
+      HIPCHK(hipMemsetAsync(cnt.p, 0, ((size_t)C * W + 1) * 4, st));
+      launch_q_boot_sample(st, c->boot_cum.as<uint64_t>(), C, c->boot_n, c->boot_seed, (uint32_t)b0, (uint32_t)n_rep, cnt.as<uint32_t>(), (int64_t)W, 1);
+      HIPCHK(hipStreamSynchronize(st));
+    }
+    ScopeTimer timer(&c->boot_em_s);
+    launch_q_boot_init(st, c->w.as<double>(), T, lw, th[0].as<double>(), xx[0].as<double>());
+    A.active = n_rep >= 64 ? ~0ull : (1ull << n_rep) - 1ull;
+    int cur = 0;
+    int64_t it = 0;
+    while (A.active && it < c->max_iters) {
+      it++;
+      const bool look = it % 16 == 0 || it == c->max_iters;
+      if (look) HIPCHK(hipMemsetAsync(rel, 0, W * 8, st));
+      launch_q_boot_classes(st, A, xx[cur].as<double>());
+      launch_q_boot_tx(st, A, th[cur].as<double>(), xx[cur].as<double>(), th[cur ^ 1].as<double>(), xx[cur ^ 1].as<double>(), look ? rel : nullptr);
+      cur ^= 1;
+      if (!look) continue;
+      HIPCHK(hipMemcpyAsync(bits, rel, W * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (int j = 0; j < n_rep; j++) {
+        if (!((A.active >> j) & 1ull)) continue;
+        double r;
+        memcpy(&r, &bits[j], 8);
+        if (r < c->tolerance || it == c->max_iters) {   // frozen at this iteration's theta
+          A.active &= ~(1ull << j);
+          c->boot_iters += it;
+          if (n_iters) n_iters[b0 + j] = (int32_t)it;
+        }
+      }
+    }
+    launch_q_boot_store(st, th[cur].as<double>(), T, lw, n_rep, c->boot_res.as<double>() + (size_t)b0 * (size_t)T);
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  c->boot_done = true;   // the result is there, and the parameters are fixed from here on
+  return BR_OK;
+}
+
+extern "C" int br_quant_boot_counts(br_quant *c, int32_t first, int32_t count, uint32_t *counts) {
+  if (!c || !c->finished || c->bootstraps == 0 || first < 0 || count < 0 || (int64_t)first + count > c->bootstraps || (count && !counts)) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  const int64_t C = c->n_cls;
+  RC(quant_boot_cum(c));
+  if (C == 0 || count == 0) return BR_OK;
+  const int32_t piece = std::min<int32_t>(count, Q_BOOT_CHUNK);
+  ColBuf rows;
+  DropGuard dropper{c, {&rows}};
+  RC(c->alloc(rows, (size_t)piece * (size_t)C * 4));
+  for (int32_t k = 0; k < count; k += piece) {
+    const int32_t n = std::min<int32_t>(piece, count - k);
+    HIPCHK(hipMemsetAsync(rows.p, 0, (size_t)n * (size_t)C * 4, st));
+    launch_q_boot_sample(st, c->boot_cum.as<uint64_t>(), C, c->boot_n, c->boot_seed, (uint32_t)(first + k), (uint32_t)n, rows.as<uint32_t>(), 1, C);
+    HIPCHK(hipMemcpyAsync(counts + (size_t)k * (size_t)C, rows.p, (size_t)n * (size_t)C * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  return BR_OK;
+}
+
+extern "C" int br_quant_boot_theta(br_quant *c, int32_t first, int32_t count, double *theta) {
+  if (!c || !c->boot_done || !c->boot_res.p || first < 0 || count < 0 || (int64_t)first + count > c->bootstraps || (count && !theta)) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t T = (size_t)c->n_tx;
+  if (T && count) HIPCHK(hipMemcpyAsync(theta, c->boot_res.as<double>() + (size_t)first * T, (size_t)count * T * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return BR_OK;
+}
+
+extern "C" int br_quant_boot_summary(br_quant *c, double *mean, double *var) {
+  if (!c || !c->boot_done || !c->boot_res.p) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  const size_t T = (size_t)c->n_tx;
+  ColBuf mv;   // mean, then var
+  DropGuard dropper{c, {&mv}};
+  RC(c->alloc(mv, (2 * T + 1) * 8));
+  launch_q_boot_summary(st, c->boot_res.as<double>(), (int64_t)T, (int32_t)c->bootstraps, mv.as<double>(), mv.as<double>() + T);
+  if (mean && T) HIPCHK(hipMemcpyAsync(mean, mv.p, T * 8, hipMemcpyDeviceToHost, st));
+  if (var && T) HIPCHK(hipMemcpyAsync(var, mv.as<double>() + T, T * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return BR_OK;
+}
+
+extern "C" int br_quant_boot_stats(const br_quant *c, double *sample_seconds, double *em_seconds, int64_t *iterations_total) {
+  if (!c) return BR_ERR_INVALID_ARG;
+  if (sample_seconds) *sample_seconds = c->boot_sample_s;
+  if (em_seconds) *em_seconds = c->boot_em_s;
+  if (iterations_total) *iterations_total = c->boot_iters;
   return BR_OK;
 }
 

@@ -91,4 +91,29 @@ void launch_q_em_classes(hipStream_t st, const QEmArgs &E, const double *x);
 void launch_q_em_tx(hipStream_t st, const QEmArgs &E, const double *theta, const double *x, double *theta_out, double *x_out,
                     unsigned long long *rel);
 
+// Bootstrap replicates (definitions: bramble_amd.h, br_quant).  A chunk is W = 1 << lw replicates (W <= 64) that run together:
+// theta, x (n_tx * W), q and the resampled counts (n_cls * W) hold replicate j of item i at [i * W + j].
+constexpr int Q_BOOT_CHUNK = 16;   // the default W: a gather of 16 doubles is one 128-byte line
+struct QBootArgs {
+  QEmArgs E;             // the tables of the point EM (cnt is not read); q: n_cls * W
+  const uint32_t *cnt;   // the resampled counts, n_cls * W
+  int lw;
+  uint64_t active;       // bit j: replicate j of the chunk still runs; a frozen one's theta and x are copied through
+};
+// the resampled counts of replicates b_first .. b_first + n_rep - 1: one lane a draw (Philox4x32-10 under `seed`, counter (draw,
+// replicate), rank = high half of u * n, class by binary search in cum, the exclusive prefix sums of the counts with cum[n_cls] = n),
+// one integer atomicAdd each into out[c * stride_c + (b - b_first) * stride_b], which the caller has zeroed
+void launch_q_boot_sample(hipStream_t st, const uint64_t *cum, int64_t n_cls, uint64_t n, uint64_t seed, uint32_t b_first, uint32_t n_rep,
+                          uint32_t *out, int64_t stride_c, int64_t stride_b);
+// theta = 1, x = w for every replicate of the chunk
+void launch_q_boot_init(hipStream_t st, const double *w, int64_t n_tx, int lw, double *theta, double *x);
+// launch_q_em_classes / launch_q_em_tx over the chunk; rel != NULL: W words, one per replicate
+void launch_q_boot_classes(hipStream_t st, const QBootArgs &B, const double *x);
+void launch_q_boot_tx(hipStream_t st, const QBootArgs &B, const double *theta, const double *x, double *theta_out, double *x_out,
+                      unsigned long long *rel);
+// out[j * n_tx + t] = theta[t * W + j] for j < n_rep
+void launch_q_boot_store(hipStream_t st, const double *theta, int64_t n_tx, int lw, int n_rep, double *out);
+// mean and variance (over n_boot - 1; 0 for n_boot = 1) per transcript of the n_boot x n_tx result, summed in replicate order
+void launch_q_boot_summary(hipStream_t st, const double *res, int64_t n_tx, int32_t n_boot, double *mean, double *var);
+
 }  // namespace br

@@ -9,6 +9,9 @@
 //   table    radix passes over (transcript, label entry) + k_q_transpose: per transcript its classes, ascending; k_q_bin;
 //            k_q_counts: unique / ambiguous names per transcript
 //   EM       k_q_em_classes / k_q_em_tx, a lane per item of up to Q_WAVE_ITEMS entries and a wave per larger one
+//   bootstrap  k_q_boot_sample (a lane per draw: Philox4x32-10, a binary search in the scanned counts, an integer atomicAdd);
+//            k_q_boot_classes / k_q_boot_tx, the EM over a chunk of W replicates with the replicate innermost, a lane per (item,
+//            replicate) and a wave per larger item; k_q_boot_store, k_q_boot_summary
 //   lengths  ("eff_len") k_q_frag / k_q_frag_big behind the names of an add: per read name of one label the length of its first
 //            fragment, counted in LDS by integer atomics and flushed to the add's own table with one integer atomicAdd per
 //            non-zero bin and block; k_q_fld_commit adds a good add's table to the run's; at finish k_q_fld_prefix (C and S) and
@@ -526,6 +529,190 @@ __global__ void __launch_bounds__(256) k_q_em_tx(QEmArgs E, const double *theta,
     r = wave_max(r);
     if ((threadIdx.x & 63) == 0 && r) atomicMax(rel, (unsigned long long)r);
   }
+}
+
+// ---- bootstrap replicates (the definitions: bramble_amd.h, br_quant) -------------------------------------------------------------
+// A chunk is W = 1 << lw replicates; x, theta, q and the resampled counts hold replicate j of item i at [i * W + j], so one read of
+// an index table serves W replicates and a gather is W * 8 contiguous bytes.  Per replicate every sum has the point kernels'
+// shape -- a lane's ascending loop, or lane l's entries l, l + 64, ... and the xor tree -- so a replicate's bits are those of
+// a point EM on its counts.  A replicate whose bit in `active` is clear is frozen: its theta and x are copied through.
+namespace {
+// Philox4x32-10 of counter (c0, c1, c2, 0) under key (k0, k1): the first two output words as one 64-bit number
+__device__ __forceinline__ uint64_t philox_u64(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t k0, uint32_t k1) {
+  uint32_t c3 = 0;
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0, hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return (uint64_t)c0 | ((uint64_t)c1 << 32);
+}
+}  // namespace
+
+// one lane per draw; blockIdx.y: the replicate of the launch.  The count of class c and replicate y is out[c * stride_c + y * stride_b]
+__global__ void __launch_bounds__(256) k_q_boot_sample(const uint64_t *cum, int64_t n_cls, uint64_t n, uint32_t k0, uint32_t k1, uint32_t b_first,
+                                                       uint32_t *out, int64_t stride_c, int64_t stride_b) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t u = philox_u64((uint32_t)i, (uint32_t)(i >> 32), b_first + blockIdx.y, k0, k1);
+  const uint64_t r = __umul64hi(u, n);   // < n = cum[n_cls]
+  int64_t lo = 0, hi = n_cls;            // the last class c with cum[c] <= r (cum[0] = 0: there is one)
+  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (cum[mid] <= r) lo = mid + 1; else hi = mid; }
+  atomicAdd(out + (lo - 1) * stride_c + (int64_t)blockIdx.y * stride_b, 1u);
+}
+
+__global__ void __launch_bounds__(256) k_q_boot_init(const double *w, int64_t n_tx, int lw, double *theta, double *x) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if ((g >> lw) >= n_tx) return;
+  theta[g] = 1.0; x[g] = w[g >> lw];
+}
+
+constexpr int Q_BOOT_SUB = 4;   // replicates a wave carries through one walk over a large item's entries
+
+template <bool BIG>
+__global__ void __launch_bounds__(256) k_q_boot_classes(QBootArgs B, const double *x) {
+  const QEmArgs &E = B.E;
+  const int lw = B.lw, W = 1 << lw;
+  if (BIG) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= E.n_big_cls) return;
+    const uint64_t c = E.big_cls[i];
+    const uint64_t e0 = E.label_off[c], e1 = E.label_off[c + 1];
+    for (int j0 = 0; j0 < W; j0 += Q_BOOT_SUB) {
+      if (((B.active >> j0) & ((1ull << Q_BOOT_SUB) - 1ull)) == 0) continue;
+      double d[Q_BOOT_SUB];
+#pragma unroll
+      for (int k = 0; k < Q_BOOT_SUB; k++) d[k] = 0.0;
+      for (uint64_t e = e0 + (uint64_t)lane; e < e1; e += 64) {
+        const double *p = x + (((uint64_t)E.labels[e] << lw) + (uint64_t)j0);
+#pragma unroll
+        for (int k = 0; k < Q_BOOT_SUB; k++) if (j0 + k < W) d[k] += p[k];
+      }
+#pragma unroll
+      for (int k = 0; k < Q_BOOT_SUB; k++) {
+        const double s = wave_sum(d[k]);
+        if (lane == 0 && j0 + k < W && ((B.active >> (j0 + k)) & 1ull)) {
+          const uint64_t g = (c << lw) + (uint64_t)(j0 + k);
+          E.q[g] = s > 0.0 ? (double)B.cnt[g] / s : 0.0;
+        }
+      }
+    }
+  } else {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t c = g >> lw;
+    const int j = (int)(g & (int64_t)(W - 1));
+    if (c >= E.n_cls || !((B.active >> j) & 1ull)) return;
+    const uint64_t b = E.label_off[c], e1 = E.label_off[c + 1];
+    if (e1 - b > (uint64_t)Q_WAVE_ITEMS) return;
+    double d = 0.0;
+    for (uint64_t e = b; e < e1; e++) d += x[((uint64_t)E.labels[e] << lw) + (uint64_t)j];
+    E.q[g] = d > 0.0 ? (double)B.cnt[g] / d : 0.0;
+  }
+}
+
+// rel != NULL: rel[j] takes the largest relative change of replicate j (atomicMax on the bits, as the point kernel's one word)
+template <bool BIG>
+__global__ void __launch_bounds__(256) k_q_boot_tx(QBootArgs B, const double *theta, const double *x, double *theta_out, double *x_out,
+                                                   unsigned long long *rel) {
+  const QEmArgs &E = B.E;
+  const int lw = B.lw, W = 1 << lw;
+  const int lane = threadIdx.x & 63;
+  if (BIG) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= E.n_big_tx) return;   // (wave-uniform)
+    const uint64_t t = E.big_tx[i];
+    const uint64_t p0 = E.t_off[t], p1 = E.t_off[t + 1];
+    for (int j0 = 0; j0 < W; j0 += Q_BOOT_SUB) {
+      if (((B.active >> j0) & ((1ull << Q_BOOT_SUB) - 1ull)) == 0) continue;
+      double s[Q_BOOT_SUB];
+#pragma unroll
+      for (int k = 0; k < Q_BOOT_SUB; k++) s[k] = 0.0;
+      for (uint64_t p = p0 + (uint64_t)lane; p < p1; p += 64) {
+        const double *qp = E.q + (((uint64_t)E.t_cls[p] << lw) + (uint64_t)j0);
+#pragma unroll
+        for (int k = 0; k < Q_BOOT_SUB; k++) if (j0 + k < W) s[k] += qp[k];
+      }
+#pragma unroll
+      for (int k = 0; k < Q_BOOT_SUB; k++) {
+        const double sum = wave_sum(s[k]);
+        if (lane == 0 && j0 + k < W && ((B.active >> (j0 + k)) & 1ull)) {
+          const uint64_t g = (t << lw) + (uint64_t)(j0 + k);
+          const double now = x[g] * sum;
+          theta_out[g] = now; x_out[g] = now * E.w[t];
+          if (rel) { const uint64_t r = rel_bits(now, theta[g]); if (r) atomicMax(rel + j0 + k, (unsigned long long)r); }
+        }
+      }
+    }
+    if (lane < W && !((B.active >> lane) & 1ull)) {   // the frozen ones
+      const uint64_t g = (t << lw) + (uint64_t)lane;
+      theta_out[g] = theta[g]; x_out[g] = x[g];
+    }
+  } else {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t t = g >> lw;
+    const int j = (int)(g & (int64_t)(W - 1));
+    uint64_t r = 0;
+    if (t < E.n_tx && E.t_off[t + 1] - E.t_off[t] <= (uint64_t)Q_WAVE_ITEMS) {
+      if ((B.active >> j) & 1ull) {
+        double s = 0.0;
+        for (uint64_t p = E.t_off[t]; p < E.t_off[t + 1]; p++) s += E.q[((uint64_t)E.t_cls[p] << lw) + (uint64_t)j];
+        const double now = x[g] * s;
+        theta_out[g] = now; x_out[g] = now * E.w[t];
+        if (rel) r = rel_bits(now, theta[g]);
+      } else { theta_out[g] = theta[g]; x_out[g] = x[g]; }
+    }
+    if (rel) {   // lanes l, l + W, ... of a wave hold replicate l: a xor tree over those, then one atomicMax a wave and replicate
+      for (int d = 32; d >= W; d >>= 1) { const uint64_t y = __shfl_xor(r, d); r = y > r ? y : r; }
+      if (lane < W && r) atomicMax(rel + lane, (unsigned long long)r);
+    }
+  }
+}
+
+// the chunk's theta (replicate innermost) -> the rows of its first n_rep replicates in the result (replicate-major)
+__global__ void __launch_bounds__(256) k_q_boot_store(const double *theta, int64_t n_tx, int lw, int n_rep, double *out) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t t = g >> lw;
+  const int j = (int)(g & (int64_t)((1 << lw) - 1));
+  if (t < n_tx && j < n_rep) out[(int64_t)j * n_tx + t] = theta[g];
+}
+
+// one lane per transcript over the n_boot x n_tx result, both sums in replicate order (built with -ffp-contract=off: no fused multiply-add)
+__global__ void __launch_bounds__(256) k_q_boot_summary(const double *res, int64_t n_tx, int32_t n_boot, double *mean, double *var) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_tx) return;
+  double s = 0.0;
+  for (int32_t b = 0; b < n_boot; b++) s += res[(int64_t)b * n_tx + t];
+  const double m = s / (double)n_boot;
+  double v = 0.0;
+  for (int32_t b = 0; b < n_boot; b++) { const double d = res[(int64_t)b * n_tx + t] - m; v = __dadd_rn(v, __dmul_rn(d, d)); }
+  mean[t] = m; var[t] = n_boot > 1 ? v / (double)(n_boot - 1) : 0.0;
+}
+
+void launch_q_boot_sample(hipStream_t st, const uint64_t *cum, int64_t n_cls, uint64_t n, uint64_t seed, uint32_t b_first, uint32_t n_rep,
+                          uint32_t *out, int64_t stride_c, int64_t stride_b) {
+  if (n == 0 || n_cls <= 0 || n_rep == 0) return;
+  hipLaunchKernelGGL(k_q_boot_sample, dim3(blocks256((int64_t)n), n_rep), dim3(256), 0, st, cum, n_cls, n, (uint32_t)seed, (uint32_t)(seed >> 32),
+                     b_first, out, stride_c, stride_b);
+}
+void launch_q_boot_init(hipStream_t st, const double *w, int64_t n_tx, int lw, double *theta, double *x) {
+  if (n_tx > 0) hipLaunchKernelGGL(k_q_boot_init, dim3(blocks256(n_tx << lw)), dim3(256), 0, st, w, n_tx, lw, theta, x);
+}
+void launch_q_boot_classes(hipStream_t st, const QBootArgs &B, const double *x) {
+  if (B.E.n_cls > 0) hipLaunchKernelGGL(k_q_boot_classes<false>, dim3(blocks256(B.E.n_cls << B.lw)), dim3(256), 0, st, B, x);
+  if (B.E.n_big_cls) hipLaunchKernelGGL(k_q_boot_classes<true>, dim3((B.E.n_big_cls + 3) / 4), dim3(256), 0, st, B, x);
+}
+void launch_q_boot_tx(hipStream_t st, const QBootArgs &B, const double *theta, const double *x, double *theta_out, double *x_out,
+                      unsigned long long *rel) {
+  if (B.E.n_tx > 0) hipLaunchKernelGGL(k_q_boot_tx<false>, dim3(blocks256(B.E.n_tx << B.lw)), dim3(256), 0, st, B, theta, x, theta_out, x_out, rel);
+  if (B.E.n_big_tx) hipLaunchKernelGGL(k_q_boot_tx<true>, dim3((B.E.n_big_tx + 3) / 4), dim3(256), 0, st, B, theta, x, theta_out, x_out, rel);
+}
+void launch_q_boot_store(hipStream_t st, const double *theta, int64_t n_tx, int lw, int n_rep, double *out) {
+  if (n_tx > 0 && n_rep > 0) hipLaunchKernelGGL(k_q_boot_store, dim3(blocks256(n_tx << lw)), dim3(256), 0, st, theta, n_tx, lw, n_rep, out);
+}
+void launch_q_boot_summary(hipStream_t st, const double *res, int64_t n_tx, int32_t n_boot, double *mean, double *var) {
+  if (n_tx > 0) hipLaunchKernelGGL(k_q_boot_summary, dim3(blocks256(n_tx)), dim3(256), 0, st, res, n_tx, n_boot, mean, var);
 }
 
 void launch_q_span(hipStream_t st, const uint64_t *row_off, const uint32_t *group_off, int64_t n_groups, uint64_t *span) {

@@ -178,6 +178,7 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_sorter_index", "br_sorter_free", "br_ctx_last_device_bam", "br_device_bam_download",
            "br_quant_new", "br_quant_set_param", "br_quant_set_tolerance", "br_quant_add", "br_quant_add_rows", "br_quant_add_last", "br_quant_finish",
            "br_quant_classes", "br_quant_em", "br_quant_result", "br_quant_fld", "br_quant_eff_lengths", "br_quant_stats", "br_quant_free",
+           "br_quant_bootstrap", "br_quant_boot_counts", "br_quant_boot_theta", "br_quant_boot_summary", "br_quant_boot_stats",
            "br_coverage_new", "br_coverage_set_param", "br_coverage_add_rows", "br_coverage_add_last", "br_coverage_finish", "br_coverage_runs",
            "br_coverage_depth", "br_coverage_summary", "br_coverage_stats", "br_coverage_free",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
@@ -1176,12 +1177,16 @@ class Quant(_Accumulator):
                 "finish": [C.c_void_p, _P(C.c_int64), _P(C.c_int64)], "classes": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                 "em": [C.c_void_p, _P(C.c_int32), _P(C.c_double)], "result": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                 "stats": [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_uint64),
-                          _P(C.c_int64), _P(C.c_int64)], "free": [C.c_void_p]}
+                          _P(C.c_int64), _P(C.c_int64)], "free": [C.c_void_p],
+                "bootstrap": [C.c_void_p, C.c_void_p], "boot_counts": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
+                "boot_theta": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p], "boot_summary": [C.c_void_p, C.c_void_p, C.c_void_p],
+                "boot_stats": [C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_int64)]}
 
     def __init__(self, n_transcripts, lengths=None, device=0):
         self.n_transcripts = int(n_transcripts)
         self.n_names = self.n_classes = 0
         self.fld_max = 1000
+        self.bootstraps = 0
         lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64)
         assert lens is None or lens.size == self.n_transcripts
         self._open(device, self.n_transcripts, lens.ctypes.data if lens is not None else None)
@@ -1189,13 +1194,18 @@ class Quant(_Accumulator):
             self.set_param("length_norm", 0)
 
     def set_param(self, name, value):
-        """"hash_bits", "length_norm", "max_iters", "eff_len", "fld_max" (integers) or "tolerance" (a float)."""
+        """"hash_bits", "length_norm", "max_iters", "eff_len", "fld_max", "bootstraps", "boot_seed" (the bits of an int64: a seed
+        of 2^63 or more is taken modulo 2^64), "boot_chunk" (integers) or "tolerance" (a float)."""
         if name == "tolerance":
             self._call("set_tolerance", float(value))
         else:
+            if name == "boot_seed":
+                value = C.c_int64(int(value) & 0xffffffffffffffff).value
             super().set_param(name, value)
             if name == "fld_max":
                 self.fld_max = int(value)
+            if name == "bootstraps":
+                self.bootstraps = int(value)
 
     def add_raw(self, a, row_off, group_off, n_groups, on_device, stream=None):
         """br_quant_add as it is: the return code (0, or a BR_ERR_* value)."""
@@ -1280,6 +1290,37 @@ class Quant(_Accumulator):
         self._call("result", out["theta"].ctypes.data if em else None, out["tpm"].ctypes.data if em else None, out["unique"].ctypes.data,
                    out["ambig"].ctypes.data)
         return {k: v[:self.n_transcripts] for k, v in out.items()}
+
+    def bootstrap(self):
+        """The "bootstraps" replicates: resampled counts and an EM each -> the iterations every replicate ran (int32 [B])"""
+        it = np.zeros(max(self.bootstraps, 1), dtype=np.int32)
+        self._call("bootstrap", it.ctypes.data)
+        return it[:self.bootstraps]
+
+    def boot_counts(self, first=0, count=None):
+        """-> uint32 [count, C]: the resampled class counts of replicates first .. first + count - 1, generated again"""
+        count = self.bootstraps - first if count is None else count
+        out = np.zeros(max(count * self.n_classes, 1), dtype=np.uint32)
+        self._call("boot_counts", first, count, out.ctypes.data)
+        return out[:count * self.n_classes].reshape(count, self.n_classes)
+
+    def boot_theta(self, first=0, count=None):
+        """-> float64 [count, T]: theta of replicates first .. first + count - 1 (after bootstrap)"""
+        count = self.bootstraps - first if count is None else count
+        out = np.zeros(max(count * self.n_transcripts, 1), dtype=np.float64)
+        self._call("boot_theta", first, count, out.ctypes.data)
+        return out[:count * self.n_transcripts].reshape(count, self.n_transcripts)
+
+    def boot_summary(self):
+        """-> (mean, var) per transcript over the replicates (var over B - 1; 0 for B = 1)"""
+        mean, var = np.zeros(max(self.n_transcripts, 1), dtype=np.float64), np.zeros(max(self.n_transcripts, 1), dtype=np.float64)
+        self._call("boot_summary", mean.ctypes.data, var.ctypes.data)
+        return mean[:self.n_transcripts], var[:self.n_transcripts]
+
+    def boot_stats(self):
+        s, e, n = C.c_double(), C.c_double(), C.c_int64()
+        self._call("boot_stats", C.byref(s), C.byref(e), C.byref(n))
+        return {"sample_s": s.value, "em_s": e.value, "iterations_total": int(n.value)}
 
     def fld(self):
         """-> dict of hist (uint64 [fld_max + 1]: observed fragment lengths of the read names of one label) and n_obs,

@@ -665,7 +665,20 @@ void br_sorter_free(br_sorter *);
  *                  |theta'_t - theta_t| / theta'_t; the run stops when that is < tolerance, or at max_iters (tolerance = 0 runs
  *                  exactly max_iters iterations).  Defaults: max_iters 10000, tolerance 1e-2 (salmon's minAlpha /
  *                  relDiffTolerance convention).  TPM_t = 1e6 theta_t w_t / sum of theta w.  Not modelled: sequence or position
- *                  bias, bootstraps
+ *                  bias
+ *   bootstrap      ("bootstraps" = B > 0.)  C classes with counts n_c in class order, N = sum of n_c (the names with labels; N <
+ *                  2^32), cum = the exclusive prefix sums of n_c.  Random numbers: Philox4x32-10 (multipliers 0xD2511F53 /
+ *                  0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds) under the key ("boot_seed" low 32 bits, high 32
+ *                  bits); the counter of draw i of replicate b is (i & 0xffffffff, i >> 32, b, 0), its output words w0 .. w3, and u =
+ *                  w0 | w1 << 32.  Replicate b makes N draws, i = 0 .. N - 1; draw i picks the name rank r = floor(u N / 2^64) (the
+ *                  high half of the 64 x 64 product), which lands in the class c with cum[c] <= r < cum[c + 1]; n_c^(b) (uint32) is
+ *                  the number of draws that land in c.  N = 0: all counts and all results are 0
+ *   replicate EM   the EM above with n_c^(b) in place of n_c: the same w (eff's with "eff_len"), the same start, the same sums in
+ *                  the same order, and the same stopping rule for every replicate by its own relative change.  A replicate that has
+ *                  stopped keeps the theta of its stopping iteration whatever the replicates that run beside it go on to do, so
+ *                  replicate b's theta has the bits a point EM on n_c^(b) would have, however the replicates are cut into chunks
+ *   summary        per transcript, float64, no fused multiply-add: mean_t = (theta_t^(0) + ... + theta_t^(B-1)) / B and var_t = (sum
+ *                  over b of (theta_t^(b) - mean_t)^2) / (B - 1), both sums in replicate order, one division each; var = 0 for B = 1
  *   fragment       ("eff_len" = 1; salmon's and kallisto's truncated-mean effective length.)  A row r with BR_ROW_PAIRED |
  *                  BR_ROW_SAME_TX | BR_ROW_FIRST all set, together with row r + 1, which must lie inside the same read name's rows,
  *                  have BR_ROW_PAIRED set and BR_ROW_FIRST clear, and carry the same transcript_id.  A row that fails any of these
@@ -716,9 +729,22 @@ void br_sorter_free(br_sorter *);
  *   br_quant_result     host copies, n_transcripts each, any may be NULL: theta and tpm (after em), unique and ambig (after finish)
  *   br_quant_stats      device bytes held now, the most held so far, seconds in add / finish / em, label sets met with equal
  *                       hashes and different contents, names without rows, labels over all classes (any pointer may be NULL)
+ *   br_quant_set_param  (bootstrap) "bootstraps" 0 .. 10000 (default 0), "boot_seed" (the int64's bits are the seed, default 0),
+ *                       "boot_chunk" (test hook: the replicates that run together, 1 .. 64; 0, the default, leaves it to the
+ *                       library; the result does not depend on it): accepted, after finish as well, until br_quant_bootstrap has run
+ *   br_quant_bootstrap  the B replicates, after finish, before or after br_quant_em, whose result it leaves alone; n_iters (B
+ *                       entries, or NULL): the iterations of every replicate.  BR_ERR_INVALID_ARG before finish, with "bootstraps"
+ *                       0 or where br_quant_em refuses; BR_ERR_CAPACITY when the B x T result or a chunk does not fit
+ *   br_quant_boot_counts  count x n_classes resampled counts, replicate-major, of replicates first .. first + count - 1, generated
+ *                       again (the generator is counter-based: nothing of size B x C is kept); after finish with "bootstraps" > 0
+ *   br_quant_boot_theta   count x n_transcripts, replicate-major; after br_quant_bootstrap
+ *   br_quant_boot_summary mean and var, n_transcripts each, either may be NULL; after br_quant_bootstrap
+ *   br_quant_boot_stats   seconds resampling and in the replicates' EM, and the iterations of all replicates together
  * Device memory: 4 bytes a row and 20 bytes a read name while adding; finish peaks at 32 more a name with labels, then holds 24
  * bytes a class, 8 a label and 24 a transcript; the EM adds 40 a transcript and 8 a class; "eff_len" adds 16 (fld_max + 4) for the
- * histogram (the run's and an add's own), 16 (fld_max + 1) for the prefixes during finish and 8 a transcript for eff (quant.cpp). */
+ * histogram (the run's and an add's own), 16 (fld_max + 1) for the prefixes during finish and 8 a transcript for eff; the bootstrap
+ * holds 8 B a transcript (the result) and 8 a class (cum), and while it runs, for a chunk of W replicates (16 by default), 32 W a
+ * transcript and 12 W a class, the summary 16 a transcript (quant.cpp). */
 typedef struct br_quant br_quant;
 int br_quant_new(int device, int64_t n_transcripts, const int64_t *lengths, br_quant **out);
 int br_quant_set_param(br_quant *, const char *name, int64_t value);
@@ -735,6 +761,11 @@ int br_quant_fld(br_quant *, uint64_t *hist, uint64_t *n_obs, uint64_t *n_no_fra
 int br_quant_eff_lengths(br_quant *, double *eff);
 int br_quant_stats(const br_quant *, uint64_t *held_bytes, uint64_t *peak_bytes, double *add_seconds, double *finish_seconds,
                    double *em_seconds, uint64_t *collisions, int64_t *n_unassigned, int64_t *n_labels);
+int br_quant_bootstrap(br_quant *, int32_t *n_iters);
+int br_quant_boot_counts(br_quant *, int32_t first, int32_t count, uint32_t *counts);
+int br_quant_boot_theta(br_quant *, int32_t first, int32_t count, double *theta);
+int br_quant_boot_summary(br_quant *, double *mean, double *var);
+int br_quant_boot_stats(const br_quant *, double *sample_seconds, double *em_seconds, int64_t *iterations_total);
 void br_quant_free(br_quant *);
 
 /* Coverage: the depth of coverage along every transcript, from the rows of a whole run, in one device's HBM (coverage.cpp,
@@ -866,7 +897,7 @@ const char *const *br_annotation_refnames(const br_annotation *);
  * GPU) / --host-deflate / --compression-level N (host codec), --device-reader (default for a regular file on one device: the
  * input is inflated and split into records on the GPU, br_bam_reader) / --host-reader, --bundle-size and --device / --devices,
  * --collate, -O bam|sam, --sort [--write-index], --quant FILE [--quant-classes FILE] [--quant-eff-length [--quant-fld FILE]]
- * (br_quant above), --coverage FILE / --coverage-summary FILE [--coverage-primary] (br_coverage above; the usage text says the
+ * [--quant-bootstraps B [--quant-seed S] [--quant-boot-out FILE]] (br_quant above), --coverage FILE / --coverage-summary FILE [--coverage-primary] (br_coverage above; the usage text says the
  * rest).
  * Returns the process exit code. */
 int br_cli_main(int argc, char **argv);
