@@ -502,8 +502,9 @@ __global__ void __launch_bounds__(256) k_scan5_tiles(DirectArgs D, uint64_t *til
 }
 // One block per quantity, SCAN5_TOP_ITEMS tile sums per thread and round.  Alone, the 10 206 sums of a quantity of the bench
 // step take 13 us with 8 sums per thread (58 VGPRs), 15 with 16, 22 with 32 (155 VGPRs) and 18 with 64; on the step's path
-// the kernel takes 0.12 ms whatever the shape, because its five blocks wait for wave slots that k_group_desc's 2 048
-// resident blocks hold on the second stream (DESIGN 10.1, row 26).
+// the kernel takes 0.12 ms whatever the shape.  Not for want of wave slots (with k_group_desc at 1 792 blocks, a slot per
+// SIMD free, it took as long): k_group_desc keeps 8 192 waves of scattered loads and stores in flight on the second stream,
+// and every dependent round trip of the one-block scan queues behind them in the memory system (DESIGN 10.1, row 26).
 constexpr int SCAN5_TOP_ITEMS = 8;
 __global__ void __launch_bounds__(256) k_scan5_top(uint64_t *tile_sums, int64_t n_tiles, uint64_t *total_out) {
   __shared__ uint64_t sh[4];

@@ -707,6 +707,20 @@ template <int PRE> __device__ __forceinline__ DevCfg proj_cfg(const CountArgs &C
   return c;
 }
 
+// A global pointer of the kernel's arguments, held in two VGPRs of every lane: the empty asm hides from the compiler that
+// the value is uniform, so it is not kept in (or spilled from) scalar registers.  For the main count pass, whose SGPR
+// budget at 8 waves/SIMD is 80: its pointer arguments arrive in wide scalar loads (the five outputs as one 16-dword tuple),
+// the register allocator of ROCm 7.2 spills such a tuple to VGPR lanes as a whole and reloads it as a whole, and every
+// store in the loop over the alignments was preceded by sixteen v_readlane for the one pointer it needs (three times per
+// alignment).  That is a behaviour of this compiler, not a property of the code: after a compiler upgrade, count the
+// v_readlane in the kernel's loop again and re-measure with and without lane_ptr.
+template <class T> __device__ __forceinline__ T *lane_ptr(T *p) {
+  uint32_t lo = (uint32_t)(uintptr_t)p, hi = (uint32_t)((uintptr_t)p >> 32);
+  asm volatile("" : "+v"(lo), "+v"(hi));
+  // (through the global address space, so that the accesses stay global_load / global_store and not flat ones)
+  return (T *)(__attribute__((address_space(1))) T *)(((uintptr_t)hi << 32) | lo);
+}
+
 template <int G, bool EMIT, bool SIMF, int MODE = 0, int PRE = 0, class Args = ProjectArgs>
 __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(Args A) {
   __shared__ uint32_t sh_slab[SLAB_LDS];
@@ -745,10 +759,20 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(Args A) {
   // rest is written by k_emit_dense); the count pass listed them in big_list.
   if constexpr (EMIT) { if (tot_over(A.tot, A.lim_m, A.lim_c)) return; }
   const Ix n_work = EMIT ? (Ix)*A.n_big : MODE == 2 ? (Ix)*A.n_walk : (Ix)A.n_aln;
+  // what the loop reads (head, head2) and writes (the rest) once per alignment; the short-read preset's main count pass
+  // keeps these pointers in VGPRs (lane_ptr: it has 27 to spare at 8 waves/SIMD), the other instantiations as they come
+  // (the generic main pass keeps the argument tuple in SGPRs: nothing to gain, and nothing that measures it)
+  constexpr bool VPTR = MODE == 1 && CNT && PRE == 1;
+  auto p_head = A.head; auto p_head2 = A.head2; auto p_ranges = A.ranges; auto p_nm = A.n_matches; auto p_mask = A.mask;
+  [[maybe_unused]] uint32_t *p_light = nullptr;
+  if constexpr (VPTR) {
+    p_head = lane_ptr(p_head); p_head2 = lane_ptr(p_head2); p_ranges = lane_ptr(p_ranges); p_nm = lane_ptr(p_nm); p_mask = lane_ptr(p_mask);
+    p_light = lane_ptr(A.light_flag);   // (null on the match-table path)
+  }
   for (Ix w = gid; w < n_work; w += groups_total) {
     const Ix a = EMIT ? (Ix)A.big_list[w] : MODE == 2 ? (Ix)A.walk_list[w] : w;
-    uint4 hd = A.head[a];
-    uint4 hd2 = A.head2[a];
+    uint4 hd = p_head[a];
+    uint4 hd2 = p_head2[a];
     uint32_t n_seg = hd.z;
     if (EMIT && n_seg == 0) continue;
     uint2 q0 = make_uint2(hd.x, hd.y);
@@ -819,7 +843,7 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(Args A) {
         hi[0] = res[0]; lo[0] = res[1] < res[0] ? res[1] : res[0];
         hi[1] = res[2]; lo[1] = res[3] < res[2] ? res[3] : res[2];
       }
-      if (gl == 0) A.ranges[a] = make_uint4(lo[0], hi[0], lo[1], hi[1]);
+      if (gl == 0) p_ranges[a] = make_uint4(lo[0], hi[0], lo[1], hi[1]);
     }
     uint32_t n0 = hi[0] - lo[0], n1 = hi[1] - lo[1];
     uint32_t n_items = n0 + n1;
@@ -863,7 +887,11 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(Args A) {
         if (valid) {
           s = item < n0 ? 0 : 1;
           row = s == 0 ? lo[0] + item : lo[1] + (item - n0);
-          // one round trip, one sector: the 32-byte row
+          // The 32-byte row, one sector -- but two round trips for a row that passes: the compiler fetches the first three
+          // words here and sinks the other half (offset 20, three words) below the overlap test and classify(), so only the
+          // lanes that pass ask for it.  Asking for both halves at once, loading the rows a round ahead and prefetching the
+          // next alignments' head and table words were all measured: each made this kernel slower
+          // at 8 waves/SIMD.
           const uint4 r_a = ix.s_row[2 * (size_t)row], r_b = ix.s_row[2 * (size_t)row + 1];
           gs = r_a.x; gend = r_a.y; nxt = r_a.z; nxe = r_b.w; pay = make_uint4(r_b.x, r_b.y, r_a.w, r_b.z);
           bool want = true;
@@ -1016,8 +1044,8 @@ __global__ void __launch_bounds__(256, EMIT ? 4 : 8) k_project(Args A) {
     if constexpr (MODE == 1 && CNT && PRE == 1)
       light = n_seg == 2 && hd2.z != 0 && n_items <= 64 && ((__ballot(inexact != 0u) >> gbase) & gmask) == 0;
     if (!EMIT && gl == 0) {
-      A.n_matches[a] = total; A.mask[a] = mask_all;
-      if constexpr (MODE == 1 && CNT && PRE == 1) { if (light && A.light_flag) A.light_flag[a] = (1u << 31) | (3u + 2u * (4u * 2u + 2u)); }
+      p_nm[a] = total; p_mask[a] = mask_all;
+      if constexpr (MODE == 1 && CNT && PRE == 1) { if (light && p_light) p_light[a] = (1u << 31) | (3u + 2u * (4u * 2u + 2u)); }
       if (n_items > 64 && total) {
         const uint32_t k = atomicAdd(&sh_bn, 1u);
         if (k < BIG_LDS) sh_bl[EMIT ? 0 : k] = (uint32_t)a;
