@@ -20,6 +20,9 @@
                                          alignments, the classes, the EM -- seconds in add / finish / em, iterations, names, classes,
                                          labels, quantifier peak device bytes per read name; then the same with the fragment-length
                                          model ("eff_len": the adds through br_quant_add_rows), as runs_eff_length
+  python bench_extra.py quant_genes [--reads N] [--bootstraps B]   the gene level on the quant workload: br_quant_genes' seconds beside
+                                         br_quant_finish's of the same run, br_quant_gene_result, and br_quant_gene_boot_summary
+                                         (the first call, which makes the B x G table, and a second) beside br_quant_boot_summary
   python bench_extra.py quant_boot [--reads N] [--bootstraps B] [--boot-chunk W]  the bootstrap replicates on the quant workload, in one
                                          process: br_quant_em (seconds, iterations, seconds per replicate-iteration), then
                                          br_quant_bootstrap with B replicates (default 32; W of them together, 0: the library's
@@ -51,7 +54,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "quant_boot", "coverage"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "quant_boot", "quant_genes", "coverage"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
@@ -162,7 +165,7 @@ def main():
                              "peak_bytes_per_record": round(stt["peak_bytes"] / n_rows, 1)})
         print(json.dumps({"config": "sort", "pairs": n, "records": n_rows, "stream_bytes": n_bytes, "runs": runs}))
         return
-    if args.config in ("quant", "quant_boot"):
+    if args.config in ("quant", "quant_boot", "quant_genes"):
         n = args.reads or 10_000_000
         ann = synth.Annotation("G")
         batch = ann.reads(n, "pe")
@@ -211,6 +214,38 @@ def main():
                                  "labels": stt["n_labels"], "peak_bytes": stt["peak_bytes"]})
             print(json.dumps({"config": "quant_boot", "pairs": n, "alignments": n_aln, "rows": n_rows, "transcripts": n_tx, "bootstraps": args.bootstraps,
                               "boot_chunk": args.boot_chunk, "runs": runs}))
+            return
+        if args.config == "quant_genes":
+            tx_gene = np.ascontiguousarray(ann.flat["tx_gene"], dtype=np.uint32)
+            n_genes = int(tx_gene.max()) + 1
+
+            def timed(f):
+                t0 = time.perf_counter()
+                f()
+                return round(time.perf_counter() - t0, 5)
+            runs = []
+            for step in range(args.warmup + args.steps):
+                q = lib.Quant(n_tx, lens)
+                q.set_param("bootstraps", args.bootstraps)
+                q.set_param("boot_seed", step)
+                for g0, g1 in zip(cuts, cuts[1:]):
+                    lib.check(q.add_raw(rows.a, rows.row_off, db["group_off"].data_ptr() + 4 * g0, g1 - g0, True), "br_quant_add")
+                names, classes = q.finish()
+                q.em()
+                q.genes(tx_gene, n_genes)
+                gst, stt = q.gene_stats(), q.stats()
+                run = {"finish_s": round(stt["finish_s"], 4), "genes_s": round(gst["seconds"], 4), "gene_result_s": timed(q.gene_result), "names": names,
+                       "classes": classes, "labels": stt["n_labels"], "gene_classes": q.n_gene_classes, "gene_labels": gst["n_gene_labels"],
+                       "held_bytes": stt["held_bytes"], "peak_bytes": stt["peak_bytes"]}
+                if args.bootstraps:
+                    q.bootstrap()
+                    run.update({"boot_summary_s": timed(q.boot_summary), "gene_boot_summary_first_s": timed(q.gene_boot_summary),   # (the first call makes B x G)
+                                "gene_boot_summary_s": timed(q.gene_boot_summary)})
+                q.close()
+                if step >= args.warmup:
+                    runs.append(run)
+            print(json.dumps({"config": "quant_genes", "pairs": n, "alignments": n_aln, "rows": n_rows, "transcripts": n_tx, "genes": n_genes,
+                              "bootstraps": args.bootstraps, "runs": runs}))
             return
         runs, runs_eff = [], []
         for eff_len in (0, 1):   # 1: the fragment-length model, the adds through br_quant_add_rows (the CIGAR references and the pool as well)

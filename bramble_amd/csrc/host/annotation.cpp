@@ -38,11 +38,11 @@
 
 struct br_annotation {
   std::vector<std::string> refnames;             // order of first appearance (gclib's gseq ids)
-  std::vector<std::string> ids, seqnames;
+  std::vector<std::string> ids, seqnames, genes;  // genes: br_annotation_gene_ids
   std::vector<char> strands;
   std::vector<std::vector<br_exon>> exons;       // 1-based half-open [start, end+1), like bramble.cpp:164-165
   std::vector<br_transcript> view;
-  std::vector<const char *> refname_view;
+  std::vector<const char *> refname_view, gene_view;
 };
 
 namespace {
@@ -56,6 +56,7 @@ struct Tx {
   bool by_exon = false;                          // GffObj::createdByExon: the record began with an exon-like line (never cleared, gff.cpp:1486)
   uint32_t cur_start = 0;                        // GffObj::start while the file is read: what gfoFind measures the locus distance from
   int level = 0;                                 // GffObj::gff_level
+  std::string gene, parent_gene;                 // the first non-empty gene_id of the record's lines; GFF3: the first Parent= of its transcript line
   std::vector<std::pair<uint32_t, uint32_t>> segs;  // sorted, merged, 1-based inclusive
 };
 
@@ -228,14 +229,17 @@ extern "C" int br_annotation_load_mt(const char *path, int threads, br_annotatio
   };
   // an exon-like line for the transcript `id` (readAll, gff.cpp:1763-1836; readExonFeature, :1503-1533): it joins the record
   // of that ID in its locus; without one, it starts a record of its own ("new GTF-like record starting directly here")
-  auto exon_line = [&](sv id, const Rec &r) {
+  auto exon_line = [&](sv id, const Rec &r) -> Tx & {
     std::vector<size_t> &lst = list_of(id, r.seq);
     Tx *tx = find_tx(lst, r.strand, r.fs);
     if (!tx) { Tx &n = new_tx(lst, id, r.seq, r.strand, r.fs); n.by_exon = true; tx = &n; }
     else if (tx->strand == '.') tx->strand = r.strand;            // (find_tx lets a line through only on the record's strand, or on none)
     add_segment(tx->segs, r.fs, r.fe);
     tx->cur_start = std::min(tx->cur_start, std::min(r.fs, r.fe));
+    return *tx;
   };
+  // the record's gene: the gene_id of the first line applied to it that has one (carried along, never compared)
+  auto take_gene = [](Tx &tx, const Rec &r) { if (tx.gene.empty() && r.has_gid && !r.gid.empty()) tx.gene.assign(r.gid.data(), r.gid.size()); };
   // a transcript line with that ID (gff.cpp:1684-1733): it completes a record that exon lines began; a record that already
   // came from a transcript line stays as it is and the line becomes a separate record under the same ID (a discontinuous
   // feature in the GFF3 sense) -- exon lines that follow still go to the first record of the locus
@@ -278,6 +282,12 @@ extern "C" int br_annotation_load_mt(const char *path, int threads, br_annotatio
         Tx &tx = transcript_line(id, r);
         tx.level = level_under(parent);
         feat_level[std::string(id)] = tx.level;
+        take_gene(tx, r);
+        if (tx.parent_gene.empty()) {   // Parent=id1,id2: the first entry
+          sv pid = parent.substr(0, parent.find(','));
+          while (!pid.empty() && pid.back() == ' ') pid.remove_suffix(1);
+          tx.parent_gene.assign(pid.data(), pid.size());
+        }
       } else if (kind == K_EXONLIKE) {
         if (parent.empty()) return;
         size_t a = 0;
@@ -286,7 +296,7 @@ extern "C" int br_annotation_load_mt(const char *path, int threads, br_annotatio
           if (b == sv::npos) b = parent.size();
           sv pid = parent.substr(a, b - a);
           while (!pid.empty() && pid.back() == ' ') pid.remove_suffix(1);
-          if (!pid.empty()) exon_line(pid, r);
+          if (!pid.empty()) take_gene(exon_line(pid, r), r);
           a = b + 1;
         }
       }
@@ -302,8 +312,9 @@ extern "C" int br_annotation_load_mt(const char *path, int threads, br_annotatio
         Tx &tx = transcript_line(r.tid, r);
         // a `transcript` line names its gene as parent (gff.cpp:733-741)
         if (r.has_gid) { auto it = feat_level.find(std::string(r.gid)); if (it != feat_level.end()) tx.level = it->second + 1; }
+        take_gene(tx, r);
       }
-      else exon_line(r.tid, r);
+      else take_gene(exon_line(r.tid, r), r);
     }
   };
 
@@ -439,6 +450,8 @@ extern "C" int br_annotation_load_mt(const char *path, int threads, br_annotatio
   if (getenv("BRAMBLE_AMD_TIMING")) fprintf(stderr, "[annotation] finish + sort %.3f\n", secs_since(t_sort0));
   br_annotation *A = new br_annotation();
   A->refnames = refnames;
+  A->genes.reserve(order.size());
+  for (Tx *tx : order) A->genes.push_back(!tx->gene.empty() ? tx->gene : !tx->parent_gene.empty() ? tx->parent_gene : tx->id);   // no transcript without a gene
   A->ids.reserve(order.size()); A->seqnames.reserve(order.size()); A->strands.reserve(order.size()); A->exons.reserve(order.size()); A->view.reserve(order.size());
   for (Tx *tx : order) {
     A->ids.push_back(std::move(tx->id)); A->seqnames.push_back(std::move(tx->seqname)); A->strands.push_back(tx->strand);
@@ -449,6 +462,7 @@ extern "C" int br_annotation_load_mt(const char *path, int threads, br_annotatio
   for (size_t i = 0; i < A->ids.size(); i++)
     A->view.push_back({A->ids[i].c_str(), A->seqnames[i].c_str(), A->strands[i], A->exons[i].data(), (uint32_t)A->exons[i].size()});
   for (auto &r : A->refnames) A->refname_view.push_back(r.c_str());
+  for (auto &g : A->genes) A->gene_view.push_back(g.c_str());
   *out = A;
   return BR_OK;
 }
@@ -463,3 +477,4 @@ extern "C" size_t br_annotation_num_transcripts(const br_annotation *a) { return
 extern "C" const br_transcript *br_annotation_transcripts(const br_annotation *a) { return a ? a->view.data() : nullptr; }
 extern "C" size_t br_annotation_num_refs(const br_annotation *a) { return a ? a->refnames.size() : 0; }
 extern "C" const char *const *br_annotation_refnames(const br_annotation *a) { return a ? a->refname_view.data() : nullptr; }
+extern "C" const char *const *br_annotation_gene_ids(const br_annotation *a) { return a ? a->gene_view.data() : nullptr; }

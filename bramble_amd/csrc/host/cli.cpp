@@ -46,7 +46,8 @@ void usage(FILE *f) {
           "               [--device N | --devices a,b,...] [--collate] [--sort [--write-index]]\n"
           "               [--quant <quant.tsv> [--quant-classes <eq_classes.txt>] [--quant-length-norm | --quant-no-length-norm]\n"
           "                [--quant-eff-length [--quant-fld <fld.tsv>]]\n"
-          "                [--quant-bootstraps B [--quant-seed S] [--quant-boot-out <bootstraps.tsv>]]]\n"
+          "                [--quant-bootstraps B [--quant-seed S] [--quant-boot-out <bootstraps.tsv>]]\n"
+          "                [--quant-genes <genes.tsv> [--quant-gene-classes <gene_classes.txt>] [--quant-gene-map <tx2gene.tsv>]]]\n"
           "               [--coverage <cov.bedgraph>] [--coverage-summary <cov.tsv>] [--coverage-primary]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
@@ -82,6 +83,14 @@ void usage(FILE *f) {
           "normalisation: not with --quant-no-length-norm, and under --lr / --lr-hq only with --quant-length-norm.  --quant-fld FILE:\n"
           "the histogram, FragmentLength and Count for the lengths 0 .. 1000.  One more line in front of the quantified line:\n"
           "[bramble] fragment lengths: N observed, mean M.M, U unique names without a pair, R out of range\n"
+          "--quant-genes FILE: the transcripts' results collapsed to genes on the GPU (the gene_id of the annotation): one line per gene,\n"
+          "genes in order of first appearance in @SQ order: Name, Length (the TPM-weighted mean of its transcripts' lengths, their plain\n"
+          "mean where the gene's TPM is 0), [EffectiveLength,] NumReads, TPM, UniqueReads and AmbigReads (of the read names' gene sets: a\n"
+          "read that is ambiguous among isoforms of one gene is unique here), NumTranscripts, [BootMean, BootSD of the gene's NumReads over\n"
+          "the replicates].  --quant-gene-classes FILE: the classes merged by gene set, in the layout of --quant-classes with gene names.\n"
+          "--quant-gene-map FILE: transcript<TAB>gene lines (a tximport tx2gene table; # lines and empty lines are skipped, further\n"
+          "columns ignored) that replace the annotation's gene ids; every @SQ transcript must be in it.  One more line in front of the\n"
+          "quantified line: [bramble] gene level: G genes, C classes (X.XXs)\n"
           "--coverage FILE: the depth of coverage along every transcript, counted on one GPU from the projected records of the whole\n"
           "run, as a bedGraph (name, start, end, depth; 0-based, half-open, no header; @SQ order, then ascending start; depth > 0\n"
           "only, as bedtools genomecov -bg -split lists it).  M = X cover, D N do not; secondary records and both mates count, a base\n"
@@ -157,6 +166,9 @@ int parse_args(int argc, char **argv, Options &o) {
       o.quant_seed = x; o.quant_seed_given = true;
     }
     else if (a == "--quant-boot-out") { const char *v = value(); if (!v) return -1; o.quant_boot_out = v; }
+    else if (a == "--quant-genes") { const char *v = value(); if (!v) return -1; o.quant_genes = v; }
+    else if (a == "--quant-gene-classes") { const char *v = value(); if (!v) return -1; o.quant_gene_classes = v; }
+    else if (a == "--quant-gene-map") { const char *v = value(); if (!v) return -1; o.quant_gene_map = v; }
     else if (a == "--coverage") { const char *v = value(); if (!v) return -1; o.coverage = v; }
     else if (a == "--coverage-summary") { const char *v = value(); if (!v) return -1; o.coverage_summary = v; }
     else if (a == "--coverage-primary") o.coverage_primary = true;
@@ -182,6 +194,8 @@ int parse_args(int argc, char **argv, Options &o) {
   if (o.quant.empty() && (!o.quant_classes.empty() || o.quant_length_norm >= 0)) { fprintf(stderr, "--quant-classes, --quant-length-norm and --quant-no-length-norm need --quant\n"); return -1; }
   if (o.quant.empty() && (o.quant_eff_length || !o.quant_fld.empty())) { fprintf(stderr, "--quant-eff-length and --quant-fld need --quant\n"); return -1; }
   if (o.quant.empty() && (o.quant_bootstraps || o.quant_seed_given || !o.quant_boot_out.empty())) { fprintf(stderr, "--quant-bootstraps, --quant-seed and --quant-boot-out need --quant\n"); return -1; }
+  if (o.quant.empty() && !o.quant_genes.empty()) { fprintf(stderr, "--quant-genes needs --quant\n"); return -1; }
+  if (o.quant_genes.empty() && (!o.quant_gene_classes.empty() || !o.quant_gene_map.empty())) { fprintf(stderr, "--quant-gene-classes and --quant-gene-map need --quant-genes\n"); return -1; }
   if (!o.quant_boot_out.empty() && !o.quant_bootstraps) { fprintf(stderr, "--quant-boot-out needs --quant-bootstraps: without it there are no replicates\n"); return -1; }
   if (!o.quant_fld.empty() && !o.quant_eff_length) { fprintf(stderr, "--quant-fld needs --quant-eff-length: without it no fragment lengths are counted\n"); return -1; }
   if (o.quant_eff_length && o.quant_length_norm == 0) { fprintf(stderr, "--quant-eff-length is a length normalisation: not with --quant-no-length-norm\n"); return -1; }
@@ -513,6 +527,36 @@ struct Run {
 
 }  // namespace
 
+// --quant-gene-map: transcript<TAB>gene lines into `map` (the first line of a transcript counts); every transcript of the guides
+// must be there.  false: `err` says what is wrong
+static bool load_gene_map(const std::string &path, const br_annotation *ann, std::unordered_map<std::string, std::string> &map, std::string &err) {
+  FILE *f = fopen(path.c_str(), "r");
+  if (!f) { err = "cannot open the file"; return false; }
+  std::string line;
+  char buf[65536];
+  auto take = [&]() {
+    while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+    if (line.empty() || line[0] == '#') return;
+    const size_t a = line.find('\t');
+    if (a == std::string::npos) return;
+    const size_t b = line.find('\t', a + 1);
+    std::string gene = line.substr(a + 1, b == std::string::npos ? std::string::npos : b - a - 1);
+    if (!gene.empty()) map.emplace(line.substr(0, a), std::move(gene));
+  };
+  while (fgets(buf, sizeof buf, f)) {
+    line += buf;
+    if (line.back() != '\n') continue;   // (a line longer than the buffer: read on)
+    take();
+    line.clear();
+  }
+  take();
+  fclose(f);
+  const br_transcript *tx = br_annotation_transcripts(ann);
+  for (size_t t = 0, n = br_annotation_num_transcripts(ann); t < n; t++)
+    if (!map.count(tx[t].id)) { err = std::string("transcript ") + tx[t].id + " has no gene in it"; return false; }
+  return true;
+}
+
 static std::atomic<int> g_exit_at_end{0};
 extern "C" void br_cli_exit_at_end(int on) { g_exit_at_end.store(on ? 1 : 0); }
 
@@ -532,11 +576,19 @@ extern "C" int br_cli_main(int argc, char **argv) {
   // (below) happen beside it instead of in front of it
   br_annotation *ann = nullptr;
   std::future<int> ann_job = std::async(std::launch::async, [&]() { return br_annotation_load_mt(o.gff.c_str(), std::max(1, std::min(o.threads, 32)), &ann); });   // the lines are taken apart by -p threads
-  struct AnnJoin { std::future<int> &f; br_annotation *&a; ~AnnJoin() { if (f.valid()) { (void)f.get(); if (a) br_annotation_free(a); a = nullptr; } } } ann_join{ann_job, ann};   // (an early return: wait for it, drop its result)
+  struct AnnJoin { std::future<int> &f; br_annotation *&a; ~AnnJoin() { if (f.valid()) (void)f.get(); if (a) br_annotation_free(a); a = nullptr; } } ann_join{ann_job, ann};   // (an early return: wait for it, drop its result)
   // the devices' first touch (runtime start-up, contexts) happens beside the guide parsing, not in front of the index build
   std::vector<std::thread> warm;
   for (int d : o.devices) warm.emplace_back([d]() { (void)br_device_warmup(d); });
   struct WarmJoin { std::vector<std::thread> &t; ~WarmJoin() { for (auto &x : t) if (x.joinable()) x.join(); } } warm_join{warm};
+  int ann_rc = 0;
+  auto ann_wait = [&]() { if (ann_job.valid()) ann_rc = ann_job.get(); return ann_rc; };
+  // --quant-gene-map is checked against the guides before the input is opened or anything is written
+  std::unordered_map<std::string, std::string> gene_map;
+  if (std::string gerr; !o.quant_gene_map.empty() && ann_wait() == 0 && !load_gene_map(o.quant_gene_map, ann, gene_map, gerr)) {
+    fprintf(stderr, "error: --quant-gene-map %s: %s\n", o.quant_gene_map.c_str(), gerr.c_str());
+    return 2;
+  }
   Outbox out;
   std::string err;
   std::unique_ptr<Input> in = open_input(o, err);
@@ -553,7 +605,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
     ann = nullptr;
   };
   auto give_up = [&]() { free_all(); in->stop(); return 1; };   // a setup error
-  int rc = ann_job.get();
+  int rc = ann_wait();
   const double t_guides = since();
   if (rc) { fprintf(stderr, "error: could not load reference annotation %s: %s\n", o.gff.c_str(), br_strerror(rc)); return give_up(); }
   size_t n_tx = br_annotation_num_transcripts(ann), n_refs = br_annotation_num_refs(ann);
@@ -603,6 +655,12 @@ extern "C" int br_cli_main(int argc, char **argv) {
     env.tx.len.push_back(br_index_transcript_len(ix0, (uint32_t)t));
   }
   number_sq(env.tx);
+  if (!o.quant_genes.empty()) {   // the genes beside the names: the annotation's, or the map's
+    const char *const *gene_ids = br_annotation_gene_ids(ann);
+    if (env.tx.name.size() != n_tx) { fprintf(stderr, "error: the index does not hold the annotation's transcripts\n"); return give_up(); }
+    for (size_t t = 0; t < n_tx; t++) env.tx.gene.push_back(o.quant_gene_map.empty() ? gene_ids[t] : gene_map.find(env.tx.name[t])->second.c_str());
+    number_genes(env.tx);
+  }
   if (o.sam_out) {   // RNAME / RNEXT
     std::vector<const char *> sq;
     for (size_t t = 0; t < env.tx.len.size(); t++) if (env.tx.len[t] > 0) sq.push_back(env.tx.name[t]);

@@ -44,6 +44,8 @@ struct Options {
   long long quant_seed = 0;      // --quant-seed S: their seed (br_quant "boot_seed")
   bool quant_seed_given = false;
   std::string quant_boot_out;    // --quant-boot-out FILE: every replicate's NumReads per transcript
+  std::string quant_genes, quant_gene_classes;   // --quant-genes FILE / --quant-gene-classes FILE: the gene-level table and the gene classes (br_quant_genes)
+  std::string quant_gene_map;    // --quant-gene-map FILE: transcript<TAB>gene lines that replace the annotation's gene ids
   std::string coverage, coverage_summary;   // --coverage FILE / --coverage-summary FILE: the bedGraph of the depth along every transcript and the per-transcript table (br_coverage)
   bool coverage_primary = false; // --coverage-primary: only primary records count ("primary_only")
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used

@@ -1,9 +1,11 @@
-// SideFile and the text of the five side files (cli_output_files.h).  No call into the library.
+// SideFile and the text of the side files (cli_output_files.h).  No call into the library.
 #include "cli_output_files.h"
 
 #include <math.h>
 
 #include <algorithm>
+#include <string_view>
+#include <unordered_map>
 
 namespace brcli {
 
@@ -35,6 +37,19 @@ void number_sq(TxTable &tx) {
   tx.sq_of.assign(tx.len.size(), -1);
   tx.n_sq = 0;
   for (size_t t = 0; t < tx.len.size(); t++) if (tx.len[t] > 0) tx.sq_of[t] = tx.n_sq++;
+}
+
+void number_genes(TxTable &tx) {
+  std::unordered_map<std::string_view, uint32_t> number;
+  tx.gene_of.assign(tx.gene.size(), 0);
+  tx.gene_name.clear();
+  for (int pass = 0; pass < 2; pass++)   // the @SQ transcripts first
+    for (size_t t = 0; t < tx.gene.size(); t++) {
+      if ((tx.len[t] > 0) != (pass == 0)) continue;
+      auto it = number.emplace(tx.gene[t], (uint32_t)tx.gene_name.size());
+      if (it.second) tx.gene_name.push_back(tx.gene[t]);
+      tx.gene_of[t] = it.first->second;
+    }
 }
 
 void write_quant_table(FILE *f, const TxTable &tx, const std::vector<double> *eff, const std::vector<double> &theta, const std::vector<double> &tpm,
@@ -73,6 +88,32 @@ void write_quant_classes(FILE *f, const TxTable &tx, int64_t n_classes, const st
   for (size_t c = 0; c < (size_t)n_classes; c++) {
     fprintf(f, "%llu", (unsigned long long)(label_off[c + 1] - label_off[c]));
     for (uint64_t e = label_off[c]; e < label_off[c + 1]; e++) fprintf(f, "\t%lld", (long long)tx.sq_of[labels[(size_t)e]]);
+    fprintf(f, "\t%llu\n", (unsigned long long)counts[c]);
+  }
+}
+
+void write_quant_gene_table(FILE *f, const TxTable &tx, const std::vector<double> &length, const std::vector<double> *eff, const std::vector<double> &num_reads,
+                            const std::vector<double> &tpm, const std::vector<uint64_t> &unique, const std::vector<uint64_t> &ambig,
+                            const std::vector<uint32_t> &n_transcripts, const std::vector<double> *boot_mean, const std::vector<double> *boot_var) {
+  const bool boot = boot_mean && boot_var;
+  fprintf(f, eff ? "Name\tLength\tEffectiveLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\tNumTranscripts" : "Name\tLength\tNumReads\tTPM\tUniqueReads\tAmbigReads\tNumTranscripts");
+  fprintf(f, boot ? "\tBootMean\tBootSD\n" : "\n");
+  for (size_t g = 0; g < tx.gene_name.size(); g++) {
+    fprintf(f, "%s\t%.3f", tx.gene_name[g], length[g]);
+    if (eff) fprintf(f, "\t%.3f", (*eff)[g]);
+    fprintf(f, "\t%.6f\t%.6f\t%llu\t%llu\t%u", num_reads[g], tpm[g], (unsigned long long)unique[g], (unsigned long long)ambig[g], n_transcripts[g]);
+    if (boot) fprintf(f, "\t%.6f\t%.6f", (*boot_mean)[g], sqrt((*boot_var)[g]));
+    fputc('\n', f);
+  }
+}
+
+void write_quant_gene_classes(FILE *f, const TxTable &tx, int64_t n_classes, const std::vector<uint64_t> &label_off, const std::vector<uint32_t> &labels,
+                              const std::vector<uint64_t> &counts) {
+  fprintf(f, "%zu\n%lld\n", tx.gene_name.size(), (long long)n_classes);
+  for (const char *g : tx.gene_name) fprintf(f, "%s\n", g);
+  for (size_t c = 0; c < (size_t)n_classes; c++) {
+    fprintf(f, "%llu", (unsigned long long)(label_off[c + 1] - label_off[c]));
+    for (uint64_t e = label_off[c]; e < label_off[c + 1]; e++) fprintf(f, "\t%u", labels[(size_t)e]);
     fprintf(f, "\t%llu\n", (unsigned long long)counts[c]);
   }
 }

@@ -25,8 +25,14 @@ class SideFile {
 bool settle_all(std::initializer_list<SideFile *> files, bool failed);   // in this order; after a failed rename the rest is removed; false: one failed
 
 // Every transcript of the index; the tables list those of length > 0 (the output's @SQ list), numbered in that order by sq_of
-struct TxTable { std::vector<const char *> name; std::vector<int64_t> len, sq_of; int64_t n_sq = 0; };
+// --quant-genes: gene, every transcript's gene id (else empty); the genes are numbered in order of first appearance in @SQ order
+// (those that only transcripts outside the @SQ list have come last): gene_of per transcript, gene_name per gene
+struct TxTable {
+  std::vector<const char *> name; std::vector<int64_t> len, sq_of; int64_t n_sq = 0;
+  std::vector<const char *> gene, gene_name; std::vector<uint32_t> gene_of;
+};
 void number_sq(TxTable &tx);   // sq_of and n_sq from len
+void number_genes(TxTable &tx);   // gene_of and gene_name from gene and len
 
 // eff: the EffectiveLength column behind Length, nullptr without it; boot_mean and boot_var: the last columns BootMean and BootSD
 // (the variance's square root), nullptr without them
@@ -39,6 +45,14 @@ void write_quant_bootstraps(FILE *f, const TxTable &tx, int n_boot, const std::v
 void write_quant_classes(FILE *f, const TxTable &tx, int64_t n_classes, const std::vector<uint64_t> &label_off, const std::vector<uint32_t> &labels,
                          const std::vector<uint64_t> &counts);
 void write_fragment_lengths(FILE *f, const std::vector<uint64_t> &hist);
+// --quant-genes: a line per gene, Name Length [EffectiveLength] NumReads TPM UniqueReads AmbigReads NumTranscripts [BootMean BootSD];
+// eff, boot_mean and boot_var as in write_quant_table
+void write_quant_gene_table(FILE *f, const TxTable &tx, const std::vector<double> &length, const std::vector<double> *eff, const std::vector<double> &num_reads,
+                            const std::vector<double> &tpm, const std::vector<uint64_t> &unique, const std::vector<uint64_t> &ambig,
+                            const std::vector<uint32_t> &n_transcripts, const std::vector<double> *boot_mean = nullptr, const std::vector<double> *boot_var = nullptr);
+// write_quant_classes' layout with the genes' names and numbers
+void write_quant_gene_classes(FILE *f, const TxTable &tx, int64_t n_classes, const std::vector<uint64_t> &label_off, const std::vector<uint32_t> &labels,
+                              const std::vector<uint64_t> &counts);
 // runs [first, first + n) into the four columns; not 0: an error, which ends the file there
 using RunPage = std::function<int(int64_t first, int64_t n, uint32_t *tid, uint32_t *start, uint32_t *end, uint32_t *depth)>;
 int write_bedgraph(FILE *f, const TxTable &tx, int64_t n_runs, int64_t page, const RunPage &fetch);   // the first error of fetch

@@ -1,7 +1,8 @@
 // --quant and its switches (cli_output.h): every bundle's rows go to a br_quant (br_quant_add_last; --quant-eff-length: the adds
 // count the fragment lengths as well, "eff_len"); after the last bundle: classes, EM, and everything the three files need in one
 // download each -- the table, --quant-classes, --quant-fld; with --quant-bootstraps the replicates run behind the EM
-// (br_quant_bootstrap) and their summary joins the table, their values --quant-boot-out.
+// (br_quant_bootstrap) and their summary joins the table, their values --quant-boot-out; with --quant-genes the gene tables are
+// made last (br_quant_genes on the numbers env.tx gives the genes) and go to --quant-genes and --quant-gene-classes.
 #include "cli_output.h"
 
 namespace brcli {
@@ -9,7 +10,7 @@ namespace {
 
 class QuantOut : public Consumer {
  public:
-  explicit QuantOut(const RunEnv &e) : Consumer(e, "quantifier", "quantification"), table(e.o.quant), classes(e.o.quant_classes), fld(e.o.quant_fld), boot(e.o.quant_boot_out) {}
+  explicit QuantOut(const RunEnv &e) : Consumer(e, "quantifier", "quantification"), table(e.o.quant), classes(e.o.quant_classes), fld(e.o.quant_fld), boot(e.o.quant_boot_out), genes(e.o.quant_genes), gene_classes(e.o.quant_gene_classes) {}
   ~QuantOut() override { if (q) br_quant_free(q); }
   int open() {
     const Options &o = env.o;
@@ -51,6 +52,24 @@ class QuantOut : public Consumer {
       label_off.resize((size_t)n_classes + 1); counts.resize((size_t)n_classes + 1); labels.resize((size_t)n_labels + 1);
       if (!rc) rc = br_quant_classes(q, label_off.data(), labels.data(), counts.data(), nullptr);
     }
+    if (!rc && !genes.path.empty()) {
+      const size_t ng = env.tx.gene_name.size();
+      rc = br_quant_genes(q, env.tx.gene_of.data(), (int64_t)ng, &n_gene_classes);
+      g_len.resize(ng + 1); g_reads.resize(ng + 1); g_tpm.resize(ng + 1); g_unique.resize(ng + 1); g_ambig.resize(ng + 1); g_ntx.resize(ng + 1);
+      if (env.o.quant_eff_length) g_eff.resize(ng + 1);
+      if (!rc) rc = br_quant_gene_result(q, g_reads.data(), g_tpm.data(), g_len.data(), env.o.quant_eff_length ? g_eff.data() : nullptr, g_unique.data(),
+                                         g_ambig.data(), g_ntx.data());
+      if (!rc && env.o.quant_bootstraps) {
+        g_boot_mean.resize(ng + 1); g_boot_var.resize(ng + 1);
+        rc = br_quant_gene_boot_summary(q, g_boot_mean.data(), g_boot_var.data());
+      }
+      int64_t n_labels = 0;
+      if (!rc) rc = br_quant_gene_stats(q, &t_genes, &n_labels, nullptr);
+      if (!rc && !gene_classes.path.empty()) {
+        g_label_off.resize((size_t)n_gene_classes + 1); g_counts.resize((size_t)n_gene_classes + 1); g_labels.resize((size_t)n_labels + 1);
+        rc = br_quant_gene_classes(q, g_label_off.data(), g_labels.data(), g_counts.data(), nullptr);
+      }
+    }
     (void)br_quant_stats(q, nullptr, nullptr, &t_add, &t_finish, &t_em, nullptr, nullptr, nullptr);
     return rc;
   }
@@ -64,9 +83,14 @@ class QuantOut : public Consumer {
     if (FILE *f = fld.open()) write_fragment_lengths(f, hist);
     if (!fld.close()) return false;
     if (FILE *f = boot.open()) write_quant_bootstraps(f, env.tx, env.o.quant_bootstraps, boot_theta);
-    return boot.close();
+    if (!boot.close()) return false;
+    if (FILE *f = genes.open()) write_quant_gene_table(f, env.tx, g_len, env.o.quant_eff_length ? &g_eff : nullptr, g_reads, g_tpm, g_unique, g_ambig, g_ntx,
+                                                       with_boot ? &g_boot_mean : nullptr, with_boot ? &g_boot_var : nullptr);
+    if (!genes.close()) return false;
+    if (FILE *f = gene_classes.open()) write_quant_gene_classes(f, env.tx, n_gene_classes, g_label_off, g_labels, g_counts);
+    return gene_classes.close();
   }
-  bool settle(bool failed) override { return settle_all({&table, &classes, &fld, &boot}, failed); }
+  bool settle(bool failed) override { return settle_all({&table, &classes, &fld, &boot, &genes, &gene_classes}, failed); }
   void report() const override {
     if (env.o.quant_eff_length) {
       double sum = 0;
@@ -77,13 +101,14 @@ class QuantOut : public Consumer {
     if (env.o.quant_bootstraps)
       printf("[bramble] bootstrapped %d replicates (seed %lld, %lld iterations in all, sampling %.2fs, EM %.2fs)\n", env.o.quant_bootstraps, env.o.quant_seed,
              (long long)boot_iters, t_boot_sample, t_boot_em);
+    if (!genes.path.empty()) printf("[bramble] gene level: %zu genes, %lld classes (%.2fs)\n", env.tx.gene_name.size(), (long long)n_gene_classes, t_genes);
     printf("[bramble] quantified %lld read names in %lld classes (%d iterations, add %.2fs, classes %.2fs, EM %.2fs)\n", (long long)n_names, (long long)n_classes,
            (int)n_iters, t_add, t_finish, t_em);
   }
  private:
   static constexpr size_t FLD_MAX = 1000;   // br_quant's default "fld_max"
   br_quant *q = nullptr;
-  SideFile table, classes, fld, boot;
+  SideFile table, classes, fld, boot, genes, gene_classes;
   int64_t n_names = 0, n_classes = 0; int32_t n_iters = 0;
   double t_add = 0, t_finish = 0, t_em = 0;
   std::vector<double> theta, tpm, eff, boot_mean, boot_var, boot_theta;   // boot_*: --quant-bootstraps (boot_theta: one row a replicate)
@@ -91,6 +116,11 @@ class QuantOut : public Consumer {
   std::vector<uint64_t> unique, ambig, label_off, counts, hist;   // hist, eff: --quant-eff-length
   std::vector<uint32_t> labels;
   uint64_t fld_obs = 0, fld_nofrag = 0, fld_oor = 0;
+  // --quant-genes: per gene, and the gene classes
+  int64_t n_gene_classes = 0; double t_genes = 0;
+  std::vector<double> g_len, g_eff, g_reads, g_tpm, g_boot_mean, g_boot_var;
+  std::vector<uint64_t> g_unique, g_ambig, g_label_off, g_counts;
+  std::vector<uint32_t> g_ntx, g_labels;
 };
 
 }  // namespace

@@ -25,6 +25,17 @@
 //            The host reads W relative changes at every look and clears the bit of a replicate that stops: its theta is copied
 //            through from then on.  The chunk ends when all have stopped; its theta go to the B x T result, which a last
 //            kernel reduces to mean and variance per transcript
+//   genes    (br_quant_genes, after finish) a lane per label entry makes (class << 32) | gene of the label; the radix driver sorts
+//            the L keys, the heads of equal keys are the distinct (class, gene) entries and a scan places them in a gene-label
+//            arena, a class's gene list where its labels were; a hash of every list (a lane, or a wave above 64 genes), then
+//            finish's own sequence with a class where finish has a name: the sort of (hash, class), the heads by comparing
+//            lists with the collision repair, a scan of the members' counts for a gene class's count (finish counts 1 a name),
+//            its first member for its first name (the classes are in first-name order), the sort by first name, label_off and
+//            labels, and unique / ambiguous names per gene by integer atomics.  The transcripts by gene come from a counting
+//            sort on the host; a lane per gene sums theta / tpm / lengths over them in ascending order, a lane per (replicate,
+//            gene) the B x T result into B x G, which the transcripts' summary kernel reduces.  (The gene path stands beside
+//            quant_finish and shares its kernels for sorting, heads, repair and scans; the kernels that read per-name tables
+//            have gene twins, k_qg_*.)
 //
 // Device memory (N names, of them M with labels; R rows added; C classes; L labels over all classes; T transcripts):
 //   while adding   4 R (the arena: a slot per row) + 20 N (offset, k, hash) + 4 bytes a name of the largest add (the list of its
@@ -43,6 +54,14 @@
 //                  while it runs, for a chunk of W replicates, 32 W T (theta and theta w twice) + 12 W C (q 8, the resampled
 //                  counts 4) + 512 bytes (the relative changes); br_quant_boot_counts 4 C a replicate of up to 16 at a time, the
 //                  summary 16 T
+//   genes          (G genes, CG gene classes, LG gene labels, LE distinct (class, gene) entries, LG <= LE <= L) holds 24 CG (first
+//                  name, count, label_off) + 4 LG (labels) + 24 G (unique, ambiguous, the offsets of a gene's transcripts) + 4 T
+//                  (the transcripts by gene); while it runs 4 T (the map) + 32 L (keys 2 x 8, indices 2 x 4, the scanned heads
+//                  8) and the radix histograms, then -- those freed -- 4 LE + 12 C (the arena, a class's offset and length) + 4
+//                  bytes per class of more than 64 genes + 40 C (keys 2 x 8, indices 2 x 4, heads 8, the scanned member counts
+//                  8; 4 C more for the run marks when hashes collide) + 36 CG (gene class starts 8, the second sort 2 x 8 + 2 x
+//                  4, the class whose list it is 4); br_quant_gene_result 8 T (tpm) + 8 T (lengths, if given) + 32 G while it
+//                  runs; the gene replicates hold 8 B G from the first br_quant_gene_boot* on, their summary 16 G
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -96,6 +115,17 @@ struct br_quant : Accum {
   double boot_sample_s = 0, boot_em_s = 0;
   int64_t boot_iters = 0;
   ColBuf boot_res, boot_cum;
+  // gene level: the tables br_quant_genes leaves, and the B x G gene replicates once they were asked for
+  struct Genes {
+    ColBuf first, cnt, loff, labels, uniq, ambig, toff, tx;   // per gene class; per gene; the transcripts by gene, ascending inside one
+    std::vector<uint32_t> n_tx;                               // transcripts per gene
+    int64_t n_cls = 0, n_lab = 0;
+    uint64_t collisions = 0;
+  } gene;
+  bool genes_done = false;
+  int64_t n_genes = 0;
+  double genes_s = 0;
+  ColBuf gene_boot;
 };
 // words of `small`
 enum { QS_BITS = 0, QS_COLL = 2, QS_SPAN = 3, QS_NBIG = 5, QS_MAXTID = 6, QS_BAD = 7, QS_REL = 8, QS_NBIG_CLS = 9, QS_NBIG_TX = 10, QS_WORDS = 16 };
@@ -673,6 +703,14 @@ extern "C" int br_quant_boot_stats(const br_quant *c, double *sample_seconds, do
   return BR_OK;
 }
 
+// tpm from x = theta w, which the stream has brought to the host: one pass over T numbers, in transcript order
+static void quant_tpm(const std::vector<double> &x, double *tpm) {
+  const size_t T = x.size();
+  double sum = 0.0;
+  for (size_t t = 0; t < T; t++) sum += x[t];
+  for (size_t t = 0; t < T; t++) tpm[t] = sum > 0.0 ? 1e6 * x[t] / sum : 0.0;
+}
+
 extern "C" int br_quant_result(br_quant *c, double *theta, double *tpm, uint64_t *unique, uint64_t *ambig) {
   if (!c || !c->finished || ((theta || tpm) && !c->em_done)) return BR_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
@@ -685,11 +723,236 @@ extern "C" int br_quant_result(br_quant *c, double *theta, double *tpm, uint64_t
   if (unique) HIPCHK(hipMemcpyAsync(unique, c->uniq.p, T * 8, hipMemcpyDeviceToHost, st));
   if (ambig) HIPCHK(hipMemcpyAsync(ambig, c->ambig.p, T * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  if (tpm) {   // one pass over T numbers, in transcript order
-    double sum = 0.0;
-    for (size_t t = 0; t < T; t++) sum += x[t];
-    for (size_t t = 0; t < T; t++) tpm[t] = sum > 0.0 ? 1e6 * x[t] / sum : 0.0;
+  if (tpm) quant_tpm(x, tpm);
+  return BR_OK;
+}
+
+// ---- gene level (the definitions: bramble_amd.h, br_quant) ---------------------------------------------------------------------------
+// The map is checked by the caller.  Everything is built in tables of the call's own, which become the object's at the end: a
+// call that fails leaves the object as it was.
+static int quant_genes(br_quant *c, const uint32_t *tx_gene, int64_t G) {
+  hipStream_t st = c->st;
+  const int64_t T = c->n_tx, C = c->n_cls, L = c->n_lab;
+  uint64_t *small = c->small.as<uint64_t>();
+  br_quant::Genes g;
+  DropGuard held{c, {&g.first, &g.cnt, &g.loff, &g.labels, &g.uniq, &g.ambig, &g.toff, &g.tx}};
+  // per gene its transcripts in ascending order: a counting sort of T numbers on the host
+  std::vector<uint64_t> toff((size_t)G + 1, 0);
+  std::vector<uint32_t> order((size_t)T);
+  g.n_tx.assign((size_t)G, 0);
+  for (int64_t t = 0; t < T; t++) g.n_tx[tx_gene[t]]++;
+  for (int64_t k = 0; k < G; k++) toff[(size_t)k + 1] = toff[(size_t)k] + g.n_tx[(size_t)k];
+  {
+    std::vector<uint64_t> at(toff.begin(), toff.end() - 1);
+    for (int64_t t = 0; t < T; t++) order[(size_t)at[tx_gene[t]]++] = (uint32_t)t;
   }
+  const size_t g1 = (size_t)G + 1;
+  RC(c->alloc(g.toff, g1 * 8)); RC(c->alloc(g.tx, ((size_t)T + 1) * 4)); RC(c->alloc(g.uniq, g1 * 8)); RC(c->alloc(g.ambig, g1 * 8));
+  HIPCHK(hipMemcpyAsync(g.toff.p, toff.data(), g1 * 8, hipMemcpyHostToDevice, st));
+  if (T) HIPCHK(hipMemcpyAsync(g.tx.p, order.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(g.uniq.p, 0, g1 * 8, st)); HIPCHK(hipMemsetAsync(g.ambig.p, 0, g1 * 8, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (C > 0) {
+    ColBuf d_txg, key[2], idx[2], pos, glab, goff, gk, big, head, mark, pre, gbeg, key2[2], val2[2], rep;
+    DropGuard tables{c, {&d_txg, &key[0], &key[1], &idx[0], &idx[1], &pos, &glab, &goff, &gk, &big, &head, &mark, &pre, &gbeg, &key2[0], &key2[1],
+                         &val2[0], &val2[1], &rep}};
+    // the distinct (class, gene) entries, a class's genes ascending: the gene-label arena
+    const size_t l1 = (size_t)L + 1, c1 = (size_t)C + 1;
+    RC(c->alloc(d_txg, ((size_t)T + 1) * 4));
+    HIPCHK(hipMemcpyAsync(d_txg.p, tx_gene, (size_t)T * 4, hipMemcpyHostToDevice, st));
+    RC(c->alloc(key[0], l1 * 8)); RC(c->alloc(key[1], l1 * 8)); RC(c->alloc(idx[0], l1 * 4)); RC(c->alloc(idx[1], l1 * 4));
+    launch_qg_key(st, c->c_loff.as<uint64_t>(), c->c_labels.as<uint32_t>(), d_txg.as<uint32_t>(), C, L, key[0].as<uint64_t>(), idx[0].as<uint32_t>());
+    int cur = 0;
+    RC(quant_sort(c, key, idx, L, &cur));
+    RC(c->alloc(pos, l1 * 8)); RC(quant_tmp(c, L));
+    launch_qg_flag(st, key[cur].as<uint64_t>(), L, pos.as<uint64_t>());
+    launch_scan(st, pos.as<uint64_t>(), L, c->tmp.as<uint64_t>());
+    uint64_t LE = 0;
+    HIPCHK(hipMemcpyAsync(&LE, pos.as<uint64_t>() + L, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (LE == 0 || LE > (uint64_t)L) return BR_ERR_HIP;
+    RC(c->alloc(glab, ((size_t)LE + 1) * 4)); RC(c->alloc(goff, c1 * 8)); RC(c->alloc(gk, c1 * 4));
+    launch_qg_arena(st, key[cur].as<uint64_t>(), pos.as<uint64_t>(), c->c_loff.as<uint64_t>(), L, C, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>());
+    HIPCHK(hipStreamSynchronize(st));
+    c->drop(d_txg); c->drop(pos);
+    for (int k = 0; k < 2; k++) { c->drop(key[k]); c->drop(idx[k]); }
+    // the classes by the hash of their gene lists; from here it is finish's sequence with a class where finish has a name
+    const size_t most = (size_t)(LE / (Q_WAVE_ITEMS + 1) + 1);
+    RC(c->alloc(big, most * 4));
+    HIPCHK(hipMemsetAsync(small + QS_NBIG, 0, 8, st));
+    launch_q_bin(st, goff.as<uint64_t>(), C, big.as<uint32_t>(), (uint32_t *)(small + QS_NBIG));
+    uint32_t n_big = 0;
+    HIPCHK(hipMemcpyAsync(&n_big, small + QS_NBIG, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    RC(c->alloc(key[0], c1 * 8)); RC(c->alloc(key[1], c1 * 8)); RC(c->alloc(idx[0], c1 * 4)); RC(c->alloc(idx[1], c1 * 4));
+    const uint64_t mask = c->hash_bits >= 64 ? ~0ull : (1ull << c->hash_bits) - 1;
+    launch_qg_hash(st, glab.as<uint32_t>(), goff.as<uint64_t>(), C, big.as<uint32_t>(), n_big, mask, key[0].as<uint64_t>(), idx[0].as<uint32_t>());
+    RC(quant_sort(c, key, idx, C, &cur));
+    RC(c->alloc(head, c1 * 8));
+    auto heads = [&](uint32_t *mk, uint64_t *n_coll) -> int {
+      HIPCHK(hipMemsetAsync(small + QS_COLL, 0, 8, st));
+      launch_q_heads(st, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>(), key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), C, head.as<uint64_t>(),
+                     (unsigned long long *)(small + QS_COLL), mk);
+      HIPCHK(hipMemcpyAsync(n_coll, small + QS_COLL, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      return BR_OK;
+    };
+    uint64_t n_coll = 0;
+    RC(heads(nullptr, &n_coll));
+    g.collisions = n_coll;
+    if (n_coll) {
+      RC(c->alloc(mark, (size_t)C * 4));
+      HIPCHK(hipMemsetAsync(mark.p, 0, (size_t)C * 4, st));
+      RC(heads(mark.as<uint32_t>(), &n_coll));
+      launch_q_resolve(st, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>(), key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), C, mark.as<uint32_t>(),
+                       key[cur ^ 1].as<uint64_t>(), idx[cur ^ 1].as<uint32_t>());
+      cur ^= 1;
+      RC(heads(nullptr, &n_coll));
+    }
+    RC(quant_tmp(c, C));
+    launch_scan(st, head.as<uint64_t>(), C, c->tmp.as<uint64_t>());   // head -> gene class ids (exclusive), head[C] = their number
+    uint64_t CG = 0;
+    HIPCHK(hipMemcpyAsync(&CG, head.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (CG == 0 || CG > (uint64_t)C) return BR_ERR_HIP;
+    const size_t cg1 = (size_t)CG + 1;
+    RC(c->alloc(gbeg, cg1 * 8));
+    launch_col_gbeg(st, head.as<uint64_t>(), C, gbeg.as<uint64_t>());
+    // a gene class's count: the integer sum of its members' counts, from one scan over the members in sorted order
+    RC(c->alloc(pre, c1 * 8));
+    launch_qg_member_cnt(st, idx[cur].as<uint32_t>(), c->c_cnt.as<uint64_t>(), C, pre.as<uint64_t>());
+    launch_scan(st, pre.as<uint64_t>(), C, c->tmp.as<uint64_t>());
+    // the gene classes by their first name
+    RC(c->alloc(key2[0], cg1 * 8)); RC(c->alloc(key2[1], cg1 * 8)); RC(c->alloc(val2[0], cg1 * 4)); RC(c->alloc(val2[1], cg1 * 4));
+    launch_qg_class_key(st, gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), c->c_first.as<uint64_t>(), (int64_t)CG, key2[0].as<uint64_t>(), val2[0].as<uint32_t>());
+    int cur2 = 0;
+    RC(quant_sort(c, key2, val2, (int64_t)CG, &cur2));
+    RC(c->alloc(g.first, cg1 * 8)); RC(c->alloc(g.cnt, cg1 * 8)); RC(c->alloc(g.loff, cg1 * 8)); RC(c->alloc(rep, cg1 * 4));
+    launch_qg_class_fill(st, key2[cur2].as<uint64_t>(), val2[cur2].as<uint32_t>(), gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), pre.as<uint64_t>(),
+                         gk.as<uint32_t>(), (int64_t)CG, g.first.as<uint64_t>(), g.cnt.as<uint64_t>(), g.loff.as<uint64_t>(), rep.as<uint32_t>());
+    RC(quant_tmp(c, (int64_t)CG));
+    launch_scan(st, g.loff.as<uint64_t>(), (int64_t)CG, c->tmp.as<uint64_t>());
+    uint64_t LG = 0;
+    HIPCHK(hipMemcpyAsync(&LG, g.loff.as<uint64_t>() + CG, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (LG == 0 || LG > LE) return BR_ERR_HIP;
+    RC(c->alloc(g.labels, ((size_t)LG + 1) * 4));
+    launch_qg_labels(st, g.loff.as<uint64_t>(), rep.as<uint32_t>(), goff.as<uint64_t>(), glab.as<uint32_t>(), g.cnt.as<uint64_t>(), (int64_t)CG, (int64_t)LG,
+                     g.labels.as<uint32_t>(), g.uniq.as<uint64_t>(), g.ambig.as<uint64_t>());
+    HIPCHK(hipStreamSynchronize(st));
+    g.n_cls = (int64_t)CG; g.n_lab = (int64_t)LG;
+  }
+  c->gene = std::move(g);   // (a swap: the guard drops the empty tables the object had)
+  return BR_OK;
+}
+
+extern "C" int br_quant_genes(br_quant *c, const uint32_t *tx_gene, int64_t n_genes, int64_t *n_gene_classes) {
+  if (!c || !c->finished || c->genes_done || n_genes < 0 || n_genes >= (1ll << 32) || (c->n_tx && !tx_gene)) return BR_ERR_INVALID_ARG;
+  for (int64_t t = 0; t < c->n_tx; t++) if ((int64_t)tx_gene[t] >= n_genes) return BR_ERR_INVALID_ARG;
+  const ScopeTimer timer;
+  HIPCHK(hipSetDevice(c->device));
+  RC(quant_genes(c, tx_gene, n_genes));
+  c->n_genes = n_genes; c->genes_done = true;
+  c->genes_s = timer.seconds();
+  if (n_gene_classes) *n_gene_classes = c->gene.n_cls;
+  return BR_OK;
+}
+
+extern "C" int br_quant_gene_classes(br_quant *c, uint64_t *label_off, uint32_t *labels, uint64_t *counts, uint64_t *first_name) {
+  if (!c || !c->genes_done) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  const size_t C = (size_t)c->gene.n_cls, L = (size_t)c->gene.n_lab;
+  if (label_off) { if (C) HIPCHK(hipMemcpyAsync(label_off, c->gene.loff.p, (C + 1) * 8, hipMemcpyDeviceToHost, st)); else label_off[0] = 0; }
+  if (labels && L) HIPCHK(hipMemcpyAsync(labels, c->gene.labels.p, L * 4, hipMemcpyDeviceToHost, st));
+  if (counts && C) HIPCHK(hipMemcpyAsync(counts, c->gene.cnt.p, C * 8, hipMemcpyDeviceToHost, st));
+  if (first_name && C) HIPCHK(hipMemcpyAsync(first_name, c->gene.first.p, C * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return BR_OK;
+}
+
+extern "C" int br_quant_gene_result(br_quant *c, double *num_reads, double *tpm, double *length, double *eff_length, uint64_t *unique,
+                                    uint64_t *ambig, uint32_t *n_transcripts) {
+  if (!c || !c->genes_done) return BR_ERR_INVALID_ARG;
+  const bool sums = num_reads || tpm || length || eff_length;
+  if (sums && !c->em_done) return BR_ERR_INVALID_ARG;
+  if (eff_length && (!c->eff_len || !c->eff.p)) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  const size_t T = (size_t)c->n_tx, G = (size_t)c->n_genes;
+  if (!G) return BR_OK;
+  ColBuf d_tpm, d_lens, out;   // out: num_reads, tpm, length, eff_length
+  DropGuard dropper{c, {&d_tpm, &d_lens, &out}};
+  std::vector<double> x(T), tpm_t(T);
+  if (sums) {
+    const bool has_lens = !c->lens.empty();
+    RC(c->alloc(d_tpm, (T + 1) * 8)); RC(c->alloc(out, (4 * G + 1) * 8));
+    if (has_lens) RC(c->alloc(d_lens, (T + 1) * 8));
+    if (T) HIPCHK(hipMemcpyAsync(x.data(), c->x[c->cur].p, T * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    quant_tpm(x, tpm_t.data());   // the values br_quant_result returns
+    if (T) HIPCHK(hipMemcpyAsync(d_tpm.p, tpm_t.data(), T * 8, hipMemcpyHostToDevice, st));
+    if (T && has_lens) HIPCHK(hipMemcpyAsync(d_lens.p, c->lens.data(), T * 8, hipMemcpyHostToDevice, st));
+    double *o = out.as<double>();
+    launch_qg_sums(st, c->gene.toff.as<uint64_t>(), c->gene.tx.as<uint32_t>(), (int64_t)G, c->theta[c->cur].as<double>(), d_tpm.as<double>(),
+                   has_lens ? d_lens.as<int64_t>() : nullptr, eff_length ? c->eff.as<double>() : nullptr, o, o + G, o + 2 * G, eff_length ? o + 3 * G : nullptr);
+    if (num_reads) HIPCHK(hipMemcpyAsync(num_reads, o, G * 8, hipMemcpyDeviceToHost, st));
+    if (tpm) HIPCHK(hipMemcpyAsync(tpm, o + G, G * 8, hipMemcpyDeviceToHost, st));
+    if (length) HIPCHK(hipMemcpyAsync(length, o + 2 * G, G * 8, hipMemcpyDeviceToHost, st));
+    if (eff_length) HIPCHK(hipMemcpyAsync(eff_length, o + 3 * G, G * 8, hipMemcpyDeviceToHost, st));
+  }
+  if (unique) HIPCHK(hipMemcpyAsync(unique, c->gene.uniq.p, G * 8, hipMemcpyDeviceToHost, st));
+  if (ambig) HIPCHK(hipMemcpyAsync(ambig, c->gene.ambig.p, G * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (n_transcripts) memcpy(n_transcripts, c->gene.n_tx.data(), G * 4);
+  return BR_OK;
+}
+
+// the B x G gene replicates, made from the B x T result when they are first asked for (br_quant_genes and br_quant_bootstrap come
+// in either order) and held from then on
+static int quant_gene_boot(br_quant *c) {
+  if (c->gene_boot.p) return BR_OK;
+  const size_t B = (size_t)c->bootstraps, G = (size_t)c->n_genes;
+  ColBuf t;
+  DropGuard dropper{c, {&t}};
+  RC(c->alloc(t, (B * G + 1) * 8));
+  launch_qg_boot(c->st, c->boot_res.as<double>(), c->n_tx, (int64_t)B, c->gene.toff.as<uint64_t>(), c->gene.tx.as<uint32_t>(), (int64_t)G, t.as<double>());
+  HIPCHK(hipStreamSynchronize(c->st));
+  c->gene_boot = std::move(t);
+  return BR_OK;
+}
+
+extern "C" int br_quant_gene_boot(br_quant *c, int32_t first, int32_t count, double *num_reads) {
+  if (!c || !c->genes_done || !c->boot_done || !c->boot_res.p || first < 0 || count < 0 || (int64_t)first + count > c->bootstraps) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  RC(quant_gene_boot(c));
+  const size_t G = (size_t)c->n_genes;
+  if (num_reads && G && count) HIPCHK(hipMemcpyAsync(num_reads, c->gene_boot.as<double>() + (size_t)first * G, (size_t)count * G * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return BR_OK;
+}
+
+extern "C" int br_quant_gene_boot_summary(br_quant *c, double *mean, double *var) {
+  if (!c || !c->genes_done || !c->boot_done || !c->boot_res.p) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  RC(quant_gene_boot(c));
+  hipStream_t st = c->st;
+  const size_t G = (size_t)c->n_genes;
+  ColBuf mv;   // mean, then var
+  DropGuard dropper{c, {&mv}};
+  RC(c->alloc(mv, (2 * G + 1) * 8));
+  launch_q_boot_summary(st, c->gene_boot.as<double>(), (int64_t)G, (int32_t)c->bootstraps, mv.as<double>(), mv.as<double>() + G);
+  if (mean && G) HIPCHK(hipMemcpyAsync(mean, mv.p, G * 8, hipMemcpyDeviceToHost, st));
+  if (var && G) HIPCHK(hipMemcpyAsync(var, mv.as<double>() + G, G * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return BR_OK;
+}
+
+extern "C" int br_quant_gene_stats(const br_quant *c, double *seconds, int64_t *n_gene_labels, uint64_t *collisions) {
+  if (!c) return BR_ERR_INVALID_ARG;
+  if (seconds) *seconds = c->genes_s;
+  if (n_gene_labels) *n_gene_labels = c->gene.n_lab;
+  if (collisions) *collisions = c->gene.collisions;
   return BR_OK;
 }
 

@@ -116,4 +116,34 @@ void launch_q_boot_store(hipStream_t st, const double *theta, int64_t n_tx, int 
 // mean and variance (over n_boot - 1; 0 for n_boot = 1) per transcript of the n_boot x n_tx result, summed in replicate order
 void launch_q_boot_summary(hipStream_t st, const double *res, int64_t n_tx, int32_t n_boot, double *mean, double *var);
 
+// Gene level (definitions: bramble_amd.h, br_quant).
+// key[e] = (class of label entry e << 32) | tx_gene[labels[e]], idx[e] = e: to be sorted
+void launch_qg_key(hipStream_t st, const uint64_t *label_off, const uint32_t *labels, const uint32_t *tx_gene, int64_t n_cls, int64_t n_lab,
+                   uint64_t *key, uint32_t *idx);
+// flag[e] = sorted key e differs from key e - 1: a distinct (class, gene) entry (to be scanned)
+void launch_qg_flag(hipStream_t st, const uint64_t *key, int64_t n, uint64_t *flag);
+// the gene-label arena from the sorted keys and the scanned flags: glab, and per class its offset (n_cls + 1) and length
+void launch_qg_arena(hipStream_t st, const uint64_t *key, const uint64_t *pos, const uint64_t *label_off, int64_t n_lab, int64_t n_cls,
+                     uint32_t *glab, uint64_t *goff, uint32_t *gk);
+// key[c] = the names' hash of class c's gene list under mask, idx[c] = c; big: the classes of more than Q_WAVE_ITEMS genes (launch_q_bin)
+void launch_qg_hash(hipStream_t st, const uint32_t *glab, const uint64_t *goff, int64_t n_cls, const uint32_t *big, uint32_t n_big, uint64_t mask,
+                    uint64_t *key, uint32_t *idx);
+// w[j] = cnt[idx[j]]: the sorted members' counts (to be scanned)
+void launch_qg_member_cnt(hipStream_t st, const uint32_t *idx, const uint64_t *cnt, int64_t n, uint64_t *w);
+// gene classes in hash order -> (first name, gene class in hash order), to be sorted
+void launch_qg_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *c_first, int64_t n, uint64_t *key, uint32_t *val);
+// gene classes in their final order: first name, count (pre: the scanned member counts), number of labels (to be scanned) and
+// the transcript class whose list is theirs
+void launch_qg_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *pre,
+                          const uint32_t *gk, int64_t n, uint64_t *first, uint64_t *cnt, uint64_t *label_off, uint32_t *rep);
+// labels[e], and cnt of e's class added to uniq / ambig of its gene (zeroed by the caller)
+void launch_qg_labels(hipStream_t st, const uint64_t *label_off, const uint32_t *rep, const uint64_t *goff, const uint32_t *glab, const uint64_t *cnt,
+                      int64_t n_cls, int64_t n_lab, uint32_t *labels, uint64_t *uniq, uint64_t *ambig);
+// per gene the sums over its transcripts g_tx[g_toff[g] .. g_toff[g + 1]) in that order; lens / eff / eff_length may be NULL
+void launch_qg_sums(hipStream_t st, const uint64_t *g_toff, const uint32_t *g_tx, int64_t n_genes, const double *theta, const double *tpm_t,
+                    const int64_t *lens, const double *eff, double *num_reads, double *tpm, double *length, double *eff_length);
+// out[b * n_genes + g] = the sum of res[b * n_tx + t] over the gene's transcripts in that order
+void launch_qg_boot(hipStream_t st, const double *res, int64_t n_tx, int64_t n_boot, const uint64_t *g_toff, const uint32_t *g_tx, int64_t n_genes,
+                    double *out);
+
 }  // namespace br

@@ -12,6 +12,11 @@
 //   bootstrap  k_q_boot_sample (a lane per draw: Philox4x32-10, a binary search in the scanned counts, an integer atomicAdd);
 //            k_q_boot_classes / k_q_boot_tx, the EM over a chunk of W replicates with the replicate innermost, a lane per (item,
 //            replicate) and a wave per larger item; k_q_boot_store, k_q_boot_summary
+//   genes    k_qg_key + radix passes + k_qg_flag + scan + k_qg_arena: a class's distinct genes, ascending; k_qg_hash (a lane, or a
+//            wave above Q_WAVE_ITEMS genes); the classes' sequence again on the gene lists -- radix passes, k_q_heads, k_q_resolve --
+//            then k_qg_member_cnt + scan (a gene class's count), k_qg_class_key, k_qg_class_fill, k_qg_labels (with the unique /
+//            ambiguous names per gene: integer atomics); k_qg_sums (a lane a gene, its transcripts one after the other) and
+//            k_qg_boot (a lane per replicate and gene)
 //   lengths  ("eff_len") k_q_frag / k_q_frag_big behind the names of an add: per read name of one label the length of its first
 //            fragment, counted in LDS by integer atomics and flushed to the add's own table with one integer atomicAdd per
 //            non-zero bin and block; k_q_fld_commit adds a good add's table to the run's; at finish k_q_fld_prefix (C and S) and
@@ -688,6 +693,170 @@ __global__ void __launch_bounds__(256) k_q_boot_summary(const double *res, int64
   double v = 0.0;
   for (int32_t b = 0; b < n_boot; b++) { const double d = res[(int64_t)b * n_tx + t] - m; v = __dadd_rn(v, __dmul_rn(d, d)); }
   mean[t] = m; var[t] = n_boot > 1 ? v / (double)(n_boot - 1) : 0.0;
+}
+
+// ---- gene level (the definitions: bramble_amd.h, br_quant) -------------------------------------------------------------------------
+// The transcript classes relabelled by gene and merged.  A class's gene list -- the distinct genes of its labels, ascending --
+// comes from one radix sort of (class, gene) keys; the lists go through finish's own sequence with a class where finish has a
+// name: k_q_heads / k_q_resolve compare them under the hash, a scan of the members' counts gives a gene class its count, and
+// its first member in class order (the classes are in the order of their first names) gives its first name.
+namespace {
+// the class of label entry e: the last c with label_off[c] <= e
+__device__ __forceinline__ int64_t class_of_entry(const uint64_t *label_off, int64_t n_cls, int64_t e) {
+  int64_t lo = 0, hi = n_cls;
+  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (label_off[mid] <= (uint64_t)e) lo = mid + 1; else hi = mid; }
+  return lo - 1;
+}
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_qg_key(const uint64_t *label_off, const uint32_t *labels, const uint32_t *tx_gene, int64_t n_cls,
+                                                int64_t n_lab, uint64_t *key, uint32_t *idx) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_lab) return;
+  key[e] = ((uint64_t)class_of_entry(label_off, n_cls, e) << 32) | (uint64_t)tx_gene[labels[e]];
+  idx[e] = (uint32_t)e;
+}
+__global__ void __launch_bounds__(256) k_qg_flag(const uint64_t *key, int64_t n, uint64_t *flag) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < n) flag[e] = e == 0 || key[e] != key[e - 1] ? 1 : 0;
+}
+// pos: the scanned flags.  The sorted keys keep a class's entries in its own range of label_off, so its list starts at
+// pos[label_off[c]] of the arena
+__global__ void __launch_bounds__(256) k_qg_arena(const uint64_t *key, const uint64_t *pos, const uint64_t *label_off, int64_t n_lab,
+                                                  int64_t n_cls, uint32_t *glab, uint64_t *goff, uint32_t *gk) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n_lab && pos[i + 1] != pos[i]) glab[pos[i]] = (uint32_t)key[i];
+  if (i <= n_cls) goff[i] = pos[label_off[i]];
+  if (i < n_cls) gk[i] = (uint32_t)(pos[label_off[i + 1]] - pos[label_off[i]]);
+}
+// the hash the names get, of a class's gene list: a lane per list of up to Q_WAVE_ITEMS genes; a wave per larger one loads 64
+// genes at a time and every lane steps through them (the chain is sequential)
+template <bool BIG>
+__global__ void __launch_bounds__(256) k_qg_hash(const uint32_t *glab, const uint64_t *goff, int64_t n_cls, const uint32_t *big, uint32_t n_big,
+                                                 uint64_t mask, uint64_t *key, uint32_t *idx) {
+  if (BIG) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= n_big) return;   // (wave-uniform)
+    const uint32_t c = big[i];
+    const uint64_t o = goff[c], k = goff[c + 1] - o;
+    uint64_t h = 1469598103934665603ull;
+    for (uint64_t base = 0; base < k; base += 64) {
+      const uint32_t v = base + (uint64_t)lane < k ? glab[o + base + (uint64_t)lane] : 0u;
+      const int n = k - base < 64 ? (int)(k - base) : 64;
+      for (int j = 0; j < n; j++) h = hash_step(h, (uint64_t)(uint32_t)__shfl((int)v, j));
+    }
+    if (lane == 0) { key[c] = hash_end(h, k) & mask; idx[c] = c; }
+  } else {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_cls) return;
+    const uint64_t o = goff[c], k = goff[c + 1] - o;
+    if (k > (uint64_t)Q_WAVE_ITEMS) return;
+    uint64_t h = 1469598103934665603ull;
+    for (uint64_t j = 0; j < k; j++) h = hash_step(h, glab[o + j]);
+    key[c] = hash_end(h, k) & mask; idx[c] = (uint32_t)c;
+  }
+}
+__global__ void __launch_bounds__(256) k_qg_member_cnt(const uint32_t *idx, const uint64_t *cnt, int64_t n, uint64_t *w) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < n) w[j] = cnt[idx[j]];
+}
+__global__ void __launch_bounds__(256) k_qg_class_key(const uint64_t *gbeg, const uint32_t *idx, const uint64_t *c_first, int64_t n,
+                                                      uint64_t *key, uint32_t *val) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g < n) { key[g] = c_first[idx[gbeg[g]]]; val[g] = (uint32_t)g; }   // (members ascend: the first one has the smallest first name)
+}
+__global__ void __launch_bounds__(256) k_qg_class_fill(const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx,
+                                                       const uint64_t *pre, const uint32_t *gk, int64_t n, uint64_t *first, uint64_t *cnt,
+                                                       uint64_t *label_off, uint32_t *rep) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= n) return;
+  const uint32_t s = val[g], r = idx[gbeg[s]];
+  first[g] = key[g]; cnt[g] = pre[gbeg[s + 1]] - pre[gbeg[s]]; label_off[g] = gk[r]; rep[g] = r;
+}
+// one lane per gene-label entry: the label, and the class's count to its gene's unique or ambiguous names (integer atomics)
+__global__ void __launch_bounds__(256) k_qg_labels(const uint64_t *label_off, const uint32_t *rep, const uint64_t *goff, const uint32_t *glab,
+                                                   const uint64_t *cnt, int64_t n_cls, int64_t n_lab, uint32_t *labels,
+                                                   unsigned long long *uniq, unsigned long long *ambig) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_lab) return;
+  const int64_t c = class_of_entry(label_off, n_cls, e);
+  const uint32_t g = glab[goff[rep[c]] + ((uint64_t)e - label_off[c])];
+  labels[e] = g;
+  atomicAdd((label_off[c + 1] - label_off[c] == 1 ? uniq : ambig) + g, (unsigned long long)cnt[c]);
+}
+// one lane per gene, its transcripts one after the other in ascending order; every product is rounded before it is added
+__global__ void __launch_bounds__(256) k_qg_sums(const uint64_t *g_toff, const uint32_t *g_tx, int64_t n_genes, const double *theta,
+                                                 const double *tpm_t, const int64_t *lens, const double *eff, double *num_reads, double *tpm,
+                                                 double *length, double *eff_length) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= n_genes) return;
+  const uint64_t p0 = g_toff[g], p1 = g_toff[g + 1];
+  double nr = 0.0, tp = 0.0, wl = 0.0, sl = 0.0, we = 0.0, se = 0.0;
+  for (uint64_t p = p0; p < p1; p++) {
+    const uint32_t t = g_tx[p];
+    const double v = tpm_t[t];
+    nr = __dadd_rn(nr, theta[t]); tp = __dadd_rn(tp, v);
+    if (lens) { const double l = (double)lens[t]; wl = __dadd_rn(wl, __dmul_rn(v, l)); sl = __dadd_rn(sl, l); }
+    if (eff) { const double l = eff[t]; we = __dadd_rn(we, __dmul_rn(v, l)); se = __dadd_rn(se, l); }
+  }
+  const double n = (double)(p1 - p0);
+  num_reads[g] = nr; tpm[g] = tp;
+  length[g] = !lens || p1 == p0 ? 0.0 : tp > 0.0 ? wl / tp : sl / n;
+  if (eff_length) eff_length[g] = !eff || p1 == p0 ? 0.0 : tp > 0.0 ? we / tp : se / n;
+}
+// one lane per (replicate, gene) of the n_boot x n_tx result
+__global__ void __launch_bounds__(256) k_qg_boot(const double *res, int64_t n_tx, int64_t n_boot, const uint64_t *g_toff, const uint32_t *g_tx,
+                                                 int64_t n_genes, double *out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_boot * n_genes) return;
+  const int64_t b = i / n_genes, g = i - b * n_genes;
+  const double *row = res + b * n_tx;
+  double s = 0.0;
+  for (uint64_t p = g_toff[g]; p < g_toff[g + 1]; p++) s = __dadd_rn(s, row[g_tx[p]]);
+  out[i] = s;
+}
+
+void launch_qg_key(hipStream_t st, const uint64_t *label_off, const uint32_t *labels, const uint32_t *tx_gene, int64_t n_cls, int64_t n_lab,
+                   uint64_t *key, uint32_t *idx) {
+  if (n_lab > 0) hipLaunchKernelGGL(k_qg_key, dim3(blocks256(n_lab)), dim3(256), 0, st, label_off, labels, tx_gene, n_cls, n_lab, key, idx);
+}
+void launch_qg_flag(hipStream_t st, const uint64_t *key, int64_t n, uint64_t *flag) {
+  if (n > 0) hipLaunchKernelGGL(k_qg_flag, dim3(blocks256(n)), dim3(256), 0, st, key, n, flag);
+}
+void launch_qg_arena(hipStream_t st, const uint64_t *key, const uint64_t *pos, const uint64_t *label_off, int64_t n_lab, int64_t n_cls,
+                     uint32_t *glab, uint64_t *goff, uint32_t *gk) {
+  const int64_t m = n_lab > n_cls + 1 ? n_lab : n_cls + 1;
+  hipLaunchKernelGGL(k_qg_arena, dim3(blocks256(m)), dim3(256), 0, st, key, pos, label_off, n_lab, n_cls, glab, goff, gk);
+}
+void launch_qg_hash(hipStream_t st, const uint32_t *glab, const uint64_t *goff, int64_t n_cls, const uint32_t *big, uint32_t n_big, uint64_t mask,
+                    uint64_t *key, uint32_t *idx) {
+  if (n_cls > 0) hipLaunchKernelGGL(k_qg_hash<false>, dim3(blocks256(n_cls)), dim3(256), 0, st, glab, goff, n_cls, big, n_big, mask, key, idx);
+  if (n_big) hipLaunchKernelGGL(k_qg_hash<true>, dim3((n_big + 3) / 4), dim3(256), 0, st, glab, goff, n_cls, big, n_big, mask, key, idx);
+}
+void launch_qg_member_cnt(hipStream_t st, const uint32_t *idx, const uint64_t *cnt, int64_t n, uint64_t *w) {
+  if (n > 0) hipLaunchKernelGGL(k_qg_member_cnt, dim3(blocks256(n)), dim3(256), 0, st, idx, cnt, n, w);
+}
+void launch_qg_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *c_first, int64_t n, uint64_t *key, uint32_t *val) {
+  if (n > 0) hipLaunchKernelGGL(k_qg_class_key, dim3(blocks256(n)), dim3(256), 0, st, gbeg, idx, c_first, n, key, val);
+}
+void launch_qg_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *pre,
+                          const uint32_t *gk, int64_t n, uint64_t *first, uint64_t *cnt, uint64_t *label_off, uint32_t *rep) {
+  if (n > 0) hipLaunchKernelGGL(k_qg_class_fill, dim3(blocks256(n)), dim3(256), 0, st, key, val, gbeg, idx, pre, gk, n, first, cnt, label_off, rep);
+}
+void launch_qg_labels(hipStream_t st, const uint64_t *label_off, const uint32_t *rep, const uint64_t *goff, const uint32_t *glab, const uint64_t *cnt,
+                      int64_t n_cls, int64_t n_lab, uint32_t *labels, uint64_t *uniq, uint64_t *ambig) {
+  if (n_lab > 0) hipLaunchKernelGGL(k_qg_labels, dim3(blocks256(n_lab)), dim3(256), 0, st, label_off, rep, goff, glab, cnt, n_cls, n_lab, labels,
+                                    (unsigned long long *)uniq, (unsigned long long *)ambig);
+}
+void launch_qg_sums(hipStream_t st, const uint64_t *g_toff, const uint32_t *g_tx, int64_t n_genes, const double *theta, const double *tpm_t,
+                    const int64_t *lens, const double *eff, double *num_reads, double *tpm, double *length, double *eff_length) {
+  if (n_genes > 0) hipLaunchKernelGGL(k_qg_sums, dim3(blocks256(n_genes)), dim3(256), 0, st, g_toff, g_tx, n_genes, theta, tpm_t, lens, eff, num_reads,
+                                      tpm, length, eff_length);
+}
+void launch_qg_boot(hipStream_t st, const double *res, int64_t n_tx, int64_t n_boot, const uint64_t *g_toff, const uint32_t *g_tx, int64_t n_genes,
+                    double *out) {
+  if (n_boot * n_genes > 0) hipLaunchKernelGGL(k_qg_boot, dim3(blocks256(n_boot * n_genes)), dim3(256), 0, st, res, n_tx, n_boot, g_toff, g_tx, n_genes, out);
 }
 
 void launch_q_boot_sample(hipStream_t st, const uint64_t *cum, int64_t n_cls, uint64_t n, uint64_t seed, uint32_t b_first, uint32_t n_rep,

@@ -169,7 +169,7 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_config_long_read", "br_config_resolve", "br_batch_prepare", "br_batch_seq_source", "br_ctx_new", "br_ctx_free",
            "br_project_batch", "br_project_batch_device", "br_device_rows_expand", "br_batch_stage", "br_project_staged", "br_host_rows_wait", "br_project_batch_packed",
            "br_pin_host", "br_unpin_host", "br_project_group", "br_project_groups", "br_bam_encode_device", "br_project_bam_device", "br_project_bam_bundle", "br_bam_bundle_stage", "br_project_bam_staged", "br_bam_split", "br_annotation_load", "br_annotation_load_mt", "br_annotation_free",
-           "br_annotation_num_transcripts", "br_annotation_transcripts", "br_annotation_num_refs", "br_annotation_refnames", "br_cli_main", "br_cli_exit_at_end", "br_device_warmup", "br_project_bam_staged_nowait", "br_host_bam_wait", "br_bgzf_scan", "br_bgzf_inflate_device", "br_bam_split_device", "br_bam_reader_new", "br_bam_reader_next", "br_bam_reader_set_piece_blocks", "br_bam_reader_release", "br_bam_reader_free", "br_bam_piece_upload", "br_bam_piece_process", "br_bam_reader_seconds", "br_bam_reader_upload_seconds", "br_project_bam_resident", "br_bgzf_write_file", "br_bgzf_read_file",
+           "br_annotation_num_transcripts", "br_annotation_transcripts", "br_annotation_num_refs", "br_annotation_refnames", "br_annotation_gene_ids", "br_cli_main", "br_cli_exit_at_end", "br_device_warmup", "br_project_bam_staged_nowait", "br_host_bam_wait", "br_bgzf_scan", "br_bgzf_inflate_device", "br_bam_split_device", "br_bam_reader_new", "br_bam_reader_next", "br_bam_reader_set_piece_blocks", "br_bam_reader_release", "br_bam_reader_free", "br_bam_piece_upload", "br_bam_piece_process", "br_bam_reader_seconds", "br_bam_reader_upload_seconds", "br_project_bam_resident", "br_bgzf_write_file", "br_bgzf_read_file",
            "br_ctx_set_sam_refs", "br_sam_format_device",
            "br_sam_header_scan", "br_sam_reader_new", "br_sam_reader_next", "br_sam_reader_upload", "br_sam_reader_next_staged", "br_sam_reader_release", "br_sam_reader_free", "br_sam_reader_error", "br_sam_reader_stats",
            "br_collator_new", "br_collator_add", "br_collator_finish", "br_collator_next", "br_collator_order", "br_collator_set_param",
@@ -179,6 +179,7 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_quant_new", "br_quant_set_param", "br_quant_set_tolerance", "br_quant_add", "br_quant_add_rows", "br_quant_add_last", "br_quant_finish",
            "br_quant_classes", "br_quant_em", "br_quant_result", "br_quant_fld", "br_quant_eff_lengths", "br_quant_stats", "br_quant_free",
            "br_quant_bootstrap", "br_quant_boot_counts", "br_quant_boot_theta", "br_quant_boot_summary", "br_quant_boot_stats",
+           "br_quant_genes", "br_quant_gene_classes", "br_quant_gene_result", "br_quant_gene_boot", "br_quant_gene_boot_summary", "br_quant_gene_stats",
            "br_coverage_new", "br_coverage_set_param", "br_coverage_add_rows", "br_coverage_add_last", "br_coverage_finish", "br_coverage_runs",
            "br_coverage_depth", "br_coverage_summary", "br_coverage_stats", "br_coverage_free",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
@@ -279,6 +280,33 @@ def lib():
         L.br_strerror.argtypes = [C.c_int]
         _LIB = L
     return _LIB
+
+
+def load_annotation(path, threads=None):
+    """The guide loader (br_annotation_load / br_annotation_load_mt with `threads`) on a GTF / GFF3 file, plain or gzip -> dict of
+    refnames (order of first appearance), transcripts ({id, seqname, strand, exons (1-based half-open)}, in the loader's order)
+    and gene_ids (the gene of every transcript, in that order)."""
+    L = lib()
+    L.br_annotation_load.argtypes = [C.c_char_p, _P(C.c_void_p)]
+    L.br_annotation_load_mt.argtypes = [C.c_char_p, C.c_int, _P(C.c_void_p)]
+    L.br_annotation_free.argtypes = [C.c_void_p]
+    for name, res in (("num_transcripts", C.c_size_t), ("num_refs", C.c_size_t), ("transcripts", _P(BrTranscript)),
+                      ("refnames", _P(C.c_char_p)), ("gene_ids", _P(C.c_char_p))):
+        f = getattr(L, "br_annotation_" + name)
+        f.restype, f.argtypes = res, [C.c_void_p]
+    h = C.c_void_p()
+    if threads is None:
+        check(L.br_annotation_load(os.fsencode(path), C.byref(h)), "br_annotation_load")
+    else:
+        check(L.br_annotation_load_mt(os.fsencode(path), int(threads), C.byref(h)), "br_annotation_load_mt")
+    try:
+        n, t, g, rn = L.br_annotation_num_transcripts(h), L.br_annotation_transcripts(h), L.br_annotation_gene_ids(h), L.br_annotation_refnames(h)
+        txs = [{"id": t[i].id.decode(), "seqname": t[i].seqname.decode(), "strand": t[i].strand.decode(),
+                "exons": [[t[i].exons[k].start, t[i].exons[k].end] for k in range(t[i].n_exons)]} for i in range(n)]
+        return {"refnames": [rn[i].decode() for i in range(L.br_annotation_num_refs(h))], "transcripts": txs,
+                "gene_ids": [g[i].decode() for i in range(n)]}
+    finally:
+        L.br_annotation_free(h)
 
 
 def check(rc, what):
@@ -1180,11 +1208,18 @@ class Quant(_Accumulator):
                           _P(C.c_int64), _P(C.c_int64)], "free": [C.c_void_p],
                 "bootstrap": [C.c_void_p, C.c_void_p], "boot_counts": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p],
                 "boot_theta": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p], "boot_summary": [C.c_void_p, C.c_void_p, C.c_void_p],
-                "boot_stats": [C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_int64)]}
+                "boot_stats": [C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_int64)],
+                "genes": [C.c_void_p, C.c_void_p, C.c_int64, _P(C.c_int64)],
+                "gene_classes": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                "gene_result": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                "gene_boot": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p], "gene_boot_summary": [C.c_void_p, C.c_void_p, C.c_void_p],
+                "gene_stats": [C.c_void_p, _P(C.c_double), _P(C.c_int64), _P(C.c_uint64)]}
 
     def __init__(self, n_transcripts, lengths=None, device=0):
         self.n_transcripts = int(n_transcripts)
         self.n_names = self.n_classes = 0
+        self.n_genes = self.n_gene_classes = 0
+        self.eff_len = False
         self.fld_max = 1000
         self.bootstraps = 0
         lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64)
@@ -1206,6 +1241,8 @@ class Quant(_Accumulator):
                 self.fld_max = int(value)
             if name == "bootstraps":
                 self.bootstraps = int(value)
+            if name == "eff_len":
+                self.eff_len = bool(value)
 
     def add_raw(self, a, row_off, group_off, n_groups, on_device, stream=None):
         """br_quant_add as it is: the return code (0, or a BR_ERR_* value)."""
@@ -1321,6 +1358,59 @@ class Quant(_Accumulator):
         s, e, n = C.c_double(), C.c_double(), C.c_int64()
         self._call("boot_stats", C.byref(s), C.byref(e), C.byref(n))
         return {"sample_s": s.value, "em_s": e.value, "iterations_total": int(n.value)}
+
+    def genes_raw(self, tx_gene, n_genes):
+        """br_quant_genes as it is (tx_gene: an address or None): the return code (0, or a BR_ERR_* value)."""
+        return self._raw("genes", C.c_void_p(tx_gene), int(n_genes), None)
+
+    def genes(self, tx_gene, n_genes):
+        """The gene tables from tx_gene (one gene number below n_genes per transcript), after finish -> the number of gene classes"""
+        m = np.ascontiguousarray(tx_gene, dtype=np.uint32)
+        assert m.size == self.n_transcripts
+        n = C.c_int64()
+        self._call("genes", m.ctypes.data if m.size else None, int(n_genes), C.byref(n))
+        self.n_genes, self.n_gene_classes = int(n_genes), int(n.value)
+        return self.n_gene_classes
+
+    def gene_classes(self):
+        """-> (label_off uint64 [C + 1], labels uint32, counts uint64 [C], first_name uint64 [C]) of the gene classes"""
+        nc = self.n_gene_classes
+        off = np.zeros(nc + 1, dtype=np.uint64)
+        cnt, first = np.zeros(max(nc, 1), dtype=np.uint64), np.zeros(max(nc, 1), dtype=np.uint64)
+        self._call("gene_classes", off.ctypes.data, None, None, None)
+        labels = np.zeros(max(int(off[-1]), 1), dtype=np.uint32)
+        self._call("gene_classes", None, labels.ctypes.data, cnt.ctypes.data, first.ctypes.data)
+        return off, labels[:int(off[-1])], cnt[:nc], first[:nc]
+
+    def gene_result(self, em=True):
+        """-> dict of num_reads, tpm, length (float64; with em; eff_length as well with "eff_len" on) and unique, ambig (uint64),
+        n_transcripts (uint32), one entry per gene"""
+        ng = max(self.n_genes, 1)
+        out = {"unique": np.zeros(ng, dtype=np.uint64), "ambig": np.zeros(ng, dtype=np.uint64), "n_transcripts": np.zeros(ng, dtype=np.uint32)}
+        fl = (["num_reads", "tpm", "length"] + (["eff_length"] if self.eff_len else [])) if em else []
+        for k in fl:
+            out[k] = np.zeros(ng, dtype=np.float64)
+        ptr = [out[k].ctypes.data if k in out else None for k in ("num_reads", "tpm", "length", "eff_length", "unique", "ambig", "n_transcripts")]
+        self._call("gene_result", *ptr)
+        return {k: v[:self.n_genes] for k, v in out.items()}
+
+    def gene_boot(self, first=0, count=None):
+        """-> float64 [count, G]: the genes' num_reads of replicates first .. first + count - 1 (after genes and bootstrap)"""
+        count = self.bootstraps - first if count is None else count
+        out = np.zeros(max(count * self.n_genes, 1), dtype=np.float64)
+        self._call("gene_boot", first, count, out.ctypes.data)
+        return out[:count * self.n_genes].reshape(count, self.n_genes)
+
+    def gene_boot_summary(self):
+        """-> (mean, var) per gene over the replicates (var over B - 1; 0 for B = 1)"""
+        mean, var = np.zeros(max(self.n_genes, 1), dtype=np.float64), np.zeros(max(self.n_genes, 1), dtype=np.float64)
+        self._call("gene_boot_summary", mean.ctypes.data, var.ctypes.data)
+        return mean[:self.n_genes], var[:self.n_genes]
+
+    def gene_stats(self):
+        s, n, co = C.c_double(), C.c_int64(), C.c_uint64()
+        self._call("gene_stats", C.byref(s), C.byref(n), C.byref(co))
+        return {"seconds": s.value, "n_gene_labels": int(n.value), "collisions": int(co.value)}
 
     def fld(self):
         """-> dict of hist (uint64 [fld_max + 1]: observed fragment lengths of the read names of one label) and n_obs,

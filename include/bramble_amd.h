@@ -679,6 +679,23 @@ void br_sorter_free(br_sorter *);
  *                  replicate b's theta has the bits a point EM on n_c^(b) would have, however the replicates are cut into chunks
  *   summary        per transcript, float64, no fused multiply-add: mean_t = (theta_t^(0) + ... + theta_t^(B-1)) / B and var_t = (sum
  *                  over b of (theta_t^(b) - mean_t)^2) / (B - 1), both sums in replicate order, one division each; var = 0 for B = 1
+ *   gene map       (br_quant_genes.)  tx_gene[t] < n_genes for every transcript, 0 <= n_genes < 2^32.  A gene that owns no
+ *                  transcript is allowed: all its results are 0 and n_transcripts[g] = 0
+ *   gene class     the gene set of a class is the ascending list of the distinct tx_gene[label] of its labels; the gene classes
+ *                  are the distinct gene sets.  A gene class's count is the sum of the counts of the classes that have that set,
+ *                  its first_name the smallest of their first_name; gene classes are ordered by first_name, the labels ascend
+ *                  inside one.  That is exactly what br_quant_finish would have produced had every row's transcript_id been
+ *                  replaced by its gene before the adds
+ *   per gene       unique[g] = names whose gene class is {g}; ambig[g] = names whose gene class holds g and has two labels or
+ *                  more; n_transcripts[g] = the number of transcripts of g
+ *   gene abundance (after br_quant_em.)  float64, no fused multiply-add, no floating-point atomics; every sum runs sequentially
+ *                  over the gene's transcripts in ascending transcript order, whatever their number (no wave tree: the bits do not
+ *                  depend on a width).  num_reads[g] = sum of theta_t; tpm[g] = sum of tpm_t, the values br_quant_result returns;
+ *                  length[g] = (sum of tpm_t * (double)L_t) / tpm[g] when tpm[g] > 0, each product rounded, then added, else (sum
+ *                  of (double)L_t) / (double)n_transcripts[g], and 0 for a gene without transcripts or a quantifier without
+ *                  lengths; eff_length[g] the same with eff_t in place of L_t ("eff_len" on)
+ *   gene bootstrap (after br_quant_bootstrap.)  num_reads^(b)[g] = sum of theta_t^(b) in the same order; mean and var as `summary`
+ *                  above defines them, over these gene values
  *   fragment       ("eff_len" = 1; salmon's and kallisto's truncated-mean effective length.)  A row r with BR_ROW_PAIRED |
  *                  BR_ROW_SAME_TX | BR_ROW_FIRST all set, together with row r + 1, which must lie inside the same read name's rows,
  *                  have BR_ROW_PAIRED set and BR_ROW_FIRST clear, and carry the same transcript_id.  A row that fails any of these
@@ -740,11 +757,25 @@ void br_sorter_free(br_sorter *);
  *   br_quant_boot_theta   count x n_transcripts, replicate-major; after br_quant_bootstrap
  *   br_quant_boot_summary mean and var, n_transcripts each, either may be NULL; after br_quant_bootstrap
  *   br_quant_boot_stats   seconds resampling and in the replicates' EM, and the iterations of all replicates together
+ *   br_quant_genes      the gene tables from the map (host memory, n_transcripts entries); the number of gene classes.  After finish,
+ *                       once, before or after br_quant_em / br_quant_bootstrap, whose results it never changes.
+ *                       BR_ERR_INVALID_ARG, and the object as it was, for a second call, a call before finish, a NULL map with
+ *                       transcripts, an entry >= n_genes or an n_genes outside 0 .. 2^32 - 1 (the map is checked before anything
+ *                       is made).  A run without named reads gives 0 classes and zero tables
+ *   br_quant_gene_classes  br_quant_classes of the gene classes; after br_quant_genes; any pointer may be NULL
+ *   br_quant_gene_result   host copies, n_genes each, any may be NULL.  BR_ERR_INVALID_ARG for num_reads / tpm / length /
+ *                       eff_length before br_quant_em, and for eff_length without "eff_len"
+ *   br_quant_gene_boot  count x n_genes, replicate-major, of replicates first .. first + count - 1; after br_quant_genes and
+ *                       br_quant_bootstrap, BR_ERR_INVALID_ARG before
+ *   br_quant_gene_boot_summary  mean and var, n_genes each, either may be NULL; after both as well
+ *   br_quant_gene_stats seconds in br_quant_genes, labels over all gene classes, gene sets met with equal hashes and different
+ *                       contents (any pointer may be NULL)
  * Device memory: 4 bytes a row and 20 bytes a read name while adding; finish peaks at 32 more a name with labels, then holds 24
  * bytes a class, 8 a label and 24 a transcript; the EM adds 40 a transcript and 8 a class; "eff_len" adds 16 (fld_max + 4) for the
  * histogram (the run's and an add's own), 16 (fld_max + 1) for the prefixes during finish and 8 a transcript for eff; the bootstrap
  * holds 8 B a transcript (the result) and 8 a class (cum), and while it runs, for a chunk of W replicates (16 by default), 32 W a
- * transcript and 12 W a class, the summary 16 a transcript (quant.cpp). */
+ * transcript and 12 W a class, the summary 16 a transcript; br_quant_genes holds 24 bytes a gene class, 4 a gene label, 24 a gene and
+ * 4 a transcript, peaks at 32 a label and 4 a transcript beside them, and the gene replicates add 8 B a gene (quant.cpp). */
 typedef struct br_quant br_quant;
 int br_quant_new(int device, int64_t n_transcripts, const int64_t *lengths, br_quant **out);
 int br_quant_set_param(br_quant *, const char *name, int64_t value);
@@ -766,6 +797,13 @@ int br_quant_boot_counts(br_quant *, int32_t first, int32_t count, uint32_t *cou
 int br_quant_boot_theta(br_quant *, int32_t first, int32_t count, double *theta);
 int br_quant_boot_summary(br_quant *, double *mean, double *var);
 int br_quant_boot_stats(const br_quant *, double *sample_seconds, double *em_seconds, int64_t *iterations_total);
+int br_quant_genes(br_quant *, const uint32_t *tx_gene, int64_t n_genes, int64_t *n_gene_classes);
+int br_quant_gene_classes(br_quant *, uint64_t *label_off, uint32_t *labels, uint64_t *counts, uint64_t *first_name);
+int br_quant_gene_result(br_quant *, double *num_reads, double *tpm, double *length, double *eff_length, uint64_t *unique,
+                         uint64_t *ambig, uint32_t *n_transcripts);
+int br_quant_gene_boot(br_quant *, int32_t first, int32_t count, double *num_reads);   /* count x n_genes, replicate-major */
+int br_quant_gene_boot_summary(br_quant *, double *mean, double *var);
+int br_quant_gene_stats(const br_quant *, double *seconds, int64_t *n_gene_labels, uint64_t *collisions);
 void br_quant_free(br_quant *);
 
 /* Coverage: the depth of coverage along every transcript, from the rows of a whole run, in one device's HBM (coverage.cpp,
@@ -891,13 +929,24 @@ size_t br_annotation_num_transcripts(const br_annotation *);
 const br_transcript *br_annotation_transcripts(const br_annotation *);
 size_t br_annotation_num_refs(const br_annotation *);            /* reference names in order of first appearance */
 const char *const *br_annotation_refnames(const br_annotation *);
+/* The gene of every transcript: one C string per transcript, in the order of br_annotation_transcripts, owned by the handle.
+ *   GTF    the gene_id attribute of the first line applied to the record that has a non-empty one: the `transcript` line or an
+ *          exon-like line, whichever came first in file order
+ *   GFF3   the record's gene_id= attribute if a transcript or exon-like line of the record has one; otherwise the first entry of
+ *          the transcript line's Parent=; otherwise (a record made by exon lines only, or one without a parent) the transcript's
+ *          own id
+ * A record for which none of this yields a non-empty string gets its own transcript id: no transcript is left without a gene.
+ * The gene id is carried along and never compared: the transcripts' order does not depend on it, and it does not depend on the
+ * number of loader threads. */
+const char *const *br_annotation_gene_ids(const br_annotation *);
 
 /* The reference's command line (src/bramble.cpp:443-485): in.bam -G -o [-S] [-p] [--fr|--rf]
  * [--lr|--lr-hq] [--strict] [--max-*] [--similarity-threshold] [--quiet], plus --device-deflate (default: BGZF blocks made on the
  * GPU) / --host-deflate / --compression-level N (host codec), --device-reader (default for a regular file on one device: the
  * input is inflated and split into records on the GPU, br_bam_reader) / --host-reader, --bundle-size and --device / --devices,
  * --collate, -O bam|sam, --sort [--write-index], --quant FILE [--quant-classes FILE] [--quant-eff-length [--quant-fld FILE]]
- * [--quant-bootstraps B [--quant-seed S] [--quant-boot-out FILE]] (br_quant above), --coverage FILE / --coverage-summary FILE [--coverage-primary] (br_coverage above; the usage text says the
+ * [--quant-bootstraps B [--quant-seed S] [--quant-boot-out FILE]] [--quant-genes FILE [--quant-gene-classes FILE] [--quant-gene-map FILE]]
+ * (br_quant above; the genes are br_annotation_gene_ids', numbered in order of first appearance in @SQ order, or the map file's), --coverage FILE / --coverage-summary FILE [--coverage-primary] (br_coverage above; the usage text says the
  * rest).
  * Returns the process exit code. */
 int br_cli_main(int argc, char **argv);
