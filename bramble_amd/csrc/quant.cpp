@@ -28,14 +28,15 @@
 //   genes    (br_quant_genes, after finish) a lane per label entry makes (class << 32) | gene of the label; the radix driver sorts
 //            the L keys, the heads of equal keys are the distinct (class, gene) entries and a scan places them in a gene-label
 //            arena, a class's gene list where its labels were; a hash of every list (a lane, or a wave above 64 genes), then
-//            finish's own sequence with a class where finish has a name: the sort of (hash, class), the heads by comparing
-//            lists with the collision repair, a scan of the members' counts for a gene class's count (finish counts 1 a name),
-//            its first member for its first name (the classes are in first-name order), the sort by first name, label_off and
-//            labels, and unique / ambiguous names per gene by integer atomics.  The transcripts by gene come from a counting
-//            sort on the host; a lane per gene sums theta / tpm / lengths over them in ascending order, a lane per (replicate,
-//            gene) the B x T result into B x G, which the transcripts' summary kernel reduces.  (The gene path stands beside
-//            quant_finish and shares its kernels for sorting, heads, repair and scans; the kernels that read per-name tables
-//            have gene twins, k_qg_*.)
+//            the routine that made the transcript classes (quant_classes), and the labels with unique / ambiguous names per
+//            gene by integer atomics.  The transcripts by gene come from a counting sort on the host; a lane per gene sums
+//            theta / tpm / lengths over them in ascending order, a lane per (replicate, gene) the B x T result into B x G,
+//            which the transcripts' summary kernel reduces
+//   One routine, quant_classes, makes the classes of both levels from items: an item owns a list, has a first name and stands for
+//   a number of names (its weight).  For finish an item is a read name with labels -- its first name is itself, its weight 1, and
+//   neither table exists; for the genes it is a transcript class with its gene list, the class's first name and the class's count
+//   (one more scan, of the sorted items' weights, gives a gene class its count).  From the unsorted (hash, item) pairs on, the
+//   sort, the heads with the collision repair, the counts, the sort by first name and label_off are the same code
 //
 // Device memory (N names, of them M with labels; R rows added; C classes; L labels over all classes; T transcripts):
 //   while adding   4 R (the arena: a slot per row) + 20 N (offset, k, hash) + 4 bytes a name of the largest add (the list of its
@@ -87,12 +88,17 @@ struct br_quant : Accum {
   bool finished = false, em_done = false;
   int64_t n = 0;               // names added
   uint64_t rows = 0;           // arena slots in use
-  int64_t n_assigned = 0, n_cls = 0, n_lab = 0;
+  int64_t n_assigned = 0;
   uint32_t n_big_cls = 0, n_big_tx = 0;
-  uint64_t collisions = 0;
   double add_s = 0, finish_s = 0, em_s = 0;
   ColBuf lab, noff, nk, hash, big;                       // add
-  ColBuf c_first, c_cnt, c_loff, c_labels, t_cls, t_off, uniq, ambig, big_cls, big_tx;   // after finish
+  // the classes of one level in first-name order (quant_classes): per class its first name, count and label_off; the labels
+  struct Classes {
+    ColBuf first, cnt, loff, labels;
+    int64_t n_cls = 0, n_lab = 0;
+    uint64_t collisions = 0;
+  } cls;                                                 // the transcript classes, after finish
+  ColBuf t_cls, t_off, uniq, ambig, big_cls, big_tx;     // after finish
   ColBuf theta[2], x[2], w, qv;                          // em
   ColBuf fld_stage, fld_total, eff;                      // "eff_len": fld_max + 1 bins + Q_FLD_SIDE counters each (an add's, the run's); per transcript
   size_t fld_words() const { return (size_t)fld_max + 1 + Q_FLD_SIDE; }
@@ -116,11 +122,9 @@ struct br_quant : Accum {
   int64_t boot_iters = 0;
   ColBuf boot_res, boot_cum;
   // gene level: the tables br_quant_genes leaves, and the B x G gene replicates once they were asked for
-  struct Genes {
-    ColBuf first, cnt, loff, labels, uniq, ambig, toff, tx;   // per gene class; per gene; the transcripts by gene, ascending inside one
+  struct Genes : Classes {                                    // the gene classes, and
+    ColBuf uniq, ambig, toff, tx;                             // per gene; the transcripts by gene, ascending inside one
     std::vector<uint32_t> n_tx;                               // transcripts per gene
-    int64_t n_cls = 0, n_lab = 0;
-    uint64_t collisions = 0;
   } gene;
   bool genes_done = false;
   int64_t n_genes = 0;
@@ -306,6 +310,75 @@ static int quant_sort(br_quant *c, ColBuf key[2], ColBuf idx[2], int64_t n, int 
   return c->radix_sort(key, idx, n, bits, c->tmp, cur);
 }
 
+// The classes of n items, for every level of the quantifier.  Item i owns the list lab[off[i] .. off[i] + k[i]); its first name is
+// first[i] (NULL: i itself -- the item is a read name) and it stands for weight[i] names (NULL: one).  key[0] / idx[0] hold the n
+// unsorted (hash & mask, item) pairs, n > 0.  The sort of (hash, item) is stable, so the items of a class ascend; the heads compare
+// the lists of neighbours, and a run of equal hashes that holds different lists is put in order by (k, list, item) and the heads
+// found again: exact at any hash_bits.  out gets the classes in first-name order -- first, cnt (the sum of the items' weights),
+// loff (scanned, loff[C] = L) -- with n_cls = C, n_lab = L and the collisions; rep != NULL gets per class an item whose list is
+// the class's.  Everything else, key and idx included, is dropped when it returns: the caller makes its label tables after that
+static int quant_classes(br_quant *c, const uint32_t *lab, const uint64_t *off, const uint32_t *k, const uint64_t *first, const uint64_t *weight,
+                         ColBuf key[2], ColBuf idx[2], int64_t n, br_quant::Classes &out, ColBuf *rep) {
+  hipStream_t st = c->st;
+  uint64_t *small = c->small.as<uint64_t>();
+  ColBuf head, mark, pre, gbeg, key2[2], val2[2];
+  DropGuard sort_bufs{c, {&key[0], &key[1], &idx[0], &idx[1], &head, &mark, &pre, &gbeg, &key2[0], &key2[1], &val2[0], &val2[1]}};
+  int cur = 0;
+  RC(quant_sort(c, key, idx, n, &cur));
+  // class heads; runs of equal hashes with different lists are put in order and the heads found again
+  RC(c->alloc(head, (size_t)(n + 1) * 8));
+  auto heads = [&](uint32_t *mk, uint64_t *n_coll) -> int {
+    HIPCHK(hipMemsetAsync(small + QS_COLL, 0, 8, st));
+    launch_q_heads(st, lab, off, k, key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), n, head.as<uint64_t>(), (unsigned long long *)(small + QS_COLL), mk);
+    HIPCHK(hipMemcpyAsync(n_coll, small + QS_COLL, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return BR_OK;
+  };
+  uint64_t n_coll = 0;
+  RC(heads(nullptr, &n_coll));
+  out.collisions = n_coll;
+  if (n_coll) {
+    RC(c->alloc(mark, (size_t)n * 4));
+    HIPCHK(hipMemsetAsync(mark.p, 0, (size_t)n * 4, st));
+    RC(heads(mark.as<uint32_t>(), &n_coll));
+    launch_q_resolve(st, lab, off, k, key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), n, mark.as<uint32_t>(), key[cur ^ 1].as<uint64_t>(), idx[cur ^ 1].as<uint32_t>());
+    cur ^= 1;
+    RC(heads(nullptr, &n_coll));
+  }
+  RC(quant_tmp(c, n));
+  launch_scan(st, head.as<uint64_t>(), n, c->tmp.as<uint64_t>());   // head -> class ids (exclusive), head[n] = C
+  uint64_t C = 0;
+  HIPCHK(hipMemcpyAsync(&C, head.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (C == 0 || C > (uint64_t)n) return BR_ERR_HIP;
+  out.n_cls = (int64_t)C;
+  const size_t c1 = (size_t)C + 1;
+  RC(c->alloc(gbeg, c1 * 8));
+  launch_col_gbeg(st, head.as<uint64_t>(), n, gbeg.as<uint64_t>());
+  if (weight) {   // a class's count: the integer sum of its items' weights, from one scan over the items in sorted order
+    RC(c->alloc(pre, (size_t)(n + 1) * 8));
+    launch_qg_member_cnt(st, idx[cur].as<uint32_t>(), weight, n, pre.as<uint64_t>());
+    launch_scan(st, pre.as<uint64_t>(), n, c->tmp.as<uint64_t>());
+  }
+  // the classes by their first name
+  RC(c->alloc(key2[0], c1 * 8)); RC(c->alloc(key2[1], c1 * 8)); RC(c->alloc(val2[0], c1 * 4)); RC(c->alloc(val2[1], c1 * 4));
+  launch_q_class_key(st, gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), first, (int64_t)C, key2[0].as<uint64_t>(), val2[0].as<uint32_t>());
+  int cur2 = 0;
+  RC(quant_sort(c, key2, val2, (int64_t)C, &cur2));
+  RC(c->alloc(out.first, c1 * 8)); RC(c->alloc(out.cnt, c1 * 8)); RC(c->alloc(out.loff, c1 * 8));
+  if (rep) RC(c->alloc(*rep, c1 * 4));
+  launch_q_class_fill(st, key2[cur2].as<uint64_t>(), val2[cur2].as<uint32_t>(), gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), pre.as<uint64_t>(), k, (int64_t)C,
+                      out.first.as<uint64_t>(), out.cnt.as<uint64_t>(), out.loff.as<uint64_t>(), rep ? rep->as<uint32_t>() : nullptr);
+  RC(quant_tmp(c, (int64_t)C));
+  launch_scan(st, out.loff.as<uint64_t>(), (int64_t)C, c->tmp.as<uint64_t>());
+  uint64_t L = 0;
+  HIPCHK(hipMemcpyAsync(&L, out.loff.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (L >= (1ull << 32)) return BR_ERR_CAPACITY;   // (32-bit radix indices)
+  out.n_lab = (int64_t)L;
+  return BR_OK;
+}
+
 static int quant_finish(br_quant *c) {
   hipStream_t st = c->st;
   const int64_t N = c->n, T = c->n_tx;
@@ -317,8 +390,8 @@ static int quant_finish(br_quant *c) {
   if (N == 0) return BR_OK;
   // the names with labels
   uint64_t M = 0;
-  ColBuf key[2], idx[2], head, mark, gbeg, key2[2], val2[2];
-  DropGuard sort_bufs{c, {&key[0], &key[1], &idx[0], &idx[1], &head, &mark, &gbeg, &key2[0], &key2[1], &val2[0], &val2[1]}};
+  ColBuf key[2], idx[2];
+  DropGuard sort_bufs{c, {&key[0], &key[1], &idx[0], &idx[1]}};
   {
     ColBuf pos;
     DropGuard dropper{c, {&pos}};
@@ -338,62 +411,16 @@ static int quant_finish(br_quant *c) {
     launch_q_compact(st, c->nk.as<uint32_t>(), c->hash.as<uint64_t>(), pos.as<uint64_t>(), N, mask, key[0].as<uint64_t>(), idx[0].as<uint32_t>());
     HIPCHK(hipStreamSynchronize(st));
   }
-  const int64_t m = (int64_t)M;
-  int cur = 0;
-  RC(quant_sort(c, key, idx, m, &cur));
-  // class heads; runs of equal hashes with different lists are put in order and the heads found again
-  const uint32_t *lab = c->lab.as<uint32_t>(), *nk = c->nk.as<uint32_t>();
+  // their classes: a name is its own first name and counts once; a class's list is its first name's, so no rep
+  const uint32_t *lab = c->lab.as<uint32_t>();
   const uint64_t *noff = c->noff.as<uint64_t>();
-  RC(c->alloc(head, (size_t)(m + 1) * 8));
-  auto heads = [&](uint32_t *mk, uint64_t *n_coll) -> int {
-    HIPCHK(hipMemsetAsync(small + QS_COLL, 0, 8, st));
-    launch_q_heads(st, lab, noff, nk, key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), m, head.as<uint64_t>(), (unsigned long long *)(small + QS_COLL), mk);
-    HIPCHK(hipMemcpyAsync(n_coll, small + QS_COLL, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return BR_OK;
-  };
-  uint64_t n_coll = 0;
-  RC(heads(nullptr, &n_coll));
-  c->collisions = n_coll;
-  if (n_coll) {
-    RC(c->alloc(mark, (size_t)m * 4));
-    HIPCHK(hipMemsetAsync(mark.p, 0, (size_t)m * 4, st));
-    RC(heads(mark.as<uint32_t>(), &n_coll));
-    launch_q_resolve(st, lab, noff, nk, key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), m, mark.as<uint32_t>(), key[cur ^ 1].as<uint64_t>(), idx[cur ^ 1].as<uint32_t>());
-    cur ^= 1;
-    RC(heads(nullptr, &n_coll));
-  }
-  RC(quant_tmp(c, m));
-  launch_scan(st, head.as<uint64_t>(), m, c->tmp.as<uint64_t>());   // head -> class ids (exclusive), head[m] = C
-  uint64_t C = 0;
-  HIPCHK(hipMemcpyAsync(&C, head.as<uint64_t>() + m, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (C == 0 || C > (uint64_t)m) return BR_ERR_HIP;
-  c->n_cls = (int64_t)C;
-  const size_t c1 = (size_t)C + 1;
-  RC(c->alloc(gbeg, c1 * 8));
-  launch_col_gbeg(st, head.as<uint64_t>(), m, gbeg.as<uint64_t>());
-  // the classes by their first name
-  RC(c->alloc(key2[0], c1 * 8)); RC(c->alloc(key2[1], c1 * 8)); RC(c->alloc(val2[0], c1 * 4)); RC(c->alloc(val2[1], c1 * 4));
-  launch_q_class_key(st, gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), (int64_t)C, key2[0].as<uint64_t>(), val2[0].as<uint32_t>());
-  int cur2 = 0;
-  RC(quant_sort(c, key2, val2, (int64_t)C, &cur2));
-  RC(c->alloc(c->c_first, c1 * 8)); RC(c->alloc(c->c_cnt, c1 * 8)); RC(c->alloc(c->c_loff, c1 * 8));
-  launch_q_class_fill(st, key2[cur2].as<uint64_t>(), val2[cur2].as<uint32_t>(), gbeg.as<uint64_t>(), nk, (int64_t)C, c->c_first.as<uint64_t>(),
-                      c->c_cnt.as<uint64_t>(), c->c_loff.as<uint64_t>());
-  RC(quant_tmp(c, (int64_t)C));
-  launch_scan(st, c->c_loff.as<uint64_t>(), (int64_t)C, c->tmp.as<uint64_t>());
-  uint64_t L = 0;
-  HIPCHK(hipMemcpyAsync(&L, c->c_loff.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (L >= (1ull << 32)) return BR_ERR_CAPACITY;   // (32-bit radix indices)
-  c->n_lab = (int64_t)L;
-  for (auto *b : sort_bufs.b) c->drop(*b);   // (dropping twice is harmless: an empty buffer counts nothing)
+  RC(quant_classes(c, lab, noff, c->nk.as<uint32_t>(), nullptr, nullptr, key, idx, (int64_t)M, c->cls, nullptr));
+  const int64_t C = c->cls.n_cls, L = c->cls.n_lab;
   // labels and the transposed table
   ColBuf ecls, tkey[2], tidx[2], d_lens;
   DropGuard table_bufs{c, {&ecls, &tkey[0], &tkey[1], &tidx[0], &tidx[1], &d_lens}};
   const size_t l1 = (size_t)L + 1;
-  RC(c->alloc(c->c_labels, l1 * 4)); RC(c->alloc(ecls, l1 * 4)); RC(c->alloc(c->t_cls, l1 * 4));
+  RC(c->alloc(c->cls.labels, l1 * 4)); RC(c->alloc(ecls, l1 * 4)); RC(c->alloc(c->t_cls, l1 * 4));
   RC(c->alloc(tkey[0], l1 * 8)); RC(c->alloc(tkey[1], l1 * 8)); RC(c->alloc(tidx[0], l1 * 4)); RC(c->alloc(tidx[1], l1 * 4));
   const bool check_len = c->length_norm && !c->lens.empty();
   if (c->length_norm && c->lens.empty()) return BR_ERR_INVALID_ARG;   // length normalisation without lengths
@@ -402,27 +429,27 @@ static int quant_finish(br_quant *c) {
     HIPCHK(hipMemcpyAsync(d_lens.p, c->lens.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
   }
   HIPCHK(hipMemsetAsync(small + QS_BAD, 0, 8, st));
-  launch_q_labels(st, c->c_loff.as<uint64_t>(), c->c_first.as<uint64_t>(), noff, lab, (int64_t)C, (int64_t)L, check_len ? d_lens.as<int64_t>() : nullptr,
-                  c->c_labels.as<uint32_t>(), ecls.as<uint32_t>(), tkey[0].as<uint64_t>(), tidx[0].as<uint32_t>(), (uint32_t *)(small + QS_BAD));
+  launch_q_labels(st, c->cls.loff.as<uint64_t>(), c->cls.first.as<uint64_t>(), noff, lab, C, L, check_len ? d_lens.as<int64_t>() : nullptr,
+                  c->cls.labels.as<uint32_t>(), ecls.as<uint32_t>(), tkey[0].as<uint64_t>(), tidx[0].as<uint32_t>(), (uint32_t *)(small + QS_BAD));
   uint32_t bad = 0;
   HIPCHK(hipMemcpyAsync(&bad, small + QS_BAD, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (bad) return BR_ERR_INVALID_ARG;   // a transcript of length <= 0 has reads, and lengths normalise
   c->drop(c->lab); c->drop(c->noff); c->drop(c->nk); c->drop(c->hash); c->drop(c->big);   // the names are classes now
   int cur3 = 0;
-  RC(quant_sort(c, tkey, tidx, (int64_t)L, &cur3));
-  launch_q_transpose(st, tkey[cur3].as<uint64_t>(), tidx[cur3].as<uint32_t>(), ecls.as<uint32_t>(), (int64_t)L, T, c->t_cls.as<uint32_t>(), c->t_off.as<uint64_t>());
+  RC(quant_sort(c, tkey, tidx, L, &cur3));
+  launch_q_transpose(st, tkey[cur3].as<uint64_t>(), tidx[cur3].as<uint32_t>(), ecls.as<uint32_t>(), L, T, c->t_cls.as<uint32_t>(), c->t_off.as<uint64_t>());
   // the wave-sized items
   const size_t most = (size_t)(L / (Q_WAVE_ITEMS + 1) + 1);
   RC(c->alloc(c->big_cls, most * 4)); RC(c->alloc(c->big_tx, most * 4));
   HIPCHK(hipMemsetAsync(small + QS_NBIG_CLS, 0, 16, st));
-  launch_q_bin(st, c->c_loff.as<uint64_t>(), (int64_t)C, c->big_cls.as<uint32_t>(), (uint32_t *)(small + QS_NBIG_CLS));
+  launch_q_bin(st, c->cls.loff.as<uint64_t>(), C, c->big_cls.as<uint32_t>(), (uint32_t *)(small + QS_NBIG_CLS));
   launch_q_bin(st, c->t_off.as<uint64_t>(), T, c->big_tx.as<uint32_t>(), (uint32_t *)(small + QS_NBIG_TX));
   uint64_t nb[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(nb, small + QS_NBIG_CLS, 16, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   c->n_big_cls = (uint32_t)nb[0]; c->n_big_tx = (uint32_t)nb[1];
-  launch_q_counts(st, c->t_cls.as<uint32_t>(), c->t_off.as<uint64_t>(), c->c_loff.as<uint64_t>(), c->c_cnt.as<uint64_t>(), T, c->big_tx.as<uint32_t>(),
+  launch_q_counts(st, c->t_cls.as<uint32_t>(), c->t_off.as<uint64_t>(), c->cls.loff.as<uint64_t>(), c->cls.cnt.as<uint64_t>(), T, c->big_tx.as<uint32_t>(),
                   c->n_big_tx, c->uniq.as<uint64_t>(), c->ambig.as<uint64_t>());
   HIPCHK(hipStreamSynchronize(st));
   return BR_OK;
@@ -455,21 +482,25 @@ extern "C" int br_quant_finish(br_quant *c, int64_t *n_names, int64_t *n_classes
   c->finished = true;
   c->finish_s = timer.seconds();
   if (n_names) *n_names = c->n;
-  if (n_classes) *n_classes = c->n_cls;
+  if (n_classes) *n_classes = c->cls.n_cls;
   return BR_OK;
 }
 
-extern "C" int br_quant_classes(br_quant *c, uint64_t *label_off, uint32_t *labels, uint64_t *counts, uint64_t *first_name) {
-  if (!c || !c->finished) return BR_ERR_INVALID_ARG;
+// one level's classes to the host
+static int quant_copy_classes(br_quant *c, const br_quant::Classes &k, uint64_t *label_off, uint32_t *labels, uint64_t *counts,
+                              uint64_t *first_name) {
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->st;
-  const size_t C = (size_t)c->n_cls, L = (size_t)c->n_lab;
-  if (label_off) { if (C) HIPCHK(hipMemcpyAsync(label_off, c->c_loff.p, (C + 1) * 8, hipMemcpyDeviceToHost, st)); else label_off[0] = 0; }
-  if (labels && L) HIPCHK(hipMemcpyAsync(labels, c->c_labels.p, L * 4, hipMemcpyDeviceToHost, st));
-  if (counts && C) HIPCHK(hipMemcpyAsync(counts, c->c_cnt.p, C * 8, hipMemcpyDeviceToHost, st));
-  if (first_name && C) HIPCHK(hipMemcpyAsync(first_name, c->c_first.p, C * 8, hipMemcpyDeviceToHost, st));
+  const size_t C = (size_t)k.n_cls, L = (size_t)k.n_lab;
+  if (label_off) { if (C) HIPCHK(hipMemcpyAsync(label_off, k.loff.p, (C + 1) * 8, hipMemcpyDeviceToHost, st)); else label_off[0] = 0; }
+  if (labels && L) HIPCHK(hipMemcpyAsync(labels, k.labels.p, L * 4, hipMemcpyDeviceToHost, st));
+  if (counts && C) HIPCHK(hipMemcpyAsync(counts, k.cnt.p, C * 8, hipMemcpyDeviceToHost, st));
+  if (first_name && C) HIPCHK(hipMemcpyAsync(first_name, k.first.p, C * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return BR_OK;
+}
+extern "C" int br_quant_classes(br_quant *c, uint64_t *label_off, uint32_t *labels, uint64_t *counts, uint64_t *first_name) {
+  return c && c->finished ? quant_copy_classes(c, c->cls, label_off, labels, counts, first_name) : BR_ERR_INVALID_ARG;
 }
 
 extern "C" int br_quant_fld(br_quant *c, uint64_t *hist, uint64_t *n_obs, uint64_t *n_no_fragment, uint64_t *n_out_of_range) {
@@ -497,9 +528,26 @@ extern "C" int br_quant_eff_lengths(br_quant *c, double *eff) {
   return BR_OK;
 }
 
-static double quant_weight(const br_quant *c, int64_t t) {
-  if (!c->length_norm) return 1.0;
-  return c->lens[(size_t)t] > 0 ? 1.0 / (double)c->lens[(size_t)t] : 0.0;   // (a transcript of length <= 0 has no reads: finish saw to it)
+// w per transcript on the device: 1 / length where lengths normalise, else 1 (with "eff_len" it is 1 / eff, there since finish: k_q_efflen)
+static int quant_put_w(br_quant *c) {
+  const size_t T = (size_t)c->n_tx;
+  RC(c->alloc(c->w, (T + 1) * 8));
+  if (c->eff_len) return BR_OK;
+  std::vector<double> w(T, 1.0);
+  if (c->length_norm) for (size_t t = 0; t < T; t++) w[t] = c->lens[t] > 0 ? 1.0 / (double)c->lens[t] : 0.0;   // (length <= 0: no reads, finish saw to it)
+  if (T) HIPCHK(hipMemcpyAsync(c->w.p, w.data(), T * 8, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));   // (w goes)
+  return BR_OK;
+}
+// the tables of the EM; q: a double per class (and replicate)
+static QEmArgs quant_em_args(const br_quant *c, double *q) {
+  QEmArgs E{};
+  E.n_cls = c->cls.n_cls; E.n_tx = c->n_tx;
+  E.label_off = c->cls.loff.as<uint64_t>(); E.labels = c->cls.labels.as<uint32_t>(); E.cnt = c->cls.cnt.as<uint64_t>();
+  E.t_off = c->t_off.as<uint64_t>(); E.t_cls = c->t_cls.as<uint32_t>();
+  E.big_cls = c->big_cls.as<uint32_t>(); E.n_big_cls = c->n_big_cls; E.big_tx = c->big_tx.as<uint32_t>(); E.n_big_tx = c->n_big_tx;
+  E.w = c->w.as<double>(); E.q = q;
+  return E;
 }
 
 extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
@@ -508,27 +556,16 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
   const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->st;
-  const int64_t T = c->n_tx, C = c->n_cls;
+  const int64_t T = c->n_tx, C = c->cls.n_cls;
   const size_t t1 = (size_t)T + 1;
   for (int k = 0; k < 2; k++) { RC(c->alloc(c->theta[k], t1 * 8)); RC(c->alloc(c->x[k], t1 * 8)); }
-  RC(c->alloc(c->w, t1 * 8)); RC(c->alloc(c->qv, (size_t)(C + 1) * 8));
-  std::vector<double> one((size_t)T, 1.0), w;
-  if (T) HIPCHK(hipMemcpyAsync(c->theta[0].p, one.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
-  if (c->eff_len) {   // w = 1 / eff is on the device since finish (k_q_efflen)
-    if (T) HIPCHK(hipMemcpyAsync(c->x[0].p, c->w.p, (size_t)T * 8, hipMemcpyDeviceToDevice, st));
-  } else {
-    w.resize((size_t)T);
-    for (int64_t t = 0; t < T; t++) w[(size_t)t] = quant_weight(c, t);
-    if (T) {
-      HIPCHK(hipMemcpyAsync(c->x[0].p, w.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));   // theta w at theta = 1
-      HIPCHK(hipMemcpyAsync(c->w.p, w.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
-    }
+  RC(quant_put_w(c)); RC(c->alloc(c->qv, (size_t)(C + 1) * 8));
+  const std::vector<double> one((size_t)T, 1.0);
+  if (T) {
+    HIPCHK(hipMemcpyAsync(c->theta[0].p, one.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->x[0].p, c->w.p, (size_t)T * 8, hipMemcpyDeviceToDevice, st));   // theta w at theta = 1
   }
-  QEmArgs E{};
-  E.n_cls = C; E.n_tx = T; E.label_off = c->c_loff.as<uint64_t>(); E.labels = c->c_labels.as<uint32_t>(); E.cnt = c->c_cnt.as<uint64_t>();
-  E.t_off = c->t_off.as<uint64_t>(); E.t_cls = c->t_cls.as<uint32_t>();
-  E.big_cls = c->big_cls.as<uint32_t>(); E.n_big_cls = c->n_big_cls; E.big_tx = c->big_tx.as<uint32_t>(); E.n_big_tx = c->n_big_tx;
-  E.w = c->w.as<double>(); E.q = c->qv.as<double>();
+  const QEmArgs E = quant_em_args(c, c->qv.as<double>());
   unsigned long long *d_rel = (unsigned long long *)(c->small.as<uint64_t>() + QS_REL);
   int cur = 0;
   int64_t it = 0;
@@ -560,12 +597,12 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
 static int quant_boot_cum(br_quant *c) {
   if (c->boot_cum.p) return BR_OK;
   hipStream_t st = c->st;
-  const int64_t C = c->n_cls;
+  const int64_t C = c->cls.n_cls;
   RC(c->alloc(c->boot_cum, (size_t)(C + 1) * 8));
   c->boot_n = 0;
   if (C == 0) return BR_OK;
   RC(quant_tmp(c, C));
-  HIPCHK(hipMemcpyAsync(c->boot_cum.p, c->c_cnt.p, (size_t)C * 8, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(c->boot_cum.p, c->cls.cnt.p, (size_t)C * 8, hipMemcpyDeviceToDevice, st));
   launch_scan(st, c->boot_cum.as<uint64_t>(), C, c->tmp.as<uint64_t>());
   HIPCHK(hipMemcpyAsync(&c->boot_n, c->boot_cum.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -580,20 +617,14 @@ extern "C" int br_quant_bootstrap(br_quant *c, int32_t *n_iters) {
   if (!quant_boot_ready(c)) return BR_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->st;
-  const int64_t T = c->n_tx, C = c->n_cls, B = c->bootstraps;
+  const int64_t T = c->n_tx, C = c->cls.n_cls, B = c->bootstraps;
   // replicates a chunk, and the power of two that holds them: the layout's W
   const int per = (int)std::min<int64_t>(c->boot_chunk ? c->boot_chunk : (int64_t)Q_BOOT_CHUNK, B);
   int lw = 0;
   while ((1 << lw) < per) lw++;
   const size_t W = (size_t)1 << lw;
   c->boot_sample_s = c->boot_em_s = 0; c->boot_iters = 0;
-  if (!c->eff_len) {   // w as br_quant_em makes it (with "eff_len" it is on the device since finish)
-    std::vector<double> w((size_t)T);
-    for (int64_t t = 0; t < T; t++) w[(size_t)t] = quant_weight(c, t);
-    RC(c->alloc(c->w, ((size_t)T + 1) * 8));
-    if (T) HIPCHK(hipMemcpyAsync(c->w.p, w.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));   // (w goes)
-  }
+  RC(quant_put_w(c));
   RC(quant_boot_cum(c));
   RC(c->alloc(c->boot_res, ((size_t)B * (size_t)T + 1) * 8));
   ColBuf th[2], xx[2], q, cnt, d_rel;
@@ -601,11 +632,8 @@ extern "C" int br_quant_bootstrap(br_quant *c, int32_t *n_iters) {
   for (int k = 0; k < 2; k++) { RC(c->alloc(th[k], ((size_t)T * W + 1) * 8)); RC(c->alloc(xx[k], ((size_t)T * W + 1) * 8)); }
   RC(c->alloc(q, ((size_t)C * W + 1) * 8)); RC(c->alloc(cnt, ((size_t)C * W + 1) * 4)); RC(c->alloc(d_rel, 64 * 8));
   QBootArgs A{};
-  QEmArgs &E = A.E;
-  E.n_cls = C; E.n_tx = T; E.label_off = c->c_loff.as<uint64_t>(); E.labels = c->c_labels.as<uint32_t>(); E.cnt = nullptr;
-  E.t_off = c->t_off.as<uint64_t>(); E.t_cls = c->t_cls.as<uint32_t>();
-  E.big_cls = c->big_cls.as<uint32_t>(); E.n_big_cls = c->n_big_cls; E.big_tx = c->big_tx.as<uint32_t>(); E.n_big_tx = c->n_big_tx;
-  E.w = c->w.as<double>(); E.q = q.as<double>();
+  A.E = quant_em_args(c, q.as<double>());
+  A.E.cnt = nullptr;   // (a replicate's counts are its own: A.cnt)
   A.cnt = cnt.as<uint32_t>(); A.lw = lw;
   unsigned long long *rel = d_rel.as<unsigned long long>();
   uint64_t bits[64];
@@ -654,7 +682,7 @@ extern "C" int br_quant_boot_counts(br_quant *c, int32_t first, int32_t count, u
   if (!c || !c->finished || c->bootstraps == 0 || first < 0 || count < 0 || (int64_t)first + count > c->bootstraps || (count && !counts)) return BR_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->st;
-  const int64_t C = c->n_cls;
+  const int64_t C = c->cls.n_cls;
   RC(quant_boot_cum(c));
   if (C == 0 || count == 0) return BR_OK;
   const int32_t piece = std::min<int32_t>(count, Q_BOOT_CHUNK);
@@ -680,19 +708,22 @@ extern "C" int br_quant_boot_theta(br_quant *c, int32_t first, int32_t count, do
   return BR_OK;
 }
 
+// mean and variance over the replicates of the bootstraps x n result res, per column
+static int quant_summary(br_quant *c, const ColBuf &res, size_t n, double *mean, double *var) {
+  hipStream_t st = c->st;
+  ColBuf mv;   // mean, then var
+  DropGuard dropper{c, {&mv}};
+  RC(c->alloc(mv, (2 * n + 1) * 8));
+  launch_q_boot_summary(st, res.as<double>(), (int64_t)n, (int32_t)c->bootstraps, mv.as<double>(), mv.as<double>() + n);
+  if (mean && n) HIPCHK(hipMemcpyAsync(mean, mv.p, n * 8, hipMemcpyDeviceToHost, st));
+  if (var && n) HIPCHK(hipMemcpyAsync(var, mv.as<double>() + n, n * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return BR_OK;
+}
 extern "C" int br_quant_boot_summary(br_quant *c, double *mean, double *var) {
   if (!c || !c->boot_done || !c->boot_res.p) return BR_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->st;
-  const size_t T = (size_t)c->n_tx;
-  ColBuf mv;   // mean, then var
-  DropGuard dropper{c, {&mv}};
-  RC(c->alloc(mv, (2 * T + 1) * 8));
-  launch_q_boot_summary(st, c->boot_res.as<double>(), (int64_t)T, (int32_t)c->bootstraps, mv.as<double>(), mv.as<double>() + T);
-  if (mean && T) HIPCHK(hipMemcpyAsync(mean, mv.p, T * 8, hipMemcpyDeviceToHost, st));
-  if (var && T) HIPCHK(hipMemcpyAsync(var, mv.as<double>() + T, T * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return BR_OK;
+  return quant_summary(c, c->boot_res, (size_t)c->n_tx, mean, var);
 }
 
 extern "C" int br_quant_boot_stats(const br_quant *c, double *sample_seconds, double *em_seconds, int64_t *iterations_total) {
@@ -732,7 +763,7 @@ extern "C" int br_quant_result(br_quant *c, double *theta, double *tpm, uint64_t
 // call that fails leaves the object as it was.
 static int quant_genes(br_quant *c, const uint32_t *tx_gene, int64_t G) {
   hipStream_t st = c->st;
-  const int64_t T = c->n_tx, C = c->n_cls, L = c->n_lab;
+  const int64_t T = c->n_tx, C = c->cls.n_cls, L = c->cls.n_lab;
   uint64_t *small = c->small.as<uint64_t>();
   br_quant::Genes g;
   DropGuard held{c, {&g.first, &g.cnt, &g.loff, &g.labels, &g.uniq, &g.ambig, &g.toff, &g.tx}};
@@ -753,15 +784,14 @@ static int quant_genes(br_quant *c, const uint32_t *tx_gene, int64_t G) {
   HIPCHK(hipMemsetAsync(g.uniq.p, 0, g1 * 8, st)); HIPCHK(hipMemsetAsync(g.ambig.p, 0, g1 * 8, st));
   HIPCHK(hipStreamSynchronize(st));
   if (C > 0) {
-    ColBuf d_txg, key[2], idx[2], pos, glab, goff, gk, big, head, mark, pre, gbeg, key2[2], val2[2], rep;
-    DropGuard tables{c, {&d_txg, &key[0], &key[1], &idx[0], &idx[1], &pos, &glab, &goff, &gk, &big, &head, &mark, &pre, &gbeg, &key2[0], &key2[1],
-                         &val2[0], &val2[1], &rep}};
+    ColBuf d_txg, key[2], idx[2], pos, glab, goff, gk, big, rep;
+    DropGuard tables{c, {&d_txg, &key[0], &key[1], &idx[0], &idx[1], &pos, &glab, &goff, &gk, &big, &rep}};
     // the distinct (class, gene) entries, a class's genes ascending: the gene-label arena
     const size_t l1 = (size_t)L + 1, c1 = (size_t)C + 1;
     RC(c->alloc(d_txg, ((size_t)T + 1) * 4));
     HIPCHK(hipMemcpyAsync(d_txg.p, tx_gene, (size_t)T * 4, hipMemcpyHostToDevice, st));
     RC(c->alloc(key[0], l1 * 8)); RC(c->alloc(key[1], l1 * 8)); RC(c->alloc(idx[0], l1 * 4)); RC(c->alloc(idx[1], l1 * 4));
-    launch_qg_key(st, c->c_loff.as<uint64_t>(), c->c_labels.as<uint32_t>(), d_txg.as<uint32_t>(), C, L, key[0].as<uint64_t>(), idx[0].as<uint32_t>());
+    launch_qg_key(st, c->cls.loff.as<uint64_t>(), c->cls.labels.as<uint32_t>(), d_txg.as<uint32_t>(), C, L, key[0].as<uint64_t>(), idx[0].as<uint32_t>());
     int cur = 0;
     RC(quant_sort(c, key, idx, L, &cur));
     RC(c->alloc(pos, l1 * 8)); RC(quant_tmp(c, L));
@@ -772,11 +802,11 @@ static int quant_genes(br_quant *c, const uint32_t *tx_gene, int64_t G) {
     HIPCHK(hipStreamSynchronize(st));
     if (LE == 0 || LE > (uint64_t)L) return BR_ERR_HIP;
     RC(c->alloc(glab, ((size_t)LE + 1) * 4)); RC(c->alloc(goff, c1 * 8)); RC(c->alloc(gk, c1 * 4));
-    launch_qg_arena(st, key[cur].as<uint64_t>(), pos.as<uint64_t>(), c->c_loff.as<uint64_t>(), L, C, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>());
+    launch_qg_arena(st, key[cur].as<uint64_t>(), pos.as<uint64_t>(), c->cls.loff.as<uint64_t>(), L, C, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>());
     HIPCHK(hipStreamSynchronize(st));
     c->drop(d_txg); c->drop(pos);
     for (int k = 0; k < 2; k++) { c->drop(key[k]); c->drop(idx[k]); }
-    // the classes by the hash of their gene lists; from here it is finish's sequence with a class where finish has a name
+    // the hash of every gene list
     const size_t most = (size_t)(LE / (Q_WAVE_ITEMS + 1) + 1);
     RC(c->alloc(big, most * 4));
     HIPCHK(hipMemsetAsync(small + QS_NBIG, 0, 8, st));
@@ -787,60 +817,13 @@ static int quant_genes(br_quant *c, const uint32_t *tx_gene, int64_t G) {
     RC(c->alloc(key[0], c1 * 8)); RC(c->alloc(key[1], c1 * 8)); RC(c->alloc(idx[0], c1 * 4)); RC(c->alloc(idx[1], c1 * 4));
     const uint64_t mask = c->hash_bits >= 64 ? ~0ull : (1ull << c->hash_bits) - 1;
     launch_qg_hash(st, glab.as<uint32_t>(), goff.as<uint64_t>(), C, big.as<uint32_t>(), n_big, mask, key[0].as<uint64_t>(), idx[0].as<uint32_t>());
-    RC(quant_sort(c, key, idx, C, &cur));
-    RC(c->alloc(head, c1 * 8));
-    auto heads = [&](uint32_t *mk, uint64_t *n_coll) -> int {
-      HIPCHK(hipMemsetAsync(small + QS_COLL, 0, 8, st));
-      launch_q_heads(st, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>(), key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), C, head.as<uint64_t>(),
-                     (unsigned long long *)(small + QS_COLL), mk);
-      HIPCHK(hipMemcpyAsync(n_coll, small + QS_COLL, 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      return BR_OK;
-    };
-    uint64_t n_coll = 0;
-    RC(heads(nullptr, &n_coll));
-    g.collisions = n_coll;
-    if (n_coll) {
-      RC(c->alloc(mark, (size_t)C * 4));
-      HIPCHK(hipMemsetAsync(mark.p, 0, (size_t)C * 4, st));
-      RC(heads(mark.as<uint32_t>(), &n_coll));
-      launch_q_resolve(st, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>(), key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), C, mark.as<uint32_t>(),
-                       key[cur ^ 1].as<uint64_t>(), idx[cur ^ 1].as<uint32_t>());
-      cur ^= 1;
-      RC(heads(nullptr, &n_coll));
-    }
-    RC(quant_tmp(c, C));
-    launch_scan(st, head.as<uint64_t>(), C, c->tmp.as<uint64_t>());   // head -> gene class ids (exclusive), head[C] = their number
-    uint64_t CG = 0;
-    HIPCHK(hipMemcpyAsync(&CG, head.as<uint64_t>() + C, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (CG == 0 || CG > (uint64_t)C) return BR_ERR_HIP;
-    const size_t cg1 = (size_t)CG + 1;
-    RC(c->alloc(gbeg, cg1 * 8));
-    launch_col_gbeg(st, head.as<uint64_t>(), C, gbeg.as<uint64_t>());
-    // a gene class's count: the integer sum of its members' counts, from one scan over the members in sorted order
-    RC(c->alloc(pre, c1 * 8));
-    launch_qg_member_cnt(st, idx[cur].as<uint32_t>(), c->c_cnt.as<uint64_t>(), C, pre.as<uint64_t>());
-    launch_scan(st, pre.as<uint64_t>(), C, c->tmp.as<uint64_t>());
-    // the gene classes by their first name
-    RC(c->alloc(key2[0], cg1 * 8)); RC(c->alloc(key2[1], cg1 * 8)); RC(c->alloc(val2[0], cg1 * 4)); RC(c->alloc(val2[1], cg1 * 4));
-    launch_qg_class_key(st, gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), c->c_first.as<uint64_t>(), (int64_t)CG, key2[0].as<uint64_t>(), val2[0].as<uint32_t>());
-    int cur2 = 0;
-    RC(quant_sort(c, key2, val2, (int64_t)CG, &cur2));
-    RC(c->alloc(g.first, cg1 * 8)); RC(c->alloc(g.cnt, cg1 * 8)); RC(c->alloc(g.loff, cg1 * 8)); RC(c->alloc(rep, cg1 * 4));
-    launch_qg_class_fill(st, key2[cur2].as<uint64_t>(), val2[cur2].as<uint32_t>(), gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), pre.as<uint64_t>(),
-                         gk.as<uint32_t>(), (int64_t)CG, g.first.as<uint64_t>(), g.cnt.as<uint64_t>(), g.loff.as<uint64_t>(), rep.as<uint32_t>());
-    RC(quant_tmp(c, (int64_t)CG));
-    launch_scan(st, g.loff.as<uint64_t>(), (int64_t)CG, c->tmp.as<uint64_t>());
-    uint64_t LG = 0;
-    HIPCHK(hipMemcpyAsync(&LG, g.loff.as<uint64_t>() + CG, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (LG == 0 || LG > LE) return BR_ERR_HIP;
-    RC(c->alloc(g.labels, ((size_t)LG + 1) * 4));
-    launch_qg_labels(st, g.loff.as<uint64_t>(), rep.as<uint32_t>(), goff.as<uint64_t>(), glab.as<uint32_t>(), g.cnt.as<uint64_t>(), (int64_t)CG, (int64_t)LG,
+    // their classes: a transcript class's first name and count are the item's, and rep names the class whose gene list it is
+    RC(quant_classes(c, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>(), c->cls.first.as<uint64_t>(), c->cls.cnt.as<uint64_t>(), key, idx, C, g, &rep));
+    if (g.n_lab == 0 || (uint64_t)g.n_lab > LE) return BR_ERR_HIP;
+    RC(c->alloc(g.labels, ((size_t)g.n_lab + 1) * 4));
+    launch_qg_labels(st, g.loff.as<uint64_t>(), rep.as<uint32_t>(), goff.as<uint64_t>(), glab.as<uint32_t>(), g.cnt.as<uint64_t>(), g.n_cls, g.n_lab,
                      g.labels.as<uint32_t>(), g.uniq.as<uint64_t>(), g.ambig.as<uint64_t>());
     HIPCHK(hipStreamSynchronize(st));
-    g.n_cls = (int64_t)CG; g.n_lab = (int64_t)LG;
   }
   c->gene = std::move(g);   // (a swap: the guard drops the empty tables the object had)
   return BR_OK;
@@ -859,16 +842,7 @@ extern "C" int br_quant_genes(br_quant *c, const uint32_t *tx_gene, int64_t n_ge
 }
 
 extern "C" int br_quant_gene_classes(br_quant *c, uint64_t *label_off, uint32_t *labels, uint64_t *counts, uint64_t *first_name) {
-  if (!c || !c->genes_done) return BR_ERR_INVALID_ARG;
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->st;
-  const size_t C = (size_t)c->gene.n_cls, L = (size_t)c->gene.n_lab;
-  if (label_off) { if (C) HIPCHK(hipMemcpyAsync(label_off, c->gene.loff.p, (C + 1) * 8, hipMemcpyDeviceToHost, st)); else label_off[0] = 0; }
-  if (labels && L) HIPCHK(hipMemcpyAsync(labels, c->gene.labels.p, L * 4, hipMemcpyDeviceToHost, st));
-  if (counts && C) HIPCHK(hipMemcpyAsync(counts, c->gene.cnt.p, C * 8, hipMemcpyDeviceToHost, st));
-  if (first_name && C) HIPCHK(hipMemcpyAsync(first_name, c->gene.first.p, C * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return BR_OK;
+  return c && c->genes_done ? quant_copy_classes(c, c->gene, label_off, labels, counts, first_name) : BR_ERR_INVALID_ARG;
 }
 
 extern "C" int br_quant_gene_result(br_quant *c, double *num_reads, double *tpm, double *length, double *eff_length, uint64_t *unique,
@@ -936,16 +910,7 @@ extern "C" int br_quant_gene_boot_summary(br_quant *c, double *mean, double *var
   if (!c || !c->genes_done || !c->boot_done || !c->boot_res.p) return BR_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
   RC(quant_gene_boot(c));
-  hipStream_t st = c->st;
-  const size_t G = (size_t)c->n_genes;
-  ColBuf mv;   // mean, then var
-  DropGuard dropper{c, {&mv}};
-  RC(c->alloc(mv, (2 * G + 1) * 8));
-  launch_q_boot_summary(st, c->gene_boot.as<double>(), (int64_t)G, (int32_t)c->bootstraps, mv.as<double>(), mv.as<double>() + G);
-  if (mean && G) HIPCHK(hipMemcpyAsync(mean, mv.p, G * 8, hipMemcpyDeviceToHost, st));
-  if (var && G) HIPCHK(hipMemcpyAsync(var, mv.as<double>() + G, G * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return BR_OK;
+  return quant_summary(c, c->gene_boot, (size_t)c->n_genes, mean, var);
 }
 
 extern "C" int br_quant_gene_stats(const br_quant *c, double *seconds, int64_t *n_gene_labels, uint64_t *collisions) {
@@ -964,8 +929,8 @@ extern "C" int br_quant_stats(const br_quant *c, uint64_t *held_bytes, uint64_t 
   if (add_seconds) *add_seconds = c->add_s;
   if (finish_seconds) *finish_seconds = c->finish_s;
   if (em_seconds) *em_seconds = c->em_s;
-  if (collisions) *collisions = c->collisions;
+  if (collisions) *collisions = c->cls.collisions;
   if (n_unassigned) *n_unassigned = c->finished ? c->n - c->n_assigned : 0;
-  if (n_labels) *n_labels = c->n_lab;
+  if (n_labels) *n_labels = c->cls.n_lab;
   return BR_OK;
 }

@@ -58,11 +58,15 @@ void launch_q_heads(hipStream_t st, const uint32_t *lab, const uint64_t *noff, c
 // the marked runs ordered by (k, labels, name index), every other item where it was
 void launch_q_resolve(hipStream_t st, const uint32_t *lab, const uint64_t *noff, const uint32_t *nk, const uint64_t *key,
                       const uint32_t *idx, int64_t n, const uint32_t *mark, uint64_t *key_out, uint32_t *idx_out);
-// classes in hash order -> (first name index, class in hash order), to be sorted
-void launch_q_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *idx, int64_t n_cls, uint64_t *key, uint32_t *val);
-// classes in their final order: first name, count, number of labels (to be scanned into label_off)
-void launch_q_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *nk,
-                         int64_t n_cls, uint64_t *first, uint64_t *cnt, uint64_t *label_off);
+// classes in hash order (gbeg: their starts among the sorted items idx) -> (first name, class in hash order), to be sorted.  An
+// item's first name is item_first[i]; NULL: i itself (a read name)
+void launch_q_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *item_first, int64_t n_cls, uint64_t *key,
+                        uint32_t *val);
+// classes in their final order: first name, count, number of labels (to be scanned into label_off) and, rep != NULL, an item
+// whose list is the class's.  The count is the sum of the items' weights, from pre, the scanned weights of the sorted items; NULL:
+// every item weighs 1
+void launch_q_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *pre,
+                         const uint32_t *nk, int64_t n_cls, uint64_t *first, uint64_t *cnt, uint64_t *label_off, uint32_t *rep);
 // one thread per label entry e: labels[e], its class, (transcript, e) for the transposed table; *bad |= 1 for a transcript
 // whose length is <= 0 (lens != NULL)
 void launch_q_labels(hipStream_t st, const uint64_t *label_off, const uint64_t *first, const uint64_t *noff, const uint32_t *lab,
@@ -128,15 +132,9 @@ void launch_qg_arena(hipStream_t st, const uint64_t *key, const uint64_t *pos, c
 // key[c] = the names' hash of class c's gene list under mask, idx[c] = c; big: the classes of more than Q_WAVE_ITEMS genes (launch_q_bin)
 void launch_qg_hash(hipStream_t st, const uint32_t *glab, const uint64_t *goff, int64_t n_cls, const uint32_t *big, uint32_t n_big, uint64_t mask,
                     uint64_t *key, uint32_t *idx);
-// w[j] = cnt[idx[j]]: the sorted members' counts (to be scanned)
+// w[j] = cnt[idx[j]]: the sorted items' weights (to be scanned into launch_q_class_fill's pre)
 void launch_qg_member_cnt(hipStream_t st, const uint32_t *idx, const uint64_t *cnt, int64_t n, uint64_t *w);
-// gene classes in hash order -> (first name, gene class in hash order), to be sorted
-void launch_qg_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *c_first, int64_t n, uint64_t *key, uint32_t *val);
-// gene classes in their final order: first name, count (pre: the scanned member counts), number of labels (to be scanned) and
-// the transcript class whose list is theirs
-void launch_qg_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *pre,
-                          const uint32_t *gk, int64_t n, uint64_t *first, uint64_t *cnt, uint64_t *label_off, uint32_t *rep);
-// labels[e], and cnt of e's class added to uniq / ambig of its gene (zeroed by the caller)
+// labels[e] from the list of rep[class of e], and cnt of e's class added to uniq / ambig of its gene (zeroed by the caller)
 void launch_qg_labels(hipStream_t st, const uint64_t *label_off, const uint32_t *rep, const uint64_t *goff, const uint32_t *glab, const uint64_t *cnt,
                       int64_t n_cls, int64_t n_lab, uint32_t *labels, uint64_t *uniq, uint64_t *ambig);
 // per gene the sums over its transcripts g_tx[g_toff[g] .. g_toff[g + 1]) in that order; lens / eff / eff_length may be NULL

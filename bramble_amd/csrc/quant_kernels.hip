@@ -13,10 +13,10 @@
 //            k_q_boot_classes / k_q_boot_tx, the EM over a chunk of W replicates with the replicate innermost, a lane per (item,
 //            replicate) and a wave per larger item; k_q_boot_store, k_q_boot_summary
 //   genes    k_qg_key + radix passes + k_qg_flag + scan + k_qg_arena: a class's distinct genes, ascending; k_qg_hash (a lane, or a
-//            wave above Q_WAVE_ITEMS genes); the classes' sequence again on the gene lists -- radix passes, k_q_heads, k_q_resolve --
-//            then k_qg_member_cnt + scan (a gene class's count), k_qg_class_key, k_qg_class_fill, k_qg_labels (with the unique /
-//            ambiguous names per gene: integer atomics); k_qg_sums (a lane a gene, its transcripts one after the other) and
-//            k_qg_boot (a lane per replicate and gene)
+//            wave above Q_WAVE_ITEMS genes); the classes' kernels on the gene lists -- radix passes, k_q_heads, k_q_resolve,
+//            k_q_class_key, k_q_class_fill -- with k_qg_member_cnt + scan for the members' counts (an item's weight); k_qg_labels
+//            (with the unique / ambiguous names per gene: integer atomics); k_qg_sums (a lane a gene, its transcripts one after
+//            the other) and k_qg_boot (a lane per replicate and gene)
 //   lengths  ("eff_len") k_q_frag / k_q_frag_big behind the names of an add: per read name of one label the length of its first
 //            fragment, counted in LDS by integer atomics and flushed to the add's own table with one integer atomicAdd per
 //            non-zero bin and block; k_q_fld_commit adds a good add's table to the run's; at finish k_q_fld_prefix (C and S) and
@@ -58,6 +58,12 @@ __device__ __forceinline__ bool list_less(const uint32_t *lab, const uint64_t *n
   for (uint32_t i = 0; i < ka; i++) if (x[i] != y[i]) return x[i] < y[i];
   eq = true;
   return false;
+}
+// the class of label entry e: the last c with label_off[c] <= e
+__device__ __forceinline__ int64_t class_of_entry(const uint64_t *label_off, int64_t n_cls, int64_t e) {
+  int64_t lo = 0, hi = n_cls;
+  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (label_off[mid] <= (uint64_t)e) lo = mid + 1; else hi = mid; }
+  return lo - 1;
 }
 unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
@@ -406,25 +412,31 @@ __global__ void __launch_bounds__(256) k_q_resolve(const uint32_t *lab, const ui
   key_out[pos] = kj; idx_out[pos] = me;
 }
 
-__global__ void __launch_bounds__(256) k_q_class_key(const uint64_t *gbeg, const uint32_t *idx, int64_t n_cls, uint64_t *key, uint32_t *val) {
-  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (c < n_cls) { key[c] = idx[gbeg[c]]; val[c] = (uint32_t)c; }   // (names inside a class ascend: its first item is its first name)
-}
-__global__ void __launch_bounds__(256) k_q_class_fill(const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *nk,
-                                                      int64_t n_cls, uint64_t *first, uint64_t *cnt, uint64_t *label_off) {
+// An item's first name is item_first[i], or i itself where the table is NULL; the items of a class ascend, and so do their first
+// names, so a class's first item has its first name
+__global__ void __launch_bounds__(256) k_q_class_key(const uint64_t *gbeg, const uint32_t *idx, const uint64_t *item_first, int64_t n_cls,
+                                                     uint64_t *key, uint32_t *val) {
   const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (c >= n_cls) return;
-  const uint32_t s = val[c];
-  first[c] = key[c]; cnt[c] = gbeg[s + 1] - gbeg[s]; label_off[c] = nk[key[c]];
+  const uint32_t i = idx[gbeg[c]];
+  key[c] = item_first ? item_first[i] : (uint64_t)i; val[c] = (uint32_t)c;
+}
+// An item's weight is 1 where pre is NULL (a class counts its items), else pre holds the scanned weights of the sorted items
+__global__ void __launch_bounds__(256) k_q_class_fill(const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx,
+                                                      const uint64_t *pre, const uint32_t *nk, int64_t n_cls, uint64_t *first, uint64_t *cnt,
+                                                      uint64_t *label_off, uint32_t *rep) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n_cls) return;
+  const uint32_t s = val[c], r = idx[gbeg[s]];
+  first[c] = key[c]; cnt[c] = pre ? pre[gbeg[s + 1]] - pre[gbeg[s]] : gbeg[s + 1] - gbeg[s]; label_off[c] = nk[r];
+  if (rep) rep[c] = r;
 }
 __global__ void __launch_bounds__(256) k_q_labels(const uint64_t *label_off, const uint64_t *first, const uint64_t *noff, const uint32_t *lab,
                                                   int64_t n_cls, int64_t n_lab, const int64_t *lens, uint32_t *labels, uint32_t *ecls,
                                                   uint64_t *tkey, uint32_t *tidx, uint32_t *bad) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= n_lab) return;
-  int64_t lo = 0, hi = n_cls;   // the class of entry e: the last c with label_off[c] <= e
-  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (label_off[mid] <= (uint64_t)e) lo = mid + 1; else hi = mid; }
-  const int64_t c = lo - 1;
+  const int64_t c = class_of_entry(label_off, n_cls, e);
   const uint32_t t = lab[noff[first[c]] + ((uint64_t)e - label_off[c])];
   labels[e] = t; ecls[e] = (uint32_t)c; tkey[e] = t; tidx[e] = (uint32_t)e;
   if (lens && lens[t] <= 0) *bad = 1;
@@ -697,18 +709,8 @@ __global__ void __launch_bounds__(256) k_q_boot_summary(const double *res, int64
 
 // ---- gene level (the definitions: bramble_amd.h, br_quant) -------------------------------------------------------------------------
 // The transcript classes relabelled by gene and merged.  A class's gene list -- the distinct genes of its labels, ascending --
-// comes from one radix sort of (class, gene) keys; the lists go through finish's own sequence with a class where finish has a
-// name: k_q_heads / k_q_resolve compare them under the hash, a scan of the members' counts gives a gene class its count, and
-// its first member in class order (the classes are in the order of their first names) gives its first name.
-namespace {
-// the class of label entry e: the last c with label_off[c] <= e
-__device__ __forceinline__ int64_t class_of_entry(const uint64_t *label_off, int64_t n_cls, int64_t e) {
-  int64_t lo = 0, hi = n_cls;
-  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (label_off[mid] <= (uint64_t)e) lo = mid + 1; else hi = mid; }
-  return lo - 1;
-}
-}  // namespace
-
+// comes from one radix sort of (class, gene) keys; the lists then go through the classes' kernels as items whose first name is
+// the transcript class's and whose weight is its count (k_qg_member_cnt gathers the weights in sorted order, to be scanned).
 __global__ void __launch_bounds__(256) k_qg_key(const uint64_t *label_off, const uint32_t *labels, const uint32_t *tx_gene, int64_t n_cls,
                                                 int64_t n_lab, uint64_t *key, uint32_t *idx) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -760,19 +762,6 @@ __global__ void __launch_bounds__(256) k_qg_hash(const uint32_t *glab, const uin
 __global__ void __launch_bounds__(256) k_qg_member_cnt(const uint32_t *idx, const uint64_t *cnt, int64_t n, uint64_t *w) {
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j < n) w[j] = cnt[idx[j]];
-}
-__global__ void __launch_bounds__(256) k_qg_class_key(const uint64_t *gbeg, const uint32_t *idx, const uint64_t *c_first, int64_t n,
-                                                      uint64_t *key, uint32_t *val) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g < n) { key[g] = c_first[idx[gbeg[g]]]; val[g] = (uint32_t)g; }   // (members ascend: the first one has the smallest first name)
-}
-__global__ void __launch_bounds__(256) k_qg_class_fill(const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx,
-                                                       const uint64_t *pre, const uint32_t *gk, int64_t n, uint64_t *first, uint64_t *cnt,
-                                                       uint64_t *label_off, uint32_t *rep) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= n) return;
-  const uint32_t s = val[g], r = idx[gbeg[s]];
-  first[g] = key[g]; cnt[g] = pre[gbeg[s + 1]] - pre[gbeg[s]]; label_off[g] = gk[r]; rep[g] = r;
 }
 // one lane per gene-label entry: the label, and the class's count to its gene's unique or ambiguous names (integer atomics)
 __global__ void __launch_bounds__(256) k_qg_labels(const uint64_t *label_off, const uint32_t *rep, const uint64_t *goff, const uint32_t *glab,
@@ -836,13 +825,6 @@ void launch_qg_hash(hipStream_t st, const uint32_t *glab, const uint64_t *goff, 
 }
 void launch_qg_member_cnt(hipStream_t st, const uint32_t *idx, const uint64_t *cnt, int64_t n, uint64_t *w) {
   if (n > 0) hipLaunchKernelGGL(k_qg_member_cnt, dim3(blocks256(n)), dim3(256), 0, st, idx, cnt, n, w);
-}
-void launch_qg_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *c_first, int64_t n, uint64_t *key, uint32_t *val) {
-  if (n > 0) hipLaunchKernelGGL(k_qg_class_key, dim3(blocks256(n)), dim3(256), 0, st, gbeg, idx, c_first, n, key, val);
-}
-void launch_qg_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *pre,
-                          const uint32_t *gk, int64_t n, uint64_t *first, uint64_t *cnt, uint64_t *label_off, uint32_t *rep) {
-  if (n > 0) hipLaunchKernelGGL(k_qg_class_fill, dim3(blocks256(n)), dim3(256), 0, st, key, val, gbeg, idx, pre, gk, n, first, cnt, label_off, rep);
 }
 void launch_qg_labels(hipStream_t st, const uint64_t *label_off, const uint32_t *rep, const uint64_t *goff, const uint32_t *glab, const uint64_t *cnt,
                       int64_t n_cls, int64_t n_lab, uint32_t *labels, uint64_t *uniq, uint64_t *ambig) {
@@ -938,12 +920,13 @@ void launch_q_resolve(hipStream_t st, const uint32_t *lab, const uint64_t *noff,
                       const uint32_t *idx, int64_t n, const uint32_t *mark, uint64_t *key_out, uint32_t *idx_out) {
   if (n > 0) hipLaunchKernelGGL(k_q_resolve, dim3(blocks256(n)), dim3(256), 0, st, lab, noff, nk, key, idx, n, mark, key_out, idx_out);
 }
-void launch_q_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *idx, int64_t n_cls, uint64_t *key, uint32_t *val) {
-  if (n_cls > 0) hipLaunchKernelGGL(k_q_class_key, dim3(blocks256(n_cls)), dim3(256), 0, st, gbeg, idx, n_cls, key, val);
+void launch_q_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *item_first, int64_t n_cls, uint64_t *key,
+                        uint32_t *val) {
+  if (n_cls > 0) hipLaunchKernelGGL(k_q_class_key, dim3(blocks256(n_cls)), dim3(256), 0, st, gbeg, idx, item_first, n_cls, key, val);
 }
-void launch_q_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *nk,
-                         int64_t n_cls, uint64_t *first, uint64_t *cnt, uint64_t *label_off) {
-  if (n_cls > 0) hipLaunchKernelGGL(k_q_class_fill, dim3(blocks256(n_cls)), dim3(256), 0, st, key, val, gbeg, nk, n_cls, first, cnt, label_off);
+void launch_q_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *pre,
+                         const uint32_t *nk, int64_t n_cls, uint64_t *first, uint64_t *cnt, uint64_t *label_off, uint32_t *rep) {
+  if (n_cls > 0) hipLaunchKernelGGL(k_q_class_fill, dim3(blocks256(n_cls)), dim3(256), 0, st, key, val, gbeg, idx, pre, nk, n_cls, first, cnt, label_off, rep);
 }
 void launch_q_labels(hipStream_t st, const uint64_t *label_off, const uint64_t *first, const uint64_t *noff, const uint32_t *lab,
                      int64_t n_cls, int64_t n_lab, const int64_t *lens, uint32_t *labels, uint32_t *ecls, uint64_t *tkey,

@@ -3,7 +3,7 @@ of the definitions (test_quant_genes_cpu.py), never against the device's own gen
 bit for bit.  The device's transcript-level theta / tpm / effective lengths / replicates are inputs to the yardstick (the other
 quant tests hold them to their references).  On the oracle's rows of the synthetic inputs under three maps, on hand-built tables
 for the wave-sized and the large paths, with colliding hashes on purpose, in every order of the calls; what is refused; and the
-command line."""
+command line.  One test holds the two levels to each other: the gene classes against finish on rows relabelled by gene."""
 import functools
 import os
 import re
@@ -169,6 +169,28 @@ def test_wide_classes(bits):
     assert sorted(len(s) for s in want["labels"])[-3:] == [2, 64, 65] and want["counts"][want["labels"].index(tuple(range(65)))] == 2
     assert (q.gene_stats()["collisions"] > 0) == (bits != 64)
     q.close()
+
+
+@pytest.mark.parametrize("bits", [64, 1])
+def test_gene_classes_are_finish_on_relabelled_rows(bits):
+    """The defining property, device against device: the gene classes are what finish makes of the same names when every row's
+    transcript id is its gene before the adds (the add drops the repeats inside a name).  Some names come twice or more, so
+    the transcript classes that merge do not all count 1.  At hash_bits 1 both levels go through the collision repair."""
+    names, n_tx, tx_gene, n_genes = _wide()
+    names = names + [names[1], names[6], names[3], names[0], names[0], names[9]]
+    a = _quant_of(names, n_tx, hash_bits=bits)
+    assert max(a.classes()[2].tolist()) > 1
+    a.genes(tx_gene, n_genes)
+    b = _quant_of([[int(tx_gene[t]) for t in nm] for nm in names], n_genes, hash_bits=bits)
+    assert a.n_gene_classes == b.n_classes
+    for got, want in zip(a.gene_classes(), b.classes()):
+        assert got.dtype == want.dtype and np.array_equal(got, want)
+    ga, tb = a.gene_result(em=False), b.result(em=False)
+    assert np.array_equal(ga["unique"], tb["unique"]) and np.array_equal(ga["ambig"], tb["ambig"])
+    assert a.gene_stats()["n_gene_labels"] == b.stats()["n_labels"]
+    assert (a.gene_stats()["collisions"] > 0) == (b.stats()["collisions"] > 0) == (bits != 64)
+    a.close()
+    b.close()
 
 
 def test_a_gene_of_200_transcripts():
