@@ -54,7 +54,8 @@ __device__ __forceinline__ uint32_t pick_from(uint64_t z0, const uint8_t *name, 
 //     mate without survivors            -> the leader (lower index) is SOLO, the other one emits nothing
 //     both with survivors               -> PAIR: kept = transcripts common to both; none common and one transcript
 //                                          each -> both kept (a pair on different transcripts); else nothing
-// Only PAIRs need transcript ids.  Every lane of a PAIR walks its own mask and stages its survivors' tids (slab rows
+// Only PAIRs need transcript ids.  Nearly all of them are settled in registers, as the AND of two 64-bit tid masks (pair_window,
+// BM); for the others every lane of a PAIR walks its own mask and stages its survivors' tids (slab rows
 // under the set bits) in LDS, a list rounded up to four slots so that lists are read four tids at a time.  The
 // intersection is done once per pair, from the ACTIVE side (the leader; or a mate whose leader sits outside the wave's
 // window, which then stages a copy of the leader's list next to its own): one lane per active entry scans the partner's
@@ -99,11 +100,48 @@ __device__ __forceinline__ void stage_list(const uint32_t *__restrict__ s_tid, u
   }
 }
 
-// one window of 64 alignments starting at w0; false: its lists do not fit CAP slots (nothing of the PAIRs was written)
+// the next eight survivors of a mask (mm != 0), as stage_list walks them: their tids, eight gathers in flight, and their mask bits,
+// a byte each in pb; past the list's end the round's first survivor again, which changes no minimum, maximum or OR.
+// c0 / c1: what turns a bit below / from n0 into its slab row (row_of_bit: lo0, lo1 - n0)
+__device__ __forceinline__ void tids8(const uint32_t *__restrict__ s_tid, uint64_t &mm, uint32_t c0, uint32_t c1, uint32_t n0,
+                                      uint2 &pb, uint32_t (&t)[8]) {
+  uint32_t b[8];
+#pragma unroll
+  for (int u = 0; u < 8; u++) { b[u] = mm ? (uint32_t)__builtin_ctzll(mm) : b[0]; mm &= mm - 1; }
+#pragma unroll
+  for (int u = 0; u < 8; u++) t[u] = s_tid[b[u] + (b[u] < n0 ? c0 : c1)];
+  pb = make_uint2(b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24), b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24));
+}
+// a round's tids into the list's tid mask: bit (tid - lo) per survivor, lo = the smallest tid so far -- a round that lowers lo
+// moves the mask up.  A list that spans more than 64 tids loses bits here; its hi - lo says so, and the span rule sends it away.
+__device__ __forceinline__ void fold8(const uint32_t (&t)[8], uint32_t &lo, uint32_t &hi, uint64_t &tm) {
+  uint32_t rlo = t[0], rhi = t[0];
+#pragma unroll
+  for (int u = 1; u < 8; u++) { rlo = min(rlo, t[u]); rhi = max(rhi, t[u]); }
+  const uint32_t nlo = min(lo, rlo), sh = lo - nlo;
+  tm = sh > 63u ? 0ull : tm << sh;
+  lo = nlo; hi = max(hi, rhi);
+#pragma unroll
+  for (int u = 0; u < 8; u++) tm |= 1ull << ((t[u] - lo) & 63u);
+}
+
+// of a round's survivors (tids t, mask bits pb) the mask bits of those whose tid bit, relative to base, is in common
+__device__ __forceinline__ uint64_t keep8(uint2 pb, const uint32_t (&t)[8], uint64_t common, uint32_t base) {
+  uint64_t f = 0;
+#pragma unroll
+  for (int u = 0; u < 8; u++) f |= ((common >> ((t[u] - base) & 63u)) & 1ull) << (((u < 4 ? pb.x : pb.y) >> (8 * (u & 3))) & 63u);
+  return f;
+}
+
+// one window of 64 alignments starting at w0; false: its lists do not fit CAP slots (nothing of the list path's PAIRs was written)
 // Lanes 1..62 own their alignments; lanes 0 and 63 are the neighbours on either side, loaded and staged like the others so
 // that a pair that straddles two waves' ranges (mates are neighbours as a rule) finds its partner inside the window; they
 // write nothing.  Partners further apart than that are copied next to the lane that needs them.
-template <int CAP>
+// BM (br_ctx_set_param "pair_bitmask"): a pair whose partner is inside the window and whose two lists together span at most 64
+// tids -- transcripts are numbered in location order, so that is nearly every pair -- never reaches the lists: each lane
+// folds its tids into a 64-bit mask relative to the pair's smallest tid, and the intersection is one AND.  What the rule turns
+// away takes the list path below, with the same results: how transcripts are numbered decides the speed and nothing else.
+template <int CAP, bool BM>
 __device__ __forceinline__ bool pair_window(const DirectArgs &D, PmSh<CAP> &S, int64_t w0, int lane) {
   const int64_t i64 = w0 + lane;
   const bool valid = i64 >= 0 && i64 < D.n_aln;
@@ -137,8 +175,58 @@ __device__ __forceinline__ bool pair_window(const DirectArgs &D, PmSh<CAP> &S, i
     D.n_kept[i] = solo ? cnt : 0u; D.n_rows[i] = solo ? cnt : 0u; D.pflag[i] = 0;
   }
   // (a neighbour lane takes part only for a partner inside the window)
-  const bool pair = role == PR_PAIR && !defer && (owner || m_in);
+  bool pair = role == PR_PAIR && !defer && (owner || m_in);
   if (!__ballot(pair && owner)) return true;
+  uint64_t on_list = 0;   // (BM) the owners the list path resolves
+  if (BM) {
+    const bool mp = pair && m_in;   // (the partner's lane reaches the same verdicts: every test here is symmetric)
+    uint32_t t0[8], t1[8], lo = 0xffffffffu, hi = 0;
+    uint2 pb0, pb1, pb;
+    const uint32_t c0 = rg.x, c1 = rg.z - n0;
+    uint64_t tm = 0, mm = mp ? mk : 0;
+    // The kernel runs at full occupancy and waits: what it costs is the number of dependent round trips a wave makes.  So the
+    // first two rounds of eight (97 % of the bench's lists are within them) are asked for together, the second one skipped
+    // wave-uniformly when no lane has that many, and their 16 tids stay in registers for the pass over the survivors below.
+    // (A third round in the same trip takes 65 VGPRs.)  The rounds leave their mask bits packed a byte each (pb): the pass over
+    // the survivors reads them with one bit-field extract where finding them again costs eight 64-bit operations each, and the
+    // kernel, once it waits less, is bound by what it issues.
+    const bool any2 = __ballot(mp && cnt > 8u) != 0;
+    if (mm) tids8(D.s_tid, mm, c0, c1, n0, pb0, t0);
+    if (any2 && mm) tids8(D.s_tid, mm, c0, c1, n0, pb1, t1);
+    if (mp) fold8(t0, lo, hi, tm);
+    if (mp && cnt > 8u) fold8(t1, lo, hi, tm);
+    while (mm) { uint32_t t[8]; tids8(D.s_tid, mm, c0, c1, n0, pb, t); fold8(t, lo, hi, tm); }
+    const uint32_t lo_p = __shfl(lo, src), hi_p = __shfl(hi, src), cnt_p = __shfl(cnt, src);
+    const uint32_t base = min(lo, lo_p);
+    const bool fits = mp && max(hi, hi_p) - base <= 63u;   // the span rule
+    const uint64_t tmb = fits ? tm << (lo - base) : 0ull;
+    const uint64_t common = tmb & __shfl((unsigned long long)tmb, src);
+    if (fits) {
+      uint64_t fmask = mk;   // every survivor is common: the usual case
+      if (common == 0) fmask = (cnt == 1u && cnt_p == 1u) ? mk : 0ull;   // a pair on different transcripts, or nothing
+      else if (common != tmb) {   // the survivors whose tid bit is common: the first 16 from registers, the others gathered again (L1 hits)
+        fmask = keep8(pb0, t0, common, base);
+        if (cnt > 8u) fmask |= keep8(pb1, t1, common, base);
+        if (cnt > 16u) {
+          mm = mk;
+          for (int u = 0; u < 16; u++) mm &= mm - 1;
+          while (mm) { uint32_t t[8]; tids8(D.s_tid, mm, c0, c1, n0, pb, t); fmask |= keep8(pb, t, common, base); }
+        }
+      }
+      if (owner) {
+        const uint32_t nk = (uint32_t)__popcll(fmask);
+        const bool paired = nk != 0;
+        D.fm[i] = make_uint2((uint32_t)fmask, (uint32_t)(fmask >> 32));
+        D.n_kept[i] = nk;
+        D.n_rows[i] = leader ? 2u * nk : 0u;
+        D.pflag[i] = (uint8_t)((paired ? PF_PAIRED : 0u) | ((paired && common != 0) ? PF_SAME : 0u) | ((paired && !leader) ? PF_MATE : 0u));
+      }
+    }
+    // the list path: what the span rule turned away, and partners outside the window
+    pair = pair && !fits;
+    on_list = __ballot(pair && owner);
+    if (!on_list) return true;
+  }
   const bool active = pair && (leader || !m_in);
   const uint32_t cnt4 = (cnt + 3u) & ~3u;
   const uint32_t ext = (active && !m_in) ? (uint32_t)__popcll(mk_p) : 0u;
@@ -189,22 +277,28 @@ __device__ __forceinline__ bool pair_window(const DirectArgs &D, PmSh<CAP> &S, i
     D.n_rows[i] = leader ? 2u * nk : 0u;
     D.pflag[i] = (uint8_t)((paired ? PF_PAIRED : 0u) | ((paired && S.same[lane]) ? PF_SAME : 0u) | ((paired && !leader) ? PF_MATE : 0u));
   }
+  // br_ctx_direct_diag: the alignments the lists resolved, one atomic per wave that has any, spread like k_group_desc's
+  if (BM && lane == 0)
+    atomicAdd((unsigned long long *)&D.counters[GD_SLOT0 + (size_t)((uint64_t)(w0 + 1) / 62u & (GD_SLOTS - 1)) * GD_SLOT_STRIDE + PM_SLOT_WORD],
+              (unsigned long long)__popcll(on_list));
   return true;
 }
 
+template <bool BM>
 __global__ void __launch_bounds__(256) k_pair_mask(DirectArgs D) {
   __shared__ PmSh<PM_CAP> sh_all[4];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t wi = (int64_t)blockIdx.x * 4 + wv;   // window: alignments 62 * wi .. 62 * wi + 61 (+ a neighbour on either side)
   const int64_t w0 = wi * 62 - 1;
   if (w0 + 1 >= D.n_aln) return;   // the whole wave
-  if (!pair_window<PM_CAP>(D, sh_all[wv], w0, lane) && lane == 0) D.pm_list[atomicAdd(D.pm_n, 1u)] = (uint32_t)wi;
+  if (!pair_window<PM_CAP, BM>(D, sh_all[wv], w0, lane) && lane == 0) D.pm_list[atomicAdd(D.pm_n, 1u)] = (uint32_t)wi;
 }
+template <bool BM>
 __global__ void __launch_bounds__(64) k_pair_mask_wide(DirectArgs D) {
   __shared__ PmSh<PM_CAP_WIDE> sh;
   const uint32_t n_work = *D.pm_n;
   for (uint32_t q = blockIdx.x; q < n_work; q += gridDim.x) {
-    (void)pair_window<PM_CAP_WIDE>(D, sh, (int64_t)D.pm_list[q] * 62 - 1, (int)threadIdx.x);
+    (void)pair_window<PM_CAP_WIDE, BM>(D, sh, (int64_t)D.pm_list[q] * 62 - 1, (int)threadIdx.x);
     WAVE_SYNC();
   }
 }
@@ -847,10 +941,14 @@ static inline int grid_for_d(int64_t n, int per_block) { return (int)((n + per_b
 void launch_name_seed(hipStream_t st, const DirectArgs &D) {
   if (D.n_groups > 0 && D.names) hipLaunchKernelGGL(k_name_seed, dim3(grid_for_d(D.n_groups, 256)), dim3(256), 0, st, D);
 }
-void launch_pair_mask(hipStream_t st, const DirectArgs &D, int wide_blocks) {
+template <bool BM>
+static void launch_pair_mask_t(hipStream_t st, const DirectArgs &D, int wide_blocks) {
+  hipLaunchKernelGGL((k_pair_mask<BM>), dim3(grid_for_d(D.n_aln, 4 * 62)), dim3(256), 0, st, D);   // a wave per 62 alignments
+  hipLaunchKernelGGL((k_pair_mask_wide<BM>), dim3(wide_blocks), dim3(64), 0, st, D);   // the windows the first kernel listed (dense loci)
+}
+void launch_pair_mask(hipStream_t st, const DirectArgs &D, int wide_blocks, bool bitmask) {
   if (D.n_aln <= 0) return;
-  hipLaunchKernelGGL(k_pair_mask, dim3(grid_for_d(D.n_aln, 4 * 62)), dim3(256), 0, st, D);   // a wave per 62 alignments
-  hipLaunchKernelGGL(k_pair_mask_wide, dim3(wide_blocks), dim3(64), 0, st, D);   // the windows the first kernel listed (dense loci)
+  if (bitmask) launch_pair_mask_t<true>(st, D, wide_blocks); else launch_pair_mask_t<false>(st, D, wide_blocks);
 }
 void launch_big_collect(hipStream_t st, const ProjectArgs &A, const DirectArgs &D, int n_blocks) {
   if (D.n_aln > 0 && A.ix.n_rows != 0) hipLaunchKernelGGL((k_big<0>), dim3(n_blocks), dim3(64), 0, st, A, D);

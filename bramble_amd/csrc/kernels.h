@@ -223,7 +223,7 @@ __device__ __forceinline__ bool rows_over(const uint64_t *tot, uint64_t lim_r) {
 // sets), one fused scan places every kept match, and the emit kernels write the packed rows themselves: no match table,
 // no per-record r_rec, no k_pair<true> / k_rows.
 //   k_name_seed     per read name: the first mt19937_64 output of its seed (the primary tie-break's only heavy part; it
-//                   needs nothing but the name, so it runs beside the count pass)
+//                   needs nothing but the name, so it runs beside k_pair_mask)
 //   k_pair_mask     per alignment: filtered survivor mask, records per leader
 //   k_big_collect / k_pair_big   the same for alignments with > 64 candidate rows (tid lists in a side arena)
 //   k_scan5_*       kept matches -> class-list position, CIGAR arena base, row offsets (one pass, one host wait)
@@ -276,8 +276,10 @@ struct DirectArgs {
 #define GD_SLOT0 16
 #define GD_SLOT_STRIDE 16
 #define GD_COUNTER_WORDS (GD_SLOT0 + GD_SLOTS * GD_SLOT_STRIDE)
+// third word of every slot: the PAIR alignments that k_pair_mask's list path resolved (pair_bitmask = 1; br_ctx_direct_diag)
+#define PM_SLOT_WORD 2
 void launch_name_seed(hipStream_t st, const DirectArgs &D);
-void launch_pair_mask(hipStream_t st, const DirectArgs &D, int wide_blocks);
+void launch_pair_mask(hipStream_t st, const DirectArgs &D, int wide_blocks, bool bitmask);   // bitmask: br_ctx_set_param "pair_bitmask"
 void launch_big_collect(hipStream_t st, const ProjectArgs &A, const DirectArgs &D, int n_blocks);
 void launch_pair_big(hipStream_t st, const DirectArgs &D, int n_blocks);
 void launch_scan5(hipStream_t st, const DirectArgs &D, uint64_t *tile_sums, uint64_t *total_out5);

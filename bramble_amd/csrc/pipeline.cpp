@@ -471,7 +471,7 @@ static int run_device_small(br_ctx *c, const DevCfg &dc, const br_device_batch *
 // switched off).  segment -> count -> [k_pair_mask || k_big<0> + k_pair_big] -> k_scan5 (one host wait: sizes) ->
 // k_expand_rows -> k_emit_rows (|| k_big<1>): the packed rows are written once, by the lane that computes the match; the
 // match table, the per-record r_rec, k_pair<true> and k_rows do not exist on this path.  On the side streams: the name
-// seeds of the primary tie-break (beside segment + count), the big alignments' pairing (beside k_pair_mask), k_group_desc
+// seeds of the primary tie-break (beside k_pair_mask), the big alignments' pairing (beside k_pair_mask), k_group_desc
 // (beside the scan), k_big<1> (beside the emit kernels).
 static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch *b, hipStream_t st, br_device_rows *out, Prof &pf,
                              bool keep_events) {
@@ -532,7 +532,7 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
   uint64_t kept = 0, arena = 0, n_simple = 0, n_rows = 0, n_raw = 0;
   bool expanded_ahead = false;
   // second side stream: the name seeds need nothing but the names, and their 156 dependent multiplies per read name are pure ALU work:
-  // beside k_pair_mask, which waits on LDS and memory most of the time
+  // beside k_pair_mask, which waits on memory or for its turn to issue most of the time
   if (have_names) {
     RC(seeds.fork());
     RC(pf.begin(BR_K_NAME_SEED, ax2));
@@ -552,7 +552,7 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
     RC(pf.end());
     RC(pair_big.done());
     RC(pf.begin(BR_K_PAIR_MASK));
-    launch_pair_mask(st, D, c->n_cu * 2);
+    launch_pair_mask(st, D, c->n_cu * 2, c->pair_bitmask);
     RC(pf.end());
     RC(pair_big.join());
     // NH / HI / primary per read name on the side stream beside the scan
@@ -971,6 +971,9 @@ extern "C" int br_ctx_direct_diag(br_ctx *c, uint64_t out[8], uint8_t *pflags) {
   if (pflags && D.n_aln > 0) HIPCHK(hipMemcpy(pflags, D.pflag, (size_t)D.n_aln, hipMemcpyDeviceToHost));
   memset(out, 0, 8 * sizeof(uint64_t));
   out[0] = nb[0]; out[1] = (uint64_t)c->d_side_attempts; out[2] = used; out[3] = D.side_cap; out[4] = nb[2];
+  uint64_t slots[GD_COUNTER_WORDS];
+  HIPCHK(hipMemcpy(slots, D.counters, sizeof(slots), hipMemcpyDeviceToHost));
+  for (int k = 0; k < GD_SLOTS; k++) out[6] += slots[GD_SLOT0 + k * GD_SLOT_STRIDE + PM_SLOT_WORD];
   if (D.n_aln > 0) {   // work-list entries of the light two-exon class: kept matches of simple-class alignments with two read exons
     const size_t n = (size_t)D.n_aln;
     std::vector<uint32_t> ff(n), nk(n);

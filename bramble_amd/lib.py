@@ -628,11 +628,12 @@ class Context:
     def direct_diag(self, n_aln=None):
         """What the last call (a direct-rows call) left on the device: {"n_big": big_list length, "side_attempts",
         "side_used": arena entries the last attempt asked for, "side_cap": its capacity, "pm_n": windows sent to
-        k_pair_mask_wide, "light": work-list entries of the light two-exon class}, plus "pflags" (uint8 [n_aln]: PF_PAIRED 1 | PF_SAME 2 | PF_MATE 4 | PF_BIG 8) when n_aln is given."""
+        k_pair_mask_wide, "light": work-list entries of the light two-exon class, "pm_list": PAIR alignments k_pair_mask resolved by
+        tid lists, not by 64-bit tid masks (counted with "pair_bitmask" 1)}, plus "pflags" (uint8 [n_aln]: PF_PAIRED 1 | PF_SAME 2 | PF_MATE 4 | PF_BIG 8) when n_aln is given."""
         out = (C.c_uint64 * 8)()
         pf = np.zeros(n_aln, dtype=np.uint8) if n_aln is not None else None
         check(lib().br_ctx_direct_diag(self.h, out, pf.ctypes.data if pf is not None and n_aln else None), "br_ctx_direct_diag")
-        d = dict(zip(("n_big", "side_attempts", "side_used", "side_cap", "pm_n", "light"), [int(v) for v in out[:6]]))
+        d = dict(zip(("n_big", "side_attempts", "side_used", "side_cap", "pm_n", "light", "pm_list"), [int(v) for v in out[:7]]))
         if pf is not None:
             d["pflags"] = pf
         return d

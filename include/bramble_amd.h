@@ -1006,7 +1006,8 @@ const char *br_bgzf_codec(void); /* "libdeflate" (bound at run time when present
 int br_ctx_set_profiling(br_ctx *, int enabled);
 /* Launch tuning: "group_lanes" (8|16|32|64 lanes cooperating on one alignment),
  * "blocks_per_cu" (grid size of the grid-stride projection kernels), "bam_lanes" (0, the default: a wave per 32
- * re-encoded records, their byte regions as 16-byte copy tasks; 4..64: that many lanes per record), "deflate_dynamic" (1: per-block Huffman codes, 0: the fixed code).
+ * re-encoded records, their byte regions as 16-byte copy tasks; 4..64: that many lanes per record), "deflate_dynamic" (1: per-block Huffman codes, 0: the fixed code),
+ * "pair_bitmask" (1, the default: direct rows intersect two mates' transcript sets as 64-bit masks where their ids span at most 64; 0: as lists always. Same rows.).
  * Short-read presets run the count pass of large batches as a main kernel without the exon walk plus a second one for the
  * alignments that need it, and launch the emit work list per class; small batches and the similarity-filter presets use
  * one kernel for each. */
@@ -1029,7 +1030,9 @@ int br_ctx_last_counters(br_ctx *, uint64_t out[8]);
  * out[2] = arena entries the last attempt asked for, out[3] = arena capacity of that attempt (entries), out[4] = windows
  * that k_pair_mask handed to k_pair_mask_wide, out[5] = work-list entries of the light two-exon class (kept matches of
  * "M N M" alignments whose every survivor meets the annotated junction exactly, emitted by the simple-class kernel; those
- * of alignments with more than 64 candidate rows or their mates are not counted), out[6..7] = 0.  pflags (NULL, or n_aln bytes): the pairing flags per
+ * of alignments with more than 64 candidate rows or their mates are not counted), out[6] = PAIR alignments that k_pair_mask / k_pair_mask_wide resolved by their tid lists, not by 64-bit
+ * tid masks: the partner lies outside the window of 62 alignments (+ a neighbour on either side), or the two mates' survivor
+ * tids span more than 64 (max - min > 63); counted only with "pair_bitmask" 1, out[7] = 0.  pflags (NULL, or n_aln bytes): the pairing flags per
  * alignment (1 paired, 2 a transcript in common with the mate, 4 the mate of a pair led by the other record, 8 more than
  * 64 candidate rows).  The test hook br_ctx_set_param("side_cap", v >= 64) sets the arena's first capacity; a call that
  * outgrows it grows the arena to what it asked for and repeats once. */
