@@ -40,4 +40,48 @@ void launch_cov_count(hipStream_t st, const uint32_t *depth, int64_t n, const ui
 // the run's last base the other two
 void launch_cov_runs(hipStream_t st, const uint32_t *depth, int64_t n, const uint64_t *off, int64_t n_tx, const uint64_t *tile_pre, uint4 *runs);
 
+// ---- the weighted modes ("weight" = 1, 2; definitions: bramble_amd.h, br_coverage).  A depth word is uint64, one unit is 2^32 ----
+// more words of the counters: rows with nh == 0 (weight nh), rows whose name the offsets do not give (weight em), entries kept
+// by all adds so far, entries of the add that runs; and what the apply met: a name past the count, a class past C or none at all,
+// a transcript that is not in the class, an entry that leaves the bases
+enum { CV_BAD_NH = 5, CV_BAD_NAMES = 6, CV_KEPT = 7, CV_ADD_ENTRIES = 8, CV_BAD_NAME = 9, CV_BAD_CLASS = 10, CV_BAD_LABEL = 11, CV_BAD_ENTRY = 12,
+       CV_WORDS_W = 16 };
+// A kept entry (weight em), 16 bytes: x | y << 32 = the absolute first base (below 2^40) with COV_KEEP_FIRST set on the first entry
+// of its row, z = the length, w = the add-order name index.  A counted row without a clamped, non-empty interval leaves one entry of
+// length 0 whose x is its transcript id: its weight still counts in weight_sum
+constexpr uint64_t COV_KEEP_FIRST = 1ull << 63;
+constexpr uint64_t COV_KEEP_MAX_BASES = 1ull << 40;
+enum { COV_ADD_NH = 1, COV_ADD_COUNT = 2, COV_ADD_KEEP = 3 };
+struct CovAddWArgs {
+  CovAddArgs A;                      // (A.diff is not used; A.counters has CV_WORDS_W words)
+  unsigned long long *diff;          // B + 1 words of 64 bits
+  unsigned long long *weight_sum;    // per transcript (COV_ADD_NH)
+  // COV_ADD_COUNT / COV_ADD_KEEP: entries per row of the add, at [r - r_first]; the count pass writes them and leaves their sum
+  // in counters[CV_ADD_ENTRIES], the keep pass places a wave's entries by one atomic on counters[CV_KEPT]
+  uint32_t *row_entries;
+  uint4 *arena; uint64_t arena_cap;
+  // the names of the add (as QAddArgs holds them): row r belongs to alignment a with row_off[a] <= r < row_off[a + 1], a to name g
+  // with group_off[g] <= a < group_off[g + 1]; its add-order index is name_base + g
+  const uint64_t *row_off; int64_t ro_bias; const uint32_t *group_off; int64_t n_groups; uint64_t name_base;
+};
+void launch_cov_add_w(hipStream_t st, const CovAddWArgs &W, int mode);
+// the kept entries [0, n) applied to diff with the quantifier's posteriors; every index taken from a table is checked first
+struct CovApplyArgs {
+  const uint4 *arena; uint64_t n;
+  const uint64_t *off; int64_t n_tx; uint64_t n_bases;
+  const uint32_t *name_cls; uint64_t n_names;
+  const uint64_t *label_off; const uint32_t *labels; uint64_t n_cls, n_lab;
+  const double *post;
+  unsigned long long *diff, *weight_sum, *counters;
+};
+void launch_cov_apply(hipStream_t st, const CovApplyArgs &P);
+// launch_cov_scan / summary / count / runs over 64-bit words, modulo 2^64.  The summary: the sums of the high and of the low words
+// of the depth.  A run is 24 bytes: (transcript, start, end, 0) in run4[k] and the depth in run_depth[k]
+void launch_cov_scan64(hipStream_t st, uint64_t *depth, int64_t n, uint64_t *tile_sum, uint64_t *scan_tmp);
+void launch_cov_summary64(hipStream_t st, const uint64_t *depth, const uint64_t *off, int64_t n_tx, uint64_t *aligned_hi, uint64_t *aligned_lo,
+                          uint64_t *covered, uint64_t *max_depth);
+void launch_cov_count64(hipStream_t st, const uint64_t *depth, int64_t n, const uint64_t *off, int64_t n_tx, uint64_t *tile_cnt);
+void launch_cov_runs64(hipStream_t st, const uint64_t *depth, int64_t n, const uint64_t *off, int64_t n_tx, const uint64_t *tile_pre, uint4 *run4,
+                       uint64_t *run_depth);
+
 }  // namespace br

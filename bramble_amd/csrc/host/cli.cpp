@@ -48,7 +48,8 @@ void usage(FILE *f) {
           "                [--quant-eff-length [--quant-fld <fld.tsv>]]\n"
           "                [--quant-bootstraps B [--quant-seed S] [--quant-boot-out <bootstraps.tsv>]]\n"
           "                [--quant-genes <genes.tsv> [--quant-gene-classes <gene_classes.txt>] [--quant-gene-map <tx2gene.tsv>]]]\n"
-          "               [--coverage <cov.bedgraph>] [--coverage-summary <cov.tsv>] [--coverage-primary]\n\n"
+          "               [--coverage <cov.bedgraph>] [--coverage-summary <cov.tsv>] [--coverage-primary]\n"
+          "               [--coverage-weight unit|nh|em]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -96,7 +97,12 @@ void usage(FILE *f) {
           "only, as bedtools genomecov -bg -split lists it).  M = X cover, D N do not; secondary records and both mates count, a base\n"
           "both mates cover twice.  --coverage-summary FILE: one line per @SQ transcript: Name, Length, Records, AlignedBases,\n"
           "CoveredBases, MaxDepth, MeanDepth, Breadth.  Either switch alone turns the feature on; --coverage-primary counts primary\n"
-          "records only.  One more line in front of the final report: [bramble] coverage: N records, A aligned bases on C of B bases in R runs ...\n");
+          "records only.  One more line in front of the final report: [bramble] coverage: N records, A aligned bases on C of B bases in R runs ...\n"
+          "--coverage-weight unit|nh|em (default unit): what a record adds to the depth.  nh: 1 / NH of the record; em: the posterior\n"
+          "of (read name, transcript) under the abundances --quant estimates (it needs --quant) -- the expected depth.  The depth is\n"
+          "fixed point, 32 fractional bits: the bedGraph's depth is printed with %%.10g, and the summary has the columns Name, Length,\n"
+          "Records, WeightedRecords, AlignedBases, CoveredBases, MaxDepth, MeanDepth, Breadth.  The report line becomes\n"
+          "[bramble] coverage (weight nh|em): ...\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -105,6 +111,7 @@ int parse_args(int argc, char **argv, Options &o) {
   memset(&o.cfg, 0, sizeof(o.cfg));
   o.cfg.junc_miss_discount = 1.0;
   bool codec = false, host_codec = false;   // a BGZF codec option was given; one that asks for the host codec
+  bool coverage_weight_given = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "%s: missing value\n", argv[i]); return nullptr; } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -172,6 +179,13 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (a == "--coverage") { const char *v = value(); if (!v) return -1; o.coverage = v; }
     else if (a == "--coverage-summary") { const char *v = value(); if (!v) return -1; o.coverage_summary = v; }
     else if (a == "--coverage-primary") o.coverage_primary = true;
+    else if (a == "--coverage-weight") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "unit") o.coverage_weight = 0; else if (w == "nh") o.coverage_weight = 1; else if (w == "em") o.coverage_weight = 2;
+      else { fprintf(stderr, "--coverage-weight: unknown weight %s (unit, nh or em)\n", v); return -1; }
+      coverage_weight_given = true;
+    }
     else if (a == "--device") { const char *v = value(); if (!v) return -1; o.devices.assign(1, atoi(v)); }
     else if (a == "--devices") {
       const char *v = value(); if (!v) return -1;
@@ -201,6 +215,8 @@ int parse_args(int argc, char **argv, Options &o) {
   if (o.quant_eff_length && o.quant_length_norm == 0) { fprintf(stderr, "--quant-eff-length is a length normalisation: not with --quant-no-length-norm\n"); return -1; }
   if (o.quant_eff_length && (o.cfg.lr || o.cfg.lr_hq) && o.quant_length_norm != 1) { fprintf(stderr, "--quant-eff-length under --lr / --lr-hq needs --quant-length-norm: long reads are not length-normalised by default\n"); return -1; }
   if (o.coverage_primary && o.coverage.empty() && o.coverage_summary.empty()) { fprintf(stderr, "--coverage-primary needs --coverage or --coverage-summary\n"); return -1; }
+  if (coverage_weight_given && o.coverage.empty() && o.coverage_summary.empty()) { fprintf(stderr, "--coverage-weight needs --coverage or --coverage-summary\n"); return -1; }
+  if (o.coverage_weight == 2 && o.quant.empty()) { fprintf(stderr, "--coverage-weight em needs --quant: the weights are the EM's posteriors\n"); return -1; }
   if ((!o.coverage.empty() || !o.coverage_summary.empty()) && o.devices.size() > 1) { fprintf(stderr, "--coverage works on one device: give --device N, not a --devices list\n"); return -1; }
   if (o.write_index && !o.sort) { fprintf(stderr, "--write-index needs --sort: a BAI index describes a coordinate-sorted file\n"); return -1; }
   if (o.write_index && o.sam_out) { fprintf(stderr, "--write-index applies to BAM output, not to --output-fmt sam\n"); return -1; }

@@ -29,6 +29,10 @@ class Consumer {
   // bundle goes to the writer; after finish() the writer draws them from next_piece (no rows: that was all)
   virtual bool keeps_records() const { return false; }
   virtual int next_piece(uint64_t, br_device_bam *piece) { memset(piece, 0, sizeof(*piece)); return BR_OK; }
+  // --quant only: its quantifier, for a consumer that reads it after the quantifier's finish() (the EM has run by then)
+  virtual br_quant *quantifier() { return nullptr; }
+  // once every consumer is open: one that needs another finds it among them; false: it is not there
+  virtual bool meet(const std::vector<std::unique_ptr<Consumer>> &) { return true; }
   const char *const name, *const failure;
  protected:
   const RunEnv &env;
@@ -46,7 +50,9 @@ std::unique_ptr<Consumer> open_as(const RunEnv &env, std::string &err) {
   return c;
 }
 
-// the consumers the options ask for, in the order sort, quant, coverage; false: `err` says which could not be made
+// the consumers the options ask for, in the order sort, quant, coverage -- the order of their finish() as well: coverage under
+// --coverage-weight em reads the quantifier (Consumer::quantifier) whose EM quant's finish() has run; false: `err` says which
+// could not be made
 inline bool open_consumers(const RunEnv &env, std::vector<std::unique_ptr<Consumer>> &out, std::string &err) {
   const Options &o = env.o;
   const std::pair<bool, decltype(&open_sort)> wanted[] = {{o.sort, open_sort}, {!o.quant.empty(), open_quant}, {!o.coverage.empty() || !o.coverage_summary.empty(), open_coverage}};
@@ -55,6 +61,7 @@ inline bool open_consumers(const RunEnv &env, std::vector<std::unique_ptr<Consum
     out.push_back(open(env, err));
     if (!out.back()) return false;
   }
+  for (auto &c : out) if (!c->meet(out)) { err = std::string(c->name) + ": a consumer it reads is missing"; return false; }
   return true;
 }
 

@@ -1,6 +1,8 @@
 // --coverage / --coverage-summary (cli_output.h): every bundle's rows go to a br_coverage (br_coverage_add_last); after the last
 // bundle: depth, summary and runs on the device; the per-transcript table comes home then, the runs in pages while the bedGraph
-// is written.
+// is written.  --coverage-weight nh|em: the object's "weight" 1 / 2, the 64-bit getters and the weighted files; em keeps every bundle's
+// rows by name and finishes with the --quant consumer's quantifier, which it met through Consumer::quantifier when the consumers
+// were opened (quant's finish() runs first: open_consumers' order).
 #include "cli_output.h"
 
 namespace brcli {
@@ -13,32 +15,61 @@ class CoverageOut : public Consumer {
   int open() {
     int rc = br_coverage_new(env.device, (int64_t)env.tx.len.size(), env.tx.len.data(), &c);
     if (!rc && env.o.coverage_primary) rc = br_coverage_set_param(c, "primary_only", 1);
+    if (!rc && weight) rc = br_coverage_set_param(c, "weight", weight);
     return rc;
+  }
+  bool meet(const std::vector<std::unique_ptr<Consumer>> &all) override {
+    if (weight != 2) return true;
+    for (auto &other : all) if (br_quant *q = other->quantifier()) quant = q;
+    return quant != nullptr;
   }
   int add(br_ctx *ctx) override { return br_coverage_add_last(c, ctx); }
   int finish() override {
     const size_t nt = env.tx.len.size();
-    int rc = br_coverage_finish(c, &n_runs);
+    int rc = weight == 2 ? br_coverage_finish_em(c, quant, &n_runs) : br_coverage_finish(c, &n_runs);
     if (!rc) {
       records.resize(nt + 1); aligned.resize(nt + 1); covered.resize(nt + 1); max_depth.resize(nt + 1);
-      rc = br_coverage_summary(c, records.data(), aligned.data(), covered.data(), max_depth.data());
+      if (weight) {
+        weight_sum.resize(nt + 1); aligned_lo.resize(nt + 1); max_depth64.resize(nt + 1);
+        rc = br_coverage_summary64(c, records.data(), weight_sum.data(), aligned.data(), aligned_lo.data(), covered.data(), max_depth64.data());
+      } else rc = br_coverage_summary(c, records.data(), aligned.data(), covered.data(), max_depth.data());
     }
     (void)br_coverage_stats(c, nullptr, nullptr, nullptr, nullptr, nullptr, &t_add, &t_finish);
     return rc;
   }
   bool write_files(brio::BgzfWriter &, const std::vector<br_bgzf_span> &) override {
     int rc = 0;
-    if (FILE *f = bedgraph.open())
-      rc = write_bedgraph(f, env.tx, n_runs, 1 << 20, [this](int64_t first, int64_t n, uint32_t *tid, uint32_t *start, uint32_t *end, uint32_t *depth) {
-        return br_coverage_runs(c, first, n, tid, start, end, depth);
-      });
+    if (FILE *f = bedgraph.open()) {
+      if (weight)
+        rc = write_bedgraph_weighted(f, env.tx, n_runs, 1 << 20, [this](int64_t first, int64_t n, uint32_t *tid, uint32_t *start, uint32_t *end, uint64_t *depth) {
+          return br_coverage_runs64(c, first, n, tid, start, end, depth);
+        });
+      else
+        rc = write_bedgraph(f, env.tx, n_runs, 1 << 20, [this](int64_t first, int64_t n, uint32_t *tid, uint32_t *start, uint32_t *end, uint32_t *depth) {
+          return br_coverage_runs(c, first, n, tid, start, end, depth);
+        });
+    }
     if (rc) fprintf(stderr, "error: coverage on device %d: %s\n", env.device, br_strerror(rc));
     if (!bedgraph.close() || rc) return false;
-    if (FILE *f = summary.open()) write_coverage_summary(f, env.tx, records, aligned, covered, max_depth);
+    if (FILE *f = summary.open()) {
+      if (weight) write_coverage_summary_weighted(f, env.tx, records, weight_sum, aligned, aligned_lo, covered, max_depth64);
+      else write_coverage_summary(f, env.tx, records, aligned, covered, max_depth);
+    }
     return summary.close();
   }
   bool settle(bool failed) override { return settle_all({&bedgraph, &summary}, failed); }
   void report() const override {
+    if (weight) {   // the aligned bases are fixed point here: the whole units, then the 2^-32 fractions
+      uint64_t n = 0, cv = 0, b = 0;
+      double a = 0, ws = 0;
+      for (size_t t = 0; t < env.tx.len.size(); t++) {
+        n += records[t]; cv += covered[t]; b += (uint64_t)std::max<int64_t>(env.tx.len[t], 0);
+        a += (double)aligned[t] + (double)aligned_lo[t] / 4294967296.0; ws += (double)weight_sum[t] / 4294967296.0;
+      }
+      printf("[bramble] coverage (weight %s): %llu records of weight %.2f, %.2f aligned bases on %llu of %llu bases in %lld runs (add %.2fs, finish %.2fs)\n",
+             weight == 1 ? "nh" : "em", (unsigned long long)n, ws, a, (unsigned long long)cv, (unsigned long long)b, (long long)n_runs, t_add, t_finish);
+      return;
+    }
     uint64_t n = 0, a = 0, cv = 0, b = 0;
     for (size_t t = 0; t < env.tx.len.size(); t++) { n += records[t]; a += aligned[t]; cv += covered[t]; b += (uint64_t)std::max<int64_t>(env.tx.len[t], 0); }
     printf("[bramble] coverage: %llu records, %llu aligned bases on %llu of %llu bases in %lld runs (add %.2fs, finish %.2fs)\n", (unsigned long long)n,
@@ -46,11 +77,14 @@ class CoverageOut : public Consumer {
   }
  private:
   br_coverage *c = nullptr;
+  const int weight = env.o.coverage_weight;   // br_coverage's "weight"
+  br_quant *quant = nullptr;                  // weight em: the --quant consumer's, which outlives neither of the two
   SideFile bedgraph, summary;
   int64_t n_runs = 0;
   double t_add = 0, t_finish = 0;
   std::vector<uint64_t> records, aligned, covered;
   std::vector<uint32_t> max_depth;
+  std::vector<uint64_t> weight_sum, aligned_lo, max_depth64;   // the weighted modes (aligned holds aligned_hi there)
 };
 
 }  // namespace

@@ -142,4 +142,28 @@ void write_coverage_summary(FILE *f, const TxTable &tx, const std::vector<uint64
                                (double)covered[t] / (double)tx.len[t]);
 }
 
+int write_bedgraph_weighted(FILE *f, const TxTable &tx, int64_t n_runs, int64_t page, const RunPage64 &fetch) {
+  std::vector<uint32_t> tid((size_t)std::min(n_runs, page) + 1), start(tid.size()), end(tid.size());
+  std::vector<uint64_t> depth(tid.size());
+  for (int64_t first = 0; first < n_runs; first += page) {
+    const int64_t n = std::min(page, n_runs - first);
+    if (const int rc = fetch(first, n, tid.data(), start.data(), end.data(), depth.data())) return rc;
+    for (size_t k = 0; k < (size_t)n; k++) fprintf(f, "%s\t%u\t%u\t%.10g\n", tx.name[tid[k]], start[k], end[k], (double)depth[k] / 4294967296.0);
+  }
+  return 0;
+}
+
+void write_coverage_summary_weighted(FILE *f, const TxTable &tx, const std::vector<uint64_t> &records, const std::vector<uint64_t> &weight_sum,
+                                     const std::vector<uint64_t> &aligned_hi, const std::vector<uint64_t> &aligned_lo,
+                                     const std::vector<uint64_t> &covered, const std::vector<uint64_t> &max_depth) {
+  fprintf(f, "Name\tLength\tRecords\tWeightedRecords\tAlignedBases\tCoveredBases\tMaxDepth\tMeanDepth\tBreadth\n");
+  for (size_t t = 0; t < tx.len.size(); t++) {
+    if (tx.len[t] <= 0) continue;
+    const double aligned = (double)aligned_hi[t] + (double)aligned_lo[t] / 4294967296.0;
+    fprintf(f, "%s\t%lld\t%llu\t%.6f\t%.6f\t%llu\t%.6f\t%.6f\t%.6f\n", tx.name[t], (long long)tx.len[t], (unsigned long long)records[t],
+            (double)weight_sum[t] / 4294967296.0, aligned, (unsigned long long)covered[t], (double)max_depth[t] / 4294967296.0,
+            aligned / (double)tx.len[t], (double)covered[t] / (double)tx.len[t]);
+  }
+}
+
 }  // namespace brcli

@@ -58,5 +58,13 @@ using RunPage = std::function<int(int64_t first, int64_t n, uint32_t *tid, uint3
 int write_bedgraph(FILE *f, const TxTable &tx, int64_t n_runs, int64_t page, const RunPage &fetch);   // the first error of fetch
 void write_coverage_summary(FILE *f, const TxTable &tx, const std::vector<uint64_t> &records, const std::vector<uint64_t> &aligned,
                             const std::vector<uint64_t> &covered, const std::vector<uint32_t> &max_depth);
+// --coverage-weight nh|em: the depth is fixed point, one unit 2^32, and printed as depth / 2^32 with %.10g
+using RunPage64 = std::function<int(int64_t first, int64_t n, uint32_t *tid, uint32_t *start, uint32_t *end, uint64_t *depth)>;
+int write_bedgraph_weighted(FILE *f, const TxTable &tx, int64_t n_runs, int64_t page, const RunPage64 &fetch);
+// Name Length Records WeightedRecords AlignedBases CoveredBases MaxDepth MeanDepth Breadth; the fixed-point columns (weight_sum,
+// aligned = aligned_hi + aligned_lo / 2^32, max_depth) and MeanDepth with %.6f
+void write_coverage_summary_weighted(FILE *f, const TxTable &tx, const std::vector<uint64_t> &records, const std::vector<uint64_t> &weight_sum,
+                                     const std::vector<uint64_t> &aligned_hi, const std::vector<uint64_t> &aligned_lo,
+                                     const std::vector<uint64_t> &covered, const std::vector<uint64_t> &max_depth);
 
 }  // namespace brcli

@@ -20,9 +20,11 @@ class QuantOut : public Consumer {
     if (!rc && o.quant_eff_length) rc = br_quant_set_param(q, "eff_len", 1);
     if (!rc && o.quant_bootstraps) rc = br_quant_set_param(q, "bootstraps", o.quant_bootstraps);
     if (!rc && o.quant_bootstraps) rc = br_quant_set_param(q, "boot_seed", (int64_t)o.quant_seed);
+    if (!rc && o.coverage_weight == 2) rc = br_quant_set_param(q, "keep_names", 1);   // (the coverage consumer joins rows to classes by name)
     return rc;
   }
   int add(br_ctx *ctx) override { return br_quant_add_last(q, ctx); }
+  br_quant *quantifier() override { return q; }
   int finish() override {
     const size_t nt = env.tx.len.size();
     int rc = br_quant_finish(q, &n_names, &n_classes);

@@ -32,6 +32,9 @@
 //            gene by integer atomics.  The transcripts by gene come from a counting sort on the host; a lane per gene sums
 //            theta / tpm / lengths over them in ascending order, a lane per (replicate, gene) the B x T result into B x G,
 //            which the transcripts' summary kernel reduces
+//   names    ("keep_names") quant_classes, while its sorted items and scanned heads are still there, also scatters every item's final
+//            class index to name_cls: sorted item -> head rank -> rank after the sort by first name -> name_cls[item]; after the
+//            EM a lane per class makes the posteriors of its label entries (k_q_post), its sum running over the labels one by one
 //   One routine, quant_classes, makes the classes of both levels from items: an item owns a list, has a first name and stands for
 //   a number of names (its weight).  For finish an item is a read name with labels -- its first name is itself, its weight 1, and
 //   neither table exists; for the genes it is a transcript class with its gene list, the class's first name and the class's count
@@ -48,6 +51,9 @@
 //   afterwards     24 C (first name, count, label_off) + 8 L (labels, the transposed table's classes) + 24 T (the table's offsets,
 //                  unique, ambiguous) + 4 bytes per listed class / transcript
 //   em             adds 40 T (theta and theta w twice, w) + 8 C (q)
+//   "keep_names"   holds 4 (N + 1) from finish on (name_cls: per name its class), and 4 (C + 1) more while the classes are made
+//                  (the inverse of the second sort)
+//   posteriors     (br_quant_posteriors, br_coverage_finish_em) hold 8 (L + 1) from the first call after an EM on; a later EM drops them
 //   "eff_len"      adds 16 (fld_max + 1 + 3) from the first add on (the histogram and its three counters, the run's and the add's
 //                  own), 8 per row and 4 per pool word of a host add's CIGAR copies while it runs, 16 (fld_max + 1) for the
 //                  prefixes during finish, and 8 T for eff from finish on (w, 8 T of the EM's 40, is held from finish on as well)
@@ -74,6 +80,7 @@
 #include "collate_kernels.h"
 #include "ctx.h"
 #include "quant_kernels.h"
+#include "quant_view.h"
 #include "scan_kernels.h"
 
 using namespace br;
@@ -81,7 +88,7 @@ using namespace br;
 struct br_quant : Accum {
   int64_t n_tx = 0;
   std::vector<int64_t> lens;   // empty: no lengths were given
-  int hash_bits = 64, length_norm = 1, eff_len = 0;
+  int hash_bits = 64, length_norm = 1, eff_len = 0, keep_names = 0;
   int64_t fld_max = 1000;      // (salmon's fragLenDistMax)
   int64_t max_iters = 10000;
   double tolerance = 1e-2;
@@ -99,6 +106,8 @@ struct br_quant : Accum {
     uint64_t collisions = 0;
   } cls;                                                 // the transcript classes, after finish
   ColBuf t_cls, t_off, uniq, ambig, big_cls, big_tx;     // after finish
+  ColBuf name_cls;                                       // "keep_names": per name its class, from finish on
+  ColBuf post;                                           // the posteriors, per label entry, once they were asked for after the EM
   ColBuf theta[2], x[2], w, qv;                          // em
   ColBuf fld_stage, fld_total, eff;                      // "eff_len": fld_max + 1 bins + Q_FLD_SIDE counters each (an add's, the run's); per transcript
   size_t fld_words() const { return (size_t)fld_max + 1 + Q_FLD_SIDE; }
@@ -168,6 +177,7 @@ extern "C" int br_quant_set_param(br_quant *c, const char *name, int64_t value) 
   // counts fragments makes them: before the first add only, a refused one included
   const bool fixed = c->n > 0 || c->fld_total.p != nullptr;
   if (!strcmp(name, "eff_len")) { if ((value != 0 && value != 1) || fixed) return BR_ERR_INVALID_ARG; c->eff_len = (int)value; return BR_OK; }
+  if (!strcmp(name, "keep_names")) { if ((value != 0 && value != 1) || fixed) return BR_ERR_INVALID_ARG; c->keep_names = (int)value; return BR_OK; }
   if (!strcmp(name, "fld_max")) { if (value < 1 || value > 65535 || fixed) return BR_ERR_INVALID_ARG; c->fld_max = value; return BR_OK; }
   if (!strcmp(name, "max_iters")) { if (value < 1) return BR_ERR_INVALID_ARG; c->max_iters = value; return BR_OK; }
   if (!strcmp(name, "tolerance_ppm")) { if (value < 0) return BR_ERR_INVALID_ARG; c->tolerance = (double)value * 1e-6; return BR_OK; }
@@ -316,13 +326,15 @@ static int quant_sort(br_quant *c, ColBuf key[2], ColBuf idx[2], int64_t n, int 
 // the lists of neighbours, and a run of equal hashes that holds different lists is put in order by (k, list, item) and the heads
 // found again: exact at any hash_bits.  out gets the classes in first-name order -- first, cnt (the sum of the items' weights),
 // loff (scanned, loff[C] = L) -- with n_cls = C, n_lab = L and the collisions; rep != NULL gets per class an item whose list is
-// the class's.  Everything else, key and idx included, is dropped when it returns: the caller makes its label tables after that
+// the class's; name_cls != NULL gets, at every item's index, the class the item fell into (the caller has filled it with 0xffffffff:
+// what is no item keeps that).  Everything else, key and idx included, is dropped when it returns: the caller makes its label
+// tables after that
 static int quant_classes(br_quant *c, const uint32_t *lab, const uint64_t *off, const uint32_t *k, const uint64_t *first, const uint64_t *weight,
-                         ColBuf key[2], ColBuf idx[2], int64_t n, br_quant::Classes &out, ColBuf *rep) {
+                         ColBuf key[2], ColBuf idx[2], int64_t n, br_quant::Classes &out, ColBuf *rep, uint32_t *name_cls = nullptr) {
   hipStream_t st = c->st;
   uint64_t *small = c->small.as<uint64_t>();
-  ColBuf head, mark, pre, gbeg, key2[2], val2[2];
-  DropGuard sort_bufs{c, {&key[0], &key[1], &idx[0], &idx[1], &head, &mark, &pre, &gbeg, &key2[0], &key2[1], &val2[0], &val2[1]}};
+  ColBuf head, mark, pre, gbeg, key2[2], val2[2], inv;
+  DropGuard sort_bufs{c, {&key[0], &key[1], &idx[0], &idx[1], &head, &mark, &pre, &gbeg, &key2[0], &key2[1], &val2[0], &val2[1], &inv}};
   int cur = 0;
   RC(quant_sort(c, key, idx, n, &cur));
   // class heads; runs of equal hashes with different lists are put in order and the heads found again
@@ -369,6 +381,10 @@ static int quant_classes(br_quant *c, const uint32_t *lab, const uint64_t *off, 
   if (rep) RC(c->alloc(*rep, c1 * 4));
   launch_q_class_fill(st, key2[cur2].as<uint64_t>(), val2[cur2].as<uint32_t>(), gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), pre.as<uint64_t>(), k, (int64_t)C,
                       out.first.as<uint64_t>(), out.cnt.as<uint64_t>(), out.loff.as<uint64_t>(), rep ? rep->as<uint32_t>() : nullptr);
+  if (name_cls) {   // sorted item -> head rank -> rank after the second sort -> name_cls[item], while the sort's tables are still here
+    RC(c->alloc(inv, c1 * 4));
+    launch_q_name_cls(st, head.as<uint64_t>(), idx[cur].as<uint32_t>(), n, val2[cur2].as<uint32_t>(), (int64_t)C, inv.as<uint32_t>(), name_cls);
+  }
   RC(quant_tmp(c, (int64_t)C));
   launch_scan(st, out.loff.as<uint64_t>(), (int64_t)C, c->tmp.as<uint64_t>());
   uint64_t L = 0;
@@ -388,6 +404,10 @@ static int quant_finish(br_quant *c) {
   HIPCHK(hipMemsetAsync(c->uniq.p, 0, (size_t)(T + 1) * 8, st)); HIPCHK(hipMemsetAsync(c->ambig.p, 0, (size_t)(T + 1) * 8, st));
   HIPCHK(hipStreamSynchronize(st));
   if (N == 0) return BR_OK;
+  if (c->keep_names) {   // every name starts without a class
+    RC(c->alloc(c->name_cls, (size_t)(N + 1) * 4));
+    HIPCHK(hipMemsetAsync(c->name_cls.p, 0xff, (size_t)(N + 1) * 4, st));
+  }
   // the names with labels
   uint64_t M = 0;
   ColBuf key[2], idx[2];
@@ -414,7 +434,8 @@ static int quant_finish(br_quant *c) {
   // their classes: a name is its own first name and counts once; a class's list is its first name's, so no rep
   const uint32_t *lab = c->lab.as<uint32_t>();
   const uint64_t *noff = c->noff.as<uint64_t>();
-  RC(quant_classes(c, lab, noff, c->nk.as<uint32_t>(), nullptr, nullptr, key, idx, (int64_t)M, c->cls, nullptr));
+  RC(quant_classes(c, lab, noff, c->nk.as<uint32_t>(), nullptr, nullptr, key, idx, (int64_t)M, c->cls, nullptr,
+                   c->keep_names ? c->name_cls.as<uint32_t>() : nullptr));
   const int64_t C = c->cls.n_cls, L = c->cls.n_lab;
   // labels and the transposed table
   ColBuf ecls, tkey[2], tidx[2], d_lens;
@@ -503,6 +524,15 @@ extern "C" int br_quant_classes(br_quant *c, uint64_t *label_off, uint32_t *labe
   return c && c->finished ? quant_copy_classes(c, c->cls, label_off, labels, counts, first_name) : BR_ERR_INVALID_ARG;
 }
 
+extern "C" int br_quant_name_classes(br_quant *c, int64_t first, int64_t n, uint32_t *cls) {
+  if (!c || !c->finished || !c->keep_names || first < 0 || n < 0 || first > c->n || n > c->n - first) return BR_ERR_INVALID_ARG;
+  if (!n || !cls) return BR_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpyAsync(cls, c->name_cls.as<uint32_t>() + first, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return BR_OK;
+}
+
 extern "C" int br_quant_fld(br_quant *c, uint64_t *hist, uint64_t *n_obs, uint64_t *n_no_fragment, uint64_t *n_out_of_range) {
   if (!c) return BR_ERR_INVALID_ARG;
   const size_t n_bins = (size_t)c->fld_max + 1;
@@ -558,6 +588,8 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
   hipStream_t st = c->st;
   const int64_t T = c->n_tx, C = c->cls.n_cls;
   const size_t t1 = (size_t)T + 1;
+  HIPCHK(hipStreamSynchronize(st));
+  c->drop(c->post);   // (the posteriors of an earlier EM)
   for (int k = 0; k < 2; k++) { RC(c->alloc(c->theta[k], t1 * 8)); RC(c->alloc(c->x[k], t1 * 8)); }
   RC(quant_put_w(c)); RC(c->alloc(c->qv, (size_t)(C + 1) * 8));
   const std::vector<double> one((size_t)T, 1.0);
@@ -589,6 +621,36 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
   c->em_s = timer.seconds();
   if (n_iters) *n_iters = (int32_t)it;
   if (rel_change) *rel_change = rel;
+  return BR_OK;
+}
+
+// the posteriors on the device, made once per EM: 8 bytes a label
+static int quant_post(br_quant *c) {
+  if (c->post.p) return BR_OK;
+  RC(c->alloc(c->post, (size_t)(c->cls.n_lab + 1) * 8));
+  launch_q_post(c->st, c->cls.loff.as<uint64_t>(), c->cls.labels.as<uint32_t>(), c->cls.n_cls, c->theta[c->cur].as<double>(), c->w.as<double>(),
+                c->post.as<double>());
+  HIPCHK(hipStreamSynchronize(c->st));
+  return BR_OK;
+}
+extern "C" int br_quant_posteriors(br_quant *c, double *post) {
+  if (!c || !c->finished || !c->em_done) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  RC(quant_post(c));
+  if (post && c->cls.n_lab) {
+    HIPCHK(hipMemcpyAsync(post, c->post.p, (size_t)c->cls.n_lab * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+  }
+  return BR_OK;
+}
+// what br_coverage_finish_em reads (quant_view.h); the posteriors are made if they are not there yet
+int br::quant_view(br_quant *c, QuantView *v) {
+  if (!c || !v || !c->finished || !c->em_done || !c->keep_names) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  RC(quant_post(c));
+  v->device = c->device; v->n_names = c->n; v->n_cls = c->cls.n_cls; v->n_lab = c->cls.n_lab;
+  v->name_cls = c->name_cls.as<uint32_t>(); v->label_off = c->cls.loff.as<uint64_t>(); v->labels = c->cls.labels.as<uint32_t>();
+  v->post = c->post.as<double>();
   return BR_OK;
 }
 

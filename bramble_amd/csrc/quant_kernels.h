@@ -67,6 +67,14 @@ void launch_q_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *id
 // every item weighs 1
 void launch_q_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *pre,
                          const uint32_t *nk, int64_t n_cls, uint64_t *first, uint64_t *cnt, uint64_t *label_off, uint32_t *rep);
+// "keep_names": name_cls[idx[j]] = the final index of sorted item j's class.  head: the scanned heads (n + 1 entries), val: the
+// classes' hash-order indices in their final order (the second sort's result), inv: n_cls words of scratch
+void launch_q_name_cls(hipStream_t st, const uint64_t *head, const uint32_t *idx, int64_t n, const uint32_t *val, int64_t n_cls, uint32_t *inv,
+                       uint32_t *name_cls);
+// post[e] = theta_t w_t / d_c for label entry e of class c with transcript t, d_c the sum over the class's labels in ascending
+// order, one after the other (0 where d_c == 0)
+void launch_q_post(hipStream_t st, const uint64_t *label_off, const uint32_t *labels, int64_t n_cls, const double *theta, const double *w,
+                   double *post);
 // one thread per label entry e: labels[e], its class, (transcript, e) for the transposed table; *bad |= 1 for a transcript
 // whose length is <= 0 (lens != NULL)
 void launch_q_labels(hipStream_t st, const uint64_t *label_off, const uint64_t *first, const uint64_t *noff, const uint32_t *lab,

@@ -6,6 +6,8 @@
 //   classes  k_q_flag + scan + k_q_compact: the names with labels; k_q_bits; the collator's radix passes over (hash, name);
 //            k_q_heads compares the label lists of neighbours; k_q_resolve orders a run of equal hashes that holds different
 //            lists by (k, labels, name); k_q_class_key + radix passes: classes by their first name; k_q_class_fill, k_q_labels
+//   names    ("keep_names") k_q_class_inv + k_q_name_cls: every sorted item's class, in the classes' final order, to name_cls[item];
+//            k_q_post, after the EM: a lane per class, the posteriors of its label entries
 //   table    radix passes over (transcript, label entry) + k_q_transpose: per transcript its classes, ascending; k_q_bin;
 //            k_q_counts: unique / ambiguous names per transcript
 //   EM       k_q_em_classes / k_q_em_tx, a lane per item of up to Q_WAVE_ITEMS entries and a wave per larger one
@@ -430,6 +432,31 @@ __global__ void __launch_bounds__(256) k_q_class_fill(const uint64_t *key, const
   const uint32_t s = val[c], r = idx[gbeg[s]];
   first[c] = key[c]; cnt[c] = pre ? pre[gbeg[s + 1]] - pre[gbeg[s]] : gbeg[s + 1] - gbeg[s]; label_off[c] = nk[r];
   if (rep) rep[c] = r;
+}
+// "keep_names": inv[class in hash order] = the class in its final order (val, after the second sort), then a lane per sorted item
+// j -- its class in hash order is the heads up to and including j, less one, and head holds the exclusive scan -- stores
+// name_cls[item] = that class's final index.  The names without labels were never items: they keep the caller's 0xffffffff
+__global__ void __launch_bounds__(256) k_q_class_inv(const uint32_t *val, int64_t n_cls, uint32_t *inv) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c < n_cls) inv[val[c]] = (uint32_t)c;
+}
+__global__ void __launch_bounds__(256) k_q_name_cls(const uint64_t *head, const uint32_t *idx, int64_t n, const uint32_t *inv, int64_t n_cls,
+                                                    uint32_t *name_cls) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const uint64_t s = head[j + 1] - 1;
+  if (s < (uint64_t)n_cls) name_cls[idx[j]] = inv[s];
+}
+// The posteriors (bramble_amd.h, br_quant): a lane per class, its labels one after the other whatever their number, so that the
+// shape of the sum is the definition's; one rounding per operation (the unit is built without contraction)
+__global__ void __launch_bounds__(256) k_q_post(const uint64_t *label_off, const uint32_t *labels, int64_t n_cls, const double *theta,
+                                                const double *w, double *post) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n_cls) return;
+  const uint64_t b = label_off[c], e = label_off[c + 1];
+  double d = 0.0;
+  for (uint64_t i = b; i < e; i++) { const uint32_t t = labels[i]; d += theta[t] * w[t]; }
+  for (uint64_t i = b; i < e; i++) { const uint32_t t = labels[i]; post[i] = d == 0.0 ? 0.0 : (theta[t] * w[t]) / d; }
 }
 __global__ void __launch_bounds__(256) k_q_labels(const uint64_t *label_off, const uint64_t *first, const uint64_t *noff, const uint32_t *lab,
                                                   int64_t n_cls, int64_t n_lab, const int64_t *lens, uint32_t *labels, uint32_t *ecls,
@@ -927,6 +954,16 @@ void launch_q_class_key(hipStream_t st, const uint64_t *gbeg, const uint32_t *id
 void launch_q_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *val, const uint64_t *gbeg, const uint32_t *idx, const uint64_t *pre,
                          const uint32_t *nk, int64_t n_cls, uint64_t *first, uint64_t *cnt, uint64_t *label_off, uint32_t *rep) {
   if (n_cls > 0) hipLaunchKernelGGL(k_q_class_fill, dim3(blocks256(n_cls)), dim3(256), 0, st, key, val, gbeg, idx, pre, nk, n_cls, first, cnt, label_off, rep);
+}
+void launch_q_name_cls(hipStream_t st, const uint64_t *head, const uint32_t *idx, int64_t n, const uint32_t *val, int64_t n_cls, uint32_t *inv,
+                       uint32_t *name_cls) {
+  if (n_cls <= 0 || n <= 0) return;
+  hipLaunchKernelGGL(k_q_class_inv, dim3(blocks256(n_cls)), dim3(256), 0, st, val, n_cls, inv);
+  hipLaunchKernelGGL(k_q_name_cls, dim3(blocks256(n)), dim3(256), 0, st, head, idx, n, (const uint32_t *)inv, n_cls, name_cls);
+}
+void launch_q_post(hipStream_t st, const uint64_t *label_off, const uint32_t *labels, int64_t n_cls, const double *theta, const double *w,
+                   double *post) {
+  if (n_cls > 0) hipLaunchKernelGGL(k_q_post, dim3(blocks256(n_cls)), dim3(256), 0, st, label_off, labels, n_cls, theta, w, post);
 }
 void launch_q_labels(hipStream_t st, const uint64_t *label_off, const uint64_t *first, const uint64_t *noff, const uint32_t *lab,
                      int64_t n_cls, int64_t n_lab, const int64_t *lens, uint32_t *labels, uint32_t *ecls, uint64_t *tkey,

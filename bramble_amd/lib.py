@@ -180,8 +180,10 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_quant_classes", "br_quant_em", "br_quant_result", "br_quant_fld", "br_quant_eff_lengths", "br_quant_stats", "br_quant_free",
            "br_quant_bootstrap", "br_quant_boot_counts", "br_quant_boot_theta", "br_quant_boot_summary", "br_quant_boot_stats",
            "br_quant_genes", "br_quant_gene_classes", "br_quant_gene_result", "br_quant_gene_boot", "br_quant_gene_boot_summary", "br_quant_gene_stats",
+           "br_quant_name_classes", "br_quant_posteriors",
            "br_coverage_new", "br_coverage_set_param", "br_coverage_add_rows", "br_coverage_add_last", "br_coverage_finish", "br_coverage_runs",
            "br_coverage_depth", "br_coverage_summary", "br_coverage_stats", "br_coverage_free",
+           "br_coverage_add_names", "br_coverage_finish_em", "br_coverage_runs64", "br_coverage_depth64", "br_coverage_summary64",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -1214,7 +1216,8 @@ class Quant(_Accumulator):
                 "gene_classes": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                 "gene_result": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                 "gene_boot": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p], "gene_boot_summary": [C.c_void_p, C.c_void_p, C.c_void_p],
-                "gene_stats": [C.c_void_p, _P(C.c_double), _P(C.c_int64), _P(C.c_uint64)]}
+                "gene_stats": [C.c_void_p, _P(C.c_double), _P(C.c_int64), _P(C.c_uint64)],
+                "name_classes": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p], "posteriors": [C.c_void_p, C.c_void_p]}
 
     def __init__(self, n_transcripts, lengths=None, device=0):
         self.n_transcripts = int(n_transcripts)
@@ -1230,7 +1233,7 @@ class Quant(_Accumulator):
             self.set_param("length_norm", 0)
 
     def set_param(self, name, value):
-        """"hash_bits", "length_norm", "max_iters", "eff_len", "fld_max", "bootstraps", "boot_seed" (the bits of an int64: a seed
+        """"hash_bits", "length_norm", "max_iters", "eff_len", "fld_max", "keep_names", "bootstraps", "boot_seed" (the bits of an int64: a seed
         of 2^63 or more is taken modulo 2^64), "boot_chunk" (integers) or "tolerance" (a float)."""
         if name == "tolerance":
             self._call("set_tolerance", float(value))
@@ -1413,6 +1416,24 @@ class Quant(_Accumulator):
         self._call("gene_stats", C.byref(s), C.byref(n), C.byref(co))
         return {"seconds": s.value, "n_gene_labels": int(n.value), "collisions": int(co.value)}
 
+    def name_classes(self, first=0, n=None):
+        """-> uint32 [n]: the class of add-order names first .. first + n - 1, 0xffffffff for a name without rows ("keep_names" = 1,
+        after finish)"""
+        n = self.n_names - first if n is None else n
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        self._call("name_classes", int(first), int(n), out.ctypes.data)
+        return out[:n]
+
+    def posteriors(self, fetch=True):
+        """-> float64 [n_labels]: the posterior of every label entry, parallel to classes()[1] (after em); fetch = False only makes
+        the table on the device"""
+        if not fetch:
+            self._call("posteriors", None)
+            return None
+        out = np.zeros(max(self.stats()["n_labels"], 1), dtype=np.float64)
+        self._call("posteriors", out.ctypes.data)
+        return out[:self.stats()["n_labels"]]
+
     def fld(self):
         """-> dict of hist (uint64 [fld_max + 1]: observed fragment lengths of the read names of one label) and n_obs,
         n_no_fragment, n_out_of_range, of the adds so far"""
@@ -1438,7 +1459,11 @@ class Quant(_Accumulator):
 
 class Coverage(_Accumulator):
     """br_coverage on `device`: the rows of projected batches in, the depth of coverage along every transcript out (runs of equal
-    depth, per-transcript summary, the depth itself).  lengths: one per transcript.  set_param: "primary_only" 0 / 1, before the first add."""
+    depth, per-transcript summary, the depth itself).  lengths: one per transcript.  set_param: "primary_only" 0 / 1 and "weight"
+    0 / 1 / 2 (unit, 1 / NH, the EM's posteriors: WEIGHTS), before the first add.  In a weighted mode a depth is a uint64 in units
+    of 2^-32 and runs64 / depth64 / summary64 are the getters; weight em takes add_names_* (or add_last) and finish_em(quant)."""
+
+    WEIGHTS = {"unit": 0, "nh": 1, "em": 2}
 
     RUN_PAGE = 1 << 20
 
@@ -1448,7 +1473,11 @@ class Coverage(_Accumulator):
                 "finish": [C.c_void_p, _P(C.c_int64)], "runs": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                 "depth": [C.c_void_p, C.c_int64, C.c_void_p], "summary": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                 "stats": [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double),
-                          _P(C.c_double)], "free": [C.c_void_p]}
+                          _P(C.c_double)], "free": [C.c_void_p],
+                "add_names": [C.c_void_p, _P(BrDeviceRows), C.c_void_p, C.c_int64, C.c_int, C.c_void_p],
+                "finish_em": [C.c_void_p, C.c_void_p, _P(C.c_int64)],
+                "runs64": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                "depth64": [C.c_void_p, C.c_int64, C.c_void_p], "summary64": [C.c_void_p] * 7}
 
     def __init__(self, lengths, device=0):
         self.lengths = np.ascontiguousarray(lengths, dtype=np.int64)
@@ -1486,11 +1515,68 @@ class Coverage(_Accumulator):
         """All rows of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
         self._call("add_last", ctx.h)
 
+    def add_names_raw(self, a, cigar, pool, row_off, n_rows, n_pool_words, group_off, n_groups, on_device, stream=None):
+        """br_coverage_add_names as it is (the tables as addresses): the return code (0, or a BR_ERR_* value)."""
+        rows = BrDeviceRows()
+        rows.n_rows, rows.n_pool_words = int(n_rows), int(n_pool_words)
+        rows.a, rows.cigar, rows.pool, rows.row_off = a, cigar, pool, row_off
+        return self._raw("add_names", C.byref(rows), C.c_void_p(group_off), int(n_groups), 1 if on_device else 0, C.c_void_p(stream or 0))
+
+    def add_names_host(self, rows_a, cigar, pool, row_off, group_off):
+        """The rows of the read names group_off[0 .. n] (the tables of Quant.add_rows_host, in host memory)."""
+        a = np.ascontiguousarray(rows_a, dtype=np.uint32).reshape(-1, 4)
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        pl = np.ascontiguousarray(pool, dtype=np.uint32)
+        ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+        go = np.ascontiguousarray(group_off, dtype=np.uint32)
+        assert len(cg) == len(a)
+        check(self.add_names_raw(a.ctypes.data if a.size else None, cg.ctypes.data if cg.size else None, pl.ctypes.data if pl.size else None,
+                                 ro.ctypes.data, len(a), len(pl), go.ctypes.data, len(go) - 1, False), "br_coverage_add_names")
+
+    def add_names_device(self, rows_a, cigar, pool, row_off, group_off, g0=0, g1=None):
+        """The same tables as torch CUDA tensors; the read names [g0, g1) of them are added."""
+        import torch
+        g1 = group_off.numel() - 1 if g1 is None else g1
+        check(self.add_names_raw(rows_a.data_ptr() if cigar.numel() else None, cigar.data_ptr() if cigar.numel() else None,
+                                 pool.data_ptr() if pool.numel() else None, row_off.data_ptr(), cigar.numel(), pool.numel(),
+                                 group_off.data_ptr() + 4 * g0, g1 - g0, True, torch.cuda.current_stream(row_off.device).cuda_stream),
+              "br_coverage_add_names")
+
     def finish(self):
         n = C.c_int64()
         self._call("finish", C.byref(n))
         self.n_runs = int(n.value)
         return self.n_runs
+
+    def finish_em(self, quant):
+        """weight em: finish with the posteriors of `quant` (a Quant with "keep_names", after em, fed the same names)."""
+        n = C.c_int64()
+        self._call("finish_em", quant.h, C.byref(n))
+        self.n_runs = int(n.value)
+        return self.n_runs
+
+    def runs64(self, page=None):
+        """weighted modes -> (tid, start, end: uint32 [n_runs]; depth: uint64 [n_runs], in units of 2^-32)"""
+        page = int(page or self.RUN_PAGE)
+        out = [np.zeros(max(self.n_runs, 1), dtype=np.uint32) for _ in range(3)] + [np.zeros(max(self.n_runs, 1), dtype=np.uint64)]
+        for first in range(0, self.n_runs, page):
+            n = min(page, self.n_runs - first)
+            self._call("runs64", first, n, *[o[first:].ctypes.data for o in out])
+        return tuple(o[:self.n_runs] for o in out)
+
+    def depth64(self, tid):
+        """weighted modes -> uint64 [max(L[tid], 0)]"""
+        d = np.zeros(max(int(self.lengths[tid]), 1), dtype=np.uint64)
+        self._call("depth64", int(tid), d.ctypes.data)
+        return d[:max(int(self.lengths[tid]), 0)]
+
+    def summary64(self):
+        """weighted modes -> dict of records, weight_sum, aligned_hi, aligned_lo, covered_bases, max_depth (uint64 per transcript)"""
+        nt = max(self.n_transcripts, 1)
+        keys = ("records", "weight_sum", "aligned_hi", "aligned_lo", "covered_bases", "max_depth")
+        out = {k: np.zeros(nt, dtype=np.uint64) for k in keys}
+        self._call("summary64", *[out[k].ctypes.data for k in keys])
+        return {k: v[:self.n_transcripts] for k, v in out.items()}
 
     def runs(self, page=None):
         """-> (tid, start, end, depth), uint32 [n_runs] each, ordered by (tid, start); fetched in pages of `page` runs"""

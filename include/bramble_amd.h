@@ -716,6 +716,13 @@ void br_sorter_free(br_sorter *);
  *                  transcript's over its classes in ascending order through a transposed membership table; items of more than 64
  *                  entries are summed by a wave (lane l takes entries l, l + 64, ..., then a fixed tree), so the shape of every sum
  *                  depends on the data alone and two runs on the same input give the same bits
+ *   posterior      (br_quant_posteriors, after br_quant_em.)  For label entry e of class c with transcript t: x_t = theta_t * w_t,
+ *                  with the theta br_quant_result returns and the w the EM used (1 / eff with "eff_len"); d_c = the sum of x over the
+ *                  class's labels in ascending order, one after the other whatever their number (no wave tree); p[e] = x_t / d_c,
+ *                  and 0 where d_c == 0.  float64, no fused multiply-add, one rounding per operation: a restatement in the same
+ *                  order gives the same bits.  A class of one label has p = 1.0
+ *   name classes   ("keep_names" = 1.)  name_cls[i] = the index, in the classes' order, of the class add-order name i fell into,
+ *                  0xffffffff for a name without rows; at any "hash_bits"
  *   br_quant_new        lengths: n_transcripts transcript lengths, or NULL (then "length_norm" must be 0).  BR_ERR_NO_DEVICE
  *                       without the device
  *   br_quant_set_param  before finish: "hash_bits" (test hook: 1..64 bits of the label hash are kept, so that different sets
@@ -723,7 +730,7 @@ void br_sorter_free(br_sorter *);
  *                       (tolerance in millionths; br_quant_set_tolerance takes the double itself); before the first add only, a
  *                       refused one with "eff_len" on included (the histogram is sized by then):
  *                       "eff_len" 0 / 1 (default 0: the fragment-length model above), "fld_max" 1 .. 65535 (default 1000, salmon's
- *                       fragLenDistMax)
+ *                       fragLenDistMax), "keep_names" 0 / 1 (default 0: finish leaves every name's class on the device)
  *   br_quant_add        the read names group_off[0 .. n_groups] of a batch: a / row_off / group_off as br_device_rows and
  *                       br_device_batch hold them (device memory with on_device != 0, read after the work queued on `stream`, NULL
  *                       for the null stream; host memory with on_device = 0).  Returns when the tables have been read.
@@ -770,12 +777,18 @@ void br_sorter_free(br_sorter *);
  *   br_quant_gene_boot_summary  mean and var, n_genes each, either may be NULL; after both as well
  *   br_quant_gene_stats seconds in br_quant_genes, labels over all gene classes, gene sets met with equal hashes and different
  *                       contents (any pointer may be NULL)
+ *   br_quant_name_classes  a host copy of name_cls[first .. first + n); after finish, BR_ERR_INVALID_ARG without "keep_names" or
+ *                       outside [0, n_names]
+ *   br_quant_posteriors the n_labels posteriors, parallel to the labels of br_quant_classes; after br_quant_em.  post may be NULL: the
+ *                       table is then only made and held on the device (br_coverage_finish_em reads it there).  A later br_quant_em
+ *                       drops it
  * Device memory: 4 bytes a row and 20 bytes a read name while adding; finish peaks at 32 more a name with labels, then holds 24
  * bytes a class, 8 a label and 24 a transcript; the EM adds 40 a transcript and 8 a class; "eff_len" adds 16 (fld_max + 4) for the
  * histogram (the run's and an add's own), 16 (fld_max + 1) for the prefixes during finish and 8 a transcript for eff; the bootstrap
  * holds 8 B a transcript (the result) and 8 a class (cum), and while it runs, for a chunk of W replicates (16 by default), 32 W a
  * transcript and 12 W a class, the summary 16 a transcript; br_quant_genes holds 24 bytes a gene class, 4 a gene label, 24 a gene and
- * 4 a transcript, peaks at 32 a label and 4 a transcript beside them, and the gene replicates add 8 B a gene (quant.cpp). */
+ * 4 a transcript, peaks at 32 a label and 4 a transcript beside them, and the gene replicates add 8 B a gene; "keep_names" holds 4
+ * bytes a name from finish on (and 4 a class more while the classes are made), the posteriors 8 a label (quant.cpp). */
 typedef struct br_quant br_quant;
 int br_quant_new(int device, int64_t n_transcripts, const int64_t *lengths, br_quant **out);
 int br_quant_set_param(br_quant *, const char *name, int64_t value);
@@ -804,6 +817,8 @@ int br_quant_gene_result(br_quant *, double *num_reads, double *tpm, double *len
 int br_quant_gene_boot(br_quant *, int32_t first, int32_t count, double *num_reads);   /* count x n_genes, replicate-major */
 int br_quant_gene_boot_summary(br_quant *, double *mean, double *var);
 int br_quant_gene_stats(const br_quant *, double *seconds, int64_t *n_gene_labels, uint64_t *collisions);
+int br_quant_name_classes(br_quant *, int64_t first, int64_t n, uint32_t *cls);
+int br_quant_posteriors(br_quant *, double *post);
 void br_quant_free(br_quant *);
 
 /* Coverage: the depth of coverage along every transcript, from the rows of a whole run, in one device's HBM (coverage.cpp,
@@ -826,9 +841,26 @@ void br_quant_free(br_quant *);
  *   run            a maximal interval [start, end) of one transcript with one depth > 0.  Runs never span two transcripts, whatever
  *                  the depths on both sides of the boundary; they are ordered by (transcript, start)
  *   invariance     how the rows were cut into adds, and their order, changes nothing; two runs give the same bits (integer atomics)
+ *   weighted depth ("weight" = 1: nh, 2: em; 0, the default, is everything above and nothing below.)  Fixed point: one unit of depth
+ *                  is 2^32 and a depth word is uint64.  A counted row with weight word q leaves + q at the first base of each clamped
+ *                  covered interval and - q (mod 2^64) behind its last; the depth is the inclusive scan modulo 2^64.  Rows per
+ *                  object stay below 2^32 and q <= 2^32, so no depth overflows.  Which rows count, how intervals are formed,
+ *                  merged and clamped, and clipped_bases are exactly as above
+ *   weight nh      q = (2^32 + nh / 2) / nh in integer arithmetic, nh the row's br_row_a.nh >= 1.  A row with nh == 0 is skipped and
+ *                  counts in rows_skipped; br_coverage_finish then returns BR_ERR_INVALID_ARG
+ *   weight em      q = (uint64) rint(p * 4294967296.0), ties to even, p the posterior (br_quant, `posterior`) of (the row's read
+ *                  name, the row's transcript): the entry of the row's transcript among the labels of the class the name fell
+ *                  into.  A name of a one-label class has q = 2^32 exactly (33 bits: why the depth is 64-bit).  A row with q == 0
+ *                  is still a counted record.  NH is not looked at
+ *   per transcript (weighted) records[t] = the counted rows (uint64, unweighted); weight_sum[t] = the sum of their q; aligned_hi[t] =
+ *                  the sum over the bases of depth >> 32 and aligned_lo[t] = the sum of depth & 0xffffffff (one 64-bit sum of
+ *                  fixed-point depths can overflow, these two cannot); covered_bases[t] = the bases of depth > 0; max_depth[t]; all
+ *                  uint64
+ *   run            (weighted) as above with the fixed-point depth: depths one unit of 2^-32 apart are different runs
  *   br_coverage_new        BR_ERR_INVALID_ARG for a length above 2^32 - 1 (start and end are 32-bit), BR_ERR_NO_DEVICE without the
  *                          device, BR_ERR_CAPACITY when the device's memory does not take 4 (B + 1) bytes
- *   br_coverage_set_param  before the first add: "primary_only" 0 / 1 (default 0)
+ *   br_coverage_set_param  before the first add: "primary_only" 0 / 1 (default 0); "weight" 0 / 1 / 2 (default 0; diff is made again
+ *                          at 8 bytes a base for 1 and 2; BR_ERR_CAPACITY for 2 with 2^40 bases or more)
  *   br_coverage_add_rows   the rows [r0, r1) of a table: a, cigar, pool, n_rows and n_pool_words of `rows` (device memory with
  *                          on_device != 0, read after the work queued on `stream`, NULL for the null stream; host memory in the
  *                          same layout with on_device = 0).  Returns when the tables have been read.  A row whose transcript_id is
@@ -845,7 +877,32 @@ void br_quant_free(br_quant *);
  *   br_coverage_summary    after finish: n_transcripts entries each
  *   br_coverage_stats      rows counted / skipped and bases clipped by the adds so far, device bytes held now and the most held so
  *                          far, seconds in add / finish
- * Any out-pointer may be NULL.  Device memory: 4 bytes a base (diff, which finish turns into the depth in place) and 16 a transcript
+ *   br_coverage_add_names  the rows of the read names group_off[0 .. n_groups] of a batch: the shapes and rules of br_quant_add_rows
+ *                          (rows->row_off, n_rows and n_pool_words are read as well).  With "weight" 0 and 1 it is
+ *                          br_coverage_add_rows over the names' row range.  With "weight" 2 the add keeps instead of counting: for
+ *                          every clamped, non-empty interval of a counted row 16 bytes (the absolute first base, the length, the
+ *                          add-order index of the name; a counted row without such an interval leaves one entry of length 0, so
+ *                          that its weight reaches weight_sum); records and the counters are updated at the add.  Offsets that
+ *                          descend (host tables), or a row that the offsets give to no name (device tables: every row's name
+ *                          is checked against the offsets on both sides): BR_ERR_INVALID_ARG and nothing added.
+ *                          BR_ERR_CAPACITY at 2^32 names
+ *   br_coverage_add_rows   ("weight" 2) BR_ERR_INVALID_ARG: the rows have no names
+ *   br_coverage_add_last   ("weight" 2) br_coverage_add_names of the context's last call (a call that left no names: BR_OK)
+ *   br_coverage_finish     ("weight" 2) BR_ERR_INVALID_ARG: br_coverage_finish_em
+ *   br_coverage_finish_em  "weight" 2 only: the kept entries are applied with the quantifier's posteriors, the arena is freed, then
+ *                          depth, summary and runs.  It needs a quantifier on the same device, with "keep_names", after br_quant_em,
+ *                          whose names number what this object's add_names were given -- the two were fed the same names in the same
+ *                          order; else BR_ERR_INVALID_ARG and the object is as it was.  Every index the apply takes from a table is
+ *                          compared with that table's size first: a name past the count, a class past the classes (a name without
+ *                          rows among them) or a transcript that is not in the name's class is counted, never looked up, and makes
+ *                          the call return BR_ERR_INVALID_ARG (the object answers BR_ERR_INVALID_ARG from then on)
+ *   br_coverage_runs64 / _depth64 / _summary64  the getters of the weighted modes (depth words uint64; runs as three uint32 arrays and
+ *                          the depth); they answer BR_ERR_INVALID_ARG with "weight" 0, br_coverage_runs / _depth / _summary with
+ *                          "weight" 1 and 2.  br_coverage_stats is valid in every mode
+ * Any out-pointer may be NULL.  Device memory in a weighted mode: 8 bytes a base and 24 a transcript from "weight" on, 128 bytes of
+ * counters; weight em holds 16 bytes a kept entry until finish_em has applied them (room grows by half, the old arena beside the
+ * new while copying) and 4 bytes a row of an add while it runs; finish adds 32 a transcript, 24 a run and 8 a tile while it runs
+ * (coverage.cpp).  Device memory with "weight" 0: 4 bytes a base (diff, which finish turns into the depth in place) and 16 a transcript
  * from br_coverage_new on; finish adds 20 a transcript, 16 a run and, while it runs, 8 a tile of 4096 bases; a host add holds 24
  * bytes a row and 4 a pool word while it runs (coverage.cpp). */
 typedef struct br_coverage br_coverage;
@@ -859,6 +916,13 @@ int br_coverage_depth(br_coverage *, int64_t tid, uint32_t *depth);
 int br_coverage_summary(br_coverage *, uint64_t *records, uint64_t *aligned_bases, uint64_t *covered_bases, uint32_t *max_depth);
 int br_coverage_stats(const br_coverage *, uint64_t *rows_counted, uint64_t *rows_skipped, uint64_t *clipped_bases, uint64_t *held_bytes,
                       uint64_t *peak_bytes, double *add_seconds, double *finish_seconds);
+/* the weighted modes ("weight" = 1, 2) */
+int br_coverage_add_names(br_coverage *, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups, int on_device, void *stream);
+int br_coverage_finish_em(br_coverage *, br_quant *, int64_t *n_runs);
+int br_coverage_runs64(br_coverage *, int64_t first, int64_t n, uint32_t *tid, uint32_t *start, uint32_t *end, uint64_t *depth);
+int br_coverage_depth64(br_coverage *, int64_t tid, uint64_t *depth);
+int br_coverage_summary64(br_coverage *, uint64_t *records, uint64_t *weight_sum, uint64_t *aligned_hi, uint64_t *aligned_lo,
+                          uint64_t *covered_bases, uint64_t *max_depth);
 void br_coverage_free(br_coverage *);
 
 /* br_project_bam_staged / _nowait for records that are in HBM already (a br_bam_reader bundle, or br_bam_split_device's);
@@ -946,7 +1010,7 @@ const char *const *br_annotation_gene_ids(const br_annotation *);
  * input is inflated and split into records on the GPU, br_bam_reader) / --host-reader, --bundle-size and --device / --devices,
  * --collate, -O bam|sam, --sort [--write-index], --quant FILE [--quant-classes FILE] [--quant-eff-length [--quant-fld FILE]]
  * [--quant-bootstraps B [--quant-seed S] [--quant-boot-out FILE]] [--quant-genes FILE [--quant-gene-classes FILE] [--quant-gene-map FILE]]
- * (br_quant above; the genes are br_annotation_gene_ids', numbered in order of first appearance in @SQ order, or the map file's), --coverage FILE / --coverage-summary FILE [--coverage-primary] (br_coverage above; the usage text says the
+ * (br_quant above; the genes are br_annotation_gene_ids', numbered in order of first appearance in @SQ order, or the map file's), --coverage FILE / --coverage-summary FILE [--coverage-primary] [--coverage-weight unit|nh|em] (br_coverage above; the usage text says the
  * rest).
  * Returns the process exit code. */
 int br_cli_main(int argc, char **argv);
