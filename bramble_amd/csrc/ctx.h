@@ -121,7 +121,8 @@ struct br_ctx {
   // sets before anything is emitted, and the emit kernels write the packed rows themselves
   int direct_rows = 1;       // "direct_rows" / BRAMBLE_AMD_DIRECT_ROWS=0: the match-table path (k_emit_dense -> k_pair -> k_rows), the A/B switch
   int pair_bitmask = 1;      // "pair_bitmask": k_pair_mask intersects mates' survivor sets as 64-bit tid masks where their tids span at most 64 (0: lists only, the A/B switch)
-  DevBuf d_fm, d_nkept, d_desc, d_hi0, d_clspos, d_rnd, d_side, d_sidectr;
+  int emit_rank_tids = 1;    // "emit_rank_tids": k_pair_mask leaves a pair's common tids as a word per alignment and the emit kernels rank by counting its bits (0: the rank loop only, the A/B switch)
+  DevBuf d_fm, d_nkept, d_desc, d_hi0, d_clspos, d_rnd, d_side, d_sidectr, d_kt;
   uint64_t d_side_cap = 0;   // (br_ctx_set_param "side_cap": the first capacity, a test hook)
   int d_side_attempts = 0;   // side-arena attempts of the last direct-rows call (br_ctx_direct_diag)
   bool last_direct = false;  // the last call's rows came from the direct path: the detail column is re-emitted on request, not gathered

@@ -133,6 +133,9 @@ __device__ __forceinline__ uint64_t keep8(uint2 pb, const uint32_t (&t)[8], uint
   return f;
 }
 
+// the tid word of alignment i (DirectArgs::kt): none -- the emit pass ranks its kept survivors by the loop
+__device__ __forceinline__ void kt_none(const DirectArgs &D, uint32_t i) { if (D.kt) D.kt[i] = make_uint4(0u, 0u, KT_NONE, 0u); }
+
 // one window of 64 alignments starting at w0; false: its lists do not fit CAP slots (nothing of the list path's PAIRs was written)
 // Lanes 1..62 own their alignments; lanes 0 and 63 are the neighbours on either side, loaded and staged like the others so
 // that a pair that straddles two waves' ranges (mates are neighbours as a rule) finds its partner inside the window; they
@@ -141,6 +144,10 @@ __device__ __forceinline__ uint64_t keep8(uint2 pb, const uint32_t (&t)[8], uint
 // tids -- transcripts are numbered in location order, so that is nearly every pair -- never reaches the lists: each lane
 // folds its tids into a 64-bit mask relative to the pair's smallest tid, and the intersection is one AND.  What the rule turns
 // away takes the list path below, with the same results: how transcripts are numbered decides the speed and nothing else.
+// The tid word (D.kt, null with "emit_rank_tids" 0): a pair on the mask path with a common transcript keeps exactly the common
+// tids on both sides, so {common, base} IS the sorted list of an alignment's kept tids, and the emit lanes take a record's
+// rank from it with one population count instead of gathering the kept survivors' tids again.  Every place that writes fm[i]
+// writes kt[i] too -- the word, or the marker KT_NONE -- so no emit lane ever meets a word of an earlier call.
 template <int CAP, bool BM>
 __device__ __forceinline__ bool pair_window(const DirectArgs &D, PmSh<CAP> &S, int64_t w0, int lane) {
   const int64_t i64 = w0 + lane;
@@ -173,6 +180,7 @@ __device__ __forceinline__ bool pair_window(const DirectArgs &D, PmSh<CAP> &S, i
     const bool solo = role == PR_SOLO;
     D.fm[i] = solo ? make_uint2((uint32_t)mk, (uint32_t)(mk >> 32)) : make_uint2(0, 0);
     D.n_kept[i] = solo ? cnt : 0u; D.n_rows[i] = solo ? cnt : 0u; D.pflag[i] = 0;
+    kt_none(D, i);
   }
   // (a neighbour lane takes part only for a partner inside the window)
   bool pair = role == PR_PAIR && !defer && (owner || m_in);
@@ -220,6 +228,8 @@ __device__ __forceinline__ bool pair_window(const DirectArgs &D, PmSh<CAP> &S, i
         D.n_kept[i] = nk;
         D.n_rows[i] = leader ? 2u * nk : 0u;
         D.pflag[i] = (uint8_t)((paired ? PF_PAIRED : 0u) | ((paired && common != 0) ? PF_SAME : 0u) | ((paired && !leader) ? PF_MATE : 0u));
+        // the kept survivors' tids are exactly the common ones: the emit pass ranks a survivor by counting common's bits below its own
+        if (D.kt) D.kt[i] = make_uint4((uint32_t)common, (uint32_t)(common >> 32), common ? base : KT_NONE, 0u);
       }
     }
     // the list path: what the span rule turned away, and partners outside the window
@@ -276,6 +286,7 @@ __device__ __forceinline__ bool pair_window(const DirectArgs &D, PmSh<CAP> &S, i
     D.n_kept[i] = nk;
     D.n_rows[i] = leader ? 2u * nk : 0u;
     D.pflag[i] = (uint8_t)((paired ? PF_PAIRED : 0u) | ((paired && S.same[lane]) ? PF_SAME : 0u) | ((paired && !leader) ? PF_MATE : 0u));
+    kt_none(D, i);
   }
   // br_ctx_direct_diag: the alignments the lists resolved, one atomic per wave that has any, spread like k_group_desc's
   if (BM && lane == 0)
@@ -551,6 +562,7 @@ __global__ void __launch_bounds__(64) k_pair_big(DirectArgs D) {
         D.n_kept[m] = nkp;
         D.n_rows[m] = leader ? 0u : (pp ? 2u * nkp : 0u);   // the partner leads when b does not
         D.pflag[m] = (uint8_t)((pp ? PF_PAIRED : 0u) | ((pp && same) ? PF_SAME : 0u) | ((pp && leader) ? PF_MATE : 0u));
+        kt_none(D, (uint32_t)m);
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -796,7 +808,8 @@ __global__ void __launch_bounds__(256) k_expand_rows(DirectArgs D) {
 
 // ---------------------------------------------------------------------------
 // k_emit_rows<CLS>: one lane per kept match (work-list entry).  Entry -> alignment -> its k-th kept survivor (k-th set
-// bit of the filtered mask) and that survivor's tid rank c among the kept (the rank loop over s_tid, as k_emit_dense) ->
+// bit of the filtered mask) and that survivor's tid rank c among the kept (from the alignment's tid word, DirectArgs::kt, where
+// k_pair_mask left one: the bits of the common tids below the lane's own; else the rank loop over s_tid, as k_emit_dense) ->
 // candidate row -> ideal CIGAR, merge -> the packed row at first record + stride * c.  CLS as k_emit_dense: 1 = the simple
 // prefix (one read exon from a single M op, and the light two-exon class the count pass adds to it: "M N M" with exact
 // inner junctions, a closed form as well), 2 = the rest.
@@ -825,6 +838,8 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 5) k_emit_rows(ProjectArgs
   const ntl2 f_ = __builtin_nontemporal_load((const ntl2 *)(D.fm + a)), gd_ = __builtin_nontemporal_load((const ntl2 *)(D.gd + a)), dp_ = __builtin_nontemporal_load((const ntl2 *)(D.dpos + a));
   const uint4 hd = make_uint4(hd_.x, hd_.y, hd_.z, hd_.w), rg = make_uint4(rg_.x, rg_.y, rg_.z, rg_.w);
   const uint2 f = make_uint2(f_.x, f_.y), gd = make_uint2(gd_.x, gd_.y), dp = make_uint2(dp_.x, dp_.y);
+  ntl4 kt = {0u, 0u, KT_NONE, 0u};   // the alignment's tid word (null array: "emit_rank_tids" 0, every lane ranks by the loop)
+  if (D.kt) kt = __builtin_nontemporal_load((const ntl4 *)(D.kt + a));
   const uint4 E = make_uint4(gd.x, gd.y, dp.x, dp.y);   // the emit descriptor: {PF_* | (primary rank + 1) << 8, NH, first record, work-list position}
   const uint32_t is_fast = CLS == 1;
   uint4 hd2 = make_uint4(0, 0, 0, 0);
@@ -846,8 +861,15 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 5) k_emit_rows(ProjectArgs
   const uint32_t gs = r_a.x, gend = r_a.y;
   const uint4 pay = make_uint4(r_b.x, r_b.y, r_a.w, r_b.z);
   uint32_t c = 0;   // rank by tid among the kept: its record among the alignment's
-  {
-    for (uint64_t m2 = fmask; m2;) {   // eight loads in flight per step: unconditional (spent slots re-read the lane's own row)
+  // With a tid word (k_pair_mask's mask path: nearly every pair) the kept tids are the bits of `common` relative to `base`, and
+  // the rank is the number of bits below the lane's own; a single kept survivor has rank 0.  What is left -- SOLO alignments
+  // with several survivors, list-path pairs, partners of big alignments -- gathers the kept survivors' tids, and a wave
+  // without such a lane skips that.
+  const bool has_word = kt.z != KT_NONE;
+  const bool by_loop = !has_word && (fmask & (fmask - 1)) != 0;
+  if (has_word) c = (uint32_t)__popcll(((uint64_t)kt.x | ((uint64_t)kt.y << 32)) & ((1ull << ((pay.x - kt.z) & 63u)) - 1ull));
+  if (__ballot(by_loop)) {
+    for (uint64_t m2 = by_loop ? fmask : 0ull; m2;) {   // eight loads in flight per step: unconditional (spent slots re-read the lane's own row)
       uint32_t t8[8]; bool ok[8];
 #pragma unroll
       for (int u = 0; u < 8; u++) {

@@ -232,6 +232,7 @@ __device__ __forceinline__ bool rows_over(const uint64_t *tot, uint64_t lim_r) {
 //   k_emit_rows<CLS>, k_big_emit   one lane per kept match -> packed row at row_off[leader] + stride * rank (+ is_mate)
 // ---------------------------------------------------------------------------
 enum : uint32_t { PF_PAIRED = 1, PF_SAME = 2, PF_MATE = 4, PF_BIG = 8 };   // pflag / low byte of the descriptor's .y
+#define KT_NONE 0xffffffffu   // DirectArgs::kt[i].z: no tid word
 struct DirectArgs {
   int64_t n_aln, n_groups;
   const uint32_t *group_off;     // [n_groups + 1]
@@ -248,7 +249,11 @@ struct DirectArgs {
   uint32_t *n_kept;              // [n_aln] kept survivors = emitted records of the alignment
   uint32_t *n_rows;              // [n_aln] records of a leader (its own + its mate's), else 0
   uint8_t *pflag;                // [n_aln] PF_*
-  uint2 *side;                   // big alignments: {tid, rank among the kept | ~0u: dropped} per survivor, candidate order
+  // [n_aln] the tid word of an alignment with a mask, written wherever its fm is: {common.lo, common.hi, base, 0} = the kept
+  // tids as bits relative to the pair's smallest tid (the mask path with a common transcript), else .z = KT_NONE: the emit
+  // pass ranks by its loop.  Null ("emit_rank_tids" 0): nobody writes or reads it.
+  uint4 *kt;
+  uint2 *side;                  // big alignments: {tid, rank among the kept | ~0u: dropped} per survivor, candidate order
   uint64_t side_cap;
   uint32_t *pm_list, *pm_n;      // k_pair_mask: windows (index / 64) whose tid lists exceed its staging area, and their count
   unsigned long long *side_used; // [0] entries handed out, [1] set when the arena ran out (the host grows it and repeats)

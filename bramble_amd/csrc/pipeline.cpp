@@ -490,6 +490,7 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
   RC(c->aln_group.ensure((size_t)n * 4)); RC(c->n_rows.ensure((size_t)n * 4 + 16)); RC(c->pbit.ensure((size_t)n + 16));
   RC(c->d_fm.ensure((size_t)n * sizeof(uint2) + (size_t)(n / 62 + 2) * 4));   // + the window list of k_pair_mask
   RC(c->d_nkept.ensure((size_t)n * 4)); RC(c->d_desc.ensure((size_t)n * sizeof(uint4)));
+  if (c->emit_rank_tids) RC(c->d_kt.ensure((size_t)n * sizeof(uint4)));   // the tid words of k_pair_mask ("emit_rank_tids", read at every launch)
   RC(c->d_hi0.ensure((size_t)n * 4)); RC(c->d_clspos.ensure((size_t)n * 4)); RC(c->d_rnd.ensure((size_t)std::max<int64_t>(ng, 1) * 8));
   if (c->d_side_cap == 0) c->d_side_cap = std::max<uint64_t>((uint64_t)n / 4, 1u << 20);
   RC(c->d_side.ensure((size_t)c->d_side_cap * sizeof(uint2)));
@@ -510,6 +511,7 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
   D.n_matches = c->n_matches.as<uint32_t>(); D.mask = c->mask.as<uint64_t>(); D.ranges = c->ranges.as<uint4>();
   D.fast_flag = c->fast_flag.as<uint32_t>(); D.s_tid = ix->dev.s_tid; D.big_list = A.big_list; D.n_big = A.n_big;
   D.fm = c->d_fm.as<uint2>(); D.pm_list = (uint32_t *)(c->d_fm.as<uint2>() + n); D.pm_n = dz_nbig + 2; D.n_kept = c->d_nkept.as<uint32_t>(); D.n_rows = c->n_rows.as<uint32_t>(); D.pflag = c->pbit.as<uint8_t>();
+  D.kt = c->emit_rank_tids ? c->d_kt.as<uint4>() : nullptr;
   D.side = c->d_side.as<uint2>(); D.side_cap = c->d_side_cap; D.side_used = (unsigned long long *)(dz + GD_COUNTER_WORDS);
   D.cls_pos = c->d_clspos.as<uint32_t>(); D.cig_base = c->cig_base.as<uint64_t>(); D.row_off = c->row_off.as<uint64_t>();
   D.name_off = have_names ? b->name_off : nullptr; D.names = have_names ? b->names : nullptr; D.rnd0 = c->d_rnd.as<uint64_t>();
@@ -988,6 +990,20 @@ extern "C" int br_ctx_direct_diag(br_ctx *c, uint64_t out[8], uint8_t *pflags) {
       if ((ff[a] >> 31) && hd[a].z == 2 && !(pf[a] & PF_BIG)) light += nk[a];
     out[5] = light;
   }
+  return BR_OK;
+}
+
+// Diagnostic: the tid words the last direct-rows call's pairing left (DirectArgs::kt), one per alignment.  A call made with
+// "emit_rank_tids" 0 has none: every alignment reads as "no word".
+extern "C" int br_ctx_direct_tidwords(br_ctx *c, uint64_t *common, uint32_t *base) {
+  if (!c || !common || !base || !c->last_direct) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->ix->device));
+  const DirectArgs &D = c->dD;
+  const size_t n = D.n_aln > 0 ? (size_t)D.n_aln : 0;
+  std::vector<uint4> w(n, make_uint4(0u, 0u, KT_NONE, 0u));
+  HIPCHK(hipDeviceSynchronize());
+  if (D.kt && n) HIPCHK(hipMemcpy(w.data(), D.kt, n * sizeof(uint4), hipMemcpyDeviceToHost));
+  for (size_t a = 0; a < n; a++) { common[a] = (uint64_t)w[a].x | ((uint64_t)w[a].y << 32); base[a] = w[a].z; }
   return BR_OK;
 }
 

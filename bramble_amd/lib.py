@@ -160,6 +160,7 @@ class BrDeviceBam(C.Structure):
     _fields_ = [("data", C.c_void_p), ("n_bytes", C.c_uint64), ("row_off", C.c_void_p), ("n_rows", C.c_int64)]
 
 
+KT_NONE = 0xffffffff   # Context.direct_tidwords: base of an alignment without a tid word (kernels.h)
 # the pairing flags per alignment that Context.direct_diag returns (kernels.h)
 PF_PAIRED, PF_SAME, PF_MATE, PF_BIG = 1, 2, 4, 8
 
@@ -185,7 +186,7 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_coverage_depth", "br_coverage_summary", "br_coverage_stats", "br_coverage_free",
            "br_coverage_add_names", "br_coverage_finish_em", "br_coverage_runs64", "br_coverage_depth64", "br_coverage_summary64",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
-           "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
+           "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_direct_tidwords", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
 _LIB = None
 
@@ -270,6 +271,7 @@ def lib():
         L.br_ctx_collect_counters.argtypes = [C.c_void_p, _P(BrDeviceBatch), C.c_void_p]
         L.br_ctx_last_counters.argtypes = [C.c_void_p, C.c_void_p]
         L.br_ctx_direct_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.br_ctx_direct_tidwords.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.br_ctx_rescue_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.br_ctx_ksw_diag.argtypes = [C.c_void_p, C.c_void_p]
         L.br_device_rows_detail.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -639,6 +641,15 @@ class Context:
         if pf is not None:
             d["pflags"] = pf
         return d
+
+    def direct_tidwords(self, n_aln):
+        """The tid words the last call's (a direct-rows call's) pairing left, one per alignment: (common uint64 [n_aln], base
+        uint32 [n_aln]).  base[a] != KT_NONE: bit b of common[a] = transcript base[a] + b is kept, and the emit kernels ranked the
+        alignment's records by counting bits; KT_NONE: no word, ranked by the loop (always, after a call with "emit_rank_tids" 0).
+        Diagnostic only; the words of alignments that keep nothing mean nothing."""
+        common, base = np.zeros(n_aln, dtype=np.uint64), np.zeros(n_aln, dtype=np.uint32)
+        check(lib().br_ctx_direct_tidwords(self.h, common.ctypes.data if n_aln else None, base.ctypes.data if n_aln else None), "br_ctx_direct_tidwords")
+        return common, base
 
     def project_bam_device(self, cfg, blob, rec_off, rec_len, ref_map, stream=0):
         """Raw mapped BAM records resident in HBM -> (BrDeviceRows, BrDeviceBam): reader side, projection and

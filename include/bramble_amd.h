@@ -1071,7 +1071,8 @@ int br_ctx_set_profiling(br_ctx *, int enabled);
 /* Launch tuning: "group_lanes" (8|16|32|64 lanes cooperating on one alignment),
  * "blocks_per_cu" (grid size of the grid-stride projection kernels), "bam_lanes" (0, the default: a wave per 32
  * re-encoded records, their byte regions as 16-byte copy tasks; 4..64: that many lanes per record), "deflate_dynamic" (1: per-block Huffman codes, 0: the fixed code),
- * "pair_bitmask" (1, the default: direct rows intersect two mates' transcript sets as 64-bit masks where their ids span at most 64; 0: as lists always. Same rows.).
+ * "pair_bitmask" (1, the default: direct rows intersect two mates' transcript sets as 64-bit masks where their ids span at most 64; 0: as lists always. Same rows.),
+ * "emit_rank_tids" (1, the default: that intersection leaves the pair's common transcript ids as a 16-byte word per alignment and the direct-rows emit kernels take a record's rank from it; 0: they gather the kept survivors' ids, no word is stored. Same rows; br_ctx_direct_tidwords.).
  * Short-read presets run the count pass of large batches as a main kernel without the exon walk plus a second one for the
  * alignments that need it, and launch the emit work list per class; small batches and the similarity-filter presets use
  * one kernel for each. */
@@ -1101,6 +1102,15 @@ int br_ctx_last_counters(br_ctx *, uint64_t out[8]);
  * 64 candidate rows).  The test hook br_ctx_set_param("side_cap", v >= 64) sets the arena's first capacity; a call that
  * outgrows it grows the arena to what it asked for and repeats once. */
 int br_ctx_direct_diag(br_ctx *, uint64_t out[8], uint8_t *pflags);
+/* Diagnostic of the last call, which must have been a direct-rows call (else BR_ERR_INVALID_ARG), never part of a timed
+ * region: the tid word of each of its n_aln alignments.  base[a] != 0xffffffff: k_pair_mask intersected the pair's
+ * transcript sets as 64-bit masks and found a common transcript; base[a] is the pair's smallest transcript id, bit b of
+ * common[a] says that transcript base[a] + b is kept, and the emit kernels took a record's rank among the alignment's by
+ * counting the bits below its own.  base[a] == 0xffffffff: no word (an alignment without a partner, a pair on the list path
+ * or without a common transcript, the partner of an alignment with more than 64 candidate rows): ranked by gathering the kept
+ * survivors' ids.  Words of alignments that keep nothing, or that have more than 64 candidate rows, mean nothing.  After a call made with
+ * br_ctx_set_param("emit_rank_tids", 0) (1, the default; read at every call; same rows) every alignment reads as "no word". */
+int br_ctx_direct_tidwords(br_ctx *, uint64_t *common, uint32_t *base);
 
 /* -S runs: out[0] = rescue problems of the last call, out[1] = ksw2 DP cells (sum of qlen x tlen),
  * out[2] = accepted rescues, out[3] = coded sequence bytes. */
