@@ -14,6 +14,7 @@
 //                   bundle goes to the writer, and after the last bundle the consumer's pieces take the same way out
 //                   (br_device_bam_download -> writer); the writer notes the blocks it writes for the consumer's index
 #include <ctype.h>
+#include <math.h>
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -47,6 +48,7 @@ void usage(FILE *f) {
           "               [--quant <quant.tsv> [--quant-classes <eq_classes.txt>] [--quant-length-norm | --quant-no-length-norm]\n"
           "                [--quant-eff-length [--quant-fld <fld.tsv>]]\n"
           "                [--quant-bootstraps B [--quant-seed S] [--quant-boot-out <bootstraps.tsv>]]\n"
+          "                [--quant-vb [--quant-vb-prior P] [--quant-vb-per-nucleotide]]\n"
           "                [--quant-genes <genes.tsv> [--quant-gene-classes <gene_classes.txt>] [--quant-gene-map <tx2gene.tsv>]]]\n"
           "               [--coverage <cov.bedgraph>] [--coverage-summary <cov.tsv>] [--coverage-primary]\n"
           "               [--coverage-weight unit|nh|em]\n\n"
@@ -84,6 +86,12 @@ void usage(FILE *f) {
           "normalisation: not with --quant-no-length-norm, and under --lr / --lr-hq only with --quant-length-norm.  --quant-fld FILE:\n"
           "the histogram, FragmentLength and Count for the lengths 0 .. 1000.  One more line in front of the quantified line:\n"
           "[bramble] fragment lengths: N observed, mean M.M, U unique names without a pair, R out of range\n"
+          "--quant-vb: the variational Bayes EM (salmon's default estimator) in place of the maximum-likelihood EM, for the point estimate,\n"
+          "the replicates and the posteriors of --coverage-weight em: a Dirichlet prior of P reads per transcript (--quant-vb-prior P,\n"
+          "default 0.01, finite and >= 0) or, with --quant-vb-per-nucleotide, per nucleotide of its (effective) length, which needs\n"
+          "length normalisation; isoforms without evidence of their own go to zero.  Transcripts the data cannot tell apart are\n"
+          "split by rounding (the same on every run).  The files keep their columns.  One more line in front of the quantified line:\n"
+          "[bramble] variational Bayes: prior P per transcript|nucleotide, N transcripts at zero\n"
           "--quant-genes FILE: the transcripts' results collapsed to genes on the GPU (the gene_id of the annotation): one line per gene,\n"
           "genes in order of first appearance in @SQ order: Name, Length (the TPM-weighted mean of its transcripts' lengths, their plain\n"
           "mean where the gene's TPM is 0), [EffectiveLength,] NumReads, TPM, UniqueReads and AmbigReads (of the read names' gene sets: a\n"
@@ -172,6 +180,14 @@ int parse_args(int argc, char **argv, Options &o) {
       if (e == v || *e || errno) { fprintf(stderr, "--quant-seed: %s is not a 64-bit integer\n", v); return -1; }
       o.quant_seed = x; o.quant_seed_given = true;
     }
+    else if (a == "--quant-vb") o.quant_vb = true;
+    else if (a == "--quant-vb-per-nucleotide") o.quant_vb_per_nt = true;
+    else if (a == "--quant-vb-prior") {
+      const char *v = value(); if (!v) return -1;
+      char *e = nullptr; const double x = strtod(v, &e);
+      if (e == v || *e || !(x >= 0.0) || !isfinite(x)) { fprintf(stderr, "--quant-vb-prior: %s is not a finite number >= 0\n", v); return -1; }
+      o.quant_vb_prior = x; o.quant_vb_prior_given = true;
+    }
     else if (a == "--quant-boot-out") { const char *v = value(); if (!v) return -1; o.quant_boot_out = v; }
     else if (a == "--quant-genes") { const char *v = value(); if (!v) return -1; o.quant_genes = v; }
     else if (a == "--quant-gene-classes") { const char *v = value(); if (!v) return -1; o.quant_gene_classes = v; }
@@ -208,6 +224,9 @@ int parse_args(int argc, char **argv, Options &o) {
   if (o.quant.empty() && (!o.quant_classes.empty() || o.quant_length_norm >= 0)) { fprintf(stderr, "--quant-classes, --quant-length-norm and --quant-no-length-norm need --quant\n"); return -1; }
   if (o.quant.empty() && (o.quant_eff_length || !o.quant_fld.empty())) { fprintf(stderr, "--quant-eff-length and --quant-fld need --quant\n"); return -1; }
   if (o.quant.empty() && (o.quant_bootstraps || o.quant_seed_given || !o.quant_boot_out.empty())) { fprintf(stderr, "--quant-bootstraps, --quant-seed and --quant-boot-out need --quant\n"); return -1; }
+  if (o.quant.empty() && (o.quant_vb || o.quant_vb_prior_given || o.quant_vb_per_nt)) { fprintf(stderr, "--quant-vb, --quant-vb-prior and --quant-vb-per-nucleotide need --quant\n"); return -1; }
+  if (!o.quant_vb && (o.quant_vb_prior_given || o.quant_vb_per_nt)) { fprintf(stderr, "--quant-vb-prior and --quant-vb-per-nucleotide need --quant-vb: without it there is no prior\n"); return -1; }
+  if (o.quant_vb_per_nt && (o.quant_length_norm == 0 || ((o.cfg.lr || o.cfg.lr_hq) && o.quant_length_norm != 1))) { fprintf(stderr, "--quant-vb-per-nucleotide needs length normalisation: the prior is scaled by the length the reads are weighted by (not with --quant-no-length-norm; under --lr / --lr-hq only with --quant-length-norm)\n"); return -1; }
   if (o.quant.empty() && !o.quant_genes.empty()) { fprintf(stderr, "--quant-genes needs --quant\n"); return -1; }
   if (o.quant_genes.empty() && (!o.quant_gene_classes.empty() || !o.quant_gene_map.empty())) { fprintf(stderr, "--quant-gene-classes and --quant-gene-map need --quant-genes\n"); return -1; }
   if (!o.quant_boot_out.empty() && !o.quant_bootstraps) { fprintf(stderr, "--quant-boot-out needs --quant-bootstraps: without it there are no replicates\n"); return -1; }

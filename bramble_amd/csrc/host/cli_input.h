@@ -44,6 +44,10 @@ struct Options {
   long long quant_seed = 0;      // --quant-seed S: their seed (br_quant "boot_seed")
   bool quant_seed_given = false;
   std::string quant_boot_out;    // --quant-boot-out FILE: every replicate's NumReads per transcript
+  bool quant_vb = false;         // --quant-vb: the variational Bayes EM (br_quant "vb")
+  double quant_vb_prior = 1e-2;  // --quant-vb-prior P: its prior (br_quant_set_vb_prior; salmon's --vbPrior default)
+  bool quant_vb_prior_given = false;
+  bool quant_vb_per_nt = false;  // --quant-vb-per-nucleotide: the prior per nucleotide ("vb_per_nucleotide")
   std::string quant_genes, quant_gene_classes;   // --quant-genes FILE / --quant-gene-classes FILE: the gene-level table and the gene classes (br_quant_genes)
   std::string quant_gene_map;    // --quant-gene-map FILE: transcript<TAB>gene lines that replace the annotation's gene ids
   std::string coverage, coverage_summary;   // --coverage FILE / --coverage-summary FILE: the bedGraph of the depth along every transcript and the per-transcript table (br_coverage)

@@ -2,7 +2,8 @@
 // count the fragment lengths as well, "eff_len"); after the last bundle: classes, EM, and everything the three files need in one
 // download each -- the table, --quant-classes, --quant-fld; with --quant-bootstraps the replicates run behind the EM
 // (br_quant_bootstrap) and their summary joins the table, their values --quant-boot-out; with --quant-genes the gene tables are
-// made last (br_quant_genes on the numbers env.tx gives the genes) and go to --quant-genes and --quant-gene-classes.
+// made last (br_quant_genes on the numbers env.tx gives the genes) and go to --quant-genes and --quant-gene-classes; --quant-vb
+// turns the variational Bayes EM on ("vb") for all of them.
 #include "cli_output.h"
 
 namespace brcli {
@@ -20,6 +21,9 @@ class QuantOut : public Consumer {
     if (!rc && o.quant_eff_length) rc = br_quant_set_param(q, "eff_len", 1);
     if (!rc && o.quant_bootstraps) rc = br_quant_set_param(q, "bootstraps", o.quant_bootstraps);
     if (!rc && o.quant_bootstraps) rc = br_quant_set_param(q, "boot_seed", (int64_t)o.quant_seed);
+    if (!rc && o.quant_vb) rc = br_quant_set_param(q, "vb", 1);
+    if (!rc && o.quant_vb) rc = br_quant_set_vb_prior(q, o.quant_vb_prior);
+    if (!rc && o.quant_vb_per_nt) rc = br_quant_set_param(q, "vb_per_nucleotide", 1);
     if (!rc && o.coverage_weight == 2) rc = br_quant_set_param(q, "keep_names", 1);   // (the coverage consumer joins rows to classes by name)
     return rc;
   }
@@ -103,6 +107,11 @@ class QuantOut : public Consumer {
     if (env.o.quant_bootstraps)
       printf("[bramble] bootstrapped %d replicates (seed %lld, %lld iterations in all, sampling %.2fs, EM %.2fs)\n", env.o.quant_bootstraps, env.o.quant_seed,
              (long long)boot_iters, t_boot_sample, t_boot_em);
+    if (env.o.quant_vb) {
+      size_t at_zero = 0;
+      for (size_t t = 0; t < env.tx.len.size(); t++) at_zero += theta[t] <= 1e-8;
+      printf("[bramble] variational Bayes: prior %g per %s, %zu transcripts at zero\n", env.o.quant_vb_prior, env.o.quant_vb_per_nt ? "nucleotide" : "transcript", at_zero);
+    }
     if (!genes.path.empty()) printf("[bramble] gene level: %zu genes, %lld classes (%.2fs)\n", env.tx.gene_name.size(), (long long)n_gene_classes, t_genes);
     printf("[bramble] quantified %lld read names in %lld classes (%d iterations, add %.2fs, classes %.2fs, EM %.2fs)\n", (long long)n_names, (long long)n_classes,
            (int)n_iters, t_add, t_finish, t_em);

@@ -18,6 +18,10 @@
 //   em       per iteration a class kernel (q_c = n_c / sum over its labels of theta_t w_t) and a transcript kernel (theta'_t =
 //            theta_t w_t * sum of q_c over the transcript's classes, gathered through the transposed table); every 16th iteration
 //            and the last the transcript kernel also leaves the largest relative change in one word, which the host reads
+//   vb       ("vb") the class and transcript kernels as they are -- alpha in theta's place; the x they leave is replaced -- then three
+//            launches that make x from the new alpha: a partial of alpha + p per 256 transcripts, the partials summed in a fixed
+//            order by one block a replicate, which also takes psi(S), and a lane per (transcript, replicate) for
+//            exp(psi(alpha + p) - psi(S)) w.  The point EM runs them as a chunk of one replicate
 //   bootstrap B replicates in chunks of W (16 by default): a chunk's class counts are resampled when it starts (a lane a draw:
 //            Philox4x32-10 by (draw, replicate), a binary search in the scanned counts, an integer atomicAdd) and its EMs run
 //            together, replicate innermost in theta, theta w, q and the counts, so an index is read once for W replicates and a
@@ -61,6 +65,8 @@
 //                  while it runs, for a chunk of W replicates, 32 W T (theta and theta w twice) + 12 W C (q 8, the resampled
 //                  counts 4) + 512 bytes (the relative changes); br_quant_boot_counts 4 C a replicate of up to 16 at a time, the
 //                  summary 16 T
+//   "vb"           holds 8 T (p per transcript) from the first EM or bootstrap on, 8 bytes per 256 transcripts + 512 for the point EM's
+//                  partials of S and psi(S); a chunk of W replicates has W times the partials while it runs
 //   genes          (G genes, CG gene classes, LG gene labels, LE distinct (class, gene) entries, LG <= LE <= L) holds 24 CG (first
 //                  name, count, label_off) + 4 LG (labels) + 24 G (unique, ambiguous, the offsets of a gene's transcripts) + 4 T
 //                  (the transcripts by gene); while it runs 4 T (the map) + 32 L (keys 2 x 8, indices 2 x 4, the scanned heads
@@ -92,6 +98,8 @@ struct br_quant : Accum {
   int64_t fld_max = 1000;      // (salmon's fragLenDistMax)
   int64_t max_iters = 10000;
   double tolerance = 1e-2;
+  int vb = 0, vb_per_nt = 0;   // the variational Bayes EM, and its prior per nucleotide
+  double vb_prior = 1e-2;      // (salmon's vbPrior)
   bool finished = false, em_done = false;
   int64_t n = 0;               // names added
   uint64_t rows = 0;           // arena slots in use
@@ -109,6 +117,7 @@ struct br_quant : Accum {
   ColBuf name_cls;                                       // "keep_names": per name its class, from finish on
   ColBuf post;                                           // the posteriors, per label entry, once they were asked for after the EM
   ColBuf theta[2], x[2], w, qv;                          // em
+  ColBuf prior, vb_part, vb_psi;                         // "vb": p per transcript (held from the first EM or bootstrap on); the point EM's partials and psi(S)
   ColBuf fld_stage, fld_total, eff;                      // "eff_len": fld_max + 1 bins + Q_FLD_SIDE counters each (an add's, the run's); per transcript
   size_t fld_words() const { return (size_t)fld_max + 1 + Q_FLD_SIDE; }
   int fld_tables() {                                     // (zeroed once; a commit leaves the add's table zero again)
@@ -180,12 +189,20 @@ extern "C" int br_quant_set_param(br_quant *c, const char *name, int64_t value) 
   if (!strcmp(name, "keep_names")) { if ((value != 0 && value != 1) || fixed) return BR_ERR_INVALID_ARG; c->keep_names = (int)value; return BR_OK; }
   if (!strcmp(name, "fld_max")) { if (value < 1 || value > 65535 || fixed) return BR_ERR_INVALID_ARG; c->fld_max = value; return BR_OK; }
   if (!strcmp(name, "max_iters")) { if (value < 1) return BR_ERR_INVALID_ARG; c->max_iters = value; return BR_OK; }
+  if (!strcmp(name, "vb")) { if (value != 0 && value != 1) return BR_ERR_INVALID_ARG; c->vb = (int)value; return BR_OK; }
+  if (!strcmp(name, "vb_per_nucleotide")) { if (value != 0 && value != 1) return BR_ERR_INVALID_ARG; c->vb_per_nt = (int)value; return BR_OK; }
   if (!strcmp(name, "tolerance_ppm")) { if (value < 0) return BR_ERR_INVALID_ARG; c->tolerance = (double)value * 1e-6; return BR_OK; }
   return BR_ERR_INVALID_ARG;
 }
 extern "C" int br_quant_set_tolerance(br_quant *c, double tolerance) {
   if (!c || c->finished || !(tolerance >= 0.0)) return BR_ERR_INVALID_ARG;
   c->tolerance = tolerance;
+  return BR_OK;
+}
+
+extern "C" int br_quant_set_vb_prior(br_quant *c, double prior) {
+  if (!c || c->finished || !(prior >= 0.0) || !(prior <= 1.79769313486231570815e308)) return BR_ERR_INVALID_ARG;
+  c->vb_prior = prior;
   return BR_OK;
 }
 
@@ -569,6 +586,44 @@ static int quant_put_w(br_quant *c) {
   HIPCHK(hipStreamSynchronize(c->st));   // (w goes)
   return BR_OK;
 }
+// "vb": p per transcript on the device -- the prior, or per nucleotide the prior times eff (with "eff_len") or the length, 0 where
+// the length is <= 0 -- and the caller's checks: the prior per nucleotide needs lengths
+static bool quant_vb_ready(const br_quant *c) { return !(c->vb && c->vb_per_nt && c->lens.empty()); }
+static int quant_put_prior(br_quant *c) {
+  const size_t T = (size_t)c->n_tx;
+  RC(c->alloc(c->prior, (T + 1) * 8));
+  std::vector<double> p(T, c->vb_prior);
+  if (c->vb_per_nt) {
+    std::vector<double> eff;
+    if (c->eff_len && T) {
+      eff.resize(T);
+      HIPCHK(hipMemcpyAsync(eff.data(), c->eff.p, T * 8, hipMemcpyDeviceToHost, c->st));
+      HIPCHK(hipStreamSynchronize(c->st));
+    }
+    for (size_t t = 0; t < T; t++) p[t] = c->lens[t] > 0 ? c->vb_prior * (eff.empty() ? (double)c->lens[t] : eff[t]) : 0.0;
+  }
+  if (T) HIPCHK(hipMemcpyAsync(c->prior.p, p.data(), T * 8, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));   // (p goes)
+  return BR_OK;
+}
+// theta w of the last EM on the host, what the TPM is made of: the device's x, or after a variational run -- whose x is not
+// theta w -- the product made here (one rounding, as the device's)
+static int quant_host_x(br_quant *c, std::vector<double> &x) {
+  const size_t T = (size_t)c->n_tx;
+  x.resize(T);
+  if (!T) return BR_OK;
+  if (!c->vb) {
+    HIPCHK(hipMemcpyAsync(x.data(), c->x[c->cur].p, T * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return BR_OK;
+  }
+  std::vector<double> w(T);
+  HIPCHK(hipMemcpyAsync(x.data(), c->theta[c->cur].p, T * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(w.data(), c->w.p, T * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  for (size_t t = 0; t < T; t++) x[t] = x[t] * w[t];   // (built without contraction)
+  return BR_OK;
+}
 // the tables of the EM; q: a double per class (and replicate)
 static QEmArgs quant_em_args(const br_quant *c, double *q) {
   QEmArgs E{};
@@ -583,6 +638,7 @@ static QEmArgs quant_em_args(const br_quant *c, double *q) {
 extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
   if (!c || !c->finished) return BR_ERR_INVALID_ARG;
   if (c->eff_len && (!c->length_norm || c->lens.empty())) return BR_ERR_INVALID_ARG;   // effective lengths are a length normalisation
+  if (!quant_vb_ready(c)) return BR_ERR_INVALID_ARG;
   const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->st;
@@ -592,11 +648,17 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
   c->drop(c->post);   // (the posteriors of an earlier EM)
   for (int k = 0; k < 2; k++) { RC(c->alloc(c->theta[k], t1 * 8)); RC(c->alloc(c->x[k], t1 * 8)); }
   RC(quant_put_w(c)); RC(c->alloc(c->qv, (size_t)(C + 1) * 8));
+  if (c->vb) { RC(quant_put_prior(c)); RC(c->alloc(c->vb_part, (size_t)((T + 255) / 256 + 1) * 8)); RC(c->alloc(c->vb_psi, 64 * 8)); }
+  // "vb": x from alpha, after the transcript kernel and for alpha = 1 at the start (three launches more an iteration)
+  auto vb_x = [&](int k) {
+    if (c->vb) launch_q_vb_x(st, c->theta[k].as<double>(), c->prior.as<double>(), c->w.as<double>(), T, 0, 1ull, c->vb_part.as<double>(), c->vb_psi.as<double>(), c->x[k].as<double>());
+  };
   const std::vector<double> one((size_t)T, 1.0);
   if (T) {
     HIPCHK(hipMemcpyAsync(c->theta[0].p, one.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->x[0].p, c->w.p, (size_t)T * 8, hipMemcpyDeviceToDevice, st));   // theta w at theta = 1
   }
+  vb_x(0);
   const QEmArgs E = quant_em_args(c, c->qv.as<double>());
   unsigned long long *d_rel = (unsigned long long *)(c->small.as<uint64_t>() + QS_REL);
   int cur = 0;
@@ -609,6 +671,7 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
     launch_q_em_classes(st, E, c->x[cur].as<double>());
     launch_q_em_tx(st, E, c->theta[cur].as<double>(), c->x[cur].as<double>(), c->theta[cur ^ 1].as<double>(), c->x[cur ^ 1].as<double>(), look ? d_rel : nullptr);
     cur ^= 1;
+    vb_x(cur);
     if (!look) continue;
     uint64_t bits = 0;
     HIPCHK(hipMemcpyAsync(&bits, d_rel, 8, hipMemcpyDeviceToHost, st));
@@ -628,8 +691,8 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
 static int quant_post(br_quant *c) {
   if (c->post.p) return BR_OK;
   RC(c->alloc(c->post, (size_t)(c->cls.n_lab + 1) * 8));
-  launch_q_post(c->st, c->cls.loff.as<uint64_t>(), c->cls.labels.as<uint32_t>(), c->cls.n_cls, c->theta[c->cur].as<double>(), c->w.as<double>(),
-                c->post.as<double>());
+  launch_q_post(c->st, c->cls.loff.as<uint64_t>(), c->cls.labels.as<uint32_t>(), c->cls.n_cls, c->vb ? c->x[c->cur].as<double>() : c->theta[c->cur].as<double>(),
+                c->vb ? nullptr : c->w.as<double>(), c->post.as<double>());   // ("vb": x itself)
   HIPCHK(hipStreamSynchronize(c->st));
   return BR_OK;
 }
@@ -672,7 +735,7 @@ static int quant_boot_cum(br_quant *c) {
 }
 static bool quant_boot_ready(const br_quant *c) {
   if (!c || !c->finished || c->bootstraps == 0) return false;
-  return !(c->eff_len && (!c->length_norm || c->lens.empty()));   // (what br_quant_em refuses)
+  return !(c->eff_len && (!c->length_norm || c->lens.empty())) && quant_vb_ready(c);   // (what br_quant_em refuses)
 }
 
 extern "C" int br_quant_bootstrap(br_quant *c, int32_t *n_iters) {
@@ -689,10 +752,11 @@ extern "C" int br_quant_bootstrap(br_quant *c, int32_t *n_iters) {
   RC(quant_put_w(c));
   RC(quant_boot_cum(c));
   RC(c->alloc(c->boot_res, ((size_t)B * (size_t)T + 1) * 8));
-  ColBuf th[2], xx[2], q, cnt, d_rel;
-  DropGuard chunk_bufs{c, {&th[0], &th[1], &xx[0], &xx[1], &q, &cnt, &d_rel}};
+  ColBuf th[2], xx[2], q, cnt, d_rel, part, psi;
+  DropGuard chunk_bufs{c, {&th[0], &th[1], &xx[0], &xx[1], &q, &cnt, &d_rel, &part, &psi}};
   for (int k = 0; k < 2; k++) { RC(c->alloc(th[k], ((size_t)T * W + 1) * 8)); RC(c->alloc(xx[k], ((size_t)T * W + 1) * 8)); }
   RC(c->alloc(q, ((size_t)C * W + 1) * 8)); RC(c->alloc(cnt, ((size_t)C * W + 1) * 4)); RC(c->alloc(d_rel, 64 * 8));
+  if (c->vb) { RC(quant_put_prior(c)); RC(c->alloc(part, ((size_t)((T + 255) / 256) * W + 1) * 8)); RC(c->alloc(psi, 64 * 8)); }
   QBootArgs A{};
   A.E = quant_em_args(c, q.as<double>());
   A.E.cnt = nullptr;   // (a replicate's counts are its own: A.cnt)
@@ -710,6 +774,10 @@ extern "C" int br_quant_bootstrap(br_quant *c, int32_t *n_iters) {
     ScopeTimer timer(&c->boot_em_s);
     launch_q_boot_init(st, c->w.as<double>(), T, lw, th[0].as<double>(), xx[0].as<double>());
     A.active = n_rep >= 64 ? ~0ull : (1ull << n_rep) - 1ull;
+    auto vb_x = [&](int k) {   // as br_quant_em's, for the replicates that still run
+      if (c->vb) launch_q_vb_x(st, th[k].as<double>(), c->prior.as<double>(), c->w.as<double>(), T, lw, A.active, part.as<double>(), psi.as<double>(), xx[k].as<double>());
+    };
+    vb_x(0);
     int cur = 0;
     int64_t it = 0;
     while (A.active && it < c->max_iters) {
@@ -719,6 +787,7 @@ extern "C" int br_quant_bootstrap(br_quant *c, int32_t *n_iters) {
       launch_q_boot_classes(st, A, xx[cur].as<double>());
       launch_q_boot_tx(st, A, th[cur].as<double>(), xx[cur].as<double>(), th[cur ^ 1].as<double>(), xx[cur ^ 1].as<double>(), look ? rel : nullptr);
       cur ^= 1;
+      vb_x(cur);
       if (!look) continue;
       HIPCHK(hipMemcpyAsync(bits, rel, W * 8, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
@@ -812,7 +881,7 @@ extern "C" int br_quant_result(br_quant *c, double *theta, double *tpm, uint64_t
   if (!T) return BR_OK;
   std::vector<double> x;
   if (theta) HIPCHK(hipMemcpyAsync(theta, c->theta[c->cur].p, T * 8, hipMemcpyDeviceToHost, st));
-  if (tpm) { x.resize(T); HIPCHK(hipMemcpyAsync(x.data(), c->x[c->cur].p, T * 8, hipMemcpyDeviceToHost, st)); }
+  if (tpm) RC(quant_host_x(c, x));
   if (unique) HIPCHK(hipMemcpyAsync(unique, c->uniq.p, T * 8, hipMemcpyDeviceToHost, st));
   if (ambig) HIPCHK(hipMemcpyAsync(ambig, c->ambig.p, T * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -924,8 +993,7 @@ extern "C" int br_quant_gene_result(br_quant *c, double *num_reads, double *tpm,
     const bool has_lens = !c->lens.empty();
     RC(c->alloc(d_tpm, (T + 1) * 8)); RC(c->alloc(out, (4 * G + 1) * 8));
     if (has_lens) RC(c->alloc(d_lens, (T + 1) * 8));
-    if (T) HIPCHK(hipMemcpyAsync(x.data(), c->x[c->cur].p, T * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    RC(quant_host_x(c, x));
     quant_tpm(x, tpm_t.data());   // the values br_quant_result returns
     if (T) HIPCHK(hipMemcpyAsync(d_tpm.p, tpm_t.data(), T * 8, hipMemcpyHostToDevice, st));
     if (T && has_lens) HIPCHK(hipMemcpyAsync(d_lens.p, c->lens.data(), T * 8, hipMemcpyHostToDevice, st));
@@ -995,4 +1063,28 @@ extern "C" int br_quant_stats(const br_quant *c, uint64_t *held_bytes, uint64_t 
   if (n_unassigned) *n_unassigned = c->finished ? c->n - c->n_assigned : 0;
   if (n_labels) *n_labels = c->cls.n_lab;
   return BR_OK;
+}
+
+// test hook: the device's psi over n numbers in host memory
+extern "C" int br_quant_digamma(int device, const double *a, int64_t n, double *out) {
+  if (n < 0 || (n && (!a || !out))) return BR_ERR_INVALID_ARG;
+  Accum acc;
+  RC(acc.open(device));
+  ColBuf in, res;
+  int rc = BR_OK;
+  {
+    DropGuard dropper{&acc, {&in, &res}};
+    auto run = [&]() -> int {
+      if (!n) return BR_OK;
+      RC(acc.alloc(in, (size_t)n * 8)); RC(acc.alloc(res, (size_t)n * 8));
+      HIPCHK(hipMemcpyAsync(in.p, a, (size_t)n * 8, hipMemcpyHostToDevice, acc.st));
+      launch_q_digamma(acc.st, in.as<double>(), n, res.as<double>());
+      HIPCHK(hipMemcpyAsync(out, res.p, (size_t)n * 8, hipMemcpyDeviceToHost, acc.st));
+      HIPCHK(hipStreamSynchronize(acc.st));
+      return BR_OK;
+    };
+    rc = run();
+  }
+  acc.close();
+  return rc;
 }

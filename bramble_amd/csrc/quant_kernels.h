@@ -72,7 +72,7 @@ void launch_q_class_fill(hipStream_t st, const uint64_t *key, const uint32_t *va
 void launch_q_name_cls(hipStream_t st, const uint64_t *head, const uint32_t *idx, int64_t n, const uint32_t *val, int64_t n_cls, uint32_t *inv,
                        uint32_t *name_cls);
 // post[e] = theta_t w_t / d_c for label entry e of class c with transcript t, d_c the sum over the class's labels in ascending
-// order, one after the other (0 where d_c == 0)
+// order, one after the other (0 where d_c == 0).  w = NULL: theta is x itself (a variational run's), post[e] = x_t / d_c
 void launch_q_post(hipStream_t st, const uint64_t *label_off, const uint32_t *labels, int64_t n_cls, const double *theta, const double *w,
                    double *post);
 // one thread per label entry e: labels[e], its class, (transcript, e) for the transposed table; *bad |= 1 for a transcript
@@ -128,8 +128,17 @@ void launch_q_boot_store(hipStream_t st, const double *theta, int64_t n_tx, int 
 // mean and variance (over n_boot - 1; 0 for n_boot = 1) per transcript of the n_boot x n_tx result, summed in replicate order
 void launch_q_boot_summary(hipStream_t st, const double *res, int64_t n_tx, int32_t n_boot, double *mean, double *var);
 
+// Variational Bayes (definitions: bramble_amd.h, br_quant, `variational`), for the point EM (lw = 0, active = 1) and a chunk alike.
+// After launch_q_em_tx / launch_q_boot_tx have written theta (alpha'): x[t * W + j] = exp(psi(theta + prior[t]) - psi(S_j)) * w[t]
+// for every replicate j in `active`, S_j the sum of theta + prior over the transcripts -- per block of 256 transcripts a partial
+// (part: ceil(n_tx / 256) * W doubles), the partials in a fixed order (psi_s: W doubles), no atomics.  Three launches
+void launch_q_vb_x(hipStream_t st, const double *theta, const double *prior, const double *w, int64_t n_tx, int lw, uint64_t active, double *part,
+                   double *psi_s, double *x_out);
+// out[i] = the device's psi(a[i]) (NaN where a[i] is not a positive finite number)
+void launch_q_digamma(hipStream_t st, const double *a, int64_t n, double *out);
+
 // Gene level (definitions: bramble_amd.h, br_quant).
-// key[e] = (class of label entry e << 32) | tx_gene[labels[e]], idx[e] = e: to be sorted
+// key[e] =(class of label entry e << 32) | tx_gene[labels[e]], idx[e] = e: to be sorted
 void launch_qg_key(hipStream_t st, const uint64_t *label_off, const uint32_t *labels, const uint32_t *tx_gene, int64_t n_cls, int64_t n_lab,
                    uint64_t *key, uint32_t *idx);
 // flag[e] = sorted key e differs from key e - 1: a distinct (class, gene) entry (to be scanned)

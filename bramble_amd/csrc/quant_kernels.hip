@@ -11,6 +11,7 @@
 //   table    radix passes over (transcript, label entry) + k_q_transpose: per transcript its classes, ascending; k_q_bin;
 //            k_q_counts: unique / ambiguous names per transcript
 //   EM       k_q_em_classes / k_q_em_tx, a lane per item of up to Q_WAVE_ITEMS entries and a wave per larger one
+//   vb       k_q_vb_part / k_q_vb_sum / k_q_vb_x behind the EM's two kernels: x = exp(psi(alpha + p) - psi(S)) w, S without atomics
 //   bootstrap  k_q_boot_sample (a lane per draw: Philox4x32-10, a binary search in the scanned counts, an integer atomicAdd);
 //            k_q_boot_classes / k_q_boot_tx, the EM over a chunk of W replicates with the replicate innermost, a lane per (item,
 //            replicate) and a wave per larger item; k_q_boot_store, k_q_boot_summary
@@ -455,6 +456,11 @@ __global__ void __launch_bounds__(256) k_q_post(const uint64_t *label_off, const
   if (c >= n_cls) return;
   const uint64_t b = label_off[c], e = label_off[c + 1];
   double d = 0.0;
+  if (!w) {   // (theta is x itself: a variational run's)
+    for (uint64_t i = b; i < e; i++) d += theta[labels[i]];
+    for (uint64_t i = b; i < e; i++) post[i] = d == 0.0 ? 0.0 : theta[labels[i]] / d;
+    return;
+  }
   for (uint64_t i = b; i < e; i++) { const uint32_t t = labels[i]; d += theta[t] * w[t]; }
   for (uint64_t i = b; i < e; i++) { const uint32_t t = labels[i]; post[i] = d == 0.0 ? 0.0 : (theta[t] * w[t]) / d; }
 }
@@ -732,6 +738,97 @@ __global__ void __launch_bounds__(256) k_q_boot_summary(const double *res, int64
   double v = 0.0;
   for (int32_t b = 0; b < n_boot; b++) { const double d = res[(int64_t)b * n_tx + t] - m; v = __dadd_rn(v, __dmul_rn(d, d)); }
   mean[t] = m; var[t] = n_boot > 1 ? v / (double)(n_boot - 1) : 0.0;
+}
+
+// ---- variational Bayes (the definitions: bramble_amd.h, br_quant, paragraph `variational`) -------------------------------------------
+// An iteration is the EM's two kernels -- they read x and write alpha' = x * (sum of q); the x they write beside it is replaced --
+// and then x = exp(psi(alpha' + p) - psi(S)) * w, which needs S of the whole new alpha: k_q_vb_part (a partial per 256
+// transcripts), k_q_vb_sum (the partials in a fixed order, psi(S) once a replicate), k_q_vb_x (a lane per (transcript,
+// replicate)).  The point EM is a chunk of one replicate (lw = 0, active = 1).  No atomics: the shape of S depends on n_tx alone.
+namespace {
+// psi(a), a > 0: psi(a) = psi(a + 1) - 1 / a until the argument is 16 or more, then the asymptotic series through 1 / (132 a^10).
+// The trip count differs between lanes (0 for a transcript with 16 reads or more, 16 below 1); the body is one division and two adds
+__device__ __forceinline__ double q_digamma(double a) {
+  double r = 0.0;
+  while (a < 16.0) { r += 1.0 / a; a += 1.0; }
+  const double i = 1.0 / a, z = i * i;
+  const double tail = z * (1.0 / 12.0 - z * (1.0 / 120.0 - z * (1.0 / 252.0 - z * (1.0 / 240.0 - z * (1.0 / 132.0)))));
+  return ((log(a) - 0.5 * i) - tail) - r;
+}
+constexpr int Q_VB_SUB = 8;   // replicates a lane loads before it reduces them: 64 contiguous bytes of its transcript's row
+}  // namespace
+
+__global__ void __launch_bounds__(256) k_q_digamma(const double *a, int64_t n, double *out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double v = a[i];
+  out[i] = v > 0.0 && v <= 1.79769313486231570815e308 ? q_digamma(v) : __longlong_as_double(0x7ff8000000000000ll);   // (the recurrence ends only for these)
+}
+
+// part[b * W + j] = the sum of theta[t * W + j] + prior[t] over the transcripts t of block b = [256 b, 256 b + 256): a xor tree per
+// wave, then the four waves in order -- whatever W is, so a replicate's partials are the point run's
+__global__ void __launch_bounds__(256) k_q_vb_part(const double *theta, const double *prior, int64_t n_tx, int lw, uint64_t active, double *part) {
+  __shared__ double sh[64 * 4];
+  const int W = 1 << lw;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool in = t < n_tx;
+  const double p = in ? prior[t] : 0.0;
+  const double *row = theta + ((in ? t : 0) << lw);
+  for (int j0 = 0; j0 < W; j0 += Q_VB_SUB) {
+    if (((active >> j0) & ((1ull << Q_VB_SUB) - 1ull)) == 0) continue;   // (block-uniform)
+    double v[Q_VB_SUB];
+#pragma unroll
+    for (int k = 0; k < Q_VB_SUB; k++) v[k] = in && j0 + k < W ? row[j0 + k] + p : 0.0;
+#pragma unroll
+    for (int k = 0; k < Q_VB_SUB; k++) {
+      const double s = wave_sum(v[k]);
+      if ((threadIdx.x & 63) == 0 && j0 + k < W) sh[(j0 + k) * 4 + (threadIdx.x >> 6)] = s;
+    }
+  }
+  __syncthreads();
+  const int j = threadIdx.x;
+  if (j < W && ((active >> j) & 1ull)) part[(int64_t)blockIdx.x * W + j] = ((sh[j * 4] + sh[j * 4 + 1]) + sh[j * 4 + 2]) + sh[j * 4 + 3];
+}
+
+// block j: S of replicate j from its n_part partials -- thread i adds partials i, i + 256, ... in ascending order, then the block
+// sum of k_q_vb_part -- and psi_s[j] = psi(S) (0 where S is 0: every A is 0 then, and no x reads it)
+__global__ void __launch_bounds__(256) k_q_vb_sum(const double *part, int64_t n_part, int lw, uint64_t active, double *psi_s) {
+  __shared__ double sh[4];
+  const int j = blockIdx.x;
+  if (!((active >> j) & 1ull)) return;   // (block-uniform)
+  double s = 0.0;
+  for (int64_t b = threadIdx.x; b < n_part; b += 256) s += part[(b << lw) + j];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double S = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    psi_s[j] = S > 0.0 ? q_digamma(S) : 0.0;
+  }
+}
+
+// x[t * W + j] = exp(psi(A) - psi(S_j)) * w[t] with A = theta[t * W + j] + prior[t], 0 where A <= 1e-10 (salmon's digammaMin); a
+// frozen replicate keeps the x the transcript kernel copied through
+__global__ void __launch_bounds__(256) k_q_vb_x(const double *theta, const double *prior, const double *w, int64_t n_tx, int lw, uint64_t active,
+                                                const double *psi_s, double *x_out) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t t = g >> lw;
+  const int j = (int)(g & (int64_t)((1 << lw) - 1));
+  if (t >= n_tx || !((active >> j) & 1ull)) return;
+  const double A = theta[g] + prior[t];
+  x_out[g] = A > 1e-10 ? exp(q_digamma(A) - psi_s[j]) * w[t] : 0.0;
+}
+
+void launch_q_digamma(hipStream_t st, const double *a, int64_t n, double *out) {
+  if (n > 0) hipLaunchKernelGGL(k_q_digamma, dim3(blocks256(n)), dim3(256), 0, st, a, n, out);
+}
+void launch_q_vb_x(hipStream_t st, const double *theta, const double *prior, const double *w, int64_t n_tx, int lw, uint64_t active, double *part,
+                   double *psi_s, double *x_out) {
+  if (n_tx <= 0 || !active) return;
+  const int64_t n_part = (n_tx + 255) / 256;
+  hipLaunchKernelGGL(k_q_vb_part, dim3((unsigned)n_part), dim3(256), 0, st, theta, prior, n_tx, lw, active, part);
+  hipLaunchKernelGGL(k_q_vb_sum, dim3(1u << lw), dim3(256), 0, st, (const double *)part, n_part, lw, active, psi_s);
+  hipLaunchKernelGGL(k_q_vb_x, dim3(blocks256(n_tx << lw)), dim3(256), 0, st, theta, prior, w, n_tx, lw, active, (const double *)psi_s, x_out);
 }
 
 // ---- gene level (the definitions: bramble_amd.h, br_quant) -------------------------------------------------------------------------

@@ -177,7 +177,7 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_collator_stats", "br_collator_free",
            "br_sorter_new", "br_sorter_set_param", "br_sorter_add", "br_sorter_finish", "br_sorter_next", "br_sorter_order", "br_sorter_stats",
            "br_sorter_index", "br_sorter_free", "br_ctx_last_device_bam", "br_device_bam_download",
-           "br_quant_new", "br_quant_set_param", "br_quant_set_tolerance", "br_quant_add", "br_quant_add_rows", "br_quant_add_last", "br_quant_finish",
+           "br_quant_new", "br_quant_set_param", "br_quant_set_tolerance", "br_quant_set_vb_prior", "br_quant_digamma", "br_quant_add", "br_quant_add_rows", "br_quant_add_last", "br_quant_finish",
            "br_quant_classes", "br_quant_em", "br_quant_result", "br_quant_fld", "br_quant_eff_lengths", "br_quant_stats", "br_quant_free",
            "br_quant_bootstrap", "br_quant_boot_counts", "br_quant_boot_theta", "br_quant_boot_summary", "br_quant_boot_stats",
            "br_quant_genes", "br_quant_gene_classes", "br_quant_gene_result", "br_quant_gene_boot", "br_quant_gene_boot_summary", "br_quant_gene_stats",
@@ -1212,7 +1212,7 @@ class Quant(_Accumulator):
 
     NAME = "quant"
     ARGTYPES = {"new": [C.c_int, C.c_int64, C.c_void_p, _P(C.c_void_p)], "set_param": [C.c_void_p, C.c_char_p, C.c_int64],
-                "set_tolerance": [C.c_void_p, C.c_double],
+                "set_tolerance": [C.c_void_p, C.c_double], "set_vb_prior": [C.c_void_p, C.c_double],
                 "add": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p],
                 "add_rows": [C.c_void_p, _P(BrDeviceRows), C.c_void_p, C.c_int64, C.c_int, C.c_void_p], "add_last": [C.c_void_p, C.c_void_p],
                 "fld": [C.c_void_p, C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)], "eff_lengths": [C.c_void_p, C.c_void_p],
@@ -1230,7 +1230,7 @@ class Quant(_Accumulator):
                 "gene_stats": [C.c_void_p, _P(C.c_double), _P(C.c_int64), _P(C.c_uint64)],
                 "name_classes": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p], "posteriors": [C.c_void_p, C.c_void_p]}
 
-    def __init__(self, n_transcripts, lengths=None, device=0):
+    def __init__(self, n_transcripts, lengths=None, device=0, vb=None, vb_prior=None, vb_per_nucleotide=None):
         self.n_transcripts = int(n_transcripts)
         self.n_names = self.n_classes = 0
         self.n_genes = self.n_gene_classes = 0
@@ -1242,12 +1242,17 @@ class Quant(_Accumulator):
         self._open(device, self.n_transcripts, lens.ctypes.data if lens is not None else None)
         if lens is None:
             self.set_param("length_norm", 0)
+        for name, value in (("vb", vb), ("vb_prior", vb_prior), ("vb_per_nucleotide", vb_per_nucleotide)):
+            if value is not None:
+                self.set_param(name, value)
 
     def set_param(self, name, value):
-        """"hash_bits", "length_norm", "max_iters", "eff_len", "fld_max", "keep_names", "bootstraps", "boot_seed" (the bits of an int64: a seed
+        """"vb", "vb_per_nucleotide" (0 / 1: the variational Bayes EM and its prior per nucleotide), "vb_prior" (a float), "hash_bits", "length_norm", "max_iters", "eff_len", "fld_max", "keep_names", "bootstraps", "boot_seed" (the bits of an int64: a seed
         of 2^63 or more is taken modulo 2^64), "boot_chunk" (integers) or "tolerance" (a float)."""
         if name == "tolerance":
             self._call("set_tolerance", float(value))
+        elif name == "vb_prior":
+            self._call("set_vb_prior", float(value))
         else:
             if name == "boot_seed":
                 value = C.c_int64(int(value) & 0xffffffffffffffff).value
@@ -1466,6 +1471,16 @@ class Quant(_Accumulator):
         self._call("stats", C.byref(h), C.byref(p), C.byref(ad), C.byref(fi), C.byref(em), C.byref(co), C.byref(un), C.byref(nl))
         return {"held_bytes": int(h.value), "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value, "em_s": em.value,
                 "collisions": int(co.value), "n_unassigned": int(un.value), "n_labels": int(nl.value)}
+
+
+def quant_digamma(a, device=0):
+    """br_quant_digamma: the device's psi (br_quant's `psi`) over a float64 array -> an array of its shape"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    out = np.zeros(max(a.size, 1), dtype=np.float64)
+    L = lib()
+    L.br_quant_digamma.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    check(L.br_quant_digamma(int(device), a.ctypes.data if a.size else None, a.size, out.ctypes.data), "br_quant_digamma")
+    return out[:a.size].reshape(a.shape)
 
 
 class Coverage(_Accumulator):

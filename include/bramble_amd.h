@@ -721,6 +721,34 @@ void br_sorter_free(br_sorter *);
  *                  class's labels in ascending order, one after the other whatever their number (no wave tree); p[e] = x_t / d_c,
  *                  and 0 where d_c == 0.  float64, no fused multiply-add, one rounding per operation: a restatement in the same
  *                  order gives the same bits.  A class of one label has p = 1.0
+ *   variational    ("vb" = 1; salmon's default estimator, the variational Bayes EM with a Dirichlet prior.  With "vb" = 0, the
+ *                  default, nothing below applies and every result has the bits it had.)  The prior is br_quant_set_vb_prior's,
+ *                  finite and >= 0, default 1e-2 (salmon's --vbPrior).  Per transcript p_t = prior; with "vb_per_nucleotide" = 1
+ *                  p_t = prior * eff_t when "eff_len" is on, else prior * (double)L_t, and 0 where L_t <= 0.  The state is alpha
+ *                  in theta's place: alpha_t = 1 at the start, and the theta br_quant_result returns is the final alpha, without
+ *                  the prior (NumReads).  One iteration: A_t = alpha_t + p_t; S = the sum of A_t over all transcripts; e_t =
+ *                  exp(psi(A_t) - psi(S)) when A_t > 1e-10 (salmon's digammaMin), else 0; x_t = e_t * w_t with the EM's w; d_c =
+ *                  the sum of x_t over the class's labels; alpha'_t = x_t * the sum over the classes that hold t of n_c / d_c (a
+ *                  class with d_c == 0 contributes nothing).  Stopping: the EM's rule, unchanged, on alpha.  TPM_t = 1e6 alpha_t
+ *                  w_t / sum of alpha w.  The posteriors after a variational run take this x_t, made from the final alpha, in
+ *                  place of theta_t w_t; br_coverage_finish_em reads them unchanged.  The replicate EM is this iteration with
+ *                  n_c^(b), every replicate with its own S and its own stopping, frozen as `replicate EM` says.  Gene values are
+ *                  sums of transcript values as before
+ *   psi            (digamma, for a positive argument.)  psi(a) = psi(a + 1) - 1 / a until the argument is 16 or more (the
+ *                  threshold is 16; the series then needs no 1 / a^12 term), then ln a - 1/(2a) - 1/(12a^2) + 1/(120a^4) -
+ *                  1/(252a^6) + 1/(240a^8) - 1/(132a^10).  Against a float64 library digamma the restatement of this series is
+ *                  within 1.4e-15 of max(1, |psi|) over [1e-10, 1e9]
+ *   vb numerics    float64, no fused multiply-add, no floating-point atomics.  S is summed in a shape that depends on
+ *                  n_transcripts alone: the A_t of transcripts 256 b .. 256 b + 255 make partial b (a xor tree over each 64, the
+ *                  four results added in order), thread i of one block adds partials i, i + 256, ... in ascending order and the
+ *                  same block sum closes it -- in the point run and, per replicate, in a chunk of any width.  So two runs give
+ *                  the same bits and a replicate's bits do not depend on "boot_chunk".  Bit-equality with a CPU restatement
+ *                  is not claimed for "vb" = 1: the device's log and exp are not libm's
+ *   vb caveat      the iteration sits at an unstable fixed point for transcripts the data cannot tell apart (the same classes
+ *                  with the same counts, the same w): rounding decides which of them takes the reads -- two transcripts with
+ *                  mirrored classes of 154 / 154 / 2 names end at 1.52 / 1.52 reads under one summation order and at 0 / 3.45
+ *                  under another.  The device's result is the same bits in every run, but no more meaningful there than
+ *                  salmon's; the plain EM keeps such transcripts equal
  *   name classes   ("keep_names" = 1.)  name_cls[i] = the index, in the classes' order, of the class add-order name i fell into,
  *                  0xffffffff for a name without rows; at any "hash_bits"
  *   br_quant_new        lengths: n_transcripts transcript lengths, or NULL (then "length_norm" must be 0).  BR_ERR_NO_DEVICE
@@ -730,7 +758,9 @@ void br_sorter_free(br_sorter *);
  *                       (tolerance in millionths; br_quant_set_tolerance takes the double itself); before the first add only, a
  *                       refused one with "eff_len" on included (the histogram is sized by then):
  *                       "eff_len" 0 / 1 (default 0: the fragment-length model above), "fld_max" 1 .. 65535 (default 1000, salmon's
- *                       fragLenDistMax), "keep_names" 0 / 1 (default 0: finish leaves every name's class on the device)
+ *                       fragLenDistMax), "keep_names" 0 / 1 (default 0: finish leaves every name's class on the device); before
+ *                       finish, as "max_iters": "vb" 0 / 1 (default 0) and "vb_per_nucleotide" 0 / 1 (default 0), see `variational`
+ *   br_quant_set_vb_prior  the prior of `variational`, before finish; BR_ERR_INVALID_ARG for a negative or non-finite one
  *   br_quant_add        the read names group_off[0 .. n_groups] of a batch: a / row_off / group_off as br_device_rows and
  *                       br_device_batch hold them (device memory with on_device != 0, read after the work queued on `stream`, NULL
  *                       for the null stream; host memory with on_device = 0).  Returns when the tables have been read.
@@ -747,7 +777,7 @@ void br_sorter_free(br_sorter *);
  *   br_quant_classes    host copies: label_off (n_classes + 1), labels (label_off[n_classes]), counts, first_name (the add-order
  *                       index of the class's first read name); any pointer may be NULL
  *   br_quant_em         the EM, after finish; the iterations run and the last relative change looked at.  BR_ERR_INVALID_ARG with
- *                       "eff_len" on and "length_norm" off, or without lengths
+ *                       "eff_len" on and "length_norm" off, or without lengths; with "vb" and "vb_per_nucleotide" on and no lengths
  *   br_quant_fld        host copies, any may be NULL: hist ("fld_max" + 1 entries) and the three counters, of the adds so far
  *   br_quant_eff_lengths  eff, n_transcripts doubles; after finish, with "eff_len" on and lengths given
  *   br_quant_result     host copies, n_transcripts each, any may be NULL: theta and tpm (after em), unique and ambig (after finish)
@@ -782,17 +812,21 @@ void br_sorter_free(br_sorter *);
  *   br_quant_posteriors the n_labels posteriors, parallel to the labels of br_quant_classes; after br_quant_em.  post may be NULL: the
  *                       table is then only made and held on the device (br_coverage_finish_em reads it there).  A later br_quant_em
  *                       drops it
+ *   br_quant_digamma    test hook: out[i] = the device's psi(a[i]) for n numbers in host memory (NaN where a[i] is not positive
+ *                       and finite); BR_ERR_NO_DEVICE without the device
  * Device memory: 4 bytes a row and 20 bytes a read name while adding; finish peaks at 32 more a name with labels, then holds 24
  * bytes a class, 8 a label and 24 a transcript; the EM adds 40 a transcript and 8 a class; "eff_len" adds 16 (fld_max + 4) for the
  * histogram (the run's and an add's own), 16 (fld_max + 1) for the prefixes during finish and 8 a transcript for eff; the bootstrap
  * holds 8 B a transcript (the result) and 8 a class (cum), and while it runs, for a chunk of W replicates (16 by default), 32 W a
  * transcript and 12 W a class, the summary 16 a transcript; br_quant_genes holds 24 bytes a gene class, 4 a gene label, 24 a gene and
  * 4 a transcript, peaks at 32 a label and 4 a transcript beside them, and the gene replicates add 8 B a gene; "keep_names" holds 4
- * bytes a name from finish on (and 4 a class more while the classes are made), the posteriors 8 a label (quant.cpp). */
+ * bytes a name from finish on (and 4 a class more while the classes are made), the posteriors 8 a label; "vb" holds 8 a transcript more (p) and
+ * 8 bytes per 256 transcripts for the partials of S, times W while a chunk runs (quant.cpp). */
 typedef struct br_quant br_quant;
 int br_quant_new(int device, int64_t n_transcripts, const int64_t *lengths, br_quant **out);
 int br_quant_set_param(br_quant *, const char *name, int64_t value);
 int br_quant_set_tolerance(br_quant *, double tolerance);
+int br_quant_set_vb_prior(br_quant *, double prior);
 int br_quant_add(br_quant *, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t n_groups, int on_device,
                  void *stream);
 int br_quant_add_rows(br_quant *, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups, int on_device, void *stream);
@@ -819,6 +853,7 @@ int br_quant_gene_boot_summary(br_quant *, double *mean, double *var);
 int br_quant_gene_stats(const br_quant *, double *seconds, int64_t *n_gene_labels, uint64_t *collisions);
 int br_quant_name_classes(br_quant *, int64_t first, int64_t n, uint32_t *cls);
 int br_quant_posteriors(br_quant *, double *post);
+int br_quant_digamma(int device, const double *a, int64_t n, double *out);
 void br_quant_free(br_quant *);
 
 /* Coverage: the depth of coverage along every transcript, from the rows of a whole run, in one device's HBM (coverage.cpp,
