@@ -451,6 +451,9 @@ extern "C" int br_ctx_set_param(br_ctx *c, const char *key, int64_t v) {
   if (!strcmp(key, "host_detail")) { c->host_detail = v != 0; return BR_OK; }
   if (!strcmp(key, "split_spoil")) { if (v < 0 || v > 1000000) return BR_ERR_INVALID_ARG; c->split_spoil = (int)v; return BR_OK; }   // test hook, see split_impl
   if (!strcmp(key, "side_cap")) { if (v < 64) return BR_ERR_INVALID_ARG; c->d_side_cap = (uint64_t)v; return BR_OK; }   // test hook: the side arena's first capacity (entries), see run_device_direct
+  // the records without an output record are kept (br_ctx_unprojected_*): 1 per record, 2 per read name; not while some are held
+  if (!strcmp(key, "keep_unprojected")) { if (v < 0 || v > 2 || (c->un.n && v != c->un.keep)) return BR_ERR_INVALID_ARG; c->un.keep = (int)v; return BR_OK; }
+  if (!strcmp(key, "unprojected_cap")) { if (v < 0) return BR_ERR_INVALID_ARG; c->un.first_cap = (uint64_t)v; return BR_OK; }   // test hook: their arena's first capacity (bytes)
   if (!strcmp(key, "blocks_per_cu")) { if (v < 1 || v > 64) return BR_ERR_INVALID_ARG; c->blocks_per_cu = (int)v; return BR_OK; }
   return BR_ERR_INVALID_ARG;
 }

@@ -10,9 +10,10 @@
 #include "ctx.h"
 
 // aux_done: k_bam_scan already ran over these records with the same configuration
-// (br_project_bam_device); keep_events: append to the running event list instead of restarting it
+// (br_project_bam_device); keep_events: append to the running event list instead of restarting it; group_off / n_groups: the
+// bundle's read-name groups (br_project_bam_device), for the unprojected records ("keep_unprojected"), else NULL
 static int bam_encode_impl(br_ctx *c, const br_config *cfg, const br_device_records *recs, hipStream_t st,
-                           br_device_bam *out, bool aux_done, bool keep_events) {
+                           br_device_bam *out, bool aux_done, bool keep_events, const uint32_t *group_off = nullptr, int64_t n_groups = 0) {
   memset(out, 0, sizeof(*out));
   if (recs->n_aln != c->last_n_aln) return BR_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->ix->device));
@@ -48,6 +49,10 @@ static int bam_encode_impl(br_ctx *c, const br_config *cfg, const br_device_reco
   RC(pf.begin(BR_K_SCAN));
   launch_scan(st, B.out_len, nr, c->tile_sums.as<uint64_t>(), c->bam_off.p, true, d_tot + TOT_BAM_BYTES);
   RC(pf.end());
+  // the records without an output row: measured here, so that their totals come home with the encoder's size
+  const bool unproj = group_off && c->un.keep;
+  UnprojArgs U{};
+  if (unproj) RC(unproj_measure(c, st, pf, B, group_off, n_groups, U));
   HIPCHK(hipMemcpyAsync(c->rb->bam, d_tot + TOT_BAM_LONG, 16, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   // (bam[0], "a spilled CIGAR spans 2^28 reference bases or more", is set by the encoder: checked after it)
@@ -57,10 +62,12 @@ static int bam_encode_impl(br_ctx *c, const br_config *cfg, const br_device_reco
   RC(pf.begin(BR_K_BAM));
   launch_bam_encode(st, B, c->bam_lanes);
   RC(pf.end());
+  if (unproj) RC(unproj_gather(c, st, pf, U));   // complete at the synchronise below: the caller may release the input then
   HIPCHK(hipMemcpyAsync(c->rb->bam, d_tot + TOT_BAM_LONG, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (nr && c->rb->bam[0]) { pf.collect(); return BR_ERR_UNSUPPORTED; }  // bam_write1 refuses such a record too
   RC(pf.collect());
+  if (unproj) unproj_commit(c, U);
   out->data = c->bam_out.as<uint8_t>(); out->n_bytes = total; out->row_off = c->bam_off.as<uint64_t>();
   return BR_OK;
 }
@@ -188,7 +195,7 @@ extern "C" int br_project_bam_device(br_ctx *c, const br_config *cfg, const br_d
   db.n_cigar_words = (int64_t)n_words; db.max_n_cigar = (int32_t)max_nc;
   db.name_off = P.name_off; db.names = P.names;
   { WantDetail wd(c, true); RC(run_device(c, cfg, &db, st, rows, true)); }   // the encoder reads input alignment and HI of every row
-  RC(bam_encode_impl(c, cfg, recs, st, out, true, true));
+  RC(bam_encode_impl(c, cfg, recs, st, out, true, true, P.group_off, (int64_t)ng));
   return BR_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "device_types.h"
 #include "devmem.h"
 #include "kernels.h"
+#include "unprojected_kernels.h"
 
 using namespace br;
 
@@ -55,14 +56,29 @@ struct ReadBack {
   uint64_t parse_max;                     // max n_cigar | max soft clip << 32
   uint64_t bam[2];                        // the encoder: a record it cannot write, the records' bytes (TOT_BAM_LONG, TOT_BAM_BYTES)
   uint64_t deflate_total;                 // compressed bytes of a BGZF call
+  uint64_t unproj[UNPROJ_SMALL_N];        // the unprojected records of a call: bytes, records, names without / with some record projected
   // flat batches (host_rows.cpp)
   uint64_t host_groups, host_max, host_pool;   // read-name groups, max n_cigar | max soft clip << 32, dense pool words
   // SAM text out (sam_writer.cpp)
   uint64_t sam_bad, sam_bytes;            // the first record the text cannot say (~0: none), the text's bytes
 };
 
+// The input records of the bundle calls that got no output record, kept in HBM until drawn (unprojected.cpp).
+struct Unprojected {
+  int keep = 0;                 // "keep_unprojected": 0 off, 1 scope record, 2 scope name
+  uint64_t first_cap = 0;       // "unprojected_cap": the arena's first capacity in bytes (a test hook)
+  ColBuf arena, off;            // [block_size][record]... in input order; off: n + 1 offsets, the last one = used
+  ColBuf old_arena, old_off;    // what a growing call replaced: freed behind that call's last synchronise
+  uint64_t used = 0; int64_t n = 0, cur = 0;   // arena bytes and records held; the next record br_ctx_unprojected_next hands out
+  uint64_t stats[6] = {0, 0, 0, 0, 0, 0};     // br_ctx_unprojected_stats [0..5]
+  uint64_t live = 0, peak = 0;  // device bytes of the arenas now / at most
+  DevBuf flag, len, one, out_off, rank, small, piece_rows;   // a call's tables; the row_off of the last piece
+  void drop(ColBuf &b) { live -= b.cap; b.release(); }
+};
+
 struct br_ctx {
   const br_index *ix = nullptr;
+  Unprojected un;
   int group_lanes = 8;
   int bam_lanes = 0;   // 0: k_bam_tasks (a wave per 32 rows); 4..64: k_bam_encode<G>, G lanes per row
   int blocks_per_cu = 8;
@@ -268,3 +284,9 @@ int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStr
 int ensure_detail(br_ctx *c, hipStream_t st);
 int expand_rows(br_ctx *c, hipStream_t st, br_device_wide_rows *out);
 int sam_format_impl(br_ctx *c, const br_device_bam *in, hipStream_t st, const uint8_t **text, uint64_t *n_bytes);
+// The unprojected records of a bundle call (unprojected.cpp), in three steps around the encoder's two waits: the kernels up to
+// the scans and the copy of their totals into rb->unproj, queued in front of the wait for the encoder's size; the gather into
+// the arena, queued beside the encoder once those totals are home; the bookkeeping behind the call's last synchronise.
+int unproj_measure(br_ctx *c, hipStream_t st, Prof &pf, const BamArgs &B, const uint32_t *group_off, int64_t n_groups, UnprojArgs &U);
+int unproj_gather(br_ctx *c, hipStream_t st, Prof &pf, UnprojArgs &U);
+void unproj_commit(br_ctx *c, const UnprojArgs &U);

@@ -7,7 +7,7 @@
 //   uploader      : br_bam_bundle_stage (host bundles: records to one of three device slots, own copy stream)
 //   runner        : br_project_bam_staged_nowait / br_project_bam_resident (everything between the raw records on the device)
 //   writer thread : BGZF deflate (threaded) -> output file; device-made BGZF blocks or SAM lines (-O sam) go out as they are
-//   consumers     : what else takes something from every projected bundle -- --sort, --quant, --coverage (cli_output.h: one consumer
+//   consumers     : what else takes something from every projected bundle -- --sort, --quant, --coverage, --unprojected (cli_output.h: one consumer
 //                   per feature).  The runner hands each bundle to every consumer right after its projection call; after the last
 //                   bundle each finishes on the device, writes its files under temporary names and prints its report line.  One of
 //                   them may keep the records (--sort): then the projection leaves them in HBM (BR_OUT_RESIDENT), nothing of a
@@ -51,7 +51,8 @@ void usage(FILE *f) {
           "                [--quant-vb [--quant-vb-prior P] [--quant-vb-per-nucleotide]]\n"
           "                [--quant-genes <genes.tsv> [--quant-gene-classes <gene_classes.txt>] [--quant-gene-map <tx2gene.tsv>]]]\n"
           "               [--coverage <cov.bedgraph>] [--coverage-summary <cov.tsv>] [--coverage-primary]\n"
-          "               [--coverage-weight unit|nh|em]\n\n"
+          "               [--coverage-weight unit|nh|em]\n"
+          "               [--unprojected <unprojected.bam> [--unprojected-scope record|name]]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -110,7 +111,13 @@ void usage(FILE *f) {
           "of (read name, transcript) under the abundances --quant estimates (it needs --quant) -- the expected depth.  The depth is\n"
           "fixed point, 32 fractional bits: the bedGraph's depth is printed with %%.10g, and the summary has the columns Name, Length,\n"
           "Records, WeightedRecords, AlignedBases, CoveredBases, MaxDepth, MeanDepth, Breadth.  The report line becomes\n"
-          "[bramble] coverage (weight nh|em): ...\n");
+          "[bramble] coverage (weight nh|em): ...\n"
+          "--unprojected FILE: the input records that no output record came from -- no transcript accepted them, or their matches died\n"
+          "at pairing -- written to FILE on the way: a BAM (whatever -O says) under the input's header, the records byte for byte as\n"
+          "they came in, in input order.  They are picked out and kept on one GPU while the bundles are projected.  Unmapped input\n"
+          "records are not among them.  --unprojected-scope record (the default): every such record; name: only the records of read\n"
+          "names of which no record was projected (the mate of a half-projected pair stays out).  One more line in front of the final\n"
+          "report: [bramble] unprojected: R of N records written (W read names without a projected record, P partly projected; scope record|name)\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -119,7 +126,7 @@ int parse_args(int argc, char **argv, Options &o) {
   memset(&o.cfg, 0, sizeof(o.cfg));
   o.cfg.junc_miss_discount = 1.0;
   bool codec = false, host_codec = false;   // a BGZF codec option was given; one that asks for the host codec
-  bool coverage_weight_given = false;
+  bool coverage_weight_given = false, unprojected_scope_given = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "%s: missing value\n", argv[i]); return nullptr; } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -202,6 +209,14 @@ int parse_args(int argc, char **argv, Options &o) {
       else { fprintf(stderr, "--coverage-weight: unknown weight %s (unit, nh or em)\n", v); return -1; }
       coverage_weight_given = true;
     }
+    else if (a == "--unprojected") { const char *v = value(); if (!v) return -1; o.unprojected = v; }
+    else if (a == "--unprojected-scope") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "record") o.unprojected_scope = 1; else if (w == "name") o.unprojected_scope = 2;
+      else { fprintf(stderr, "--unprojected-scope: unknown scope %s (record or name)\n", v); return -1; }
+      unprojected_scope_given = true;
+    }
     else if (a == "--device") { const char *v = value(); if (!v) return -1; o.devices.assign(1, atoi(v)); }
     else if (a == "--devices") {
       const char *v = value(); if (!v) return -1;
@@ -237,6 +252,9 @@ int parse_args(int argc, char **argv, Options &o) {
   if (coverage_weight_given && o.coverage.empty() && o.coverage_summary.empty()) { fprintf(stderr, "--coverage-weight needs --coverage or --coverage-summary\n"); return -1; }
   if (o.coverage_weight == 2 && o.quant.empty()) { fprintf(stderr, "--coverage-weight em needs --quant: the weights are the EM's posteriors\n"); return -1; }
   if ((!o.coverage.empty() || !o.coverage_summary.empty()) && o.devices.size() > 1) { fprintf(stderr, "--coverage works on one device: give --device N, not a --devices list\n"); return -1; }
+  if (unprojected_scope_given && o.unprojected.empty()) { fprintf(stderr, "--unprojected-scope needs --unprojected\n"); return -1; }
+  if (o.unprojected == "-") { fprintf(stderr, "--unprojected needs a file, not standard output: that is the main output's\n"); return -1; }
+  if (!o.unprojected.empty() && o.devices.size() > 1) { fprintf(stderr, "--unprojected works on one device: give --device N, not a --devices list\n"); return -1; }
   if (o.write_index && !o.sort) { fprintf(stderr, "--write-index needs --sort: a BAI index describes a coordinate-sorted file\n"); return -1; }
   if (o.write_index && o.sam_out) { fprintf(stderr, "--write-index applies to BAM output, not to --output-fmt sam\n"); return -1; }
   if (o.write_index && o.out_bam == "-") { fprintf(stderr, "--write-index needs an output file, not standard output\n"); return -1; }
@@ -684,7 +702,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
   for (size_t r = 0; r < hdr.ref_names.size(); r++) { auto it = ref_of.find(hdr.ref_names[r]); ref_map[r] = it != ref_of.end() ? it->second : extra++; }
   // every transcript's name and length, once: a line of a file, an RNAME, a BAI bin belong to the @SQ list, the transcripts of
   // length > 0 in index order (what make_bam_header writes)
-  RunEnv env{o, o.devices[0], {}};
+  RunEnv env{o, o.devices[0], {}, hdr};
   for (size_t t = 0, nt = br_index_num_transcripts(ix0); t < nt; t++) {
     env.tx.name.push_back(br_index_transcript_name(ix0, (uint32_t)t));
     env.tx.len.push_back(br_index_transcript_len(ix0, (uint32_t)t));
@@ -703,6 +721,10 @@ extern "C" int br_cli_main(int argc, char **argv) {
       int src = br_ctx_set_sam_refs(w->ctx, sq.data(), (int32_t)sq.size());
       if (src) { fprintf(stderr, "error: reference names on device %d: %s\n", w->device, br_strerror(src)); return give_up(); }
     }
+  }
+  if (!o.unprojected.empty()) {   // (one device: the records stay in worker 0's context until the consumer draws them)
+    const int urc = br_ctx_set_param(workers[0]->ctx, "keep_unprojected", o.unprojected_scope);
+    if (urc) { fprintf(stderr, "error: unprojected records on device %d: %s\n", workers[0]->device, br_strerror(urc)); return give_up(); }
   }
   if (!open_consumers(env, consumers, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return give_up(); }
   OutFile file(o.out_bam);

@@ -53,6 +53,8 @@ struct Options {
   std::string coverage, coverage_summary;   // --coverage FILE / --coverage-summary FILE: the bedGraph of the depth along every transcript and the per-transcript table (br_coverage)
   bool coverage_primary = false; // --coverage-primary: only primary records count ("primary_only")
   int coverage_weight = 0;       // --coverage-weight unit|nh|em: br_coverage's "weight" (0, 1, 2); em reads the --quant consumer's posteriors
+  std::string unprojected;       // --unprojected FILE: the input records without an output record, as a BAM under the input's header
+  int unprojected_scope = 1;     // --unprojected-scope record|name: the context's "keep_unprojected" (1, 2)
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };
 inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }

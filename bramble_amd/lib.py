@@ -177,6 +177,7 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_collator_stats", "br_collator_free",
            "br_sorter_new", "br_sorter_set_param", "br_sorter_add", "br_sorter_finish", "br_sorter_next", "br_sorter_order", "br_sorter_stats",
            "br_sorter_index", "br_sorter_free", "br_ctx_last_device_bam", "br_device_bam_download",
+           "br_ctx_unprojected_stats", "br_ctx_unprojected_next", "br_ctx_unprojected_reset",
            "br_quant_new", "br_quant_set_param", "br_quant_set_tolerance", "br_quant_set_vb_prior", "br_quant_digamma", "br_quant_add", "br_quant_add_rows", "br_quant_add_last", "br_quant_finish",
            "br_quant_classes", "br_quant_em", "br_quant_result", "br_quant_fld", "br_quant_eff_lengths", "br_quant_stats", "br_quant_free",
            "br_quant_bootstrap", "br_quant_boot_counts", "br_quant_boot_theta", "br_quant_boot_summary", "br_quant_boot_stats",
@@ -761,6 +762,45 @@ class Context:
         check(L.br_device_bam_download(self.h, C.byref(piece), int(out_mode), 0, C.byref(out)), "br_device_bam_download")
         n = int(out.n_bytes)
         return np.ctypeslib.as_array(C.cast(out.data, _P(C.c_uint8)), shape=(n,)).copy() if n else np.zeros(0, np.uint8)
+
+    UNPROJECTED_STATS = ("records", "unprojected", "bytes", "names", "names_none", "names_partial", "held_bytes", "peak_bytes")
+
+    def unprojected_stats(self):
+        """br_ctx_unprojected_stats as a dict (UNPROJECTED_STATS): sums over the bundle calls since the last reset, made with
+        set_param("keep_unprojected", 1 | 2)."""
+        out = (C.c_uint64 * 8)()
+        L = lib()
+        L.br_ctx_unprojected_stats.argtypes = [C.c_void_p, C.c_void_p]
+        check(L.br_ctx_unprojected_stats(self.h, out), "br_ctx_unprojected_stats")
+        return dict(zip(self.UNPROJECTED_STATS, [int(v) for v in out]))
+
+    def unprojected_records(self, max_bytes):
+        """br_ctx_unprojected_next as it is: the next piece as a BrDeviceBam in HBM (n_rows = 0 at the end; valid until the next
+        call on the context)."""
+        piece = BrDeviceBam()
+        L = lib()
+        L.br_ctx_unprojected_next.argtypes = [C.c_void_p, C.c_uint64, _P(BrDeviceBam)]
+        check(L.br_ctx_unprojected_next(self.h, int(max_bytes), C.byref(piece)), "br_ctx_unprojected_next")
+        return piece
+
+    def unprojected_next(self, max_bytes):
+        """The next unprojected records in input order, up to max_bytes and at least one, as numpy copies: (uint8 stream of
+        [block_size][record]..., uint64 row_off [n_rows + 1] into it); both empty when that was all."""
+        import torch
+        from .device import _DevArray
+        p = self.unprojected_records(max_bytes)
+        n = int(p.n_rows)
+        if n == 0:
+            return np.zeros(0, np.uint8), np.zeros(0, np.uint64)
+        dev = "cuda:%d" % self.index.device
+        off = torch.as_tensor(_DevArray(p.row_off, n + 1, "<u8"), device=dev).cpu().numpy().astype(np.uint64)
+        data = torch.as_tensor(_DevArray(p.data, int(p.n_bytes), "|u1"), device=dev).cpu().numpy().copy()
+        return data, off
+
+    def unprojected_reset(self):
+        L = lib()
+        L.br_ctx_unprojected_reset.argtypes = [C.c_void_p]
+        check(L.br_ctx_unprojected_reset(self.h), "br_ctx_unprojected_reset")
 
     def project_bam_bundle(self, cfg, blob, rec_off, rec_len, ref_map, bgzf_on_device=False, sam_text=False):
         """Host form: numpy blob / rec_off (uint64) / rec_len (uint32) in, (stream uint8[], counters dict) out; with sam_text the

@@ -973,6 +973,37 @@ int br_project_bam_resident(br_ctx *, const br_config *, const br_device_records
 int br_ctx_last_device_bam(const br_ctx *, br_device_bam *out);
 int br_device_bam_download(br_ctx *, const br_device_bam *in, int out_mode, int nowait, br_host_bam *out);
 
+/* ---- the records that did not project ------------------------------------------------------ */
+
+/* An input record is unprojected when no output record came from it.  With br_ctx_set_param(ctx, "keep_unprojected", 1)
+ * (scope record) or 2 (scope name: only the records of read names of which NO record projected) every bundle call --
+ * br_project_bam_device and the entry points above it: br_project_bam_bundle, _staged, _staged_nowait, _resident -- appends the
+ * bundle's unprojected records to an arena the context owns: [block_size][record], the input's bytes, in input order.  The
+ * work (a flag per input alignment from the emitted rows, a count per read name, two scans, one gather) runs inside the call,
+ * beside the record encoder, and is complete when the call returns: the caller may release or overwrite the input records
+ * then.  It adds no host wait to the call.  0, the default: nothing is launched and nothing allocated.  Changing the
+ * parameter while records are held answers BR_ERR_INVALID_ARG (draw or reset first).
+ *
+ *   - Flat batches (br_project_batch*, br_project_group*) have no records and add nothing.
+ *   - Unmapped input records never reach a bundle (br_bam_split and the readers drop them) and are not in the result.
+ *   - Memory: the held bytes plus 8 bytes a record, all in HBM until drawn and reset (while the arena grows, by half, the
+ *     old one lies beside the new).  BR_ERR_CAPACITY from the projection call when the device's memory does not take it; the
+ *     call's projected records are lost with it, what was held before stays.
+ *   - The test hook "unprojected_cap" sets the arena's first capacity in bytes.
+ *
+ *   br_ctx_unprojected_stats   sums over the calls since the last reset: out[0] records seen, [1] unprojected records,
+ *                              [2] their bytes (with the block_size words), [3] read names seen, [4] names with no record
+ *                              projected, [5] names partly projected (some records, not all; counted in either scope),
+ *                              [6] device bytes of the arena and its offsets now, [7] at most
+ *   br_ctx_unprojected_next    the next records in order, up to max_bytes and at least one: a slice of the arena with row_off
+ *                              rebased to the piece, valid until the next call on the context; n_rows = 0: that was all.
+ *                              br_device_bam_download turns a piece into records, BGZF blocks or SAM lines, as it does a
+ *                              sorter's.  Records added after a draw are handed out by the draws that follow
+ *   br_ctx_unprojected_reset   forgets what is held, frees the arena and zeroes the counters */
+int br_ctx_unprojected_stats(const br_ctx *, uint64_t out[8]);
+int br_ctx_unprojected_next(br_ctx *, uint64_t max_bytes, br_device_bam *piece);
+int br_ctx_unprojected_reset(br_ctx *);
+
 /* ---- SAM text out -------------------------------------------------------------------------- */
 
 /* The reference names RNAME and RNEXT print, in refID order (a refID < 0 or >= n prints '*'); uploaded to HBM once, kept by
