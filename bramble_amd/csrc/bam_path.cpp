@@ -362,7 +362,8 @@ static int project_bam_tail(br_ctx *c, const br_config *cfg, const br_device_rec
   char note[160]; note[0] = 0;
   if (timing) snprintf(note, sizeof note, "[bundle] %lld records: upload wait %.1f ms, records -> records %.1f ms", (long long)dr->n_aln, wait_ms,
                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
-  if (out_mode == BR_OUT_RESIDENT) { c->last_bam = db; out->n_rows = db.n_rows; if (timing) fprintf(stderr, "%s, kept in HBM\n", note); }
+  c->last_bam = db;   // in every output mode: the buffer lives until the context's next call (br_sorter and br_assign take it from there)
+  if (out_mode == BR_OUT_RESIDENT) { out->n_rows = db.n_rows; if (timing) fprintf(stderr, "%s, kept in HBM\n", note); }
   else RC(device_bam_home(c, db, out_mode, nowait, note, out));
   out->total_complete = rows.total_complete; out->total_unique = rows.total_unique;
   out->dropped_reads = rows.dropped_reads; out->total_processed = rows.total_processed;

@@ -158,7 +158,7 @@ struct br_ctx {
   uint8_t *h_bam[2] = {nullptr, nullptr}; size_t h_bam_cap[2] = {0, 0}; int h_bam_next = 0;  // pinned download buffers of br_project_bam_bundle (alternating)
   BigPinned h_bam_mem[2];
   int64_t last_n_rows = 0, last_n_aln = 0;
-  br_device_bam last_bam{};   // BR_OUT_RESIDENT: the last bundle's projected records, left in HBM (br_ctx_last_device_bam)
+  br_device_bam last_bam{};   // the last bundle call's projected records in HBM, in every output mode (br_ctx_last_device_bam); a flat batch call has none
   // the last projection call's rows, read-name groups and stream, whichever entry point made it (br_quant_add_last); valid like the rows
   br_device_rows last_rows{}; const uint32_t *last_group_off = nullptr; int64_t last_n_groups = 0; hipStream_t last_stream = nullptr;
   DevBuf fa_stats, fa_n_prob, fa_seq_bytes, fa_prob_off, fa_seqarena_off, fa_probs, fa_results, fa_seq_arena, fa_clip_ops,

@@ -7,7 +7,7 @@
 //   uploader      : br_bam_bundle_stage (host bundles: records to one of three device slots, own copy stream)
 //   runner        : br_project_bam_staged_nowait / br_project_bam_resident (everything between the raw records on the device)
 //   writer thread : BGZF deflate (threaded) -> output file; device-made BGZF blocks or SAM lines (-O sam) go out as they are
-//   consumers     : what else takes something from every projected bundle -- --sort, --quant, --coverage, --unprojected (cli_output.h: one consumer
+//   consumers     : what else takes something from every projected bundle -- --sort, --quant, --coverage, --unprojected, --quant-bam (cli_output.h: one consumer
 //                   per feature).  The runner hands each bundle to every consumer right after its projection call; after the last
 //                   bundle each finishes on the device, writes its files under temporary names and prints its report line.  One of
 //                   them may keep the records (--sort): then the projection leaves them in HBM (BR_OUT_RESIDENT), nothing of a
@@ -52,7 +52,8 @@ void usage(FILE *f) {
           "                [--quant-genes <genes.tsv> [--quant-gene-classes <gene_classes.txt>] [--quant-gene-map <tx2gene.tsv>]]]\n"
           "               [--coverage <cov.bedgraph>] [--coverage-summary <cov.tsv>] [--coverage-primary]\n"
           "               [--coverage-weight unit|nh|em]\n"
-          "               [--unprojected <unprojected.bam> [--unprojected-scope record|name]]\n\n"
+          "               [--unprojected <unprojected.bam> [--unprojected-scope record|name]]\n"
+          "               [--quant-bam <post.bam> [--quant-bam-mode tag|sample]]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -117,7 +118,14 @@ void usage(FILE *f) {
           "they came in, in input order.  They are picked out and kept on one GPU while the bundles are projected.  Unmapped input\n"
           "records are not among them.  --unprojected-scope record (the default): every such record; name: only the records of read\n"
           "names of which no record was projected (the mate of a half-projected pair stays out).  One more line in front of the final\n"
-          "report: [bramble] unprojected: R of N records written (W read names without a projected record, P partly projected; scope record|name)\n");
+          "report: [bramble] unprojected: R of N records written (W read names without a projected record, P partly projected; scope record|name)\n"
+          "--quant-bam FILE (it needs --quant): a second BAM, under the header the output has without --sort, with the posterior of\n"
+          "--quant's EM on the projected records, weighed and rewritten on one GPU.  --quant-bam-mode tag (the default): every\n"
+          "projected record in the order of the unsorted output, with ZW:f:<w> appended (RSEM's tag): w is the posterior of (read name,\n"
+          "transcript), split evenly among the read's records on that transcript, a pair's two terms added.  sample: one placement per\n"
+          "read name, drawn with probability w (Philox4x32-10 under --quant-seed S: the same seed gives the same file), rewritten to\n"
+          "NH:i:1, HI:i:1, primary, the MAPQ of a unique record, with ZW:f:<w>.  BAM whatever -O says; --host-deflate applies.  One more\n"
+          "line in front of the final report: [bramble] posterior BAM: R of N records written for M read names (mode tag|sample; add X.XXs, weigh Y.YYs)\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -126,7 +134,7 @@ int parse_args(int argc, char **argv, Options &o) {
   memset(&o.cfg, 0, sizeof(o.cfg));
   o.cfg.junc_miss_discount = 1.0;
   bool codec = false, host_codec = false;   // a BGZF codec option was given; one that asks for the host codec
-  bool coverage_weight_given = false, unprojected_scope_given = false;
+  bool coverage_weight_given = false, unprojected_scope_given = false, quant_bam_mode_given = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "%s: missing value\n", argv[i]); return nullptr; } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -217,6 +225,14 @@ int parse_args(int argc, char **argv, Options &o) {
       else { fprintf(stderr, "--unprojected-scope: unknown scope %s (record or name)\n", v); return -1; }
       unprojected_scope_given = true;
     }
+    else if (a == "--quant-bam") { const char *v = value(); if (!v) return -1; o.quant_bam = v; }
+    else if (a == "--quant-bam-mode") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "tag") o.quant_bam_mode = 0; else if (w == "sample") o.quant_bam_mode = 1;
+      else { fprintf(stderr, "--quant-bam-mode: unknown mode %s (tag or sample)\n", v); return -1; }
+      quant_bam_mode_given = true;
+    }
     else if (a == "--device") { const char *v = value(); if (!v) return -1; o.devices.assign(1, atoi(v)); }
     else if (a == "--devices") {
       const char *v = value(); if (!v) return -1;
@@ -238,6 +254,10 @@ int parse_args(int argc, char **argv, Options &o) {
   if (!o.quant.empty() && o.devices.size() > 1) { fprintf(stderr, "--quant works on one device: give --device N, not a --devices list\n"); return -1; }
   if (o.quant.empty() && (!o.quant_classes.empty() || o.quant_length_norm >= 0)) { fprintf(stderr, "--quant-classes, --quant-length-norm and --quant-no-length-norm need --quant\n"); return -1; }
   if (o.quant.empty() && (o.quant_eff_length || !o.quant_fld.empty())) { fprintf(stderr, "--quant-eff-length and --quant-fld need --quant\n"); return -1; }
+  if (o.quant.empty() && !o.quant_bam.empty()) { fprintf(stderr, "--quant-bam needs --quant: the weights are the EM's posteriors\n"); return -1; }
+  if (quant_bam_mode_given && o.quant_bam.empty()) { fprintf(stderr, "--quant-bam-mode needs --quant-bam\n"); return -1; }
+  if (o.quant_bam == "-") { fprintf(stderr, "--quant-bam needs a file, not standard output: that is the main output's\n"); return -1; }
+  if (!o.quant_bam.empty() && o.devices.size() > 1) { fprintf(stderr, "--quant-bam works on one device: give --device N, not a --devices list\n"); return -1; }
   if (o.quant.empty() && (o.quant_bootstraps || o.quant_seed_given || !o.quant_boot_out.empty())) { fprintf(stderr, "--quant-bootstraps, --quant-seed and --quant-boot-out need --quant\n"); return -1; }
   if (o.quant.empty() && (o.quant_vb || o.quant_vb_prior_given || o.quant_vb_per_nt)) { fprintf(stderr, "--quant-vb, --quant-vb-prior and --quant-vb-per-nucleotide need --quant\n"); return -1; }
   if (!o.quant_vb && (o.quant_vb_prior_given || o.quant_vb_per_nt)) { fprintf(stderr, "--quant-vb-prior and --quant-vb-per-nucleotide need --quant-vb: without it there is no prior\n"); return -1; }
@@ -726,6 +746,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
     const int urc = br_ctx_set_param(workers[0]->ctx, "keep_unprojected", o.unprojected_scope);
     if (urc) { fprintf(stderr, "error: unprojected records on device %d: %s\n", workers[0]->device, br_strerror(urc)); return give_up(); }
   }
+  if (!o.quant_bam.empty()) env.out_header = make_bam_header(make_header_text(hdr.text, ix0, cl, o.gff, false), ix0);
   if (!open_consumers(env, consumers, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return give_up(); }
   OutFile file(o.out_bam);
   if (!file.wr.open(file.tmp.c_str(), o.threads, o.level, !o.sam_out)) { fprintf(stderr, "error: %s\n", file.wr.error().c_str()); return give_up(); }

@@ -55,6 +55,8 @@ struct Options {
   int coverage_weight = 0;       // --coverage-weight unit|nh|em: br_coverage's "weight" (0, 1, 2); em reads the --quant consumer's posteriors
   std::string unprojected;       // --unprojected FILE: the input records without an output record, as a BAM under the input's header
   int unprojected_scope = 1;     // --unprojected-scope record|name: the context's "keep_unprojected" (1, 2)
+  std::string quant_bam;         // --quant-bam FILE: the projected records with the EM's posterior (ZW:f), as a BAM under the unsorted output's header
+  int quant_bam_mode = 0;        // --quant-bam-mode tag|sample: br_assign's "mode" (0, 1)
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };
 inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }

@@ -1,5 +1,5 @@
 // What consumes a run of the command line (cli.cpp) beside the main output: --sort (cli_output_sort.cpp), --quant
-// (cli_output_quant.cpp), --coverage (cli_output_coverage.cpp), --unprojected (cli_output_unprojected.cpp), behind one interface.  A consumer takes something from every
+// (cli_output_quant.cpp), --coverage (cli_output_coverage.cpp), --unprojected (cli_output_unprojected.cpp), --quant-bam (cli_output_assign.cpp), behind one interface.  A consumer takes something from every
 // projected bundle on device o.devices[0], does its device work once the input is through, writes its files (cli_output_files.h)
 // and prints one report line; the runners, the writer and br_cli_main loop over the consumers and never learn which kind one is.
 #pragma once
@@ -10,7 +10,8 @@ namespace brcli {
 
 // what every consumer is made from, built once: tid = the index's transcript, its line in a file = the @SQ list's; hdr: the
 // input's header (--unprojected writes its file under it)
-struct RunEnv { const Options &o; int device; TxTable tx; const BamHeader &hdr; };
+// out_header: the main output's BAM header as it is without --sort (--quant-bam writes its file under it; empty unless asked for)
+struct RunEnv { const Options &o; int device; TxTable tx; const BamHeader &hdr; std::vector<uint8_t> out_header; };
 
 class Consumer {
  public:
@@ -44,6 +45,7 @@ std::unique_ptr<Consumer> open_sort(const RunEnv &env, std::string &err);
 std::unique_ptr<Consumer> open_quant(const RunEnv &env, std::string &err);
 std::unique_ptr<Consumer> open_coverage(const RunEnv &env, std::string &err);
 std::unique_ptr<Consumer> open_unprojected(const RunEnv &env, std::string &err);   // (begins its file: err is the writer's)
+std::unique_ptr<Consumer> open_assign(const RunEnv &env, std::string &err);        // (likewise)
 // (for the three above) T::open() makes the library's object and sets its parameters
 template <typename T>
 std::unique_ptr<Consumer> open_as(const RunEnv &env, std::string &err) {
@@ -52,12 +54,12 @@ std::unique_ptr<Consumer> open_as(const RunEnv &env, std::string &err) {
   return c;
 }
 
-// the consumers the options ask for, in the order sort, quant, coverage, unprojected -- the order of their finish() as well: coverage under
-// --coverage-weight em reads the quantifier (Consumer::quantifier) whose EM quant's finish() has run; false: `err` says which
+// the consumers the options ask for, in the order sort, quant, coverage, unprojected, quant-bam -- the order of their finish() as well: coverage under
+// --coverage-weight em and --quant-bam read the quantifier (Consumer::quantifier) whose EM quant's finish() has run; false: `err` says which
 // could not be made
 inline bool open_consumers(const RunEnv &env, std::vector<std::unique_ptr<Consumer>> &out, std::string &err) {
   const Options &o = env.o;
-  const std::pair<bool, decltype(&open_sort)> wanted[] = {{o.sort, open_sort}, {!o.quant.empty(), open_quant}, {!o.coverage.empty() || !o.coverage_summary.empty(), open_coverage}, {!o.unprojected.empty(), open_unprojected}};
+  const std::pair<bool, decltype(&open_sort)> wanted[] = {{o.sort, open_sort}, {!o.quant.empty(), open_quant}, {!o.coverage.empty() || !o.coverage_summary.empty(), open_coverage}, {!o.unprojected.empty(), open_unprojected}, {!o.quant_bam.empty(), open_assign}};
   for (auto &[want, open] : wanted) {
     if (!want) continue;
     out.push_back(open(env, err));

@@ -186,6 +186,8 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_coverage_new", "br_coverage_set_param", "br_coverage_add_rows", "br_coverage_add_last", "br_coverage_finish", "br_coverage_runs",
            "br_coverage_depth", "br_coverage_summary", "br_coverage_stats", "br_coverage_free",
            "br_coverage_add_names", "br_coverage_finish_em", "br_coverage_runs64", "br_coverage_depth64", "br_coverage_summary64",
+           "br_assign_new", "br_assign_set_param", "br_assign_add", "br_assign_add_last", "br_assign_finish", "br_assign_values", "br_assign_next",
+           "br_assign_stats", "br_assign_free",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_direct_tidwords", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -1033,7 +1035,7 @@ class SamReader:
 
 
 class _Accumulator:
-    """What the wrappers of the run accumulators (br_collator, br_sorter, br_quant, br_coverage) share: the handle, made by
+    """What the wrappers of the run accumulators (br_collator, br_sorter, br_quant, br_coverage, br_assign) share: the handle, made by
     br_<NAME>_new and freed by br_<NAME>_free, and the calls of br_<NAME>_<what> on it.  A subclass gives NAME and ARGTYPES
     (<what> -> the argument types)."""
     NAME, ARGTYPES, h = None, {}, None
@@ -1674,3 +1676,92 @@ class Coverage(_Accumulator):
         self._call("stats", C.byref(rc), C.byref(rs), C.byref(cb), C.byref(h), C.byref(p), C.byref(ad), C.byref(fi))
         return {"rows_counted": int(rc.value), "rows_skipped": int(rs.value), "clipped_bases": int(cb.value), "held_bytes": int(h.value),
                 "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value}
+
+
+class Assign(_Accumulator):
+    """br_assign on `device`: the rows of projected batches by read name, and (or not: on every add or on none) the records they
+    were encoded to, in; after finish(quant) the posterior weight w of every record's placement (values), and the records again
+    with ZW:f appended -- all of them ("mode" 0, tag) or one drawn placement per read name ("mode" 1, sample: MODES).  set_param:
+    "mode", "seed", "long_reads", "max_bytes", before the first add."""
+
+    MODES = {"tag": 0, "sample": 1}
+    BAD = ("names", "classes", "transcripts", "posteriors")
+
+    NAME = "assign"
+    ARGTYPES = {"new": [C.c_int, _P(C.c_void_p)], "set_param": [C.c_void_p, C.c_char_p, C.c_int64],
+                "add": [C.c_void_p, C.c_void_p, _P(BrDeviceRows), C.c_void_p, C.c_int64, C.c_int, C.c_void_p],
+                "add_last": [C.c_void_p, C.c_void_p], "finish": [C.c_void_p, C.c_void_p, _P(C.c_int64), _P(C.c_int64)],
+                "values": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+                "next": [C.c_void_p, C.c_uint64, _P(BrDeviceBam)],
+                "stats": [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_double), C.c_void_p],
+                "free": [C.c_void_p]}
+
+    def __init__(self, device=0, **params):
+        self.n = self.n_out = self.n_named = 0
+        self._open(device)
+        for k, v in params.items():
+            self.set_param(k, v)
+
+    def add_raw(self, recs, a, row_off, n_rows, group_off, n_groups, on_device, stream=None):
+        """br_assign_add as it is (recs: a BrDeviceBam or None; the tables as addresses): the return code (0, or a BR_ERR_* value)."""
+        rows = BrDeviceRows()
+        rows.n_rows, rows.a, rows.row_off = int(n_rows), a, row_off
+        rc = self._raw("add", C.cast(C.byref(recs), C.c_void_p) if recs is not None else None, C.byref(rows), C.c_void_p(group_off), int(n_groups),
+                       1 if on_device else 0, C.c_void_p(stream or 0))
+        return rc
+
+    def add_host(self, rows_a, row_off, group_off, stream_np=None, rec_off=None):
+        """The rows of the read names group_off[0 .. n] (rows_a uint32 [n_rows, 4], row_off uint64 per alignment, in host memory);
+        stream_np: the rows' records as an uncompressed record stream in host memory (row i = record i), or None."""
+        a = np.ascontiguousarray(rows_a, dtype=np.uint32).reshape(-1, 4)
+        ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+        go = np.ascontiguousarray(group_off, dtype=np.uint32)
+        recs = None
+        if stream_np is not None:
+            data = np.ascontiguousarray(stream_np, dtype=np.uint8)
+            off = Sorter.row_offsets(data) if rec_off is None else np.ascontiguousarray(rec_off, dtype=np.uint64)
+            recs = BrDeviceBam(data.ctypes.data if data.size else None, data.size, off.ctypes.data, len(off) - 1)
+        check(self.add_raw(recs, a.ctypes.data if a.size else None, ro.ctypes.data, len(a), go.ctypes.data, len(go) - 1, False), "br_assign_add")
+
+    def add_device(self, rows_a, row_off, group_off, n_rows, recs=None, g0=0, g1=None):
+        """The same tables as torch CUDA tensors; the read names [g0, g1) of them are added.  recs: a BrDeviceBam of the rows'
+        records in HBM (what project_bam_resident_kept returns), or None."""
+        import torch
+        g1 = group_off.numel() - 1 if g1 is None else g1
+        check(self.add_raw(recs, rows_a.data_ptr() if n_rows else None, row_off.data_ptr(), n_rows, group_off.data_ptr() + 4 * g0, g1 - g0, True,
+                           torch.cuda.current_stream(row_off.device).cuda_stream), "br_assign_add")
+
+    def add_last(self, ctx):
+        """The rows, names and records of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
+        self._call("add_last", ctx.h)
+
+    def finish(self, quant):
+        """With the posteriors of `quant` (a Quant with "keep_names", after em, fed the same names) -> (records that will be
+        written, names with records)."""
+        n, m = C.c_int64(), C.c_int64()
+        self._call("finish", quant.h, C.byref(n), C.byref(m))
+        self.n_out, self.n_named = int(n.value), int(m.value)
+        return self.n_out, self.n_named
+
+    def values(self, first, n):
+        """-> w (float64), zw (float32), kept (uint8) of the add-order records [first, first + n)"""
+        k = max(int(n), 1)
+        w, zw, kept = np.zeros(k, np.float64), np.zeros(k, np.float32), np.zeros(k, np.uint8)
+        self._call("values", int(first), int(n), w.ctypes.data, zw.ctypes.data, kept.ctypes.data)
+        return w[:n], zw[:n], kept[:n]
+
+    def next_records(self, max_bytes):
+        """The next piece as a BrDeviceBam in HBM (n_rows = 0 at the end; valid until the second next call)."""
+        piece = BrDeviceBam()
+        self._call("next", int(max_bytes), C.byref(piece))
+        return piece
+
+    pieces = Sorter.pieces
+
+    def stats(self):
+        h, p, ad, fi, nx = C.c_uint64(), C.c_uint64(), C.c_double(), C.c_double(), C.c_double()
+        bad = np.zeros(4, np.uint64)
+        self._call("stats", C.byref(h), C.byref(p), C.byref(ad), C.byref(fi), C.byref(nx), bad.ctypes.data)
+        out = {"held_bytes": int(h.value), "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value, "next_s": nx.value}
+        out.update({"bad_" + k: int(v) for k, v in zip(self.BAD, bad)})
+        return out

@@ -966,7 +966,9 @@ int br_project_bam_resident(br_ctx *, const br_config *, const br_device_records
                             int bgzf_on_device, int nowait, br_host_bam *out);
 /* The calls above with bgzf_on_device = BR_OUT_RESIDENT leave the projected records in HBM: no deflate, no SAM text, no
  * download (br_host_bam: the counters and n_rows, n_bytes = 0, data = NULL).  br_ctx_last_device_bam returns them, valid until
- * the context's next call (a br_sorter takes them from there).  br_device_bam_download is the other half: a record stream in
+ * the context's next call (a br_sorter takes them from there).  In the other output modes the same call returns the records the
+ * bundle call encoded before it deflated, formatted or downloaded them, valid as long (br_assign_add_last reads them); a flat
+ * batch call leaves none (n_rows = 0).  br_device_bam_download is the other half: a record stream in
  * HBM (a br_sorter_next piece) -> the bytes of out_mode (0 records, 1 BGZF blocks, BR_OUT_SAM_TEXT lines) in the context's
  * pinned buffers, under the buffer rule of br_host_bam; nowait as br_project_bam_staged_nowait (br_host_bam_wait). */
 #define BR_OUT_RESIDENT 3
@@ -1003,6 +1005,77 @@ int br_device_bam_download(br_ctx *, const br_device_bam *in, int out_mode, int 
 int br_ctx_unprojected_stats(const br_ctx *, uint64_t out[8]);
 int br_ctx_unprojected_next(br_ctx *, uint64_t max_bytes, br_device_bam *piece);
 int br_ctx_unprojected_reset(br_ctx *);
+
+/* ---- the posterior on the records ----------------------------------------------------------- */
+
+/* br_assign: a run accumulator like br_quant and br_coverage.  It is fed the rows of every projection call by read name, as
+ * br_coverage_add_names is, and with them the records the call encoded; after the quantifier's EM it knows the posterior weight of
+ * every record and hands the records out again, each with a ZW:f entry (mode tag) or one drawn placement per read name (mode
+ * sample).  All arithmetic is float64, no fused multiply-add, one rounding per operation; every sum is sequential in the stated
+ * order, whatever its length, so a restatement in the same order gives the same bits.
+ *   record r       row r of an add: records and rows of a projection call correspond one to one (br_device_bam row i is
+ *                  br_device_rows row i).  The records of all adds are numbered in add order
+ *   name(r)        the add-order index of r's read name, from row_off / group_off exactly as br_coverage_add_names takes it
+ *   t(r)           a[r].transcript_id
+ *   p(r)           the posterior (br_quant_posteriors) of the entry of t(r) among the labels of class name_cls[name(r)].  Every index
+ *                  is compared with its table's size before it becomes an address; what fails is counted, never looked up
+ *   m(r)           the number of records of name(r) whose transcript is t(r) (at least 1: r itself)
+ *   placement      a record with BR_ROW_FIRST set; with BR_ROW_PAIRED set the next record is part of it, which must lie inside the
+ *                  same name, have BR_ROW_PAIRED set and BR_ROW_FIRST clear.  A record that belongs to no placement, or a leader
+ *                  without such a mate, makes the add BR_ERR_INVALID_ARG.  A name's placements are numbered in record order
+ *   w(placement)   p(r0) / (double)m(r0), plus p(r1) / (double)m(r1) for a pair, the leader's term first: a read's (name,
+ *                  transcript) posterior is split evenly among its records on that transcript, so the w of a name's placements sum
+ *                  to the sum of its posteriors (1 up to rounding); a pair on two transcripts (BR_ROW_SAME_TX clear) is one placement
+ *   ZW(r)          (float)w of r's placement, rounded to nearest even; both mates carry the same value
+ *   draw           (mode sample) per name with at least one placement: Philox4x32-10 (the bootstrap's generator) under the key
+ *                  ("seed" low word, high word) at the counter (name & 0xffffffff, name >> 32, 0, 1) -- word 3 = 1 keeps it apart
+ *                  from the bootstrap's counters --; u = w0 | w1 << 32, U = (double)(u >> 11) * 2^-53; W = the sum of w over the
+ *                  name's placements in order, target = U * W; the pick is the first placement j with cum_j > target, cum_j =
+ *                  cum_(j-1) + w_j from 0; none: the last placement with w > 0; every w 0: placement 0.  A name without rows has no
+ *                  pick and no records
+ *   rewritten      the input record's bytes with block_size + 7 and the seven bytes 'Z' 'W' 'f' <float32 LE> behind its last byte
+ *   record         (behind a CG:B,I spill as well).  In mode sample also: the values of the encoder's NH:i and HI:i entries become 1
+ *                  (it writes exactly one of each as 4-byte 'i', AS:i between them for long reads, the CG spill behind them), flag bit
+ *                  0x100 is cleared and MAPQ = br_row_mapq(1, "long_reads").  Every other byte is the input's
+ *   invariance     how the names were cut into adds, and whether the tables came from host or device memory, changes nothing
+ *
+ *   br_assign_set_param   before the first add: "mode" 0 tag (default) / 1 sample, "seed" (the int64's bits), "long_reads" 0 / 1,
+ *                         "max_bytes" (a cap on the arena's bytes, 0: none)
+ *   br_assign_add         the rows of the read names group_off[0 .. n_groups] (shapes and rules of br_coverage_add_names; a is all it
+ *                         reads of the rows) and their records: recs->row_off[r] .. [r + 1] of recs->data for row r.  recs is NULL on
+ *                         every add or on none (a mix: BR_ERR_INVALID_ARG): without records the object computes w, zw and kept
+ *                         only.  recs->n_rows != rows->n_rows, offsets that descend, a row the offsets give to no name, a bad
+ *                         placement: BR_ERR_INVALID_ARG and nothing added.  BR_ERR_CAPACITY for memory that is not there, the
+ *                         "max_bytes" cap, 2^32 names or records
+ *   br_assign_add_last    br_assign_add of the context's last call: its rows, names and records (br_ctx_last_device_bam).  A flat
+ *                         batch call has no records: BR_ERR_INVALID_ARG unless the object is without records (an object without
+ *                         adds becomes that)
+ *   br_assign_finish      needs a quantifier on the same device, with "keep_names", after br_quant_em, whose names number what the
+ *                         adds were given; else BR_ERR_INVALID_ARG and the object is as it was.  A name past the count, a class
+ *                         past the classes, a transcript that is not in its name's class or a posterior outside [0, 1] is counted,
+ *                         never looked up, and makes the call return BR_ERR_INVALID_ARG; from then on every call but
+ *                         br_assign_stats and br_assign_free answers that.  The records that will be written and the names with
+ *                         records
+ *   br_assign_values      after finish: w, zw and kept of the add-order records [first, first + n); any pointer may be NULL
+ *   br_assign_next        as br_sorter_next: the next whole kept records, rewritten, up to max_bytes and at least one, with their
+ *                         rebased row_off; valid until the second next; n_rows = 0: that was all.  BR_ERR_INVALID_ARG without
+ *                         records, and (the object is dead then) for a kept record of mode sample without the NH / HI entries
+ *   br_assign_stats       device bytes held now and at most, seconds in add / finish / next, bad[4]: what finish's look-up counted
+ *                         (names, classes, transcripts, posteriors); any pointer may be NULL
+ * Device memory (n records, K of them kept): the arena's 4 + block_size bytes a record (+ 64; it grows by half, the old one beside
+ * the new while copying), 16 bytes a record of notes, 8 of offsets; from finish on 9 a record (w, kept) and 12 a kept record (the
+ * list, the rewritten offsets), while it runs 20 a record more (p, m, the ranks); next holds two piece buffers (assign.cpp). */
+typedef struct br_assign br_assign;
+int br_assign_new(int device, br_assign **out);
+int br_assign_set_param(br_assign *, const char *name, int64_t value);
+int br_assign_add(br_assign *, const br_device_bam *recs, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups,
+                  int on_device, void *stream);
+int br_assign_add_last(br_assign *, br_ctx *);
+int br_assign_finish(br_assign *, br_quant *, int64_t *n_records_out, int64_t *n_names_with_records);
+int br_assign_values(br_assign *, int64_t first, int64_t n, double *w, float *zw, uint8_t *kept);
+int br_assign_next(br_assign *, uint64_t max_bytes, br_device_bam *piece);
+int br_assign_stats(const br_assign *, uint64_t *held, uint64_t *peak, double *add_s, double *finish_s, double *next_s, uint64_t *bad);
+void br_assign_free(br_assign *);
 
 /* ---- SAM text out -------------------------------------------------------------------------- */
 
