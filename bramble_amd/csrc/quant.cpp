@@ -15,20 +15,23 @@
 //            rows on one transcript: positions and the reference bases of the two rewritten CIGARs) into the add's own histogram,
 //            which joins the run's once the add is known to be good; finish scans the histogram into C and S and writes the
 //            effective length and w = 1 / eff per transcript, which the EM then takes from the device
-//   em       per iteration a class kernel (q_c = n_c / sum over its labels of theta_t w_t) and a transcript kernel (theta'_t =
-//            theta_t w_t * sum of q_c over the transcript's classes, gathered through the transposed table); every 16th iteration
-//            and the last the transcript kernel also leaves the largest relative change in one word, which the host reads
+//   em       one EM (quant_em_run) over a chunk of W = 2^k replicates that run together, replicate innermost in theta, theta w, q
+//            and the counts, so an index is read once for W replicates and a gather is W * 8 contiguous bytes; a replicate's sums
+//            do not know W, so its bits are those of the EM run alone on its counts.  Per iteration a class kernel (q_c = n_c /
+//            sum over its labels of theta_t w_t) and a transcript kernel (theta'_t = theta_t w_t * sum of q_c over the
+//            transcript's classes, gathered through the transposed table); every 16th iteration and the last the transcript
+//            kernel also leaves every replicate's largest relative change in a word of its own.  The host reads the W words and
+//            clears the bit of a replicate that stops: its theta is copied through from then on.  The EM ends when all have
+//            stopped.  br_quant_em is the chunk of one replicate on the observed counts, with kernel instantiations in which
+//            W = 1 is a compile-time fact, in buffers the object keeps
 //   vb       ("vb") the class and transcript kernels as they are -- alpha in theta's place; the x they leave is replaced -- then three
 //            launches that make x from the new alpha: a partial of alpha + p per 256 transcripts, the partials summed in a fixed
 //            order by one block a replicate, which also takes psi(S), and a lane per (transcript, replicate) for
-//            exp(psi(alpha + p) - psi(S)) w.  The point EM runs them as a chunk of one replicate
+//            exp(psi(alpha + p) - psi(S)) w
 //   bootstrap B replicates in chunks of W (16 by default): a chunk's class counts are resampled when it starts (a lane a draw:
-//            Philox4x32-10 by (draw, replicate), a binary search in the scanned counts, an integer atomicAdd) and its EMs run
-//            together, replicate innermost in theta, theta w, q and the counts, so an index is read once for W replicates and a
-//            gather is W * 8 contiguous bytes; per replicate the sums have the point kernels' shape, so its bits are a point EM's.
-//            The host reads W relative changes at every look and clears the bit of a replicate that stops: its theta is copied
-//            through from then on.  The chunk ends when all have stopped; its theta go to the B x T result, which a last
-//            kernel reduces to mean and variance per transcript
+//            Philox4x32-10 by (draw, replicate), a binary search in the scanned counts, an integer atomicAdd), the EM runs over
+//            the chunk in buffers of the call, and its theta go to the B x T result, which a last kernel reduces to mean and
+//            variance per transcript
 //   genes    (br_quant_genes, after finish) a lane per label entry makes (class << 32) | gene of the label; the radix driver sorts
 //            the L keys, the heads of equal keys are the distinct (class, gene) entries and a scan places them in a gene-label
 //            arena, a class's gene list where its labels were; a hash of every list (a lane, or a wave above 64 genes), then
@@ -91,6 +94,10 @@
 
 using namespace br;
 
+// The buffers of an EM over W replicates (quant_em_alloc): theta and theta w, each twice, T W doubles; q, C W; "vb": the partials of
+// S, W per 256 transcripts, and psi(S)
+struct QEmBufs { ColBuf theta[2], x[2], q, vb_part, vb_psi; };
+
 struct br_quant : Accum {
   int64_t n_tx = 0;
   std::vector<int64_t> lens;   // empty: no lengths were given
@@ -116,8 +123,8 @@ struct br_quant : Accum {
   ColBuf t_cls, t_off, uniq, ambig, big_cls, big_tx;     // after finish
   ColBuf name_cls;                                       // "keep_names": per name its class, from finish on
   ColBuf post;                                           // the posteriors, per label entry, once they were asked for after the EM
-  ColBuf theta[2], x[2], w, qv;                          // em
-  ColBuf prior, vb_part, vb_psi;                         // "vb": p per transcript (held from the first EM or bootstrap on); the point EM's partials and psi(S)
+  QEmBufs em;                                            // the point EM's, held: theta[cur] and x[cur] are its result
+  ColBuf w, prior;                                       // per transcript; "vb": p, held from the first EM or bootstrap on
   ColBuf fld_stage, fld_total, eff;                      // "eff_len": fld_max + 1 bins + Q_FLD_SIDE counters each (an add's, the run's); per transcript
   size_t fld_words() const { return (size_t)fld_max + 1 + Q_FLD_SIDE; }
   int fld_tables() {                                     // (zeroed once; a commit leaves the add's table zero again)
@@ -587,8 +594,7 @@ static int quant_put_w(br_quant *c) {
   return BR_OK;
 }
 // "vb": p per transcript on the device -- the prior, or per nucleotide the prior times eff (with "eff_len") or the length, 0 where
-// the length is <= 0 -- and the caller's checks: the prior per nucleotide needs lengths
-static bool quant_vb_ready(const br_quant *c) { return !(c->vb && c->vb_per_nt && c->lens.empty()); }
+// the length is <= 0 (quant_em_ready: with lengths)
 static int quant_put_prior(br_quant *c) {
   const size_t T = (size_t)c->n_tx;
   RC(c->alloc(c->prior, (T + 1) * 8));
@@ -613,77 +619,94 @@ static int quant_host_x(br_quant *c, std::vector<double> &x) {
   x.resize(T);
   if (!T) return BR_OK;
   if (!c->vb) {
-    HIPCHK(hipMemcpyAsync(x.data(), c->x[c->cur].p, T * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(x.data(), c->em.x[c->cur].p, T * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return BR_OK;
   }
   std::vector<double> w(T);
-  HIPCHK(hipMemcpyAsync(x.data(), c->theta[c->cur].p, T * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipMemcpyAsync(x.data(), c->em.theta[c->cur].p, T * 8, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipMemcpyAsync(w.data(), c->w.p, T * 8, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
   for (size_t t = 0; t < T; t++) x[t] = x[t] * w[t];   // (built without contraction)
   return BR_OK;
 }
-// the tables of the EM; q: a double per class (and replicate)
-static QEmArgs quant_em_args(const br_quant *c, double *q) {
-  QEmArgs E{};
-  E.n_cls = c->cls.n_cls; E.n_tx = c->n_tx;
-  E.label_off = c->cls.loff.as<uint64_t>(); E.labels = c->cls.labels.as<uint32_t>(); E.cnt = c->cls.cnt.as<uint64_t>();
-  E.t_off = c->t_off.as<uint64_t>(); E.t_cls = c->t_cls.as<uint32_t>();
-  E.big_cls = c->big_cls.as<uint32_t>(); E.n_big_cls = c->n_big_cls; E.big_tx = c->big_tx.as<uint32_t>(); E.n_big_tx = c->n_big_tx;
-  E.w = c->w.as<double>(); E.q = q;
-  return E;
+// what br_quant_em and br_quant_bootstrap both need: effective lengths are a length normalisation, and "vb"'s prior per nucleotide
+// needs lengths
+static bool quant_em_ready(const br_quant *c) {
+  if (!c || !c->finished) return false;
+  return !(c->eff_len && (!c->length_norm || c->lens.empty())) && !(c->vb && c->vb_per_nt && c->lens.empty());
 }
-
-extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
-  if (!c || !c->finished) return BR_ERR_INVALID_ARG;
-  if (c->eff_len && (!c->length_norm || c->lens.empty())) return BR_ERR_INVALID_ARG;   // effective lengths are a length normalisation
-  if (!quant_vb_ready(c)) return BR_ERR_INVALID_ARG;
-  const ScopeTimer timer;
-  HIPCHK(hipSetDevice(c->device));
+// w, "vb"'s p and the buffers of an EM over W replicates
+static int quant_em_alloc(br_quant *c, QEmBufs &b, size_t W) {
+  const size_t T = (size_t)c->n_tx, C = (size_t)c->cls.n_cls;
+  RC(quant_put_w(c));
+  for (int k = 0; k < 2; k++) { RC(c->alloc(b.theta[k], (T * W + 1) * 8)); RC(c->alloc(b.x[k], (T * W + 1) * 8)); }
+  RC(c->alloc(b.q, (C * W + 1) * 8));
+  if (c->vb) { RC(quant_put_prior(c)); RC(c->alloc(b.vb_part, ((T + 255) / 256 * W + 1) * 8)); RC(c->alloc(b.vb_psi, 64 * 8)); }
+  return BR_OK;
+}
+// where an EM ended: the buffer that holds theta and x, and per replicate the iteration it stopped at and the relative change read there
+struct QEmEnd { int cur = 0; int32_t iters[64] = {}; double rel[64] = {}; };
+// One EM from theta = 1 to its end over b, as a chunk of 1 << lw replicates of which the first n_rep run: on the resampled counts
+// boot_cnt, or -- NULL, with lw = 0 and n_rep = 1 -- the point EM on the observed ones.  rel: a word per replicate of the chunk.
+// Every 16th iteration and the last are looks: the transcript kernel leaves every replicate's largest relative change, the host
+// reads them and a replicate that is below the tolerance, or at the last iteration, stops -- frozen at this iteration's theta
+static int quant_em_run(br_quant *c, QEmBufs &b, const uint32_t *boot_cnt, int lw, int n_rep, unsigned long long *rel, QEmEnd *end) {
   hipStream_t st = c->st;
-  const int64_t T = c->n_tx, C = c->cls.n_cls;
-  const size_t t1 = (size_t)T + 1;
-  HIPCHK(hipStreamSynchronize(st));
-  c->drop(c->post);   // (the posteriors of an earlier EM)
-  for (int k = 0; k < 2; k++) { RC(c->alloc(c->theta[k], t1 * 8)); RC(c->alloc(c->x[k], t1 * 8)); }
-  RC(quant_put_w(c)); RC(c->alloc(c->qv, (size_t)(C + 1) * 8));
-  if (c->vb) { RC(quant_put_prior(c)); RC(c->alloc(c->vb_part, (size_t)((T + 255) / 256 + 1) * 8)); RC(c->alloc(c->vb_psi, 64 * 8)); }
+  const int64_t T = c->n_tx;
+  const size_t W = (size_t)1 << lw;
+  QEmArgs A{};
+  A.n_cls = c->cls.n_cls; A.n_tx = T;
+  A.label_off = c->cls.loff.as<uint64_t>(); A.labels = c->cls.labels.as<uint32_t>(); A.cnt = c->cls.cnt.as<uint64_t>();
+  A.t_off = c->t_off.as<uint64_t>(); A.t_cls = c->t_cls.as<uint32_t>();
+  A.big_cls = c->big_cls.as<uint32_t>(); A.n_big_cls = c->n_big_cls; A.big_tx = c->big_tx.as<uint32_t>(); A.n_big_tx = c->n_big_tx;
+  A.w = c->w.as<double>(); A.q = b.q.as<double>();
+  A.boot_cnt = boot_cnt; A.lw = lw;
+  A.active = n_rep >= 64 ? ~0ull : (1ull << n_rep) - 1ull;
   // "vb": x from alpha, after the transcript kernel and for alpha = 1 at the start (three launches more an iteration)
   auto vb_x = [&](int k) {
-    if (c->vb) launch_q_vb_x(st, c->theta[k].as<double>(), c->prior.as<double>(), c->w.as<double>(), T, 0, 1ull, c->vb_part.as<double>(), c->vb_psi.as<double>(), c->x[k].as<double>());
+    if (c->vb) launch_q_vb_x(st, b.theta[k].as<double>(), c->prior.as<double>(), A.w, T, lw, A.active, b.vb_part.as<double>(), b.vb_psi.as<double>(), b.x[k].as<double>());
   };
-  const std::vector<double> one((size_t)T, 1.0);
-  if (T) {
-    HIPCHK(hipMemcpyAsync(c->theta[0].p, one.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->x[0].p, c->w.p, (size_t)T * 8, hipMemcpyDeviceToDevice, st));   // theta w at theta = 1
-  }
+  launch_q_em_init(st, A.w, T, lw, b.theta[0].as<double>(), b.x[0].as<double>());
   vb_x(0);
-  const QEmArgs E = quant_em_args(c, c->qv.as<double>());
-  unsigned long long *d_rel = (unsigned long long *)(c->small.as<uint64_t>() + QS_REL);
+  uint64_t bits[64];
   int cur = 0;
   int64_t it = 0;
-  double rel = 0.0;
-  while (it < c->max_iters) {
+  while (A.active && it < c->max_iters) {
     it++;
     const bool look = it % 16 == 0 || it == c->max_iters;
-    if (look) HIPCHK(hipMemsetAsync(d_rel, 0, 8, st));
-    launch_q_em_classes(st, E, c->x[cur].as<double>());
-    launch_q_em_tx(st, E, c->theta[cur].as<double>(), c->x[cur].as<double>(), c->theta[cur ^ 1].as<double>(), c->x[cur ^ 1].as<double>(), look ? d_rel : nullptr);
+    if (look) HIPCHK(hipMemsetAsync(rel, 0, W * 8, st));
+    launch_q_em_classes(st, A, b.x[cur].as<double>());
+    launch_q_em_tx(st, A, b.theta[cur].as<double>(), b.x[cur].as<double>(), b.theta[cur ^ 1].as<double>(), b.x[cur ^ 1].as<double>(), look ? rel : nullptr);
     cur ^= 1;
     vb_x(cur);
     if (!look) continue;
-    uint64_t bits = 0;
-    HIPCHK(hipMemcpyAsync(&bits, d_rel, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(bits, rel, W * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    memcpy(&rel, &bits, 8);
-    if (rel < c->tolerance) break;
+    for (int j = 0; j < n_rep; j++) {
+      if (!((A.active >> j) & 1ull)) continue;
+      double r;
+      memcpy(&r, &bits[j], 8);
+      if (r < c->tolerance || it == c->max_iters) { A.active &= ~(1ull << j); end->iters[j] = (int32_t)it; end->rel[j] = r; }
+    }
   }
-  HIPCHK(hipStreamSynchronize(st));
-  c->cur = cur; c->em_done = true;
+  end->cur = cur;
+  return BR_OK;
+}
+
+extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
+  if (!quant_em_ready(c)) return BR_ERR_INVALID_ARG;
+  const ScopeTimer timer;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->st));
+  c->drop(c->post);   // (the posteriors of an earlier EM)
+  RC(quant_em_alloc(c, c->em, 1));
+  QEmEnd end;
+  RC(quant_em_run(c, c->em, nullptr, 0, 1, (unsigned long long *)(c->small.as<uint64_t>() + QS_REL), &end));
+  c->cur = end.cur; c->em_done = true;
   c->em_s = timer.seconds();
-  if (n_iters) *n_iters = (int32_t)it;
-  if (rel_change) *rel_change = rel;
+  if (n_iters) *n_iters = end.iters[0];
+  if (rel_change) *rel_change = end.rel[0];
   return BR_OK;
 }
 
@@ -691,7 +714,7 @@ extern "C" int br_quant_em(br_quant *c, int32_t *n_iters, double *rel_change) {
 static int quant_post(br_quant *c) {
   if (c->post.p) return BR_OK;
   RC(c->alloc(c->post, (size_t)(c->cls.n_lab + 1) * 8));
-  launch_q_post(c->st, c->cls.loff.as<uint64_t>(), c->cls.labels.as<uint32_t>(), c->cls.n_cls, c->vb ? c->x[c->cur].as<double>() : c->theta[c->cur].as<double>(),
+  launch_q_post(c->st, c->cls.loff.as<uint64_t>(), c->cls.labels.as<uint32_t>(), c->cls.n_cls, c->vb ? c->em.x[c->cur].as<double>() : c->em.theta[c->cur].as<double>(),
                 c->vb ? nullptr : c->w.as<double>(), c->post.as<double>());   // ("vb": x itself)
   HIPCHK(hipStreamSynchronize(c->st));
   return BR_OK;
@@ -733,13 +756,9 @@ static int quant_boot_cum(br_quant *c) {
   HIPCHK(hipStreamSynchronize(st));
   return BR_OK;
 }
-static bool quant_boot_ready(const br_quant *c) {
-  if (!c || !c->finished || c->bootstraps == 0) return false;
-  return !(c->eff_len && (!c->length_norm || c->lens.empty())) && quant_vb_ready(c);   // (what br_quant_em refuses)
-}
 
 extern "C" int br_quant_bootstrap(br_quant *c, int32_t *n_iters) {
-  if (!quant_boot_ready(c)) return BR_ERR_INVALID_ARG;
+  if (!quant_em_ready(c) || c->bootstraps == 0) return BR_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->st;
   const int64_t T = c->n_tx, C = c->cls.n_cls, B = c->bootstraps;
@@ -749,20 +768,13 @@ extern "C" int br_quant_bootstrap(br_quant *c, int32_t *n_iters) {
   while ((1 << lw) < per) lw++;
   const size_t W = (size_t)1 << lw;
   c->boot_sample_s = c->boot_em_s = 0; c->boot_iters = 0;
-  RC(quant_put_w(c));
   RC(quant_boot_cum(c));
   RC(c->alloc(c->boot_res, ((size_t)B * (size_t)T + 1) * 8));
-  ColBuf th[2], xx[2], q, cnt, d_rel, part, psi;
-  DropGuard chunk_bufs{c, {&th[0], &th[1], &xx[0], &xx[1], &q, &cnt, &d_rel, &part, &psi}};
-  for (int k = 0; k < 2; k++) { RC(c->alloc(th[k], ((size_t)T * W + 1) * 8)); RC(c->alloc(xx[k], ((size_t)T * W + 1) * 8)); }
-  RC(c->alloc(q, ((size_t)C * W + 1) * 8)); RC(c->alloc(cnt, ((size_t)C * W + 1) * 4)); RC(c->alloc(d_rel, 64 * 8));
-  if (c->vb) { RC(quant_put_prior(c)); RC(c->alloc(part, ((size_t)((T + 255) / 256) * W + 1) * 8)); RC(c->alloc(psi, 64 * 8)); }
-  QBootArgs A{};
-  A.E = quant_em_args(c, q.as<double>());
-  A.E.cnt = nullptr;   // (a replicate's counts are its own: A.cnt)
-  A.cnt = cnt.as<uint32_t>(); A.lw = lw;
-  unsigned long long *rel = d_rel.as<unsigned long long>();
-  uint64_t bits[64];
+  QEmBufs b;
+  ColBuf cnt, d_rel;
+  DropGuard chunk_bufs{c, {&b.theta[0], &b.theta[1], &b.x[0], &b.x[1], &b.q, &b.vb_part, &b.vb_psi, &cnt, &d_rel}};
+  RC(quant_em_alloc(c, b, W));
+  RC(c->alloc(cnt, ((size_t)C * W + 1) * 4)); RC(c->alloc(d_rel, 64 * 8));
   for (int64_t b0 = 0; b0 < B; b0 += per) {
     const int n_rep = (int)std::min<int64_t>(per, B - b0);
     {
@@ -772,37 +784,13 @@ extern "C" int br_quant_bootstrap(br_quant *c, int32_t *n_iters) {
       HIPCHK(hipStreamSynchronize(st));
     }
     ScopeTimer timer(&c->boot_em_s);
-    launch_q_boot_init(st, c->w.as<double>(), T, lw, th[0].as<double>(), xx[0].as<double>());
-    A.active = n_rep >= 64 ? ~0ull : (1ull << n_rep) - 1ull;
-    auto vb_x = [&](int k) {   // as br_quant_em's, for the replicates that still run
-      if (c->vb) launch_q_vb_x(st, th[k].as<double>(), c->prior.as<double>(), c->w.as<double>(), T, lw, A.active, part.as<double>(), psi.as<double>(), xx[k].as<double>());
-    };
-    vb_x(0);
-    int cur = 0;
-    int64_t it = 0;
-    while (A.active && it < c->max_iters) {
-      it++;
-      const bool look = it % 16 == 0 || it == c->max_iters;
-      if (look) HIPCHK(hipMemsetAsync(rel, 0, W * 8, st));
-      launch_q_boot_classes(st, A, xx[cur].as<double>());
-      launch_q_boot_tx(st, A, th[cur].as<double>(), xx[cur].as<double>(), th[cur ^ 1].as<double>(), xx[cur ^ 1].as<double>(), look ? rel : nullptr);
-      cur ^= 1;
-      vb_x(cur);
-      if (!look) continue;
-      HIPCHK(hipMemcpyAsync(bits, rel, W * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      for (int j = 0; j < n_rep; j++) {
-        if (!((A.active >> j) & 1ull)) continue;
-        double r;
-        memcpy(&r, &bits[j], 8);
-        if (r < c->tolerance || it == c->max_iters) {   // frozen at this iteration's theta
-          A.active &= ~(1ull << j);
-          c->boot_iters += it;
-          if (n_iters) n_iters[b0 + j] = (int32_t)it;
-        }
-      }
+    QEmEnd end;
+    RC(quant_em_run(c, b, cnt.as<uint32_t>(), lw, n_rep, d_rel.as<unsigned long long>(), &end));
+    for (int j = 0; j < n_rep; j++) {
+      c->boot_iters += end.iters[j];
+      if (n_iters) n_iters[b0 + j] = end.iters[j];
     }
-    launch_q_boot_store(st, th[cur].as<double>(), T, lw, n_rep, c->boot_res.as<double>() + (size_t)b0 * (size_t)T);
+    launch_q_boot_store(st, b.theta[end.cur].as<double>(), T, lw, n_rep, c->boot_res.as<double>() + (size_t)b0 * (size_t)T);
     HIPCHK(hipStreamSynchronize(st));
   }
   c->boot_done = true;   // the result is there, and the parameters are fixed from here on
@@ -880,7 +868,7 @@ extern "C" int br_quant_result(br_quant *c, double *theta, double *tpm, uint64_t
   const size_t T = (size_t)c->n_tx;
   if (!T) return BR_OK;
   std::vector<double> x;
-  if (theta) HIPCHK(hipMemcpyAsync(theta, c->theta[c->cur].p, T * 8, hipMemcpyDeviceToHost, st));
+  if (theta) HIPCHK(hipMemcpyAsync(theta, c->em.theta[c->cur].p, T * 8, hipMemcpyDeviceToHost, st));
   if (tpm) RC(quant_host_x(c, x));
   if (unique) HIPCHK(hipMemcpyAsync(unique, c->uniq.p, T * 8, hipMemcpyDeviceToHost, st));
   if (ambig) HIPCHK(hipMemcpyAsync(ambig, c->ambig.p, T * 8, hipMemcpyDeviceToHost, st));
@@ -998,7 +986,7 @@ extern "C" int br_quant_gene_result(br_quant *c, double *num_reads, double *tpm,
     if (T) HIPCHK(hipMemcpyAsync(d_tpm.p, tpm_t.data(), T * 8, hipMemcpyHostToDevice, st));
     if (T && has_lens) HIPCHK(hipMemcpyAsync(d_lens.p, c->lens.data(), T * 8, hipMemcpyHostToDevice, st));
     double *o = out.as<double>();
-    launch_qg_sums(st, c->gene.toff.as<uint64_t>(), c->gene.tx.as<uint32_t>(), (int64_t)G, c->theta[c->cur].as<double>(), d_tpm.as<double>(),
+    launch_qg_sums(st, c->gene.toff.as<uint64_t>(), c->gene.tx.as<uint32_t>(), (int64_t)G, c->em.theta[c->cur].as<double>(), d_tpm.as<double>(),
                    has_lens ? d_lens.as<int64_t>() : nullptr, eff_length ? c->eff.as<double>() : nullptr, o, o + G, o + 2 * G, eff_length ? o + 3 * G : nullptr);
     if (num_reads) HIPCHK(hipMemcpyAsync(num_reads, o, G * 8, hipMemcpyDeviceToHost, st));
     if (tpm) HIPCHK(hipMemcpyAsync(tpm, o + G, G * 8, hipMemcpyDeviceToHost, st));

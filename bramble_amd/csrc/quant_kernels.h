@@ -88,48 +88,47 @@ void launch_q_bin(hipStream_t st, const uint64_t *off, int64_t n, uint32_t *list
 void launch_q_counts(hipStream_t st, const uint32_t *t_cls, const uint64_t *t_off, const uint64_t *label_off, const uint64_t *cnt,
                      int64_t n_tx, const uint32_t *big, uint32_t n_big, uint64_t *uniq, uint64_t *ambig);
 
-// EM.  x[t] = theta[t] * w[t].  One iteration: launch_q_em_classes (q[c] = n_c / sum of x over the class, 0 when that is 0), then
-// launch_q_em_tx (theta'[t] = x[t] * sum of q over the classes of t in ascending class order; x'[t] = theta'[t] * w[t]).
-// rel != NULL: atomicMax of the bits of |theta' - theta| / theta' over theta' > 1e-8 (non-negative doubles order like their bits)
+// EM.  x = theta * w.  It runs over a chunk of W = 1 << lw replicates (W <= 64): theta, x (n_tx * W), q and the resampled counts
+// (n_cls * W) hold replicate j of item i at [i * W + j].  The point EM is the chunk of one replicate (lw = 0, active = 1) on the
+// observed counts, and has instantiations of its own in which those are compile-time facts.  One iteration, per replicate in
+// `active`: launch_q_em_classes (q[c] = n_c / sum of x over the class, 0 when that is 0), then launch_q_em_tx (theta'[t] = x[t] *
+// sum of q over the classes of t in ascending class order; x'[t] = theta'[t] * w[t]); a frozen replicate's theta and x are copied
+// through.  rel != NULL: W words, rel[j] takes the atomicMax of the bits of |theta' - theta| / theta' over theta' > 1e-8 of replicate
+// j (non-negative doubles order like their bits)
+constexpr int Q_BOOT_CHUNK = 16;   // the bootstrap's default W: a gather of 16 doubles is one 128-byte line
 struct QEmArgs {
   int64_t n_cls, n_tx;
-  const uint64_t *label_off; const uint32_t *labels; const uint64_t *cnt;
+  const uint64_t *label_off; const uint32_t *labels;
+  const uint64_t *cnt;        // the observed counts, n_cls: the point EM's (a chunk does not read them)
   const uint64_t *t_off; const uint32_t *t_cls;
   const uint32_t *big_cls; uint32_t n_big_cls; const uint32_t *big_tx; uint32_t n_big_tx;
   const double *w;
-  double *q;
+  double *q;                  // n_cls * W
+  // a chunk's; the point instantiations ignore the three
+  const uint32_t *boot_cnt;   // the resampled counts, n_cls * W
+  int lw;
+  uint64_t active;            // bit j: replicate j of the chunk still runs
 };
+// theta = 1, x = w for every replicate of the chunk
+void launch_q_em_init(hipStream_t st, const double *w, int64_t n_tx, int lw, double *theta, double *x);
+// boot_cnt == NULL: the point EM
 void launch_q_em_classes(hipStream_t st, const QEmArgs &E, const double *x);
 void launch_q_em_tx(hipStream_t st, const QEmArgs &E, const double *theta, const double *x, double *theta_out, double *x_out,
                     unsigned long long *rel);
 
-// Bootstrap replicates (definitions: bramble_amd.h, br_quant).  A chunk is W = 1 << lw replicates (W <= 64) that run together:
-// theta, x (n_tx * W), q and the resampled counts (n_cls * W) hold replicate j of item i at [i * W + j].
-constexpr int Q_BOOT_CHUNK = 16;   // the default W: a gather of 16 doubles is one 128-byte line
-struct QBootArgs {
-  QEmArgs E;             // the tables of the point EM (cnt is not read); q: n_cls * W
-  const uint32_t *cnt;   // the resampled counts, n_cls * W
-  int lw;
-  uint64_t active;       // bit j: replicate j of the chunk still runs; a frozen one's theta and x are copied through
-};
+// Bootstrap replicates (definitions: bramble_amd.h, br_quant).
 // the resampled counts of replicates b_first .. b_first + n_rep - 1: one lane a draw (Philox4x32-10 under `seed`, counter (draw,
 // replicate), rank = high half of u * n, class by binary search in cum, the exclusive prefix sums of the counts with cum[n_cls] = n),
 // one integer atomicAdd each into out[c * stride_c + (b - b_first) * stride_b], which the caller has zeroed
 void launch_q_boot_sample(hipStream_t st, const uint64_t *cum, int64_t n_cls, uint64_t n, uint64_t seed, uint32_t b_first, uint32_t n_rep,
                           uint32_t *out, int64_t stride_c, int64_t stride_b);
-// theta = 1, x = w for every replicate of the chunk
-void launch_q_boot_init(hipStream_t st, const double *w, int64_t n_tx, int lw, double *theta, double *x);
-// launch_q_em_classes / launch_q_em_tx over the chunk; rel != NULL: W words, one per replicate
-void launch_q_boot_classes(hipStream_t st, const QBootArgs &B, const double *x);
-void launch_q_boot_tx(hipStream_t st, const QBootArgs &B, const double *theta, const double *x, double *theta_out, double *x_out,
-                      unsigned long long *rel);
 // out[j * n_tx + t] = theta[t * W + j] for j < n_rep
 void launch_q_boot_store(hipStream_t st, const double *theta, int64_t n_tx, int lw, int n_rep, double *out);
 // mean and variance (over n_boot - 1; 0 for n_boot = 1) per transcript of the n_boot x n_tx result, summed in replicate order
 void launch_q_boot_summary(hipStream_t st, const double *res, int64_t n_tx, int32_t n_boot, double *mean, double *var);
 
 // Variational Bayes (definitions: bramble_amd.h, br_quant, `variational`), for the point EM (lw = 0, active = 1) and a chunk alike.
-// After launch_q_em_tx / launch_q_boot_tx have written theta (alpha'): x[t * W + j] = exp(psi(theta + prior[t]) - psi(S_j)) * w[t]
+// After launch_q_em_tx has written theta (alpha'): x[t * W + j] = exp(psi(theta + prior[t]) - psi(S_j)) * w[t]
 // for every replicate j in `active`, S_j the sum of theta + prior over the transcripts -- per block of 256 transcripts a partial
 // (part: ceil(n_tx / 256) * W doubles), the partials in a fixed order (psi_s: W doubles), no atomics.  Three launches
 void launch_q_vb_x(hipStream_t st, const double *theta, const double *prior, const double *w, int64_t n_tx, int lw, uint64_t active, double *part,

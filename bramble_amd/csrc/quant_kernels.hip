@@ -10,11 +10,11 @@
 //            k_q_post, after the EM: a lane per class, the posteriors of its label entries
 //   table    radix passes over (transcript, label entry) + k_q_transpose: per transcript its classes, ascending; k_q_bin;
 //            k_q_counts: unique / ambiguous names per transcript
-//   EM       k_q_em_classes / k_q_em_tx, a lane per item of up to Q_WAVE_ITEMS entries and a wave per larger one
+//   EM       k_q_em_init; k_q_em_classes / k_q_em_tx over a chunk of W replicates with the replicate innermost, a lane per (item,
+//            replicate) of up to Q_WAVE_ITEMS entries and a wave per larger item; the point EM is their instantiation for W = 1
 //   vb       k_q_vb_part / k_q_vb_sum / k_q_vb_x behind the EM's two kernels: x = exp(psi(alpha + p) - psi(S)) w, S without atomics
-//   bootstrap  k_q_boot_sample (a lane per draw: Philox4x32-10, a binary search in the scanned counts, an integer atomicAdd);
-//            k_q_boot_classes / k_q_boot_tx, the EM over a chunk of W replicates with the replicate innermost, a lane per (item,
-//            replicate) and a wave per larger item; k_q_boot_store, k_q_boot_summary
+//   bootstrap  k_q_boot_sample (a lane per draw: Philox4x32-10, a binary search in the scanned counts, an integer atomicAdd), the
+//            EM's kernels on the resampled counts, k_q_boot_store, k_q_boot_summary
 //   genes    k_qg_key + radix passes + k_qg_flag + scan + k_qg_arena: a class's distinct genes, ascending; k_qg_hash (a lane, or a
 //            wave above Q_WAVE_ITEMS genes); the classes' kernels on the gene lists -- radix passes, k_q_heads, k_q_resolve,
 //            k_q_class_key, k_q_class_fill -- with k_qg_member_cnt + scan for the members' counts (an item's weight); k_qg_labels
@@ -524,26 +524,16 @@ __global__ void __launch_bounds__(256) k_q_counts(const uint32_t *t_cls, const u
   }
 }
 
-template <bool BIG>
-__global__ void __launch_bounds__(256) k_q_em_classes(QEmArgs E, const double *x) {
-  if (BIG) {
-    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (i >= E.n_big_cls) return;
-    const uint32_t c = E.big_cls[i];
-    double d = 0.0;
-    for (uint64_t e = E.label_off[c] + (uint64_t)lane; e < E.label_off[c + 1]; e += 64) d += x[E.labels[e]];
-    d = wave_sum(d);
-    if (lane == 0) E.q[c] = d > 0.0 ? (double)E.cnt[c] / d : 0.0;
-  } else {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c >= E.n_cls) return;
-    const uint64_t b = E.label_off[c], e1 = E.label_off[c + 1];
-    if (e1 - b > (uint64_t)Q_WAVE_ITEMS) return;
-    double d = 0.0;
-    for (uint64_t e = b; e < e1; e++) d += x[E.labels[e]];
-    E.q[c] = d > 0.0 ? (double)E.cnt[c] / d : 0.0;
-  }
+// ---- EM (the definitions: bramble_amd.h, br_quant) ---------------------------------------------------------------------------------
+// A chunk is W = 1 << lw replicates; x, theta, q and the resampled counts hold replicate j of item i at [i * W + j], so one read of
+// an index table serves W replicates and a gather is W * 8 contiguous bytes.  A replicate's sums do not know W -- a lane's
+// ascending loop, or lane l's entries l, l + 64, ... and the xor tree -- so its bits are those of the EM run alone on its counts.
+// A replicate whose bit in `active` is clear is frozen: its theta and x are copied through.  POINT: the point EM, a chunk of one
+// replicate on the observed counts -- lw = 0, active = 1 and one replicate a walk are compile-time facts, E's own are not read
+__global__ void __launch_bounds__(256) k_q_em_init(const double *w, int64_t n_tx, int lw, double *theta, double *x) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if ((g >> lw) >= n_tx) return;
+  theta[g] = 1.0; x[g] = w[g >> lw];
 }
 
 __device__ __forceinline__ uint64_t rel_bits(double now, double before) {
@@ -551,41 +541,110 @@ __device__ __forceinline__ uint64_t rel_bits(double now, double before) {
   return (uint64_t)__double_as_longlong(fabs(now - before) / now);
 }
 
-template <bool BIG>
-__global__ void __launch_bounds__(256) k_q_em_tx(QEmArgs E, const double *theta, const double *x, double *theta_out, double *x_out,
-                                                 unsigned long long *rel) {
-  uint64_t r = 0;
+constexpr int Q_BOOT_SUB = 4;   // replicates a wave carries through one walk over a large item's entries
+
+template <bool BIG, bool POINT>
+__global__ void __launch_bounds__(256) k_q_em_classes(QEmArgs E, const double *x) {
+  constexpr int SUB = POINT ? 1 : Q_BOOT_SUB;
+  const int lw = POINT ? 0 : E.lw, W = 1 << lw;
+  const uint64_t active = POINT ? 1ull : E.active;
   if (BIG) {
     const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (i >= E.n_big_tx) return;   // (wave-uniform)
-    const uint32_t t = E.big_tx[i];
-    double s = 0.0;
-    for (uint64_t p = E.t_off[t] + (uint64_t)lane; p < E.t_off[t + 1]; p += 64) s += E.q[E.t_cls[p]];
-    s = wave_sum(s);
-    const double now = x[t] * s;
-    if (lane == 0) { theta_out[t] = now; x_out[t] = now * E.w[t]; if (rel) r = rel_bits(now, theta[t]); }
-  } else {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < E.n_tx && E.t_off[t + 1] - E.t_off[t] <= (uint64_t)Q_WAVE_ITEMS) {
-      double s = 0.0;
-      for (uint64_t p = E.t_off[t]; p < E.t_off[t + 1]; p++) s += E.q[E.t_cls[p]];
-      const double now = x[t] * s;
-      theta_out[t] = now; x_out[t] = now * E.w[t];
-      if (rel) r = rel_bits(now, theta[t]);
+    if (i >= E.n_big_cls) return;
+    const uint64_t c = E.big_cls[i];
+    const uint64_t e0 = E.label_off[c], e1 = E.label_off[c + 1];
+    for (int j0 = 0; j0 < W; j0 += SUB) {
+      if (((active >> j0) & ((1ull << SUB) - 1ull)) == 0) continue;
+      double d[SUB];
+#pragma unroll
+      for (int k = 0; k < SUB; k++) d[k] = 0.0;
+      for (uint64_t e = e0 + (uint64_t)lane; e < e1; e += 64) {
+        const double *p = x + (((uint64_t)E.labels[e] << lw) + (uint64_t)j0);
+#pragma unroll
+        for (int k = 0; k < SUB; k++) if (j0 + k < W) d[k] += p[k];
+      }
+#pragma unroll
+      for (int k = 0; k < SUB; k++) {
+        const double s = wave_sum(d[k]);
+        if (lane == 0 && j0 + k < W && ((active >> (j0 + k)) & 1ull)) {
+          const uint64_t g = (c << lw) + (uint64_t)(j0 + k);
+          E.q[g] = s > 0.0 ? (POINT ? (double)E.cnt[g] : (double)E.boot_cnt[g]) / s : 0.0;
+        }
+      }
     }
+  } else {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t c = g >> lw;
+    const int j = (int)(g & (int64_t)(W - 1));
+    if (c >= E.n_cls || !((active >> j) & 1ull)) return;
+    const uint64_t b = E.label_off[c], e1 = E.label_off[c + 1];
+    if (e1 - b > (uint64_t)Q_WAVE_ITEMS) return;
+    double d = 0.0;
+    for (uint64_t e = b; e < e1; e++) d += x[((uint64_t)E.labels[e] << lw) + (uint64_t)j];
+    E.q[g] = d > 0.0 ? (POINT ? (double)E.cnt[g] : (double)E.boot_cnt[g]) / d : 0.0;
   }
-  if (rel) {
-    r = wave_max(r);
-    if ((threadIdx.x & 63) == 0 && r) atomicMax(rel, (unsigned long long)r);
+}
+
+template <bool BIG, bool POINT>
+__global__ void __launch_bounds__(256) k_q_em_tx(QEmArgs E, const double *theta, const double *x, double *theta_out, double *x_out,
+                                                 unsigned long long *rel) {
+  constexpr int SUB = POINT ? 1 : Q_BOOT_SUB;
+  const int lw = POINT ? 0 : E.lw, W = 1 << lw;
+  const uint64_t active = POINT ? 1ull : E.active;
+  const int lane = threadIdx.x & 63;
+  if (BIG) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= E.n_big_tx) return;   // (wave-uniform)
+    const uint64_t t = E.big_tx[i];
+    const uint64_t p0 = E.t_off[t], p1 = E.t_off[t + 1];
+    for (int j0 = 0; j0 < W; j0 += SUB) {
+      if (((active >> j0) & ((1ull << SUB) - 1ull)) == 0) continue;
+      double s[SUB];
+#pragma unroll
+      for (int k = 0; k < SUB; k++) s[k] = 0.0;
+      for (uint64_t p = p0 + (uint64_t)lane; p < p1; p += 64) {
+        const double *qp = E.q + (((uint64_t)E.t_cls[p] << lw) + (uint64_t)j0);
+#pragma unroll
+        for (int k = 0; k < SUB; k++) if (j0 + k < W) s[k] += qp[k];
+      }
+#pragma unroll
+      for (int k = 0; k < SUB; k++) {
+        const double sum = wave_sum(s[k]);
+        if (lane == 0 && j0 + k < W && ((active >> (j0 + k)) & 1ull)) {
+          const uint64_t g = (t << lw) + (uint64_t)(j0 + k);
+          const double now = x[g] * sum;
+          theta_out[g] = now; x_out[g] = now * E.w[t];
+          if (rel) { const uint64_t r = rel_bits(now, theta[g]); if (r) atomicMax(rel + j0 + k, (unsigned long long)r); }
+        }
+      }
+    }
+    if (lane < W && !((active >> lane) & 1ull)) {   // the frozen ones
+      const uint64_t g = (t << lw) + (uint64_t)lane;
+      theta_out[g] = theta[g]; x_out[g] = x[g];
+    }
+  } else {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t t = g >> lw;
+    const int j = (int)(g & (int64_t)(W - 1));
+    uint64_t r = 0;
+    if (t < E.n_tx && E.t_off[t + 1] - E.t_off[t] <= (uint64_t)Q_WAVE_ITEMS) {
+      if ((active >> j) & 1ull) {
+        double s = 0.0;
+        for (uint64_t p = E.t_off[t]; p < E.t_off[t + 1]; p++) s += E.q[((uint64_t)E.t_cls[p] << lw) + (uint64_t)j];
+        const double now = x[g] * s;
+        theta_out[g] = now; x_out[g] = now * E.w[t];
+        if (rel) r = rel_bits(now, theta[g]);
+      } else { theta_out[g] = theta[g]; x_out[g] = x[g]; }
+    }
+    if (rel) {   // lanes l, l + W, ... of a wave hold replicate l: a xor tree over those, then one atomicMax a wave and replicate
+      for (int d = 32; d >= W; d >>= 1) { const uint64_t y = __shfl_xor(r, d); r = y > r ? y : r; }
+      if (lane < W && r) atomicMax(rel + lane, (unsigned long long)r);
+    }
   }
 }
 
 // ---- bootstrap replicates (the definitions: bramble_amd.h, br_quant) -------------------------------------------------------------
-// A chunk is W = 1 << lw replicates; x, theta, q and the resampled counts hold replicate j of item i at [i * W + j], so one read of
-// an index table serves W replicates and a gather is W * 8 contiguous bytes.  Per replicate every sum has the point kernels'
-// shape -- a lane's ascending loop, or lane l's entries l, l + 64, ... and the xor tree -- so a replicate's bits are those of
-// a point EM on its counts.  A replicate whose bit in `active` is clear is frozen: its theta and x are copied through.
 namespace {
 // Philox4x32-10 of counter (c0, c1, c2, 0) under key (k0, k1): the first two output words as one 64-bit number
 __device__ __forceinline__ uint64_t philox_u64(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t k0, uint32_t k1) {
@@ -610,114 +669,6 @@ __global__ void __launch_bounds__(256) k_q_boot_sample(const uint64_t *cum, int6
   int64_t lo = 0, hi = n_cls;            // the last class c with cum[c] <= r (cum[0] = 0: there is one)
   while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (cum[mid] <= r) lo = mid + 1; else hi = mid; }
   atomicAdd(out + (lo - 1) * stride_c + (int64_t)blockIdx.y * stride_b, 1u);
-}
-
-__global__ void __launch_bounds__(256) k_q_boot_init(const double *w, int64_t n_tx, int lw, double *theta, double *x) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if ((g >> lw) >= n_tx) return;
-  theta[g] = 1.0; x[g] = w[g >> lw];
-}
-
-constexpr int Q_BOOT_SUB = 4;   // replicates a wave carries through one walk over a large item's entries
-
-template <bool BIG>
-__global__ void __launch_bounds__(256) k_q_boot_classes(QBootArgs B, const double *x) {
-  const QEmArgs &E = B.E;
-  const int lw = B.lw, W = 1 << lw;
-  if (BIG) {
-    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (i >= E.n_big_cls) return;
-    const uint64_t c = E.big_cls[i];
-    const uint64_t e0 = E.label_off[c], e1 = E.label_off[c + 1];
-    for (int j0 = 0; j0 < W; j0 += Q_BOOT_SUB) {
-      if (((B.active >> j0) & ((1ull << Q_BOOT_SUB) - 1ull)) == 0) continue;
-      double d[Q_BOOT_SUB];
-#pragma unroll
-      for (int k = 0; k < Q_BOOT_SUB; k++) d[k] = 0.0;
-      for (uint64_t e = e0 + (uint64_t)lane; e < e1; e += 64) {
-        const double *p = x + (((uint64_t)E.labels[e] << lw) + (uint64_t)j0);
-#pragma unroll
-        for (int k = 0; k < Q_BOOT_SUB; k++) if (j0 + k < W) d[k] += p[k];
-      }
-#pragma unroll
-      for (int k = 0; k < Q_BOOT_SUB; k++) {
-        const double s = wave_sum(d[k]);
-        if (lane == 0 && j0 + k < W && ((B.active >> (j0 + k)) & 1ull)) {
-          const uint64_t g = (c << lw) + (uint64_t)(j0 + k);
-          E.q[g] = s > 0.0 ? (double)B.cnt[g] / s : 0.0;
-        }
-      }
-    }
-  } else {
-    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t c = g >> lw;
-    const int j = (int)(g & (int64_t)(W - 1));
-    if (c >= E.n_cls || !((B.active >> j) & 1ull)) return;
-    const uint64_t b = E.label_off[c], e1 = E.label_off[c + 1];
-    if (e1 - b > (uint64_t)Q_WAVE_ITEMS) return;
-    double d = 0.0;
-    for (uint64_t e = b; e < e1; e++) d += x[((uint64_t)E.labels[e] << lw) + (uint64_t)j];
-    E.q[g] = d > 0.0 ? (double)B.cnt[g] / d : 0.0;
-  }
-}
-
-// rel != NULL: rel[j] takes the largest relative change of replicate j (atomicMax on the bits, as the point kernel's one word)
-template <bool BIG>
-__global__ void __launch_bounds__(256) k_q_boot_tx(QBootArgs B, const double *theta, const double *x, double *theta_out, double *x_out,
-                                                   unsigned long long *rel) {
-  const QEmArgs &E = B.E;
-  const int lw = B.lw, W = 1 << lw;
-  const int lane = threadIdx.x & 63;
-  if (BIG) {
-    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= E.n_big_tx) return;   // (wave-uniform)
-    const uint64_t t = E.big_tx[i];
-    const uint64_t p0 = E.t_off[t], p1 = E.t_off[t + 1];
-    for (int j0 = 0; j0 < W; j0 += Q_BOOT_SUB) {
-      if (((B.active >> j0) & ((1ull << Q_BOOT_SUB) - 1ull)) == 0) continue;
-      double s[Q_BOOT_SUB];
-#pragma unroll
-      for (int k = 0; k < Q_BOOT_SUB; k++) s[k] = 0.0;
-      for (uint64_t p = p0 + (uint64_t)lane; p < p1; p += 64) {
-        const double *qp = E.q + (((uint64_t)E.t_cls[p] << lw) + (uint64_t)j0);
-#pragma unroll
-        for (int k = 0; k < Q_BOOT_SUB; k++) if (j0 + k < W) s[k] += qp[k];
-      }
-#pragma unroll
-      for (int k = 0; k < Q_BOOT_SUB; k++) {
-        const double sum = wave_sum(s[k]);
-        if (lane == 0 && j0 + k < W && ((B.active >> (j0 + k)) & 1ull)) {
-          const uint64_t g = (t << lw) + (uint64_t)(j0 + k);
-          const double now = x[g] * sum;
-          theta_out[g] = now; x_out[g] = now * E.w[t];
-          if (rel) { const uint64_t r = rel_bits(now, theta[g]); if (r) atomicMax(rel + j0 + k, (unsigned long long)r); }
-        }
-      }
-    }
-    if (lane < W && !((B.active >> lane) & 1ull)) {   // the frozen ones
-      const uint64_t g = (t << lw) + (uint64_t)lane;
-      theta_out[g] = theta[g]; x_out[g] = x[g];
-    }
-  } else {
-    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t t = g >> lw;
-    const int j = (int)(g & (int64_t)(W - 1));
-    uint64_t r = 0;
-    if (t < E.n_tx && E.t_off[t + 1] - E.t_off[t] <= (uint64_t)Q_WAVE_ITEMS) {
-      if ((B.active >> j) & 1ull) {
-        double s = 0.0;
-        for (uint64_t p = E.t_off[t]; p < E.t_off[t + 1]; p++) s += E.q[((uint64_t)E.t_cls[p] << lw) + (uint64_t)j];
-        const double now = x[g] * s;
-        theta_out[g] = now; x_out[g] = now * E.w[t];
-        if (rel) r = rel_bits(now, theta[g]);
-      } else { theta_out[g] = theta[g]; x_out[g] = x[g]; }
-    }
-    if (rel) {   // lanes l, l + W, ... of a wave hold replicate l: a xor tree over those, then one atomicMax a wave and replicate
-      for (int d = 32; d >= W; d >>= 1) { const uint64_t y = __shfl_xor(r, d); r = y > r ? y : r; }
-      if (lane < W && r) atomicMax(rel + lane, (unsigned long long)r);
-    }
-  }
 }
 
 // the chunk's theta (replicate innermost) -> the rows of its first n_rep replicates in the result (replicate-major)
@@ -971,18 +922,6 @@ void launch_q_boot_sample(hipStream_t st, const uint64_t *cum, int64_t n_cls, ui
   hipLaunchKernelGGL(k_q_boot_sample, dim3(blocks256((int64_t)n), n_rep), dim3(256), 0, st, cum, n_cls, n, (uint32_t)seed, (uint32_t)(seed >> 32),
                      b_first, out, stride_c, stride_b);
 }
-void launch_q_boot_init(hipStream_t st, const double *w, int64_t n_tx, int lw, double *theta, double *x) {
-  if (n_tx > 0) hipLaunchKernelGGL(k_q_boot_init, dim3(blocks256(n_tx << lw)), dim3(256), 0, st, w, n_tx, lw, theta, x);
-}
-void launch_q_boot_classes(hipStream_t st, const QBootArgs &B, const double *x) {
-  if (B.E.n_cls > 0) hipLaunchKernelGGL(k_q_boot_classes<false>, dim3(blocks256(B.E.n_cls << B.lw)), dim3(256), 0, st, B, x);
-  if (B.E.n_big_cls) hipLaunchKernelGGL(k_q_boot_classes<true>, dim3((B.E.n_big_cls + 3) / 4), dim3(256), 0, st, B, x);
-}
-void launch_q_boot_tx(hipStream_t st, const QBootArgs &B, const double *theta, const double *x, double *theta_out, double *x_out,
-                      unsigned long long *rel) {
-  if (B.E.n_tx > 0) hipLaunchKernelGGL(k_q_boot_tx<false>, dim3(blocks256(B.E.n_tx << B.lw)), dim3(256), 0, st, B, theta, x, theta_out, x_out, rel);
-  if (B.E.n_big_tx) hipLaunchKernelGGL(k_q_boot_tx<true>, dim3((B.E.n_big_tx + 3) / 4), dim3(256), 0, st, B, theta, x, theta_out, x_out, rel);
-}
 void launch_q_boot_store(hipStream_t st, const double *theta, int64_t n_tx, int lw, int n_rep, double *out) {
   if (n_tx > 0 && n_rep > 0) hipLaunchKernelGGL(k_q_boot_store, dim3(blocks256(n_tx << lw)), dim3(256), 0, st, theta, n_tx, lw, n_rep, out);
 }
@@ -1080,14 +1019,21 @@ void launch_q_counts(hipStream_t st, const uint32_t *t_cls, const uint64_t *t_of
   if (n_tx > 0) hipLaunchKernelGGL(k_q_counts<false>, dim3(blocks256(n_tx)), dim3(256), 0, st, t_cls, t_off, label_off, cnt, n_tx, big, n_big, uniq, ambig);
   if (n_big) hipLaunchKernelGGL(k_q_counts<true>, dim3((n_big + 3) / 4), dim3(256), 0, st, t_cls, t_off, label_off, cnt, n_tx, big, n_big, uniq, ambig);
 }
+void launch_q_em_init(hipStream_t st, const double *w, int64_t n_tx, int lw, double *theta, double *x) {
+  if (n_tx > 0) hipLaunchKernelGGL(k_q_em_init, dim3(blocks256(n_tx << lw)), dim3(256), 0, st, w, n_tx, lw, theta, x);
+}
 void launch_q_em_classes(hipStream_t st, const QEmArgs &E, const double *x) {
-  if (E.n_cls > 0) hipLaunchKernelGGL(k_q_em_classes<false>, dim3(blocks256(E.n_cls)), dim3(256), 0, st, E, x);
-  if (E.n_big_cls) hipLaunchKernelGGL(k_q_em_classes<true>, dim3((E.n_big_cls + 3) / 4), dim3(256), 0, st, E, x);
+  const bool point = !E.boot_cnt;
+  const auto lanes = point ? k_q_em_classes<false, true> : k_q_em_classes<false, false>, waves = point ? k_q_em_classes<true, true> : k_q_em_classes<true, false>;
+  if (E.n_cls > 0) hipLaunchKernelGGL(lanes, dim3(blocks256(E.n_cls << E.lw)), dim3(256), 0, st, E, x);
+  if (E.n_big_cls) hipLaunchKernelGGL(waves, dim3((E.n_big_cls + 3) / 4), dim3(256), 0, st, E, x);
 }
 void launch_q_em_tx(hipStream_t st, const QEmArgs &E, const double *theta, const double *x, double *theta_out, double *x_out,
                     unsigned long long *rel) {
-  if (E.n_tx > 0) hipLaunchKernelGGL(k_q_em_tx<false>, dim3(blocks256(E.n_tx)), dim3(256), 0, st, E, theta, x, theta_out, x_out, rel);
-  if (E.n_big_tx) hipLaunchKernelGGL(k_q_em_tx<true>, dim3((E.n_big_tx + 3) / 4), dim3(256), 0, st, E, theta, x, theta_out, x_out, rel);
+  const bool point = !E.boot_cnt;
+  const auto lanes = point ? k_q_em_tx<false, true> : k_q_em_tx<false, false>, waves = point ? k_q_em_tx<true, true> : k_q_em_tx<true, false>;
+  if (E.n_tx > 0) hipLaunchKernelGGL(lanes, dim3(blocks256(E.n_tx << E.lw)), dim3(256), 0, st, E, theta, x, theta_out, x_out, rel);
+  if (E.n_big_tx) hipLaunchKernelGGL(waves, dim3((E.n_big_tx + 3) / 4), dim3(256), 0, st, E, theta, x, theta_out, x_out, rel);
 }
 
 }  // namespace br
