@@ -444,6 +444,7 @@ extern "C" int br_ctx_set_param(br_ctx *c, const char *key, int64_t v) {
   if (!strcmp(key, "speculate_n")) { if (v < 0) return BR_ERR_INVALID_ARG; c->speculate_n = v; return BR_OK; }
   if (!strcmp(key, "small_n")) { if (v < 0) return BR_ERR_INVALID_ARG; c->small_n = v; return BR_OK; }
   if (!strcmp(key, "deflate_dynamic")) { c->deflate_dynamic = v != 0; return BR_OK; }
+  if (!strcmp(key, "deflate_waves")) { if (v < 0 || v > (1 << 20)) return BR_ERR_INVALID_ARG; c->deflate_waves = (int)v; return BR_OK; }   // test hook, see deflate_device_impl
   if (!strcmp(key, "bam_lanes")) { if (v != 0 && v != 4 && v != 8 && v != 16 && v != 32 && v != 64) return BR_ERR_INVALID_ARG; c->bam_lanes = (int)v; return BR_OK; }
   if (!strcmp(key, "ksw_fast")) { c->ksw_fast = v != 0; return BR_OK; }
   if (!strcmp(key, "ksw_tape_pct")) { if (v < 0 || v > 100) return BR_ERR_INVALID_ARG; c->ksw_tape_pct = (int)v; return BR_OK; }

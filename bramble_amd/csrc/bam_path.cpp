@@ -233,6 +233,7 @@ static int deflate_device_impl(br_ctx *c, const uint8_t *src, uint64_t n, hipStr
   int dyn_waves = 0;
   if (c->deflate_dynamic) {  // persistent waves: as many as the chip holds (6 workgroups of 4 waves per CU by their LDS), a token list each
     uint64_t want = (uint64_t)c->n_cu * 24;
+    if (c->deflate_waves > 0) want = std::min<uint64_t>(want, ((uint64_t)c->deflate_waves + 3) / 4 * 4);   // fewer waves, more blocks each
     dyn_waves = (int)std::min<uint64_t>((nb + 3) / 4 * 4, want / 4 * 4);
     if (dyn_waves < 4) dyn_waves = 4;
     RC(c->z_tokens.ensure((size_t)dyn_waves * DEFLATE_PAYLOAD * 4 + 64));

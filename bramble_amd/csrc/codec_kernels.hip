@@ -10,7 +10,12 @@
 //   k_bgzf_compact    slots -> one dense byte stream (after a scan of the block sizes).
 //
 // The compressed bytes are not part of the parity contract (the reference writes through htslib/zlib);
-// what is checked is that any inflater reproduces the stream (tests/test_gpu_codec.py: Python zlib / gzip).
+// what is checked is that any inflater reproduces the stream (tests/test_gpu_codec.py: Python zlib / gzip and this library's
+// k_inflate) and, token by token with a reader written from RFC 1951 (tests/deflate_ref.py), that the blocks are what these
+// comments say: one final block of the mode's type per BGZF block, complete codes of at most 15 bits behind the flat header,
+// matches of 4 to 258 bytes up to 32768 back found at every length and distance code boundary and up to the last byte, every
+// block within its slot (the bound: kernels.h, DEFLATE_PAYLOAD), and bytes that do not depend on which persistent wave made a
+// block (the "deflate_waves" parameter).
 // The projected stream repeats every read's name/SEQ/QUAL/aux once per compatible transcript a few hundred
 // bytes apart, which is what the hash-table matcher picks up.
 #include <hip/hip_runtime.h>

@@ -127,6 +127,7 @@ struct br_ctx {
   int z_dense_which = 0;           // br_project_bam_staged_nowait: the packed blocks of call j are still on their way home while call j + 1 packs its own
   hipStream_t down_stream = nullptr; hipEvent_t ev_home[2] = {nullptr, nullptr}; std::atomic<bool> home_pending[2] = {{false}, {false}};
   int deflate_dynamic = 1;
+  int deflate_waves = 0;     // "deflate_waves": a cap on k_deflate_dynamic's persistent waves (rounded up to 4), 0: as many as the chip holds; a test hook that makes one wave take many blocks
   int64_t speculate_n = 4194304;
   int speculate = 1;         // large batches are launched from the last call's counts, checked once at the end (run_device_small, big)
   int64_t hist_n = 0; uint64_t hist[4] = {0, 0, 0, 0}; bool hist_simf = false;   // the last call: alignments; matches, arena words, simple-class matches, records

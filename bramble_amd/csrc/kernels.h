@@ -374,7 +374,26 @@ struct BamArgs {
 void launch_bam_scan(hipStream_t st, const BamArgs &B);
 
 // BGZF on the device (codec_kernels.hip)
-#define DEFLATE_PAYLOAD 57344u   // uncompressed bytes per BGZF block: worst case (all 9-bit literals) still fits 64 KiB
+// Uncompressed bytes per BGZF block.  A block is 18 + payload + 8 bytes and BSIZE states at most 65536 (the slot), so a payload
+// may have 65510 bytes.
+//   fixed code    a literal costs at most 9 bits, a match (4 bytes or more) at most 8 + 5 + 5 + 13 = 31: at most 3 + 9 * 57344 + 7
+//                 bits = 64514 bytes, a block of 64540.
+//   dynamic code  167 bytes of header, then the tokens.  build_lengths starts from Shannon lengths ceil(log2(T / f)) over the T
+//                 tokens of the block, which cost below T * (H + 1) bits (H: the entropy of the token histogram); holding a
+//                 symbol at 15 bits and the slack phase only shorten codes.
+//                 With a share p of the tokens matches (at least 4 bytes each; at most 29 length and 30 distance symbols; at most
+//                 5 + 13 extra bits), H <= h(p) + (1 - p) * log2(257) + p * log2(29), so a token costs below
+//                 1 + h(p) + (1 - p) * 8.006 + p * (4.858 + 5.907 + 18) bits and covers 1 + 3 p bytes: at most 9.024 bits a byte
+//                 (at p = 0.012; 9.006 without matches), 64683 bytes of tokens, a payload below 64850 and a block below 64876.
+//                 Not in that figure: the 15-bit phase.  A symbol that wants 16 bits or more (frequency 1 or 2; at most 285 of
+//                 them) adds at most half a unit of 2^-15 to the Kraft sum by staying at 15, so the sum passes one by at most 143
+//                 units, and the phase takes them back a bit at a time from the rarest symbol below 15 bits.  A symbol at its
+//                 Shannon length l has f < T / 2^(l-1) and frees 2^(14-l) units by its first step: below T / 2^13 <= 7 bits a
+//                 unit, about 125 bytes for 143 units.  Repeated steps on one symbol and the last step's overshoot cost more
+//                 per unit and are not bounded here; the margin left for them is 660 bytes.  No block the tests make enters
+//                 this phase on the device (tests/test_gpu_codec.py prints those that do).
+// The largest blocks seen are far below both (tests/test_gpu_codec.py prints them: about 59 K and 61 K).
+#define DEFLATE_PAYLOAD 57344u
 #define DEFLATE_SLOT 65536u
 #define DEFLATE_CRC_CHUNK 896u   // 64 lane-chunks per full block
 struct DeflateArgs {

@@ -1209,7 +1209,7 @@ const char *br_bgzf_codec(void); /* "libdeflate" (bound at run time when present
 int br_ctx_set_profiling(br_ctx *, int enabled);
 /* Launch tuning: "group_lanes" (8|16|32|64 lanes cooperating on one alignment),
  * "blocks_per_cu" (grid size of the grid-stride projection kernels), "bam_lanes" (0, the default: a wave per 32
- * re-encoded records, their byte regions as 16-byte copy tasks; 4..64: that many lanes per record), "deflate_dynamic" (1: per-block Huffman codes, 0: the fixed code),
+ * re-encoded records, their byte regions as 16-byte copy tasks; 4..64: that many lanes per record), "deflate_dynamic" (1: per-block Huffman codes, 0: the fixed code), "deflate_waves" (test hook: a cap on the dynamic coder's persistent waves, rounded up to 4, so that one wave takes many blocks; 0: as many as the chip holds),
  * "pair_bitmask" (1, the default: direct rows intersect two mates' transcript sets as 64-bit masks where their ids span at most 64; 0: as lists always. Same rows.),
  * "emit_rank_tids" (1, the default: that intersection leaves the pair's common transcript ids as a 16-byte word per alignment and the direct-rows emit kernels take a record's rank from it; 0: they gather the kept survivors' ids, no word is stored. Same rows; br_ctx_direct_tidwords.).
  * Short-read presets run the count pass of large batches as a main kernel without the exon walk plus a second one for the
