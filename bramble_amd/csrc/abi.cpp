@@ -439,6 +439,7 @@ extern "C" int br_ctx_set_param(br_ctx *c, const char *key, int64_t v) {
   if (!strcmp(key, "direct_rows")) { c->direct_rows = v != 0; return BR_OK; }
   if (!strcmp(key, "pair_bitmask")) { if (v != 0 && v != 1) return BR_ERR_INVALID_ARG; c->pair_bitmask = v != 0; return BR_OK; }
   if (!strcmp(key, "emit_rank_tids")) { if (v != 0 && v != 1) return BR_ERR_INVALID_ARG; c->emit_rank_tids = v != 0; return BR_OK; }
+  if (!strcmp(key, "emit_general_preset")) { if (v != 0 && v != 1) return BR_ERR_INVALID_ARG; c->emit_general_preset = v != 0; return BR_OK; }
   if (!strcmp(key, "small_batch")) { c->small_batch = v != 0; return BR_OK; }
   if (!strcmp(key, "speculate")) { c->speculate = v != 0; return BR_OK; }
   if (!strcmp(key, "speculate_n")) { if (v < 0) return BR_ERR_INVALID_ARG; c->speculate_n = v; return BR_OK; }

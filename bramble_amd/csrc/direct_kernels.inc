@@ -816,8 +816,19 @@ __global__ void __launch_bounds__(256) k_expand_rows(DirectArgs D) {
 // ---------------------------------------------------------------------------
 // (CLS 2 at five waves per SIMD: 91 VGPRs and no scratch.  At six, the most its LDS allows, the budget is 80 VGPRs and ten
 // of them went to 44 bytes of scratch per lane: 0.80-0.87 ms against 0.73-0.74 now that the class holds only heavy entries.)
-template <int CLS>
+//
+// PRE = 1 (CLS 2 only; "emit_general_preset", launch_emit_rows): the general class of the short-read preset, where the count pass's
+// PRE = 1 applies -- no long-read rules and no small-exon rescue, as constants, so pass 1 of the walk, the slab search of the
+// INS_EXON rule and the skipped-exon rule are not in its code.  Its CIGAR scratch is typed: a lane whose ideal and rewritten
+// CIGAR fit its LDS slot (lds_ideal_fits / lds_out_fits: reads of up to five exons) builds and merges them through LDS
+// pointers (ds_read / ds_write) and touches the arena only to copy a result of three or more ops out.  The lanes that do not
+// fit run the generic (flat) code behind that; a wave without one skips it.  <2, 0> is the kernel of every other preset and
+// the A/B switch's other side.  (0.77 -> 0.55 ms at the bench step, all of it from the typed scratch: the constants alone,
+// six waves per SIMD at 80 VGPRs, cig_base loaded early and the result's first words kept in registers changed nothing or
+// cost time, DESIGN 10.1 rows 43-47.)
+template <int CLS, int PRE = 0>
 __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 5) k_emit_rows(ProjectArgs A, DirectArgs D, int64_t first, int64_t n_end) {
+  static_assert(PRE == 0 || CLS == 2, "the preset instantiation is the general class's");
   __shared__ uint32_t sh_cig[CLS == 1 ? 1 : 256 * LDS_SLOT];
   __shared__ uint16_t sh_mops[CLS == 1 ? 1 : 256];
   if (CLS != 1) {
@@ -827,7 +838,9 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 5) k_emit_rows(ProjectArgs
   const int64_t e64 = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e64 >= n_end) return;
   const DevIndex &ix = A.ix;
-  const DevCfg &cfg = A.cfg;
+  DevCfg cfg_pre = A.cfg;
+  if (PRE) { cfg_pre.long_reads = 0; cfg_pre.ignore_small_exons = 0; cfg_pre.max_error_exon = 0; }
+  const DevCfg &cfg = PRE ? cfg_pre : A.cfg;
   // (the work-list entry and the alignment's records are read once: streaming loads, so that they do not displace the index
   // rows the gathers below come back to -- k_emit_rows<2> 1.84 -> 1.79 ms)
   typedef uint32_t ntl4 __attribute__((ext_vector_type(4)));
@@ -925,9 +938,10 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 5) k_emit_rows(ProjectArgs
   const uint32_t i0 = pay.y & 0x7fffffffu;
   CandOut p1;
   bool plain = false;
-  const uint32_t sb = ix.slab_off[2 * rid + s], se = ix.slab_off[2 * rid + s + 1];
+  uint32_t sb = 0, se = 0;   // (the slab's bounds: the INS_EXON rule's search only)
+  if (!PRE) { sb = ix.slab_off[2 * rid + s]; se = ix.slab_off[2 * rid + s + 1]; }
   if (n_seg == 1) { p1.alive = true; p1.fwpos = h0.pos; p1.rcpos = h0.pos; p1.n_seg = 1; p1.n_gex = 1; p1.i_lastm = i0; p1.last_right_ins = h0.right_ins; p1.last_right_gap = h0.right_gap; }
-  else if (!cfg.long_reads && !cfg.ignore_small_exons) {
+  else if (PRE || (!cfg.long_reads && !cfg.ignore_small_exons)) {
     // short-read presets without --max-error-exon: pass 1's counts are the read's exon count (see k_emit_dense)
     plain = true;
     p1.alive = true; p1.fwpos = h0.pos; p1.rcpos = h0.pos; p1.n_seg = n_seg; p1.n_gex = n_seg; p1.i_lastm = i0;
@@ -938,6 +952,48 @@ __global__ void __launch_bounds__(256, CLS == 1 ? 8 : 5) k_emit_rows(ProjectArgs
   const uint32_t cap = rd.n_real + 2u * ideal_cap;
   const uint64_t slot_off = D.cig_base[a] + (uint64_t)c * cap;
   uint32_t *slot = A.cig_arena + slot_off;
+  if constexpr (PRE != 0) {
+    lds_u32 *lds = (lds_u32 *)&sh_cig[threadIdx.x * LDS_SLOT];
+    lds_cu16 *mops = (lds_cu16 *)&sh_mops[0];
+    Acc acc;
+    uint32_t n_out = 0, n_ideal = 0;
+    uint2 w01 = make_uint2(0, 0);   // the result's first two words
+    const bool t_ideal = lds_ideal_fits(n_seg);
+    bool done = false;
+    if (t_ideal) {
+      IdealSinkT<lds_u32 *> sk;
+      sk.init(lds);
+      walk_pass2(ix, cfg, rd, Ex, s == 1, sb, se, i0, q0, make_uint4(gs, gend, pay.z, 0), make_uint2(r_a.z, r_b.w), h0, p1, acc, sk, no_clip(), no_clip());
+      n_ideal = sk.finish();
+      if (lds_out_fits(rd.n_real, n_ideal)) {
+        lds_u32 *outp = lds + n_ideal;
+        n_out = merge_cigars_t(rc, rd.n_real, lds, n_ideal, outp, mops);
+        w01 = make_uint2(n_out > 0 ? outp[0] : 0u, n_out > 1 ? outp[1] : 0u);   // (ds_read: a wait on LDS alone)
+        for (uint32_t q = 0; n_out > 2 && q < n_out; q++) slot[q] = outp[q];   // (the arena copy: the result)
+        done = true;
+      }
+      // (else the output goes to the arena and the ideal CIGAR stays where it is: the generic merge below reads it through a
+      // flat pointer)
+    }
+    if (__ballot(!done)) {
+      if (!done) {
+        uint32_t *ideal = t_ideal ? (uint32_t *)lds : slot + rd.n_real + ideal_cap;
+        if (!t_ideal) {
+          IdealSink sk;
+          sk.init(ideal);
+          walk_pass2(ix, cfg, rd, Ex, s == 1, sb, se, i0, q0, make_uint4(gs, gend, pay.z, 0), make_uint2(r_a.z, r_b.w), h0, p1, acc, sk, no_clip(), no_clip());
+          n_ideal = sk.finish();
+        }
+        n_out = merge_cigars(rc, rd.n_real, ideal, n_ideal, slot, (const uint16_t *)mops);
+        w01 = make_uint2(n_out > 0 ? slot[0] : 0u, n_out > 1 ? slot[1] : 0u);
+      }
+    }
+    uint64_t cig_ref = slot_off;
+    if (n_out <= 2) cig_ref = (uint64_t)(n_out > 0 ? w01.x : 0u) | ((uint64_t)(n_out > 1 ? w01.y : 0u) << 32);
+    write_row(D, E, a, c, pay.x, (s == 0) ? p1.fwpos : (plain ? acc.last_pos : p1.rcpos), n_out, s == 1, cig_ref,
+              (uint32_t)acc.junc_hits, (uint32_t)acc.ref_consumed);
+    return;
+  }
   uint32_t *lds = &sh_cig[(CLS == 1 ? 0 : threadIdx.x) * LDS_SLOT];
   const bool ideal_lds = ideal_cap <= LDS_IDEAL;
   uint32_t *ideal = ideal_lds ? lds : slot + rd.n_real + ideal_cap;
@@ -995,8 +1051,17 @@ void launch_expand_rows(hipStream_t st, const DirectArgs &D) {
   if (D.n_aln > 0) hipLaunchKernelGGL(k_expand_rows, dim3(grid_for_d(D.n_aln, 256)), dim3(256), 0, st, D);
 }
 // part 1: the work list's simple prefix [0, n_simple), 2: the rest
-void launch_emit_rows(hipStream_t st, const ProjectArgs &A, const DirectArgs &D, int64_t n_kept, int64_t n_simple, int part) {
+// preset ("emit_general_preset"): part 2 runs k_emit_rows<2, 1> where its constants hold -- the count pass's PRE = 1 (launch_count_g)
+// on the direct-rows route, which the similarity filter and -S never take -- and k_emit_rows<2, 0> otherwise
+static inline bool emit_general_preset_applies(const DevCfg &cfg, bool preset) {
+  return preset && !cfg.long_reads && !cfg.ignore_small_exons && !cfg.filter_by_similarity && !cfg.use_fasta;
+}
+void launch_emit_rows(hipStream_t st, const ProjectArgs &A, const DirectArgs &D, int64_t n_kept, int64_t n_simple, int part, bool preset) {
   if (A.n_aln <= 0 || n_kept <= 0) return;
   if (part == 1) { if (n_simple > 0) hipLaunchKernelGGL((k_emit_rows<1>), dim3(grid_for_d(n_simple, 256)), dim3(256), 0, st, A, D, (int64_t)0, n_simple); }
-  else if (n_kept > n_simple) hipLaunchKernelGGL((k_emit_rows<2>), dim3(grid_for_d(n_kept - n_simple, 256)), dim3(256), 0, st, A, D, n_simple, n_kept);
+  else if (n_kept > n_simple) {
+    const dim3 g(grid_for_d(n_kept - n_simple, 256)), b(256);
+    if (emit_general_preset_applies(A.cfg, preset)) hipLaunchKernelGGL((k_emit_rows<2, 1>), g, b, 0, st, A, D, n_simple, n_kept);
+    else hipLaunchKernelGGL((k_emit_rows<2, 0>), g, b, 0, st, A, D, n_simple, n_kept);
+  }
 }

@@ -290,7 +290,8 @@ void launch_pair_big(hipStream_t st, const DirectArgs &D, int n_blocks);
 void launch_scan5(hipStream_t st, const DirectArgs &D, uint64_t *tile_sums, uint64_t *total_out5);
 void launch_group_desc(hipStream_t st, const DirectArgs &D);
 void launch_expand_rows(hipStream_t st, const DirectArgs &D);
-void launch_emit_rows(hipStream_t st, const ProjectArgs &A, const DirectArgs &D, int64_t n_kept, int64_t n_simple, int part);
+void launch_emit_rows(hipStream_t st, const ProjectArgs &A, const DirectArgs &D, int64_t n_kept, int64_t n_simple, int part,
+                      bool preset = true);   // preset: br_ctx_set_param "emit_general_preset" (part 2: k_emit_rows<2, 1> where it applies)
 void launch_big_emit(hipStream_t st, const ProjectArgs &A, const DirectArgs &D, int n_blocks);
 
 // dense copy of the long (> 2 op) rewritten CIGARs for the host (the device rows point into the sparse arena)

@@ -625,7 +625,7 @@ static int run_device_direct(br_ctx *c, const DevCfg &dc, const br_device_batch 
     launch_emit_rows(st, A, D, (int64_t)kept, (int64_t)n_simple, 1);
     RC(pf.end());
     RC(pf.begin(BR_K_EMIT_ROWS));
-    launch_emit_rows(st, A, D, (int64_t)kept, (int64_t)n_simple, 2);
+    launch_emit_rows(st, A, D, (int64_t)kept, (int64_t)n_simple, 2, c->emit_general_preset != 0);
     RC(pf.end());
     RC(big_emit.join());
   } else {
@@ -837,7 +837,7 @@ int ensure_detail(br_ctx *c, hipStream_t st) {
       DirectArgs D = c->dD;
       D.r_x = c->pk_x.as<uint4>();
       launch_emit_rows(st, c->dA, D, c->d_kept, c->d_simple, 1);
-      launch_emit_rows(st, c->dA, D, c->d_kept, c->d_simple, 2);
+      launch_emit_rows(st, c->dA, D, c->d_kept, c->d_simple, 2, c->emit_general_preset != 0);
       launch_big_emit(st, c->dA, D, c->n_cu * 4);
     }
     c->detail_valid = true;

@@ -188,21 +188,32 @@ __device__ __forceinline__ bool classify(bool minus, int status, uint32_t qs, ui
 
 // Ideal-CIGAR accumulator: Cigar::add_operation (include/evaluate.h:108-126).
 // One pending op lives in registers; completed ops go to `buf` (may be null
-// when only the accumulators are wanted).
-struct IdealSink {
-  uint32_t *buf; uint32_t n; uint32_t cur; bool has;
-  __device__ __forceinline__ void init(uint32_t *b) { buf = b; n = 0; cur = 0; has = false; }
+// when only the accumulators are wanted).  P: the buffer's pointer type -- a generic uint32_t * (IdealSink: global or LDS,
+// decided at run time, so every store is a flat one), or lds_u32 * where the buffer is known to be the lane's LDS slot
+// (k_emit_rows<2, 1>: ds_write, which no later vector-memory wait has to cover).
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+typedef __attribute__((address_space(3))) const uint16_t lds_cu16;
+// "null = not wanted" holds for the generic pointers only: a typed LDS pointer is always a buffer, and its address may well be
+// 0 (the block's first LDS byte), which a test against null would take for "none"
+template <class P> struct ptr_may_be_null { static constexpr bool value = true; };
+template <> struct ptr_may_be_null<lds_u32 *> { static constexpr bool value = false; };
+template <> struct ptr_may_be_null<lds_cu16 *> { static constexpr bool value = false; };
+template <class P> __device__ __forceinline__ bool ptr_given(P p) { return !ptr_may_be_null<P>::value || p; }
+template <class P> struct IdealSinkT {
+  P buf; uint32_t n; uint32_t cur; bool has;
+  __device__ __forceinline__ void init(P b) { buf = b; n = 0; cur = 0; has = false; }
   __device__ __forceinline__ void add(uint32_t len, uint32_t op) {
     // one predicated store instead of three exits (the emit kernels are bound by instruction issue)
     const bool same = has && CIG_OP(cur) == op;
     const bool flush = has && !same;
-    if (flush && buf) buf[n] = cur;
+    if (flush && ptr_given(buf)) buf[n] = cur;
     n += flush ? 1u : 0u;
     cur = same ? cur + (len << 4) : CIG_GEN(len, op);
     has = true;
   }
-  __device__ __forceinline__ uint32_t finish() { if (has) { if (buf) buf[n] = cur; n++; has = false; } return n; }
+  __device__ __forceinline__ uint32_t finish() { if (has) { if (ptr_given(buf)) buf[n] = cur; n++; has = false; } return n; }
 };
+typedef IdealSinkT<uint32_t *> IdealSink;
 
 // ExonChainMatch accumulators (include/evaluate.h:168-181, create_match :658-673)
 struct Acc {
@@ -214,7 +225,8 @@ struct Acc {
 };
 
 // build_cigar_match (src/evaluate.cpp:675-786)
-__device__ __forceinline__ void build_match(Acc &m, IdealSink &sk, const Hit &h, int status, uint32_t qs,
+template <class SK>
+__device__ __forceinline__ void build_match(Acc &m, SK &sk, const Hit &h, int status, uint32_t qs,
                                             uint32_t qe, uint32_t gs, uint32_t ge, bool first_match,
                                             bool last_match, bool has_lc, bool has_rc) {
   if (h.left_ins > 0) {
@@ -318,9 +330,10 @@ __device__ __forceinline__ uint32_t merge_action(uint32_t r, uint32_t i) {
 // mops: (merge_action << 8 | merge_ops) as a 16 x 16 table in LDS (k_emit_dense fills it once per block: the kernel is
 // bound by the scalar unit, and the 22-way chain of merge_ops and the case ladder of the loop are most of the merge's
 // control flow), or null = evaluate the chains
-__device__ uint32_t merge_cigars(const RealCig &real, uint32_t n_real,
-                                 const uint32_t *ideal, uint32_t n_ideal, uint32_t *out, const uint16_t *mops = nullptr) {
-#define MERGE_OPS(R, I) ((mops && (I) < 16u) ? (uint32_t)(mops[((R) << 4) | (I)] & 0xffu) : merge_ops((R), (I)))
+// IP / OP / MP: the pointer types of `ideal`, `out` and `mops` (generic, or LDS: see IdealSinkT).
+template <class IP, class OP, class MP>
+__device__ __forceinline__ uint32_t merge_cigars_t(const RealCig &real, uint32_t n_real, IP ideal, uint32_t n_ideal, OP out, MP mops) {
+#define MERGE_OPS(R, I) ((ptr_given(mops) && (I) < 16u) ? (uint32_t)(mops[((R) << 4) | (I)] & 0xffu) : merge_ops((R), (I)))
   uint32_t front_h = 0, front_s = 0, ci = 0;
   if (n_real > 0 && CIG_OP(real[0]) == OP_H) { front_h = CIG_LEN(real[0]); ci++; }
   if (ci < n_real && CIG_OP(real[ci]) == OP_S) front_s = CIG_LEN(real[ci]);
@@ -397,7 +410,7 @@ __device__ uint32_t merge_cigars(const RealCig &real, uint32_t n_real,
     uint32_t real_op = CIG_OP(rw), ideal_op = CIG_OP(iw);
     uint32_t real_rem = CIG_LEN(rw) - real_pos, ideal_rem = CIG_LEN(iw) - ideal_pos;
     // one body for the five cases: what is written and how far either side advances follow from the action code
-    const uint32_t t = mops ? (uint32_t)mops[(real_op << 4) | ideal_op] : ((merge_action(real_op, ideal_op) << 8) | merge_ops(real_op, ideal_op));
+    const uint32_t t = ptr_given(mops) ? (uint32_t)mops[(real_op << 4) | ideal_op] : ((merge_action(real_op, ideal_op) << 8) | merge_ops(real_op, ideal_op));
     const uint32_t act = t >> 8;
     const uint32_t chunk = real_rem < ideal_rem ? real_rem : ideal_rem;
     const bool both = act == 1u || act == 4u;
@@ -432,6 +445,10 @@ __device__ uint32_t merge_cigars(const RealCig &real, uint32_t n_real,
     else { lastw = w; out[nidx++] = w; }
   }
   return nidx;
+}
+__device__ uint32_t merge_cigars(const RealCig &real, uint32_t n_real,
+                                 const uint32_t *ideal, uint32_t n_ideal, uint32_t *out, const uint16_t *mops = nullptr) {
+  return merge_cigars_t(real, n_real, ideal, n_ideal, out, mops);
 }
 
 // Lane-local "does ANY row of the slab pass the tolerance test for this read
@@ -593,7 +610,8 @@ __device__ __forceinline__ void apply_clips(CandOut &o, bool minus, uint32_t pos
 }
 
 // build_cigar_clip (src/evaluate.cpp:824-841)
-__device__ __forceinline__ void build_clip(Acc &m, IdealSink &sk, const ClipSide &c) {
+template <class SK>
+__device__ __forceinline__ void build_clip(Acc &m, SK &sk, const ClipSide &c) {
   for (uint32_t i = 0; i < c.n_ops; i++) {
     uint32_t w = c.ops[i], op = CIG_OP(w), len = CIG_LEN(w);
     sk.add(len, op);
@@ -606,10 +624,11 @@ __device__ __forceinline__ void build_clip(Acc &m, IdealSink &sk, const ClipSide
 // clips (both !ok without -S): a clip segment opens / closes the chain, zeroes the
 // neighbouring match segment's left_ins / right_ins (:489-490,648) and turns on
 // td.has_left_clip / has_right_clip for build_cigar_match.
+template <class SK>
 __device__ __forceinline__ void walk_pass2(const DevIndex &ix, const DevCfg &cfg, const ReadCtx &rd,
                                            const uint4 *E, bool minus, uint32_t sb, uint32_t se, uint32_t i0,
                                            uint2 q0, uint4 e0, uint2 nx, const Hit &h0_in,
-                                           const CandOut &p1, Acc &acc, IdealSink &sk, const ClipSide &L,
+                                           const CandOut &p1, Acc &acc, SK &sk, const ClipSide &L,
                                            const ClipSide &R) {
   acc.init();
   uint32_t k = 0;
@@ -682,6 +701,14 @@ __device__ __forceinline__ bool similarity(const DevCfg &cfg, const Acc &acc, do
 #define BIG_LDS 256     // ... and alignments with more than 64 candidate rows
 #define LDS_SLOT 25     // words of CIGAR scratch per lane (odd: conflict-free)
 #define LDS_IDEAL 10    // ideal CIGAR words kept in LDS (n_seg <= 2)
+// The fit rule of k_emit_rows<2, 1> (typed LDS scratch), stated here and nowhere else.  A lane's slot holds its ideal CIGAR from
+// word 0 and the rewritten CIGAR right behind the ideal's actual length:
+//   ideal in LDS   iff  its capacity 4 * n_seg + 2 <= LDS_SLOT                 (n_seg <= 5; decided before the walk)
+//   output in LDS  iff  the ideal is, and  n_ideal + (n_real + n_ideal) <= LDS_SLOT   (n_real + n_ideal: merge_cigars' bound
+//                                                                               on what it writes; decided after the walk)
+// A lane that fails either test takes the generic code behind the typed one (its wave skips that when no lane needs it).
+__device__ __forceinline__ bool lds_ideal_fits(uint32_t n_seg) { return 4u * n_seg + 2u <= LDS_SLOT; }
+__device__ __forceinline__ bool lds_out_fits(uint32_t n_real, uint32_t n_ideal) { return n_real + 2u * n_ideal <= LDS_SLOT; }
 
 // MODE (count pass of the presets without the similarity filter): 1 = main pass: an alignment with a candidate that
 // needs the full exon walk (three or more read exons, or a two-exon read outside the shortcut) is put on walk_list

@@ -1211,7 +1211,8 @@ int br_ctx_set_profiling(br_ctx *, int enabled);
  * "blocks_per_cu" (grid size of the grid-stride projection kernels), "bam_lanes" (0, the default: a wave per 32
  * re-encoded records, their byte regions as 16-byte copy tasks; 4..64: that many lanes per record), "deflate_dynamic" (1: per-block Huffman codes, 0: the fixed code), "deflate_waves" (test hook: a cap on the dynamic coder's persistent waves, rounded up to 4, so that one wave takes many blocks; 0: as many as the chip holds),
  * "pair_bitmask" (1, the default: direct rows intersect two mates' transcript sets as 64-bit masks where their ids span at most 64; 0: as lists always. Same rows.),
- * "emit_rank_tids" (1, the default: that intersection leaves the pair's common transcript ids as a 16-byte word per alignment and the direct-rows emit kernels take a record's rank from it; 0: they gather the kept survivors' ids, no word is stored. Same rows; br_ctx_direct_tidwords.).
+ * "emit_rank_tids" (1, the default: that intersection leaves the pair's common transcript ids as a 16-byte word per alignment and the direct-rows emit kernels take a record's rank from it; 0: they gather the kept survivors' ids, no word is stored. Same rows; br_ctx_direct_tidwords.),
+ * "emit_general_preset" (1, the default: on the direct-rows route the short-read preset without --max-error-exon emits its general class with the kernel specialised to it, k_emit_rows<2, 1>; 0: with the kernel of every other preset. Read at every launch. Same rows.).
  * Short-read presets run the count pass of large batches as a main kernel without the exon walk plus a second one for the
  * alignments that need it, and launch the emit work list per class; small batches and the similarity-filter presets use
  * one kernel for each. */
