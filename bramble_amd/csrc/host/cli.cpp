@@ -7,7 +7,7 @@
 //   uploader      : br_bam_bundle_stage (host bundles: records to one of three device slots, own copy stream)
 //   runner        : br_project_bam_staged_nowait / br_project_bam_resident (everything between the raw records on the device)
 //   writer thread : BGZF deflate (threaded) -> output file; device-made BGZF blocks or SAM lines (-O sam) go out as they are
-//   consumers     : what else takes something from every projected bundle -- --sort, --quant, --coverage, --unprojected, --quant-bam (cli_output.h: one consumer
+//   consumers     : what else takes something from every projected bundle -- --sort, --dedup, --quant, --coverage, --unprojected, --quant-bam (cli_output.h: one consumer
 //                   per feature).  The runner hands each bundle to every consumer right after its projection call; after the last
 //                   bundle each finishes on the device, writes its files under temporary names and prints its report line.  One of
 //                   them may keep the records (--sort): then the projection leaves them in HBM (BR_OUT_RESIDENT), nothing of a
@@ -53,7 +53,9 @@ void usage(FILE *f) {
           "               [--coverage <cov.bedgraph>] [--coverage-summary <cov.tsv>] [--coverage-primary]\n"
           "               [--coverage-weight unit|nh|em]\n"
           "               [--unprojected <unprojected.bam> [--unprojected-scope record|name]]\n"
-          "               [--quant-bam <post.bam> [--quant-bam-mode tag|sample]]\n\n"
+          "               [--quant-bam <post.bam> [--quant-bam-mode tag|sample]]\n"
+          "               [--dedup unique|directional [--dedup-umi name|tag] [--dedup-umi-sep C] [--dedup-umi-tag XY]\n"
+          "                [--dedup-stats <sizes.tsv>] [--dedup-bam <dedup.bam> [--dedup-bam-mode remove|mark]]]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -125,7 +127,18 @@ void usage(FILE *f) {
           "transcript), split evenly among the read's records on that transcript, a pair's two terms added.  sample: one placement per\n"
           "read name, drawn with probability w (Philox4x32-10 under --quant-seed S: the same seed gives the same file), rewritten to\n"
           "NH:i:1, HI:i:1, primary, the MAPQ of a unique record, with ZW:f:<w>.  BAM whatever -O says; --host-deflate applies.  One more\n"
-          "line in front of the final report: [bramble] posterior BAM: R of N records written for M read names (mode tag|sample; add X.XXs, weigh Y.YYs)\n");
+          "line in front of the final report: [bramble] posterior BAM: R of N records written for M read names (mode tag|sample; add X.XXs, weigh Y.YYs)\n"
+          "--dedup unique|directional: UMI-aware duplicate removal on one GPU, by READ NAME: two read names are copies of one molecule\n"
+          "when they carry the same UMI and were projected to the same set of placements (transcript, unclipped 5' end, strand and mate\n"
+          "bits of every record); directional (umi_tools' default) also joins a UMI to a more abundant one a single mismatch away.  Whole\n"
+          "read names are kept or dropped, so a multi-mapper's records stay together.  The UMI is what follows the last --dedup-umi-sep\n"
+          "character (default _) of the read name (--dedup-umi name, the default: umi_tools extract's convention) or the value of the\n"
+          "--dedup-umi-tag tag (default RX; --dedup-umi tag), at most 32 bytes; a read without one is never a duplicate.  With --quant\n"
+          "the duplicate names are not counted: quant.tsv holds molecules.  The main output, --coverage (unit, nh) and --unprojected\n"
+          "still see every record.  Not with --quant-bam or --coverage-weight em.  --dedup-stats FILE: size<TAB>molecules, a line per\n"
+          "molecule size that occurs.  --dedup-bam FILE: the projected records under the header the output has without --sort, without\n"
+          "the duplicate names' (--dedup-bam-mode remove, the default) or all of them, the duplicates' with flag 0x400 (mark).  One more\n"
+          "line in front of the final report: [bramble] dedup: M molecules of N read names (D duplicates, U without UMI; G position groups; method unique|directional; add X.XXs, finish Y.YYs)\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -134,7 +147,7 @@ int parse_args(int argc, char **argv, Options &o) {
   memset(&o.cfg, 0, sizeof(o.cfg));
   o.cfg.junc_miss_discount = 1.0;
   bool codec = false, host_codec = false;   // a BGZF codec option was given; one that asks for the host codec
-  bool coverage_weight_given = false, unprojected_scope_given = false, quant_bam_mode_given = false;
+  bool coverage_weight_given = false, unprojected_scope_given = false, quant_bam_mode_given = false, dedup_switch_given = false, dedup_bam_mode_given = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "%s: missing value\n", argv[i]); return nullptr; } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -233,6 +246,38 @@ int parse_args(int argc, char **argv, Options &o) {
       else { fprintf(stderr, "--quant-bam-mode: unknown mode %s (tag or sample)\n", v); return -1; }
       quant_bam_mode_given = true;
     }
+    else if (a == "--dedup") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "unique") o.dedup = 0; else if (w == "directional") o.dedup = 1;
+      else { fprintf(stderr, "--dedup: unknown method %s (unique or directional)\n", v); return -1; }
+    }
+    else if (a == "--dedup-umi") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "name") o.dedup_umi = 0; else if (w == "tag") o.dedup_umi = 1;
+      else { fprintf(stderr, "--dedup-umi: unknown source %s (name or tag)\n", v); return -1; }
+      dedup_switch_given = true;
+    }
+    else if (a == "--dedup-umi-sep") {
+      const char *v = value(); if (!v) return -1;
+      if (strlen(v) != 1) { fprintf(stderr, "--dedup-umi-sep: %s is not one character\n", v); return -1; }
+      o.dedup_umi_sep = (unsigned char)v[0]; dedup_switch_given = true;
+    }
+    else if (a == "--dedup-umi-tag") {
+      const char *v = value(); if (!v) return -1;
+      if (strlen(v) != 2) { fprintf(stderr, "--dedup-umi-tag: %s is not a two-character tag\n", v); return -1; }
+      o.dedup_umi_tag = (unsigned char)v[0] | (unsigned char)v[1] << 8; dedup_switch_given = true;
+    }
+    else if (a == "--dedup-stats") { const char *v = value(); if (!v) return -1; o.dedup_stats = v; dedup_switch_given = true; }
+    else if (a == "--dedup-bam") { const char *v = value(); if (!v) return -1; o.dedup_bam = v; dedup_switch_given = true; }
+    else if (a == "--dedup-bam-mode") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "remove") o.dedup_bam_mode = 0; else if (w == "mark") o.dedup_bam_mode = 1;
+      else { fprintf(stderr, "--dedup-bam-mode: unknown mode %s (remove or mark)\n", v); return -1; }
+      dedup_switch_given = dedup_bam_mode_given = true;
+    }
     else if (a == "--device") { const char *v = value(); if (!v) return -1; o.devices.assign(1, atoi(v)); }
     else if (a == "--devices") {
       const char *v = value(); if (!v) return -1;
@@ -275,6 +320,12 @@ int parse_args(int argc, char **argv, Options &o) {
   if (unprojected_scope_given && o.unprojected.empty()) { fprintf(stderr, "--unprojected-scope needs --unprojected\n"); return -1; }
   if (o.unprojected == "-") { fprintf(stderr, "--unprojected needs a file, not standard output: that is the main output's\n"); return -1; }
   if (!o.unprojected.empty() && o.devices.size() > 1) { fprintf(stderr, "--unprojected works on one device: give --device N, not a --devices list\n"); return -1; }
+  if (dedup_switch_given && o.dedup < 0) { fprintf(stderr, "--dedup-umi, --dedup-umi-sep, --dedup-umi-tag, --dedup-stats, --dedup-bam and --dedup-bam-mode need --dedup\n"); return -1; }
+  if (dedup_bam_mode_given && o.dedup_bam.empty()) { fprintf(stderr, "--dedup-bam-mode needs --dedup-bam\n"); return -1; }
+  if (o.dedup_bam == "-") { fprintf(stderr, "--dedup-bam needs a file, not standard output: that is the main output's\n"); return -1; }
+  if (o.dedup >= 0 && o.devices.size() > 1) { fprintf(stderr, "--dedup works on one device: give --device N, not a --devices list\n"); return -1; }
+  if (o.dedup >= 0 && !o.quant_bam.empty()) { fprintf(stderr, "--dedup not with --quant-bam: the posterior BAM needs a class for every read name with records, and the duplicate names have none\n"); return -1; }
+  if (o.dedup >= 0 && o.coverage_weight == 2) { fprintf(stderr, "--dedup not with --coverage-weight em: the weighted coverage needs a class for every read name with records, and the duplicate names have none\n"); return -1; }
   if (o.write_index && !o.sort) { fprintf(stderr, "--write-index needs --sort: a BAI index describes a coordinate-sorted file\n"); return -1; }
   if (o.write_index && o.sam_out) { fprintf(stderr, "--write-index applies to BAM output, not to --output-fmt sam\n"); return -1; }
   if (o.write_index && o.out_bam == "-") { fprintf(stderr, "--write-index needs an output file, not standard output\n"); return -1; }
@@ -746,7 +797,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
     const int urc = br_ctx_set_param(workers[0]->ctx, "keep_unprojected", o.unprojected_scope);
     if (urc) { fprintf(stderr, "error: unprojected records on device %d: %s\n", workers[0]->device, br_strerror(urc)); return give_up(); }
   }
-  if (!o.quant_bam.empty()) env.out_header = make_bam_header(make_header_text(hdr.text, ix0, cl, o.gff, false), ix0);
+  if (!o.quant_bam.empty() || !o.dedup_bam.empty()) env.out_header = make_bam_header(make_header_text(hdr.text, ix0, cl, o.gff, false), ix0);
   if (!open_consumers(env, consumers, err)) { fprintf(stderr, "error: %s\n", err.c_str()); return give_up(); }
   OutFile file(o.out_bam);
   if (!file.wr.open(file.tmp.c_str(), o.threads, o.level, !o.sam_out)) { fprintf(stderr, "error: %s\n", file.wr.error().c_str()); return give_up(); }

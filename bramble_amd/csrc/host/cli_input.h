@@ -57,6 +57,13 @@ struct Options {
   int unprojected_scope = 1;     // --unprojected-scope record|name: the context's "keep_unprojected" (1, 2)
   std::string quant_bam;         // --quant-bam FILE: the projected records with the EM's posterior (ZW:f), as a BAM under the unsorted output's header
   int quant_bam_mode = 0;        // --quant-bam-mode tag|sample: br_assign's "mode" (0, 1)
+  int dedup = -1;                // --dedup unique|directional: br_dedup's "method" (0, 1); -1: no duplicate removal
+  int dedup_umi = 0;             // --dedup-umi name|tag: "umi_source" (0, 1)
+  int dedup_umi_sep = '_';       // --dedup-umi-sep C: "umi_sep"
+  int dedup_umi_tag = 'R' | 'X' << 8;   // --dedup-umi-tag XY: "umi_tag"
+  std::string dedup_stats;       // --dedup-stats FILE: size<TAB>molecules, a line per non-empty bin of the histogram
+  std::string dedup_bam;         // --dedup-bam FILE: the projected records without the duplicate names' (or with 0x400 on them), under the unsorted output's header
+  int dedup_bam_mode = 0;        // --dedup-bam-mode remove|mark: br_dedup's "mark" (0, 1)
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };
 inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }

@@ -1,5 +1,5 @@
-// What consumes a run of the command line (cli.cpp) beside the main output: --sort (cli_output_sort.cpp), --quant
-// (cli_output_quant.cpp), --coverage (cli_output_coverage.cpp), --unprojected (cli_output_unprojected.cpp), --quant-bam (cli_output_assign.cpp), behind one interface.  A consumer takes something from every
+// What consumes a run of the command line (cli.cpp) beside the main output: --sort (cli_output_sort.cpp), --dedup
+// (cli_output_dedup.cpp), --quant (cli_output_quant.cpp), --coverage (cli_output_coverage.cpp), --unprojected (cli_output_unprojected.cpp), --quant-bam (cli_output_assign.cpp), behind one interface.  A consumer takes something from every
 // projected bundle on device o.devices[0], does its device work once the input is through, writes its files (cli_output_files.h)
 // and prints one report line; the runners, the writer and br_cli_main loop over the consumers and never learn which kind one is.
 #pragma once
@@ -10,7 +10,8 @@ namespace brcli {
 
 // what every consumer is made from, built once: tid = the index's transcript, its line in a file = the @SQ list's; hdr: the
 // input's header (--unprojected writes its file under it)
-// out_header: the main output's BAM header as it is without --sort (--quant-bam writes its file under it; empty unless asked for)
+// out_header: the main output's BAM header as it is without --sort (--quant-bam and --dedup-bam write their files under it; empty
+// unless asked for)
 struct RunEnv { const Options &o; int device; TxTable tx; const BamHeader &hdr; std::vector<uint8_t> out_header; };
 
 class Consumer {
@@ -33,6 +34,9 @@ class Consumer {
   virtual int next_piece(uint64_t, br_device_bam *piece) { memset(piece, 0, sizeof(*piece)); return BR_OK; }
   // --quant only: its quantifier, for a consumer that reads it after the quantifier's finish() (the EM has run by then)
   virtual br_quant *quantifier() { return nullptr; }
+  // --dedup only: one byte per read name of the run in HBM, non-zero for a duplicate (br_dedup_flags: BR_ERR_INVALID_ARG before its
+  // finish()); the --quant consumer drops those names in front of its own finish().  Every other consumer: BR_ERR_UNSUPPORTED
+  virtual int duplicate_flags(const uint8_t **, int64_t *) { return BR_ERR_UNSUPPORTED; }
   // once every consumer is open: one that needs another finds it among them; false: it is not there
   virtual bool meet(const std::vector<std::unique_ptr<Consumer>> &) { return true; }
   const char *const name, *const failure;
@@ -46,6 +50,7 @@ std::unique_ptr<Consumer> open_quant(const RunEnv &env, std::string &err);
 std::unique_ptr<Consumer> open_coverage(const RunEnv &env, std::string &err);
 std::unique_ptr<Consumer> open_unprojected(const RunEnv &env, std::string &err);   // (begins its file: err is the writer's)
 std::unique_ptr<Consumer> open_assign(const RunEnv &env, std::string &err);        // (likewise)
+std::unique_ptr<Consumer> open_dedup(const RunEnv &env, std::string &err);         // (likewise, with --dedup-bam)
 // (for the three above) T::open() makes the library's object and sets its parameters
 template <typename T>
 std::unique_ptr<Consumer> open_as(const RunEnv &env, std::string &err) {
@@ -54,12 +59,12 @@ std::unique_ptr<Consumer> open_as(const RunEnv &env, std::string &err) {
   return c;
 }
 
-// the consumers the options ask for, in the order sort, quant, coverage, unprojected, quant-bam -- the order of their finish() as well: coverage under
-// --coverage-weight em and --quant-bam read the quantifier (Consumer::quantifier) whose EM quant's finish() has run; false: `err` says which
-// could not be made
+// the consumers the options ask for, in the order sort, dedup, quant, coverage, unprojected, quant-bam -- the order of their finish() as well: quant
+// drops the names dedup's finish() has found to be duplicates (Consumer::duplicate_flags), coverage under --coverage-weight em and
+// --quant-bam read the quantifier (Consumer::quantifier) whose EM quant's finish() has run; false: `err` says which could not be made
 inline bool open_consumers(const RunEnv &env, std::vector<std::unique_ptr<Consumer>> &out, std::string &err) {
   const Options &o = env.o;
-  const std::pair<bool, decltype(&open_sort)> wanted[] = {{o.sort, open_sort}, {!o.quant.empty(), open_quant}, {!o.coverage.empty() || !o.coverage_summary.empty(), open_coverage}, {!o.unprojected.empty(), open_unprojected}, {!o.quant_bam.empty(), open_assign}};
+  const std::pair<bool, decltype(&open_sort)> wanted[] = {{o.sort, open_sort}, {o.dedup >= 0, open_dedup}, {!o.quant.empty(), open_quant}, {!o.coverage.empty() || !o.coverage_summary.empty(), open_coverage}, {!o.unprojected.empty(), open_unprojected}, {!o.quant_bam.empty(), open_assign}};
   for (auto &[want, open] : wanted) {
     if (!want) continue;
     out.push_back(open(env, err));

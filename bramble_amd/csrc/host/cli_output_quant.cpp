@@ -3,7 +3,8 @@
 // download each -- the table, --quant-classes, --quant-fld; with --quant-bootstraps the replicates run behind the EM
 // (br_quant_bootstrap) and their summary joins the table, their values --quant-boot-out; with --quant-genes the gene tables are
 // made last (br_quant_genes on the numbers env.tx gives the genes) and go to --quant-genes and --quant-gene-classes; --quant-vb
-// turns the variational Bayes EM on ("vb") for all of them.
+// turns the variational Bayes EM on ("vb") for all of them.  Beside --dedup the names that consumer has found to be duplicates are
+// dropped in front of the classes (br_quant_drop_names with its flags, from where they lie in HBM): the file's numbers are molecules.
 #include "cli_output.h"
 
 namespace brcli {
@@ -29,9 +30,19 @@ class QuantOut : public Consumer {
   }
   int add(br_ctx *ctx) override { return br_quant_add_last(q, ctx); }
   br_quant *quantifier() override { return q; }
+  bool meet(const std::vector<std::unique_ptr<Consumer>> &all) override {
+    for (auto &other : all) if (other->duplicate_flags(nullptr, nullptr) != BR_ERR_UNSUPPORTED) dedup = other.get();
+    return dedup != nullptr || env.o.dedup < 0;
+  }
   int finish() override {
     const size_t nt = env.tx.len.size();
-    int rc = br_quant_finish(q, &n_names, &n_classes);
+    int rc = BR_OK;
+    if (dedup) {   // (its finish() has run)
+      const uint8_t *flags = nullptr; int64_t n = 0;
+      rc = dedup->duplicate_flags(&flags, &n);
+      if (!rc) rc = br_quant_drop_names(q, flags, n, 1, nullptr);
+    }
+    if (!rc) rc = br_quant_finish(q, &n_names, &n_classes);
     if (!rc) rc = br_quant_em(q, &n_iters, nullptr);
     if (!rc) {
       theta.resize(nt + 1); tpm.resize(nt + 1); unique.resize(nt + 1); ambig.resize(nt + 1);
@@ -119,6 +130,7 @@ class QuantOut : public Consumer {
  private:
   static constexpr size_t FLD_MAX = 1000;   // br_quant's default "fld_max"
   br_quant *q = nullptr;
+  Consumer *dedup = nullptr;   // the --dedup consumer, which outlives neither of the two
   SideFile table, classes, fld, boot, genes, gene_classes;
   int64_t n_names = 0, n_classes = 0; int32_t n_iters = 0;
   double t_add = 0, t_finish = 0, t_em = 0;

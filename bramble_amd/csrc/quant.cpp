@@ -329,6 +329,30 @@ extern "C" int br_quant_add_last(br_quant *c, br_ctx *ctx) {
   return br_quant_add_rows(c, &ctx->last_rows, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
 }
 
+// the names with a non-zero flag lose their labels before finish looks at them: to everything finish makes they are names without rows
+extern "C" int br_quant_drop_names(br_quant *c, const uint8_t *flags, int64_t n, int on_device, int64_t *n_dropped) {
+  if (!c || c->finished || n != c->n || (n && !flags)) return BR_ERR_INVALID_ARG;
+  if (n_dropped) *n_dropped = 0;
+  if (n == 0) return BR_OK;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  uint64_t *small = c->small.as<uint64_t>();
+  ColBuf d_flags;
+  DropGuard dropper{c, {&d_flags}};
+  if (!on_device) {
+    RC(c->alloc(d_flags, (size_t)n));
+    HIPCHK(hipMemcpyAsync(d_flags.p, flags, (size_t)n, hipMemcpyHostToDevice, st));
+    flags = d_flags.as<uint8_t>();
+  } else RC(c->after(nullptr));   // after whatever made the flags
+  HIPCHK(hipMemsetAsync(small + QS_BAD, 0, 8, st));
+  launch_q_drop(st, flags, n, c->nk.as<uint32_t>(), (unsigned long long *)(small + QS_BAD));
+  uint64_t dropped = 0;
+  HIPCHK(hipMemcpyAsync(&dropped, small + QS_BAD, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (n_dropped) *n_dropped = (int64_t)dropped;
+  return BR_OK;
+}
+
 static int quant_tmp(br_quant *c, int64_t n) { return c->alloc(c->tmp, scan_tmp_bytes(n)); }
 // the radix sort of (key, idx) over the digits in which the keys differ (launch_q_bits finds them); *cur = the buffer that holds the result
 static int quant_sort(br_quant *c, ColBuf key[2], ColBuf idx[2], int64_t n, int *cur) {

@@ -45,6 +45,9 @@ void launch_q_fld_prefix(hipStream_t st, const unsigned long long *hist, uint32_
 // eff[t] and w[t] = 1 / eff[t] (0 where eff is 0) from the lengths and the prefix sums
 void launch_q_efflen(hipStream_t st, const int64_t *lens, int64_t n_tx, const uint64_t *cs, uint32_t n_bins, double *eff, double *w);
 
+// br_quant_drop_names: nk[i] = 0 where flags[i] != 0 (k_q_flag then sees a name without labels); *n_dropped += those names
+void launch_q_drop(hipStream_t st, const uint8_t *flags, int64_t n, uint32_t *nk, unsigned long long *n_dropped);
+
 // finish: the assigned names (k > 0) in add order -> (hash & mask, name index)
 void launch_q_flag(hipStream_t st, const uint32_t *nk, int64_t n, uint64_t *flag);
 void launch_q_compact(hipStream_t st, const uint32_t *nk, const uint64_t *hash, const uint64_t *pos, int64_t n, uint64_t mask,

@@ -349,6 +349,13 @@ __global__ void __launch_bounds__(256) k_q_efflen(const int64_t *lens, int64_t n
   eff[t] = e; w[t] = e > 0.0 ? 1.0 / e : 0.0;
 }
 
+__global__ void __launch_bounds__(256) k_q_drop(const uint8_t *flags, int64_t n, uint32_t *nk, unsigned long long *n_dropped) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool drop = i < n && flags[i] != 0;
+  if (drop) nk[i] = 0;
+  const uint64_t bal = __ballot(drop);
+  if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_dropped, (unsigned long long)__popcll((unsigned long long)bal));
+}
 __global__ void __launch_bounds__(256) k_q_flag(const uint32_t *nk, int64_t n, uint64_t *flag) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) flag[i] = nk[i] ? 1 : 0;
@@ -962,6 +969,9 @@ void launch_q_efflen(hipStream_t st, const int64_t *lens, int64_t n_tx, const ui
   if (n_tx <= 0) return;
   if (n_bins <= Q_EFF_LDS_BINS) hipLaunchKernelGGL(k_q_efflen<true>, dim3(blocks256(n_tx)), dim3(256), (size_t)n_bins * 16, st, lens, n_tx, cs, n_bins, eff, w);
   else hipLaunchKernelGGL(k_q_efflen<false>, dim3(blocks256(n_tx)), dim3(256), 0, st, lens, n_tx, cs, n_bins, eff, w);
+}
+void launch_q_drop(hipStream_t st, const uint8_t *flags, int64_t n, uint32_t *nk, unsigned long long *n_dropped) {
+  if (n > 0) hipLaunchKernelGGL(k_q_drop, dim3(blocks256(n)), dim3(256), 0, st, flags, n, nk, n_dropped);
 }
 void launch_q_flag(hipStream_t st, const uint32_t *nk, int64_t n, uint64_t *flag) {
   if (n > 0) hipLaunchKernelGGL(k_q_flag, dim3(blocks256(n)), dim3(256), 0, st, nk, n, flag);

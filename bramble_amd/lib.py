@@ -188,6 +188,8 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_coverage_add_names", "br_coverage_finish_em", "br_coverage_runs64", "br_coverage_depth64", "br_coverage_summary64",
            "br_assign_new", "br_assign_set_param", "br_assign_add", "br_assign_add_last", "br_assign_finish", "br_assign_values", "br_assign_next",
            "br_assign_stats", "br_assign_free",
+           "br_dedup_new", "br_dedup_set_param", "br_dedup_add", "br_dedup_add_last", "br_dedup_finish", "br_dedup_umis", "br_dedup_result",
+           "br_dedup_hist", "br_dedup_flags", "br_dedup_next", "br_dedup_stats", "br_dedup_free", "br_quant_drop_names",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_direct_tidwords", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -1270,7 +1272,8 @@ class Quant(_Accumulator):
                 "gene_result": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                 "gene_boot": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p], "gene_boot_summary": [C.c_void_p, C.c_void_p, C.c_void_p],
                 "gene_stats": [C.c_void_p, _P(C.c_double), _P(C.c_int64), _P(C.c_uint64)],
-                "name_classes": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p], "posteriors": [C.c_void_p, C.c_void_p]}
+                "name_classes": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p], "posteriors": [C.c_void_p, C.c_void_p],
+                "drop_names": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _P(C.c_int64)]}
 
     def __init__(self, n_transcripts, lengths=None, device=0, vb=None, vb_prior=None, vb_per_nucleotide=None):
         self.n_transcripts = int(n_transcripts)
@@ -1357,6 +1360,20 @@ class Quant(_Accumulator):
     def add_last(self, ctx):
         """The read names of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
         self._call("add_last", ctx.h)
+
+    def drop_names(self, flags):
+        """Before finish: the names with a non-zero flag count as names without rows.  flags: a finished Dedup (its duplicates, from
+        where they lie in HBM), a torch CUDA uint8 tensor or a host array, one byte per name added -> the names dropped."""
+        k = C.c_int64()
+        if isinstance(flags, Dedup):
+            ptr, n = flags.flags()
+            self._call("drop_names", C.c_void_p(ptr), n, 1, C.byref(k))
+        elif hasattr(flags, "data_ptr"):
+            self._call("drop_names", C.c_void_p(flags.data_ptr() if flags.numel() else None), flags.numel(), 1, C.byref(k))
+        else:
+            f = np.ascontiguousarray(flags, dtype=np.uint8)
+            self._call("drop_names", C.c_void_p(f.ctypes.data if f.size else None), f.size, 0, C.byref(k))
+        return int(k.value)
 
     def finish(self):
         n, c = C.c_int64(), C.c_int64()
@@ -1765,3 +1782,124 @@ class Assign(_Accumulator):
         out = {"held_bytes": int(h.value), "peak_bytes": int(p.value), "add_s": ad.value, "finish_s": fi.value, "next_s": nx.value}
         out.update({"bad_" + k: int(v) for k, v in zip(self.BAD, bad)})
         return out
+
+
+class Dedup(_Accumulator):
+    """br_dedup on `device`: the rows of projected batches by read name and the records they were encoded to, in; after finish() per
+    read name whether it is a PCR copy (result: rep, group_first, dup), the molecules' size histogram (hist) and, with
+    "keep_records", the records again without the duplicates' ("mark" 0) or with 0x400 set on them ("mark" 1).  set_param: "method"
+    (METHODS), "umi_source" (SOURCES), "umi_sep", "umi_tag", "keep_records", "mark", "max_bytes", "hist_max" before the first add,
+    "hash_bits" before finish."""
+
+    METHODS = {"unique": 0, "directional": 1}
+    SOURCES = {"name": 0, "tag": 1}
+    STATS = ("names", "names_with_rows", "no_umi", "umi_too_long", "bad_aux", "groups", "nodes", "edges", "sweeps", "max_group_nodes",
+             "collisions", "held_bytes", "peak_bytes", "add_us", "finish_us", "records_out")
+
+    NAME = "dedup"
+    ARGTYPES = {"new": [C.c_int, _P(C.c_void_p)], "set_param": [C.c_void_p, C.c_char_p, C.c_int64],
+                "add": [C.c_void_p, C.c_void_p, _P(BrDeviceRows), C.c_void_p, C.c_int64, C.c_int, C.c_void_p],
+                "add_last": [C.c_void_p, C.c_void_p], "finish": [C.c_void_p, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)],
+                "umis": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
+                "result": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p], "hist": [C.c_void_p, C.c_void_p],
+                "flags": [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)], "next": [C.c_void_p, C.c_uint64, _P(BrDeviceBam)],
+                "stats": [C.c_void_p, C.c_void_p], "free": [C.c_void_p]}
+
+    def __init__(self, device=0, **params):
+        self.n_names = self.n_molecules = self.n_duplicates = 0
+        self.hist_max = 1000
+        self._open(device)
+        for k, v in params.items():
+            self.set_param(k, v)
+
+    def set_param(self, name, value):
+        if name == "umi_tag" and not isinstance(value, int):
+            b = value.encode() if isinstance(value, str) else bytes(value)
+            value = b[0] | b[1] << 8
+        if name == "umi_sep" and not isinstance(value, int):
+            value = (value.encode() if isinstance(value, str) else bytes(value))[0]
+        super().set_param(name, value)
+        if name == "hist_max":
+            self.hist_max = int(value)
+
+    def add_raw(self, recs, a, cigar, pool, row_off, n_rows, n_pool_words, group_off, n_groups, on_device, stream=None):
+        """br_dedup_add as it is (recs: a BrDeviceBam or None; the tables as addresses): the return code (0, or a BR_ERR_* value)."""
+        rows = BrDeviceRows()
+        rows.n_rows, rows.n_pool_words = int(n_rows), int(n_pool_words)
+        rows.a, rows.cigar, rows.pool, rows.row_off = a, cigar, pool, row_off
+        return self._raw("add", C.cast(C.byref(recs), C.c_void_p) if recs is not None else None, C.byref(rows), C.c_void_p(group_off), int(n_groups),
+                         1 if on_device else 0, C.c_void_p(stream or 0))
+
+    def add_host(self, rows_a, cigar, pool, row_off, group_off, stream_np, rec_off=None):
+        """The rows of the read names group_off[0 .. n] (rows_a uint32 [n_rows, 4], cigar uint64 [n_rows], pool uint32, row_off uint64
+        per alignment) and their records as an uncompressed record stream (row i = record i), all in host memory."""
+        a = np.ascontiguousarray(rows_a, dtype=np.uint32).reshape(-1, 4)
+        cg = np.ascontiguousarray(cigar, dtype=np.uint64)
+        pl = np.ascontiguousarray(pool, dtype=np.uint32)
+        ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+        go = np.ascontiguousarray(group_off, dtype=np.uint32)
+        data = np.ascontiguousarray(stream_np, dtype=np.uint8)
+        off = Sorter.row_offsets(data) if rec_off is None else np.ascontiguousarray(rec_off, dtype=np.uint64)
+        recs = BrDeviceBam(data.ctypes.data if data.size else None, data.size, off.ctypes.data, len(off) - 1)
+        check(self.add_raw(recs, a.ctypes.data if a.size else None, cg.ctypes.data if cg.size else None, pl.ctypes.data if pl.size else None,
+                           ro.ctypes.data, len(a), len(pl), go.ctypes.data, len(go) - 1, False), "br_dedup_add")
+
+    def add_device(self, rows_a, cigar, pool, row_off, group_off, recs, g0=0, g1=None):
+        """The same tables as torch CUDA tensors; the read names [g0, g1) of them are added.  recs: a BrDeviceBam of the rows' records
+        in HBM."""
+        import torch
+        g1 = group_off.numel() - 1 if g1 is None else g1
+        n_rows = cigar.numel()
+        check(self.add_raw(recs, rows_a.data_ptr() if n_rows else None, cigar.data_ptr() if n_rows else None, pool.data_ptr() if pool.numel() else None,
+                           row_off.data_ptr(), n_rows, pool.numel(), group_off.data_ptr() + 4 * g0, g1 - g0, True,
+                           torch.cuda.current_stream(row_off.device).cuda_stream), "br_dedup_add")
+
+    def add_last(self, ctx):
+        """The rows, names and records of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
+        self._call("add_last", ctx.h)
+
+    def finish(self):
+        """-> (names added, molecules, duplicates)"""
+        n, m, d = C.c_int64(), C.c_int64(), C.c_int64()
+        self._call("finish", C.byref(n), C.byref(m), C.byref(d))
+        self.n_names, self.n_molecules, self.n_duplicates = int(n.value), int(m.value), int(d.value)
+        return self.n_names, self.n_molecules, self.n_duplicates
+
+    def umis(self, first, n):
+        """-> (umi uint8 [n, 32] zero padded, len uint8 [n]) of the add-order names [first, first + n)"""
+        k = max(int(n), 1)
+        umi, ln = np.zeros((k, 32), np.uint8), np.zeros(k, np.uint8)
+        self._call("umis", int(first), int(n), umi.ctypes.data, ln.ctypes.data)
+        return umi[:n], ln[:n]
+
+    def result(self, first=0, n=None):
+        """-> rep (uint32), group_first (uint32), dup (uint8) of the add-order names [first, first + n)"""
+        n = self.n_names - first if n is None else n
+        k = max(int(n), 1)
+        rep, gf, dup = np.zeros(k, np.uint32), np.zeros(k, np.uint32), np.zeros(k, np.uint8)
+        self._call("result", int(first), int(n), rep.ctypes.data, gf.ctypes.data, dup.ctypes.data)
+        return rep[:n], gf[:n], dup[:n]
+
+    def hist(self):
+        h = np.zeros(self.hist_max + 1, np.uint64)
+        self._call("hist", h.ctypes.data)
+        return h
+
+    def flags(self):
+        """-> (the address of dup in HBM, the names)"""
+        p, n = C.c_void_p(), C.c_int64()
+        self._call("flags", C.byref(p), C.byref(n))
+        return p.value, int(n.value)
+
+    def next_records(self, max_bytes):
+        """The next piece as a BrDeviceBam in HBM (n_rows = 0 at the end; valid until the second next call)."""
+        piece = BrDeviceBam()
+        self._call("next", int(max_bytes), C.byref(piece))
+        return piece
+
+    pieces = Sorter.pieces
+
+    def stats(self):
+        out = np.zeros(16, np.uint64)
+        self._call("stats", out.ctypes.data)
+        return {k: int(v) for k, v in zip(self.STATS, out)}

@@ -1077,6 +1077,103 @@ int br_assign_next(br_assign *, uint64_t max_bytes, br_device_bam *piece);
 int br_assign_stats(const br_assign *, uint64_t *held, uint64_t *peak, double *add_s, double *finish_s, double *next_s, uint64_t *bad);
 void br_assign_free(br_assign *);
 
+/* ---- UMI-aware duplicate removal ------------------------------------------------------------ */
+
+/* br_dedup: a run accumulator like br_quant, br_coverage and br_assign.  It is fed the rows of every projection call by read name and
+ * the records the call encoded, and decides per READ NAME whether it is a PCR copy of another: two names are copies of one molecule
+ * when they carry the same UMI (method directional: UMIs one mismatch apart, the rarer joining the more abundant) and project to
+ * the same set of placements.  Whole names are kept or dropped, so a multi-mapper's records stay together.  All of it is integer and
+ * byte arithmetic: a restatement gives the same bits.
+ *   name i         the add-order index of a read name, from row_off / group_off exactly as br_coverage_add_names / br_assign_add take
+ *                  it.  Records and rows correspond one to one (br_device_bam row r is br_device_rows row r)
+ *   UMI(i)         from the name's first record, at add time; at most 32 bytes, compared as bytes: length first, then content, case-
+ *                  sensitive.  A record lies in the stream as [block_size][record]; from the block's start l_read_name is at byte 12,
+ *                  n_cigar_op at 16, flag at 18, l_seq at 20, read_name at 36, aux at 36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2
+ *                  + l_seq.  "umi_source" 0 (name, umi_tools extract's convention): the bytes of read_name (without its NUL) behind
+ *                  the last byte equal to "umi_sep" (default '_').  "umi_source" 1 (tag): the value, without its NUL, of the first aux
+ *                  field whose two tag bytes equal "umi_tag" (b0 | b1 << 8, default RX) and whose type is Z; a field type outside
+ *                  AcCsSiIfZHB or a field that runs past the record's end ends the walk: the name has no UMI and counts in n_bad_aux
+ *                  (nothing past the record is read; no error).  No separator, no such tag, a length of 0 or above 32: NO UMI; the
+ *                  name counts in n_no_umi (as the n_bad_aux ones do), a length above 32 in n_umi_too_long as well.  A name without a
+ *                  UMI is its own molecule and never a duplicate.  A name without rows has no record: its UMI reads as length 0 and it
+ *                  is counted nowhere
+ *   entry(r)       (t, five, f) of a row r: t = a[r].transcript_id; f = the record's own flag word & 0xD1 (paired, reverse, read1,
+ *                  read2); five = the unclipped 5' coordinate, int64: the row's rewritten CIGAR is read as br_quant's fragments read
+ *                  it (cigar[r] itself when BR_ROW_NCIGAR(meta) <= 2, else pool[cigar[r] ...]), reflen = the sum over the ops M D N =
+ *                  X, lead = the length of an S op that is the first op or follows only H ops, else 0, trail the same from the end -- of
+ *                  the ops in the RECORD's order: a row with BR_ROW_MINUS holds them reversed, as the encoder writes them out;
+ *                  five = pos - lead when !(f & 0x10), else pos + reflen + trail.  A pooled CIGAR reference that leaves n_pool_words:
+ *                  BR_ERR_INVALID_ARG and nothing added
+ *   signature(i)   the name's entries in ascending order of (t unsigned, five signed, f), equal ones repeated: a sorted multiset, so
+ *                  the order in which an aligner listed a multi-mapper's alignments does not matter
+ *   position group the names with at least one row that have equal signatures.  A name without rows is in no group: rep and
+ *                  group_first 0xffffffff, dup 0, counted among neither molecules nor duplicates
+ *   unique         ("method" 0) a molecule is the names of one position group with equal UMI
+ *   directional    ("method" 1, the default; umi_tools' default) per position group the nodes are its distinct UMIs, c_u the number
+ *                  of names carrying u; the nodes are ordered by (c descending, length ascending, bytes ascending); an edge u -> v
+ *                  when both have the same length, their Hamming distance over bytes is exactly 1 and c_u >= 2 c_v - 1; root(v) is the
+ *                  node of lowest order index among v and every node from which v can be reached along edges (umi_tools' breadth-
+ *                  first assignment from the highest counts down: the earliest node that reaches v is reachable from no earlier one);
+ *                  it is the fixed point of label[v] = min(label[v], label[u] for u -> v), whatever the schedule.  A molecule is the
+ *                  names whose UMI has the same root
+ *   rep, dup       unique: the molecule's name of lowest index; directional: the lowest-index name among those carrying the root's
+ *                  UMI (umi_tools' choice: a read of the most abundant UMI).  rep[i] is that index, dup[i] = 1 when the name has rows
+ *                  and rep[i] != i, else 0.  group_first[i]: the lowest name index of i's position group
+ *   histogram      hist[s], s = 1 .. "hist_max" (default 1000): the molecules of s names, larger ones in the last bin; hist[0] = 0
+ *   invariance     neither how the names were cut into adds, nor whether the tables lay in host or device memory, nor "hash_bits"
+ *                  (the quantifier's test hook: fewer bits make unlike signatures collide; equality is always decided on the
+ *                  contents) changes any result, and two runs give the same bits
+ *
+ *   br_dedup_set_param  before the first add: "method", "umi_source", "umi_sep", "umi_tag", "keep_records" 0 / 1 (default 0), "mark"
+ *                       0 / 1 (default 0), "max_bytes" (a cap on the arena's bytes, 0: none), "hist_max" 1 .. 65535; before finish:
+ *                       "hash_bits" 1 .. 64
+ *   br_dedup_add        shapes and rules of br_assign_add, with the rows' cigar and pool: offsets that descend, recs->n_rows !=
+ *                       rows->n_rows, a record of less than 36 bytes, a name of 2^30 rows or more: BR_ERR_INVALID_ARG and nothing
+ *                       added.  recs is required.  BR_ERR_CAPACITY for memory that is not there, the cap, 2^32 names or rows.  With
+ *                       "keep_records" the records are copied into an arena in HBM, growing by half; without, nothing of a record is
+ *                       kept beyond the 33 UMI bytes a name and the flag bits in the entries
+ *   br_dedup_add_last   the context's last call: its rows, names and records (br_ctx_last_device_bam); a flat batch call has no
+ *                       records: BR_ERR_INVALID_ARG
+ *   br_dedup_finish     the verdicts; names added, molecules, duplicates (names with rows - molecules).  A failure leaves the object
+ *                       answering BR_ERR_INVALID_ARG to everything but br_dedup_stats and br_dedup_free.  The label propagation is
+ *                       the only iterative part: it stops when a sweep changes nothing and is bounded by (largest group's node count)
+ *                       sweeps, beyond which the call returns BR_ERR_HIP
+ *   br_dedup_umis       after any add, for the names added so far: n x 32 bytes zero padded, and the lengths; either may be NULL
+ *   br_dedup_result / br_dedup_hist   after finish; any pointer may be NULL; a range outside [0, n_names]: BR_ERR_INVALID_ARG
+ *   br_dedup_flags      after finish: dup as a device array of n_names bytes owned by the object (br_quant_drop_names takes it)
+ *   br_dedup_next       after finish, with "keep_records" (else BR_ERR_INVALID_ARG), as br_sorter_next / br_assign_next: whole records
+ *                       in add order, up to max_bytes and at least one, with row_off rebased; valid until the second next; n_rows = 0:
+ *                       that was all.  "mark" 0: the records of the names with dup == 0, every byte the input's; "mark" 1: every
+ *                       record, those of duplicate names with 0x400 OR-ed into the flag word at byte 18, every other byte the input's
+ *   br_dedup_stats      names, names with rows, n_no_umi, n_umi_too_long, n_bad_aux, position groups, nodes, edges, propagation
+ *                       sweeps run (the last, which changed nothing, included), the largest group's node count, collisions met, device
+ *                       bytes now and at most, microseconds in add and in finish, records br_dedup_next hands out
+ * Device memory: 53 bytes a name (UMI 32, length 1, signature offset 8, length 4, hash 8) and 16 a row (the entry) until finish, with
+ * "keep_records" the records' bytes (+ 64; the arena grows by half, the old one beside the new while copying) and 8 a row; an add
+ * holds 16 bytes a row and 4 a name of its own while it runs.  From finish on 9 a name (rep, group_first, dup), 8 (hist_max + 1) and,
+ * with records, 1 a row and 12 a record handed out; while it runs 4 a name, 32 a name with rows, 105 a node (its UMI 32, length 1, count,
+ * first name, group and place 4 each, two labels 8, edge offset 8, cursor 4, molecule size 4, begin 8, two sort pairs 24), 24 a group
+ * and 4 an edge (dedup.cpp). */
+typedef struct br_dedup br_dedup;
+int br_dedup_new(int device, br_dedup **out);
+int br_dedup_set_param(br_dedup *, const char *name, int64_t value);
+int br_dedup_add(br_dedup *, const br_device_bam *recs, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups,
+                 int on_device, void *stream);
+int br_dedup_add_last(br_dedup *, br_ctx *);
+int br_dedup_finish(br_dedup *, int64_t *n_names, int64_t *n_molecules, int64_t *n_duplicates);
+int br_dedup_umis(br_dedup *, int64_t first, int64_t n, uint8_t *umi /* n x 32, zero padded */, uint8_t *len);
+int br_dedup_result(br_dedup *, int64_t first, int64_t n, uint32_t *rep, uint32_t *group_first, uint8_t *dup);
+int br_dedup_hist(br_dedup *, uint64_t *hist /* hist_max + 1 */);
+int br_dedup_flags(br_dedup *, const uint8_t **dup_device, int64_t *n);
+int br_dedup_next(br_dedup *, uint64_t max_bytes, br_device_bam *piece);
+int br_dedup_stats(const br_dedup *, uint64_t out[16]);
+void br_dedup_free(br_dedup *);
+/* Before br_quant_finish; n must equal the names added, else BR_ERR_INVALID_ARG and nothing changes.  Every name with a non-zero flag
+ * (host or device memory) becomes a name without rows for everything finish makes: classes, counts, unique / ambig, name_cls
+ * (0xffffffff), n_unassigned and the bootstrap's resampling pool.  The fragment-length histogram of "eff_len" was counted at the adds
+ * and stays as it is.  *n_dropped: the names with a non-zero flag. */
+int br_quant_drop_names(br_quant *, const uint8_t *flags, int64_t n, int on_device, int64_t *n_dropped);
+
 /* ---- SAM text out -------------------------------------------------------------------------- */
 
 /* The reference names RNAME and RNEXT print, in refID order (a refID < 0 or >= n prints '*'); uploaded to HBM once, kept by
