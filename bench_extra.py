@@ -37,6 +37,12 @@
                                          about 1 M records: one CLI bundle) against br_bgzf_deflate_device of the same stream in the
                                          same process (ms per bundle, text GB/s), then the command line file to file with -O sam
                                          against the default BAM, alternated (SAMOUT_CLI_RUNS pairs, default 3; 0 skips them)
+  python bench_extra.py cells [--reads K]  br_cells on seeded synthetic tables fed straight to br_quant + br_cells from HBM: K cells (default
+                                         10 000) of 300 read names over 200 of the cell's transcripts each (one to three a name, two
+                                         transcripts a gene), plus a tail of 5 K barcodes of one to five names; mode em at the default
+                                         tolerance.  add / finish seconds and the value kernel's seconds: all cells at the default
+                                         "lds_bytes" (one launch, wave and block routes), the same with "lds_bytes" 0 (the block cells on
+                                         scratch in HBM), the large cells alone (block route), the tail alone (wave route)
   python bench_extra.py small            small calls: us per device-resident step at 1 .. 52 000 pairs (without the per-kernel
                                          events bench.py keeps on), the path without host round trips against the ordinary one,
                                          and br_project_group / br_project_groups host to host from plain C (profiles/group_latency.c)
@@ -54,7 +60,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "quant_boot", "quant_genes", "coverage"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "quant_boot", "quant_genes", "coverage", "cells"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
@@ -65,6 +71,87 @@ def main():
     import torch
     from bramble_amd import device as brdev
     from bramble_amd import lib, synth
+    if args.config == "cells":
+        k_cells = args.reads or 10_000
+        n_tx, per_cell, own = 20_000, 300, 200
+        rng = np.random.default_rng(11)
+
+        def barcodes(n, width):
+            return rng.choice(np.frombuffer(b"ACGT", np.uint8), size=(n, width))
+        big_bc, tail_bc = barcodes(k_cells, 16), barcodes(5 * k_cells, 15)   # (another length: the tail's never equal a cell's)
+        # names: (barcode row, 1..3 transcripts out of the cell's own 200, skewed towards its first ones)
+        n_big = k_cells * per_cell
+        tail_sizes = rng.integers(1, 6, 5 * k_cells)
+        cell_of = np.concatenate([np.repeat(np.arange(k_cells), per_cell), k_cells + np.repeat(np.arange(5 * k_cells), tail_sizes)])
+        n_names = len(cell_of)
+        k_rows = rng.choice([1, 2, 3], size=n_names, p=[0.7, 0.2, 0.1])
+        cell_base = rng.integers(0, n_tx - own, 6 * k_cells)
+        row_name = np.repeat(np.arange(n_names), k_rows)
+        pick = np.minimum((rng.random(len(row_name)) ** 2 * own).astype(np.int64), own - 1)
+        tids = (cell_base[cell_of[row_name]] + pick).astype(np.uint32)
+        order = rng.permutation(n_names)   # the cells' names interleaved, as a run leaves them
+
+        def tables(keep):
+            """the names `keep` (in the shuffled order) as row tables and records: one alignment a name, record = fixed fields + name"""
+            sel = order[keep[order]]
+            starts = np.concatenate([[0], np.cumsum(k_rows)])
+            first = np.concatenate([[0], np.cumsum(k_rows[sel])[:-1]])   # the first row of every kept name among the kept rows
+            rows = np.repeat(starts[sel] - first, k_rows[sel]) + np.arange(int(k_rows[sel].sum()))
+            a = np.zeros((len(rows), 4), np.uint32)
+            a[:, 0] = tids[rows]
+            row_off = np.concatenate([[0], np.cumsum(k_rows[sel])]).astype(np.uint64)
+            group_off = np.arange(len(sel) + 1, dtype=np.uint32)
+            # [block_size][32 fixed bytes][name + NUL]; a cell's names are r_<16>_<UMI>, the tail's rx_<15>_<UMI>
+            l_name = 2 + 16 + 1 + 8 + 1
+            rec = np.zeros((len(rows), 36 + l_name), np.uint8)
+            rec[:, 0] = 32 + l_name
+            rec[:, 12] = l_name
+            name = rec[:, 36:]
+            cell = cell_of[np.repeat(sel, k_rows[sel])]
+            is_big = cell < k_cells
+            name[:, 0] = ord("r")
+            name[is_big, 1] = ord("_")
+            name[is_big, 2:18] = big_bc[cell[is_big]]
+            name[~is_big, 1] = ord("x")
+            name[~is_big, 2] = ord("_")
+            name[~is_big, 3:18] = tail_bc[cell[~is_big] - k_cells]
+            name[:, 18] = ord("_")
+            name[:, 19:27] = np.frombuffer(b"ACGTACGT", np.uint8)
+            rec_off = (np.arange(len(rows) + 1, dtype=np.uint64) * np.uint64(rec.shape[1]))
+            return a, row_off, group_off, rec.reshape(-1), rec_off
+        tx_feature = (np.arange(n_tx, dtype=np.uint32) // 2)
+        out = {"config": "cells", "workload": "%d cells of %d read names + %d barcodes of 1-5 names, %d transcripts, %d genes, mode em" % (k_cells, per_cell, 5 * k_cells, n_tx, n_tx // 2)}
+        keeps = {"all": np.ones(n_names, bool), "large": np.arange(n_names) < n_big, "tail": np.arange(n_names) >= n_big}
+        for label, which, lds in (("all_default_lds", "all", None), ("all_lds_0", "all", 0), ("large_only_block_route", "large", None), ("tail_only_wave_route", "tail", None)):
+            a, row_off, group_off, data, rec_off = tables(keeps[which])
+            t = [torch.from_numpy(x).cuda() for x in (a.view(np.int32), row_off.view(np.int64), group_off.view(np.int32), data, rec_off.view(np.int64))]
+            recs = lib.BrDeviceBam(t[3].data_ptr(), t[3].numel(), t[4].data_ptr(), t[4].numel() - 1)
+            torch.cuda.synchronize()
+            runs = []
+            for step in range(args.warmup + args.steps):
+                q = lib.Quant(n_tx)
+                q.set_param("keep_names", 1)
+                c = lib.Cells(mode=2, **({} if lds is None else {"lds_bytes": lds}))
+                n_g = len(group_off) - 1
+                for g0 in range(0, n_g, 1_000_000):
+                    g1 = min(n_g, g0 + 1_000_000)
+                    q.add_device(t[0], t[1], t[2], g0, g1)
+                    c.add_device(t[1], t[2], recs, g0, g1)
+                q.finish()
+                n_c, n_z = c.finish(q, tx_feature, n_tx // 2)
+                st = c.stats()
+                iters = c.cell_stats()["iterations"]
+                c.close()
+                q.close()
+                if step >= args.warmup:
+                    runs.append({"add_s": round(st["add_us"] * 1e-6, 4), "finish_s": round(st["finish_us"] * 1e-6, 4), "values_kernel_s": round(st["values_us"] * 1e-6, 5),
+                                 "cells": n_c, "matrix_entries": n_z, "names": st["names"], "entries": st["entries"], "pairs": st["pairs"], "slots": st["slots"],
+                                 "wave_cells": st["wave_cells"], "block_cells": st["block_cells"], "hbm_cells": st["hbm_cells"],
+                                 "iterations_mean": round(float(iters.mean()), 2), "iterations_max": int(iters.max())})
+            out[label] = runs
+            del t
+        print(json.dumps(out))
+        return
     if args.config == "collate":
         import ctypes as C
         n = args.reads or 10_000_000

@@ -39,8 +39,8 @@
 using namespace br;
 
 struct br_dedup : Accum {
-  int method = 1, umi_source = 0, keep_records = 0, mark = 0, hash_bits = 64;
-  uint32_t umi_sep = '_', umi_tag = 'R' | 'X' << 8, hist_max = 1000;
+  int method = 1, umi_source = 0, cell_source = 0, keep_records = 0, mark = 0, hash_bits = 64;
+  uint32_t umi_sep = '_', umi_tag = 'R' | 'X' << 8, cell_tag = 'C' | 'B' << 8, hist_max = 1000;
   uint64_t max_bytes = 0;   // 0: no cap on the arena but the device's memory
   bool added = false, finished = false, dead = false;
   uint64_t n = 0, rows = 0, used = 0;   // names, rows, arena bytes of all adds
@@ -48,7 +48,7 @@ struct br_dedup : Accum {
   uint64_t n_groups = 0, n_nodes = 0, n_edges = 0, sweeps = 0, max_nodes = 0, collisions = 0, n_mols = 0;
   uint64_t n_out = 0, cur = 0;
   double add_s = 0, finish_s = 0;
-  ColBuf small, umi, ulen, noff, nk, hash, ent, arena, rec_at;
+  ColBuf small, umi, ulen, cb, cblen, noff, nk, hash, ent, arena, rec_at;
   ColBuf rep, gfirst, dup, hist, rdup, sel, out_off;
   ColBuf buf[2], prow[2];
   int which = 0;
@@ -80,6 +80,8 @@ extern "C" int br_dedup_set_param(br_dedup *c, const char *name, int64_t value) 
   if (!strcmp(name, "method")) { if (!flag) return BR_ERR_INVALID_ARG; c->method = (int)value; return BR_OK; }
   if (!strcmp(name, "umi_source")) { if (!flag) return BR_ERR_INVALID_ARG; c->umi_source = (int)value; return BR_OK; }
   if (!strcmp(name, "umi_sep")) { if (value < 0 || value > 255) return BR_ERR_INVALID_ARG; c->umi_sep = (uint32_t)value; return BR_OK; }
+  if (!strcmp(name, "cell_source")) { if (value < 0 || value > 2) return BR_ERR_INVALID_ARG; c->cell_source = (int)value; return BR_OK; }
+  if (!strcmp(name, "cell_tag")) { if (value < 0 || value > 65535) return BR_ERR_INVALID_ARG; c->cell_tag = (uint32_t)value; return BR_OK; }
   if (!strcmp(name, "umi_tag")) { if (value < 0 || value > 65535) return BR_ERR_INVALID_ARG; c->umi_tag = (uint32_t)value; return BR_OK; }
   if (!strcmp(name, "keep_records")) { if (!flag) return BR_ERR_INVALID_ARG; c->keep_records = (int)value; return BR_OK; }
   if (!strcmp(name, "mark")) { if (!flag) return BR_ERR_INVALID_ARG; c->mark = (int)value; return BR_OK; }
@@ -101,6 +103,7 @@ static int dedup_reserve(br_dedup *c, uint64_t ng, uint64_t m, uint64_t bytes) {
   const uint64_t N = c->n + ng, R = c->rows + m;
   RC(dedup_grow(c, c->umi, N, 32)); RC(dedup_grow(c, c->ulen, N, 1)); RC(dedup_grow(c, c->noff, N, 8)); RC(dedup_grow(c, c->nk, N, 4));
   RC(dedup_grow(c, c->hash, N, 8)); RC(dedup_grow(c, c->ent, R, 16));
+  if (c->cell_source) { RC(dedup_grow(c, c->cb, N, 32)); RC(dedup_grow(c, c->cblen, N, 1)); }
   if (!c->keep_records) return BR_OK;
   const uint64_t need = c->used + bytes;
   if (c->max_bytes && need > c->max_bytes) return BR_ERR_CAPACITY;
@@ -135,6 +138,8 @@ static int dedup_add_names(br_dedup *c, DdAddArgs A, const uint8_t *data, uint64
     A.data = window.as<uint8_t>(); A.data_bias = first_off;
   }
   A.umi_source = c->umi_source; A.umi_sep = c->umi_sep; A.umi_tag = c->umi_tag;
+  A.cell_source = c->cell_source; A.cell_tag = c->cell_tag;
+  if (c->cell_source) { A.cb = c->cb.as<uint64_t>() + 4 * c->n; A.cblen = c->cblen.as<uint8_t>() + c->n; }
   A.raw = raw.as<uint4>(); A.ent = c->ent.as<uint32_t>(); A.row_base = c->rows;
   A.noff = c->noff.as<uint64_t>() + c->n; A.nk = c->nk.as<uint32_t>() + c->n; A.hash = c->hash.as<uint64_t>() + c->n;
   A.umi = c->umi.as<uint64_t>() + 4 * c->n; A.ulen = c->ulen.as<uint8_t>() + c->n;
@@ -311,15 +316,31 @@ static int dedup_finish(br_dedup *c) {
   RC(c->alloc(gbeg, (size_t)(G + 1) * 8)); RC(c->alloc(name_gid, n1 * 4));
   launch_col_gbeg(st, head.as<uint64_t>(), n, gbeg.as<uint64_t>());
   launch_dd_groups(st, head.as<uint64_t>(), gbeg.as<uint64_t>(), s.idx[0].as<uint32_t>(), n, c->gfirst.as<uint32_t>(), name_gid.as<uint32_t>());
-  // within the groups by (length, UMI): least significant word first, every sort stable, so the names of a node ascend
   const uint64_t *umi = c->umi.as<uint64_t>();
   const uint8_t *ulen = c->ulen.as<uint8_t>();
-  for (int w = 3; w >= 0; w--) {
-    launch_dd_ukey(st, s.idx[0].as<uint32_t>(), umi, ulen, name_gid.as<uint32_t>(), n, w, s.key[0].as<uint64_t>());
-    RC(dedup_sort(c, s, n, tmp));
+  // (group, length, bytes) of a 32-byte field: least significant word first, every sort stable, so equal items' names ascend
+  auto sort_by_field = [&](const uint64_t *words, const uint8_t *len) -> int {
+    for (int w = 3; w >= 0; w--) {
+      launch_dd_ukey(st, s.idx[0].as<uint32_t>(), words, len, name_gid.as<uint32_t>(), n, w, s.key[0].as<uint64_t>());
+      RC(dedup_sort(c, s, n, tmp));
+    }
+    launch_dd_ukey(st, s.idx[0].as<uint32_t>(), words, len, name_gid.as<uint32_t>(), n, 4, s.key[0].as<uint64_t>());
+    return dedup_sort(c, s, n, tmp);
+  };
+  if (c->cell_source) {   // per cell: a group of equal signatures is cut where the barcode changes, by the barcodes themselves
+    RC(sort_by_field(c->cb.as<uint64_t>(), c->cblen.as<uint8_t>()));
+    launch_dd_cheads(st, s.idx[0].as<uint32_t>(), c->cb.as<uint64_t>(), c->cblen.as<uint8_t>(), name_gid.as<uint32_t>(), n, head.as<uint64_t>());
+    launch_scan(st, head.as<uint64_t>(), n, tmp.as<uint64_t>());
+    HIPCHK(hipMemcpyAsync(&G, head.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (G < c->n_groups || G > M) return BR_ERR_HIP;
+    c->n_groups = G;
+    RC(c->alloc(gbeg, (size_t)(G + 1) * 8));
+    launch_col_gbeg(st, head.as<uint64_t>(), n, gbeg.as<uint64_t>());
+    launch_dd_groups(st, head.as<uint64_t>(), gbeg.as<uint64_t>(), s.idx[0].as<uint32_t>(), n, c->gfirst.as<uint32_t>(), name_gid.as<uint32_t>());
   }
-  launch_dd_ukey(st, s.idx[0].as<uint32_t>(), umi, ulen, name_gid.as<uint32_t>(), n, 4, s.key[0].as<uint64_t>());
-  RC(dedup_sort(c, s, n, tmp));
+  // within the groups by (length, UMI), so the names of a node ascend
+  RC(sort_by_field(umi, ulen));
   // nodes
   launch_dd_nheads(st, s.idx[0].as<uint32_t>(), umi, ulen, name_gid.as<uint32_t>(), n, head.as<uint64_t>());
   launch_scan(st, head.as<uint64_t>(), n, tmp.as<uint64_t>());

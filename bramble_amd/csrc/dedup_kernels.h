@@ -36,11 +36,13 @@ struct DdAddArgs {
   uint64_t r_first, r_last;
   const uint8_t *data; uint64_t data_bias; const uint64_t *rec_off; int64_t rec_bias;
   int umi_source; uint32_t umi_sep, umi_tag;
+  int cell_source; uint32_t cell_tag;             // "cell_source" 0: no barcode is read and cb, cblen are not written
   uint4 *raw;            // the add's entries in row order (r_last - r_first), scratch
   uint32_t *ent;         // the object's entry arena, four words an entry: a name's sorted entries sit at its first row's slot
   uint64_t row_base;
   uint64_t *noff; uint32_t *nk; uint64_t *hash;   // per name, at the add's first name: arena offset and length in WORDS, the signature's hash
   uint64_t *umi; uint8_t *ulen;                   // per name likewise: four words, the length
+  uint64_t *cb; uint8_t *cblen;                   // with "cell_source": the cell barcode likewise (a name without one: length 0)
   uint32_t *big;         // the names of more than DD_SMALL_ROWS rows
   uint64_t *rec_at;      // NULL, or ("keep_records") the arena offsets of the add's records, r_last - r_first + 1 of them from arena_base
   uint64_t arena_base;
@@ -55,6 +57,9 @@ void launch_dd_groups(hipStream_t st, const uint64_t *gid, const uint64_t *gbeg,
 void launch_dd_ukey(hipStream_t st, const uint32_t *idx, const uint64_t *umi, const uint8_t *ulen, const uint32_t *name_gid, int64_t n, int w, uint64_t *key);
 // head[j] = sorted item j starts a node: its (group, UMI) differs from item j - 1's, or it has no UMI
 void launch_dd_nheads(hipStream_t st, const uint32_t *idx, const uint64_t *umi, const uint8_t *ulen, const uint32_t *name_gid, int64_t n, uint64_t *head);
+// "cell_source": the items sorted by (group, barcode length, barcode bytes): head[j] = item j's (group, barcode) differs from item
+// j - 1's -- the per-cell position groups' starts (names without a barcode share the empty one)
+void launch_dd_cheads(hipStream_t st, const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, const uint32_t *name_gid, int64_t n, uint64_t *head);
 // the nodes in (group, length, bytes) order: key[q] = group << 32 | ~count, val[q] = q: to be sorted (stable) into the node order
 void launch_dd_node_key(hipStream_t st, const uint64_t *nbeg, const uint32_t *idx, const uint32_t *name_gid, int64_t n_nodes, uint64_t *key, uint32_t *val);
 struct DdNodes {

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/bramble_amd.h"
+#include "barcode_inl.h"
 #include "dedup_kernels.h"
 #include "wave_inl.h"
 
@@ -65,54 +66,13 @@ __device__ __forceinline__ uint64_t ent_hash(const uint4 e) {
 }
 __device__ __forceinline__ uint64_t sig_hash(uint64_t sum, uint64_t k) { return fmix64(sum ^ fmix64(k + 0x9E3779B97F4A7C15ull)); }
 
-// the UMI of a record (rec: [block_size][record], len bytes) into four words, bytes in comparison order, zero padded; its length,
-// 0: none.  too_long / bad_aux: why
+// the UMI of a record and, with "cell_source", its cell barcode (barcode_inl.h)
 __device__ __forceinline__ uint32_t umi_of(const DdAddArgs &A, const uint8_t *rec, uint64_t len, uint64_t w[4], bool &too_long, bool &bad_aux) {
-  w[0] = w[1] = w[2] = w[3] = 0;
-  too_long = bad_aux = false;
-  const uint64_t l_name = rec[12];
-  const uint8_t *u = nullptr;
-  uint64_t ul = 0;
-  if (A.umi_source == 0) {
-    if (l_name < 2 || 36 + l_name > len) return 0;
-    const uint64_t nl = l_name - 1;   // (without its NUL)
-    int64_t at = -1;
-    for (uint64_t i = 0; i < nl; i++) if (rec[36 + i] == (uint8_t)A.umi_sep) at = (int64_t)i;
-    if (at < 0) return 0;
-    u = rec + 36 + at + 1; ul = nl - (uint64_t)at - 1;
-  } else {
-    const uint64_t n_cigar = ld16(rec + 16), l_seq = ld32(rec + 20);
-    uint64_t p = 36 + l_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
-    if (p > len) { bad_aux = true; return 0; }
-    while (p < len) {
-      if (p + 3 > len) { bad_aux = true; return 0; }
-      const uint32_t tag = ld16(rec + p), type = rec[p + 2];
-      p += 3;
-      uint64_t size = 0;
-      if (type == 'A' || type == 'c' || type == 'C') size = 1;
-      else if (type == 's' || type == 'S') size = 2;
-      else if (type == 'i' || type == 'I' || type == 'f') size = 4;
-      else if (type == 'Z' || type == 'H') {
-        uint64_t e = p;
-        while (e < len && rec[e]) e++;
-        if (e >= len) { bad_aux = true; return 0; }   // no NUL inside the record
-        if (type == 'Z' && tag == A.umi_tag) { u = rec + p; ul = e - p; break; }
-        size = e - p + 1;
-      } else if (type == 'B') {
-        if (p + 5 > len) { bad_aux = true; return 0; }
-        const uint32_t sub = rec[p];
-        const uint64_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
-        if (!es) { bad_aux = true; return 0; }
-        size = 5 + es * (uint64_t)ld32(rec + p + 1);
-      } else { bad_aux = true; return 0; }
-      if (size > len - p) { bad_aux = true; return 0; }
-      p += size;
-    }
-    if (!u) return 0;
-  }
-  if (ul > (uint64_t)DD_UMI_MAX) { too_long = true; return 0; }
-  for (uint64_t i = 0; i < ul; i++) w[i >> 3] |= (uint64_t)u[i] << (56 - 8 * (i & 7));
-  return (uint32_t)ul;
+  return record_field(rec, len, A.umi_source == 0 ? BC_NAME_LAST : BC_TAG, A.umi_sep, A.umi_tag, w, too_long, bad_aux);
+}
+__device__ __forceinline__ uint32_t cell_of(const DdAddArgs &A, const uint8_t *rec, uint64_t len, uint64_t w[4]) {
+  bool too_long, bad_aux;
+  return record_field(rec, len, A.cell_source == 1 ? BC_NAME_PREV : BC_TAG, A.umi_sep, A.cell_tag, w, too_long, bad_aux);
 }
 }  // namespace
 
@@ -198,8 +158,8 @@ __global__ void __launch_bounds__(256) k_dd_names(DdAddArgs A) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   bool is_big = false, is_bad = false, no_umi = false, too_long = false, bad_aux = false;
   if (g < A.n_groups) {
-    uint64_t r0, r1, w[4] = {0, 0, 0, 0};
-    uint32_t ul = 0;
+    uint64_t r0, r1, w[4] = {0, 0, 0, 0}, cw[4] = {0, 0, 0, 0};
+    uint32_t ul = 0, cl = 0;
     if (!name_rows(A, g, r0, r1)) { is_bad = true; A.noff[g] = 4 * A.row_base; A.nk[g] = 0; A.hash[g] = 0; }
     else {
       const uint64_t o = 4 * (A.row_base + (r0 - A.r_first));
@@ -207,7 +167,10 @@ __global__ void __launch_bounds__(256) k_dd_names(DdAddArgs A) {
       if (r1 - r0 >= (1ull << 30)) is_bad = true;   // (the signature's length in words is 32-bit)
       else if (r1 > r0) {
         const uint8_t *rec; uint64_t len;
-        if (record_of(A, r0, rec, len)) { ul = umi_of(A, rec, len, w, too_long, bad_aux); no_umi = ul == 0u; }
+        if (record_of(A, r0, rec, len)) {
+          ul = umi_of(A, rec, len, w, too_long, bad_aux); no_umi = ul == 0u;
+          if (A.cell_source) cl = cell_of(A, rec, len, cw);
+        }
         if (r1 - r0 > (uint64_t)DD_SMALL_ROWS) is_big = true;
         else { uint64_t h; sig_small(A, r0, r1, o, h); A.hash[g] = h; }
       } else A.hash[g] = 0;
@@ -215,6 +178,11 @@ __global__ void __launch_bounds__(256) k_dd_names(DdAddArgs A) {
 #pragma unroll
     for (int k = 0; k < 4; k++) A.umi[4 * g + k] = w[k];
     A.ulen[g] = (uint8_t)ul;
+    if (A.cell_source) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) A.cb[4 * g + k] = cw[k];
+      A.cblen[g] = (uint8_t)cl;
+    }
   }
   const uint64_t bal = __ballot(is_big);
   if (bal) {
@@ -300,6 +268,22 @@ __global__ void __launch_bounds__(256) k_dd_nheads(const uint32_t *idx, const ui
 }
 void launch_dd_nheads(hipStream_t st, const uint32_t *idx, const uint64_t *umi, const uint8_t *ulen, const uint32_t *name_gid, int64_t n, uint64_t *head) {
   if (n > 0) hipLaunchKernelGGL(k_dd_nheads, dim3(blocks256(n)), dim3(256), 0, st, idx, umi, ulen, name_gid, n, head);
+}
+
+__global__ void __launch_bounds__(256) k_dd_cheads(const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, const uint32_t *name_gid, int64_t n,
+                                                   uint64_t *head) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  uint64_t h = 1;
+  if (j > 0) {
+    const uint64_t a = idx[j], b = idx[j - 1];
+    h = (cblen[a] != cblen[b] || name_gid[a] != name_gid[b] || cb[4 * a] != cb[4 * b] || cb[4 * a + 1] != cb[4 * b + 1] ||
+         cb[4 * a + 2] != cb[4 * b + 2] || cb[4 * a + 3] != cb[4 * b + 3]) ? 1 : 0;
+  }
+  head[j] = h;
+}
+void launch_dd_cheads(hipStream_t st, const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, const uint32_t *name_gid, int64_t n, uint64_t *head) {
+  if (n > 0) hipLaunchKernelGGL(k_dd_cheads, dim3(blocks256(n)), dim3(256), 0, st, idx, cb, cblen, name_gid, n, head);
 }
 
 __global__ void __launch_bounds__(256) k_dd_node_key(const uint64_t *nbeg, const uint32_t *idx, const uint32_t *name_gid, int64_t n_nodes, uint64_t *key,

@@ -55,7 +55,9 @@ void usage(FILE *f) {
           "               [--unprojected <unprojected.bam> [--unprojected-scope record|name]]\n"
           "               [--quant-bam <post.bam> [--quant-bam-mode tag|sample]]\n"
           "               [--dedup unique|directional [--dedup-umi name|tag] [--dedup-umi-sep C] [--dedup-umi-tag XY]\n"
-          "                [--dedup-stats <sizes.tsv>] [--dedup-bam <dedup.bam> [--dedup-bam-mode remove|mark]]]\n\n"
+          "                [--dedup-stats <sizes.tsv>] [--dedup-bam <dedup.bam> [--dedup-bam-mode remove|mark]]]\n"
+          "               [--cells <prefix> [--cells-barcode name|tag] [--cells-barcode-tag XY] [--cells-features gene|transcript]\n"
+          "                [--cells-multi unique|uniform|em]]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -138,7 +140,19 @@ void usage(FILE *f) {
           "still see every record.  Not with --quant-bam or --coverage-weight em.  --dedup-stats FILE: size<TAB>molecules, a line per\n"
           "molecule size that occurs.  --dedup-bam FILE: the projected records under the header the output has without --sort, without\n"
           "the duplicate names' (--dedup-bam-mode remove, the default) or all of them, the duplicates' with flag 0x400 (mark).  One more\n"
-          "line in front of the final report: [bramble] dedup: M molecules of N read names (D duplicates, U without UMI; G position groups; method unique|directional; add X.XXs, finish Y.YYs)\n");
+          "line in front of the final report: [bramble] dedup: M molecules of N read names (D duplicates, U without UMI; G position groups; method unique|directional; add X.XXs, finish Y.YYs)\n"
+          "--cells PREFIX: a single-cell count matrix on one GPU, beside --quant: the cell barcode of a read name is what lies between\n"
+          "the last two --dedup-umi-sep characters (default _) of the read name (--cells-barcode name, the default: umi_tools extract's\n"
+          "READ_CB_UMI) or the value of the --cells-barcode-tag tag (default CB; --cells-barcode tag), at most 32 bytes; a read name\n"
+          "without one is in no cell.  The features are genes (--cells-features gene, the default: the gene_id of the annotation or\n"
+          "--quant-gene-map, as for --quant-genes) or transcripts.  A read name whose transcripts span several features counts for none\n"
+          "(--cells-multi unique, the default: integer counts), for each an equal share (uniform) or the shares of an EM run per cell on\n"
+          "the GPU (em: STARsolo's and alevin's estimator).  PREFIXmatrix.mtx (Matrix Market, features x cells, the 10x layout),\n"
+          "PREFIXbarcodes.tsv, PREFIXfeatures.tsv and PREFIXcells.tsv (Barcode Names Unique Multi Features Iterations); the directory of\n"
+          "PREFIX must exist.  The matrix is the raw one: no whitelist, no barcode correction, no cell filtering.  With --dedup the\n"
+          "duplicates are found per cell (umi_tools' --per-cell) and the matrix counts molecules; quant.tsv then reflects the per-cell\n"
+          "molecules as well.  One more line in front of the final report: [bramble] cells: C cells, M of N read names counted (B\n"
+          "without barcode; Z matrix entries; features gene|transcript; multi unique|uniform|em; add X.XXs, finish Y.YYs)\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -147,7 +161,7 @@ int parse_args(int argc, char **argv, Options &o) {
   memset(&o.cfg, 0, sizeof(o.cfg));
   o.cfg.junc_miss_discount = 1.0;
   bool codec = false, host_codec = false;   // a BGZF codec option was given; one that asks for the host codec
-  bool coverage_weight_given = false, unprojected_scope_given = false, quant_bam_mode_given = false, dedup_switch_given = false, dedup_bam_mode_given = false;
+  bool coverage_weight_given = false, unprojected_scope_given = false, quant_bam_mode_given = false, dedup_switch_given = false, dedup_bam_mode_given = false, cells_switch_given = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "%s: missing value\n", argv[i]); return nullptr; } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -269,6 +283,33 @@ int parse_args(int argc, char **argv, Options &o) {
       if (strlen(v) != 2) { fprintf(stderr, "--dedup-umi-tag: %s is not a two-character tag\n", v); return -1; }
       o.dedup_umi_tag = (unsigned char)v[0] | (unsigned char)v[1] << 8; dedup_switch_given = true;
     }
+    else if (a == "--cells") { const char *v = value(); if (!v) return -1; o.cells = v; }
+    else if (a == "--cells-barcode") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "name") o.cells_barcode = 0; else if (w == "tag") o.cells_barcode = 1;
+      else { fprintf(stderr, "--cells-barcode: unknown source %s (name or tag)\n", v); return -1; }
+      cells_switch_given = true;
+    }
+    else if (a == "--cells-barcode-tag") {
+      const char *v = value(); if (!v) return -1;
+      if (strlen(v) != 2) { fprintf(stderr, "--cells-barcode-tag: %s is not a two-character tag\n", v); return -1; }
+      o.cells_barcode_tag = (unsigned char)v[0] | (unsigned char)v[1] << 8; cells_switch_given = true;
+    }
+    else if (a == "--cells-features") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "gene") o.cells_features = 0; else if (w == "transcript") o.cells_features = 1;
+      else { fprintf(stderr, "--cells-features: unknown features %s (gene or transcript)\n", v); return -1; }
+      cells_switch_given = true;
+    }
+    else if (a == "--cells-multi") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "unique") o.cells_multi = 0; else if (w == "uniform") o.cells_multi = 1; else if (w == "em") o.cells_multi = 2;
+      else { fprintf(stderr, "--cells-multi: unknown mode %s (unique, uniform or em)\n", v); return -1; }
+      cells_switch_given = true;
+    }
     else if (a == "--dedup-stats") { const char *v = value(); if (!v) return -1; o.dedup_stats = v; dedup_switch_given = true; }
     else if (a == "--dedup-bam") { const char *v = value(); if (!v) return -1; o.dedup_bam = v; dedup_switch_given = true; }
     else if (a == "--dedup-bam-mode") {
@@ -296,6 +337,7 @@ int parse_args(int argc, char **argv, Options &o) {
   if (o.sam_out && codec) { fprintf(stderr, "--compression-level, --host-deflate and --device-deflate apply to BAM output, not to --output-fmt sam\n"); return -1; }
   if (o.collate && o.devices.size() > 1) { fprintf(stderr, "--collate works on one device: give --device N, not a --devices list\n"); return -1; }
   if (o.sort && o.devices.size() > 1) { fprintf(stderr, "--sort works on one device: give --device N, not a --devices list\n"); return -1; }
+  if (!o.cells.empty() && o.devices.size() > 1) { fprintf(stderr, "--cells works on one device: give --device N, not a --devices list\n"); return -1; }
   if (!o.quant.empty() && o.devices.size() > 1) { fprintf(stderr, "--quant works on one device: give --device N, not a --devices list\n"); return -1; }
   if (o.quant.empty() && (!o.quant_classes.empty() || o.quant_length_norm >= 0)) { fprintf(stderr, "--quant-classes, --quant-length-norm and --quant-no-length-norm need --quant\n"); return -1; }
   if (o.quant.empty() && (o.quant_eff_length || !o.quant_fld.empty())) { fprintf(stderr, "--quant-eff-length and --quant-fld need --quant\n"); return -1; }
@@ -308,7 +350,10 @@ int parse_args(int argc, char **argv, Options &o) {
   if (!o.quant_vb && (o.quant_vb_prior_given || o.quant_vb_per_nt)) { fprintf(stderr, "--quant-vb-prior and --quant-vb-per-nucleotide need --quant-vb: without it there is no prior\n"); return -1; }
   if (o.quant_vb_per_nt && (o.quant_length_norm == 0 || ((o.cfg.lr || o.cfg.lr_hq) && o.quant_length_norm != 1))) { fprintf(stderr, "--quant-vb-per-nucleotide needs length normalisation: the prior is scaled by the length the reads are weighted by (not with --quant-no-length-norm; under --lr / --lr-hq only with --quant-length-norm)\n"); return -1; }
   if (o.quant.empty() && !o.quant_genes.empty()) { fprintf(stderr, "--quant-genes needs --quant\n"); return -1; }
-  if (o.quant_genes.empty() && (!o.quant_gene_classes.empty() || !o.quant_gene_map.empty())) { fprintf(stderr, "--quant-gene-classes and --quant-gene-map need --quant-genes\n"); return -1; }
+  const bool cell_genes = !o.cells.empty() && o.cells_features == 0;   // (--cells takes its genes where --quant-genes does)
+  if (o.quant_genes.empty() && (!o.quant_gene_classes.empty() || (!o.quant_gene_map.empty() && !cell_genes))) { fprintf(stderr, "--quant-gene-classes and --quant-gene-map need --quant-genes\n"); return -1; }
+  if (cells_switch_given && o.cells.empty()) { fprintf(stderr, "--cells-barcode, --cells-barcode-tag, --cells-features and --cells-multi need --cells\n"); return -1; }
+  if (!o.cells.empty() && o.quant.empty()) { fprintf(stderr, "--cells needs --quant: the matrix is made from the quantifier's classes\n"); return -1; }
   if (!o.quant_boot_out.empty() && !o.quant_bootstraps) { fprintf(stderr, "--quant-boot-out needs --quant-bootstraps: without it there are no replicates\n"); return -1; }
   if (!o.quant_fld.empty() && !o.quant_eff_length) { fprintf(stderr, "--quant-fld needs --quant-eff-length: without it no fragment lengths are counted\n"); return -1; }
   if (o.quant_eff_length && o.quant_length_norm == 0) { fprintf(stderr, "--quant-eff-length is a length normalisation: not with --quant-no-length-norm\n"); return -1; }
@@ -779,7 +824,7 @@ extern "C" int br_cli_main(int argc, char **argv) {
     env.tx.len.push_back(br_index_transcript_len(ix0, (uint32_t)t));
   }
   number_sq(env.tx);
-  if (!o.quant_genes.empty()) {   // the genes beside the names: the annotation's, or the map's
+  if (!o.quant_genes.empty() || (!o.cells.empty() && o.cells_features == 0)) {   // the genes beside the names: the annotation's, or the map's
     const char *const *gene_ids = br_annotation_gene_ids(ann);
     if (env.tx.name.size() != n_tx) { fprintf(stderr, "error: the index does not hold the annotation's transcripts\n"); return give_up(); }
     for (size_t t = 0; t < n_tx; t++) env.tx.gene.push_back(o.quant_gene_map.empty() ? gene_ids[t] : gene_map.find(env.tx.name[t])->second.c_str());

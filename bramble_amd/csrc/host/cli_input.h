@@ -64,6 +64,11 @@ struct Options {
   std::string dedup_stats;       // --dedup-stats FILE: size<TAB>molecules, a line per non-empty bin of the histogram
   std::string dedup_bam;         // --dedup-bam FILE: the projected records without the duplicate names' (or with 0x400 on them), under the unsorted output's header
   int dedup_bam_mode = 0;        // --dedup-bam-mode remove|mark: br_dedup's "mark" (0, 1)
+  std::string cells;             // --cells PREFIX: the cell x feature matrix of the run (br_cells): PREFIXmatrix.mtx, barcodes.tsv, features.tsv, cells.tsv
+  int cells_barcode = 0;         // --cells-barcode name|tag: br_cells' "barcode_source" (0, 1); with --dedup its "cell_source" (1, 2)
+  int cells_barcode_tag = 'C' | 'B' << 8;   // --cells-barcode-tag XY: "barcode_tag" / "cell_tag"
+  int cells_features = 0;        // --cells-features gene|transcript (0, 1)
+  int cells_multi = 0;           // --cells-multi unique|uniform|em: br_cells' "mode" (0, 1, 2)
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };
 inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }

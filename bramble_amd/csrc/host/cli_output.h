@@ -1,5 +1,5 @@
 // What consumes a run of the command line (cli.cpp) beside the main output: --sort (cli_output_sort.cpp), --dedup
-// (cli_output_dedup.cpp), --quant (cli_output_quant.cpp), --coverage (cli_output_coverage.cpp), --unprojected (cli_output_unprojected.cpp), --quant-bam (cli_output_assign.cpp), behind one interface.  A consumer takes something from every
+// (cli_output_dedup.cpp), --quant (cli_output_quant.cpp), --cells (cli_output_cells.cpp), --coverage (cli_output_coverage.cpp), --unprojected (cli_output_unprojected.cpp), --quant-bam (cli_output_assign.cpp), behind one interface.  A consumer takes something from every
 // projected bundle on device o.devices[0], does its device work once the input is through, writes its files (cli_output_files.h)
 // and prints one report line; the runners, the writer and br_cli_main loop over the consumers and never learn which kind one is.
 #pragma once
@@ -51,6 +51,7 @@ std::unique_ptr<Consumer> open_coverage(const RunEnv &env, std::string &err);
 std::unique_ptr<Consumer> open_unprojected(const RunEnv &env, std::string &err);   // (begins its file: err is the writer's)
 std::unique_ptr<Consumer> open_assign(const RunEnv &env, std::string &err);        // (likewise)
 std::unique_ptr<Consumer> open_dedup(const RunEnv &env, std::string &err);         // (likewise, with --dedup-bam)
+std::unique_ptr<Consumer> open_cells(const RunEnv &env, std::string &err);         // (it tries PREFIX: err may be the file's)
 // (for the three above) T::open() makes the library's object and sets its parameters
 template <typename T>
 std::unique_ptr<Consumer> open_as(const RunEnv &env, std::string &err) {
@@ -59,12 +60,12 @@ std::unique_ptr<Consumer> open_as(const RunEnv &env, std::string &err) {
   return c;
 }
 
-// the consumers the options ask for, in the order sort, dedup, quant, coverage, unprojected, quant-bam -- the order of their finish() as well: quant
+// the consumers the options ask for, in the order sort, dedup, quant, cells, coverage, unprojected, quant-bam -- the order of their finish() as well: quant
 // drops the names dedup's finish() has found to be duplicates (Consumer::duplicate_flags), coverage under --coverage-weight em and
-// --quant-bam read the quantifier (Consumer::quantifier) whose EM quant's finish() has run; false: `err` says which could not be made
+// --quant-bam read the quantifier (Consumer::quantifier) whose EM quant's finish() has run, cells its classes; false: `err` says which could not be made
 inline bool open_consumers(const RunEnv &env, std::vector<std::unique_ptr<Consumer>> &out, std::string &err) {
   const Options &o = env.o;
-  const std::pair<bool, decltype(&open_sort)> wanted[] = {{o.sort, open_sort}, {o.dedup >= 0, open_dedup}, {!o.quant.empty(), open_quant}, {!o.coverage.empty() || !o.coverage_summary.empty(), open_coverage}, {!o.unprojected.empty(), open_unprojected}, {!o.quant_bam.empty(), open_assign}};
+  const std::pair<bool, decltype(&open_sort)> wanted[] = {{o.sort, open_sort}, {o.dedup >= 0, open_dedup}, {!o.quant.empty(), open_quant}, {!o.cells.empty(), open_cells}, {!o.coverage.empty() || !o.coverage_summary.empty(), open_coverage}, {!o.unprojected.empty(), open_unprojected}, {!o.quant_bam.empty(), open_assign}};
   for (auto &[want, open] : wanted) {
     if (!want) continue;
     out.push_back(open(env, err));

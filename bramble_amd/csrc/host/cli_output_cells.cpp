@@ -1,0 +1,98 @@
+// --cells PREFIX and its switches (cli_output.h): every bundle's names and records go to a br_cells (br_cells_add_last), which keeps
+// the cell barcode of every read name.  Its finish() runs behind the --quant consumer's (open_consumers' order), which it met through
+// Consumer::quantifier: the quantifier's classes per name (with --dedup: without the names that consumer found to be duplicates, per
+// cell) become the sparse cell x feature matrix on the device, the features being the genes env.tx numbers or the @SQ transcripts.
+// Four files through SideFiles: PREFIXmatrix.mtx, PREFIXbarcodes.tsv, PREFIXfeatures.tsv, PREFIXcells.tsv.
+#include "cli_output.h"
+
+namespace brcli {
+namespace {
+
+class CellsOut : public Consumer {
+ public:
+  explicit CellsOut(const RunEnv &e)
+      : Consumer(e, "cell matrix", "the cell matrix"), matrix(e.o.cells + "matrix.mtx"), barcodes(e.o.cells + "barcodes.tsv"),
+        features(e.o.cells + "features.tsv"), table(e.o.cells + "cells.tsv") {}
+  ~CellsOut() override {
+    if (probed) remove(matrix.tmp.c_str());   // (a set-up error elsewhere: no settle came)
+    if (c) br_cells_free(c);
+  }
+  // PREFIX is tried here, in front of the run: a directory that is not there fails before anything is projected
+  bool open(std::string &err) {
+    const Options &o = env.o;
+    FILE *f = fopen(matrix.tmp.c_str(), "w");
+    if (!f) { err = "--cells: could not write " + matrix.tmp + " (the directory of the prefix must exist)"; return false; }
+    fclose(f);
+    probed = true;
+    int rc = br_cells_new(env.device, &c);
+    if (!rc) rc = br_cells_set_param(c, "barcode_source", o.cells_barcode);
+    if (!rc) rc = br_cells_set_param(c, "barcode_sep", o.dedup_umi_sep);
+    if (!rc) rc = br_cells_set_param(c, "barcode_tag", o.cells_barcode_tag);
+    if (!rc) rc = br_cells_set_param(c, "mode", o.cells_multi);
+    if (rc) { err = std::string(name) + " on device " + std::to_string(env.device) + ": " + br_strerror(rc); return false; }
+    return true;
+  }
+  int add(br_ctx *ctx) override { return br_cells_add_last(c, ctx); }
+  bool meet(const std::vector<std::unique_ptr<Consumer>> &all) override {
+    for (auto &other : all) if (other->quantifier()) quant = other.get();
+    return quant != nullptr;
+  }
+  int finish() override {
+    const bool genes = env.o.cells_features == 0;
+    const size_t nt = env.tx.len.size();
+    std::vector<uint32_t> tx_feature(nt + 1, 0);   // (a transcript outside the @SQ list has no rows: its entry is never read)
+    for (size_t t = 0; t < nt; t++) tx_feature[t] = genes ? env.tx.gene_of[t] : env.tx.sq_of[t] >= 0 ? (uint32_t)env.tx.sq_of[t] : 0u;
+    n_features = genes ? env.tx.gene_name.size() : (size_t)env.tx.n_sq;
+    int64_t n_cells = 0, n_entries = 0;
+    int rc = br_cells_finish(c, quant->quantifier(), tx_feature.data(), (int64_t)n_features, &n_cells, &n_entries);   // (the quantifier's finish() has run)
+    if (!rc) {
+      const size_t k = (size_t)n_cells, z = (size_t)n_entries;
+      cb.resize(32 * k + 1); len.resize(k); names.resize(k + 1); unique.resize(k + 1); multi.resize(k + 1); n_feat.resize(k + 1); iters.resize(k + 1);
+      cell_off.resize(k + 1); feature.resize(z + 1); value.resize(z + 1);
+      rc = br_cells_cell_barcodes(c, 0, n_cells, cb.data(), len.data());
+      if (!rc) rc = br_cells_cell_stats(c, 0, n_cells, names.data(), unique.data(), multi.data(), n_feat.data(), iters.data());
+      if (!rc) rc = br_cells_matrix(c, 0, n_cells, cell_off.data(), feature.data(), value.data());
+    }
+    (void)br_cells_stats(c, st);
+    return rc;
+  }
+  bool write_files(brio::BgzfWriter &, const std::vector<br_bgzf_span> &) override {
+    probed = false;   // (the matrix's own file takes the place of the trial)
+    if (FILE *f = matrix.open()) write_cells_matrix(f, n_features, cell_off, feature, value, env.o.cells_multi == 0);
+    if (!matrix.close()) return false;
+    if (FILE *f = barcodes.open()) write_cells_table(f, cb, len, names, unique, multi, n_feat, iters, false);
+    if (!barcodes.close()) return false;
+    if (FILE *f = features.open()) write_cells_features(f, env.tx, env.o.cells_features == 0);
+    if (!features.close()) return false;
+    if (FILE *f = table.open()) write_cells_table(f, cb, len, names, unique, multi, n_feat, iters, true);
+    return table.close();
+  }
+  bool settle(bool failed) override { probed = false; return settle_all({&matrix, &barcodes, &features, &table}, failed); }
+  void report() const override {
+    static const char *const multi_name[] = {"unique", "uniform", "em"};
+    printf("[bramble] cells: %llu cells, %llu of %llu read names counted (%llu without barcode; %llu matrix entries; features %s; multi %s; add %.2fs, finish %.2fs)\n",
+           (unsigned long long)st[5], (unsigned long long)st[1], (unsigned long long)st[0], (unsigned long long)st[2], (unsigned long long)st[9],
+           env.o.cells_features == 0 ? "gene" : "transcript", multi_name[env.o.cells_multi], (double)st[13] * 1e-6, (double)st[14] * 1e-6);
+  }
+ private:
+  br_cells *c = nullptr;
+  Consumer *quant = nullptr;   // the --quant consumer, which outlives neither of the two
+  SideFile matrix, barcodes, features, table;
+  bool probed = false;
+  size_t n_features = 0;
+  uint64_t st[16] = {};
+  std::vector<uint8_t> cb, len;
+  std::vector<uint64_t> names, unique, multi, cell_off;
+  std::vector<uint32_t> n_feat, iters, feature;
+  std::vector<double> value;
+};
+
+}  // namespace
+
+std::unique_ptr<Consumer> open_cells(const RunEnv &env, std::string &err) {
+  auto c = std::make_unique<CellsOut>(env);
+  if (!c->open(err)) return nullptr;
+  return c;
+}
+
+}  // namespace brcli

@@ -31,6 +31,8 @@ class DedupOut : public Consumer {
     if (!rc) rc = br_dedup_set_param(d, "umi_source", o.dedup_umi);
     if (!rc) rc = br_dedup_set_param(d, "umi_sep", o.dedup_umi_sep);
     if (!rc) rc = br_dedup_set_param(d, "umi_tag", o.dedup_umi_tag);
+    if (!rc && !o.cells.empty()) rc = br_dedup_set_param(d, "cell_source", 1 + o.cells_barcode);   // (--cells: duplicates per cell)
+    if (!rc && !o.cells.empty()) rc = br_dedup_set_param(d, "cell_tag", o.cells_barcode_tag);
     if (!rc && !file.path.empty()) rc = br_dedup_set_param(d, "keep_records", 1);
     if (!rc && !file.path.empty()) rc = br_dedup_set_param(d, "mark", o.dedup_bam_mode);
     if (rc) { err = std::string(name) + " on device " + std::to_string(env.device) + ": " + br_strerror(rc); return false; }

@@ -52,6 +52,35 @@ void number_genes(TxTable &tx) {
     }
 }
 
+void write_cells_matrix(FILE *f, size_t n_features, const std::vector<uint64_t> &cell_off, const std::vector<uint32_t> &feature,
+                        const std::vector<double> &value, bool integer) {
+  const size_t n_cells = cell_off.empty() ? 0 : cell_off.size() - 1;
+  fprintf(f, "%%%%MatrixMarket matrix coordinate %s general\n%%\n%zu %zu %llu\n", integer ? "integer" : "real", n_features, n_cells,
+          (unsigned long long)(n_cells ? cell_off[n_cells] : 0));
+  for (size_t k = 0; k < n_cells; k++)
+    for (uint64_t z = cell_off[k]; z < cell_off[k + 1]; z++) {
+      if (integer) fprintf(f, "%u %zu %llu\n", feature[z] + 1, k + 1, (unsigned long long)value[z]);
+      else fprintf(f, "%u %zu %.10g\n", feature[z] + 1, k + 1, value[z]);
+    }
+}
+
+void write_cells_features(FILE *f, const TxTable &tx, bool genes) {
+  if (genes) for (const char *g : tx.gene_name) fprintf(f, "%s\t%s\tGene Expression\n", g, g);
+  else for (size_t t = 0; t < tx.len.size(); t++) if (tx.len[t] > 0) fprintf(f, "%s\t%s\tGene Expression\n", tx.name[t], tx.name[t]);
+}
+
+// table: the whole line; else the barcode alone (barcodes.tsv)
+void write_cells_table(FILE *f, const std::vector<uint8_t> &barcodes, const std::vector<uint8_t> &len, const std::vector<uint64_t> &names,
+                       const std::vector<uint64_t> &unique, const std::vector<uint64_t> &multi, const std::vector<uint32_t> &features,
+                       const std::vector<uint32_t> &iters, bool table) {
+  if (table) fprintf(f, "Barcode\tNames\tUnique\tMulti\tFeatures\tIterations\n");
+  for (size_t k = 0; k < len.size(); k++) {
+    fwrite(barcodes.data() + 32 * k, 1, len[k], f);
+    if (table) fprintf(f, "\t%llu\t%llu\t%llu\t%u\t%u", (unsigned long long)names[k], (unsigned long long)unique[k], (unsigned long long)multi[k], features[k], iters[k]);
+    fputc('\n', f);
+  }
+}
+
 void write_quant_table(FILE *f, const TxTable &tx, const std::vector<double> *eff, const std::vector<double> &theta, const std::vector<double> &tpm,
                        const std::vector<uint64_t> &unique, const std::vector<uint64_t> &ambig, const std::vector<double> *boot_mean,
                        const std::vector<double> *boot_var) {

@@ -25,7 +25,7 @@ class QuantOut : public Consumer {
     if (!rc && o.quant_vb) rc = br_quant_set_param(q, "vb", 1);
     if (!rc && o.quant_vb) rc = br_quant_set_vb_prior(q, o.quant_vb_prior);
     if (!rc && o.quant_vb_per_nt) rc = br_quant_set_param(q, "vb_per_nucleotide", 1);
-    if (!rc && (o.coverage_weight == 2 || !o.quant_bam.empty())) rc = br_quant_set_param(q, "keep_names", 1);   // (the coverage and the posterior-BAM consumers join rows to classes by name)
+    if (!rc && (o.coverage_weight == 2 || !o.quant_bam.empty() || !o.cells.empty())) rc = br_quant_set_param(q, "keep_names", 1);   // (the coverage, posterior-BAM and cells consumers join names to classes)
     return rc;
   }
   int add(br_ctx *ctx) override { return br_quant_add_last(q, ctx); }

@@ -764,6 +764,15 @@ int br::quant_view(br_quant *c, QuantView *v) {
   return BR_OK;
 }
 
+int br::quant_class_view(br_quant *c, QuantClassView *v) {
+  if (!c || !v || !c->finished || !c->keep_names) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->st));
+  v->device = c->device; v->n_names = c->n; v->n_tx = c->n_tx; v->n_cls = c->cls.n_cls; v->n_lab = c->cls.n_lab;
+  v->name_cls = c->name_cls.as<uint32_t>(); v->label_off = c->cls.loff.as<uint64_t>(); v->labels = c->cls.labels.as<uint32_t>();
+  return BR_OK;
+}
+
 // ---- bootstrap replicates (the definitions: bramble_amd.h, br_quant) ---------------------------------------------------------------
 // cum: the exclusive prefix sums of the classes' counts, cum[C] = the names with labels
 static int quant_boot_cum(br_quant *c) {

@@ -18,4 +18,15 @@ struct QuantView {
 // BR_ERR_INVALID_ARG before br_quant_em or without "keep_names"; it waits for the quantifier's stream
 int quant_view(br_quant *, QuantView *);
 
+// The classes alone, which br_quant_finish with "keep_names" has made: no EM is asked for (br_cells_finish is the reader).  Valid
+// until the quantifier is freed.  BR_ERR_INVALID_ARG before br_quant_finish or without "keep_names"; it waits for the stream
+struct QuantClassView {
+  int device;
+  int64_t n_names, n_tx, n_cls, n_lab;
+  const uint32_t *name_cls;     // as above
+  const uint64_t *label_off;
+  const uint32_t *labels;
+};
+int quant_class_view(br_quant *, QuantClassView *);
+
 }  // namespace br

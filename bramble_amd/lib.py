@@ -190,6 +190,8 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_assign_stats", "br_assign_free",
            "br_dedup_new", "br_dedup_set_param", "br_dedup_add", "br_dedup_add_last", "br_dedup_finish", "br_dedup_umis", "br_dedup_result",
            "br_dedup_hist", "br_dedup_flags", "br_dedup_next", "br_dedup_stats", "br_dedup_free", "br_quant_drop_names",
+           "br_cells_new", "br_cells_set_param", "br_cells_set_tolerance", "br_cells_add", "br_cells_add_last", "br_cells_barcodes", "br_cells_finish",
+           "br_cells_cell_barcodes", "br_cells_name_cells", "br_cells_matrix", "br_cells_cell_stats", "br_cells_stats", "br_cells_free",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_direct_tidwords", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -1789,10 +1791,11 @@ class Dedup(_Accumulator):
     read name whether it is a PCR copy (result: rep, group_first, dup), the molecules' size histogram (hist) and, with
     "keep_records", the records again without the duplicates' ("mark" 0) or with 0x400 set on them ("mark" 1).  set_param: "method"
     (METHODS), "umi_source" (SOURCES), "umi_sep", "umi_tag", "keep_records", "mark", "max_bytes", "hist_max" before the first add,
-    "hash_bits" before finish."""
+    "hash_bits" before finish.  "cell_source" (CELL_SOURCES) and "cell_tag" before the first add: position groups per cell."""
 
     METHODS = {"unique": 0, "directional": 1}
     SOURCES = {"name": 0, "tag": 1}
+    CELL_SOURCES = {"none": 0, "name": 1, "tag": 2}
     STATS = ("names", "names_with_rows", "no_umi", "umi_too_long", "bad_aux", "groups", "nodes", "edges", "sweeps", "max_group_nodes",
              "collisions", "held_bytes", "peak_bytes", "add_us", "finish_us", "records_out")
 
@@ -1813,7 +1816,7 @@ class Dedup(_Accumulator):
             self.set_param(k, v)
 
     def set_param(self, name, value):
-        if name == "umi_tag" and not isinstance(value, int):
+        if name in ("umi_tag", "cell_tag") and not isinstance(value, int):
             b = value.encode() if isinstance(value, str) else bytes(value)
             value = b[0] | b[1] << 8
         if name == "umi_sep" and not isinstance(value, int):
@@ -1898,6 +1901,141 @@ class Dedup(_Accumulator):
         return piece
 
     pieces = Sorter.pieces
+
+    def stats(self):
+        out = np.zeros(16, np.uint64)
+        self._call("stats", out.ctypes.data)
+        return {k: int(v) for k, v in zip(self.STATS, out)}
+
+
+class Cells(_Accumulator):
+    """br_cells on `device`: the names of projected batches and the records they were encoded to, in; after finish(quant, tx_feature,
+    n_features) the cell x feature matrix of the quantifier's classes (matrix: CSR by cell), the cells' barcodes and numbers.
+    set_param before the first add: "barcode_source" (SOURCES), "barcode_sep", "barcode_tag", "mode" (MODES), "max_iters", "hash_bits",
+    "lds_bytes"; `tolerance` likewise."""
+
+    SOURCES = {"name": 0, "tag": 1}
+    MODES = {"unique": 0, "uniform": 1, "em": 2}
+    STATS = ("names", "counted", "no_barcode", "barcode_too_long", "bad_aux", "cells", "entries", "pairs", "slots", "matrix_entries",
+             "wave_cells", "block_cells", "hbm_cells", "add_us", "finish_us", "values_us")
+
+    NAME = "cells"
+    ARGTYPES = {"new": [C.c_int, _P(C.c_void_p)], "set_param": [C.c_void_p, C.c_char_p, C.c_int64], "set_tolerance": [C.c_void_p, C.c_double],
+                "add": [C.c_void_p, C.c_void_p, _P(BrDeviceRows), C.c_void_p, C.c_int64, C.c_int, C.c_void_p],
+                "add_last": [C.c_void_p, C.c_void_p], "barcodes": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
+                "finish": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _P(C.c_int64), _P(C.c_int64)],
+                "cell_barcodes": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
+                "name_cells": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
+                "matrix": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+                "cell_stats": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                "stats": [C.c_void_p, C.c_void_p], "free": [C.c_void_p]}
+
+    def __init__(self, device=0, tolerance=None, **params):
+        self.n_cells = self.n_entries = 0
+        self._open(device)
+        for k, v in params.items():
+            self.set_param(k, v)
+        if tolerance is not None:
+            self.set_tolerance(tolerance)
+
+    def set_param(self, name, value):
+        if name == "barcode_tag" and not isinstance(value, int):
+            b = value.encode() if isinstance(value, str) else bytes(value)
+            value = b[0] | b[1] << 8
+        if name == "barcode_sep" and not isinstance(value, int):
+            value = (value.encode() if isinstance(value, str) else bytes(value))[0]
+        super().set_param(name, value)
+
+    def set_tolerance(self, tolerance):
+        self._call("set_tolerance", float(tolerance))
+
+    def add_raw(self, recs, row_off, n_rows, group_off, n_groups, on_device, stream=None):
+        """br_cells_add as it is (recs: a BrDeviceBam or None; the tables as addresses): the return code (0, or a BR_ERR_* value)."""
+        rows = BrDeviceRows()
+        rows.n_rows, rows.n_pool_words = int(n_rows), 0
+        rows.a, rows.cigar, rows.pool, rows.row_off = None, None, None, row_off
+        return self._raw("add", C.cast(C.byref(recs), C.c_void_p) if recs is not None else None, C.byref(rows), C.c_void_p(group_off), int(n_groups),
+                         1 if on_device else 0, C.c_void_p(stream or 0))
+
+    def add_host(self, row_off, group_off, stream_np, rec_off=None):
+        """The read names group_off[0 .. n] (row_off uint64 per alignment) and their rows' records as an uncompressed record stream
+        (row i = record i), all in host memory."""
+        ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+        go = np.ascontiguousarray(group_off, dtype=np.uint32)
+        data = np.ascontiguousarray(stream_np, dtype=np.uint8)
+        off = Sorter.row_offsets(data) if rec_off is None else np.ascontiguousarray(rec_off, dtype=np.uint64)
+        recs = BrDeviceBam(data.ctypes.data if data.size else None, data.size, off.ctypes.data, len(off) - 1)
+        check(self.add_raw(recs, ro.ctypes.data, len(off) - 1, go.ctypes.data, len(go) - 1, False), "br_cells_add")
+
+    def add_device(self, row_off, group_off, recs, g0=0, g1=None):
+        """The same tables as torch CUDA tensors; the read names [g0, g1) of them are added.  recs: a BrDeviceBam of the rows' records
+        in HBM."""
+        import torch
+        g1 = group_off.numel() - 1 if g1 is None else g1
+        check(self.add_raw(recs, row_off.data_ptr(), recs.n_rows, group_off.data_ptr() + 4 * g0, g1 - g0, True,
+                           torch.cuda.current_stream(row_off.device).cuda_stream), "br_cells_add")
+
+    def add_last(self, ctx):
+        """The names and records of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
+        self._call("add_last", ctx.h)
+
+    @staticmethod
+    def _barcode_list(cb, ln):
+        return [bytes(cb[i, :ln[i]]) if ln[i] else None for i in range(len(ln))]
+
+    def barcodes(self, first, n):
+        """-> (barcode uint8 [n, 32] zero padded, len uint8 [n]) of the add-order names [first, first + n)"""
+        k = max(int(n), 1)
+        cb, ln = np.zeros((k, 32), np.uint8), np.zeros(k, np.uint8)
+        self._call("barcodes", int(first), int(n), cb.ctypes.data, ln.ctypes.data)
+        return cb[:n], ln[:n]
+
+    def finish_raw(self, quant, tx_feature, n_features):
+        """br_cells_finish as it is -> the return code"""
+        tf = np.ascontiguousarray(tx_feature, dtype=np.uint32)
+        n, z = C.c_int64(), C.c_int64()
+        rc = self._raw("finish", quant.h if quant is not None else None, tf.ctypes.data if tf.size else None, int(n_features), C.byref(n), C.byref(z))
+        if rc == 0:
+            self.n_cells, self.n_entries = int(n.value), int(z.value)
+        return rc
+
+    def finish(self, quant, tx_feature, n_features):
+        """quant: a Quant after finish() with "keep_names"; tx_feature: uint32 per transcript -> (cells, matrix entries)"""
+        check(self.finish_raw(quant, tx_feature, n_features), "br_cells_finish")
+        return self.n_cells, self.n_entries
+
+    def cell_barcodes(self, first=0, n=None):
+        """-> the cells' barcodes as a list of bytes"""
+        n = self.n_cells - first if n is None else n
+        k = max(int(n), 1)
+        cb, ln = np.zeros((k, 32), np.uint8), np.zeros(k, np.uint8)
+        self._call("cell_barcodes", int(first), int(n), cb.ctypes.data, ln.ctypes.data)
+        return self._barcode_list(cb[:n], ln[:n])
+
+    def name_cells(self, first, n):
+        """-> uint32 per add-order name: its cell, 0xffffffff for a name in none"""
+        out = np.zeros(max(int(n), 1), np.uint32)
+        self._call("name_cells", int(first), int(n), out.ctypes.data)
+        return out[:n]
+
+    def matrix(self, first=0, n=None):
+        """-> (cell_off uint64 [n + 1], feature uint32, value float64): CSR by cell, features ascending"""
+        n = self.n_cells - first if n is None else n
+        off = np.zeros(int(n) + 1, np.uint64)
+        self._call("matrix", int(first), int(n), off.ctypes.data, None, None)
+        z = int(off[-1])
+        feat, val = np.zeros(max(z, 1), np.uint32), np.zeros(max(z, 1), np.float64)
+        self._call("matrix", int(first), int(n), off.ctypes.data, feat.ctypes.data, val.ctypes.data)
+        return off, feat[:z], val[:z]
+
+    def cell_stats(self, first=0, n=None):
+        """-> dict of per-cell arrays: names, unique, multi (uint64), features, iterations (uint32)"""
+        n = self.n_cells - first if n is None else n
+        k = max(int(n), 1)
+        names, uniq, multi = np.zeros(k, np.uint64), np.zeros(k, np.uint64), np.zeros(k, np.uint64)
+        feat, iters = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        self._call("cell_stats", int(first), int(n), names.ctypes.data, uniq.ctypes.data, multi.ctypes.data, feat.ctypes.data, iters.ctypes.data)
+        return {"names": names[:n], "unique": uniq[:n], "multi": multi[:n], "features": feat[:n], "iterations": iters[:n]}
 
     def stats(self):
         out = np.zeros(16, np.uint64)

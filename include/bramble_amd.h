@@ -1125,8 +1125,8 @@ void br_assign_free(br_assign *);
  *                  contents) changes any result, and two runs give the same bits
  *
  *   br_dedup_set_param  before the first add: "method", "umi_source", "umi_sep", "umi_tag", "keep_records" 0 / 1 (default 0), "mark"
- *                       0 / 1 (default 0), "max_bytes" (a cap on the arena's bytes, 0: none), "hist_max" 1 .. 65535; before finish:
- *                       "hash_bits" 1 .. 64
+ *                       0 / 1 (default 0), "max_bytes" (a cap on the arena's bytes, 0: none), "hist_max" 1 .. 65535, "cell_source" and
+ *                       "cell_tag" (per cell: behind this block); before finish: "hash_bits" 1 .. 64
  *   br_dedup_add        shapes and rules of br_assign_add, with the rows' cigar and pool: offsets that descend, recs->n_rows !=
  *                       rows->n_rows, a record of less than 36 bytes, a name of 2^30 rows or more: BR_ERR_INVALID_ARG and nothing
  *                       added.  recs is required.  BR_ERR_CAPACITY for memory that is not there, the cap, 2^32 names or rows.  With
@@ -1173,6 +1173,79 @@ void br_dedup_free(br_dedup *);
  * (0xffffffff), n_unassigned and the bootstrap's resampling pool.  The fragment-length histogram of "eff_len" was counted at the adds
  * and stays as it is.  *n_dropped: the names with a non-zero flag. */
 int br_quant_drop_names(br_quant *, const uint8_t *flags, int64_t n, int on_device, int64_t *n_dropped);
+
+/* br_dedup per cell.  "cell_source" (before the first add) 0: none, the default, and everything above as it stands; 1: name; 2: tag,
+ * "cell_tag" (b0 | b1 << 8, default CB).  The barcode of a name is read as br_cells reads it (below), with "umi_sep" as the separator;
+ * a name without one has the empty barcode.  A position group is then the names with at least one row that have equal signatures AND
+ * equal barcodes (length first, then bytes): umi_tools' --per-cell.  The signature groups are made as above; inside them the names
+ * are sorted by (length, barcode) with stable radix passes and cut where the barcode changes, by comparing the barcodes themselves, so
+ * "hash_bits" has no say in it.  Nodes, edges, rep, dup, group_first, the histogram and the invariance clause read as above with that
+ * group.  Device memory: 33 bytes a name more (barcode 32, length 1).
+ *
+ * br_cells: a run accumulator like br_dedup.  It is fed the names of every projection call and the records the call encoded, keeps the
+ * cell barcode of every READ NAME, and at finish turns the quantifier's per-name classes into a sparse cell x feature matrix.
+ *   name i         as br_dedup's; records and rows correspond one to one
+ *   barcode(i)     from the name's first record, at add time; at most 32 bytes, compared as bytes: length first, then content.
+ *                  "barcode_source" 0 (name, umi_tools extract's READ_CB_UMI): with p2 the last byte of read_name (without its NUL)
+ *                  equal to "barcode_sep" (default '_') and p1 the last such byte before p2, the bytes between p1 and p2; fewer
+ *                  than two separators: none.  "barcode_source" 1 (tag): the value of the first aux field whose tag bytes equal
+ *                  "barcode_tag" (default CB) and whose type is Z, the aux walk and its bad_aux rule being br_dedup's.  A length
+ *                  of 0 or above 32: NO barcode; the name counts in n_no_barcode (as the n_bad_aux ones do), a length above 32 in
+ *                  n_barcode_too_long as well.  A name without rows has no record: length 0, counted nowhere
+ *   finish         takes a br_quant on the same device on which br_quant_finish has run with "keep_names" (the EM is not needed)
+ *                  and whose name count equals the object's, else BR_ERR_INVALID_ARG and nothing changes; tx_feature[t] <
+ *                  n_features for each of the quantifier's transcripts, else the same
+ *   counted name   a name with a barcode and name_cls != 0xffffffff (so a name br_quant_drop_names dropped does not count: with
+ *                  br_dedup in front the unit is the molecule, without it the read name)
+ *   cell k         the distinct barcodes of the counted names, numbered in ascending (length, bytes) order
+ *   entry e        of cell k: a distinct class of the cell's counted names, in ascending class index; n_e the number of such names,
+ *                  F_e the ascending distinct tx_feature[t] over the class's labels, m_e = |F_e|
+ *   slot s         of cell k: the ascending distinct features over the cell's entries
+ *   "mode" 0       unique: value[k, f] = the sum of n_e over the entries with F_e = {f}, exact integers; the slots that end at 0
+ *                  are not part of the matrix.  Per cell, in every mode: names = the sum of n_e, unique = that over m_e == 1,
+ *                  multi = that over the others
+ *   "mode" 2       em: theta_s = 1; one iteration: d_e = the sum of theta_f over F_e ascending, q_e = n_e / d_e (0 when d_e == 0),
+ *                  theta'_s = theta_s * the sum of q_e over the entries containing s in ascending entry order; rel = the maximum of
+ *                  |theta' - theta| / theta' over theta' > 1e-8.  Checked after every iteration, per cell: the cell stops at rel <
+ *                  tolerance (default 1e-2) or at "max_iters" (default 10000), which bounds the loop whatever the numbers are.
+ *                  value = theta, n_iters per cell.  Every slot is part of the matrix
+ *   "mode" 1       uniform: exactly one such iteration, value = the sum of n_e / m_e; n_iters = 1
+ *   sums           one after the other in the stated order, except a list of more than 64 items: lane l of a wave takes the items
+ *                  l, l + 64, ... in ascending order and the 64 partial sums meet in wave_sum's fixed tree.  No floating-point
+ *                  atomic.  Two runs with the same parameters give the same bits; neither the cut into adds, nor host or device
+ *                  tables, nor "hash_bits" (accepted for symmetry: the barcodes are sorted by their bytes, nothing is hashed), nor
+ *                  "lds_bytes" changes any
+ *   routes         the whole iteration loop of a cell runs inside one kernel launch for all cells.  A cell of at most 64 slots and
+ *                  at most 64 pairs (entry x feature) is one wave's work, four to a block; a larger one gets a block of 256 threads
+ *                  with theta, theta' and q in LDS when 8 (2 slots + entries) + 64 <= "lds_bytes" (0 .. 65536, default 65536), else
+ *                  the same code on scratch in HBM
+ *
+ *   br_cells_set_param / br_cells_set_tolerance   before the first add
+ *   br_cells_add / br_cells_add_last   shapes and refusal rules of br_dedup_add; rows->a, cigar and pool are not read
+ *   br_cells_barcodes        after any add: n x 32 bytes zero padded, and the lengths; either may be NULL
+ *   br_cells_finish          *n_cells, *n_entries (the matrix's).  A failure other than BR_ERR_INVALID_ARG leaves the object dead
+ *   br_cells_cell_barcodes / br_cells_name_cells (0xffffffff: in no cell) / br_cells_cell_stats   after finish; pointers may be NULL
+ *   br_cells_matrix          CSR by cell over the cells [first_cell, first_cell + n): cell_off (n + 1, from 0), features ascending
+ *                            (feature and value hold cell_off[n] items; size them by a first call with both NULL)
+ *   br_cells_stats           names, counted names, n_no_barcode, n_barcode_too_long, n_bad_aux, cells, entries, pairs, slots, matrix
+ *                            entries, cells of the wave / block / HBM route, microseconds in add, in finish and in the value kernel
+ * Device memory: 33 bytes a name until finish; finish and what it keeps: cells.cpp. */
+typedef struct br_cells br_cells;
+int br_cells_new(int device, br_cells **out);
+int br_cells_set_param(br_cells *, const char *name, int64_t value);
+int br_cells_set_tolerance(br_cells *, double tolerance);
+int br_cells_add(br_cells *, const br_device_bam *recs, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups,
+                 int on_device, void *stream);
+int br_cells_add_last(br_cells *, br_ctx *);
+int br_cells_barcodes(br_cells *, int64_t first, int64_t n, uint8_t *cb /* n x 32, zero padded */, uint8_t *len);
+int br_cells_finish(br_cells *, br_quant *, const uint32_t *tx_feature, int64_t n_features, int64_t *n_cells, int64_t *n_entries);
+int br_cells_cell_barcodes(br_cells *, int64_t first, int64_t n, uint8_t *cb, uint8_t *len);
+int br_cells_name_cells(br_cells *, int64_t first, int64_t n, uint32_t *cell);
+int br_cells_matrix(br_cells *, int64_t first_cell, int64_t n, uint64_t *cell_off, uint32_t *feature, double *value);
+int br_cells_cell_stats(br_cells *, int64_t first, int64_t n, uint64_t *names, uint64_t *unique, uint64_t *multi, uint32_t *n_features,
+                        uint32_t *n_iters);
+int br_cells_stats(const br_cells *, uint64_t out[16]);
+void br_cells_free(br_cells *);
 
 /* ---- SAM text out -------------------------------------------------------------------------- */
 
