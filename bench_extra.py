@@ -43,6 +43,11 @@
                                          tolerance.  add / finish seconds and the value kernel's seconds: all cells at the default
                                          "lds_bytes" (one launch, wave and block routes), the same with "lds_bytes" 0 (the block cells on
                                          scratch in HBM), the large cells alone (block route), the tail alone (wave route)
+  python bench_extra.py whitelist [--reads N]  br_whitelist of 6 794 880 random 16-mers (the size of the 10x v3 list) and N read names
+                                         (default 4 M, one row each) over 100 000 of them, 1 % with one substituted base, fed to
+                                         br_quant + br_cells from HBM: build seconds and the longest probe chain, then per step
+                                         br_cells_finish (mode unique) without a whitelist and with it under 1mm and 1mm-multi -- the
+                                         resolve's seconds, the statuses' names and, beside them, the finish's seconds without the resolve
   python bench_extra.py small            small calls: us per device-resident step at 1 .. 52 000 pairs (without the per-kernel
                                          events bench.py keeps on), the path without host round trips against the ordinary one,
                                          and br_project_group / br_project_groups host to host from plain C (profiles/group_latency.c)
@@ -60,7 +65,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "quant_boot", "quant_genes", "coverage", "cells"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "quant_boot", "quant_genes", "coverage", "cells", "whitelist"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
@@ -71,6 +76,72 @@ def main():
     import torch
     from bramble_amd import device as brdev
     from bramble_amd import lib, synth
+    if args.config == "whitelist":
+        n_wl, n_names, n_cells, n_tx = 6_794_880, args.reads or 4_000_000, 100_000, 20_000
+        rng = np.random.default_rng(7)
+        acgt = np.frombuffer(b"ACGT", np.uint8)
+        wl = np.zeros((n_wl, 32), np.uint8)
+        wl[:, :16] = rng.choice(acgt, size=(n_wl, 16))
+        ln = np.full(n_wl, 16, np.uint8)
+        cells = rng.choice(n_wl, n_cells, replace=False)
+        bc = wl[cells[rng.integers(0, n_cells, n_names)], :16].copy()
+        bad = np.flatnonzero(rng.random(n_names) < 0.01)
+        pos = rng.integers(0, 16, len(bad))
+        bc[bad, pos] = acgt[(np.searchsorted(acgt, bc[bad, pos]) + rng.integers(1, 4, len(bad))) % 4]   # another base
+        # one row a name; [block_size][32 fixed bytes][r_<16>_<UMI> NUL]
+        l_name = 2 + 16 + 1 + 8 + 1
+        rec = np.zeros((n_names, 36 + l_name), np.uint8)
+        rec[:, 0] = 32 + l_name
+        rec[:, 12] = l_name
+        rec[:, 36], rec[:, 37], rec[:, 54] = ord("r"), ord("_"), ord("_")
+        rec[:, 38:54] = bc
+        rec[:, 55:63] = np.frombuffer(b"ACGTACGT", np.uint8)
+        a = np.zeros((n_names, 4), np.uint32)
+        a[:, 0] = rng.integers(0, n_tx, n_names)
+        row_off = np.arange(n_names + 1, dtype=np.uint64)
+        group_off = np.arange(n_names + 1, dtype=np.uint32)
+        rec_off = np.arange(n_names + 1, dtype=np.uint64) * np.uint64(rec.shape[1])
+        t = [torch.from_numpy(x).cuda() for x in (a.view(np.int32), row_off.view(np.int64), group_off.view(np.int32), rec.reshape(-1), rec_off.view(np.int64))]
+        recs = lib.BrDeviceBam(t[3].data_ptr(), t[3].numel(), t[4].data_ptr(), t[4].numel() - 1)
+        tx_feature = np.arange(n_tx, dtype=np.uint32) // 2
+        torch.cuda.synchronize()
+        out = {"config": "whitelist", "workload": "%d random 16-mers, %d read names over %d of them, %d with one substituted base" % (n_wl, n_names, n_cells, len(bad)),
+               "builds": [], "runs": []}
+        w = None
+        for step in range(args.warmup + args.steps):
+            if w is not None:
+                w.close()
+            w = lib.Whitelist((wl, ln))
+            st = w.stats()
+            if step >= args.warmup:
+                out["builds"].append({"build_s": round(st["build_us"] * 1e-6, 3), "distinct": st["distinct"], "slots": st["slots"], "longest_chain": st["longest_chain"],
+                                      "held_bytes": st["held_bytes"], "peak_bytes": st["peak_bytes"]})
+        for step in range(args.warmup + args.steps):
+            for correct in (None, "1mm", "1mm-multi"):
+                q = lib.Quant(n_tx)
+                q.set_param("keep_names", 1)
+                c = lib.Cells(mode=0)
+                if correct:
+                    c.set_whitelist(w, correct)
+                for g0 in range(0, n_names, 1_000_000):
+                    g1 = min(n_names, g0 + 1_000_000)
+                    q.add_device(t[0], t[1], t[2], g0, g1)
+                    c.add_device(t[1], t[2], recs, g0, g1)
+                q.finish()
+                n_c, _ = c.finish(q, tx_feature, n_tx // 2)
+                st = c.stats()
+                run = {"correct": correct, "cells": n_c, "finish_s": round(st["finish_us"] * 1e-6, 4)}
+                if correct:
+                    ws = c.whitelist_stats()
+                    run.update({"resolve_s": round(ws["resolve_us"] * 1e-6, 4), "finish_without_resolve_s": round((st["finish_us"] - ws["resolve_us"]) * 1e-6, 4)})
+                    run.update({k: ws[k] for k in ("exact", "corrected", "no_match", "ambiguous", "distinct_observed")})
+                c.close()
+                q.close()
+                if step >= args.warmup:
+                    out["runs"].append(run)
+        w.close()
+        print(json.dumps(out))
+        return
     if args.config == "cells":
         k_cells = args.reads or 10_000
         n_tx, per_cell, own = 20_000, 300, 200

@@ -3,7 +3,9 @@
 //
 //   add      per name the cell barcode of its first record (barcode_inl.h); the offsets are checked here, so an add that is refused
 //            has added nothing.  Nothing else of a record is kept
-//   finish   reads the quantifier's classes (quant_view.h: name_cls and the label tables; no EM is asked for).  The names that count
+//   finish   with a br_whitelist set (br_cells_set_whitelist): first the barcodes resolved in place against it (whitelist.h: status
+//            per name, a name without a match has no barcode any more; its tables are gone before the rest begins).  Then it
+//            reads the quantifier's classes (quant_view.h: name_cls and the label tables; no EM is asked for).  The names that count
 //            -- a barcode and a class -- sorted by (length, barcode) into cells; (cell << 32 | class) sorted and run-length encoded
 //            into entries; the classes' feature lists by the quantifier's (class, gene) arena routine; entries x features expanded
 //            into (cell << 32 | feature) pairs, whose stable sort gives every pair its slot and, as it stands, the per-slot lists of
@@ -24,11 +26,13 @@
 
 #include "accum.h"
 #include "barcode_inl.h"
+#include "barcode_sort.h"
 #include "cells_kernels.h"
 #include "ctx.h"
 #include "quant_kernels.h"
 #include "quant_view.h"
 #include "scan_kernels.h"
+#include "whitelist.h"
 
 using namespace br;
 
@@ -42,7 +46,10 @@ struct br_cells : Accum {
   uint64_t n_no_barcode = 0, n_too_long = 0, n_bad_aux = 0;
   uint64_t n_counted = 0, n_cells = 0, n_entries = 0, n_pairs = 0, n_slots = 0, n_matrix = 0, n_wave = 0, n_block = 0, n_hbm = 0;
   double add_s = 0, finish_s = 0, em_s = 0;
-  ColBuf small, cb, cblen;
+  const br_whitelist *wl = nullptr;   // set: finish resolves the barcodes against it first ("correct": wl_correct)
+  int wl_correct = 1;
+  WlResolved wl_res;
+  ColBuf small, cb, cblen, status;
   ColBuf name_cell, cell_cb, cell_len, m_off, m_feat, m_val, c_names, c_unique, c_multi, c_feat, c_iters;
 };
 
@@ -74,6 +81,12 @@ extern "C" int br_cells_set_param(br_cells *c, const char *name, int64_t value) 
   if (!strcmp(name, "hash_bits")) { if (value < 1 || value > 64) return BR_ERR_INVALID_ARG; c->hash_bits = (int)value; return BR_OK; }
   if (!strcmp(name, "lds_bytes")) { if (value < 0 || value > (int64_t)CL_LDS_MAX) return BR_ERR_INVALID_ARG; c->lds_bytes = (uint32_t)value; return BR_OK; }
   return BR_ERR_INVALID_ARG;
+}
+
+extern "C" int br_cells_set_whitelist(br_cells *c, const br_whitelist *wl, int correct) {
+  if (!c || !wl || c->dead || c->finished || correct < 0 || correct > 2 || wl_device(wl) != c->device) return BR_ERR_INVALID_ARG;
+  c->wl = wl; c->wl_correct = correct;
+  return BR_OK;
 }
 
 extern "C" int br_cells_set_tolerance(br_cells *c, double tolerance) {
@@ -184,32 +197,8 @@ extern "C" int br_cells_add_last(br_cells *c, br_ctx *ctx) {
   return br_cells_add(c, &recs, &ctx->last_rows, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
 }
 
-namespace {
-// key / index pairs of a radix sort: the sorted pairs are those of [0] when sort returns
-struct SortBufs {
-  ColBuf key[2], idx[2];
-  int make(Accum *c, size_t items) {
-    for (int k = 0; k < 2; k++) { RC(c->alloc(key[k], (items + 1) * 8)); RC(c->alloc(idx[k], (items + 1) * 4)); }
-    return BR_OK;
-  }
-};
-}  // namespace
-
-// the radix sort of (key[0], idx[0]) over the digits in which the keys differ
-static int cells_sort(br_cells *c, SortBufs &s, int64_t n, ColBuf &tmp) {
-  if (n <= 0) return BR_OK;
-  hipStream_t st = c->st;
-  uint64_t *small = c->small.as<uint64_t>();
-  RC(c->alloc(tmp, scan_tmp_bytes(n)));
-  launch_q_bits(st, s.key[0].as<uint64_t>(), n, tmp.as<uint64_t>(), small + CL_BITS);
-  uint64_t bits[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(bits, small + CL_BITS, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  int cur = 0;
-  RC(c->radix_sort(s.key, s.idx, n, bits, tmp, &cur));
-  if (cur) { std::swap(s.key[0], s.key[1]); std::swap(s.idx[0], s.idx[1]); }
-  return BR_OK;
-}
+// the radix sort of (key[0], idx[0]) over the digits in which the keys differ (barcode_sort.h)
+static int cells_sort(br_cells *c, SortBufs &s, int64_t n, ColBuf &tmp) { return sort_pairs(c, s, n, tmp, c->small.as<uint64_t>() + CL_BITS); }
 
 // flag (n items, then one more) scanned in place; -> its total
 static int cells_scan(br_cells *c, ColBuf &flag, int64_t n, ColBuf &tmp, uint64_t *total) {
@@ -248,10 +237,7 @@ static int cells_finish(br_cells *c, const QuantClassView &V, const uint32_t *tx
   // cells: by (length, bytes), least significant word first, every sort stable
   const uint64_t *cb = c->cb.as<uint64_t>();
   const uint8_t *cblen = c->cblen.as<uint8_t>();
-  for (int w = 3; w >= -1; w--) {
-    launch_cl_bkey(st, s.idx[0].as<uint32_t>(), cb, cblen, n, w < 0 ? 4 : w, s.key[0].as<uint64_t>());
-    RC(cells_sort(c, s, n, tmp));
-  }
+  RC(sort_by_barcode(c, s, cb, cblen, n, tmp, small + CL_BITS));
   uint64_t K = 0;
   RC(c->alloc(flag, ((size_t)M + 1) * 8));
   launch_cl_bheads(st, s.idx[0].as<uint32_t>(), cb, cblen, n, flag.as<uint64_t>());
@@ -376,7 +362,12 @@ extern "C" int br_cells_finish(br_cells *c, br_quant *quant, const uint32_t *tx_
   for (int64_t t = 0; t < V.n_tx; t++) if ((int64_t)tx_feature[t] >= n_features) return BR_ERR_INVALID_ARG;
   const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
-  const int rc = cells_finish(c, V, tx_feature);
+  int rc = BR_OK;
+  if (c->wl) {   // the observed barcodes become whitelist entries, or nothing
+    rc = c->alloc(c->status, (size_t)c->n + 1);
+    if (!rc) rc = wl_resolve(c, c->wl, c->wl_correct, c->cb.as<uint64_t>(), c->cblen.as<uint8_t>(), (int64_t)c->n, c->status.as<uint8_t>(), nullptr, &c->wl_res);
+  }
+  if (!rc) rc = cells_finish(c, V, tx_feature);
   if (rc) { c->dead = true; return rc; }
   c->finished = true;
   c->finish_s = timer.seconds();
@@ -420,6 +411,23 @@ extern "C" int br_cells_name_cells(br_cells *c, int64_t first, int64_t n, uint32
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipMemcpyAsync(cell, c->name_cell.as<uint32_t>() + first, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
   HIPCHK(hipStreamSynchronize(c->st));
+  return BR_OK;
+}
+
+extern "C" int br_cells_name_status(br_cells *c, int64_t first, int64_t n, uint8_t *status) {
+  if (!c || c->dead || !c->finished || !c->wl || !in_range(c->n, first, n)) return BR_ERR_INVALID_ARG;
+  if (n == 0 || !status) return BR_OK;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipMemcpyAsync(status, c->status.as<uint8_t>() + first, (size_t)n, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return BR_OK;
+}
+
+extern "C" int br_cells_whitelist_stats(const br_cells *c, uint64_t out[8]) {
+  if (!c || !out || !c->wl) return BR_ERR_INVALID_ARG;
+  const WlResolved &r = c->wl_res;
+  const uint64_t v[8] = {r.status[0], r.status[1], r.status[2], r.status[3], r.status[4], r.distinct, (uint64_t)(r.seconds * 1e6), (uint64_t)c->wl_correct};
+  memcpy(out, v, sizeof(v));
   return BR_OK;
 }
 

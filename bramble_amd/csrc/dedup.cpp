@@ -23,6 +23,8 @@
 // the heads) + the sorts' histograms and scratch, then 105 D (UMI 32, length 1, count, first name, group and place 4 each, two
 // labels 8, the edge offsets 8, cursor 4, molecule size 4, the nodes' begins 8, two key / index pairs 24) + 24 a group + 4 E.  next holds two piece buffers of the largest piece's bytes
 // + 16 and 8 bytes a record of theirs.  128 bytes of counters.
+// With a br_whitelist set (br_dedup_set_whitelist, "cell_source" != 0) finish first resolves the cell barcodes in place against it
+// (whitelist.h): 1 N of status and the resolve's own tables, all gone before the groups are made.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +37,7 @@
 #include "dedup_kernels.h"
 #include "quant_kernels.h"
 #include "scan_kernels.h"
+#include "whitelist.h"
 
 using namespace br;
 
@@ -48,6 +51,10 @@ struct br_dedup : Accum {
   uint64_t n_groups = 0, n_nodes = 0, n_edges = 0, sweeps = 0, max_nodes = 0, collisions = 0, n_mols = 0;
   uint64_t n_out = 0, cur = 0;
   double add_s = 0, finish_s = 0;
+  const br_whitelist *wl = nullptr;   // set: finish resolves the cell barcodes against it first ("correct": wl_correct)
+  int wl_correct = 1;
+  WlResolved wl_res;
+  ColBuf status;
   ColBuf small, umi, ulen, cb, cblen, noff, nk, hash, ent, arena, rec_at;
   ColBuf rep, gfirst, dup, hist, rdup, sel, out_off;
   ColBuf buf[2], prow[2];
@@ -439,7 +446,13 @@ extern "C" int br_dedup_finish(br_dedup *c, int64_t *n_names, int64_t *n_molecul
   if (!c || c->dead || c->finished) return BR_ERR_INVALID_ARG;
   const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
-  int rc = dedup_finish(c);
+  int rc = BR_OK;
+  if (c->wl) {   // the observed cell barcodes become whitelist entries, or the empty barcode
+    rc = c->alloc(c->status, (size_t)c->n + 1);
+    if (!rc) rc = wl_resolve(c, c->wl, c->wl_correct, c->cb.as<uint64_t>(), c->cblen.as<uint8_t>(), (int64_t)c->n, c->status.as<uint8_t>(), nullptr, &c->wl_res);
+    c->drop(c->status);
+  }
+  if (!rc) rc = dedup_finish(c);
   if (!rc) rc = dedup_records(c);
   if (rc) { c->dead = true; return rc; }
   c->drop(c->ent); c->drop(c->hash); c->drop(c->nk); c->drop(c->noff);   // the names are molecules now
@@ -448,6 +461,20 @@ extern "C" int br_dedup_finish(br_dedup *c, int64_t *n_names, int64_t *n_molecul
   if (n_names) *n_names = (int64_t)c->n;
   if (n_molecules) *n_molecules = (int64_t)c->n_mols;
   if (n_duplicates) *n_duplicates = (int64_t)(c->n_with_rows - c->n_mols);
+  return BR_OK;
+}
+
+extern "C" int br_dedup_set_whitelist(br_dedup *c, const br_whitelist *wl, int correct) {
+  if (!c || !wl || c->dead || c->finished || !c->cell_source || correct < 0 || correct > 2 || wl_device(wl) != c->device) return BR_ERR_INVALID_ARG;
+  c->wl = wl; c->wl_correct = correct;
+  return BR_OK;
+}
+
+extern "C" int br_dedup_whitelist_stats(const br_dedup *c, uint64_t out[8]) {
+  if (!c || !out || !c->wl) return BR_ERR_INVALID_ARG;
+  const WlResolved &r = c->wl_res;
+  const uint64_t v[8] = {r.status[0], r.status[1], r.status[2], r.status[3], r.status[4], r.distinct, (uint64_t)(r.seconds * 1e6), (uint64_t)c->wl_correct};
+  memcpy(out, v, sizeof(v));
   return BR_OK;
 }
 

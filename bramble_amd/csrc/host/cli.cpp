@@ -57,7 +57,7 @@ void usage(FILE *f) {
           "               [--dedup unique|directional [--dedup-umi name|tag] [--dedup-umi-sep C] [--dedup-umi-tag XY]\n"
           "                [--dedup-stats <sizes.tsv>] [--dedup-bam <dedup.bam> [--dedup-bam-mode remove|mark]]]\n"
           "               [--cells <prefix> [--cells-barcode name|tag] [--cells-barcode-tag XY] [--cells-features gene|transcript]\n"
-          "                [--cells-multi unique|uniform|em]]\n\n"
+          "                [--cells-multi unique|uniform|em] [--cells-whitelist <file> [--cells-correct exact|1mm|1mm-multi]]]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -149,10 +149,19 @@ void usage(FILE *f) {
           "(--cells-multi unique, the default: integer counts), for each an equal share (uniform) or the shares of an EM run per cell on\n"
           "the GPU (em: STARsolo's and alevin's estimator).  PREFIXmatrix.mtx (Matrix Market, features x cells, the 10x layout),\n"
           "PREFIXbarcodes.tsv, PREFIXfeatures.tsv and PREFIXcells.tsv (Barcode Names Unique Multi Features Iterations); the directory of\n"
-          "PREFIX must exist.  The matrix is the raw one: no whitelist, no barcode correction, no cell filtering.  With --dedup the\n"
+          "PREFIX must exist.  The matrix is the raw one unless --cells-whitelist is given; there is no cell filtering.  With --dedup the\n"
           "duplicates are found per cell (umi_tools' --per-cell) and the matrix counts molecules; quant.tsv then reflects the per-cell\n"
           "molecules as well.  One more line in front of the final report: [bramble] cells: C cells, M of N read names counted (B\n"
-          "without barcode; Z matrix entries; features gene|transcript; multi unique|uniform|em; add X.XXs, finish Y.YYs)\n");
+          "without barcode; Z matrix entries; features gene|transcript; multi unique|uniform|em; add X.XXs, finish Y.YYs)\n"
+          "--cells-whitelist FILE: the allowed cell barcodes, plain text, one a line (the first whitespace-delimited field, 32 bytes at\n"
+          "most; empty lines and lines starting with # are skipped; not compressed).  Every observed barcode is mapped onto the list on\n"
+          "the GPU before the cells and, with --dedup, the per-cell duplicate groups are made.  --cells-correct exact: only barcodes\n"
+          "on the list; 1mm (the default, STARsolo's 1MM): a barcode not on the list becomes the one entry that differs from it in one\n"
+          "base, and is dropped when there are several or none; 1mm-multi (1MM_multi): among several the one most read names carry\n"
+          "exactly, dropped on a tie.  A read name whose barcode is dropped is in no cell.  The barcodes printed are entries of the\n"
+          "list; PREFIXcells.tsv gains a last column Corrected.  One more line: [bramble] whitelist: W barcodes; B read names with a\n"
+          "barcode: X exact, C corrected, R without match, A ambiguous (D distinct observed; correct exact|1mm|1mm-multi; build\n"
+          "X.XXs, resolve Y.YYs)\n");
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -161,7 +170,7 @@ int parse_args(int argc, char **argv, Options &o) {
   memset(&o.cfg, 0, sizeof(o.cfg));
   o.cfg.junc_miss_discount = 1.0;
   bool codec = false, host_codec = false;   // a BGZF codec option was given; one that asks for the host codec
-  bool coverage_weight_given = false, unprojected_scope_given = false, quant_bam_mode_given = false, dedup_switch_given = false, dedup_bam_mode_given = false, cells_switch_given = false;
+  bool coverage_weight_given = false, unprojected_scope_given = false, quant_bam_mode_given = false, dedup_switch_given = false, dedup_bam_mode_given = false, cells_switch_given = false, cells_correct_given = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "%s: missing value\n", argv[i]); return nullptr; } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -303,6 +312,14 @@ int parse_args(int argc, char **argv, Options &o) {
       else { fprintf(stderr, "--cells-features: unknown features %s (gene or transcript)\n", v); return -1; }
       cells_switch_given = true;
     }
+    else if (a == "--cells-whitelist") { const char *v = value(); if (!v) return -1; o.cells_whitelist = v; }
+    else if (a == "--cells-correct") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "exact") o.cells_correct = 0; else if (w == "1mm") o.cells_correct = 1; else if (w == "1mm-multi") o.cells_correct = 2;
+      else { fprintf(stderr, "--cells-correct: unknown mode %s (exact, 1mm or 1mm-multi)\n", v); return -1; }
+      cells_correct_given = true;
+    }
     else if (a == "--cells-multi") {
       const char *v = value(); if (!v) return -1;
       const std::string w = v;
@@ -353,6 +370,8 @@ int parse_args(int argc, char **argv, Options &o) {
   const bool cell_genes = !o.cells.empty() && o.cells_features == 0;   // (--cells takes its genes where --quant-genes does)
   if (o.quant_genes.empty() && (!o.quant_gene_classes.empty() || (!o.quant_gene_map.empty() && !cell_genes))) { fprintf(stderr, "--quant-gene-classes and --quant-gene-map need --quant-genes\n"); return -1; }
   if (cells_switch_given && o.cells.empty()) { fprintf(stderr, "--cells-barcode, --cells-barcode-tag, --cells-features and --cells-multi need --cells\n"); return -1; }
+  if (!o.cells_whitelist.empty() && o.cells.empty()) { fprintf(stderr, "--cells-whitelist needs --cells\n"); return -1; }
+  if (cells_correct_given && o.cells_whitelist.empty()) { fprintf(stderr, "--cells-correct needs --cells-whitelist\n"); return -1; }
   if (!o.cells.empty() && o.quant.empty()) { fprintf(stderr, "--cells needs --quant: the matrix is made from the quantifier's classes\n"); return -1; }
   if (!o.quant_boot_out.empty() && !o.quant_bootstraps) { fprintf(stderr, "--quant-boot-out needs --quant-bootstraps: without it there are no replicates\n"); return -1; }
   if (!o.quant_fld.empty() && !o.quant_eff_length) { fprintf(stderr, "--quant-fld needs --quant-eff-length: without it no fragment lengths are counted\n"); return -1; }

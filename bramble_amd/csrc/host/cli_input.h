@@ -69,6 +69,8 @@ struct Options {
   int cells_barcode_tag = 'C' | 'B' << 8;   // --cells-barcode-tag XY: "barcode_tag" / "cell_tag"
   int cells_features = 0;        // --cells-features gene|transcript (0, 1)
   int cells_multi = 0;           // --cells-multi unique|uniform|em: br_cells' "mode" (0, 1, 2)
+  std::string cells_whitelist;   // --cells-whitelist FILE: the allowed cell barcodes (br_whitelist), one a line
+  int cells_correct = 1;         // --cells-correct exact|1mm|1mm-multi: "correct" (0, 1, 2)
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };
 inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }

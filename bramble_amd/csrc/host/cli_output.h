@@ -37,6 +37,8 @@ class Consumer {
   // --dedup only: one byte per read name of the run in HBM, non-zero for a duplicate (br_dedup_flags: BR_ERR_INVALID_ARG before its
   // finish()); the --quant consumer drops those names in front of its own finish().  Every other consumer: BR_ERR_UNSUPPORTED
   virtual int duplicate_flags(const uint8_t **, int64_t *) { return BR_ERR_UNSUPPORTED; }
+  // --cells with --cells-whitelist only: its whitelist and "correct", which the --dedup consumer sets on its br_dedup too
+  virtual const br_whitelist *whitelist(int *) { return nullptr; }
   // once every consumer is open: one that needs another finds it among them; false: it is not there
   virtual bool meet(const std::vector<std::unique_ptr<Consumer>> &) { return true; }
   const char *const name, *const failure;

@@ -3,7 +3,10 @@
 // Consumer::quantifier: the quantifier's classes per name (with --dedup: without the names that consumer found to be duplicates, per
 // cell) become the sparse cell x feature matrix on the device, the features being the genes env.tx numbers or the @SQ transcripts.
 // Four files through SideFiles: PREFIXmatrix.mtx, PREFIXbarcodes.tsv, PREFIXfeatures.tsv, PREFIXcells.tsv.
+// --cells-whitelist FILE: the list is read (whitelist_file.h) and the run's one br_whitelist built here, in front of the run; the
+// br_cells gets it, and the --dedup consumer takes it from here (Consumer::whitelist) for its br_dedup.
 #include "cli_output.h"
+#include "whitelist_file.h"
 
 namespace brcli {
 namespace {
@@ -16,6 +19,7 @@ class CellsOut : public Consumer {
   ~CellsOut() override {
     if (probed) remove(matrix.tmp.c_str());   // (a set-up error elsewhere: no settle came)
     if (c) br_cells_free(c);
+    if (wl) br_whitelist_free(wl);
   }
   // PREFIX is tried here, in front of the run: a directory that is not there fails before anything is projected
   bool open(std::string &err) {
@@ -24,7 +28,11 @@ class CellsOut : public Consumer {
     if (!f) { err = "--cells: could not write " + matrix.tmp + " (the directory of the prefix must exist)"; return false; }
     fclose(f);
     probed = true;
+    std::vector<uint8_t> wl_cb, wl_len;
+    if (!o.cells_whitelist.empty() && !read_whitelist_file(o.cells_whitelist, wl_cb, wl_len, err)) return false;
     int rc = br_cells_new(env.device, &c);
+    if (!rc && !wl_len.empty()) rc = br_whitelist_new(env.device, wl_cb.data(), wl_len.data(), (int64_t)wl_len.size(), 0, &wl);
+    if (!rc && wl) rc = br_cells_set_whitelist(c, wl, o.cells_correct);
     if (!rc) rc = br_cells_set_param(c, "barcode_source", o.cells_barcode);
     if (!rc) rc = br_cells_set_param(c, "barcode_sep", o.dedup_umi_sep);
     if (!rc) rc = br_cells_set_param(c, "barcode_tag", o.cells_barcode_tag);
@@ -33,6 +41,7 @@ class CellsOut : public Consumer {
     return true;
   }
   int add(br_ctx *ctx) override { return br_cells_add_last(c, ctx); }
+  const br_whitelist *whitelist(int *correct) override { *correct = env.o.cells_correct; return wl; }
   bool meet(const std::vector<std::unique_ptr<Consumer>> &all) override {
     for (auto &other : all) if (other->quantifier()) quant = other.get();
     return quant != nullptr;
@@ -52,7 +61,17 @@ class CellsOut : public Consumer {
       rc = br_cells_cell_barcodes(c, 0, n_cells, cb.data(), len.data());
       if (!rc) rc = br_cells_cell_stats(c, 0, n_cells, names.data(), unique.data(), multi.data(), n_feat.data(), iters.data());
       if (!rc) rc = br_cells_matrix(c, 0, n_cells, cell_off.data(), feature.data(), value.data());
+      if (!rc && wl) {   // Corrected: the counted names of the cell whose status is 2
+        const size_t n = (size_t)st_names();
+        std::vector<uint8_t> status(n + 1);
+        std::vector<uint32_t> cell(n + 1);
+        rc = br_cells_name_status(c, 0, (int64_t)n, status.data());
+        if (!rc) rc = br_cells_name_cells(c, 0, (int64_t)n, cell.data());
+        corrected.assign(k + 1, 0);
+        if (!rc) for (size_t i = 0; i < n; i++) if (status[i] == 2 && cell[i] < k) corrected[cell[i]]++;
+      }
     }
+    if (wl) { (void)br_cells_whitelist_stats(c, wst); (void)br_whitelist_stats(wl, lst); }
     (void)br_cells_stats(c, st);
     return rc;
   }
@@ -64,18 +83,28 @@ class CellsOut : public Consumer {
     if (!barcodes.close()) return false;
     if (FILE *f = features.open()) write_cells_features(f, env.tx, env.o.cells_features == 0);
     if (!features.close()) return false;
-    if (FILE *f = table.open()) write_cells_table(f, cb, len, names, unique, multi, n_feat, iters, true);
+    if (FILE *f = table.open()) write_cells_table(f, cb, len, names, unique, multi, n_feat, iters, true, wl ? &corrected : nullptr);
     return table.close();
   }
   bool settle(bool failed) override { probed = false; return settle_all({&matrix, &barcodes, &features, &table}, failed); }
   void report() const override {
     static const char *const multi_name[] = {"unique", "uniform", "em"};
+    static const char *const correct_name[] = {"exact", "1mm", "1mm-multi"};
+    if (wl)
+      printf("[bramble] whitelist: %llu barcodes; %llu read names with a barcode: %llu exact, %llu corrected, %llu without match, %llu ambiguous (%llu distinct observed; correct %s; build %.2fs, resolve %.2fs)\n",
+             (unsigned long long)lst[0], (unsigned long long)(wst[1] + wst[2] + wst[3] + wst[4]), (unsigned long long)wst[1], (unsigned long long)wst[2],
+             (unsigned long long)wst[3], (unsigned long long)wst[4], (unsigned long long)wst[5], correct_name[env.o.cells_correct], (double)lst[4] * 1e-6,
+             (double)wst[6] * 1e-6);
     printf("[bramble] cells: %llu cells, %llu of %llu read names counted (%llu without barcode; %llu matrix entries; features %s; multi %s; add %.2fs, finish %.2fs)\n",
            (unsigned long long)st[5], (unsigned long long)st[1], (unsigned long long)st[0], (unsigned long long)st[2], (unsigned long long)st[9],
            env.o.cells_features == 0 ? "gene" : "transcript", multi_name[env.o.cells_multi], (double)st[13] * 1e-6, (double)st[14] * 1e-6);
   }
  private:
+  uint64_t st_names() const { uint64_t v[16] = {}; (void)br_cells_stats(c, v); return v[0]; }
   br_cells *c = nullptr;
+  br_whitelist *wl = nullptr;   // --cells-whitelist: the run's one
+  uint64_t wst[8] = {}, lst[8] = {};
+  std::vector<uint64_t> corrected;
   Consumer *quant = nullptr;   // the --quant consumer, which outlives neither of the two
   SideFile matrix, barcodes, features, table;
   bool probed = false;

@@ -38,6 +38,14 @@ class DedupOut : public Consumer {
     if (rc) { err = std::string(name) + " on device " + std::to_string(env.device) + ": " + br_strerror(rc); return false; }
     return true;
   }
+  // --cells-whitelist: the per-cell groups are made from the barcodes the cells consumer's whitelist resolves
+  bool meet(const std::vector<std::unique_ptr<Consumer>> &all) override {
+    for (auto &other : all) {
+      int correct = 0;
+      if (const br_whitelist *wl = other->whitelist(&correct)) if (br_dedup_set_whitelist(d, wl, correct)) return false;
+    }
+    return true;
+  }
   int add(br_ctx *c) override { ctx = c; return br_dedup_add_last(d, c); }
   int finish() override {
     int rc = br_dedup_finish(d, &n_names, &n_molecules, &n_duplicates);

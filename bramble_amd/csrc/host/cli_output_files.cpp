@@ -72,11 +72,12 @@ void write_cells_features(FILE *f, const TxTable &tx, bool genes) {
 // table: the whole line; else the barcode alone (barcodes.tsv)
 void write_cells_table(FILE *f, const std::vector<uint8_t> &barcodes, const std::vector<uint8_t> &len, const std::vector<uint64_t> &names,
                        const std::vector<uint64_t> &unique, const std::vector<uint64_t> &multi, const std::vector<uint32_t> &features,
-                       const std::vector<uint32_t> &iters, bool table) {
-  if (table) fprintf(f, "Barcode\tNames\tUnique\tMulti\tFeatures\tIterations\n");
+                       const std::vector<uint32_t> &iters, bool table, const std::vector<uint64_t> *corrected) {
+  if (table) fprintf(f, corrected ? "Barcode\tNames\tUnique\tMulti\tFeatures\tIterations\tCorrected\n" : "Barcode\tNames\tUnique\tMulti\tFeatures\tIterations\n");
   for (size_t k = 0; k < len.size(); k++) {
     fwrite(barcodes.data() + 32 * k, 1, len[k], f);
     if (table) fprintf(f, "\t%llu\t%llu\t%llu\t%u\t%u", (unsigned long long)names[k], (unsigned long long)unique[k], (unsigned long long)multi[k], features[k], iters[k]);
+    if (table && corrected) fprintf(f, "\t%llu", (unsigned long long)(*corrected)[k]);
     fputc('\n', f);
   }
 }

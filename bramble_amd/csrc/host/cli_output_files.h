@@ -60,10 +60,10 @@ void write_cells_matrix(FILE *f, size_t n_features, const std::vector<uint64_t> 
 // id<TAB>name<TAB>Gene Expression, a line per feature (genes: tx.gene_name; else the @SQ transcripts)
 void write_cells_features(FILE *f, const TxTable &tx, bool genes);
 // table: Barcode Names Unique Multi Features Iterations, a line per cell under that header; else the barcode alone (barcodes.tsv).
-// barcodes: n x 32 bytes with their lengths
+// barcodes: n x 32 bytes with their lengths.  corrected (--cells-whitelist): a last column Corrected of the table
 void write_cells_table(FILE *f, const std::vector<uint8_t> &barcodes, const std::vector<uint8_t> &len, const std::vector<uint64_t> &names,
                        const std::vector<uint64_t> &unique, const std::vector<uint64_t> &multi, const std::vector<uint32_t> &features,
-                       const std::vector<uint32_t> &iters, bool table);
+                       const std::vector<uint32_t> &iters, bool table, const std::vector<uint64_t> *corrected = nullptr);
 // runs [first, first + n) into the four columns; not 0: an error, which ends the file there
 using RunPage = std::function<int(int64_t first, int64_t n, uint32_t *tid, uint32_t *start, uint32_t *end, uint32_t *depth)>;
 int write_bedgraph(FILE *f, const TxTable &tx, int64_t n_runs, int64_t page, const RunPage &fetch);   // the first error of fetch

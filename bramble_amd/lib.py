@@ -192,6 +192,8 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_dedup_hist", "br_dedup_flags", "br_dedup_next", "br_dedup_stats", "br_dedup_free", "br_quant_drop_names",
            "br_cells_new", "br_cells_set_param", "br_cells_set_tolerance", "br_cells_add", "br_cells_add_last", "br_cells_barcodes", "br_cells_finish",
            "br_cells_cell_barcodes", "br_cells_name_cells", "br_cells_matrix", "br_cells_cell_stats", "br_cells_stats", "br_cells_free",
+           "br_whitelist_new", "br_whitelist_barcodes", "br_whitelist_match", "br_whitelist_stats", "br_whitelist_free", "br_cells_set_whitelist",
+           "br_dedup_set_whitelist", "br_cells_name_status", "br_cells_whitelist_stats", "br_dedup_whitelist_stats",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_direct_tidwords", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -1806,7 +1808,8 @@ class Dedup(_Accumulator):
                 "umis": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
                 "result": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p], "hist": [C.c_void_p, C.c_void_p],
                 "flags": [C.c_void_p, _P(C.c_void_p), _P(C.c_int64)], "next": [C.c_void_p, C.c_uint64, _P(BrDeviceBam)],
-                "stats": [C.c_void_p, C.c_void_p], "free": [C.c_void_p]}
+                "stats": [C.c_void_p, C.c_void_p], "free": [C.c_void_p],
+                "set_whitelist": [C.c_void_p, C.c_void_p, C.c_int], "whitelist_stats": [C.c_void_p, C.c_void_p]}
 
     def __init__(self, device=0, **params):
         self.n_names = self.n_molecules = self.n_duplicates = 0
@@ -1861,6 +1864,17 @@ class Dedup(_Accumulator):
         """The rows, names and records of the last projection call on `ctx` (a Context), from where that call left them in HBM."""
         self._call("add_last", ctx.h)
 
+    def set_whitelist(self, whitelist, correct="1mm"):
+        """Before finish, with "cell_source": the cell barcodes are resolved against `whitelist` (a Whitelist on this device, kept
+        alive here) under `correct` (Whitelist.CORRECT) before the per-cell groups are made."""
+        self._call("set_whitelist", whitelist.h if whitelist is not None else None, Whitelist.correct_value(correct))
+        self._whitelist = whitelist
+
+    def whitelist_stats(self):
+        out = np.zeros(8, np.uint64)
+        self._call("whitelist_stats", out.ctypes.data)
+        return {k: int(v) for k, v in zip(Whitelist.RESOLVE_STATS, out)}
+
     def finish(self):
         """-> (names added, molecules, duplicates)"""
         n, m, d = C.c_int64(), C.c_int64(), C.c_int64()
@@ -1908,6 +1922,86 @@ class Dedup(_Accumulator):
         return {k: int(v) for k, v in zip(self.STATS, out)}
 
 
+class Whitelist(_Accumulator):
+    """br_whitelist on `device`: the allowed cell barcodes (a list of bytes / str, 1..32 bytes each), sorted, made distinct and
+    hashed into a table in HBM.  Read-only once made: Cells.set_whitelist and Dedup.set_whitelist share one.  match() resolves
+    barcodes given directly, one name each."""
+
+    CORRECT = {"exact": 0, "1mm": 1, "1mm-multi": 2}
+    STATUS = ("none", "exact", "corrected", "no_match", "ambiguous")
+    STATS = ("given", "distinct", "slots", "longest_chain", "build_us", "hash_bits", "held_bytes", "peak_bytes")
+    RESOLVE_STATS = ("no_barcode", "exact", "corrected", "no_match", "ambiguous", "distinct_observed", "resolve_us", "correct")
+    NONE = 0xffffffff
+
+    NAME = "whitelist"
+    ARGTYPES = {"new": [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _P(C.c_void_p)],
+                "barcodes": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
+                "match": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p],
+                "stats": [C.c_void_p, C.c_void_p], "free": [C.c_void_p]}
+
+    @classmethod
+    def correct_value(cls, correct):
+        return cls.CORRECT[correct] if isinstance(correct, str) else int(correct)
+
+    @staticmethod
+    def pack(barcodes):
+        """a list of bytes / str / None (no barcode) -> (uint8 [n, 32] zero padded, uint8 [n]); a length above 255 is stored as 255"""
+        n = len(barcodes)
+        cb, ln = np.zeros((max(n, 1), 32), np.uint8), np.zeros(max(n, 1), np.uint8)
+        for i, b in enumerate(barcodes):
+            b = b"" if b is None else b.encode() if isinstance(b, str) else bytes(b)
+            ln[i] = min(len(b), 255)
+            k = min(len(b), 32)
+            cb[i, :k] = np.frombuffer(b[:k], np.uint8)
+        return cb, ln
+
+    @classmethod
+    def new_raw(cls, device, cb, ln, n, hash_bits=64):
+        """br_whitelist_new as it is -> (the return code, the handle's value or None)"""
+        L = lib()
+        L.br_whitelist_new.argtypes = cls.ARGTYPES["new"]
+        L.br_whitelist_free.argtypes = cls.ARGTYPES["free"]
+        h = C.c_void_p()
+        rc = L.br_whitelist_new(int(device), cb.ctypes.data, ln.ctypes.data, int(n), int(hash_bits), C.byref(h))
+        if rc == 0:
+            L.br_whitelist_free(h)
+        return rc, h.value
+
+    def __init__(self, barcodes, device=0, hash_bits=64):
+        """barcodes: a list of bytes / str, or what pack() returns: (uint8 [n, 32] zero padded, uint8 [n])"""
+        packed = isinstance(barcodes, tuple) and len(barcodes) == 2 and isinstance(barcodes[0], np.ndarray)
+        cb, ln = barcodes if packed else self.pack(barcodes)
+        cb, ln = np.ascontiguousarray(cb, dtype=np.uint8), np.ascontiguousarray(ln, dtype=np.uint8)
+        self._open(device, cb.ctypes.data, ln.ctypes.data, len(ln) if packed else len(barcodes), int(hash_bits))
+        self.n = self.stats()["distinct"]
+
+    def barcodes(self, first=0, n=None):
+        """-> the distinct entries [first, first + n) as a list of bytes, in entry order"""
+        n = self.n - first if n is None else n
+        k = max(int(n), 1)
+        cb, ln = np.zeros((k, 32), np.uint8), np.zeros(k, np.uint8)
+        self._call("barcodes", int(first), int(n), cb.ctypes.data, ln.ctypes.data)
+        return [bytes(cb[i, :ln[i]]) for i in range(int(n))]
+
+    def match_raw(self, cb, ln, n, correct):
+        """br_whitelist_match as it is -> (the return code, entry uint32 [n], status uint8 [n])"""
+        entry, status = np.zeros(max(int(n), 1), np.uint32), np.zeros(max(int(n), 1), np.uint8)
+        rc = self._raw("match", cb.ctypes.data, ln.ctypes.data, int(n), int(correct), entry.ctypes.data, status.ctypes.data)
+        return rc, entry[:n], status[:n]
+
+    def match(self, barcodes, correct="1mm"):
+        """barcodes: one per name (bytes / str, None or empty: no barcode) -> (entry uint32, NONE for none; status uint8)"""
+        cb, ln = self.pack(barcodes)
+        rc, entry, status = self.match_raw(cb, ln, len(barcodes), self.correct_value(correct))
+        check(rc, "br_whitelist_match")
+        return entry, status
+
+    def stats(self):
+        out = np.zeros(8, np.uint64)
+        self._call("stats", out.ctypes.data)
+        return {k: int(v) for k, v in zip(self.STATS, out)}
+
+
 class Cells(_Accumulator):
     """br_cells on `device`: the names of projected batches and the records they were encoded to, in; after finish(quant, tx_feature,
     n_features) the cell x feature matrix of the quantifier's classes (matrix: CSR by cell), the cells' barcodes and numbers.
@@ -1928,7 +2022,9 @@ class Cells(_Accumulator):
                 "name_cells": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
                 "matrix": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
                 "cell_stats": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
-                "stats": [C.c_void_p, C.c_void_p], "free": [C.c_void_p]}
+                "stats": [C.c_void_p, C.c_void_p], "free": [C.c_void_p],
+                "set_whitelist": [C.c_void_p, C.c_void_p, C.c_int], "name_status": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
+                "whitelist_stats": [C.c_void_p, C.c_void_p]}
 
     def __init__(self, device=0, tolerance=None, **params):
         self.n_cells = self.n_entries = 0
@@ -1948,6 +2044,23 @@ class Cells(_Accumulator):
 
     def set_tolerance(self, tolerance):
         self._call("set_tolerance", float(tolerance))
+
+    def set_whitelist(self, whitelist, correct="1mm"):
+        """Before finish: the barcodes are resolved against `whitelist` (a Whitelist on this device, kept alive here) under
+        `correct` (Whitelist.CORRECT) before the cells are made."""
+        self._call("set_whitelist", whitelist.h if whitelist is not None else None, Whitelist.correct_value(correct))
+        self._whitelist = whitelist
+
+    def name_status(self, first, n):
+        """After a finish with a whitelist -> uint8 per add-order name (Whitelist.STATUS)"""
+        out = np.zeros(max(int(n), 1), np.uint8)
+        self._call("name_status", int(first), int(n), out.ctypes.data)
+        return out[:n]
+
+    def whitelist_stats(self):
+        out = np.zeros(8, np.uint64)
+        self._call("whitelist_stats", out.ctypes.data)
+        return {k: int(v) for k, v in zip(Whitelist.RESOLVE_STATS, out)}
 
     def add_raw(self, recs, row_off, n_rows, group_off, n_groups, on_device, stream=None):
         """br_cells_add as it is (recs: a BrDeviceBam or None; the tables as addresses): the return code (0, or a BR_ERR_* value)."""

@@ -1247,6 +1247,63 @@ int br_cells_cell_stats(br_cells *, int64_t first, int64_t n, uint64_t *names, u
 int br_cells_stats(const br_cells *, uint64_t out[16]);
 void br_cells_free(br_cells *);
 
+/* br_whitelist: the allowed cell barcodes of a run in one device's HBM, built once and read-only afterwards, so one object serves any
+ * number of br_cells and br_dedup objects on its device.  With one set, br_cells_finish and br_dedup_finish first map every
+ * name's observed barcode onto the list, repairing single-byte errors: STARsolo's --soloCBwhitelist / --soloCBmatchWLtype.
+ *   whitelist      W barcodes of 1..32 bytes, compared as bytes: length first, then content, as the cells are.  Duplicates collapse;
+ *                  entry w is the barcode's rank among the distinct ones in ascending (length, bytes) order
+ *   observed       the barcode of a name as br_cells / br_dedup read it at add time, unchanged
+ *   count[w]       the number of names added over the whole run (all adds) whose observed barcode equals entry w exactly.  Only names
+ *                  with rows have a barcode; the class of a name and its duplicate verdict play no part, so br_dedup and br_cells,
+ *                  fed the same names, resolve every name the same way
+ *   candidates     of an observed barcode b that is not in the whitelist: the distinct entries of b's length that differ from b in
+ *                  exactly one byte.  They are found by replacing one byte of b by one of A C G T other than the byte itself (an N
+ *                  has four replacements), so an entry with other bytes can only match exactly
+ *   "correct" 0    exact: b resolves to itself if it is in the whitelist, else to nothing
+ *   "correct" 1    1mm (STARsolo 1MM): as exact; a b not in the whitelist resolves to its candidate when it has exactly one, is
+ *                  ambiguous with two or more, and has no match with none
+ *   "correct" 2    1mm-multi (STARsolo 1MM_multi without base qualities): among the candidates with count > 0 the one with the
+ *                  largest count; two or more sharing the largest count: ambiguous; no candidate with count > 0: no match
+ *                  An exact hit always wins, whatever lies one byte away
+ *   status         per name.  0: no observed barcode; 1: exact; 2: corrected; 3: no match; 4: ambiguous
+ *   afterwards     a name of status 1 or 2 carries the entry's bytes as its barcode; a name of status 3 or 4 has none (length 0): for
+ *                  br_cells it is in no cell, for br_dedup it has the empty barcode, as a name without one has
+ *   table          open addressing in HBM: a power of two >= 2 W slots, 64 at least; a slot is one 64-bit word (tag << 32) | (entry +
+ *                  1), 0 when empty, claimed with a 64-bit compare-and-swap, linear probing.  The hash is a 64-bit mix (murmur3's
+ *                  fmix64) of the four words and the length, masked to "hash_bits" (1..64; 0: the default, 64); home slot and tag
+ *                  are both taken from the masked hash, so at 1 bit every entry has one of two home slots and every tag collides.
+ *                  Which slot an entry lands in depends on the order of the atomics; no result does.  Insert and probe loops are
+ *                  bounded by the slots
+ * Everything is integers and bytes: the same bits come out whatever the cut into adds, host or device tables, or "hash_bits".
+ *
+ *   br_whitelist_new        cb: n x 32 bytes (what lies past a barcode's length is not read), len: n.  n = 0, n >= 2^31, a length of 0
+ *                           or above 32, hash_bits outside 0..64: BR_ERR_INVALID_ARG and nothing is made
+ *   br_whitelist_barcodes   the distinct entries [first, first + n) in order; either pointer may be NULL
+ *   br_whitelist_match      the n barcodes as n names, one barcode each, from host arrays: length 0 means no barcode (above 32:
+ *                           BR_ERR_INVALID_ARG); count is taken over these n.  entry: 0xffffffff for none.  Not to be called from
+ *                           two threads at once on one object
+ *   br_whitelist_stats      given, distinct, slots, the longest probe chain at build (slots one insert looked at), microseconds in
+ *                           build, hash_bits, device bytes held, device bytes at most
+ *   br_cells_set_whitelist / br_dedup_set_whitelist   before finish, a whitelist on the object's device and "correct" 0..2, else
+ *                           BR_ERR_INVALID_ARG and nothing changes; br_dedup needs "cell_source" != 0.  The whitelist must live until
+ *                           finish has returned.  finish resolves after its argument checks; after it br_cells_barcodes returns
+ *                           the resolved barcodes.  Without a whitelist set nothing new is launched or allocated
+ *   br_cells_name_status    after a finish with a whitelist: the status per add-order name
+ *   br_cells_whitelist_stats / br_dedup_whitelist_stats   after such a finish: the names of status 0, 1, 2, 3, 4, the distinct
+ *                           observed barcodes D, microseconds in the resolve, "correct"
+ * Device memory: 33 bytes an entry and 8 a slot; the resolve's tables (whitelist.cpp) are gone before finish goes on. */
+typedef struct br_whitelist br_whitelist;
+int br_whitelist_new(int device, const uint8_t *cb /* n x 32, zero padded */, const uint8_t *len, int64_t n, int hash_bits, br_whitelist **out);
+int br_whitelist_barcodes(br_whitelist *, int64_t first, int64_t n, uint8_t *cb, uint8_t *len);
+int br_whitelist_match(br_whitelist *, const uint8_t *cb, const uint8_t *len, int64_t n, int correct, uint32_t *entry, uint8_t *status);
+int br_whitelist_stats(const br_whitelist *, uint64_t out[8]);
+void br_whitelist_free(br_whitelist *);
+int br_cells_set_whitelist(br_cells *, const br_whitelist *, int correct);
+int br_dedup_set_whitelist(br_dedup *, const br_whitelist *, int correct);
+int br_cells_name_status(br_cells *, int64_t first, int64_t n, uint8_t *status);
+int br_cells_whitelist_stats(const br_cells *, uint64_t out[8]);
+int br_dedup_whitelist_stats(const br_dedup *, uint64_t out[8]);
+
 /* ---- SAM text out -------------------------------------------------------------------------- */
 
 /* The reference names RNAME and RNEXT print, in refID order (a refID < 0 or >= n prints '*'); uploaded to HBM once, kept by
