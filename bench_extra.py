@@ -48,6 +48,11 @@
                                          br_quant + br_cells from HBM: build seconds and the longest probe chain, then per step
                                          br_cells_finish (mode unique) without a whitelist and with it under 1mm and 1mm-multi -- the
                                          resolve's seconds, the statuses' names and, beside them, the finish's seconds without the resolve
+  python bench_extra.py cellcall [--reads K]  br_cellcall at its default parameters (emptydrops, 10 000 simulations) on a seeded generated
+                                         CSR resident in HBM: K barcodes (default 300 000) x 30 000 features, 4 000 large cells, 6 000
+                                         barcodes of 500 .. 2 000 counts (half from the cells' profile, half ambient) and an ambient
+                                         tail: the four stage times of br_cellcall_stats (rank, ambient, simulate, p-value), the whole
+                                         run, the calls; and, for scale, the tests' restatement over 100 of the simulations on the CPU
   python bench_extra.py small            small calls: us per device-resident step at 1 .. 52 000 pairs (without the per-kernel
                                          events bench.py keeps on), the path without host round trips against the ordinary one,
                                          and br_project_group / br_project_groups host to host from plain C (profiles/group_latency.c)
@@ -65,7 +70,7 @@ import time
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "quant_boot", "quant_genes", "coverage", "cells", "whitelist"])
+    ap.add_argument("config", choices=["c3", "c5", "bam", "bundle", "cli", "small", "inflate", "sam", "collate", "samout", "sort", "quant", "quant_boot", "quant_genes", "coverage", "cells", "whitelist", "cellcall"])
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reads", type=int, default=0)
     ap.add_argument("--steps", type=int, default=3)
@@ -76,6 +81,57 @@ def main():
     import torch
     from bramble_amd import device as brdev
     from bramble_amd import lib, synth
+    if args.config == "cellcall":
+        K, F, n_large, n_mid = args.reads or 300_000, 30_000, 4_000, 6_000
+        rng = np.random.default_rng(13)
+        amb = rng.gamma(0.3, 1.0, F) + 1e-4
+        amb /= amb.sum()
+        cellp = rng.permutation(amb) * rng.gamma(2.0, 1.0, F)
+        cellp /= cellp.sum()
+        totals = np.concatenate([rng.integers(5000, 20001, n_large), rng.integers(500, 2001, n_mid), np.minimum(rng.geometric(0.03, K - n_large - n_mid), 450)])
+        like_cell = np.concatenate([np.ones(n_large, bool), rng.random(n_mid) < 0.5, np.zeros(K - n_large - n_mid, bool)])
+        perm = rng.permutation(K)   # (the barcodes in no order of size)
+
+        def draws(mask, prof):
+            cells = np.repeat(perm[np.flatnonzero(mask)], totals[mask]).astype(np.int64)
+            return cells * F + rng.choice(F, len(cells), p=prof)
+        key, cnt = np.unique(np.concatenate([draws(like_cell, cellp), draws(~like_cell, amb)]), return_counts=True)
+        off = np.searchsorted(key // F, np.arange(K + 1)).astype(np.uint64)
+        feat = (key % F).astype(np.uint32)
+        t = [torch.from_numpy(x).cuda() for x in (off.view(np.int64), feat.view(np.int32), cnt.astype(np.uint32).view(np.int32))]
+        torch.cuda.synchronize()
+        out = {"config": "cellcall", "workload": "%d barcodes x %d features, %d entries, %d counts; %d large cells, %d of 500..2000 counts (%d of them cell-like)"
+               % (K, F, len(key), int(cnt.sum()), n_large, n_mid, int(like_cell[n_large:].sum())), "runs": []}
+        c = None
+        for step in range(args.warmup + args.steps):
+            if c is not None:
+                c.close()
+            c = lib.CellCall(keep_sims=0)
+            t0 = time.perf_counter()
+            c.run_device(t[0], t[1], t[2], F)
+            wall = time.perf_counter() - t0
+            st = c.stats()
+            if step >= args.warmup:
+                run = {k[:-3] + "_s": round(st[k] * 1e-6, 4) for k in ("rank_us", "ambient_us", "simulate_us", "pvalue_us")}
+                run.update({"run_s": round(wall, 4)})
+                run.update({k: st[k] for k in ("called_simple", "called_emptydrops", "threshold", "candidates", "n_max", "wanted_totals", "active_features",
+                                               "p_route", "sim_chunks", "fallback", "sims", "peak_bytes")})
+                out["runs"].append(run)
+        status = c.calls()[0]
+        mid = perm[n_large:n_large + n_mid]
+        out["mid_cell_like_called"] = int(np.sum(status[mid[like_cell[n_large:n_large + n_mid]]] == 2))
+        out["mid_ambient_called"] = int(np.sum(status[mid[~like_cell[n_large:n_large + n_mid]]] == 2))
+        try:   # for scale only: the tests' restatement (numpy, one thread) over 100 of the simulations, on this host's CPU
+            from tests import cellcall_cases
+            a, ln, want = c.ambient(), c.logtable(), c.wanted()
+            t0 = time.perf_counter()
+            cellcall_cases.simulate(a["T"], a["lp"], ln, st["n_max"], 100, 0, [int(x) for x in want])
+            out["restatement_100_sims_s"] = round(time.perf_counter() - t0, 3)
+        except ImportError:
+            pass
+        c.close()
+        print(json.dumps(out))
+        return
     if args.config == "whitelist":
         n_wl, n_names, n_cells, n_tx = 6_794_880, args.reads or 4_000_000, 100_000, 20_000
         rng = np.random.default_rng(7)

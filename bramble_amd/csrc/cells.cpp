@@ -27,6 +27,8 @@
 #include "accum.h"
 #include "barcode_inl.h"
 #include "barcode_sort.h"
+#include "cellcall.h"
+#include "cellcall_kernels.h"
 #include "cells_kernels.h"
 #include "ctx.h"
 #include "quant_kernels.h"
@@ -51,6 +53,11 @@ struct br_cells : Accum {
   WlResolved wl_res;
   ColBuf small, cb, cblen, status;
   ColBuf name_cell, cell_cb, cell_len, m_off, m_feat, m_val, c_names, c_unique, c_multi, c_feat, c_iters;
+  // "call_counts": the "unique" counts as integers (u_off, u_feat alias the matrix's in mode 0: empty here), then what br_cells_call left
+  int call_counts = 0;
+  bool called = false;
+  uint64_t n_u = 0, n_called = 0, n_called_entries = 0;
+  ColBuf u_off, u_feat, u_cnt, f_off, f_cells, f_feat, f_val;
 };
 
 extern "C" void br_cells_free(br_cells *c) {
@@ -79,6 +86,7 @@ extern "C" int br_cells_set_param(br_cells *c, const char *name, int64_t value) 
   if (!strcmp(name, "mode")) { if (value < 0 || value > 2) return BR_ERR_INVALID_ARG; c->mode = (int)value; return BR_OK; }
   if (!strcmp(name, "max_iters")) { if (value < 1 || value > 0xffffffffll) return BR_ERR_INVALID_ARG; c->max_iters = value; return BR_OK; }
   if (!strcmp(name, "hash_bits")) { if (value < 1 || value > 64) return BR_ERR_INVALID_ARG; c->hash_bits = (int)value; return BR_OK; }
+  if (!strcmp(name, "call_counts")) { if (value < 0 || value > 1) return BR_ERR_INVALID_ARG; c->call_counts = (int)value; return BR_OK; }
   if (!strcmp(name, "lds_bytes")) { if (value < 0 || value > (int64_t)CL_LDS_MAX) return BR_ERR_INVALID_ARG; c->lds_bytes = (uint32_t)value; return BR_OK; }
   return BR_ERR_INVALID_ARG;
 }
@@ -350,6 +358,28 @@ static int cells_finish(br_cells *c, const QuantClassView &V, const uint32_t *tx
   launch_cl_matrix(st, T, flag.as<uint64_t>(), (int64_t)S, s_feat.as<uint32_t>(), val.as<double>(), c->m_off.as<uint64_t>(), c->m_feat.as<uint32_t>(),
                    c->m_val.as<double>(), c->c_feat.as<uint32_t>());
   HIPCHK(hipStreamSynchronize(st));
+  if (c->call_counts) {   // the counts the cells are called on: "unique"'s values without the slots at 0, whatever the mode
+    uint64_t U = Z;
+    const double *from = c->m_val.as<double>();
+    ColBuf uval, nf;
+    DropGuard dropper{c, {&uval, &nf}};
+    if (c->mode != 0) {
+      RC(c->alloc(nf, k1 * 4));
+      launch_cl_unique(st, T, (int64_t)S, val.as<double>());   // (the mode's values are in the matrix by now)
+      launch_cl_keep(st, val.as<double>(), (int64_t)S, 1, flag.as<uint64_t>());
+      RC(cells_scan(c, flag, (int64_t)S, tmp, &U));
+      if (U > S) return BR_ERR_HIP;
+      RC(c->alloc(c->u_off, k1 * 8)); RC(c->alloc(c->u_feat, ((size_t)U + 1) * 4));
+      RC(c->alloc(uval, ((size_t)U + 1) * 8));
+      launch_cl_matrix(st, T, flag.as<uint64_t>(), (int64_t)S, s_feat.as<uint32_t>(), val.as<double>(), c->u_off.as<uint64_t>(), c->u_feat.as<uint32_t>(),
+                       uval.as<double>(), nf.as<uint32_t>());
+      from = uval.as<double>();
+    }
+    RC(c->alloc(c->u_cnt, ((size_t)U + 1) * 4));
+    launch_cc_counts(st, from, U, c->u_cnt.as<uint32_t>());
+    HIPCHK(hipStreamSynchronize(st));
+    c->n_u = U;
+  }
   c->n_cells = K; c->n_entries = E; c->n_pairs = P; c->n_slots = S; c->n_matrix = Z;
   return BR_OK;
 }
@@ -440,6 +470,54 @@ extern "C" int br_cells_matrix(br_cells *c, int64_t first_cell, int64_t n, uint6
   const uint64_t z0 = cell_off[0], z = cell_off[n] - z0;
   if (z && feature) HIPCHK(hipMemcpyAsync(feature, c->m_feat.as<uint32_t>() + z0, (size_t)z * 4, hipMemcpyDeviceToHost, st));
   if (z && value) HIPCHK(hipMemcpyAsync(value, c->m_val.as<double>() + z0, (size_t)z * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int64_t k = 0; k <= n; k++) cell_off[k] -= z0;
+  return BR_OK;
+}
+
+extern "C" int br_cells_call(br_cells *c, br_cellcall *cc, int64_t n_features) {
+  if (!c || c->dead || !c->finished || !c->call_counts || c->called || !cc_fresh(cc, c->device)) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  const bool own = c->mode != 0;
+  RC(cc_run(cc, (int64_t)c->n_cells, n_features, (own ? c->u_off : c->m_off).as<uint64_t>(), (own ? c->u_feat : c->m_feat).as<uint32_t>(),
+            c->u_cnt.as<uint32_t>(), c->n_u));
+  // the matrix's rows of the called cells
+  int64_t K = 0;
+  uint64_t n_called = 0;
+  const uint8_t *status = cc_status(cc, &K, &n_called);
+  if (!status || (uint64_t)K != c->n_cells) return BR_ERR_HIP;
+  const size_t k1 = (size_t)K + 1;
+  ColBuf flag, len, tmp;
+  DropGuard bufs{c, {&flag, &len, &tmp}};
+  RC(c->alloc(flag, k1 * 8)); RC(c->alloc(len, k1 * 8));
+  HIPCHK(hipMemsetAsync(flag.p, 0, k1 * 8, st));
+  HIPCHK(hipMemsetAsync(len.p, 0, k1 * 8, st));
+  launch_cc_called(st, status, c->m_off.as<uint64_t>(), K, flag.as<uint64_t>(), len.as<uint64_t>());
+  uint64_t got = 0, Zc = 0;
+  RC(cells_scan(c, flag, K, tmp, &got));
+  RC(cells_scan(c, len, K, tmp, &Zc));
+  if (got != n_called || Zc > c->n_matrix) return BR_ERR_HIP;
+  RC(c->alloc(c->f_off, ((size_t)got + 1) * 8)); RC(c->alloc(c->f_cells, ((size_t)got + 1) * 4));
+  RC(c->alloc(c->f_feat, ((size_t)Zc + 1) * 4)); RC(c->alloc(c->f_val, ((size_t)Zc + 1) * 8));
+  launch_cc_rows(st, status, flag.as<uint64_t>(), len.as<uint64_t>(), K, c->m_off.as<uint64_t>(), c->m_feat.as<uint32_t>(), c->m_val.as<double>(),
+                 c->f_cells.as<uint32_t>(), c->f_off.as<uint64_t>(), c->f_feat.as<uint32_t>(), c->f_val.as<double>());
+  HIPCHK(hipMemcpyAsync(c->f_off.as<uint64_t>() + got, &Zc, 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  c->n_called = got; c->n_called_entries = Zc; c->called = true;
+  return BR_OK;
+}
+
+extern "C" int br_cells_matrix_called(br_cells *c, int64_t first, int64_t n, uint32_t *cells, uint64_t *cell_off, uint32_t *feature, double *value) {
+  if (!c || c->dead || !c->called || !in_range(c->n_called, first, n) || !cell_off) return BR_ERR_INVALID_ARG;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  HIPCHK(hipMemcpyAsync(cell_off, c->f_off.as<uint64_t>() + first, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (n && cells) HIPCHK(hipMemcpyAsync(cells, c->f_cells.as<uint32_t>() + first, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t z0 = cell_off[0], z = cell_off[n] - z0;
+  if (z && feature) HIPCHK(hipMemcpyAsync(feature, c->f_feat.as<uint32_t>() + z0, (size_t)z * 4, hipMemcpyDeviceToHost, st));
+  if (z && value) HIPCHK(hipMemcpyAsync(value, c->f_val.as<double>() + z0, (size_t)z * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   for (int64_t k = 0; k <= n; k++) cell_off[k] -= z0;
   return BR_OK;

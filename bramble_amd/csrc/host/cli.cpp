@@ -57,7 +57,10 @@ void usage(FILE *f) {
           "               [--dedup unique|directional [--dedup-umi name|tag] [--dedup-umi-sep C] [--dedup-umi-tag XY]\n"
           "                [--dedup-stats <sizes.tsv>] [--dedup-bam <dedup.bam> [--dedup-bam-mode remove|mark]]]\n"
           "               [--cells <prefix> [--cells-barcode name|tag] [--cells-barcode-tag XY] [--cells-features gene|transcript]\n"
-          "                [--cells-multi unique|uniform|em] [--cells-whitelist <file> [--cells-correct exact|1mm|1mm-multi]]]\n\n"
+          "                [--cells-multi unique|uniform|em] [--cells-whitelist <file> [--cells-correct exact|1mm|1mm-multi]]\n"
+          "                [--cells-filter topcells|cr2.2|emptydrops [--cells-expected N] [--cells-filter-percentile P]\n"
+          "                 [--cells-filter-ratio R] [--cells-ed-window LO,HI] [--cells-ed-umi-min N] [--cells-ed-umi-frac F]\n"
+          "                 [--cells-ed-candidates N] [--cells-ed-fdr F] [--cells-ed-sims N]]]\n\n"
           "Project spliced genomic alignments into transcriptomic space.\n"
           "The output BGZF blocks are deflated on the GPU by default (per-block Huffman codes); --host-deflate or\n"
           "--compression-level N use the host codec (libdeflate / zlib, level 6 like the reference unless N is given).\n"
@@ -149,7 +152,7 @@ void usage(FILE *f) {
           "(--cells-multi unique, the default: integer counts), for each an equal share (uniform) or the shares of an EM run per cell on\n"
           "the GPU (em: STARsolo's and alevin's estimator).  PREFIXmatrix.mtx (Matrix Market, features x cells, the 10x layout),\n"
           "PREFIXbarcodes.tsv, PREFIXfeatures.tsv and PREFIXcells.tsv (Barcode Names Unique Multi Features Iterations); the directory of\n"
-          "PREFIX must exist.  The matrix is the raw one unless --cells-whitelist is given; there is no cell filtering.  With --dedup the\n"
+          "PREFIX must exist.  The matrix is the raw one unless --cells-whitelist is given; --cells-filter calls the cells.  With --dedup the\n"
           "duplicates are found per cell (umi_tools' --per-cell) and the matrix counts molecules; quant.tsv then reflects the per-cell\n"
           "molecules as well.  One more line in front of the final report: [bramble] cells: C cells, M of N read names counted (B\n"
           "without barcode; Z matrix entries; features gene|transcript; multi unique|uniform|em; add X.XXs, finish Y.YYs)\n"
@@ -161,7 +164,28 @@ void usage(FILE *f) {
           "exactly, dropped on a tie.  A read name whose barcode is dropped is in no cell.  The barcodes printed are entries of the\n"
           "list; PREFIXcells.tsv gains a last column Corrected.  One more line: [bramble] whitelist: W barcodes; B read names with a\n"
           "barcode: X exact, C corrected, R without match, A ambiguous (D distinct observed; correct exact|1mm|1mm-multi; build\n"
-          "X.XXs, resolve Y.YYs)\n");
+          "X.XXs, resolve Y.YYs)\n"
+          "--cells-filter METHOD: the cells are called on the GPU, on their unique counts whatever --cells-multi is, by definitions\n"
+          "modelled on STARsolo's --soloCellFilter (not compared with its or CellRanger's output).  topcells: the --cells-expected N\n"
+          "(3000) barcodes with the most counts, ties included.  cr2.2: every barcode with at least 1 / --cells-filter-ratio (10) of\n"
+          "the count at rank N * (1 - --cells-filter-percentile (0.99)).  emptydrops: those, and of the --cells-ed-candidates (20000)\n"
+          "next barcodes with --cells-ed-umi-min (500) counts and --cells-ed-umi-frac (0.01) of the median cell's or more the ones\n"
+          "whose counts the ambient profile -- the barcodes at ranks --cells-ed-window LO,HI (45000,90000), Good-Turing smoothed --\n"
+          "does not explain: --cells-ed-sims (10000) multinomial simulations under --quant-seed, Benjamini-Hochberg at --cells-ed-fdr\n"
+          "(0.01).  PREFIXfiltered_matrix.mtx and PREFIXfiltered_barcodes.tsv (the called cells; features.tsv serves both) and\n"
+          "PREFIXcalls.tsv (Barcode Total Rank Status LogLik Lower PValue PAdj; status 1: by count, 2: by emptydrops; a dot where a\n"
+          "barcode was no candidate).  One more line: [bramble] cell calling: C of K cells called (...)\n");
+}
+// a whole number in [lo, hi] / a real in [lo, hi]; false: said
+bool parse_count(const char *opt, const char *s, long long lo, long long hi, long long &v) {
+  char *e; errno = 0; const long long x = strtoll(s, &e, 10);
+  if (e == s || *e || errno || x < lo || x > hi) { fprintf(stderr, "%s: %s is not a whole number in %lld .. %lld\n", opt, s, lo, hi); return false; }
+  v = x; return true;
+}
+bool parse_real(const char *opt, const char *s, double lo, double hi, double &v) {
+  char *e; const double x = strtod(s, &e);
+  if (e == s || *e || !(x >= lo && x <= hi)) { fprintf(stderr, "%s: %s is not a number in %g .. %g\n", opt, s, lo, hi); return false; }
+  v = x; return true;
 }
 bool parse_u32(const char *s, uint32_t &v) { char *e; unsigned long x = strtoul(s, &e, 10); if (e == s || *e) return false; v = (uint32_t)x; return true; }
 
@@ -170,7 +194,7 @@ int parse_args(int argc, char **argv, Options &o) {
   memset(&o.cfg, 0, sizeof(o.cfg));
   o.cfg.junc_miss_discount = 1.0;
   bool codec = false, host_codec = false;   // a BGZF codec option was given; one that asks for the host codec
-  bool coverage_weight_given = false, unprojected_scope_given = false, quant_bam_mode_given = false, dedup_switch_given = false, dedup_bam_mode_given = false, cells_switch_given = false, cells_correct_given = false;
+  bool coverage_weight_given = false, unprojected_scope_given = false, quant_bam_mode_given = false, dedup_switch_given = false, dedup_bam_mode_given = false, cells_switch_given = false, cells_correct_given = false, cells_filter_switch_given = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "%s: missing value\n", argv[i]); return nullptr; } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -327,6 +351,30 @@ int parse_args(int argc, char **argv, Options &o) {
       else { fprintf(stderr, "--cells-multi: unknown mode %s (unique, uniform or em)\n", v); return -1; }
       cells_switch_given = true;
     }
+    else if (a == "--cells-filter") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      if (w == "topcells") o.cells_filter = 0; else if (w == "cr2.2") o.cells_filter = 1; else if (w == "emptydrops") o.cells_filter = 2;
+      else { fprintf(stderr, "--cells-filter: unknown method %s (topcells, cr2.2 or emptydrops)\n", v); return -1; }
+    }
+    else if (a == "--cells-expected") { const char *v = value(); if (!v || !parse_count("--cells-expected", v, 1, 0x7fffffffll, o.cells_expected)) return -1; cells_filter_switch_given = true; }
+    else if (a == "--cells-filter-percentile") { const char *v = value(); if (!v || !parse_real("--cells-filter-percentile", v, 0.0, 1.0, o.cells_percentile)) return -1; cells_filter_switch_given = true; }
+    else if (a == "--cells-filter-ratio") { const char *v = value(); if (!v || !parse_real("--cells-filter-ratio", v, 1.0, 1e9, o.cells_ratio)) return -1; cells_filter_switch_given = true; }
+    else if (a == "--cells-ed-window") {
+      const char *v = value(); if (!v) return -1;
+      const std::string w = v;
+      const size_t comma = w.find(',');
+      if (comma == std::string::npos || !parse_count("--cells-ed-window", w.substr(0, comma).c_str(), 0, 0x7fffffffll, o.cells_ed_lo) ||
+          !parse_count("--cells-ed-window", w.substr(comma + 1).c_str(), 0, 0x7fffffffll, o.cells_ed_hi) || o.cells_ed_lo >= o.cells_ed_hi) {
+        fprintf(stderr, "--cells-ed-window: %s is not LO,HI with LO < HI\n", v); return -1;
+      }
+      cells_filter_switch_given = true;
+    }
+    else if (a == "--cells-ed-umi-min") { const char *v = value(); if (!v || !parse_count("--cells-ed-umi-min", v, 0, 0xffffffffll, o.cells_ed_umi_min)) return -1; cells_filter_switch_given = true; }
+    else if (a == "--cells-ed-umi-frac") { const char *v = value(); if (!v || !parse_real("--cells-ed-umi-frac", v, 0.0, 1.0, o.cells_ed_umi_frac)) return -1; cells_filter_switch_given = true; }
+    else if (a == "--cells-ed-candidates") { const char *v = value(); if (!v || !parse_count("--cells-ed-candidates", v, 1, 0x7fffffffll, o.cells_ed_candidates)) return -1; cells_filter_switch_given = true; }
+    else if (a == "--cells-ed-fdr") { const char *v = value(); if (!v || !parse_real("--cells-ed-fdr", v, 0.0, 1.0, o.cells_ed_fdr)) return -1; cells_filter_switch_given = true; }
+    else if (a == "--cells-ed-sims") { const char *v = value(); if (!v || !parse_count("--cells-ed-sims", v, 1, 0x7fffffffll, o.cells_ed_sims)) return -1; cells_filter_switch_given = true; }
     else if (a == "--dedup-stats") { const char *v = value(); if (!v) return -1; o.dedup_stats = v; dedup_switch_given = true; }
     else if (a == "--dedup-bam") { const char *v = value(); if (!v) return -1; o.dedup_bam = v; dedup_switch_given = true; }
     else if (a == "--dedup-bam-mode") {
@@ -371,6 +419,8 @@ int parse_args(int argc, char **argv, Options &o) {
   if (o.quant_genes.empty() && (!o.quant_gene_classes.empty() || (!o.quant_gene_map.empty() && !cell_genes))) { fprintf(stderr, "--quant-gene-classes and --quant-gene-map need --quant-genes\n"); return -1; }
   if (cells_switch_given && o.cells.empty()) { fprintf(stderr, "--cells-barcode, --cells-barcode-tag, --cells-features and --cells-multi need --cells\n"); return -1; }
   if (!o.cells_whitelist.empty() && o.cells.empty()) { fprintf(stderr, "--cells-whitelist needs --cells\n"); return -1; }
+  if (o.cells_filter >= 0 && o.cells.empty()) { fprintf(stderr, "--cells-filter needs --cells\n"); return -1; }
+  if (cells_filter_switch_given && o.cells_filter < 0) { fprintf(stderr, "--cells-expected, --cells-filter-percentile, --cells-filter-ratio and the --cells-ed switches need --cells-filter\n"); return -1; }
   if (cells_correct_given && o.cells_whitelist.empty()) { fprintf(stderr, "--cells-correct needs --cells-whitelist\n"); return -1; }
   if (!o.cells.empty() && o.quant.empty()) { fprintf(stderr, "--cells needs --quant: the matrix is made from the quantifier's classes\n"); return -1; }
   if (!o.quant_boot_out.empty() && !o.quant_bootstraps) { fprintf(stderr, "--quant-boot-out needs --quant-bootstraps: without it there are no replicates\n"); return -1; }

@@ -71,6 +71,10 @@ struct Options {
   int cells_multi = 0;           // --cells-multi unique|uniform|em: br_cells' "mode" (0, 1, 2)
   std::string cells_whitelist;   // --cells-whitelist FILE: the allowed cell barcodes (br_whitelist), one a line
   int cells_correct = 1;         // --cells-correct exact|1mm|1mm-multi: "correct" (0, 1, 2)
+  int cells_filter = -1;         // --cells-filter topcells|cr2.2|emptydrops: br_cellcall's "method" (0, 1, 2); -1: the cells are not called
+  long long cells_expected = 3000, cells_ed_lo = 45000, cells_ed_hi = 90000, cells_ed_umi_min = 500, cells_ed_candidates = 20000,
+            cells_ed_sims = 10000;   // --cells-expected, --cells-ed-window LO,HI, --cells-ed-umi-min, --cells-ed-candidates, --cells-ed-sims
+  double cells_percentile = 0.99, cells_ratio = 10.0, cells_ed_umi_frac = 0.01, cells_ed_fdr = 0.01;   // --cells-filter-percentile, -ratio, --cells-ed-umi-frac, -fdr
   int device_reader = -1;       // inflate + record split on the GPU (br_bam_reader): -1 = when the input is a regular file and one device is used
 };
 inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }

@@ -82,6 +82,24 @@ void write_cells_table(FILE *f, const std::vector<uint8_t> &barcodes, const std:
   }
 }
 
+void write_cells_calls(FILE *f, const std::vector<uint8_t> &barcodes, const std::vector<uint8_t> &len, const std::vector<uint64_t> &total,
+                       const std::vector<uint32_t> &rank, const std::vector<uint8_t> &status, const std::vector<uint32_t> &cand_of,
+                       const std::vector<double> &loglik, const std::vector<uint32_t> &lower, const std::vector<double> &pval,
+                       const std::vector<double> &padj, bool only) {
+  if (!only) fprintf(f, "Barcode\tTotal\tRank\tStatus\tLogLik\tLower\tPValue\tPAdj\n");
+  for (size_t k = 0; k < len.size(); k++) {
+    if (only && !status[k]) continue;
+    fwrite(barcodes.data() + 32 * k, 1, len[k], f);
+    if (!only) {
+      fprintf(f, "\t%llu\t%u\t%u", (unsigned long long)total[k], rank[k], (unsigned)status[k]);
+      const uint32_t j = cand_of[k];
+      if (j == 0xffffffffu) fprintf(f, "\t.\t.\t.\t.");
+      else fprintf(f, "\t%.17g\t%u\t%.17g\t%.17g", loglik[j], lower[j], pval[j], padj[j]);
+    }
+    fputc('\n', f);
+  }
+}
+
 void write_quant_table(FILE *f, const TxTable &tx, const std::vector<double> *eff, const std::vector<double> &theta, const std::vector<double> &tpm,
                        const std::vector<uint64_t> &unique, const std::vector<uint64_t> &ambig, const std::vector<double> *boot_mean,
                        const std::vector<double> *boot_var) {

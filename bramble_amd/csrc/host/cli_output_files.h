@@ -64,6 +64,13 @@ void write_cells_features(FILE *f, const TxTable &tx, bool genes);
 void write_cells_table(FILE *f, const std::vector<uint8_t> &barcodes, const std::vector<uint8_t> &len, const std::vector<uint64_t> &names,
                        const std::vector<uint64_t> &unique, const std::vector<uint64_t> &multi, const std::vector<uint32_t> &features,
                        const std::vector<uint32_t> &iters, bool table, const std::vector<uint64_t> *corrected = nullptr);
+// --cells-filter: Barcode Total Rank Status LogLik Lower PValue PAdj, a line per cell in barcode order.  cand_of[k]: the cell's place among
+// the candidates (their columns with %.17g), or 0xffffffff: a dot in each of the four; `only`: the barcodes of the cells with a status
+// other than 0, nothing else (filtered_barcodes.tsv)
+void write_cells_calls(FILE *f, const std::vector<uint8_t> &barcodes, const std::vector<uint8_t> &len, const std::vector<uint64_t> &total,
+                       const std::vector<uint32_t> &rank, const std::vector<uint8_t> &status, const std::vector<uint32_t> &cand_of,
+                       const std::vector<double> &loglik, const std::vector<uint32_t> &lower, const std::vector<double> &pval,
+                       const std::vector<double> &padj, bool only);
 // runs [first, first + n) into the four columns; not 0: an error, which ends the file there
 using RunPage = std::function<int(int64_t first, int64_t n, uint32_t *tid, uint32_t *start, uint32_t *end, uint32_t *depth)>;
 int write_bedgraph(FILE *f, const TxTable &tx, int64_t n_runs, int64_t page, const RunPage &fetch);   // the first error of fetch

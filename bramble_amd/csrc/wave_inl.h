@@ -10,6 +10,7 @@
 //   block_bits(o, a, out)                             OR of o and AND of a over a block of 256 threads (the radix sort's digits)
 //   load8 / store8                                    a thread's eight consecutive scan items as 16-byte accesses
 //   kth_set_bit64(mask, k)                            the index of a mask's k-th set bit, without a loop
+//   wave_match(v, bits, on)                           the mask of the wave's lanes that hold the same value
 //   scan_top_rounds<C, ITEMS>(...)                    a scan's tile sums scanned in place by one block
 #pragma once
 #include <stdint.h>
@@ -142,6 +143,19 @@ __device__ __forceinline__ uint32_t kth_set_bit64(uint64_t mask, uint32_t k) {
 __device__ __forceinline__ uint64_t wave_last64(uint64_t v) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
   return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+
+// The lanes of the wave that hold the same v as this lane, as a mask (the lane's own bit is set); a lane with `on` false is in
+// nobody's mask and gets 0.  v < 2^bits, bits the same in every lane: one ballot a bit, so the cost does not depend on how many
+// values are equal (a loop over the distinct values took 64 rounds for 64 different ones).  The whole wave calls it.
+__device__ __forceinline__ uint64_t wave_match(uint32_t v, int bits, bool on) {
+  uint64_t m = __ballot(on);
+  for (int b = 0; b < bits; b++) {
+    const bool set = (v >> b) & 1u;
+    const uint64_t y = __ballot(set);
+    m &= set ? y : ~y;
+  }
+  return on ? m : 0ull;
 }
 
 // The tile sums of a scan, scanned in place by ONE block of 256 threads: C arrays of n_tiles sums, one behind the other,

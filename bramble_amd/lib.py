@@ -194,6 +194,9 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_cells_cell_barcodes", "br_cells_name_cells", "br_cells_matrix", "br_cells_cell_stats", "br_cells_stats", "br_cells_free",
            "br_whitelist_new", "br_whitelist_barcodes", "br_whitelist_match", "br_whitelist_stats", "br_whitelist_free", "br_cells_set_whitelist",
            "br_dedup_set_whitelist", "br_cells_name_status", "br_cells_whitelist_stats", "br_dedup_whitelist_stats",
+           "br_cellcall_new", "br_cellcall_set_param", "br_cellcall_set_real", "br_cellcall_run", "br_cellcall_calls", "br_cellcall_ambient",
+           "br_cellcall_logtable", "br_cellcall_candidates", "br_cellcall_wanted", "br_cellcall_sims", "br_cellcall_stats", "br_cellcall_sgt",
+           "br_cellcall_free", "br_cells_call", "br_cells_matrix_called",
            "br_free_buffer", "br_bgzf_codec", "br_bgzf_deflate_device", "br_ctx_set_profiling",
            "br_ctx_set_param", "br_ctx_kernel_ms", "br_ctx_kernel_ms_sum", "br_ctx_collect_counters", "br_ctx_last_counters", "br_ctx_direct_diag", "br_ctx_direct_tidwords", "br_ctx_rescue_stats", "br_ctx_ksw_diag", "br_device_rows_detail", "br_ctx_ksw_pairs", "br_primary_pick", "br_row_mapq", "br_version", "br_strerror"]
 
@@ -2024,7 +2027,8 @@ class Cells(_Accumulator):
                 "cell_stats": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
                 "stats": [C.c_void_p, C.c_void_p], "free": [C.c_void_p],
                 "set_whitelist": [C.c_void_p, C.c_void_p, C.c_int], "name_status": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
-                "whitelist_stats": [C.c_void_p, C.c_void_p]}
+                "whitelist_stats": [C.c_void_p, C.c_void_p], "call": [C.c_void_p, C.c_void_p, C.c_int64],
+                "matrix_called": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]}
 
     def __init__(self, device=0, tolerance=None, **params):
         self.n_cells = self.n_entries = 0
@@ -2141,6 +2145,24 @@ class Cells(_Accumulator):
         self._call("matrix", int(first), int(n), off.ctypes.data, feat.ctypes.data, val.ctypes.data)
         return off, feat[:z], val[:z]
 
+    def call(self, cellcall, n_features):
+        """After finish(), with "call_counts": runs `cellcall` (a CellCall with its parameters set) on the cells' unique counts"""
+        self._call("call", cellcall.h, int(n_features))
+        cellcall.n_cells, cellcall.n_features = self.n_cells, int(n_features)
+        st = cellcall.stats()
+        self.n_called = st["called_simple"] + st["called_emptydrops"]
+        return cellcall
+
+    def matrix_called(self, first=0, n=None):
+        """After call() -> (cells uint32 [n], cell_off uint64 [n + 1], feature uint32, value float64): the called cells' rows"""
+        n = self.n_called - first if n is None else n
+        cells, off = np.zeros(max(int(n), 1), np.uint32), np.zeros(int(n) + 1, np.uint64)
+        self._call("matrix_called", int(first), int(n), cells.ctypes.data, off.ctypes.data, None, None)
+        z = int(off[-1])
+        feat, val = np.zeros(max(z, 1), np.uint32), np.zeros(max(z, 1), np.float64)
+        self._call("matrix_called", int(first), int(n), None, off.ctypes.data, feat.ctypes.data, val.ctypes.data)
+        return cells[:n], off, feat[:z], val[:z]
+
     def cell_stats(self, first=0, n=None):
         """-> dict of per-cell arrays: names, unique, multi (uint64), features, iterations (uint32)"""
         n = self.n_cells - first if n is None else n
@@ -2154,3 +2176,132 @@ class Cells(_Accumulator):
         out = np.zeros(16, np.uint64)
         self._call("stats", out.ctypes.data)
         return {k: int(v) for k, v in zip(self.STATS, out)}
+
+
+class CellCall(_Accumulator):
+    """br_cellcall on `device`: which barcodes of a cell x feature count matrix (CSR by cell) are cells.  Parameters (PARAMS integers,
+    REALS reals; "method" also by name) before run(); after it calls(), ambient(), logtable(), candidates(), wanted(), sims() and
+    stats()."""
+
+    METHODS = {"topcells": 0, "cr2.2": 1, "emptydrops": 2}
+    PARAMS = ("method", "expected", "ind_min", "ind_max", "umi_min", "cand_max", "sims", "seed", "sim_bytes", "keep_sims")
+    REALS = ("percentile", "ratio", "umi_frac", "fdr")
+    FALLBACK = ("none", "empty_window", "zero_ambient", "no_candidates")
+    STATS = ("cells", "called_simple", "called_emptydrops", "threshold", "n_simple", "window", "ambient_counts", "active_features", "p_route",
+             "slope_bits", "lo", "candidates", "n_max", "wanted_totals", "sim_chunks", "fallback", "rank_us", "ambient_us", "simulate_us",
+             "pvalue_us", "method", "sims", "held_bytes", "peak_bytes", "entries", "features")
+
+    NAME = "cellcall"
+    ARGTYPES = {"new": [C.c_int, _P(C.c_void_p)], "set_param": [C.c_void_p, C.c_char_p, C.c_int64], "set_real": [C.c_void_p, C.c_char_p, C.c_double],
+                "run": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+                "calls": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+                "ambient": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                "logtable": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
+                "candidates": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+                "wanted": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
+                "sims": [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p],
+                "stats": [C.c_void_p, C.c_void_p], "free": [C.c_void_p]}
+
+    def __init__(self, device=0, **params):
+        self.n_cells = self.n_features = 0
+        self._open(device)
+        for k, v in params.items():
+            self.set_param(k, v)
+
+    def set_param(self, name, value):
+        if name in self.REALS:
+            self._call("set_real", name.encode(), float(value))
+        else:
+            super().set_param(name, self.METHODS[value] if name == "method" and isinstance(value, str) else value)
+
+    @staticmethod
+    def sgt(amb, active):
+        """br_cellcall_sgt (host only) -> (p float64, info: route, slope, active features, distinct counts)"""
+        L = lib()
+        L.br_cellcall_sgt.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        amb, active = np.ascontiguousarray(amb, dtype=np.uint64), np.ascontiguousarray(active, dtype=np.uint8)
+        p, info = np.zeros(max(len(amb), 1), np.float64), np.zeros(4, np.uint64)
+        check(L.br_cellcall_sgt(amb.ctypes.data, active.ctypes.data, len(amb), p.ctypes.data, info.ctypes.data), "br_cellcall_sgt")
+        return p[:len(amb)], {"route": int(info[0]), "slope": float(info[1:2].view(np.float64)[0]), "active": int(info[2]), "distinct": int(info[3])}
+
+    def run_raw(self, n_cells, n_features, cell_off, feature, count, on_device=False, stream=None):
+        """br_cellcall_run as it is (the tables as addresses) -> the return code"""
+        rc = self._raw("run", int(n_cells), int(n_features), C.c_void_p(cell_off), C.c_void_p(feature), C.c_void_p(count), 1 if on_device else 0,
+                       C.c_void_p(stream or 0))
+        if rc == 0:
+            self.n_cells, self.n_features = int(n_cells), int(n_features)
+        return rc
+
+    def run(self, cell_off, feature, count, n_features):
+        """The matrix as host arrays (cell_off uint64 [K + 1], feature uint32, count uint32)"""
+        off = np.ascontiguousarray(cell_off, dtype=np.uint64)
+        feat, cnt = np.ascontiguousarray(feature, dtype=np.uint32), np.ascontiguousarray(count, dtype=np.uint32)
+        check(self.run_raw(len(off) - 1, n_features, off.ctypes.data, feat.ctypes.data if feat.size else None, cnt.ctypes.data if cnt.size else None),
+              "br_cellcall_run")
+        return self
+
+    def run_device(self, cell_off, feature, count, n_features):
+        """The same tables as torch CUDA tensors (uint64 offsets as int64, uint32 as int32)"""
+        import torch
+        check(self.run_raw(cell_off.numel() - 1, n_features, cell_off.data_ptr(), feature.data_ptr(), count.data_ptr(), True,
+                           torch.cuda.current_stream(cell_off.device).cuda_stream), "br_cellcall_run")
+        return self
+
+    def calls(self, first=0, n=None):
+        """-> (status uint8, rank uint32, total uint64) per cell"""
+        n = self.n_cells - first if n is None else n
+        k = max(int(n), 1)
+        status, rank, total = np.zeros(k, np.uint8), np.zeros(k, np.uint32), np.zeros(k, np.uint64)
+        self._call("calls", int(first), int(n), status.ctypes.data, rank.ctypes.data, total.ctypes.data)
+        return status[:n], rank[:n], total[:n]
+
+    def ambient(self, first=0, n=None, counts_only=False):
+        """-> dict of per-feature arrays: amb (uint64), p, lp (float64), T (uint64)"""
+        n = self.n_features - first if n is None else n
+        k = max(int(n), 1)
+        amb, p, lp, T = np.zeros(k, np.uint64), np.zeros(k, np.float64), np.zeros(k, np.float64), np.zeros(k, np.uint64)
+        if counts_only:
+            self._call("ambient", int(first), int(n), amb.ctypes.data, None, None, None)
+            return {"amb": amb[:n]}
+        self._call("ambient", int(first), int(n), amb.ctypes.data, p.ctypes.data, lp.ctypes.data, T.ctypes.data)
+        return {"amb": amb[:n], "p": p[:n], "lp": lp[:n], "T": T[:n]}
+
+    def logtable(self):
+        """-> ln, float64 [n_max + 2] (empty without candidates)"""
+        st = self.stats()
+        n = st["n_max"] + 2 if st["candidates"] else 0
+        out = np.zeros(max(n, 1), np.float64)
+        self._call("logtable", 0, n, out.ctypes.data)
+        return out[:n]
+
+    def candidates(self):
+        """-> dict of per-candidate arrays in rank order: cell, O, lower, pval, padj"""
+        n = self.stats()["candidates"]
+        k = max(n, 1)
+        cell, O, lower = np.zeros(k, np.uint32), np.zeros(k, np.float64), np.zeros(k, np.uint32)
+        pval, padj = np.zeros(k, np.float64), np.zeros(k, np.float64)
+        self._call("candidates", 0, n, cell.ctypes.data, O.ctypes.data, lower.ctypes.data, pval.ctypes.data, padj.ctypes.data)
+        return {"cell": cell[:n], "O": O[:n], "lower": lower[:n], "pval": pval[:n], "padj": padj[:n]}
+
+    def wanted(self):
+        """-> the wanted totals, ascending (uint64)"""
+        n = self.stats()["wanted_totals"]
+        out = np.zeros(max(n, 1), np.uint64)
+        self._call("wanted", 0, n, out.ctypes.data)
+        return out[:n]
+
+    def sims(self, s_first=0, n_s=None, w_first=0, n_w=None):
+        """With "keep_sims" -> L float64 [n_w, n_s]: row w the wanted total w_first + w, column s the simulation s_first + s"""
+        st = self.stats()
+        n_s = st["sims"] - s_first if n_s is None else n_s
+        n_w = st["wanted_totals"] - w_first if n_w is None else n_w
+        out = np.zeros((max(int(n_w), 1), max(int(n_s), 1)), np.float64)
+        self._call("sims", int(s_first), int(n_s), int(w_first), int(n_w), out.ctypes.data)
+        return out[:n_w, :n_s]
+
+    def stats(self):
+        out = np.zeros(32, np.uint64)
+        self._call("stats", out.ctypes.data)
+        d = {k: int(v) for k, v in zip(self.STATS, out)}
+        d["slope"] = float(out[9:10].view(np.float64)[0])
+        return d

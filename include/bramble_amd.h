@@ -1304,6 +1304,98 @@ int br_cells_name_status(br_cells *, int64_t first, int64_t n, uint8_t *status);
 int br_cells_whitelist_stats(const br_cells *, uint64_t out[8]);
 int br_dedup_whitelist_stats(const br_dedup *, uint64_t out[8]);
 
+/* br_cellcall: which barcodes of a cell x feature count matrix are cells, in one device's HBM.  The three methods are MODELLED ON
+ * STARsolo's --soloCellFilter TopCells | CellRanger2.2 | EmptyDrops_CR; the definitions below are this library's own and are not
+ * claimed to give STARsolo's or CellRanger's sets (neither program was at hand to compare with).
+ *   matrix         K cells x F features as CSR by cell: cell_off (K + 1, cell_off[0] = 0), feature (ascending inside a cell) and
+ *                  count (> 0), in host or device memory.  total[c] = the sum of the cell's counts, below 2^32
+ *   rank           the cells sorted by the key (0xffffffff - total) << 32 | c: larger totals first, ties by ascending cell index.
+ *                  "total at rank r" below is the total of the cell at that place; K = 0 calls nothing
+ *   "method" 0     topcells: t = total at rank min("expected", K) - 1; called (status 1): every cell with total >= max(t, 1), ties
+ *                  at the threshold included
+ *   "method" 1     cr2.2, the `simple` filter, in float64 as written: r = min(K - 1, (int64)((double)expected * (1.0 - percentile))),
+ *                  tmax = total at rank r, tmin = max(1, (int64)((double)tmax / ratio + 0.5)); called (status 1): total >= tmin, the
+ *                  rank prefix of length n_simple
+ *   "method" 2     emptydrops: the simple filter first (status 1), then the steps below; where a step says `falls back` the result is
+ *                  the simple one and the stats' fallback word says why (1: empty window, 2: zero ambient sum, 3: no candidate)
+ *   ambient        amb[g] = the sum of count over the cells at ranks ["ind_min", min("ind_max", K)); an empty window or N = sum of amb
+ *                  = 0 falls back.  A feature is active if some cell of the matrix holds it
+ *   p              br_cellcall_sgt: Simple Good-Turing (Gale & Sampson 1995) over the active features, on the host in float64.  n_r =
+ *                  the active features with amb = r; r_1 < ... < r_m the values >= 1 that occur, r_0 = 0, r_{m+1} = 2 r_m - r_{m-1};
+ *                  Z_j = 2.0 * n_{r_j} / (r_{j+1} - r_{j-1}); x_j = log r_j, y_j = log Z_j; with all sums in ascending j: mx = (sum x) /
+ *                  m, my = (sum y) / m, b = (sum (x_j - mx)(y_j - my)) / (sum (x_j - mx)^2); y(r) = r * pow(1.0 + 1.0 / r, b + 1.0).
+ *                  Walking j upward, until switched: if r_j + 1 does not occur, switch; else x = (r + 1) * n_{r+1} / n_r, sd =
+ *                  sqrt((r + 1)^2 * (n_{r+1} / (n_r * n_r)) * (1.0 + n_{r+1} / n_r)); |x - y(r)| <= 1.96 sd: switch, else r* = x.
+ *                  From the switch on r* = y(r).  P0 = n_1 / N when a feature has count 1 and an active one has count 0, else 0; N' =
+ *                  sum of n_r r* (ascending j); p = (1 - P0) r* / N' for a count r >= 1 and P0 / n_0 for an active feature with count
+ *                  0; an inactive feature has p = 0.  m < 2 or not b < -1: add-one smoothing instead, p = (amb + 1) / (N + active
+ *                  features).  info: the route (0 Good-Turing, 1 add-one), the bits of b, the active features, m
+ *   tables         lp[g] = log(p[g]) of the active features (0 for the others; -inf where p is 0); ln[k] = log((double)k), k = 1 ..
+ *                  n_max + 1 (ln[0] = 0); cum_g = cum_{g-1} + p[g] over all features in index order, T[g] = (uint64)(cum_g / cum_last
+ *                  * 4294967296.0), the last active feature's and every later T = 2^32.  A 32-bit draw u picks the first g with u <
+ *                  T[g]: never an inactive feature
+ *   candidates     med = total at rank n_simple / 2, lo = max("umi_min", (int64)(umi_frac * (double)med + 0.5), 1): the cells at ranks
+ *                  >= n_simple with total >= lo, the first "cand_max" of them in rank order (m of them; none falls back).  n_max =
+ *                  the largest candidate total; the wanted totals = the distinct candidate totals, in ascending order
+ *   O_c            of a candidate: over the sequence that lists its first feature count_1 times, then its second, ...: from 0.0, step
+ *                  i (1-based) that lists feature g for the (k + 1)-th time adds ((ln[i] - ln[k + 1]) + lp[g])
+ *   L_s            of simulation s < "sims": draw i (0-based) is output word i & 3 of Philox4x32-10 with counter (i >> 2, s, 0, 2)
+ *                  under key ("seed" low, high word); it picks a feature by T; L_s is O's recurrence over the draws 0 .. n_max - 1,
+ *                  read off after every wanted total of draws
+ *   p-value        lower = #{ s : L_s(total_c) < O_c }; pval = (double)(lower + 1) / (double)(sims + 1)
+ *   padj           Benjamini-Hochberg over the m candidates sorted by (lower, rank) ascending: at the 1-based place j, q_j = min(1.0,
+ *                  pval * (double)m / (double)j); padj_j = the least q at j or behind.  Status 2 where padj <= "fdr"
+ * Every floating-point sum is one chain in the order given, without contraction, and no floating-point atomic is used: the same
+ * bits come out whatever "sim_bytes" is.
+ *
+ *   br_cellcall_set_param / _set_real   before run: "method", "expected" (3000), "ind_min" (45000), "ind_max" (90000), "umi_min" (500),
+ *                           "cand_max" (20000), "sims" (10000), "seed" (0), "sim_bytes" (2^31: the count tables of one launch; one
+ *                           simulation's table at least), "keep_sims" (0); reals "percentile" (0.99), "ratio" (10.0), "umi_frac"
+ *                           (0.01), "fdr" (0.01).  An unknown name, a value out of range, a call after run: BR_ERR_INVALID_ARG
+ *   br_cellcall_run         once.  on_device: the three tables are device memory, ready on `stream`.  Offsets that descend or do not
+ *                           start at 0, a feature >= n_features or not above the one before it, a count of 0, a total of 2^32 or
+ *                           more: BR_ERR_INVALID_ARG, and the object is as it was
+ *   br_cellcall_calls       cells [first, first + n): status (0, 1, 2), rank, total.  Here and below any pointer may be NULL
+ *   br_cellcall_ambient     features [first, first + n): amb, p, lp, T; BR_ERR_INVALID_ARG where the run made none (methods 0 and 1,
+ *                           an empty window; after a zero sum only amb)
+ *   br_cellcall_logtable    ln[first .. first + n) of its n_max + 2 entries
+ *   br_cellcall_candidates  candidates [first, first + n) in rank order: cell, O, lower, pval, padj
+ *   br_cellcall_wanted      the wanted totals [first, first + n)
+ *   br_cellcall_sims        with "keep_sims" 1: L of the wanted totals [w_first, w_first + n_w) x simulations [s_first, s_first + n_s),
+ *                           n_w rows of n_s; without it L is dropped when the p-values are made
+ *   br_cellcall_stats       K, cells of status 1, of status 2, the threshold (t or tmin), n_simple, the window's barcodes, N, active
+ *                           features, the route of p (2: none), the bits of b, lo, candidates, n_max, wanted totals, simulation
+ *                           launches, the fallback word, microseconds of rank, ambient, simulate, p-value, method, sims, device bytes
+ *                           held, device bytes at most, matrix entries, F
+ *   br_cellcall_sgt         the paragraph `p` alone, on the host: needs no device */
+typedef struct br_cellcall br_cellcall;
+int br_cellcall_new(int device, br_cellcall **out);
+int br_cellcall_set_param(br_cellcall *, const char *name, int64_t value);
+int br_cellcall_set_real(br_cellcall *, const char *name, double value);
+int br_cellcall_run(br_cellcall *, int64_t n_cells, int64_t n_features, const uint64_t *cell_off, const uint32_t *feature, const uint32_t *count,
+                    int on_device, void *stream);
+int br_cellcall_calls(br_cellcall *, int64_t first, int64_t n, uint8_t *status, uint32_t *rank, uint64_t *total);
+int br_cellcall_ambient(br_cellcall *, int64_t first, int64_t n, uint64_t *amb, double *p, double *lp, uint64_t *T);
+int br_cellcall_logtable(br_cellcall *, int64_t first, int64_t n, double *ln);
+int br_cellcall_candidates(br_cellcall *, int64_t first, int64_t n, uint32_t *cell, double *O, uint32_t *lower, double *pval, double *padj);
+int br_cellcall_wanted(br_cellcall *, int64_t first, int64_t n, uint64_t *total);
+int br_cellcall_sims(br_cellcall *, int64_t s_first, int64_t n_s, int64_t w_first, int64_t n_w, double *L);
+int br_cellcall_stats(const br_cellcall *, uint64_t out[32]);
+int br_cellcall_sgt(const uint64_t *amb, const uint8_t *active, int64_t n, double *p, uint64_t info[4]);
+void br_cellcall_free(br_cellcall *);
+/* Calling the cells of a br_cells.  With the parameter "call_counts" 1 (set before the first add) br_cells_finish also keeps the counts
+ * the cells are called on: the values of mode "unique" without the entries at 0, as 32-bit integers -- whatever "mode" is, as
+ * STARsolo ranks by its unique counts (in mode "unique" they are the matrix's own).  Without it finish launches and allocates
+ * nothing new.
+ *   br_cells_call           after finish, once: runs a br_cellcall of the same device that has its parameters and has not run on
+ *                           those device tables (n_features: the finish's), then copies the matrix's rows of the called cells
+ *                           (status != 0) on the device: a flag a cell, two scans, one launch, a wave a row.  Without
+ *                           "call_counts", before finish, a second time, a br_cellcall that has run: BR_ERR_INVALID_ARG
+ *   br_cells_matrix_called  after br_cells_call: the called cells [first, first + n) in cell order as br_cells_matrix returns cells --
+ *                           the "mode"'s values -- and `cells`, their indices; cell_off is required, the others may be NULL */
+int br_cells_call(br_cells *, br_cellcall *, int64_t n_features);
+int br_cells_matrix_called(br_cells *, int64_t first, int64_t n, uint32_t *cells, uint64_t *cell_off, uint32_t *feature, double *value);
+
 /* ---- SAM text out -------------------------------------------------------------------------- */
 
 /* The reference names RNAME and RNEXT print, in refID order (a refID < 0 or >= n prints '*'); uploaded to HBM once, kept by
