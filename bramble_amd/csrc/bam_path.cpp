@@ -101,7 +101,7 @@ extern "C" int br_project_bam_device(br_ctx *c, const br_config *cfg, const br_d
   c->last_n_aln = n; c->last_n_rows = 0;
   c->events_used = 0;
   Prof pf{c, st};
-  if (n == 0) { pf.collect(); return BR_OK; }
+  if (n == 0) { c->forget_last_call(st); pf.collect(); return BR_OK; }
 
   size_t nn = (size_t)n;
   RC(c->b_ref_id.ensure(nn * 4)); RC(c->b_ref_start.ensure(nn * 4)); RC(c->b_flags.ensure(nn * 2));
@@ -398,7 +398,7 @@ static int project_bam_staged_impl(br_ctx *c, const br_config *cfg, const br_bam
   auto t0 = std::chrono::steady_clock::now();
   HIPCHK(hipEventSynchronize(S.ready));
   const double wait_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (n == 0) return BR_OK;
+  if (n == 0) { c->forget_last_call(nullptr); return BR_OK; }   // a bundle without records: a call that leaves nothing behind
   br_device_records dr{S.blob.as<uint8_t>(), S.off.as<uint64_t>(), n, S.len.as<uint32_t>()};
   return project_bam_tail(c, cfg, &dr, bb->ref_map, bb->n_ref_map, out_mode_of(bb->bgzf_on_device), nowait, wait_ms, out);
 }
@@ -409,7 +409,7 @@ extern "C" int br_project_bam_resident(br_ctx *c, const br_config *cfg, const br
   memset(out, 0, sizeof(*out));
   HIPCHK(hipSetDevice(c->ix->device));
   out->total_processed = (uint64_t)recs->n_aln;
-  if (recs->n_aln == 0) return BR_OK;
+  if (recs->n_aln == 0) { c->forget_last_call(nullptr); return BR_OK; }
   return project_bam_tail(c, cfg, recs, ref_map, n_ref_map, out_mode_of(bgzf_on_device), nowait != 0, 0.0, out);
 }
 

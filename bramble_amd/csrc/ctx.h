@@ -163,6 +163,11 @@ struct br_ctx {
   br_device_bam last_bam{};   // the last bundle call's projected records in HBM, in every output mode (br_ctx_last_device_bam); a flat batch call has none
   // the last projection call's rows, read-name groups and stream, whichever entry point made it (br_quant_add_last); valid like the rows
   br_device_rows last_rows{}; const uint32_t *last_group_off = nullptr; int64_t last_n_groups = 0; hipStream_t last_stream = nullptr;
+  // a projection call begins: what the call before it left is no longer the last call's.  Every entry point says so before it can
+  // return, a call without alignments or records too: br_*_add_last after an empty bundle adds nothing, not the bundle before it again
+  void forget_last_call(hipStream_t st) {
+    last_rows = br_device_rows{}; last_group_off = nullptr; last_n_groups = 0; last_stream = st; last_bam = br_device_bam{};
+  }
   DevBuf fa_stats, fa_n_prob, fa_seq_bytes, fa_prob_off, fa_seqarena_off, fa_probs, fa_results, fa_seq_arena, fa_clip_ops,
       fa_ideal_cap, fa_scratch, fa_srcs, fa_want, b_seq_off, b_seqs, b_seq_src;
   // the streamed -S DP (ksw_kernels.hip): per-bin descriptors, per-problem DP results, leftovers, counters, group

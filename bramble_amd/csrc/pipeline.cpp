@@ -817,8 +817,7 @@ static int run_device_paths(br_ctx *c, const br_config *cfg, const br_device_bat
 }
 
 int run_device(br_ctx *c, const br_config *cfg, const br_device_batch *b, hipStream_t st, br_device_rows *out, bool keep_events) {
-  c->last_rows = br_device_rows{}; c->last_group_off = nullptr; c->last_n_groups = 0; c->last_stream = st;
-  c->last_bam = br_device_bam{};   // (a bundle call notes its records once they are encoded)
+  c->forget_last_call(st);   // (a bundle call notes its records once they are encoded)
   RC(run_device_paths(c, cfg, b, st, out, keep_events));
   if (out->row_off) { c->last_rows = *out; c->last_group_off = b->group_off; c->last_n_groups = b->n_groups; }   // (no rows table: an empty batch)
   return BR_OK;
