@@ -1,7 +1,9 @@
 // The host base of the run accumulators (br_collator, br_sorter, br_quant, br_coverage): objects that hold a whole run's data in
 // one device's HBM through new -> set_param -> add... -> finish -> read out -> free.  The base holds the device, the object's
 // stream and event and the count of the device bytes it holds; beside it, what more than one of them needs: the guard that drops
-// a call's tables, a timer, the scans' scratch size, the radix driver and the upload of a window of host rows.  Host only.
+// a call's tables, a timer, the scans' scratch size, the scan with its total read back, the radix driver, the upload of a window of
+// host rows, the growth of a record arena and the read-out of a table of 32-byte fields.  Host only.  (name_window.h: the front end of
+// the adds that take read names.)
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -9,6 +11,7 @@
 
 #include "collate_kernels.h"
 #include "devmem.h"
+#include "names.h"
 #include "scan_kernels.h"
 
 namespace br {
@@ -33,6 +36,11 @@ struct Accum {
     HIPCHK(hipSetDevice(dev));
     device = dev;
     return hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess ? BR_OK : BR_ERR_HIP;
+  }
+  // what br_*_new does after the new: the device, and `words` zeroed counters
+  int open(int dev, ColBuf &small, size_t words) {
+    RC(open(dev)); RC(alloc(small, words * 8));
+    return hipMemsetAsync(small.p, 0, words * 8, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess ? BR_OK : BR_ERR_HIP;
   }
   // what br_*_free does before the delete (an object that open refused has nothing to close)
   void close() {
@@ -62,6 +70,35 @@ struct Accum {
   // the stream's next work comes after whatever the caller's stream holds now (NULL: the null stream's work)
   int after(hipStream_t caller) {
     HIPCHK(hipEventRecord(ev, caller)); HIPCHK(hipStreamWaitEvent(st, ev, 0));
+    return BR_OK;
+  }
+
+  // room for `bytes` more behind the `used` bytes of a record arena, which keeps ARENA_SLACK behind its end: it grows by half, with
+  // what it held, and to no more than max_bytes (0: no cap but the device's memory)
+  int grow_arena(ColBuf &arena, uint64_t used, uint64_t bytes, uint64_t max_bytes) {
+    const uint64_t need = used + bytes;
+    if (max_bytes && need > max_bytes) return BR_ERR_CAPACITY;
+    if (need + ARENA_SLACK <= arena.cap) return BR_OK;
+    uint64_t want = std::max<uint64_t>(need + ARENA_SLACK, arena.cap + arena.cap / 2);
+    if (max_bytes) want = std::min<uint64_t>(want, max_bytes + ARENA_SLACK);
+    return alloc(arena, (size_t)want, true);
+  }
+
+  // flag (n items, then one more) scanned in place; -> its total.  tmp: made scan_tmp_bytes(n) at least; the stream is done
+  int scan_total(ColBuf &flag, int64_t n, ColBuf &tmp, uint64_t *total);
+
+  // n fields of a table from item `first` on: 32 bytes each from the words that hold them in comparison order, and the lengths
+  int fetch_fields(const ColBuf &words, const ColBuf &lens, int64_t first, int64_t n, uint8_t *out, uint8_t *len) {
+    if (n == 0) return BR_OK;
+    HIPCHK(hipSetDevice(device));
+    std::vector<uint64_t> w;
+    if (out) {
+      w.resize((size_t)n * 4);
+      HIPCHK(hipMemcpyAsync(w.data(), words.as<uint64_t>() + 4 * first, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+    }
+    if (len) HIPCHK(hipMemcpyAsync(len, lens.as<uint8_t>() + first, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (out) for (size_t i = 0; i < (size_t)n * 32; i++) out[i] = (uint8_t)(w[i >> 3] >> (56 - 8 * (i & 7)));
     return BR_OK;
   }
 
@@ -105,6 +142,19 @@ struct ScopeTimer {
 inline size_t scan_tmp_bytes(int64_t n) {
   const int64_t blocks = (n + 255) / 256, nh = 256 * ((n + COL_TILE - 1) / COL_TILE);
   return (size_t)std::max<int64_t>(2 * blocks + 2, scan_tiles_for(std::max<int64_t>(nh, n + 1))) * 8;
+}
+
+inline int Accum::scan_total(ColBuf &flag, int64_t n, ColBuf &tmp, uint64_t *total) {
+  RC(alloc(tmp, scan_tmp_bytes(n)));
+  launch_scan(st, flag.as<uint64_t>(), n, tmp.as<uint64_t>());
+  HIPCHK(hipMemcpyAsync(total, flag.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return BR_OK;
+}
+
+// [first, first + n) lies within [0, total)
+inline bool in_range(uint64_t total, int64_t first, int64_t n) {
+  return first >= 0 && n >= 0 && (uint64_t)first <= total && (uint64_t)n <= total - (uint64_t)first;
 }
 
 inline int Accum::radix_sort(ColBuf key[2], ColBuf idx[2], int64_t n, const uint64_t bits[2], const ColBuf &tmp, int *cur) {

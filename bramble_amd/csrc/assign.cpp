@@ -26,6 +26,7 @@
 #include "accum.h"
 #include "assign_kernels.h"
 #include "ctx.h"
+#include "name_window.h"
 #include "quant_kernels.h"
 #include "quant_view.h"
 #include "scan_kernels.h"
@@ -56,9 +57,7 @@ extern "C" int br_assign_new(int device, br_assign **out) {
   if (!out) return BR_ERR_INVALID_ARG;
   *out = nullptr;
   br_assign *c = new br_assign();
-  int rc = c->open(device);
-  if (!rc) rc = c->alloc(c->small, AS_WORDS * 8);
-  if (!rc && (hipMemsetAsync(c->small.p, 0, AS_WORDS * 8, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) rc = BR_ERR_HIP;
+  const int rc = c->open(device, c->small, AS_WORDS);
   if (rc) { br_assign_free(c); return rc; }
   *out = c;
   return BR_OK;
@@ -79,27 +78,21 @@ static int assign_reserve(br_assign *c, uint64_t m, uint64_t bytes, bool recs) {
   const size_t rn = (size_t)(c->n + m) + 1;
   if (rn * 16 > c->note.cap) RC(c->alloc(c->note, std::max(rn, (size_t)(c->note.cap / 16) * 3 / 2) * 16, true));
   if (!recs) return BR_OK;
-  const uint64_t need = c->used + bytes;
-  if (c->max_bytes && need > c->max_bytes) return BR_ERR_CAPACITY;
-  if (need + AS_ARENA_SLACK > c->arena.cap) {
-    uint64_t want = std::max<uint64_t>(need + AS_ARENA_SLACK, c->arena.cap + c->arena.cap / 2);
-    if (c->max_bytes) want = std::min<uint64_t>(want, c->max_bytes + AS_ARENA_SLACK);
-    RC(c->alloc(c->arena, (size_t)want, true));
-  }
+  RC(c->grow_arena(c->arena, c->used, bytes, c->max_bytes));
   if (rn * 8 > c->off.cap) RC(c->alloc(c->off, std::max(rn, (size_t)(c->off.cap / 8) * 3 / 2) * 8, true));
   return BR_OK;
 }
 
-// the rows [r0, r1) of the names A holds (a, the offsets and, with records, rec_off are set; data: the records' bytes from
-// rec_lo on, `bytes` of them, in host or device memory).  Nothing is counted before the kernels have accepted the add
-static int assign_add_rows(br_assign *c, AsAddArgs A, uint64_t r0, uint64_t r1, const uint8_t *data, uint64_t bytes, bool on_device) {
+// the rows of the names A holds (a, a_bias, names and, with records, recs are set; data: the records' bytes from the first row's
+// record on, `bytes` of them, in host or device memory).  Nothing is counted before the kernels have accepted the add
+static int assign_add_rows(br_assign *c, AsAddArgs A, const uint8_t *data, uint64_t bytes, bool on_device) {
   hipStream_t st = c->st;
-  const uint64_t m = r1 - r0;
-  const bool recs = A.rec_off != nullptr;
+  const uint64_t m = A.names.r_last - A.names.r_first;
+  const bool recs = A.recs.rec_off != nullptr;
   RC(assign_reserve(c, m, bytes, recs));
   uint64_t *small = c->small.as<uint64_t>();
   HIPCHK(hipMemsetAsync(small + AS_BAD_NAMES, 0, 16, st)); HIPCHK(hipMemsetAsync(small + AS_BAD_OFF, 0, 8, st));
-  A.r_first = r0; A.r_last = r1; A.name_base = c->n_names; A.arena_base = c->used;
+  A.name_base = c->n_names; A.arena_base = c->used;
   A.note = c->note.as<uint4>(); A.off = c->off.as<uint64_t>(); A.n0 = c->n; A.counters = c->small.as<unsigned long long>();
   if (recs && bytes) HIPCHK(hipMemcpyAsync(c->arena.as<uint8_t>() + c->used, data, (size_t)bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   launch_as_add(st, A);
@@ -111,46 +104,6 @@ static int assign_add_rows(br_assign *c, AsAddArgs A, uint64_t r0, uint64_t r1, 
   return BR_OK;
 }
 
-static int assign_add_host(br_assign *c, const br_device_bam *recs, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, uint64_t r0, uint64_t r1) {
-  const uint32_t a0 = group_off[0], a1 = group_off[ng];
-  uint64_t lo = 0, hi = 0;
-  if (recs) {
-    lo = recs->row_off[r0]; hi = recs->row_off[r1];
-    for (uint64_t r = r0; r < r1; r++) if (recs->row_off[r + 1] < recs->row_off[r]) return BR_ERR_INVALID_ARG;
-    if (hi < lo || hi > recs->n_bytes) return BR_ERR_INVALID_ARG;
-  }
-  RowWindow w;
-  ColBuf d_ro, d_go, d_rec;
-  DropGuard dropper{c, {&w.a, &w.cigar, &w.pool, &d_ro, &d_go, &d_rec}};
-  RC(c->upload_rows(rows, r0, r1, false, w));
-  RC(c->alloc(d_ro, (size_t)(a1 - a0 + 1) * 8)); RC(c->alloc(d_go, (size_t)(ng + 1) * 4));
-  HIPCHK(hipMemcpyAsync(d_ro.p, rows.row_off + a0, (size_t)(a1 - a0 + 1) * 8, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(d_go.p, group_off, (size_t)(ng + 1) * 4, hipMemcpyHostToDevice, c->st));
-  AsAddArgs A{};
-  A.a = w.a.as<uint4>(); A.a_bias = w.bias;
-  A.row_off = d_ro.as<uint64_t>(); A.ro_bias = (int64_t)a0; A.group_off = d_go.as<uint32_t>(); A.n_groups = ng;
-  if (recs) {
-    RC(c->alloc(d_rec, (size_t)(r1 - r0 + 1) * 8));
-    HIPCHK(hipMemcpyAsync(d_rec.p, recs->row_off + r0, (size_t)(r1 - r0 + 1) * 8, hipMemcpyHostToDevice, c->st));
-    A.rec_off = d_rec.as<uint64_t>(); A.rec_bias = (int64_t)r0;
-  }
-  return assign_add_rows(c, A, r0, r1, recs ? recs->data + lo : nullptr, hi - lo, false);   // (it waits for the stream: the uploads are done when the host arrays go)
-}
-
-static int assign_add_device(br_assign *c, const br_device_bam *recs, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, uint64_t r0, uint64_t r1) {
-  uint64_t ends[2] = {0, 0};
-  if (recs) {   // (after whatever made the records: the span's wait saw to it)
-    HIPCHK(hipMemcpyAsync(&ends[0], recs->row_off + r0, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipMemcpyAsync(&ends[1], recs->row_off + r1, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    if (ends[1] < ends[0] || ends[1] > recs->n_bytes) return BR_ERR_INVALID_ARG;
-  }
-  AsAddArgs A{};
-  A.a = (const uint4 *)rows.a; A.row_off = rows.row_off; A.group_off = group_off; A.n_groups = ng;
-  if (recs) A.rec_off = recs->row_off;
-  return assign_add_rows(c, A, r0, r1, recs ? recs->data + ends[0] : nullptr, ends[1] - ends[0], true);
-}
-
 extern "C" int br_assign_add(br_assign *c, const br_device_bam *recs, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups,
                              int on_device, void *stream) {
   if (!c || !rows || n_groups < 0 || c->dead || c->finished || (n_groups && (!rows->row_off || !group_off))) return BR_ERR_INVALID_ARG;
@@ -159,25 +112,25 @@ extern "C" int br_assign_add(br_assign *c, const br_device_bam *recs, const br_d
   if (n_groups == 0) { c->with_recs = recs ? 1 : 0; return BR_OK; }
   ScopeTimer timer(&c->add_s);
   HIPCHK(hipSetDevice(c->device));
-  // the names' rows
   uint64_t span[2] = {0, 0};
-  if (on_device) {
-    uint64_t *d_span = c->small.as<uint64_t>() + AS_CUT;
-    RC(c->after((hipStream_t)stream));   // after whatever made the rows
-    launch_q_span(c->st, rows->row_off, group_off, n_groups, d_span);
-    HIPCHK(hipMemcpyAsync(span, d_span, 16, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-  } else {
-    for (int64_t g = 0; g < n_groups; g++) if (group_off[g + 1] < group_off[g]) return BR_ERR_INVALID_ARG;
-    for (uint32_t i = group_off[0]; i < group_off[n_groups]; i++) if (rows->row_off[i + 1] < rows->row_off[i]) return BR_ERR_INVALID_ARG;
-    span[0] = rows->row_off[group_off[0]]; span[1] = rows->row_off[group_off[n_groups]];
-  }
-  if (span[1] < span[0] || span[1] > (uint64_t)rows->n_rows || (span[1] > span[0] && !rows->a)) return BR_ERR_INVALID_ARG;
+  RC(names_span(c, rows->row_off, (uint64_t)rows->n_rows, group_off, n_groups, on_device != 0, (hipStream_t)stream, c->small.as<uint64_t>() + AS_CUT, span));
+  if (span[1] > span[0] && !rows->a) return BR_ERR_INVALID_ARG;   // (the only table of the rows that is read)
   if (c->n_names + (uint64_t)n_groups >= (1ull << 32)) return BR_ERR_CAPACITY;
-  if (span[1] > span[0]) {
-    const int rc = on_device ? assign_add_device(c, recs, *rows, group_off, n_groups, span[0], span[1])
-                             : assign_add_host(c, recs, *rows, group_off, n_groups, span[0], span[1]);
-    if (rc) return rc;
+  if (span[1] > span[0]) {   // an empty span adds nothing; its names still count
+    RowWindow w;
+    ColBuf d_ro, d_go, d_rec;
+    DropGuard dropper{c, {&w.a, &w.cigar, &w.pool, &d_ro, &d_go, &d_rec}};
+    AsAddArgs A{};
+    const uint8_t *data = nullptr; uint64_t bytes = 0;
+    // the records are optional: without them recs.rec_off stays NULL (after whatever made them: the span's wait saw to it)
+    if (recs) RC(record_window(c, *recs, span[0], span[1], on_device != 0, d_rec, &A.recs, &data, &bytes));
+    if (on_device) { A.a = (const uint4 *)rows->a; A.names = device_names(rows->row_off, group_off, n_groups, span); }
+    else {
+      RC(c->upload_rows(*rows, span[0], span[1], false, w));
+      RC(upload_names(c, rows->row_off, group_off, n_groups, span, d_ro, d_go, &A.names));
+      A.a = w.a.as<uint4>(); A.a_bias = w.bias;
+    }
+    RC(assign_add_rows(c, A, data, bytes, on_device != 0));   // (it waits for the stream: the uploads are done when the host arrays go)
   }
   c->n_names += (uint64_t)n_groups;
   c->with_recs = recs ? 1 : 0;   // (an add that was refused decides nothing)
@@ -187,13 +140,11 @@ extern "C" int br_assign_add(br_assign *c, const br_device_bam *recs, const br_d
 extern "C" int br_assign_add_last(br_assign *c, br_ctx *ctx) {
   if (!c || !ctx || !ctx->ix || ctx->ix->device != c->device || c->dead || c->finished) return BR_ERR_INVALID_ARG;
   if (ctx->last_n_groups == 0) return BR_OK;   // a call without names
+  br_device_bam recs; bool flat;
+  last_call_records(ctx, &recs, &flat);
   // a flat batch call left rows and no records: only an object without records takes it (one without adds becomes that)
-  const bool flat = ctx->last_rows.n_rows && ctx->last_bam.n_rows != ctx->last_rows.n_rows;
   if (flat && c->with_recs == 1) return BR_ERR_INVALID_ARG;
-  if (flat || c->with_recs == 0) return br_assign_add(c, nullptr, &ctx->last_rows, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
-  br_device_bam recs = ctx->last_bam;
-  if (ctx->last_rows.n_rows == 0) recs = br_device_bam{};   // names without rows: no record stream was made
-  return br_assign_add(c, &recs, &ctx->last_rows, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
+  return br_assign_add(c, flat || c->with_recs == 0 ? nullptr : &recs, &ctx->last_rows, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
 }
 
 static int assign_finish(br_assign *c, const QuantView &v) {
@@ -254,7 +205,7 @@ extern "C" int br_assign_finish(br_assign *c, br_quant *q, int64_t *n_records_ou
 }
 
 extern "C" int br_assign_values(br_assign *c, int64_t first, int64_t n, double *w, float *zw, uint8_t *kept) {
-  if (!c || c->dead || !c->finished || first < 0 || n < 0 || (uint64_t)first > c->n || (uint64_t)n > c->n - (uint64_t)first) return BR_ERR_INVALID_ARG;
+  if (!c || c->dead || !c->finished || !in_range(c->n, first, n)) return BR_ERR_INVALID_ARG;
   if (n == 0) return BR_OK;
   HIPCHK(hipSetDevice(c->device));
   std::vector<double> tmp;

@@ -4,11 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "names.h"
+
 namespace br {
 
 constexpr uint32_t AS_M_LANE_MAX = 64;   // a name of up to this many records: a lane per record counts m; a longer one: a wave per name
 constexpr int AS_WRITE_LANES = 16;       // lanes per record of the write kernel
-constexpr uint64_t AS_ARENA_SLACK = 64;  // bytes the arena keeps behind its end: the write kernel reads whole aligned words
 constexpr uint32_t AS_TAG_BYTES = 7;     // 'Z' 'W' 'f' + float32
 // words of the counters
 enum { AS_BAD_NAMES = 0,    // add: a row the offsets give to no name
@@ -25,13 +26,12 @@ enum { AS_BAD_NAMES = 0,    // add: a row the offsets give to no name
 constexpr uint32_t AS_FIRST = 1u, AS_PAIRED = 2u;
 
 // One add: the rows [r_first, r_last) of the caller's table become the records [n0, n0 + r_last - r_first) of the object.  a may be
-// a slice: row r is at a[r - a_bias].  The names of the add as CovAddWArgs holds them.  rec_off (NULL: values only): the record
-// stream's offsets, row r's record is [rec_off[r], rec_off[r + 1]); its bytes are copied by the host, to arena_base on
+// a slice: row r is at a[r - a_bias].  The names and the records as names.h holds them: name g's add-order index is name_base + g;
+// recs.rec_off NULL: values only; recs.data is not read -- the host copies the records' bytes, to arena_base on
 struct AsAddArgs {
   const uint4 *a; int64_t a_bias;
-  uint64_t r_first, r_last;
-  const uint64_t *row_off; int64_t ro_bias; const uint32_t *group_off; int64_t n_groups; uint64_t name_base;
-  const uint64_t *rec_off; int64_t rec_bias; uint64_t arena_base;
+  NameWindow names; uint64_t name_base;
+  RecordWindow recs; uint64_t arena_base;
   uint4 *note;          // the object's, at [n0 + ...]
   uint64_t *off;        // likewise (r_last - r_first + 1 entries are written)
   uint64_t n0;

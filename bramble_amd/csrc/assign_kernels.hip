@@ -22,22 +22,18 @@ namespace br {
 namespace {
 // the add-order name of row r, from the add's offsets (name_of of coverage_kernels.hip); false where they do not give one
 __device__ __forceinline__ bool as_name_of(const AsAddArgs &A, uint64_t r, uint32_t &name) {
-  const uint32_t a0 = A.group_off[0], a1 = A.group_off[A.n_groups];
+  const NameWindow &N = A.names;
+  const uint32_t a0 = N.group_off[0], a1 = N.group_off[N.n_groups];
   if (a1 <= a0) return false;
-  const auto ro = [&](uint32_t a) { return A.row_off[(int64_t)a - A.ro_bias]; };
+  const auto ro = [&](uint32_t a) { return N.row_off[(int64_t)a - N.ro_bias]; };
   uint32_t lo = a0, hi = a1 - 1u;   // the last alignment of [a0, a1) whose rows begin at or in front of r
   while (lo < hi) { const uint32_t mid = lo + (hi - lo + 1u) / 2u; if (ro(mid) <= r) lo = mid; else hi = mid - 1u; }
   if (!(ro(lo) <= r && r < ro(lo + 1u))) return false;
-  int64_t glo = 0, ghi = A.n_groups - 1;   // the last name whose alignments begin at or in front of it
-  while (glo < ghi) { const int64_t mid = (glo + ghi + 1) >> 1; if (A.group_off[mid] <= lo) glo = mid; else ghi = mid - 1; }
-  if (!(A.group_off[glo] <= lo && lo < A.group_off[glo + 1])) return false;
+  int64_t glo = 0, ghi = N.n_groups - 1;   // the last name whose alignments begin at or in front of it
+  while (glo < ghi) { const int64_t mid = (glo + ghi + 1) >> 1; if (N.group_off[mid] <= lo) glo = mid; else ghi = mid - 1; }
+  if (!(N.group_off[glo] <= lo && lo < N.group_off[glo + 1])) return false;
   name = (uint32_t)(A.name_base + (uint64_t)glo);
   return true;
-}
-// one atomic a wave for a per-lane condition
-__device__ __forceinline__ void count_lanes(bool cond, unsigned long long *word) {
-  const uint64_t b = __ballot(cond);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(word, (unsigned long long)__popcll((unsigned long long)b));
 }
 // the first record of [lo, hi) whose name is >= g (hi when none): the names ascend with the records
 __device__ __forceinline__ uint64_t name_bound(const uint4 *note, uint64_t lo, uint64_t hi, uint64_t g) {
@@ -61,18 +57,18 @@ __device__ __forceinline__ uint32_t ld32(const uint8_t *p) { return ld16(p) | ld
 
 // ---- add -----------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_as_add(AsAddArgs A) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x, n = A.r_last - A.r_first;
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x, n = A.names.r_last - A.names.r_first;
   bool bad_name = false, bad_off = false;
   if (i < n) {
-    const uint64_t r = A.r_first + i;
+    const uint64_t r = A.names.r_first + i;
     const uint4 m = A.a[(int64_t)r - A.a_bias];
     uint32_t name = 0xffffffffu;
     if (!as_name_of(A, r, name)) { bad_name = true; name = 0xffffffffu; }
     const uint32_t bits = ((m.z & BR_ROW_FIRST) ? AS_FIRST : 0u) | ((m.z & BR_ROW_PAIRED) ? AS_PAIRED : 0u);
     A.note[A.n0 + i] = make_uint4(name, m.x, bits, 0u);
-    if (A.rec_off) {
-      const uint64_t *ro = A.rec_off - A.rec_bias;
-      const uint64_t first = ro[A.r_first], at = ro[r], next = ro[r + 1];
+    if (A.recs.rec_off) {
+      const uint64_t *ro = A.recs.rec_off - A.recs.rec_bias;
+      const uint64_t first = ro[A.names.r_first], at = ro[r], next = ro[r + 1];
       if (at < first || next < at) bad_off = true;
       A.off[A.n0 + i] = A.arena_base + (at - first);
       if (i == n - 1) A.off[A.n0 + n] = A.arena_base + (next - first);
@@ -343,7 +339,7 @@ __global__ void __launch_bounds__(256) k_as_write(AsWriteArgs W) {
 static dim3 grid_for(uint64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 void launch_as_add(hipStream_t st, const AsAddArgs &A) {
-  const uint64_t n = A.r_last - A.r_first;
+  const uint64_t n = A.names.r_last - A.names.r_first;
   if (!n) return;
   hipLaunchKernelGGL(k_as_add, grid_for(n), dim3(256), 0, st, A);
   hipLaunchKernelGGL(k_as_place, grid_for(n), dim3(256), 0, st, (const uint4 *)(A.note + A.n0), n, A.counters);

@@ -31,6 +31,7 @@
 #include "cellcall_kernels.h"
 #include "cells_kernels.h"
 #include "ctx.h"
+#include "name_window.h"
 #include "quant_kernels.h"
 #include "quant_view.h"
 #include "scan_kernels.h"
@@ -70,9 +71,7 @@ extern "C" int br_cells_new(int device, br_cells **out) {
   if (!out) return BR_ERR_INVALID_ARG;
   *out = nullptr;
   br_cells *c = new br_cells();
-  int rc = c->open(device);
-  if (!rc) rc = c->alloc(c->small, CL_WORDS * 8);
-  if (!rc && (hipMemsetAsync(c->small.p, 0, CL_WORDS * 8, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) rc = BR_ERR_HIP;
+  const int rc = c->open(device, c->small, CL_WORDS);
   if (rc) { br_cells_free(c); return rc; }
   *out = c;
   return BR_OK;
@@ -103,11 +102,11 @@ extern "C" int br_cells_set_tolerance(br_cells *c, double tolerance) {
   return BR_OK;
 }
 
-// the names of one add, their tables on the device (A: row_off, group_off, rec_off, their biases, r_first, r_last and n_groups are
-// set).  data: the records' bytes from the first row's record on, in host or device memory
-static int cells_add_names(br_cells *c, ClAddArgs A, const uint8_t *data, uint64_t bytes, uint64_t first_off, bool on_device) {
+// the names of one add, their tables on the device (A: names and recs but for recs.data are set).  data: the records' bytes from the
+// first row's record on, in host or device memory
+static int cells_add_names(br_cells *c, ClAddArgs A, const uint8_t *data, uint64_t bytes, bool on_device) {
   hipStream_t st = c->st;
-  const uint64_t ng = (uint64_t)A.n_groups;
+  const uint64_t ng = (uint64_t)A.names.n_groups;
   if (c->n + ng >= (1ull << 32)) return BR_ERR_CAPACITY;
   for (ColBuf *b : {&c->cb, &c->cblen}) {
     const size_t want = (size_t)(c->n + ng + 1) * (b == &c->cb ? 32 : 1);
@@ -117,13 +116,12 @@ static int cells_add_names(br_cells *c, ClAddArgs A, const uint8_t *data, uint64
   DropGuard dropper{c, {&window}};
   uint64_t *small = c->small.as<uint64_t>();
   HIPCHK(hipMemsetAsync(small + CL_BAD, 0, 4 * 8, st));   // CL_BAD .. CL_BAD_AUX
-  if (on_device) A.data = data;
-  else {
+  if (on_device) A.recs.data = data;   // nothing of a record is kept: the kernels read them where they are,
+  else {                               // or from a window that goes with the add
     RC(c->alloc(window, (size_t)bytes + 64));
     if (bytes) HIPCHK(hipMemcpyAsync(window.p, data, (size_t)bytes, hipMemcpyHostToDevice, st));
-    A.data = window.as<uint8_t>();
+    A.recs.data = window.as<uint8_t>();
   }
-  A.data_bias = first_off;
   A.where = c->barcode_source == 0 ? BC_NAME_PREV : BC_TAG; A.sep = c->barcode_sep; A.tag = c->barcode_tag;
   A.cb = c->cb.as<uint64_t>() + 4 * c->n; A.cblen = c->cblen.as<uint8_t>() + c->n;
   A.counters = c->small.as<unsigned long long>();
@@ -137,37 +135,6 @@ static int cells_add_names(br_cells *c, ClAddArgs A, const uint8_t *data, uint64
   return BR_OK;
 }
 
-static int cells_add_host(br_cells *c, const br_device_bam &recs, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, uint64_t r0, uint64_t r1) {
-  const uint32_t a0 = group_off[0], a1 = group_off[ng];
-  for (uint64_t r = r0; r < r1; r++) if (recs.row_off[r + 1] < recs.row_off[r]) return BR_ERR_INVALID_ARG;
-  const uint64_t lo = r1 > r0 ? recs.row_off[r0] : 0, hi = r1 > r0 ? recs.row_off[r1] : 0;   // (names without rows: no record is looked at)
-  if (hi < lo || hi > recs.n_bytes) return BR_ERR_INVALID_ARG;
-  ColBuf d_ro, d_go, d_rec;
-  DropGuard dropper{c, {&d_ro, &d_go, &d_rec}};
-  RC(c->alloc(d_ro, (size_t)(a1 - a0 + 1) * 8)); RC(c->alloc(d_go, (size_t)(ng + 1) * 4)); RC(c->alloc(d_rec, (size_t)(r1 - r0 + 1) * 8));
-  HIPCHK(hipMemcpyAsync(d_ro.p, rows.row_off + a0, (size_t)(a1 - a0 + 1) * 8, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(d_go.p, group_off, (size_t)(ng + 1) * 4, hipMemcpyHostToDevice, c->st));
-  if (r1 > r0) HIPCHK(hipMemcpyAsync(d_rec.p, recs.row_off + r0, (size_t)(r1 - r0 + 1) * 8, hipMemcpyHostToDevice, c->st));
-  ClAddArgs A{};
-  A.row_off = d_ro.as<uint64_t>(); A.ro_bias = (int64_t)a0; A.group_off = d_go.as<uint32_t>(); A.n_groups = ng; A.r_first = r0; A.r_last = r1;
-  A.rec_off = d_rec.as<uint64_t>(); A.rec_bias = (int64_t)r0;
-  return cells_add_names(c, A, r1 > r0 ? recs.data + lo : nullptr, hi - lo, lo, false);   // (it waits for the stream)
-}
-
-static int cells_add_device(br_cells *c, const br_device_bam &recs, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, uint64_t r0, uint64_t r1) {
-  uint64_t ends[2] = {0, 0};
-  if (r1 > r0) {   // (names without rows: no record is looked at)
-    HIPCHK(hipMemcpyAsync(&ends[0], recs.row_off + r0, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipMemcpyAsync(&ends[1], recs.row_off + r1, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-  }
-  if (ends[1] < ends[0] || ends[1] > recs.n_bytes) return BR_ERR_INVALID_ARG;
-  ClAddArgs A{};
-  A.row_off = rows.row_off; A.group_off = group_off; A.n_groups = ng; A.r_first = r0; A.r_last = r1;
-  A.rec_off = recs.row_off;
-  return cells_add_names(c, A, r1 > r0 ? recs.data + ends[0] : nullptr, ends[1] - ends[0], ends[0], true);
-}
-
 extern "C" int br_cells_add(br_cells *c, const br_device_bam *recs, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups,
                             int on_device, void *stream) {
   if (!c || !recs || !rows || n_groups < 0 || c->dead || c->finished || (n_groups && (!rows->row_off || !group_off))) return BR_ERR_INVALID_ARG;
@@ -177,21 +144,15 @@ extern "C" int br_cells_add(br_cells *c, const br_device_bam *recs, const br_dev
   ScopeTimer timer(&c->add_s);
   HIPCHK(hipSetDevice(c->device));
   uint64_t span[2] = {0, 0};
-  if (on_device) {
-    uint64_t *d_span = c->small.as<uint64_t>() + CL_SPAN;
-    RC(c->after((hipStream_t)stream));   // after whatever made the rows
-    launch_q_span(c->st, rows->row_off, group_off, n_groups, d_span);
-    HIPCHK(hipMemcpyAsync(span, d_span, 16, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-  } else {
-    for (int64_t g = 0; g < n_groups; g++) if (group_off[g + 1] < group_off[g]) return BR_ERR_INVALID_ARG;
-    for (uint32_t i = group_off[0]; i < group_off[n_groups]; i++) if (rows->row_off[i + 1] < rows->row_off[i]) return BR_ERR_INVALID_ARG;
-    span[0] = rows->row_off[group_off[0]]; span[1] = rows->row_off[group_off[n_groups]];
-  }
-  if (span[1] < span[0] || span[1] > (uint64_t)rows->n_rows) return BR_ERR_INVALID_ARG;
-  const int rc = on_device ? cells_add_device(c, *recs, *rows, group_off, n_groups, span[0], span[1])
-                           : cells_add_host(c, *recs, *rows, group_off, n_groups, span[0], span[1]);
-  if (rc) return rc;
+  RC(names_span(c, rows->row_off, (uint64_t)rows->n_rows, group_off, n_groups, on_device != 0, (hipStream_t)stream, c->small.as<uint64_t>() + CL_SPAN, span));
+  ColBuf d_ro, d_go, d_rec;   // (host tables only; the rows themselves are not looked at)
+  DropGuard dropper{c, {&d_ro, &d_go, &d_rec}};
+  ClAddArgs A{};
+  const uint8_t *data; uint64_t bytes;
+  RC(record_window(c, *recs, span[0], span[1], on_device != 0, d_rec, &A.recs, &data, &bytes));
+  if (on_device) A.names = device_names(rows->row_off, group_off, n_groups, span);
+  else RC(upload_names(c, rows->row_off, group_off, n_groups, span, d_ro, d_go, &A.names));
+  RC(cells_add_names(c, A, data, bytes, on_device != 0));   // (it waits for the stream)
   c->added = true;   // (an add that was refused decides nothing)
   return BR_OK;
 }
@@ -199,23 +160,14 @@ extern "C" int br_cells_add(br_cells *c, const br_device_bam *recs, const br_dev
 extern "C" int br_cells_add_last(br_cells *c, br_ctx *ctx) {
   if (!c || !ctx || !ctx->ix || ctx->ix->device != c->device || c->dead || c->finished) return BR_ERR_INVALID_ARG;
   if (ctx->last_n_groups == 0) return BR_OK;   // a call without names
-  if (ctx->last_rows.n_rows && ctx->last_bam.n_rows != ctx->last_rows.n_rows) return BR_ERR_INVALID_ARG;   // a flat batch call left no records
-  br_device_bam recs = ctx->last_bam;
-  if (ctx->last_rows.n_rows == 0) recs = br_device_bam{};   // names without rows: no record stream was made
+  br_device_bam recs; bool flat;
+  last_call_records(ctx, &recs, &flat);
+  if (flat) return BR_ERR_INVALID_ARG;   // a flat batch call left no records
   return br_cells_add(c, &recs, &ctx->last_rows, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
 }
 
 // the radix sort of (key[0], idx[0]) over the digits in which the keys differ (barcode_sort.h)
 static int cells_sort(br_cells *c, SortBufs &s, int64_t n, ColBuf &tmp) { return sort_pairs(c, s, n, tmp, c->small.as<uint64_t>() + CL_BITS); }
-
-// flag (n items, then one more) scanned in place; -> its total
-static int cells_scan(br_cells *c, ColBuf &flag, int64_t n, ColBuf &tmp, uint64_t *total) {
-  RC(c->alloc(tmp, scan_tmp_bytes(n)));
-  launch_scan(c->st, flag.as<uint64_t>(), n, tmp.as<uint64_t>());
-  HIPCHK(hipMemcpyAsync(total, flag.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return BR_OK;
-}
 
 static int cells_finish(br_cells *c, const QuantClassView &V, const uint32_t *tx_feature) {
   hipStream_t st = c->st;
@@ -235,21 +187,21 @@ static int cells_finish(br_cells *c, const QuantClassView &V, const uint32_t *tx
   uint64_t M = 0;
   RC(c->alloc(flag, n1 * 8));
   launch_cl_flag(st, c->cblen.as<uint8_t>(), V.name_cls, N, flag.as<uint64_t>());
-  RC(cells_scan(c, flag, N, tmp, &M));
+  RC(c->scan_total(flag, N, tmp, &M));
   c->n_counted = M;
   if (M == 0) return BR_OK;
   if (M > (uint64_t)N) return BR_ERR_HIP;
   const int64_t n = (int64_t)M;
   RC(s.make(c, (size_t)M));
-  launch_cl_compact(st, flag.as<uint64_t>(), N, s.idx[0].as<uint32_t>());
+  launch_bc_compact(st, flag.as<uint64_t>(), N, s.idx[0].as<uint32_t>());
   // cells: by (length, bytes), least significant word first, every sort stable
   const uint64_t *cb = c->cb.as<uint64_t>();
   const uint8_t *cblen = c->cblen.as<uint8_t>();
-  RC(sort_by_barcode(c, s, cb, cblen, n, tmp, small + CL_BITS));
+  RC(sort_by_barcode(c, s, cb, cblen, nullptr, n, tmp, small + CL_BITS));
   uint64_t K = 0;
   RC(c->alloc(flag, ((size_t)M + 1) * 8));
-  launch_cl_bheads(st, s.idx[0].as<uint32_t>(), cb, cblen, n, flag.as<uint64_t>());
-  RC(cells_scan(c, flag, n, tmp, &K));
+  launch_bc_heads(st, s.idx[0].as<uint32_t>(), cb, cblen, nullptr, 0, n, flag.as<uint64_t>());
+  RC(c->scan_total(flag, n, tmp, &K));
   if (K == 0 || K > M) return BR_ERR_HIP;
   const size_t k1 = (size_t)K + 1;
   RC(c->alloc(c->cell_cb, k1 * 32)); RC(c->alloc(c->cell_len, k1));
@@ -259,7 +211,7 @@ static int cells_finish(br_cells *c, const QuantClassView &V, const uint32_t *tx
   RC(cells_sort(c, s, n, tmp));
   launch_qg_flag(st, s.key[0].as<uint64_t>(), n, flag.as<uint64_t>());
   uint64_t E = 0;
-  RC(cells_scan(c, flag, n, tmp, &E));
+  RC(c->scan_total(flag, n, tmp, &E));
   if (E < K || E > M) return BR_ERR_HIP;
   const size_t e1 = (size_t)E + 1;
   ColBuf ebeg, e_cell, e_cls, e_n, pair_off, cell_eoff, cell_soff, d_txf, glab, goff, gk;
@@ -278,7 +230,7 @@ static int cells_finish(br_cells *c, const QuantClassView &V, const uint32_t *tx
     RC(c->alloc(pos, l1 * 8));
     launch_qg_flag(st, ls.key[0].as<uint64_t>(), L, pos.as<uint64_t>());
     uint64_t LE = 0;
-    RC(cells_scan(c, pos, L, tmp, &LE));
+    RC(c->scan_total(pos, L, tmp, &LE));
     if (LE == 0 || LE > (uint64_t)L) return BR_ERR_HIP;
     RC(c->alloc(glab, ((size_t)LE + 1) * 4)); RC(c->alloc(goff, c1 * 8)); RC(c->alloc(gk, c1 * 4));
     launch_qg_arena(st, ls.key[0].as<uint64_t>(), pos.as<uint64_t>(), V.label_off, L, C, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>());
@@ -290,7 +242,7 @@ static int cells_finish(br_cells *c, const QuantClassView &V, const uint32_t *tx
   launch_cl_entries(st, s.key[0].as<uint64_t>(), ebeg.as<uint64_t>(), (int64_t)E, (int64_t)K, gk.as<uint32_t>(), e_cell.as<uint32_t>(), e_cls.as<uint32_t>(),
                     e_n.as<uint32_t>(), pair_off.as<uint64_t>(), cell_eoff.as<uint64_t>());
   uint64_t P = 0;
-  RC(cells_scan(c, pair_off, (int64_t)E, tmp, &P));
+  RC(c->scan_total(pair_off, (int64_t)E, tmp, &P));
   if (P < E) return BR_ERR_HIP;   // (every class has a label, so every entry a feature)
   if (P >= (1ull << 32)) return BR_ERR_CAPACITY;
   c->drop(ebeg);
@@ -306,7 +258,7 @@ static int cells_finish(br_cells *c, const QuantClassView &V, const uint32_t *tx
   RC(c->alloc(flag, p1 * 8));
   launch_qg_flag(st, s.key[0].as<uint64_t>(), (int64_t)P, flag.as<uint64_t>());
   uint64_t S = 0;
-  RC(cells_scan(c, flag, (int64_t)P, tmp, &S));
+  RC(c->scan_total(flag, (int64_t)P, tmp, &S));
   if (S < K || S > P) return BR_ERR_HIP;
   const size_t s1 = (size_t)S + 1;
   RC(c->alloc(sbeg, s1 * 8)); RC(c->alloc(s_feat, s1 * 4)); RC(c->alloc(val, s1 * 8));
@@ -352,7 +304,7 @@ static int cells_finish(br_cells *c, const QuantClassView &V, const uint32_t *tx
   RC(c->alloc(flag, s1 * 8));
   launch_cl_keep(st, val.as<double>(), (int64_t)S, c->mode == 0, flag.as<uint64_t>());
   uint64_t Z = 0;
-  RC(cells_scan(c, flag, (int64_t)S, tmp, &Z));
+  RC(c->scan_total(flag, (int64_t)S, tmp, &Z));
   if (Z > S) return BR_ERR_HIP;
   RC(c->alloc(c->m_off, k1 * 8)); RC(c->alloc(c->m_feat, ((size_t)Z + 1) * 4)); RC(c->alloc(c->m_val, ((size_t)Z + 1) * 8));
   launch_cl_matrix(st, T, flag.as<uint64_t>(), (int64_t)S, s_feat.as<uint32_t>(), val.as<double>(), c->m_off.as<uint64_t>(), c->m_feat.as<uint32_t>(),
@@ -367,7 +319,7 @@ static int cells_finish(br_cells *c, const QuantClassView &V, const uint32_t *tx
       RC(c->alloc(nf, k1 * 4));
       launch_cl_unique(st, T, (int64_t)S, val.as<double>());   // (the mode's values are in the matrix by now)
       launch_cl_keep(st, val.as<double>(), (int64_t)S, 1, flag.as<uint64_t>());
-      RC(cells_scan(c, flag, (int64_t)S, tmp, &U));
+      RC(c->scan_total(flag, (int64_t)S, tmp, &U));
       if (U > S) return BR_ERR_HIP;
       RC(c->alloc(c->u_off, k1 * 8)); RC(c->alloc(c->u_feat, ((size_t)U + 1) * 4));
       RC(c->alloc(uval, ((size_t)U + 1) * 8));
@@ -406,33 +358,14 @@ extern "C" int br_cells_finish(br_cells *c, br_quant *quant, const uint32_t *tx_
   return BR_OK;
 }
 
-static bool in_range(uint64_t total, int64_t first, int64_t n) {
-  return first >= 0 && n >= 0 && (uint64_t)first <= total && (uint64_t)n <= total - (uint64_t)first;
-}
-
-// n x 32 bytes from the words that hold them in comparison order, and the lengths
-static int cells_fetch_barcodes(br_cells *c, const ColBuf &words_buf, const ColBuf &len_buf, int64_t first, int64_t n, uint8_t *cb, uint8_t *len) {
-  if (n == 0) return BR_OK;
-  HIPCHK(hipSetDevice(c->device));
-  std::vector<uint64_t> words;
-  if (cb) {
-    words.resize((size_t)n * 4);
-    HIPCHK(hipMemcpyAsync(words.data(), words_buf.as<uint64_t>() + 4 * first, (size_t)n * 32, hipMemcpyDeviceToHost, c->st));
-  }
-  if (len) HIPCHK(hipMemcpyAsync(len, len_buf.as<uint8_t>() + first, (size_t)n, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  if (cb) for (size_t i = 0; i < (size_t)n * 32; i++) cb[i] = (uint8_t)(words[i >> 3] >> (56 - 8 * (i & 7)));
-  return BR_OK;
-}
-
 extern "C" int br_cells_barcodes(br_cells *c, int64_t first, int64_t n, uint8_t *cb, uint8_t *len) {
   if (!c || c->dead || !in_range(c->n, first, n)) return BR_ERR_INVALID_ARG;
-  return cells_fetch_barcodes(c, c->cb, c->cblen, first, n, cb, len);
+  return c->fetch_fields(c->cb, c->cblen, first, n, cb, len);
 }
 
 extern "C" int br_cells_cell_barcodes(br_cells *c, int64_t first, int64_t n, uint8_t *cb, uint8_t *len) {
   if (!c || c->dead || !c->finished || !in_range(c->n_cells, first, n)) return BR_ERR_INVALID_ARG;
-  return cells_fetch_barcodes(c, c->cell_cb, c->cell_len, first, n, cb, len);
+  return c->fetch_fields(c->cell_cb, c->cell_len, first, n, cb, len);
 }
 
 extern "C" int br_cells_name_cells(br_cells *c, int64_t first, int64_t n, uint32_t *cell) {
@@ -454,11 +387,7 @@ extern "C" int br_cells_name_status(br_cells *c, int64_t first, int64_t n, uint8
 }
 
 extern "C" int br_cells_whitelist_stats(const br_cells *c, uint64_t out[8]) {
-  if (!c || !out || !c->wl) return BR_ERR_INVALID_ARG;
-  const WlResolved &r = c->wl_res;
-  const uint64_t v[8] = {r.status[0], r.status[1], r.status[2], r.status[3], r.status[4], r.distinct, (uint64_t)(r.seconds * 1e6), (uint64_t)c->wl_correct};
-  memcpy(out, v, sizeof(v));
-  return BR_OK;
+  return c && c->wl ? wl_stats(c->wl_res, c->wl_correct, out) : BR_ERR_INVALID_ARG;
 }
 
 extern "C" int br_cells_matrix(br_cells *c, int64_t first_cell, int64_t n, uint64_t *cell_off, uint32_t *feature, double *value) {
@@ -495,8 +424,8 @@ extern "C" int br_cells_call(br_cells *c, br_cellcall *cc, int64_t n_features) {
   HIPCHK(hipMemsetAsync(len.p, 0, k1 * 8, st));
   launch_cc_called(st, status, c->m_off.as<uint64_t>(), K, flag.as<uint64_t>(), len.as<uint64_t>());
   uint64_t got = 0, Zc = 0;
-  RC(cells_scan(c, flag, K, tmp, &got));
-  RC(cells_scan(c, len, K, tmp, &Zc));
+  RC(c->scan_total(flag, K, tmp, &got));
+  RC(c->scan_total(len, K, tmp, &Zc));
   if (got != n_called || Zc > c->n_matrix) return BR_ERR_HIP;
   RC(c->alloc(c->f_off, ((size_t)got + 1) * 8)); RC(c->alloc(c->f_cells, ((size_t)got + 1) * 4));
   RC(c->alloc(c->f_feat, ((size_t)Zc + 1) * 4)); RC(c->alloc(c->f_val, ((size_t)Zc + 1) * 8));

@@ -4,12 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "names.h"
+
 namespace br {
 
 constexpr uint32_t CL_WAVE_ITEMS = 64;   // a cell of up to this many slots and pairs is one wave's work; a longer list is summed by the wave
 constexpr uint32_t CL_LDS_HEAD = 64;     // bytes of a block cell's LDS in front of theta, theta' and q (the block's reduction)
 constexpr uint32_t CL_LDS_MAX = 65536;   // the largest "lds_bytes"
-constexpr uint32_t CL_MIN_RECORD = 36;   // [block_size] and the fixed fields of a record
 // words of the counters
 enum { CL_BAD = 0,        // add: offsets that descend, a record shorter than its fixed fields
        CL_NO_BC = 1, CL_TOO_LONG = 2, CL_BAD_AUX = 3,   // add: the names with rows the barcode parse counted
@@ -19,12 +20,9 @@ enum { CL_BAD = 0,        // add: offsets that descend, a record shorter than it
        CL_NEED = 11,      // finish: the most LDS bytes a block-route cell asks for
        CL_WORDS = 16 };
 
-// One add: the names [0, n_groups) of the add, their rows [r_first, r_last).  row_off may be a slice: element i is at [i - ro_bias];
-// row r's record lies at data[rec_off[r - rec_bias] - data_bias ...): [block_size][record].
+// One add: the names of the add and their records, as names.h holds them
 struct ClAddArgs {
-  const uint64_t *row_off; int64_t ro_bias; const uint32_t *group_off; int64_t n_groups;
-  uint64_t r_first, r_last;
-  const uint8_t *data; uint64_t data_bias; const uint64_t *rec_off; int64_t rec_bias;
+  NameWindow names; RecordWindow recs;
   int where; uint32_t sep, tag;        // barcode_inl.h
   uint64_t *cb; uint8_t *cblen;        // per name, at the add's first name: four words, the length
   unsigned long long *counters;
@@ -33,12 +31,6 @@ void launch_cl_add(hipStream_t st, const ClAddArgs &A);
 
 // finish.  flag[i] = name i counts: it has a barcode and a class
 void launch_cl_flag(hipStream_t st, const uint8_t *cblen, const uint32_t *name_cls, int64_t n, uint64_t *flag);
-// idx[pos[i]] = i for the names that count (pos: the scanned flags)
-void launch_cl_compact(hipStream_t st, const uint64_t *pos, int64_t n, uint32_t *idx);
-// key[j] = word w of the barcode of idx[j], bytes in comparison order (w = 0 .. 3); w = 4: its length
-void launch_cl_bkey(hipStream_t st, const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, int64_t n, int w, uint64_t *key);
-// head[j] = sorted item j starts a cell: its barcode differs from item j - 1's
-void launch_cl_bheads(hipStream_t st, const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, int64_t n, uint64_t *head);
 // cid: the scanned heads (n + 1).  name_cell[idx[j]] = the cell of item j; the cell's barcode from its first item; key[j] = cell << 32 |
 // class of idx[j], to be sorted
 void launch_cl_cells(hipStream_t st, const uint64_t *cid, const uint32_t *idx, int64_t n, const uint64_t *cb, const uint8_t *cblen,

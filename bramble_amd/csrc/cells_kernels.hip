@@ -2,9 +2,9 @@
 // bramble_amd.h, br_cells).
 //
 //   add      k_cl_rows: a lane per row checks its record's offsets; k_cl_names: a lane per name reads the barcode of its first record
-//   finish   k_cl_flag + scan + k_cl_compact: the names that count; radix sorts over k_cl_bkey, k_cl_bheads + scan, k_cl_cells: the
-//            cells; a sort of (cell, class), k_qg_flag + scan, k_cl_entries: the entries; k_cl_pairs, a stable sort of (cell, feature),
-//            k_qg_flag + scan, k_cl_transpose, k_cl_slots: the slots and the per-slot lists; k_cl_route; k_cl_em or k_cl_unique;
+//   finish   k_cl_flag + scan + the field sort's compact: the names that count; the field sort (barcode_sort.h), its heads + scan,
+//            k_cl_cells: the cells; a sort of (cell, class), k_qg_flag + scan, k_cl_entries: the entries; k_cl_pairs, a stable sort
+//            of (cell, feature), k_qg_flag + scan, k_cl_transpose, k_cl_slots: the slots and the per-slot lists; k_cl_route; k_cl_em or k_cl_unique;
 //            k_cl_cell_stats, k_cl_keep + scan, k_cl_matrix
 //
 // No floating-point atomic anywhere.  The integer atomics count lanes and append cells to the route lists, whose order no result
@@ -14,45 +14,33 @@
 #include "../../include/bramble_amd.h"
 #include "barcode_inl.h"
 #include "cells_kernels.h"
+#include "names_inl.h"
 #include "wave_inl.h"
 
 namespace br {
 
 namespace {
 unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
-__device__ __forceinline__ void count_lanes(bool cond, unsigned long long *word) {
-  const uint64_t b = __ballot(cond);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(word, (unsigned long long)__popcll((unsigned long long)b));
-}
-// row r's record: false where its offsets descend, leave the add's bytes or are too close for the fixed fields
-__device__ __forceinline__ bool record_of(const ClAddArgs &A, uint64_t r, const uint8_t *&rec, uint64_t &len) {
-  const uint64_t *ro = A.rec_off - A.rec_bias;
-  const uint64_t first = ro[A.r_first], last = ro[A.r_last], at = ro[r], next = ro[r + 1];
-  if (at < first || next < at || next > last || next - at < (uint64_t)CL_MIN_RECORD) return false;
-  rec = A.data + (at - A.data_bias); len = next - at;
-  return true;
-}
 }  // namespace
 
 // ---- add -----------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_cl_rows(ClAddArgs A) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x, n = A.r_last - A.r_first;
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x, n = A.names.r_last - A.names.r_first;
   bool bad = false;
-  if (i < n) { const uint8_t *rec; uint64_t len; bad = !record_of(A, A.r_first + i, rec, len); }
+  if (i < n) { const uint8_t *rec; uint64_t len; bad = !record_of(A.names, A.recs, A.names.r_first + i, rec, len); }
   if (__ballot(bad) && bad) A.counters[CL_BAD] = 1;
 }
 
 __global__ void __launch_bounds__(256) k_cl_names(ClAddArgs A) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   bool is_bad = false, none = false, too_long = false, bad_aux = false;
-  if (g < A.n_groups) {
-    uint64_t w[4] = {0, 0, 0, 0};
+  if (g < A.names.n_groups) {
+    uint64_t r0, r1, w[4] = {0, 0, 0, 0};
     uint32_t l = 0;
-    const uint64_t r0 = A.row_off[(int64_t)A.group_off[g] - A.ro_bias], r1 = A.row_off[(int64_t)A.group_off[g + 1] - A.ro_bias];
-    if (!(r0 >= A.r_first && r1 <= A.r_last && r0 <= r1)) is_bad = true;
+    if (!name_rows(A.names, g, r0, r1)) is_bad = true;
     else if (r1 > r0) {
       const uint8_t *rec; uint64_t len;
-      if (record_of(A, r0, rec, len)) { l = record_field(rec, len, A.where, A.sep, A.tag, w, too_long, bad_aux); none = l == 0u; }
+      if (record_of(A.names, A.recs, r0, rec, len)) { l = record_field(rec, len, A.where, A.sep, A.tag, w, too_long, bad_aux); none = l == 0u; }
     }
 #pragma unroll
     for (int k = 0; k < 4; k++) A.cb[4 * g + k] = w[k];
@@ -65,9 +53,9 @@ __global__ void __launch_bounds__(256) k_cl_names(ClAddArgs A) {
 }
 
 void launch_cl_add(hipStream_t st, const ClAddArgs &A) {
-  const uint64_t n = A.r_last - A.r_first;
+  const uint64_t n = A.names.r_last - A.names.r_first;
   if (n) hipLaunchKernelGGL(k_cl_rows, dim3(blocks256((int64_t)n)), dim3(256), 0, st, A);
-  if (A.n_groups > 0) hipLaunchKernelGGL(k_cl_names, dim3(blocks256(A.n_groups)), dim3(256), 0, st, A);
+  if (A.names.n_groups > 0) hipLaunchKernelGGL(k_cl_names, dim3(blocks256(A.names.n_groups)), dim3(256), 0, st, A);
 }
 
 // ---- finish: cells, entries, slots ---------------------------------------------------------------------------------------------
@@ -77,39 +65,6 @@ __global__ void __launch_bounds__(256) k_cl_flag(const uint8_t *cblen, const uin
 }
 void launch_cl_flag(hipStream_t st, const uint8_t *cblen, const uint32_t *name_cls, int64_t n, uint64_t *flag) {
   if (n > 0) hipLaunchKernelGGL(k_cl_flag, dim3(blocks256(n)), dim3(256), 0, st, cblen, name_cls, n, flag);
-}
-
-__global__ void __launch_bounds__(256) k_cl_compact(const uint64_t *pos, int64_t n, uint32_t *idx) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n && pos[i + 1] != pos[i]) idx[pos[i]] = (uint32_t)i;
-}
-void launch_cl_compact(hipStream_t st, const uint64_t *pos, int64_t n, uint32_t *idx) {
-  if (n > 0) hipLaunchKernelGGL(k_cl_compact, dim3(blocks256(n)), dim3(256), 0, st, pos, n, idx);
-}
-
-__global__ void __launch_bounds__(256) k_cl_bkey(const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, int64_t n, int w, uint64_t *key) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t i = idx[j];
-  key[j] = w < 4 ? cb[4 * (uint64_t)i + w] : (uint64_t)cblen[i];
-}
-void launch_cl_bkey(hipStream_t st, const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, int64_t n, int w, uint64_t *key) {
-  if (n > 0) hipLaunchKernelGGL(k_cl_bkey, dim3(blocks256(n)), dim3(256), 0, st, idx, cb, cblen, n, w, key);
-}
-
-__global__ void __launch_bounds__(256) k_cl_bheads(const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, int64_t n, uint64_t *head) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  uint64_t h = 1;
-  if (j > 0) {
-    const uint64_t a = idx[j], b = idx[j - 1];
-    h = (cblen[a] != cblen[b] || cb[4 * a] != cb[4 * b] || cb[4 * a + 1] != cb[4 * b + 1] || cb[4 * a + 2] != cb[4 * b + 2] ||
-         cb[4 * a + 3] != cb[4 * b + 3]) ? 1 : 0;
-  }
-  head[j] = h;
-}
-void launch_cl_bheads(hipStream_t st, const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, int64_t n, uint64_t *head) {
-  if (n > 0) hipLaunchKernelGGL(k_cl_bheads, dim3(blocks256(n)), dim3(256), 0, st, idx, cb, cblen, n, head);
 }
 
 __global__ void __launch_bounds__(256) k_cl_cells(const uint64_t *cid, const uint32_t *idx, int64_t n, const uint64_t *cb, const uint8_t *cblen,

@@ -37,6 +37,7 @@
 #include "accum.h"
 #include "coverage_kernels.h"
 #include "ctx.h"
+#include "name_window.h"
 #include "quant_kernels.h"
 #include "quant_view.h"
 #include "scan_kernels.h"
@@ -139,11 +140,12 @@ static int coverage_add_rows(br_coverage *c, CovAddArgs A, uint64_t r0, uint64_t
   return BR_OK;
 }
 
-// weight em: the rows [r0, r1) of the names W holds (a, cigar, bias, pool, n_pool_words and the names' offsets are set) into the
+// weight em: the rows of the names W holds (a, cigar, bias, pool, n_pool_words and names are set) into the
 // arena.  The first pass counts and changes nothing else, so an add it refuses has added nothing
-static int coverage_keep_rows(br_coverage *c, CovAddWArgs W, uint64_t r0, uint64_t r1) {
+static int coverage_keep_rows(br_coverage *c, CovAddWArgs W) {
   hipStream_t st = c->st;
   CovAddArgs &A = W.A;
+  const uint64_t r0 = W.names.r_first, r1 = W.names.r_last;
   A.r_first = r0; A.r_last = r1;
   A.n_tx = c->n_tx; A.off = c->d_off.as<uint64_t>(); A.primary_only = (uint32_t)c->primary_only;
   A.records = c->records.as<unsigned long long>(); A.counters = c->small.as<unsigned long long>();
@@ -172,7 +174,7 @@ static int coverage_keep_rows(br_coverage *c, CovAddWArgs W, uint64_t r0, uint64
   HIPCHK(hipStreamSynchronize(st));   // the caller's rows may be reused now
   if (c->counters[CV_KEPT] != c->kept + seen[CV_ADD_ENTRIES]) { c->broken = true; return BR_ERR_HIP; }   // (the two passes disagree)
   c->kept = c->counters[CV_KEPT];
-  c->rows += r1 - r0; c->n_names += W.n_groups;
+  c->rows += r1 - r0; c->n_names += W.names.n_groups;
   return BR_OK;
 }
 
@@ -204,55 +206,39 @@ extern "C" int br_coverage_add_rows(br_coverage *c, const br_device_rows *rows, 
   return on_device ? coverage_add_device(c, *rows, (uint64_t)r0, (uint64_t)r1, (hipStream_t)stream) : coverage_add_host(c, *rows, (uint64_t)r0, (uint64_t)r1);
 }
 
-// weight em: the names' rows [r0, r1) from host tables
-static int coverage_keep_host(br_coverage *c, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, uint64_t r0, uint64_t r1) {
-  const uint32_t a0 = group_off[0], a1 = group_off[ng];
-  RowWindow w;
-  ColBuf d_ro, d_go;
-  DropGuard dropper{c, {&w.a, &w.cigar, &w.pool, &d_ro, &d_go}};
-  RC(c->upload_rows(rows, r0, r1, true, w));
-  RC(c->alloc(d_ro, (size_t)(a1 - a0 + 1) * 8)); RC(c->alloc(d_go, (size_t)(ng + 1) * 4));
-  HIPCHK(hipMemcpyAsync(d_ro.p, rows.row_off + a0, (size_t)(a1 - a0 + 1) * 8, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(d_go.p, group_off, (size_t)(ng + 1) * 4, hipMemcpyHostToDevice, c->st));
-  CovAddWArgs W{};
-  W.A.a = w.a.as<uint4>(); W.A.cigar = w.cigar.as<uint64_t>(); W.A.bias = w.bias; W.A.pool = w.pool.as<uint32_t>(); W.A.n_pool_words = w.n_pool_words;
-  W.row_off = d_ro.as<uint64_t>(); W.ro_bias = (int64_t)a0; W.group_off = d_go.as<uint32_t>(); W.n_groups = ng;
-  return coverage_keep_rows(c, W, r0, r1);
-}
-
 extern "C" int br_coverage_add_names(br_coverage *c, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups, int on_device,
                                      void *stream) {
   if (!c || !rows || n_groups < 0 || c->broken || c->finished || (n_groups && (!rows->row_off || !group_off))) return BR_ERR_INVALID_ARG;
   if (rows->n_rows < 0 || rows->n_pool_words < 0) return BR_ERR_INVALID_ARG;
   if (n_groups == 0) { c->added = true; return BR_OK; }
   HIPCHK(hipSetDevice(c->device));
-  // the names' rows
   uint64_t span[2] = {0, 0};
-  if (on_device) {
+  {   // the object has no slot for the span of device tables: two words of the call's.  (None of these refusals sets `broken`:
+      // nothing was read that an add could have counted)
     ColBuf d_span;
     DropGuard dropper{c, {&d_span}};
-    RC(c->alloc(d_span, 16));
-    RC(c->after((hipStream_t)stream));
-    launch_q_span(c->st, rows->row_off, group_off, n_groups, d_span.as<uint64_t>());
-    HIPCHK(hipMemcpyAsync(span, d_span.p, 16, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-  } else {
-    for (int64_t g = 0; g < n_groups; g++) if (group_off[g + 1] < group_off[g]) return BR_ERR_INVALID_ARG;
-    for (uint32_t i = group_off[0]; i < group_off[n_groups]; i++) if (rows->row_off[i + 1] < rows->row_off[i]) return BR_ERR_INVALID_ARG;
-    span[0] = rows->row_off[group_off[0]]; span[1] = rows->row_off[group_off[n_groups]];
+    if (on_device) RC(c->alloc(d_span, 16));
+    RC(names_span(c, rows->row_off, (uint64_t)rows->n_rows, group_off, n_groups, on_device != 0, (hipStream_t)stream, d_span.as<uint64_t>(), span));
   }
-  if (span[1] < span[0] || span[1] > (uint64_t)rows->n_rows) return BR_ERR_INVALID_ARG;
   if (c->weight != 2) return br_coverage_add_rows(c, rows, (int64_t)span[0], (int64_t)span[1], on_device, stream);
   if (span[1] > span[0] && (!rows->a || !rows->cigar || (rows->n_pool_words && !rows->pool))) return BR_ERR_INVALID_ARG;
   if (c->rows + (span[1] - span[0]) >= (1ull << 32) || (uint64_t)c->n_names + (uint64_t)n_groups >= (1ull << 32)) return BR_ERR_CAPACITY;
   c->added = true;
   ScopeTimer timer(&c->add_s);
   if (span[1] == span[0]) { c->n_names += n_groups; return BR_OK; }   // names without rows
-  if (!on_device) return coverage_keep_host(c, *rows, group_off, n_groups, span[0], span[1]);
+  RowWindow w;   // host tables: the rows' window and the names'
+  ColBuf d_ro, d_go;
+  DropGuard dropper{c, {&w.a, &w.cigar, &w.pool, &d_ro, &d_go}};
   CovAddWArgs W{};
-  W.A.a = (const uint4 *)rows->a; W.A.cigar = rows->cigar; W.A.pool = rows->pool; W.A.n_pool_words = (uint64_t)rows->n_pool_words;
-  W.row_off = rows->row_off; W.group_off = group_off; W.n_groups = n_groups;
-  return coverage_keep_rows(c, W, span[0], span[1]);   // (after whatever made the rows: the span's wait saw to it)
+  if (on_device) {   // (after whatever made the rows: the span's wait saw to it)
+    W.A.a = (const uint4 *)rows->a; W.A.cigar = rows->cigar; W.A.pool = rows->pool; W.A.n_pool_words = (uint64_t)rows->n_pool_words;
+    W.names = device_names(rows->row_off, group_off, n_groups, span);
+  } else {
+    RC(c->upload_rows(*rows, span[0], span[1], true, w));
+    RC(upload_names(c, rows->row_off, group_off, n_groups, span, d_ro, d_go, &W.names));
+    W.A.a = w.a.as<uint4>(); W.A.cigar = w.cigar.as<uint64_t>(); W.A.bias = w.bias; W.A.pool = w.pool.as<uint32_t>(); W.A.n_pool_words = w.n_pool_words;
+  }
+  return coverage_keep_rows(c, W);
 }
 
 extern "C" int br_coverage_add_last(br_coverage *c, br_ctx *ctx) {

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "names.h"
+
 namespace br {
 
 constexpr uint32_t COV_SMALL_OPS = 64;      // a CIGAR of up to this many ops is one lane's walk in k_cov_add, a longer one the wave's
@@ -60,9 +62,9 @@ struct CovAddWArgs {
   // in counters[CV_ADD_ENTRIES], the keep pass places a wave's entries by one atomic on counters[CV_KEPT]
   uint32_t *row_entries;
   uint4 *arena; uint64_t arena_cap;
-  // the names of the add (as QAddArgs holds them): row r belongs to alignment a with row_off[a] <= r < row_off[a + 1], a to name g
-  // with group_off[g] <= a < group_off[g + 1]; its add-order index is name_base + g
-  const uint64_t *row_off; int64_t ro_bias; const uint32_t *group_off; int64_t n_groups; uint64_t name_base;
+  // the names of the add (names.h; their rows are A's [r_first, r_last)): row r belongs to alignment a with row_off[a] <= r <
+  // row_off[a + 1], a to name g with group_off[g] <= a < group_off[g + 1]; its add-order index is name_base + g
+  NameWindow names; uint64_t name_base;
 };
 void launch_cov_add_w(hipStream_t st, const CovAddWArgs &W, int mode);
 // the kept entries [0, n) applied to diff with the quantifier's posteriors; every index taken from a table is checked first

@@ -327,15 +327,16 @@ __device__ __forceinline__ void walk_op_w(CovSink<MODE> &k, uint64_t base, uint6
 }
 // the add-order name of row r, from the add's offsets; false where they do not give one (offsets that descend)
 __device__ __forceinline__ bool name_of(const CovAddWArgs &W, uint64_t r, uint32_t &name) {
-  const uint32_t a0 = W.group_off[0], a1 = W.group_off[W.n_groups];
+  const NameWindow &N = W.names;
+  const uint32_t a0 = N.group_off[0], a1 = N.group_off[N.n_groups];
   if (a1 <= a0) return false;
-  const auto ro = [&](uint32_t a) { return W.row_off[(int64_t)a - W.ro_bias]; };
+  const auto ro = [&](uint32_t a) { return N.row_off[(int64_t)a - N.ro_bias]; };
   uint32_t lo = a0, hi = a1 - 1u;   // the last alignment of [a0, a1) whose rows begin at or in front of r
   while (lo < hi) { const uint32_t mid = lo + (hi - lo + 1u) / 2u; if (ro(mid) <= r) lo = mid; else hi = mid - 1u; }
   if (!(ro(lo) <= r && r < ro(lo + 1u))) return false;
-  int64_t glo = 0, ghi = W.n_groups - 1;   // the last name whose alignments begin at or in front of it
-  while (glo < ghi) { const int64_t mid = (glo + ghi + 1) >> 1; if (W.group_off[mid] <= lo) glo = mid; else ghi = mid - 1; }
-  if (!(W.group_off[glo] <= lo && lo < W.group_off[glo + 1])) return false;
+  int64_t glo = 0, ghi = N.n_groups - 1;   // the last name whose alignments begin at or in front of it
+  while (glo < ghi) { const int64_t mid = (glo + ghi + 1) >> 1; if (N.group_off[mid] <= lo) glo = mid; else ghi = mid - 1; }
+  if (!(N.group_off[glo] <= lo && lo < N.group_off[glo + 1])) return false;
   name = (uint32_t)(W.name_base + (uint64_t)glo);
   return true;
 }

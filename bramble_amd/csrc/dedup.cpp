@@ -33,8 +33,10 @@
 
 #include "accum.h"
 #include "assign_kernels.h"
+#include "barcode_sort.h"
 #include "ctx.h"
 #include "dedup_kernels.h"
+#include "name_window.h"
 #include "quant_kernels.h"
 #include "scan_kernels.h"
 #include "whitelist.h"
@@ -71,9 +73,7 @@ extern "C" int br_dedup_new(int device, br_dedup **out) {
   if (!out) return BR_ERR_INVALID_ARG;
   *out = nullptr;
   br_dedup *c = new br_dedup();
-  int rc = c->open(device);
-  if (!rc) rc = c->alloc(c->small, DD_WORDS * 8);
-  if (!rc && (hipMemsetAsync(c->small.p, 0, DD_WORDS * 8, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) rc = BR_ERR_HIP;
+  const int rc = c->open(device, c->small, DD_WORDS);
   if (rc) { br_dedup_free(c); return rc; }
   *out = c;
   return BR_OK;
@@ -112,37 +112,31 @@ static int dedup_reserve(br_dedup *c, uint64_t ng, uint64_t m, uint64_t bytes) {
   RC(dedup_grow(c, c->hash, N, 8)); RC(dedup_grow(c, c->ent, R, 16));
   if (c->cell_source) { RC(dedup_grow(c, c->cb, N, 32)); RC(dedup_grow(c, c->cblen, N, 1)); }
   if (!c->keep_records) return BR_OK;
-  const uint64_t need = c->used + bytes;
-  if (c->max_bytes && need > c->max_bytes) return BR_ERR_CAPACITY;
-  if (need + DD_ARENA_SLACK > c->arena.cap) {
-    uint64_t want = std::max<uint64_t>(need + DD_ARENA_SLACK, c->arena.cap + c->arena.cap / 2);
-    if (c->max_bytes) want = std::min<uint64_t>(want, c->max_bytes + DD_ARENA_SLACK);
-    RC(c->alloc(c->arena, (size_t)want, true));
-  }
+  RC(c->grow_arena(c->arena, c->used, bytes, c->max_bytes));
   return dedup_grow(c, c->rec_at, R, 8);
 }
 
-// the names of one add, their tables on the device (A: the rows' tables, the offsets, the biases, r_first, r_last and n_groups are set;
-// rec_off likewise).  data: the records' bytes from the first row's record on, `bytes` of them, in host or device memory.  Nothing is
-// counted before the kernels have accepted the add
-static int dedup_add_names(br_dedup *c, DdAddArgs A, const uint8_t *data, uint64_t bytes, uint64_t first_off, bool on_device) {
+// the names of one add, their tables on the device (A: the rows' tables, a_bias, names and recs but for recs.data are set).  data: the
+// records' bytes from the first row's record on, `bytes` of them, in host or device memory.  Nothing is counted before the kernels
+// have accepted the add
+static int dedup_add_names(br_dedup *c, DdAddArgs A, const uint8_t *data, uint64_t bytes, bool on_device) {
   hipStream_t st = c->st;
-  const uint64_t m = A.r_last - A.r_first;
-  RC(dedup_reserve(c, (uint64_t)A.n_groups, m, bytes));
+  const uint64_t ng = (uint64_t)A.names.n_groups, m = A.names.r_last - A.names.r_first;
+  RC(dedup_reserve(c, ng, m, bytes));
   ColBuf raw, big, window;
   DropGuard dropper{c, {&raw, &big, &window}};
-  RC(c->alloc(raw, (size_t)(m + 1) * 16)); RC(c->alloc(big, (size_t)(A.n_groups + 1) * 4));
+  RC(c->alloc(raw, (size_t)(m + 1) * 16)); RC(c->alloc(big, (size_t)(ng + 1) * 4));
   uint64_t *small = c->small.as<uint64_t>();
   HIPCHK(hipMemsetAsync(small + DD_BAD, 0, 5 * 8, st));   // DD_BAD .. DD_BAD_AUX
-  if (c->keep_records) {   // one copy; the kernels read the records where they stay
+  if (c->keep_records) {   // one copy into the arena; the kernels read the records where they stay
     if (bytes) HIPCHK(hipMemcpyAsync(c->arena.as<uint8_t>() + c->used, data, (size_t)bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    A.data = c->arena.as<uint8_t>() + c->used; A.data_bias = first_off;
+    A.recs.data = c->arena.as<uint8_t>() + c->used;
     A.rec_at = c->rec_at.as<uint64_t>() + c->rows; A.arena_base = c->used;
-  } else if (on_device) { A.data = data; A.data_bias = first_off; }
+  } else if (on_device) A.recs.data = data;
   else {
-    RC(c->alloc(window, (size_t)bytes + DD_ARENA_SLACK));
+    RC(c->alloc(window, (size_t)bytes + ARENA_SLACK));
     if (bytes) HIPCHK(hipMemcpyAsync(window.p, data, (size_t)bytes, hipMemcpyHostToDevice, st));
-    A.data = window.as<uint8_t>(); A.data_bias = first_off;
+    A.recs.data = window.as<uint8_t>();
   }
   A.umi_source = c->umi_source; A.umi_sep = c->umi_sep; A.umi_tag = c->umi_tag;
   A.cell_source = c->cell_source; A.cell_tag = c->cell_tag;
@@ -156,44 +150,32 @@ static int dedup_add_names(br_dedup *c, DdAddArgs A, const uint8_t *data, uint64
   HIPCHK(hipMemcpyAsync(seen, small + DD_BAD, sizeof(seen), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));   // the caller's tables may be reused now
   if (seen[DD_BAD]) return BR_ERR_INVALID_ARG;   // nothing was added
-  c->n += (uint64_t)A.n_groups; c->rows += m; c->used += c->keep_records ? bytes : 0;
+  c->n += ng; c->rows += m; c->used += c->keep_records ? bytes : 0;
   c->n_no_umi += seen[DD_NO_UMI]; c->n_too_long += seen[DD_TOO_LONG]; c->n_bad_aux += seen[DD_BAD_AUX];
   return BR_OK;
 }
 
-static int dedup_add_host(br_dedup *c, const br_device_bam &recs, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, uint64_t r0, uint64_t r1) {
-  const uint32_t a0 = group_off[0], a1 = group_off[ng];
-  for (uint64_t r = r0; r < r1; r++) if (recs.row_off[r + 1] < recs.row_off[r]) return BR_ERR_INVALID_ARG;
-  const uint64_t lo = r1 > r0 ? recs.row_off[r0] : 0, hi = r1 > r0 ? recs.row_off[r1] : 0;   // (names without rows: no record is looked at)
-  if (hi < lo || hi > recs.n_bytes) return BR_ERR_INVALID_ARG;
+static int dedup_add_host(br_dedup *c, const br_device_bam &recs, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, const uint64_t span[2]) {
   RowWindow w;
   ColBuf d_ro, d_go, d_rec;
   DropGuard dropper{c, {&w.a, &w.cigar, &w.pool, &d_ro, &d_go, &d_rec}};
-  RC(c->upload_rows(rows, r0, r1, true, w));
-  RC(c->alloc(d_ro, (size_t)(a1 - a0 + 1) * 8)); RC(c->alloc(d_go, (size_t)(ng + 1) * 4)); RC(c->alloc(d_rec, (size_t)(r1 - r0 + 1) * 8));
-  HIPCHK(hipMemcpyAsync(d_ro.p, rows.row_off + a0, (size_t)(a1 - a0 + 1) * 8, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(d_go.p, group_off, (size_t)(ng + 1) * 4, hipMemcpyHostToDevice, c->st));
-  if (r1 > r0) HIPCHK(hipMemcpyAsync(d_rec.p, recs.row_off + r0, (size_t)(r1 - r0 + 1) * 8, hipMemcpyHostToDevice, c->st));
   DdAddArgs A{};
+  const uint8_t *data; uint64_t bytes;
+  RC(record_window(c, recs, span[0], span[1], false, d_rec, &A.recs, &data, &bytes));
+  RC(c->upload_rows(rows, span[0], span[1], true, w));
+  RC(upload_names(c, rows.row_off, group_off, ng, span, d_ro, d_go, &A.names));
   A.a = w.a.as<uint4>(); A.cigar = w.cigar.as<uint64_t>(); A.a_bias = w.bias; A.pool = w.pool.as<uint32_t>(); A.n_pool_words = w.n_pool_words;
-  A.row_off = d_ro.as<uint64_t>(); A.ro_bias = (int64_t)a0; A.group_off = d_go.as<uint32_t>(); A.n_groups = ng; A.r_first = r0; A.r_last = r1;
-  A.rec_off = d_rec.as<uint64_t>(); A.rec_bias = (int64_t)r0;
-  return dedup_add_names(c, A, r1 > r0 ? recs.data + lo : nullptr, hi - lo, lo, false);   // (it waits for the stream: the uploads are done when the host arrays go)
+  return dedup_add_names(c, A, data, bytes, false);   // (it waits for the stream: the uploads are done when the host arrays go)
 }
 
-static int dedup_add_device(br_dedup *c, const br_device_bam &recs, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, uint64_t r0, uint64_t r1) {
-  uint64_t ends[2] = {0, 0};
-  if (r1 > r0) {   // (names without rows: no record is looked at)
-    HIPCHK(hipMemcpyAsync(&ends[0], recs.row_off + r0, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipMemcpyAsync(&ends[1], recs.row_off + r1, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-  }
-  if (ends[1] < ends[0] || ends[1] > recs.n_bytes) return BR_ERR_INVALID_ARG;
+static int dedup_add_device(br_dedup *c, const br_device_bam &recs, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, const uint64_t span[2]) {
+  ColBuf none;
   DdAddArgs A{};
+  const uint8_t *data; uint64_t bytes;
+  RC(record_window(c, recs, span[0], span[1], true, none, &A.recs, &data, &bytes));
+  A.names = device_names(rows.row_off, group_off, ng, span);
   A.a = (const uint4 *)rows.a; A.cigar = rows.cigar; A.pool = rows.pool; A.n_pool_words = (uint64_t)rows.n_pool_words;
-  A.row_off = rows.row_off; A.group_off = group_off; A.n_groups = ng; A.r_first = r0; A.r_last = r1;
-  A.rec_off = recs.row_off;
-  return dedup_add_names(c, A, r1 > r0 ? recs.data + ends[0] : nullptr, ends[1] - ends[0], ends[0], true);
+  return dedup_add_names(c, A, data, bytes, true);
 }
 
 extern "C" int br_dedup_add(br_dedup *c, const br_device_bam *recs, const br_device_rows *rows, const uint32_t *group_off, int64_t n_groups,
@@ -205,21 +187,8 @@ extern "C" int br_dedup_add(br_dedup *c, const br_device_bam *recs, const br_dev
   ScopeTimer timer(&c->add_s);
   HIPCHK(hipSetDevice(c->device));
   uint64_t span[2] = {0, 0};
-  if (on_device) {
-    uint64_t *d_span = c->small.as<uint64_t>() + DD_SPAN;
-    RC(c->after((hipStream_t)stream));   // after whatever made the rows
-    launch_q_span(c->st, rows->row_off, group_off, n_groups, d_span);
-    HIPCHK(hipMemcpyAsync(span, d_span, 16, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-  } else {
-    for (int64_t g = 0; g < n_groups; g++) if (group_off[g + 1] < group_off[g]) return BR_ERR_INVALID_ARG;
-    for (uint32_t i = group_off[0]; i < group_off[n_groups]; i++) if (rows->row_off[i + 1] < rows->row_off[i]) return BR_ERR_INVALID_ARG;
-    span[0] = rows->row_off[group_off[0]]; span[1] = rows->row_off[group_off[n_groups]];
-  }
-  if (span[1] < span[0] || span[1] > (uint64_t)rows->n_rows) return BR_ERR_INVALID_ARG;
-  const int rc = on_device ? dedup_add_device(c, *recs, *rows, group_off, n_groups, span[0], span[1])
-                           : dedup_add_host(c, *recs, *rows, group_off, n_groups, span[0], span[1]);
-  if (rc) return rc;
+  RC(names_span(c, rows->row_off, (uint64_t)rows->n_rows, group_off, n_groups, on_device != 0, (hipStream_t)stream, c->small.as<uint64_t>() + DD_SPAN, span));
+  RC(on_device ? dedup_add_device(c, *recs, *rows, group_off, n_groups, span) : dedup_add_host(c, *recs, *rows, group_off, n_groups, span));
   c->added = true;   // (an add that was refused decides nothing)
   return BR_OK;
 }
@@ -227,34 +196,10 @@ extern "C" int br_dedup_add(br_dedup *c, const br_device_bam *recs, const br_dev
 extern "C" int br_dedup_add_last(br_dedup *c, br_ctx *ctx) {
   if (!c || !ctx || !ctx->ix || ctx->ix->device != c->device || c->dead || c->finished) return BR_ERR_INVALID_ARG;
   if (ctx->last_n_groups == 0) return BR_OK;   // a call without names
-  if (ctx->last_rows.n_rows && ctx->last_bam.n_rows != ctx->last_rows.n_rows) return BR_ERR_INVALID_ARG;   // a flat batch call left no records
-  br_device_bam recs = ctx->last_bam;
-  if (ctx->last_rows.n_rows == 0) recs = br_device_bam{};   // names without rows: no record stream was made
+  br_device_bam recs; bool flat;
+  last_call_records(ctx, &recs, &flat);
+  if (flat) return BR_ERR_INVALID_ARG;   // a flat batch call left no records
   return br_dedup_add(c, &recs, &ctx->last_rows, ctx->last_group_off, ctx->last_n_groups, 1, ctx->last_stream);
-}
-
-namespace {
-// key / index pairs of a radix sort: the sorted pairs are those of [0] when it returns
-struct SortBufs {
-  ColBuf key[2], idx[2];
-  void front(int cur) { if (cur) { std::swap(key[0], key[1]); std::swap(idx[0], idx[1]); } }
-};
-}  // namespace
-
-// the radix sort of (key[0], idx[0]) over the digits in which the keys differ
-static int dedup_sort(br_dedup *c, SortBufs &s, int64_t n, ColBuf &tmp) {
-  if (n <= 0) return BR_OK;
-  hipStream_t st = c->st;
-  uint64_t *small = c->small.as<uint64_t>();
-  RC(c->alloc(tmp, scan_tmp_bytes(n)));
-  launch_q_bits(st, s.key[0].as<uint64_t>(), n, tmp.as<uint64_t>(), small + DD_BITS);
-  uint64_t bits[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(bits, small + DD_BITS, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  int cur = 0;
-  RC(c->radix_sort(s.key, s.idx, n, bits, tmp, &cur));
-  s.front(cur);
-  return BR_OK;
 }
 
 static int dedup_finish(br_dedup *c) {
@@ -276,21 +221,18 @@ static int dedup_finish(br_dedup *c) {
   {
     ColBuf pos;
     DropGuard dropper{c, {&pos}};
-    RC(c->alloc(pos, n1 * 8)); RC(c->alloc(tmp, scan_tmp_bytes(N)));
+    RC(c->alloc(pos, n1 * 8));
     launch_q_flag(st, c->nk.as<uint32_t>(), N, pos.as<uint64_t>());
-    launch_scan(st, pos.as<uint64_t>(), N, tmp.as<uint64_t>());
-    HIPCHK(hipMemcpyAsync(&M, pos.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    RC(c->scan_total(pos, N, tmp, &M));
     c->n_with_rows = M;
     if (M == 0) return BR_OK;
-    const size_t m1 = (size_t)M + 1;
-    for (int k = 0; k < 2; k++) { RC(c->alloc(s.key[k], m1 * 8)); RC(c->alloc(s.idx[k], m1 * 4)); }
+    RC(s.make(c, (size_t)M));
     const uint64_t mask = c->hash_bits >= 64 ? ~0ull : (1ull << c->hash_bits) - 1;
     launch_q_compact(st, c->nk.as<uint32_t>(), c->hash.as<uint64_t>(), pos.as<uint64_t>(), N, mask, s.key[0].as<uint64_t>(), s.idx[0].as<uint32_t>());
     HIPCHK(hipStreamSynchronize(st));
   }
   const int64_t n = (int64_t)M;
-  RC(dedup_sort(c, s, n, tmp));
+  RC(sort_pairs(c, s, n, tmp, small + DD_BITS));
   // position groups: the heads compare the signatures; a run of equal keys that holds different ones is put in order and cut again
   const uint32_t *ent = c->ent.as<uint32_t>();
   const uint64_t *noff = c->noff.as<uint64_t>();
@@ -311,13 +253,11 @@ static int dedup_finish(br_dedup *c) {
     HIPCHK(hipMemsetAsync(mark.p, 0, (size_t)n * 4, st));
     RC(heads(mark.as<uint32_t>(), &n_coll));
     launch_q_resolve(st, ent, noff, nk, s.key[0].as<uint64_t>(), s.idx[0].as<uint32_t>(), n, mark.as<uint32_t>(), s.key[1].as<uint64_t>(), s.idx[1].as<uint32_t>());
-    s.front(1);
+    std::swap(s.key[0], s.key[1]); std::swap(s.idx[0], s.idx[1]);
     RC(heads(nullptr, &n_coll));
   }
-  launch_scan(st, head.as<uint64_t>(), n, tmp.as<uint64_t>());   // head -> group ids (exclusive), head[n] = G
   uint64_t G = 0;
-  HIPCHK(hipMemcpyAsync(&G, head.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  RC(c->scan_total(head, n, tmp, &G));   // head -> group ids (exclusive), head[n] = G
   if (G == 0 || G > M) return BR_ERR_HIP;
   c->n_groups = G;
   RC(c->alloc(gbeg, (size_t)(G + 1) * 8)); RC(c->alloc(name_gid, n1 * 4));
@@ -325,21 +265,12 @@ static int dedup_finish(br_dedup *c) {
   launch_dd_groups(st, head.as<uint64_t>(), gbeg.as<uint64_t>(), s.idx[0].as<uint32_t>(), n, c->gfirst.as<uint32_t>(), name_gid.as<uint32_t>());
   const uint64_t *umi = c->umi.as<uint64_t>();
   const uint8_t *ulen = c->ulen.as<uint8_t>();
-  // (group, length, bytes) of a 32-byte field: least significant word first, every sort stable, so equal items' names ascend
-  auto sort_by_field = [&](const uint64_t *words, const uint8_t *len) -> int {
-    for (int w = 3; w >= 0; w--) {
-      launch_dd_ukey(st, s.idx[0].as<uint32_t>(), words, len, name_gid.as<uint32_t>(), n, w, s.key[0].as<uint64_t>());
-      RC(dedup_sort(c, s, n, tmp));
-    }
-    launch_dd_ukey(st, s.idx[0].as<uint32_t>(), words, len, name_gid.as<uint32_t>(), n, 4, s.key[0].as<uint64_t>());
-    return dedup_sort(c, s, n, tmp);
-  };
+  // the field sorts below are by (group, length, bytes), every sort stable, so equal items' names ascend
   if (c->cell_source) {   // per cell: a group of equal signatures is cut where the barcode changes, by the barcodes themselves
-    RC(sort_by_field(c->cb.as<uint64_t>(), c->cblen.as<uint8_t>()));
-    launch_dd_cheads(st, s.idx[0].as<uint32_t>(), c->cb.as<uint64_t>(), c->cblen.as<uint8_t>(), name_gid.as<uint32_t>(), n, head.as<uint64_t>());
-    launch_scan(st, head.as<uint64_t>(), n, tmp.as<uint64_t>());
-    HIPCHK(hipMemcpyAsync(&G, head.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    RC(sort_by_barcode(c, s, c->cb.as<uint64_t>(), c->cblen.as<uint8_t>(), name_gid.as<uint32_t>(), n, tmp, small + DD_BITS));
+    // (names without a barcode share the empty one: an empty field is no head of its own)
+    launch_bc_heads(st, s.idx[0].as<uint32_t>(), c->cb.as<uint64_t>(), c->cblen.as<uint8_t>(), name_gid.as<uint32_t>(), 0, n, head.as<uint64_t>());
+    RC(c->scan_total(head, n, tmp, &G));
     if (G < c->n_groups || G > M) return BR_ERR_HIP;
     c->n_groups = G;
     RC(c->alloc(gbeg, (size_t)(G + 1) * 8));
@@ -347,13 +278,11 @@ static int dedup_finish(br_dedup *c) {
     launch_dd_groups(st, head.as<uint64_t>(), gbeg.as<uint64_t>(), s.idx[0].as<uint32_t>(), n, c->gfirst.as<uint32_t>(), name_gid.as<uint32_t>());
   }
   // within the groups by (length, UMI), so the names of a node ascend
-  RC(sort_by_field(umi, ulen));
-  // nodes
-  launch_dd_nheads(st, s.idx[0].as<uint32_t>(), umi, ulen, name_gid.as<uint32_t>(), n, head.as<uint64_t>());
-  launch_scan(st, head.as<uint64_t>(), n, tmp.as<uint64_t>());
+  RC(sort_by_barcode(c, s, umi, ulen, name_gid.as<uint32_t>(), n, tmp, small + DD_BITS));
+  // nodes: a name without a UMI is a node of its own
+  launch_bc_heads(st, s.idx[0].as<uint32_t>(), umi, ulen, name_gid.as<uint32_t>(), 1, n, head.as<uint64_t>());
   uint64_t D = 0;
-  HIPCHK(hipMemcpyAsync(&D, head.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  RC(c->scan_total(head, n, tmp, &D));
   if (D < G || D > M) return BR_ERR_HIP;
   c->n_nodes = D;
   const size_t d1 = (size_t)D + 1;
@@ -363,9 +292,9 @@ static int dedup_finish(br_dedup *c) {
                           &ns.key[0], &ns.key[1], &ns.idx[0], &ns.idx[1]}};
   RC(c->alloc(nbeg, d1 * 8));
   launch_col_gbeg(st, head.as<uint64_t>(), n, nbeg.as<uint64_t>());
-  for (int k = 0; k < 2; k++) { RC(c->alloc(ns.key[k], d1 * 8)); RC(c->alloc(ns.idx[k], d1 * 4)); }
+  RC(ns.make(c, (size_t)D));
   launch_dd_node_key(st, nbeg.as<uint64_t>(), s.idx[0].as<uint32_t>(), name_gid.as<uint32_t>(), (int64_t)D, ns.key[0].as<uint64_t>(), ns.idx[0].as<uint32_t>());
-  RC(dedup_sort(c, ns, (int64_t)D, tmp));
+  RC(sort_pairs(c, ns, (int64_t)D, tmp, small + DD_BITS));
   RC(c->alloc(o_umi, d1 * 32)); RC(c->alloc(o_len, d1)); RC(c->alloc(o_cnt, d1 * 4)); RC(c->alloc(o_first, d1 * 4)); RC(c->alloc(o_gid, d1 * 4));
   RC(c->alloc(inv, d1 * 4)); RC(c->alloc(gn0, (size_t)(G + 1) * 8)); RC(c->alloc(work, (size_t)(G + 1) * 8));
   RC(c->alloc(eoff, d1 * 8)); RC(c->alloc(cursor, d1 * 4)); RC(c->alloc(label[0], d1 * 4)); RC(c->alloc(label[1], d1 * 4)); RC(c->alloc(msize, d1 * 4));
@@ -379,7 +308,7 @@ static int dedup_finish(br_dedup *c) {
   launch_dd_nodes(st, Nd, ns.idx[0].as<uint32_t>(), nbeg.as<uint64_t>(), s.idx[0].as<uint32_t>(), umi, ulen, name_gid.as<uint32_t>());
   RC(c->alloc(tmp, scan_tmp_bytes((int64_t)std::max(G, D))));
   launch_scan(st, work.as<uint64_t>(), (int64_t)G, tmp.as<uint64_t>());
-  uint64_t got[2] = {0, 0};   // the tile pairs, the largest group's nodes
+  uint64_t got[2] = {0, 0};   // the tile pairs, the largest group's nodes: the scan's total and a counter come back in one wait
   HIPCHK(hipMemcpyAsync(&got[0], work.as<uint64_t>() + G, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(&got[1], small + DD_MAXM, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -389,10 +318,8 @@ static int dedup_finish(br_dedup *c) {
   int lab = 0;
   if (c->method == 1 && got[0]) {
     launch_dd_edges(st, Nd, nullptr, got[0], false);
-    launch_scan(st, eoff.as<uint64_t>(), (int64_t)D, tmp.as<uint64_t>());
     uint64_t E = 0;
-    HIPCHK(hipMemcpyAsync(&E, eoff.as<uint64_t>() + D, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    RC(c->scan_total(eoff, (int64_t)D, tmp, &E));
     c->n_edges = E;
     if (E) {
       RC(c->alloc(esrc, (size_t)(E + 1) * 4));
@@ -428,7 +355,7 @@ static int dedup_records(br_dedup *c) {
   DropGuard dropper{c, {&rank, &tmp}};
   RC(c->alloc(c->rdup, (size_t)R + 1)); RC(c->alloc(rank, (size_t)(R + 1) * 8)); RC(c->alloc(tmp, scan_scratch_bytes((int64_t)R + 1)));
   launch_dd_keep(st, c->noff.as<uint64_t>(), (int64_t)c->n, c->dup.as<uint8_t>(), R, c->mark, rank.as<uint64_t>(), c->rdup.as<uint8_t>());
-  launch_scan(st, rank.as<uint64_t>(), (int64_t)R, tmp.as<uint64_t>());
+  launch_scan(st, rank.as<uint64_t>(), (int64_t)R, tmp.as<uint64_t>());   // (not scan_total: the scratch here is the scan's own, smaller size)
   uint64_t K = 0;
   HIPCHK(hipMemcpyAsync(&K, rank.as<uint64_t>() + R, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -471,34 +398,16 @@ extern "C" int br_dedup_set_whitelist(br_dedup *c, const br_whitelist *wl, int c
 }
 
 extern "C" int br_dedup_whitelist_stats(const br_dedup *c, uint64_t out[8]) {
-  if (!c || !out || !c->wl) return BR_ERR_INVALID_ARG;
-  const WlResolved &r = c->wl_res;
-  const uint64_t v[8] = {r.status[0], r.status[1], r.status[2], r.status[3], r.status[4], r.distinct, (uint64_t)(r.seconds * 1e6), (uint64_t)c->wl_correct};
-  memcpy(out, v, sizeof(v));
-  return BR_OK;
-}
-
-static bool dedup_range(const br_dedup *c, int64_t first, int64_t n) {
-  return first >= 0 && n >= 0 && (uint64_t)first <= c->n && (uint64_t)n <= c->n - (uint64_t)first;
+  return c && c->wl ? wl_stats(c->wl_res, c->wl_correct, out) : BR_ERR_INVALID_ARG;
 }
 
 extern "C" int br_dedup_umis(br_dedup *c, int64_t first, int64_t n, uint8_t *umi, uint8_t *len) {
-  if (!c || c->dead || !dedup_range(c, first, n)) return BR_ERR_INVALID_ARG;
-  if (n == 0) return BR_OK;
-  HIPCHK(hipSetDevice(c->device));
-  std::vector<uint64_t> words;
-  if (umi) {
-    words.resize((size_t)n * 4);
-    HIPCHK(hipMemcpyAsync(words.data(), c->umi.as<uint64_t>() + 4 * first, (size_t)n * 32, hipMemcpyDeviceToHost, c->st));
-  }
-  if (len) HIPCHK(hipMemcpyAsync(len, c->ulen.as<uint8_t>() + first, (size_t)n, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  if (umi) for (size_t i = 0; i < (size_t)n * 32; i++) umi[i] = (uint8_t)(words[i >> 3] >> (56 - 8 * (i & 7)));   // (the words hold the bytes in comparison order)
-  return BR_OK;
+  if (!c || c->dead || !in_range(c->n, first, n)) return BR_ERR_INVALID_ARG;
+  return c->fetch_fields(c->umi, c->ulen, first, n, umi, len);
 }
 
 extern "C" int br_dedup_result(br_dedup *c, int64_t first, int64_t n, uint32_t *rep, uint32_t *group_first, uint8_t *dup) {
-  if (!c || c->dead || !c->finished || !dedup_range(c, first, n)) return BR_ERR_INVALID_ARG;
+  if (!c || c->dead || !c->finished || !in_range(c->n, first, n)) return BR_ERR_INVALID_ARG;
   if (n == 0) return BR_OK;
   HIPCHK(hipSetDevice(c->device));
   if (rep) HIPCHK(hipMemcpyAsync(rep, c->rep.as<uint32_t>() + first, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "names.h"
+
 namespace br {
 
 constexpr int DD_UMI_MAX = 32;           // bytes of a UMI; a name's slot holds them zero padded, as four 64-bit words
@@ -11,8 +13,6 @@ constexpr int DD_SMALL_ROWS = 16;        // a read name of up to this many rows 
 constexpr uint32_t DD_WAVE_OPS = 64;     // a pooled CIGAR of more ops than this is summed by the wave
 constexpr unsigned DD_BIG_GRID = 1024;   // blocks (of 4 waves) that walk a list whose length only the device knows
 constexpr int DD_WRITE_LANES = 16;       // lanes per record of the gather
-constexpr uint64_t DD_ARENA_SLACK = 64;  // bytes the arena keeps behind its end
-constexpr uint32_t DD_MIN_RECORD = 36;   // [block_size] and the fixed fields of a record
 // words of the counters
 enum { DD_BAD = 0,        // add: offsets that descend, a record shorter than its fixed fields, a pooled CIGAR that leaves the pool
        DD_NBIG = 1,       // add: names of more than DD_SMALL_ROWS rows (the list's length)
@@ -27,14 +27,11 @@ enum { DD_BAD = 0,        // add: offsets that descend, a record shorter than it
        DD_WORDS = 16 };
 
 // One add: the names [0, n_groups) of the add become the names [name_base, ...) of the object, their rows [r_first, r_last) its rows
-// [row_base, ...).  a, cigar may be slices: row r is at [r - a_bias]; row_off likewise at ro_bias.  Row r's record lies at
-// data[rec_off[r - rec_bias] - data_bias ...): [block_size][record].
+// [row_base, ...).  a, cigar may be slices: row r is at [r - a_bias]; the names and the records as names.h holds them.
 struct DdAddArgs {
   const uint4 *a; const uint64_t *cigar; int64_t a_bias;
   const uint32_t *pool; uint64_t n_pool_words;
-  const uint64_t *row_off; int64_t ro_bias; const uint32_t *group_off; int64_t n_groups;
-  uint64_t r_first, r_last;
-  const uint8_t *data; uint64_t data_bias; const uint64_t *rec_off; int64_t rec_bias;
+  NameWindow names; RecordWindow recs;
   int umi_source; uint32_t umi_sep, umi_tag;
   int cell_source; uint32_t cell_tag;             // "cell_source" 0: no barcode is read and cb, cblen are not written
   uint4 *raw;            // the add's entries in row order (r_last - r_first), scratch
@@ -53,13 +50,6 @@ void launch_dd_add(hipStream_t st, const DdAddArgs &A);
 // finish.  The sorted items are (key, name) pairs; gid: the scanned heads (n + 1 entries)
 // group_first[idx[j]] = idx[gbeg[group of j]], name_gid[idx[j]] = the group of j
 void launch_dd_groups(hipStream_t st, const uint64_t *gid, const uint64_t *gbeg, const uint32_t *idx, int64_t n, uint32_t *group_first, uint32_t *name_gid);
-// key[j] = word w of the UMI of idx[j], bytes in comparison order (w = 0 .. 3); w = 4: group << 8 | length
-void launch_dd_ukey(hipStream_t st, const uint32_t *idx, const uint64_t *umi, const uint8_t *ulen, const uint32_t *name_gid, int64_t n, int w, uint64_t *key);
-// head[j] = sorted item j starts a node: its (group, UMI) differs from item j - 1's, or it has no UMI
-void launch_dd_nheads(hipStream_t st, const uint32_t *idx, const uint64_t *umi, const uint8_t *ulen, const uint32_t *name_gid, int64_t n, uint64_t *head);
-// "cell_source": the items sorted by (group, barcode length, barcode bytes): head[j] = item j's (group, barcode) differs from item
-// j - 1's -- the per-cell position groups' starts (names without a barcode share the empty one)
-void launch_dd_cheads(hipStream_t st, const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, const uint32_t *name_gid, int64_t n, uint64_t *head);
 // the nodes in (group, length, bytes) order: key[q] = group << 32 | ~count, val[q] = q: to be sorted (stable) into the node order
 void launch_dd_node_key(hipStream_t st, const uint64_t *nbeg, const uint32_t *idx, const uint32_t *name_gid, int64_t n_nodes, uint64_t *key, uint32_t *val);
 struct DdNodes {

@@ -5,7 +5,7 @@
 //            more than DD_WAVE_OPS ops summed by the wave; k_dd_names: a lane per name: the UMI of its first record, and for a name
 //            of up to DD_SMALL_ROWS rows the entries in order and their hash; k_dd_sig_big: a wave per longer name
 //   finish   the names sorted by hash and cut into position groups by the quantifier's kernels (a signature is a list of words to
-//            them); k_dd_groups; four radix sorts by the UMI's words and one by (group, length) over k_dd_ukey; k_dd_nheads;
+//            them); k_dd_groups; the field sort by (group, length, UMI) and its heads (barcode_sort.h);
 //            k_dd_node_key and a sort: the node order; k_dd_nodes, k_dd_gn0, k_dd_work; k_dd_edges twice (count, fill): a wave per
 //            pair of tiles of 64 nodes; k_dd_sweep until nothing changes; k_dd_msize, k_dd_hist, k_dd_verdict
 //   next     k_dd_keep, k_dd_select, k_dd_write: DD_WRITE_LANES lanes per record
@@ -17,6 +17,7 @@
 #include "../../include/bramble_amd.h"
 #include "barcode_inl.h"
 #include "dedup_kernels.h"
+#include "names_inl.h"
 #include "wave_inl.h"
 
 namespace br {
@@ -28,24 +29,6 @@ __device__ __forceinline__ uint32_t ld32(const uint8_t *p) { return ld16(p) | ld
 __device__ __forceinline__ uint64_t fmix64(uint64_t h) {   // (murmur3's)
   h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
   return h;
-}
-// one atomic a wave for a per-lane condition
-__device__ __forceinline__ void count_lanes(bool cond, unsigned long long *word) {
-  const uint64_t b = __ballot(cond);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(word, (unsigned long long)__popcll((unsigned long long)b));
-}
-__device__ __forceinline__ bool name_rows(const DdAddArgs &A, int64_t g, uint64_t &r0, uint64_t &r1) {
-  r0 = A.row_off[(int64_t)A.group_off[g] - A.ro_bias];
-  r1 = A.row_off[(int64_t)A.group_off[g + 1] - A.ro_bias];
-  return r0 >= A.r_first && r1 <= A.r_last && r0 <= r1;
-}
-// row r's record: false where its offsets descend, leave the add's bytes or are too close for the fixed fields
-__device__ __forceinline__ bool record_of(const DdAddArgs &A, uint64_t r, const uint8_t *&rec, uint64_t &len) {
-  const uint64_t *ro = A.rec_off - A.rec_bias;
-  const uint64_t first = ro[A.r_first], last = ro[A.r_last], at = ro[r], next = ro[r + 1];
-  if (at < first || next < at || next > last || next - at < (uint64_t)DD_MIN_RECORD) return false;
-  rec = A.data + (at - A.data_bias); len = next - at;
-  return true;
 }
 // reference bases of one op: M D N = X (0, 2, 3, 7, 8) consume the reference
 __device__ __forceinline__ uint64_t ref_len(uint32_t w) { return (0x18du >> (w & 15u)) & 1u ? (uint64_t)(w >> 4) : 0ull; }
@@ -78,25 +61,26 @@ __device__ __forceinline__ uint32_t cell_of(const DdAddArgs &A, const uint8_t *r
 
 // ---- add -----------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_dd_rows(DdAddArgs A) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x, n = A.r_last - A.r_first;
+  const NameWindow &N = A.names;
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x, n = N.r_last - N.r_first;
   const int lane = threadIdx.x & 63;
   bool bad = false, live = false;
   uint32_t t = 0, f = 0, wide_n = 0;
   uint64_t pos = 0, lead = 0, trail = 0, reflen = 0, wide_off = 0;
   if (i < n) {
-    const uint64_t r = A.r_first + i;
+    const uint64_t r = N.r_first + i;
     const uint4 m = A.a[(int64_t)r - A.a_bias];
     const uint64_t c = A.cigar[(int64_t)r - A.a_bias];
     const uint32_t nc = BR_ROW_NCIGAR(m.z);
     const uint8_t *rec; uint64_t len;
     t = m.x; pos = m.y;
-    if (!record_of(A, r, rec, len)) bad = true;
+    if (!record_of(N, A.recs, r, rec, len)) bad = true;
     else {
       f = ld16(rec + 18) & 0xD1u;
       if (A.rec_at) {
-        const uint64_t *ro = A.rec_off - A.rec_bias;
-        A.rec_at[i] = A.arena_base + (ro[r] - ro[A.r_first]);
-        if (i == n - 1) A.rec_at[n] = A.arena_base + (ro[r + 1] - ro[A.r_first]);
+        const uint64_t *ro = A.recs.rec_off - A.recs.rec_bias;
+        A.rec_at[i] = A.arena_base + (ro[r] - ro[N.r_first]);
+        if (i == n - 1) A.rec_at[n] = A.arena_base + (ro[r + 1] - ro[N.r_first]);
       }
       if (nc <= 2u) {
         const uint32_t o0 = (uint32_t)c, o1 = (uint32_t)(c >> 32);
@@ -141,7 +125,7 @@ __global__ void __launch_bounds__(256) k_dd_rows(DdAddArgs A) {
 
 // the entries of name g in order and their hash: one lane
 __device__ __forceinline__ void sig_small(const DdAddArgs &A, uint64_t r0, uint64_t r1, uint64_t o, uint64_t &hash) {
-  const uint4 *raw = A.raw + (r0 - A.r_first);
+  const uint4 *raw = A.raw + (r0 - A.names.r_first);
   const uint32_t k = (uint32_t)(r1 - r0);
   uint64_t sum = 0;
   for (uint32_t j = 0; j < k; j++) {
@@ -157,17 +141,17 @@ __device__ __forceinline__ void sig_small(const DdAddArgs &A, uint64_t r0, uint6
 __global__ void __launch_bounds__(256) k_dd_names(DdAddArgs A) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   bool is_big = false, is_bad = false, no_umi = false, too_long = false, bad_aux = false;
-  if (g < A.n_groups) {
+  if (g < A.names.n_groups) {
     uint64_t r0, r1, w[4] = {0, 0, 0, 0}, cw[4] = {0, 0, 0, 0};
     uint32_t ul = 0, cl = 0;
-    if (!name_rows(A, g, r0, r1)) { is_bad = true; A.noff[g] = 4 * A.row_base; A.nk[g] = 0; A.hash[g] = 0; }
+    if (!name_rows(A.names, g, r0, r1)) { is_bad = true; A.noff[g] = 4 * A.row_base; A.nk[g] = 0; A.hash[g] = 0; }
     else {
-      const uint64_t o = 4 * (A.row_base + (r0 - A.r_first));
+      const uint64_t o = 4 * (A.row_base + (r0 - A.names.r_first));
       A.noff[g] = o; A.nk[g] = (uint32_t)(4 * (r1 - r0));
       if (r1 - r0 >= (1ull << 30)) is_bad = true;   // (the signature's length in words is 32-bit)
       else if (r1 > r0) {
         const uint8_t *rec; uint64_t len;
-        if (record_of(A, r0, rec, len)) {
+        if (record_of(A.names, A.recs, r0, rec, len)) {
           ul = umi_of(A, rec, len, w, too_long, bad_aux); no_umi = ul == 0u;
           if (A.cell_source) cl = cell_of(A, rec, len, cw);
         }
@@ -205,8 +189,8 @@ __global__ void __launch_bounds__(256) k_dd_sig_big(DdAddArgs A) {
   for (uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6); b < n_big; b += gridDim.x * 4) {
     const int64_t g = A.big[b];
     uint64_t r0, r1;
-    (void)name_rows(A, g, r0, r1);   // (k_dd_names listed it: its rows are inside the add's)
-    const uint4 *raw = A.raw + (r0 - A.r_first);
+    (void)name_rows(A.names, g, r0, r1);   // (k_dd_names listed it: its rows are inside the add's)
+    const uint4 *raw = A.raw + (r0 - A.names.r_first);
     const uint64_t k = r1 - r0, o = A.noff[g];
     uint64_t sum = 0;
     for (uint64_t j = (uint64_t)lane; j < k; j += 64) {
@@ -222,10 +206,10 @@ __global__ void __launch_bounds__(256) k_dd_sig_big(DdAddArgs A) {
 }
 
 void launch_dd_add(hipStream_t st, const DdAddArgs &A) {
-  const uint64_t n = A.r_last - A.r_first;
+  const uint64_t n = A.names.r_last - A.names.r_first;
   if (n) hipLaunchKernelGGL(k_dd_rows, dim3(blocks256((int64_t)n)), dim3(256), 0, st, A);
-  if (A.n_groups > 0) {
-    hipLaunchKernelGGL(k_dd_names, dim3(blocks256(A.n_groups)), dim3(256), 0, st, A);
+  if (A.names.n_groups > 0) {
+    hipLaunchKernelGGL(k_dd_names, dim3(blocks256(A.names.n_groups)), dim3(256), 0, st, A);
     hipLaunchKernelGGL(k_dd_sig_big, dim3(DD_BIG_GRID), dim3(256), 0, st, A);
   }
 }
@@ -241,49 +225,6 @@ __global__ void __launch_bounds__(256) k_dd_groups(const uint64_t *gid, const ui
 }
 void launch_dd_groups(hipStream_t st, const uint64_t *gid, const uint64_t *gbeg, const uint32_t *idx, int64_t n, uint32_t *group_first, uint32_t *name_gid) {
   if (n > 0) hipLaunchKernelGGL(k_dd_groups, dim3(blocks256(n)), dim3(256), 0, st, gid, gbeg, idx, n, group_first, name_gid);
-}
-
-__global__ void __launch_bounds__(256) k_dd_ukey(const uint32_t *idx, const uint64_t *umi, const uint8_t *ulen, const uint32_t *name_gid, int64_t n, int w,
-                                                 uint64_t *key) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t i = idx[j];
-  key[j] = w < 4 ? umi[4 * (uint64_t)i + w] : ((uint64_t)name_gid[i] << 8 | (uint64_t)ulen[i]);
-}
-void launch_dd_ukey(hipStream_t st, const uint32_t *idx, const uint64_t *umi, const uint8_t *ulen, const uint32_t *name_gid, int64_t n, int w, uint64_t *key) {
-  if (n > 0) hipLaunchKernelGGL(k_dd_ukey, dim3(blocks256(n)), dim3(256), 0, st, idx, umi, ulen, name_gid, n, w, key);
-}
-
-__global__ void __launch_bounds__(256) k_dd_nheads(const uint32_t *idx, const uint64_t *umi, const uint8_t *ulen, const uint32_t *name_gid, int64_t n,
-                                                   uint64_t *head) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  uint64_t h = 1;
-  if (j > 0) {
-    const uint64_t a = idx[j], b = idx[j - 1];
-    h = (ulen[a] == 0 || ulen[a] != ulen[b] || name_gid[a] != name_gid[b] || umi[4 * a] != umi[4 * b] || umi[4 * a + 1] != umi[4 * b + 1] ||
-         umi[4 * a + 2] != umi[4 * b + 2] || umi[4 * a + 3] != umi[4 * b + 3]) ? 1 : 0;
-  }
-  head[j] = h;
-}
-void launch_dd_nheads(hipStream_t st, const uint32_t *idx, const uint64_t *umi, const uint8_t *ulen, const uint32_t *name_gid, int64_t n, uint64_t *head) {
-  if (n > 0) hipLaunchKernelGGL(k_dd_nheads, dim3(blocks256(n)), dim3(256), 0, st, idx, umi, ulen, name_gid, n, head);
-}
-
-__global__ void __launch_bounds__(256) k_dd_cheads(const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, const uint32_t *name_gid, int64_t n,
-                                                   uint64_t *head) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  uint64_t h = 1;
-  if (j > 0) {
-    const uint64_t a = idx[j], b = idx[j - 1];
-    h = (cblen[a] != cblen[b] || name_gid[a] != name_gid[b] || cb[4 * a] != cb[4 * b] || cb[4 * a + 1] != cb[4 * b + 1] ||
-         cb[4 * a + 2] != cb[4 * b + 2] || cb[4 * a + 3] != cb[4 * b + 3]) ? 1 : 0;
-  }
-  head[j] = h;
-}
-void launch_dd_cheads(hipStream_t st, const uint32_t *idx, const uint64_t *cb, const uint8_t *cblen, const uint32_t *name_gid, int64_t n, uint64_t *head) {
-  if (n > 0) hipLaunchKernelGGL(k_dd_cheads, dim3(blocks256(n)), dim3(256), 0, st, idx, cb, cblen, name_gid, n, head);
 }
 
 __global__ void __launch_bounds__(256) k_dd_node_key(const uint64_t *nbeg, const uint32_t *idx, const uint32_t *name_gid, int64_t n_nodes, uint64_t *key,

@@ -86,8 +86,10 @@
 #include <vector>
 
 #include "accum.h"
+#include "barcode_sort.h"
 #include "collate_kernels.h"
 #include "ctx.h"
+#include "name_window.h"
 #include "quant_kernels.h"
 #include "quant_view.h"
 #include "scan_kernels.h"
@@ -172,9 +174,7 @@ extern "C" int br_quant_new(int device, int64_t n_transcripts, const int64_t *le
   br_quant *c = new br_quant();
   c->n_tx = n_transcripts;
   if (lengths) c->lens.assign(lengths, lengths + n_transcripts);
-  int rc = c->open(device);
-  if (!rc) rc = c->alloc(c->small, QS_WORDS * 8);
-  if (!rc && (hipMemsetAsync(c->small.p, 0, QS_WORDS * 8, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) rc = BR_ERR_HIP;
+  const int rc = c->open(device, c->small, QS_WORDS);
   if (rc) { br_quant_free(c); return rc; }
   *out = c;
   return BR_OK;
@@ -227,11 +227,12 @@ static int quant_reserve(br_quant *c, int64_t m, uint64_t rows) {
   return BR_OK;
 }
 
-// the names of one add, their tables on the device (A: a, row_off, group_off, the biases, r_first, r_last and n_groups are set;
-// cigar, pool and n_pool_words as well when the fragments are counted)
+// the names of one add, their tables on the device (A: a, a_bias and names are set; cigar, pool and n_pool_words as well when the
+// fragments are counted)
 static int quant_add_names(br_quant *c, QAddArgs A) {
   hipStream_t st = c->st;
-  RC(quant_reserve(c, A.n_groups, A.r_last - A.r_first));
+  const uint64_t m = A.names.r_last - A.names.r_first;
+  RC(quant_reserve(c, A.names.n_groups, m));
   if (A.cigar) RC(c->fld_tables());
   uint64_t *small = c->small.as<uint64_t>();
   HIPCHK(hipMemsetAsync(small + QS_NBIG, 0, 8, st)); HIPCHK(hipMemsetAsync(small + QS_BAD, 0, 8, st));
@@ -252,54 +253,32 @@ static int quant_add_names(br_quant *c, QAddArgs A) {
     return BR_ERR_INVALID_ARG;
   }
   if (A.cigar) launch_q_fld_commit(st, A.stage, c->fld_total.as<unsigned long long>(), (uint32_t)c->fld_words());
-  c->rows += A.r_last - A.r_first; c->n += A.n_groups;
+  c->rows += m; c->n += A.names.n_groups;
   return BR_OK;
 }
 
 // rows: a and row_off; cigar, pool, n_pool_words and n_rows as well when the fragments are counted (cigar != NULL)
-static int quant_add_device(br_quant *c, const br_device_rows &rows, const uint32_t *group_off, int64_t ng, hipStream_t caller) {
-  const br_row_a *a = rows.a; const uint64_t *row_off = rows.row_off;
-  hipStream_t st = c->st;
-  RC(c->after(caller));   // after whatever made the rows
-  uint64_t *small = c->small.as<uint64_t>();
-  launch_q_span(st, row_off, group_off, ng, small + QS_SPAN);
-  uint64_t span[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(span, small + QS_SPAN, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (span[1] < span[0] || (rows.cigar && span[1] > (uint64_t)rows.n_rows)) return BR_ERR_INVALID_ARG;
-  QAddArgs A{};
-  A.a = (const uint4 *)a; A.row_off = row_off; A.group_off = group_off; A.n_groups = ng; A.r_first = span[0]; A.r_last = span[1];
-  A.cigar = rows.cigar; A.pool = rows.pool; A.n_pool_words = (uint64_t)rows.n_pool_words;
-  return quant_add_names(c, A);
-}
-
-static int quant_add_host(br_quant *c, const br_device_rows &rows, const uint32_t *group_off, int64_t ng) {
-  const uint64_t *row_off = rows.row_off;
-  const uint32_t a0 = group_off[0], a1 = group_off[ng];
-  for (int64_t g = 0; g < ng; g++) if (group_off[g + 1] < group_off[g]) return BR_ERR_INVALID_ARG;
-  for (uint32_t i = a0; i < a1; i++) if (row_off[i + 1] < row_off[i]) return BR_ERR_INVALID_ARG;
-  const uint64_t r0 = row_off[a0], r1 = row_off[a1];
-  if (rows.cigar && r1 > (uint64_t)rows.n_rows) return BR_ERR_INVALID_ARG;
-  RowWindow w;   // a and, when the fragments are counted, the CIGAR references and the pool
-  ColBuf d_ro, d_go;
-  DropGuard dropper{c, {&w.a, &w.cigar, &w.pool, &d_ro, &d_go}};
-  RC(c->upload_rows(rows, r0, r1, rows.cigar != nullptr, w));
-  RC(c->alloc(d_ro, (size_t)(a1 - a0 + 1) * 8)); RC(c->alloc(d_go, (size_t)(ng + 1) * 4));
-  hipStream_t st = c->st;
-  HIPCHK(hipMemcpyAsync(d_ro.p, row_off + a0, (size_t)(a1 - a0 + 1) * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_go.p, group_off, (size_t)(ng + 1) * 4, hipMemcpyHostToDevice, st));
-  QAddArgs A{};
-  A.a = w.a.as<uint4>(); A.a_bias = w.bias; A.row_off = d_ro.as<uint64_t>(); A.ro_bias = (int64_t)a0;
-  A.group_off = d_go.as<uint32_t>(); A.n_groups = ng; A.r_first = r0; A.r_last = r1;
-  A.cigar = w.cigar.as<uint64_t>(); A.pool = w.pool.as<uint32_t>(); A.n_pool_words = w.n_pool_words;
-  return quant_add_names(c, A);   // (it waits for the stream: the uploads are done when the host arrays go)
-}
-
 static int quant_add(br_quant *c, const br_device_rows &rows, const uint32_t *group_off, int64_t n_groups, int on_device, void *stream) {
   if (n_groups == 0) return BR_OK;
   ScopeTimer timer(&c->add_s);
   HIPCHK(hipSetDevice(c->device));
-  return on_device ? quant_add_device(c, rows, group_off, n_groups, (hipStream_t)stream) : quant_add_host(c, rows, group_off, n_groups);
+  uint64_t span[2] = {0, 0};
+  const uint64_t n_rows = rows.cigar ? (uint64_t)rows.n_rows : ~0ull;   // without the CIGARs nothing says how many rows there are
+  RC(names_span(c, rows.row_off, n_rows, group_off, n_groups, on_device != 0, (hipStream_t)stream, c->small.as<uint64_t>() + QS_SPAN, span));
+  RowWindow w;   // host tables: a and, when the fragments are counted, the CIGAR references and the pool
+  ColBuf d_ro, d_go;
+  DropGuard dropper{c, {&w.a, &w.cigar, &w.pool, &d_ro, &d_go}};
+  QAddArgs A{};
+  if (on_device) {
+    A.a = (const uint4 *)rows.a; A.names = device_names(rows.row_off, group_off, n_groups, span);
+    A.cigar = rows.cigar; A.pool = rows.pool; A.n_pool_words = (uint64_t)rows.n_pool_words;
+  } else {
+    RC(c->upload_rows(rows, span[0], span[1], rows.cigar != nullptr, w));
+    RC(upload_names(c, rows.row_off, group_off, n_groups, span, d_ro, d_go, &A.names));
+    A.a = w.a.as<uint4>(); A.a_bias = w.bias;
+    A.cigar = w.cigar.as<uint64_t>(); A.pool = w.pool.as<uint32_t>(); A.n_pool_words = w.n_pool_words;
+  }
+  return quant_add_names(c, A);   // (it waits for the stream: the uploads are done when the host arrays go)
 }
 
 extern "C" int br_quant_add(br_quant *c, const br_row_a *a, const uint64_t *row_off, const uint32_t *group_off, int64_t n_groups,
@@ -354,19 +333,8 @@ extern "C" int br_quant_drop_names(br_quant *c, const uint8_t *flags, int64_t n,
 }
 
 static int quant_tmp(br_quant *c, int64_t n) { return c->alloc(c->tmp, scan_tmp_bytes(n)); }
-// the radix sort of (key, idx) over the digits in which the keys differ (launch_q_bits finds them); *cur = the buffer that holds the result
-static int quant_sort(br_quant *c, ColBuf key[2], ColBuf idx[2], int64_t n, int *cur) {
-  hipStream_t st = c->st;
-  uint64_t *small = c->small.as<uint64_t>();
-  *cur = 0;
-  if (n <= 0) return BR_OK;
-  RC(quant_tmp(c, n));
-  launch_q_bits(st, key[0].as<uint64_t>(), n, c->tmp.as<uint64_t>(), small + QS_BITS);
-  uint64_t bits[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(bits, small + QS_BITS, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return c->radix_sort(key, idx, n, bits, c->tmp, cur);
-}
+// the radix sort of (key[0], idx[0]) over the digits in which the keys differ (barcode_sort.h): the sorted pairs are those of [0]
+static int quant_sort(br_quant *c, ColBuf key[2], ColBuf idx[2], int64_t n) { return sort_pairs(c, key, idx, n, c->tmp, c->small.as<uint64_t>() + QS_BITS); }
 
 // The classes of n items, for every level of the quantifier.  Item i owns the list lab[off[i] .. off[i] + k[i]); its first name is
 // first[i] (NULL: i itself -- the item is a read name) and it stands for weight[i] names (NULL: one).  key[0] / idx[0] hold the n
@@ -383,13 +351,12 @@ static int quant_classes(br_quant *c, const uint32_t *lab, const uint64_t *off, 
   uint64_t *small = c->small.as<uint64_t>();
   ColBuf head, mark, pre, gbeg, key2[2], val2[2], inv;
   DropGuard sort_bufs{c, {&key[0], &key[1], &idx[0], &idx[1], &head, &mark, &pre, &gbeg, &key2[0], &key2[1], &val2[0], &val2[1], &inv}};
-  int cur = 0;
-  RC(quant_sort(c, key, idx, n, &cur));
+  RC(quant_sort(c, key, idx, n));
   // class heads; runs of equal hashes with different lists are put in order and the heads found again
   RC(c->alloc(head, (size_t)(n + 1) * 8));
   auto heads = [&](uint32_t *mk, uint64_t *n_coll) -> int {
     HIPCHK(hipMemsetAsync(small + QS_COLL, 0, 8, st));
-    launch_q_heads(st, lab, off, k, key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), n, head.as<uint64_t>(), (unsigned long long *)(small + QS_COLL), mk);
+    launch_q_heads(st, lab, off, k, key[0].as<uint64_t>(), idx[0].as<uint32_t>(), n, head.as<uint64_t>(), (unsigned long long *)(small + QS_COLL), mk);
     HIPCHK(hipMemcpyAsync(n_coll, small + QS_COLL, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return BR_OK;
@@ -401,8 +368,8 @@ static int quant_classes(br_quant *c, const uint32_t *lab, const uint64_t *off, 
     RC(c->alloc(mark, (size_t)n * 4));
     HIPCHK(hipMemsetAsync(mark.p, 0, (size_t)n * 4, st));
     RC(heads(mark.as<uint32_t>(), &n_coll));
-    launch_q_resolve(st, lab, off, k, key[cur].as<uint64_t>(), idx[cur].as<uint32_t>(), n, mark.as<uint32_t>(), key[cur ^ 1].as<uint64_t>(), idx[cur ^ 1].as<uint32_t>());
-    cur ^= 1;
+    launch_q_resolve(st, lab, off, k, key[0].as<uint64_t>(), idx[0].as<uint32_t>(), n, mark.as<uint32_t>(), key[1].as<uint64_t>(), idx[1].as<uint32_t>());
+    std::swap(key[0], key[1]); std::swap(idx[0], idx[1]);
     RC(heads(nullptr, &n_coll));
   }
   RC(quant_tmp(c, n));
@@ -417,21 +384,20 @@ static int quant_classes(br_quant *c, const uint32_t *lab, const uint64_t *off, 
   launch_col_gbeg(st, head.as<uint64_t>(), n, gbeg.as<uint64_t>());
   if (weight) {   // a class's count: the integer sum of its items' weights, from one scan over the items in sorted order
     RC(c->alloc(pre, (size_t)(n + 1) * 8));
-    launch_qg_member_cnt(st, idx[cur].as<uint32_t>(), weight, n, pre.as<uint64_t>());
+    launch_qg_member_cnt(st, idx[0].as<uint32_t>(), weight, n, pre.as<uint64_t>());
     launch_scan(st, pre.as<uint64_t>(), n, c->tmp.as<uint64_t>());
   }
   // the classes by their first name
   RC(c->alloc(key2[0], c1 * 8)); RC(c->alloc(key2[1], c1 * 8)); RC(c->alloc(val2[0], c1 * 4)); RC(c->alloc(val2[1], c1 * 4));
-  launch_q_class_key(st, gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), first, (int64_t)C, key2[0].as<uint64_t>(), val2[0].as<uint32_t>());
-  int cur2 = 0;
-  RC(quant_sort(c, key2, val2, (int64_t)C, &cur2));
+  launch_q_class_key(st, gbeg.as<uint64_t>(), idx[0].as<uint32_t>(), first, (int64_t)C, key2[0].as<uint64_t>(), val2[0].as<uint32_t>());
+  RC(quant_sort(c, key2, val2, (int64_t)C));
   RC(c->alloc(out.first, c1 * 8)); RC(c->alloc(out.cnt, c1 * 8)); RC(c->alloc(out.loff, c1 * 8));
   if (rep) RC(c->alloc(*rep, c1 * 4));
-  launch_q_class_fill(st, key2[cur2].as<uint64_t>(), val2[cur2].as<uint32_t>(), gbeg.as<uint64_t>(), idx[cur].as<uint32_t>(), pre.as<uint64_t>(), k, (int64_t)C,
+  launch_q_class_fill(st, key2[0].as<uint64_t>(), val2[0].as<uint32_t>(), gbeg.as<uint64_t>(), idx[0].as<uint32_t>(), pre.as<uint64_t>(), k, (int64_t)C,
                       out.first.as<uint64_t>(), out.cnt.as<uint64_t>(), out.loff.as<uint64_t>(), rep ? rep->as<uint32_t>() : nullptr);
   if (name_cls) {   // sorted item -> head rank -> rank after the second sort -> name_cls[item], while the sort's tables are still here
     RC(c->alloc(inv, c1 * 4));
-    launch_q_name_cls(st, head.as<uint64_t>(), idx[cur].as<uint32_t>(), n, val2[cur2].as<uint32_t>(), (int64_t)C, inv.as<uint32_t>(), name_cls);
+    launch_q_name_cls(st, head.as<uint64_t>(), idx[0].as<uint32_t>(), n, val2[0].as<uint32_t>(), (int64_t)C, inv.as<uint32_t>(), name_cls);
   }
   RC(quant_tmp(c, (int64_t)C));
   launch_scan(st, out.loff.as<uint64_t>(), (int64_t)C, c->tmp.as<uint64_t>());
@@ -505,9 +471,8 @@ static int quant_finish(br_quant *c) {
   HIPCHK(hipStreamSynchronize(st));
   if (bad) return BR_ERR_INVALID_ARG;   // a transcript of length <= 0 has reads, and lengths normalise
   c->drop(c->lab); c->drop(c->noff); c->drop(c->nk); c->drop(c->hash); c->drop(c->big);   // the names are classes now
-  int cur3 = 0;
-  RC(quant_sort(c, tkey, tidx, L, &cur3));
-  launch_q_transpose(st, tkey[cur3].as<uint64_t>(), tidx[cur3].as<uint32_t>(), ecls.as<uint32_t>(), L, T, c->t_cls.as<uint32_t>(), c->t_off.as<uint64_t>());
+  RC(quant_sort(c, tkey, tidx, L));
+  launch_q_transpose(st, tkey[0].as<uint64_t>(), tidx[0].as<uint32_t>(), ecls.as<uint32_t>(), L, T, c->t_cls.as<uint32_t>(), c->t_off.as<uint64_t>());
   // the wave-sized items
   const size_t most = (size_t)(L / (Q_WAVE_ITEMS + 1) + 1);
   RC(c->alloc(c->big_cls, most * 4)); RC(c->alloc(c->big_tx, most * 4));
@@ -944,17 +909,16 @@ static int quant_genes(br_quant *c, const uint32_t *tx_gene, int64_t G) {
     HIPCHK(hipMemcpyAsync(d_txg.p, tx_gene, (size_t)T * 4, hipMemcpyHostToDevice, st));
     RC(c->alloc(key[0], l1 * 8)); RC(c->alloc(key[1], l1 * 8)); RC(c->alloc(idx[0], l1 * 4)); RC(c->alloc(idx[1], l1 * 4));
     launch_qg_key(st, c->cls.loff.as<uint64_t>(), c->cls.labels.as<uint32_t>(), d_txg.as<uint32_t>(), C, L, key[0].as<uint64_t>(), idx[0].as<uint32_t>());
-    int cur = 0;
-    RC(quant_sort(c, key, idx, L, &cur));
+    RC(quant_sort(c, key, idx, L));
     RC(c->alloc(pos, l1 * 8)); RC(quant_tmp(c, L));
-    launch_qg_flag(st, key[cur].as<uint64_t>(), L, pos.as<uint64_t>());
+    launch_qg_flag(st, key[0].as<uint64_t>(), L, pos.as<uint64_t>());
     launch_scan(st, pos.as<uint64_t>(), L, c->tmp.as<uint64_t>());
     uint64_t LE = 0;
     HIPCHK(hipMemcpyAsync(&LE, pos.as<uint64_t>() + L, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (LE == 0 || LE > (uint64_t)L) return BR_ERR_HIP;
     RC(c->alloc(glab, ((size_t)LE + 1) * 4)); RC(c->alloc(goff, c1 * 8)); RC(c->alloc(gk, c1 * 4));
-    launch_qg_arena(st, key[cur].as<uint64_t>(), pos.as<uint64_t>(), c->cls.loff.as<uint64_t>(), L, C, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>());
+    launch_qg_arena(st, key[0].as<uint64_t>(), pos.as<uint64_t>(), c->cls.loff.as<uint64_t>(), L, C, glab.as<uint32_t>(), goff.as<uint64_t>(), gk.as<uint32_t>());
     HIPCHK(hipStreamSynchronize(st));
     c->drop(d_txg); c->drop(pos);
     for (int k = 0; k < 2; k++) { c->drop(key[k]); c->drop(idx[k]); }

@@ -4,19 +4,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "names.h"
+
 namespace br {
 
 constexpr int Q_SMALL_ROWS = 16;   // a read name of up to this many rows is one lane's work in k_q_names, a larger one a wave's
 constexpr int Q_WAVE_ITEMS = 64;   // a class of more labels / a transcript in more classes than this is a wave's work in the EM
 constexpr unsigned Q_BIG_GRID = 1024;   // blocks (of 4 waves) that walk a list whose length only the device knows
 
-// One add.  Rows, row_off and group_off may be slices of the caller's tables (a host add uploads only what it needs): element
-// i of the caller's table is at [i - bias] here.
+// One add.  The rows may be a slice of the caller's table (a host add uploads only what it needs): row r is at a[r - a_bias];
+// the names as names.h holds them.
 struct QAddArgs {
   const uint4 *a; int64_t a_bias;              // br_row_a
-  const uint64_t *row_off; int64_t ro_bias;
-  const uint32_t *group_off; int64_t n_groups;
-  uint64_t r_first, r_last;   // row_off[group_off[0]], row_off[group_off[n_groups]]: the add's rows
+  NameWindow names;
   uint64_t lab_base;          // arena slot of row r_first
   uint32_t *lab;              // label arena: a name's list sits at the slot of its first row (as many slots as it has rows)
   uint64_t *noff; uint32_t *nk; uint64_t *hash;   // per name, at the add's first name: arena offset, labels, hash of (k, labels)

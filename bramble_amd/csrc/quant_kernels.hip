@@ -33,6 +33,7 @@
 
 #include "../../include/bramble_amd.h"
 #include "collate_kernels.h"
+#include "names_inl.h"
 #include "quant_kernels.h"
 #include "wave_inl.h"
 
@@ -47,11 +48,6 @@ __device__ __forceinline__ uint64_t hash_end(uint64_t h, uint64_t k) {
   return h;
 }
 // the rows of name g of the add: false when they leave the add's rows
-__device__ __forceinline__ bool name_rows(const QAddArgs &A, int64_t g, uint64_t &r0, uint64_t &r1) {
-  r0 = A.row_off[(int64_t)A.group_off[g] - A.ro_bias];
-  r1 = A.row_off[(int64_t)A.group_off[g + 1] - A.ro_bias];
-  return r0 >= A.r_first && r1 <= A.r_last && r0 <= r1;
-}
 // label lists a < b by (k, labels)?  eq: they are equal
 __device__ __forceinline__ bool list_less(const uint32_t *lab, const uint64_t *noff, const uint32_t *nk, uint32_t a, uint32_t b, bool &eq) {
   const uint32_t ka = nk[a], kb = nk[b];
@@ -80,12 +76,12 @@ __global__ void __launch_bounds__(256) k_q_names(QAddArgs A) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   bool is_big = false, is_bad = false;
   uint32_t top = 0;
-  if (g < A.n_groups) {
+  if (g < A.names.n_groups) {
     uint64_t r0, r1;
-    if (!name_rows(A, g, r0, r1)) { is_bad = true; A.noff[g] = A.lab_base; A.nk[g] = 0; A.hash[g] = 0; }
-    else if (r1 - r0 > (uint64_t)Q_SMALL_ROWS) { is_big = true; A.noff[g] = A.lab_base + (r0 - A.r_first); }
+    if (!name_rows(A.names, g, r0, r1)) { is_bad = true; A.noff[g] = A.lab_base; A.nk[g] = 0; A.hash[g] = 0; }
+    else if (r1 - r0 > (uint64_t)Q_SMALL_ROWS) { is_big = true; A.noff[g] = A.lab_base + (r0 - A.names.r_first); }
     else {
-      const uint64_t o = A.lab_base + (r0 - A.r_first);
+      const uint64_t o = A.lab_base + (r0 - A.names.r_first);
       uint32_t k = 0;
       uint64_t h = 1469598103934665603ull, prev = Q_NO_TID;   // (prev: no label yet)
       for (;;) {
@@ -123,7 +119,7 @@ __global__ void __launch_bounds__(256) k_q_names_big(QAddArgs A) {
   for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n_big; i += gridDim.x * 4) {
     const int64_t g = A.big[i];
     uint64_t r0, r1;
-    (void)name_rows(A, g, r0, r1);   // (k_q_names listed it: its rows are inside the add's)
+    (void)name_rows(A.names, g, r0, r1);   // (k_q_names listed it: its rows are inside the add's)
     const uint64_t o = A.noff[g];
     uint32_t k = 0;
     uint64_t h = 1469598103934665603ull, prev = Q_NO_TID;
@@ -204,9 +200,9 @@ __global__ void __launch_bounds__(256) k_q_frag(QAddArgs A) {
   bool unique = false, found = false, is_bad = false;
   uint64_t pos[2] = {0, 0}, ref[2] = {0, 0}, wide_off[2] = {0, 0};
   uint32_t wide_n[2] = {0, 0};   // a CIGAR left to the wave
-  if (g < A.n_groups && A.nk[g] == 1u) {
+  if (g < A.names.n_groups && A.nk[g] == 1u) {
     uint64_t r0, r1;
-    if (name_rows(A, g, r0, r1) && r1 - r0 <= (uint64_t)Q_SMALL_ROWS) {   // (one label: it has a row)
+    if (name_rows(A.names, g, r0, r1) && r1 - r0 <= (uint64_t)Q_SMALL_ROWS) {   // (one label: it has a row)
       unique = true;
       uint64_t fr = 0;
       q_u4 lead = row_a(A, r0), mate = lead;
@@ -268,7 +264,7 @@ __global__ void __launch_bounds__(256) k_q_frag_big(QAddArgs A) {
     const int64_t g = A.big[i];
     if (A.nk[g] != 1u) continue;   // (wave-uniform, as everything below that branches)
     uint64_t r0, r1;
-    (void)name_rows(A, g, r0, r1);
+    (void)name_rows(A.names, g, r0, r1);
     uint64_t fr = Q_NO_ROW;
     for (uint64_t base = r0; fr == Q_NO_ROW && base + 1 < r1; base += 64) {
       // a row is loaded once: the neighbour's transcript and meta come from the next lane, lane 63's from the stride's edge
@@ -940,22 +936,22 @@ void launch_q_span(hipStream_t st, const uint64_t *row_off, const uint32_t *grou
   hipLaunchKernelGGL(k_q_span, dim3(1), dim3(1), 0, st, row_off, group_off, n_groups, span);
 }
 void launch_q_names(hipStream_t st, const QAddArgs &A) {
-  if (A.n_groups <= 0) return;
-  hipLaunchKernelGGL(k_q_names, dim3(blocks256(A.n_groups)), dim3(256), 0, st, A);
-  const int64_t most = (A.n_groups + 3) / 4;   // (the list is no longer than the names)
+  if (A.names.n_groups <= 0) return;
+  hipLaunchKernelGGL(k_q_names, dim3(blocks256(A.names.n_groups)), dim3(256), 0, st, A);
+  const int64_t most = (A.names.n_groups + 3) / 4;   // (the list is no longer than the names)
   hipLaunchKernelGGL(k_q_names_big, dim3((unsigned)(most < (int64_t)Q_BIG_GRID ? most : (int64_t)Q_BIG_GRID)), dim3(256), 0, st, A);
 }
 void launch_q_frag(hipStream_t st, const QAddArgs &A) {
-  if (A.n_groups <= 0) return;
+  if (A.names.n_groups <= 0) return;
   const bool lds = A.fld_max < Q_FLD_LDS_BINS;
   const size_t sh = lds ? (size_t)(A.fld_max + 1u) * 4 : 0;
-  const int64_t most = (A.n_groups + 3) / 4;
+  const int64_t most = (A.names.n_groups + 3) / 4;
   const dim3 big_grid((unsigned)(most < (int64_t)Q_BIG_GRID ? most : (int64_t)Q_BIG_GRID));
   if (lds) {
-    hipLaunchKernelGGL(k_q_frag<true>, dim3(blocks256(A.n_groups)), dim3(256), sh, st, A);
+    hipLaunchKernelGGL(k_q_frag<true>, dim3(blocks256(A.names.n_groups)), dim3(256), sh, st, A);
     hipLaunchKernelGGL(k_q_frag_big<true>, big_grid, dim3(256), sh, st, A);
   } else {
-    hipLaunchKernelGGL(k_q_frag<false>, dim3(blocks256(A.n_groups)), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_q_frag<false>, dim3(blocks256(A.names.n_groups)), dim3(256), 0, st, A);
     hipLaunchKernelGGL(k_q_frag_big<false>, big_grid, dim3(256), 0, st, A);
   }
 }

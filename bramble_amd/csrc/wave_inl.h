@@ -6,6 +6,7 @@
 //
 //   wave_scan<T, W>(v)                                inclusive prefix sum over the group (lane k: v of lanes 0 .. k)
 //   wave_sum / wave_max / wave_min / wave_or / wave_and   butterfly reductions: every lane of the group gets the result
+//   count_lanes(cond, word)                           *word += the wave's lanes with cond, one atomic a wave
 //   block_excl_scan_256(v, sh, total)                 exclusive prefix sum over a block of 256 threads
 //   block_bits(o, a, out)                             OR of o and AND of a over a block of 256 threads (the radix sort's digits)
 //   load8 / store8                                    a thread's eight consecutive scan items as 16-byte accesses
@@ -56,6 +57,12 @@ __device__ __forceinline__ T wave_and(T v) {
 #pragma unroll
   for (int d = W / 2; d >= 1; d >>= 1) v &= __shfl_xor(v, d, W);
   return v;
+}
+
+// one atomic a wave for a per-lane condition (every lane of the wave calls it)
+__device__ __forceinline__ void count_lanes(bool cond, unsigned long long *word) {
+  const uint64_t b = __ballot(cond);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(word, (unsigned long long)__popcll((unsigned long long)b));
 }
 
 // Exclusive prefix sum of v over the block's 256 threads; total = the block's sum, in every thread.  Wave scans by shuffles,

@@ -1,8 +1,8 @@
 // br_whitelist: the allowed cell barcodes in one device's HBM, and the resolution of observed barcodes against them
 // (whitelist_kernels.hip; the definitions are in bramble_amd.h).
 //
-//   new       the barcodes as words in comparison order, uploaded; sorted by (length, bytes) with the cells' five stable radix passes
-//             (barcode_sort.h), cut into the distinct entries by the cells' head flags and a scan; the entries inserted into an
+//   new       the barcodes as words in comparison order, uploaded; sorted by (length, bytes) with the field sort's five stable radix
+//             passes (barcode_sort.h), cut into the distinct entries by its head flags and a scan; the entries inserted into an
 //             open-addressing table of 64-bit slots (a power of two >= 2 W, 64 at least).  Read-only from then on: one object serves
 //             any number of accumulators on its device
 //   resolve   (wl_resolve: br_cells_finish, br_dedup_finish and br_whitelist_match call it on their own tables, on their own stream)
@@ -21,7 +21,6 @@
 
 #include "accum.h"
 #include "barcode_sort.h"
-#include "cells_kernels.h"
 #include "collate_kernels.h"
 #include "scan_kernels.h"
 #include "whitelist.h"
@@ -51,15 +50,6 @@ static void words_of(const uint8_t *cb, const uint8_t *len, int64_t n, std::vect
     for (uint32_t b = 0; b < len[i]; b++) words[(size_t)i * 4 + (b >> 3)] |= (uint64_t)cb[(size_t)i * 32 + b] << (56 - 8 * (b & 7));
 }
 
-// flag (n items, then one more) scanned in place; -> its total
-static int wl_scan(Accum *c, ColBuf &flag, int64_t n, ColBuf &tmp, uint64_t *total) {
-  RC(c->alloc(tmp, scan_tmp_bytes(n)));
-  launch_scan(c->st, flag.as<uint64_t>(), n, tmp.as<uint64_t>());
-  HIPCHK(hipMemcpyAsync(total, flag.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return BR_OK;
-}
-
 static int wl_build(br_whitelist *c, const uint8_t *cb, const uint8_t *len, int64_t n) {
   hipStream_t st = c->st;
   uint64_t *small = c->small.as<uint64_t>();
@@ -76,13 +66,13 @@ static int wl_build(br_whitelist *c, const uint8_t *cb, const uint8_t *len, int6
   HIPCHK(hipMemsetAsync(head.p, 0, n1 * 8, st));
   launch_wl_flag(st, rawlen.as<uint8_t>(), n, head.as<uint64_t>(), nullptr);
   uint64_t all = 0;
-  RC(wl_scan(c, head, n, tmp, &all));
+  RC(c->scan_total(head, n, tmp, &all));
   if (all != (uint64_t)n) return BR_ERR_HIP;
-  launch_cl_compact(st, head.as<uint64_t>(), n, s.idx[0].as<uint32_t>());
-  RC(sort_by_barcode(c, s, raw.as<uint64_t>(), rawlen.as<uint8_t>(), n, tmp, small + WL_BITS));
-  launch_cl_bheads(st, s.idx[0].as<uint32_t>(), raw.as<uint64_t>(), rawlen.as<uint8_t>(), n, head.as<uint64_t>());
+  launch_bc_compact(st, head.as<uint64_t>(), n, s.idx[0].as<uint32_t>());
+  RC(sort_by_barcode(c, s, raw.as<uint64_t>(), rawlen.as<uint8_t>(), nullptr, n, tmp, small + WL_BITS));
+  launch_bc_heads(st, s.idx[0].as<uint32_t>(), raw.as<uint64_t>(), rawlen.as<uint8_t>(), nullptr, 0, n, head.as<uint64_t>());
   uint64_t E = 0;
-  RC(wl_scan(c, head, n, tmp, &E));
+  RC(c->scan_total(head, n, tmp, &E));
   if (E == 0 || E > (uint64_t)n) return BR_ERR_HIP;
   RC(c->alloc(c->cb, ((size_t)E + 1) * 32)); RC(c->alloc(c->len, (size_t)E + 1));
   launch_wl_gather(st, head.as<uint64_t>(), s.idx[0].as<uint32_t>(), n, raw.as<uint64_t>(), rawlen.as<uint8_t>(), c->cb.as<uint64_t>(), c->len.as<uint8_t>());
@@ -114,9 +104,7 @@ extern "C" int br_whitelist_new(int device, const uint8_t *cb, const uint8_t *le
   for (int64_t i = 0; i < n; i++) if (len[i] == 0 || len[i] > 32) return BR_ERR_INVALID_ARG;
   br_whitelist *c = new br_whitelist();
   const ScopeTimer timer;
-  int rc = c->open(device);
-  if (!rc) rc = c->alloc(c->small, WL_WORDS * 8);
-  if (!rc && (hipMemsetAsync(c->small.p, 0, WL_WORDS * 8, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) rc = BR_ERR_HIP;
+  int rc = c->open(device, c->small, WL_WORDS);
   c->hash_bits = hash_bits ? hash_bits : 64;
   c->n_given = (uint64_t)n;
   if (!rc) rc = wl_build(c, cb, len, n);
@@ -127,23 +115,20 @@ extern "C" int br_whitelist_new(int device, const uint8_t *cb, const uint8_t *le
 }
 
 extern "C" int br_whitelist_barcodes(br_whitelist *c, int64_t first, int64_t n, uint8_t *cb, uint8_t *len) {
-  if (!c || first < 0 || n < 0 || (uint64_t)first > c->n_entries || (uint64_t)n > c->n_entries - (uint64_t)first) return BR_ERR_INVALID_ARG;
-  if (n == 0) return BR_OK;
-  HIPCHK(hipSetDevice(c->device));
-  std::vector<uint64_t> words;
-  if (cb) {
-    words.resize((size_t)n * 4);
-    HIPCHK(hipMemcpyAsync(words.data(), c->cb.as<uint64_t>() + 4 * first, (size_t)n * 32, hipMemcpyDeviceToHost, c->st));
-  }
-  if (len) HIPCHK(hipMemcpyAsync(len, c->len.as<uint8_t>() + first, (size_t)n, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  if (cb) for (size_t i = 0; i < (size_t)n * 32; i++) cb[i] = (uint8_t)(words[i >> 3] >> (56 - 8 * (i & 7)));
-  return BR_OK;
+  if (!c || !in_range(c->n_entries, first, n)) return BR_ERR_INVALID_ARG;
+  return c->fetch_fields(c->cb, c->len, first, n, cb, len);
 }
 
 extern "C" int br_whitelist_stats(const br_whitelist *c, uint64_t out[8]) {
   if (!c || !out) return BR_ERR_INVALID_ARG;
   const uint64_t v[8] = {c->n_given, c->n_entries, c->n_slots, c->chain, (uint64_t)(c->build_s * 1e6), (uint64_t)c->hash_bits, c->live, c->peak};
+  memcpy(out, v, sizeof(v));
+  return BR_OK;
+}
+
+int br::wl_stats(const WlResolved &r, int correct, uint64_t out[8]) {
+  if (!out) return BR_ERR_INVALID_ARG;
+  const uint64_t v[8] = {r.status[0], r.status[1], r.status[2], r.status[3], r.status[4], r.distinct, (uint64_t)(r.seconds * 1e6), (uint64_t)correct};
   memcpy(out, v, sizeof(v));
   return BR_OK;
 }
@@ -164,21 +149,21 @@ int br::wl_resolve(Accum *c, const br_whitelist *wl, int correct, uint64_t *cb, 
   uint64_t M = 0;
   RC(c->alloc(flag, ((size_t)N + 1) * 8));
   launch_wl_flag(st, cblen, N, flag.as<uint64_t>(), entry);
-  RC(wl_scan(c, flag, N, tmp, &M));
+  RC(c->scan_total(flag, N, tmp, &M));
   if (M > (uint64_t)N) return BR_ERR_HIP;
   out->status[0] = (uint64_t)N - M;
   if (M == 0) { out->seconds = timer.seconds(); return BR_OK; }
   const int64_t n = (int64_t)M;
   RC(s.make(c, (size_t)M));
-  launch_cl_compact(st, flag.as<uint64_t>(), N, s.idx[0].as<uint32_t>());
+  launch_bc_compact(st, flag.as<uint64_t>(), N, s.idx[0].as<uint32_t>());
   HIPCHK(hipStreamSynchronize(st));
   c->drop(flag);
   // the distinct observed barcodes
-  RC(sort_by_barcode(c, s, cb, cblen, n, tmp, small.as<uint64_t>() + WL_BITS));
+  RC(sort_by_barcode(c, s, cb, cblen, nullptr, n, tmp, small.as<uint64_t>() + WL_BITS));
   uint64_t D = 0;
   RC(c->alloc(head, ((size_t)M + 1) * 8));
-  launch_cl_bheads(st, s.idx[0].as<uint32_t>(), cb, cblen, n, head.as<uint64_t>());
-  RC(wl_scan(c, head, n, tmp, &D));
+  launch_bc_heads(st, s.idx[0].as<uint32_t>(), cb, cblen, nullptr, 0, n, head.as<uint64_t>());
+  RC(c->scan_total(head, n, tmp, &D));
   if (D == 0 || D > M) return BR_ERR_HIP;
   out->distinct = D;
   for (int k = 0; k < 2; k++) c->drop(s.key[k]);
@@ -190,11 +175,11 @@ int br::wl_resolve(Accum *c, const br_whitelist *wl, int correct, uint64_t *cb, 
   launch_wl_exact(st, T, s.idx[0].as<uint32_t>(), obeg.as<uint64_t>(), (int64_t)D, cb, cblen, obs_entry.as<uint32_t>(), count.as<uint64_t>(), miss.as<uint64_t>());
   if (correct) {
     uint64_t m = 0;
-    RC(wl_scan(c, miss, (int64_t)D, tmp, &m));
+    RC(c->scan_total(miss, (int64_t)D, tmp, &m));
     if (m > D) return BR_ERR_HIP;
     if (m) {
       RC(c->alloc(list, ((size_t)m + 1) * 4));
-      launch_cl_compact(st, miss.as<uint64_t>(), (int64_t)D, list.as<uint32_t>());
+      launch_bc_compact(st, miss.as<uint64_t>(), (int64_t)D, list.as<uint32_t>());
       launch_wl_near(st, T, list.as<uint32_t>(), (int64_t)m, s.idx[0].as<uint32_t>(), obeg.as<uint64_t>(), cb, cblen, count.as<uint64_t>(), correct,
                      obs_entry.as<uint32_t>());
     }

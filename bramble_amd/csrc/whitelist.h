@@ -14,6 +14,8 @@ struct WlResolved {
 };
 
 int wl_device(const br_whitelist *wl);
+// br_*_whitelist_stats of an accumulator that resolved against a whitelist: the five statuses, D, microseconds, "correct"
+int wl_stats(const WlResolved &r, int correct, uint64_t out[8]);
 
 // The N names' barcodes cb / cblen (device tables of c, which runs the work on its stream and counts the memory) resolved in place
 // under "correct" 0 .. 2: status (N bytes on the device) and, where given, entry (N words).  Every table of the resolve is dropped

@@ -49,10 +49,6 @@ __device__ __forceinline__ uint32_t wl_probe(const WlTable &T, uint64_t w0, uint
   }
   return WL_NONE;
 }
-__device__ __forceinline__ void count_lanes(bool cond, unsigned long long *word) {
-  const uint64_t b = __ballot(cond);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(word, (unsigned long long)__popcll((unsigned long long)b));
-}
 }  // namespace
 
 // ---- build -----------------------------------------------------------------------------------------------------------------------
