@@ -36,6 +36,7 @@
 
 #include "accum.h"
 #include "coverage_kernels.h"
+#include "coverage_view.h"
 #include "ctx.h"
 #include "name_window.h"
 #include "quant_kernels.h"
@@ -60,11 +61,21 @@ struct br_coverage : Accum {
   int64_t n_names = 0;         // names of all add_names (weight em)
   uint64_t kept = 0;           // entries in the arena
   ColBuf weight_sum, aligned_lo, run_depth, arena;
+  BigwigState *bigwig = nullptr;   // br_coverage_bigwig's image (bigwig.cpp), through coverage_view
   size_t counter_words() const { return weight ? (size_t)CV_WORDS_W : (size_t)CV_WORDS; }
 };
 
+// the hook of bigwig.cpp (coverage_view.h): what a finished object holds
+int br::coverage_view(br_coverage *c, CoverageView *v) {
+  if (!c || c->broken || !c->finished) return BR_ERR_INVALID_ARG;
+  *v = CoverageView{c, c->weight, c->n_tx, c->n_runs, &c->off, c->d_off.as<uint64_t>(), c->diff.p, c->runs.as<uint4>(),
+                    c->weight ? c->run_depth.as<uint64_t>() : nullptr, &c->bigwig};
+  return BR_OK;
+}
+
 extern "C" void br_coverage_free(br_coverage *c) {
   if (!c) return;
+  bigwig_state_free(c, c->bigwig);
   c->close();
   delete c;
 }

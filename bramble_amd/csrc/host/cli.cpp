@@ -52,6 +52,7 @@ void usage(FILE *f) {
           "                [--quant-genes <genes.tsv> [--quant-gene-classes <gene_classes.txt>] [--quant-gene-map <tx2gene.tsv>]]]\n"
           "               [--coverage <cov.bedgraph>] [--coverage-summary <cov.tsv>] [--coverage-primary]\n"
           "               [--coverage-weight unit|nh|em]\n"
+          "               [--coverage-bigwig <cov.bw> [--coverage-bigwig-zooms 0-10] [--coverage-bigwig-uncompressed]]\n"
           "               [--unprojected <unprojected.bam> [--unprojected-scope record|name]]\n"
           "               [--quant-bam <post.bam> [--quant-bam-mode tag|sample]]\n"
           "               [--dedup unique|directional [--dedup-umi name|tag] [--dedup-umi-sep C] [--dedup-umi-tag XY]\n"
@@ -120,6 +121,12 @@ void usage(FILE *f) {
           "fixed point, 32 fractional bits: the bedGraph's depth is printed with %%.10g, and the summary has the columns Name, Length,\n"
           "Records, WeightedRecords, AlignedBases, CoveredBases, MaxDepth, MeanDepth, Breadth.  The report line becomes\n"
           "[bramble] coverage (weight nh|em): ...\n"
+          "--coverage-bigwig FILE: the same depth as a bigWig track (UCSC's binary format, version 4), built and compressed on the GPU: no\n"
+          "text, no sort | bedGraphToBigWig.  Alone or with --coverage / --coverage-summary, with every weight.  Only transcripts with\n"
+          "coverage are in it, in the byte order of their names; one item per bedGraph line, the value a float (24 bits: unit depths\n"
+          "above 16 777 216 lose their low bits).  --coverage-bigwig-zooms N (0 .. 10, default 4): zoom levels of 32, 128, 512, ...\n"
+          "bases per summary.  --coverage-bigwig-uncompressed: plain sections in place of zlib streams.  One more line behind the\n"
+          "coverage line: [bramble] bigwig: C transcripts, S sections of R runs, Z zoom levels (z0, z1, ... records), U -> B bytes (build X.XXs)\n"
           "--unprojected FILE: the input records that no output record came from -- no transcript accepted them, or their matches died\n"
           "at pairing -- written to FILE on the way: a BAM (whatever -O says) under the input's header, the records byte for byte as\n"
           "they came in, in input order.  They are picked out and kept on one GPU while the bundles are projected.  Unmapped input\n"
@@ -194,6 +201,7 @@ int parse_args(int argc, char **argv, Options &o) {
   memset(&o.cfg, 0, sizeof(o.cfg));
   o.cfg.junc_miss_discount = 1.0;
   bool codec = false, host_codec = false;   // a BGZF codec option was given; one that asks for the host codec
+  bool coverage_bigwig_switch_given = false;
   bool coverage_weight_given = false, unprojected_scope_given = false, quant_bam_mode_given = false, dedup_switch_given = false, dedup_bam_mode_given = false, cells_switch_given = false, cells_correct_given = false, cells_filter_switch_given = false;
   auto need = [&](int &i) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "%s: missing value\n", argv[i]); return nullptr; } return argv[++i]; };
   for (int i = 1; i < argc; i++) {
@@ -270,6 +278,13 @@ int parse_args(int argc, char **argv, Options &o) {
     else if (a == "--coverage") { const char *v = value(); if (!v) return -1; o.coverage = v; }
     else if (a == "--coverage-summary") { const char *v = value(); if (!v) return -1; o.coverage_summary = v; }
     else if (a == "--coverage-primary") o.coverage_primary = true;
+    else if (a == "--coverage-bigwig") { const char *v = value(); if (!v) return -1; o.coverage_bigwig = v; }
+    else if (a == "--coverage-bigwig-zooms") {
+      const char *v = value(); long long z = 0;
+      if (!v || !parse_count("--coverage-bigwig-zooms", v, 0, 10, z)) return -1;
+      o.coverage_bigwig_zooms = (int)z; coverage_bigwig_switch_given = true;
+    }
+    else if (a == "--coverage-bigwig-uncompressed") { o.coverage_bigwig_uncompressed = true; coverage_bigwig_switch_given = true; }
     else if (a == "--coverage-weight") {
       const char *v = value(); if (!v) return -1;
       const std::string w = v;
@@ -427,10 +442,12 @@ int parse_args(int argc, char **argv, Options &o) {
   if (!o.quant_fld.empty() && !o.quant_eff_length) { fprintf(stderr, "--quant-fld needs --quant-eff-length: without it no fragment lengths are counted\n"); return -1; }
   if (o.quant_eff_length && o.quant_length_norm == 0) { fprintf(stderr, "--quant-eff-length is a length normalisation: not with --quant-no-length-norm\n"); return -1; }
   if (o.quant_eff_length && (o.cfg.lr || o.cfg.lr_hq) && o.quant_length_norm != 1) { fprintf(stderr, "--quant-eff-length under --lr / --lr-hq needs --quant-length-norm: long reads are not length-normalised by default\n"); return -1; }
-  if (o.coverage_primary && o.coverage.empty() && o.coverage_summary.empty()) { fprintf(stderr, "--coverage-primary needs --coverage or --coverage-summary\n"); return -1; }
-  if (coverage_weight_given && o.coverage.empty() && o.coverage_summary.empty()) { fprintf(stderr, "--coverage-weight needs --coverage or --coverage-summary\n"); return -1; }
+  const bool coverage_wanted = !o.coverage.empty() || !o.coverage_summary.empty() || !o.coverage_bigwig.empty();
+  if (o.coverage_primary && !coverage_wanted) { fprintf(stderr, "--coverage-primary needs --coverage, --coverage-summary or --coverage-bigwig\n"); return -1; }
+  if (coverage_weight_given && !coverage_wanted) { fprintf(stderr, "--coverage-weight needs --coverage, --coverage-summary or --coverage-bigwig\n"); return -1; }
+  if (coverage_bigwig_switch_given && o.coverage_bigwig.empty()) { fprintf(stderr, "--coverage-bigwig-zooms and --coverage-bigwig-uncompressed need --coverage-bigwig\n"); return -1; }
   if (o.coverage_weight == 2 && o.quant.empty()) { fprintf(stderr, "--coverage-weight em needs --quant: the weights are the EM's posteriors\n"); return -1; }
-  if ((!o.coverage.empty() || !o.coverage_summary.empty()) && o.devices.size() > 1) { fprintf(stderr, "--coverage works on one device: give --device N, not a --devices list\n"); return -1; }
+  if (coverage_wanted && o.devices.size() > 1) { fprintf(stderr, "--coverage works on one device: give --device N, not a --devices list\n"); return -1; }
   if (unprojected_scope_given && o.unprojected.empty()) { fprintf(stderr, "--unprojected-scope needs --unprojected\n"); return -1; }
   if (o.unprojected == "-") { fprintf(stderr, "--unprojected needs a file, not standard output: that is the main output's\n"); return -1; }
   if (!o.unprojected.empty() && o.devices.size() > 1) { fprintf(stderr, "--unprojected works on one device: give --device N, not a --devices list\n"); return -1; }

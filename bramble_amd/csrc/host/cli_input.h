@@ -52,6 +52,9 @@ struct Options {
   std::string quant_gene_map;    // --quant-gene-map FILE: transcript<TAB>gene lines that replace the annotation's gene ids
   std::string coverage, coverage_summary;   // --coverage FILE / --coverage-summary FILE: the bedGraph of the depth along every transcript and the per-transcript table (br_coverage)
   bool coverage_primary = false; // --coverage-primary: only primary records count ("primary_only")
+  std::string coverage_bigwig;   // --coverage-bigwig FILE: the depth as a bigWig track, built on the device (br_coverage_bigwig)
+  int coverage_bigwig_zooms = 4; // --coverage-bigwig-zooms N: zoom levels, 0 .. 10
+  bool coverage_bigwig_uncompressed = false;   // --coverage-bigwig-uncompressed: plain sections
   int coverage_weight = 0;       // --coverage-weight unit|nh|em: br_coverage's "weight" (0, 1, 2); em reads the --quant consumer's posteriors
   std::string unprojected;       // --unprojected FILE: the input records without an output record, as a BAM under the input's header
   int unprojected_scope = 1;     // --unprojected-scope record|name: the context's "keep_unprojected" (1, 2)

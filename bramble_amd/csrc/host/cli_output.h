@@ -67,7 +67,7 @@ std::unique_ptr<Consumer> open_as(const RunEnv &env, std::string &err) {
 // --quant-bam read the quantifier (Consumer::quantifier) whose EM quant's finish() has run, cells its classes; false: `err` says which could not be made
 inline bool open_consumers(const RunEnv &env, std::vector<std::unique_ptr<Consumer>> &out, std::string &err) {
   const Options &o = env.o;
-  const std::pair<bool, decltype(&open_sort)> wanted[] = {{o.sort, open_sort}, {o.dedup >= 0, open_dedup}, {!o.quant.empty(), open_quant}, {!o.cells.empty(), open_cells}, {!o.coverage.empty() || !o.coverage_summary.empty(), open_coverage}, {!o.unprojected.empty(), open_unprojected}, {!o.quant_bam.empty(), open_assign}};
+  const std::pair<bool, decltype(&open_sort)> wanted[] = {{o.sort, open_sort}, {o.dedup >= 0, open_dedup}, {!o.quant.empty(), open_quant}, {!o.cells.empty(), open_cells}, {!o.coverage.empty() || !o.coverage_summary.empty() || !o.coverage_bigwig.empty(), open_coverage}, {!o.unprojected.empty(), open_unprojected}, {!o.quant_bam.empty(), open_assign}};
   for (auto &[want, open] : wanted) {
     if (!want) continue;
     out.push_back(open(env, err));

@@ -186,6 +186,7 @@ EXPORTS = ["br_index_build", "br_index_build_flat", "br_index_free", "br_index_n
            "br_coverage_new", "br_coverage_set_param", "br_coverage_add_rows", "br_coverage_add_last", "br_coverage_finish", "br_coverage_runs",
            "br_coverage_depth", "br_coverage_summary", "br_coverage_stats", "br_coverage_free",
            "br_coverage_add_names", "br_coverage_finish_em", "br_coverage_runs64", "br_coverage_depth64", "br_coverage_summary64",
+           "br_coverage_bigwig", "br_coverage_bigwig_read", "br_coverage_bigwig_stats", "br_zlib_sections_device",
            "br_assign_new", "br_assign_set_param", "br_assign_add", "br_assign_add_last", "br_assign_finish", "br_assign_values", "br_assign_next",
            "br_assign_stats", "br_assign_free",
            "br_dedup_new", "br_dedup_set_param", "br_dedup_add", "br_dedup_add_last", "br_dedup_finish", "br_dedup_umis", "br_dedup_result",
@@ -1549,6 +1550,32 @@ def quant_digamma(a, device=0):
     return out[:a.size].reshape(a.shape)
 
 
+class BrBigwigOpts(C.Structure):  # br_bigwig_opts: a field that is 0 takes its default
+    _fields_ = [("items_per_slot", C.c_uint32), ("block_size", C.c_uint32), ("zoom_levels", C.c_int32), ("first_reduction", C.c_uint32),
+                ("compress", C.c_int32)]
+
+
+def zlib_sections(device, payloads, mode=0):
+    """br_zlib_sections_device: every payload (bytes, at most 131072 each) as a zlib stream of its own, made on `device` -> list of
+    bytes.  mode 0: one fixed-Huffman block, or stored where that is not smaller than the payload; 1: stored."""
+    payloads = [bytes(p) for p in payloads]
+    src = np.frombuffer(b"".join(payloads), dtype=np.uint8)
+    off = np.zeros(len(payloads) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(p) for p in payloads], dtype=np.uint64)
+    out_off = np.zeros(len(payloads) + 1, dtype=np.uint64)
+    out = C.c_void_p()
+    L = lib()
+    L.br_zlib_sections_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _P(C.c_void_p), C.c_void_p]
+    L.br_free_buffer.argtypes = [C.c_void_p]
+    check(L.br_zlib_sections_device(int(device), src.ctypes.data if src.size else None, off.ctypes.data, len(payloads), int(mode), C.byref(out),
+                                    out_off.ctypes.data), "br_zlib_sections_device")
+    try:
+        blob = C.string_at(out.value, int(out_off[-1]))
+    finally:
+        L.br_free_buffer(out)
+    return [blob[int(a):int(b)] for a, b in zip(out_off, out_off[1:])]
+
+
 class Coverage(_Accumulator):
     """br_coverage on `device`: the rows of projected batches in, the depth of coverage along every transcript out (runs of equal
     depth, per-transcript summary, the depth itself).  lengths: one per transcript.  set_param: "primary_only" 0 / 1 and "weight"
@@ -1569,7 +1596,11 @@ class Coverage(_Accumulator):
                 "add_names": [C.c_void_p, _P(BrDeviceRows), C.c_void_p, C.c_int64, C.c_int, C.c_void_p],
                 "finish_em": [C.c_void_p, C.c_void_p, _P(C.c_int64)],
                 "runs64": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
-                "depth64": [C.c_void_p, C.c_int64, C.c_void_p], "summary64": [C.c_void_p] * 7}
+                "depth64": [C.c_void_p, C.c_int64, C.c_void_p], "summary64": [C.c_void_p] * 7,
+                "bigwig": [C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_uint64)], "bigwig_read": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p],
+                "bigwig_stats": [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_int32), C.c_void_p, _P(C.c_uint64), _P(C.c_uint64),
+                                 _P(C.c_uint64), _P(C.c_double)]}
+    BIGWIG_PAGE = 64 << 20
 
     def __init__(self, lengths, device=0):
         self.lengths = np.ascontiguousarray(lengths, dtype=np.int64)
@@ -1693,6 +1724,35 @@ class Coverage(_Accumulator):
         self._call("summary", out["records"].ctypes.data, out["aligned_bases"].ctypes.data, out["covered_bases"].ctypes.data,
                    out["max_depth"].ctypes.data)
         return {k: v[:self.n_transcripts] for k, v in out.items()}
+
+    def bigwig_raw(self, names, **opts):
+        """br_coverage_bigwig as it is: (the return code, the size of the image).  names: one per transcript, str, bytes or None."""
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() if isinstance(n, str) else n for n in names])
+        o = BrBigwigOpts(**{k: int(v) for k, v in opts.items()})
+        n = C.c_uint64()
+        return self._raw("bigwig", arr if len(names) else None, C.byref(o) if opts else None, C.byref(n)), int(n.value)
+
+    def bigwig(self, names, page=None, **opts):
+        """After finish: the coverage as a bigWig file image, built on the device and read home in pages -> bytes.  opts: the fields of
+        br_bigwig_opts (items_per_slot, block_size, zoom_levels, first_reduction, compress)."""
+        rc, n = self.bigwig_raw(names, **opts)
+        check(rc, "br_coverage_bigwig")
+        page = int(page or self.BIGWIG_PAGE)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        for first in range(0, n, page):
+            self._call("bigwig_read", first, min(page, n - first), out[first:].ctypes.data)
+        return out[:n].tobytes()
+
+    def bigwig_stats(self):
+        """of the last bigwig(): chromosomes, sections, zoom_levels, zoom_records (per level), raw_bytes and data_bytes (sections and zoom
+        blocks before and after compression), n_bytes (the file), seconds"""
+        nc, ns, rb, db, nb = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        z, sec = C.c_int32(), C.c_double()
+        zr = np.zeros(10, dtype=np.uint64)
+        self._call("bigwig_stats", C.byref(nc), C.byref(ns), C.byref(z), zr.ctypes.data, C.byref(rb), C.byref(db), C.byref(nb), C.byref(sec))
+        return {"chromosomes": int(nc.value), "sections": int(ns.value), "zoom_levels": int(z.value),
+                "zoom_records": [int(v) for v in zr[:z.value]], "raw_bytes": int(rb.value), "data_bytes": int(db.value),
+                "n_bytes": int(nb.value), "seconds": sec.value}
 
     def stats(self):
         rc, rs, cb, h, p = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()

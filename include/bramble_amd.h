@@ -960,6 +960,76 @@ int br_coverage_summary64(br_coverage *, uint64_t *records, uint64_t *weight_sum
                           uint64_t *covered_bases, uint64_t *max_depth);
 void br_coverage_free(br_coverage *);
 
+/* The coverage as a bigWig (Kent et al. 2010; UCSC's bbiFile.h layout, version 4), built and compressed in the device's HBM from what
+ * br_coverage_finish / _finish_em left there (bigwig.cpp, bigwig_kernels.hip; the host's pieces: host/bigwig_file.cpp).  Little-endian.
+ * The file, in order:
+ *   header         64 bytes: u32 magic 0x888FFC26, u16 version 4, u16 zoomLevels, u64 chromosomeTreeOffset, fullDataOffset,
+ *                  fullIndexOffset, u16 fieldCount 0, definedFieldCount 0, u64 autoSqlOffset 0, totalSummaryOffset, u32 uncompressBufSize,
+ *                  u64 extensionOffset 0
+ *   zoom headers   24 bytes a level: u32 reductionLevel, u32 0, u64 dataOffset, indexOffset
+ *   total summary  40 bytes: u64 validCount, f64 minVal, maxVal, sumData, sumSquares
+ *   chromosome tree  32 bytes (u32 magic 0x78CA8C91, blockSize, keySize, valSize 8, u64 itemCount, 0), then nodes: u8 isLeaf, u8 0, u16
+ *                  count; leaf items key[keySize] (zero padded), u32 chromId, chromSize; inner items key (the first key below), u64 childOffset
+ *   full data      u64 sectionCount, then the sections: before compression 24 bytes (u32 chromId, chromStart, chromEnd, itemStep 0,
+ *                  itemSpan 0, u8 type 1 = bedGraph, u8 0, u16 itemCount) and 12 an item (u32 start, end, f32 value)
+ *   full index     an R-tree: 48 bytes (u32 magic 0x2468ACE0, blockSize, u64 itemCount, u32 startChromIx, startBase, endChromIx, endBase, u64
+ *                  endFileOffset = where the indexed data ends, u32 itemsPerSlot 1, u32 0), then nodes: u8 isLeaf, u8 0, u16 count; leaf
+ *                  items 32 bytes (the four u32 bounds, u64 dataOffset, dataSize), inner items 24 (the bounds, u64 childOffset)
+ *   per zoom level its data (u32 recordCount, then blocks of 32-byte records: u32 chromId, chromStart, chromEnd, validCount, f32 minVal,
+ *                  maxVal, sumData, sumSquares) and its R-tree
+ *   u32 magic again
+ * Both kinds of tree are written from the root's level down, each level left to right; a level over n items has ceil(n / blockSize)
+ * nodes of 4 + blockSize x item bytes, the unused tail zero; a tree of at most blockSize items (or of none) is one leaf; blockSize in a
+ * tree's header is min(option, max(itemCount, 1)).  The definitions:
+ *   chromosomes    the transcripts with at least one run, no others.  chromId = the rank of the name in bytewise (strcmp) order, which
+ *                  is not @SQ order; chromSize = L[t]; keySize = the longest of these names.  Sections, zoom records and tree items are
+ *                  ordered by (chromId, start)
+ *   value          weight 0: (float) depth; weighted: (float) ((double) depth64 * 2^-32).  One item a run of br_coverage_runs, neighbours
+ *                  whose values round to the same float included.  A float holds 24 bits: unit depths above 2^24 lose their low bits
+ *   sections       a chromosome's runs in ceil(n / S) sections of S = items_per_slot runs, the last shorter; none spans two
+ *                  chromosomes; chromStart / chromEnd: the first start and the last end
+ *   zoom level k   R = first_reduction * 4^k.  For every chromosome and every aligned window [w R, min((w + 1) R, L)) with a base of
+ *                  depth > 0 one record: validCount = those bases, minVal / maxVal = the values of the least and the greatest depth among
+ *                  them, sumData / sumSquares = the sums of the value and of its square over them, summed in double from the depth array
+ *                  in a fixed order (the same bits every run) and rounded to float.  Blocks of S consecutive records, across chromosomes
+ *   total summary  the same five over all covered bases, in double (from the runs: value x length)
+ *   R-tree bounds  a leaf item: (chromId, start) of its first and (chromId, end) of its last item; an inner item: the lexicographic
+ *                  minimum and maximum of its children
+ *   compression    every section and zoom block is a zlib stream of its own: 0x78 0x9C, one final fixed-Huffman block (RFC 1951 3.2.6)
+ *                  from the greedy parse of the BGZF path, Adler-32 big-endian.  Where that block is not smaller than the payload:
+ *                  stored (BTYPE 00), payload + 11 bytes (a payload above 65535 bytes -- zoom blocks of more than 2047 records --
+ *                  takes a stored block per 65535 bytes, 5 bytes each).  uncompressBufSize = max(24 + 12 S, 32 S); uncompressed: 0.  The
+ *                  compressed bytes are no part of the contract, what they decode to is
+ *   br_coverage_bigwig        after finish, in every weight mode, any number of times: the image of an earlier call goes when the
+ *                  arguments have been accepted.  names: n_transcripts C strings (those of transcripts without runs are not read).  opts
+ *                  or NULL; a field that is 0 takes its default.  *n_bytes = the size of the file.  BR_ERR_INVALID_ARG, with nothing made
+ *                  and an earlier image kept, before finish, for an option out of range (first_reduction * 4^k must stay below 2^31),
+ *                  a NULL or empty name of a transcript with runs, two such transcripts of one name.  BR_ERR_CAPACITY for memory that is
+ *                  not there, 2^32 records in a zoom level: no image is left
+ *   br_coverage_bigwig_read   a host copy of the image's bytes [off, off + n); outside the image, or without one: BR_ERR_INVALID_ARG
+ *   br_coverage_bigwig_stats  of the image: chromosomes, sections, zoom levels, records per level (10 entries), the bytes of all sections
+ *                  and zoom blocks before and after compression, the size of the file, the seconds of the build
+ *   br_zlib_sections_device   the codec alone: section i is src[off[i] .. off[i + 1]) in host memory, at most 131072 bytes (the public
+ *                  file needs 16384 for its sections at the default S); *out (br_free_buffer) holds the streams back to back,
+ *                  out_off[0 .. n] their bounds.  mode 0: the fixed code with the stored fallback; 1: stored
+ * Device memory: the image, I bytes, is in br_coverage_stats' held bytes from the call's return until the next call or
+ * br_coverage_free.  While the call runs every part of the file lies in a buffer of its own, beside them 28 bytes a chromosome, the
+ * raw sections (24 a section, 12 a run) with 24 a section of offsets and bounds, compressed also their slots (9/8 of the raw bytes
+ * and 32 a section) and 8 a section of sizes; a zoom level holds 40 bytes a window until its records are compacted, then 32 a record
+ * and 24 a block; at the end the image beside its parts, so the peak is about 2 I above what finish left (bigwig.cpp). */
+typedef struct br_bigwig_opts {   /* 0 in a field: its default */
+  uint32_t items_per_slot;   /* S: runs per data section, zoom records per zoom block: default 1024, 1 .. 4096 */
+  uint32_t block_size;       /* children per node of both kinds of tree: default 256, 2 .. 4096 */
+  int32_t zoom_levels;       /* default 4; -1: none; at most 10 */
+  uint32_t first_reduction;  /* bases per window at level 0: default 32 */
+  int32_t compress;          /* default 1: zlib sections; -1: uncompressed */
+} br_bigwig_opts;
+int br_coverage_bigwig(br_coverage *, const char *const *names, const br_bigwig_opts *opts, uint64_t *n_bytes);
+int br_coverage_bigwig_read(br_coverage *, uint64_t off, uint64_t n, uint8_t *dst);
+int br_coverage_bigwig_stats(const br_coverage *, uint64_t *n_chromosomes, uint64_t *n_sections, int32_t *zoom_levels, uint64_t *zoom_records,
+                             uint64_t *raw_bytes, uint64_t *data_bytes, uint64_t *n_bytes, double *seconds);
+int br_zlib_sections_device(int device, const uint8_t *src, const uint64_t *off, int64_t n, int mode, uint8_t **out, uint64_t *out_off);
+
 /* br_project_bam_staged / _nowait for records that are in HBM already (a br_bam_reader bundle, or br_bam_split_device's);
  * bgzf_on_device takes the values of br_bam_bundle.bgzf_on_device (0, 1, BR_OUT_SAM_TEXT) */
 int br_project_bam_resident(br_ctx *, const br_config *, const br_device_records *recs, const int32_t *ref_map, int32_t n_ref_map,
@@ -1468,7 +1538,7 @@ const char *const *br_annotation_gene_ids(const br_annotation *);
  * input is inflated and split into records on the GPU, br_bam_reader) / --host-reader, --bundle-size and --device / --devices,
  * --collate, -O bam|sam, --sort [--write-index], --quant FILE [--quant-classes FILE] [--quant-eff-length [--quant-fld FILE]]
  * [--quant-bootstraps B [--quant-seed S] [--quant-boot-out FILE]] [--quant-genes FILE [--quant-gene-classes FILE] [--quant-gene-map FILE]]
- * (br_quant above; the genes are br_annotation_gene_ids', numbered in order of first appearance in @SQ order, or the map file's), --coverage FILE / --coverage-summary FILE [--coverage-primary] [--coverage-weight unit|nh|em] (br_coverage above; the usage text says the
+ * (br_quant above; the genes are br_annotation_gene_ids', numbered in order of first appearance in @SQ order, or the map file's), --coverage FILE / --coverage-summary FILE [--coverage-primary] [--coverage-weight unit|nh|em] / --coverage-bigwig FILE [--coverage-bigwig-zooms 0-10] [--coverage-bigwig-uncompressed] (br_coverage and br_coverage_bigwig above;the usage text says the
  * rest).
  * Returns the process exit code. */
 int br_cli_main(int argc, char **argv);
