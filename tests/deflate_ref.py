@@ -95,12 +95,13 @@ class _Bits:
 class Block:
     """One DEFLATE block: btype, bfinal, hlit / hdist / hclen (the counts, not the header fields: 257.., 1.., 4..) and
     cl_lens (19, in symbol order) / ll_lens / d_lens for btype 2, tokens (an int literal or (length, distance, output
-    position)), data (the bytes it expands to), bit_start / bit_end in the stream."""
+    position)), token_bits (the bit of the stream each token of a coded block starts at), data (the bytes it expands to),
+    bit_start / bit_end in the stream."""
     def __init__(self):
         self.btype = self.bfinal = None
         self.hlit = self.hdist = self.hclen = None
         self.cl_lens = self.ll_lens = self.d_lens = None
-        self.tokens, self.data = [], b""
+        self.tokens, self.token_bits, self.data = [], [], b""
         self.bit_start = self.bit_end = 0
 
     def matches(self):
@@ -173,10 +174,12 @@ def inflate(data, start=0, history=b""):
             else:
                 ll, dd = fixed_ll, fixed_d
             while True:
+                t0 = br.pos
                 s = br.symbol(ll, "literal/length code")
                 if s < 256:
                     out.append(s)
                     b.tokens.append(s)
+                    b.token_bits.append(t0)
                 elif s == 256:
                     break
                 else:
@@ -192,6 +195,7 @@ def inflate(data, start=0, history=b""):
                     if dist > len(out):
                         raise DeflateError("distance %d beyond the %d bytes of output so far" % (dist, len(out)))
                     b.tokens.append((length, dist, len(out) - h))
+                    b.token_bits.append(t0)
                     if dist >= length:
                         out += out[len(out) - dist:len(out) - dist + length]
                     else:
