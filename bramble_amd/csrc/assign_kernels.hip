@@ -1,7 +1,7 @@
 // The posterior of every projected record and the rewritten record stream on the device (host side: assign.cpp, which holds the
 // pipeline's description; the definitions -- p, m, w, the draw, the rewritten record -- are in bramble_amd.h, br_assign).
 //
-//   add      k_as_add: a lane per row: the note (name by the search of k_cov_add_w, transcript, FIRST / PAIRED) and the record's
+//   add      k_as_add: a lane per row: the note (name by the search of k_cov_add, transcript, FIRST / PAIRED) and the record's
 //            offset in the arena; k_as_place: every record belongs to a placement that lies inside its name
 //   finish   k_as_p (the bounds-checked look-up of k_cov_apply) -> k_as_m (a lane per record over its name's records; the names
 //            above AS_M_LANE_MAX records are listed) -> k_as_m_big (a wave per listed name) -> k_as_w -> k_as_draw (mode sample:

@@ -168,16 +168,13 @@ __device__ __forceinline__ double list_sum(const double *v, const uint32_t *at, 
 __device__ __forceinline__ double lists_sum(const double *v, const uint32_t *at, uint64_t b, uint64_t n, uint64_t base) {
   const int lane = threadIdx.x & 63;
   double d = n <= CL_WAVE_ITEMS ? list_sum(v, at, b, n, base) : 0.0;
-  uint64_t todo = __ballot(n > CL_WAVE_ITEMS);
-  while (todo) {
-    const int src = __ffsll((unsigned long long)todo) - 1;
-    todo &= todo - 1;
+  wave_turns(n > CL_WAVE_ITEMS, [&](int src) {
     const uint64_t bb = __shfl(b, src), nn = __shfl(n, src);
     double s = 0;
     for (uint64_t j = (uint64_t)lane; j < nn; j += 64) s += v[at[bb + j] - base];
     s = wave_sum(s);
     if (lane == src) d = s;
-  }
+  });
   return d;
 }
 

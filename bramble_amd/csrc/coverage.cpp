@@ -17,7 +17,9 @@
 // 64 bits, one unit 2^32, and a row leaves + q / - q.  Weight nh knows q at the add.  Weight em does not: its add keeps, per
 // clamped non-empty interval, 16 bytes (first base, length, name) in an arena -- a pass that counts a row's entries, room made on
 // the host, a pass that writes them -- and br_coverage_finish_em applies them with the quantifier's posteriors (quant_view.h)
-// before the scan.  Mode 0 launches what it launched before these modes existed: every weighted path is behind `weight != 0`.
+// before the scan.  The kernels are the same ones in every mode: the add is instantiated per way of ending an interval (the unit
+// mode's instance holds nothing of the others: no q, no names, no entries), the scan, the summary, the run count and the run writer
+// per depth word, and coverage_finish below is one routine for both words.
 //
 // Device memory in a weighted mode (E kept entries: the intervals, and one for every counted row without one):
 //   from "weight" on  8 (B + 1) (diff, then the depth) + 24 (T + 1) (offsets, records, weight_sum) + 128 bytes of counters (what
@@ -138,12 +140,10 @@ static int coverage_add_rows(br_coverage *c, CovAddArgs A, uint64_t r0, uint64_t
   A.r_first = r0; A.r_last = r1;
   A.n_tx = c->n_tx; A.off = c->d_off.as<uint64_t>(); A.primary_only = (uint32_t)c->primary_only;
   A.records = c->records.as<unsigned long long>(); A.counters = c->small.as<unsigned long long>();
-  if (c->weight == 0) { A.diff = c->diff.as<uint32_t>(); launch_cov_add(st, A); }
-  else {   // weight nh: the same rows through the variant that adds the row's q to 64-bit words
-    CovAddWArgs W{};
-    W.A = A; W.diff = c->diff.as<unsigned long long>(); W.weight_sum = c->weight_sum.as<unsigned long long>();
-    launch_cov_add_w(st, W, COV_ADD_NH);
-  }
+  A.diff = c->diff.p;
+  CovAddWArgs W{};
+  W.A = A; W.weight_sum = c->weight_sum.as<unsigned long long>();   // (weight nh: the row's q into 64-bit words, and into weight_sum)
+  launch_cov_add(st, W, c->weight ? COV_ADD_NH : COV_ADD_UNIT);
   HIPCHK(hipMemcpyAsync(c->counters, c->small.p, c->counter_words() * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));   // the caller's rows may be reused now
   c->rows += r1 - r0;
@@ -160,14 +160,13 @@ static int coverage_keep_rows(br_coverage *c, CovAddWArgs W) {
   A.r_first = r0; A.r_last = r1;
   A.n_tx = c->n_tx; A.off = c->d_off.as<uint64_t>(); A.primary_only = (uint32_t)c->primary_only;
   A.records = c->records.as<unsigned long long>(); A.counters = c->small.as<unsigned long long>();
-  W.diff = c->diff.as<unsigned long long>(); W.weight_sum = c->weight_sum.as<unsigned long long>();
   W.name_base = (uint64_t)c->n_names;
   ColBuf entries;
   DropGuard dropper{c, {&entries}};
   RC(c->alloc(entries, (size_t)(r1 - r0 + 1) * 4));
   W.row_entries = entries.as<uint32_t>();
   HIPCHK(hipMemsetAsync(c->small.as<uint64_t>() + CV_ADD_ENTRIES, 0, 8, st));
-  launch_cov_add_w(st, W, COV_ADD_COUNT);
+  launch_cov_add(st, W, COV_ADD_COUNT);
   uint64_t seen[CV_WORDS_W];
   HIPCHK(hipMemcpyAsync(seen, c->small.p, sizeof(seen), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -180,7 +179,7 @@ static int coverage_keep_rows(br_coverage *c, CovAddWArgs W) {
   const size_t need = (size_t)(c->kept + seen[CV_ADD_ENTRIES]) + 1;
   if (need * 16 > c->arena.cap) RC(c->alloc(c->arena, std::max(need, (size_t)(c->arena.cap / 16) * 3 / 2) * 16, true));
   W.arena = c->arena.as<uint4>(); W.arena_cap = c->arena.cap / 16;
-  launch_cov_add_w(st, W, COV_ADD_KEEP);
+  launch_cov_add(st, W, COV_ADD_KEEP);
   HIPCHK(hipMemcpyAsync(c->counters, c->small.p, CV_WORDS_W * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));   // the caller's rows may be reused now
   if (c->counters[CV_KEPT] != c->kept + seen[CV_ADD_ENTRIES]) { c->broken = true; return BR_ERR_HIP; }   // (the two passes disagree)
@@ -262,63 +261,38 @@ extern "C" int br_coverage_add_last(br_coverage *c, br_ctx *ctx) {
   return br_coverage_add_rows(c, &ctx->last_rows, 0, ctx->last_rows.n_rows, 1, ctx->last_stream);
 }
 
+// diff (it holds every row's events by now) -> depth, summary and runs, over the mode's depth word
+template <typename W>
 static int coverage_finish(br_coverage *c) {
+  constexpr bool wide = sizeof(W) == 8;
   hipStream_t st = c->st;
   const int64_t B = c->n_bases, T = c->n_tx;
-  if (c->counters[CV_BAD_TID]) return BR_ERR_INVALID_ARG;   // a transcript id the object has no transcript for
   const size_t t1 = (size_t)T + 1;
   const int64_t tiles = (B + COV_TILE - 1) / COV_TILE;
   ColBuf tile, tmp;
   DropGuard dropper{c, {&tile, &tmp}};
-  RC(c->alloc(c->aligned, t1 * 8)); RC(c->alloc(c->covered, t1 * 8)); RC(c->alloc(c->max_depth, t1 * 4));
+  RC(c->alloc(c->aligned, t1 * 8));
+  if (wide) RC(c->alloc(c->aligned_lo, t1 * 8));
+  RC(c->alloc(c->covered, t1 * 8)); RC(c->alloc(c->max_depth, t1 * sizeof(W)));
   RC(c->alloc(tile, (size_t)(tiles + 2) * 8)); RC(c->alloc(tmp, scan_scratch_bytes(tiles)));
-  HIPCHK(hipMemsetAsync(c->aligned.p, 0, t1 * 8, st)); HIPCHK(hipMemsetAsync(c->covered.p, 0, t1 * 8, st));
-  HIPCHK(hipMemsetAsync(c->max_depth.p, 0, t1 * 4, st));
-  uint32_t *depth = c->diff.as<uint32_t>();
+  HIPCHK(hipMemsetAsync(c->aligned.p, 0, t1 * 8, st));
+  if (wide) HIPCHK(hipMemsetAsync(c->aligned_lo.p, 0, t1 * 8, st));
+  HIPCHK(hipMemsetAsync(c->covered.p, 0, t1 * 8, st)); HIPCHK(hipMemsetAsync(c->max_depth.p, 0, t1 * sizeof(W), st));
+  W *depth = c->diff.as<W>();
   const uint64_t *off = c->d_off.as<uint64_t>();
   launch_cov_scan(st, depth, B, tile.as<uint64_t>(), tmp.as<uint64_t>());
-  if (B > 0) launch_cov_summary(st, depth, off, T, c->aligned.as<uint64_t>(), c->covered.as<uint64_t>(), c->max_depth.as<uint32_t>());
+  if (B > 0) launch_cov_summary(st, (const W *)depth, off, T, c->aligned.as<uint64_t>(), c->aligned_lo.as<uint64_t>(), c->covered.as<uint64_t>(), c->max_depth.as<W>());
   uint64_t R = 0;
   if (B > 0) {
-    launch_cov_count(st, depth, B, off, T, tile.as<uint64_t>());
+    launch_cov_count(st, (const W *)depth, B, off, T, tile.as<uint64_t>());
     launch_scan(st, tile.as<uint64_t>(), tiles, tmp.as<uint64_t>());   // tile counts -> the first run of every tile; [tiles] = R
     HIPCHK(hipMemcpyAsync(&R, tile.as<uint64_t>() + tiles, 8, hipMemcpyDeviceToHost, st));
   }
   HIPCHK(hipStreamSynchronize(st));
   if (R > (uint64_t)B) return BR_ERR_HIP;
   RC(c->alloc(c->runs, (size_t)(R + 1) * 16));
-  if (R) launch_cov_runs(st, depth, B, off, T, tile.as<uint64_t>(), c->runs.as<uint4>());
-  HIPCHK(hipStreamSynchronize(st));
-  c->n_runs = (int64_t)R;
-  return BR_OK;
-}
-
-// coverage_finish over 64-bit words (diff holds every row's events by now)
-static int coverage_finish64(br_coverage *c) {
-  hipStream_t st = c->st;
-  const int64_t B = c->n_bases, T = c->n_tx;
-  const size_t t1 = (size_t)T + 1;
-  const int64_t tiles = (B + COV_TILE - 1) / COV_TILE;
-  ColBuf tile, tmp;
-  DropGuard dropper{c, {&tile, &tmp}};
-  RC(c->alloc(c->aligned, t1 * 8)); RC(c->alloc(c->aligned_lo, t1 * 8)); RC(c->alloc(c->covered, t1 * 8)); RC(c->alloc(c->max_depth, t1 * 8));
-  RC(c->alloc(tile, (size_t)(tiles + 2) * 8)); RC(c->alloc(tmp, scan_scratch_bytes(tiles)));
-  HIPCHK(hipMemsetAsync(c->aligned.p, 0, t1 * 8, st)); HIPCHK(hipMemsetAsync(c->aligned_lo.p, 0, t1 * 8, st));
-  HIPCHK(hipMemsetAsync(c->covered.p, 0, t1 * 8, st)); HIPCHK(hipMemsetAsync(c->max_depth.p, 0, t1 * 8, st));
-  uint64_t *depth = c->diff.as<uint64_t>();
-  const uint64_t *off = c->d_off.as<uint64_t>();
-  launch_cov_scan64(st, depth, B, tile.as<uint64_t>(), tmp.as<uint64_t>());
-  if (B > 0) launch_cov_summary64(st, depth, off, T, c->aligned.as<uint64_t>(), c->aligned_lo.as<uint64_t>(), c->covered.as<uint64_t>(), c->max_depth.as<uint64_t>());
-  uint64_t R = 0;
-  if (B > 0) {
-    launch_cov_count64(st, depth, B, off, T, tile.as<uint64_t>());
-    launch_scan(st, tile.as<uint64_t>(), tiles, tmp.as<uint64_t>());
-    HIPCHK(hipMemcpyAsync(&R, tile.as<uint64_t>() + tiles, 8, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  if (R > (uint64_t)B) return BR_ERR_HIP;
-  RC(c->alloc(c->runs, (size_t)(R + 1) * 16)); RC(c->alloc(c->run_depth, (size_t)(R + 1) * 8));
-  if (R) launch_cov_runs64(st, depth, B, off, T, tile.as<uint64_t>(), c->runs.as<uint4>(), c->run_depth.as<uint64_t>());
+  if (wide) RC(c->alloc(c->run_depth, (size_t)(R + 1) * 8));
+  if (R) launch_cov_runs(st, (const W *)depth, B, off, T, tile.as<uint64_t>(), c->runs.as<uint4>(), c->run_depth.as<uint64_t>());
   HIPCHK(hipStreamSynchronize(st));
   c->n_runs = (int64_t)R;
   return BR_OK;
@@ -353,7 +327,7 @@ extern "C" int br_coverage_finish_em(br_coverage *c, br_quant *q, int64_t *n_run
   int rc = coverage_apply(c, v);
   // an entry that names nothing of the quantifier's: counted by the apply, never looked up
   if (!rc && (c->counters[CV_BAD_NAME] || c->counters[CV_BAD_CLASS] || c->counters[CV_BAD_LABEL] || c->counters[CV_BAD_ENTRY])) rc = BR_ERR_INVALID_ARG;
-  if (!rc) rc = coverage_finish64(c);
+  if (!rc) rc = coverage_finish<uint64_t>(c);
   if (rc) { c->broken = true; return rc; }   // (diff holds part of the events, or half a depth)
   c->finished = true;
   c->finish_s = timer.seconds();
@@ -365,9 +339,10 @@ extern "C" int br_coverage_finish(br_coverage *c, int64_t *n_runs) {
   if (!c || c->broken || c->finished || c->weight == 2) return BR_ERR_INVALID_ARG;   // (weight em: br_coverage_finish_em)
   const ScopeTimer timer;
   HIPCHK(hipSetDevice(c->device));
-  if (c->weight == 1 && (c->counters[CV_BAD_TID] || c->counters[CV_BAD_NH])) return BR_ERR_INVALID_ARG;   // a row without a weight: nh == 0
-  const int rc = c->weight ? coverage_finish64(c) : coverage_finish(c);
-  if (rc) { if (rc != BR_ERR_INVALID_ARG) c->broken = true; return rc; }   // (diff may be half a depth by now)
+  // a transcript id the object has no transcript for, or (weight nh) a row without a weight: nh == 0
+  if (c->counters[CV_BAD_TID] || (c->weight == 1 && c->counters[CV_BAD_NH])) return BR_ERR_INVALID_ARG;
+  const int rc = c->weight ? coverage_finish<uint64_t>(c) : coverage_finish<uint32_t>(c);
+  if (rc) { c->broken = true; return rc; }   // (diff may be half a depth by now)
   c->finished = true;
   c->finish_s = timer.seconds();
   if (n_runs) *n_runs = c->n_runs;

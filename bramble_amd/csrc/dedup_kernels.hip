@@ -16,6 +16,7 @@
 
 #include "../../include/bramble_amd.h"
 #include "barcode_inl.h"
+#include "cigar_inl.h"
 #include "dedup_kernels.h"
 #include "names_inl.h"
 #include "wave_inl.h"
@@ -30,9 +31,6 @@ __device__ __forceinline__ uint64_t fmix64(uint64_t h) {   // (murmur3's)
   h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
   return h;
 }
-// reference bases of one op: M D N = X (0, 2, 3, 7, 8) consume the reference
-__device__ __forceinline__ uint64_t ref_len(uint32_t w) { return (0x18du >> (w & 15u)) & 1u ? (uint64_t)(w >> 4) : 0ull; }
-
 // an entry as the arena's four words: x = t, (y, z) = five, w = f
 __device__ __forceinline__ bool ent_less(const uint4 a, const uint4 b, bool &eq) {
   eq = false;
@@ -84,11 +82,12 @@ __global__ void __launch_bounds__(256) k_dd_rows(DdAddArgs A) {
       }
       if (nc <= 2u) {
         const uint32_t o0 = (uint32_t)c, o1 = (uint32_t)(c >> 32);
-        if (nc >= 1u) { reflen = ref_len(o0); if ((o0 & 15u) == 4u) lead = o0 >> 4; }
-        if (nc == 2u) { reflen += ref_len(o1); if ((o0 & 15u) == 5u && (o1 & 15u) == 4u) lead = o1 >> 4; }
+        reflen = cigar_ref_len_inline(c, nc);
+        if (nc >= 1u && (o0 & 15u) == 4u) lead = o0 >> 4;
+        if (nc == 2u && (o0 & 15u) == 5u && (o1 & 15u) == 4u) lead = o1 >> 4;
         if (nc == 1u) trail = lead;
         if (nc == 2u) { if ((o1 & 15u) == 4u) trail = o1 >> 4; else if ((o1 & 15u) == 5u && (o0 & 15u) == 4u) trail = o0 >> 4; }
-      } else if (!(c <= A.n_pool_words && (uint64_t)nc <= A.n_pool_words - c)) bad = true;
+      } else if (!pool_holds(A.n_pool_words, c, nc)) bad = true;
       else {
         const uint32_t *ops = A.pool + c;
         uint32_t k = 0;
@@ -97,7 +96,7 @@ __global__ void __launch_bounds__(256) k_dd_rows(DdAddArgs A) {
         k = nc;
         while (k > 0u && (ops[k - 1u] & 15u) == 5u) k--;
         if (k > 0u && (ops[k - 1u] & 15u) == 4u) trail = ops[k - 1u] >> 4;
-        if (nc <= DD_WAVE_OPS) { for (uint32_t j = 0; j < nc; j++) reflen += ref_len(ops[j]); }
+        if (nc <= DD_WAVE_OPS) { for (uint32_t j = 0; j < nc; j++) reflen += cigar_ref_len(ops[j]); }
         else { wide_off = c; wide_n = nc; }
       }
       // the record holds the ops of a row on a '-' transcript in reverse order (the encoder's), and five is the record's
@@ -105,17 +104,10 @@ __global__ void __launch_bounds__(256) k_dd_rows(DdAddArgs A) {
       live = !bad;
     }
   }
-  uint64_t todo = __ballot(wide_n != 0u);
-  while (todo) {
-    const int src = __ffsll((unsigned long long)todo) - 1;
-    todo &= todo - 1;
-    const uint64_t off = __shfl(wide_off, src);
-    const uint32_t nn = (uint32_t)__shfl((int)wide_n, src);
-    uint64_t s = 0;
-    for (uint32_t k = (uint32_t)lane; k < nn; k += 64u) s += ref_len(A.pool[off + k]);
-    s = wave_sum(s);
+  wave_turns(wide_n != 0u, [&](int src) {
+    const uint64_t s = wave_cigar_ref_len(A.pool, __shfl(wide_off, src), (uint32_t)__shfl((int)wide_n, src));
     if (lane == src) reflen = s;
-  }
+  });
   if (i < n) {
     const int64_t five = live ? ((f & 0x10u) ? (int64_t)(pos + reflen + trail) : (int64_t)pos - (int64_t)lead) : 0;
     A.raw[i] = make_uint4(t, (uint32_t)(uint64_t)five, (uint32_t)((uint64_t)five >> 32), f);

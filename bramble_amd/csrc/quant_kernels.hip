@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/bramble_amd.h"
+#include "cigar_inl.h"
 #include "collate_kernels.h"
 #include "names_inl.h"
 #include "quant_kernels.h"
@@ -155,12 +156,6 @@ __device__ __forceinline__ uint64_t row_cigar(const QAddArgs &A, uint64_t r) { r
 __device__ __forceinline__ bool is_fragment(const q_u4 lead, const q_u4 mate) {
   return (lead.z & Q_LEAD) == Q_LEAD && (mate.z & (BR_ROW_PAIRED | BR_ROW_FIRST)) == BR_ROW_PAIRED && mate.x == lead.x;
 }
-// reference bases of one op: M D N = X (0, 2, 3, 7, 8) consume the reference
-__device__ __forceinline__ uint64_t ref_len(uint32_t w) { return (0x18du >> (w & 15u)) & 1u ? (uint64_t)(w >> 4) : 0ull; }
-__device__ __forceinline__ uint64_t ref_len_inline(uint64_t c, uint32_t n) {
-  return (n >= 1u ? ref_len((uint32_t)c) : 0ull) + (n >= 2u ? ref_len((uint32_t)(c >> 32)) : 0ull);
-}
-__device__ __forceinline__ bool in_pool(const QAddArgs &A, uint64_t off, uint32_t n) { return off <= A.n_pool_words && (uint64_t)n <= A.n_pool_words - off; }
 __device__ __forceinline__ void count_length(const QAddArgs &A, uint32_t *sh_hist, bool lds, uint64_t lo, uint64_t hi, uint32_t &n_obs, uint32_t &n_oor) {
   const uint64_t len = hi - lo;
   if (len == 0 || len > (uint64_t)A.fld_max) { n_oor++; return; }
@@ -218,28 +213,20 @@ __global__ void __launch_bounds__(256) k_q_frag(QAddArgs A) {
           const uint32_t n = BR_ROW_NCIGAR(m.z);
           const uint64_t c = row_cigar(A, fr + (uint64_t)j);
           pos[j] = m.y;
-          if (n <= 2u) ref[j] = ref_len_inline(c, n);
-          else if (!in_pool(A, c, n)) is_bad = true;
-          else if (n <= 64u) { uint64_t s = 0; for (uint32_t k = 0; k < n; k++) s += ref_len(A.pool[c + k]); ref[j] = s; }
+          if (n <= 2u) ref[j] = cigar_ref_len_inline(c, n);
+          else if (!pool_holds(A.n_pool_words, c, n)) is_bad = true;
+          else if (n <= 64u) { uint64_t s = 0; for (uint32_t k = 0; k < n; k++) s += cigar_ref_len(A.pool[c + k]); ref[j] = s; }
           else { wide_off[j] = c; wide_n[j] = n; }
         }
       }
     }
   }
 #pragma unroll
-  for (int j = 0; j < 2; j++) {
-    uint64_t todo = __ballot(wide_n[j] != 0u && !is_bad);
-    while (todo) {
-      const int src = __ffsll((unsigned long long)todo) - 1;
-      todo &= todo - 1;
-      const uint64_t off = __shfl(wide_off[j], src);
-      const uint32_t n = (uint32_t)__shfl((int)wide_n[j], src);
-      uint64_t s = 0;
-      for (uint32_t k = (uint32_t)lane; k < n; k += 64u) s += ref_len(A.pool[off + k]);
-      s = wave_sum(s);
+  for (int j = 0; j < 2; j++)
+    wave_turns(wide_n[j] != 0u && !is_bad, [&](int src) {
+      const uint64_t s = wave_cigar_ref_len(A.pool, __shfl(wide_off[j], src), (uint32_t)__shfl((int)wide_n[j], src));
       if (lane == src) ref[j] = s;
-    }
-  }
+    });
   uint32_t n_obs = 0, n_oor = 0;
   if (found && !is_bad) {
     const uint64_t lo = pos[0] < pos[1] ? pos[0] : pos[1], e0 = pos[0] + ref[0], e1 = pos[1] + ref[1];
@@ -283,13 +270,9 @@ __global__ void __launch_bounds__(256) k_q_frag_big(QAddArgs A) {
       const uint32_t n = BR_ROW_NCIGAR(m.z);
       const uint64_t c = row_cigar(A, fr + (uint64_t)j);
       pos[j] = m.y; ref[j] = 0;
-      if (n <= 2u) ref[j] = ref_len_inline(c, n);
-      else if (!in_pool(A, c, n)) ok = false;
-      else {
-        uint64_t s = 0;
-        for (uint32_t k = (uint32_t)lane; k < n; k += 64u) s += ref_len(A.pool[c + k]);
-        ref[j] = wave_sum(s);
-      }
+      if (n <= 2u) ref[j] = cigar_ref_len_inline(c, n);
+      else if (!pool_holds(A.n_pool_words, c, n)) ok = false;
+      else ref[j] = wave_cigar_ref_len(A.pool, c, n);
     }
     if (!ok) { is_bad = true; continue; }
     if (lane == 0) {

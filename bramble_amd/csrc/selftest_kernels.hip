@@ -1,10 +1,12 @@
-// Test-only probes of the shared scan unit and the wave and block primitives (scan_kernels.h, wave_inl.h, launch_scan3):
+// Test-only probes of the shared scan unit, the wave and block primitives and the rows' CIGARs (scan_kernels.h, wave_inl.h,
+// launch_scan3, cigar_inl.h):
 // libbramble_selftest.so, loaded by tests/scan_probe.py and by nothing in the product.  Every entry point takes raw device
 // pointers, launches the product's own code on the stream it is given (0: the null stream), synchronises and returns the
 // HIP error code.  The probe kernels only move values between memory and the primitive under test.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cigar_inl.h"
 #include "kernels.h"
 #include "scan_kernels.h"
 #include "wave_inl.h"
@@ -70,6 +72,45 @@ __global__ void __launch_bounds__(256) k_probe_top(uint64_t *tile_sums, int64_t 
 __global__ void __launch_bounds__(256) k_probe_kth_bit(const uint64_t *masks, const uint32_t *ks, uint32_t *out, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = kth_set_bit64(masks[i], ks[i]);
+}
+
+// one block of 256: f(src) appends (src, the value of lane src by shuffle, the lanes that are in f) to the list of its wave (64
+// entries of three words); counts[wave] = the calls
+__global__ void __launch_bounds__(256) k_probe_turns(const uint32_t *flag, const uint32_t *val, uint32_t *lists, uint32_t *counts) {
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint32_t v = val[threadIdx.x];
+  uint32_t n = 0;
+  wave_turns(flag[threadIdx.x] != 0u, [&](int src) {
+    const uint32_t x = (uint32_t)__shfl((int)v, src), in = (uint32_t)__popcll((unsigned long long)__ballot(true));
+    if (n < 64u && lane == 0) { uint32_t *e = lists + 3 * (64 * w + n); e[0] = (uint32_t)src; e[1] = x; e[2] = in; }
+    n++;
+  });
+  if (lane == 0) counts[w] = n;
+}
+
+// one block of 256: its waves take the CIGARs (offs[i], ns[i]) in turn: sums[i] = wave_cigar_ref_len, same[i] = the lanes that
+// got lane 0's sum.  Thread t < 16 probes the op tables with ops[t]: tab[t] = covers | skips << 1, tab_len[t] = cigar_ref_len,
+// and inl[3 t + n] = cigar_ref_len_inline(ops[t] | ops[(t + 1) & 15] << 32, n) for n = 0, 1, 2
+__global__ void __launch_bounds__(256) k_probe_cigar(const uint32_t *pool, const uint64_t *offs, const uint32_t *ns, int n_cigars, uint64_t *sums,
+                                                    uint32_t *same, const uint32_t *ops, uint32_t *tab, uint64_t *tab_len, uint64_t *inl) {
+  const uint32_t lane = threadIdx.x & 63;
+  for (int i = threadIdx.x >> 6; i < n_cigars; i += 4) {
+    const uint64_t s = wave_cigar_ref_len(pool, offs[i], ns[i]);
+    const uint64_t agree = __ballot(s == __shfl(s, 0));
+    if (lane == 0) { sums[i] = s; same[i] = (uint32_t)__popcll((unsigned long long)agree); }
+  }
+  if (threadIdx.x < 16) {
+    const uint32_t t = threadIdx.x, op = ops[t];
+    tab[t] = (cigar_covers(op) ? 1u : 0u) | (cigar_skips(op) ? 2u : 0u);
+    tab_len[t] = cigar_ref_len(op);
+    const uint64_t c = (uint64_t)op | (uint64_t)ops[(t + 1) & 15u] << 32;
+    for (uint32_t n = 0; n < 3; n++) inl[3 * t + n] = cigar_ref_len_inline(c, n);
+  }
+}
+
+// out[i] = pool_holds(n_pool_words, offs[i], ns[i]) for i < n <= 256
+__global__ void __launch_bounds__(256) k_probe_pool_holds(uint64_t n_pool_words, const uint64_t *offs, const uint32_t *ns, int n, uint32_t *out) {
+  if ((int)threadIdx.x < n) out[threadIdx.x] = pool_holds(n_pool_words, offs[threadIdx.x], ns[threadIdx.x]) ? 1u : 0u;
 }
 
 static int finish(hipStream_t st) {
@@ -166,6 +207,28 @@ int brst_top_rounds(void *st, int channels, int items, uint64_t *tile_sums, int6
 int brst_kth_bit(void *st, const uint64_t *masks, const uint32_t *ks, uint32_t *out, int64_t n) {
   if (n < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_probe_kth_bit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)st, masks, ks, out, n);
+  return finish((hipStream_t)st);
+}
+
+// wave_turns by one block of 256: flag and val hold 256 words, lists 4 x 64 x 3, counts 4
+int brst_wave_turns(void *st, const uint32_t *flag, const uint32_t *val, uint32_t *lists, uint32_t *counts) {
+  hipLaunchKernelGGL(k_probe_turns, dim3(1), dim3(256), 0, (hipStream_t)st, flag, val, lists, counts);
+  return finish((hipStream_t)st);
+}
+
+// wave_cigar_ref_len over n_cigars pooled CIGARs (the caller keeps them inside the pool) and the op tables over the 16 words of
+// ops, by one block of 256: sums and same hold n_cigars items, tab and tab_len 16, inl 48
+int brst_cigar(void *st, const uint32_t *pool, const uint64_t *offs, const uint32_t *ns, int n_cigars, uint64_t *sums, uint32_t *same,
+               const uint32_t *ops, uint32_t *tab, uint64_t *tab_len, uint64_t *inl) {
+  if (n_cigars < 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_cigar, dim3(1), dim3(256), 0, (hipStream_t)st, pool, offs, ns, n_cigars, sums, same, ops, tab, tab_len, inl);
+  return finish((hipStream_t)st);
+}
+
+// pool_holds(n_pool_words, offs[i], ns[i]) -> out[i] for i < n <= 256
+int brst_pool_holds(void *st, uint64_t n_pool_words, const uint64_t *offs, const uint32_t *ns, int n, uint32_t *out) {
+  if (n < 1 || n > 256) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_probe_pool_holds, dim3(1), dim3(256), 0, (hipStream_t)st, n_pool_words, offs, ns, n, out);
   return finish((hipStream_t)st);
 }
 

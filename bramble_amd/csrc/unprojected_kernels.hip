@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "unprojected_kernels.h"
+#include "wave_inl.h"
 
 namespace br {
 
@@ -38,15 +39,14 @@ __global__ void __launch_bounds__(256) k_unproj_names(UnprojArgs A) {
     for (uint32_t i = a; i < e; i++) cnt += A.flag[i];
     if (A.scope == 2 && cnt && cnt < e - a) for (uint32_t i = a; i < e; i++) A.flag[i] = 1;
   }
-  for (uint64_t todo = __ballot(big); todo; todo &= todo - 1) {
-    const int src = __ffsll((unsigned long long)todo) - 1;
+  wave_turns(big, [&](int src) {
     const uint32_t ba = (uint32_t)__shfl((int)a, src), be = (uint32_t)__shfl((int)e, src);
     uint32_t c = 0;
     for (uint32_t i = ba + lane; i < be; i += 64) c += A.flag[i];
-    for (int d = 32; d; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
+    c = wave_sum(c);
     if (A.scope == 2 && c && c < be - ba) for (uint32_t i = ba + lane; i < be; i += 64) A.flag[i] = 1;
     if ((int)lane == src) cnt = c;
-  }
+  });
   const bool none = g < A.n_groups && e > a && cnt == 0, part = g < A.n_groups && cnt && cnt < e - a;
   const uint64_t b_none = __ballot(none), b_part = __ballot(part);
   if (lane == 0) {

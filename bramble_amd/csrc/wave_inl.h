@@ -7,6 +7,7 @@
 //   wave_scan<T, W>(v)                                inclusive prefix sum over the group (lane k: v of lanes 0 .. k)
 //   wave_sum / wave_max / wave_min / wave_or / wave_and   butterfly reductions: every lane of the group gets the result
 //   count_lanes(cond, word)                           *word += the wave's lanes with cond, one atomic a wave
+//   wave_turns(mine, f)                               f(src) for every lane src with mine set, lowest first, the wave converged
 //   block_excl_scan_256(v, sh, total)                 exclusive prefix sum over a block of 256 threads
 //   block_bits(o, a, out)                             OR of o and AND of a over a block of 256 threads (the radix sort's digits)
 //   load8 / store8                                    a thread's eight consecutive scan items as 16-byte accesses
@@ -63,6 +64,14 @@ __device__ __forceinline__ T wave_and(T v) {
 __device__ __forceinline__ void count_lanes(bool cond, unsigned long long *word) {
   const uint64_t b = __ballot(cond);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(word, (unsigned long long)__popcll((unsigned long long)b));
+}
+
+// The lanes whose item is too long for one lane take turns, and the wave does each one: f(src) runs once for every lane src
+// of the wave that has `mine` set, lowest lane first, with all 64 lanes in it (they fetch src's item by __shfl(.., src), share
+// its work and leave the result to the lane with lane == src).  Every lane of the wave calls it.
+template <typename F>
+__device__ __forceinline__ void wave_turns(bool mine, F f) {
+  for (uint64_t todo = __ballot(mine); todo; todo &= todo - 1) f(__ffsll((unsigned long long)todo) - 1);
 }
 
 // Exclusive prefix sum of v over the block's 256 threads; total = the block's sum, in every thread.  Wave scans by shuffles,

@@ -1,5 +1,5 @@
-"""ctypes access to libbramble_selftest.so (bramble_amd/csrc/selftest_kernels.hip): the probes of the scan unit and the wave
-primitives, and guarded device buffers for them.  Test-only: the product never loads this library."""
+"""ctypes access to libbramble_selftest.so (bramble_amd/csrc/selftest_kernels.hip): the probes of the scan unit, the wave
+primitives and the rows' CIGARs (cigar_inl.h), and guarded device buffers for them.  Test-only: the product never loads this library."""
 import ctypes as C
 import functools
 import os
@@ -31,7 +31,8 @@ def lib():
     for name, args in (("brst_scan_u32", [p, p, i64, p, p, i32, p]), ("brst_scan_u64_inplace", [p, p, i64, p]),
                        ("brst_scan3", [p, i64, p, p, p, p, p, p, p, p, p]), ("brst_top_rounds", [p, i32, i32, p, i64, p]),
                        ("brst_copy8", [p, i32, p, i64, p, p]), ("brst_wave", [p, i32, i32, i32, p, p, i32]), ("brst_block_scan", [p, i32, p, p, p, i32]),
-                       ("brst_block_bits", [p, p, p, p, p, i32])):
+                       ("brst_block_bits", [p, p, p, p, p, i32]), ("brst_wave_turns", [p, p, p, p, p]),
+                       ("brst_cigar", [p, p, p, p, i32, p, p, p, p, p, p]), ("brst_pool_holds", [p, C.c_uint64, p, p, i32, p])):
         f = getattr(L, name)
         f.restype, f.argtypes = i32, args
     return L
