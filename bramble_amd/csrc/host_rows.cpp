@@ -494,12 +494,18 @@ extern "C" int br_project_groups(br_ctx *c, const br_config *cfg, const br_align
   return project_groups_impl(c, cfg, alns, n, false, out, n_out);
 }
 
-// Diagnostic: the -S rescue DP alone.  Runs k_ksw on n (target, query) pairs as right-side problems and returns, per
-// pair, whether the rescue is accepted, the maximum, and the raw traceback CIGAR (forward order, BAM-packed M / I / D).
+// Diagnostic: the -S rescue DP alone.  Runs k_ksw on n (target, query) pairs and returns, per pair, whether the rescue is
+// accepted, the maximum, and the raw traceback CIGAR (forward order, BAM-packed M / I / D).  side (optional; null = all
+// right): 0 = a left-side problem, whose strings the caller passes already reversed (align_reversed, src/evaluate.cpp:368-395),
+// 1 = a right-side one.  refc / n_seg / seg (optional, all or none): what clip_segment made of the traceback -- KswRes.refc,
+// KswRes.n_ops and the override ops read back from clip_ops[seq_off + p], seg[p * cigar_cap ...].
 extern "C" int br_ctx_ksw_pairs(br_ctx *c, int64_t n, const char *const *tseq, const char *const *qseq, int32_t *ok,
-                                int32_t *max, uint32_t *n_cigar, uint32_t *cigar, uint32_t cigar_cap) {
+                                int32_t *max, uint32_t *n_cigar, uint32_t *cigar, uint32_t cigar_cap, const uint8_t *side,
+                                int32_t *refc, uint32_t *n_seg, uint32_t *seg) {
   if (!c || n < 0 || (n && (!tseq || !qseq || !ok || !max || !n_cigar || !cigar)) || !cigar_cap) return BR_ERR_INVALID_ARG;
+  if ((refc || n_seg || seg) && !(refc && n_seg && seg)) return BR_ERR_INVALID_ARG;
   if (n == 0) return BR_OK;
+  if (side) for (int64_t p = 0; p < n; p++) if (side[p] > 1) return BR_ERR_INVALID_ARG;
   HIPCHK(hipSetDevice(c->ix->device));
   hipStream_t st = nullptr;
   struct HProb { uint32_t qlen, tlen, side, pad; uint64_t seq_off; };
@@ -510,7 +516,7 @@ extern "C" int br_ctx_ksw_pairs(br_ctx *c, int64_t n, const char *const *tseq, c
   uint64_t qmax = 0, tmaxv = 0;
   for (int64_t p = 0; p < n; p++) {
     size_t ql = strlen(qseq[p]), tl = strlen(tseq[p]);
-    probs[(size_t)p] = HProb{(uint32_t)ql, (uint32_t)tl, 1u, 0u, (uint64_t)arena.size()};
+    probs[(size_t)p] = HProb{(uint32_t)ql, (uint32_t)tl, side ? (uint32_t)side[p] : 1u, 0u, (uint64_t)arena.size()};
     for (size_t k = 0; k < ql; k++) arena.push_back(code(qseq[p][k]));
     for (size_t k = 0; k < tl; k++) { uint8_t cd = code(tseq[p][k]); probs[(size_t)p].pad |= cd >> 2; arena.push_back(cd); }
     qmax = std::max<uint64_t>(qmax, ql); tmaxv = std::max<uint64_t>(tmaxv, tl);
@@ -519,6 +525,7 @@ extern "C" int br_ctx_ksw_pairs(br_ctx *c, int64_t n, const char *const *tseq, c
   int rc = BR_OK;
   struct HRes { int32_t ok, score, refc; uint32_t n_ops; };
   std::vector<HRes> res((size_t)n);
+  std::vector<uint32_t> ops(seg ? arena.size() + (size_t)n + 1 : 0);
   do {
     if ((rc = d_probs.ensure((size_t)n * sizeof(HProb))) || (rc = d_res.ensure((size_t)n * ksw_res_bytes())) ||
         (rc = d_arena.ensure(arena.size() + 1024)) || (rc = d_ops.ensure((arena.size() + (size_t)n + 1) * 4)) ||
@@ -535,8 +542,16 @@ extern "C" int br_ctx_ksw_pairs(br_ctx *c, int64_t n, const char *const *tseq, c
         hipMemcpyAsync(max, d_max.p, (size_t)n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(n_cigar, d_rawn.p, (size_t)n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(cigar, d_raw.p, (size_t)n * cigar_cap * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (seg && hipMemcpyAsync(ops.data(), d_ops.p, ops.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
         hipStreamSynchronize(st) != hipSuccess) { rc = BR_ERR_HIP; break; }
     for (int64_t p = 0; p < n; p++) ok[p] = res[(size_t)p].ok;
+    if (seg) for (int64_t p = 0; p < n; p++) {
+      const HRes &r = res[(size_t)p];
+      refc[p] = r.ok ? r.refc : 0; n_seg[p] = r.ok ? r.n_ops : 0;
+      // a problem's ops lie in the qlen + tlen + 1 words from clip_ops[seq_off + p] on
+      const uint32_t room = probs[(size_t)p].qlen + probs[(size_t)p].tlen + 1, take = std::min(std::min(n_seg[p], room), cigar_cap);
+      memcpy(seg + (size_t)p * cigar_cap, ops.data() + probs[(size_t)p].seq_off + (size_t)p, (size_t)take * 4);
+    }
   } while (0);
   return rc;
 }

@@ -7,9 +7,17 @@
 //                        the rescue results applied, 3 emits them.
 //   The DP itself (ksw_extz2, traceback, build_left/right_clip_segment) is ksw_kernels.hip.
 //
-// No reference test exercises this path and ksw2.h is not in the reference tree; the DP is pinned by an independent
-// full-matrix checker instead (tests/ksw2_gotoh.c, tests/golden/ksw2_cases.json; k_ksw is compared with both through
-// br_ctx_ksw_pairs in tests/test_ksw2_pinned.py).
+// No reference test exercises this path and ksw2.h is not in the reference tree.  What pins it instead:
+//   the DP        an independent full-matrix checker (tests/ksw2_gotoh.c, tests/golden/ksw2_cases.json; k_ksw / k_ksw_dp /
+//                 k_ksw_trace are compared with both through br_ctx_ksw_pairs in tests/test_ksw2_pinned.py), and behind it
+//                 clip_segment on left- and right-side problems against build_left / build_right_clip_segment restated in
+//                 tests/rescue_ref.py (the same test, br_ctx_ksw_pairs with sides and segments);
+//   the front end every decision below -- the 5-base rule, max >= 10, the gap / overhang gating, no neighbour exon, the cap at
+//                 the shared sequence's length, its source record, the target window over short exons and its trim, N and
+//                 lower case in the exon pool, both sides of one candidate, more rows than G and than 64, rcpos -- one
+//                 hand-built read each (tests/rescue_cases.py), rows against tests/rescue_ref.py's frozen answers
+//                 (tests/golden/rescue_expect.json) and the oracle, br_ctx_rescue_stats against its problem / rescued counts,
+//                 on every route and through the BAM-record entry (tests/test_gpu_rescue_cases.py).
 
 __device__ __forceinline__ uint8_t base_code(uint8_t c) {
   switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2;

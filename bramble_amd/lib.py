@@ -289,7 +289,7 @@ def lib():
         L.br_ctx_ksw_diag.argtypes = [C.c_void_p, C.c_void_p]
         L.br_device_rows_detail.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.br_ctx_ksw_pairs.argtypes = [C.c_void_p, C.c_int64, _P(C.c_char_p), _P(C.c_char_p), C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_uint32]
+                                       C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.br_primary_pick.restype = C.c_uint32
         L.br_primary_pick.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32]
         L.br_version.restype = C.c_char_p
@@ -844,8 +844,10 @@ class Context:
               "br_bam_encode_device")
         return out
 
-    def ksw_pairs(self, pairs, cap=None):
-        """Diagnostic: k_ksw alone on [(target, query)] -> (ok int32[n], max int32[n], [cigar uint32[] per pair])."""
+    def ksw_pairs(self, pairs, cap=None, sides=None, segments=False):
+        """Diagnostic: k_ksw alone on [(target, query)] -> (ok int32[n], max int32[n], [cigar uint32[] per pair]).
+        sides: per pair 0 (left-side problem: both strings already reversed by the caller) or 1 (right; the default).
+        segments: also (refc int32[n], [clip-segment override ops uint32[] per pair]) at the end of the tuple."""
         n = len(pairs)
         cap = int(cap or max([len(t) + len(q) + 4 for t, q in pairs] + [8]))
         ts = (C.c_char_p * max(n, 1))(*[t.encode() for t, _ in pairs])
@@ -854,9 +856,19 @@ class Context:
         mx = np.zeros(max(n, 1), np.int32)
         nc = np.zeros(max(n, 1), np.uint32)
         cig = np.zeros(max(n, 1) * cap, np.uint32)
-        check(lib().br_ctx_ksw_pairs(self.h, n, ts, qs, ok.ctypes.data, mx.ctypes.data, nc.ctypes.data, cig.ctypes.data, cap),
-              "br_ctx_ksw_pairs")
-        return ok[:n], mx[:n], [cig[p * cap:p * cap + int(nc[p])].copy() for p in range(n)]
+        sd = None if sides is None else np.ascontiguousarray(np.asarray(sides, dtype=np.uint8))
+        assert sd is None or sd.shape == (n,)
+        refc = np.zeros(max(n, 1), np.int32) if segments else None
+        ns = np.zeros(max(n, 1), np.uint32) if segments else None
+        seg = np.zeros(max(n, 1) * cap, np.uint32) if segments else None
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data   # noqa: E731
+        check(lib().br_ctx_ksw_pairs(self.h, n, ts, qs, ok.ctypes.data, mx.ctypes.data, nc.ctypes.data, cig.ctypes.data, cap,
+                                     ptr(sd), ptr(refc), ptr(ns), ptr(seg)), "br_ctx_ksw_pairs")
+        out = (ok[:n], mx[:n], [cig[p * cap:p * cap + int(nc[p])].copy() for p in range(n)])
+        if segments:
+            assert int(ns[:n].max(initial=0)) <= cap
+            out += (refc[:n], [seg[p * cap:p * cap + int(ns[p])].copy() for p in range(n)])
+        return out
 
     def rescue_stats(self):
         out = (C.c_uint64 * 4)()

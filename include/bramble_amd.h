@@ -1654,9 +1654,16 @@ int br_ctx_ksw_diag(br_ctx *, uint64_t out[16]);
 /* Diagnostic: the -S rescue DP alone (k_ksw = ksw_extz2_sse as src/evaluate.cpp:296-313 calls it, on the device).
  * n (target, query) ASCII pairs in; per pair: ok[p] = the rescue would be accepted (max >= 10 and the walk reached the
  * last cell, src/evaluate.cpp:484,643), max[p], and -- when ok -- the traceback CIGAR in forward order (BAM-packed
- * M / I / D) at cigar[p * cigar_cap ...], n_cigar[p] ops. */
+ * M / I / D) at cigar[p * cigar_cap ...], n_cigar[p] ops.
+ * side (may be null: every pair a right-side problem): side[p] = 0 makes pair p a left-side problem, 1 a right-side one.
+ * The DP is the same; the side decides how the traceback becomes a clip segment.  For side 0 the caller passes both
+ * strings already reversed, as align_reversed does (src/evaluate.cpp:368-395).
+ * refc, n_seg, seg (all three or none): the clip segment of every accepted pair (build_left/right_clip_segment,
+ * src/evaluate.cpp:397-448,548-598) as the rescue's emit pass reads it: refc[p] = reference bases consumed, n_seg[p]
+ * override ops (len << 4 | 10 match, 11 deletion, 12 insertion, 13 clip; a leftover clip included) at seg[p * cigar_cap ...]; 0 for a pair not accepted. */
 int br_ctx_ksw_pairs(br_ctx *, int64_t n, const char *const *tseq, const char *const *qseq, int32_t *ok, int32_t *max,
-                     uint32_t *n_cigar, uint32_t *cigar, uint32_t cigar_cap);
+                     uint32_t *n_cigar, uint32_t *cigar, uint32_t cigar_cap, const uint8_t *side, int32_t *refc,
+                     uint32_t *n_seg, uint32_t *seg);
 
 /* The reference's primary tie-break (src/core.cpp:214-218,298-299):
  * uniform_int_distribution<uint32_t>(0, n_tied-1)(mt19937_64(std::hash<std::string>(name))),

@@ -108,6 +108,33 @@ def test_k_ksw_reproduces_the_golden_vectors_and_the_checker_on_random_pairs():
             assert ksw2_check.cigar_text(cigs[p]) == w["cigar"], (pairs[p], ksw2_check.cigar_text(cigs[p]), w)
             n_ok += 1
     assert n_ok > 5000
+    # clip_segment (ksw_kernels.hip) behind the DP: the same pairs, every other one as a left-side problem (its strings taken as
+    # already reversed), against build_left / build_right_clip_segment restated in tests/rescue_ref.py on the checker's CIGAR:
+    # score, refc, the override ops and the leftover clip of every accepted pair
+    from bramble_amd.batch import parse_cigar
+    from tests import rescue_ref as rr
+    sides = np.arange(len(pairs)) & 1
+    ok2, mx2, cigs2, refc, segs = ctx.ksw_pairs(pairs, sides=sides, segments=True)
+    assert np.array_equal(ok2, ok) and np.array_equal(mx2, mx)
+    n_seg = {0: 0, 1: 0}
+    n_rest = {0: 0, 1: 0}
+    for p, w in enumerate(want):
+        if not ok[p]:
+            assert int(refc[p]) == 0 and len(segs[p]) == 0
+            continue
+        assert ksw2_check.cigar_text(cigs2[p]) == w["cigar"], (pairs[p],)
+        side = "right" if sides[p] else "left"
+        want_refc, want_ops = rr.clip_segment(side, parse_cigar(w["cigar"]), len(pairs[p][1]))
+        got_ops = [(int(x) >> 4, int(x) & 15) for x in segs[p]]
+        assert int(refc[p]) == want_refc and got_ops == want_ops, (side, pairs[p], w["cigar"], int(refc[p]), want_refc, got_ops, want_ops)
+        # the leftover clip: the query bases the walk did not reach, at the outer end
+        rest = len(pairs[p][1]) - sum(int(x) >> 4 for x in cigs2[p] if (int(x) & 15) in (0, 1))
+        outer = got_ops[0] if side == "left" else got_ops[-1]
+        assert rest == 0 or (outer[1] == rr.CLIP_OVR and outer[0] >= rest), (side, pairs[p], got_ops, rest)
+        assert sum(n for n, op in got_ops if op != rr.DEL_OVR) == len(pairs[p][1])      # the segment spells the whole query
+        n_seg[int(sides[p])] += 1
+        n_rest[int(sides[p])] += rest > 0
+    assert min(n_seg.values()) > 2500 and min(n_rest.values()) > 100, (n_seg, n_rest)
     ctx.close()
     idx.close()
 
